@@ -11,17 +11,19 @@ pairs bidirectionalised, D=100 fp32), fanout [25,10], B=1024, GraphSAGE 100->256
 §8(d) C2).  MAG240M (the config the metric is quoted on) does not fit one GPU (375 GB of features),
 so per the contract the N=1 line is the largest single-GPU configuration.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--group G] [--workload W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--streams S] [--group G] [--workload W]
 
 Steps are independent batches.  One library call takes G consecutive batches through ONE set of ~20 launches
 (gigl_sage_plan_set_groups: every batch keeps its own union graph, rows are bit-identical to G single-batch
 calls — tests/test_gpu_groups.py); calls are pipelined over S HIP streams (one library ctx + one host thread per
 stream, all sharing the HBM-resident graph and hash table; defaults S = 3, G = 64 — a sweep of S in 2..6, G in
-16..128 stays within 7 % of the best).  The regime does not depend on --steps.  A --steps that is a whole number of rounds
-(S*G = 192 steps by default: 192, 384, 960, ...) is honoured exactly: one timed repetition = K steps, `steps` = K,
-`steps_honoured`: true; any other value is rounded up to whole rounds (>= --min-rounds) and the line carries the rounded
-`steps` with `steps_honoured`: false (likewise --warmup / `warmup_honoured`).  The repetition is repeated until the timed
-region lasts >= --min-seconds; median / p10 / p90 over the repetitions are reported next to the aggregate.
+16..128 stays within 7 % of the best).  The regime does not depend on --steps.  A plain run sets up, warms up, times
+exactly K steps once (K // G whole calls, then one call of the K % G remaining batches), counts their edges on the device
+and prints the line.  --dump-outputs DIR writes the last timed step's embedding rows as DIR/embeddings.npy (float32; the
+timed batches come first in the seeded root pool, so they do not depend on --warmup, --streams or --group).
+--full adds everything else: the timed range is then whole rounds (S*G = 192 steps by default; any other --steps is
+rounded up, >= --min-rounds, `steps_honoured`: false), repeated until it lasts >= --min-seconds with median / p10 / p90
+over the repetitions, plus the per-kernel roofline probes, live PMC passes, CPU baselines and the emulated sharded sub-record.
 N>1: one process per GPU (torch.distributed, RCCL); every rank holds a replica of the graph and takes
 its own root batches — the path shards by roots with no data-path collective ("weak" scaling);
 time = max over ranks, value = total edges of all ranks / that time.

@@ -26,13 +26,20 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=960,
-                    help="MINIMUM number of timed steps; the timed range is rounded up to whole rounds and repeated "
-                         "until --min-seconds (the regime — streams x batches per call — does not depend on it)")
+                    help="timed steps (the regime — streams x batches per call — does not depend on it); --full: the "
+                         "MINIMUM number, the timed range rounded up to whole rounds and repeated until --min-seconds")
     ap.add_argument("--warmup", type=int, default=64)
-    ap.add_argument("--min-seconds", type=float, default=2.5, help="lower bound of the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeated timed ranges with their spread, per-kernel roofline "
+                         "probes, live PMC passes, CPU baselines, the emulated sharded sub-record (off: setup, warm-up, "
+                         "exactly --steps timed steps, the result line)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(the products-family workloads: embeddings.npy, the last timed batch's rows)")
+    ap.add_argument("--min-seconds", type=float, default=2.5, help="lower bound of the timed region (products family: --full only)")
     ap.add_argument("--min-rounds", type=int, default=10,
-                    help="rounds (streams x batches-per-call steps) per timed repetition, at least")
-    ap.add_argument("--min-reps", type=int, default=7, help="timed repetitions, at least (median / p10 / p90)")
+                    help="rounds (streams x batches-per-call steps) per timed repetition, at least (products family: --full only)")
+    ap.add_argument("--min-reps", type=int, default=7, help="timed repetitions, at least (median / p10 / p90; products family: --full only)")
     ap.add_argument("--batch", type=int, default=0, help="roots per batch (0: the workload's: 1024)")
     ap.add_argument("--fanouts", type=str, default="", help="per-hop fanouts (empty: the workload's: 25,10)")
     ap.add_argument("--streams", type=int, default=3)
@@ -62,7 +69,7 @@ def main():
                          "(in-process transport): per-rank pulled rows / bytes / bucket fill / hub-row hit rate / compute "
                          "time are measured, the W-GPU step is projected from them (labelled so)")
     ap.add_argument("--no-emulated-sub", action="store_true",
-                    help="N=1 headline: skip the `sharded_emulated` sub-record (an 8-rank emulated world at a reduced scale, "
+                    help="N=1 headline under --full: skip the `sharded_emulated` sub-record (an 8-rank emulated world at a reduced scale, "
                          "run in a child process)")
     ap.add_argument("--no-sharded-sub", action="store_true",
                     help="N > 1 headline: skip the `sharded` sub-record (the mag240m-sharded workload at this N)")
@@ -88,13 +95,13 @@ def main():
                     help="mag240m-sharded: owners apply the first layer's weights before sending (256 fp32 per row "
                          "instead of 768 fp16)")
     ap.add_argument("--small", action="store_true", help="200k-node graph (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (products family: --full only)")
     ap.add_argument("--timed-only", action="store_true",
                     help="counter-collection runs (scripts/gpu_pmc.sh): only warm-up + the timed region, so every "
                          "library launch in the trace is a grouped launch; prints timing without edge counts")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="N=1 headline: skip the rocprofv3 counter passes that measure this run's HBM traffic per kernel "
+                    help="N=1 headline under --full: skip the rocprofv3 counter passes that measure this run's HBM traffic per kernel "
                          "(roofline.traffic then comes from the newest committed profiles/*_pmc*.json of the workload, or is "
                          "null); the passes run as child processes after the timed region, ~1.5 min")
     ap.add_argument("--mode", type=str, default="parity", choices=["parity", "fast"])
@@ -143,6 +150,11 @@ def main():
         wl = WORKLOADS.get(args.workload)
         args.batch = sampler_call_size(1 << 30, [int(v) for v in args.fanouts.split(",")], int(wl[3]) if wl else 100)
     args.batch = args.batch or wl_b
+
+    products_family = not args.train and args.entry == "plan" and args.workload not in ("mag240m-sharded", "gat-lp", "typed-dblp")
+    if args.dump_outputs and not products_family:
+        print("bench.py: --dump-outputs is implemented for the products-family inference plan only", file=sys.stderr)
+        sys.exit(2)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:  # no launcher: this process becomes one
         sys.exit(self_launch(args))

@@ -69,7 +69,7 @@ def test_self_launch_two_ranks_on_one_gpu():
 def test_a_failing_sharded_sub_record_never_costs_the_headline():
     """the sub-record's collectives have not run on a real multi-GPU node yet: it runs in child processes, so if it
     crashes, fails or hangs, rank 0 still prints the (complete) headline line, with the failure noted"""
-    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--small", "--no-cpu-baseline", "--min-seconds", "0.3",
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--small", "--full", "--no-cpu-baseline", "--min-seconds", "0.3",
                         "--min-reps", "2", "--min-rounds", "2", "--group", "8", "--shard-group", "4", "--shard-scale",
                         "0.0005", "--steps", "16", "--warmup", "8"],
                        env=_env(GIGL_BENCH_SHARE_GPU="1", GIGL_BENCH_SUB_TIMEOUT="0.001"), capture_output=True, text=True,
@@ -101,3 +101,26 @@ def test_under_torchrun_the_sharded_headline_rendezvous_works():
     assert line["n_gpus"] == 2 and "sharded" not in line, line.get("sharded")
     assert "MAG240M-shaped" in line["config"]["workload"] and line["comm"]["ranks"] == 2
     assert line["headline_is"].startswith("mag240m-sharded") and line["replicas"]["value"] > 0
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_exactly_its_steps_and_dumps_the_last_one(tmp_path):
+    """without --full: exactly --steps timed steps (here 12 calls of 8 batches + a 4-batch tail call), no roofline / baseline
+    / sub-record, and --dump-outputs writes the last timed batch's rows — the same rows whatever the regime"""
+    import numpy as np
+    dumps = []
+    for k, extra in enumerate((["--group", "8"], ["--group", "64", "--streams", "1"])):
+        out = tmp_path / f"run{k}"
+        p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--small", "--steps", "100", "--warmup", "3",
+                            "--dump-outputs", str(out)] + extra, env=_env(), capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 100 and line["steps_honoured"] and line["timing"]["steps_total"] == 100
+        assert line["ms_per_step"] > 0 and line["value"] > 0 and line["full"] is False
+        assert line["roofline"] is None and line["cpu_baseline"] is None and "sharded_emulated" not in line
+        emb = np.load(out / "embeddings.npy")
+        assert emb.dtype == np.float32 and emb.shape == (1024, 47) and np.isfinite(emb).all()
+        dumps.append(emb)
+    np.testing.assert_allclose(dumps[0], dumps[1], rtol=1e-6, atol=1e-6)
