@@ -61,6 +61,7 @@ SYMBOLS = [
     "gigl_typed_plan_merged_csr", "gigl_sage_plan_half_split", "gigl_sage_plan_fused_layers", "gigl_sort_distinct_u64", "gigl_sort_distinct_u32",
     "gigl_typed_plan_merged_csr_ex", "gigl_hgt_aggregate_act", "gigl_dist_plan_set_aggr", "gigl_typed_plan_run_nodes", "gigl_typed_plan_run_edges", "gigl_typed_plan_clone", "gigl_hgt_infer_create", "gigl_hgt_infer_run",
     "gigl_hgt_infer_set_model", "gigl_hgt_infer_use_graph", "gigl_hgt_infer_destroy",
+    "gigl_expand_frontier_keyed", "gigl_typed_plan_set_op_keys",
     "gigl_sage_plan_run_part", "gigl_sage_plan_set_graph_stream", "gigl_sage_plan_overflow_add",
     "gigl_sage_train_plan_create", "gigl_sage_train_plan_step", "gigl_sage_train_plan_step2", "gigl_sage_train_plan_loss", "gigl_sage_train_plan_destroy",
     "gigl_nablp_train_plan_create", "gigl_nablp_train_plan_step", "gigl_nablp_train_plan_step2", "gigl_gat_nablp_train_plan_create", "gigl_gat_nablp_train_plan_grads", "gigl_nablp_train_plan_loss", "gigl_nablp_train_plan_destroy", "gigl_nablp_train_plan_grads",
@@ -172,6 +173,8 @@ class GiglTypedEdgeFeat(C.Structure):
 
 
 REC_ROOTED_NODE_NEIGHBORHOOD, REC_NODE_ANCHOR_LINK_PRED = 0, 1
+# SamplingOp methods (GIGL_SAMPLE_*): the hash rule, and the two keyed by an edge feature (gigl_expand_frontier_keyed)
+SAMPLE_RANDOM_UNIFORM, SAMPLE_TOPK, SAMPLE_RANDOM_WEIGHTED = 0, 1, 2
 STATS = {"sampled": 0, "aggregated": 1, "union_edges": 2, "union_nodes": 3, "expand_bytes": 4, "agg_layer0": 5,
          "rows_layer0": 9, "overflow": 13, "pulled_rows": 14, "pull_bucket_max": 15}
 COMM_RCCL, COMM_LOCAL, COMM_CALLBACK = 0, 1, 2
@@ -263,6 +266,8 @@ def load() -> C.CDLL:
         "gigl_typed_plan_run_nodes": [vp, vp, i32],
         "gigl_typed_plan_run_edges": [vp, i32],
         "gigl_typed_plan_clone": [vp, vp, P(vp)],
+        "gigl_typed_plan_set_op_keys": [vp, i32, i32, vp],
+        "gigl_expand_frontier_keyed": [vp, vp, vp, i32, vp, vp, i64, i32, i32, vp, vp],
         "gigl_hgt_infer_create": [vp, vp, i32, P(GiglHgtModel), P(i32), P(i32), P(vp)],
         "gigl_hgt_infer_run": [vp, vp, i32, vp, i32, vp],
         "gigl_hgt_infer_set_model": [vp, P(GiglHgtModel)],

@@ -12,7 +12,8 @@
 // What gigl_amd/graphdb_sampler.py::batch_graph did with one library call per op and a chain of torch.unique /
 // searchsorted calls (each a host synchronisation: their output sizes are data) is one stream of device work here:
 //   per op      frontier = parents' results side by side (dag_frontier_kernel) -> gigl_rows_dedup -> ran / mask / path
-//               sums (dag_mask_kernel) -> gigl_expand_frontier on the op's (edge type, direction) graph
+//               sums (dag_mask_kernel) -> gigl_expand_frontier on the op's (edge type, direction) graph (a keyed
+//               TopK / RandomWeighted op: gigl_expand_frontier_keyed, csrc/keyed.hip)
 //   per type    every id the ops produced for the type -> radix sort -> distinct, ascending = the type's local
 //               numbering (the numbering of batch_graph: torch.unique)
 //   per edge    endpoints -> local ids by binary search -> (src << 32 | dst) keys -> radix sort -> distinct
@@ -31,6 +32,8 @@ struct gigl_typed_plan {
   std::vector<gigl_dag_op> ops;
   std::vector<int32_t> width;          // frontier slots per root of every op
   std::vector<int64_t> window_end;     // per op: largest hash-window end any of its rows can reach (-1: unbounded)
+  std::vector<int32_t> key_method;     // per op: GIGL_SAMPLE_* (gigl_typed_plan_set_op_keys; RANDOM_UNIFORM = hash rule)
+  std::vector<const float*> key_col;   // per op: the keyed method's weights, one per edge of the op's graph
   // device, per op: frontier [b][w], path sums [b][w], neighbours [b][w][f], counts [b][w], ran [b]
   std::vector<uint32_t*> front, ksum, nbr;
   std::vector<int32_t*> cnt;
@@ -333,6 +336,8 @@ int32_t gigl_typed_plan_create(gigl_ctx* ctx, const gigl_dag_op* ops, int32_t n_
   p->b_max = b_max;
   p->ops.assign(ops, ops + n_ops);
   p->width.assign(n_ops, 0);
+  p->key_method.assign(n_ops, GIGL_SAMPLE_RANDOM_UNIFORM);
+  p->key_col.assign(n_ops, nullptr);
   p->cand_per_root.assign(n_node_types, 0);
   p->pairs_per_root.assign(n_edge_slots, 0);
   p->slot_src_type.assign(n_edge_slots, -1);
@@ -465,7 +470,33 @@ int32_t gigl_typed_plan_create(gigl_ctx* ctx, const gigl_dag_op* ops, int32_t n_
 
 int32_t gigl_typed_plan_clone(gigl_typed_plan* src, gigl_ctx* ctx, gigl_typed_plan** out) {
   if (!src || !ctx || !out) return GIGL_E_INVALID_ARG;
-  return gigl_typed_plan_create(ctx, src->ops.data(), src->n_ops, src->n_types, src->root_type, src->n_slots, src->b_max, out);
+  const int32_t rc =
+      gigl_typed_plan_create(ctx, src->ops.data(), src->n_ops, src->n_types, src->root_type, src->n_slots, src->b_max, out);
+  if (rc != GIGL_OK) return rc;
+  (*out)->key_method = src->key_method;
+  (*out)->key_col = src->key_col;
+  (*out)->window_end = src->window_end;
+  return GIGL_OK;
+}
+
+int32_t gigl_typed_plan_set_op_keys(gigl_typed_plan* p, int32_t op, int32_t method, const float* key_col) {
+  if (!p || !p->ctx) return GIGL_E_INVALID_ARG;
+  gigl_ctx* ctx = p->ctx;
+  GIGL_REQUIRE(ctx, op >= 0 && op < p->n_ops, "op %d outside [0,%d)", op, p->n_ops);
+  GIGL_REQUIRE(ctx, method == GIGL_SAMPLE_RANDOM_UNIFORM || method == GIGL_SAMPLE_TOPK || method == GIGL_SAMPLE_RANDOM_WEIGHTED,
+               "bad sampling method %d", method);
+  if (method == GIGL_SAMPLE_RANDOM_UNIFORM) {
+    p->key_method[op] = method;
+    p->key_col[op] = nullptr;
+    return GIGL_OK;
+  }
+  GIGL_REQUIRE(ctx, key_col || p->ops[op].graph->e == 0, "op %d: null key column", op);
+  if (p->ops[op].graph->multi)
+    return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "op %d: keyed sampling needs rows without repeated ids", op);
+  p->key_method[op] = method;
+  p->key_col[op] = key_col;
+  p->window_end[op] = -1;  // (a keyed op reads no hash window)
+  return GIGL_OK;
 }
 
 int32_t gigl_typed_plan_run(gigl_typed_plan* p, const uint32_t* roots, int32_t b) {
@@ -500,8 +531,12 @@ int32_t gigl_typed_plan_run_nodes(gigl_typed_plan* p, const uint32_t* roots, int
     }
     hipLaunchKernelGGL(dag_mask_kernel, dim3((unsigned)((b + TB / 64 - 1) / (TB / 64))), dim3(TB), 0, st, rs, roots,
                        (int64_t)b, w, p->front[o], p->ksum[o], p->ran[o]);
-    const int32_t rc = gigl_expand_frontier(ctx, op.graph, p->front[o], p->ksum[o], (int64_t)b * w, op.fanout, op.hash_add, 1,
-                                            p->window_end[o], p->nbr[o], p->cnt[o]);
+    const int32_t rc =
+        p->key_method[o] != GIGL_SAMPLE_RANDOM_UNIFORM
+            ? gigl_expand_frontier_keyed(ctx, op.graph, p->key_col[o], p->key_method[o], p->front[o], p->ksum[o],
+                                         (int64_t)b * w, op.fanout, op.hash_add, p->nbr[o], p->cnt[o])
+            : gigl_expand_frontier(ctx, op.graph, p->front[o], p->ksum[o], (int64_t)b * w, op.fanout, op.hash_add, 1,
+                                   p->window_end[o], p->nbr[o], p->cnt[o]);
     if (rc != GIGL_OK) return rc;
   }
   // ---- per node type: the distinct ids, ascending

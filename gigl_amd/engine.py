@@ -405,6 +405,24 @@ class HipEngine:
                                              C.c_void_p(nbr.data_ptr()), C.c_void_p(cnt.data_ptr())), self._ctx)
         return nbr[: m * f], cnt[:m]
 
+    def expand_frontier_keyed(self, nodes: torch.Tensor, ksums: torch.Tensor, f: int, hash_add: int, method: int,
+                              key_col: torch.Tensor, label_edges: str):
+        """one hop of a TopK / RandomWeighted op (gigl_expand_frontier_keyed) over an explicit frontier on a named edge
+        list loaded with load_label_edges; key_col: fp32 device tensor, one weight per edge in that graph's `col` order.
+        Same layout as expand_frontier -> (nbr [m*f] int32, cnt [m] int32)"""
+        graph = self._label_edges[label_edges]["graph"]
+        assert key_col.dtype == torch.float32 and key_col.is_contiguous() and key_col.device == self.device
+        assert int(key_col.numel()) == int(self._label_edges[label_edges]["n_edges"])
+        m = int(nodes.numel())
+        nbr = torch.empty(max(m * f, 1), dtype=torch.int32, device=self.device)
+        cnt = torch.empty(max(m, 1), dtype=torch.int32, device=self.device)
+        hash_add = ((int(hash_add) + 2**31) % 2**32) - 2**31
+        check(self._lib.gigl_expand_frontier_keyed(self._ctx, graph, C.c_void_p(key_col.data_ptr()), int(method),
+                                                   C.c_void_p(nodes.data_ptr()), C.c_void_p(ksums.data_ptr()), m, f,
+                                                   hash_add, C.c_void_p(nbr.data_ptr()), C.c_void_p(cnt.data_ptr())),
+              self._ctx)
+        return nbr[: m * f], cnt[:m]
+
     def frontier_bucket(self, nodes: torch.Tensor, ksums: Optional[torch.Tensor], world: int, cap: int,
                         req: torch.Tensor, slot_idx: torch.Tensor, counts: torch.Tensor) -> None:
         """bucket frontier slots by owner (gigl_frontier_bucket): req int32 [world, 2, cap], slot_idx int32

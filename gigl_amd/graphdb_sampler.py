@@ -35,6 +35,12 @@ from . import wire
 
 INCOMING, OUTGOING = "INCOMING", "OUTGOING"
 INVALID = 0xFFFFFFFF
+# SamplingOp.sampling_method: the oneof of the reference's SamplingOp (subgraph_sampling_strategy.proto:7-58) that this
+# sampler runs — the hash rule, and the two methods keyed by a named edge feature (gigl_expand_frontier_keyed: TopK =
+# ORDER BY e.<edgeFeatName> DESC, RandomWeighted = ORDER BY e.<edgeFeatName> * rand() DESC, NebulaQueryResponseTranslator
+# .scala:39-104)
+RANDOM_UNIFORM, RANDOM_WEIGHTED, TOP_K = "random_uniform", "random_weighted", "top_k"
+SAMPLING_METHODS = (RANDOM_UNIFORM, RANDOM_WEIGHTED, TOP_K)
 
 
 @dataclass(frozen=True)
@@ -51,6 +57,12 @@ class SamplingOp:
     num_nodes_to_sample: int
     input_op_names: Sequence[str] = ()
     sampling_direction: str = INCOMING  # proto default
+    sampling_method: str = RANDOM_UNIFORM  # one of SAMPLING_METHODS
+    edge_feat_name: Optional[str] = None  # random_weighted / top_k: the edge feature the neighbours are ranked by
+
+    @property
+    def keyed(self) -> bool:
+        return self.sampling_method != RANDOM_UNIFORM
 
 
 @dataclass
@@ -112,12 +124,16 @@ def _result_type(op: SamplingOp) -> str:
 
 
 def validate_sampling_op_dags(root_type_to_ops: Dict[str, Sequence[SamplingOp]], node_types: Sequence[str],
-                              edge_types: Sequence[EdgeType], expected_root_node_types: Sequence[str] = ()) -> None:
+                              edge_types: Sequence[EdgeType], expected_root_node_types: Sequence[str] = (),
+                              edge_feature_keys: Optional[Dict[EdgeType, Dict[str, int]]] = None) -> None:
     """the checks of SubgraphSamplingStrategyPbWrapper / SamplingOpPbWrapper (python/gigl/src/common/types/pb_wrappers/
     subgraph_sampling_strategy.py:26-260, sampling_op.py): unique op names, known input ops, no cycles, root node types
     known to the graph (and to the task, when given), a root op per non-empty DAG, edge types of the graph, and edge
     alignment — a root op starts from the DAG's root node type, a child op starts from the node type its parent returns.
-    On typed graphs a misaligned edge would index one type's id space with another type's ids."""
+    On typed graphs a misaligned edge would index one type's id space with another type's ids.
+    Per op (sampling_op.py:46-84): num_nodes_to_sample > 0, a method this sampler runs, and for the keyed methods a
+    non-empty edge_feat_name; with `edge_feature_keys` ({edge type: {feature key: width}}) that name must be a feature
+    key of the op's edge type, one column wide."""
     known_et = {(e.src_node_type, e.relation, e.dst_node_type) for e in edge_types}
     for root_type, ops in root_type_to_ops.items():
         if root_type not in node_types:
@@ -135,6 +151,7 @@ def validate_sampling_op_dags(root_type_to_ops: Dict[str, Sequence[SamplingOp]],
             et = op.edge_type
             if (et.src_node_type, et.relation, et.dst_node_type) not in known_et:
                 raise SubgraphSamplingValidationError("SAMPLING_OP_EDGE_TYPE_NOT_IN_GRAPH_METADATA", f"{et} of op {op.op_name!r}")
+            _validate_sampling_method(op, edge_feature_keys)
             if not op.input_op_names and _frontier_type(op) != root_type:
                 raise SubgraphSamplingValidationError(
                     "CONTAINS_INVALID_EDGE_IN_DAG", f"root op {op.op_name!r} ({op.sampling_direction}) starts from "
@@ -162,6 +179,31 @@ def validate_sampling_op_dags(root_type_to_ops: Dict[str, Sequence[SamplingOp]],
     for t in expected_root_node_types:
         if t not in root_type_to_ops:
             raise SubgraphSamplingValidationError("MISSING_EXPECTED_ROOT_NODE_TYPE", f"no DAG for node type {t!r}")
+
+
+def _validate_sampling_method(op: SamplingOp, edge_feature_keys: Optional[Dict[EdgeType, Dict[str, int]]]) -> None:
+    if op.sampling_method not in SAMPLING_METHODS:
+        raise SubgraphSamplingValidationError(
+            "UNSUPPORTED_SAMPLING_METHOD", f"op {op.op_name!r}: {op.sampling_method!r} (supported: {SAMPLING_METHODS})")
+    if int(op.num_nodes_to_sample) <= 0:
+        raise SubgraphSamplingValidationError(
+            "INVALID_NUM_NODES_TO_SAMPLE", f"op {op.op_name!r}: num_nodes_to_sample {op.num_nodes_to_sample} must be > 0")
+    if not op.keyed:
+        return
+    if not op.edge_feat_name:
+        raise SubgraphSamplingValidationError("EMPTY_EDGE_FEAT_NAME", f"op {op.op_name!r} ({op.sampling_method}) names no "
+                                              "edge feature")
+    if edge_feature_keys is None:
+        return
+    keys = edge_feature_keys.get(op.edge_type) or {}
+    if op.edge_feat_name not in keys:
+        raise SubgraphSamplingValidationError(
+            "EDGE_FEAT_NAME_NOT_IN_EDGE_FEATURES", f"op {op.op_name!r}: {op.edge_feat_name!r} is not a feature key of "
+            f"{op.edge_type} (keys: {sorted(keys)})")
+    if int(keys[op.edge_feat_name]) != 1:
+        raise SubgraphSamplingValidationError(
+            "EDGE_FEAT_NOT_SCALAR", f"op {op.op_name!r}: edge feature {op.edge_feat_name!r} of {op.edge_type} is "
+            f"{keys[op.edge_feat_name]} columns wide; a keyed op ranks by one")
 
 
 @dataclass
@@ -193,9 +235,15 @@ class HipGraphDBSampler:
     def __init__(self, node_types: Dict[str, int], num_nodes: Dict[str, int],
                  edges: Dict[EdgeType, Tuple[np.ndarray, np.ndarray]], condensed_edge_types: Dict[EdgeType, int],
                  features: Optional[Dict[str, np.ndarray]] = None, device: int = 0, sampling_seed: int = 42,
-                 edge_features: Optional[Dict[EdgeType, np.ndarray]] = None):
+                 edge_features: Optional[Dict[EdgeType, np.ndarray]] = None,
+                 edge_key_columns: Optional[Dict[EdgeType, Dict[str, np.ndarray]]] = None):
+        """edge_key_columns {edge type: {feature name: fp32 [n_edges]}}: the named scalar edge features the keyed ops
+        (top_k / random_weighted) rank by, row i belonging to edge i of edges[et]"""
         from .engine import HipEngine
         self.node_types, self.num_nodes, self.condensed_edge_types = node_types, num_nodes, condensed_edge_types
+        self._edges = edges
+        self._edge_key_columns = {et: dict(cols) for et, cols in (edge_key_columns or {}).items()}
+        self._key_cols: Dict[Tuple[EdgeType, str, str], torch.Tensor] = {}  # (et, direction, name) -> device, col order
         self.features = features or {}
         self.sampling_seed = sampling_seed
         self.engine = HipEngine(device)
@@ -220,6 +268,53 @@ class HipGraphDBSampler:
     @staticmethod
     def _key(et: EdgeType, direction: str) -> str:
         return f"{et.src_node_type}|{et.relation}|{et.dst_node_type}|{direction}"
+
+    def key_column(self, et: EdgeType, direction: str, name: str) -> torch.Tensor:
+        """the weights of edge feature `name` of `et` in the `col` order of the (et, direction) graph, fp32 on the
+        device, built on first use: every input edge row finds its position in that graph (gigl_edge_ids, as
+        load_label_edges lays out edge features); several rows for one (src, dst): the first wins"""
+        import ctypes as C
+        from . import _lib
+        k = (et, direction, name)
+        if k in self._key_cols:
+            return self._key_cols[k]
+        cols = self._edge_key_columns.get(et) or {}
+        if name not in cols:
+            raise KeyError(f"no edge feature column {name!r} for {et} (the sampler has {sorted(cols)})")
+        eng = self.engine
+        dev = eng.device
+        entry = eng._label_edges[self._key(et, direction)]
+        src, dst = (np.asarray(a).astype(np.uint32) for a in self._edges[et])
+        w = np.ascontiguousarray(np.asarray(cols[name], dtype=np.float32).reshape(-1))
+        if w.shape[0] != src.shape[0]:
+            raise ValueError(f"edge feature column {name!r} of {et}: {w.shape[0]} rows for {src.shape[0]} edges")
+        rows_ids, col_ids = (dst, src) if direction == INCOMING else (src, dst)  # rows = the node a query starts from
+        n_e, n_rows = int(entry["n_edges"]), int(src.shape[0])
+        with torch.cuda.stream(eng._stream):
+            out = torch.zeros(max(n_e, 1), dtype=torch.float32, device=dev)
+            if n_rows:
+                rt = torch.from_numpy(rows_ids.view(np.int32)).to(dev)
+                ct = torch.from_numpy(col_ids.view(np.int32)).to(dev)
+                eid = torch.empty(n_rows, dtype=torch.int64, device=dev)
+                _lib.check(eng._lib.gigl_edge_ids(eng._ctx, entry["graph"], C.c_void_p(ct.data_ptr()),
+                                                  C.c_void_p(rt.data_ptr()), n_rows, C.c_void_p(eid.data_ptr())), eng._ctx)
+                win = torch.full((max(n_e, 1),), n_rows, dtype=torch.int64, device=dev)
+                win.scatter_reduce_(0, eid, torch.arange(n_rows, device=dev), reduce="amin")
+                wt = torch.from_numpy(w).to(dev)
+                out = wt[win.clamp(max=n_rows - 1)].contiguous()
+            out = out[:n_e].contiguous()
+        self._key_cols[k] = out
+        return out
+
+    def _expand_op(self, op: SamplingOp, front: torch.Tensor, ksum: torch.Tensor, f: int, hash_add: int):
+        """one op over its frontier slots: the hash rule, or the keyed rule of a top_k / random_weighted op"""
+        from ._lib import SAMPLE_RANDOM_WEIGHTED, SAMPLE_TOPK
+        label = self._key(op.edge_type, op.sampling_direction)
+        if not op.keyed:
+            return self.engine.expand_frontier(front, ksum, f, hash_add, 1, label_edges=label)
+        method = SAMPLE_TOPK if op.sampling_method == TOP_K else SAMPLE_RANDOM_WEIGHTED
+        col = self.key_column(op.edge_type, op.sampling_direction, op.edge_feat_name)
+        return self.engine.expand_frontier_keyed(front, ksum, f, hash_add, method, col, label)
 
     def close(self):
         for pl in getattr(self, "_plans", {}).values():  # one-call typed plans hold device buffers of their own
@@ -255,8 +350,7 @@ class HipGraphDBSampler:
             w, f = int(front.shape[1]), int(op.num_nodes_to_sample)
             ksum = (front + roots.view(b, 1)).contiguous()  # int32 add wraps like the sampler's K sums
             counter = 1 + dag.op_order.index(name)
-            nbr, cnt = eng.expand_frontier(front.view(-1), ksum.view(-1), f, self.sampling_seed * counter, 1,
-                                           label_edges=self._key(op.edge_type, op.sampling_direction))
+            nbr, cnt = self._expand_op(op, front.view(-1), ksum.view(-1), f, self.sampling_seed * counter)
             res[name] = OpResult(front, nbr.view(b, w, f), cnt.view(b, w))
         return res
 
@@ -416,6 +510,15 @@ class HipGraphDBSampler:
         plan = C.c_void_p()
         _lib.check(eng._lib.gigl_typed_plan_create(eng._ctx, ops, len(order), len(types), tix[root_node_type], len(slots),
                                                    int(b_max), C.byref(plan)), eng._ctx)
+        for i, name in enumerate(order):  # keyed ops: their weight columns (built once, held by the sampler)
+            op = dag.nodes[name].sampling_op
+            if op.keyed:
+                col = self.key_column(op.edge_type, op.sampling_direction, op.edge_feat_name)
+                method = _lib.SAMPLE_TOPK if op.sampling_method == TOP_K else _lib.SAMPLE_RANDOM_WEIGHTED
+                rc = eng._lib.gigl_typed_plan_set_op_keys(plan, i, method, C.c_void_p(col.data_ptr()))
+                if rc != 0:
+                    eng._lib.gigl_typed_plan_destroy(plan)
+                    _lib.check(rc, eng._ctx)
         out = _lib.GiglTypedPlanOut()
         _lib.check(eng._lib.gigl_typed_plan_buffers(plan, C.byref(out)), eng._ctx)
         entry = {"plan": plan, "out": out, "types": types, "slots": slots, "order": order, "b_max": int(b_max),

@@ -323,7 +323,7 @@ def _typed_run_hbm(self, cfg: GbmlConfigPbWrapper, inferencer, dev, rank: int = 
     homogeneous route's file sharding (data_loaders/utils.py:23-56)."""
     from .graphdb_sampler import HipGraphDBSampler
     from .hbm import planned_root_order
-    from .subgraph_sampler import load_preprocessed_typed_graph, sampling_op_dags
+    from .subgraph_sampler import edge_key_columns, load_preprocessed_typed_graph, sampling_op_dags
     info = (_get(cfg.doc, "sharedConfig.inferenceMetadata.nodeTypeToInferencerOutputInfoMap", {}) or {})
     wanted = [t for t, v in info.items() if v.get("embeddingsPath")]
     node_types, num, ids, feats, edges, cet, efeats = load_preprocessed_typed_graph(cfg)
@@ -338,7 +338,7 @@ def _typed_run_hbm(self, cfg: GbmlConfigPbWrapper, inferencer, dev, rank: int = 
     # edge_attr_dict, joined on the device; HGT ignores them)
     has_ef = (not is_hgt) and any(np.asarray(v).size for v in (efeats or {}).values())
     s = HipGraphDBSampler(node_types, num, edges, cet, feats, device=dev.index or 0, sampling_seed=seed,
-                          edge_features=efeats if has_ef else None)
+                          edge_features=efeats if has_ef else None, edge_key_columns=edge_key_columns(cfg, dags, efeats))
     out_files: Dict[str, str] = {}
     n_rows = 0
     b = int(cfg.inference_batch_size)

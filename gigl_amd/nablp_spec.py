@@ -679,13 +679,13 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         if any((cfg.dataset_split_uri(sp) and tfrecord_files(cfg.dataset_split_uri(sp))) for sp in ("train", "val", "test")):
             return None
         from .graphdb_sampler import EdgeType, HipGraphDBSampler
-        from .subgraph_sampler import load_preprocessed_typed_graph, sampling_op_dags
+        from .subgraph_sampler import edge_key_columns, load_preprocessed_typed_graph, sampling_op_dags
         pos_et = EdgeType(*cfg.supervision_edge_types[0])
         node_types, num, ids, feats, edges, cet, efeats = load_preprocessed_typed_graph(cfg)
         seed = 42 if cfg.permutation_strategy == "deterministic" else 1 + int.from_bytes(os.urandom(3), "little") % ((1 << 20) - 1)
-        smp = HipGraphDBSampler(node_types, num, edges, cet, feats, device=device.index or 0, sampling_seed=seed,
-                                edge_features=efeats)
         dags = sampling_op_dags(cfg, list(dict.fromkeys([pos_et.src_node_type, pos_et.dst_node_type])))
+        smp = HipGraphDBSampler(node_types, num, edges, cet, feats, device=device.index or 0, sampling_seed=seed,
+                                edge_features=efeats, edge_key_columns=edge_key_columns(cfg, dags, efeats))
         # the sampler job's main samples (SubgraphSampler._run_graphdb_nablp): which roots have one, in which order
         roots = np.asarray(ids[pos_et.src_node_type], dtype=np.int64)
         cap = cfg.num_max_training_samples_to_output

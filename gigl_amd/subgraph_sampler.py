@@ -263,7 +263,8 @@ class SubgraphSampler:
         dags = sampling_op_dags(cfg, anchor_target)
         rn_prefixes = cfg.random_negative_tfrecord_uri_prefixes
         out: Dict[str, List[str]] = {}
-        s = HipGraphDBSampler(node_types, num, edges, cet, feats, device=device, sampling_seed=seed, edge_features=efeats)
+        s = HipGraphDBSampler(node_types, num, edges, cet, feats, device=device, sampling_seed=seed, edge_features=efeats,
+                              edge_key_columns=edge_key_columns(cfg, dags, efeats))
         try:
             for t in anchor_target:
                 if t not in rn_prefixes:
@@ -432,6 +433,40 @@ def load_preprocessed_typed_graph(cfg: GbmlConfigPbWrapper):
     return node_types, num, ids, feats, edges, cet, efeats
 
 
+def typed_edge_feature_layout(cfg: GbmlConfigPbWrapper):
+    """{edge type: [(feature key, width)]} of the preprocessed typed edge tables, in the order
+    load_preprocessed_typed_graph concatenates them into its edge feature rows (keys of width 0 take no column)"""
+    from .graphdb_sampler import EdgeType
+    from .ingest import feature_widths
+    pm = cfg.preprocessed_metadata
+    out = {}
+    for c, (s_t, rel, d_t) in cfg.condensed_edge_type_map.items():
+        em = pm.edges[c]
+        files = tfrecord_files(os.path.join(_res(cfg, em.tfrecord_uri_prefix), ""))
+        widths = feature_widths(files[0], em.feature_keys) if files and em.feature_keys else [0] * len(em.feature_keys or [])
+        out[EdgeType(s_t, rel, d_t)] = list(zip(em.feature_keys or [], (int(w) for w in widths)))
+    return out
+
+
+def edge_key_columns(cfg: GbmlConfigPbWrapper, dags, efeats):
+    """the scalar edge features the keyed ops (top_k / random_weighted) of `dags` rank by, cut out of the edge feature
+    rows of load_preprocessed_typed_graph -> {edge type: {feature key: fp32 [n_edges]}} (empty without keyed ops)"""
+    wanted = {(op.edge_type, op.edge_feat_name) for dag in dags.values() for node in dag.nodes.values()
+              for op in (node.sampling_op,) if op.keyed}
+    if not wanted:
+        return {}
+    layout = typed_edge_feature_layout(cfg)
+    out: Dict = {}
+    for et, name in sorted(wanted, key=lambda t: (t[0].src_node_type, t[0].relation, t[0].dst_node_type, t[1])):
+        off = 0
+        for k, w in layout.get(et, []):
+            if k == name:
+                break
+            off += w
+        out.setdefault(et, {})[name] = np.ascontiguousarray(np.asarray(efeats[et], dtype=np.float32)[:, off])
+    return out
+
+
 def default_sampling_op_dag(cfg: GbmlConfigPbWrapper, root_node_type: str):
     """the k-hop message-passing DAG of a root node type when the config names no SubgraphSamplingStrategy: hop 1 =
     one INCOMING op per edge type that ends in the root type, hop h+1 = for every hop-h op one INCOMING op per edge
@@ -456,8 +491,8 @@ def default_sampling_op_dag(cfg: GbmlConfigPbWrapper, root_node_type: str):
 
 def sampling_op_dags(cfg: GbmlConfigPbWrapper, node_types: Sequence[str]):
     """getNodeTypeToSamplingOpDagMap (SubgraphSamplingStrategyWrapper.scala:10-20) for the node types asked for"""
-    from .graphdb_sampler import (EdgeType, SamplingOp, SamplingOpDAG, SubgraphSamplingValidationError,
-                                  validate_sampling_op_dags)
+    from .graphdb_sampler import (RANDOM_UNIFORM, RANDOM_WEIGHTED, TOP_K, EdgeType, SamplingOp, SamplingOpDAG,
+                                  SubgraphSamplingValidationError, validate_sampling_op_dags)
     out = {}
     raw: Dict[str, list] = {}
     for path in cfg.message_passing_paths:
@@ -466,13 +501,23 @@ def sampling_op_dags(cfg: GbmlConfigPbWrapper, node_types: Sequence[str]):
         ops = []
         for op in path.get("samplingOps") or []:
             et = op["edgeType"]
+            # the SamplingOp's `sampling_method` oneof (subgraph_sampling_strategy.proto:7-58)
+            method, spec = RANDOM_UNIFORM, op.get("randomUniform")
+            for key, name in (("randomWeighted", RANDOM_WEIGHTED), ("topK", TOP_K), ("userDefined", "user_defined")):
+                if op.get(key) is not None:
+                    method, spec = name, op[key]
+            spec = spec or {}
             ops.append(SamplingOp(
                 op["opName"], EdgeType(et["srcNodeType"], et["relation"], et["dstNodeType"]),
-                int((op.get("randomUniform") or {}).get("numNodesToSample", 0) or op.get("numNodesToSample", 0)),
-                list(op.get("inputOpNames") or []), str(op.get("samplingDirection", "INCOMING"))))
+                int(spec.get("numNodesToSample", 0) or op.get("numNodesToSample", 0)),
+                list(op.get("inputOpNames") or []), str(op.get("samplingDirection", "INCOMING")),
+                method, spec.get("edgeFeatName") if method in (RANDOM_WEIGHTED, TOP_K) else None))
         raw[str(path["rootNodeType"])] = ops
+    keyed = any(op.keyed for ops in raw.values() for op in ops)
     validate_sampling_op_dags(raw, list(cfg.condensed_node_type_map.values()),
-                              [EdgeType(*t) for t in cfg.condensed_edge_type_map.values()])
+                              [EdgeType(*t) for t in cfg.condensed_edge_type_map.values()],
+                              edge_feature_keys=({et: {k: w for k, w in keys} for et, keys in
+                                                  typed_edge_feature_layout(cfg).items()} if keyed else None))
     for root_type, ops in raw.items():
         out[root_type] = SamplingOpDAG.from_ops(ops)
     for t in node_types:

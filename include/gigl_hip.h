@@ -309,6 +309,34 @@ int32_t gigl_expand_frontier(gigl_ctx* ctx, gigl_graph* shard, const uint32_t* n
                              int64_t m, int32_t f, int32_t hash_add, int32_t world, int64_t max_window_end,
                              uint32_t* out_nbr, int32_t* out_cnt);
 
+/* the neighbour-selection methods of a SamplingOp (proto/snapchat/research/gbml/subgraph_sampling_strategy.proto:7-58;
+ * validated by python/gigl/src/common/types/pb_wrappers/sampling_op.py:46-84).  RANDOM_UNIFORM is the hash rule of
+ * gigl_expand_frontier; the two keyed methods select by a named edge feature (csrc/keyed.hip). */
+#define GIGL_SAMPLE_RANDOM_UNIFORM 0
+#define GIGL_SAMPLE_TOPK 1
+#define GIGL_SAMPLE_RANDOM_WEIGHTED 2
+/* one hop of a KEYED op over an explicit frontier (world = 1): TopK and RandomWeighted as the reference's GraphDB
+ * sampler runs them (scala_spark35/common/src/main/scala/graphdb/nebula/NebulaQueryResponseTranslator.scala:39-104,
+ * pinned by scala_spark35/common/src/test/scala/graphdb/nebula/SamplingOpToNebulaQueryTranslatorTest.scala:66-120):
+ *   TopK            ORDER BY e.<edgeFeatName> DESC | LIMIT k
+ *   RandomWeighted  ORDER BY e.<edgeFeatName> * rand() DESC | LIMIT k  (the reference's comment at :71-73: "not TRUE
+ *                   RandomWeighted sampling" — its rule, followed here)
+ * For frontier slot i (node v = nodes[i], K = ksums[i]) let nbr[0..n) be v's row of `graph` (distinct ids, ascending)
+ * and w[j] = key_col[rowptr[v] + j] (key_col: one fp32 per edge in the graph's `col` order; the caller lays out the
+ * named feature there, the first input row of a repeated (src, dst) winning).
+ *   TopK            key[j] = w[j]
+ *   RandomWeighted  key[j] = fl32(w[j] * u[j]), one multiply, u[j] = (float)((h[j] >> 40) + 1) * 2^-24 in (0, 1], where
+ *                   h[j] = xxh64_int32(wrap32((j + 1) + K + hash_add), seed 42) as an unsigned 64-bit value — the hash
+ *                   the uniform rule sorts position j by (the CPU oracle's xxh64_int32 export)
+ * The f largest keys are taken, compared as IEEE floats with -0 == +0, NaN below every number, ties to the lower
+ * position; n <= f takes the whole row and reads no key.  Output exactly as gigl_expand_frontier: the taken ids in
+ * ascending order at out_nbr[i*f ..], out_cnt[i] = min(n, f), GIGL_INVALID padding, GIGL_INVALID / out-of-range slots
+ * empty.  method: GIGL_SAMPLE_TOPK or GIGL_SAMPLE_RANDOM_WEIGHTED.  GIGL_E_UNSUPPORTED outside f in [1, GIGL_MAX_FANOUT]
+ * or on a graph whose rows repeat ids.  Never uses the hash threshold table; nothing synchronises with the host. */
+int32_t gigl_expand_frontier_keyed(gigl_ctx* ctx, gigl_graph* graph, const float* key_col, int32_t method,
+                                   const uint32_t* nodes, const uint32_t* ksums, int64_t m, int32_t f, int32_t hash_add,
+                                   uint32_t* out_nbr, int32_t* out_cnt);
+
 /* the requester side of a hop on a hash-partitioned graph (see gigl_expand_frontier for the owner side): bucket the
  * frontier by owner for ONE equal-split all_to_all, and scatter the owners' answers back into the tree layout.
  * Replaces the per-batch RPC fan-out of the reference's distributed loader
@@ -525,6 +553,11 @@ int32_t gigl_typed_plan_run_nodes(gigl_typed_plan* plan, const uint32_t* roots, 
 int32_t gigl_typed_plan_run_edges(gigl_typed_plan* plan, int32_t b);
 /* a second workspace of the same DAG on another ctx (its own stream): what lets batch i + 1 be built while batch i is read */
 int32_t gigl_typed_plan_clone(gigl_typed_plan* plan, gigl_ctx* ctx, gigl_typed_plan** out);
+/* op `op` (index into the ops given to gigl_typed_plan_create) becomes a keyed op: every run expands it with
+ * gigl_expand_frontier_keyed(method, key_col) instead of the hash rule (GIGL_SAMPLE_RANDOM_UNIFORM: back to the hash
+ * rule).  key_col: DEVICE, one fp32 per edge of the op's graph in its `col` order, owned by the caller and alive while
+ * the plan runs.  Call after create and before the runs; gigl_typed_plan_clone carries it over. */
+int32_t gigl_typed_plan_set_op_keys(gigl_typed_plan* plan, int32_t op, int32_t method, const float* key_col);
 int32_t gigl_typed_plan_buffers(gigl_typed_plan* plan, gigl_typed_plan_out* out);
 /* The batch graph's edges of ALL listed slots as ONE CSR by destination — the operand of the typed attention layers
  * (torch_geometric HGTConv's per-destination softmax over every incoming edge type; python/gigl/src/common/models/pyg/
