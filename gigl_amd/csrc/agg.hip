@@ -748,106 +748,12 @@ __global__ __launch_bounds__(256) void linear_lds_kernel(const float* __restrict
 
 // Weight gradient of the projection: dW[n][k] += sum_{r < m} dy[r][n] * a[r][k]  (and db[n] += sum_r dy[r][n]), the ROWS
 // being the inner dimension — a small output over tens of thousands of rows, of which only the first *m_dev are real.
-// grid = (row chunks of RC rows) x (64-wide n tiles) x (64-wide k tiles): a workgroup stages 32 rows of its dy and a
-// tiles in LDS at a time, every thread keeps a 4 x 4 block of the 64 x 64 partial in registers and adds it to dW with
-// fp32 atomics at the end (one pass over the chunk's rows: the chunks are what parallelises the reduction).  With
-// relu_y, dy is masked by y > 0 on the way in (the activation's backward), so the masked gradient is never
-// materialised for this product.
+// grid = (row chunks of rc rows, wgrad_rows_per_chunk) x (64-wide n tiles) x (64-wide k tiles)
+// (linear_weight_grad_mfma_kernel below).  With relu_y, dy is masked by y > 0 on the way in (the activation's backward),
+// so the masked gradient is never materialised for this product.  The partial tiles go to scratch — part[chunk][n][k],
+// partb[chunk][n] — and a second kernel adds the chunks in order: a fixed summation order, and no atomics piling up on
+// the 256 x 200 addresses of dW.
 constexpr int WG_RC = 256;
-// (the partial tiles go to scratch — part[chunk][n][k], partb[chunk][n] — and a second kernel adds the chunks in order:
-// a fixed summation order, and no atomics piling up on the 256 x 200 addresses of dW)
-__global__ __launch_bounds__(256) void linear_weight_grad_kernel(const float* __restrict__ dy, const float* __restrict__ a,
-                                                                 const float* __restrict__ relu_y,
-                                                                 const int32_t* __restrict__ m_dev, int N, int K,
-                                                                 float* __restrict__ part, float* __restrict__ partb,
-                                                                 int rc) {
-  __shared__ float s_dy[32][68];
-  __shared__ float s_a[32][68];
-  const int M = *m_dev;
-  const int r0 = blockIdx.x * rc;
-  if (r0 >= M) return;
-  const int r1 = min(M, r0 + rc);
-  const int n0 = blockIdx.y * 64, k0 = blockIdx.z * 64;
-  const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
-  float acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-  float colsum = 0.f;  // (k tile 0 only) column sums of dy: thread tid < 64 owns column n0 + tid
-  // staging: thread -> (row tid / 8 of the 32-row block, 8 columns); the NEXT block's operands are already in registers
-  // while the current block is multiplied
-  const int lr = tid >> 3, lc = (tid & 7) * 8;
-  const bool vec = ((N | K) & 3) == 0;
-  float rv[8], ru[8];
-  auto fetch = [&](int rb) {
-    const int row = rb + lr;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) rv[t] = ru[t] = 0.f;
-    if (row >= r1) return;
-    const float* pd = dy + (int64_t)row * N + n0 + lc;
-    const float* py = relu_y ? relu_y + (int64_t)row * N + n0 + lc : nullptr;
-    const float* pa = a + (int64_t)row * K + k0 + lc;
-    if (vec) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        if (n0 + lc + 4 * h < N) {
-          const float4_t v = *reinterpret_cast<const float4_t*>(pd + 4 * h);
-          float4_t m = {1.f, 1.f, 1.f, 1.f};
-          if (py) m = *reinterpret_cast<const float4_t*>(py + 4 * h);
-#pragma unroll
-          for (int t = 0; t < 4; ++t) rv[4 * h + t] = (!py || m[t] > 0.f) ? v[t] : 0.f;
-        }
-        if (k0 + lc + 4 * h < K) {
-          const float4_t u = *reinterpret_cast<const float4_t*>(pa + 4 * h);
-#pragma unroll
-          for (int t = 0; t < 4; ++t) ru[4 * h + t] = u[t];
-        }
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        if (n0 + lc + t < N) rv[t] = (!py || py[t] > 0.f) ? pd[t] : 0.f;
-        if (k0 + lc + t < K) ru[t] = pa[t];
-      }
-    }
-  };
-  fetch(r0);
-  for (int rb = r0; rb < r1; rb += 32) {
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      s_dy[lr][lc + t] = rv[t];
-      s_a[lr][lc + t] = ru[t];
-    }
-    __syncthreads();
-    if (rb + 32 < r1) fetch(rb + 32);
-#pragma unroll 8
-    for (int r = 0; r < 32; ++r) {
-      const float4_t dv = *reinterpret_cast<const float4_t*>(&s_dy[r][ty * 4]);
-      const float4_t av = *reinterpret_cast<const float4_t*>(&s_a[r][tx * 4]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] += dv[i] * av[j];
-    }
-    if (partb && blockIdx.z == 0 && tid < 64)
-      for (int r = 0; r < 32; ++r) colsum += s_dy[r][tid];
-    __syncthreads();
-  }
-  float* pt = part + (int64_t)blockIdx.x * N * K;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int n = n0 + ty * 4 + i;
-    if (n >= N) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int k = k0 + tx * 4 + j;
-      if (k < K) pt[(int64_t)n * K + k] = acc[i][j];
-    }
-  }
-  if (partb && blockIdx.z == 0 && tid < 64 && n0 + tid < N) partb[(int64_t)blockIdx.x * N + n0 + tid] = colsum;
-}
-
 // dw[i] += sum over the chunks that hold real rows of part[c][i] (in chunk order), likewise db
 __global__ __launch_bounds__(256) void linear_weight_grad_reduce_kernel(const float* __restrict__ part,
                                                                         const float* __restrict__ partb,
@@ -1306,215 +1212,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ONE || (HS
 }
 
 // ------------------------------------------------------------------------------------------
-// Two SAGE layers' projections in one kernel (round 5): the first layer's [mean | self] projection with the LAST layer's
+// Two SAGE layers' projections in one kernel: the first layer's [mean | self] projection with the LAST layer's
 // [W_l | W_r] applied to its hidden rows before they leave the workgroup.
 //   SAGEConv layer 1 (homogeneous.py:122-126 -> PyG SAGEConv): out_r = W_l mean_j h_j + b + W_r h_r, and W_l mean_j h_j =
 //   mean_j (W_l h_j): with p_j = [W_l h_j | W_r h_j] (2 x 47 floats instead of the 256-float h_j) the second layer is ONE
 //   reduction over p rows (sage_fused_out_kernel) — the 1-KB hidden rows are never written, the second gather reads
 //   192-byte pieces, the second projection disappears.
-// Shape: hidden width = 256 (two column tiles of 128), 2 * out <= 96.  A workgroup (row tile tm, column tile tn) holds
-// hidden columns [128 tn, +128) of 128 rows, so the second product is K-split over the two column tiles: each writes
-// its PARTIAL p rows to plane tn of y2 ([2][rows][96] floats) and the reduction kernel adds the planes (a fixed order:
-// plane 0 + plane 1 — no atomics).
-// First product: as linear_split_kernel<2, KVEC, SELF, false, HS, ONE> (two fp16 planes per operand, three MFMAs, the
-// same loaders, LDS planes and swizzle), except that the four waves split the ROWS (wave = 32 rows x 128 hidden) and the
-// MFMA operands are swapped, acc = W-fragment x A-fragment = the TRANSPOSED block: lane r holds row r, its 16 registers
-// hidden columns 8 (v / 4) + 4 g + v % 4 — which IS the A-fragment layout of the next product (lane = row, registers = k)
-// up to a permutation of k inside each 16-block, applied to W2's planes when they are prepared (fused2_split_kernel):
-// the hidden tile goes from accumulators to operand registers without touching LDS.
+// Shape: hidden width = 256, 2 * out <= 96.  A workgroup takes 128 rows x ALL 256 hidden columns (a wave: 32 rows x 256,
+// 128 accumulator registers, two waves per SIMD) and writes whole p rows of y2 ([rows][96] floats).
+// First product: the half split of linear_split_kernel (two fp16 planes per operand, three MFMAs), except that the four
+// waves split the ROWS and the MFMA operands are swapped, acc = W-fragment x A-fragment = the TRANSPOSED block: lane r
+// holds row r, its 16 registers hidden columns 8 (v / 4) + 4 g + v % 4 — which IS the A-fragment layout of the next
+// product (lane = row, registers = k) up to a permutation of k inside each 16-block, applied to W2's planes when they are
+// laid out: the hidden tile goes from accumulators to operand registers without touching LDS.
+//   * a wave's A rows are read by that wave only, so they need no LDS: lane (r, g) loads its own row's 16 floats of a
+//     32-k chunk (four 16-byte loads: floats 8 q + 4 g .. + 4, so one instruction reads 32 contiguous bytes per row) and
+//     splits them in registers into the two MFMA steps' fragments;
+//   * W1's fp16 planes are laid out ONCE per run (fused2_images_kernel) as the chunk's LDS images — swizzle included, k
+//     inside a chunk permuted to the order the lanes hold it: position 16 s + 8 g + e <- k = 16 s + 8 (e / 4) + 4 g + e % 4,
+//     the permutation the accumulator layout imposes on the second product anyway — so a chunk of W is eight 16-byte
+//     copies per thread through registers, no vector ALU work, into one of TWO buffers (64 KB of LDS): ONE barrier per chunk.
 // Second product: h = relu(acc / (s_a s_w) + b1) is bounded by K max|W1| max|a| + max|b1| =: B (found on the device
 // from the scales of the first product), so it takes the half split too: h s_h = h1 + h2 with s_h a power of two that
-// brings B under 2^14; element error max(2^-22 |h|, 2^-39 B).  W2's planes (fp16, scaled by s_w2) are staged through LDS
-// 64 hidden columns at a time (rows padded to 144 bytes: conflict-free 16-byte reads).
+// brings B under 2^14; element error max(2^-22 |h|, 2^-39 B).  W2's planes (fp16, scaled by s_w2) are images too, 32 hidden
+// columns (= one accumulator block) per round, ping-ponging between the two buffers, and go global -> LDS without passing
+// registers (global_load_lds_dwordx4: a wave instruction lands 1 KB at a wave-uniform LDS address + 16 lane — the images
+// are copied in that order anyway).
+// (Round 6, profiles/r06x_fused2w_ablations.txt: the parts of the kernel ADD UP — A loads 1.5 us/step, output stores 0.7,
+// second product 0.9, W copies 0.5, first product's MFMAs 0.7, conversions + bookkeeping 1.3 — nothing hides behind
+// anything else, and two waves per SIMD run as fast as three.  The kernels it replaced: DESIGN_HISTORY.md.)
 typedef _Float16 half8v_t __attribute__((ext_vector_type(8)));
 constexpr int F2_N2 = 96;     // padded width of a p row: [W_l h (out, padded to 48) | W_r h (out, padded to 48)]
 constexpr int F2_HID = 256;   // hidden width the kernel is built for
-constexpr int F2_W2LD = 72;   // halves per staged W2 row (64 + 8 of padding)
-
-// PD = chunks of operands in flight (registers): a chunk's MFMAs last ~0.3 us, a load from HBM under three streams
-// 1-2 us — with ONE chunk in flight (round 5) a workgroup's 7 chunks were 7 round trips one after the other.  WPE = waves
-// per SIMD the register budget is cut for (3: 170 registers, 2: 256).
-template <int PD, int WPE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void linear_fused2_kernel(
-    const float* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias,
-    const int32_t* __restrict__ m_dev, int K, float* __restrict__ y2, int64_t plane_stride, int a_tiled,
-    const float* __restrict__ self_src, const uint32_t* __restrict__ self_ids, int d_mean, int self_ld,
-    const float* __restrict__ hs_scale, const float* __restrict__ f2_scale, const _Float16* __restrict__ w2h) {
-  constexpr int BK = 32, LDK = 32, BM = 128, BN = 128, NJ = 2;
-  constexpr int A_EL = 2 * BM * LDK, W_EL = 2 * BN * LDK;  // (shorts) 16 KB + 16 KB
-  static_assert(2 * F2_N2 * F2_W2LD <= A_EL + W_EL, "the staged W2 planes reuse the operand planes");
-  __shared__ __attribute__((aligned(16))) short s_buf[A_EL + W_EL];
-  short(*s_a)[BM * LDK] = reinterpret_cast<short(*)[BM * LDK]>(s_buf);
-  short(*s_w)[BN * LDK] = reinterpret_cast<short(*)[BN * LDK]>(s_buf + A_EL);
-  const int M = *m_dev;
-  constexpr int N = F2_HID, tiles_n = 2;
-  const float hs_a = hs_scale[0], hs_w = hs_scale[1], hs_o = hs_scale[2];
-  int tm, tn;
-  {  // the two column tiles of a row tile run back to back on one XCD (ids 8 apart): the A tile comes from HBM once
-    const unsigned bid = blockIdx.x, span = 8u * (unsigned)tiles_n;
-    const unsigned full = (gridDim.x / span) * span;
-    if (bid < full) {
-      const unsigned grp = bid / span, in = bid % span;
-      tm = (int)(grp * 8u + (in & 7u));
-      tn = (int)(in >> 3);
-    } else {
-      tm = (int)(bid / (unsigned)tiles_n);
-      tn = (int)(bid % (unsigned)tiles_n);
-    }
-  }
-  const int m0b = tm * BM, n0b = tn * BN;
-  if (m0b >= M) return;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int r = lane & 31, g = lane >> 5;
-  const float4_t zero4 = {0.f, 0.f, 0.f, 0.f};
-  float16_t acc[4];  // [hidden block j of 32][.]: lane r = row 32 wv + r, register v = hidden 8 (v / 4) + 4 g + v % 4
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[j][v] = 0.f;
-  const int lr = tid >> 3, lc = tid & 7;
-  float4_t gas[PD][4], gws[PD][2 * NJ];
-  const float* self_row[4] = {nullptr, nullptr, nullptr, nullptr};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = m0b + lr + 32 * i;
-    if (row < M) self_row[i] = self_src + (int64_t)(self_ids ? self_ids[row] : (uint32_t)row) * self_ld;
-  }
-  auto gload = [&](int k0, float4_t (&ga)[4], float4_t (&gw)[2 * NJ]) {
-    const int kk = k0 + lc * 4;
-    const float* at = a + ((int64_t)tm * a_tiled + (k0 >> 5)) * 4096 + lc * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = m0b + lr + 32 * i;
-      const float* src = at + (lr + 32 * i) * 32;
-      if (kk >= d_mean && row < M) src = self_row[i] + (kk - d_mean);
-      ga[i] = (row < M && kk < K) ? *reinterpret_cast<const float4_t*>(src) : zero4;
-    }
-#pragma unroll
-    for (int i = 0; i < 2 * NJ; ++i) {
-      const int row = n0b + lr + 32 * i;
-      gw[i] = (row < N && kk < K) ? *reinterpret_cast<const float4_t*>(w + (int64_t)row * K + kk) : zero4;
-    }
-  };
-#pragma unroll
-  for (int s = 0; s < PD; ++s)
-    if (s * BK < K) gload(s * BK, gas[s], gws[s]);
-  auto chunk = [&](int k0, float4_t (&ga)[4], float4_t (&gw)[2 * NJ]) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int o = split_lds_off(lr + 32 * i, lc * 4);
-      hsplit_store(ga[i], &s_a[0][o], &s_a[1][o], hs_a);
-    }
-#pragma unroll
-    for (int i = 0; i < 2 * NJ; ++i) {
-      const int o = split_lds_off(lr + 32 * i, lc * 4);
-      hsplit_store(gw[i], &s_w[0][o], &s_w[1][o], hs_w);
-    }
-    __syncthreads();
-    if (k0 + PD * BK < K) gload(k0 + PD * BK, ga, gw);  // (the stage just emptied: PD chunks ahead)
-#pragma unroll
-    for (int ks = 0; ks < BK; ks += 16) {
-      if (k0 + ks >= K) break;
-      half8v_t fa[2], fw[4][2];
-#pragma unroll
-      for (int p = 0; p < 2; ++p)
-        fa[p] = *reinterpret_cast<const half8v_t*>(&s_a[p][split_lds_off(wv * 32 + r, ks + 8 * g)]);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-          fw[j][p] = *reinterpret_cast<const half8v_t*>(&s_w[p][split_lds_off(j * 32 + r, ks + 8 * g)]);
-      // three products, smallest terms first, the four accumulators interleaved; operands swapped: the block comes out
-      // transposed (lane = row)
-      constexpr int HA[3] = {1, 0, 0}, HW[3] = {0, 1, 0};
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fw[j][HW[t]], fa[HA[t]], acc[j], 0, 0, 0);
-    }
-  };
-  for (int k0 = 0; k0 < K; k0 += PD * BK) {
-#pragma unroll
-    for (int s = 0; s < PD; ++s)
-      if (k0 + s * BK < K) chunk(k0 + s * BK, gas[s], gws[s]);
-  }
-  // ---- second product: p[row][0:96] (partial over this tile's 128 hidden columns) = relu(h) . W2p[:, 128 tn ..]^T
-  const float s_h = f2_scale[0], o2 = f2_scale[2];
-  _Float16* s_w2 = reinterpret_cast<_Float16*>(s_buf);  // [2 planes][96][F2_W2LD]
-  float16_t acc2[3];
-#pragma unroll
-  for (int n = 0; n < 3; ++n)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc2[n][v] = 0.f;
-#pragma unroll
-  for (int rd = 0; rd < 2; ++rd) {
-    __syncthreads();  // the operand planes (rd = 0) / the previous 64 columns' W2 fragments are done with
-    // stage W2p[plane][n2][n0b + 64 rd .. +64) (halves, k already permuted per 16-block): 2 * 96 rows of 128 bytes
-    for (int q = tid; q < 2 * F2_N2 * 8; q += 256) {
-      const int pl = q / (F2_N2 * 8), rem = q - pl * (F2_N2 * 8), row = rem >> 3, pc = rem & 7;
-      const uint4 v = *reinterpret_cast<const uint4*>(w2h + ((int64_t)pl * F2_N2 + row) * F2_HID + n0b + 64 * rd + 8 * pc);
-      *reinterpret_cast<uint4*>(s_w2 + (pl * F2_N2 + row) * F2_W2LD + 8 * pc) = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
-      const int j = 2 * rd + jj;
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        // this lane's 8 hidden values of the 16-block: registers v = 8 hf .. 8 hf + 7 = hidden 32 j + 16 hf + {4 g + t, 8 + 4 g + t}
-        half8v_t h1, h2;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const float4_t bq = bias ? *reinterpret_cast<const float4_t*>(bias + n0b + 32 * j + 8 * (2 * hf + q) + 4 * g) : zero4;
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            float x = acc[j][8 * hf + 4 * q + t] * hs_o + bq[t];
-            x = (x > 0.f ? x : 0.f) * s_h;
-            const _Float16 a1 = (_Float16)x;
-            h1[4 * q + t] = a1;
-            h2[4 * q + t] = (_Float16)(x - (float)a1);
-          }
-        }
-        const int kb = 2 * jj + hf;  // 16-block of the staged 64 columns
-#pragma unroll
-        for (int n = 0; n < 3; ++n) {
-          const half8v_t w1 = *reinterpret_cast<const half8v_t*>(s_w2 + (n * 32 + r) * F2_W2LD + 16 * kb + 8 * g);
-          const half8v_t w2 = *reinterpret_cast<const half8v_t*>(s_w2 + (F2_N2 + n * 32 + r) * F2_W2LD + 16 * kb + 8 * g);
-          acc2[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2, w1, acc2[n], 0, 0, 0);
-          acc2[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h1, w2, acc2[n], 0, 0, 0);
-          acc2[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h1, w1, acc2[n], 0, 0, 0);
-        }
-      }
-    }
-  }
-  // D layout of acc2[n]: lane r = column 32 n + r of p, register v = row 8 (v / 4) + 4 g + v % 4 of the wave's 32 rows:
-  // one store instruction covers two rows x 32 columns = two whole 128-byte lines (p rows are 384 bytes)
-  float* yp = y2 + (int64_t)tn * plane_stride;
-#pragma unroll
-  for (int n = 0; n < 3; ++n)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const int row = m0b + wv * 32 + 8 * (v >> 2) + 4 * g + (v & 3);
-      if (row < M) yp[(int64_t)row * F2_N2 + n * 32 + r] = acc2[n][v] * o2;
-    }
-}
-
-// ---- round 6: the same two products with the A operand straight from global memory
-// What the round-5 kernel waited on (SQ counters, profiles/r06h_sq_products.json: matrix pipe 30 %, LDS 21-36 %, vector ALU
-// ~40 % busy, 2.7 waves per SIMD resident, each waiting ~80 % of its cycles; deeper register prefetch at two waves per SIMD
-// was slower, profiles/r06v_*): the chain per 32-k chunk — operands land, EVERY thread splits 16 A + 16 W floats into LDS,
-// barrier, fragments back out of LDS, MFMAs, barrier — with three workgroups per CU to overlap it.  But the four waves split
-// the ROWS, so a wave's A rows are read by that wave only: they need no LDS.  Here
-//   * lane (r, g) of wave wv loads its own row's 16 floats of the chunk (four 16-byte loads: floats 8 q + 4 g .. + 4, so one
-//     instruction reads 32 contiguous bytes per row) and splits them in registers into the two MFMA steps' fragments;
-//   * W1's fp16 planes are laid out ONCE per run (fused2_images_kernel) as the chunk's 16-KB LDS image — swizzle included, k
-//     inside a chunk permuted to the order the lanes hold it: position 16 s + 8 g + e <- k = 16 s + 8 (e / 4) + 4 g + e % 4,
-//     the permutation the accumulator layout imposes on the second product anyway — so a chunk of W is four 16-byte copies
-//     per thread, no vector ALU work, into one of TWO image buffers: ONE barrier per chunk;
-//   * W2's planes likewise, 32 hidden columns (= one accumulator block) per round, ping-ponging between the two buffers.
-// Per chunk and workgroup: 16 KB of LDS writes + 64 KB of reads (was 32 + 80), half the conversions, half the barriers.
 constexpr int F2_IMG1 = 2 * 128 * 32;  // halves per W1 chunk image: [plane][128 hidden columns][32 k, swizzled]
 constexpr int F2_IMG2 = 2 * F2_N2 * 32;  // halves per W2 round image: [plane][96 p columns][32 hidden, swizzled]
 __device__ __forceinline__ int f2_perm(int kpos) {  // k (inside a 32-block) held at fragment position kpos
@@ -1522,213 +1251,12 @@ __device__ __forceinline__ int f2_perm(int kpos) {  // k (inside a 32-block) hel
 }
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-// DBG: `ablate` switches parts of the kernel off (wrong rows; timing experiments only — GIGL_F2_ABLATE, bits: 1 no A loads,
-// 2 no W image copies, 4 one MFMA of three in the first product, 8 no second product, 16 no output stores, 32 no barriers)
-template <int AD, int WPE, bool DBG>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void linear_fused2w_kernel(
-    const float* __restrict__ a, const float* __restrict__ bias, const int32_t* __restrict__ m_dev, int K,
-    float* __restrict__ y2, int64_t plane_stride, int a_tiled, const float* __restrict__ self_src,
-    const uint32_t* __restrict__ self_ids, int d_mean, int self_ld, const float* __restrict__ hs_scale,
-    const float* __restrict__ f2_scale, const _Float16* __restrict__ w1img, const _Float16* __restrict__ w2img, int ablate) {
-  const int ab = DBG ? ablate : 0;
-  auto barrier = [&]() {
-    if (!(ab & 32)) __syncthreads();
-  };
-  __shared__ __attribute__((aligned(16))) short s_buf[2][F2_IMG1];
-  const int M = *m_dev;
-  constexpr int tiles_n = 2;
-  const float hs_a = hs_scale[0], hs_o = hs_scale[2];
-  int tm, tn;
-  {  // (as linear_fused2_kernel: the two column tiles of a row tile back to back on one XCD)
-    const unsigned bid = blockIdx.x, span = 8u * (unsigned)tiles_n;
-    const unsigned full = (gridDim.x / span) * span;
-    if (bid < full) {
-      const unsigned grp = bid / span, in = bid % span;
-      tm = (int)(grp * 8u + (in & 7u));
-      tn = (int)(in >> 3);
-    } else {
-      tm = (int)(bid / (unsigned)tiles_n);
-      tn = (int)(bid % (unsigned)tiles_n);
-    }
-  }
-  const int m0b = tm * 128, n0b = tn * 128;
-  if (m0b >= M) return;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int r = lane & 31, g = lane >> 5;
-  const int nc = (K + 31) >> 5;
-  const float4_t zero4 = {0.f, 0.f, 0.f, 0.f};
-  float16_t acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[j][v] = 0.f;
-  const int row = m0b + wv * 32 + r;
-  const bool valid = row < M;
-  const float* self_row = valid ? self_src + (int64_t)(self_ids ? self_ids[row] : (uint32_t)row) * self_ld : self_src;
-  const float* at = a + (int64_t)tm * a_tiled * 4096 + (wv * 32 + r) * 32 + 4 * g;
-  auto aload = [&](int c, float4_t (&ra)[4]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int kk = c * 32 + 8 * q + 4 * g;
-      const float* src = kk >= d_mean ? self_row + (kk - d_mean) : at + (int64_t)c * 4096 + 8 * q;
-      ra[q] = (valid && kk < K && !(ab & 1)) ? *reinterpret_cast<const float4_t*>(src) : zero4;
-    }
-  };
-  const u32x4_t* w1src = reinterpret_cast<const u32x4_t*>(w1img) + (int64_t)tn * nc * (F2_IMG1 / 8) + tid;
-  u32x4_t wr0, wr1, wr2, wr3;  // (named: as an array the compiler kept two of them in scratch memory)
-  auto wload = [&](int c) {
-    if (ab & 2) return;
-    const u32x4_t* src = w1src + (int64_t)c * (F2_IMG1 / 8);
-    wr0 = src[0];
-    wr1 = src[256];
-    wr2 = src[512];
-    wr3 = src[768];
-  };
-  auto wstore = [&](int b) {
-    if (ab & 2) return;
-    u32x4_t* dst = reinterpret_cast<u32x4_t*>(s_buf[b]) + tid;
-    dst[0] = wr0;
-    dst[256] = wr1;
-    dst[512] = wr2;
-    dst[768] = wr3;
-  };
-  float4_t ras[AD][4];
-  wload(0);
-#pragma unroll
-  for (int d = 0; d < AD; ++d)
-    if (d < nc) aload(d, ras[d]);
-  wstore(0);
-  if (nc > 1) wload(1);
-  const u32x4_t* w2src = reinterpret_cast<const u32x4_t*>(w2img) + (int64_t)tn * 4 * (F2_IMG2 / 8) + tid;
-  auto w2load = [&](int rd) {
-    const u32x4_t* src = w2src + (int64_t)rd * (F2_IMG2 / 8);
-    wr0 = src[0];
-    wr1 = src[256];
-    wr2 = src[512];
-  };
-  auto w2store = [&](int b) {
-    u32x4_t* dst = reinterpret_cast<u32x4_t*>(s_buf[b]) + tid;
-    dst[0] = wr0;
-    dst[256] = wr1;
-    dst[512] = wr2;
-  };
-  if (nc == 1) w2load(0);
-  barrier();
-  auto chunk = [&](int c, float4_t (&ra)[4]) {
-    half8v_t fa[2][2];  // [MFMA step][plane]
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float x = ra[2 * s + (e >> 2)][e & 3] * hs_a;
-        const _Float16 a1 = (_Float16)x;
-        fa[s][0][e] = a1;
-        fa[s][1][e] = (_Float16)(x - (float)a1);
-      }
-    if (c + AD < nc) aload(c + AD, ra);
-    const short* sw = s_buf[c & 1];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      if (c * 32 + 16 * s >= K) break;
-      half8v_t fw[4][2];
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-          fw[j][p] = *reinterpret_cast<const half8v_t*>(&sw[p * (F2_IMG1 / 2) + split_lds_off(j * 32 + r, 16 * s + 8 * g)]);
-      constexpr int HA[3] = {1, 0, 0}, HW[3] = {0, 1, 0};
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        if ((ab & 4) && t < 2) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fw[j][HW[t]], fa[s][HA[t]], acc[j], 0, 0, 0);
-      }
-    }
-    if (c + 1 < nc) {
-      wstore((c + 1) & 1);
-      if (c + 2 < nc) wload(c + 2);
-      else w2load(0);  // (the image registers are free from here on: the second product's first round)
-    }
-    barrier();
-  };
-  for (int c = 0; c < nc; c += AD) {
-#pragma unroll
-    for (int d = 0; d < AD; ++d)
-      if (c + d < nc) chunk(c + d, ras[d]);
-  }
-  // ---- second product, one accumulator block (32 hidden columns) per round
-  const float s_h = f2_scale[0], o2 = f2_scale[2];
-  float16_t acc2[3];
-#pragma unroll
-  for (int n = 0; n < 3; ++n)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc2[n][v] = 0.f;
-  w2store(0);
-  w2load(1);
-  barrier();
-#pragma unroll
-  for (int rd = 0; rd < 4; ++rd) {
-    if (ab & 8) break;
-    const _Float16* sw2 = reinterpret_cast<const _Float16*>(s_buf[rd & 1]);
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      half8v_t h1, h2;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const float4_t bq = bias ? *reinterpret_cast<const float4_t*>(bias + n0b + 32 * rd + 8 * (2 * hf + q) + 4 * g) : zero4;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          float x = acc[rd][8 * hf + 4 * q + t] * hs_o + bq[t];
-          x = (x > 0.f ? x : 0.f) * s_h;
-          const _Float16 a1 = (_Float16)x;
-          h1[4 * q + t] = a1;
-          h2[4 * q + t] = (_Float16)(x - (float)a1);
-        }
-      }
-#pragma unroll
-      for (int n = 0; n < 3; ++n) {
-        const half8v_t w1 = *reinterpret_cast<const half8v_t*>(sw2 + split_lds_off(n * 32 + r, 16 * hf + 8 * g));
-        const half8v_t w2 = *reinterpret_cast<const half8v_t*>(sw2 + F2_IMG2 / 2 + split_lds_off(n * 32 + r, 16 * hf + 8 * g));
-        acc2[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2, w1, acc2[n], 0, 0, 0);
-        acc2[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h1, w2, acc2[n], 0, 0, 0);
-        acc2[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h1, w1, acc2[n], 0, 0, 0);
-      }
-    }
-    if (rd + 1 < 4) {
-      w2store((rd + 1) & 1);
-      if (rd + 2 < 4) w2load(rd + 2);
-      barrier();
-    }
-  }
-  float* yp = y2 + (int64_t)tn * plane_stride;
-#pragma unroll
-  for (int n = 0; n < 3; ++n)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const int orow = m0b + wv * 32 + 8 * (v >> 2) + 4 * g + (v & 3);
-      if (orow < M && !(ab & 16)) yp[(int64_t)orow * F2_N2 + n * 32 + r] = acc2[n][v] * o2;
-    }
-}
-
-// ---- the whole hidden width in one workgroup (round 6, after the ablation runs of linear_fused2w_kernel,
-// profiles/r06x_fused2w_ablations.txt: the parts of the kernel ADD UP — A loads 1.5 us/step, output stores 0.7, second product
-// 0.9, W copies 0.5, first product's MFMAs 0.7, conversions + bookkeeping 1.3 — nothing hides behind anything else, and two
-// waves per SIMD run as fast as three).  So do less of each: a workgroup takes 128 rows x ALL 256 hidden columns (a wave: 32
-// rows x 256, 128 accumulator registers, two waves per SIMD): a row's A chunk is loaded and split ONCE (was once per column
-// tile: twice), the second product is not K-split any more — one p row of 384 B leaves instead of two partial ones, and
-// sage_fused_out_kernel reads one 192-byte piece per edge instead of two.  LDS: two buffers of two W1 chunk images (64 KB).
-// GLDS: the images go global -> LDS without passing registers (global_load_lds_dwordx4: a wave instruction lands 1 KB at a
-// wave-uniform LDS address + 16 lane — the images are copied in that order anyway): no staging registers, no ds_write pass.
-template <bool DBG, bool GLDS, bool GLDS2>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void linear_fused2x_kernel(
     const float* __restrict__ a, const float* __restrict__ bias, const int32_t* __restrict__ m_dev, int K,
     float* __restrict__ y2, int a_tiled, const float* __restrict__ self_src, const uint32_t* __restrict__ self_ids,
     int d_mean, int self_ld, const float* __restrict__ hs_scale, const float* __restrict__ f2_scale,
-    const _Float16* __restrict__ w1img, const _Float16* __restrict__ w2img, int ablate,
-    const int32_t* __restrict__ n_self_rows) {
+    const _Float16* __restrict__ w1img, const _Float16* __restrict__ w2img, const int32_t* __restrict__ n_self_rows) {
   __shared__ __attribute__((aligned(16))) short s_buf[2][2 * F2_IMG1];
-  const int ab = DBG ? ablate : 0;
   const int M = *m_dev;
   const float hs_a = hs_scale[0], hs_o = hs_scale[2];
   const int tm = blockIdx.x, m0b = tm * 128;
@@ -1756,7 +1284,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void l
     for (int q = 0; q < 4; ++q) {
       const int kk = c * 32 + 8 * q + 4 * g;
       const float* src = kk >= d_mean ? self_row + (kk - d_mean) : at + (int64_t)c * 4096 + 8 * q;
-      ra[q] = (valid && kk < K && !(ab & 1)) ? *reinterpret_cast<const float4_t*>(src) : zero4;
+      ra[q] = (valid && kk < K) ? *reinterpret_cast<const float4_t*>(src) : zero4;
     }
   };
   constexpr int IMGU = F2_IMG1 / 8;  // 16-byte units per W1 chunk image
@@ -1764,30 +1292,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void l
   u32x4_t wr0, wr1, wr2, wr3, wr4, wr5, wr6, wr7;
   typedef const __attribute__((address_space(1))) void* gptr_t;
   typedef __attribute__((address_space(3))) void* lptr_t;
-  auto wload = [&](int c, int b) {  // (GLDS: straight into buffer b)
-    if (ab & 2) return;
+  auto wload = [&](int c) {  // W1 chunk c's two images (hidden columns 0..127, 128..255) into the staging registers
     const u32x4_t* s0 = w1src + (int64_t)c * IMGU;
     const u32x4_t* s1 = w1src + (int64_t)(nc + c) * IMGU;
-    if constexpr (GLDS) {
-      short* dst = s_buf[b] + wv * 512;  // (this wave's 1-KB piece of each quarter image)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        __builtin_amdgcn_global_load_lds((gptr_t)(s0 + 256 * i), (lptr_t)(dst + 2048 * i), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gptr_t)(s1 + 256 * i), (lptr_t)(dst + F2_IMG1 + 2048 * i), 16, 0, 0);
-      }
-    } else {
-      wr0 = s0[0];
-      wr1 = s0[256];
-      wr2 = s0[512];
-      wr3 = s0[768];
-      wr4 = s1[0];
-      wr5 = s1[256];
-      wr6 = s1[512];
-      wr7 = s1[768];
-    }
+    wr0 = s0[0];
+    wr1 = s0[256];
+    wr2 = s0[512];
+    wr3 = s0[768];
+    wr4 = s1[0];
+    wr5 = s1[256];
+    wr6 = s1[512];
+    wr7 = s1[768];
   };
   auto wstore = [&](int b) {
-    if (GLDS || (ab & 2)) return;
     u32x4_t* dst = reinterpret_cast<u32x4_t*>(s_buf[b]) + tid;
     dst[0] = wr0;
     dst[256] = wr1;
@@ -1799,37 +1316,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void l
     dst[IMGU + 768] = wr7;
   };
   const u32x4_t* w2src = reinterpret_cast<const u32x4_t*>(w2img) + tid;
-  auto w2load = [&](int rd, int b) {
+  auto w2load = [&](int rd, int b) {  // W2 round rd's image straight into buffer b (this wave's 1-KB piece of each third)
     const u32x4_t* src = w2src + (int64_t)rd * (F2_IMG2 / 8);
-    if constexpr (GLDS2) {
-      short* dst = s_buf[b] + wv * 512;
+    short* dst = s_buf[b] + wv * 512;
 #pragma unroll
-      for (int i = 0; i < 3; ++i) __builtin_amdgcn_global_load_lds((gptr_t)(src + 256 * i), (lptr_t)(dst + 2048 * i), 16, 0, 0);
-    } else {
-      wr0 = src[0];
-      wr1 = src[256];
-      wr2 = src[512];
-    }
-  };
-  auto w2store = [&](int b) {
-    if (GLDS2) return;
-    u32x4_t* dst = reinterpret_cast<u32x4_t*>(s_buf[b]) + tid;
-    dst[0] = wr0;
-    dst[256] = wr1;
-    dst[512] = wr2;
-  };
-  auto barrier = [&]() {
-    if (!(ab & 32)) __syncthreads();
+    for (int i = 0; i < 3; ++i) __builtin_amdgcn_global_load_lds((gptr_t)(src + 256 * i), (lptr_t)(dst + 2048 * i), 16, 0, 0);
   };
   // stage k (W1 chunks 0 .. nc - 1, then W2's rounds) lives in buffer k & 1; its image is fetched while stage k - 1 is worked on
-  wload(0, 0);
+  wload(0);
   aload(0);
   wstore(0);
-  if constexpr (!GLDS) {
-    if (nc > 1) wload(1, 1);
-    else if constexpr (!GLDS2) w2load(0, 1);
-  }
-  barrier();
+  if (nc > 1) wload(1);
+  __syncthreads();
   for (int c = 0; c < nc; ++c) {
     half8v_t fa[2][2];  // [MFMA step][plane]
 #pragma unroll
@@ -1842,12 +1340,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void l
         fa[s][1][e] = (_Float16)(x - (float)a1);
       }
     if (c + 1 < nc) aload(c + 1);
-    if constexpr (GLDS) {
-      if (c + 1 < nc) wload(c + 1, (c + 1) & 1);
-    }
-    if constexpr (GLDS2) {
-      if (c + 1 == nc) w2load(0, nc & 1);  // (that buffer's last reader was chunk nc - 2)
-    }
+    if (c + 1 == nc) w2load(0, nc & 1);  // (that buffer's last reader was chunk nc - 2)
     // the first layer's bias for the second product: fetched during the LAST chunk's MFMAs into the tail of the buffer that
     // chunk does not read (a W2 round image takes 12 of its 32 KB) — read per lane from global memory inside the rounds, each
     // of the sixteen (round, half) blocks opened with a wait for its bias load (an L2 round trip behind nine MFMAs)
@@ -1872,22 +1365,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void l
                 &sw[tn * F2_IMG1 + p * (F2_IMG1 / 2) + split_lds_off(j * 32 + r, 16 * s + 8 * g)]);
         constexpr int HA[3] = {1, 0, 0}, HW[3] = {0, 1, 0};
 #pragma unroll
-        for (int t = 0; t < 3; ++t) {
-          if ((ab & 4) && t < 2) continue;
+        for (int t = 0; t < 3; ++t)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             acc[4 * tn + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fw[j][HW[t]], fa[s][HA[t]], acc[4 * tn + j], 0, 0, 0);
-        }
       }
     }
-    if constexpr (!GLDS) {
-      if (c + 1 < nc) {
-        wstore((c + 1) & 1);
-        if (c + 2 < nc) wload(c + 2, 0);
-        else if constexpr (!GLDS2) w2load(0, 0);  // (the image registers are free from here on: the second product's first round)
-      }
+    if (c + 1 < nc) {
+      wstore((c + 1) & 1);
+      if (c + 2 < nc) wload(c + 2);
     }
-    barrier();
+    __syncthreads();
   }
   const float4_t* s_bias = reinterpret_cast<const float4_t*>(s_buf[nc & 1] + F2_IMG2);  // [64]: hidden columns 4 i .. 4 i + 3
   // ---- second product, one accumulator block (32 hidden columns) per round, the rounds' W2 images ping-ponging
@@ -1897,18 +1385,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void l
   for (int n = 0; n < 3; ++n)
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc2[n][v] = 0.f;
-  if constexpr (!GLDS2) {
-    w2store(nc & 1);
-    w2load(1, 0);
-    barrier();
-  }
 #pragma unroll
   for (int rd = 0; rd < 8; ++rd) {
-    if (ab & 8) break;
     const _Float16* sw2 = reinterpret_cast<const _Float16*>(s_buf[(nc + rd) & 1]);
-    if constexpr (GLDS2) {
-      if (rd + 1 < 8) w2load(rd + 1, (nc + rd + 1) & 1);
-    }
+    if (rd + 1 < 8) w2load(rd + 1, (nc + rd + 1) & 1);
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
       half8v_t h1, h2;
@@ -1934,13 +1414,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void l
         acc2[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h1, w1, acc2[n], 0, 0, 0);
       }
     }
-    if (rd + 1 < 8) {
-      if constexpr (!GLDS2) {
-        w2store((nc + rd + 1) & 1);
-        if (rd + 2 < 8) w2load(rd + 2, 0);
-      }
-      barrier();
-    }
+    if (rd + 1 < 8) __syncthreads();
   }
 #pragma unroll
   for (int n = 0; n < 3; ++n) {
@@ -1948,15 +1422,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void l
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
       const int orow = m0b + wv * 32 + 8 * (v >> 2) + 4 * g + (v & 3);
-      if (orow < M && !(ab & 16)) y2[(int64_t)orow * F2_N2 + n * 32 + r] = acc2[n][v] * o2;
+      if (orow < M) y2[(int64_t)orow * F2_N2 + n * 32 + r] = acc2[n][v] * o2;
     }
   }
 }
 
-// the LDS images linear_fused2w_kernel copies: per run, after the scales (hs[1] = s_w of the first product, f2[1] = s_w2).
+// the LDS images linear_fused2x_kernel copies: per run, after the scales (hs[1] = s_w of the first product, f2[1] = s_w2).
 //   w1img[tn][chunk][plane][split_lds_off(c, kpos)] = plane of s_w W1[128 tn + c][32 chunk + f2_perm(kpos)]  (0 beyond K)
 //   w2img[tn][round][plane][split_lds_off(n, kpos)] = plane of s_w2 W2p[n][128 tn + 32 round + f2_perm(kpos)]
-// (W2p = [W_l ; W_r] of the last layer padded to 96 rows, as fused2_split_kernel).  One thread per element.
+// (W2p = [W_l ; W_r] of the last layer padded to 96 rows: rows 0..out-1 = W_l, 48..48+out-1 = W_r, the rest zero).  One
+// thread per element.
 __global__ __launch_bounds__(256) void fused2_images_kernel(const float* __restrict__ hs, const float* __restrict__ f2,
                                                             const float* __restrict__ w1, int K, const float* __restrict__ w2,
                                                             int n_out, _Float16* __restrict__ w1img,
@@ -2044,26 +1519,6 @@ __global__ __launch_bounds__(256) void fused2_scale_kernel(const float* __restri
   }
 }
 
-// the fp16 planes of W2p = [W_l ; W_r] of the last layer ([96][256]: rows 0..out-1 = W_l, 48..48+out-1 = W_r, the rest
-// zero), scaled by s_w2 = f2[1], each 16-block of k stored in the order the fused kernel's accumulator registers hold it:
-// position 8 g + e <- element 8 (e / 4) + 4 g + e % 4.  One thread per element.
-__global__ __launch_bounds__(256) void fused2_split_kernel(const float* __restrict__ f2, const float* __restrict__ w2,
-                                                           int n_out, _Float16* __restrict__ w2h) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= F2_N2 * F2_HID) return;
-  const float s_w2 = f2[1];
-  const int c = i / F2_HID, pos = i - c * F2_HID;
-  const int blk = pos >> 4, in = pos & 15, gg = in >> 3, e = in & 7;
-  const int k = blk * 16 + 8 * (e >> 2) + 4 * gg + (e & 3);  // the element that sits at position `pos`
-  float x = 0.f;
-  if (c < n_out) x = w2[(int64_t)c * 2 * F2_HID + k];
-  else if (c >= F2_N2 / 2 && c - F2_N2 / 2 < n_out) x = w2[(int64_t)(c - F2_N2 / 2) * 2 * F2_HID + F2_HID + k];
-  x *= s_w2;
-  const _Float16 a1 = (_Float16)x;
-  w2h[i] = a1;
-  w2h[F2_N2 * F2_HID + i] = (_Float16)(x - (float)a1);
-}
-
 // Half-split scales of a layer >= 1 (round 5): its operand [reduce(h) | h] is made of the previous layer's outputs h =
 // act(a . W^T + b), bounded by K max|W| max|a| + max|b| — and max|a| < 2^15 / s_a, max|W| < 2^15 / s_w are what the
 // previous layer's own scales hs_prev = {s_a, s_w, ..} say.  hs_out = {s_h, s_w', 1 / (s_h s_w')}: s_h brings that bound
@@ -2128,14 +1583,13 @@ __global__ __launch_bounds__(256) void hs_chain_kernel(const float* __restrict__
   }
 }
 
-// The last SAGE layer over the p rows of linear_fused2_kernel: for root slot s (local id i = root_local[s]):
-//   out[s][c] = act( reduce_{e in row i} (p0 + p1)[col[e]][c] + (p0 + p1)[i][48 + c] + b2[c] ),  c < n_out
-// (reduce = mean / sum; p0 / p1 = the two K-split partial planes, added plane 0 first).  One wave per root slot: four
-// groups of 16 lanes take every fourth edge, 12 lanes of a group a float4 of the 48-float half row each.  Writes the
-// roots' rows straight into the caller's buffer (a failed batch set: NaN rows, as gigl_take_rows).
-template <int OP, int PLANES>
-__global__ __launch_bounds__(256) void sage_fused_out_kernel(const float* __restrict__ p, int64_t plane_stride,
-                                                             const int32_t* __restrict__ rowptr,
+// The last SAGE layer over the p rows of linear_fused2x_kernel: for root slot s (local id i = root_local[s]):
+//   out[s][c] = act( reduce_{e in row i} p[col[e]][c] + p[i][48 + c] + b2[c] ),  c < n_out
+// (reduce = mean / sum).  One wave per root slot: four groups of 16 lanes take every fourth edge, 12 lanes of a group a
+// float4 of the 48-float half row each.  Writes the roots' rows straight into the caller's buffer (a failed batch set:
+// NaN rows, as gigl_take_rows).
+template <int OP>
+__global__ __launch_bounds__(256) void sage_fused_out_kernel(const float* __restrict__ p, const int32_t* __restrict__ rowptr,
                                                              const int32_t* __restrict__ rowend,
                                                              const int32_t* __restrict__ col,
                                                              const int32_t* __restrict__ root_local, int b, int n_out,
@@ -2152,23 +1606,16 @@ __global__ __launch_bounds__(256) void sage_fused_out_kernel(const float* __rest
     for (int c = lane; c < n_out; c += 64) o[c] = v;
     return;
   }
-  const float* p0 = p;
-  const float* p1 = p + plane_stride;
   const int e0 = rowptr[i], m = rowend[i] - e0;
   float4_t acc = {0.f, 0.f, 0.f, 0.f};
   if (sl < 12) {
     for (int e = sub; e < m; e += 8) {  // two edges of this group in flight
       const int ja = col[e0 + e], eb = e + 4;
       const int jb = eb < m ? col[e0 + eb] : ja;
-      const float4_t a0 = *reinterpret_cast<const float4_t*>(p0 + (int64_t)ja * F2_N2 + 4 * sl);
-      float4_t a1 = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (PLANES == 2) a1 = *reinterpret_cast<const float4_t*>(p1 + (int64_t)ja * F2_N2 + 4 * sl);
-      float4_t b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};
-      if (eb < m) {
-        b0 = *reinterpret_cast<const float4_t*>(p0 + (int64_t)jb * F2_N2 + 4 * sl);
-        if constexpr (PLANES == 2) b1 = *reinterpret_cast<const float4_t*>(p1 + (int64_t)jb * F2_N2 + 4 * sl);
-      }
-      acc += (a0 + a1) + (b0 + b1);
+      const float4_t a0 = *reinterpret_cast<const float4_t*>(p + (int64_t)ja * F2_N2 + 4 * sl);
+      float4_t b0 = {0.f, 0.f, 0.f, 0.f};
+      if (eb < m) b0 = *reinterpret_cast<const float4_t*>(p + (int64_t)jb * F2_N2 + 4 * sl);
+      acc += a0 + b0;
     }
   }
 #pragma unroll
@@ -2179,10 +1626,8 @@ __global__ __launch_bounds__(256) void sage_fused_out_kernel(const float* __rest
   }
   if (sub == 0 && sl < 12) {
     const float dv = (OP == GIGL_AGGR_MEAN && m > 0) ? (float)m : 1.f;
-    const float4_t s0 = *reinterpret_cast<const float4_t*>(p0 + (int64_t)i * F2_N2 + F2_N2 / 2 + 4 * sl);
-    float4_t s1 = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (PLANES == 2) s1 = *reinterpret_cast<const float4_t*>(p1 + (int64_t)i * F2_N2 + F2_N2 / 2 + 4 * sl);
-    float4_t rr = acc / dv + (s0 + s1);
+    const float4_t s0 = *reinterpret_cast<const float4_t*>(p + (int64_t)i * F2_N2 + F2_N2 / 2 + 4 * sl);
+    float4_t rr = acc / dv + s0;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int c = 4 * sl + t;
@@ -2748,24 +2193,6 @@ __global__ __launch_bounds__(256) void gat_input_gather_kernel(
   }
 }
 
-// sum over the 64 lanes of a wave, returned to every lane, on the VALU / SALU only: four DPP steps give every lane its
-// row-of-16 total (xor 1, xor 2 inside quads, then the half-row and row mirrors), four v_readlane + scalar adds combine
-// the rows.  (__shfl_xor lowers the wide steps to ds_bpermute: the one-pass kernel below spent a quarter of its
-// instructions in the LDS pipeline on them.)
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-  auto dpp = [](float x, auto ctrl) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xF,
-                                                                   0xF, true));
-  };
-  v += dpp(v, std::integral_constant<int, 0xB1>{});   // quad_perm [1,0,3,2]
-  v += dpp(v, std::integral_constant<int, 0x4E>{});   // quad_perm [2,3,0,1]
-  v += dpp(v, std::integral_constant<int, 0x141>{});  // row_half_mirror
-  v += dpp(v, std::integral_constant<int, 0x140>{});  // row_mirror
-  const int b = __builtin_bit_cast(int, v);
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16)) +
-         __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
-}
-
 // ---- the same first layer in ONE row pass (the one-call plan's layer 0): the folded source vectors stay in
 // registers and every edge's logit is formed from the feature row that has just been read for the aggregation, online
 // softmax over the row.  No per-node score array exists,
@@ -2960,263 +2387,14 @@ __global__ __launch_bounds__(256) void gat_input_online_kernel(
 //   z_i^h = sum_e alpha_e^h x_e,  alpha = softmax_e leaky(<x_e, us^h> + <x_i, ud^h>)  (e over the in-edges and the self loop)
 //   given dz_i^h:  d alpha_e = <dz_i^h, x_e>,  S = sum_e alpha_e d alpha_e,  dpre_e = alpha_e (d alpha_e - S) leaky'(pre_e),
 //                  d us^h += sum_e dpre_e x_e,   d ud^h += (sum_e dpre_e) x_i
-// One wave per destination row (the forward's lane layout), two sweeps over the row's edges: the first forms every
-// edge's logit and d alpha from the source row as it is read (reduced together, gigl_wave_reduce16) and parks the two
-// scalars per head in edge_scr; the second re-reads the rows (L2 / MALL hits) and accumulates d us.  A wave keeps its
-// d us / d ud sums in registers over all its rows and adds them to `du` once, at the end (fp32 atomics).
-template <typename T, int V, int H>
-__global__ __launch_bounds__(256) void gat_input_backward_kernel(
-    const T* __restrict__ src, int d, const uint32_t* __restrict__ gather_ids, const float* __restrict__ u,
-    const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rowend, const int32_t* __restrict__ col,
-    const int32_t* __restrict__ n_rows_dev, float slope, const float* __restrict__ dz, int64_t head_stride,
-    float* __restrict__ edge_scr, float* __restrict__ du) {
-  constexpr int U = 4;                                  // feature rows in flight per wave (first sweep)
-  constexpr int U2 = (V * H * (sizeof(T) == 2 ? 2 : 4) > 12) ? 4 : 8;  // ... second sweep (no logits to hold)
-  constexpr int NV = U * 2 * H, NC = (NV + 15) / 16;    // (logit, d alpha) per head and edge of a group
-  typedef RawRow4<T> RR;
-  typedef typename RR::type raw_t;
-  const int lane = threadIdx.x & 63;
-  const int wave = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-  const int waves = (int)(((int64_t)gridDim.x * blockDim.x) >> 6);
-  const int n_rows = *n_rows_dev;
-  const float4_t zero4 = {0.f, 0.f, 0.f, 0.f};
-  auto leaky = [&](float v) { return v > 0.f ? v : slope * v; };
-  auto dot4 = [](const float4_t& a, const float4_t& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; };
-  auto lane_value = [](float v, int from) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), from));
-  };
-  int el[V];
-  bool on[V];
-  float4_t us[H][V], acc_s[H][V], acc_d[H][V];
-#pragma unroll
-  for (int v = 0; v < V; ++v) {
-    el[v] = (v * 64 + lane) * 4;
-    on[v] = el[v] < d;
-#pragma unroll
-    for (int h = 0; h < H; ++h) {
-      us[h][v] = on[v] ? *reinterpret_cast<const float4_t*>(u + (int64_t)h * d + el[v]) : zero4;
-      acc_s[h][v] = zero4;
-      acc_d[h][v] = zero4;
-    }
-  }
-  for (int i = wave; i < n_rows; i += waves) {
-    const int e0 = rowptr[i], m = rowend[i] - e0;
-    const uint32_t self_gid = gather_ids[i];
-    float4_t xs[V], dzv[H][V];
-    float sd[H], das[H], mx[H], den[H], pre_self[H];
-    {
-      float pv[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) pv[k] = 0.f;
-      const T* row = src + (int64_t)self_gid * d;
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        xs[v] = on[v] ? RR::f4(RR::load(row, el[v])) : zero4;
-#pragma unroll
-        for (int h = 0; h < H; ++h) {
-          dzv[h][v] = on[v] ? *reinterpret_cast<const float4_t*>(dz + h * head_stride + (int64_t)i * d + el[v]) : zero4;
-          const float4_t udv = on[v] ? *reinterpret_cast<const float4_t*>(u + (int64_t)(H + h) * d + el[v]) : zero4;
-          pv[h] += dot4(xs[v], us[h][v]);
-          pv[H + h] += dot4(xs[v], udv);
-          pv[2 * H + h] += dot4(xs[v], dzv[h][v]);
-        }
-      }
-      const float tot = gigl_wave_reduce16(pv);  // (3H <= 12 values)
-#pragma unroll
-      for (int h = 0; h < H; ++h) {
-        const float fs = lane_value(tot, h << 2);
-        sd[h] = lane_value(tot, (H + h) << 2);
-        das[h] = lane_value(tot, (2 * H + h) << 2);
-        pre_self[h] = fs + sd[h];
-        mx[h] = leaky(pre_self[h]);
-        den[h] = 1.f;
-      }
-    }
-    // a row whose dz is all zero adds nothing (padding rows, rows no root depends on): skipped, wave-uniformly
-    {
-      bool nz = false;
-#pragma unroll
-      for (int h = 0; h < H; ++h)
-#pragma unroll
-        for (int v = 0; v < V; ++v) nz |= dzv[h][v].x != 0.f || dzv[h][v].y != 0.f || dzv[h][v].z != 0.f || dzv[h][v].w != 0.f;
-      if (__ballot(nz) == 0ull) continue;
-    }
-    // ---- sweep 1: logits and d alpha of every edge -> edge_scr[e][h] = (zl, d alpha); running max / denominator
-    for (int c0 = 0; c0 < m; c0 += 64) {
-      const int mm = min(64, m - c0);
-      uint32_t gid = self_gid;
-      bool take = false;
-      if (lane < mm) {
-        const int j = col[e0 + c0 + lane];
-        take = j != i;
-        gid = gather_ids[j];
-      }
-      const unsigned long long keep = __ballot(take);
-      for (int e = 0; e < mm; e += U) {
-        raw_t x[U][V];
-        bool live[U];
-#pragma unroll
-        for (int t = 0; t < U; ++t) {
-          live[t] = e + t < mm && ((keep >> (e + t)) & 1ull);
-          const T* row = src + (int64_t)__shfl(gid, (e + t) & 63, 64) * d;
-#pragma unroll
-          for (int v = 0; v < V; ++v) x[t][v] = (live[t] && on[v]) ? RR::load(row, el[v]) : RR::zero();
-        }
-        float vals[NC * 16];
-#pragma unroll
-        for (int cc = 0; cc < NC; ++cc) {
-          float pv[16];
-#pragma unroll
-          for (int k = 0; k < 16; ++k) {
-            const int idx = cc * 16 + k;  // = (t * H + h) * 2 + which
-            float a = 0.f;
-            if (idx < NV) {
-              const int t = idx / (2 * H), h = (idx / 2) % H, which = idx & 1;
-#pragma unroll
-              for (int v = 0; v < V; ++v) a += dot4(RR::f4(x[t][v]), which ? dzv[h][v] : us[h][v]);
-            }
-            pv[k] = a;
-          }
-          const float tot = gigl_wave_reduce16(pv);
-#pragma unroll
-          for (int k = 0; k < 16; ++k) vals[cc * 16 + k] = lane_value(tot, k << 2);
-        }
-#pragma unroll
-        for (int t = 0; t < U; ++t) {
-          if (!live[t]) continue;
-#pragma unroll
-          for (int h = 0; h < H; ++h) {
-            const float zl = leaky(vals[(t * H + h) * 2] + sd[h]), da = vals[(t * H + h) * 2 + 1];
-            const float nm = fmaxf(mx[h], zl);
-            den[h] = den[h] * __expf(mx[h] - nm) + __expf(zl - nm);
-            mx[h] = nm;
-            if (lane == 0) {
-              float* sp = edge_scr + ((int64_t)(e0 + c0 + e + t) * H + h) * 2;
-              sp[0] = zl;
-              sp[1] = da;
-            }
-          }
-        }
-      }
-    }
-    // ---- S = sum_e alpha_e d alpha_e (edges: a lane per edge of a chunk; plus the self loop)
-    float inv[H], al_self[H], S[H], dpre_self[H], sum_dpre[H];
-#pragma unroll
-    for (int h = 0; h < H; ++h) {
-      inv[h] = 1.0f / (den[h] + 1e-16f);
-      al_self[h] = __expf(leaky(pre_self[h]) - mx[h]) * inv[h];
-      S[h] = al_self[h] * das[h];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // (lane 0's parked scalars, read below by their lanes)
-    for (int c0 = 0; c0 < m; c0 += 64) {
-      const int mm = min(64, m - c0);
-      const bool mine = lane < mm && col[e0 + c0 + lane] != i;
-#pragma unroll
-      for (int h = 0; h < H; ++h) {
-        float part = 0.f;
-        if (mine) {
-          const float* sp = edge_scr + ((int64_t)(e0 + c0 + lane) * H + h) * 2;
-          part = __expf(sp[0] - mx[h]) * inv[h] * sp[1];
-        }
-        S[h] += wave_sum_dpp(part);
-      }
-    }
-#pragma unroll
-    for (int h = 0; h < H; ++h) {
-      dpre_self[h] = al_self[h] * (das[h] - S[h]) * (pre_self[h] > 0.f ? 1.f : slope);
-      sum_dpre[h] = dpre_self[h];
-    }
-    // ---- sweep 2: d us += dpre_e x_e
-    for (int c0 = 0; c0 < m; c0 += 64) {
-      const int mm = min(64, m - c0);
-      uint32_t gid = self_gid;
-      bool take = false;
-      if (lane < mm) {
-        const int j = col[e0 + c0 + lane];
-        take = j != i;
-        gid = gather_ids[j];
-      }
-      float dpre[H];
-#pragma unroll
-      for (int h = 0; h < H; ++h) {
-        dpre[h] = 0.f;
-        if (take) {
-          const float* sp = edge_scr + ((int64_t)(e0 + c0 + lane) * H + h) * 2;
-          const float zl = sp[0];
-          dpre[h] = __expf(zl - mx[h]) * inv[h] * (sp[1] - S[h]) * (zl > 0.f ? 1.f : slope);
-        }
-        sum_dpre[h] += wave_sum_dpp(dpre[h]);
-      }
-      const unsigned long long keep = __ballot(take);
-      for (int e = 0; e < mm; e += U2) {
-        raw_t x[U2][V];
-        bool live[U2];
-#pragma unroll
-        for (int t = 0; t < U2; ++t) {
-          live[t] = e + t < mm && ((keep >> (e + t)) & 1ull);
-          const T* row = src + (int64_t)__shfl(gid, (e + t) & 63, 64) * d;
-#pragma unroll
-          for (int v = 0; v < V; ++v) x[t][v] = (live[t] && on[v]) ? RR::load(row, el[v]) : RR::zero();
-        }
-#pragma unroll
-        for (int t = 0; t < U2; ++t) {
-          if (!live[t]) continue;
-#pragma unroll
-          for (int h = 0; h < H; ++h) {
-            const float dp = lane_value(dpre[h], (e + t) & 63);  // (a uniform lane: v_readlane, not an LDS permute)
-#pragma unroll
-            for (int v = 0; v < V; ++v) acc_s[h][v] += dp * RR::f4(x[t][v]);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int h = 0; h < H; ++h)
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        acc_s[h][v] += dpre_self[h] * xs[v];
-        acc_d[h][v] += sum_dpre[h] * xs[v];
-      }
-  }
-  // the workgroup's four waves add their sums in LDS first, in wave order, and one wave adds the total to `du`: every
-  // atomic lands on one of only 2 H d addresses, so their number — (workgroups) x 2 H d — is what this tail costs
-  __shared__ float4_t s_red[2 * H * V * 64];
-  const int wv = threadIdx.x >> 6;
-  for (int w = 0; w < 4; ++w) {
-    if (wv == w) {
-#pragma unroll
-      for (int h = 0; h < H; ++h)
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-          float4_t& rs = s_red[(h * V + v) * 64 + lane];
-          float4_t& rd = s_red[((H + h) * V + v) * 64 + lane];
-          rs = w == 0 ? acc_s[h][v] : rs + acc_s[h][v];
-          rd = w == 0 ? acc_d[h][v] : rd + acc_d[h][v];
-        }
-    }
-    __syncthreads();
-  }
-  if (wv != 0) return;
-#pragma unroll
-  for (int h = 0; h < 2 * H; ++h)
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      if (!on[v]) continue;
-      const float4_t t = s_red[(h * V + v) * 64 + lane];
-      float* pu = du + (int64_t)h * d + el[v];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (t[q] != 0.f) atomicAdd(pu + q, t[q]);
-    }
-}
-
-// ---- the same backward in ONE sweep over the source rows (round 6).  The two-sweep kernel reads every source row twice
-// because dpre_e = alpha_e (d alpha_e - S) leaky'(pre_e) needs S = sum_e alpha_e d alpha_e — known only after the row's last
-// edge.  But  sum_e dpre_e x_e = ( sum_e w_e l_e d alpha_e x_e  -  S sum_e w_e l_e x_e ) / den   with w_e = exp(zl_e - max),
+// One wave per destination row (the forward's lane layout), ONE sweep over the row's edges (round 6; two sweeps before,
+// parking every edge's logit and d alpha in scratch).  S is known only after the row's last edge, but
+//   sum_e dpre_e x_e = ( sum_e w_e l_e d alpha_e x_e  -  S sum_e w_e l_e x_e ) / den   with w_e = exp(zl_e - max),
 // l_e = leaky'(pre_e), den = sum_e w_e, S = (sum_e w_e d alpha_e) / den: two vector accumulators A, B (and three scalars) per
 // head, kept relative to the RUNNING maximum and rescaled when it grows — the online softmax of the forward applied to its
-// own backward.  Each row is read once; no per-edge scalars are parked (edge_scr is not used).  The self loop is the first
-// "edge" (x_e = x_i, w = 1).  Same lane layout, same cross-row accumulation and final atomics as the two-sweep kernel.
+// own backward.  Each row is read once, each edge's logit and d alpha formed from the source row as it is read (reduced
+// together, gigl_wave_reduce16).  The self loop is the first "edge" (x_e = x_i, w = 1).  A wave keeps its d us / d ud sums
+// in registers over all its rows and adds them to `du` once, at the end (fp32 atomics).
 template <typename T, int V, int H>
 __global__ __launch_bounds__(256) void gat_input_backward_onepass_kernel(
     const T* __restrict__ src, int d, const uint32_t* __restrict__ gather_ids, const float* __restrict__ u,
@@ -4306,10 +3484,8 @@ int32_t gigl_sage_project_features(gigl_ctx* ctx, gigl_feat* feat, const float* 
   // two staging buffers for an fp16 table: chunk c + 1 is widened while chunk c is multiplied? (one stream: they run
   // back to back; two buffers only keep the conversion of c + 1 from overwriting the operand of c's product)
   const int64_t cm = n < chunk ? n : chunk;
-  // fp16 rows go through the projection as stored when K % 4 == 0 (GIGL_PROJECT_WIDEN=1, or GIGL_LINEAR_EXACT: the
-  // widened copy + the fp32 path, for comparison)
-  const bool half_direct = feat->dtype == GIGL_DTYPE_F16 && (d & 3) == 0 && !getenv("GIGL_PROJECT_WIDEN") &&
-                           !getenv("GIGL_LINEAR_EXACT");
+  // fp16 rows go through the projection as stored when K % 4 == 0 (GIGL_LINEAR_EXACT: the widened copy + the fp32 path)
+  const bool half_direct = feat->dtype == GIGL_DTYPE_F16 && (d & 3) == 0 && !getenv("GIGL_LINEAR_EXACT");
   // (cnt: [0..1] row counts, [2..4] hs scales, [6..7] the scale kernel's running maximum + ticket: zero to begin with)
   if (hipMalloc((void**)&cnt, 64) != hipSuccess || hipMemsetAsync(cnt, 0, 64, st) != hipSuccess ||
       (feat->dtype == GIGL_DTYPE_F16 && !half_direct && hipMalloc((void**)&stage, (size_t)cm * d * 4 + 16) != hipSuccess)) {
@@ -4609,8 +3785,7 @@ int32_t gigl_gat_aggregate_backward(gigl_ctx* ctx, const float* h, const float* 
                        ctx->stream, edge_attr, edge_dim, att_edge_folded, heads, cap_edges, a_edge);
   // (few rows — the roots' layer of a training step — are shared by several waves each; not with the message term, whose
   // z_out rows are written whole by one wave)
-  static const bool one_wave = getenv("GIGL_GAT_BWD_ONE_WAVE") != nullptr;  // (A/B knob: a wave per row, as before round 5)
-  const int wpr = (u_msg || one_wave) ? 1 : (rows_cap >= 32768 ? 1 : (rows_cap >= 8192 ? 2 : (rows_cap >= 2048 ? 4 : 8)));
+  const int wpr = u_msg ? 1 : (rows_cap >= 32768 ? 1 : (rows_cap >= 8192 ? 2 : (rows_cap >= 2048 ? 4 : 8)));
   int64_t ablocks = (nodes_cap + 3) / 4, gblocks = (rows_cap * wpr + 3) / 4;
   if (ablocks > 256 * 32) ablocks = 256 * 32;
   if (gblocks > 256 * 32) gblocks = 256 * 32;
@@ -4881,12 +4056,8 @@ int32_t gigl_linear_weight_grad(gigl_ctx* ctx, const float* dy, const float* a, 
   float* partb = db ? (float*)gigl_arena_alloc(ctx, chunks * n * 4) : nullptr;
   if (!part || (db && !partb)) return gigl_fail(ctx, GIGL_E_OOM, "arena exhausted");
   const dim3 grid((unsigned)chunks, (unsigned)((n + 63) / 64), (unsigned)((k + 63) / 64));
-  static const bool valu = getenv("GIGL_WGRAD_VALU") != nullptr;  // (A/B knob: the fp32 FMA kernel)
-  if (valu)
-    hipLaunchKernelGGL(linear_weight_grad_kernel, grid, dim3(256), 0, ctx->stream, dy, a, relu_y, m_dev, n, k, part, partb, rcw);
-  else
-    hipLaunchKernelGGL(linear_weight_grad_mfma_kernel, grid, dim3(256), 0, ctx->stream, dy, a, relu_y, m_dev, n, k, part, partb,
-                       rcw);
+  hipLaunchKernelGGL(linear_weight_grad_mfma_kernel, grid, dim3(256), 0, ctx->stream, dy, a, relu_y, m_dev, n, k, part, partb,
+                     rcw);
   hipLaunchKernelGGL(linear_weight_grad_reduce_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, ctx->stream, part,
                      partb, m_dev, nk, n, dw, db, rcw);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
@@ -5115,37 +4286,24 @@ static int32_t linear_tiled_strided(gigl_ctx* ctx, const float* a_tiled, const f
   return GIGL_OK;
 }
 
-// ---- the fused two-layer projection (linear_fused2_kernel) and its companions
+// ---- the fused two-layer projection (linear_fused2x_kernel) and its companions
 bool gigl_fused2_shape_ok(int32_t d0, int32_t hid, int32_t n_out) {
   return hid == F2_HID && n_out >= 1 && n_out <= F2_N2 / 2 && (d0 & 3) == 0 && d0 >= 4;
 }
-// [W2's planes as the round-5 kernel reads them | W1 chunk images | W2 round images]  (k1 = the first product's K)
-static int64_t fused2_w2h_legacy_bytes() { return (int64_t)2 * F2_N2 * F2_HID * 2; }
+// [W1 chunk images | W2 round images]  (k1 = the first product's K)
 static int64_t fused2_img1_bytes(int32_t k1) { return (int64_t)2 * ((k1 + 31) / 32) * F2_IMG1 * 2; }
-int64_t gigl_fused2_w2h_bytes(int32_t k1) { return fused2_w2h_legacy_bytes() + fused2_img1_bytes(k1) + (int64_t)2 * 4 * F2_IMG2 * 2; }
-static int fused2_variant() {
-  static const int variant = [] {
-    const char* e = getenv("GIGL_F2_VARIANT");
-    return e ? atoi(e) : 7;  // 0: linear_fused2_kernel (round 5), 4: linear_fused2w_kernel, 7: linear_fused2x_kernel, 8: 7 + LDS-direct
-  }();
-  return variant;
-}
+int64_t gigl_fused2_w2h_bytes(int32_t k1) { return fused2_img1_bytes(k1) + (int64_t)2 * 4 * F2_IMG2 * 2; }
 int32_t gigl_fused2_row_floats() { return F2_N2; }
-int32_t gigl_fused2_planes() { return fused2_variant() >= 7 ? 1 : 2; }
 
 int32_t gigl_fused2_prepare(gigl_ctx* ctx, const float* hs_dev, const float* b1, const float* w1, const float* w2, int32_t n_out,
                             int32_t k1, float* f2, void* w2h) {
   // (f2: 16 floats, zero-initialised by the caller once: [4..6] are the scale kernel's accumulators + ticket)
   hipLaunchKernelGGL(fused2_scale_kernel, dim3(24), dim3(256), 0, ctx->stream, hs_dev, b1, w2, n_out * 2 * F2_HID, k1, f2);
-  if (fused2_variant() >= 4) {
-    _Float16* img1 = reinterpret_cast<_Float16*>(reinterpret_cast<char*>(w2h) + fused2_w2h_legacy_bytes());
-    _Float16* img2 = reinterpret_cast<_Float16*>(reinterpret_cast<char*>(img1) + fused2_img1_bytes(k1));
-    const int n = 2 * ((k1 + 31) / 32) * 128 * 32 + 2 * 4 * F2_N2 * 32;
-    hipLaunchKernelGGL(fused2_images_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, hs_dev,
-                       (const float*)f2, w1, k1, w2, n_out, img1, img2);
-  } else
-  hipLaunchKernelGGL(fused2_split_kernel, dim3((F2_N2 * F2_HID + 255) / 256), dim3(256), 0, ctx->stream, f2, w2, n_out,
-                     (_Float16*)w2h);
+  _Float16* img1 = reinterpret_cast<_Float16*>(w2h);
+  _Float16* img2 = reinterpret_cast<_Float16*>(reinterpret_cast<char*>(w2h) + fused2_img1_bytes(k1));
+  const int n = 2 * ((k1 + 31) / 32) * 128 * 32 + 2 * 4 * F2_N2 * 32;
+  hipLaunchKernelGGL(fused2_images_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, hs_dev,
+                     (const float*)f2, w1, k1, w2, n_out, img1, img2);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -5160,74 +4318,37 @@ int32_t gigl_hs_chain_update(gigl_ctx* ctx, const float* hs_prev, const float* b
   return GIGL_OK;
 }
 
-int32_t gigl_linear_fused2(gigl_ctx* ctx, const float* a_tiled, const float* w, const float* bias, const int32_t* m_dev,
-                           int64_t m_cap, int32_t k, float* y2, int64_t plane_stride, const float* self_src,
-                           const uint32_t* self_ids, int32_t d_mean, int32_t self_ld, const float* hs_scale,
-                           const float* f2, const void* w2h, const int32_t* n_root_rows) {
-  GIGL_REQUIRE(ctx, a_tiled && w && m_dev && y2 && self_src && hs_scale && f2 && w2h && (k & 3) == 0 && d_mean > 0 &&
+int32_t gigl_linear_fused2(gigl_ctx* ctx, const float* a_tiled, const float* bias, const int32_t* m_dev, int64_t m_cap,
+                           int32_t k, float* y2, const float* self_src, const uint32_t* self_ids, int32_t d_mean,
+                           int32_t self_ld, const float* hs_scale, const float* f2, const void* w2h,
+                           const int32_t* n_root_rows) {
+  GIGL_REQUIRE(ctx, a_tiled && m_dev && y2 && self_src && hs_scale && f2 && w2h && (k & 3) == 0 && d_mean > 0 &&
                         (d_mean & 3) == 0 && d_mean < k && self_ld >= k - d_mean && (((uintptr_t)bias) & 15) == 0,
                "bad arguments");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (m_cap == 0) return GIGL_OK;
   gigl_prof_scope ps(ctx, GIGL_K_LINEAR);
-  const int64_t bm = (m_cap + 127) / 128;
-  const int variant = fused2_variant();
-  if (variant >= 4) {
-    const _Float16* img1 = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(w2h) + fused2_w2h_legacy_bytes());
-    const _Float16* img2 = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(img1) + fused2_img1_bytes(k));
-    static const int ablate = [] {
-      const char* e = getenv("GIGL_F2_ABLATE");
-      return e ? atoi(e) : 0;
-    }();
-#define GIGL_F2W_LAUNCH(AD, WPE, DBG)                                                                                         \
-  hipLaunchKernelGGL((linear_fused2w_kernel<AD, WPE, DBG>), dim3((unsigned)(bm * 2)), dim3(256), 0, ctx->stream, a_tiled, bias, \
-                     m_dev, k, y2, plane_stride, (d_mean + 31) / 32, self_src, self_ids, d_mean, self_ld, hs_scale, f2, img1,  \
-                     img2, ablate)
-    if (variant >= 7) {
-#define GIGL_F2X_LAUNCH(DBG, GLDS, GLDS2)                                                                                   \
-  hipLaunchKernelGGL((linear_fused2x_kernel<DBG, GLDS, GLDS2>), dim3((unsigned)bm), dim3(256), 0, ctx->stream, a_tiled, bias, \
-                     m_dev, k, y2, (d_mean + 31) / 32, self_src, self_ids, d_mean, self_ld, hs_scale, f2, img1, img2, ablate, \
-                     n_root_rows)
-      if (ablate) GIGL_F2X_LAUNCH(true, false, true);
-      else if (variant == 8) GIGL_F2X_LAUNCH(false, true, true);
-      else if (variant == 9) GIGL_F2X_LAUNCH(false, false, false);
-      else GIGL_F2X_LAUNCH(false, false, true);
-#undef GIGL_F2X_LAUNCH
-    } else if (ablate) GIGL_F2W_LAUNCH(1, 3, true);
-    else GIGL_F2W_LAUNCH(1, 3, false);  // (two A chunks in flight at two waves per SIMD: 6.8 us per step against 5.9)
-#undef GIGL_F2W_LAUNCH
-    GIGL_HIP_CHECK(ctx, hipGetLastError());
-    return GIGL_OK;
-  }
-#define GIGL_F2_LAUNCH(PD, WPE)                                                                                              \
-  hipLaunchKernelGGL((linear_fused2_kernel<PD, WPE>), dim3((unsigned)(bm * 2)), dim3(256), 0, ctx->stream, a_tiled, w, bias, \
-                     m_dev, k, y2, plane_stride, (d_mean + 31) / 32, self_src, self_ids, d_mean, self_ld, hs_scale, f2,      \
-                     (const _Float16*)w2h)
-  // (measured and dropped, profiles/r06v_*: 2 / 3 chunks in flight at two waves per SIMD: 7.6 / 7.8 us per step against 6.3)
-  GIGL_F2_LAUNCH(1, 3);
-#undef GIGL_F2_LAUNCH
+  const _Float16* img1 = reinterpret_cast<const _Float16*>(w2h);
+  const _Float16* img2 = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(w2h) + fused2_img1_bytes(k));
+  hipLaunchKernelGGL(linear_fused2x_kernel, dim3((unsigned)((m_cap + 127) / 128)), dim3(256), 0, ctx->stream, a_tiled, bias,
+                     m_dev, k, y2, (d_mean + 31) / 32, self_src, self_ids, d_mean, self_ld, hs_scale, f2, img1, img2,
+                     n_root_rows);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
 
-int32_t gigl_sage_fused_out(gigl_ctx* ctx, const float* p, int64_t plane_stride, const int32_t* rowptr,
-                            const int32_t* rowend, const int32_t* col, const int32_t* root_local, int32_t b,
-                            int32_t n_out, const float* bias, int32_t act, int32_t aggr, const int32_t* meta, float* out) {
+int32_t gigl_sage_fused_out(gigl_ctx* ctx, const float* p, const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
+                            const int32_t* root_local, int32_t b, int32_t n_out, const float* bias, int32_t act,
+                            int32_t aggr, const int32_t* meta, float* out) {
   GIGL_REQUIRE(ctx, aggr == GIGL_AGGR_MEAN || aggr == GIGL_AGGR_SUM, "the fused last layer needs a linear reduction");
   if (b == 0) return GIGL_OK;
   gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
   const dim3 g((unsigned)(((int64_t)b + 3) / 4)), blk(256);
-  const bool one = fused2_variant() >= 7;  // (linear_fused2x_kernel: whole p rows, one plane)
-#define GIGL_FOUT(OP, PL)                                                                                                  \
-  hipLaunchKernelGGL((sage_fused_out_kernel<OP, PL>), g, blk, 0, ctx->stream, p, plane_stride, rowptr, rowend, col, root_local, \
-                     b, n_out, bias, act, meta, out)
-  if (aggr == GIGL_AGGR_MEAN) {
-    if (one) GIGL_FOUT(GIGL_AGGR_MEAN, 1);
-    else GIGL_FOUT(GIGL_AGGR_MEAN, 2);
-  } else {
-    if (one) GIGL_FOUT(GIGL_AGGR_SUM, 1);
-    else GIGL_FOUT(GIGL_AGGR_SUM, 2);
-  }
+#define GIGL_FOUT(OP)                                                                                                     \
+  hipLaunchKernelGGL((sage_fused_out_kernel<OP>), g, blk, 0, ctx->stream, p, rowptr, rowend, col, root_local, b, n_out, bias, \
+                     act, meta, out)
+  if (aggr == GIGL_AGGR_MEAN) GIGL_FOUT(GIGL_AGGR_MEAN);
+  else GIGL_FOUT(GIGL_AGGR_SUM);
 #undef GIGL_FOUT
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
@@ -5427,10 +4548,10 @@ int32_t gigl_gat_input_aggregate(gigl_ctx* ctx, const void* src, int32_t src_dty
 int32_t gigl_gat_input_aggregate_backward(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d,
                                           const uint32_t* gather_ids, const float* u, int32_t heads, float negative_slope,
                                           const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
-                                          const int32_t* n_rows_dev, int64_t rows_cap, const float* dz, float* edge_scratch,
-                                          float* du) {
+                                          const int32_t* n_rows_dev, int64_t rows_cap, const float* dz,
+                                          float* /* edge_scratch: unused */, float* du) {
   if (!ctx) return GIGL_E_INVALID_ARG;
-  GIGL_REQUIRE(ctx, src && gather_ids && u && rowptr && rowend && col && n_rows_dev && dz && edge_scratch && du, "null argument");
+  GIGL_REQUIRE(ctx, src && gather_ids && u && rowptr && rowend && col && n_rows_dev && dz && du, "null argument");
   GIGL_REQUIRE(ctx, d > 0 && rows_cap >= 0, "bad sizes");
   int32_t rc = gat_input_shape_ok(ctx, d, heads, src_dtype, "gigl_gat_input_aggregate_backward");
   if (rc != GIGL_OK) return rc;
@@ -5443,18 +4564,9 @@ int32_t gigl_gat_input_aggregate_backward(gigl_ctx* ctx, const void* src, int32_
   const float slope = negative_slope;
   int64_t blocks = (rows_cap + 3) / 4;
   if (blocks > 256 * 2) blocks = 256 * 2;  // (two workgroups per CU fill its registers; fewer workgroups = fewer final atomics)
-  // (A/B knob: GIGL_GAT_BWD_TWO_SWEEPS=1 keeps the two-sweep kernel — every source row read twice, the edges' logits parked)
-  static const bool two_sweeps = getenv("GIGL_GAT_BWD_TWO_SWEEPS") != nullptr;
 #define GIGL_GAT_BW(TT, PP, HH)                                                                                        \
-  do {                                                                                                                  \
-    if (two_sweeps)                                                                                                     \
-      hipLaunchKernelGGL((gat_input_backward_kernel<TT, PP, HH>), dim3((unsigned)blocks), dim3(256), 0, st,            \
-                         (const TT*)src, d, gather_ids, u, rowptr, rowend, col, n_rows_dev, slope, dz, head_stride,     \
-                         edge_scratch, du);                                                                            \
-    else                                                                                                                \
-      hipLaunchKernelGGL((gat_input_backward_onepass_kernel<TT, PP, HH>), dim3((unsigned)blocks), dim3(256), 0, st,    \
-                         (const TT*)src, d, gather_ids, u, rowptr, rowend, col, n_rows_dev, slope, dz, head_stride, du); \
-  } while (0)
+  hipLaunchKernelGGL((gat_input_backward_onepass_kernel<TT, PP, HH>), dim3((unsigned)blocks), dim3(256), 0, st,        \
+                     (const TT*)src, d, gather_ids, u, rowptr, rowend, col, n_rows_dev, slope, dz, head_stride, du)
 #define GIGL_GAT_BW_P(TT, HH)                                                                                          \
   do {                                                                                                                  \
     if (P == 1) GIGL_GAT_BW(TT, 1, HH);                                                                                \

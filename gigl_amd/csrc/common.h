@@ -188,12 +188,12 @@ int32_t gigl_gat_input_layer_fused_hs(gigl_ctx* ctx, const void* src, int32_t sr
                                       float negative_slope, const int32_t* rowptr, const int32_t* rowend,
                                       const int32_t* col, const int32_t* n_rows_dev, int64_t rows_cap, const float* bias,
                                       int32_t act, float* scratch, float* out, const float* hs_scale);
-// The fused two-layer projection (agg.hip, linear_fused2_kernel): layer 0's [mean | self] projection (half split, two-source
+// The fused two-layer projection (agg.hip, linear_fused2x_kernel): layer 0's [mean | self] projection (half split, two-source
 // tiled operand) with the LAST layer's [W_l | W_r] applied to the hidden rows before they leave the workgroup — y2 =
-// [2 K-split partial planes][rows][gigl_fused2_row_floats()] of p = [W_l h | W_r h]; gigl_sage_fused_out is the last
-// layer over those rows (one reduction + self half + bias per root, written straight into the caller's `out`);
-// gigl_fused2_prepare (per run, after gigl_hs_scale_update on the same stream) finds the second product's scales and
-// lays out W2's fp16 planes.  gigl_fused2_shape_ok: hidden width 256, 2 * out <= row floats, d0 % 4 == 0.
+// [rows][gigl_fused2_row_floats()] of p = [W_l h | W_r h]; gigl_sage_fused_out is the last layer over those rows (one
+// reduction + self half + bias per root, written straight into the caller's `out`); gigl_fused2_prepare (per run, after
+// gigl_hs_scale_update on the same stream) finds the second product's scales and lays out W1's and W2's fp16 images in
+// w2h (gigl_fused2_w2h_bytes).  gigl_fused2_shape_ok: hidden width 256, 2 * out <= row floats, d0 % 4 == 0.
 // half-split scales of a layer >= 1 from the previous layer's (its outputs are bounded by K max|W| max|a| + max|b|): hs_out
 // = {s_h, s_w, 1 / (s_h s_w)} for gigl_linear_tiled(.., hs_scale); fan > 1 under a sum reduction.  Per run, on the stream.
 int32_t gigl_hs_chain_update(gigl_ctx* ctx, const float* hs_prev, const float* b_prev, int32_t n_b, int32_t k_prev, float fan,
@@ -201,17 +201,16 @@ int32_t gigl_hs_chain_update(gigl_ctx* ctx, const float* hs_prev, const float* b
 bool gigl_fused2_shape_ok(int32_t d0, int32_t hid, int32_t n_out);
 int64_t gigl_fused2_w2h_bytes(int32_t k1);
 int32_t gigl_fused2_row_floats();
-int32_t gigl_fused2_planes();  // partial p planes per node: 1 (linear_fused2x_kernel, whole rows) or 2 (K-split over the hidden tiles)
 int32_t gigl_fused2_prepare(gigl_ctx* ctx, const float* hs_dev, const float* b1, const float* w1, const float* w2, int32_t n_out,
                             int32_t k1, float* f2, void* w2h);
-int32_t gigl_linear_fused2(gigl_ctx* ctx, const float* a_tiled, const float* w, const float* bias, const int32_t* m_dev,
-                           int64_t m_cap, int32_t k, float* y2, int64_t plane_stride, const float* self_src,
-                           const uint32_t* self_ids, int32_t d_mean, int32_t self_ld, const float* hs_scale,
-                           const float* f2, const void* w2h, const int32_t* n_root_rows = nullptr);
+int32_t gigl_linear_fused2(gigl_ctx* ctx, const float* a_tiled, const float* bias, const int32_t* m_dev, int64_t m_cap,
+                           int32_t k, float* y2, const float* self_src, const uint32_t* self_ids, int32_t d_mean,
+                           int32_t self_ld, const float* hs_scale, const float* f2, const void* w2h,
+                           const int32_t* n_root_rows = nullptr);
 // (n_root_rows: DEVICE count of the leading rows that are roots — only their W_r half is ever read; NULL: every row's)
-int32_t gigl_sage_fused_out(gigl_ctx* ctx, const float* p, int64_t plane_stride, const int32_t* rowptr,
-                            const int32_t* rowend, const int32_t* col, const int32_t* root_local, int32_t b,
-                            int32_t n_out, const float* bias, int32_t act, int32_t aggr, const int32_t* meta, float* out);
+int32_t gigl_sage_fused_out(gigl_ctx* ctx, const float* p, const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
+                            const int32_t* root_local, int32_t b, int32_t n_out, const float* bias, int32_t act,
+                            int32_t aggr, const int32_t* meta, float* out);
 bool gigl_half_split_enabled();  // (GIGL_GEMM_SPLIT=bf16 keeps every projection on the bf16 planes)
 int32_t gigl_dev_absmax_f32(gigl_ctx* ctx, const float* p, int64_t n, float* out);  // synchronises the ctx's stream
 int32_t gigl_feat_absmax(gigl_ctx* ctx, gigl_feat* feat, float* out);

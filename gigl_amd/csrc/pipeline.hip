@@ -79,16 +79,16 @@ struct gigl_sage_plan {
   bool tiled = false;
   bool two_source = false;  // the projection takes the self half of [mean | self] from the source rows (no self copy)
   float* hbuf[2] = {nullptr, nullptr};  // ping-pong [act_rows][max_out]
-  // fused two-layer projection (agg.hip linear_fused2_kernel; two-layer SAGE, hidden 256, 2 * out <= 96, half-split first
+  // fused two-layer projection (agg.hip linear_fused2x_kernel; two-layer SAGE, hidden 256, 2 * out <= 96, half-split first
   // layer over an fp32 table): layer 0's projection applies the last layer's [W_l | W_r] to its hidden rows before they
-  // leave the workgroup — hbuf[0] then holds the two K-split planes of p = [W_l h | W_r h] ([2][act_rows][96]) instead of
-  // hidden rows, and the last layer is one reduction over p rows written straight into the caller's `out`
+  // leave the workgroup — hbuf[0] then holds p = [W_l h | W_r h] ([act_rows][96]) instead of hidden rows, and the last
+  // layer is one reduction over p rows written straight into the caller's `out`
   // layers >= 1 on the half split too (round 5): their operands are previous-layer outputs, bounded from the previous
   // layer's own scales (gigl_hs_chain_update) — hs_layer[l] = {s_h, s_w, 1 / (s_h s_w)} of layer l, chained from hs_dev
   float* hs_layer[GIGL_MAX_HOPS] = {nullptr};
   bool f2_ok = false;
   float* f2_dev = nullptr;  // {s_h, s_w2, 1 / (s_h s_w2)}: the second product's scales (gigl_fused2_prepare, per run)
-  void* w2h = nullptr;      // W2's fp16 planes
+  void* w2h = nullptr;      // W1's and W2's fp16 images (gigl_fused2_prepare)
   std::vector<void*> owned;
   // hipGraph replay
   bool use_graph = false;
@@ -245,9 +245,8 @@ int32_t enqueue_stage(gigl_sage_plan* p, int s, const uint32_t* roots, int32_t s
   if (s == n_stages(p) - 1) {
     const int dout = p->dims[L];
     if (fused2_on(p))  // the last layer over the p rows of the fused projection, one row per root, into `out`
-      return gigl_sage_fused_out(ctx, p->hbuf[0], (int64_t)p->act_rows * gigl_fused2_row_floats(), p->un.rowptr, p->un.rowend,
-                                 p->un.col, p->un.root_local, p->b, dout, p->bias[L - 1], p->act_last ? 1 : 0, p->aggr,
-                                 p->un.meta, out);
+      return gigl_sage_fused_out(ctx, p->hbuf[0], p->un.rowptr, p->un.rowend, p->un.col, p->un.root_local, p->b, dout,
+                                 p->bias[L - 1], p->act_last ? 1 : 0, p->aggr, p->un.meta, out);
     gigl_take_rows(ctx->stream, p->hbuf[(L - 1) & 1], p->un.root_local, p->b, dout, p->un.meta, out);
     GIGL_HIP_CHECK(ctx, hipGetLastError());
     return GIGL_OK;
@@ -344,9 +343,8 @@ int32_t enqueue_stage(gigl_sage_plan* p, int s, const uint32_t* roots, int32_t s
   if (l == 0 && fused2_on(p)) {
     int32_t rc = gigl_fused2_prepare(ctx, p->hs_dev, p->bias[0], p->w[0], p->w[1], p->dims[2], 2 * d, p->f2_dev, p->w2h);
     if (rc != GIGL_OK) return rc;
-    return gigl_linear_fused2(ctx, p->abuf, p->w[0], p->bias[0], n_rows, rows_cap, 2 * d, p->hbuf[0],
-                              (int64_t)p->act_rows * gigl_fused2_row_floats(), (const float*)p->feat->rows, p->un.nodes, d, d,
-                              hs_scale, p->f2_dev, p->w2h,
+    return gigl_linear_fused2(ctx, p->abuf, p->bias[0], n_rows, rows_cap, 2 * d, p->hbuf[0], (const float*)p->feat->rows,
+                              p->un.nodes, d, d, hs_scale, p->f2_dev, p->w2h,
                               getenv("GIGL_F2_ALL_WR") ? nullptr : p->un.meta + GIGL_META_LEVEL0);
   }
   if (two_src)
@@ -879,7 +877,7 @@ int32_t gigl_sage_plan_set_weights(gigl_sage_plan* p, const float* const* w, con
 
 int32_t gigl_sage_plan_half_split(gigl_sage_plan* p) { return p && p->hs0 ? 1 : 0; }
 
-int32_t gigl_sage_plan_fused_layers(gigl_sage_plan* p) { return p && fused2_on(p) ? gigl_fused2_planes() : 0; }
+int32_t gigl_sage_plan_fused_layers(gigl_sage_plan* p) { return p && fused2_on(p) ? 1 : 0; }
 
 int32_t gigl_sage_plan_set_aggr(gigl_sage_plan* p, int32_t aggr) {
   if (!p) return GIGL_E_INVALID_ARG;
@@ -1116,9 +1114,8 @@ int32_t gigl_sage_plan_set_graph_stream(gigl_sage_plan* p, void* hip_stream, int
 // two parts already share the GPU, the step follows the SUM of the launches more than the longer chain.)
 constexpr int TRAIN_WS = 3;
 // the input gradient of layers >= 1 by gigl_gather_mean_backward_transposed (every row written once, no cleared block, no
-// float atomics) when the hidden widths allow float4 rows; GIGL_TRAIN_BWD_ATOMIC=1 keeps the scatter (A/B)
+// float atomics) when the hidden widths allow float4 rows
 static bool train_bwd_gather(const int32_t* dims, int32_t hops) {
-  if (getenv("GIGL_TRAIN_BWD_ATOMIC")) return false;
   for (int l = 1; l < hops; ++l)
     if (dims[l] & 3) return false;
   return true;
@@ -1160,10 +1157,6 @@ struct gigl_sage_train_plan {
   int32_t part_rc[GIGL_MAX_HOPS] = {0};
   int32_t* ticket = nullptr;
   float** loss_slot = nullptr;
-  // the loss rows' sum (+ the step counter / halt flag) on a BRANCH of the captured layers: beside the last layer's weight
-  // gradient instead of in front of it, joined before Adam reads the counter
-  hipStream_t aux = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   float* gw[GIGL_MAX_HOPS] = {nullptr};
   float* gb[GIGL_MAX_HOPS] = {nullptr};
   float* mom[4 * GIGL_MAX_HOPS] = {nullptr};  // m_w, v_w, m_b, v_b per layer
@@ -1227,16 +1220,9 @@ int32_t train_enqueue_layers(gigl_sage_train_plan* t, int k) {
     hipLaunchKernelGGL(ce_roots_kernel, dim3((unsigned)((t->b + 3) / 4)), dim3(256), 0, st, (const float*)t->h[L - 1], width,
                        (const int32_t*)p->un.root_local, (const int64_t*)t->labels_buf, (const int32_t*)t->n_valid_buf, t->b,
                        (const int32_t*)p->un.meta, t->dh[L - 1], t->loss_rows);
-    hipStream_t ls = st;
-    if (fz && t->aux) {  // fork
-      GIGL_HIP_CHECK(ctx, hipEventRecord(t->ev_fork, st));
-      GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(t->aux, t->ev_fork, 0));
-      ls = t->aux;
-    }
-    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, ls, (const float*)t->loss_rows, t->b,
+    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->loss_rows, t->b,
                        (const int32_t*)t->n_valid_buf, t->loss, t->n_valid_buf + 1, (const int32_t*)p->un.meta,
                        t->n_valid_buf + 2, fz ? (float* const*)t->loss_slot : (float* const*)nullptr);
-    if (ls != st) GIGL_HIP_CHECK(ctx, hipEventRecord(t->ev_join, ls));
   }
   // ---- backward
   for (int l = L - 1; l >= 0; --l) {
@@ -1301,7 +1287,6 @@ int32_t train_enqueue_layers(gigl_sage_train_plan* t, int k) {
   ap.beta2 = t->beta2;
   ap.eps = t->eps;
   ap.wd = t->wd;
-  if (fz && t->aux) GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, t->ev_join, 0));  // join: Adam reads the step counter / halt flag
   hipLaunchKernelGGL(adam_kernel, fz ? dim3(208, (unsigned)ap.count) : dim3(256), dim3(256), 0, st, ap,
                      (const int32_t*)(t->n_valid_buf + 1), (const int32_t*)p->un.meta, (const int32_t*)(t->n_valid_buf + 2));
   GIGL_HIP_CHECK(ctx, hipGetLastError());
@@ -1388,12 +1373,6 @@ int32_t gigl_sage_train_plan_destroy(gigl_sage_train_plan* t) {
   }
   for (int k = 0; k < TRAIN_WS + 1; ++k)
     if (t->ev_layers[k]) hipEventDestroy(t->ev_layers[k]);
-  if (t->aux) {
-    hipStreamSynchronize(t->aux);
-    hipStreamDestroy(t->aux);
-  }
-  if (t->ev_fork) hipEventDestroy(t->ev_fork);
-  if (t->ev_join) hipEventDestroy(t->ev_join);
   for (void* q : t->owned) hipFree(q);
   for (int k = 0; k < TRAIN_WS; ++k)
     if (t->side[k]) gigl_ctx_destroy(t->side[k]);
@@ -1503,14 +1482,9 @@ int32_t gigl_sage_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat*
   if (ok && hipMemset(t->n_valid_buf, 0, 16) != hipSuccess) ok = false;
   t->fused_small = getenv("GIGL_TRAIN_PLAN_UNFUSED") == nullptr;
   if (t->fused_small && ok) {
-    // (measured, round 6: the sum on a BRANCH of the captured layers — forked after the loss rows, joined before Adam — took
-    // the step from 0.201 to 0.263 ms: a graph with a second branch is replayed through two queues with a barrier packet per
-    // edge.  GIGL_TRAIN_LOSS_BRANCH=1 turns it on for the A/B; off by default)
-    if (getenv("GIGL_TRAIN_LOSS_BRANCH") != nullptr &&
-        (hipStreamCreateWithFlags(&t->aux, hipStreamNonBlocking) != hipSuccess ||
-         hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming) != hipSuccess ||
-         hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming) != hipSuccess))
-      t->aux = nullptr;
+    // (measured, round 6: the loss sum on a BRANCH of the captured layers — forked after the loss rows, joined before Adam —
+    // took the step from 0.201 to 0.263 ms: a graph with a second branch is replayed through two queues with a barrier
+    // packet per edge.  The layers part stays one stream)
     t->ticket = (int32_t*)alloc(16);
     t->loss_slot = (float**)alloc(16);
     ok = t->ticket && t->loss_slot && hipMemset(t->ticket, 0, 16) == hipSuccess && hipMemset(t->loss_slot, 0, 16) == hipSuccess;
@@ -1683,8 +1657,7 @@ struct gigl_nablp_train_plan {
     float *u = nullptr, *du = nullptr;  // folded attention vectors [2H][d] and their gradient
     // forward state per encode: z [H][rows1][d], xw [rows1][c1], out_pre [b][c1]; backward scratch shared by both
     float *z[2] = {nullptr, nullptr}, *xw[2] = {nullptr, nullptr}, *out_pre[2] = {nullptr, nullptr};
-    float *dxw = nullptr, *ds = nullptr, *dd = nullptr, *alpha = nullptr, *dh0 = nullptr, *dh0s = nullptr, *dz = nullptr,
-          *edge_scratch = nullptr;
+    float *dxw = nullptr, *ds = nullptr, *dd = nullptr, *alpha = nullptr, *dh0 = nullptr, *dh0s = nullptr, *dz = nullptr;
     // (round 6, as the SAGE plans: GIGL_TRAIN_PLAN_UNFUSED=1 for the A/B) the projections' weight gradients stay per-chunk partial
     // sums — per encode: W1's, and W0's / b0's per head — added up inside the Adam kernel; W1^T and the heads' W0^T are laid
     // out once per step
@@ -1701,7 +1674,7 @@ struct gigl_nablp_train_plan {
     // so that nothing is shared with the main batch's encode while both run; folded together after the join
     struct Alt {
       float *alpha = nullptr, *dxw = nullptr, *ds = nullptr, *dd = nullptr, *dh0 = nullptr, *dh0s = nullptr, *dz = nullptr,
-            *edge_scratch = nullptr, *du = nullptr;
+            *du = nullptr;
       float* g[8] = {nullptr};
     } x;
   } gat;
@@ -2860,7 +2833,7 @@ int32_t gat_lp_backward(gigl_nablp_train_plan* t, int which) {
   auto& g = t->gat;
   float *s_alpha = alt ? g.x.alpha : g.alpha, *s_dxw = alt ? g.x.dxw : g.dxw, *s_ds = alt ? g.x.ds : g.ds,
         *s_dd = alt ? g.x.dd : g.dd, *s_dh0 = alt ? g.x.dh0 : g.dh0, *s_dh0s = alt ? g.x.dh0s : g.dh0s,
-        *s_dz = alt ? g.x.dz : g.dz, *s_edge = alt ? g.x.edge_scratch : g.edge_scratch, *s_du = alt ? g.x.du : g.du;
+        *s_dz = alt ? g.x.dz : g.dz, *s_du = alt ? g.x.du : g.du;
   float* const* gg = alt ? g.x.g : g.g;
   const int H = g.heads, C0 = g.c0, C1 = g.c1, d = g.d_in, HC = H * C0;
   const int64_t rows1 = gat_rows1(t, which);
@@ -2918,7 +2891,7 @@ int32_t gat_lp_backward(gigl_nablp_train_plan* t, int which) {
     if (rc != GIGL_OK) return rc;
   }
   rc = gigl_gat_input_aggregate_backward(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
-                                         p->un.rowend, p->un.col, n1, rows1, s_dz, s_edge, s_du);
+                                         p->un.rowend, p->un.col, n1, rows1, s_dz, nullptr, s_du);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return rc;
 }
@@ -3128,10 +3101,9 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
   g.dh0 = (float*)alloc((size_t)rows1_max * H * C0 * 4);
   g.dh0s = (float*)alloc((size_t)rows1_max * H * C0 * 4);
   g.dz = (float*)alloc((size_t)H * rows1_max * d * 4);
-  g.edge_scratch = (float*)alloc((size_t)2 * H * cap_edges * 4);
   const size_t wt_floats = std::max((size_t)C1 * H * C0, (size_t)C0 * d);
   t->wt = (float*)alloc(wt_floats * 4);
-  ok = ok && t->zero_base && g.u && g.dxw && g.ds && g.alpha && g.dh0 && g.dh0s && g.dz && g.edge_scratch && t->wt;
+  ok = ok && t->zero_base && g.u && g.dxw && g.ds && g.alpha && g.dh0 && g.dh0s && g.dz && t->wt;
   g.fused = getenv("GIGL_TRAIN_PLAN_UNFUSED") == nullptr;
   if (want_fork && ok) {  // the second encode's own scratch (its rows, its edges), a ctx with a stream of its own, the events
     const int64_t r1 = t->enc[1].rows_cap[0], ce1 = t->work[0].base[1]->un.cap_edges;
@@ -3142,8 +3114,7 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
     g.x.dh0 = (float*)alloc((size_t)r1 * H * C0 * 4);
     g.x.dh0s = (float*)alloc((size_t)r1 * H * C0 * 4);
     g.x.dz = (float*)alloc((size_t)H * r1 * d * 4);
-    g.x.edge_scratch = (float*)alloc((size_t)2 * H * ce1 * 4);
-    ok = g.x.dxw && g.x.ds && g.x.alpha && g.x.dh0 && g.x.dh0s && g.x.dz && g.x.edge_scratch && g.x.du &&
+    ok = g.x.dxw && g.x.ds && g.x.alpha && g.x.dh0 && g.x.dh0s && g.x.dz && g.x.du &&
          gigl_ctx_create(ctx->device, &t->actx) == GIGL_OK;
     for (int i = 0; i < 2 && ok; ++i)
       ok = hipEventCreateWithFlags(&t->ev_fork[i], hipEventDisableTiming) == hipSuccess &&

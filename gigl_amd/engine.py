@@ -954,11 +954,10 @@ class HipEngine:
         d = self.feat_dim
         assert dz.is_cuda and dz.is_contiguous() and tuple(dz.shape) == (heads, rows_cap, d) and dz.dtype == torch.float32
         du = torch.zeros((2 * heads, d), dtype=torch.float32, device=self.device)
-        scr = torch.empty(2 * heads * max(int(col.numel()), 1), dtype=torch.float32, device=self.device)
         p = lambda t: C.c_void_p(t.data_ptr())
         check(self._lib.gigl_gat_input_aggregate_backward(self._ctx, self._feat_ptr, self.feat_dtype, d, p(node_ids),
                                                           p(u_fold), heads, negative_slope, p(rowptr), p(rowend), p(col),
-                                                          p(n_rows_dev), rows_cap, p(dz), p(scr), p(du)), self._ctx)
+                                                          p(n_rows_dev), rows_cap, p(dz), None, p(du)), self._ctx)
         return du
 
     def gat_backward_epilogue(self, dh: torch.Tensor, ds: torch.Tensor, dd: torch.Tensor, xw: torch.Tensor,
@@ -1270,7 +1269,7 @@ class SagePlan:
         return bool(self._lib.gigl_sage_plan_fused_layers(self._plan))
 
     def fused_planes(self) -> int:
-        """partial planes of p rows the fused projection writes per node (0: layers apart; 1: whole rows; 2: K-split)"""
+        """planes of p rows the fused projection writes per node (0: layers apart; 1: one plane of whole rows)"""
         return int(self._lib.gigl_sage_plan_fused_layers(self._plan))
 
     def set_graph_stream(self, stream: Optional[torch.cuda.Stream]) -> None:

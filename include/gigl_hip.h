@@ -827,7 +827,7 @@ int32_t gigl_gat_input_layer(gigl_ctx* ctx, const void* src, int32_t src_dtype, 
  *                                      (z: DEVICE fp32 [heads][rows_cap][d], plain rows), alpha the layer's attention
  *   gigl_gat_input_aggregate_backward  given dz (same shape): du[0:heads] += d u_src, du[heads:2 heads] += d u_dst
  *                                      (du [2*heads][d] is ADDED to: zero it first; fp32 atomics).  The feature rows are
- *                                      inputs: no gradient.  edge_scratch: DEVICE fp32 [2 * heads * cap_edges].
+ *                                      inputs: no gradient.  edge_scratch: unused; may be NULL.
  * Every `col` entry is a local id translated through gather_ids (all rows numbered: a staged union graph).  Rows whose
  * dz is all zero are skipped.  PyG's autograd of GATConv reaches the same gradients through x W first; this order reads
  * each d-wide stored row per edge instead of projecting every source row (python/gigl/src/common/models/pyg/
@@ -1169,11 +1169,9 @@ int32_t gigl_sage_plan_set_projected_input(gigl_sage_plan* plan, const float* pr
  * GIGL_GEMM_SPLIT=bf16 in the environment.  GAT plans (gigl_gat_plan_create / _set_weights) take the same decision for
  * their first layer's projection. */
 int32_t gigl_sage_plan_half_split(gigl_sage_plan* plan);
-/* Non-zero when the plan runs its two SAGE layers' projections in ONE kernel (the value = the partial planes of p rows that
- * kernel writes per node: 1 = whole rows, linear_fused2x_kernel, the default; 2 = K-split over the hidden width's two column
- * tiles, the round-5 kernel, GIGL_F2_VARIANT=0 / 4): layer 0's hidden rows are multiplied by the last
- * layer's [W_l | W_r] before they leave the workgroup (W_l mean_j h_j = mean_j W_l h_j), 2 x out floats per node leave
- * instead of the hidden row, and the last layer (homogeneous.py:122-126 -> SAGEConv: W_l mean + b + W_r self) is one
+/* 1 when the plan runs its two SAGE layers' projections in ONE kernel (0: apart): layer 0's hidden rows are multiplied by
+ * the last layer's [W_l | W_r] before they leave the workgroup (W_l mean_j h_j = mean_j W_l h_j), 2 x out floats per node
+ * leave instead of the hidden row, and the last layer (homogeneous.py:122-126 -> SAGEConv: W_l mean + b + W_r self) is one
  * reduction over those rows.  Two layers, hidden width 256, 2 x out <= 96, half-split first layer over an fp32 table, a
  * linear reduction (mean / sum); GIGL_PLAN_NO_FUSE2=1 at plan creation keeps the layers apart (A/B).  Same rows up to
  * rounding (1e-5 of the fp32 CPU forward: tests/test_gpu_plan.py). */
