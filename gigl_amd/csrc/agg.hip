@@ -1230,8 +1230,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ONE || (HS
 //     splits them in registers into the two MFMA steps' fragments;
 //   * W1's fp16 planes are laid out ONCE per run (fused2_images_kernel) as the chunk's LDS images — swizzle included, k
 //     inside a chunk permuted to the order the lanes hold it: position 16 s + 8 g + e <- k = 16 s + 8 (e / 4) + 4 g + e % 4,
-//     the permutation the accumulator layout imposes on the second product anyway — so a chunk of W is eight 16-byte
-//     copies per thread through registers, no vector ALU work, into one of TWO buffers (64 KB of LDS): ONE barrier per chunk.
+//     the permutation the accumulator layout imposes on the second product anyway — so a chunk of W is eight LDS-direct
+//     16-byte loads per thread (global_load_lds_dwordx4, no staging registers, no vector ALU work) into one of TWO buffers
+//     (64 KB of LDS), issued right after the barrier that freed that buffer: ONE barrier per chunk.
 // Second product: h = relu(acc / (s_a s_w) + b1) is bounded by K max|W1| max|a| + max|b1| =: B (found on the device
 // from the scales of the first product), so it takes the half split too: h s_h = h1 + h2 with s_h a power of two that
 // brings B under 2^14; element error max(2^-22 |h|, 2^-39 B).  W2's planes (fp16, scaled by s_w2) are images too, 32 hidden
@@ -1288,32 +1289,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void l
     }
   };
   constexpr int IMGU = F2_IMG1 / 8;  // 16-byte units per W1 chunk image
-  const u32x4_t* w1src = reinterpret_cast<const u32x4_t*>(w1img) + tid;
-  u32x4_t wr0, wr1, wr2, wr3, wr4, wr5, wr6, wr7;
   typedef const __attribute__((address_space(1))) void* gptr_t;
   typedef __attribute__((address_space(3))) void* lptr_t;
-  auto wload = [&](int c) {  // W1 chunk c's two images (hidden columns 0..127, 128..255) into the staging registers
+  const u32x4_t* w1src = reinterpret_cast<const u32x4_t*>(w1img) + tid;
+  auto w1load = [&](int c, int b) {  // W1 chunk c's two images straight into buffer b (this wave's 1-KB pieces of each)
     const u32x4_t* s0 = w1src + (int64_t)c * IMGU;
     const u32x4_t* s1 = w1src + (int64_t)(nc + c) * IMGU;
-    wr0 = s0[0];
-    wr1 = s0[256];
-    wr2 = s0[512];
-    wr3 = s0[768];
-    wr4 = s1[0];
-    wr5 = s1[256];
-    wr6 = s1[512];
-    wr7 = s1[768];
-  };
-  auto wstore = [&](int b) {
-    u32x4_t* dst = reinterpret_cast<u32x4_t*>(s_buf[b]) + tid;
-    dst[0] = wr0;
-    dst[256] = wr1;
-    dst[512] = wr2;
-    dst[768] = wr3;
-    dst[IMGU] = wr4;
-    dst[IMGU + 256] = wr5;
-    dst[IMGU + 512] = wr6;
-    dst[IMGU + 768] = wr7;
+    short* dst = s_buf[b] + wv * 512;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) __builtin_amdgcn_global_load_lds((gptr_t)(s0 + 256 * i), (lptr_t)(dst + 2048 * i), 16, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      __builtin_amdgcn_global_load_lds((gptr_t)(s1 + 256 * i), (lptr_t)(dst + F2_IMG1 + 2048 * i), 16, 0, 0);
   };
   const u32x4_t* w2src = reinterpret_cast<const u32x4_t*>(w2img) + tid;
   auto w2load = [&](int rd, int b) {  // W2 round rd's image straight into buffer b (this wave's 1-KB piece of each third)
@@ -1322,13 +1309,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void l
 #pragma unroll
     for (int i = 0; i < 3; ++i) __builtin_amdgcn_global_load_lds((gptr_t)(src + 256 * i), (lptr_t)(dst + 2048 * i), 16, 0, 0);
   };
-  // stage k (W1 chunks 0 .. nc - 1, then W2's rounds) lives in buffer k & 1; its image is fetched while stage k - 1 is worked on
-  wload(0);
+  // stage k (W1 chunks 0 .. nc - 1, then W2's rounds) lives in buffer k & 1.  Everything stage k + 1 needs — its W image
+  // (LDS-direct) and, for a chunk, the wave's A registers — is issued at the top of stage k, right after the barrier that
+  // freed buffer (k + 1) & 1, and waited for at the barrier that closes stage k: a whole stage of MFMAs in between, and no
+  // staging registers for W
+  w1load(0, 0);
   aload(0);
-  wstore(0);
-  if (nc > 1) wload(1);
   __syncthreads();
   for (int c = 0; c < nc; ++c) {
+    if (c + 1 < nc) w1load(c + 1, (c + 1) & 1);  // (that buffer's last reader was chunk c - 1)
     half8v_t fa[2][2];  // [MFMA step][plane]
 #pragma unroll
     for (int s = 0; s < 2; ++s)
@@ -1370,10 +1359,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void l
           for (int j = 0; j < 4; ++j)
             acc[4 * tn + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fw[j][HW[t]], fa[s][HA[t]], acc[4 * tn + j], 0, 0, 0);
       }
-    }
-    if (c + 1 < nc) {
-      wstore((c + 1) & 1);
-      if (c + 2 < nc) wload(c + 2);
     }
     __syncthreads();
   }
