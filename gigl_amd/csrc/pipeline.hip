@@ -470,8 +470,8 @@ __global__ __launch_bounds__(256) void ce_roots_kernel(const float* __restrict__
 }
 
 // ---- round 6: the node-classification step's small launches folded together (each costs ~5 us of a 0.22-ms step) ----
-// prep: the cleared block (gw | gb | dh), the transposed weights of layers >= 1 (the backward's da = dh . W needs W^T as the
-// projection's weight operand; the weights only change in the previous step's Adam) and the loss ticket, in ONE launch
+// prep: the cleared block (the dh rows that are ADDED to) and the transposed weights of layers >= 1 (the backward's
+// da = dh . W needs W^T as the projection's weight operand; the weights only change in the previous step's Adam), in ONE launch
 struct TrainPrep {
   uint32_t* zero;
   int64_t zero_words;
@@ -479,7 +479,6 @@ struct TrainPrep {
   float* wt[GIGL_MAX_HOPS];
   int32_t rows[GIGL_MAX_HOPS], cols[GIGL_MAX_HOPS];
   int32_t n_t;
-  int32_t* ticket;
 };
 // the step's inputs into the static buffers the captured launches read — labels, the number of real roots, where the
 // caller wants the loss — in one launch (was: a device copy, a 32-bit fill and, after the step, another device copy)
@@ -507,7 +506,7 @@ __global__ __launch_bounds__(256) void train_stage_kernel(const int64_t* __restr
 __global__ __launch_bounds__(1024) void loss_sum_kernel(const float* __restrict__ loss_rows, int b,
                                                         const int32_t* __restrict__ n_valid_dev, float* __restrict__ loss,
                                                         int32_t* __restrict__ step, const int32_t* __restrict__ meta,
-                                                        int32_t* __restrict__ halt, float* const* loss_slot = nullptr) {
+                                                        int32_t* __restrict__ halt, float* const* loss_slot) {
   __shared__ float s_p[16];
   float v = 0.f;
   for (int i = threadIdx.x; i < b; i += 1024) v += loss_rows[i];
@@ -526,8 +525,7 @@ __global__ __launch_bounds__(1024) void loss_sum_kernel(const float* __restrict_
     else if (meta[GIGL_META_OVERFLOW] == 0) *step += 1;
     else *halt = 1;
     // (round 6: the caller's loss slot, set by train_stage_kernel — no device copy after the step)
-    float* extra = loss_slot ? *loss_slot : nullptr;
-    if (extra) *extra = *loss;
+    if (*loss_slot) **loss_slot = *loss;
   }
 }
 
@@ -547,25 +545,49 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
   }
 }
 
-// Adam with L2 weight decay (torch.optim.Adam: the decay joins the gradient), every parameter tensor in one launch
+// Adam with L2 weight decay (torch.optim.Adam: the decay joins the gradient), every parameter tensor in one launch.
+// A tensor's gradient is the sum of up to two SOURCES (the two encodes of a link-prediction step share the weights).  A
+// source is a plain vector g, or the weight-gradient kernel's per-chunk PARTIAL sums (part != NULL: [chunks][n] floats, the
+// chunks below ceil(*rows / rc) hold real rows) added up here in chunk order — one reduce launch less per layer; source 0
+// may hold both (the GAT plan: the folded attention vectors' share of W0's gradient beside the projections' partial sums)
+constexpr int ADAM_MAX = 16;  // tensors (or slices of tensors: the GAT plan's heads) per launch
 struct AdamPack {
-  float* p[2 * GIGL_MAX_HOPS];
-  const float* g[2 * GIGL_MAX_HOPS];
-  float* m[2 * GIGL_MAX_HOPS];
-  float* v[2 * GIGL_MAX_HOPS];
-  int64_t n[2 * GIGL_MAX_HOPS];
-  // round 6: a tensor's gradient may arrive as the weight-gradient kernel's per-chunk PARTIAL sums (part != NULL:
-  // [chunks][n] floats, the chunks below ceil(*rows / rc) hold real rows) — summed here in chunk order, one launch less per layer
-  const float* part[2 * GIGL_MAX_HOPS];
-  const int32_t* rows[2 * GIGL_MAX_HOPS];
-  int32_t rc[2 * GIGL_MAX_HOPS];
+  float* p[ADAM_MAX];
+  float* m[ADAM_MAX];
+  float* v[ADAM_MAX];
+  int64_t n[ADAM_MAX];
+  const float* g[2][ADAM_MAX];
+  const float* part[2][ADAM_MAX];
+  const int32_t* rows[2][ADAM_MAX];
+  int32_t rc[2][ADAM_MAX];
   int32_t count;
+  // 1: gradient = source 0 (node classification); 2: source 0 + source 1 — the order of reduce + reduce + add; a tensor
+  // without a second source adds 0
+  int32_t n_src;
   float lr, beta1, beta2, eps, wd;
 };
 
+// (sixteen chunks' loads in flight, added in chunk order)
+__device__ __forceinline__ float chunk_sum(const float* __restrict__ part, int chunks, int64_t n, int64_t i) {
+  float s = 0.f;
+  int c = 0;
+  for (; c + 15 < chunks; c += 16) {
+    float pv[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) pv[q] = part[(int64_t)(c + q) * n + i];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s += pv[q];
+  }
+  for (; c < chunks; ++c) s += part[(int64_t)c * n + i];
+  return s;
+}
+
+// meta_b: the second encode's batch (NULL: the step has one); halt: the sticky "a batch failed" word (NULL: the plan has none)
 __global__ __launch_bounds__(256) void adam_kernel(AdamPack a, const int32_t* __restrict__ step_dev,
-                                                   const int32_t* __restrict__ meta, const int32_t* __restrict__ halt) {
-  if (meta[GIGL_META_OVERFLOW] != 0 || *halt != 0) return;  // a failed batch trains nothing (its loss is NaN)
+                                                   const int32_t* __restrict__ meta_a, const int32_t* __restrict__ meta_b,
+                                                   const int32_t* __restrict__ halt) {
+  // a failed batch trains nothing (its loss is NaN)
+  if (meta_a[GIGL_META_OVERFLOW] != 0 || (meta_b && meta_b[GIGL_META_OVERFLOW] != 0) || (halt && *halt != 0)) return;
   const double t = (double)*step_dev;
   const float bc1 = (float)(1.0 - pow((double)a.beta1, t)), bc2s = (float)sqrt(1.0 - pow((double)a.beta2, t));
   const float step_size = a.lr / bc1;
@@ -574,28 +596,22 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamPack a, const int32_t* __
   const int k_lo = gridDim.y > 1 ? (int)blockIdx.y : 0, k_hi = gridDim.y > 1 ? (int)blockIdx.y + 1 : a.count;
   for (int k = k_lo; k < k_hi && k < a.count; ++k) {
     float* p = a.p[k];
-    const float* g = a.g[k];
     float* m = a.m[k];
     float* v = a.v[k];
-    const float* part = a.part[k];
-    const int chunks = part ? (*a.rows[k] + a.rc[k] - 1) / a.rc[k] : 0;
+    const float *g0 = a.g[0][k], *g1 = a.g[1][k], *part0 = a.part[0][k], *part1 = a.part[1][k];
+    const int ch0 = part0 ? (*a.rows[0][k] + a.rc[0][k] - 1) / a.rc[0][k] : 0;
+    const int ch1 = part1 ? (*a.rows[1][k] + a.rc[1][k] - 1) / a.rc[1][k] : 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n[k]; i += (int64_t)gridDim.x * blockDim.x) {
       const float w = p[i];
-      float gsum = 0.f;
-      if (part) {  // (sixteen chunks' loads in flight, added in chunk order)
-        int c = 0;
-        for (; c + 15 < chunks; c += 16) {
-          float pv[16];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) pv[q] = part[(int64_t)(c + q) * a.n[k] + i];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) gsum += pv[q];
-        }
-        for (; c < chunks; ++c) gsum += part[(int64_t)c * a.n[k] + i];
+      float ga = part0 ? chunk_sum(part0, ch0, a.n[k], i) : g0[i];
+      if (part0 && g0) ga += g0[i];
+      float gr;
+      if (a.n_src == 2) {
+        const float gb = part1 ? chunk_sum(part1, ch1, a.n[k], i) : (g1 ? g1[i] : 0.f);
+        gr = (ga + gb) + a.wd * w;
       } else {
-        gsum = g[i];
+        gr = ga + a.wd * w;
       }
-      const float gr = gsum + a.wd * w;
       const float mm = m[i] + (gr - m[i]) * (1.f - a.beta1);
       const float vv = v[i] * a.beta2 + (1.f - a.beta2) * gr * gr;
       m[i] = mm;
@@ -1098,8 +1114,9 @@ int32_t gigl_sage_plan_set_graph_stream(gigl_sage_plan* p, void* hip_stream, int
 
 // ---- gigl_sage_train_plan: one TRAINING step per call, all of it in the library —
 //   sample -> batch union graph (the one-call plan's leaf-global build) -> GraphSAGE forward keeping every layer's
-//   operand and output -> cross-entropy on the roots -> backward (weight gradients by gigl_linear_weight_grad, the
-//   layers' input gradients by one projection over the transposed weights + gigl_gather_mean_backward) -> Adam.
+//   operand and output -> cross-entropy on the roots -> backward (weight gradients as gigl_linear_weight_grad_parts'
+//   partial sums, the layers' input gradients by one projection over the transposed weights + the mean's backward) -> Adam,
+//   which adds the partial sums up.
 // Replaces the loop body of NodeClassificationModelingTaskSpec._train
 // (python/gigl/src/common/modeling_task_specs/node_classification_modeling_task_spec.py:134-173) for batches sampled in
 // HBM: ~25 launches and two memsets, no torch kernel between them, replayed from hipGraphs.
@@ -1121,7 +1138,261 @@ static bool train_bwd_gather(const int32_t* dims, int32_t hops) {
   return true;
 }
 
-struct gigl_sage_train_plan {
+// ---- the GraphSAGE training encoder, written once: the node-classification plan runs one encode per step, the
+// link-prediction plan two (main batch, random negatives) over the SHARED weights
+
+// what the encodes of a plan share: the layers' shapes, the parameters, Adam's state
+struct SageTrainShared {
+  int32_t L = 0, act_last = 0;
+  int32_t dims[GIGL_MAX_HOPS + 1] = {0};
+  float* w[GIGL_MAX_HOPS] = {nullptr};  // fused [dims[l+1]][2 dims[l]]: borrowed, UPDATED IN PLACE
+  float* bias[GIGL_MAX_HOPS] = {nullptr};
+  float* mom[4 * GIGL_MAX_HOPS] = {nullptr};  // m_w, v_w, m_b, v_b per layer
+  // W_l^T of layers >= 1 (the backward's da = dh . W needs it as the projection's weight operand), laid out ONCE per step
+  float* wt_l[GIGL_MAX_HOPS] = {nullptr};
+  bool bwd_gather = false;  // layers >= 1 hand their input gradient down by the transposed gather (train_bwd_gather)
+  float lr = 0.f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, wd = 0.f;
+};
+
+// one encode's state
+struct SageTrainEnc {
+  gigl_sage_plan* base = nullptr;  // (link-prediction plans) tree / union workspace of this encode's roots, set per step
+  int32_t b = 0;                   // roots
+  int64_t rows_cap[GIGL_MAX_HOPS] = {0};  // rows layer l may compute
+  float* a[GIGL_MAX_HOPS] = {nullptr};    // [rows_cap[l]][2 dims[l]]: the layer's [mean | self] operand
+  float* h[GIGL_MAX_HOPS] = {nullptr};    // [rows_cap[l]][dims[l+1]]: its output (activated below the last layer)
+  float* dh[GIGL_MAX_HOPS] = {nullptr};   // gradient of h[l]
+  // the weight gradients' per-chunk partial sums: added up inside the Adam kernel, no reduce launch per layer
+  float* part_w[GIGL_MAX_HOPS] = {nullptr};
+  float* part_b[GIGL_MAX_HOPS] = {nullptr};
+  int32_t part_rc[GIGL_MAX_HOPS] = {0};
+  // the gradients themselves, where a plan hands them out (gigl_nablp_train_plan_grads adds the partial sums up on demand)
+  float* gw[GIGL_MAX_HOPS] = {nullptr};
+  float* gb[GIGL_MAX_HOPS] = {nullptr};
+  float* emb = nullptr;  // (link prediction) [b][d_out]: the roots' embeddings (normalised when the model says so)
+  float* inv = nullptr;  // (link prediction) [b]: 1 / max(|h_r|, 1e-12) (1 without normalisation; 0: no such root)
+};
+
+namespace {
+
+void* train_alloc(std::vector<void*>& owned, size_t bytes) {
+  void* q = nullptr;
+  if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
+  owned.push_back(q);
+  return q;
+}
+
+// the shapes and parameters (s.L is set), Adam's moments (zero) and the W_l^T buffers
+bool sage_shared_alloc(SageTrainShared& s, std::vector<void*>& owned, const int32_t* dims, float* const* w, float* const* bias) {
+  bool ok = true;
+  for (int l = 0; l <= s.L; ++l) s.dims[l] = dims[l];
+  s.bwd_gather = train_bwd_gather(dims, s.L);
+  for (int l = 0; l < s.L; ++l) {
+    s.w[l] = w[l];
+    s.bias[l] = bias ? bias[l] : nullptr;
+    const size_t nw = (size_t)dims[l + 1] * 2 * dims[l];
+    for (int k = 0; k < 4; ++k) {
+      const size_t n = k < 2 ? nw : (size_t)dims[l + 1];
+      s.mom[4 * l + k] = (float*)train_alloc(owned, n * 4);
+      ok = ok && s.mom[4 * l + k] && hipMemset(s.mom[4 * l + k], 0, n * 4) == hipSuccess;
+    }
+    if (l >= 1) {
+      s.wt_l[l] = (float*)train_alloc(owned, nw * 4);
+      ok = ok && s.wt_l[l];
+    }
+  }
+  return ok;
+}
+
+// (the input gradient of a layer below the last is written whole by the transposed gather: not part of a cleared block)
+bool sage_dh_cleared(const SageTrainShared& s, int l) { return !(s.bwd_gather && l < s.L - 1); }
+
+// one encode's buffers for its e.b roots.  Its share of the plan's cleared block — the dh rows that are ADDED to, and with
+// `grads` gw | gb — is counted into *zero_floats and handed out by sage_enc_carve once the block exists; *da_floats
+// grows to the operand-gradient scratch its backward needs
+bool sage_enc_alloc(const SageTrainShared& s, SageTrainEnc& e, std::vector<void*>& owned, bool wide, const int32_t* fanouts,
+                    bool grads, size_t* zero_floats, size_t* da_floats) {
+  bool ok = true;
+  for (int l = 0; l < s.L; ++l) {
+    const int n_out = s.dims[l + 1], k2 = 2 * s.dims[l];
+    const int64_t rows = gigl_level_rows(wide, e.b, fanouts, s.L, s.L - 1 - l);  // layer l computes the nodes of level <= L-1-l
+    e.rows_cap[l] = rows;
+    if (grads) *zero_floats += (size_t)n_out * k2 + n_out;
+    if (l >= 1) *da_floats = std::max(*da_floats, (size_t)rows * k2);
+    e.a[l] = (float*)train_alloc(owned, (size_t)rows * k2 * 4);
+    e.h[l] = (float*)train_alloc(owned, (size_t)rows * n_out * 4);
+    if (sage_dh_cleared(s, l)) {
+      *zero_floats += (size_t)rows * n_out;
+    } else {
+      e.dh[l] = (float*)train_alloc(owned, (size_t)rows * n_out * 4);
+      ok = ok && e.dh[l];
+    }
+    const int64_t chunks = gigl_linear_weight_grad_chunks(rows, n_out, k2, &e.part_rc[l]);
+    e.part_w[l] = (float*)train_alloc(owned, (size_t)chunks * n_out * k2 * 4);
+    e.part_b[l] = (float*)train_alloc(owned, (size_t)chunks * n_out * 4);
+    ok = ok && e.a[l] && e.h[l] && e.part_w[l] && e.part_b[l];
+  }
+  return ok;
+}
+
+// the encode's share of the cleared block at z, per layer gw | gb | dh -> the end of the share
+float* sage_enc_carve(const SageTrainShared& s, SageTrainEnc& e, bool grads, float* z) {
+  for (int l = 0; l < s.L; ++l) {
+    if (grads) {
+      e.gw[l] = z;
+      z += (size_t)s.dims[l + 1] * 2 * s.dims[l];
+      e.gb[l] = z;
+      z += s.dims[l + 1];
+    }
+    if (sage_dh_cleared(s, l)) {
+      e.dh[l] = z;
+      z += (size_t)e.rows_cap[l] * s.dims[l + 1];
+    }
+  }
+  return z;
+}
+
+// the transposed lists of layers >= 1 for one workspace (cap_edges: its union graph's) of the encode
+bool sage_tlists_alloc(const SageTrainShared& s, const SageTrainEnc& e, std::vector<void*>& owned, int64_t cap_edges, int32_t** tl) {
+  for (int l = 1; l < s.L && s.bwd_gather; ++l) {
+    tl[l] = (int32_t*)train_alloc(owned, (size_t)gigl_transposed_rows_words(e.rows_cap[l - 1], cap_edges) * 4);
+    if (!tl[l]) return false;
+  }
+  return true;
+}
+
+// the graph part of one root set, on workspace p's ctx: sample + union (+ the level guard) ...
+int32_t sage_enqueue_graph(const SageTrainShared& s, const SageTrainEnc& e, gigl_sage_plan* p, int32_t* const* tl,
+                           int32_t sampling_seed, int32_t mode) {
+  int32_t rc = enqueue_range(p, 0, 2, p->roots_buf, sampling_seed, mode, nullptr);
+  // ... and who reads which source row in the backward of layers >= 1 (a function of the batch graph alone)
+  for (int l = 1; l < s.L && rc == GIGL_OK && s.bwd_gather; ++l)
+    rc = gigl_transposed_rows_build(p->ctx, p->un.rowptr, p->un.rowend, p->un.col, p->un.meta + GIGL_META_LEVEL0 + (s.L - 1 - l),
+                                    e.rows_cap[l], p->un.meta + GIGL_META_LEVEL0 + (s.L - l), e.rows_cap[l - 1], p->un.cap_edges,
+                                    tl[l]);
+  return rc;
+}
+
+// forward over workspace p's batch graph, on ctx: every layer's operand a[l] and output h[l] are kept
+int32_t sage_enc_forward(gigl_ctx* ctx, const SageTrainShared& s, const SageTrainEnc& e, const gigl_sage_plan* p) {
+  const int L = s.L;
+  int32_t rc = GIGL_OK;
+  const int32_t* n_local = p->leaf_global ? (L >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (L - 2) : p->zero_dev) : nullptr;
+  for (int l = 0; l < L; ++l) {
+    const int32_t* n_rows = p->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
+    const int d = s.dims[l];
+    if (l == 0)
+      rc = gigl_gather_reduce_mixed(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col,
+                                    n_rows, e.rows_cap[0], GIGL_AGGR_MEAN, n_local, e.a[0]);
+    else
+      rc = gigl_gather_reduce(ctx, e.h[l - 1], GIGL_DTYPE_F32, d, nullptr, p->un.rowptr, p->un.rowend, p->un.col, n_rows,
+                              e.rows_cap[l], GIGL_AGGR_MEAN, e.a[l]);
+    if (rc != GIGL_OK) return rc;
+    rc = gigl_linear(ctx, e.a[l], s.w[l], s.bias[l], n_rows, e.rows_cap[l], 2 * d, s.dims[l + 1],
+                     (l < L - 1 || s.act_last) ? 1 : 0, e.h[l]);
+    if (rc != GIGL_OK) return rc;
+  }
+  return GIGL_OK;
+}
+
+// backward from dh[L - 1] down, on ctx: the weight gradients as partial sums (part_w / part_b: Adam adds them up), the
+// layers' input gradients by one projection over W_l^T (s.wt_l, laid out before) into `da` + the mean's backward over
+// workspace p's batch graph (tl: its transposed lists).  wctx != NULL: the weight gradients run on that ctx's stream
+// beside the chain, each behind ev_w (nothing in the chain waits for them; the caller joins wctx before Adam)
+int32_t sage_enc_backward(gigl_ctx* ctx, const SageTrainShared& s, const SageTrainEnc& e, const gigl_sage_plan* p,
+                          int32_t* const* tl, float* da, gigl_ctx* wctx, hipEvent_t ev_w) {
+  hipStream_t st = ctx->stream;
+  const int L = s.L;
+  int32_t rc = GIGL_OK;
+  for (int l = L - 1; l >= 0; --l) {
+    const int32_t* n_rows = p->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
+    const int d = s.dims[l], n_out = s.dims[l + 1];
+    const bool act = l < L - 1 || s.act_last;
+    auto relu_mask = [&]() {
+      int64_t blocks = (e.rows_cap[l] * n_out + 255) / 256;
+      if (blocks > 4096) blocks = 4096;
+      hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, st, e.dh[l], (const float*)e.h[l], n_rows, n_out);
+    };
+    if (wctx) {
+      // the mask first (the chain needs the masked rows anyway), then the gradient of the MASKED rows beside the chain: the
+      // same products as the masked read of the unmasked rows
+      if (act) relu_mask();
+      GIGL_HIP_CHECK(ctx, hipEventRecord(ev_w, st));
+      GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(wctx->stream, ev_w, 0));
+      rc = gigl_linear_weight_grad_parts(wctx, e.dh[l], e.a[l], nullptr, n_rows, e.rows_cap[l], n_out, 2 * d, e.part_w[l],
+                                         s.bias[l] ? e.part_b[l] : nullptr);
+    } else {
+      rc = gigl_linear_weight_grad_parts(ctx, e.dh[l], e.a[l], act ? e.h[l] : nullptr, n_rows, e.rows_cap[l], n_out, 2 * d,
+                                         e.part_w[l], s.bias[l] ? e.part_b[l] : nullptr);
+    }
+    if (rc != GIGL_OK) return rc;
+    if (l == 0) break;  // (the first layer's input is the feature table: no gradient)
+    if (act && !wctx) relu_mask();
+    rc = gigl_linear(ctx, e.dh[l], s.wt_l[l], nullptr, n_rows, e.rows_cap[l], n_out, 2 * d, 0, da);
+    if (rc != GIGL_OK) return rc;
+    if (s.bwd_gather)
+      rc = gigl_gather_mean_backward_lists(ctx, da, d, p->un.rowptr, p->un.rowend, n_rows, p->un.meta + GIGL_META_LEVEL0 + (L - l),
+                                           e.rows_cap[l - 1], tl[l], GIGL_AGGR_MEAN, e.dh[l - 1]);
+    else
+      rc = gigl_gather_mean_backward(ctx, da, d, p->un.rowptr, p->un.rowend, p->un.col, n_rows, e.rows_cap[l], e.dh[l - 1]);
+    if (rc != GIGL_OK) return rc;
+  }
+  return GIGL_OK;
+}
+
+// Adam's pack over the partial sums of one encode (e1 == NULL) or of two, each over its workspace's batch
+AdamPack sage_adam_pack(const SageTrainShared& s, const SageTrainEnc* e0, const gigl_sage_plan* p0, const SageTrainEnc* e1,
+                        const gigl_sage_plan* p1) {
+  AdamPack ap{};
+  const SageTrainEnc* e[2] = {e0, e1};
+  const gigl_sage_plan* p[2] = {p0, p1};
+  ap.n_src = e1 ? 2 : 1;
+  for (int l = 0; l < s.L; ++l)
+    for (int is_bias = 0; is_bias < (s.bias[l] ? 2 : 1); ++is_bias) {
+      const int k = ap.count++;
+      ap.p[k] = is_bias ? s.bias[l] : s.w[l];
+      ap.m[k] = s.mom[4 * l + 2 * is_bias];
+      ap.v[k] = s.mom[4 * l + 2 * is_bias + 1];
+      ap.n[k] = is_bias ? (int64_t)s.dims[l + 1] : (int64_t)s.dims[l + 1] * 2 * s.dims[l];
+      for (int q = 0; q < ap.n_src; ++q) {
+        ap.part[q][k] = is_bias ? e[q]->part_b[l] : e[q]->part_w[l];
+        ap.rows[q][k] = p[q]->un.meta + GIGL_META_LEVEL0 + (s.L - 1 - l);
+        ap.rc[q][k] = e[q]->part_rc[l];
+      }
+    }
+  ap.lr = s.lr;
+  ap.beta1 = s.beta1;
+  ap.beta2 = s.beta2;
+  ap.eps = s.eps;
+  ap.wd = s.wd;
+  return ap;
+}
+
+// Adam's moments of tensor `index` (2 l: layer l's weights, 2 l + 1: its bias) -> m, v (device; either may be NULL), on ctx's stream
+int32_t sage_moments_copy(gigl_ctx* ctx, const SageTrainShared& s, int index, float* m, float* v) {
+  const int l = index >> 1, is_bias = index & 1;
+  const size_t n = is_bias ? (size_t)s.dims[l + 1] : (size_t)s.dims[l + 1] * 2 * s.dims[l];
+  float* dst[2] = {m, v};
+  for (int k = 0; k < 2; ++k)
+    if (dst[k])
+      GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst[k], s.mom[4 * l + 2 * is_bias + k], n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  return GIGL_OK;
+}
+
+// every moment of src into dst's (plans of the same shape), on ctx's stream
+int32_t sage_moments_adopt(gigl_ctx* ctx, const SageTrainShared& dst, const SageTrainShared& src) {
+  GIGL_REQUIRE(ctx, dst.L == src.L, "plans of different depth");
+  for (int l = 0; l <= dst.L; ++l) GIGL_REQUIRE(ctx, dst.dims[l] == src.dims[l], "plans of different widths");
+  for (int i = 0; i < 2 * dst.L; ++i) {
+    const int32_t rc = sage_moments_copy(ctx, src, i, dst.mom[4 * (i >> 1) + 2 * (i & 1)], dst.mom[4 * (i >> 1) + 2 * (i & 1) + 1]);
+    if (rc != GIGL_OK) return rc;
+  }
+  return GIGL_OK;
+}
+
+}  // namespace
+
+struct gigl_sage_train_plan : SageTrainShared {
   gigl_ctx* ctx = nullptr;         // the caller's (its stream carries the layers part; errors are reported on it)
   // two ctxs of the plan's own, for their ARENAS: scratch addresses are baked into the captured launches, and another
   // plan on the caller's ctx (the inference plan of an evaluation pass between epochs) may grow — reallocate — that arena
@@ -1136,37 +1407,16 @@ struct gigl_sage_train_plan {
   // layers part that read the workspace done (recorded on the caller's stream); [2]: the caller's stream as it stands
   // when a graph part is issued (the roots it is handed were written there)
   hipEvent_t ev_layers[TRAIN_WS + 1] = {nullptr};
-  int32_t L = 0, b = 0, act_last = 0;
-  int32_t dims[GIGL_MAX_HOPS + 1] = {0};
-  int64_t rows_cap[GIGL_MAX_HOPS] = {0};  // rows layer l may compute
-  float* w[GIGL_MAX_HOPS] = {nullptr};    // fused [dims[l+1]][2 dims[l]]: borrowed, UPDATED IN PLACE
-  float* bias[GIGL_MAX_HOPS] = {nullptr};
-  float* a[GIGL_MAX_HOPS] = {nullptr};    // [rows_cap[l]][2 dims[l]]: the layer's [mean | self] operand
-  float* h[GIGL_MAX_HOPS] = {nullptr};    // [rows_cap[l]][dims[l+1]]: its output (activated below the last layer)
-  float* dh[GIGL_MAX_HOPS] = {nullptr};   // gradient of h[l]
-  bool bwd_gather = false;                // layers >= 1 hand their input gradient down by the transposed gather
+  SageTrainEnc enc;                       // the step's one encode (over the workspace base[k] the step reads)
   int32_t* tlists[TRAIN_WS][GIGL_MAX_HOPS] = {{nullptr}};  // its transposed lists per workspace and layer >= 1, built by the graph part
   float* da = nullptr;                    // [max rows_cap[l >= 1]][2 max dims]: gradient of a layer's operand
-  float* wt = nullptr;                    // a layer's transposed weight
-  // round 6 (GIGL_TRAIN_PLAN_UNFUSED=1 keeps the separate launches: A/B): per-layer transposed weights written by the prep
-  // kernel, the weight gradients' partial sums (summed inside Adam), the fused loss's ticket and the loss pointer slot
-  bool fused_small = false;
-  float* wt_l[GIGL_MAX_HOPS] = {nullptr};
-  float* part_w[GIGL_MAX_HOPS] = {nullptr};
-  float* part_b[GIGL_MAX_HOPS] = {nullptr};
-  int32_t part_rc[GIGL_MAX_HOPS] = {0};
-  int32_t* ticket = nullptr;
-  float** loss_slot = nullptr;
-  float* gw[GIGL_MAX_HOPS] = {nullptr};
-  float* gb[GIGL_MAX_HOPS] = {nullptr};
-  float* mom[4 * GIGL_MAX_HOPS] = {nullptr};  // m_w, v_w, m_b, v_b per layer
-  void* zero_base = nullptr;              // gw | gb | dh: cleared at the start of every step
+  float** loss_slot = nullptr;            // where the caller wants the step's loss (set by train_stage_kernel)
+  void* zero_base = nullptr;              // the dh rows that are added to: cleared at the start of every step
   size_t zero_bytes = 0;
   int64_t* labels_buf = nullptr;
   int32_t* n_valid_buf = nullptr;  // [0] real roots of the batch, [1] Adam's step counter, [2] sticky "a batch failed" (halt)
   float* loss_rows = nullptr;
   float* loss = nullptr;
-  float lr = 0.01f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, wd = 0.f;
   std::vector<void*> owned;
   // hipGraph replay, per workspace and part
   hipGraphExec_t exec_graph[TRAIN_WS] = {nullptr}, exec_layers[TRAIN_WS] = {nullptr};
@@ -1176,119 +1426,33 @@ struct gigl_sage_train_plan {
 
 namespace {
 
-int32_t train_enqueue_graph(gigl_sage_train_plan* t, int k, int32_t sampling_seed, int32_t mode) {
-  gigl_sage_plan* p = t->base[k];
-  int32_t rc = enqueue_range(p, 0, 2, p->roots_buf, sampling_seed, mode, nullptr);  // sample + union (+ the level guard)
-  // ... and who reads which source row in the backward of layers >= 1 (a function of the batch graph alone)
-  for (int l = 1; l < t->L && rc == GIGL_OK && t->bwd_gather; ++l)
-    rc = gigl_transposed_rows_build(p->ctx, p->un.rowptr, p->un.rowend, p->un.col, p->un.meta + GIGL_META_LEVEL0 + (t->L - 1 - l),
-                                    t->rows_cap[l], p->un.meta + GIGL_META_LEVEL0 + (t->L - l), t->rows_cap[l - 1],
-                                    p->un.cap_edges, t->tlists[k][l]);
-  return rc;
-}
-
+// everything after the graph part, over workspace k, on lctx's stream (the caller's); train_stage_kernel ran ahead of it
 int32_t train_enqueue_layers(gigl_sage_train_plan* t, int k) {
   gigl_sage_plan* p = t->base[k];
   gigl_ctx* ctx = t->lctx;
   const int L = t->L;
   hipStream_t st = ctx->stream;
-  int32_t rc = GIGL_OK;
-  const bool fz = t->fused_small;
-  if (!fz) gigl_fill_u32(st, t->zero_base, 0u, (int64_t)(t->zero_bytes / 4));  // (fused: train_stage_kernel cleared it)
-  const int32_t* n_local = p->leaf_global ? (L >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (L - 2) : p->zero_dev) : nullptr;
-  // ---- forward
-  for (int l = 0; l < L; ++l) {
-    const int32_t* n_rows = p->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
-    const int d = t->dims[l];
-    if (l == 0)
-      rc = gigl_gather_reduce_mixed(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col,
-                                    n_rows, t->rows_cap[0], GIGL_AGGR_MEAN, n_local, t->a[0]);
-    else
-      rc = gigl_gather_reduce(ctx, t->h[l - 1], GIGL_DTYPE_F32, d, nullptr, p->un.rowptr, p->un.rowend, p->un.col, n_rows,
-                              t->rows_cap[l], GIGL_AGGR_MEAN, t->a[l]);
-    if (rc != GIGL_OK) return rc;
-    rc = gigl_linear(ctx, t->a[l], t->w[l], t->bias[l], n_rows, t->rows_cap[l], 2 * d, t->dims[l + 1],
-                     (l < L - 1 || t->act_last) ? 1 : 0, t->h[l]);
-    if (rc != GIGL_OK) return rc;
-  }
+  const SageTrainEnc& e = t->enc;
+  int32_t rc = sage_enc_forward(ctx, *t, e, p);
+  if (rc != GIGL_OK) return rc;
   // ---- loss on the roots, its gradient into dh[L - 1]
   {
     const int width = t->dims[L];
     // (the loss rows and their sum stay two launches: folding the sum into the last workgroup of the first — a ticket behind
     // device-scope fences — took 22.7 us instead of 5.0 + 5.1, and the L2 write-backs of its 256 fences slowed the next batch's
     // graph part on the side stream: measured, round 6)
-    hipLaunchKernelGGL(ce_roots_kernel, dim3((unsigned)((t->b + 3) / 4)), dim3(256), 0, st, (const float*)t->h[L - 1], width,
-                       (const int32_t*)p->un.root_local, (const int64_t*)t->labels_buf, (const int32_t*)t->n_valid_buf, t->b,
-                       (const int32_t*)p->un.meta, t->dh[L - 1], t->loss_rows);
-    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->loss_rows, t->b,
+    hipLaunchKernelGGL(ce_roots_kernel, dim3((unsigned)((e.b + 3) / 4)), dim3(256), 0, st, (const float*)e.h[L - 1], width,
+                       (const int32_t*)p->un.root_local, (const int64_t*)t->labels_buf, (const int32_t*)t->n_valid_buf, e.b,
+                       (const int32_t*)p->un.meta, e.dh[L - 1], t->loss_rows);
+    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->loss_rows, e.b,
                        (const int32_t*)t->n_valid_buf, t->loss, t->n_valid_buf + 1, (const int32_t*)p->un.meta,
-                       t->n_valid_buf + 2, fz ? (float* const*)t->loss_slot : (float* const*)nullptr);
+                       t->n_valid_buf + 2, (float* const*)t->loss_slot);
   }
-  // ---- backward
-  for (int l = L - 1; l >= 0; --l) {
-    const int32_t* n_rows = p->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
-    const int d = t->dims[l], n_out = t->dims[l + 1];
-    const bool act = l < L - 1 || t->act_last;
-    if (fz)  // (the partial sums only: Adam adds them up)
-      rc = gigl_linear_weight_grad_parts(ctx, t->dh[l], t->a[l], act ? t->h[l] : nullptr, n_rows, t->rows_cap[l], n_out, 2 * d,
-                                         t->part_w[l], t->bias[l] ? t->part_b[l] : nullptr);
-    else
-      rc = gigl_linear_weight_grad(ctx, t->dh[l], t->a[l], act ? t->h[l] : nullptr, n_rows, t->rows_cap[l], n_out, 2 * d,
-                                   t->gw[l], t->bias[l] ? t->gb[l] : nullptr);
-    if (rc != GIGL_OK) return rc;
-    if (l == 0) break;  // (the first layer's input is the feature table: no gradient)
-    if (act) {
-      int64_t blocks = (t->rows_cap[l] * n_out + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, st, t->dh[l], (const float*)t->h[l], n_rows, n_out);
-    }
-    const float* wt = t->wt;
-    if (fz) {
-      wt = t->wt_l[l];  // (written by the prep kernel)
-    } else {
-      int64_t blocks = ((int64_t)n_out * 2 * d + 255) / 256;
-      hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)t->w[l], n_out, 2 * d, t->wt);
-    }
-    rc = gigl_linear(ctx, t->dh[l], wt, nullptr, n_rows, t->rows_cap[l], n_out, 2 * d, 0, t->da);
-    if (rc != GIGL_OK) return rc;
-    if (t->bwd_gather)
-      rc = gigl_gather_mean_backward_lists(ctx, t->da, d, p->un.rowptr, p->un.rowend, n_rows,
-                                           p->un.meta + GIGL_META_LEVEL0 + (L - l), t->rows_cap[l - 1], t->tlists[k][l],
-                                           GIGL_AGGR_MEAN, t->dh[l - 1]);
-    else
-      rc = gigl_gather_mean_backward(ctx, t->da, d, p->un.rowptr, p->un.rowend, p->un.col, n_rows, t->rows_cap[l], t->dh[l - 1]);
-    if (rc != GIGL_OK) return rc;
-  }
-  // ---- Adam
-  AdamPack ap{};
-  for (int l = 0; l < L; ++l) {
-    const int32_t* n_rows = p->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
-    ap.p[ap.count] = t->w[l];
-    ap.g[ap.count] = t->gw[l];
-    ap.part[ap.count] = fz ? t->part_w[l] : nullptr;
-    ap.rows[ap.count] = n_rows;
-    ap.rc[ap.count] = t->part_rc[l];
-    ap.m[ap.count] = t->mom[4 * l];
-    ap.v[ap.count] = t->mom[4 * l + 1];
-    ap.n[ap.count++] = (int64_t)t->dims[l + 1] * 2 * t->dims[l];
-    if (t->bias[l]) {
-      ap.p[ap.count] = t->bias[l];
-      ap.g[ap.count] = t->gb[l];
-      ap.part[ap.count] = fz ? t->part_b[l] : nullptr;
-      ap.rows[ap.count] = n_rows;
-      ap.rc[ap.count] = t->part_rc[l];
-      ap.m[ap.count] = t->mom[4 * l + 2];
-      ap.v[ap.count] = t->mom[4 * l + 3];
-      ap.n[ap.count++] = t->dims[l + 1];
-    }
-  }
-  ap.lr = t->lr;
-  ap.beta1 = t->beta1;
-  ap.beta2 = t->beta2;
-  ap.eps = t->eps;
-  ap.wd = t->wd;
-  hipLaunchKernelGGL(adam_kernel, fz ? dim3(208, (unsigned)ap.count) : dim3(256), dim3(256), 0, st, ap,
-                     (const int32_t*)(t->n_valid_buf + 1), (const int32_t*)p->un.meta, (const int32_t*)(t->n_valid_buf + 2));
+  rc = sage_enc_backward(ctx, *t, e, p, t->tlists[k], t->da, nullptr, nullptr);
+  if (rc != GIGL_OK) return rc;
+  const AdamPack ap = sage_adam_pack(*t, &e, p, nullptr, nullptr);
+  hipLaunchKernelGGL(adam_kernel, dim3(208, (unsigned)ap.count), dim3(256), 0, st, ap, (const int32_t*)(t->n_valid_buf + 1),
+                     (const int32_t*)p->un.meta, (const int32_t*)nullptr, (const int32_t*)(t->n_valid_buf + 2));
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -1347,9 +1511,9 @@ int32_t train_graph_part(gigl_sage_train_plan* t, int k, const uint32_t* roots, 
   if (t->ev_layers[k]) GIGL_HIP_CHECK(sc, hipStreamWaitEvent(sc->stream, t->ev_layers[k], 0));
   GIGL_HIP_CHECK(sc, hipEventRecord(t->ev_layers[TRAIN_WS], t->ctx->stream));
   GIGL_HIP_CHECK(sc, hipStreamWaitEvent(sc->stream, t->ev_layers[TRAIN_WS], 0));
-  GIGL_HIP_CHECK(sc, hipMemcpyAsync(t->base[k]->roots_buf, roots, (size_t)t->b * 4, hipMemcpyDeviceToDevice, sc->stream));
+  GIGL_HIP_CHECK(sc, hipMemcpyAsync(t->base[k]->roots_buf, roots, (size_t)t->enc.b * 4, hipMemcpyDeviceToDevice, sc->stream));
   const int32_t rc = train_run_part(sc, &t->exec_graph[k], &t->warm_graph[k],
-                                    [&]() { return train_enqueue_graph(t, k, sampling_seed, mode); }, 0);
+                                    [&]() { return sage_enqueue_graph(*t, t->enc, t->base[k], t->tlists[k], sampling_seed, mode); }, 0);
   if (rc != GIGL_OK) return rc;
   GIGL_HIP_CHECK(sc, hipEventRecord(t->ev_graph[k], sc->stream));
   return GIGL_OK;
@@ -1413,90 +1577,34 @@ int32_t gigl_sage_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat*
     return rc;
   }
   t->L = hops;
-  t->b = b;
+  t->enc.b = b;
   t->act_last = act_last;
   t->lr = lr;
   t->beta1 = beta1;
   t->beta2 = beta2;
   t->eps = eps;
   t->wd = weight_decay;
-  auto alloc = [&](size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    t->owned.push_back(q);
-    return q;
-  };
-  bool ok = true;
-  size_t zero_floats = 0, da_floats = 16, wt_floats = 16;
-  for (int l = 0; l <= hops; ++l) t->dims[l] = dims[l];
-  t->bwd_gather = train_bwd_gather(dims, hops);
-  for (int l = 0; l < hops; ++l) {
-    t->w[l] = w[l];
-    t->bias[l] = bias ? bias[l] : nullptr;
-    const int64_t rows = gigl_level_rows(ctx->wide, b, fanouts, hops, hops - 1 - l);  // layer l computes the nodes of level <= L-1-l
-    t->rows_cap[l] = rows;
-    const size_t nw = (size_t)dims[l + 1] * 2 * dims[l];
-    zero_floats += nw + dims[l + 1] + (t->bwd_gather && l < hops - 1 ? 0 : (size_t)rows * dims[l + 1]);
-    if (l >= 1) {
-      da_floats = std::max(da_floats, (size_t)rows * 2 * dims[l]);
-      wt_floats = std::max(wt_floats, nw);
-    }
-    t->a[l] = (float*)alloc((size_t)rows * 2 * dims[l] * 4);
-    t->h[l] = (float*)alloc((size_t)rows * dims[l + 1] * 4);
-    for (int k = 0; k < 4; ++k) {
-      const size_t n = k < 2 ? nw : (size_t)dims[l + 1];
-      t->mom[4 * l + k] = (float*)alloc(n * 4);
-      if (t->mom[4 * l + k] && hipMemset(t->mom[4 * l + k], 0, n * 4) != hipSuccess) ok = false;
-      ok = ok && t->mom[4 * l + k];
-    }
-    ok = ok && t->a[l] && t->h[l];
-  }
+  auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
+  size_t zero_floats = 0, da_floats = 16;
+  bool ok = sage_shared_alloc(*t, t->owned, dims, w, bias);
+  // (no entry point hands this plan's gradients out: the cleared block is the dh rows alone)
+  ok = sage_enc_alloc(*t, t->enc, t->owned, ctx->wide, fanouts, false, &zero_floats, &da_floats) && ok;
   float* z = (float*)alloc(zero_floats * 4);
   t->zero_base = z;
   t->zero_bytes = zero_floats * 4;
-  for (int l = 0; l < hops && z; ++l) {
-    t->gw[l] = z;
-    z += (size_t)dims[l + 1] * 2 * dims[l];
-    t->gb[l] = z;
-    z += dims[l + 1];
-    if (t->bwd_gather && l < hops - 1) {  // (written whole by the transposed gather: not part of the cleared block)
-      t->dh[l] = (float*)alloc((size_t)t->rows_cap[l] * dims[l + 1] * 4);
-      ok = ok && t->dh[l];
-      continue;
-    }
-    t->dh[l] = z;
-    z += (size_t)t->rows_cap[l] * dims[l + 1];
-  }
+  if (z) sage_enc_carve(*t, t->enc, false, z);
+  for (int k = 0; k < TRAIN_WS; ++k) ok = sage_tlists_alloc(*t, t->enc, t->owned, t->base[k]->un.cap_edges, t->tlists[k]) && ok;
   t->da = (float*)alloc(da_floats * 4);
-  t->wt = (float*)alloc(wt_floats * 4);
-  for (int k = 0; k < TRAIN_WS && t->bwd_gather; ++k)
-    for (int l = 1; l < hops; ++l) {
-      t->tlists[k][l] = (int32_t*)alloc((size_t)gigl_transposed_rows_words(t->rows_cap[l - 1], t->base[k]->un.cap_edges) * 4);
-      ok = ok && t->tlists[k][l];
-    }
   t->labels_buf = (int64_t*)alloc((size_t)b * 8);
   t->n_valid_buf = (int32_t*)alloc(16);
   t->loss_rows = (float*)alloc((size_t)b * 4);
   t->loss = (float*)alloc(16);
-  ok = ok && t->zero_base && t->da && t->wt && t->labels_buf && t->n_valid_buf && t->loss_rows && t->loss;
-  if (ok && hipMemset(t->n_valid_buf, 0, 16) != hipSuccess) ok = false;
-  t->fused_small = getenv("GIGL_TRAIN_PLAN_UNFUSED") == nullptr;
-  if (t->fused_small && ok) {
-    // (measured, round 6: the loss sum on a BRANCH of the captured layers — forked after the loss rows, joined before Adam —
-    // took the step from 0.201 to 0.263 ms: a graph with a second branch is replayed through two queues with a barrier
-    // packet per edge.  The layers part stays one stream)
-    t->ticket = (int32_t*)alloc(16);
-    t->loss_slot = (float**)alloc(16);
-    ok = t->ticket && t->loss_slot && hipMemset(t->ticket, 0, 16) == hipSuccess && hipMemset(t->loss_slot, 0, 16) == hipSuccess;
-    for (int l = 0; l < hops && ok; ++l) {
-      const int n_out = dims[l + 1], k2 = 2 * dims[l];
-      const int64_t chunks = gigl_linear_weight_grad_chunks(t->rows_cap[l], n_out, k2, &t->part_rc[l]);
-      t->part_w[l] = (float*)alloc((size_t)chunks * n_out * k2 * 4);
-      t->part_b[l] = (float*)alloc((size_t)chunks * n_out * 4);
-      if (l >= 1) t->wt_l[l] = (float*)alloc((size_t)n_out * k2 * 4);
-      ok = t->part_w[l] && t->part_b[l] && (l == 0 || t->wt_l[l]);
-    }
-  }
+  // (measured, round 6: the loss sum on a BRANCH of the captured layers — forked after the loss rows, joined before Adam —
+  // took the step from 0.201 to 0.263 ms: a graph with a second branch is replayed through two queues with a barrier
+  // packet per edge.  The layers part stays one stream)
+  t->loss_slot = (float**)alloc(16);
+  ok = ok && t->zero_base && t->da && t->labels_buf && t->n_valid_buf && t->loss_rows && t->loss && t->loss_slot &&
+       hipMemset(t->n_valid_buf, 0, 16) == hipSuccess && hipMemset(t->loss_slot, 0, 16) == hipSuccess;
   if (!ok) {
     gigl_sage_train_plan_destroy(t);
     return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the training workspace failed");
@@ -1515,7 +1623,7 @@ int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* t, const uint32_t* root
                                    int32_t mode, float* loss_out) {
   if (!t) return GIGL_E_INVALID_ARG;
   gigl_ctx* ctx = t->ctx;
-  GIGL_REQUIRE(ctx, roots && labels && n_valid >= 1 && n_valid <= t->b, "bad argument");
+  GIGL_REQUIRE(ctx, roots && labels && n_valid >= 1 && n_valid <= t->enc.b, "bad argument");
   if (mode == GIGL_MODE_REPLACE)
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "the training plan needs duplicate-free trees (no with-replacement mode)");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -1543,31 +1651,25 @@ int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* t, const uint32_t* root
     t->fetched[kk] = true;
     t->fetched_roots[kk] = ahead[d];
   }
-  // the step's inputs go into the static buffers the (captured) launches read: labels, the number of real roots (a
-  // 32-bit fill: no host memory involved, ordered on the stream)
-  if (t->fused_small) {
-    TrainPrep pa{};
-    pa.zero = (uint32_t*)t->zero_base;
-    pa.zero_words = (int64_t)(t->zero_bytes / 4);
-    for (int l = 1; l < t->L; ++l) {
-      pa.w[pa.n_t] = t->w[l];
-      pa.wt[pa.n_t] = t->wt_l[l];
-      pa.rows[pa.n_t] = t->dims[l + 1];
-      pa.cols[pa.n_t] = 2 * t->dims[l];
-      ++pa.n_t;
-    }
-    pa.ticket = t->ticket;
-    int64_t blocks = (pa.zero_words + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 64) blocks = 64;
-    // (the layers of the previous step read labels_buf / the cleared block: this launch is behind them on the stream)
-    hipLaunchKernelGGL(train_stage_kernel, dim3((unsigned)blocks), dim3(256), 0, st, labels, n_valid, t->labels_buf, t->n_valid_buf,
-                       t->loss_slot, loss_out, pa);
-    GIGL_HIP_CHECK(ctx, hipGetLastError());
-  } else {
-    GIGL_HIP_CHECK(ctx, hipMemcpyAsync(t->labels_buf, labels, (size_t)n_valid * 8, hipMemcpyDeviceToDevice, st));
-    GIGL_HIP_CHECK(ctx, hipMemsetD32Async((hipDeviceptr_t)t->n_valid_buf, n_valid, 1, st));
+  // the step's inputs go into the static buffers the (captured) launches read — labels, the number of real roots, where the
+  // caller wants the loss (the loss kernel writes it there itself) — in the launch that also clears the dh block and lays out W_l^T
+  TrainPrep pa{};
+  pa.zero = (uint32_t*)t->zero_base;
+  pa.zero_words = (int64_t)(t->zero_bytes / 4);
+  for (int l = 1; l < t->L; ++l) {
+    pa.w[pa.n_t] = t->w[l];
+    pa.wt[pa.n_t] = t->wt_l[l];
+    pa.rows[pa.n_t] = t->dims[l + 1];
+    pa.cols[pa.n_t] = 2 * t->dims[l];
+    ++pa.n_t;
   }
+  int64_t blocks = (pa.zero_words + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 64) blocks = 64;
+  // (the layers of the previous step read labels_buf / the cleared block: this launch is behind them on the stream)
+  hipLaunchKernelGGL(train_stage_kernel, dim3((unsigned)blocks), dim3(256), 0, st, labels, n_valid, t->labels_buf, t->n_valid_buf,
+                     t->loss_slot, loss_out, pa);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
   GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, t->ev_graph[k], 0));
   if (t->lctx->stream != st || t->lctx->own_stream) {
     const int32_t rs = gigl_ctx_set_stream(t->lctx, st);
@@ -1577,8 +1679,6 @@ int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* t, const uint32_t* root
   if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
   GIGL_HIP_CHECK(ctx, hipEventRecord(t->ev_layers[k], st));
   t->cur = (k + 1) % TRAIN_WS;
-  // (fused: the loss kernel wrote loss_out itself, through the pointer slot the stage kernel set)
-  if (loss_out && !t->fused_small) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(loss_out, t->loss, 4, hipMemcpyDeviceToDevice, st));
   return GIGL_OK;
 }
 
@@ -1603,37 +1703,13 @@ int32_t gigl_sage_train_plan_resume(gigl_sage_train_plan* t) {
 // (1 + P) rooted trees, anchor-major (anchor, its P positive slots; a missing positive repeats the anchor and is masked
 // out by pos_cnt); random negatives = n_rn roots.  Everything is capacity-shaped (Q = b P query rows, C = Q + n_rn
 // candidates, validity masks on the device): no host read, no torch kernel, one captured hipGraph per step.
-struct gigl_nablp_train_plan {
+struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, dims, act_last and hyper-parameters only)
   gigl_ctx* ctx = nullptr;
   gigl_ctx* lctx = nullptr;  // private ctx (own arena) bound to the caller's stream: every launch of the step
-  struct Enc {
-    gigl_sage_plan* base = nullptr;  // tree / union workspace of this encode's roots
-    int32_t b = 0;
-    int64_t rows_cap[GIGL_MAX_HOPS] = {0};
-    float* a[GIGL_MAX_HOPS] = {nullptr};
-    float* h[GIGL_MAX_HOPS] = {nullptr};
-    float* dh[GIGL_MAX_HOPS] = {nullptr};
-    float* gw[GIGL_MAX_HOPS] = {nullptr};
-    float* gb[GIGL_MAX_HOPS] = {nullptr};
-    // (round 6) the weight gradients' per-chunk partial sums: added up inside the Adam kernel, no reduce launch per layer
-    float* part_w[GIGL_MAX_HOPS] = {nullptr};
-    float* part_b[GIGL_MAX_HOPS] = {nullptr};
-    int32_t part_rc[GIGL_MAX_HOPS] = {0};
-    float* emb = nullptr;   // [b][d_out]: the roots' embeddings (normalised when the model says so)
-    float* inv = nullptr;   // [b]: 1 / max(|h_r|, 1e-12) (1 without normalisation; 0: no such root)
-    float* demb = nullptr;  // [b][d_out]
-  } enc[2];                 // 0: main batch, 1: random negatives
-  int32_t L = 0, b = 0, P = 0, n_rn = 0, normalize = 0, remove_hits = 1, act_last = 0;
+  SageTrainEnc enc[2];       // 0: main batch, 1: random negatives
+  int32_t b = 0, P = 0, n_rn = 0, normalize = 0, remove_hits = 1;
   float temperature = 0.07f;
-  int32_t dims[GIGL_MAX_HOPS + 1] = {0};
-  float* w[GIGL_MAX_HOPS] = {nullptr};  // fused [dims[l+1]][2 dims[l]]: borrowed, UPDATED IN PLACE
-  float* bias[GIGL_MAX_HOPS] = {nullptr};
-  float* mom[4 * GIGL_MAX_HOPS] = {nullptr};
-  float* da = nullptr;
-  float* wt = nullptr;
-  bool fused_small = false;   // (SAGE encoder, GIGL_TRAIN_PLAN_UNFUSED unset) partial sums inside Adam, W^T once per step
-  float* wt_l[GIGL_MAX_HOPS] = {nullptr};
-  bool bwd_gather = false;    // (as in gigl_sage_train_plan)
+  float* da = nullptr;        // gradient of a layer's operand (SAGE)
   void* zero_base = nullptr;  // both encodes' gw | gb | dh: cleared at the start of every step
   size_t zero_bytes = 0;
   // the head: repeated queries, candidates, ids, validity, scores and their gradients
@@ -1643,7 +1719,6 @@ struct gigl_nablp_train_plan {
   int32_t* pos_cnt = nullptr;  // [b] static copy of the step's input
   int32_t* consts = nullptr;   // device {Q, C, Adam step, ...}
   float *row_lse = nullptr, *row_loss = nullptr, *loss = nullptr;  // loss[0] = the step's loss, loss[1] = valid query rows
-  float lr = 5e-3f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, wd = 0.f;
   // ---- GAT encoder (kind == 1, gigl_gat_nablp_train_plan_create): two layers, the first from the INPUT side
   int kind = 0;
   struct Gat {
@@ -1658,10 +1733,8 @@ struct gigl_nablp_train_plan {
     // forward state per encode: z [H][rows1][d], xw [rows1][c1], out_pre [b][c1]; backward scratch shared by both
     float *z[2] = {nullptr, nullptr}, *xw[2] = {nullptr, nullptr}, *out_pre[2] = {nullptr, nullptr};
     float *dxw = nullptr, *ds = nullptr, *dd = nullptr, *alpha = nullptr, *dh0 = nullptr, *dh0s = nullptr, *dz = nullptr;
-    // (round 6, as the SAGE plans: GIGL_TRAIN_PLAN_UNFUSED=1 for the A/B) the projections' weight gradients stay per-chunk partial
-    // sums — per encode: W1's, and W0's / b0's per head — added up inside the Adam kernel; W1^T and the heads' W0^T are laid
-    // out once per step
-    bool fused = false;
+    // (as the SAGE plans) the projections' weight gradients stay per-chunk partial sums — per encode: W1's, and W0's / b0's
+    // per head — added up inside the Adam kernel; W1^T and the heads' W0^T are laid out once per step
     float* part_w1[2] = {nullptr, nullptr};
     int32_t rc_w1[2] = {0, 0};
     float* part_w0[2][4] = {{nullptr}};
@@ -1706,7 +1779,6 @@ struct gigl_nablp_train_plan {
   gigl_ctx* wctx = nullptr;
   hipEvent_t ev_w = nullptr, ev_wjoin = nullptr;
   int cur = 0;
-  int cur_layers_ws = 0;  // the workspace the layers part being enqueued reads
   int32_t cap_seed = 0, cap_mode = -1;
 };
 
@@ -1961,153 +2033,26 @@ __global__ __launch_bounds__(256) void lp_unpack_scatter_kernel(const float* __r
   }
 }
 
-// Adam over the SUM of the two encodes' gradients (both forwards share the weights)
-constexpr int ADAM2_MAX = 16;  // tensors (or slices of tensors: the GAT plan's heads) per launch
-struct AdamPack2 {
-  float* p[ADAM2_MAX];
-  const float* g1[ADAM2_MAX];
-  const float* g2[ADAM2_MAX];
-  float* m[ADAM2_MAX];
-  float* v[ADAM2_MAX];
-  int64_t n[ADAM2_MAX];
-  // (round 6) part1 / part2 != NULL: the two encodes' gradients as per-chunk partial sums ([chunks][n], the chunks below
-  // ceil(*rows / rc) real), each added up in chunk order, then the two totals — the order of reduce + reduce + add; g1 may
-  // hold a further term beside them (the GAT plan: the folded attention vectors' share of W0's gradient)
-  const float* part1[ADAM2_MAX];
-  const float* part2[ADAM2_MAX];
-  const int32_t* rows1[ADAM2_MAX];
-  const int32_t* rows2[ADAM2_MAX];
-  int32_t rc1[ADAM2_MAX], rc2[ADAM2_MAX];
-  int32_t count;
-  float lr, beta1, beta2, eps, wd;
-};
-
-__device__ __forceinline__ float chunk_sum(const float* __restrict__ part, int chunks, int64_t n, int64_t i) {
-  float s = 0.f;
-  int c = 0;
-  for (; c + 15 < chunks; c += 16) {
-    float pv[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) pv[q] = part[(int64_t)(c + q) * n + i];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) s += pv[q];
-  }
-  for (; c < chunks; ++c) s += part[(int64_t)c * n + i];
-  return s;
-}
-
-__global__ __launch_bounds__(256) void lp_adam_kernel(AdamPack2 a, const int32_t* __restrict__ step_dev,
-                                                      const int32_t* __restrict__ meta_a, const int32_t* __restrict__ meta_b) {
-  if (meta_a[GIGL_META_OVERFLOW] != 0 || meta_b[GIGL_META_OVERFLOW] != 0) return;  // a failed batch trains nothing
-  const double t = (double)*step_dev;
-  const float bc1 = (float)(1.0 - pow((double)a.beta1, t)), bc2s = (float)sqrt(1.0 - pow((double)a.beta2, t));
-  const float step_size = a.lr / bc1;
-  const int k_lo = gridDim.y > 1 ? (int)blockIdx.y : 0, k_hi = gridDim.y > 1 ? (int)blockIdx.y + 1 : a.count;  // (a grid slice per tensor)
-  for (int k = k_lo; k < k_hi && k < a.count; ++k) {
-    float* p = a.p[k];
-    float* m = a.m[k];
-    float* v = a.v[k];
-    const int ch1 = a.part1[k] ? (*a.rows1[k] + a.rc1[k] - 1) / a.rc1[k] : 0;
-    const int ch2 = a.part2[k] ? (*a.rows2[k] + a.rc2[k] - 1) / a.rc2[k] : 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n[k]; i += (int64_t)gridDim.x * blockDim.x) {
-      const float w = p[i];
-      float ga = a.part1[k] ? chunk_sum(a.part1[k], ch1, a.n[k], i) : a.g1[k][i];
-      const float gb_ = a.part2[k] ? chunk_sum(a.part2[k], ch2, a.n[k], i) : (a.g2[k] ? a.g2[k][i] : 0.f);
-      if (a.part1[k] && a.g1[k]) ga += a.g1[k][i];
-      const float gr = (ga + gb_) + a.wd * w;
-      const float mm = m[i] + (gr - m[i]) * (1.f - a.beta1);
-      const float vv = v[i] * a.beta2 + (1.f - a.beta2) * gr * gr;
-      m[i] = mm;
-      v[i] = vv;
-      p[i] = w - step_size * (mm / (sqrtf(vv) / bc2s + a.eps));
-    }
-  }
-}
-
+// an encode's forward and the roots' embeddings; the random negatives' on the forked stream
 int32_t lp_forward(gigl_nablp_train_plan* t, int which) {
-  gigl_nablp_train_plan::Enc& e = t->enc[which];
-  gigl_sage_plan* p = e.base;
+  const SageTrainEnc& e = t->enc[which];
   gigl_ctx* ctx = which == 1 && t->fork ? t->actx : t->lctx;
-  const int L = t->L;
-  int32_t rc = GIGL_OK;
-  const int32_t* n_local = p->leaf_global ? (L >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (L - 2) : p->zero_dev) : nullptr;
-  for (int l = 0; l < L; ++l) {
-    const int32_t* n_rows = p->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
-    const int d = t->dims[l];
-    if (l == 0)
-      rc = gigl_gather_reduce_mixed(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col,
-                                    n_rows, e.rows_cap[0], GIGL_AGGR_MEAN, n_local, e.a[0]);
-    else
-      rc = gigl_gather_reduce(ctx, e.h[l - 1], GIGL_DTYPE_F32, d, nullptr, p->un.rowptr, p->un.rowend, p->un.col, n_rows,
-                              e.rows_cap[l], GIGL_AGGR_MEAN, e.a[l]);
-    if (rc != GIGL_OK) return rc;
-    rc = gigl_linear(ctx, e.a[l], t->w[l], t->bias[l], n_rows, e.rows_cap[l], 2 * d, t->dims[l + 1],
-                     (l < L - 1 || t->act_last) ? 1 : 0, e.h[l]);
-    if (rc != GIGL_OK) return rc;
-  }
-  const int dout = t->dims[L];
-  hipLaunchKernelGGL(lp_take_norm_kernel, dim3((unsigned)((e.b + 3) / 4)), dim3(256), 0, ctx->stream, (const float*)e.h[L - 1],
-                     (const int32_t*)p->un.root_local, e.b, dout, t->normalize, (const int32_t*)p->un.meta, e.emb, e.inv);
+  const int32_t rc = sage_enc_forward(ctx, *t, e, e.base);
+  if (rc != GIGL_OK) return rc;
+  hipLaunchKernelGGL(lp_take_norm_kernel, dim3((unsigned)((e.b + 3) / 4)), dim3(256), 0, ctx->stream, (const float*)e.h[t->L - 1],
+                     (const int32_t*)e.base->un.root_local, e.b, t->dims[t->L], t->normalize, (const int32_t*)e.base->un.meta, e.emb,
+                     e.inv);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
 
-int32_t lp_backward(gigl_nablp_train_plan* t, int which) {
-  gigl_nablp_train_plan::Enc& e = t->enc[which];
-  gigl_sage_plan* p = e.base;
-  gigl_ctx* ctx = which == 1 && t->fork ? t->actx : t->lctx;
-  float* da = which == 1 && t->fork ? t->da2 : t->da;
-  hipStream_t st = ctx->stream;
-  const int L = t->L;
-  int32_t rc = GIGL_OK;
-  for (int l = L - 1; l >= 0; --l) {
-    const int32_t* n_rows = p->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
-    const int d = t->dims[l], n_out = t->dims[l + 1];
-    const bool act = l < L - 1 || t->act_last;
-    const bool side_w = which == 0 && t->fork && t->wctx;  // (this gradient on the third stream: see wctx)
-    if (side_w) {
-      // the mask first (the chain needs the masked rows anyway), then the gradient of the MASKED rows beside the chain: the
-      // same products as the masked read of the unmasked rows
-      if (act) {
-        int64_t blocks = (e.rows_cap[l] * n_out + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, st, e.dh[l], (const float*)e.h[l], n_rows, n_out);
-      }
-      GIGL_HIP_CHECK(ctx, hipEventRecord(t->ev_w, st));
-      GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(t->wctx->stream, t->ev_w, 0));
-      rc = gigl_linear_weight_grad_parts(t->wctx, e.dh[l], e.a[l], nullptr, n_rows, e.rows_cap[l], n_out, 2 * d, e.part_w[l],
-                                         t->bias[l] ? e.part_b[l] : nullptr);
-    } else if (t->fused_small)
-      rc = gigl_linear_weight_grad_parts(ctx, e.dh[l], e.a[l], act ? e.h[l] : nullptr, n_rows, e.rows_cap[l], n_out, 2 * d,
-                                         e.part_w[l], t->bias[l] ? e.part_b[l] : nullptr);
-    else
-      rc = gigl_linear_weight_grad(ctx, e.dh[l], e.a[l], act ? e.h[l] : nullptr, n_rows, e.rows_cap[l], n_out, 2 * d, e.gw[l],
-                                   t->bias[l] ? e.gb[l] : nullptr);
-    if (rc != GIGL_OK) return rc;
-    if (l == 0) break;
-    if (act && !side_w) {
-      int64_t blocks = (e.rows_cap[l] * n_out + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, st, e.dh[l], (const float*)e.h[l], n_rows, n_out);
-    }
-    const float* wt = t->wt;
-    if (t->fused_small) {
-      wt = t->wt_l[l];  // (transposed ONCE per step, at the start of the layers: both encodes read it)
-    } else {
-      int64_t blocks = ((int64_t)n_out * 2 * d + 255) / 256;
-      hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)t->w[l], n_out, 2 * d, t->wt);
-    }
-    rc = gigl_linear(ctx, e.dh[l], wt, nullptr, n_rows, e.rows_cap[l], n_out, 2 * d, 0, da);
-    if (rc != GIGL_OK) return rc;
-    if (t->bwd_gather)
-      rc = gigl_gather_mean_backward_lists(ctx, da, d, p->un.rowptr, p->un.rowend, n_rows,
-                                           p->un.meta + GIGL_META_LEVEL0 + (L - l), e.rows_cap[l - 1],
-                                           t->work[t->cur_layers_ws].tlists[which][l], GIGL_AGGR_MEAN, e.dh[l - 1]);
-    else
-      rc = gigl_gather_mean_backward(ctx, da, d, p->un.rowptr, p->un.rowend, p->un.col, n_rows, e.rows_cap[l], e.dh[l - 1]);
-    if (rc != GIGL_OK) return rc;
-  }
-  return GIGL_OK;
+// an encode's backward over workspace w: the random negatives' on the forked stream with its own `da`, the main batch's
+// weight gradients on the third stream (see wctx)
+int32_t lp_backward(gigl_nablp_train_plan* t, int which, int w) {
+  const SageTrainEnc& e = t->enc[which];
+  const bool alt = which == 1 && t->fork;
+  return sage_enc_backward(alt ? t->actx : t->lctx, *t, e, e.base, t->work[w].tlists[which], alt ? t->da2 : t->da,
+                           which == 0 && t->fork ? t->wctx : nullptr, t->ev_w);
 }
 
 // every launch of a step, on lctx's stream (the caller's)
@@ -2116,16 +2061,10 @@ int32_t gat_lp_forward(gigl_nablp_train_plan* t, int which);
 int32_t gat_lp_backward(gigl_nablp_train_plan* t, int which);
 int32_t gat_lp_finish(gigl_nablp_train_plan* t);
 
-// sample + union of both root sets of workspace w, on its side stream
+// sample + union of both root sets of workspace w, on its side stream (bwd_gather is a SAGE encoder's: no lists for the GAT kind)
 int32_t lp_enqueue_graph(gigl_nablp_train_plan* t, int w, int32_t sampling_seed, int32_t mode) {
   for (int k = 0; k < 2; ++k) {
-    gigl_sage_plan* p = t->work[w].base[k];
-    int32_t rc = enqueue_range(p, 0, 2, p->roots_buf, sampling_seed, mode, nullptr);
-    // (SAGE: who reads which source row in the backward of layers >= 1 — a function of the batch graph alone)
-    for (int l = 1; l < t->L && rc == GIGL_OK && t->kind == 0 && t->bwd_gather; ++l)
-      rc = gigl_transposed_rows_build(p->ctx, p->un.rowptr, p->un.rowend, p->un.col, p->un.meta + GIGL_META_LEVEL0 + (t->L - 1 - l),
-                                      t->enc[k].rows_cap[l], p->un.meta + GIGL_META_LEVEL0 + (t->L - l),
-                                      t->enc[k].rows_cap[l - 1], p->un.cap_edges, t->work[w].tlists[k][l]);
+    const int32_t rc = sage_enqueue_graph(*t, t->enc[k], t->work[w].base[k], t->work[w].tlists[k], sampling_seed, mode);
     if (rc != GIGL_OK) return rc;
   }
   return GIGL_OK;
@@ -2138,13 +2077,12 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
   const int L = t->L, d = t->dims[L], Q = t->b * t->P, Cn = Q + t->n_rn;
   int32_t rc = GIGL_OK;
   for (int k = 0; k < 2; ++k) t->enc[k].base = t->work[w].base[k];
-  t->cur_layers_ws = w;
   gigl_fill_u32(st, t->zero_base, 0u, (int64_t)(t->zero_bytes / 4));
   if (t->kind == 1) {
     rc = gat_lp_begin(t);
     if (rc != GIGL_OK) return rc;
   }
-  for (int l = 1; l < L && t->fused_small; ++l) {  // W_l^T for the input gradients of both encodes
+  for (int l = 1; l < L && t->kind == 0; ++l) {  // W_l^T for the input gradients of both encodes
     const int64_t nw = (int64_t)t->dims[l + 1] * 2 * t->dims[l];
     hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, (const float*)t->w[l],
                        t->dims[l + 1], 2 * t->dims[l], t->wt_l[l]);
@@ -2188,7 +2126,7 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
   rc = gigl_linear_weight_grad(ctx, t->dscores, t->rq, nullptr, t->consts + 0, Q, Cn, d, t->d_cand, nullptr);
   if (rc != GIGL_OK) return rc;
   for (int k = 0; k < 2; ++k) {
-    const gigl_nablp_train_plan::Enc& e = t->enc[k];
+    const SageTrainEnc& e = t->enc[k];
     hipLaunchKernelGGL(lp_unpack_scatter_kernel, dim3((unsigned)((e.b + 3) / 4)), dim3(256), 0, st, (const float*)t->d_rq,
                        (const float*)t->d_cand, (const int32_t*)t->valid, (const float*)e.emb, (const float*)e.inv,
                        (const int32_t*)e.base->un.root_local, k, t->b, t->P, t->n_rn, d, t->normalize, e.dh[L - 1]);
@@ -2199,7 +2137,7 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
     GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(t->actx->stream, t->ev_fork[1], 0));
   }
   for (int k = 0; k < 2; ++k) {
-    rc = t->kind == 1 ? gat_lp_backward(t, k) : lp_backward(t, k);
+    rc = t->kind == 1 ? gat_lp_backward(t, k) : lp_backward(t, k, w);
     if (rc != GIGL_OK) return rc;
   }
   if (t->fork) {
@@ -2211,48 +2149,94 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
     }
   }
   if (t->kind == 1) return gat_lp_finish(t);
-  AdamPack2 ap{};
-  for (int l = 0; l < L; ++l) {
-    const bool fz = t->fused_small;
-    const int32_t* r1 = pm->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
-    const int32_t* r2 = pr->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
-    ap.p[ap.count] = t->w[l];
-    ap.g1[ap.count] = fz ? nullptr : t->enc[0].gw[l];
-    ap.g2[ap.count] = fz ? nullptr : t->enc[1].gw[l];
-    ap.part1[ap.count] = fz ? t->enc[0].part_w[l] : nullptr;
-    ap.part2[ap.count] = fz ? t->enc[1].part_w[l] : nullptr;
-    ap.rows1[ap.count] = r1;
-    ap.rows2[ap.count] = r2;
-    ap.rc1[ap.count] = t->enc[0].part_rc[l];
-    ap.rc2[ap.count] = t->enc[1].part_rc[l];
-    ap.m[ap.count] = t->mom[4 * l];
-    ap.v[ap.count] = t->mom[4 * l + 1];
-    ap.n[ap.count++] = (int64_t)t->dims[l + 1] * 2 * t->dims[l];
-    if (t->bias[l]) {
-      ap.p[ap.count] = t->bias[l];
-      ap.g1[ap.count] = fz ? nullptr : t->enc[0].gb[l];
-      ap.g2[ap.count] = fz ? nullptr : t->enc[1].gb[l];
-      ap.part1[ap.count] = fz ? t->enc[0].part_b[l] : nullptr;
-      ap.part2[ap.count] = fz ? t->enc[1].part_b[l] : nullptr;
-      ap.rows1[ap.count] = r1;
-      ap.rows2[ap.count] = r2;
-      ap.rc1[ap.count] = t->enc[0].part_rc[l];
-      ap.rc2[ap.count] = t->enc[1].part_rc[l];
-      ap.m[ap.count] = t->mom[4 * l + 2];
-      ap.v[ap.count] = t->mom[4 * l + 3];
-      ap.n[ap.count++] = t->dims[l + 1];
-    }
-  }
-  ap.lr = t->lr;
-  ap.beta1 = t->beta1;
-  ap.beta2 = t->beta2;
-  ap.eps = t->eps;
-  ap.wd = t->wd;
-  hipLaunchKernelGGL(lp_adam_kernel, t->fused_small ? dim3(208, (unsigned)ap.count) : dim3(256), dim3(256), 0, st, ap,
-                     (const int32_t*)(t->consts + 2),
-                     (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta);
+  const AdamPack ap = sage_adam_pack(*t, &t->enc[0], pm, &t->enc[1], pr);
+  hipLaunchKernelGGL(adam_kernel, dim3(208, (unsigned)ap.count), dim3(256), 0, st, ap, (const int32_t*)(t->consts + 2),
+                     (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta, (const int32_t*)nullptr);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
+}
+
+// ---- what the two link-prediction plans' creation shares (t->ctx, b, P, n_rn are set)
+
+// the layers' ctx and, per workspace, a side ctx, the two root sets' tree / union workspaces (base plans: their own layer
+// buffers stay unused) and its events; "the caller's stream, now"
+int32_t lp_create_workspaces(gigl_nablp_train_plan* t, gigl_graph* graph, gigl_feat* feat, const int32_t* fanouts, int32_t hops,
+                             const int32_t* dims, float* const* w, float* const* bias, int32_t act_last) {
+  gigl_ctx* ctx = t->ctx;
+  int32_t rc = gigl_ctx_create(ctx->device, &t->lctx);
+  const int32_t nb[2] = {t->b * (1 + t->P), t->n_rn > 0 ? t->n_rn : 1};
+  for (int wi = 0; wi < gigl_nablp_train_plan::WS && rc == GIGL_OK; ++wi) {
+    gigl_nablp_train_plan::Work& wk = t->work[wi];
+    rc = gigl_ctx_create(ctx->device, &wk.side);
+    if (rc == GIGL_OK) wk.side->wide = ctx->wide;
+    for (int k = 0; k < 2 && rc == GIGL_OK; ++k) {
+      t->enc[k].b = nb[k];
+      rc = plan_create(wk.side, graph, feat, nb[k], fanouts, hops, dims, (const float* const*)w, (const float* const*)bias,
+                       act_last, false, &wk.base[k]);
+      if (rc != GIGL_OK) gigl_fail(ctx, rc, "%s", gigl_last_error(wk.side));
+    }
+    if (rc == GIGL_OK && (hipEventCreateWithFlags(&wk.ev_graph, hipEventDisableTiming) != hipSuccess ||
+                          hipEventCreateWithFlags(&wk.ev_layers, hipEventDisableTiming) != hipSuccess))
+      rc = GIGL_E_HIP;
+  }
+  if (rc == GIGL_OK && hipEventCreateWithFlags(&t->ev_now, hipEventDisableTiming) != hipSuccess) rc = GIGL_E_HIP;
+  if (rc == GIGL_OK)
+    for (int k = 0; k < 2; ++k) t->enc[k].base = t->work[0].base[k];
+  return rc;
+}
+
+// the head over embeddings of width d: the encodes' root rows, repeated queries, candidates, ids, validity, scores, their
+// gradients, the loss words; consts = {Q, C, Adam's step counter}
+bool lp_head_alloc(gigl_nablp_train_plan* t, size_t d) {
+  auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
+  const size_t Q = (size_t)t->b * t->P, Cn = Q + (size_t)t->n_rn;
+  bool ok = true;
+  for (SageTrainEnc& e : t->enc) {
+    e.emb = (float*)alloc((size_t)e.b * d * 4);
+    e.inv = (float*)alloc((size_t)e.b * 4);
+    ok = ok && e.emb && e.inv;
+  }
+  t->rq = (float*)alloc(Q * d * 4);
+  t->cand = (float*)alloc(Cn * d * 4);
+  t->cand_t = (float*)alloc(Cn * d * 4);
+  t->scores = (float*)alloc(Q * Cn * 4);
+  t->dscores = (float*)alloc(Q * Cn * 4);
+  t->d_rq = (float*)alloc(Q * d * 4);
+  t->d_cand = (float*)alloc(Cn * d * 4);
+  t->qid = (int64_t*)alloc(Q * 8);
+  t->cid = (int64_t*)alloc(Cn * 8);
+  t->valid = (int32_t*)alloc(Cn * 4);
+  t->pos_cnt = (int32_t*)alloc((size_t)t->b * 4);
+  t->consts = (int32_t*)alloc(64);
+  t->row_lse = (float*)alloc(Q * 4);
+  t->row_loss = (float*)alloc(Q * 4);
+  t->loss = (float*)alloc(64);
+  ok = ok && t->rq && t->cand && t->cand_t && t->scores && t->dscores && t->d_rq && t->d_cand && t->qid && t->cid && t->valid &&
+       t->pos_cnt && t->consts && t->row_lse && t->row_loss && t->loss;
+  const int32_t c[16] = {(int32_t)Q, (int32_t)Cn, 0 /* Adam's step counter */, 0};
+  return ok && hipMemcpy(t->consts, c, sizeof(c), hipMemcpyHostToDevice) == hipSuccess && hipMemset(t->loss, 0, 64) == hipSuccess;
+}
+
+// (default on, GIGL_LP_FORK=0 off) the random negatives' encode on a stream of its own
+bool lp_fork_wanted(const gigl_nablp_train_plan* t) {
+  const char* fork_env = getenv("GIGL_LP_FORK");
+  return t->n_rn > 0 && !(fork_env && fork_env[0] == '0');
+}
+
+// the forked streams' ctxs and events (the second encode's own scratch is its plan's business); -> t->fork
+bool lp_fork_setup(gigl_nablp_train_plan* t) {
+  bool ok = gigl_ctx_create(t->ctx->device, &t->actx) == GIGL_OK;
+  for (int i = 0; i < 2 && ok; ++i)
+    ok = hipEventCreateWithFlags(&t->ev_fork[i], hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&t->ev_join[i], hipEventDisableTiming) == hipSuccess;
+  const char* w_env = getenv("GIGL_LP_WGRAD_STREAM");  // (=0: the main batch's weight gradients stay in its chain)
+  // (the GAT plan's 768-wide weight gradients fill the GPU and slow the chain beside them: measured, see gat_lp_backward)
+  if (ok && t->kind == 0 && !(w_env && w_env[0] == '0'))
+    ok = gigl_ctx_create(t->ctx->device, &t->wctx) == GIGL_OK &&
+         hipEventCreateWithFlags(&t->ev_w, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&t->ev_wjoin, hipEventDisableTiming) == hipSuccess;
+  t->fork = ok;
+  return ok;
 }
 
 }  // namespace
@@ -2323,146 +2307,30 @@ int32_t gigl_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat
   t->beta2 = beta2;
   t->eps = eps;
   t->wd = weight_decay;
-  int32_t rc = gigl_ctx_create(ctx->device, &t->lctx);
-  const int32_t nb[2] = {b_anchors * (1 + num_positives), n_random_negatives > 0 ? n_random_negatives : 1};
-  for (int wi = 0; wi < gigl_nablp_train_plan::WS && rc == GIGL_OK; ++wi) {
-    gigl_nablp_train_plan::Work& wk = t->work[wi];
-    rc = gigl_ctx_create(ctx->device, &wk.side);
-    if (rc == GIGL_OK) wk.side->wide = ctx->wide;
-    for (int k = 0; k < 2 && rc == GIGL_OK; ++k) {
-      t->enc[k].b = nb[k];
-      rc = plan_create(wk.side, graph, feat, nb[k], fanouts, hops, dims, (const float* const*)w, (const float* const*)bias,
-                       act_last, false, &wk.base[k]);
-      if (rc != GIGL_OK) gigl_fail(ctx, rc, "%s", gigl_last_error(wk.side));
-    }
-    if (rc == GIGL_OK && (hipEventCreateWithFlags(&wk.ev_graph, hipEventDisableTiming) != hipSuccess ||
-                          hipEventCreateWithFlags(&wk.ev_layers, hipEventDisableTiming) != hipSuccess))
-      rc = GIGL_E_HIP;
-  }
-  if (rc == GIGL_OK && hipEventCreateWithFlags(&t->ev_now, hipEventDisableTiming) != hipSuccess) rc = GIGL_E_HIP;
-  if (rc == GIGL_OK)
-    for (int k = 0; k < 2; ++k) t->enc[k].base = t->work[0].base[k];
+  const int32_t rc = lp_create_workspaces(t, graph, feat, fanouts, hops, dims, w, bias, act_last);
   if (rc != GIGL_OK) {
     gigl_nablp_train_plan_destroy(t);
     return rc;
   }
-  auto alloc = [&](size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    t->owned.push_back(q);
-    return q;
-  };
-  bool ok = true;
-  size_t zero_floats = 0, da_floats = 16, wt_floats = 16;
-  for (int l = 0; l <= hops; ++l) t->dims[l] = dims[l];
-  t->bwd_gather = train_bwd_gather(dims, hops);
-  for (int l = 0; l < hops; ++l) {
-    t->w[l] = w[l];
-    t->bias[l] = bias ? bias[l] : nullptr;
-    const size_t nw = (size_t)dims[l + 1] * 2 * dims[l];
-    wt_floats = std::max(wt_floats, nw);
-    for (int k = 0; k < 4; ++k) {
-      const size_t n = k < 2 ? nw : (size_t)dims[l + 1];
-      t->mom[4 * l + k] = (float*)alloc(n * 4);
-      if (t->mom[4 * l + k] && hipMemset(t->mom[4 * l + k], 0, n * 4) != hipSuccess) ok = false;
-      ok = ok && t->mom[4 * l + k];
-    }
-    for (int k = 0; k < 2; ++k) {
-      gigl_nablp_train_plan::Enc& e = t->enc[k];
-      const int64_t rows = gigl_level_rows(ctx->wide, e.b, fanouts, hops, hops - 1 - l);
-      e.rows_cap[l] = rows;
-      zero_floats += nw + dims[l + 1] + (t->bwd_gather && l < hops - 1 ? 0 : (size_t)rows * dims[l + 1]);
-      if (l >= 1) da_floats = std::max(da_floats, (size_t)rows * 2 * dims[l]);
-      e.a[l] = (float*)alloc((size_t)rows * 2 * dims[l] * 4);
-      e.h[l] = (float*)alloc((size_t)rows * dims[l + 1] * 4);
-      ok = ok && e.a[l] && e.h[l];
-    }
-  }
+  auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
+  size_t zero_floats = 0, da_floats = 16;
+  bool ok = sage_shared_alloc(*t, t->owned, dims, w, bias);
+  // (gw | gb are part of the cleared block: gigl_nablp_train_plan_grads adds the partial sums up into them)
+  for (SageTrainEnc& e : t->enc) ok = sage_enc_alloc(*t, e, t->owned, ctx->wide, fanouts, true, &zero_floats, &da_floats) && ok;
   float* z = (float*)alloc(zero_floats * 4);
   t->zero_base = z;
   t->zero_bytes = zero_floats * 4;
-  for (int k = 0; k < 2 && z; ++k)
-    for (int l = 0; l < hops; ++l) {
-      gigl_nablp_train_plan::Enc& e = t->enc[k];
-      e.gw[l] = z;
-      z += (size_t)dims[l + 1] * 2 * dims[l];
-      e.gb[l] = z;
-      z += dims[l + 1];
-      if (t->bwd_gather && l < hops - 1) {
-        e.dh[l] = (float*)alloc((size_t)e.rows_cap[l] * dims[l + 1] * 4);
-        ok = ok && e.dh[l];
-        continue;
-      }
-      e.dh[l] = z;
-      z += (size_t)e.rows_cap[l] * dims[l + 1];
-    }
-  for (int wi = 0; wi < gigl_nablp_train_plan::WS && t->bwd_gather; ++wi)
-    for (int k = 0; k < 2; ++k)
-      for (int l = 1; l < hops; ++l) {
-        t->work[wi].tlists[k][l] = (int32_t*)alloc(
-            (size_t)gigl_transposed_rows_words(t->enc[k].rows_cap[l - 1], t->work[wi].base[k]->un.cap_edges) * 4);
-        ok = ok && t->work[wi].tlists[k][l];
-      }
-  const size_t d = (size_t)dims[hops], Q = (size_t)b_anchors * num_positives, Cn = Q + (size_t)t->n_rn;
-  for (int k = 0; k < 2; ++k) {
-    gigl_nablp_train_plan::Enc& e = t->enc[k];
-    e.emb = (float*)alloc((size_t)e.b * d * 4);
-    e.inv = (float*)alloc((size_t)e.b * 4);
-    ok = ok && e.emb && e.inv;
-  }
+  for (int k = 0; k < 2 && z; ++k) z = sage_enc_carve(*t, t->enc[k], true, z);
+  for (auto& wk : t->work)
+    for (int k = 0; k < 2; ++k) ok = sage_tlists_alloc(*t, t->enc[k], t->owned, wk.base[k]->un.cap_edges, wk.tlists[k]) && ok;
   t->da = (float*)alloc(da_floats * 4);
-  t->wt = (float*)alloc(wt_floats * 4);
-  t->rq = (float*)alloc(Q * d * 4);
-  t->cand = (float*)alloc(Cn * d * 4);
-  t->cand_t = (float*)alloc(Cn * d * 4);
-  t->scores = (float*)alloc(Q * Cn * 4);
-  t->dscores = (float*)alloc(Q * Cn * 4);
-  t->d_rq = (float*)alloc(Q * d * 4);
-  t->d_cand = (float*)alloc(Cn * d * 4);
-  t->qid = (int64_t*)alloc(Q * 8);
-  t->cid = (int64_t*)alloc(Cn * 8);
-  t->valid = (int32_t*)alloc(Cn * 4);
-  t->pos_cnt = (int32_t*)alloc((size_t)b_anchors * 4);
-  t->consts = (int32_t*)alloc(64);
-  t->row_lse = (float*)alloc(Q * 4);
-  t->row_loss = (float*)alloc(Q * 4);
-  t->loss = (float*)alloc(64);
-  ok = ok && t->zero_base && t->da && t->wt && t->rq && t->cand && t->cand_t && t->scores && t->dscores && t->d_rq &&
-       t->d_cand && t->qid && t->cid && t->valid && t->pos_cnt && t->consts && t->row_lse && t->row_loss && t->loss;
-  t->fused_small = getenv("GIGL_TRAIN_PLAN_UNFUSED") == nullptr;
-  for (int l = 0; l < hops && ok && t->fused_small; ++l) {
-    const int n_out = dims[l + 1], k2 = 2 * dims[l];
-    for (int k = 0; k < 2 && ok; ++k) {
-      gigl_nablp_train_plan::Enc& e = t->enc[k];
-      const int64_t chunks = gigl_linear_weight_grad_chunks(e.rows_cap[l], n_out, k2, &e.part_rc[l]);
-      e.part_w[l] = (float*)alloc((size_t)chunks * n_out * k2 * 4);
-      e.part_b[l] = (float*)alloc((size_t)chunks * n_out * 4);
-      ok = e.part_w[l] && e.part_b[l];
-    }
-    if (l >= 1) t->wt_l[l] = (float*)alloc((size_t)n_out * k2 * 4);
-    ok = ok && (l == 0 || t->wt_l[l]);
-  }
-  // (default on, GIGL_LP_FORK=0 off: 1.18 -> 1.07 ms per step, bit-identical results.  The forked step's layers part is
+  ok = ok && t->zero_base && t->da && lp_head_alloc(t, (size_t)dims[hops]);
+  // (GIGL_LP_FORK=0 off: 1.18 -> 1.07 ms per step, bit-identical results.  The forked step's layers part is
   // launched EAGERLY, not replayed: captured, the two-branch graph brought the whole GPU suite down with a segmentation fault
   // inside a step — ~400 tests into the session, three runs of three — and never in six runs once it was launched eagerly)
-  const char* fork_env = getenv("GIGL_LP_FORK");
-  if (ok && t->fused_small && t->n_rn > 0 && !(fork_env && fork_env[0] == '0')) {
+  if (ok && lp_fork_wanted(t)) {
     t->da2 = (float*)alloc(da_floats * 4);
-    ok = t->da2 != nullptr && gigl_ctx_create(ctx->device, &t->actx) == GIGL_OK;
-    for (int i = 0; i < 2 && ok; ++i)
-      ok = hipEventCreateWithFlags(&t->ev_fork[i], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&t->ev_join[i], hipEventDisableTiming) == hipSuccess;
-    const char* w_env = getenv("GIGL_LP_WGRAD_STREAM");  // (=0: the main batch's weight gradients stay in its chain)
-    if (ok && t->kind == 0 && !(w_env && w_env[0] == '0'))
-      ok = gigl_ctx_create(ctx->device, &t->wctx) == GIGL_OK &&
-           hipEventCreateWithFlags(&t->ev_w, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&t->ev_wjoin, hipEventDisableTiming) == hipSuccess;
-    t->fork = ok;
-  }
-  if (ok) {
-    const int32_t c[16] = {(int32_t)Q, (int32_t)Cn, 0 /* Adam's step counter */, 0};
-    if (hipMemcpy(t->consts, c, sizeof(c), hipMemcpyHostToDevice) != hipSuccess || hipMemset(t->loss, 0, 64) != hipSuccess)
-      ok = false;
+    ok = t->da2 != nullptr && lp_fork_setup(t);
   }
   if (!ok) {
     gigl_nablp_train_plan_destroy(t);
@@ -2508,7 +2376,7 @@ int32_t gigl_nablp_train_plan_step2(gigl_nablp_train_plan* t, const uint32_t* ma
   if (mode == GIGL_MODE_REPLACE)
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "the training plan needs duplicate-free trees (no with-replacement mode)");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  t->gat.parts_pending = t->kind == 1 && t->gat.fused;  // (this step's gradient buffers will lack the partial sums)
+  t->gat.parts_pending = t->kind == 1;  // (this step's gradient buffers will lack the partial sums)
   hipStream_t st = ctx->stream;
   if (t->lctx->stream != st || t->lctx->own_stream) {
     const int32_t rs = gigl_ctx_set_stream(t->lctx, st);
@@ -2573,50 +2441,32 @@ int32_t gigl_sage_train_plan_moments(gigl_sage_train_plan* t, int32_t layer, flo
   gigl_ctx* ctx = t->ctx;
   GIGL_REQUIRE(ctx, layer >= 0 && layer < t->L, "layer %d", layer);
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t nw = (size_t)t->dims[layer + 1] * 2 * t->dims[layer], nb = (size_t)t->dims[layer + 1];
-  float* dst[4] = {m_w, v_w, m_b, v_b};
-  for (int k = 0; k < 4; ++k)
-    if (dst[k])
-      GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst[k], t->mom[4 * layer + k], (k < 2 ? nw : nb) * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  return GIGL_OK;
+  const int32_t rc = sage_moments_copy(ctx, *t, 2 * layer, m_w, v_w);
+  return rc != GIGL_OK ? rc : sage_moments_copy(ctx, *t, 2 * layer + 1, m_b, v_b);
 }
 
 int32_t gigl_nablp_train_plan_moments(gigl_nablp_train_plan* t, int32_t index, float* m, float* v) {
   if (!t) return GIGL_E_INVALID_ARG;
   gigl_ctx* ctx = t->ctx;
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const float *sm = nullptr, *sv = nullptr;
-  size_t n = 0;
-  if (t->kind == 1) {
-    GIGL_REQUIRE(ctx, index >= 0 && index < 8, "tensor %d", index);
-    sm = t->gat.mom[2 * index];
-    sv = t->gat.mom[2 * index + 1];
-    n = (size_t)t->gat.n[index];
-  } else {
+  if (t->kind == 0) {
     GIGL_REQUIRE(ctx, index >= 0 && index < 2 * t->L, "tensor %d", index);
-    const int l = index >> 1, bias = index & 1;
-    sm = t->mom[4 * l + 2 * bias];
-    sv = t->mom[4 * l + 2 * bias + 1];
-    n = bias ? (size_t)t->dims[l + 1] : (size_t)t->dims[l + 1] * 2 * t->dims[l];
+    return sage_moments_copy(ctx, *t, index, m, v);
   }
-  if (m && n) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(m, sm, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  if (v && n) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(v, sv, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  GIGL_REQUIRE(ctx, index >= 0 && index < 8, "tensor %d", index);
+  const size_t n = (size_t)t->gat.n[index];
+  if (m && n) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(m, t->gat.mom[2 * index], n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  if (v && n) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(v, t->gat.mom[2 * index + 1], n * 4, hipMemcpyDeviceToDevice, ctx->stream));
   return GIGL_OK;
 }
 
 int32_t gigl_sage_train_plan_adopt(gigl_sage_train_plan* dst, gigl_sage_train_plan* src) {
   if (!dst || !src) return GIGL_E_INVALID_ARG;
   gigl_ctx* ctx = dst->ctx;
-  GIGL_REQUIRE(ctx, dst->L == src->L, "plans of different depth");
-  for (int l = 0; l <= dst->L; ++l) GIGL_REQUIRE(ctx, dst->dims[l] == src->dims[l], "plans of different widths");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   GIGL_HIP_CHECK(ctx, hipStreamSynchronize(src->ctx->stream));
-  for (int l = 0; l < dst->L; ++l) {
-    const size_t nw = (size_t)dst->dims[l + 1] * 2 * dst->dims[l];
-    for (int k = 0; k < 4; ++k)
-      GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->mom[4 * l + k], src->mom[4 * l + k], (k < 2 ? nw : (size_t)dst->dims[l + 1]) * 4,
-                                         hipMemcpyDeviceToDevice, ctx->stream));
-  }
+  const int32_t rc = sage_moments_adopt(ctx, *dst, *src);
+  if (rc != GIGL_OK) return rc;
   GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->n_valid_buf + 1, src->n_valid_buf + 1, 4, hipMemcpyDeviceToDevice, ctx->stream));
   GIGL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return GIGL_OK;
@@ -2636,13 +2486,8 @@ int32_t gigl_nablp_train_plan_adopt(gigl_nablp_train_plan* dst, gigl_nablp_train
                                            (size_t)(dst->gat.n[i] ? dst->gat.n[i] : 1) * 4, hipMemcpyDeviceToDevice, ctx->stream));
     }
   } else {
-    for (int l = 0; l <= dst->L; ++l) GIGL_REQUIRE(ctx, dst->dims[l] == src->dims[l], "plans of different widths");
-    for (int l = 0; l < dst->L; ++l) {
-      const size_t nw = (size_t)dst->dims[l + 1] * 2 * dst->dims[l];
-      for (int k = 0; k < 4; ++k)
-        GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->mom[4 * l + k], src->mom[4 * l + k], (k < 2 ? nw : (size_t)dst->dims[l + 1]) * 4,
-                                           hipMemcpyDeviceToDevice, ctx->stream));
-    }
+    const int32_t rc = sage_moments_adopt(ctx, *dst, *src);
+    if (rc != GIGL_OK) return rc;
   }
   GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->consts + 2, src->consts + 2, 4, hipMemcpyDeviceToDevice, ctx->stream));
   GIGL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2655,17 +2500,14 @@ int32_t gigl_nablp_train_plan_grads(gigl_nablp_train_plan* t, int32_t layer, flo
   GIGL_REQUIRE(ctx, t->kind == 0 && layer >= 0 && layer < t->L && gw, "bad plan / layer / null output");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int64_t nw = (int64_t)t->dims[layer + 1] * 2 * t->dims[layer];
-  if (t->fused_small) {  // the step kept partial sums only: add them up now, into the (cleared) gradient buffers
-    for (int k = 0; k < 2; ++k) {
-      gigl_nablp_train_plan::Enc& e = t->enc[k];
-      gigl_fill_u32(ctx->stream, e.gw[layer], 0u, nw);
-      if (t->bias[layer]) gigl_fill_u32(ctx->stream, e.gb[layer], 0u, (int64_t)t->dims[layer + 1]);
-      const int32_t rc = gigl_linear_weight_grad_sum(ctx, e.part_w[layer], t->bias[layer] ? e.part_b[layer] : nullptr,
-                                                     e.base->un.meta + GIGL_META_LEVEL0 + (t->L - 1 - layer), t->dims[layer + 1],
-                                                     2 * t->dims[layer], e.part_rc[layer], e.gw[layer],
-                                                     t->bias[layer] ? e.gb[layer] : nullptr);
-      if (rc != GIGL_OK) return rc;
-    }
+  for (const SageTrainEnc& e : t->enc) {  // the step kept partial sums only: add them up now, into the (cleared) gradient buffers
+    gigl_fill_u32(ctx->stream, e.gw[layer], 0u, nw);
+    if (t->bias[layer]) gigl_fill_u32(ctx->stream, e.gb[layer], 0u, (int64_t)t->dims[layer + 1]);
+    const int32_t rc = gigl_linear_weight_grad_sum(ctx, e.part_w[layer], t->bias[layer] ? e.part_b[layer] : nullptr,
+                                                   e.base->un.meta + GIGL_META_LEVEL0 + (t->L - 1 - layer), t->dims[layer + 1],
+                                                   2 * t->dims[layer], e.part_rc[layer], e.gw[layer],
+                                                   t->bias[layer] ? e.gb[layer] : nullptr);
+    if (rc != GIGL_OK) return rc;
   }
   hipLaunchKernelGGL(lp_add2_kernel, dim3(256), dim3(256), 0, ctx->stream, (const float*)t->enc[0].gw[layer],
                      (const float*)t->enc[1].gw[layer], nw, gw);
@@ -2776,21 +2618,20 @@ int32_t gat_lp_begin(gigl_nablp_train_plan* t) {
   hipLaunchKernelGGL(gat_fold_kernel, dim3((unsigned)(2 * g.heads), (unsigned)((g.d_in + 63) / 64)), dim3(256), 0,
                      t->lctx->stream, (const float*)g.w[0],
                      (const float*)g.att_src[0], (const float*)g.att_dst[0], g.heads, g.c0, g.d_in, g.u);
-  if (g.fused) {  // W1^T and the heads' W0^T for the input gradients of both encodes
-    hipStream_t st = t->lctx->stream;
-    const int HC = g.heads * g.c0;
-    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(((int64_t)g.c1 * HC + 255) / 256)), dim3(256), 0, st, (const float*)g.w[1],
-                       g.c1, HC, g.wt1);
-    for (int h = 0; h < g.heads; ++h)
-      hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(((int64_t)g.c0 * g.d_in + 255) / 256)), dim3(256), 0, st,
-                         (const float*)(g.w[0] + (int64_t)h * g.c0 * g.d_in), g.c0, g.d_in, g.wt0[h]);
-  }
+  // W1^T and the heads' W0^T for the input gradients of both encodes
+  hipStream_t st = t->lctx->stream;
+  const int HC = g.heads * g.c0;
+  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(((int64_t)g.c1 * HC + 255) / 256)), dim3(256), 0, st, (const float*)g.w[1],
+                     g.c1, HC, g.wt1);
+  for (int h = 0; h < g.heads; ++h)
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(((int64_t)g.c0 * g.d_in + 255) / 256)), dim3(256), 0, st,
+                       (const float*)(g.w[0] + (int64_t)h * g.c0 * g.d_in), g.c0, g.d_in, g.wt0[h]);
   GIGL_HIP_CHECK(t->lctx, hipGetLastError());
   return GIGL_OK;
 }
 
 int32_t gat_lp_forward(gigl_nablp_train_plan* t, int which) {
-  gigl_nablp_train_plan::Enc& e = t->enc[which];
+  SageTrainEnc& e = t->enc[which];
   gigl_sage_plan* p = e.base;
   const bool alt = which == 1 && t->fork;
   gigl_ctx* ctx = alt ? t->actx : t->lctx;
@@ -2825,7 +2666,7 @@ int32_t gat_lp_forward(gigl_nablp_train_plan* t, int which) {
 }
 
 int32_t gat_lp_backward(gigl_nablp_train_plan* t, int which) {
-  gigl_nablp_train_plan::Enc& e = t->enc[which];
+  SageTrainEnc& e = t->enc[which];
   gigl_sage_plan* p = e.base;
   const bool alt = which == 1 && t->fork;
   gigl_ctx* ctx = alt ? t->actx : t->lctx;
@@ -2839,9 +2680,8 @@ int32_t gat_lp_backward(gigl_nablp_train_plan* t, int which) {
   const int64_t rows1 = gat_rows1(t, which);
   const int32_t* n0 = p->un.meta + GIGL_META_LEVEL0;
   const int32_t* n1 = p->un.meta + GIGL_META_LEVEL0 + 1;
-  float *gw0 = gg[0], *gas0 = gg[1], *gad0 = gg[2], *gb0 = gg[3], *gw1 = gg[4], *gas1 = gg[5], *gad1 = gg[6], *gb1 = gg[7];
-  (void)gas0;
-  (void)gad0;
+  // (gg[0..4] — W0, its attention vectors, b0, W1 — come from the partial sums and the fold's backward)
+  float *gas1 = gg[5], *gad1 = gg[6], *gb1 = gg[7];
   // ---- second layer (the roots' rows): e.dh[1] = d loss / d (out before the bias)
   if (g.bias[1])
     hipLaunchKernelGGL(gat_bias_grad_kernel, dim3((unsigned)((e.rows_cap[1] + 7) / 8)), dim3(256), 0, st, (const float*)e.dh[1],
@@ -2857,14 +2697,9 @@ int32_t gat_lp_backward(gigl_nablp_train_plan* t, int which) {
   if (rc != GIGL_OK) return rc;
   // (measured: the main batch's weight gradients on a third stream, as the GraphSAGE plan runs them — 1.75 against 1.71 ms:
   // these 768-wide ones fill the GPU and slow the chain beside them)
-  if (g.fused) rc = gigl_linear_weight_grad_parts(ctx, s_dxw, e.h[0], nullptr, n1, rows1, C1, HC, g.part_w1[which], nullptr);
-  else rc = gigl_linear_weight_grad(ctx, s_dxw, e.h[0], nullptr, n1, rows1, C1, HC, gw1, nullptr);
+  rc = gigl_linear_weight_grad_parts(ctx, s_dxw, e.h[0], nullptr, n1, rows1, C1, HC, g.part_w1[which], nullptr);
   if (rc != GIGL_OK) return rc;
-  if (!g.fused) {
-    int64_t blocks = ((int64_t)C1 * HC + 255) / 256;
-    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)g.w[1], C1, HC, t->wt);
-  }
-  rc = gigl_linear(ctx, s_dxw, g.fused ? g.wt1 : t->wt, nullptr, n1, rows1, C1, HC, 0, s_dh0);
+  rc = gigl_linear(ctx, s_dxw, g.wt1, nullptr, n1, rows1, C1, HC, 0, s_dh0);
   if (rc != GIGL_OK) return rc;
   // ---- first layer: relu mask, the heads' slices, their projections' backward, the attention-weighted sums' backward
   {
@@ -2875,19 +2710,10 @@ int32_t gat_lp_backward(gigl_nablp_train_plan* t, int which) {
   }
   for (int h = 0; h < H; ++h) {
     const float* dyh = s_dh0s + (int64_t)h * rows1 * C0;
-    if (g.fused)
-      rc = gigl_linear_weight_grad_parts(ctx, dyh, g.z[which] + (int64_t)h * rows1 * d, nullptr, n1, rows1, C0, d,
-                                         g.part_w0[which][h], g.bias[0] ? g.part_b0[which][h] : nullptr);
-    else
-      rc = gigl_linear_weight_grad(ctx, dyh, g.z[which] + (int64_t)h * rows1 * d, nullptr, n1, rows1, C0, d,
-                                   gw0 + (int64_t)h * C0 * d, g.bias[0] ? gb0 + h * C0 : nullptr);
+    rc = gigl_linear_weight_grad_parts(ctx, dyh, g.z[which] + (int64_t)h * rows1 * d, nullptr, n1, rows1, C0, d,
+                                       g.part_w0[which][h], g.bias[0] ? g.part_b0[which][h] : nullptr);
     if (rc != GIGL_OK) return rc;
-    if (!g.fused) {
-      int64_t blocks = ((int64_t)C0 * d + 255) / 256;
-      hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)(g.w[0] + (int64_t)h * C0 * d),
-                         C0, d, t->wt);
-    }
-    rc = gigl_linear(ctx, dyh, g.fused ? g.wt0[h] : t->wt, nullptr, n1, rows1, C0, d, 0, s_dz + (int64_t)h * rows1 * d);
+    rc = gigl_linear(ctx, dyh, g.wt0[h], nullptr, n1, rows1, C0, d, 0, s_dz + (int64_t)h * rows1 * d);
     if (rc != GIGL_OK) return rc;
   }
   rc = gigl_gat_input_aggregate_backward(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
@@ -2906,48 +2732,48 @@ int32_t gat_lp_finish(gigl_nablp_train_plan* t) {
   hipLaunchKernelGGL(gat_fold_backward_kernel, dim3((unsigned)(g.heads * g.c0)), dim3(256), 0, st, (const float*)g.w[0],
                      (const float*)g.att_src[0], (const float*)g.att_dst[0], (const float*)g.du, g.heads, g.c0, g.d_in, g.g[0],
                      g.g[1], g.g[2]);
-  AdamPack2 ap{};
+  AdamPack ap{};
+  ap.n_src = 2;
   float* params[8] = {g.w[0], g.att_src[0], g.att_dst[0], g.bias[0], g.w[1], g.att_src[1], g.att_dst[1], g.bias[1]};
   const int32_t* n1a = t->enc[0].base->un.meta + GIGL_META_LEVEL0 + 1;
   const int32_t* n1b = t->enc[1].base->un.meta + GIGL_META_LEVEL0 + 1;
   auto add = [&](float* prm, const float* grad, float* m, float* v, int64_t n, const float* pa, const float* pb, int32_t rca,
                  int32_t rcb, const float* grad2 = nullptr) {
-    ap.p[ap.count] = prm;
-    ap.g1[ap.count] = grad;
-    ap.g2[ap.count] = grad2;
-    ap.part1[ap.count] = pa;
-    ap.part2[ap.count] = pb;
-    ap.rows1[ap.count] = n1a;
-    ap.rows2[ap.count] = n1b;
-    ap.rc1[ap.count] = rca;
-    ap.rc2[ap.count] = rcb;
-    ap.m[ap.count] = m;
-    ap.v[ap.count] = v;
-    ap.n[ap.count++] = n;
+    const int k = ap.count++;
+    ap.p[k] = prm;
+    ap.g[0][k] = grad;
+    ap.g[1][k] = grad2;
+    ap.part[0][k] = pa;
+    ap.part[1][k] = pb;
+    ap.rows[0][k] = n1a;
+    ap.rows[1][k] = n1b;
+    ap.rc[0][k] = rca;
+    ap.rc[1][k] = rcb;
+    ap.m[k] = m;
+    ap.v[k] = v;
+    ap.n[k] = n;
   };
   for (int i = 0; i < 8; ++i) {
     if (!params[i]) continue;
-    if (g.fused && (i == 0 || i == 3)) {  // W0 / b0: a slice per head, each with its own partial sums of both encodes
+    if (i == 0 || i == 3) {  // W0 / b0: a slice per head, each with its own partial sums of both encodes
       const int64_t ns = i == 0 ? (int64_t)g.c0 * g.d_in : g.c0;
       for (int h = 0; h < g.heads; ++h)
         add(params[i] + h * ns, g.g[i] + h * ns, g.mom[2 * i] + h * ns, g.mom[2 * i + 1] + h * ns, ns,
             i == 0 ? g.part_w0[0][h] : g.part_b0[0][h], i == 0 ? g.part_w0[1][h] : g.part_b0[1][h], g.rc_w0[0], g.rc_w0[1]);
-    } else if (g.fused && i == 4) {
+    } else if (i == 4) {
       add(params[i], g.g[i], g.mom[2 * i], g.mom[2 * i + 1], g.n[i], g.part_w1[0], g.part_w1[1], g.rc_w1[0], g.rc_w1[1]);
     } else {  // (fork: the second layer's attention vectors and bias were accumulated per encode)
       add(params[i], g.g[i], g.mom[2 * i], g.mom[2 * i + 1], g.n[i], nullptr, nullptr, 0, 0,
           t->fork && i >= 5 ? g.x.g[i] : nullptr);
     }
   }
-
   ap.lr = t->lr;
   ap.beta1 = t->beta1;
   ap.beta2 = t->beta2;
   ap.eps = t->eps;
   ap.wd = t->wd;
-  hipLaunchKernelGGL(lp_adam_kernel, g.fused ? dim3(104, (unsigned)ap.count) : dim3(256), dim3(256), 0, st, ap,
-                     (const int32_t*)(t->consts + 2), (const int32_t*)t->enc[0].base->un.meta,
-                     (const int32_t*)t->enc[1].base->un.meta);
+  hipLaunchKernelGGL(adam_kernel, dim3(104, (unsigned)ap.count), dim3(256), 0, st, ap, (const int32_t*)(t->consts + 2),
+                     (const int32_t*)t->enc[0].base->un.meta, (const int32_t*)t->enc[1].base->un.meta, (const int32_t*)nullptr);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -3006,37 +2832,16 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
   }
   const int32_t dims[3] = {d, H * C0, C1};
   for (int l = 0; l <= 2; ++l) t->dims[l] = dims[l];
-  int32_t rc = gigl_ctx_create(ctx->device, &t->lctx);
-  const int32_t nb[2] = {b_anchors * (1 + num_positives), n_random_negatives > 0 ? n_random_negatives : 1};
-  for (int wi = 0; wi < gigl_nablp_train_plan::WS && rc == GIGL_OK; ++wi) {
-    gigl_nablp_train_plan::Work& wk = t->work[wi];
-    rc = gigl_ctx_create(ctx->device, &wk.side);
-    if (rc == GIGL_OK) wk.side->wide = ctx->wide;
-    for (int k = 0; k < 2 && rc == GIGL_OK; ++k) {
-      t->enc[k].b = nb[k];
-      // (the base plans are tree + union workspaces here: their own layer buffers stay unused)
-      rc = plan_create(wk.side, graph, feat, nb[k], fanouts, hops, dims, (const float* const*)w, (const float* const*)bias, 0,
-                       false, &wk.base[k]);
-      if (rc != GIGL_OK) gigl_fail(ctx, rc, "%s", gigl_last_error(wk.side));
-      // every node of the batch graph is numbered: gigl_gat_input_aggregate reads its sources through un.nodes
-      if (rc == GIGL_OK) wk.base[k]->leaf_global = false;
-    }
-    if (rc == GIGL_OK && (hipEventCreateWithFlags(&wk.ev_graph, hipEventDisableTiming) != hipSuccess ||
-                          hipEventCreateWithFlags(&wk.ev_layers, hipEventDisableTiming) != hipSuccess))
-      rc = GIGL_E_HIP;
-  }
-  if (rc == GIGL_OK && hipEventCreateWithFlags(&t->ev_now, hipEventDisableTiming) != hipSuccess) rc = GIGL_E_HIP;
+  // (the base plans are tree + union workspaces here: their own layer buffers stay unused)
+  const int32_t rc = lp_create_workspaces(t, graph, feat, fanouts, hops, dims, w, bias, 0);
   if (rc != GIGL_OK) {
     gigl_nablp_train_plan_destroy(t);
     return rc;
   }
-  for (int k = 0; k < 2; ++k) t->enc[k].base = t->work[0].base[k];
-  auto alloc = [&](size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    t->owned.push_back(q);
-    return q;
-  };
+  // every node of the batch graph is numbered: gigl_gat_input_aggregate reads its sources through un.nodes
+  for (auto& wk : t->work)
+    for (gigl_sage_plan* bp : wk.base) bp->leaf_global = false;
+  auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
   bool ok = true;
   const int64_t n_par[8] = {(int64_t)H * C0 * d, H * C0, H * C0, g.bias[0] ? H * C0 : 0, (int64_t)C1 * H * C0, C1, C1, g.bias[1] ? C1 : 0};
   size_t zero_floats = (size_t)2 * H * d;  // du
@@ -3044,13 +2849,12 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
     g.n[i] = n_par[i];
     zero_floats += (size_t)n_par[i];
   }
-  // (default on, GIGL_LP_FORK=0 off, as the GraphSAGE plan: the forked step's layers part launched eagerly; needs the partial-sum mode)
-  const char* fork_env = getenv("GIGL_LP_FORK");
-  const bool want_fork = n_random_negatives > 0 && getenv("GIGL_TRAIN_PLAN_UNFUSED") == nullptr && !(fork_env && fork_env[0] == '0');
+  // (default on, GIGL_LP_FORK=0 off, as the GraphSAGE plan: the forked step's layers part launched eagerly)
+  const bool want_fork = lp_fork_wanted(t);
   if (want_fork) zero_floats += (size_t)2 * H * d + (size_t)(n_par[5] + n_par[6] + n_par[7]);  // the second encode's du, att / bias sums
   int64_t rows1_max = 0;
   for (int k = 0; k < 2; ++k) {
-    gigl_nablp_train_plan::Enc& e = t->enc[k];
+    SageTrainEnc& e = t->enc[k];
     e.rows_cap[0] = gigl_level_rows(ctx->wide, e.b, fanouts, hops, 1);  // nodes of level <= 1
     e.rows_cap[1] = e.b;
     if (e.rows_cap[0] > rows1_max) rows1_max = e.rows_cap[0];
@@ -3060,9 +2864,7 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
     g.z[k] = (float*)alloc((size_t)H * e.rows_cap[0] * d * 4);
     g.xw[k] = (float*)alloc((size_t)e.rows_cap[0] * C1 * 4);
     g.out_pre[k] = (float*)alloc((size_t)e.b * C1 * 4);
-    e.emb = (float*)alloc((size_t)e.b * C1 * 4);
-    e.inv = (float*)alloc((size_t)e.b * 4);
-    ok = ok && e.h[0] && e.h[1] && g.z[k] && g.xw[k] && g.out_pre[k] && e.emb && e.inv;
+    ok = ok && e.h[0] && e.h[1] && g.z[k] && g.xw[k] && g.out_pre[k];
   }
   float* z = (float*)alloc(zero_floats * 4);
   t->zero_base = z;
@@ -3101,10 +2903,7 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
   g.dh0 = (float*)alloc((size_t)rows1_max * H * C0 * 4);
   g.dh0s = (float*)alloc((size_t)rows1_max * H * C0 * 4);
   g.dz = (float*)alloc((size_t)H * rows1_max * d * 4);
-  const size_t wt_floats = std::max((size_t)C1 * H * C0, (size_t)C0 * d);
-  t->wt = (float*)alloc(wt_floats * 4);
-  ok = ok && t->zero_base && g.u && g.dxw && g.ds && g.alpha && g.dh0 && g.dh0s && g.dz && t->wt;
-  g.fused = getenv("GIGL_TRAIN_PLAN_UNFUSED") == nullptr;
+  ok = ok && t->zero_base && g.u && g.dxw && g.ds && g.alpha && g.dh0 && g.dh0s && g.dz;
   if (want_fork && ok) {  // the second encode's own scratch (its rows, its edges), a ctx with a stream of its own, the events
     const int64_t r1 = t->enc[1].rows_cap[0], ce1 = t->work[0].base[1]->un.cap_edges;
     g.x.dxw = (float*)alloc((size_t)r1 * C1 * 4);
@@ -3114,19 +2913,9 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
     g.x.dh0 = (float*)alloc((size_t)r1 * H * C0 * 4);
     g.x.dh0s = (float*)alloc((size_t)r1 * H * C0 * 4);
     g.x.dz = (float*)alloc((size_t)H * r1 * d * 4);
-    ok = g.x.dxw && g.x.ds && g.x.alpha && g.x.dh0 && g.x.dh0s && g.x.dz && g.x.du &&
-         gigl_ctx_create(ctx->device, &t->actx) == GIGL_OK;
-    for (int i = 0; i < 2 && ok; ++i)
-      ok = hipEventCreateWithFlags(&t->ev_fork[i], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&t->ev_join[i], hipEventDisableTiming) == hipSuccess;
-    const char* w_env = getenv("GIGL_LP_WGRAD_STREAM");  // (=0: the main batch's weight gradients stay in its chain)
-    if (ok && t->kind == 0 && !(w_env && w_env[0] == '0'))
-      ok = gigl_ctx_create(ctx->device, &t->wctx) == GIGL_OK &&
-           hipEventCreateWithFlags(&t->ev_w, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&t->ev_wjoin, hipEventDisableTiming) == hipSuccess;
-    t->fork = ok;
+    ok = g.x.dxw && g.x.ds && g.x.alpha && g.x.dh0 && g.x.dh0s && g.x.dz && g.x.du && lp_fork_setup(t);
   }
-  if (g.fused && ok) {
+  if (ok) {
     g.wt1 = (float*)alloc((size_t)C1 * H * C0 * 4);
     ok = g.wt1 != nullptr;
     for (int h = 0; h < H && ok; ++h) {
@@ -3146,29 +2935,7 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
       }
     }
   }
-  const size_t de = (size_t)C1, Q = (size_t)b_anchors * num_positives, Cn = Q + (size_t)t->n_rn;
-  t->rq = (float*)alloc(Q * de * 4);
-  t->cand = (float*)alloc(Cn * de * 4);
-  t->cand_t = (float*)alloc(Cn * de * 4);
-  t->scores = (float*)alloc(Q * Cn * 4);
-  t->dscores = (float*)alloc(Q * Cn * 4);
-  t->d_rq = (float*)alloc(Q * de * 4);
-  t->d_cand = (float*)alloc(Cn * de * 4);
-  t->qid = (int64_t*)alloc(Q * 8);
-  t->cid = (int64_t*)alloc(Cn * 8);
-  t->valid = (int32_t*)alloc(Cn * 4);
-  t->pos_cnt = (int32_t*)alloc((size_t)b_anchors * 4);
-  t->consts = (int32_t*)alloc(64);
-  t->row_lse = (float*)alloc(Q * 4);
-  t->row_loss = (float*)alloc(Q * 4);
-  t->loss = (float*)alloc(64);
-  ok = ok && t->rq && t->cand && t->cand_t && t->scores && t->dscores && t->d_rq && t->d_cand && t->qid && t->cid && t->valid &&
-       t->pos_cnt && t->consts && t->row_lse && t->row_loss && t->loss;
-  if (ok) {
-    const int32_t c[16] = {(int32_t)Q, (int32_t)Cn, 0 /* Adam's step counter */, 0};
-    if (hipMemcpy(t->consts, c, sizeof(c), hipMemcpyHostToDevice) != hipSuccess || hipMemset(t->loss, 0, 64) != hipSuccess)
-      ok = false;
-  }
+  ok = ok && lp_head_alloc(t, (size_t)C1);
   if (!ok) {
     gigl_nablp_train_plan_destroy(t);
     return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the GAT link-prediction training workspace failed");
@@ -3183,7 +2950,7 @@ int32_t gigl_gat_nablp_train_plan_grads(gigl_nablp_train_plan* t, int32_t layer,
   gigl_ctx* ctx = t->ctx;
   GIGL_REQUIRE(ctx, t->kind == 1 && layer >= 0 && layer < 2 && gw && g_att_src && g_att_dst, "bad plan / layer / null output");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (t->gat.fused && t->gat.parts_pending) {  // the step kept the projections' gradients as partial sums: add them up, once
+  if (t->gat.parts_pending) {  // the step kept the projections' gradients as partial sums: add them up, once
     auto& g = t->gat;
     for (int k = 0; k < 2; ++k) {
       const int32_t* n1 = t->enc[k].base->un.meta + GIGL_META_LEVEL0 + 1;
