@@ -1802,6 +1802,43 @@ __global__ void gat_edge_alpha_kernel(const float* __restrict__ edge_attr, int D
 
 constexpr int GAT_MAX_EDGE_DIM = 256;
 
+// component k of the attribute of the edge stored at col position p: row p of a dense [positions][De] array, or — the
+// one-call plan, eid != NULL — row eid[p] of the resident edge table read in place (eid < 0: no such edge, zeros)
+__device__ __forceinline__ float gat_edge_value(const float* __restrict__ edge_attr, const int32_t* __restrict__ eid,
+                                                int64_t p, int De, int k) {
+  if (!eid) return edge_attr[p * De + k];
+  const int32_t r = eid[p];
+  return r >= 0 ? edge_attr[(int64_t)r * De + k] : 0.f;
+}
+
+// a_edge over the USED positions of `col` with the attributes read through eid: one wave per destination row, lanes
+// over its edges
+__global__ __launch_bounds__(256) void gat_edge_alpha_rows_kernel(const float* __restrict__ table, int De,
+                                                                  const float* __restrict__ v_att, int heads,
+                                                                  const int32_t* __restrict__ eid,
+                                                                  const int32_t* __restrict__ rowptr,
+                                                                  const int32_t* __restrict__ rowend,
+                                                                  const int32_t* __restrict__ n_rows_dev,
+                                                                  float* __restrict__ a_edge) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int waves_total = (gridDim.x * blockDim.x) >> 6;
+  const int n_rows = *n_rows_dev;
+  for (int i = wave; i < n_rows; i += waves_total) {
+    const int e0 = rowptr[i], m = rowend[i] - e0;
+    for (int e = lane; e < m; e += 64) {
+      const int32_t r = eid[e0 + e];
+      const float* row = table + (int64_t)(r >= 0 ? r : 0) * De;
+      for (int hd = 0; hd < heads; ++hd) {
+        float s = 0.f;
+        if (r >= 0)
+          for (int k = 0; k < De; ++k) s += row[k] * v_att[(int64_t)hd * De + k];
+        a_edge[(int64_t)(e0 + e) * heads + hd] = s;
+      }
+    }
+  }
+}
+
 // As gat_gather_kernel, with e_ij += a_edge[p] for the edge stored at col position p.  The self loop carries the
 // MEAN of the row's (non-self) edge attributes (PyG add_self_loops(fill_value="mean")), hence — by linearity — the
 // mean of their a_edge, 0 for a row without in-edges.  w_msg != NULL (EdgeAttrGATConv, edge_attr_gat_conv.py:131-144):
@@ -1811,7 +1848,7 @@ __global__ __launch_bounds__(256) void gat_edge_gather_kernel(
     const float* __restrict__ a_edge, const float* __restrict__ edge_attr, int De, const float* __restrict__ w_msg,
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rowend, const int32_t* __restrict__ col,
     const int32_t* __restrict__ n_rows_dev, int heads, int C, float slope, int concat,
-    const float* __restrict__ bias, int act, float* __restrict__ out) {
+    const float* __restrict__ bias, int act, float* __restrict__ out, const int32_t* __restrict__ eid) {
   __shared__ float s_z[4][GAT_MAX_EDGE_DIM];
   const int lane = threadIdx.x & 63, wl = threadIdx.x >> 6;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -1863,7 +1900,7 @@ __global__ __launch_bounds__(256) void gat_edge_gather_kernel(
             if (j == i) continue;
             float x = a_src[(int64_t)j * heads + hd] + ad + a_edge[(int64_t)(e0 + e) * heads + hd];
             x = x > 0.f ? x : slope * x;
-            const float ev = edge_attr[(int64_t)(e0 + e) * De + k];
+            const float ev = gat_edge_value(edge_attr, eid, e0 + e, De, k);
             zz += expf(x - mx) * inv * ev;
             mean += ev;
           }
@@ -2191,6 +2228,14 @@ __global__ __launch_bounds__(256) void gat_input_gather_kernel(
 // bit-identical, in every wave of the row.
 // Four row elements as they are stored (the fp16 table: 8 bytes; widened where they are used, so that the U rows in
 // flight cost half the registers and the conversions fold into the multiply-adds)
+// the edge terms of the first layer (gat_input_online_kernel<.., EDGE>): all DEVICE
+struct GatEdgeIn {
+  const int32_t* eid = nullptr;   // [positions of col] row of `table` per stored edge (< 0: none — a zero attribute)
+  const float* table = nullptr;   // [n_edges][De] fp32
+  const float* v = nullptr;       // [H][De] folded att_edge
+  int De = 0;
+  float* ze = nullptr;            // [rows][H][De] out: sum_e alpha_e e (edge messages), NULL without them
+};
 template <typename T>
 struct RawRow4;
 template <>
@@ -2218,16 +2263,26 @@ struct RawRow4<__half> {
 // the U*H partial logits are reduced TOGETHER (gigl_wave_reduce16: 35 instructions per 16 totals), the totals are wave-
 // uniform scalars (v_readlane), and the running softmax is rescaled once per group — the group's largest logit first,
 // then acc = acc*sc + sum_t pw_t x_t.  No LDS, no barrier.
-template <typename T, int V, int H>
+// EDGE (the one-call plan's first layer over a graph with edge features, gigl_gat_edge_terms): the edge stored at col
+// position p carries the De-wide row table[eid[p]].  Lanes over the edges of a 64-edge chunk form a_e^h = <e, v_h> from it
+// (v = the folded att_edge) — once in a pre-pass that gives the self loop its logit term, the mean of the row's a_e (the
+// self loop carries the MEAN attribute, and the term is linear), and once more as the chunk is consumed (the rows' second
+// touch comes from L2); the group loop adds the edge's a_e^h to its logit from the owning lane (v_readlane).  With edge
+// MESSAGES (ze != NULL) lane k < De also keeps ze_h[k] = sum_e alpha_e^h e[k] under the same rescale as acc — one register
+// per head — next to the plain sum of e[k] and the self loop's running weight, from which the self loop's share
+// alpha_self^h * mean e[k] is added at the end: ze[i][h][0:De], read by gat_edge_msg_epilogue_kernel.
+template <typename T, int V, int H, bool EDGE = false>
 __global__ __launch_bounds__(256) void gat_input_online_kernel(
     const T* __restrict__ src, int d, const uint32_t* __restrict__ gather_ids, const int32_t* __restrict__ n_local_dev,
     const float* __restrict__ u, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rowend,
     const int32_t* __restrict__ col, const int32_t* __restrict__ n_rows_dev, float slope, int nkc, int64_t head_stride,
-    float* __restrict__ z) {
+    float* __restrict__ z, GatEdgeIn ed) {
   // feature rows in flight per wave: 8 while they, the accumulators and the source vectors fit the registers of two
   // waves per SIMD without spilling (the fp16 table at d = 768, two heads: 204 VGPRs; forcing three waves spilled and
   // ran 30 % slower), 4 for the wide fp32 / four-head shapes
-  constexpr int U = (V * H * (sizeof(T) == 2 ? 2 : 4) > 12) ? 4 : 8;
+  // (EDGE adds the edge terms' state — up to 41 VGPRs at U = 8: the flagship shape goes 204 -> 245, still two waves; where
+  // that would cost a wave, three chunks x four heads, fewer rows are kept in flight instead)
+  constexpr int U = (EDGE && V == 3 && H == 4) ? 2 : (V * H * (sizeof(T) == 2 ? 2 : 4) > 12) ? 4 : 8;
   constexpr int NV = U * H, NC = (NV + 15) / 16;
   typedef RawRow4<T> RR;
   typedef typename RR::type raw_t;
@@ -2258,6 +2313,64 @@ __global__ __launch_bounds__(256) void gat_input_online_kernel(
     const bool local = i < n_local;
     float sd[H], mx[H], den[H];
     float4_t acc[H][V];
+    // this lane's edge of the chunk at c0: kept?, the source's global id, the edge table row and its logit terms
+    auto chunk_edge = [&](int c0, uint32_t& gid, int& id, float (&ae)[H]) -> bool {
+      bool take = false;
+      gid = self_gid;  // (lanes past the row and self loops among the edges: skipped by the callers)
+      id = -1;
+#pragma unroll
+      for (int h = 0; h < H; ++h) ae[h] = 0.f;
+      if (c0 + lane < m) {
+        const int j = col[e0 + c0 + lane];
+        if (local) {
+          take = j != i;
+          gid = gather_ids[j];
+        } else {
+          gid = (uint32_t)j;
+          take = gid != self_gid;
+        }
+        if constexpr (EDGE) {
+          if (take) id = ed.eid[e0 + c0 + lane];
+          if (id >= 0) {
+            const float* er = ed.table + (int64_t)id * ed.De;
+            for (int k = 0; k < ed.De; ++k) {
+              const float ev = er[k];
+#pragma unroll
+              for (int h = 0; h < H; ++h) ae[h] += ev * ed.v[h * ed.De + k];
+            }
+          }
+        }
+      }
+      return take;
+    };
+    float ae_self[H], wself[H], ze[H], esum = 0.f, inv_cnt = 0.f;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+      ae_self[h] = 0.f;
+      wself[h] = 1.f;
+      ze[h] = 0.f;
+    }
+    if constexpr (EDGE) {
+      float cntf = 0.f;
+      for (int c0 = 0; c0 < m; c0 += 64) {
+        uint32_t gid;
+        int id;
+        float ae[H];
+        if (chunk_edge(c0, gid, id, ae)) {
+          cntf += 1.f;
+#pragma unroll
+          for (int h = 0; h < H; ++h) ae_self[h] += ae[h];
+        }
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        cntf += __shfl_xor(cntf, off, 64);
+#pragma unroll
+        for (int h = 0; h < H; ++h) ae_self[h] += __shfl_xor(ae_self[h], off, 64);
+      }
+      inv_cnt = cntf > 0.f ? 1.0f / cntf : 0.f;
+#pragma unroll
+      for (int h = 0; h < H; ++h) ae_self[h] = lane_value(ae_self[h] * inv_cnt, 0);
+    }
     {
       float pv[16];
 #pragma unroll
@@ -2279,24 +2392,16 @@ __global__ __launch_bounds__(256) void gat_input_online_kernel(
       for (int h = 0; h < H; ++h) {
         const float fs = lane_value(tot, h << 2), fd = lane_value(tot, (H + h) << 2);
         sd[h] = fd;
-        mx[h] = leaky(fs + fd);
+        mx[h] = leaky(EDGE ? fs + fd + ae_self[h] : fs + fd);
         den[h] = 1.f;
       }
     }
     for (int c0 = 0; c0 < m; c0 += 64) {
       const int mm = min(64, m - c0);
-      uint32_t gid = self_gid;  // (lanes past the row and self loops among the edges: skipped below)
-      bool take = false;
-      if (lane < mm) {
-        const int j = col[e0 + c0 + lane];
-        if (local) {
-          take = j != i;
-          gid = gather_ids[j];
-        } else {
-          gid = (uint32_t)j;
-          take = gid != self_gid;
-        }
-      }
+      uint32_t gid;
+      int eidl;
+      float ael[H];
+      const bool take = chunk_edge(c0, gid, eidl, ael);
       const unsigned long long keep = __ballot(take);
       for (int e = 0; e < mm; e += U) {
         raw_t x[U][V];
@@ -2327,13 +2432,26 @@ __global__ __launch_bounds__(256) void gat_input_online_kernel(
 #pragma unroll
           for (int k = 0; k < 16; ++k) fsum[cc * 16 + k] = lane_value(tot, k << 2);
         }
+        float ev[EDGE ? U : 1];  // lane k: component k of the U edges' attribute rows (edge messages only)
+        if constexpr (EDGE) {
+          if (ed.ze) {
+#pragma unroll
+            for (int t = 0; t < U; ++t) {
+              const int id = __builtin_amdgcn_readlane(eidl, (e + t) & 63);
+              ev[t] = (live[t] && id >= 0 && lane < ed.De) ? ed.table[(int64_t)id * ed.De + lane] : 0.f;
+              esum += ev[t];
+            }
+          }
+        }
 #pragma unroll
         for (int h = 0; h < H; ++h) {
           float zl[U];
           float gmax = mx[h];
 #pragma unroll
           for (int t = 0; t < U; ++t) {
-            zl[t] = live[t] ? leaky(fsum[t * H + h] + sd[h]) : -__builtin_inff();
+            float lg = fsum[t * H + h] + sd[h];
+            if constexpr (EDGE) lg += lane_value(ael[h], (e + t) & 63);
+            zl[t] = live[t] ? leaky(lg) : -__builtin_inff();
             gmax = fmaxf(gmax, zl[t]);
           }
           const float sc = __expf(mx[h] - gmax);
@@ -2351,9 +2469,25 @@ __global__ __launch_bounds__(256) void gat_input_online_kernel(
             for (int t = 0; t < U; ++t) a += pw[t] * RR::f4(x[t][v]);
             acc[h][v] = a;
           }
+          if constexpr (EDGE) {
+            if (ed.ze) {
+              float zz = ze[h] * sc;
+#pragma unroll
+              for (int t = 0; t < U; ++t) zz += pw[t] * ev[t];
+              ze[h] = zz;
+              wself[h] *= sc;
+            }
+          }
           den[h] = dn;
           mx[h] = gmax;
         }
+      }
+    }
+    if constexpr (EDGE) {
+      if (ed.ze && lane < ed.De) {
+#pragma unroll
+        for (int h = 0; h < H; ++h)
+          ed.ze[((int64_t)i * H + h) * ed.De + lane] = (ze[h] + wself[h] * (esum * inv_cnt)) * (1.0f / den[h]);
       }
     }
 #pragma unroll
@@ -2365,6 +2499,28 @@ __global__ __launch_bounds__(256) void gat_input_online_kernel(
 #pragma unroll
       for (int h = 0; h < H; ++h) *reinterpret_cast<float4_t*>(tbase + h * head_stride) = acc[h][v] * (1.0f / den[h]);
     }
+  }
+}
+
+// the edge messages' share of that layer: out[i][c] = act(out[i][c] + <w_msg[c], ze[i][c / C]> + bias[c]) for i < *n_rows_dev
+// (one thread per output element: De multiply-adds)
+constexpr int GAT_INPUT_MAX_EDGE_DIM = 64;
+__global__ __launch_bounds__(256) void gat_edge_msg_epilogue_kernel(const float* __restrict__ ze, const float* __restrict__ w_msg,
+                                                                    const float* __restrict__ bias,
+                                                                    const int32_t* __restrict__ n_rows_dev, int H, int C, int De,
+                                                                    int act, float* __restrict__ out) {
+  const int HC = H * C;
+  const int64_t n = (int64_t)(*n_rows_dev) * HC;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / HC;
+    const int c = (int)(t - i * HC);
+    const float* zr = ze + (i * H + c / C) * De;
+    const float* wr = w_msg + (int64_t)c * De;
+    float a = 0.f;
+    for (int k = 0; k < De; ++k) a += wr[k] * zr[k];
+    float v = out[t] + a + (bias ? bias[c] : 0.f);
+    if (act == 1) v = v > 0.f ? v : 0.f;
+    out[t] = v;
   }
 }
 
@@ -2694,7 +2850,7 @@ __global__ __launch_bounds__(256) void gat_gather_fast_kernel(
     const int32_t* __restrict__ col, const int32_t* __restrict__ n_rows_dev, int heads, int C, int group,
     int rows_per_head, float slope, const float* __restrict__ bias, int act, const float* __restrict__ edge_attr,
     int De, const float* __restrict__ wt, float* __restrict__ out, int32_t* __restrict__ heavy_count,
-    int32_t* __restrict__ heavy_list) {
+    int32_t* __restrict__ heavy_list, const int32_t* __restrict__ eid) {
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int waves_total = (gridDim.x * blockDim.x) >> 6;
@@ -2749,7 +2905,7 @@ __global__ __launch_bounds__(256) void gat_gather_fast_kernel(
 #pragma unroll
           for (int r = 0; r < GAT_ZR; ++r) {
             const int k = r * group + kl;
-            ev[t][r] = k < De ? edge_attr[(int64_t)(e0 + e + t) * De + k] : 0.f;
+            ev[t][r] = k < De ? gat_edge_value(edge_attr, eid, e0 + e + t, De, k) : 0.f;
           }
         }
       }
@@ -3260,7 +3416,8 @@ static bool launch_gat_fast(gigl_ctx* ctx, const float* h, const float* att_src,
                             float slope, int concat, const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
                             const int32_t* n_nodes_dev, int64_t nodes_cap, const int32_t* n_rows_dev, int64_t rows_cap,
                             const float* bias, int act, float* a_src, float* a_dst, const float* a_edge, float* out,
-                            const float* edge_attr = nullptr, int De = 0, const float* w_msg = nullptr) {
+                            const float* edge_attr = nullptr, int De = 0, const float* w_msg = nullptr,
+                            const int32_t* eid = nullptr) {
   GatShape g;
   if (!(concat || heads == 1) || !gat_fast_shape(heads, C, g)) return false;
   float* wt = nullptr;
@@ -3291,11 +3448,11 @@ static bool launch_gat_fast(gigl_ctx* ctx, const float* h, const float* att_src,
   if (wt)                                                                                                            \
     hipLaunchKernelGGL((gat_gather_fast_kernel<VV, true>), dim3((unsigned)gblocks), dim3(256), 0, ctx->stream, h,    \
                        a_src, a_dst, a_edge, rowptr, rowend, col, n_rows_dev, heads, C, g.group, g.rows_per_head,    \
-                       slope, bias, act, edge_attr, De, wt, out, heavy_count, heavy_list);                           \
+                       slope, bias, act, edge_attr, De, wt, out, heavy_count, heavy_list, eid);                      \
   else {                                                                                                             \
     hipLaunchKernelGGL((gat_gather_fast_kernel<VV, false>), dim3((unsigned)gblocks), dim3(256), 0, ctx->stream, h,   \
                        a_src, a_dst, a_edge, rowptr, rowend, col, n_rows_dev, heads, C, g.group, g.rows_per_head,    \
-                       slope, bias, act, edge_attr, De, wt, out, heavy_count, heavy_list);                           \
+                       slope, bias, act, edge_attr, De, wt, out, heavy_count, heavy_list, eid);                      \
     const size_t lds = (size_t)GAT_HEAVY_WAVES * VV * 7 * 64 * 4;                                                                  \
     if (lds > 48 * 1024)                                                                                             \
       hipFuncSetAttribute((const void*)gat_gather_heavy_kernel<VV>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
@@ -3681,6 +3838,23 @@ int32_t gigl_gat_aggregate_edge(gigl_ctx* ctx, const float* h, const float* att_
                                 int64_t rows_cap, const float* bias, int32_t act, const float* edge_attr,
                                 int32_t edge_dim, int64_t cap_edges, const float* att_edge_folded,
                                 const float* w_edge_msg, float* alpha_scratch, float* out) {
+  return gigl_gat_aggregate_edge_indexed(ctx, h, att_src, att_dst, heads, channels, negative_slope, concat, rowptr, rowend,
+                                         col, n_nodes_dev, nodes_cap, n_rows_dev, rows_cap, bias, act, edge_attr, nullptr,
+                                         edge_dim, cap_edges, att_edge_folded, w_edge_msg, alpha_scratch, out);
+}
+
+}  // extern "C"
+
+// eid != NULL: edge_attr is the resident edge table, the edge at col position p carries its row eid[p] (the one-call
+// plan: no dense [cap_edges][De] array); a_edge is then formed for the used positions only
+int32_t gigl_gat_aggregate_edge_indexed(gigl_ctx* ctx, const float* h, const float* att_src, const float* att_dst,
+                                        int32_t heads, int32_t channels, float negative_slope, int32_t concat,
+                                        const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
+                                        const int32_t* n_nodes_dev, int64_t nodes_cap, const int32_t* n_rows_dev,
+                                        int64_t rows_cap, const float* bias, int32_t act, const float* edge_attr,
+                                        const int32_t* eid, int32_t edge_dim, int64_t cap_edges,
+                                        const float* att_edge_folded, const float* w_edge_msg, float* alpha_scratch,
+                                        float* out) {
   if (!ctx) return GIGL_E_INVALID_ARG;
   GIGL_REQUIRE(ctx, h && att_src && att_dst && rowptr && rowend && col && n_nodes_dev && n_rows_dev &&
                         alpha_scratch && out && edge_attr && att_edge_folded, "null argument");
@@ -3693,13 +3867,19 @@ int32_t gigl_gat_aggregate_edge(gigl_ctx* ctx, const float* h, const float* att_
   float* a_src = alpha_scratch;
   float* a_dst = alpha_scratch + nodes_cap * heads;
   float* a_edge = alpha_scratch + 2 * nodes_cap * heads;
-  if (cap_edges > 0)
+  if (cap_edges > 0 && eid) {
+    int64_t blocks = (rows_cap + 3) / 4;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(gat_edge_alpha_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, edge_attr, edge_dim,
+                       att_edge_folded, heads, eid, rowptr, rowend, n_rows_dev, a_edge);
+  } else if (cap_edges > 0) {
     hipLaunchKernelGGL(gat_edge_alpha_kernel, dim3((unsigned)((cap_edges * heads + 255) / 256)), dim3(256), 0,
                        ctx->stream, edge_attr, edge_dim, att_edge_folded, heads, cap_edges, a_edge);
+  }
   if (cap_edges > 0 &&
       launch_gat_fast(ctx, h, att_src, att_dst, heads, channels, negative_slope, concat, rowptr, rowend, col,
                       n_nodes_dev, nodes_cap, n_rows_dev, rows_cap, bias, act, a_src, a_dst, a_edge, out, edge_attr,
-                      edge_dim, w_edge_msg)) {
+                      edge_dim, w_edge_msg, eid)) {
     GIGL_HIP_CHECK(ctx, hipGetLastError());
     return GIGL_OK;
   }
@@ -3709,10 +3889,12 @@ int32_t gigl_gat_aggregate_edge(gigl_ctx* ctx, const float* h, const float* att_
   if (blocks > 256 * 16) blocks = 256 * 16;
   hipLaunchKernelGGL(gat_edge_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, h, a_src, a_dst,
                      a_edge, edge_attr, edge_dim, w_edge_msg, rowptr, rowend, col, n_rows_dev, heads, channels,
-                     negative_slope, concat, bias, act, out);
+                     negative_slope, concat, bias, act, out, eid);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
+
+extern "C" {
 
 int32_t gigl_gat_backward_epilogue(gigl_ctx* ctx, float* dh, const float* ds, const float* dd, const float* xw,
                                    const float* att_src, const float* att_dst, const int32_t* n_nodes_dev, int64_t nodes_cap,
@@ -4507,7 +4689,7 @@ int32_t gigl_gat_input_aggregate(gigl_ctx* ctx, const void* src, int32_t src_dty
   if (blocks > 256 * 16) blocks = 256 * 16;
 #define GIGL_GAT_AG(TT, PP, HH)                                                                                        \
   hipLaunchKernelGGL((gat_input_online_kernel<TT, PP, HH>), dim3((unsigned)blocks), dim3(256), 0, st, (const TT*)src, d, \
-                     gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, slope, nkc, head_stride, z)
+                     gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, slope, nkc, head_stride, z, GatEdgeIn{})
 #define GIGL_GAT_AG_P(TT, HH)                                                                                          \
   do {                                                                                                                  \
     if (P == 1) GIGL_GAT_AG(TT, 1, HH);                                                                                \
@@ -4582,7 +4764,7 @@ int32_t gigl_gat_input_layer_fused(gigl_ctx* ctx, const void* src, int32_t src_d
                                    int32_t act, float* scratch, float* out) {
   return gigl_gat_input_layer_fused_hs(ctx, src, src_dtype, d, gather_ids, n_local_dev, w, att_src, att_dst, heads, channels,
                                        negative_slope, rowptr, rowend, col, n_rows_dev, rows_cap, bias, act, scratch, out,
-                                       nullptr);
+                                       nullptr, nullptr);
 }
 
 // hs_scale != NULL: the projection of the aggregated rows over two fp16 planes per operand — the rows are convex
@@ -4592,10 +4774,17 @@ int32_t gigl_gat_input_layer_fused_hs(gigl_ctx* ctx, const void* src, int32_t sr
                                       const float* att_src, const float* att_dst, int32_t heads, int32_t channels,
                                       float negative_slope, const int32_t* rowptr, const int32_t* rowend,
                                       const int32_t* col, const int32_t* n_rows_dev, int64_t rows_cap, const float* bias,
-                                      int32_t act, float* scratch, float* out, const float* hs_scale) {
+                                      int32_t act, float* scratch, float* out, const float* hs_scale,
+                                      const gigl_gat_edge_terms* edge) {
   if (!ctx) return GIGL_E_INVALID_ARG;
   GIGL_REQUIRE(ctx, src && gather_ids && w && att_src && att_dst && rowptr && rowend && col && n_rows_dev && scratch && out,
                "null argument");
+  if (edge) {
+    GIGL_REQUIRE(ctx, edge->eid && edge->table && edge->att_edge_folded && (!edge->w_edge_msg || edge->ze), "null edge term");
+    if (edge->edge_dim < 1 || edge->edge_dim > GAT_INPUT_MAX_EDGE_DIM)
+      return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "gigl_gat_input_layer_fused: edge_dim %d outside [1,%d] (a lane per "
+                       "component of the edge messages)", edge->edge_dim, GAT_INPUT_MAX_EDGE_DIM);
+  }
   GIGL_REQUIRE(ctx, d > 0 && heads > 0 && channels > 0 && rows_cap >= 0, "bad sizes");
   GIGL_REQUIRE(ctx, src_dtype == GIGL_DTYPE_F32 || src_dtype == GIGL_DTYPE_F16, "bad dtype %d", src_dtype);
   GIGL_REQUIRE(ctx, act == 0 || act == 1, "bad act %d", act);
@@ -4617,10 +4806,25 @@ int32_t gigl_gat_input_layer_fused_hs(gigl_ctx* ctx, const void* src, int32_t sr
                        att_dst, H, C, d, u);
     int64_t blocks = (rows_cap + 3) / 4;  // one wave per row, four rows per workgroup
     if (blocks > 256 * 16) blocks = 256 * 16;
+    GatEdgeIn ed;
+    if (edge) {
+      ed.eid = edge->eid;
+      ed.table = edge->table;
+      ed.v = edge->att_edge_folded;
+      ed.De = edge->edge_dim;
+      ed.ze = edge->w_edge_msg ? edge->ze : nullptr;
+    }
 #define GIGL_GAT_ON(TT, PP, HH)                                                                                         \
-  hipLaunchKernelGGL((gat_input_online_kernel<TT, PP, HH>), dim3((unsigned)blocks), dim3(256), 0, st,                 \
-                     (const TT*)src, d, gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, negative_slope,    \
-                     nkc, head_stride, z)
+  do {                                                                                                                  \
+    if (edge)                                                                                                           \
+      hipLaunchKernelGGL((gat_input_online_kernel<TT, PP, HH, true>), dim3((unsigned)blocks), dim3(256), 0, st,        \
+                         (const TT*)src, d, gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, negative_slope, \
+                         nkc, head_stride, z, ed);                                                                      \
+    else                                                                                                                \
+      hipLaunchKernelGGL((gat_input_online_kernel<TT, PP, HH>), dim3((unsigned)blocks), dim3(256), 0, st,              \
+                         (const TT*)src, d, gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, negative_slope, \
+                         nkc, head_stride, z, ed);                                                                      \
+  } while (0)
 #define GIGL_GAT_ON_P(TT, HH)                                                                                           \
   do {                                                                                                                  \
     if (P == 1) GIGL_GAT_ON(TT, 1, HH);                                                                                 \
@@ -4640,6 +4844,20 @@ int32_t gigl_gat_input_layer_fused_hs(gigl_ctx* ctx, const void* src, int32_t sr
 #undef GIGL_GAT_ON_P
 #undef GIGL_GAT_ON
     GIGL_HIP_CHECK(ctx, hipGetLastError());
+  }
+  if (edge && edge->w_edge_msg) {
+    // out_h = W_h z_h + W_msg,h ze_h + bias: the De-wide term has its own magnitude (it does not share the projection's
+    // power-of-two scales) and is small — rows x H*C x De multiply-adds in fp32 next to the bias and the activation
+    const int32_t rc = linear_tiled_strided(ctx, z, w, nullptr, n_rows_dev, rows_cap, d, C, 0, out, H * C, H, head_stride,
+                                            (int64_t)C * d, nullptr, nullptr, 0, 0, hs_scale);
+    if (rc != GIGL_OK) return rc;
+    gigl_prof_scope ps(ctx, GIGL_K_LINEAR);
+    int64_t blocks = (rows_cap * H * C + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(gat_edge_msg_epilogue_kernel, dim3((unsigned)blocks), dim3(256), 0, st, edge->ze, edge->w_edge_msg,
+                       bias, n_rows_dev, H, C, edge->edge_dim, act, out);
+    GIGL_HIP_CHECK(ctx, hipGetLastError());
+    return GIGL_OK;
   }
   return linear_tiled_strided(ctx, z, w, bias, n_rows_dev, rows_cap, d, C, act, out, H * C, H, head_stride, (int64_t)C * d,
                               nullptr, nullptr, 0, 0, hs_scale);

@@ -182,12 +182,35 @@ int32_t gigl_feat_half_split_scale(gigl_ctx* ctx, gigl_feat* feat, float fan, fl
 // hs_dev[0..2] = {s_a, s_w, 1 / (s_a s_w)} with s_w from the largest |w[i]| as the n weights are when the launch runs —
 // one small launch on the ctx's stream, no synchronisation, may be captured
 int32_t gigl_hs_scale_update(gigl_ctx* ctx, const float* w, int64_t n, float s_a, float* hs_dev);
+// the first GAT layer's edge terms (the one-call plan over a graph with edge features; semantics of gigl_gat_aggregate_edge):
+// the edge stored at col position p carries row eid[p] of `table` ([n_edges][edge_dim] fp32, read in place); the logits gain
+// <e, att_edge_folded[h]>, the added self loop carries the mean attribute of the row's other in-edges; w_edge_msg != NULL
+// (EdgeAttrGATConv): out_h += W_msg,h (sum_e alpha_e e), through ze [rows_cap][heads][edge_dim] (scratch).  All DEVICE.
+struct gigl_gat_edge_terms {
+  const int32_t* eid;
+  const float* table;
+  int32_t edge_dim;  // 1 .. 64 (GIGL_E_UNSUPPORTED beyond)
+  const float* att_edge_folded;
+  const float* w_edge_msg;
+  float* ze;
+};
 int32_t gigl_gat_input_layer_fused_hs(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d,
                                       const uint32_t* gather_ids, const int32_t* n_local_dev, const float* w,
                                       const float* att_src, const float* att_dst, int32_t heads, int32_t channels,
                                       float negative_slope, const int32_t* rowptr, const int32_t* rowend,
                                       const int32_t* col, const int32_t* n_rows_dev, int64_t rows_cap, const float* bias,
-                                      int32_t act, float* scratch, float* out, const float* hs_scale);
+                                      int32_t act, float* scratch, float* out, const float* hs_scale,
+                                      const gigl_gat_edge_terms* edge);
+// gigl_gat_aggregate_edge with the attributes read in place from the resident edge table: row eid[p] for the edge at col
+// position p (eid == NULL: edge_attr is the dense [cap_edges][edge_dim] array of the public entry point)
+int32_t gigl_gat_aggregate_edge_indexed(gigl_ctx* ctx, const float* h, const float* att_src, const float* att_dst,
+                                        int32_t heads, int32_t channels, float negative_slope, int32_t concat,
+                                        const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
+                                        const int32_t* n_nodes_dev, int64_t nodes_cap, const int32_t* n_rows_dev,
+                                        int64_t rows_cap, const float* bias, int32_t act, const float* edge_attr,
+                                        const int32_t* eid, int32_t edge_dim, int64_t cap_edges,
+                                        const float* att_edge_folded, const float* w_edge_msg, float* alpha_scratch,
+                                        float* out);
 // The fused two-layer projection (agg.hip, linear_fused2x_kernel): layer 0's [mean | self] projection (half split, two-source
 // tiled operand) with the LAST layer's [W_l | W_r] applied to the hidden rows before they leave the workgroup — y2 =
 // [rows][gigl_fused2_row_floats()] of p = [W_l h | W_r h]; gigl_sage_fused_out is the last layer over those rows (one

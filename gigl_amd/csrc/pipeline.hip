@@ -63,6 +63,14 @@ struct gigl_sage_plan {
   float* gat_scratch = nullptr;    // first layer: folded vectors + the per-head tiled operands
   float* alpha_scratch = nullptr;  // layers >= 1: per-node attention dots [2 * act_rows * max heads]
   float* hw = nullptr;             // layers >= 1: projected source rows [act_rows][max heads*channels]
+  // edge features (gigl_gat_plan_set_edge_features): the resident edge table is read in place through eid — the table row
+  // of the edge stored at every used position of un.col, written by the GRAPH part (plan_edge_ids_kernel)
+  gigl_feat* efeat = nullptr;
+  const float* att_edge[GIGL_MAX_HOPS] = {nullptr};  // folded [heads_l][De], device, borrowed
+  const float* w_msg[GIGL_MAX_HOPS] = {nullptr};     // [heads_l*channels_l][De] or null, device, borrowed
+  int32_t* eid = nullptr;   // [positions of un.col]
+  float* ze = nullptr;      // first layer: sum_e alpha_e e per row and head [act_rows][heads_0][De] (edge messages)
+  bool l2_normalize = false;  // the b output rows become x / max(|x|_2, 1e-12) (gigl_sage_plan_set_l2_normalize)
   // leaf-global union (union.hip): pure leaves get no local id and stay global ids in their parents' rows — the
   // plan never computes anything for them, it only gathers their feature rows
   bool leaf_global = false;
@@ -127,6 +135,60 @@ __global__ void guard_levels_kernel(int32_t* meta, int hops, int32_t act_rows) {
 
 __global__ void overflow_add_kernel(const int32_t* __restrict__ meta, int32_t* __restrict__ acc) {
   if (threadIdx.x == 0 && blockIdx.x == 0 && meta[GIGL_META_OVERFLOW] != 0) atomicAdd(acc, 1);
+}
+
+// Edge ids of the plan's union graph: eid[p] = position in the resident graph's `col` (= row of the edge table) of the
+// edge stored at position p of un.col, for every row that has in-edges (levels < hops).  The union is leaf-global: rows
+// >= *n_local_dev hold GLOBAL source ids, rows below it local ids that go through un.nodes (n_local_dev == NULL: every
+// row).  One wave per destination row, lanes over its edges (rows reach hundreds of edges); the resident row is ascending
+// in global id: a lower-bound search over rowptr[dst] .. rowptr[dst + 1] (the first of equal ids, as gigl_union_edge_ids);
+// -1 when the edge is not there.  int32 is enough: the graph build refuses 2^31 edges.
+__global__ __launch_bounds__(256) void plan_edge_ids_kernel(const int64_t* __restrict__ g_rowptr, const uint32_t* __restrict__ g_col,
+                                                            int64_t g_n, const uint32_t* __restrict__ nodes,
+                                                            const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rowend,
+                                                            const int32_t* __restrict__ col, const int32_t* __restrict__ n_rows_dev,
+                                                            const int32_t* __restrict__ n_local_dev, int64_t rows_cap,
+                                                            int64_t pos_cap, int32_t* __restrict__ eid) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  int64_t n_rows = *n_rows_dev;
+  if (n_rows > rows_cap) n_rows = rows_cap;
+  const int64_t n_local = n_local_dev ? *n_local_dev : 0x7FFFFFFF;
+  for (int64_t i = wave; i < n_rows; i += waves) {
+    const uint32_t dst = nodes[i];
+    const int64_t p0 = rowptr[i], p1 = rowend[i];
+    const bool known = (int64_t)dst < g_n;
+    const int64_t r0 = known ? g_rowptr[dst] : 0, r1 = known ? g_rowptr[(int64_t)dst + 1] : 0;
+    const bool local = i < n_local;
+    for (int64_t p = p0 + lane; p < p1 && p < pos_cap; p += 64) {
+      if (p < 0) continue;
+      const int32_t j = col[p];
+      const uint32_t s = local ? nodes[j] : (uint32_t)j;
+      int64_t lo = r0, hi = r1;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (g_col[mid] < s) lo = mid + 1;
+        else hi = mid;
+      }
+      eid[p] = (lo < r1 && g_col[lo] == s) ? (int32_t)lo : -1;
+    }
+  }
+}
+
+// out[i] = out[i] / max(|out[i]|_2, 1e-12) for the b rows of a call (torch.nn.functional.normalize): one wave per row.
+// NaN rows (a failed batch set) stay NaN.
+__global__ __launch_bounds__(256) void l2_normalize_rows_kernel(float* __restrict__ out, int b, int d) {
+  const int lane = threadIdx.x & 63;
+  const int i = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  if (i >= b) return;
+  float* row = out + (int64_t)i * d;
+  float ss = 0.f;
+  for (int c = lane; c < d; c += 64) ss += row[c] * row[c];
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  const float nrm = sqrtf(ss);
+  const float den = nrm < 1e-12f ? 1e-12f : nrm;  // (NaN < x is false: a NaN norm stays)
+  for (int c = lane; c < d; c += 64) row[c] = row[c] / den;
 }
 
 // exact work counts of the last batch set, accumulated into acc[GIGL_STATS_LEN] (see gigl_sage_plan_stats)
@@ -240,14 +302,29 @@ int32_t enqueue_stage(gigl_sage_plan* p, int s, const uint32_t* roots, int32_t s
     hipLaunchKernelGGL(guard_levels_kernel, dim3(1), dim3(64), 0, ctx->stream, p->un.meta, p->hops,
                        (int32_t)(p->act_rows < 0x7FFFFFFF ? p->act_rows : 0x7FFFFFFF));
     GIGL_HIP_CHECK(ctx, hipGetLastError());
+    if (p->efeat) {  // the edge ids belong to the GRAPH part: integer work over the union, independent of the weights
+      const int64_t rows_cap = gigl_level_rows(p->wide, p->b, p->fanouts, L, L - 1);
+      int64_t blocks = (rows_cap + 3) / 4;
+      if (blocks > 256 * 16) blocks = 256 * 16;
+      const int32_t* n_local = p->leaf_global ? (L >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (L - 2) : p->zero_dev) : nullptr;
+      hipLaunchKernelGGL(plan_edge_ids_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, p->graph->rowptr, p->graph->col,
+                         p->graph->n, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col, p->un.meta + GIGL_META_LEVEL0 + (L - 1),
+                         n_local, rows_cap, p->un.cap_edges + (p->alias_rows ? p->last_slots : 0), p->eid);
+      GIGL_HIP_CHECK(ctx, hipGetLastError());
+    }
     return GIGL_OK;
   }
   if (s == n_stages(p) - 1) {
     const int dout = p->dims[L];
-    if (fused2_on(p))  // the last layer over the p rows of the fused projection, one row per root, into `out`
-      return gigl_sage_fused_out(ctx, p->hbuf[0], p->un.rowptr, p->un.rowend, p->un.col, p->un.root_local, p->b, dout,
-                                 p->bias[L - 1], p->act_last ? 1 : 0, p->aggr, p->un.meta, out);
-    gigl_take_rows(ctx->stream, p->hbuf[(L - 1) & 1], p->un.root_local, p->b, dout, p->un.meta, out);
+    if (fused2_on(p)) {  // the last layer over the p rows of the fused projection, one row per root, into `out`
+      const int32_t rc = gigl_sage_fused_out(ctx, p->hbuf[0], p->un.rowptr, p->un.rowend, p->un.col, p->un.root_local, p->b,
+                                             dout, p->bias[L - 1], p->act_last ? 1 : 0, p->aggr, p->un.meta, out);
+      if (rc != GIGL_OK) return rc;
+    } else {
+      gigl_take_rows(ctx->stream, p->hbuf[(L - 1) & 1], p->un.root_local, p->b, dout, p->un.meta, out);
+    }
+    if (p->l2_normalize)
+      hipLaunchKernelGGL(l2_normalize_rows_kernel, dim3((unsigned)((p->b + 3) / 4)), dim3(256), 0, ctx->stream, out, p->b, dout);
     GIGL_HIP_CHECK(ctx, hipGetLastError());
     return GIGL_OK;
   }
@@ -271,16 +348,31 @@ int32_t enqueue_stage(gigl_sage_plan* p, int s, const uint32_t* roots, int32_t s
         const int32_t rc = gigl_hs_scale_update(ctx, p->w[0], (int64_t)p->heads[0] * p->channels[0] * d, p->hs_sa, p->hs_dev);
         if (rc != GIGL_OK) return rc;
       }
+      gigl_gat_edge_terms et{};
+      if (p->efeat) {
+        et.eid = p->eid;
+        et.table = (const float*)p->efeat->rows;
+        et.edge_dim = p->efeat->d;
+        et.att_edge_folded = p->att_edge[0];
+        et.w_edge_msg = p->w_msg[0];
+        et.ze = p->ze;
+      }
       return gigl_gat_input_layer_fused_hs(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, n_local, p->w[0], p->att_src[0],
                                            p->att_dst[0], p->heads[0], p->channels[0], p->slope, p->un.rowptr, p->un.rowend,
                                            p->un.col, n_rows, rows_cap, p->bias[0], act, p->gat_scratch, p->hbuf[0],
-                                           p->hs0 ? p->hs_dev : nullptr);
+                                           p->hs0 ? p->hs_dev : nullptr, p->efeat ? &et : nullptr);
     }
     // sources of layer l: the rows layer l-1 computed (level <= L-l)
     const int32_t* n_src = p->un.meta + GIGL_META_LEVEL0 + (L - l);
     int64_t src_cap = rows_cap + width;
     if (first)
       return gigl_linear(ctx, p->hbuf[(l - 1) & 1], p->w[l], nullptr, n_src, src_cap, d, p->dims[l + 1], 0, p->hw);
+    if (p->efeat)  // (a_edge lies behind the 2 * src_cap * heads node dots of alpha_scratch)
+      return gigl_gat_aggregate_edge_indexed(ctx, p->hw, p->att_src[l], p->att_dst[l], p->heads[l], p->channels[l], p->slope, 1,
+                                             p->un.rowptr, p->un.rowend, p->un.col, n_src, src_cap, n_rows, rows_cap, p->bias[l],
+                                             act, (const float*)p->efeat->rows, p->eid, p->efeat->d,
+                                             p->un.cap_edges + (p->alias_rows ? p->last_slots : 0), p->att_edge[l], p->w_msg[l],
+                                             p->alpha_scratch, p->hbuf[l & 1]);
     return gigl_gat_aggregate(ctx, p->hw, p->att_src[l], p->att_dst[l], p->heads[l], p->channels[l], p->slope, 1,
                               p->un.rowptr, p->un.rowend, p->un.col, n_src, src_cap, n_rows, rows_cap, p->bias[l], act,
                               p->alpha_scratch, p->hbuf[l & 1]);
@@ -846,6 +938,61 @@ int32_t gigl_gat_plan_set_weights(gigl_sage_plan* p, const float* const* w, cons
     drop_graphs(p);
   }
   return plan_refresh_half_split(p);
+}
+
+int32_t gigl_gat_plan_set_edge_features(gigl_sage_plan* p, gigl_feat* edge_table, const float* const* att_edge_folded,
+                                        const float* const* w_edge_msg) {
+  if (!p) return GIGL_E_INVALID_ARG;
+  gigl_ctx* ctx = p->ctx;
+  GIGL_REQUIRE(ctx, p->kind == 1, "edge features apply to GAT plans (gigl_gat_plan_create)");
+  GIGL_REQUIRE(ctx, edge_table && att_edge_folded, "null argument");
+  GIGL_REQUIRE(ctx, edge_table->dtype == GIGL_DTYPE_F32 && edge_table->n == p->graph->e,
+               "the edge table holds one fp32 row per resident edge (%lld rows, %lld edges)", (long long)edge_table->n,
+               (long long)p->graph->e);
+  const int32_t De = edge_table->d;
+  if (De < 1 || De > 64)  // (the first layer keeps one lane per component of an edge row: gigl_gat_input_layer_fused)
+    return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "GAT plan: edge_dim %d outside [1,64]", De);
+  for (int l = 0; l < p->hops; ++l) GIGL_REQUIRE(ctx, att_edge_folded[l], "layer %d: null folded att_edge", l);
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (p->captured) {  // the pointers are baked into the captured kernels
+    hipStreamSynchronize(ctx->stream);
+    drop_graphs(p);
+  }
+  auto alloc = [&](size_t bytes) -> void* {
+    void* q = nullptr;
+    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
+    p->owned.push_back(q);
+    return q;
+  };
+  const int64_t positions = p->un.cap_edges + (p->alias_rows ? p->last_slots : 0);
+  int32_t max_h = 1;
+  for (int l = 0; l < p->hops; ++l) max_h = p->heads[l] > max_h ? p->heads[l] : max_h;
+  if (!p->eid) {  // sized once, for every later run (nothing is allocated inside a run: the plan is captured)
+    GIGL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (alpha_scratch is replaced: no launch may still use it)
+    int32_t* eid = (int32_t*)alloc((size_t)positions * 4);
+    float* alpha = (float*)alloc((size_t)(2 * p->act_rows + positions) * max_h * 4);
+    if (!eid || !alpha) return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the GAT plan's edge workspace failed");
+    GIGL_HIP_CHECK(ctx, hipMemset(eid, 0xFF, (size_t)positions * 4));
+    p->eid = eid;
+    p->alpha_scratch = alpha;
+  }
+  const size_t ze_floats = (size_t)p->act_rows * p->heads[0] * 64;
+  if (w_edge_msg && w_edge_msg[0] && !p->ze) {
+    p->ze = (float*)alloc(ze_floats * 4);
+    if (!p->ze) return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the GAT plan's edge workspace failed");
+  }
+  for (int l = 0; l < p->hops; ++l) {
+    p->att_edge[l] = att_edge_folded[l];
+    p->w_msg[l] = w_edge_msg ? w_edge_msg[l] : nullptr;
+  }
+  p->efeat = edge_table;
+  return GIGL_OK;
+}
+
+int32_t gigl_sage_plan_set_l2_normalize(gigl_sage_plan* p, int32_t on) {
+  if (!p) return GIGL_E_INVALID_ARG;
+  p->l2_normalize = on != 0;  // (the stage that writes `out` runs eagerly: no captured graph holds the decision)
+  return GIGL_OK;
 }
 
 // The first layer's operands are rows of the feature table reduced by mean / max (|.| <= the table's largest magnitude),

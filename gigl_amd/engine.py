@@ -1173,13 +1173,16 @@ class HipEngine:
 
     # ---- one-call batch pipeline -----------------------------------------------------------
     def make_sage_plan(self, weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]], b: int,
-                       fanouts: Sequence[int], act_last: bool = False, groups: int = 1, aggr: str = "mean") -> "SagePlan":
+                       fanouts: Sequence[int], act_last: bool = False, groups: int = 1, aggr: str = "mean",
+                       l2_normalize: bool = False) -> "SagePlan":
         """weights[l]: fused fp32 [out_l, 2*in_l] = cat(lin_l.weight, lin_r.weight, dim=1) on this device.
         groups > 1: one call takes groups*b roots = `groups` independent batches of b roots each.
-        aggr: "mean" | "sum" | "max" (PyG SAGEConv aggr)."""
+        aggr: "mean" | "sum" | "max" (PyG SAGEConv aggr).  l2_normalize: the output rows are L2-normalised."""
         plan = SagePlan(self, weights, biases, b, fanouts, act_last, groups)
         if aggr != "mean":
             check(self._lib.gigl_sage_plan_set_aggr(plan._plan, _lib.AGGR[aggr]), self._ctx)
+        if l2_normalize:
+            plan.set_l2_normalize(True)
         return plan
 
 
@@ -1258,6 +1261,10 @@ class SagePlan:
         assert proj.is_cuda and proj.dtype == torch.float32 and proj.is_contiguous() and proj.shape[1] == 2 * self.dims[1]
         check(self._lib.gigl_sage_plan_set_projected_input(self._plan, C.c_void_p(proj.data_ptr())), self.eng._ctx)
         self._proj = proj  # borrowed by the plan
+
+    def set_l2_normalize(self, on: bool = True) -> None:
+        """the output rows become x / max(|x|_2, 1e-12), torch.nn.functional.normalize (gigl_sage_plan_set_l2_normalize)"""
+        check(self._lib.gigl_sage_plan_set_l2_normalize(self._plan, 1 if on else 0), self.eng._ctx)
 
     def half_split(self) -> bool:
         """the first projection runs over two fp16 planes per operand (gigl_sage_plan_half_split)"""
@@ -1726,10 +1733,16 @@ class GatPlan(SagePlan):
     handle is a gigl_sage_plan: run / use_graph / stats / last_batch_to_host are SagePlan's)"""
 
     def __init__(self, eng: HipEngine, weights, att_src, att_dst, biases, heads, channels, b: int, fanouts,
-                 negative_slope: float = 0.2, act_last: bool = False, groups: int = 1):
+                 negative_slope: float = 0.2, act_last: bool = False, groups: int = 1, att_edge=None, edge_msg=None,
+                 l2_normalize: bool = False):
+        """att_edge (edge features, gigl_gat_plan_set_edge_features): per layer the folded [heads, De] att_edge
+        (GATConv.folded_att_edge); edge_msg: per layer EdgeAttrGATConv's message weight [heads*channels, De] or None.
+        The engine's resident edge table (load_edge_features) is read in place."""
         assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
         L = len(fanouts)
         assert len(weights) == len(att_src) == len(att_dst) == len(heads) == len(channels) == L and groups >= 1
+        if att_edge is not None and not getattr(eng, "_efeat_handle", None):
+            raise RuntimeError("a GAT plan with edge features needs the engine's edge table (load_edge_features)")
         self.group_roots, self.groups = int(b), int(groups)
         self.eng, self.b, self.fanouts = eng, int(b) * int(groups), [int(f) for f in fanouts]
         self._lib = eng._lib
@@ -1746,6 +1759,28 @@ class GatPlan(SagePlan):
         if not hasattr(eng, "_plans"):
             eng._plans = []
         eng._plans.append(self)
+        self._keep_edge = None
+        try:
+            if att_edge is not None:
+                self._set_edge_params(att_edge, edge_msg)
+            if l2_normalize:
+                self.set_l2_normalize(True)
+        except Exception:
+            self.close()
+            raise
+
+    def _set_edge_params(self, att_edge, edge_msg) -> None:
+        L = len(self.fanouts)
+        edge_msg = [None] * L if edge_msg is None else list(edge_msg)
+        assert len(att_edge) == L and len(edge_msg) == L
+        dev = lambda t: t.detach().to(device=self.eng.device, dtype=torch.float32).contiguous()
+        ae, em = [dev(a) for a in att_edge], [None if m is None else dev(m) for m in edge_msg]
+        de = self.eng.edge_feat_dim
+        assert all(a.dim() == 2 and a.shape[1] == de for a in ae), "att_edge rows do not match the edge table's width"
+        arr = lambda ts: (C.c_void_p * L)(*[(t.data_ptr() if t is not None else None) for t in ts])
+        check(self._lib.gigl_gat_plan_set_edge_features(self._plan, self.eng._efeat_handle, arr(ae), arr(em)),
+              self.eng._ctx)
+        self._keep_edge = (ae, em, self.eng._efeat)  # the plan borrows these device buffers and the edge table
 
     def _gat_ptr_arrays(self, weights, att_src, att_dst, biases):
         L = len(weights)
@@ -1756,6 +1791,10 @@ class GatPlan(SagePlan):
         arr = lambda ts: (C.c_void_p * L)(*[(t.data_ptr() if t is not None else None) for t in ts])
         return arr(ws), arr(a_s), arr(a_d), arr(bs)
 
-    def set_weights(self, weights, att_src, att_dst, biases) -> None:
+    def set_weights(self, weights, att_src, att_dst, biases, att_edge=None, edge_msg=None) -> None:
+        """the arguments are GAT.plan_params(): four lists, six for a model with edge features"""
+        assert (att_edge is not None) == (self._keep_edge is not None), "the plan was built with / without edge features"
         check(self._lib.gigl_gat_plan_set_weights(self._plan, *self._gat_ptr_arrays(weights, att_src, att_dst, biases)),
               self.eng._ctx)
+        if att_edge is not None:
+            self._set_edge_params(att_edge, edge_msg)

@@ -350,18 +350,25 @@ class GAT(nn.Module):
     def make_plan(self, eng, b: int, fanouts, groups: int = 1):
         """one-call pipeline (sample -> union -> this model's forward -> one row per root) for batches of `b` roots on
         `eng` (engine.GatPlan); weights are snapshotted — plan.set_weights(*model.plan_params()) after updates.  The
-        first layer runs from the input side (gigl_gat_input_layer_fused): plain GATConv layers, heads concatenated."""
+        first layer runs from the input side (gigl_gat_input_layer_fused), heads concatenated.  A model with `edge_dim`
+        (GATConv(edge_dim) / EdgeAttrGATConv) reads the engine's resident edge table in place
+        (gigl_gat_plan_set_edge_features); the output is L2-normalised in the plan when the model asks for it."""
         from .engine import GatPlan
         assert len(fanouts) == self.num_layers, "one hop per layer"
-        if self.edge_dim is not None or any(not c.concat and c.heads > 1 for c in self.conv_layers) or \
-                self.should_l2_normalize_embedding_layer_output:
-            raise NotImplementedError("the one-call plan computes plain GATConv layers (no edge features, concatenated "
-                                      "heads, no output normalisation); use forward(HipBatch)")
-        w, a_s, a_d, bs = self.plan_params()
+        if any(not c.concat and c.heads > 1 for c in self.conv_layers):
+            raise NotImplementedError("the one-call plan computes concatenated heads; use forward(HipBatch)")
+        if self.edge_dim is not None:
+            if not getattr(eng, "_efeat_handle", None):
+                raise RuntimeError(f"the model was built with edge_dim={self.edge_dim} but the engine holds no edge "
+                                   "features (HipEngine.load_edge_features)")
+            if eng.edge_feat_dim != self.edge_dim:
+                raise ValueError(f"edge_dim={self.edge_dim} but the engine's edge table is {eng.edge_feat_dim} wide")
+        w, a_s, a_d, bs, *edge = self.plan_params()
         return GatPlan(eng, w, a_s, a_d, bs, [c.heads for c in self.conv_layers],
                        [c.out_channels for c in self.conv_layers], b, fanouts,
                        negative_slope=self.conv_layers[0].negative_slope, act_last=self.activation_after_last_conv,
-                       groups=groups)
+                       groups=groups, att_edge=edge[0] if edge else None, edge_msg=edge[1] if edge else None,
+                       l2_normalize=self.should_l2_normalize_embedding_layer_output)
 
     def make_dist_plan(self, comm, b: int, fanouts, group_roots=None, max_window_end: int = -1, **kw):
         """the sharded one-call plan of this model on a hash-partitioned graph (dist.DistGatPlan): same layer
@@ -379,9 +386,15 @@ class GAT(nn.Module):
                            group_roots=group_roots, max_window_end=max_window_end, **kw)
 
     def plan_params(self):
+        """the arguments of GatPlan.set_weights: weights, att_src, att_dst, biases — and, for a model with edge features,
+        the folded att_edge and the edge message weights (None per plain GATConv layer)"""
         cs = self.conv_layers
-        return ([c.lin.weight.detach() for c in cs], [c.att_src.detach() for c in cs], [c.att_dst.detach() for c in cs],
+        base = ([c.lin.weight.detach() for c in cs], [c.att_src.detach() for c in cs], [c.att_dst.detach() for c in cs],
                 [None if c.bias is None else c.bias.detach() for c in cs])
+        if self.edge_dim is None:
+            return base
+        msg = [c.edge_message_weight() for c in cs]
+        return base + ([c.folded_att_edge().detach() for c in cs], [None if m is None else m.detach() for m in msg])
 
     def _forward_graph(self, g, eng) -> torch.Tensor:
         if eng is None:

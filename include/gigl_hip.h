@@ -1128,7 +1128,8 @@ int32_t gigl_sage_plan_stats(gigl_sage_plan* plan, const uint32_t* roots, int64_
  * graph/feature tables are baked into the captured kernels: call again (or set_weights + use_graph) after
  * changing them.  gigl_sage_plan_flush_profile folds the timing events of in-flight replays into
  * gigl_profile_read (synchronises). */
-/* The same one-call pipeline with GAT layers (GAT.init_conv_layers, homogeneous.py:300-343; no edge features):
+/* The same one-call pipeline with GAT layers (GAT.init_conv_layers, homogeneous.py:300-343; edge features:
+ * gigl_gat_plan_set_edge_features):
  * sample -> union -> layer 0 from the input side in one row pass (gigl_gat_input_layer_fused: the plan's leaf-global
  * union needs no dense numbering of the leaves) -> layers >= 1 as projection + gigl_gat_aggregate -> one row per root.
  * w[l]: lin weight [heads[l]*channels[l]][in_l] (in_0 = the feature dim, in_l = heads[l-1]*channels[l-1]: heads are
@@ -1141,6 +1142,22 @@ int32_t gigl_gat_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, 
                              float negative_slope, int32_t act_last, gigl_sage_plan** out);
 int32_t gigl_gat_plan_set_weights(gigl_sage_plan* plan, const float* const* w, const float* const* att_src,
                                   const float* const* att_dst, const float* const* bias);
+/* Edge features for the GAT plan: GATConv(edge_dim) (GAT.init_conv_layers passes edge_dim, homogeneous.py:300-343) and
+ * EdgeAttrGATConv (python/gigl/src/common/models/pyg/nn/conv/edge_attr_gat_conv.py:11-144), with the semantics of
+ * gigl_gat_aggregate_edge in every layer.  edge_table: [n_edges][De] fp32 rows in the resident graph's `col` order, read
+ * IN PLACE — the plan's GRAPH part finds the table row of every edge of the batch's union graph (one wave per row, a
+ * binary search in the resident row), the first layer adds <e, v_h> to the logits as it reads the feature rows, layers
+ * >= 1 index the table from the attention kernels; no dense [cap_edges][De] array is built, which is what
+ * gigl_union_edge_ids + a host-driven gather gave the staged forward.  att_edge_folded[l]: [heads_l][De] = W_e^T att_edge
+ * per head; w_edge_msg[l]: [heads_l*channels_l][De], or NULL (the array or an entry: plain GATConv, the edge features
+ * enter the logits only).  DEVICE, borrowed.  De in [1, 64] (GIGL_E_UNSUPPORTED beyond).  Call after create and after
+ * every gigl_gat_plan_set_weights that changes the edge parameters; captured graphs are dropped. */
+int32_t gigl_gat_plan_set_edge_features(gigl_sage_plan* plan, gigl_feat* edge_table, const float* const* att_edge_folded,
+                                        const float* const* w_edge_msg);
+/* SAGE and GAT plans: the b output rows become x / max(|x|_2, 1e-12) — torch.nn.functional.normalize, the encoder's last
+ * step under should_l2_normalize_embedding_layer_output (BasicHomogeneousGNN.forward, homogeneous.py:107-153; on by
+ * default in node_anchor_based_link_prediction_modeling_task_spec.py:95-96).  Rows of a failed batch set stay NaN. */
+int32_t gigl_sage_plan_set_l2_normalize(gigl_sage_plan* plan, int32_t on);
 /* the SAGE layers' reduction: GIGL_AGGR_MEAN (default) | GIGL_AGGR_SUM | GIGL_AGGR_MAX (PyG SAGEConv aggr) */
 int32_t gigl_sage_plan_set_aggr(gigl_sage_plan* plan, int32_t aggr);
 /* Projected input (inference passes over a feature table whose rows are wider than the first layer's output — MAG240M:
