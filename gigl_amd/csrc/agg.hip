@@ -2536,12 +2536,29 @@ __global__ __launch_bounds__(256) void gat_edge_msg_epilogue_kernel(const float*
 // own backward.  Each row is read once, each edge's logit and d alpha formed from the source row as it is read (reduced
 // together, gigl_wave_reduce16).  The self loop is the first "edge" (x_e = x_i, w = 1).  A wave keeps its d us / d ud sums
 // in registers over all its rows and adds them to `du` once, at the end (fp32 atomics).
-template <typename T, int V, int H>
+// EDGE (the training plan over a graph with edge features; the forward is gat_input_online_kernel<.., EDGE>): the logit
+// gains a_e = <e_e, v> (v = the folded att_edge), the self loop the mean of the row's a_e; with edge MESSAGES (ed.dze !=
+// NULL: dze_i = W_msg^T dy_i, [rows][H][De]) d alpha_e gains <dze_i, e_e>.  Both are scalars per edge: lanes over the edges
+// of a 64-edge chunk form them from the table row — in the forward's pre-pass, which gives the self loop its means, and
+// again as the chunk is consumed — and the group loop takes them from the owning lane.  New output d v = sum_e dpre_e e_e
+// (the self loop through its mean attribute): the same A / B pair as d us, ONE float each per head in lane k < De (Ae, Be),
+// the self loop's share added at the row's end from its running weight and the plain sum of e[k] (as the forward's ze);
+// a wave keeps d v in a register per head over all its rows, the workgroup adds its four waves' and issues one atomic per
+// component.
+struct GatEdgeBwd {
+  const int32_t* eid = nullptr;  // [positions of col] row of `table` per stored edge (< 0: a zero attribute)
+  const float* table = nullptr;  // [n_edges][De] fp32
+  const float* v = nullptr;      // [H][De] folded att_edge
+  int De = 0;
+  const float* dze = nullptr;    // [rows][H][De] or NULL (no edge messages)
+  float* dv = nullptr;           // [H][De] out (ADDED to)
+};
+template <typename T, int V, int H, bool EDGE = false>
 __global__ __launch_bounds__(256) void gat_input_backward_onepass_kernel(
     const T* __restrict__ src, int d, const uint32_t* __restrict__ gather_ids, const float* __restrict__ u,
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rowend, const int32_t* __restrict__ col,
     const int32_t* __restrict__ n_rows_dev, float slope, const float* __restrict__ dz, int64_t head_stride,
-    float* __restrict__ du) {
+    float* __restrict__ du, GatEdgeBwd ed) {
   constexpr int U = 4;                                  // feature rows in flight per wave
   constexpr int NV = U * 2 * H, NC = (NV + 15) / 16;    // (logit, d alpha) per head and edge of a group
   typedef RawRow4<T> RR;
@@ -2570,11 +2587,74 @@ __global__ __launch_bounds__(256) void gat_input_backward_onepass_kernel(
       acc_d[h][v] = zero4;
     }
   }
+  float acc_v[H];  // (EDGE) lane k < De: d v[h][k] over this wave's rows
+#pragma unroll
+  for (int h = 0; h < H; ++h) acc_v[h] = 0.f;
   for (int i = wave; i < n_rows; i += waves) {
     const int e0 = rowptr[i], m = rowend[i] - e0;
     const uint32_t self_gid = gather_ids[i];
     float4_t xs[V], dzv[H][V], A[H][V], B[H][V];
     float sd[H], mx[H], den[H], Sw[H], a_s[H], b_s[H];
+    // (EDGE) this lane's edge of the chunk at c0: kept?, the source's global id, its table row, its logit term <e, v_h> and
+    // its d alpha term <e, dze_i,h>
+    auto chunk_edge = [&](int c0, uint32_t& gid, int& id, float (&ae)[H], float (&de)[H]) -> bool {
+      bool take = false;
+      gid = self_gid;
+      id = -1;
+#pragma unroll
+      for (int h = 0; h < H; ++h) ae[h] = de[h] = 0.f;
+      if (c0 + lane < m) {
+        const int j = col[e0 + c0 + lane];
+        take = j != i;
+        gid = gather_ids[j];
+        if (take) id = ed.eid[e0 + c0 + lane];
+        if (id >= 0) {
+          const float* er = ed.table + (int64_t)id * ed.De;
+          for (int k = 0; k < ed.De; ++k) {
+            const float ev = er[k];
+#pragma unroll
+            for (int h = 0; h < H; ++h) {
+              ae[h] += ev * ed.v[h * ed.De + k];
+              if (ed.dze) de[h] += ev * ed.dze[((int64_t)i * H + h) * ed.De + k];
+            }
+          }
+        }
+      }
+      return take;
+    };
+    float ae_self[H], de_self[H], wself[H], cs_self[H], cds_self[H], Ae[H], Be[H], esum = 0.f, inv_cnt = 0.f;
+#pragma unroll
+    for (int h = 0; h < H; ++h) ae_self[h] = de_self[h] = cs_self[h] = cds_self[h] = Ae[h] = Be[h] = 0.f, wself[h] = 1.f;
+    if constexpr (EDGE) {
+      float cntf = 0.f;
+      for (int c0 = 0; c0 < m; c0 += 64) {
+        uint32_t gid;
+        int id;
+        float ae[H], de[H];
+        if (chunk_edge(c0, gid, id, ae, de)) {
+          cntf += 1.f;
+#pragma unroll
+          for (int h = 0; h < H; ++h) {
+            ae_self[h] += ae[h];
+            de_self[h] += de[h];
+          }
+        }
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        cntf += __shfl_xor(cntf, off, 64);
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+          ae_self[h] += __shfl_xor(ae_self[h], off, 64);
+          de_self[h] += __shfl_xor(de_self[h], off, 64);
+        }
+      }
+      inv_cnt = cntf > 0.f ? 1.0f / cntf : 0.f;
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        ae_self[h] = lane_value(ae_self[h] * inv_cnt, 0);
+        de_self[h] = lane_value(de_self[h] * inv_cnt, 0);
+      }
+    }
     {
       float pv[16];
 #pragma unroll
@@ -2597,9 +2677,13 @@ __global__ __launch_bounds__(256) void gat_input_backward_onepass_kernel(
       for (int h = 0; h < H; ++h) {
         const float fs = lane_value(tot, h << 2);
         sd[h] = lane_value(tot, (H + h) << 2);
-        const float das = lane_value(tot, (2 * H + h) << 2);
-        const float pre_self = fs + sd[h];
+        const float das = EDGE ? lane_value(tot, (2 * H + h) << 2) + de_self[h] : lane_value(tot, (2 * H + h) << 2);
+        const float pre_self = EDGE ? fs + sd[h] + ae_self[h] : fs + sd[h];
         const float lk = pre_self > 0.f ? 1.f : slope;
+        if constexpr (EDGE) {
+          cs_self[h] = lk;
+          cds_self[h] = lk * das;
+        }
         mx[h] = leaky(pre_self);
         den[h] = 1.f;     // the self loop: w = exp(zl_self - max) = 1
         Sw[h] = das;
@@ -2625,7 +2709,11 @@ __global__ __launch_bounds__(256) void gat_input_backward_onepass_kernel(
       const int mm = min(64, m - c0);
       uint32_t gid = self_gid;
       bool take = false;
-      if (lane < mm) {
+      int eidl = -1;
+      float ael[H], del[H];
+      if constexpr (EDGE) {
+        take = chunk_edge(c0, gid, eidl, ael, del);
+      } else if (lane < mm) {
         const int j = col[e0 + c0 + lane];
         take = j != i;
         gid = gather_ids[j];
@@ -2660,12 +2748,25 @@ __global__ __launch_bounds__(256) void gat_input_backward_onepass_kernel(
 #pragma unroll
           for (int k = 0; k < 16; ++k) vals[cc * 16 + k] = lane_value(tot, k << 2);
         }
+        float ev[EDGE ? U : 1];  // (EDGE) lane k: component k of the U edges' attribute rows
+        if constexpr (EDGE) {
+#pragma unroll
+          for (int t = 0; t < U; ++t) {
+            const int id = __builtin_amdgcn_readlane(eidl, (e + t) & 63);
+            ev[t] = (live[t] && id >= 0 && lane < ed.De) ? ed.table[(int64_t)id * ed.De + lane] : 0.f;
+            esum += ev[t];
+          }
+        }
 #pragma unroll
         for (int t = 0; t < U; ++t) {
           if (!live[t]) continue;
 #pragma unroll
           for (int h = 0; h < H; ++h) {
-            const float pre = vals[(t * H + h) * 2] + sd[h], da = vals[(t * H + h) * 2 + 1];
+            float pre = vals[(t * H + h) * 2] + sd[h], da = vals[(t * H + h) * 2 + 1];
+            if constexpr (EDGE) {
+              pre += lane_value(ael[h], (e + t) & 63);
+              da += lane_value(del[h], (e + t) & 63);
+            }
             const float zl = leaky(pre), lk = pre > 0.f ? 1.f : slope;
             if (zl > mx[h]) {  // (wave-uniform: the values are broadcasts) the running maximum grows: everything rescales
               const float sc = __expf(mx[h] - zl);
@@ -2673,6 +2774,11 @@ __global__ __launch_bounds__(256) void gat_input_backward_onepass_kernel(
               Sw[h] *= sc;
               a_s[h] *= sc;
               b_s[h] *= sc;
+              if constexpr (EDGE) {
+                Ae[h] *= sc;
+                Be[h] *= sc;
+                wself[h] *= sc;
+              }
 #pragma unroll
               for (int v = 0; v < V; ++v) {
                 A[h][v] = sc * A[h][v];
@@ -2691,6 +2797,10 @@ __global__ __launch_bounds__(256) void gat_input_backward_onepass_kernel(
               A[h][v] += cd * xv;
               B[h][v] += c * xv;
             }
+            if constexpr (EDGE) {
+              Ae[h] += cd * ev[t];
+              Be[h] += c * ev[t];
+            }
           }
         }
       }
@@ -2700,6 +2810,10 @@ __global__ __launch_bounds__(256) void gat_input_backward_onepass_kernel(
       const float inv = 1.0f / (den[h] + 1e-16f);
       const float S = Sw[h] * inv;
       const float sum_dpre = (a_s[h] - S * b_s[h]) * inv;
+      if constexpr (EDGE) {  // (the self loop: weight wself, the mean attribute)
+        const float em = esum * inv_cnt;
+        acc_v[h] += inv * ((Ae[h] + wself[h] * cds_self[h] * em) - S * (Be[h] + wself[h] * cs_self[h] * em));
+      }
 #pragma unroll
       for (int v = 0; v < V; ++v) {
         acc_s[h][v] += inv * (A[h][v] - S * B[h][v]);
@@ -2708,7 +2822,12 @@ __global__ __launch_bounds__(256) void gat_input_backward_onepass_kernel(
     }
   }
   __shared__ float4_t s_red[2 * H * V * 64];
+  __shared__ float s_v[EDGE ? 4 * H * 64 : 1];
   const int wv = threadIdx.x >> 6;
+  if constexpr (EDGE) {
+#pragma unroll
+    for (int h = 0; h < H; ++h) s_v[(wv * H + h) * 64 + lane] = acc_v[h];
+  }
   for (int w = 0; w < 4; ++w) {
     if (wv == w) {
 #pragma unroll
@@ -2724,6 +2843,15 @@ __global__ __launch_bounds__(256) void gat_input_backward_onepass_kernel(
     __syncthreads();
   }
   if (wv != 0) return;
+  if constexpr (EDGE) {
+    if (lane < ed.De) {
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        const float t = (s_v[h * 64 + lane] + s_v[(H + h) * 64 + lane]) + (s_v[(2 * H + h) * 64 + lane] + s_v[(3 * H + h) * 64 + lane]);
+        if (t != 0.f) atomicAdd(ed.dv + h * ed.De + lane, t);
+      }
+    }
+  }
 #pragma unroll
   for (int h = 0; h < 2 * H; ++h)
 #pragma unroll
@@ -3250,6 +3378,204 @@ __global__ __launch_bounds__(256) void gat_backward_kernel(
         }
       }
     }
+  }
+}
+
+// ---- the same backward for ONE head over a graph with edge features, the attributes read in place from the resident
+// edge table (the training plan's second layer: the roots' rows).  The edge at col position p carries table[eid[p]]
+// (eid < 0: a zero attribute); no dense [cap_edges][De] array, no per-edge output, any C % 4 == 0 up to 256 V.
+//   pre_e = a_src[j] + a_dst[i] + <e_e, v>;  d alpha_e = <g_i, x_e> + <dze_i, e_e>  (dze_i = W_msg^T g_i: edge messages)
+//   dx_e += alpha_e g_i;  d a_src[j] += dpre_e;  d a_dst[i] += sum dpre_e;  d v += sum_e dpre_e e_e;  z_i = sum_e alpha_e e_e
+// One wave per destination row, lane l owning the float4 chunks v*64 + l.  Pass 1: lanes over the row's edges — every
+// lane forms its edge's two scalars from the table row — give max, denominator, the count and the sums for the self loop's
+// MEAN attribute; pass 2 reads every source row once, the edge's scalars taken from the lane that formed them, lane k < De
+// holding component k of the attribute row.  d v stays in a register over the wave's rows: one atomic per lane at the end.
+template <int V>
+__global__ __launch_bounds__(256) void gat_backward_indexed_kernel(
+    const float* __restrict__ h, const float* __restrict__ a_src, const float* __restrict__ a_dst,
+    const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rowend, const int32_t* __restrict__ col,
+    const int32_t* __restrict__ n_rows_dev, int C, float slope, const float* __restrict__ out_pre,
+    const float* __restrict__ dout, const int32_t* __restrict__ eid, const float* __restrict__ table, int De,
+    const float* __restrict__ vatt, const float* __restrict__ dze, float* __restrict__ dh, float* __restrict__ d_src,
+    float* __restrict__ d_dst, float* __restrict__ dv, float* __restrict__ zout) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  const int waves = (int)(((int64_t)gridDim.x * blockDim.x) >> 6);
+  const int n_rows = *n_rows_dev, chunks = C >> 2;
+  const float4_t zero4 = {0.f, 0.f, 0.f, 0.f};
+  auto dot4 = [](const float4_t& a, const float4_t& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; };
+  auto wave_sum = [](float t) {
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+    return t;
+  };
+  bool on[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) on[v] = v * 64 + lane < chunks;
+  float acc_v = 0.f;  // lane k < De: d v[k] over this wave's rows
+  for (int i = wave; i < n_rows; i += waves) {
+    const int e0 = rowptr[i], m = rowend[i] - e0;
+    float4_t g[V], xi[V];
+    float Sp = 0.f, dsp = 0.f;
+    bool nz = false;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      g[v] = on[v] ? reinterpret_cast<const float4_t*>(dout + (int64_t)i * C)[v * 64 + lane] : zero4;
+      xi[v] = on[v] ? reinterpret_cast<const float4_t*>(h + (int64_t)i * C)[v * 64 + lane] : zero4;
+      const float4_t o = on[v] ? reinterpret_cast<const float4_t*>(out_pre + (int64_t)i * C)[v * 64 + lane] : zero4;
+      Sp += dot4(g[v], o);
+      dsp += dot4(g[v], xi[v]);
+      nz |= g[v].x != 0.f || g[v].y != 0.f || g[v].z != 0.f || g[v].w != 0.f;
+    }
+    if (__ballot(nz) == 0ull) {  // (a padding root: no gradient, a zero z row)
+      if (zout && lane < De) zout[(int64_t)i * De + lane] = 0.f;
+      continue;
+    }
+    const float S = wave_sum(Sp);
+    const float ad = a_dst[i];
+    // this lane's edge of the chunk at c0: kept?, its source, its table row, <e, v> and <e, dze_i>
+    auto chunk_edge = [&](int c0, int& j, int& id, float& ae, float& de) -> bool {
+      bool take = false;
+      j = i;
+      id = -1;
+      ae = de = 0.f;
+      if (c0 + lane < m) {
+        j = col[e0 + c0 + lane];
+        take = j != i;
+        if (take) id = eid[e0 + c0 + lane];
+        if (id >= 0) {
+          const float* er = table + (int64_t)id * De;
+          for (int k = 0; k < De; ++k) {
+            ae += er[k] * vatt[k];
+            if (dze) de += er[k] * dze[(int64_t)i * De + k];
+          }
+        }
+      }
+      return take;
+    };
+    // pass 1
+    float mx = -INFINITY, den = 0.f, cnt = 0.f, sum_ae = 0.f, sum_de = 0.f;
+    for (int c0 = 0; c0 < m; c0 += 64) {
+      int j, id;
+      float ae, de;
+      if (chunk_edge(c0, j, id, ae, de)) {
+        float z = a_src[j] + ad + ae;
+        z = z > 0.f ? z : slope * z;
+        const float nm = fmaxf(mx, z);
+        den = den * __expf(mx - nm) + __expf(z - nm);
+        mx = nm;
+        cnt += 1.f;
+        sum_ae += ae;
+        sum_de += de;
+      }
+    }
+    cnt = wave_sum(cnt);
+    sum_ae = wave_sum(sum_ae);
+    sum_de = wave_sum(sum_de);
+    const float inv_cnt = cnt > 0.f ? 1.0f / cnt : 0.f;
+    const float pre_self = a_src[i] + ad + sum_ae * inv_cnt;
+    const float z_self = pre_self > 0.f ? pre_self : slope * pre_self;
+    float gmx = fmaxf(mx, z_self);
+    for (int off = 32; off > 0; off >>= 1) gmx = fmaxf(gmx, __shfl_xor(gmx, off, 64));
+    den = wave_sum(mx == -INFINITY ? 0.f : den * __expf(mx - gmx)) + __expf(z_self - gmx);
+    const float inv_den = 1.0f / (den + 1e-16f);
+    const float al_self = __expf(z_self - gmx) * inv_den;
+    const float da_self = wave_sum(dsp) + sum_de * inv_cnt;
+    const float dpre_self = al_self * (da_self - S) * (pre_self > 0.f ? 1.f : slope);
+    float dd = dpre_self, zl = 0.f, dvl = 0.f, esum = 0.f;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      if (!on[v]) continue;
+      float* o = dh + (int64_t)i * C + 4 * (v * 64 + lane);
+      atomicAdd(o + 0, al_self * g[v].x);
+      atomicAdd(o + 1, al_self * g[v].y);
+      atomicAdd(o + 2, al_self * g[v].z);
+      atomicAdd(o + 3, al_self * g[v].w);
+    }
+    if (lane == 0) atomicAdd(d_src + i, dpre_self);
+    // pass 2
+    for (int c0 = 0; c0 < m; c0 += 64) {
+      const int mm = min(64, m - c0);
+      int jl, idl;
+      float ael, del;
+      const bool take = chunk_edge(c0, jl, idl, ael, del);
+      const float prel = take ? a_src[jl] + ad + ael : 0.f;
+      const unsigned long long keep = __ballot(take);
+      for (int e = 0; e < mm; ++e) {
+        if (!((keep >> e) & 1ull)) continue;  // (uniform over the wave)
+        const int j = __builtin_amdgcn_readlane(jl, e), id = __builtin_amdgcn_readlane(idl, e);
+        const float pre = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, prel), e));
+        const float de = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, del), e));
+        float dap = 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const float4_t x = on[v] ? reinterpret_cast<const float4_t*>(h + (int64_t)j * C)[v * 64 + lane] : zero4;
+          dap += dot4(g[v], x);
+        }
+        const float ev = (id >= 0 && lane < De) ? table[(int64_t)id * De + lane] : 0.f;
+        const float da = wave_sum(dap) + de;
+        const float z = pre > 0.f ? pre : slope * pre;
+        const float al = __expf(z - gmx) * inv_den;
+        const float dpre = al * (da - S) * (pre > 0.f ? 1.f : slope);
+        dd += dpre;
+        zl += al * ev;
+        dvl += dpre * ev;
+        esum += ev;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          if (!on[v]) continue;
+          float* o = dh + (int64_t)j * C + 4 * (v * 64 + lane);
+          atomicAdd(o + 0, al * g[v].x);
+          atomicAdd(o + 1, al * g[v].y);
+          atomicAdd(o + 2, al * g[v].z);
+          atomicAdd(o + 3, al * g[v].w);
+        }
+        if (lane == 0) atomicAdd(d_src + j, dpre);
+      }
+    }
+    if (lane == 0) atomicAdd(d_dst + i, dd);
+    const float em = esum * inv_cnt;  // the self loop's (mean) attribute
+    acc_v += dvl + dpre_self * em;
+    if (zout && lane < De) zout[(int64_t)i * De + lane] = zl + al_self * em;
+  }
+  if (lane < De && acc_v != 0.f) atomicAdd(dv + lane, acc_v);
+}
+
+// the edge messages' two small products around that backward, for a layer whose output gradient dy is stored as H planes
+// (dy[h][i][c] = dy_base[h * plane + i * C + c]; one plane: plain rows) and whose z is [rows][H][De]:
+//   dze[i][h][k] = sum_c W_msg[hC + c][k] dy[h][i][c]                     (one thread per element)
+__global__ __launch_bounds__(256) void gat_edge_msg_dze_kernel(const float* __restrict__ dy, int64_t plane,
+                                                               const float* __restrict__ w_msg,
+                                                               const int32_t* __restrict__ n_rows_dev, int H, int C, int De,
+                                                               float* __restrict__ dze) {
+  const int64_t n = (int64_t)(*n_rows_dev) * H * De;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+    const int k = (int)(t % De), hh = (int)((t / De) % H);
+    const int64_t i = t / ((int64_t)De * H);
+    const float* dr = dy + hh * plane + i * C;
+    const float* wr = w_msg + (int64_t)hh * C * De + k;
+    float a = 0.f;
+    for (int c = 0; c < C; ++c) a += wr[(int64_t)c * De] * dr[c];
+    dze[t] = a;
+  }
+}
+//   g_w_msg[hC + c][k] += sum_i dy[h][i][c] z[i][h][k]: a workgroup owns GAT_MSG_ROWS rows, a thread the elements
+//   t, t + 256, ... of the [H*C][De] matrix — one atomic per (workgroup, element)
+constexpr int GAT_MSG_ROWS = 64;
+__global__ __launch_bounds__(256) void gat_edge_msg_wgrad_kernel(const float* __restrict__ dy, int64_t plane,
+                                                                 const float* __restrict__ z,
+                                                                 const int32_t* __restrict__ n_rows_dev, int H, int C, int De,
+                                                                 float* __restrict__ g_w_msg) {
+  const int n = *n_rows_dev;
+  const int r0 = blockIdx.x * GAT_MSG_ROWS, r1 = r0 + GAT_MSG_ROWS < n ? r0 + GAT_MSG_ROWS : n;
+  if (r0 >= n) return;
+  const int total = H * C * De;
+  for (int t = threadIdx.x; t < total; t += blockDim.x) {
+    const int k = t % De, r = t / De, hh = r / C, c = r - hh * C;
+    const float* dr = dy + hh * plane + c;
+    const float* zr = z + (int64_t)hh * De + k;
+    float a = 0.f;
+    for (int i = r0; i < r1; ++i) a += dr[(int64_t)i * C] * zr[(int64_t)i * H * De];
+    if (a != 0.f) atomicAdd(g_w_msg + t, a);
   }
 }
 
@@ -4667,15 +4993,33 @@ static int32_t gat_input_shape_ok(gigl_ctx* ctx, int32_t d, int32_t heads, int32
   return GIGL_OK;
 }
 
-int32_t gigl_gat_input_aggregate(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d, const uint32_t* gather_ids,
-                                 const float* u, int32_t heads, float negative_slope, const int32_t* rowptr,
-                                 const int32_t* rowend, const int32_t* col, const int32_t* n_rows_dev, int64_t rows_cap,
-                                 float* z) {
+static int32_t gat_edge_terms_ok(gigl_ctx* ctx, const gigl_gat_edge_terms* edge, const char* who) {
+  GIGL_REQUIRE(ctx, edge->eid && edge->table && edge->att_edge_folded && (!edge->w_edge_msg || edge->ze), "%s: null edge term", who);
+  if (edge->edge_dim < 1 || edge->edge_dim > GAT_INPUT_MAX_EDGE_DIM)
+    return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "%s: edge_dim %d outside [1,%d] (a lane per component of an edge row)", who,
+                     edge->edge_dim, GAT_INPUT_MAX_EDGE_DIM);
+  return GIGL_OK;
+}
+
+int32_t gigl_gat_input_aggregate_edge(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d, const uint32_t* gather_ids,
+                                      const float* u, int32_t heads, float negative_slope, const int32_t* rowptr,
+                                      const int32_t* rowend, const int32_t* col, const int32_t* n_rows_dev, int64_t rows_cap,
+                                      float* z, const gigl_gat_edge_terms* edge) {
   if (!ctx) return GIGL_E_INVALID_ARG;
   GIGL_REQUIRE(ctx, src && gather_ids && u && rowptr && rowend && col && n_rows_dev && z, "null argument");
   GIGL_REQUIRE(ctx, d > 0 && rows_cap >= 0, "bad sizes");
   int32_t rc = gat_input_shape_ok(ctx, d, heads, src_dtype, "gigl_gat_input_aggregate");
   if (rc != GIGL_OK) return rc;
+  GatEdgeIn ed;
+  if (edge) {
+    rc = gat_edge_terms_ok(ctx, edge, "gigl_gat_input_aggregate_edge");
+    if (rc != GIGL_OK) return rc;
+    ed.eid = edge->eid;
+    ed.table = edge->table;
+    ed.v = edge->att_edge_folded;
+    ed.De = edge->edge_dim;
+    ed.ze = edge->w_edge_msg ? edge->ze : nullptr;
+  }
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (rows_cap == 0) return GIGL_OK;
   gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
@@ -4688,8 +5032,16 @@ int32_t gigl_gat_input_aggregate(gigl_ctx* ctx, const void* src, int32_t src_dty
   int64_t blocks = (rows_cap + 3) / 4;
   if (blocks > 256 * 16) blocks = 256 * 16;
 #define GIGL_GAT_AG(TT, PP, HH)                                                                                        \
-  hipLaunchKernelGGL((gat_input_online_kernel<TT, PP, HH>), dim3((unsigned)blocks), dim3(256), 0, st, (const TT*)src, d, \
-                     gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, slope, nkc, head_stride, z, GatEdgeIn{})
+  do {                                                                                                                  \
+    if (edge)                                                                                                           \
+      hipLaunchKernelGGL((gat_input_online_kernel<TT, PP, HH, true>), dim3((unsigned)blocks), dim3(256), 0, st,        \
+                         (const TT*)src, d, gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, slope, nkc,    \
+                         head_stride, z, ed);                                                                           \
+    else                                                                                                                \
+      hipLaunchKernelGGL((gat_input_online_kernel<TT, PP, HH>), dim3((unsigned)blocks), dim3(256), 0, st,              \
+                         (const TT*)src, d, gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, slope, nkc,    \
+                         head_stride, z, ed);                                                                           \
+  } while (0)
 #define GIGL_GAT_AG_P(TT, HH)                                                                                          \
   do {                                                                                                                  \
     if (P == 1) GIGL_GAT_AG(TT, 1, HH);                                                                                \
@@ -4712,16 +5064,49 @@ int32_t gigl_gat_input_aggregate(gigl_ctx* ctx, const void* src, int32_t src_dty
   return GIGL_OK;
 }
 
-int32_t gigl_gat_input_aggregate_backward(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d,
-                                          const uint32_t* gather_ids, const float* u, int32_t heads, float negative_slope,
-                                          const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
-                                          const int32_t* n_rows_dev, int64_t rows_cap, const float* dz,
-                                          float* /* edge_scratch: unused */, float* du) {
+// (the EDGE form of four chunks x four heads — rows wider than 768 floats under four heads — is not built: its state does not
+// fit the register file, and a spilling kernel is not offered; gigl_gat_input_aggregate_backward_edge refuses the shape)
+template <typename T, int V, int H>
+static void launch_gat_input_backward(bool edge, unsigned blocks, hipStream_t st, const T* src, int d, const uint32_t* gather_ids,
+                                      const float* u, const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
+                                      const int32_t* n_rows_dev, float slope, const float* dz, int64_t head_stride, float* du,
+                                      const GatEdgeBwd& ed) {
+  if constexpr (V * H < 16) {
+    if (edge) {
+      hipLaunchKernelGGL((gat_input_backward_onepass_kernel<T, V, H, true>), dim3(blocks), dim3(256), 0, st, src, d, gather_ids, u,
+                         rowptr, rowend, col, n_rows_dev, slope, dz, head_stride, du, ed);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((gat_input_backward_onepass_kernel<T, V, H>), dim3(blocks), dim3(256), 0, st, src, d, gather_ids, u, rowptr,
+                     rowend, col, n_rows_dev, slope, dz, head_stride, du, ed);
+}
+
+int32_t gigl_gat_input_aggregate_backward_edge(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d,
+                                               const uint32_t* gather_ids, const float* u, int32_t heads, float negative_slope,
+                                               const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
+                                               const int32_t* n_rows_dev, int64_t rows_cap, const float* dz, float* du,
+                                               const gigl_gat_edge_terms* edge, const float* dze, float* dv) {
   if (!ctx) return GIGL_E_INVALID_ARG;
   GIGL_REQUIRE(ctx, src && gather_ids && u && rowptr && rowend && col && n_rows_dev && dz && du, "null argument");
   GIGL_REQUIRE(ctx, d > 0 && rows_cap >= 0, "bad sizes");
   int32_t rc = gat_input_shape_ok(ctx, d, heads, src_dtype, "gigl_gat_input_aggregate_backward");
   if (rc != GIGL_OK) return rc;
+  GatEdgeBwd ed;
+  if (edge) {
+    rc = gat_edge_terms_ok(ctx, edge, "gigl_gat_input_aggregate_backward_edge");
+    if (rc != GIGL_OK) return rc;
+    GIGL_REQUIRE(ctx, dv && (!edge->w_edge_msg || dze), "the edge backward needs dv (and dze with edge messages)");
+    if (heads == 4 && d > 768)
+      return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "gigl_gat_input_aggregate_backward_edge: four heads over rows wider than 768 "
+                       "floats (d=%d) are not built with edge features", d);
+    ed.eid = edge->eid;
+    ed.table = edge->table;
+    ed.v = edge->att_edge_folded;
+    ed.De = edge->edge_dim;
+    ed.dze = edge->w_edge_msg ? dze : nullptr;
+    ed.dv = dv;
+  }
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (rows_cap == 0) return GIGL_OK;
   gigl_prof_scope ps(ctx, GIGL_K_GATHER_BWD);
@@ -4732,8 +5117,8 @@ int32_t gigl_gat_input_aggregate_backward(gigl_ctx* ctx, const void* src, int32_
   int64_t blocks = (rows_cap + 3) / 4;
   if (blocks > 256 * 2) blocks = 256 * 2;  // (two workgroups per CU fill its registers; fewer workgroups = fewer final atomics)
 #define GIGL_GAT_BW(TT, PP, HH)                                                                                        \
-  hipLaunchKernelGGL((gat_input_backward_onepass_kernel<TT, PP, HH>), dim3((unsigned)blocks), dim3(256), 0, st,        \
-                     (const TT*)src, d, gather_ids, u, rowptr, rowend, col, n_rows_dev, slope, dz, head_stride, du)
+  launch_gat_input_backward<TT, PP, HH>(edge != nullptr, (unsigned)blocks, st, (const TT*)src, d, gather_ids, u, rowptr, \
+                                        rowend, col, n_rows_dev, slope, dz, head_stride, du, ed)
 #define GIGL_GAT_BW_P(TT, HH)                                                                                          \
   do {                                                                                                                  \
     if (P == 1) GIGL_GAT_BW(TT, 1, HH);                                                                                \
@@ -4754,6 +5139,23 @@ int32_t gigl_gat_input_aggregate_backward(gigl_ctx* ctx, const void* src, int32_
 #undef GIGL_GAT_BW
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
+}
+
+int32_t gigl_gat_input_aggregate(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d, const uint32_t* gather_ids,
+                                 const float* u, int32_t heads, float negative_slope, const int32_t* rowptr,
+                                 const int32_t* rowend, const int32_t* col, const int32_t* n_rows_dev, int64_t rows_cap,
+                                 float* z) {
+  return gigl_gat_input_aggregate_edge(ctx, src, src_dtype, d, gather_ids, u, heads, negative_slope, rowptr, rowend, col,
+                                       n_rows_dev, rows_cap, z, nullptr);
+}
+
+int32_t gigl_gat_input_aggregate_backward(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d,
+                                          const uint32_t* gather_ids, const float* u, int32_t heads, float negative_slope,
+                                          const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
+                                          const int32_t* n_rows_dev, int64_t rows_cap, const float* dz,
+                                          float* /* edge_scratch: unused */, float* du) {
+  return gigl_gat_input_aggregate_backward_edge(ctx, src, src_dtype, d, gather_ids, u, heads, negative_slope, rowptr, rowend,
+                                                col, n_rows_dev, rows_cap, dz, du, nullptr, nullptr, nullptr);
 }
 
 int32_t gigl_gat_input_layer_fused(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d,
@@ -4861,4 +5263,85 @@ int32_t gigl_gat_input_layer_fused_hs(gigl_ctx* ctx, const void* src, int32_t sr
   }
   return linear_tiled_strided(ctx, z, w, bias, n_rows_dev, rows_cap, d, C, act, out, H * C, H, head_stride, (int64_t)C * d,
                               nullptr, nullptr, 0, 0, hs_scale);
+}
+
+// ---- the training plan's edge-feature pieces around those (pipeline.hip, gigl_gat_nablp_train_plan_set_edge_features)
+
+// out[i][c] = act(out[i][c] + <w_msg[c], ze[i][c / C]> + bias[c]) for the rows i < *n_rows_dev (EdgeAttrGATConv's messages)
+int32_t gigl_gat_edge_msg_add(gigl_ctx* ctx, const float* ze, const float* w_msg, const float* bias, const int32_t* n_rows_dev,
+                              int64_t rows_cap, int32_t heads, int32_t channels, int32_t edge_dim, int32_t act, float* out) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  GIGL_REQUIRE(ctx, ze && w_msg && n_rows_dev && out && heads > 0 && channels > 0 && edge_dim > 0 && rows_cap >= 0, "bad argument");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (rows_cap == 0) return GIGL_OK;
+  gigl_prof_scope ps(ctx, GIGL_K_LINEAR);
+  int64_t blocks = (rows_cap * heads * channels + 255) / 256;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  hipLaunchKernelGGL(gat_edge_msg_epilogue_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ze, w_msg, bias, n_rows_dev,
+                     heads, channels, edge_dim, act, out);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+// the messages' backward: dze[i][h] = W_msg,h^T dy[h][i] (dze != NULL) and g_w_msg += sum_i dy_i (x) z_i (z != NULL); dy is
+// stored as `heads` planes of [rows][channels] floats, `plane` floats apart
+int32_t gigl_gat_edge_msg_backward(gigl_ctx* ctx, const float* dy, int64_t plane, const float* w_msg, const float* z,
+                                   const int32_t* n_rows_dev, int64_t rows_cap, int32_t heads, int32_t channels,
+                                   int32_t edge_dim, float* dze, float* g_w_msg) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  GIGL_REQUIRE(ctx, dy && n_rows_dev && heads > 0 && channels > 0 && edge_dim > 0 && rows_cap >= 0 && (!dze || w_msg) &&
+                        (!z || g_w_msg), "bad argument");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (rows_cap == 0) return GIGL_OK;
+  gigl_prof_scope ps(ctx, GIGL_K_GATHER_BWD);
+  if (dze) {
+    int64_t blocks = (rows_cap * heads * edge_dim + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(gat_edge_msg_dze_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, dy, plane, w_msg, n_rows_dev,
+                       heads, channels, edge_dim, dze);
+  }
+  if (z)
+    hipLaunchKernelGGL(gat_edge_msg_wgrad_kernel, dim3((unsigned)((rows_cap + GAT_MSG_ROWS - 1) / GAT_MSG_ROWS)), dim3(256), 0,
+                       ctx->stream, dy, plane, z, n_rows_dev, heads, channels, edge_dim, g_w_msg);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+// gigl_gat_aggregate_backward for one head over the resident edge table (gat_backward_indexed_kernel): dh / d_alpha_src /
+// d_alpha_dst as there (ADDED to), dv [edge_dim] += sum_e dpre_e e_e, z_out [rows_cap][edge_dim] = sum_e alpha_e e_e (NULL
+// without edge messages; dze = W_msg^T dout then too)
+int32_t gigl_gat_aggregate_backward_indexed(gigl_ctx* ctx, const float* h, const float* att_src, const float* att_dst,
+                                            int32_t channels, float negative_slope, const int32_t* rowptr,
+                                            const int32_t* rowend, const int32_t* col, const int32_t* n_nodes_dev,
+                                            int64_t nodes_cap, const int32_t* n_rows_dev, int64_t rows_cap, const float* out_pre,
+                                            const float* dout, const float* table, const int32_t* eid, int32_t edge_dim,
+                                            const float* att_edge_folded, const float* dze, float* alpha_scratch, float* dh,
+                                            float* d_alpha_src, float* d_alpha_dst, float* dv, float* z_out) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  GIGL_REQUIRE(ctx, h && att_src && att_dst && rowptr && rowend && col && n_nodes_dev && n_rows_dev && out_pre && dout && table &&
+                        eid && att_edge_folded && alpha_scratch && dh && d_alpha_src && d_alpha_dst && dv, "null argument");
+  GIGL_REQUIRE(ctx, (dze == nullptr) == (z_out == nullptr), "dze and z_out go together");
+  GIGL_REQUIRE(ctx, channels > 0 && rows_cap >= 0 && nodes_cap >= rows_cap, "bad sizes");
+  if ((channels & 3) || channels > 512 || edge_dim < 1 || edge_dim > GAT_INPUT_MAX_EDGE_DIM ||
+      (((uintptr_t)h | (uintptr_t)dout | (uintptr_t)out_pre | (uintptr_t)dh) & 15))
+    return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "indexed GAT backward: channels %d (%% 4 == 0, <= 512), edge_dim %d (1..%d), "
+                     "16-byte aligned matrices", channels, edge_dim, GAT_INPUT_MAX_EDGE_DIM);
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (rows_cap == 0) return GIGL_OK;
+  gigl_prof_scope ps(ctx, GIGL_K_GATHER_BWD);
+  float* a_src = alpha_scratch;
+  float* a_dst = alpha_scratch + nodes_cap;
+  hipLaunchKernelGGL(gat_alpha_kernel, dim3((unsigned)((nodes_cap + 255) / 256)), dim3(256), 0, ctx->stream, h, att_src, att_dst,
+                     n_nodes_dev, 1, channels, a_src, a_dst);
+  int64_t blocks = (rows_cap + 3) / 4;
+  if (blocks > 256 * 8) blocks = 256 * 8;
+#define GAT_BWD_IX(VV)                                                                                                       \
+  hipLaunchKernelGGL((gat_backward_indexed_kernel<VV>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, h, a_src, a_dst,   \
+                     rowptr, rowend, col, n_rows_dev, channels, negative_slope, out_pre, dout, eid, table, edge_dim,         \
+                     att_edge_folded, dze, dh, d_alpha_src, d_alpha_dst, dv, z_out)
+  if (channels <= 256) GAT_BWD_IX(1);
+  else GAT_BWD_IX(2);
+#undef GAT_BWD_IX
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
 }

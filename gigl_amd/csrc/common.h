@@ -211,6 +211,31 @@ int32_t gigl_gat_aggregate_edge_indexed(gigl_ctx* ctx, const float* h, const flo
                                         const int32_t* eid, int32_t edge_dim, int64_t cap_edges,
                                         const float* att_edge_folded, const float* w_edge_msg, float* alpha_scratch,
                                         float* out);
+// The training plan's edge-feature pieces (agg.hip; gigl_gat_nablp_train_plan_set_edge_features).  gigl_gat_input_aggregate /
+// _backward with the first layer's edge terms (edge == NULL: exactly those): the forward also writes edge->ze when
+// edge->w_edge_msg is set; the backward takes dze [rows][heads][edge_dim] = W_msg^T dy then and ADDS d v = sum_e dpre_e e_e
+// (the self loop through its mean attribute) to dv [heads][edge_dim] in the same single sweep
+int32_t gigl_gat_input_aggregate_edge(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d, const uint32_t* gather_ids,
+                                      const float* u, int32_t heads, float negative_slope, const int32_t* rowptr,
+                                      const int32_t* rowend, const int32_t* col, const int32_t* n_rows_dev, int64_t rows_cap,
+                                      float* z, const gigl_gat_edge_terms* edge);
+int32_t gigl_gat_input_aggregate_backward_edge(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d,
+                                               const uint32_t* gather_ids, const float* u, int32_t heads, float negative_slope,
+                                               const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
+                                               const int32_t* n_rows_dev, int64_t rows_cap, const float* dz, float* du,
+                                               const gigl_gat_edge_terms* edge, const float* dze, float* dv);
+int32_t gigl_gat_edge_msg_add(gigl_ctx* ctx, const float* ze, const float* w_msg, const float* bias, const int32_t* n_rows_dev,
+                              int64_t rows_cap, int32_t heads, int32_t channels, int32_t edge_dim, int32_t act, float* out);
+int32_t gigl_gat_edge_msg_backward(gigl_ctx* ctx, const float* dy, int64_t plane, const float* w_msg, const float* z,
+                                   const int32_t* n_rows_dev, int64_t rows_cap, int32_t heads, int32_t channels,
+                                   int32_t edge_dim, float* dze, float* g_w_msg);
+int32_t gigl_gat_aggregate_backward_indexed(gigl_ctx* ctx, const float* h, const float* att_src, const float* att_dst,
+                                            int32_t channels, float negative_slope, const int32_t* rowptr,
+                                            const int32_t* rowend, const int32_t* col, const int32_t* n_nodes_dev,
+                                            int64_t nodes_cap, const int32_t* n_rows_dev, int64_t rows_cap, const float* out_pre,
+                                            const float* dout, const float* table, const int32_t* eid, int32_t edge_dim,
+                                            const float* att_edge_folded, const float* dze, float* alpha_scratch, float* dh,
+                                            float* d_alpha_src, float* d_alpha_dst, float* dv, float* z_out);
 // The fused two-layer projection (agg.hip, linear_fused2x_kernel): layer 0's [mean | self] projection (half split, two-source
 // tiled operand) with the LAST layer's [W_l | W_r] applied to the hidden rows before they leave the workgroup — y2 =
 // [rows][gigl_fused2_row_floats()] of p = [W_l h | W_r h]; gigl_sage_fused_out is the last layer over those rows (one

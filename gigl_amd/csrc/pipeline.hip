@@ -642,7 +642,8 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
 // source is a plain vector g, or the weight-gradient kernel's per-chunk PARTIAL sums (part != NULL: [chunks][n] floats, the
 // chunks below ceil(*rows / rc) hold real rows) added up here in chunk order — one reduce launch less per layer; source 0
 // may hold both (the GAT plan: the folded attention vectors' share of W0's gradient beside the projections' partial sums)
-constexpr int ADAM_MAX = 16;  // tensors (or slices of tensors: the GAT plan's heads) per launch
+constexpr int ADAM_MAX = 24;  // tensors (or slices of tensors: the GAT plan's heads, up to 2 * 4 + 6, and its six edge
+                               // tensors) per launch — 88 bytes each: the pack stays near 2 KB of kernel arguments
 struct AdamPack {
   float* p[ADAM_MAX];
   float* m[ADAM_MAX];
@@ -1897,7 +1898,29 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
             *du = nullptr;
       float* g[8] = {nullptr};
     } x;
+    // edge features (gigl_gat_nablp_train_plan_set_edge_features): the resident table is read in place through the base
+    // plans' eid (written by the graph part); tensor slot 3 l + {0: lin_edge.weight, 1: att_edge, 2: lin_edge_message.weight}
+    struct Edge {
+      gigl_feat* table = nullptr;
+      int32_t De = 0;
+      float *w_edge[2] = {nullptr, nullptr}, *att_edge[2] = {nullptr, nullptr};  // borrowed, UPDATED IN PLACE
+      float* w_msg[2] = {nullptr, nullptr};  // NULL (GATConv), == w_edge[l] (shared: one tensor, one update) or its own buffer
+      float* v = nullptr;                    // folded att_edge, per step: [H][De] of layer 0, then [De] of layer 1
+      float* ge[6] = {nullptr};              // gradients (a shared message weight's join lin_edge.weight's)
+      float* mom[12] = {nullptr};
+      int64_t n[6] = {0};
+      float* dv = nullptr;                   // d v, laid out as v
+      void* zero_base = nullptr;             // ge | dv (| the forked encode's): cleared at the start of every step
+      size_t zero_bytes = 0;
+      float* ze[2] = {nullptr, nullptr};     // forward state per encode: sum_e alpha_e e of layer 0 [rows1][H][De]
+      float *dze = nullptr, *z1 = nullptr;   // backward scratch: W_msg^T dy [rows1][H][De], layer 1's sum_e alpha_e e [b][De]
+      struct Alt {
+        float* ge[6] = {nullptr};
+        float *dv = nullptr, *dze = nullptr, *z1 = nullptr;
+      } x;
+    } e;
   } gat;
+  bool stepped = false;  // a step has run: the plan's shape is final
   std::vector<void*> owned;
   // Two workspaces of trees + union graphs (as gigl_sage_train_plan): the graph part of the NEXT step's roots (sample +
   // union of both root sets: latency-bound launches) runs on a side stream beside this step's layers
@@ -2524,6 +2547,7 @@ int32_t gigl_nablp_train_plan_step2(gigl_nablp_train_plan* t, const uint32_t* ma
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "the training plan needs duplicate-free trees (no with-replacement mode)");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   t->gat.parts_pending = t->kind == 1;  // (this step's gradient buffers will lack the partial sums)
+  t->stepped = true;
   hipStream_t st = ctx->stream;
   if (t->lctx->stream != st || t->lctx->own_stream) {
     const int32_t rs = gigl_ctx_set_stream(t->lctx, st);
@@ -2600,10 +2624,12 @@ int32_t gigl_nablp_train_plan_moments(gigl_nablp_train_plan* t, int32_t index, f
     GIGL_REQUIRE(ctx, index >= 0 && index < 2 * t->L, "tensor %d", index);
     return sage_moments_copy(ctx, *t, index, m, v);
   }
-  GIGL_REQUIRE(ctx, index >= 0 && index < 8, "tensor %d", index);
-  const size_t n = (size_t)t->gat.n[index];
-  if (m && n) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(m, t->gat.mom[2 * index], n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  if (v && n) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(v, t->gat.mom[2 * index + 1], n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  GIGL_REQUIRE(ctx, index >= 0 && index < (t->gat.e.table ? 14 : 8), "tensor %d", index);
+  // (8 + 3 l + j: the edge tensors of gigl_gat_nablp_train_plan_set_edge_features)
+  const size_t n = (size_t)(index < 8 ? t->gat.n[index] : t->gat.e.n[index - 8]);
+  float* const* mom = index < 8 ? t->gat.mom + 2 * index : t->gat.e.mom + 2 * (index - 8);
+  if (m && n) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(m, mom[0], n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  if (v && n) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(v, mom[1], n * 4, hipMemcpyDeviceToDevice, ctx->stream));
   return GIGL_OK;
 }
 
@@ -2631,6 +2657,14 @@ int32_t gigl_nablp_train_plan_adopt(gigl_nablp_train_plan* dst, gigl_nablp_train
       for (int j = 0; j < 2; ++j)
         GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->gat.mom[2 * i + j], src->gat.mom[2 * i + j],
                                            (size_t)(dst->gat.n[i] ? dst->gat.n[i] : 1) * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    GIGL_REQUIRE(ctx, (dst->gat.e.table != nullptr) == (src->gat.e.table != nullptr), "plans with / without edge features");
+    for (int i = 0; i < 6 && dst->gat.e.table; ++i) {
+      GIGL_REQUIRE(ctx, dst->gat.e.n[i] == src->gat.e.n[i], "plans of different edge widths");
+      for (int j = 0; j < 2; ++j)
+        GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->gat.e.mom[2 * i + j], src->gat.e.mom[2 * i + j],
+                                           (size_t)(dst->gat.e.n[i] ? dst->gat.e.n[i] : 1) * 4, hipMemcpyDeviceToDevice,
+                                           ctx->stream));
     }
   } else {
     const int32_t rc = sage_moments_adopt(ctx, *dst, *src);
@@ -2757,7 +2791,50 @@ __global__ __launch_bounds__(256) void gat_bias_grad_kernel(const float* __restr
   }
 }
 
+// the edge terms' fold, v[h][k] = sum_c att_edge[hC + c] W_e[hC + c][k] (<lin_edge(e), att_edge_h> = <e, v_h>): one thread
+// per (h, k)
+__global__ __launch_bounds__(256) void gat_edge_fold_kernel(const float* __restrict__ w_e, const float* __restrict__ att_e, int H,
+                                                            int C, int De, float* __restrict__ v) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= H * De) return;
+  const int h = t / De, k = t - h * De;
+  float acc = 0.f;
+  for (int c = 0; c < C; ++c) acc += att_e[h * C + c] * w_e[(int64_t)(h * C + c) * De + k];
+  v[t] = acc;
+}
+// its backward, one wave per weight row r = hC + c, lane k < De (De <= 64):
+//   g_w[r][k] += att_edge[r] dv[h][k];  g_att[r] += <W_e[r], dv[h]>
+__global__ __launch_bounds__(256) void gat_edge_fold_backward_kernel(const float* __restrict__ w_e, const float* __restrict__ att_e,
+                                                                     const float* __restrict__ dv, int H, int C, int De,
+                                                                     float* __restrict__ g_w, float* __restrict__ g_att) {
+  const int lane = threadIdx.x & 63;
+  const int r = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  if (r >= H * C) return;
+  const int h = r / C;
+  float p = 0.f;
+  if (lane < De) {
+    const float dvk = dv[h * De + lane];
+    g_w[(int64_t)r * De + lane] += att_e[r] * dvk;
+    p = w_e[(int64_t)r * De + lane] * dvk;
+  }
+  for (int o = 32; o >= 1; o >>= 1) p += __shfl_xor(p, o, 64);
+  if (lane == 0) g_att[r] += p;
+}
+
 int64_t gat_rows1(const gigl_nablp_train_plan* t, int which) { return t->enc[which].rows_cap[0]; }
+
+// the first layer's edge terms over encode `which`'s batch graph (the base plan's eid: its graph part wrote them)
+gigl_gat_edge_terms gat_edge_terms0(const gigl_nablp_train_plan* t, int which) {
+  const auto& ge = t->gat.e;
+  gigl_gat_edge_terms et{};
+  et.eid = t->enc[which].base->eid;
+  et.table = (const float*)ge.table->rows;
+  et.edge_dim = ge.De;
+  et.att_edge_folded = ge.v;
+  et.w_edge_msg = ge.w_msg[0];
+  et.ze = ge.ze[which];
+  return et;
+}
 
 // once per step: the folded attention vectors of the first layer (both encodes read them)
 int32_t gat_lp_begin(gigl_nablp_train_plan* t) {
@@ -2773,6 +2850,14 @@ int32_t gat_lp_begin(gigl_nablp_train_plan* t) {
   for (int h = 0; h < g.heads; ++h)
     hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(((int64_t)g.c0 * g.d_in + 255) / 256)), dim3(256), 0, st,
                        (const float*)(g.w[0] + (int64_t)h * g.c0 * g.d_in), g.c0, g.d_in, g.wt0[h]);
+  if (g.e.table) {  // both layers' folded att_edge (the parameters change every step), the edge gradients' clean slate
+    const int De = g.e.De;
+    gigl_fill_u32(st, g.e.zero_base, 0u, (int64_t)(g.e.zero_bytes / 4));
+    hipLaunchKernelGGL(gat_edge_fold_kernel, dim3((unsigned)((g.heads * De + 255) / 256)), dim3(256), 0, st,
+                       (const float*)g.e.w_edge[0], (const float*)g.e.att_edge[0], g.heads, g.c0, De, g.e.v);
+    hipLaunchKernelGGL(gat_edge_fold_kernel, dim3(1), dim3(256), 0, st, (const float*)g.e.w_edge[1],
+                       (const float*)g.e.att_edge[1], 1, g.c1, De, g.e.v + g.heads * De);
+  }
   GIGL_HIP_CHECK(t->lctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -2789,16 +2874,27 @@ int32_t gat_lp_forward(gigl_nablp_train_plan* t, int which) {
   const int64_t rows1 = gat_rows1(t, which);
   const int32_t* n0 = p->un.meta + GIGL_META_LEVEL0;
   const int32_t* n1 = p->un.meta + GIGL_META_LEVEL0 + 1;
-  int32_t rc = gigl_gat_input_aggregate(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
-                                        p->un.rowend, p->un.col, n1, rows1, g.z[which]);
+  const bool edge = g.e.table != nullptr, msg0 = edge && g.e.w_msg[0];
+  const gigl_gat_edge_terms et = edge ? gat_edge_terms0(t, which) : gigl_gat_edge_terms{};
+  int32_t rc = gigl_gat_input_aggregate_edge(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
+                                             p->un.rowend, p->un.col, n1, rows1, g.z[which], edge ? &et : nullptr);
   if (rc != GIGL_OK) return rc;
-  // h0[:, hC:(h+1)C] = relu(z_h W_h^T + b_h): one launch for all heads
-  rc = gigl_linear_batched(ctx, g.z[which], g.w[0], g.bias[0], n1, rows1, d, C0, 1, H, rows1 * d, (int64_t)C0 * d, H * C0, e.h[0]);
+  // h0[:, hC:(h+1)C] = relu(z_h W_h^T (+ W_msg,h ze_h) + b_h): one launch for all heads (the messages' De-wide term, the
+  // bias and the relu in one more)
+  rc = gigl_linear_batched(ctx, g.z[which], g.w[0], msg0 ? nullptr : g.bias[0], n1, rows1, d, C0, msg0 ? 0 : 1, H, rows1 * d,
+                           (int64_t)C0 * d, H * C0, e.h[0]);
+  if (rc == GIGL_OK && msg0) rc = gigl_gat_edge_msg_add(ctx, g.e.ze[which], g.e.w_msg[0], g.bias[0], n1, rows1, H, C0, g.e.De, 1, e.h[0]);
   if (rc != GIGL_OK) return rc;
   rc = gigl_linear(ctx, e.h[0], g.w[1], nullptr, n1, rows1, H * C0, C1, 0, g.xw[which]);
   if (rc != GIGL_OK) return rc;
-  rc = gigl_gat_aggregate(ctx, g.xw[which], g.att_src[1], g.att_dst[1], 1, C1, g.slope, 1, p->un.rowptr, p->un.rowend,
-                          p->un.col, n1, rows1, n0, e.rows_cap[1], nullptr, 0, alpha, g.out_pre[which]);
+  if (edge)
+    rc = gigl_gat_aggregate_edge_indexed(ctx, g.xw[which], g.att_src[1], g.att_dst[1], 1, C1, g.slope, 1, p->un.rowptr,
+                                         p->un.rowend, p->un.col, n1, rows1, n0, e.rows_cap[1], nullptr, 0,
+                                         (const float*)g.e.table->rows, p->eid, g.e.De, p->un.cap_edges, g.e.v + H * g.e.De,
+                                         g.e.w_msg[1], alpha, g.out_pre[which]);
+  else
+    rc = gigl_gat_aggregate(ctx, g.xw[which], g.att_src[1], g.att_dst[1], 1, C1, g.slope, 1, p->un.rowptr, p->un.rowend,
+                            p->un.col, n1, rows1, n0, e.rows_cap[1], nullptr, 0, alpha, g.out_pre[which]);
   if (rc != GIGL_OK) return rc;
   {
     int64_t blocks = (e.rows_cap[1] * C1 + 255) / 256;
@@ -2835,10 +2931,32 @@ int32_t gat_lp_backward(gigl_nablp_train_plan* t, int which) {
                        n0, C1, gb1);
   gigl_fill_u32(st, s_dxw, 0u, rows1 * C1);
   gigl_fill_u32(st, s_ds, 0u, s_dd - s_ds + rows1);  // (ds | dd: dd starts where the larger encode's ds ends)
-  int32_t rc = gigl_gat_aggregate_backward(ctx, g.xw[which], g.att_src[1], g.att_dst[1], 1, C1, g.slope, p->un.rowptr,
-                                           p->un.rowend, p->un.col, n1, rows1, n0, e.rows_cap[1], g.out_pre[which], e.dh[1],
-                                           nullptr, 0, p->un.cap_edges, nullptr, s_alpha, s_dxw, s_ds, s_dd, nullptr, nullptr,
-                                           nullptr);
+  // (edge features: both layers' d v on this stream's buffer, the message weights' gradients on this stream's slots — a
+  // shared weight's on lin_edge.weight's)
+  const bool edge = g.e.table != nullptr;
+  const int De = g.e.De;
+  float* const* ge = alt ? g.e.x.ge : g.e.ge;
+  float *s_dv = alt ? g.e.x.dv : g.e.dv, *s_dze = alt ? g.e.x.dze : g.e.dze, *s_z1 = alt ? g.e.x.z1 : g.e.z1;
+  auto msg_slot = [&](int l) { return ge[g.e.w_msg[l] == g.e.w_edge[l] ? 3 * l : 3 * l + 2]; };
+  int32_t rc = GIGL_OK;
+  if (edge) {
+    const bool msg1 = g.e.w_msg[1] != nullptr;
+    if (msg1)  // dze_i = W_msg^T dout_i
+      rc = gigl_gat_edge_msg_backward(ctx, e.dh[1], 0, g.e.w_msg[1], nullptr, n0, e.rows_cap[1], 1, C1, De, s_dze, nullptr);
+    if (rc == GIGL_OK)
+      rc = gigl_gat_aggregate_backward_indexed(ctx, g.xw[which], g.att_src[1], g.att_dst[1], C1, g.slope, p->un.rowptr,
+                                               p->un.rowend, p->un.col, n1, rows1, n0, e.rows_cap[1], g.out_pre[which], e.dh[1],
+                                               (const float*)g.e.table->rows, p->eid, De, g.e.v + H * De,
+                                               msg1 ? s_dze : nullptr, s_alpha, s_dxw, s_ds, s_dd, s_dv + H * De,
+                                               msg1 ? s_z1 : nullptr);
+    if (rc == GIGL_OK && msg1)  // d W_msg += sum_i dout_i (x) z1_i
+      rc = gigl_gat_edge_msg_backward(ctx, e.dh[1], 0, nullptr, s_z1, n0, e.rows_cap[1], 1, C1, De, nullptr, msg_slot(1));
+  } else {
+    rc = gigl_gat_aggregate_backward(ctx, g.xw[which], g.att_src[1], g.att_dst[1], 1, C1, g.slope, p->un.rowptr,
+                                     p->un.rowend, p->un.col, n1, rows1, n0, e.rows_cap[1], g.out_pre[which], e.dh[1],
+                                     nullptr, 0, p->un.cap_edges, nullptr, s_alpha, s_dxw, s_ds, s_dd, nullptr, nullptr,
+                                     nullptr);
+  }
   if (rc != GIGL_OK) return rc;
   rc = gigl_gat_backward_epilogue(ctx, s_dxw, s_ds, s_dd, g.xw[which], g.att_src[1], g.att_dst[1], n1, rows1, 1, C1, gas1, gad1);
   if (rc != GIGL_OK) return rc;
@@ -2863,8 +2981,19 @@ int32_t gat_lp_backward(gigl_nablp_train_plan* t, int which) {
     rc = gigl_linear(ctx, dyh, g.wt0[h], nullptr, n1, rows1, C0, d, 0, s_dz + (int64_t)h * rows1 * d);
     if (rc != GIGL_OK) return rc;
   }
-  rc = gigl_gat_input_aggregate_backward(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
-                                         p->un.rowend, p->un.col, n1, rows1, s_dz, nullptr, s_du);
+  if (edge) {
+    const bool msg0 = g.e.w_msg[0] != nullptr;
+    const gigl_gat_edge_terms et = gat_edge_terms0(t, which);
+    if (msg0) {  // dze_i,h = W_msg,h^T dy_i,h and d W_msg += sum_i dy_i (x) ze_i, from the heads' masked slices
+      rc = gigl_gat_edge_msg_backward(ctx, s_dh0s, rows1 * C0, g.e.w_msg[0], g.e.ze[which], n1, rows1, H, C0, De, s_dze, msg_slot(0));
+      if (rc != GIGL_OK) return rc;
+    }
+    rc = gigl_gat_input_aggregate_backward_edge(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
+                                                p->un.rowend, p->un.col, n1, rows1, s_dz, s_du, &et, msg0 ? s_dze : nullptr, s_dv);
+  } else {
+    rc = gigl_gat_input_aggregate_backward(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
+                                           p->un.rowend, p->un.col, n1, rows1, s_dz, nullptr, s_du);
+  }
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return rc;
 }
@@ -2879,6 +3008,16 @@ int32_t gat_lp_finish(gigl_nablp_train_plan* t) {
   hipLaunchKernelGGL(gat_fold_backward_kernel, dim3((unsigned)(g.heads * g.c0)), dim3(256), 0, st, (const float*)g.w[0],
                      (const float*)g.att_src[0], (const float*)g.att_dst[0], (const float*)g.du, g.heads, g.c0, g.d_in, g.g[0],
                      g.g[1], g.g[2]);
+  if (g.e.table) {  // d v of both layers -> lin_edge.weight and att_edge (v = W_e^T att_edge per head)
+    const int De = g.e.De;
+    if (t->fork) hipLaunchKernelGGL(lp_acc_kernel, dim3(1), dim3(256), 0, st, g.e.dv, (const float*)g.e.x.dv, (int64_t)(g.heads + 1) * De);
+    hipLaunchKernelGGL(gat_edge_fold_backward_kernel, dim3((unsigned)((g.heads * g.c0 + 3) / 4)), dim3(256), 0, st,
+                       (const float*)g.e.w_edge[0], (const float*)g.e.att_edge[0], (const float*)g.e.dv, g.heads, g.c0, De,
+                       g.e.ge[0], g.e.ge[1]);
+    hipLaunchKernelGGL(gat_edge_fold_backward_kernel, dim3((unsigned)((g.c1 + 3) / 4)), dim3(256), 0, st,
+                       (const float*)g.e.w_edge[1], (const float*)g.e.att_edge[1], (const float*)(g.e.dv + g.heads * De), 1, g.c1,
+                       De, g.e.ge[3], g.e.ge[4]);
+  }
   AdamPack ap{};
   ap.n_src = 2;
   float* params[8] = {g.w[0], g.att_src[0], g.att_dst[0], g.bias[0], g.w[1], g.att_src[1], g.att_dst[1], g.bias[1]};
@@ -2912,6 +3051,15 @@ int32_t gat_lp_finish(gigl_nablp_train_plan* t) {
     } else {  // (fork: the second layer's attention vectors and bias were accumulated per encode)
       add(params[i], g.g[i], g.mom[2 * i], g.mom[2 * i + 1], g.n[i], nullptr, nullptr, 0, 0,
           t->fork && i >= 5 ? g.x.g[i] : nullptr);
+    }
+  }
+  for (int l = 0; l < 2 && g.e.table; ++l) {  // the edge tensors (a shared message weight IS lin_edge.weight: one entry)
+    float* eprm[3] = {g.e.w_edge[l], g.e.att_edge[l], g.e.w_msg[l]};
+    for (int j = 0; j < 3; ++j) {
+      const int k = 3 * l + j;
+      if (!g.e.n[k]) continue;
+      add(eprm[j], g.e.ge[k], g.e.mom[2 * k], g.e.mom[2 * k + 1], g.e.n[k], nullptr, nullptr, 0, 0,
+          t->fork && j != 1 ? g.e.x.ge[k] : nullptr);
     }
   }
   ap.lr = t->lr;
@@ -3117,6 +3265,119 @@ int32_t gigl_gat_nablp_train_plan_grads(gigl_nablp_train_plan* t, int32_t layer,
     if (t->fork && j >= 5)  // (the second encode's share, accumulated on its own stream)
       hipLaunchKernelGGL(lp_acc_kernel, dim3(4), dim3(256), 0, ctx->stream, dst[i], (const float*)t->gat.x.g[j], t->gat.n[j]);
   }
+  return GIGL_OK;
+}
+
+int32_t gigl_gat_nablp_train_plan_set_edge_features(gigl_nablp_train_plan* t, gigl_feat* edge_table, float* const* w_edge,
+                                                    float* const* att_edge, float* const* w_edge_msg) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  gigl_ctx* ctx = t->ctx;
+  GIGL_REQUIRE(ctx, t->kind == 1, "edge features apply to the GAT link-prediction plan (gigl_gat_nablp_train_plan_create)");
+  GIGL_REQUIRE(ctx, !t->stepped && !t->gat.e.table, "edge features are set once, after create and before the first step");
+  GIGL_REQUIRE(ctx, edge_table && w_edge && att_edge, "null argument");
+  const gigl_graph* graph = t->work[0].base[0]->graph;
+  const int32_t De = edge_table->d;
+  if (edge_table->dtype != GIGL_DTYPE_F32 || De < 1 || De > 64)  // (a lane per component of an edge row)
+    return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "GAT link-prediction plan: the edge table must be fp32, 1..64 wide (dtype %d, %d)",
+                     edge_table->dtype, De);
+  if (t->gat.heads == 4 && t->gat.d_in > 768)  // (the one shape whose edge backward would spill: not built, agg.hip)
+    return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "GAT link-prediction plan: edge features with four heads need rows of at most 768 "
+                     "floats (%d)", t->gat.d_in);
+  GIGL_REQUIRE(ctx, edge_table->n == graph->e, "the edge table holds one row per resident edge (%lld rows, %lld edges)",
+               (long long)edge_table->n, (long long)graph->e);
+  for (int l = 0; l < 2; ++l) GIGL_REQUIRE(ctx, w_edge[l] && att_edge[l], "layer %d: null edge parameter", l);
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  auto& g = t->gat;
+  auto& ge = g.e;
+  const int H = g.heads;
+  const int64_t hc[2] = {(int64_t)H * g.c0, g.c1};
+  ge.De = De;
+  for (int l = 0; l < 2; ++l) {
+    ge.w_edge[l] = w_edge[l];
+    ge.att_edge[l] = att_edge[l];
+    ge.w_msg[l] = w_edge_msg ? w_edge_msg[l] : nullptr;
+    ge.n[3 * l] = hc[l] * De;
+    ge.n[3 * l + 1] = hc[l];
+    ge.n[3 * l + 2] = ge.w_msg[l] && ge.w_msg[l] != ge.w_edge[l] ? hc[l] * De : 0;
+  }
+  auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
+  const bool fork = t->fork, any_msg = ge.w_msg[0] || ge.w_msg[1];
+  const size_t nv = (size_t)(H + 1) * De;
+  size_t set_floats = nv;  // ge | dv
+  for (int i = 0; i < 6; ++i) set_floats += (size_t)ge.n[i];
+  float* z = (float*)alloc(set_floats * (fork ? 2 : 1) * 4);
+  ge.v = (float*)alloc(nv * 4);
+  bool ok = z && ge.v;
+  ge.zero_base = z;
+  ge.zero_bytes = set_floats * (fork ? 2 : 1) * 4;
+  for (int side = 0; side < (fork ? 2 : 1) && ok; ++side) {
+    float** slots = side ? ge.x.ge : ge.ge;
+    for (int i = 0; i < 6; ++i) {
+      slots[i] = z;
+      z += ge.n[i];
+    }
+    (side ? ge.x.dv : ge.dv) = z;
+    z += nv;
+  }
+  for (int i = 0; i < 6 && ok; ++i)
+    for (int j = 0; j < 2; ++j) {
+      const size_t bytes = (size_t)(ge.n[i] ? ge.n[i] : 1) * 4;
+      ge.mom[2 * i + j] = (float*)alloc(bytes);
+      if (!ge.mom[2 * i + j] || hipMemset(ge.mom[2 * i + j], 0, bytes) != hipSuccess) ok = false;
+    }
+  if (any_msg && ok) {
+    int64_t rows1_max = 0, b_max = 0;
+    for (int k = 0; k < 2; ++k) {
+      rows1_max = t->enc[k].rows_cap[0] > rows1_max ? t->enc[k].rows_cap[0] : rows1_max;
+      b_max = t->enc[k].b > b_max ? t->enc[k].b : b_max;
+      ge.ze[k] = (float*)alloc((size_t)t->enc[k].rows_cap[0] * H * De * 4);
+      ok = ok && ge.ze[k];
+    }
+    ge.dze = (float*)alloc((size_t)rows1_max * H * De * 4);
+    ge.z1 = (float*)alloc((size_t)b_max * De * 4);
+    ok = ok && ge.dze && ge.z1;
+    if (fork) {  // the second encode's own scratch, as its Alt buffers
+      ge.x.dze = (float*)alloc((size_t)t->enc[1].rows_cap[0] * H * De * 4);
+      ge.x.z1 = (float*)alloc((size_t)t->enc[1].b * De * 4);
+      ok = ok && ge.x.dze && ge.x.z1;
+    }
+  }
+  // every workspace's batch graphs get their edge ids from their own graph part (plan_edge_ids_kernel; all rows are numbered)
+  for (auto& wk : t->work)
+    for (gigl_sage_plan* bp : wk.base) {
+      if (!ok) break;
+      const int64_t positions = bp->un.cap_edges + (bp->alias_rows ? bp->last_slots : 0);
+      void* q = nullptr;
+      if (hipMalloc(&q, (size_t)(positions > 0 ? positions : 4) * 4) != hipSuccess) {
+        ok = false;
+        break;
+      }
+      bp->owned.push_back(q);
+      if (hipMemset(q, 0xFF, (size_t)(positions > 0 ? positions : 4) * 4) != hipSuccess) ok = false;
+      bp->eid = (int32_t*)q;
+      bp->efeat = edge_table;
+    }
+  if (!ok) return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the GAT link-prediction plan's edge workspace failed");
+  ge.table = edge_table;
+  return GIGL_OK;
+}
+
+int32_t gigl_gat_nablp_train_plan_edge_grads(gigl_nablp_train_plan* t, int32_t layer, float* g_w_edge, float* g_att_edge,
+                                             float* g_w_edge_msg) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  gigl_ctx* ctx = t->ctx;
+  GIGL_REQUIRE(ctx, t->kind == 1 && t->gat.e.table && layer >= 0 && layer < 2, "bad plan / layer");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const auto& ge = t->gat.e;
+  float* dst[3] = {g_w_edge, g_att_edge, g_w_edge_msg};
+  for (int j = 0; j < 3; ++j) {
+    const int k = 3 * layer + j;
+    if (!dst[j] || !ge.n[k]) continue;
+    GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst[j], ge.ge[k], (size_t)ge.n[k] * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    if (t->fork && j != 1)  // (the second encode's share of the message weights' gradients, accumulated on its own stream)
+      hipLaunchKernelGGL(lp_acc_kernel, dim3(16), dim3(256), 0, ctx->stream, dst[j], (const float*)ge.x.ge[k], ge.n[k]);
+  }
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
 

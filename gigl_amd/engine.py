@@ -1645,10 +1645,8 @@ class GatNablpTrainPlan(NablpTrainPlan):
                  temperature: float = 0.07, remove_accidental_hits: bool = True, lr: float = 5e-3,
                  weight_decay: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8):
         assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
-        if not self.applies(model, eng.feat_dim) or len(fanouts) != 2:
-            raise NotImplementedError("the GAT link-prediction plan runs two plain GATConv layers (concatenated heads, one "
-                                      "head in the second, no edge features) whose input rows are wider than the first "
-                                      "layer's output")
+        if not self._applies_to(eng, model) or len(fanouts) != 2:
+            raise NotImplementedError(self._COVERS)
         self.eng, self.b, self.P, self.n_rn = eng, int(b_anchors), int(num_positives), int(n_random_negatives)
         self.fanouts = [int(f) for f in fanouts]
         self._lib = eng._lib
@@ -1665,24 +1663,46 @@ class GatNablpTrainPlan(NablpTrainPlan):
                 (C.c_int32 * 2)(*self.heads), (C.c_int32 * 2)(*self.channels), arr(self.w), arr(self.att_src), arr(self.att_dst),
                 arr(self.bias), slope, norm, float(temperature), 1 if remove_accidental_hits else 0, float(lr), float(betas[0]),
                 float(betas[1]), float(eps), float(weight_decay), C.byref(h)), eng._ctx)
+            try:
+                self._after_create(h)
+            except Exception:
+                self._lib.gigl_nablp_train_plan_destroy(h)
+                raise
             return h
         self._create, self._adopt, self._destroy = create, self._lib.gigl_nablp_train_plan_adopt, self._lib.gigl_nablp_train_plan_destroy
         self.wide = False
         self._plan = create()
         self.loss = torch.zeros(2, dtype=torch.float32, device=eng.device)
 
+    _COVERS = ("the GAT link-prediction plan runs two plain GATConv layers (concatenated heads, one head in the second, no "
+               "edge features) whose input rows are wider than the first layer's output")
+
+    def _applies_to(self, eng, model) -> bool:
+        return self.applies(model, eng.feat_dim)
+
+    def _after_create(self, handle) -> None:
+        """what every (re)created plan handle needs before its first step (grow() re-creates: GatEdgeNablpTrainPlan)"""
+
     @staticmethod
-    def applies(model, feat_dim: int) -> bool:
-        from .models_attn import GAT, GATConv
-        if type(model) is not GAT or model.num_layers != 2 or model.edge_dim is not None or model.activation_after_last_conv:
+    def _node_side_applies(model, feat_dim: int) -> bool:
+        """what both GAT plans ask of the model apart from its edge features: models_attn.GAT, two layers of concatenated
+        heads then one head, built widths, input rows wider than the first layer's output (the input-side first layer)"""
+        from .models_attn import GAT
+        if type(model) is not GAT or model.num_layers != 2 or model.activation_after_last_conv:
             return False
         c0, c1 = model.conv_layers
-        if type(c0) is not GATConv or type(c1) is not GATConv or not c0.concat or c1.heads != 1:
+        if not c0.concat or c1.heads != 1:
             return False
         d = int(c0.in_channels)
         return (d == int(feat_dim) and d % 4 == 0 and d <= 1024 and c0.heads in (1, 2, 4) and d > c0.heads * c0.out_channels
                 and c0.heads * c0.out_channels <= 1024 and c0.out_channels % 4 == 0 and c1.out_channels % 4 == 0
                 and c1.out_channels <= 512 and c0.negative_slope == c1.negative_slope)
+
+    @staticmethod
+    def applies(model, feat_dim: int) -> bool:
+        from .models_attn import GATConv
+        return (GatNablpTrainPlan._node_side_applies(model, feat_dim) and model.edge_dim is None
+                and all(type(c) is GATConv for c in model.conv_layers))
 
     def load(self, model) -> None:
         dev = self.eng.device
@@ -1723,6 +1743,92 @@ class GatNablpTrainPlan(NablpTrainPlan):
                     continue
                 m, v = torch.empty_like(ts[l]), torch.empty_like(ts[l])
                 check(self._lib.gigl_nablp_train_plan_moments(self._plan, 4 * l + k, C.c_void_p(m.data_ptr()),
+                                                              C.c_void_p(v.data_ptr())), self.eng._ctx)
+                out[f"conv_layers.{l}.{name}"] = (m, v)
+        return out
+
+
+class GatEdgeNablpTrainPlan(GatNablpTrainPlan):
+    """GatNablpTrainPlan over a graph with edge features (gigl_gat_nablp_train_plan_set_edge_features): two GATConv(edge_dim)
+    layers — the attributes enter the logits — or two EdgeAttrGATConv layers, whose messages carry them too, with the shared
+    (`lin_edge.weight` used twice: one tensor, one update) or the separate `lin_edge_message.weight`.  The engine's resident
+    edge table (load_edge_features) is read in place; without one the constructor raises."""
+
+    _COVERS = ("the edge-featured GAT link-prediction plan runs two GATConv(edge_dim) or two EdgeAttrGATConv layers "
+               "(concatenated heads, one head in the second) over an fp32 edge table of edge_dim in [1, 64] columns, input rows "
+               "wider than the first layer's output (at most 768 floats under four heads)")
+
+    def _applies_to(self, eng, model) -> bool:
+        if getattr(model, "edge_dim", None) is not None and not getattr(eng, "_efeat_handle", None):
+            raise RuntimeError("a GAT training plan with edge features needs the engine's edge table (load_edge_features)")
+        return self.applies(model, eng.feat_dim, eng.edge_feat_dim)
+
+    @staticmethod
+    def applies(model, feat_dim: int, edge_feat_dim: int) -> bool:
+        from .models_attn import EdgeAttrGATConv, GATConv
+        if not GatNablpTrainPlan._node_side_applies(model, feat_dim) or model.edge_dim is None:
+            return False
+        kinds = {type(c) for c in model.conv_layers}
+        if kinds != {GATConv} and kinds != {EdgeAttrGATConv}:
+            return False
+        c0 = model.conv_layers[0]
+        return (int(model.edge_dim) == int(edge_feat_dim) and 1 <= int(edge_feat_dim) <= 64
+                and not (c0.heads == 4 and int(c0.in_channels) > 768))  # (the one shape whose backward would spill: not built)
+
+    def load(self, model) -> None:
+        super().load(model)
+        dev = self.eng.device
+        f = lambda t: t.detach().to(dev, torch.float32).contiguous().clone()
+        self.w_edge = [f(c.lin_edge.weight) for c in model.conv_layers]
+        self.att_edge = [f(c.att_edge).reshape(-1) for c in model.conv_layers]
+        # the message weight: None (GATConv), the SAME tensor as w_edge (shared: the library sees equal pointers) or its own
+        self.w_edge_msg = []
+        for l, c in enumerate(model.conv_layers):
+            lm = getattr(c, "lin_edge_message", None)
+            if c.edge_message_weight() is None:
+                self.w_edge_msg.append(None)
+            else:
+                self.w_edge_msg.append(self.w_edge[l] if lm is None else f(lm.weight))
+
+    def _after_create(self, handle) -> None:
+        arr = lambda ts: (C.c_void_p * 2)(*[(t.data_ptr() if t is not None else None) for t in ts])
+        self._keep_edge = self.eng._efeat  # (the plan borrows the table)
+        check(self._lib.gigl_gat_nablp_train_plan_set_edge_features(handle, self.eng._efeat_handle, arr(self.w_edge),
+                                                                    arr(self.att_edge), arr(self.w_edge_msg)), self.eng._ctx)
+
+    def store(self, model) -> None:
+        super().store(model)
+        with torch.no_grad():
+            for l, c in enumerate(model.conv_layers):
+                c.lin_edge.weight.copy_(self.w_edge[l])
+                c.att_edge.copy_(self.att_edge[l].view_as(c.att_edge))
+                if getattr(c, "lin_edge_message", None) is not None:
+                    c.lin_edge_message.weight.copy_(self.w_edge_msg[l])
+
+    def _separate_msg(self, l: int) -> bool:
+        return self.w_edge_msg[l] is not None and self.w_edge_msg[l] is not self.w_edge[l]
+
+    def grads(self, layer: int):
+        """GatNablpTrainPlan.grads + (d lin_edge.weight, d att_edge, d lin_edge_message.weight | None) of the LAST step; a
+        shared message weight's gradient is part of d lin_edge.weight"""
+        outs = [torch.empty_like(self.w_edge[layer]), torch.empty_like(self.att_edge[layer]),
+                torch.empty_like(self.w_edge_msg[layer]) if self._separate_msg(layer) else None]
+        base = super().grads(layer)
+        check(self._lib.gigl_gat_nablp_train_plan_edge_grads(self._plan, int(layer),
+                                                             *[(C.c_void_p(t.data_ptr()) if t is not None else None) for t in outs]),
+              self.eng._ctx)
+        return base + tuple(outs)
+
+    def moments(self) -> dict:
+        """GatNablpTrainPlan.moments + "conv_layers.l.lin_edge.weight" | att_edge | lin_edge_message.weight"""
+        out = super().moments()
+        for l in range(2):
+            for k, (name, t) in enumerate((("lin_edge.weight", self.w_edge[l]), ("att_edge", self.att_edge[l]),
+                                           ("lin_edge_message.weight", self.w_edge_msg[l] if self._separate_msg(l) else None))):
+                if t is None:
+                    continue
+                m, v = torch.empty_like(t), torch.empty_like(t)
+                check(self._lib.gigl_nablp_train_plan_moments(self._plan, 8 + 3 * l + k, C.c_void_p(m.data_ptr()),
                                                               C.c_void_p(v.data_ptr())), self.eng._ctx)
                 out[f"conv_layers.{l}.{name}"] = (m, v)
         return out

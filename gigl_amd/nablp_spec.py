@@ -836,7 +836,8 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         """-> engine.NablpTrainPlan when this job's training step can run as ONE library call per batch
         (gigl_nablp_train_plan_*: both encodes, the head, the backward and Adam inside the library, a hipGraph per step),
         else None (the autograd loop below).  That is: the in-HBM route with a whole replica in one process, the plain
-        mean-GraphSAGE encoder — or configs[4]'s two-layer GAT (engine.GatNablpTrainPlan.applies) —, the inner-product
+        mean-GraphSAGE encoder — or configs[4]'s two-layer GAT (engine.GatNablpTrainPlan.applies), or that encoder with
+        edge_dim over the engine's resident edge table (engine.GatEdgeNablpTrainPlan: no table raises) —, the inner-product
         decoder, the Retrieval task alone with its own cross-entropy and no
         candidate-sampling correction, torch.optim.Adam with its default betas / eps, a constant learning rate, no gradient
         clipping; trainerArgs train_plan = "off" keeps the autograd loop."""
@@ -847,10 +848,13 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         enc, dec = inner.encoder, inner.decoder
         tasks = list(self.tasks._task_to_fn_map.values())
         from ._lib import MODE_SPARK_HASH
-        from .engine import GatNablpTrainPlan
+        from .engine import GatEdgeNablpTrainPlan, GatNablpTrainPlan
         sage = type(enc).__module__ == "gigl_amd.models" and type(enc).__name__ == "GraphSAGE" and not res.train_as_graph_data
         gat = GatNablpTrainPlan.applies(enc, res.feat_dim) and len(res.fanouts) == 2  # (configs[4]'s encoder)
-        if _rank_world()[1] > 1 or res.sharded or res.mode != MODE_SPARK_HASH or not (sage or gat) or \
+        # ... with edge features: the table's width is the engine's (0 without a table: the constructor then raises)
+        gat_edge = (not gat and getattr(enc, "edge_dim", None) is not None and len(res.fanouts) == 2 and
+                    GatEdgeNablpTrainPlan.applies(enc, res.feat_dim, res.engine.edge_feat_dim or int(enc.edge_dim)))
+        if _rank_world()[1] > 1 or res.sharded or res.mode != MODE_SPARK_HASH or not (sage or gat or gat_edge) or \
                 len(tasks) != 1 or type(tasks[0]) is not Retrieval or \
                 tasks[0].should_enable_candidate_sampling_correction or tasks[0].loss._loss is not None or \
                 self.tasks._task_to_weights_map.get(tasks[0].task_name) != 1.0 or \
@@ -871,7 +875,7 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         from ._lib import GiglError
         from .engine import NablpTrainPlan
         try:
-            return (NablpTrainPlan if sage else GatNablpTrainPlan)(
+            return (NablpTrainPlan if sage else GatEdgeNablpTrainPlan if gat_edge else GatNablpTrainPlan)(
                 res.engine, enc, self.main_sample_batch_size, cfg.num_positive_samples,
                 self.random_negative_sample_batch_size, res.fanouts, temperature=float(tasks[0].loss._temperature or 0.0),
                 remove_accidental_hits=bool(tasks[0].loss._remove_accidental_hits), lr=self._optim_kwargs["lr"],

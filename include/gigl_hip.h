@@ -1307,12 +1307,14 @@ int32_t gigl_nablp_train_plan_grads(gigl_nablp_train_plan* plan, int32_t layer, 
 /* as gigl_sage_train_plan_adopt, for the link-prediction plans (GraphSAGE and GAT encoders alike) */
 int32_t gigl_nablp_train_plan_adopt(gigl_nablp_train_plan* dst, gigl_nablp_train_plan* src);
 /* moments of one parameter tensor of a link-prediction plan: GraphSAGE encoder: index = 2 * layer (fused weight) | 2 * layer
- * + 1 (bias); GAT encoder: index 0..7 = w0, att_src0, att_dst0, bias0, w1, att_src1, att_dst1, bias1 */
+ * + 1 (bias); GAT encoder: index 0..7 = w0, att_src0, att_dst0, bias0, w1, att_src1, att_dst1, bias1, 8..13 = its edge
+ * tensors (gigl_gat_nablp_train_plan_set_edge_features) */
 int32_t gigl_nablp_train_plan_moments(gigl_nablp_train_plan* plan, int32_t index, float* m, float* v);
 int32_t gigl_nablp_train_plan_destroy(gigl_nablp_train_plan* plan);
 /* The same plan with the GAT encoder configs[4] names (GAT.init_conv_layers, python/gigl/src/common/models/pyg/
  * homogeneous.py:300-343): hops == 2, heads[0] in {1, 2, 4} concatenated heads of channels[0] in the first layer, one head of
- * channels[1] (= the embedding width, <= 512) in the second, no edge features, no activation after the last layer; feature
+ * channels[1] (= the embedding width, <= 512) in the second, no activation after the last layer (edge features:
+ * gigl_gat_nablp_train_plan_set_edge_features below); feature
  * rows of d % 4 == 0, d <= 1024 floats (fp32 or fp16 table).  The first layer runs from the INPUT side (attention-weighted
  * sums of the stored rows under the folded attention vectors, then one projection per head) for the nodes of level <= 1, the
  * second for the roots; the batch graphs number every node (generic union).  Parameters per layer: w [heads*channels][in],
@@ -1328,6 +1330,22 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
                                          float weight_decay, gigl_nablp_train_plan** out);
 int32_t gigl_gat_nablp_train_plan_grads(gigl_nablp_train_plan* plan, int32_t layer, float* gw, float* g_att_src,
                                         float* g_att_dst, float* gb);
+/* Edge features for that plan: GATConv(edge_dim) (torch_geometric's, as GAT.init_conv_layers builds it with edge_dim,
+ * python/gigl/src/common/models/pyg/homogeneous.py:300-343) and EdgeAttrGATConv (python/gigl/src/common/models/pyg/nn/conv/
+ * edge_attr_gat_conv.py:11-144: the messages are h_j + W_msg e_ij).  Called once, after create and before the first step
+ * (GIGL_E_INVALID_ARG afterwards, or on a GraphSAGE plan).  edge_table: the resident edge table, one fp32 row of edge_dim in
+ * [1, 64] floats per resident edge, read in place (GIGL_E_UNSUPPORTED for another dtype or width); self edges are dropped and
+ * the added self loop carries the mean attribute of the row's kept in-edges.  Per layer l: w_edge[l] = lin_edge.weight
+ * [heads_l*channels_l][edge_dim], att_edge[l] [heads_l*channels_l]; w_edge_msg NULL or w_edge_msg[l] NULL: the attributes
+ * enter the logits only; w_edge_msg[l] == w_edge[l]: share_edge_att_message_weight (ONE tensor: its two gradients are added,
+ * one Adam update); any other buffer: lin_edge_message.weight.  All DEVICE fp32, borrowed and UPDATED IN PLACE.
+ * gigl_nablp_train_plan_moments: index 8 + 3 * layer + {0: w_edge, 1: att_edge, 2: w_edge_msg when separate}.
+ * _edge_grads: the LAST step's gradients of one layer (any output may be NULL; a shared message weight's gradient is part of
+ * g_w_edge, g_w_edge_msg is then left alone). */
+int32_t gigl_gat_nablp_train_plan_set_edge_features(gigl_nablp_train_plan* plan, gigl_feat* edge_table, float* const* w_edge,
+                                                    float* const* att_edge, float* const* w_edge_msg);
+int32_t gigl_gat_nablp_train_plan_edge_grads(gigl_nablp_train_plan* plan, int32_t layer, float* g_w_edge, float* g_att_edge,
+                                             float* g_w_edge_msg);
 
 /* Count-min sketch of candidate ids for the Retrieval task's candidate-sampling correction
  * (python/gigl/src/common/models/layers/count_min_sketch.py:11-95, used by task.py:140-205): table = DEVICE int32
