@@ -64,7 +64,7 @@ SYMBOLS = [
     "gigl_expand_frontier_keyed", "gigl_typed_plan_set_op_keys",
     "gigl_sage_plan_run_part", "gigl_sage_plan_set_graph_stream", "gigl_sage_plan_overflow_add",
     "gigl_sage_train_plan_create", "gigl_sage_train_plan_step", "gigl_sage_train_plan_step2", "gigl_sage_train_plan_loss", "gigl_sage_train_plan_destroy",
-    "gigl_nablp_train_plan_create", "gigl_nablp_train_plan_step", "gigl_nablp_train_plan_step2", "gigl_gat_nablp_train_plan_create", "gigl_gat_nablp_train_plan_grads", "gigl_gat_nablp_train_plan_set_edge_features", "gigl_gat_nablp_train_plan_edge_grads", "gigl_nablp_train_plan_loss", "gigl_nablp_train_plan_destroy", "gigl_nablp_train_plan_grads",
+    "gigl_nablp_train_plan_create", "gigl_nablp_train_plan_step", "gigl_nablp_train_plan_step2", "gigl_gat_nablp_train_plan_create", "gigl_gat_nablp_train_plan_grads", "gigl_gat_nablp_train_plan_set_edge_features", "gigl_gat_nablp_train_plan_edge_grads", "gigl_nablp_train_plan_loss", "gigl_nablp_train_plan_destroy", "gigl_nablp_train_plan_grads", "gigl_nablp_train_plan_set_clip_grad_norm", "gigl_nablp_train_plan_set_constant_lr", "gigl_nablp_train_plan_grad_norm",
 ]
 
 KERNEL_IDS = {
@@ -433,6 +433,9 @@ def load() -> C.CDLL:
         "gigl_nablp_train_plan_step2": [vp, vp, vp, vp, vp, vp, i32, i32, vp],
         "gigl_nablp_train_plan_destroy": [vp],
         "gigl_nablp_train_plan_grads": [vp, i32, vp, vp],
+        "gigl_nablp_train_plan_set_clip_grad_norm": [vp, C.c_float],
+        "gigl_nablp_train_plan_set_constant_lr": [vp, C.c_float, i32],
+        "gigl_nablp_train_plan_grad_norm": [vp, vp],
         "gigl_gat_input_layer_fused": [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, i64, vp, i32,
                                        vp, vp],
         "gigl_gat_input_layer": [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, i64, vp, i64, vp, i64,

@@ -10,8 +10,10 @@
 //       (.../node_classification_modeling_task_spec.py:176-187),
 //   fed by process_raw_pyg_samples_and_collate_fn (rooted_node_neighborhood_data_loader.py:161-241).
 #include "common.h"
+#include "wave_reduce.h"
 
 #include <algorithm>
+#include <cmath>
 #include <functional>
 #include <new>
 #include <vector>
@@ -658,6 +660,10 @@ struct AdamPack {
   // without a second source adds 0
   int32_t n_src;
   float lr, beta1, beta2, eps, wd;
+  // torch.optim.lr_scheduler.ConstantLR, stepped after the optimiser: Adam's step t (1-based) runs at lr_warm (= lr * factor,
+  // multiplied once on the host) while t - 1 < warm_iters, at lr from then on.  warm_iters 0: no schedule
+  float lr_warm;
+  int32_t warm_iters;
 };
 
 // (sixteen chunks' loads in flight, added in chunk order)
@@ -675,15 +681,85 @@ __device__ __forceinline__ float chunk_sum(const float* __restrict__ part, int c
   return s;
 }
 
-// meta_b: the second encode's batch (NULL: the step has one); halt: the sticky "a batch failed" word (NULL: the plan has none)
+// element i of tensor k's RAW gradient — its sources added up, before clipping and before the decay: the one expression
+// both the norm pass and Adam evaluate (ch0 / ch1: the chunks of source 0 / 1 that hold real rows)
+__device__ __forceinline__ float adam_raw_grad(const AdamPack& a, int k, int ch0, int ch1, int64_t i) {
+  const float *g0 = a.g[0][k], *g1 = a.g[1][k], *part0 = a.part[0][k], *part1 = a.part[1][k];
+  float ga = part0 ? chunk_sum(part0, ch0, a.n[k], i) : g0[i];
+  if (part0 && g0) ga += g0[i];
+  if (a.n_src == 2) {
+    const float gb = part1 ? chunk_sum(part1, ch1, a.n[k], i) : (g1 ? g1[i] : 0.f);
+    return ga + gb;
+  }
+  return ga;
+}
+
+// a failed batch trains nothing (its loss is NaN).  meta_b: the second encode's batch (NULL: the step has one); halt: the
+// sticky "a batch failed" word (NULL: the plan has none)
+__device__ __forceinline__ bool adam_batch_failed(const int32_t* meta_a, const int32_t* meta_b, const int32_t* halt) {
+  return meta_a[GIGL_META_OVERFLOW] != 0 || (meta_b && meta_b[GIGL_META_OVERFLOW] != 0) || (halt && *halt != 0);
+}
+
+// Gradient clipping (torch.nn.utils.clip_grad_norm_, 2-norm over all parameters) needs the norm of gradients that only
+// exist inside the Adam kernel — partial sums, two sources — so it takes a pass of its own over the same pack, on the same
+// grid (x: a tensor's elements, y: the tensor): every workgroup squares the raw gradients of its elements into fp64, reduces
+// them over the wave and then over its four waves in LDS, and stores ONE partial at [blockIdx.y][blockIdx.x].  A pack entry
+// counts once (a shared tensor is one entry, the per-head slices partition W0).  No atomics, no tickets: grad_norm_final_kernel
+// adds the partials in index order.
+constexpr int ADAM_GRID_X_MAX = 208;
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(AdamPack a, const int32_t* __restrict__ meta_a,
+                                                          const int32_t* __restrict__ meta_b, const int32_t* __restrict__ halt,
+                                                          double* __restrict__ partials) {
+  if (adam_batch_failed(meta_a, meta_b, halt)) return;
+  __shared__ double s_w[4];
+  const int k = (int)blockIdx.y;  // (gridDim.y == a.count)
+  const int ch0 = a.part[0][k] ? (*a.rows[0][k] + a.rc[0][k] - 1) / a.rc[0][k] : 0;
+  const int ch1 = a.part[1][k] ? (*a.rows[1][k] + a.rc[1][k] - 1) / a.rc[1][k] : 0;
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n[k]; i += (int64_t)gridDim.x * blockDim.x) {
+    const double g = (double)adam_raw_grad(a, k, ch0, ch1, i);
+    acc += g * g;
+  }
+  acc = gigl_wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+
+// total_norm = sqrt(sum of the n partials, lane-strided then butterfly then wave order: fixed), coef = min(1, max_norm /
+// (total_norm + 1e-6)) -> out2 = {total_norm, coef}; one workgroup.  A NaN norm gives a NaN coef, as torch's clamp does.
+__global__ __launch_bounds__(256) void grad_norm_final_kernel(const double* __restrict__ partials, int n, float max_norm,
+                                                              const int32_t* __restrict__ meta_a,
+                                                              const int32_t* __restrict__ meta_b,
+                                                              const int32_t* __restrict__ halt, float* __restrict__ out2) {
+  if (adam_batch_failed(meta_a, meta_b, halt)) return;  // (the words keep the last trained step's)
+  __shared__ double s_w[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) acc += partials[i];
+  acc = gigl_wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double norm = sqrt(((s_w[0] + s_w[1]) + s_w[2]) + s_w[3]);
+    const double c = (double)max_norm / (norm + 1e-6);
+    out2[0] = (float)norm;
+    out2[1] = (float)(c > 1.0 ? 1.0 : c);
+  }
+}
+
+// CLIP: every raw gradient is multiplied by clip[1] (the coef grad_norm_final_kernel left) before the decay joins it.  The
+// CLIP = false instantiation (clip NULL) is the kernel as it was before clipping existed: the same arithmetic, the same bits.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adam_kernel(AdamPack a, const int32_t* __restrict__ step_dev,
                                                    const int32_t* __restrict__ meta_a, const int32_t* __restrict__ meta_b,
-                                                   const int32_t* __restrict__ halt) {
-  // a failed batch trains nothing (its loss is NaN)
-  if (meta_a[GIGL_META_OVERFLOW] != 0 || (meta_b && meta_b[GIGL_META_OVERFLOW] != 0) || (halt && *halt != 0)) return;
-  const double t = (double)*step_dev;
+                                                   const int32_t* __restrict__ halt, const float* __restrict__ clip) {
+  if (adam_batch_failed(meta_a, meta_b, halt)) return;
+  const int32_t step = *step_dev;
+  const double t = (double)step;
   const float bc1 = (float)(1.0 - pow((double)a.beta1, t)), bc2s = (float)sqrt(1.0 - pow((double)a.beta2, t));
-  const float step_size = a.lr / bc1;
+  const float step_size = (step - 1 < a.warm_iters ? a.lr_warm : a.lr) / bc1;
+  float coef = 1.f;
+  if constexpr (CLIP) coef = clip[1];
   // gridDim.y > 1: one slice of the grid per tensor (the partial sums are chains of dependent-latency loads: the tensors'
   // chains run side by side instead of one after the other)
   const int k_lo = gridDim.y > 1 ? (int)blockIdx.y : 0, k_hi = gridDim.y > 1 ? (int)blockIdx.y + 1 : a.count;
@@ -691,20 +767,18 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamPack a, const int32_t* __
     float* p = a.p[k];
     float* m = a.m[k];
     float* v = a.v[k];
-    const float *g0 = a.g[0][k], *g1 = a.g[1][k], *part0 = a.part[0][k], *part1 = a.part[1][k];
-    const int ch0 = part0 ? (*a.rows[0][k] + a.rc[0][k] - 1) / a.rc[0][k] : 0;
-    const int ch1 = part1 ? (*a.rows[1][k] + a.rc[1][k] - 1) / a.rc[1][k] : 0;
+    const int ch0 = a.part[0][k] ? (*a.rows[0][k] + a.rc[0][k] - 1) / a.rc[0][k] : 0;
+    const int ch1 = a.part[1][k] ? (*a.rows[1][k] + a.rc[1][k] - 1) / a.rc[1][k] : 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n[k]; i += (int64_t)gridDim.x * blockDim.x) {
       const float w = p[i];
-      float ga = part0 ? chunk_sum(part0, ch0, a.n[k], i) : g0[i];
-      if (part0 && g0) ga += g0[i];
-      float gr;
-      if (a.n_src == 2) {
-        const float gb = part1 ? chunk_sum(part1, ch1, a.n[k], i) : (g1 ? g1[i] : 0.f);
-        gr = (ga + gb) + a.wd * w;
-      } else {
-        gr = ga + a.wd * w;
+      float g = adam_raw_grad(a, k, ch0, ch1, i);
+      if constexpr (CLIP) {
+        g *= coef;
+        // (the product is rounded here, as torch's grad.mul_(coef) rounds it: the empty statement keeps the compiler from
+        // contracting it into the decay's multiply-add, so coef = 1 gives the bits of the unclipped kernel)
+        asm volatile("" : "+v"(g));
       }
+      const float gr = g + a.wd * w;
       const float mm = m[i] + (gr - m[i]) * (1.f - a.beta1);
       const float vv = v[i] * a.beta2 + (1.f - a.beta2) * gr * gr;
       m[i] = mm;
@@ -712,6 +786,28 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamPack a, const int32_t* __
       p[i] = w - step_size * (mm / (sqrtf(vv) / bc2s + a.eps));
     }
   }
+}
+
+// where a plan keeps its clipping state (gigl_nablp_train_plan_set_clip_grad_norm); max_norm 0: off
+struct AdamClip {
+  float max_norm = 0.f;
+  double* partials = nullptr;  // [ADAM_MAX][ADAM_GRID_X_MAX]
+  float* out2 = nullptr;       // {total_norm, coef} of the last trained step
+};
+
+// the optimiser's launches over `ap` on a (gx, ap.count) grid: Adam alone, or — clipping on — the norm pass and its
+// finalising launch ahead of it
+void launch_adam(hipStream_t st, unsigned gx, const AdamPack& ap, const int32_t* step_dev, const int32_t* meta_a,
+                 const int32_t* meta_b, const int32_t* halt, const AdamClip* clip) {
+  const dim3 grid(gx, (unsigned)ap.count);
+  if (!clip || !(clip->max_norm > 0.f)) {
+    hipLaunchKernelGGL(adam_kernel<false>, grid, dim3(256), 0, st, ap, step_dev, meta_a, meta_b, halt, (const float*)nullptr);
+    return;
+  }
+  hipLaunchKernelGGL(grad_sqnorm_kernel, grid, dim3(256), 0, st, ap, meta_a, meta_b, halt, clip->partials);
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, st, (const double*)clip->partials, (int)(gx * ap.count),
+                     clip->max_norm, meta_a, meta_b, halt, clip->out2);
+  hipLaunchKernelGGL(adam_kernel<true>, grid, dim3(256), 0, st, ap, step_dev, meta_a, meta_b, halt, (const float*)clip->out2);
 }
 
 }  // namespace
@@ -1599,8 +1695,8 @@ int32_t train_enqueue_layers(gigl_sage_train_plan* t, int k) {
   rc = sage_enc_backward(ctx, *t, e, p, t->tlists[k], t->da, nullptr, nullptr);
   if (rc != GIGL_OK) return rc;
   const AdamPack ap = sage_adam_pack(*t, &e, p, nullptr, nullptr);
-  hipLaunchKernelGGL(adam_kernel, dim3(208, (unsigned)ap.count), dim3(256), 0, st, ap, (const int32_t*)(t->n_valid_buf + 1),
-                     (const int32_t*)p->un.meta, (const int32_t*)nullptr, (const int32_t*)(t->n_valid_buf + 2));
+  launch_adam(st, 208, ap, (const int32_t*)(t->n_valid_buf + 1), (const int32_t*)p->un.meta, (const int32_t*)nullptr,
+              (const int32_t*)(t->n_valid_buf + 2), nullptr);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -1921,6 +2017,10 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
     } e;
   } gat;
   bool stepped = false;  // a step has run: the plan's shape is final
+  // the optimiser's two other knobs (set after create, before the first step: the step is captured)
+  AdamClip clip;           // gigl_nablp_train_plan_set_clip_grad_norm
+  float lr_warm = 0.f;     // gigl_nablp_train_plan_set_constant_lr: lr * factor ...
+  int32_t warm_iters = 0;  // ... for Adam's first warm_iters steps
   std::vector<void*> owned;
   // Two workspaces of trees + union graphs (as gigl_sage_train_plan): the graph part of the NEXT step's roots (sample +
   // union of both root sets: latency-bound launches) runs on a side stream beside this step's layers
@@ -2319,9 +2419,11 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
     }
   }
   if (t->kind == 1) return gat_lp_finish(t);
-  const AdamPack ap = sage_adam_pack(*t, &t->enc[0], pm, &t->enc[1], pr);
-  hipLaunchKernelGGL(adam_kernel, dim3(208, (unsigned)ap.count), dim3(256), 0, st, ap, (const int32_t*)(t->consts + 2),
-                     (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta, (const int32_t*)nullptr);
+  AdamPack ap = sage_adam_pack(*t, &t->enc[0], pm, &t->enc[1], pr);
+  ap.lr_warm = t->lr_warm;
+  ap.warm_iters = t->warm_iters;
+  launch_adam(st, 208, ap, (const int32_t*)(t->consts + 2), (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta,
+              (const int32_t*)nullptr, &t->clip);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -2597,6 +2699,46 @@ int32_t gigl_nablp_train_plan_step(gigl_nablp_train_plan* t, const uint32_t* mai
 
 const float* gigl_nablp_train_plan_loss(gigl_nablp_train_plan* t) { return t ? t->loss : nullptr; }
 
+int32_t gigl_nablp_train_plan_set_clip_grad_norm(gigl_nablp_train_plan* t, float max_norm) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  gigl_ctx* ctx = t->ctx;
+  GIGL_REQUIRE(ctx, !t->stepped, "gradient clipping is set after create and before the first step (the step is captured)");
+  GIGL_REQUIRE(ctx, std::isfinite(max_norm) && max_norm > 0.f, "max_norm must be finite and > 0");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (!t->clip.partials) {
+    t->clip.partials = (double*)train_alloc(t->owned, (size_t)ADAM_MAX * ADAM_GRID_X_MAX * sizeof(double));
+    t->clip.out2 = (float*)train_alloc(t->owned, 16);
+    if (!t->clip.partials || !t->clip.out2) {
+      t->clip = AdamClip{};
+      return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the gradient norm's partial sums failed");
+    }
+    GIGL_HIP_CHECK(ctx, hipMemset(t->clip.out2, 0, 16));
+  }
+  t->clip.max_norm = max_norm;
+  return GIGL_OK;
+}
+
+int32_t gigl_nablp_train_plan_set_constant_lr(gigl_nablp_train_plan* t, float factor, int32_t total_iters) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  gigl_ctx* ctx = t->ctx;
+  GIGL_REQUIRE(ctx, !t->stepped, "the learning-rate schedule is set after create and before the first step (the step is captured)");
+  GIGL_REQUIRE(ctx, factor > 0.f && factor <= 1.f, "ConstantLR: factor must be in (0, 1]");
+  GIGL_REQUIRE(ctx, total_iters >= 0, "ConstantLR: total_iters must be >= 0");
+  t->lr_warm = t->lr * factor;  // (once, in fp32: a power-of-two factor is exact)
+  t->warm_iters = total_iters;
+  return GIGL_OK;
+}
+
+int32_t gigl_nablp_train_plan_grad_norm(gigl_nablp_train_plan* t, float* out2) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  gigl_ctx* ctx = t->ctx;
+  GIGL_REQUIRE(ctx, out2, "null output");
+  GIGL_REQUIRE(ctx, t->clip.out2, "the plan does not clip (gigl_nablp_train_plan_set_clip_grad_norm): no norm is computed");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  GIGL_HIP_CHECK(ctx, hipMemcpyAsync(out2, t->clip.out2, 8, hipMemcpyDeviceToDevice, ctx->stream));
+  return GIGL_OK;
+}
+
 namespace {
 __global__ __launch_bounds__(256) void lp_acc_kernel(float* __restrict__ dst, const float* __restrict__ src, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] += src[i];
@@ -2670,7 +2812,10 @@ int32_t gigl_nablp_train_plan_adopt(gigl_nablp_train_plan* dst, gigl_nablp_train
     const int32_t rc = sage_moments_adopt(ctx, *dst, *src);
     if (rc != GIGL_OK) return rc;
   }
+  // (Adam's step counter: the bias correction and the ConstantLR schedule go on where src stood)
   GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->consts + 2, src->consts + 2, 4, hipMemcpyDeviceToDevice, ctx->stream));
+  if (dst->clip.out2 && src->clip.out2)
+    GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->clip.out2, src->clip.out2, 8, hipMemcpyDeviceToDevice, ctx->stream));
   GIGL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return GIGL_OK;
 }
@@ -3067,8 +3212,10 @@ int32_t gat_lp_finish(gigl_nablp_train_plan* t) {
   ap.beta2 = t->beta2;
   ap.eps = t->eps;
   ap.wd = t->wd;
-  hipLaunchKernelGGL(adam_kernel, dim3(104, (unsigned)ap.count), dim3(256), 0, st, ap, (const int32_t*)(t->consts + 2),
-                     (const int32_t*)t->enc[0].base->un.meta, (const int32_t*)t->enc[1].base->un.meta, (const int32_t*)nullptr);
+  ap.lr_warm = t->lr_warm;
+  ap.warm_iters = t->warm_iters;
+  launch_adam(st, 104, ap, (const int32_t*)(t->consts + 2), (const int32_t*)t->enc[0].base->un.meta,
+              (const int32_t*)t->enc[1].base->un.meta, (const int32_t*)nullptr, &t->clip);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }

@@ -11,6 +11,15 @@ __host__ __device__ __forceinline__ int gigl_wave_reduce16_index(int lane) {
   return ((lane >> 2) & 1) | (((lane >> 3) & 1) << 1) | (((lane >> 4) & 1) << 2) | (((lane >> 5) & 1) << 3);
 }
 
+// One fp64 value per lane -> its total over the 64 lanes, in every lane: a butterfly over lane distances 32, 16, ... 1.
+// Every lane adds the same pairs at every step (fp addition commutes), so all lanes end with the same bits, and the
+// order is fixed: the same inputs give the same bits on every wave.  All 64 lanes must be active.
+__device__ __forceinline__ double gigl_wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
 __device__ __forceinline__ float gigl_wave_reduce16(const float (&p)[16]) {
   typedef unsigned int gigl_u2 __attribute__((ext_vector_type(2)));
   auto f2u = [](float x) { return __builtin_bit_cast(unsigned, x); };

@@ -1528,7 +1528,8 @@ class NablpTrainPlan:
 
     def __init__(self, eng: HipEngine, model, b_anchors: int, num_positives: int, n_random_negatives: int, fanouts,
                  temperature: float = 0.07, remove_accidental_hits: bool = True, lr: float = 5e-3,
-                 weight_decay: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8):
+                 weight_decay: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8, clip_grad_norm: float = 0.0,
+                 lr_factor: float = 1.0, lr_total_iters: int = 0):
         assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
         L = len(fanouts)
         assert model.num_layers == L, "one hop per layer"
@@ -1538,6 +1539,7 @@ class NablpTrainPlan:
         self.eng, self.b, self.P, self.n_rn = eng, int(b_anchors), int(num_positives), int(n_random_negatives)
         self.fanouts = [int(f) for f in fanouts]
         self._lib = eng._lib
+        self._optim_knobs = (float(clip_grad_norm), float(lr_factor), int(lr_total_iters))
         self.w, self.bias = [], []
         SageTrainPlan.load(self, model)
         self.dims = [int(self.w[0].shape[1]) // 2] + [int(w.shape[0]) for w in self.w]
@@ -1553,6 +1555,11 @@ class NablpTrainPlan:
                 eng._ctx, eng._graph, eng._feat, self.b, self.P, self.n_rn, fo, L, dims, w_arr, b_arr, flags[0], flags[1],
                 float(temperature), 1 if remove_accidental_hits else 0, float(lr), float(betas[0]), float(betas[1]), float(eps),
                 float(weight_decay), C.byref(h)), eng._ctx)
+            try:
+                self._apply_optim_knobs(h)
+            except Exception:
+                self._lib.gigl_nablp_train_plan_destroy(h)
+                raise
             return h
         self._create, self._adopt, self._destroy = create, self._lib.gigl_nablp_train_plan_adopt, self._lib.gigl_nablp_train_plan_destroy
         self.wide = False
@@ -1563,6 +1570,24 @@ class NablpTrainPlan:
     store = SageTrainPlan.store
     grow = SageTrainPlan.grow
     step_checked = SageTrainPlan.step_checked
+
+    def _apply_optim_knobs(self, handle) -> None:
+        """gradient clipping and the ConstantLR warm-up of a (re)created plan handle, before its first step (called inside
+        create(), so that grow()'s wide plan clips and schedules like the one it replaces)"""
+        clip, factor, total_iters = self._optim_knobs
+        if clip != 0.0:  # (0 = off, the trainer's default; anything else is the library's to judge)
+            check(self._lib.gigl_nablp_train_plan_set_clip_grad_norm(handle, clip), self.eng._ctx)
+        if factor != 1.0 or total_iters < 0:
+            check(self._lib.gigl_nablp_train_plan_set_constant_lr(handle, factor, total_iters), self.eng._ctx)
+
+    def grad_norm(self):
+        """(total_norm, coef) of the LAST trained step of a clipping plan (gigl_nablp_train_plan_grad_norm): the 2-norm over
+        all parameter gradients and the factor min(1, max_norm / (total_norm + 1e-6)) they were multiplied by; synchronises"""
+        out = torch.empty(2, dtype=torch.float32, device=self.eng.device)
+        check(self._lib.gigl_nablp_train_plan_grad_norm(self._plan, C.c_void_p(out.data_ptr())), self.eng._ctx)
+        self.eng.synchronize()
+        t = out.cpu()
+        return float(t[0]), float(t[1])
 
     def _padded(self, main_roots: torch.Tensor, pos_cnt: Optional[torch.Tensor], rn_roots: torch.Tensor):
         T = 1 + self.P
@@ -1643,13 +1668,15 @@ class GatNablpTrainPlan(NablpTrainPlan):
 
     def __init__(self, eng: HipEngine, model, b_anchors: int, num_positives: int, n_random_negatives: int, fanouts,
                  temperature: float = 0.07, remove_accidental_hits: bool = True, lr: float = 5e-3,
-                 weight_decay: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8):
+                 weight_decay: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8, clip_grad_norm: float = 0.0,
+                 lr_factor: float = 1.0, lr_total_iters: int = 0):
         assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
         if not self._applies_to(eng, model) or len(fanouts) != 2:
             raise NotImplementedError(self._COVERS)
         self.eng, self.b, self.P, self.n_rn = eng, int(b_anchors), int(num_positives), int(n_random_negatives)
         self.fanouts = [int(f) for f in fanouts]
         self._lib = eng._lib
+        self._optim_knobs = (float(clip_grad_norm), float(lr_factor), int(lr_total_iters))
         self.load(model)
         c0, c1 = model.conv_layers
         self.heads, self.channels = [int(c0.heads), 1], [int(c0.out_channels), int(c1.out_channels)]
@@ -1665,6 +1692,7 @@ class GatNablpTrainPlan(NablpTrainPlan):
                 float(betas[1]), float(eps), float(weight_decay), C.byref(h)), eng._ctx)
             try:
                 self._after_create(h)
+                self._apply_optim_knobs(h)
             except Exception:
                 self._lib.gigl_nablp_train_plan_destroy(h)
                 raise

@@ -832,6 +832,23 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             yield RootedNodeNeighborhoodBatch.process_raw_pyg_samples_and_collate_fn(raw, node_type=cfg.node_types[0])
 
     # ---- loops
+    def _train_plan_optim_kwargs(self) -> Optional[Dict[str, Any]]:
+        """-> the optimiser's keyword arguments of the library's training plan (engine.NablpTrainPlan and its GAT kinds) when
+        the plan's Adam is this job's optimiser, else None.  The plan runs torch.optim.Adam with default betas / eps and no
+        amsgrad (any optimiser argument besides optim_lr / optim_weight_decay keeps the autograd loop), clips the gradients'
+        2-norm as clip_grad_norm_ does (clip_grad_norm > 0) and follows the ConstantLR schedule (factor, total_iters); any
+        other scheduler class keeps the autograd loop."""
+        if self._optim_cls is not torch.optim.Adam or set(self._optim_kwargs) - {"lr", "weight_decay"}:
+            return None
+        if self._lr_scheduler_cls is not torch.optim.lr_scheduler.ConstantLR or \
+                set(self._lr_scheduler_kwargs) - {"factor", "total_iters"}:
+            return None
+        factor = float(self._lr_scheduler_kwargs.get("factor", 1.0 / 3))  # (ConstantLR's own defaults)
+        total_iters = int(self._lr_scheduler_kwargs.get("total_iters", 5))
+        return dict(lr=float(self._optim_kwargs["lr"]), weight_decay=float(self._optim_kwargs["weight_decay"]),
+                    clip_grad_norm=max(float(self.clip_grad_norm), 0.0),  # (the trainer clips only when it is > 0)
+                    lr_factor=factor, lr_total_iters=total_iters if factor != 1.0 else 0)
+
     def _library_train_plan(self, cfg: GbmlConfigPbWrapper):
         """-> engine.NablpTrainPlan when this job's training step can run as ONE library call per batch
         (gigl_nablp_train_plan_*: both encodes, the head, the backward and Adam inside the library, a hipGraph per step),
@@ -839,8 +856,10 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         mean-GraphSAGE encoder — or configs[4]'s two-layer GAT (engine.GatNablpTrainPlan.applies), or that encoder with
         edge_dim over the engine's resident edge table (engine.GatEdgeNablpTrainPlan: no table raises) —, the inner-product
         decoder, the Retrieval task alone with its own cross-entropy and no
-        candidate-sampling correction, torch.optim.Adam with its default betas / eps, a constant learning rate, no gradient
-        clipping; trainerArgs train_plan = "off" keeps the autograd loop."""
+        candidate-sampling correction, and an optimiser the plan runs (_train_plan_optim_kwargs: torch.optim.Adam with its
+        default betas / eps — with or without gradient-norm clipping (clip_grad_norm) and the ConstantLR warm-up (factor,
+        total_iters), both applied inside the plan's Adam launch sequence —; any other scheduler class keeps the autograd
+        loop); trainerArgs train_plan = "off" keeps the autograd loop."""
         if str(self._kwargs.get("train_plan", "auto")).lower() == "off" or self._hbm_split(cfg) is None:
             return None
         res = self._resident
@@ -859,12 +878,12 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
                 tasks[0].should_enable_candidate_sampling_correction or tasks[0].loss._loss is not None or \
                 self.tasks._task_to_weights_map.get(tasks[0].task_name) != 1.0 or \
                 str(getattr(dec, "decoder_type", "inner_product")).split(".")[-1] != "inner_product" or \
-                self._optim_cls is not torch.optim.Adam or self.clip_grad_norm > 0 or \
-                self._lr_scheduler_cls is not torch.optim.lr_scheduler.ConstantLR or \
-                float(self._lr_scheduler_kwargs.get("factor", 1.0)) != 1.0 or int(enc.conv_layers[-1].out_channels) > 512:
+                int(enc.conv_layers[-1].out_channels) > 512:
             return None
-        # the plan's Adam is torch's with default betas / eps and no amsgrad: any other optimiser setting keeps the autograd loop
-        if set(self._optim_kwargs) - {"lr", "weight_decay"}:
+        # the plan's Adam is torch's with default betas / eps and no amsgrad, clipped and ConstantLR-scheduled as the trainer
+        # asks: any other optimiser or scheduler setting keeps the autograd loop
+        optim = self._train_plan_optim_kwargs()
+        if optim is None:
             return None
         # ... and it trains exactly the tensors its load / store move: the conv layers' weights (+ biases / attention vectors).
         # A model with any other trainable parameter (a decoder MLP, a final linear, batch norm, embeddings) would have it
@@ -878,8 +897,7 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             return (NablpTrainPlan if sage else GatEdgeNablpTrainPlan if gat_edge else GatNablpTrainPlan)(
                 res.engine, enc, self.main_sample_batch_size, cfg.num_positive_samples,
                 self.random_negative_sample_batch_size, res.fanouts, temperature=float(tasks[0].loss._temperature or 0.0),
-                remove_accidental_hits=bool(tasks[0].loss._remove_accidental_hits), lr=self._optim_kwargs["lr"],
-                weight_decay=self._optim_kwargs["weight_decay"])
+                remove_accidental_hits=bool(tasks[0].loss._remove_accidental_hits), **optim)
         except (NotImplementedError, GiglError):
             return None
 

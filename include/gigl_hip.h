@@ -1301,6 +1301,23 @@ int32_t gigl_nablp_train_plan_step2(gigl_nablp_train_plan* plan, const uint32_t*
                                     const uint32_t* rn_roots, const uint32_t* next_main_roots,
                                     const uint32_t* next_rn_roots, int32_t sampling_seed, int32_t mode, float* loss_out);
 const float* gigl_nablp_train_plan_loss(gigl_nablp_train_plan* plan);
+/* The trainer's two other optimiser arguments (node_anchor_based_link_prediction_modeling_task_spec.py:118-132), for every
+ * kind of link-prediction plan (GraphSAGE, GAT, GAT with edge features).  Both are called after create and before the first
+ * step (GIGL_E_INVALID_ARG afterwards: the step is captured).
+ * set_clip_grad_norm: replaces torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) between backward and
+ *   optimizer.step (:401-404): total_norm = the 2-norm over ALL parameter gradients (a norm pass of its own over the
+ *   partial sums, fp64, summed in a fixed order: two more launches per step), coef = min(1, max_norm / (total_norm +
+ *   1e-6)), every gradient times coef before the weight decay joins it.  max_norm finite and > 0.  A non-finite norm
+ *   propagates (error_if_nonfinite=False).  Without this call the step issues the launches it always did.
+ * set_constant_lr: replaces torch.optim.lr_scheduler.ConstantLR(optimizer, factor, total_iters) stepped after the
+ *   optimiser (:405-406): Adam's steps 1 .. total_iters run at lr * factor (multiplied once, in fp32), later ones at lr;
+ *   chosen on the device from Adam's step counter, so a failed batch does not advance the schedule and
+ *   gigl_nablp_train_plan_adopt carries it over.  factor in (0, 1], total_iters >= 0.
+ * grad_norm: {total_norm, coef} of the last trained step -> out2 (DEVICE float[2], on the ctx stream);
+ *   GIGL_E_INVALID_ARG for a plan that does not clip. */
+int32_t gigl_nablp_train_plan_set_clip_grad_norm(gigl_nablp_train_plan* plan, float max_norm);
+int32_t gigl_nablp_train_plan_set_constant_lr(gigl_nablp_train_plan* plan, float factor, int32_t total_iters);
+int32_t gigl_nablp_train_plan_grad_norm(gigl_nablp_train_plan* plan, float* out2);
 /* the LAST step's parameter gradients of layer `layer` (the two encodes' added): gw DEVICE [dims[l+1]][2 dims[l]] (= d loss
  * / d [W_l | W_r]), gb DEVICE [dims[l+1]] (may be NULL) — what the step's Adam update consumed; for gradient parity tests */
 int32_t gigl_nablp_train_plan_grads(gigl_nablp_train_plan* plan, int32_t layer, float* gw, float* gb);
