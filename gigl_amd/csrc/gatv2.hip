@@ -255,7 +255,7 @@ bool gatv2_shape(gigl_ctx* ctx, int heads, int C, int& V, int& group) {
   const int gl = C / 4, chunks = heads * C / 4;
   V = (chunks + 63) / 64;
   group = gl;
-  const bool ok = C % 4 == 0 && gl >= 1 && gl <= 64 && (gl & (gl - 1)) == 0 && (V == 1 || V == 2 || V == 4);
+  const bool ok = C % 4 == 0 && gl >= 1 && gl <= 64 && (gl & (gl - 1)) == 0 && V >= 1 && V <= 4;  // (V == 3 runs on <4>)
   if (!ok)
     gigl_fail(ctx, GIGL_E_UNSUPPORTED, "heads=%d channels=%d: the GATv2 kernels need channels %% 4 == 0, channels/4 a "
               "power of two <= 64 and heads*channels <= 1024", heads, C);

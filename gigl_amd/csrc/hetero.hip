@@ -337,8 +337,9 @@ __global__ __launch_bounds__(256) void weighted_aggregate_backward_kernel(
 }
 
 __device__ __forceinline__ void atomic_max_float(float* addr, float val) {
-  // floats order like sign-magnitude integers: positive values as int, negative as reversed unsigned
-  if (val >= 0.f) atomicMax((int*)addr, __float_as_int(val));
+  // floats order like sign-magnitude integers: positive values as int, negative as reversed unsigned.  The branch is
+  // on the sign BIT: -0.0 as an int is INT_MIN, below the -inf the maxima start from
+  if (__float_as_int(val) >= 0) atomicMax((int*)addr, __float_as_int(val));
   else atomicMin((unsigned int*)addr, __float_as_uint(val));
 }
 
