@@ -118,6 +118,12 @@ int32_t gigl_fail(gigl_ctx* ctx, int32_t code, const char* fmt, ...);
 int32_t gigl_arena_reset(gigl_ctx* ctx, int64_t need_bytes);
 void* gigl_arena_alloc(gigl_ctx* ctx, int64_t bytes);
 
+// gigl_lp_rank_metrics on `st` with the caller's per-anchor buffer part [b][2 + n_ks] doubles (loss.hip); meta_a / meta_b
+// (both or neither): union meta words of the batch — when either reports an overflow nothing is added to acc
+int32_t gigl_lp_rank_metrics_enqueue(gigl_ctx* ctx, hipStream_t st, const float* scores, int64_t ld, int32_t b, int32_t P,
+                                     const int32_t* pos_cnt, int32_t n_neg, int32_t neg_col0, const int32_t* neg_valid,
+                                     const int32_t* ks, int32_t n_ks, const int32_t* meta_a, const int32_t* meta_b,
+                                     double* part, double* acc);
 // fills g->maxdeg from the resident rowptr (synchronises the ctx stream)
 int32_t gigl_graph_compute_maxdeg(gigl_ctx* ctx, gigl_graph* g);
 // the weight gradient's per-chunk partial sums without the reduction launch (agg.hip): see gigl_linear_weight_grad_parts

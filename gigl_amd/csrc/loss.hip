@@ -204,9 +204,121 @@ __global__ __launch_bounds__(256) void cms_estimate_kernel(const int32_t* __rest
   out[k] = best;
 }
 
+// ---- rank metrics of a score matrix (the evaluation's hit_rate_at_k / mean_reciprocal_rank,
+// python/gigl/src/common/utils/eval_metrics.py:6-73, which the trainer calls once per anchor).  One wave per anchor:
+// for each of its p = min(pos_cnt, P) positives the lanes stride over the negatives and count those that score STRICTLY
+// higher (a tie counts for the positive); rank = 1 + that count.  part[a] = {mean_j 1 / rank_j, 1, mean_j [rank_j <= k]
+// per k}, all zero for an anchor without a positive.
+struct RankKs {
+  int32_t k[GIGL_LP_EVAL_MAX_KS];
+};
+
+__global__ __launch_bounds__(256) void lp_rank_rows_kernel(const float* __restrict__ scores, int64_t ld, int b, int P,
+                                                           const int32_t* __restrict__ pos_cnt, int n_neg, int neg_col0,
+                                                           const int32_t* __restrict__ neg_valid, RankKs ks, int n_ks,
+                                                           double* __restrict__ part) {
+  const int lane = threadIdx.x & 63;
+  const int a = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (a >= b) return;
+  const int W = 2 + n_ks;
+  double* out = part + (int64_t)a * W;
+  const int p = min(pos_cnt[a], P);
+  if (p <= 0) {
+    if (lane < W) out[lane] = 0.0;
+    return;
+  }
+  double mrr = 0.0;
+  int hits[GIGL_LP_EVAL_MAX_KS] = {0};
+  for (int j = 0; j < p; ++j) {
+    const int64_t q = (int64_t)a * P + j;
+    const float* row = scores + q * ld;
+    const float pos = row[q];
+    int cnt = 0;
+    for (int c = lane; c < n_neg; c += 64)
+      if ((!neg_valid || neg_valid[c]) && row[neg_col0 + c] > pos) ++cnt;
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    const int rank = 1 + cnt;
+    mrr += 1.0 / (double)rank;
+#pragma unroll
+    for (int k = 0; k < GIGL_LP_EVAL_MAX_KS; ++k) hits[k] += (k < n_ks && rank <= ks.k[k]) ? 1 : 0;
+  }
+  if (lane == 0) {
+    out[0] = mrr / (double)p;
+    out[1] = 1.0;
+#pragma unroll
+    for (int k = 0; k < GIGL_LP_EVAL_MAX_KS; ++k)
+      if (k < n_ks) out[2 + k] = (double)hits[k] / (double)p;
+  }
+}
+
+// acc[MRR_SUM | RANK_NODES | HITS0 + k] += the column sums of part [b][2 + n_ks], in a fixed order (one workgroup); skipped
+// when either meta word reports an overflowed batch (the plan's evaluation: such a batch adds nothing)
+__global__ __launch_bounds__(1024) void lp_rank_sum_kernel(const double* __restrict__ part, int b, int n_ks,
+                                                           const int32_t* __restrict__ meta_a,
+                                                           const int32_t* __restrict__ meta_b, double* __restrict__ acc) {
+  constexpr int WMAX = 2 + GIGL_LP_EVAL_MAX_KS;
+  __shared__ double s_w[16][WMAX];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, W = 2 + n_ks;
+  double v[WMAX];
+#pragma unroll
+  for (int c = 0; c < WMAX; ++c) v[c] = 0.0;
+  for (int i = tid; i < b; i += 1024) {
+#pragma unroll
+    for (int c = 0; c < WMAX; ++c)
+      if (c < W) v[c] += part[(int64_t)i * W + c];
+  }
+#pragma unroll
+  for (int c = 0; c < WMAX; ++c) {
+    for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
+    if (lane == 0) s_w[w][c] = v[c];
+  }
+  __syncthreads();
+  if (tid < W) {
+    if (meta_a && (meta_a[GIGL_META_OVERFLOW] != 0 || meta_b[GIGL_META_OVERFLOW] != 0)) return;
+    double t = 0.0;
+    for (int k = 0; k < 16; ++k) t += s_w[k][tid];
+    acc[tid == 0 ? GIGL_LP_EVAL_MRR_SUM : tid == 1 ? GIGL_LP_EVAL_RANK_NODES : GIGL_LP_EVAL_HITS0 + tid - 2] += t;
+  }
+}
+
 }  // namespace
 
+int32_t gigl_lp_rank_metrics_enqueue(gigl_ctx* ctx, hipStream_t st, const float* scores, int64_t ld, int32_t b, int32_t P,
+                                     const int32_t* pos_cnt, int32_t n_neg, int32_t neg_col0, const int32_t* neg_valid,
+                                     const int32_t* ks, int32_t n_ks, const int32_t* meta_a, const int32_t* meta_b,
+                                     double* part, double* acc) {
+  GIGL_REQUIRE(ctx, scores && pos_cnt && ks && part && acc && b >= 1 && P >= 1 && n_neg >= 0 && neg_col0 >= 0, "bad arguments");
+  GIGL_REQUIRE(ctx, ld >= (int64_t)b * P && (n_neg == 0 || ld >= (int64_t)neg_col0 + n_neg),
+               "the score rows (ld=%lld) do not hold the positives' and negatives' columns", (long long)ld);
+  GIGL_REQUIRE(ctx, n_ks >= 1 && n_ks <= GIGL_LP_EVAL_MAX_KS, "n_ks=%d outside [1, %d]", n_ks, GIGL_LP_EVAL_MAX_KS);
+  RankKs k{};
+  for (int i = 0; i < n_ks; ++i) {
+    GIGL_REQUIRE(ctx, ks[i] >= 1, "ks must be greater-or-equal to 1 (got %d)", ks[i]);
+    k.k[i] = ks[i];
+  }
+  hipLaunchKernelGGL(lp_rank_rows_kernel, dim3((unsigned)((b + 3) / 4)), dim3(256), 0, st, scores, ld, b, P, pos_cnt, n_neg,
+                     neg_col0, neg_valid, k, n_ks, part);
+  hipLaunchKernelGGL(lp_rank_sum_kernel, dim3(1), dim3(1024), 0, st, (const double*)part, b, n_ks, meta_a, meta_b, acc);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
 extern "C" {
+
+int32_t gigl_lp_rank_metrics(gigl_ctx* ctx, const float* scores, int64_t ld, int32_t b, int32_t P, const int32_t* pos_cnt,
+                             int32_t n_neg, int32_t neg_col0, const int32_t* neg_valid, const int32_t* ks, int32_t n_ks,
+                             double* acc) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  GIGL_REQUIRE(ctx, b >= 1 && b <= (1 << 24), "b=%d", b);
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int64_t bytes = (int64_t)b * (2 + GIGL_LP_EVAL_MAX_KS) * (int64_t)sizeof(double);
+  const int32_t rc = gigl_arena_reset(ctx, bytes + 256);
+  if (rc != GIGL_OK) return rc;
+  double* part = (double*)gigl_arena_alloc(ctx, bytes);
+  return gigl_lp_rank_metrics_enqueue(ctx, ctx->stream, scores, ld, b, P, pos_cnt, n_neg, neg_col0, neg_valid, ks, n_ks, nullptr,
+                                      nullptr, part, acc);
+}
+
 
 int32_t gigl_retrieval_loss(gigl_ctx* ctx, const float* scores, int64_t ld, int32_t q, int32_t c, float temperature,
                             const float* cand_prob, const int64_t* query_ids, const int64_t* cand_ids,

@@ -2035,6 +2035,9 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
     int32_t* tlists[2][GIGL_MAX_HOPS] = {{nullptr}};  // transposed lists of layers >= 1 per encode (SAGE; built by the graph part)
     const uint32_t *fetched_main = nullptr, *fetched_rn = nullptr;  // the caller's buffers its graph part ran for
     bool fetched = false;
+    // gigl_nablp_train_plan_eval's graph part: a captured graph of its own (its seed / mode need not be the training steps')
+    hipGraphExec_t exec_graph_eval = nullptr;
+    bool warm_graph_eval = false;
   } work[WS];
   hipEvent_t ev_now = nullptr;  // "the caller's stream, now": the roots a graph part copies were written before it
   // (round 6; GIGL_LP_FORK=0 turns it off) the random negatives' encode — ~15 launches of a 512-root batch, all latency — runs
@@ -2050,6 +2053,8 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
   hipEvent_t ev_w = nullptr, ev_wjoin = nullptr;
   int cur = 0;
   int32_t cap_seed = 0, cap_mode = -1;
+  int32_t eval_seed = 0, eval_mode = -1;  // ... and what the evaluation's captured graph parts were captured with
+  double* rank_part = nullptr;            // [b][2 + GIGL_LP_EVAL_MAX_KS]: the rank metrics' per-anchor values
 };
 
 namespace {
@@ -2224,6 +2229,46 @@ __global__ __launch_bounds__(1024) void lp_loss_sum_kernel(const float* __restri
   }
 }
 
+// the evaluation's loss sum: acc[LOSS_SUM] += the valid rows' mean loss (as lp_loss_sum_kernel adds it up), acc[BATCHES] += 1;
+// a batch beyond the workspace adds 1 to *overflow_acc instead.  Adam's step counter is not touched.
+__global__ __launch_bounds__(1024) void lp_eval_loss_sum_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ valid,
+                                                                int Q, const int32_t* __restrict__ meta_a,
+                                                                const int32_t* __restrict__ meta_b, double* __restrict__ acc,
+                                                                int32_t* __restrict__ overflow_acc) {
+  __shared__ double s_w[16];
+  __shared__ int s_n[16];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  double sum = 0.0;
+  int n = 0;
+  for (int i = tid; i < Q; i += 1024) {
+    sum += (double)row_loss[i];
+    n += valid[i] ? 1 : 0;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    sum += __shfl_xor(sum, off, 64);
+    n += __shfl_xor(n, off, 64);
+  }
+  if (lane == 0) {
+    s_w[w] = sum;
+    s_n[w] = n;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double t = 0.0;
+    int nn = 0;
+    for (int k = 0; k < 16; ++k) {
+      t += s_w[k];
+      nn += s_n[k];
+    }
+    if (meta_a[GIGL_META_OVERFLOW] != 0 || meta_b[GIGL_META_OVERFLOW] != 0) {
+      *overflow_acc += 1;
+    } else {
+      acc[GIGL_LP_EVAL_LOSS_SUM] += (double)(float)(t / (double)(nn > 0 ? nn : 1));  // (the fp32 word a step reports)
+      acc[GIGL_LP_EVAL_BATCHES] += 1.0;
+    }
+  }
+}
+
 // dscores = d loss / d scores: (softmax - onehot) / temperature / rows for the columns that take part, 0 elsewhere
 __global__ __launch_bounds__(256) void lp_loss_backward_kernel(const float* __restrict__ scores, int Q, int Cn, float temperature,
                                                                const int64_t* __restrict__ qid, const int64_t* __restrict__ cid,
@@ -2340,8 +2385,9 @@ int32_t lp_enqueue_graph(gigl_nablp_train_plan* t, int w, int32_t sampling_seed,
   return GIGL_OK;
 }
 
-// everything after the graph part, over workspace w's trees and union graphs, on lctx's stream (the caller's)
-int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
+// the forward half of the layers part over workspace w: both encodes, the head's operands, the scores, the loss rows
+// (shared by the training step and gigl_nablp_train_plan_eval)
+int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w) {
   gigl_ctx* ctx = t->lctx;
   hipStream_t st = ctx->stream;
   const int L = t->L, d = t->dims[L], Q = t->b * t->P, Cn = Q + t->n_rn;
@@ -2380,6 +2426,18 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
   hipLaunchKernelGGL(lp_loss_rows_kernel, dim3((unsigned)Q), dim3(256), 0, st, (const float*)t->scores, Q, Cn, t->temperature,
                      (const int64_t*)t->qid, (const int64_t*)t->cid, (const int32_t*)t->valid, t->remove_hits, t->row_lse,
                      t->row_loss);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+// everything after the graph part, over workspace w's trees and union graphs, on lctx's stream (the caller's)
+int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
+  gigl_ctx* ctx = t->lctx;
+  hipStream_t st = ctx->stream;
+  const int L = t->L, d = t->dims[L], Q = t->b * t->P, Cn = Q + t->n_rn;
+  int32_t rc = lp_enqueue_forward(t, w);
+  if (rc != GIGL_OK) return rc;
+  const gigl_sage_plan *pm = t->enc[0].base, *pr = t->enc[1].base;
   hipLaunchKernelGGL(lp_loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->row_loss, (const int32_t*)t->valid, Q,
                      t->loss, t->consts + 2, (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta);
   hipLaunchKernelGGL(lp_loss_backward_kernel, dim3((unsigned)Q), dim3(256), 0, st, (const float*)t->scores, Q, Cn,
@@ -2483,7 +2541,8 @@ bool lp_head_alloc(gigl_nablp_train_plan* t, size_t d) {
   t->row_lse = (float*)alloc(Q * 4);
   t->row_loss = (float*)alloc(Q * 4);
   t->loss = (float*)alloc(64);
-  ok = ok && t->rq && t->cand && t->cand_t && t->scores && t->dscores && t->d_rq && t->d_cand && t->qid && t->cid && t->valid &&
+  t->rank_part = (double*)alloc((size_t)t->b * (2 + GIGL_LP_EVAL_MAX_KS) * sizeof(double));
+  ok = ok && t->rank_part && t->rq && t->cand && t->cand_t && t->scores && t->dscores && t->d_rq && t->d_cand && t->qid && t->cid && t->valid &&
        t->pos_cnt && t->consts && t->row_lse && t->row_loss && t->loss;
   const int32_t c[16] = {(int32_t)Q, (int32_t)Cn, 0 /* Adam's step counter */, 0};
   return ok && hipMemcpy(t->consts, c, sizeof(c), hipMemcpyHostToDevice) == hipSuccess && hipMemset(t->loss, 0, 64) == hipSuccess;
@@ -2524,6 +2583,7 @@ int32_t gigl_nablp_train_plan_destroy(gigl_nablp_train_plan* t) {
   for (auto& wk : t->work) {
     if (wk.exec_graph) hipGraphExecDestroy(wk.exec_graph);
     if (wk.exec_layers) hipGraphExecDestroy(wk.exec_layers);
+    if (wk.exec_graph_eval) hipGraphExecDestroy(wk.exec_graph_eval);
     if (wk.ev_graph) hipEventDestroy(wk.ev_graph);
     if (wk.ev_layers) hipEventDestroy(wk.ev_layers);
     for (int k = 0; k < 2; ++k)
@@ -2615,7 +2675,7 @@ int32_t gigl_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat
 namespace {
 // the graph part of workspace w for these roots, on its side stream; work[w].ev_graph marks its end
 int32_t lp_graph_part(gigl_nablp_train_plan* t, int w, const uint32_t* main_roots, const uint32_t* rn_roots,
-                      int32_t sampling_seed, int32_t mode) {
+                      int32_t sampling_seed, int32_t mode, bool eval = false) {
   gigl_nablp_train_plan::Work& wk = t->work[w];
   gigl_ctx* sc = wk.side;
   // the workspace is free once the layers part that last read it is done; the roots were written on the caller's stream
@@ -2627,10 +2687,11 @@ int32_t lp_graph_part(gigl_nablp_train_plan* t, int w, const uint32_t* main_root
     GIGL_HIP_CHECK(sc, hipMemcpyAsync(wk.base[1]->roots_buf, rn_roots, (size_t)t->n_rn * 4, hipMemcpyDeviceToDevice, sc->stream));
   else
     gigl_fill_u32(sc->stream, wk.base[1]->roots_buf, GIGL_INVALID, 1);
-  const int32_t rc = train_run_part(sc, &wk.exec_graph, &wk.warm_graph,
+  const int32_t rc = train_run_part(sc, eval ? &wk.exec_graph_eval : &wk.exec_graph, eval ? &wk.warm_graph_eval : &wk.warm_graph,
                                     [&]() { return lp_enqueue_graph(t, w, sampling_seed, mode); }, 0);
   if (rc != GIGL_OK) return rc;
   GIGL_HIP_CHECK(sc, hipEventRecord(wk.ev_graph, sc->stream));
+  if (eval) return GIGL_OK;  // (an evaluation batch is consumed by the call that samples it: nothing to recognise later)
   wk.fetched_main = main_roots;
   wk.fetched_rn = rn_roots;
   wk.fetched = true;
@@ -2697,7 +2758,66 @@ int32_t gigl_nablp_train_plan_step(gigl_nablp_train_plan* t, const uint32_t* mai
   return gigl_nablp_train_plan_step2(t, main_roots, pos_cnt, rn_roots, nullptr, nullptr, sampling_seed, mode, loss_out);
 }
 
+int32_t gigl_nablp_train_plan_eval(gigl_nablp_train_plan* t, const uint32_t* main_roots, const int32_t* pos_cnt,
+                                   const uint32_t* rn_roots, int32_t sampling_seed, int32_t mode, const int32_t* ks,
+                                   int32_t n_ks, double* acc, int32_t* overflow_acc) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  gigl_ctx* ctx = t->ctx;
+  GIGL_REQUIRE(ctx, main_roots && pos_cnt && (rn_roots || t->n_rn == 0) && ks && acc && overflow_acc, "null argument");
+  if (mode == GIGL_MODE_REPLACE)
+    return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "the training plan needs duplicate-free trees (no with-replacement mode)");
+  GIGL_REQUIRE(ctx, n_ks >= 1 && n_ks <= GIGL_LP_EVAL_MAX_KS, "n_ks=%d outside [1, %d]", n_ks, GIGL_LP_EVAL_MAX_KS);
+  for (int i = 0; i < n_ks; ++i) GIGL_REQUIRE(ctx, ks[i] >= 1, "ks must be greater-or-equal to 1 (got %d)", ks[i]);
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (t->lctx->stream != st || t->lctx->own_stream) {
+    const int32_t rs = gigl_ctx_set_stream(t->lctx, st);
+    if (rs != GIGL_OK) return gigl_fail(ctx, rs, "%s", gigl_last_error(t->lctx));
+  }
+  if (t->eval_seed != sampling_seed || t->eval_mode != mode) {  // seed and mode are baked into the captured graph parts
+    for (auto& wk : t->work) {
+      if (!wk.exec_graph_eval) continue;
+      GIGL_HIP_CHECK(ctx, hipStreamSynchronize(wk.side->stream));
+      hipGraphExecDestroy(wk.exec_graph_eval);
+      wk.exec_graph_eval = nullptr;
+    }
+    t->eval_seed = sampling_seed;
+    t->eval_mode = mode;
+  }
+  // the workspace that holds no announced batch (a _step2 with next roots left its graph part in work[cur])
+  const int w = t->work[t->cur].fetched ? (t->cur + 1) % gigl_nablp_train_plan::WS : t->cur;
+  gigl_nablp_train_plan::Work& wk = t->work[w];
+  GIGL_REQUIRE(ctx, !wk.fetched, "both workspaces hold an announced batch");
+  int32_t rc = lp_graph_part(t, w, main_roots, rn_roots, sampling_seed, mode, true);
+  if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(wk.side));
+  GIGL_HIP_CHECK(ctx, hipMemcpyAsync(t->pos_cnt, pos_cnt, (size_t)t->b * 4, hipMemcpyDeviceToDevice, st));
+  GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, wk.ev_graph, 0));
+  // (eager: no captured layers graph is made or invalidated — and none with a second branch, see gigl_nablp_train_plan_create)
+  gigl_sage_plan* const held[2] = {t->enc[0].base, t->enc[1].base};
+  rc = lp_enqueue_forward(t, w);
+  const gigl_sage_plan *pm = wk.base[0], *pr = wk.base[1];
+  for (int k = 0; k < 2; ++k) t->enc[k].base = held[k];
+  if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
+  const int Q = t->b * t->P;
+  hipLaunchKernelGGL(lp_eval_loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->row_loss, (const int32_t*)t->valid, Q,
+                     (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta, acc, overflow_acc);
+  rc = gigl_lp_rank_metrics_enqueue(t->lctx, st, t->scores, (int64_t)Q + t->n_rn, t->b, t->P, t->pos_cnt, t->n_rn, Q,
+                                    t->valid + Q, ks, n_ks, pm->un.meta, pr->un.meta, t->rank_part, acc);
+  if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
+  GIGL_HIP_CHECK(ctx, hipEventRecord(wk.ev_layers, st));
+  return GIGL_OK;
+}
+
 const float* gigl_nablp_train_plan_loss(gigl_nablp_train_plan* t) { return t ? t->loss : nullptr; }
+
+int32_t gigl_nablp_train_plan_adam_steps(gigl_nablp_train_plan* t, int32_t* out) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  gigl_ctx* ctx = t->ctx;
+  GIGL_REQUIRE(ctx, out, "null output");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  GIGL_HIP_CHECK(ctx, hipMemcpyAsync(out, t->consts + 2, 4, hipMemcpyDeviceToDevice, ctx->stream));
+  return GIGL_OK;
+}
 
 int32_t gigl_nablp_train_plan_set_clip_grad_norm(gigl_nablp_train_plan* t, float max_norm) {
   if (!t) return GIGL_E_INVALID_ARG;

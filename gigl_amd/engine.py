@@ -16,7 +16,8 @@ import torch
 
 from . import _lib
 from ._lib import (DTYPE_F16, DTYPE_F32, GIGL_INVALID, GIGL_META_LEN, GiglTree, GiglUnion, LOC_DEVICE,
-                   LOC_HOST, MODE_FAST, MODE_SPARK_HASH, check)
+                   LOC_HOST, LP_EVAL_BATCHES, LP_EVAL_HITS0, LP_EVAL_LEN, LP_EVAL_LOSS_SUM, LP_EVAL_MRR_SUM,
+                   LP_EVAL_RANK_NODES, MODE_FAST, MODE_SPARK_HASH, check)
 
 
 @dataclass
@@ -1591,7 +1592,7 @@ class NablpTrainPlan:
 
     def _padded(self, main_roots: torch.Tensor, pos_cnt: Optional[torch.Tensor], rn_roots: torch.Tensor):
         T = 1 + self.P
-        assert main_roots.is_cuda and main_roots.dtype == torch.int32 and main_roots.numel() % T == 0
+        assert main_roots.device.type == self.eng.device.type and main_roots.dtype == torch.int32 and main_roots.numel() % T == 0
         na = main_roots.numel() // T
         assert 0 < na <= self.b and (pos_cnt is None or pos_cnt.numel() == na) and rn_roots.numel() <= self.n_rn
         if na < self.b:
@@ -1628,6 +1629,61 @@ class NablpTrainPlan:
             p_(nxt_m) if nxt_m is not None else None, p_(nxt_r) if (nxt_r is not None and self.n_rn) else None,
             int(sampling_seed), int(mode), p_(self.loss)), self.eng._ctx)
         return self.loss
+
+    def adam_steps(self) -> int:
+        """Adam's step counter: the steps applied so far (gigl_nablp_train_plan_adam_steps); synchronises"""
+        out = torch.empty(1, dtype=torch.int32, device=self.eng.device)  # (no fill: it would run on torch's stream)
+        check(self._lib.gigl_nablp_train_plan_adam_steps(self._plan, C.c_void_p(out.data_ptr())), self.eng._ctx)
+        self.eng.synchronize()
+        return int(out.cpu()[0])
+
+    def eval_batch(self, main_roots: torch.Tensor, pos_cnt: torch.Tensor, rn_roots: torch.Tensor, acc: torch.Tensor,
+                   overflow: torch.Tensor, sampling_seed: int = 42, mode: int = MODE_SPARK_HASH,
+                   ks: Sequence[int] = (1, 5, 10, 50, 100, 500)) -> None:
+        """one EVALUATION batch (gigl_nablp_train_plan_eval): the plan's graph part and forward with its current parameters,
+        then the batch's mean loss and the rank metrics of its scores (hits@k for every k of `ks`, MRR) ADDED into acc
+        (float64 device [LP_EVAL_LEN]); a batch beyond the plan's workspace adds 1 to overflow (int32 device [1]) instead.
+        Arguments and padding as step's; trains nothing, moves no optimiser state, keeps an announced batch; enqueued
+        without a host read.  The padded root tensors are kept alive in self._eval_keep until the caller has synchronised."""
+        assert acc.dtype == torch.float64 and acc.numel() >= LP_EVAL_LEN and overflow.dtype == torch.int32
+        main_roots, pos_cnt, rn_roots = self._padded(main_roots, pos_cnt, rn_roots)
+        self._eval_keep = getattr(self, "_eval_keep", [])
+        self._eval_keep.append((main_roots, pos_cnt, rn_roots))
+        ks_arr = (C.c_int32 * len(ks))(*[int(k) for k in ks])
+        p_ = lambda t: C.c_void_p(t.data_ptr())
+        check(self._lib.gigl_nablp_train_plan_eval(
+            self._plan, p_(main_roots), p_(pos_cnt), p_(rn_roots) if self.n_rn else None, int(sampling_seed), int(mode),
+            ks_arr, len(ks), p_(acc), p_(overflow)), self.eng._ctx)
+
+    def evaluate(self, batches, ks: Sequence[int] = (1, 5, 10, 50, 100, 500), sampling_seed: int = 42,
+                 mode: int = MODE_SPARK_HASH) -> dict:
+        """a whole evaluation pass over `batches` = [(main_roots, pos_cnt, rn_roots), ...] -> {"loss": mean over the batches
+        of the batch's mean retrieval loss, "mrr", "hits": [one per k], "batches", "rank_nodes"}: what the trainer's
+        validate() computes with one hit_rate_at_k / mean_reciprocal_rank call per anchor, here one library call per batch
+        and ONE host read per pass.  A pass in which a batch overflowed a regular plan's workspace is redone after grow()
+        (the pass changes nothing, so redoing it is safe); a wide plan's count of such batches is left in
+        self.eval_overflowed.  The final divisions are in double."""
+        batches = list(batches)
+        ks = [int(k) for k in ks]
+        while True:
+            # acc (float64 [LP_EVAL_LEN]) and the overflow count (int32) share one buffer: one copy to the host
+            buf = torch.zeros(LP_EVAL_LEN + 1, dtype=torch.int64, device=self.eng.device)
+            acc, overflow = buf[:LP_EVAL_LEN].view(torch.float64), buf[LP_EVAL_LEN:].view(torch.int32)[:1]
+            self._eval_keep = []
+            for main_roots, pos_cnt, rn_roots in batches:
+                self.eval_batch(main_roots, pos_cnt, rn_roots, acc, overflow, sampling_seed=sampling_seed, mode=mode, ks=ks)
+            host = buf.cpu()  # (synchronises: the roots' buffers are free again)
+            self._eval_keep = []
+            a = host[:LP_EVAL_LEN].view(torch.float64).tolist()
+            self.eval_overflowed = int(host[LP_EVAL_LEN:].view(torch.int32)[0])
+            if self.eval_overflowed and not self.wide:
+                self.grow()
+                self.overflow_redone = getattr(self, "overflow_redone", 0) + 1
+                continue
+            nodes = max(a[LP_EVAL_RANK_NODES], 1.0)
+            return {"loss": a[LP_EVAL_LOSS_SUM] / max(a[LP_EVAL_BATCHES], 1.0), "mrr": a[LP_EVAL_MRR_SUM] / nodes,
+                    "hits": [a[LP_EVAL_HITS0 + i] / nodes for i in range(len(ks))],
+                    "batches": int(a[LP_EVAL_BATCHES]), "rank_nodes": int(a[LP_EVAL_RANK_NODES])}
 
     def grads(self, layer: int):
         """(d loss / d [W_l | W_r], d loss / d bias) of `layer` from the LAST step (gigl_nablp_train_plan_grads)"""

@@ -859,7 +859,13 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         candidate-sampling correction, and an optimiser the plan runs (_train_plan_optim_kwargs: torch.optim.Adam with its
         default betas / eps — with or without gradient-norm clipping (clip_grad_norm) and the ConstantLR warm-up (factor,
         total_iters), both applied inside the plan's Adam launch sequence —; any other scheduler class keeps the autograd
-        loop); trainerArgs train_plan = "off" keeps the autograd loop."""
+        loop); trainerArgs train_plan = "off" keeps the autograd loop.  The plan's random-negative capacity is the larger of
+        the training and the evaluation batch size when validation runs in the plan too (_eval_in_plan), so that evaluation
+        batches fit."""
+        return self._library_plan(cfg)
+
+    def _library_plan(self, cfg: GbmlConfigPbWrapper):
+        """_library_train_plan's choice and construction; eval() makes its plan for the test pass through this too"""
         if str(self._kwargs.get("train_plan", "auto")).lower() == "off" or self._hbm_split(cfg) is None:
             return None
         res = self._resident
@@ -893,13 +899,46 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             return None
         from ._lib import GiglError
         from .engine import NablpTrainPlan
+        n_rn = self.random_negative_sample_batch_size
+        if self._eval_in_plan():
+            n_rn = max(n_rn, self.random_negative_sample_batch_size_for_evaluation)
         try:
             return (NablpTrainPlan if sage else GatEdgeNablpTrainPlan if gat_edge else GatNablpTrainPlan)(
                 res.engine, enc, self.main_sample_batch_size, cfg.num_positive_samples,
-                self.random_negative_sample_batch_size, res.fanouts, temperature=float(tasks[0].loss._temperature or 0.0),
+                n_rn, res.fanouts, temperature=float(tasks[0].loss._temperature or 0.0),
                 remove_accidental_hits=bool(tasks[0].loss._remove_accidental_hits), **optim)
         except (NotImplementedError, GiglError):
             return None
+
+    def _eval_in_plan(self) -> bool:
+        """validation / test passes of a job that has a library plan run inside it (engine.NablpTrainPlan.evaluate: one
+        library call per batch, one host read per pass) unless trainerArgs eval_plan = "off" keeps validate()'s Python loop"""
+        v = str(self._kwargs.get("eval_plan", "auto")).lower()
+        if v not in ("auto", "on", "off"):
+            raise ValueError(f"eval_plan must be auto, on or off (got {v!r})")
+        return v != "off"
+
+    def _eval_root_batches(self, cfg: GbmlConfigPbWrapper, split: str, loop: bool):
+        """the ROOT side of _main_batches on the in-HBM route: (main roots, positives per anchor, anchor ids) per batch of the
+        split, the same anchors and order; loop: forever, like the looped validation iterator"""
+        ids, n_pos = self._hbm_split(cfg)[split]
+        while ids.size:
+            yield from self._resident.nablp_root_batches(ids, n_pos, self.main_sample_batch_size, cfg.num_positive_samples)
+            if not loop:
+                return
+
+    def _validate_with_plan(self, plan, main_roots, rn_roots, num_batches: int) -> Dict[EvalMetricType, Any]:
+        """validate() through the plan: the same batches — the iterators advance exactly as validate()'s zip does, which
+        draws one more pair than it evaluates — and the same metrics dictionary"""
+        from ._lib import MODE_SPARK_HASH
+        batches = []
+        for batch_idx, ((roots, cnt, _), rn) in enumerate(zip(main_roots, rn_roots)):
+            if batch_idx >= num_batches:
+                break
+            batches.append((roots, cnt, rn))
+        m = plan.evaluate(batches, KS_FOR_EVAL, sampling_seed=self._resident.seed, mode=MODE_SPARK_HASH)
+        return {EvalMetricType.mrr: float(m["mrr"]), EvalMetricType.loss: float(m["loss"]),
+                EvalMetricType.hits: [float(h) for h in m["hits"]]}
 
     def _train_with_plan(self, plan, cfg: GbmlConfigPbWrapper, device: torch.device, profiler=None) -> None:
         """train()'s loop with the step inside the library: batches are (roots, positives per anchor) only — the plan
@@ -911,8 +950,14 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         ids, n_pos = self._hbm_split(cfg)["train"]
         main = res.nablp_root_batches(ids, n_pos, self.main_sample_batch_size, cfg.num_positive_samples)
         rn = res.random_negative_root_batches(self.random_negative_sample_batch_size)
-        val_main = self._main_batches(cfg, "val", loop=True)
-        val_rn = self._random_negative_batches(cfg, self.random_negative_sample_batch_size_for_evaluation, split="val")
+        if self._eval_in_plan():  # validation inside the plan: root batches only, no batch graph built
+            val_main = self._eval_root_batches(cfg, "val", loop=True)
+            val_rn = res.random_negative_root_batches(self.random_negative_sample_batch_size_for_evaluation)
+            validate = lambda: self._validate_with_plan(plan, val_main, val_rn, self.num_val_batches)
+        else:
+            val_main = self._main_batches(cfg, "val", loop=True)
+            val_rn = self._random_negative_batches(cfg, self.random_negative_sample_batch_size_for_evaluation, split="val")
+            validate = lambda: self.validate(val_main, val_rn, cfg, device, self.num_val_batches)
         self.model.train()
         self.train_plan_steps = 0
         every = max(self.validate_every_n_batches, 1)
@@ -936,7 +981,7 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
                                          f"{'was grown' if plan.wide else 'did not overflow'}: the batch itself produced it)")
             if batch_index % every == 0:
                 plan.store(inner.encoder)
-                metrics = self.validate(val_main, val_rn, cfg, device, self.num_val_batches)
+                metrics = validate()
                 self.history[-1]["val"] = metrics
                 if self.early_stopper.should_early_stop(metrics, self.model):
                     break
@@ -945,7 +990,7 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
                 profiler.step()
         plan.store(inner.encoder)
         if not self.early_stopper.best_val_model:
-            metrics = self.validate(val_main, val_rn, cfg, device, self.num_val_batches)
+            metrics = validate()
             self.early_stopper.should_early_stop(metrics, self.model)
         assert len(self.early_stopper.best_val_model) > 0
         self.model.load_state_dict(self.early_stopper.best_val_model)
@@ -1031,11 +1076,23 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
 
     def eval(self, gbml_config_pb_wrapper: GbmlConfigPbWrapper, device: torch.device) -> EvalMetricsCollection:
         self._ensure_engine(device)
-        m = self.validate(self._main_batches(gbml_config_pb_wrapper, "test", loop=False),
-                          self._random_negative_batches(gbml_config_pb_wrapper,
-                                                        self.random_negative_sample_batch_size_for_evaluation,
-                                                        split="test"),
-                          gbml_config_pb_wrapper, device, self.num_test_batches)
+        cfg = gbml_config_pb_wrapper
+        # the test pass inside a plan made for it (its parameters are the model's, copied at creation) wherever training
+        # would run in one; every other job keeps validate()'s loop
+        plan = self._library_plan(cfg) if self._eval_in_plan() else None
+        if plan is not None:
+            try:
+                m = self._validate_with_plan(
+                    plan, self._eval_root_batches(cfg, "test", loop=False),
+                    self._resident.random_negative_root_batches(self.random_negative_sample_batch_size_for_evaluation),
+                    self.num_test_batches)
+            finally:
+                plan.close()
+        else:
+            m = self.validate(self._main_batches(cfg, "test", loop=False),
+                              self._random_negative_batches(cfg, self.random_negative_sample_batch_size_for_evaluation,
+                                                            split="test"),
+                              cfg, device, self.num_test_batches)
         hits = [EvalMetric(name=f"HitRate_at_{k}", value=rate) for k, rate in zip(KS_FOR_EVAL, m[EvalMetricType.hits])]
         return EvalMetricsCollection(metrics=[
             EvalMetric.from_eval_metric_type(EvalMetricType.mrr, m[EvalMetricType.mrr]),

@@ -1064,6 +1064,31 @@ int32_t gigl_retrieval_loss_backward(gigl_ctx* ctx, const float* scores, int64_t
                                      const int64_t* cand_ids, const float* row_lse, const float* grad_loss,
                                      float* dscores);
 
+/* ---- rank metrics of a score matrix: MRR and hits@k of every anchor's positives among the random negatives, one wave per
+ *      anchor, summed on the device.  Replaces hit_rate_at_k / mean_reciprocal_rank (python/gigl/src/common/utils/
+ *      eval_metrics.py:6-73) as the trainer's validate() calls them once per anchor (node_anchor_based_link_prediction_
+ *      modeling_task_spec.py:454-571) — about 18 small launches and two host synchronisations per anchor.
+ * scores: DEVICE fp32, rows `ld` floats apart; row i*P + j is anchor i's query against every candidate, positive j's score
+ *   the entry at column i*P + j (the training plan's layout), the negatives columns neg_col0 .. neg_col0 + n_neg - 1, column
+ *   c of them taking part when neg_valid == NULL or neg_valid[c] != 0 (DEVICE int32 [n_neg]).  pos_cnt: DEVICE int32 [b].
+ * For anchor i with p = min(pos_cnt[i], P) > 0: rank_j = 1 + #{valid negatives scoring STRICTLY higher than positive j} (a
+ *   tie counts for the positive); acc[GIGL_LP_EVAL_MRR_SUM] += mean_j 1 / rank_j, acc[GIGL_LP_EVAL_HITS0 + k] += mean_j
+ *   [rank_j <= ks[k]], acc[GIGL_LP_EVAL_RANK_NODES] += 1; an anchor with p <= 0 adds nothing.  Only those words of acc
+ *   (DEVICE double [GIGL_LP_EVAL_LEN]) are touched, and they are ADDED to: the caller zeroes acc, issues any number of
+ *   calls and reads it once.  Per-anchor values are added in a fixed order in fp64, without atomics: two runs give the
+ *   same bits.  ks: HOST int32 [n_ks], n_ks in [1, GIGL_LP_EVAL_MAX_KS], every k >= 1 (GIGL_E_INVALID_ARG otherwise).
+ *   Enqueued on the ctx stream, no synchronisation. */
+#define GIGL_LP_EVAL_LOSS_SUM 0   /* sum over calls of the batch's mean retrieval loss */
+#define GIGL_LP_EVAL_BATCHES 1    /* calls that contributed */
+#define GIGL_LP_EVAL_MRR_SUM 2
+#define GIGL_LP_EVAL_RANK_NODES 3 /* anchors with >= 1 positive */
+#define GIGL_LP_EVAL_HITS0 4      /* + index into ks */
+#define GIGL_LP_EVAL_MAX_KS 8
+#define GIGL_LP_EVAL_LEN 16       /* doubles */
+int32_t gigl_lp_rank_metrics(gigl_ctx* ctx, const float* scores, int64_t ld, int32_t b, int32_t P, const int32_t* pos_cnt,
+                             int32_t n_neg, int32_t neg_col0, const int32_t* neg_valid /* may be NULL */,
+                             const int32_t* ks /* HOST */, int32_t n_ks, double* acc /* DEVICE [GIGL_LP_EVAL_LEN], += */);
+
 /* ---- one-call batch pipeline: sample -> union -> GraphSAGE forward -> one output row per root.
  *      Replaces `infer_batch` of the reference's task specs for a RootedNodeNeighborhood batch
  *      (python/gigl/src/common/modeling_task_specs/node_anchor_based_link_prediction_modeling_task_spec.py:626-655,
@@ -1321,6 +1346,29 @@ int32_t gigl_nablp_train_plan_grad_norm(gigl_nablp_train_plan* plan, float* out2
 /* the LAST step's parameter gradients of layer `layer` (the two encodes' added): gw DEVICE [dims[l+1]][2 dims[l]] (= d loss
  * / d [W_l | W_r]), gb DEVICE [dims[l+1]] (may be NULL) — what the step's Adam update consumed; for gradient parity tests */
 int32_t gigl_nablp_train_plan_grads(gigl_nablp_train_plan* plan, int32_t layer, float* gw, float* gb);
+/* One EVALUATION batch per call, for every kind of link-prediction plan (GraphSAGE, GAT, GAT with edge features).  Replaces
+ * the loop body of NodeAnchorBasedLinkPredictionModelingTaskSpec.validate (node_anchor_based_link_prediction_modeling_
+ * task_spec.py:454-571: infer_task_inputs, the tasks' loss, then hit_rate_at_k and mean_reciprocal_rank once per anchor).
+ * Runs the plan's own graph part and FORWARD — sample + union of both root sets, both encodes with the plan's current
+ * parameters, the head's operands, the scores, the loss rows — then adds the batch's mean retrieval loss to
+ * acc[GIGL_LP_EVAL_LOSS_SUM], 1 to acc[GIGL_LP_EVAL_BATCHES] and the rank metrics of the scores (gigl_lp_rank_metrics over the
+ * random negatives' columns; absent anchors / negatives masked exactly as in _step) to the other words.  acc: DEVICE double
+ * [GIGL_LP_EVAL_LEN], added to; everything is enqueued on the ctx's stream, nothing synchronises (but the first calls of a
+ * plan, as for _step): a whole validation pass needs one host read.  A batch that did not fit the plan's workspace adds
+ * nothing to acc and 1 to *overflow_acc (DEVICE int32, caller-zeroed).  Arguments as for _step; ks as for
+ * gigl_lp_rank_metrics; GIGL_MODE_REPLACE returns GIGL_E_UNSUPPORTED.
+ * CONTRACT: an evaluation call changes neither the parameters, nor Adam's moments and step counter, nor the clip and
+ * learning-rate-schedule state; it runs in the workspace that holds no announced batch (after the layers part that last read
+ * it), so the graph part of a batch the previous _step2 announced stays valid and is still recognised; its graph part is
+ * replayed from a captured graph of its own and its layers part is launched eagerly, so the captured training graphs stay
+ * valid.  It overwrites the plan's forward state and loss rows (not the loss words of _loss): gigl_nablp_train_plan_grads,
+ * gigl_gat_nablp_train_plan_grads / _edge_grads and _grad_norm after an evaluation call refer to NO step. */
+int32_t gigl_nablp_train_plan_eval(gigl_nablp_train_plan* plan, const uint32_t* main_roots, const int32_t* pos_cnt,
+                                   const uint32_t* rn_roots, int32_t sampling_seed, int32_t mode,
+                                   const int32_t* ks /* HOST */, int32_t n_ks, double* acc, int32_t* overflow_acc);
+/* Adam's step counter (the steps that were applied: a failed batch does not move it, an evaluation call never does) -> *out
+ * (DEVICE int32), copied on the ctx stream: for tests of those two statements */
+int32_t gigl_nablp_train_plan_adam_steps(gigl_nablp_train_plan* plan, int32_t* out);
 /* as gigl_sage_train_plan_adopt, for the link-prediction plans (GraphSAGE and GAT encoders alike) */
 int32_t gigl_nablp_train_plan_adopt(gigl_nablp_train_plan* dst, gigl_nablp_train_plan* src);
 /* moments of one parameter tensor of a link-prediction plan: GraphSAGE encoder: index = 2 * layer (fused weight) | 2 * layer
