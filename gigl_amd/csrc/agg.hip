@@ -1507,12 +1507,15 @@ __global__ __launch_bounds__(256) void fused2_scale_kernel(const float* __restri
 // Half-split scales of a layer >= 1 (round 5): its operand [reduce(h) | h] is made of the previous layer's outputs h =
 // act(a . W^T + b), bounded by K max|W| max|a| + max|b| — and max|a| < 2^15 / s_a, max|W| < 2^15 / s_w are what the
 // previous layer's own scales hs_prev = {s_a, s_w, ..} say.  hs_out = {s_h, s_w', 1 / (s_h s_w')}: s_h brings that bound
-// under 2^14 (a mean / max of rows stays inside it; a SUM over up to `fan` rows: the bound times fan), s_w' the largest
+// under 2^14 (a mean / max of rows stays inside it; a SUM does not — a union row merges the samples of every occurrence of
+// its node, up to the node's whole in-row, whatever the fan-outs: the summed half's largest magnitude is MEASURED on the
+// operand the gather wrote, gigl_tiled_absmax into *sum_max, and joins the bound; the word is cleared here), s_w' the largest
 // |w'| of THIS layer's weights into [2^14, 2^15).  Per run (the weights are read as they are now); hs_out: 8 floats,
 // zero-initialised once by the caller.
 __global__ __launch_bounds__(256) void hs_chain_kernel(const float* __restrict__ hs_prev, const float* __restrict__ b_prev,
-                                                       int n_b, int k_prev, float fan, const float* __restrict__ w,
-                                                       int64_t n_w, float* __restrict__ hs_out) {
+                                                       int n_b, int k_prev, uint32_t* __restrict__ sum_max,
+                                                       const float* __restrict__ w, int64_t n_w,
+                                                       float* __restrict__ hs_out) {
   // (a few small workgroups + a ticket, as hs_scale_kernel: hs_out[4], [5] = running maxima, [6] = ticket, zero between runs)
   __shared__ float s_m[2][4];
   const int tid = threadIdx.x;
@@ -1557,7 +1560,8 @@ __global__ __launch_bounds__(256) void hs_chain_kernel(const float* __restrict__
       const float b = __uint_as_float(atomicExch(acc, 0u)), wm = __uint_as_float(atomicExch(acc + 1, 0u));
       acc[2] = 0u;
       const float inf = __uint_as_float(0x7F800000u);
-      float bound = ((float)k_prev * 1073741824.f * (1.f / hs_prev[0]) * (1.f / hs_prev[1]) + b) * fan;
+      float bound = (float)k_prev * 1073741824.f * (1.f / hs_prev[0]) * (1.f / hs_prev[1]) + b;
+      if (sum_max) bound = fmaxf(bound, __uint_as_float(atomicExch(sum_max, 0u)));  // (the summed half as the gather wrote it)
       if (!(bound > 0.f) || !(bound < inf)) bound = 1.f;
       const float s_h = hs_pow2_scale(bound) * 0.5f;
       const float s_w = (wm > 0.f && wm < inf) ? hs_pow2_scale(wm) : 1.f;
@@ -4660,8 +4664,11 @@ int32_t gigl_feat_half_split_scale(gigl_ctx* ctx, gigl_feat* feat, float fan, fl
 // into the scales and clears maximum and ticket for the next run.  (As one workgroup walking all the weights the kernel
 // took ~100 us next to the other streams' kernels: a serial loop of 50 loads per thread under contention.)
 // hs: [0..2] = {s_a, s_w, 1 / (s_a s_w)}, [4] = running maximum (bits), [5] = ticket — both zero between runs.
+// a_max (null: s_a as given): the operand's summed half was measured (gigl_tiled_absmax); s_a then follows the larger of
+// that and self_max, the largest magnitude of the self half — the word is cleared for the next run.
 __global__ __launch_bounds__(256) void hs_scale_kernel(const float* __restrict__ w, int64_t n, float s_a,
-                                                       float* __restrict__ hs) {
+                                                       float* __restrict__ hs, uint32_t* __restrict__ a_max = nullptr,
+                                                       float self_max = 0.f) {
   __shared__ float s_m[4];
   float m = 0.f;
   const float4* w4 = reinterpret_cast<const float4*>(w);
@@ -4689,6 +4696,10 @@ __global__ __launch_bounds__(256) void hs_scale_kernel(const float* __restrict__
       const float mm = __uint_as_float(atomicExch(acc, 0u));
       acc[1] = 0u;
       const float s_w = (mm > 0.f && mm < __uint_as_float(0x7F800000u)) ? hs_pow2_scale(mm) : 1.f;
+      if (a_max) {
+        const float top = fmaxf(__uint_as_float(atomicExch(a_max, 0u)), self_max);
+        if (top > 0.f && top < __uint_as_float(0x7F800000u)) s_a = hs_pow2_scale(top);
+      }
       hs[0] = s_a;
       hs[1] = s_w;
       hs[2] = (1.f / s_a) * (1.f / s_w);
@@ -4696,10 +4707,46 @@ __global__ __launch_bounds__(256) void hs_scale_kernel(const float* __restrict__
   }
 }
 
-int32_t gigl_hs_scale_update(gigl_ctx* ctx, const float* w, int64_t n, float s_a, float* hs_dev) {
+int32_t gigl_hs_scale_update(gigl_ctx* ctx, const float* w, int64_t n, float s_a, float* hs_dev, uint32_t* a_max,
+                             float self_max) {
   int64_t wgs = (n / 4 + 255) / 256;  // one float4 per thread where the weights allow it
   wgs = wgs < 1 ? 1 : (wgs > 64 ? 64 : wgs);
-  hipLaunchKernelGGL(hs_scale_kernel, dim3((unsigned)wgs), dim3(256), 0, ctx->stream, w, n, s_a, hs_dev);
+  hipLaunchKernelGGL(hs_scale_kernel, dim3((unsigned)wgs), dim3(256), 0, ctx->stream, w, n, s_a, hs_dev, a_max, self_max);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+// Largest |element| of the reduced half the gather wrote in the projection's tiled layout ([row tile of 128][chunk of 32
+// k][128][32]; rows < *n_rows and k < d only: the rest of a tile is not written), folded into *out_bits with atomicMax
+// (non-negative floats order like their bits; a NaN counts as +inf).  One workgroup per (row tile, chunk).
+__global__ __launch_bounds__(256) void tiled_absmax_kernel(const float* __restrict__ a, const int32_t* __restrict__ n_rows,
+                                                           int d, int nkc, uint32_t* __restrict__ out_bits) {
+  const int M = *n_rows;
+  const int tm = blockIdx.x / nkc, c = blockIdx.x - tm * nkc;
+  if (tm * 128 >= M) return;
+  const float* base = a + ((int64_t)tm * nkc + c) * 4096;
+  float m = 0.f;
+  bool bad = false;
+  for (int i = threadIdx.x; i < 4096; i += 256) {
+    const int r = i >> 5, k = c * 32 + (i & 31);
+    if (tm * 128 + r < M && k < d) {
+      const float v = fabsf(base[i]);
+      bad |= !(v == v);
+      m = fmaxf(m, v);
+    }
+  }
+  if (bad) m = __uint_as_float(0x7F800000u);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  if ((threadIdx.x & 63) == 0) atomicMax(out_bits, __float_as_uint(m));
+}
+
+int32_t gigl_tiled_absmax(gigl_ctx* ctx, const float* a_tiled, const int32_t* n_rows, int64_t rows_cap, int32_t d,
+                          uint32_t* out_bits) {
+  if (rows_cap == 0) return GIGL_OK;
+  const int nkc = (d + 31) / 32;
+  hipLaunchKernelGGL(tiled_absmax_kernel, dim3((unsigned)(((rows_cap + 127) / 128) * nkc)), dim3(256), 0, ctx->stream, a_tiled,
+                     n_rows, d, nkc, out_bits);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -4801,12 +4848,12 @@ int32_t gigl_fused2_prepare(gigl_ctx* ctx, const float* hs_dev, const float* b1,
   return GIGL_OK;
 }
 
-int32_t gigl_hs_chain_update(gigl_ctx* ctx, const float* hs_prev, const float* b_prev, int32_t n_b, int32_t k_prev, float fan,
-                             const float* w, int64_t n_w, float* hs_out) {
+int32_t gigl_hs_chain_update(gigl_ctx* ctx, const float* hs_prev, const float* b_prev, int32_t n_b, int32_t k_prev,
+                             uint32_t* sum_max, const float* w, int64_t n_w, float* hs_out) {
   int64_t wgs = (n_w / 4 + 255) / 256;
   wgs = wgs < 1 ? 1 : (wgs > 64 ? 64 : wgs);
-  hipLaunchKernelGGL(hs_chain_kernel, dim3((unsigned)wgs), dim3(256), 0, ctx->stream, hs_prev, b_prev, n_b, k_prev, fan, w, n_w,
-                     hs_out);
+  hipLaunchKernelGGL(hs_chain_kernel, dim3((unsigned)wgs), dim3(256), 0, ctx->stream, hs_prev, b_prev, n_b, k_prev, sum_max, w,
+                     n_w, hs_out);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }

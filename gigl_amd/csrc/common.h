@@ -187,7 +187,13 @@ int32_t gigl_linear_tiled(gigl_ctx* ctx, const float* a_tiled, const float* w, c
 int32_t gigl_feat_half_split_scale(gigl_ctx* ctx, gigl_feat* feat, float fan, float* s_a);
 // hs_dev[0..2] = {s_a, s_w, 1 / (s_a s_w)} with s_w from the largest |w[i]| as the n weights are when the launch runs —
 // one small launch on the ctx's stream, no synchronisation, may be captured
-int32_t gigl_hs_scale_update(gigl_ctx* ctx, const float* w, int64_t n, float s_a, float* hs_dev);
+// a_max (optional, device word, zero between runs): the operand's summed half measured by gigl_tiled_absmax on the same
+// stream — s_a then follows max(*a_max, self_max) instead of the value given, and the word is cleared
+int32_t gigl_hs_scale_update(gigl_ctx* ctx, const float* w, int64_t n, float s_a, float* hs_dev, uint32_t* a_max = nullptr,
+                             float self_max = 0.f);
+// *out_bits = max(*out_bits, largest |element| of rows < *n_rows, columns < d of a tiled reduced half) as float bits
+int32_t gigl_tiled_absmax(gigl_ctx* ctx, const float* a_tiled, const int32_t* n_rows, int64_t rows_cap, int32_t d,
+                          uint32_t* out_bits);
 // the first GAT layer's edge terms (the one-call plan over a graph with edge features; semantics of gigl_gat_aggregate_edge):
 // the edge stored at col position p carries row eid[p] of `table` ([n_edges][edge_dim] fp32, read in place); the logits gain
 // <e, att_edge_folded[h]>, the added self loop carries the mean attribute of the row's other in-edges; w_edge_msg != NULL
@@ -249,9 +255,10 @@ int32_t gigl_gat_aggregate_backward_indexed(gigl_ctx* ctx, const float* h, const
 // gigl_hs_scale_update on the same stream) finds the second product's scales and lays out W1's and W2's fp16 images in
 // w2h (gigl_fused2_w2h_bytes).  gigl_fused2_shape_ok: hidden width 256, 2 * out <= row floats, d0 % 4 == 0.
 // half-split scales of a layer >= 1 from the previous layer's (its outputs are bounded by K max|W| max|a| + max|b|): hs_out
-// = {s_h, s_w, 1 / (s_h s_w)} for gigl_linear_tiled(.., hs_scale); fan > 1 under a sum reduction.  Per run, on the stream.
-int32_t gigl_hs_chain_update(gigl_ctx* ctx, const float* hs_prev, const float* b_prev, int32_t n_b, int32_t k_prev, float fan,
-                             const float* w, int64_t n_w, float* hs_out);
+// = {s_h, s_w, 1 / (s_h s_w)} for gigl_linear_tiled(.., hs_scale); sum_max (a sum reduction; else null): the summed half's
+// measured largest magnitude (gigl_tiled_absmax), which joins the bound and is cleared.  Per run, on the stream.
+int32_t gigl_hs_chain_update(gigl_ctx* ctx, const float* hs_prev, const float* b_prev, int32_t n_b, int32_t k_prev,
+                             uint32_t* sum_max, const float* w, int64_t n_w, float* hs_out);
 bool gigl_fused2_shape_ok(int32_t d0, int32_t hid, int32_t n_out);
 int64_t gigl_fused2_w2h_bytes(int32_t k1);
 int32_t gigl_fused2_row_floats();

@@ -418,17 +418,27 @@ int32_t enqueue_stage(gigl_sage_plan* p, int s, const uint32_t* roots, int32_t s
   const int act = (l < L - 1 || p->act_last) ? 1 : 0;
   const float* hs_scale = nullptr;
   if (l == 0 && p->hs0 && p->tiled) {  // the weights' scale follows the weights as they are now (training rewrites them in place)
-    const int32_t rc = gigl_hs_scale_update(ctx, p->w[0], (int64_t)p->dims[1] * 2 * d, p->hs_sa, p->hs_dev);
+    uint32_t* a_max = nullptr;  // a sum: the scale follows the operand as the gather wrote it (hs_dev[7]: zero between runs)
+    if (p->aggr == GIGL_AGGR_SUM) {
+      a_max = reinterpret_cast<uint32_t*>(p->hs_dev + 7);
+      const int32_t rc_m = gigl_tiled_absmax(ctx, p->abuf, n_rows, rows_cap, two_src ? d : 2 * d, a_max);
+      if (rc_m != GIGL_OK) return rc_m;
+    }
+    const int32_t rc = gigl_hs_scale_update(ctx, p->w[0], (int64_t)p->dims[1] * 2 * d, p->hs_sa, p->hs_dev, a_max,
+                                            p->feat->absmax > 0.f ? p->feat->absmax : 0.f);
     if (rc != GIGL_OK) return rc;
     hs_scale = p->hs_dev;
   }
   if (l >= 1 && two_src && p->hs0 && !p->proj && p->hs_layer[l] && hs_layers_on()) {
     // half split for a layer >= 1: three fp16 products instead of six bf16 ones
     const float* prev = l == 1 ? p->hs_dev : p->hs_layer[l - 1];
-    float fan = 1.f;
-    if (p->aggr == GIGL_AGGR_SUM)
-      for (int k = 0; k < p->hops; ++k) fan = (float)p->fanouts[k] > fan ? (float)p->fanouts[k] : fan;
-    int32_t rc = gigl_hs_chain_update(ctx, prev, p->bias[l - 1], p->dims[l], 2 * p->dims[l - 1], fan, p->w[l],
+    uint32_t* sum_max = nullptr;  // (a sum of hidden rows: measured, hs_layer[l][7] — zero between runs)
+    if (p->aggr == GIGL_AGGR_SUM) {
+      sum_max = reinterpret_cast<uint32_t*>(p->hs_layer[l] + 7);
+      const int32_t rc_m = gigl_tiled_absmax(ctx, p->abuf, n_rows, rows_cap, d, sum_max);
+      if (rc_m != GIGL_OK) return rc_m;
+    }
+    int32_t rc = gigl_hs_chain_update(ctx, prev, p->bias[l - 1], p->dims[l], 2 * p->dims[l - 1], sum_max, p->w[l],
                                       (int64_t)p->dims[l + 1] * 2 * d, p->hs_layer[l]);
     if (rc != GIGL_OK) return rc;
     return gigl_linear_tiled(ctx, p->abuf, p->w[l], p->bias[l], n_rows, rows_cap, 2 * d, p->dims[l + 1], act,
@@ -1107,9 +1117,10 @@ static int32_t plan_refresh_half_split(gigl_sage_plan* p) {
   const bool gat = p->kind == 1 && p->gat_scratch;
   const bool sage = p->kind == 0 && p->tiled && p->abuf;  // (SAGE plans own abuf)
   if ((gat || sage) && p->feat && p->w[0] && p->hs_dev) {
-    float fan = 1.f;  // (a sum over up to `fan-out` rows; mean, max and softmax weights stay inside the table's range)
-    if (sage && p->aggr == GIGL_AGGR_SUM)
-      for (int k = 0; k < p->hops; ++k) fan = (float)p->fanouts[k] > fan ? (float)p->fanouts[k] : fan;
+    // (mean, max and softmax weights stay inside the table's range.  A SUM does not, and no fan-out bounds it: a union row
+    // merges the samples of every occurrence of its node — each sampled with its own hash key — up to the node's whole
+    // in-row.  The summed half is measured on the device at every run instead: gigl_tiled_absmax in enqueue_stage.)
+    const float fan = 1.f;
     const int32_t rc = gigl_feat_half_split_scale(p->ctx, p->feat, fan, &p->hs_sa);
     if (rc != GIGL_OK) return rc;
     p->hs0 = p->hs_sa > 0.f;
