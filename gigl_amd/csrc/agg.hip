@@ -13,7 +13,9 @@
 //              lane (col -> gather_ids: two dependent loads for the whole row instead of per edge);
 //              then LPR lanes stream each source row with 16-byte loads, G = 64/LPR source rows per
 //              wave-instruction and 4 instructions in flight; fp32 accumulate; the destination's own
-//              row is copied alongside, producing the [mean | self] operand of the projection.
+//              row is copied alongside, producing the [mean | self] operand of the projection.  A wave's
+//              rows form a software pipeline: the next row's indices and the bounds of the row after it
+//              are requested ahead of the current row's source rows (one memory round trip per row).
 // linear       exact-fp32 MFMA (v_mfma_f32_32x32x2_f32): every wave owns a 32 x 32*NT output tile and
 //              streams A / W rows straight from global (L2-resident W) as float4, register
 //              double-buffered one K-step (8) ahead.  K is consumed 8 at a time: lane (r, h) loads
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(256) void gather_mean_kernel(const T* __restrict__ 
   const int lane = threadIdx.x & 63;
   const int sub = lane / LPR;  // which source row of the instruction
   const int sl = lane % LPR;   // lane within the row
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));  // wave-uniform
   const int n_rows = *n_rows_dev;
   // rows >= n_local hold GLOBAL source ids already (leaf-global union): no gather_ids translation for them
   const int n_local = n_local_dev ? *n_local_dev : 0x7FFFFFFF;
@@ -162,20 +164,17 @@ __global__ __launch_bounds__(256) void gather_mean_kernel(const T* __restrict__ 
     }
     return c;
   };
-  // lane `idx` of group `sub`'s LPR lanes (grp), or entry idx + sub of the wave's index vector (wave-wide rows).
+  // entry idx + sub of the wave's index vector
   // (v_readlane + select instead of the ds_bpermute behind __shfl was measured for G <= 2 — rmat-shard 12.8 -> 16.2 us /
   // step, products 9.56 -> 9.69: the scalar round trip stalls the loads it feeds; dropped)
-  auto pick = [&](int v, int idx, bool grp) -> int {
-    return grp ? __shfl(v, (lane & ~(LPR - 1)) + idx, 64) : __shfl(v, (idx + sub) & 63, 64);
-  };
-  // write the finished row i: `acc` holds the reduction in the lanes sl of group `sub` (grp: every group owns its own
-  // row; else the whole wave owns row i and group 0 holds the total)
-  auto emit = [&](int i, int m, float4_t (&acc)[VPL], bool grp) {
-    const int self = gather_ids ? (int)gather_ids[i] : i;  // (PEER: the destination's global id)
-    const bool writer = grp || sub == 0;
+  auto pick = [&](int v, int idx) -> int { return __shfl(v, (idx + sub) & 63, 64); };
+  // write the finished row i (`self`: its source index, read by the paths that use the self row): the whole wave owns
+  // the row and group 0 holds the total
+  auto emit = [&](int i, int m, float4_t (&acc)[VPL], int self) {
+    const bool writer = sub == 0;
     // mean = sum / deg (a true division, like torch's scatter-mean), 0 for an empty row
     const float dv = (OP == GIGL_AGGR_MEAN && m > 0) ? (float)m : 1.f;
-    const int c0 = (grp ? sl : lane) * 4, cstep = (grp ? LPR : 64) * 4;  // the self-row copy's lanes
+    const int c0 = lane * 4, cstep = 64 * 4;  // the self-row copy's lanes
     if constexpr (PROJ) {
       if (writer) {
         // (self_ids: the destination's W_r row sits at row self_ids[i] of self_src — the sharded plan's second receive
@@ -201,7 +200,6 @@ __global__ __launch_bounds__(256) void gather_mean_kernel(const T* __restrict__ 
       }
       return;
     }
-    const T* ps = row_of(self);
     if (tiled_nkc) {  // the projection's operand layout: [row tile of 128][K chunk of 32][128 rows][32 floats]
       float* tbase = out + ((int64_t)(i >> 7) * tiled_nkc) * 4096 + (i & 127) * 32;
       if (writer) {
@@ -215,13 +213,16 @@ __global__ __launch_bounds__(256) void gather_mean_kernel(const T* __restrict__ 
       }
       // (no_self: the projection reads the self half of its operand straight from the source rows — two-source A
       // tile, linear_split_kernel<.., SELF> — so it is neither read nor written here)
-      if (!no_self)
+      if (!no_self) {
+        const T* ps = row_of(self);
         for (int el = c0; el < d; el += cstep) {
           const int k = d + el;
           *reinterpret_cast<float4_t*>(tbase + (int64_t)(k >> 5) * 4096 + (k & 31)) = RowLoader<T>::load4(ps, el);
         }
+      }
       return;
     }
+    const T* ps = row_of(self);
     float* o = out + (int64_t)i * 2 * d;
     if (writer) {
 #pragma unroll
@@ -233,36 +234,38 @@ __global__ __launch_bounds__(256) void gather_mean_kernel(const T* __restrict__ 
     for (int el = c0; el < d; el += cstep)  // self row copy
       *reinterpret_cast<float4_t*>(o + d + el) = RowLoader<T>::load4(ps, el);
   };
-  // one destination row on the whole wave: G source rows per instruction, four instructions in flight
-  auto wave_row = [&](int i) {
-    const int e0 = rowptr[i], m = rowend[i] - e0;
+  // the 64 entries `my` of a row (mm of them edges) into acc: G source rows per instruction, four instructions in flight
+  auto chunk = [&](int my, int mm, float4_t (&acc)[VPL]) {
+    for (int e = 0; e < mm; e += 4 * G) {  // wave-uniform trip count (the broadcasts need every lane)
+      const int ea = e + sub, eb = ea + G, ec = ea + 2 * G, ed = ea + 3 * G;
+      const int ja = pick(my, e), jb = pick(my, (e + G) & 63), jc = pick(my, (e + 2 * G) & 63), jd = pick(my, (e + 3 * G) & 63);
+      const T* pa = row_of(ja);
+      const T* pb = row_of(jb);
+      const T* pc = row_of(jc);
+      const T* pd = row_of(jd);
+#pragma unroll
+      for (int v = 0; v < VPL; ++v) {
+        const int el = (v * LPR + sl) * 4;
+        if (el < d) {
+          float4_t a = ea < mm ? RowLoader<T>::load4(pa, el) : zero4;
+          float4_t b = eb < mm ? RowLoader<T>::load4(pb, el) : zero4;
+          float4_t c = ec < mm ? RowLoader<T>::load4(pc, el) : zero4;
+          float4_t dd = ed < mm ? RowLoader<T>::load4(pd, el) : zero4;
+          acc[v] = aggr_combine<OP>(acc[v], aggr_combine<OP>(aggr_combine<OP>(a, b), aggr_combine<OP>(c, dd)));
+        }
+      }
+    }
+  };
+  // one destination row on the whole wave.  `my`: its first 64 entries, translated, one per lane (a lane past the row's
+  // end repeats the last entry; it is never broadcast).  `summed` runs between the row's sum and its stores
+  auto wave_row = [&](int i, int e0, int m, int my, int self, auto&& summed) {
     float4_t acc[VPL];
 #pragma unroll
     for (int v = 0; v < VPL; ++v) acc[v] = zero4;
-    for (int c0 = 0; c0 < m; c0 += 64) {
+    if (m > 0) chunk(my, min(64, m), acc);
+    for (int c0 = 64; c0 < m; c0 += 64) {  // a row past 64 edges: the further entries on demand
       const int mm = min(64, m - c0);
-      int my = 0;
-      if (lane < mm) my = translate(col[e0 + c0 + lane], i);
-      for (int e = 0; e < mm; e += 4 * G) {  // wave-uniform trip count (the broadcasts need every lane)
-        const int ea = e + sub, eb = ea + G, ec = ea + 2 * G, ed = ea + 3 * G;
-        const int ja = pick(my, e, false), jb = pick(my, (e + G) & 63, false), jc = pick(my, (e + 2 * G) & 63, false),
-                  jd = pick(my, (e + 3 * G) & 63, false);
-        const T* pa = row_of(ja);
-        const T* pb = row_of(jb);
-        const T* pc = row_of(jc);
-        const T* pd = row_of(jd);
-#pragma unroll
-        for (int v = 0; v < VPL; ++v) {
-          const int el = (v * LPR + sl) * 4;
-          if (el < d) {
-            float4_t a = ea < mm ? RowLoader<T>::load4(pa, el) : zero4;
-            float4_t b = eb < mm ? RowLoader<T>::load4(pb, el) : zero4;
-            float4_t c = ec < mm ? RowLoader<T>::load4(pc, el) : zero4;
-            float4_t dd = ed < mm ? RowLoader<T>::load4(pd, el) : zero4;
-            acc[v] = aggr_combine<OP>(acc[v], aggr_combine<OP>(aggr_combine<OP>(a, b), aggr_combine<OP>(c, dd)));
-          }
-        }
-      }
+      chunk(translate(col[e0 + c0 + min(lane, mm - 1)], i), mm, acc);
     }
     // combine the G partial sums (lanes sl, sl+LPR, ...)
 #pragma unroll
@@ -274,66 +277,64 @@ __global__ __launch_bounds__(256) void gather_mean_kernel(const T* __restrict__ 
         acc[v] = aggr_combine<OP>(acc[v], o4);
       }
     }
-    emit(i, m, acc, false);
+    summed();
+    emit(i, m, acc, self);
   };
 
-  // (GROUP_ROWS: measured on the MI355X — products-shaped 9.56 -> 9.73 us / step, rmat-shard 12.8 -> 14.3: the kernel
-  // already moves its bytes at ~80 % of the HBM peak with a wave per row, more rows in flight per wave buy nothing and
-  // the longer rows' second pass costs; kept for reference, compiled out)
-  constexpr bool GROUP_ROWS = false;
-  if constexpr (G == 1 || !GROUP_ROWS) {
-    for (int i = wave; i < n_rows; i += waves_total) wave_row(i);
-  } else {
-    // Rows narrower than a wave (LPR < 64 lanes cover a source row): a wave takes G consecutive destination rows.  The
-    // SHORT ones (<= SHORT_MAX in-edges — most rows of a sampled batch: a hop-1 node keeps at most f1 in-edges, on a
-    // power-law graph usually a handful) are reduced side by side, one per lane group, four source rows in flight per
-    // group: G times the rows in flight of a wave per row, and no cross-group combine.  Longer rows of the set then take
-    // the whole wave one after another.  Which path a row takes depends on its own length only, so its bits never
-    // depend on its neighbours (groups of batches == single batches).
-    constexpr int SHORT_MAX = LPR < 16 ? LPR : 16;
-    for (int base = wave * G; base < n_rows; base += waves_total * G) {
-      const int ri = base + sub;
-      int e0 = 0, m = 0;
-      if (ri < n_rows) {
-        e0 = rowptr[ri];
-        m = rowend[ri] - e0;
-      }
-      const bool shortrow = ri < n_rows && m <= SHORT_MAX;
-      const int ms = shortrow ? m : 0;
-      int my = 0;
-      if (sl < ms) my = translate(col[e0 + sl], ri);
-      int mmax = 0;  // wave-uniform trip count: the longest short row of the set
-#pragma unroll
-      for (int g = 0; g < G; ++g) mmax = max(mmax, __builtin_amdgcn_readlane(ms, g * LPR));
-      float4_t acc[VPL];
-#pragma unroll
-      for (int v = 0; v < VPL; ++v) acc[v] = zero4;
-      for (int e = 0; e < mmax; e += 4) {
-        const int ja = pick(my, e, true), jb = pick(my, e + 1, true), jc = pick(my, e + 2, true),
-                  jd = pick(my, e + 3, true);
-        const T* pa = row_of(ja);
-        const T* pb = row_of(jb);
-        const T* pc = row_of(jc);
-        const T* pd = row_of(jd);
-#pragma unroll
-        for (int v = 0; v < VPL; ++v) {
-          const int el = (v * LPR + sl) * 4;
-          if (el < d) {
-            float4_t a = e < ms ? RowLoader<T>::load4(pa, el) : zero4;
-            float4_t b = e + 1 < ms ? RowLoader<T>::load4(pb, el) : zero4;
-            float4_t c = e + 2 < ms ? RowLoader<T>::load4(pc, el) : zero4;
-            float4_t dd = e + 3 < ms ? RowLoader<T>::load4(pd, el) : zero4;
-            acc[v] = aggr_combine<OP>(acc[v], aggr_combine<OP>(aggr_combine<OP>(a, b), aggr_combine<OP>(c, dd)));
-          }
-        }
-      }
-      if (shortrow) emit(ri, m, acc, true);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        if (base + g >= n_rows) break;
-        if (__builtin_amdgcn_readlane(m, g * LPR) > SHORT_MAX) wave_row(base + g);
-      }
-    }
+  // The wave's rows i, i + W, i + 2 W, ... (W waves in the grid) as a three-stage pipeline: while row i's source rows are
+  // in flight and being added, row i + W's first 64 `col` entries and row i + 2 W's bounds are in flight too.  Vector
+  // memory returns in order and the prefetches are issued BEFORE the row's own loads, so the wait for the source rows
+  // covers them: one round trip per row in steady state (two for a row whose entries go through gather_ids), where a
+  // row by itself takes bounds -> col -> (gather_ids) -> rows -> self id one after the other.
+  // What keeps the compiler's wait counts exact:
+  //  - the prefetches are unconditional (a row that does not exist, or has no edge, reads a valid word that nobody
+  //    uses): a load behind a branch makes every wait ahead of it assume the branch was not taken;
+  //  - the bounds are fetched with VECTOR loads through an index the compiler cannot prove uniform: scalar loads
+  //    return out of order and share their counter with the __shfl broadcasts, so a prefetched one would be waited
+  //    for at the row's first broadcast;
+  //  - they move to scalar registers right after the row's sum, where they have arrived, and BEFORE the row's stores:
+  //    behind them the wait would be for the stores;
+  //  - the loop is entered with nothing in flight, as every later iteration is (but for its stores).
+  auto vec = [](int x) -> int {
+    asm("" : "+v"(x));
+    return x;
+  };
+  // the first 64 entries of the row [e0, e0 + m), one per lane
+  auto first_col = [&](int e0, int m) -> int { return *(m > 0 ? col + e0 + min(lane, min(64, m) - 1) : rowptr); };
+  const bool need_self = PROJ || !tiled_nkc || !no_self;  // the plan's tiled no_self path never reads the self row
+  int i = wave;
+  if (i >= n_rows) return;
+  int e0, m, e0n, mn;
+  {
+    const int i1 = min(i + waves_total, n_rows - 1);
+    const int rp = rowptr[vec(i)], re = rowend[vec(i)], rp1 = rowptr[vec(i1)], re1 = rowend[vec(i1)];
+    e0 = __builtin_amdgcn_readfirstlane(rp);
+    m = __builtin_amdgcn_readfirstlane(re) - e0;
+    e0n = __builtin_amdgcn_readfirstlane(rp1);
+    mn = i + waves_total < n_rows ? __builtin_amdgcn_readfirstlane(re1) - e0n : 0;
+  }
+  int c = first_col(e0, m);
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+  for (;;) {
+    const int in = i + waves_total;
+    int self = i, my = 0;
+    if (need_self && gather_ids) self = (int)gather_ids[vec(i)];  // (PEER: the destination's global id)
+    if (m > 0) my = translate(c, i);
+    const int cn = first_col(e0n, mn);
+    const int i2 = min(in + waves_total, n_rows - 1);
+    const int rp2 = rowptr[vec(i2)], re2 = rowend[vec(i2)];
+    int e0nn = 0, mnn = 0;
+    wave_row(i, e0, m, my, self, [&] {
+      e0nn = __builtin_amdgcn_readfirstlane(rp2);
+      if (in + waves_total < n_rows) mnn = __builtin_amdgcn_readfirstlane(re2) - e0nn;
+    });
+    if (in >= n_rows) break;
+    i = in;
+    e0 = e0n;
+    m = mn;
+    c = cn;
+    e0n = e0nn;
+    mn = mnn;
   }
 }
 
@@ -1577,6 +1578,10 @@ __global__ __launch_bounds__(256) void hs_chain_kernel(const float* __restrict__
 // (reduce = mean / sum).  One wave per root slot: four groups of 16 lanes take every fourth edge, 12 lanes of a group a
 // float4 of the 48-float half row each.  Writes the roots' rows straight into the caller's buffer (a failed batch set:
 // NaN rows, as gigl_take_rows).
+// Memory round trips per wave: {overflow word, root_local[s]} -> {rowptr, rowend} (scalar, the slot is wave-uniform) ->
+// the row's first 64 col entries in one coalesced load, handed to the groups by __shfl -> every p row of up to 32 edges
+// (eight float4 per lane), the root's own half row and the bias, all requested before the first add.  The adds keep
+// the order acc += p[e] + p[e + 4], e = sub, sub + 8, ... of a group walking its edges two at a time.
 template <int OP>
 __global__ __launch_bounds__(256) void sage_fused_out_kernel(const float* __restrict__ p, const int32_t* __restrict__ rowptr,
                                                              const int32_t* __restrict__ rowend,
@@ -1585,10 +1590,11 @@ __global__ __launch_bounds__(256) void sage_fused_out_kernel(const float* __rest
                                                              const float* __restrict__ bias, int act,
                                                              const int32_t* __restrict__ meta, float* __restrict__ out) {
   const int lane = threadIdx.x & 63, sub = lane >> 4, sl = lane & 15;
-  const int s = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  const int s = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
   if (s >= b) return;
-  const bool failed = meta[GIGL_META_OVERFLOW] != 0;
-  const int i = failed ? -1 : root_local[s];
+  const int overflow = meta[GIGL_META_OVERFLOW], rl = root_local[s];  // (b slots exist whatever the batch set's fate)
+  const bool failed = overflow != 0;
+  const int i = failed ? -1 : rl;
   float* o = out + (int64_t)s * n_out;
   if (i < 0) {
     const float v = failed ? __builtin_nanf("") : 0.f;
@@ -1596,15 +1602,45 @@ __global__ __launch_bounds__(256) void sage_fused_out_kernel(const float* __rest
     return;
   }
   const int e0 = rowptr[i], m = rowend[i] - e0;
-  float4_t acc = {0.f, 0.f, 0.f, 0.f};
-  if (sl < 12) {
-    for (int e = sub; e < m; e += 8) {  // two edges of this group in flight
-      const int ja = col[e0 + e], eb = e + 4;
-      const int jb = eb < m ? col[e0 + eb] : ja;
-      const float4_t a0 = *reinterpret_cast<const float4_t*>(p + (int64_t)ja * F2_N2 + 4 * sl);
-      float4_t b0 = {0.f, 0.f, 0.f, 0.f};
-      if (eb < m) b0 = *reinterpret_cast<const float4_t*>(p + (int64_t)jb * F2_N2 + 4 * sl);
-      acc += a0 + b0;
+  // lanes 12 .. 15 of a group shadow lane 11: their loads stay inside the row and their sums are never read
+  const int cl = sl < 12 ? sl : 11;
+  const float* pl = p + 4 * cl;
+  const float4_t zero4 = {0.f, 0.f, 0.f, 0.f};
+  const float4_t s0 = *reinterpret_cast<const float4_t*>(pl + (int64_t)i * F2_N2 + F2_N2 / 2);
+  float bv[4] = {0.f, 0.f, 0.f, 0.f};
+  if (bias) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) bv[t] = bias[min(4 * cl + t, n_out - 1)];  // (n_out floats; columns >= n_out are not written)
+  }
+  float4_t acc = zero4;
+  // NP pairs of edges per group — entries k0 + sub + 8 t and 4 further of the index vector `my`, t < NP — of the chunk
+  // that starts at edge c0: every load first (an entry past the row names its last edge: a row that is read anyway)
+  auto pass = [&](auto np, int my, int c0, int k0) {
+    constexpr int NP = decltype(np)::value;
+    float4_t ra[NP], rb[NP];
+#pragma unroll
+    for (int t = 0; t < NP; ++t) {
+      const int el = k0 + sub + 8 * t;
+      const int ja = __shfl(my, el, 64), jb = __shfl(my, el + 4, 64);
+      ra[t] = *reinterpret_cast<const float4_t*>(pl + (int64_t)ja * F2_N2);
+      rb[t] = *reinterpret_cast<const float4_t*>(pl + (int64_t)jb * F2_N2);
+    }
+#pragma unroll
+    for (int t = 0; t < NP; ++t) {
+      const int e = c0 + k0 + sub + 8 * t;
+      const float4_t b0 = e + 4 < m ? rb[t] : zero4;
+      if (e < m) acc += ra[t] + b0;
+    }
+  };
+  for (int c0 = 0; c0 < m; c0 += 64) {
+    const int mm = min(64, m - c0);
+    const int my = col[e0 + c0 + min(lane, mm - 1)];
+    for (int k0 = 0; k0 < mm; k0 += 32) {
+      const int np = (min(32, mm - k0) + 7) >> 3;  // wave-uniform
+      if (np == 4) pass(std::integral_constant<int, 4>{}, my, c0, k0);
+      else if (np == 3) pass(std::integral_constant<int, 3>{}, my, c0, k0);
+      else if (np == 2) pass(std::integral_constant<int, 2>{}, my, c0, k0);
+      else pass(std::integral_constant<int, 1>{}, my, c0, k0);
     }
   }
 #pragma unroll
@@ -1615,13 +1651,12 @@ __global__ __launch_bounds__(256) void sage_fused_out_kernel(const float* __rest
   }
   if (sub == 0 && sl < 12) {
     const float dv = (OP == GIGL_AGGR_MEAN && m > 0) ? (float)m : 1.f;
-    const float4_t s0 = *reinterpret_cast<const float4_t*>(p + (int64_t)i * F2_N2 + F2_N2 / 2 + 4 * sl);
     float4_t rr = acc / dv + s0;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int c = 4 * sl + t;
       if (c < n_out) {
-        float v = rr[t] + (bias ? bias[c] : 0.f);
+        float v = rr[t] + bv[t];
         if (act) v = fmaxf(v, 0.f);
         o[c] = v;
       }
