@@ -23,6 +23,7 @@
 //              and W, so no LDS staging or transposes are needed.
 #include "wave_reduce.h"
 #include "common.h"
+#include "dispatch.h"
 
 #include <cstring>
 
@@ -3807,34 +3808,48 @@ static bool launch_gat_fast(gigl_ctx* ctx, const float* h, const float* att_src,
   int64_t ablocks = (nodes_cap + 3) / 4, gblocks = (rows_cap + 3) / 4;
   if (ablocks > 256 * 32) ablocks = 256 * 32;
   if (gblocks > 256 * 32) gblocks = 256 * 32;
-#define GAT_FAST(VV)                                                                                                  \
-  hipLaunchKernelGGL((gat_alpha_fast_kernel<VV>), dim3((unsigned)ablocks), dim3(256), 0, ctx->stream, h, att_src,    \
-                     att_dst, n_nodes_dev, heads, C, g.group, g.rows_per_head, a_src, a_dst);                         \
-  if (wt)                                                                                                            \
-    hipLaunchKernelGGL((gat_gather_fast_kernel<VV, true>), dim3((unsigned)gblocks), dim3(256), 0, ctx->stream, h,    \
-                       a_src, a_dst, a_edge, rowptr, rowend, col, n_rows_dev, heads, C, g.group, g.rows_per_head,    \
-                       slope, bias, act, edge_attr, De, wt, out, heavy_count, heavy_list, eid);                      \
-  else {                                                                                                             \
-    hipLaunchKernelGGL((gat_gather_fast_kernel<VV, false>), dim3((unsigned)gblocks), dim3(256), 0, ctx->stream, h,   \
-                       a_src, a_dst, a_edge, rowptr, rowend, col, n_rows_dev, heads, C, g.group, g.rows_per_head,    \
-                       slope, bias, act, edge_attr, De, wt, out, heavy_count, heavy_list, eid);                      \
-    const size_t lds = (size_t)GAT_HEAVY_WAVES * VV * 7 * 64 * 4;                                                                  \
-    if (lds > 48 * 1024)                                                                                             \
-      hipFuncSetAttribute((const void*)gat_gather_heavy_kernel<VV>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                          (int)lds);                                                                                 \
-    hipLaunchKernelGGL((gat_gather_heavy_kernel<VV>), dim3(1024), dim3(1024), lds, ctx->stream, h, a_src, a_dst,      \
-                       a_edge, rowptr, rowend, col, heavy_count, heavy_list, heads, C, g.group, g.rows_per_head,     \
-                       slope, bias, act, out);                                                                       \
-  }
-  if (g.V == 1) {
-    GAT_FAST(1);
-  } else if (g.V == 2) {
-    GAT_FAST(2);
-  } else {
-    GAT_FAST(4);
-  }
-#undef GAT_FAST
+  dispatch_int<1, 2, 4>(g.V, [&](auto vv) {
+    constexpr int VV = decltype(vv)::value;
+    hipLaunchKernelGGL((gat_alpha_fast_kernel<VV>), dim3((unsigned)ablocks), dim3(256), 0, ctx->stream, h, att_src,
+                       att_dst, n_nodes_dev, heads, C, g.group, g.rows_per_head, a_src, a_dst);
+    if (wt)
+      hipLaunchKernelGGL((gat_gather_fast_kernel<VV, true>), dim3((unsigned)gblocks), dim3(256), 0, ctx->stream, h,
+                         a_src, a_dst, a_edge, rowptr, rowend, col, n_rows_dev, heads, C, g.group, g.rows_per_head,
+                         slope, bias, act, edge_attr, De, wt, out, heavy_count, heavy_list, eid);
+    else {
+      hipLaunchKernelGGL((gat_gather_fast_kernel<VV, false>), dim3((unsigned)gblocks), dim3(256), 0, ctx->stream, h,
+                         a_src, a_dst, a_edge, rowptr, rowend, col, n_rows_dev, heads, C, g.group, g.rows_per_head,
+                         slope, bias, act, edge_attr, De, wt, out, heavy_count, heavy_list, eid);
+      const size_t lds = (size_t)GAT_HEAVY_WAVES * VV * 7 * 64 * 4;
+      if (lds > 48 * 1024)
+        hipFuncSetAttribute((const void*)gat_gather_heavy_kernel<VV>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds);
+      hipLaunchKernelGGL((gat_gather_heavy_kernel<VV>), dim3(1024), dim3(1024), lds, ctx->stream, h, a_src, a_dst,
+                         a_edge, rowptr, rowend, col, heavy_count, heavy_list, heads, C, g.group, g.rows_per_head,
+                         slope, bias, act, out);
+    }
+  });
   return true;
+}
+
+// linear_split_kernel's grid: one workgroup per 128 rows x 64 NJ output columns; grid.y = independent products
+template <int NJ>
+static dim3 linear_split_grid(int64_t m_cap, int n, unsigned batch = 1) {
+  return dim3((unsigned)((m_cap + 127) / 128 * ((n + 64 * NJ - 1) / (64 * NJ))), batch);
+}
+
+// gather_mean_kernel's (lanes per row, float4s per lane) for rows of `vecs` float4s, vecs <= 512: the narrowest pair that
+// covers the row.  One index from the thresholds, then f(LPR tag, VPL tag).
+static int gather_lanes_index(int vecs) {
+  return vecs <= 8 ? 0 : vecs <= 16 ? 1 : vecs <= 32 ? 2 : vecs <= 64 ? 3 : vecs <= 128 ? 4 : vecs <= 256 ? 5 : 6;
+}
+template <typename F>
+static void dispatch_gather_lanes(int vecs, F&& f) {
+  dispatch_int<0, 1, 2, 3, 4, 5, 6>(gather_lanes_index(vecs), [&](auto i) {
+    constexpr int I = decltype(i)::value;
+    constexpr int LPR = I < 3 ? (8 << I) : 64, VPL = I < 4 ? 1 : (1 << (I - 3));  // (8,1) (16,1) (32,1) (64,1) (64,2) (64,4) (64,8)
+    f(std::integral_constant<int, LPR>{}, std::integral_constant<int, VPL>{});
+  });
 }
 
 template <typename T>
@@ -3850,25 +3865,6 @@ int32_t launch_gather(gigl_ctx* ctx, const T* src, int d, const uint32_t* gather
   dim3 g((unsigned)blocks), b(256);
   hipStream_t st = ctx->stream;
   const int vecs = d / 4;
-#define GLO(LPR, VPL, OP)                                                                                              \
-  do {                                                                                                                 \
-    if (peers)                                                                                                         \
-      hipLaunchKernelGGL((gather_mean_kernel<T, LPR, VPL, OP, false, true>), g, b, 0, st, src, d, gather_ids, rowptr,  \
-                         rowend, col, n_rows_dev, out, n_local_dev, tiled_nkc, global_map, src2, src3,                 \
-                         (const float*)nullptr, (const float*)nullptr, 0, 0, no_self, (const int32_t*)nullptr, 0,      \
-                         own_world, own_rank, peers);                                                                  \
-    else                                                                                                               \
-      hipLaunchKernelGGL((gather_mean_kernel<T, LPR, VPL, OP>), g, b, 0, st, src, d, gather_ids, rowptr, rowend, col,  \
-                         n_rows_dev, out, n_local_dev, tiled_nkc, global_map, src2, src3, (const float*)nullptr,       \
-                         (const float*)nullptr, 0, 0, no_self, (const int32_t*)nullptr, 0, own_world, own_rank,        \
-                         (const T* const*)nullptr);                                                                    \
-  } while (0)
-#define GL(LPR, VPL)                                        \
-  do {                                                      \
-    if (op == GIGL_AGGR_MEAN) GLO(LPR, VPL, GIGL_AGGR_MEAN); \
-    else if (op == GIGL_AGGR_SUM) GLO(LPR, VPL, GIGL_AGGR_SUM); \
-    else GLO(LPR, VPL, GIGL_AGGR_MAX);                      \
-  } while (0)
   if (peers && (own_world < 1 || own_world > 64))
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "peer-mapped tables: world %d outside [1, 64]", own_world);
   if ((d & 3) != 0 || vecs > 512) {
@@ -3876,15 +3872,24 @@ int32_t launch_gather(gigl_ctx* ctx, const T* src, int d, const uint32_t* gather
       return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "the tiled operand layout / global row map need d %% 4 == 0 and d <= 2048");
     hipLaunchKernelGGL((gather_mean_generic_kernel<T>), g, b, 0, st, src, d, gather_ids, rowptr, rowend,
                        col, n_rows_dev, out, op, n_local_dev);
-  } else if (vecs <= 8) GL(8, 1);
-  else if (vecs <= 16) GL(16, 1);
-  else if (vecs <= 32) GL(32, 1);
-  else if (vecs <= 64) GL(64, 1);
-  else if (vecs <= 128) GL(64, 2);
-  else if (vecs <= 256) GL(64, 4);
-  else GL(64, 8);
-#undef GL
-#undef GLO
+  } else {
+    dispatch_gather_lanes(vecs, [&](auto lpr, auto vpl) {
+      constexpr int LPR = decltype(lpr)::value, VPL = decltype(vpl)::value;
+      dispatch_int<GIGL_AGGR_MEAN, GIGL_AGGR_SUM, GIGL_AGGR_MAX>(op, [&](auto o) {
+        constexpr int OP = decltype(o)::value;
+        if (peers)
+          hipLaunchKernelGGL((gather_mean_kernel<T, LPR, VPL, OP, false, true>), g, b, 0, st, src, d, gather_ids, rowptr,
+                             rowend, col, n_rows_dev, out, n_local_dev, tiled_nkc, global_map, src2, src3,
+                             (const float*)nullptr, (const float*)nullptr, 0, 0, no_self, (const int32_t*)nullptr, 0,
+                             own_world, own_rank, peers);
+        else
+          hipLaunchKernelGGL((gather_mean_kernel<T, LPR, VPL, OP>), g, b, 0, st, src, d, gather_ids, rowptr, rowend, col,
+                             n_rows_dev, out, n_local_dev, tiled_nkc, global_map, src2, src3, (const float*)nullptr,
+                             (const float*)nullptr, 0, 0, no_self, (const int32_t*)nullptr, 0, own_world, own_rank,
+                             (const T* const*)nullptr);
+      });
+    });
+  }
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -3901,37 +3906,24 @@ int32_t launch_gather_projected(gigl_ctx* ctx, const float* src_l, const float* 
   if (blocks < 1) blocks = 1;
   dim3 g((unsigned)blocks), b(256);
   const int vecs = d / 4;
-#define GLPP(LPR, VPL, OP)                                                                                            \
-  hipLaunchKernelGGL((gather_mean_kernel<float, LPR, VPL, OP, true, true>), g, b, 0, ctx->stream, src_l, d, gather_ids, \
-                     rowptr, rowend, col, n_rows_dev, out, n_local_dev, 0, global_map, src2, src3, src_r, bias, act, ld, \
-                     0, self_ids, ld3, own_world, own_rank, peers)
-#define GLP(LPR, VPL)                                                                                                 \
-  do {                                                                                                                \
-    if (peers && op == GIGL_AGGR_MEAN)                                                                                \
-      GLPP(LPR, VPL, GIGL_AGGR_MEAN);                                                                                 \
-    else if (peers)                                                                                                   \
-      GLPP(LPR, VPL, GIGL_AGGR_SUM);                                                                                  \
-    else if (op == GIGL_AGGR_MEAN)                                                                                    \
-      hipLaunchKernelGGL((gather_mean_kernel<float, LPR, VPL, GIGL_AGGR_MEAN, true>), g, b, 0, ctx->stream, src_l, d, \
-                         gather_ids, rowptr, rowend, col, n_rows_dev, out, n_local_dev, 0, global_map, src2, src3,    \
-                         src_r, bias, act, ld, 0, self_ids, ld3, own_world, own_rank, (const float* const*)nullptr);  \
-    else                                                                                                              \
-      hipLaunchKernelGGL((gather_mean_kernel<float, LPR, VPL, GIGL_AGGR_SUM, true>), g, b, 0, ctx->stream, src_l, d,  \
-                         gather_ids, rowptr, rowend, col, n_rows_dev, out, n_local_dev, 0, global_map, src2, src3,    \
-                         src_r, bias, act, ld, 0, self_ids, ld3, own_world, own_rank, (const float* const*)nullptr);  \
-  } while (0)
   if (peers && (own_world < 1 || own_world > 64))
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "peer-mapped tables: world %d outside [1, 64]", own_world);
   if ((d & 3) != 0 || vecs > 512) return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "projected input: width %d (need d %% 4 == 0, d <= 2048)", d);
-  if (vecs <= 8) GLP(8, 1);
-  else if (vecs <= 16) GLP(16, 1);
-  else if (vecs <= 32) GLP(32, 1);
-  else if (vecs <= 64) GLP(64, 1);
-  else if (vecs <= 128) GLP(64, 2);
-  else if (vecs <= 256) GLP(64, 4);
-  else GLP(64, 8);
-#undef GLP
-#undef GLPP
+  // (only MEAN and SUM are built; any other op takes SUM, as the last listed value)
+  dispatch_gather_lanes(vecs, [&](auto lpr, auto vpl) {
+    constexpr int LPR = decltype(lpr)::value, VPL = decltype(vpl)::value;
+    dispatch_int<GIGL_AGGR_MEAN, GIGL_AGGR_SUM>(op, [&](auto o) {
+      constexpr int OP = decltype(o)::value;
+      if (peers)
+        hipLaunchKernelGGL((gather_mean_kernel<float, LPR, VPL, OP, true, true>), g, b, 0, ctx->stream, src_l, d, gather_ids,
+                           rowptr, rowend, col, n_rows_dev, out, n_local_dev, 0, global_map, src2, src3, src_r, bias, act, ld,
+                           0, self_ids, ld3, own_world, own_rank, peers);
+      else
+        hipLaunchKernelGGL((gather_mean_kernel<float, LPR, VPL, OP, true>), g, b, 0, ctx->stream, src_l, d, gather_ids,
+                           rowptr, rowend, col, n_rows_dev, out, n_local_dev, 0, global_map, src2, src3, src_r, bias, act, ld,
+                           0, self_ids, ld3, own_world, own_rank, (const float* const*)nullptr);
+    });
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -4027,26 +4019,17 @@ int32_t gigl_sage_project_features(gigl_ctx* ctx, gigl_feat* feat, const float* 
     if (feat->dtype == GIGL_DTYPE_F16 && half_direct) {  // the rows as stored: two bf16 planes, five products
       gigl_prof_scope ps(ctx, GIGL_K_LINEAR);
       const int nn = 2 * n_out;
-      const int64_t bm = (m + 127) / 128;
       const float* ah = reinterpret_cast<const float*>((const __half*)feat->rows + r0 * d);
-      if (hs && nn > 64)
-        hipLaunchKernelGGL((linear_split_kernel<2, true, false, true, true>), dim3((unsigned)(bm * ((nn + 127) / 128))), dim3(256),
-                           0, st, ah, (const float*)wcat, (const float*)nullptr, (const int32_t*)(cnt + (m == cm ? 0 : 1)), d,
-                           nn, 0, out + r0 * 2 * n_out, 0, 0, (int64_t)0, (int64_t)0,
-                           (const float*)nullptr, (const uint32_t*)nullptr, 0, 0, (const float*)hs_dev);
-      else if (hs)
-        hipLaunchKernelGGL((linear_split_kernel<1, true, false, true, true>), dim3((unsigned)(bm * ((nn + 63) / 64))), dim3(256),
-                           0, st, ah, (const float*)wcat, (const float*)nullptr, (const int32_t*)(cnt + (m == cm ? 0 : 1)), d,
-                           nn, 0, out + r0 * 2 * n_out, 0, 0, (int64_t)0, (int64_t)0,
-                           (const float*)nullptr, (const uint32_t*)nullptr, 0, 0, (const float*)hs_dev);
-      else if (nn > 64)
-        hipLaunchKernelGGL((linear_split_kernel<2, true, false, true>), dim3((unsigned)(bm * ((nn + 127) / 128))), dim3(256),
-                           0, st, ah, (const float*)wcat, (const float*)nullptr, (const int32_t*)(cnt + (m == cm ? 0 : 1)), d,
-                           nn, 0, out + r0 * 2 * n_out, 0, 0, (int64_t)0, (int64_t)0);
-      else
-        hipLaunchKernelGGL((linear_split_kernel<1, true, false, true>), dim3((unsigned)(bm * ((nn + 63) / 64))), dim3(256),
-                           0, st, ah, (const float*)wcat, (const float*)nullptr, (const int32_t*)(cnt + (m == cm ? 0 : 1)), d,
-                           nn, 0, out + r0 * 2 * n_out, 0, 0, (int64_t)0, (int64_t)0);
+      dispatch_int<2, 1>(nn > 64 ? 2 : 1, [&](auto nj) {
+        dispatch_bool(hs, [&](auto h) {
+          constexpr int NJ = decltype(nj)::value;
+          constexpr bool KVEC = true, SELF = false, AHALF = true, HS = decltype(h)::value;
+          hipLaunchKernelGGL((linear_split_kernel<NJ, KVEC, SELF, AHALF, HS>), linear_split_grid<NJ>(m, nn), dim3(256), 0, st, ah,
+                             (const float*)wcat, (const float*)nullptr, (const int32_t*)(cnt + (m == cm ? 0 : 1)), d, nn, 0,
+                             out + r0 * 2 * n_out, 0, 0, (int64_t)0, (int64_t)0, (const float*)nullptr,
+                             (const uint32_t*)nullptr, 0, 0, hs ? (const float*)hs_dev : (const float*)nullptr);
+        });
+      });
       if (hipGetLastError() != hipSuccess) rc = gigl_fail(ctx, GIGL_E_HIP, "projection launch failed");
       continue;
     }
@@ -4073,13 +4056,12 @@ int32_t gigl_gather_mean(gigl_ctx* ctx, const void* src, int32_t src_dtype, int3
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (rows_cap == 0) return GIGL_OK;
   gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
-  if (src_dtype == GIGL_DTYPE_F32)
-    return launch_gather<float>(ctx, (const float*)src, d, gather_ids, rowptr, rowend, col, n_rows_dev,
-                                rows_cap, out);
-  if (src_dtype == GIGL_DTYPE_F16)
-    return launch_gather<__half>(ctx, (const __half*)src, d, gather_ids, rowptr, rowend, col, n_rows_dev,
-                                 rows_cap, out);
-  return gigl_fail(ctx, GIGL_E_INVALID_ARG, "bad dtype %d", src_dtype);
+  if (src_dtype != GIGL_DTYPE_F32 && src_dtype != GIGL_DTYPE_F16)
+    return gigl_fail(ctx, GIGL_E_INVALID_ARG, "bad dtype %d", src_dtype);
+  return dispatch_type<float, __half>(src_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_gather<T>(ctx, (const T*)src, d, gather_ids, rowptr, rowend, col, n_rows_dev, rows_cap, out);
+  });
 }
 
 int32_t gigl_gather_reduce(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d, const uint32_t* gather_ids,
@@ -4092,13 +4074,12 @@ int32_t gigl_gather_reduce(gigl_ctx* ctx, const void* src, int32_t src_dtype, in
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (rows_cap == 0) return GIGL_OK;
   gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
-  if (src_dtype == GIGL_DTYPE_F32)
-    return launch_gather<float>(ctx, (const float*)src, d, gather_ids, rowptr, rowend, col, n_rows_dev, rows_cap, out,
-                                aggr);
-  if (src_dtype == GIGL_DTYPE_F16)
-    return launch_gather<__half>(ctx, (const __half*)src, d, gather_ids, rowptr, rowend, col, n_rows_dev, rows_cap,
-                                 out, aggr);
-  return gigl_fail(ctx, GIGL_E_INVALID_ARG, "bad dtype %d", src_dtype);
+  if (src_dtype != GIGL_DTYPE_F32 && src_dtype != GIGL_DTYPE_F16)
+    return gigl_fail(ctx, GIGL_E_INVALID_ARG, "bad dtype %d", src_dtype);
+  return dispatch_type<float, __half>(src_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_gather<T>(ctx, (const T*)src, d, gather_ids, rowptr, rowend, col, n_rows_dev, rows_cap, out, aggr);
+  });
 }
 
 }  // extern "C"
@@ -4112,13 +4093,12 @@ int32_t gigl_gather_reduce_mixed(gigl_ctx* ctx, const void* src, int32_t src_dty
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (rows_cap == 0) return GIGL_OK;
   gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
-  if (src_dtype == GIGL_DTYPE_F32)
-    return launch_gather<float>(ctx, (const float*)src, d, gather_ids, rowptr, rowend, col, n_rows_dev, rows_cap, out,
-                                aggr, n_local_rows_dev, tiled_nkc, global_map, (const float*)src2, (const float*)src3,
-                                no_self, own_world, own_rank, (const float* const*)peers);
-  return launch_gather<__half>(ctx, (const __half*)src, d, gather_ids, rowptr, rowend, col, n_rows_dev, rows_cap, out,
-                               aggr, n_local_rows_dev, tiled_nkc, global_map, (const __half*)src2, (const __half*)src3,
-                               no_self, own_world, own_rank, (const __half* const*)peers);
+  return dispatch_type<float, __half>(src_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_gather<T>(ctx, (const T*)src, d, gather_ids, rowptr, rowend, col, n_rows_dev, rows_cap, out, aggr,
+                            n_local_rows_dev, tiled_nkc, global_map, (const T*)src2, (const T*)src3, no_self, own_world,
+                            own_rank, (const T* const*)peers);
+  });
 }
 
 extern "C" {
@@ -4132,12 +4112,11 @@ int32_t gigl_gather_rows(gigl_ctx* ctx, const void* src, int32_t src_dtype, int3
   if (cap == 0) return GIGL_OK;
   int64_t blocks = (cap + 3) / 4;
   if (blocks > 256 * 16) blocks = 256 * 16;
-  if (src_dtype == GIGL_DTYPE_F32)
-    hipLaunchKernelGGL((gather_rows_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const float*)src,
-                       d, ids, n_dev, out);
-  else
-    hipLaunchKernelGGL((gather_rows_kernel<__half>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
-                       (const __half*)src, d, ids, n_dev, out);
+  dispatch_type<float, __half>(src_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((gather_rows_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const T*)src, d, ids,
+                       n_dev, out);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -4157,12 +4136,11 @@ int32_t gigl_gcn_aggregate(gigl_ctx* ctx, const void* h, int32_t h_dtype, int32_
                      rowend, col, n_nodes_dev, dinv_scratch);
   int64_t blocks = (rows_cap + 3) / 4;
   if (blocks > 256 * 16) blocks = 256 * 16;
-  if (h_dtype == GIGL_DTYPE_F32)
-    hipLaunchKernelGGL((gcn_gather_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const float*)h,
-                       d, gather_ids, dinv_scratch, rowptr, rowend, col, n_rows_dev, bias, act, out);
-  else
-    hipLaunchKernelGGL((gcn_gather_kernel<__half>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
-                       (const __half*)h, d, gather_ids, dinv_scratch, rowptr, rowend, col, n_rows_dev, bias, act, out);
+  dispatch_type<float, __half>(h_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((gcn_gather_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const T*)h, d,
+                       gather_ids, dinv_scratch, rowptr, rowend, col, n_rows_dev, bias, act, out);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -4322,21 +4300,15 @@ int32_t gigl_gat_aggregate_backward(gigl_ctx* ctx, const float* h, const float* 
   if (ablocks > 256 * 32) ablocks = 256 * 32;
   if (gblocks > 256 * 32) gblocks = 256 * 32;
   gblocks = (gblocks + 1) & ~(int64_t)1;  // (whole rows per launch: 4 waves per workgroup, wpr <= 8)
-#define GAT_BWD(VV)                                                                                                  \
-  hipLaunchKernelGGL((gat_alpha_fast_kernel<VV>), dim3((unsigned)ablocks), dim3(256), 0, ctx->stream, h, att_src,   \
-                     att_dst, n_nodes_dev, heads, channels, g.group, g.rows_per_head, a_src, a_dst);                \
-  hipLaunchKernelGGL((gat_backward_kernel<VV>), dim3((unsigned)gblocks), dim3(256), 0, ctx->stream, h, a_src, a_dst, \
-                     a_edge, rowptr, rowend, col, n_rows_dev, heads, channels, g.group, g.rows_per_head,            \
-                     negative_slope, out_pre, dout, dh, d_alpha_src, d_alpha_dst, d_alpha_edge, edge_attr, edge_dim,  \
-                     u_msg, z_out, wpr)
-  if (g.V == 1) {
-    GAT_BWD(1);
-  } else if (g.V == 2) {
-    GAT_BWD(2);
-  } else {
-    GAT_BWD(4);
-  }
-#undef GAT_BWD
+  dispatch_int<1, 2, 4>(g.V, [&](auto vv) {
+    constexpr int VV = decltype(vv)::value;
+    hipLaunchKernelGGL((gat_alpha_fast_kernel<VV>), dim3((unsigned)ablocks), dim3(256), 0, ctx->stream, h, att_src,
+                       att_dst, n_nodes_dev, heads, channels, g.group, g.rows_per_head, a_src, a_dst);
+    hipLaunchKernelGGL((gat_backward_kernel<VV>), dim3((unsigned)gblocks), dim3(256), 0, ctx->stream, h, a_src, a_dst,
+                       a_edge, rowptr, rowend, col, n_rows_dev, heads, channels, g.group, g.rows_per_head,
+                       negative_slope, out_pre, dout, dh, d_alpha_src, d_alpha_dst, d_alpha_edge, edge_attr, edge_dim,
+                       u_msg, z_out, wpr);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -4412,14 +4384,10 @@ int32_t gigl_gather_mean_backward_lists(gigl_ctx* ctx, const float* dout, int32_
   int64_t gg = (src_cap * lpr / 64 + 3) / 4;
   if (gg > 256 * 16) gg = 256 * 16;
   if (gg < 1) gg = 1;
-#define GMT(L)                                                                                                          \
-  hipLaunchKernelGGL(gmt_gather_kernel<L>, dim3((unsigned)gg), dim3(256), 0, st, dout, d, rowptr, rowend, n_rows_dev,   \
-                     n_src_dev, cnt, ptr, list, dsrc, mean)
-  if (lpr == 64) GMT(64);
-  else if (lpr == 32) GMT(32);
-  else if (lpr == 16) GMT(16);
-  else GMT(8);
-#undef GMT
+  dispatch_int<64, 32, 16, 8>(lpr, [&](auto l) {
+    hipLaunchKernelGGL(gmt_gather_kernel<decltype(l)::value>, dim3((unsigned)gg), dim3(256), 0, st, dout, d, rowptr, rowend,
+                       n_rows_dev, n_src_dev, cnt, ptr, list, dsrc, mean);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -4477,40 +4445,25 @@ int32_t gigl_linear(gigl_ctx* ctx, const float* a, const float* w, const float* 
   // (which kernel runs depends on k alone — never on the row count: the rows of a batch must come out bit-identical
   // whether the batch is computed alone or inside a group of batches)
   if (!exact_only) {  // split-precision bf16 MFMA (fp32-class accuracy); K % 4 != 0: the element-load instantiation
-    const int64_t bm = (m_cap + 127) / 128;
-    const bool kv = (k & 3) == 0;
-    const dim3 g2((unsigned)(bm * ((n + 127) / 128))), g1((unsigned)(bm * ((n + 63) / 64)));
-    if (n > 64 && kv)
-      hipLaunchKernelGGL((linear_split_kernel<2, true>), g2, dim3(256), 0, st, a, w, bias, m_dev, k, n, act, y, 0, 0,
-                         (int64_t)0, (int64_t)0);
-    else if (n > 64)
-      hipLaunchKernelGGL((linear_split_kernel<2, false>), g2, dim3(256), 0, st, a, w, bias, m_dev, k, n, act, y, 0, 0,
-                         (int64_t)0, (int64_t)0);
-    else if (kv)
-      hipLaunchKernelGGL((linear_split_kernel<1, true>), g1, dim3(256), 0, st, a, w, bias, m_dev, k, n, act, y, 0, 0,
-                         (int64_t)0, (int64_t)0);
-    else
-      hipLaunchKernelGGL((linear_split_kernel<1, false>), g1, dim3(256), 0, st, a, w, bias, m_dev, k, n, act, y, 0, 0,
-                         (int64_t)0, (int64_t)0);
-  } else if ((k & 3) == 0) {  // LDS-staged, coalesced operand fetch
-    const int64_t bm = (m_cap + 127) / 128;
-    if (n > 32) {
-      hipLaunchKernelGGL((linear_lds_kernel<2>), dim3((unsigned)(bm * ((n + 63) / 64))), dim3(256), 0, st, a, w,
-                         bias, m_dev, k, n, act, y);
-    } else {
-      hipLaunchKernelGGL((linear_lds_kernel<1>), dim3((unsigned)(bm * ((n + 31) / 32))), dim3(256), 0, st, a, w,
-                         bias, m_dev, k, n, act, y);
-    }
-  } else if (n > 32) {
-    constexpr int NT = 2;
-    int64_t tiles = tiles_m * ((n + 32 * NT - 1) / (32 * NT));
-    hipLaunchKernelGGL((linear_mfma_kernel<NT>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, a, w,
-                       bias, m_dev, k, n, act, y);
-  } else {
-    constexpr int NT = 1;
-    int64_t tiles = tiles_m * ((n + 31) / 32);
-    hipLaunchKernelGGL((linear_mfma_kernel<NT>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, a, w,
-                       bias, m_dev, k, n, act, y);
+    dispatch_int<2, 1>(n > 64 ? 2 : 1, [&](auto nj) {
+      dispatch_bool((k & 3) == 0, [&](auto kvec) {
+        constexpr int NJ = decltype(nj)::value;
+        constexpr bool KVEC = decltype(kvec)::value;
+        hipLaunchKernelGGL((linear_split_kernel<NJ, KVEC>), linear_split_grid<NJ>(m_cap, n), dim3(256), 0, st, a, w, bias,
+                           m_dev, k, n, act, y, 0, 0, (int64_t)0, (int64_t)0);
+      });
+    });
+  } else {  // exact fp32: LDS-staged, coalesced operand fetch for K % 4 == 0, else rows straight from global
+    dispatch_int<2, 1>(n > 32 ? 2 : 1, [&](auto nt) {
+      constexpr int NT = decltype(nt)::value;
+      const int64_t tiles_n = (n + 32 * NT - 1) / (32 * NT);
+      if ((k & 3) == 0)
+        hipLaunchKernelGGL((linear_lds_kernel<NT>), dim3((unsigned)((m_cap + 127) / 128 * tiles_n)), dim3(256), 0, st, a, w,
+                           bias, m_dev, k, n, act, y);
+      else
+        hipLaunchKernelGGL((linear_mfma_kernel<NT>), dim3((unsigned)((tiles_m * tiles_n + 3) / 4)), dim3(256), 0, st, a, w,
+                           bias, m_dev, k, n, act, y);
+    });
   }
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
@@ -4799,64 +4752,27 @@ static int32_t linear_tiled_strided(gigl_ctx* ctx, const float* a_tiled, const f
   hipStream_t st = ctx->stream;
   gigl_prof_scope ps(ctx, GIGL_K_LINEAR);
   const int nkc = (k + 31) / 32;
-  const int64_t bm = (m_cap + 127) / 128;
-  if (self_src) {  // two-source operand: the tiled buffer holds the mean chunks only
+  const bool self = self_src != nullptr;  // two-source operand: the tiled buffer holds the mean chunks only
+  if (self) {
     GIGL_REQUIRE(ctx, batch == 1 && d_mean > 0 && (d_mean & 3) == 0 && d_mean < k && self_ld >= k - d_mean, "bad two-source operand");
-    const int nkc_mean = (d_mean + 31) / 32;
     GIGL_REQUIRE(ctx, !self_half || hs, "fp16 self rows go with the half split");
-    if (hs && self_half) {
-      if (n > 64)
-        hipLaunchKernelGGL((linear_split_kernel<2, true, true, false, true, true, true>), dim3((unsigned)(bm * ((n + 127) / 128)), 1u),
-                           dim3(256), 0, st, a_tiled, w, bias, m_dev, k, n, act, y, nkc_mean, ldy, (int64_t)0, (int64_t)0,
-                           self_src, self_ids, d_mean, self_ld, hs_scale);
-      else
-        hipLaunchKernelGGL((linear_split_kernel<1, true, true, false, true, true, true>), dim3((unsigned)(bm * ((n + 63) / 64)), 1u),
-                           dim3(256), 0, st, a_tiled, w, bias, m_dev, k, n, act, y, nkc_mean, ldy, (int64_t)0, (int64_t)0,
-                           self_src, self_ids, d_mean, self_ld, hs_scale);
-      GIGL_HIP_CHECK(ctx, hipGetLastError());
-      return GIGL_OK;
-    }
-    if (hs) {
-      if (n > 64)
-        hipLaunchKernelGGL((linear_split_kernel<2, true, true, false, true, true>), dim3((unsigned)(bm * ((n + 127) / 128)), 1u),
-                           dim3(256), 0, st, a_tiled, w, bias, m_dev, k, n, act, y, nkc_mean, ldy, (int64_t)0, (int64_t)0,
-                           self_src, self_ids, d_mean, self_ld, hs_scale);
-      else
-        hipLaunchKernelGGL((linear_split_kernel<1, true, true, false, true, true>), dim3((unsigned)(bm * ((n + 63) / 64)), 1u),
-                           dim3(256), 0, st, a_tiled, w, bias, m_dev, k, n, act, y, nkc_mean, ldy, (int64_t)0, (int64_t)0,
-                           self_src, self_ids, d_mean, self_ld, hs_scale);
-      GIGL_HIP_CHECK(ctx, hipGetLastError());
-      return GIGL_OK;
-    }
-    if (n > 64)
-      hipLaunchKernelGGL((linear_split_kernel<2, true, true>), dim3((unsigned)(bm * ((n + 127) / 128)), 1u), dim3(256), 0, st,
-                         a_tiled, w, bias, m_dev, k, n, act, y, nkc_mean, ldy, (int64_t)0, (int64_t)0, self_src, self_ids,
-                         d_mean, self_ld);
-    else
-      hipLaunchKernelGGL((linear_split_kernel<1, true, true, false, false, true>), dim3((unsigned)(bm * ((n + 63) / 64)), 1u), dim3(256), 0, st,
-                         a_tiled, w, bias, m_dev, k, n, act, y, nkc_mean, ldy, (int64_t)0, (int64_t)0, self_src, self_ids,
-                         d_mean, self_ld);
-    GIGL_HIP_CHECK(ctx, hipGetLastError());
-    return GIGL_OK;
   }
-  if (hs) {
-    if (n > 64)
-      hipLaunchKernelGGL((linear_split_kernel<2, true, false, false, true, true>), dim3((unsigned)(bm * ((n + 127) / 128)), (unsigned)batch),
-                         dim3(256), 0, st, a_tiled, w, bias, m_dev, k, n, act, y, nkc, ldy, a_bstride, w_bstride,
-                         (const float*)nullptr, (const uint32_t*)nullptr, 0, 0, hs_scale);
-    else
-      hipLaunchKernelGGL((linear_split_kernel<1, true, false, false, true, true>), dim3((unsigned)(bm * ((n + 63) / 64)), (unsigned)batch),
-                         dim3(256), 0, st, a_tiled, w, bias, m_dev, k, n, act, y, nkc, ldy, a_bstride, w_bstride,
-                         (const float*)nullptr, (const uint32_t*)nullptr, 0, 0, hs_scale);
-    GIGL_HIP_CHECK(ctx, hipGetLastError());
-    return GIGL_OK;
-  }
-  if (n > 64)
-    hipLaunchKernelGGL((linear_split_kernel<2, true, false, false, false, true>), dim3((unsigned)(bm * ((n + 127) / 128)), (unsigned)batch), dim3(256), 0,
-                       st, a_tiled, w, bias, m_dev, k, n, act, y, nkc, ldy, a_bstride, w_bstride);
-  else
-    hipLaunchKernelGGL((linear_split_kernel<1, true, false, false, false, true>), dim3((unsigned)(bm * ((n + 63) / 64)), (unsigned)batch), dim3(256), 0,
-                       st, a_tiled, w, bias, m_dev, k, n, act, y, nkc, ldy, a_bstride, w_bstride);
+  const int a_chunks = self ? (d_mean + 31) / 32 : nkc;
+  // the built forms: 0 plain, 1 half split, 2 two-source, 3 two-source + half split, 4 ... + fp16 self rows
+  const int form = !self ? (hs ? 1 : 0) : (!hs ? 2 : (self_half ? 4 : 3));
+  dispatch_int<2, 1>(n > 64 ? 2 : 1, [&](auto nj) {
+    dispatch_int<0, 1, 2, 3, 4>(form, [&](auto f) {
+      constexpr int NJ = decltype(nj)::value, F = decltype(f)::value;
+      constexpr bool KVEC = true, SELF = F >= 2, AHALF = false, HS = F == 1 || F >= 3, SH = F == 4;
+      // ONE (three waves per SIMD, amdgpu_waves_per_eu) everywhere but the 128-column two-source launch without the half
+      // split, which was tuned without it: flipping it either way would build a different kernel
+      constexpr bool ONE = !(SELF && !HS && NJ == 2);
+      hipLaunchKernelGGL((linear_split_kernel<NJ, KVEC, SELF, AHALF, HS, ONE, SH>), linear_split_grid<NJ>(m_cap, n, (unsigned)batch),
+                         dim3(256), 0, st, a_tiled, w, bias, m_dev, k, n, act, y, a_chunks, ldy, self ? (int64_t)0 : a_bstride,
+                         self ? (int64_t)0 : w_bstride, self_src, self ? self_ids : (const uint32_t*)nullptr, self ? d_mean : 0,
+                         self ? self_ld : 0, hs_scale);
+    });
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -4919,12 +4835,10 @@ int32_t gigl_sage_fused_out(gigl_ctx* ctx, const float* p, const int32_t* rowptr
   if (b == 0) return GIGL_OK;
   gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
   const dim3 g((unsigned)(((int64_t)b + 3) / 4)), blk(256);
-#define GIGL_FOUT(OP)                                                                                                     \
-  hipLaunchKernelGGL((sage_fused_out_kernel<OP>), g, blk, 0, ctx->stream, p, rowptr, rowend, col, root_local, b, n_out, bias, \
-                     act, meta, out)
-  if (aggr == GIGL_AGGR_MEAN) GIGL_FOUT(GIGL_AGGR_MEAN);
-  else GIGL_FOUT(GIGL_AGGR_SUM);
-#undef GIGL_FOUT
+  dispatch_int<GIGL_AGGR_MEAN, GIGL_AGGR_SUM>(aggr, [&](auto op) {
+    hipLaunchKernelGGL((sage_fused_out_kernel<decltype(op)::value>), g, blk, 0, ctx->stream, p, rowptr, rowend, col,
+                       root_local, b, n_out, bias, act, meta, out);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -4945,13 +4859,11 @@ int32_t gigl_linear_batched(gigl_ctx* ctx, const float* a, const float* w, const
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (m_cap == 0) return GIGL_OK;
   gigl_prof_scope ps(ctx, GIGL_K_LINEAR);
-  const int64_t bm = (m_cap + 127) / 128;
-  if (n > 64)
-    hipLaunchKernelGGL((linear_split_kernel<2, true>), dim3((unsigned)(bm * ((n + 127) / 128)), (unsigned)batch),
-                       dim3(256), 0, ctx->stream, a, w, bias, m_dev, k, n, act, y, 0, ldy, a_bstride, w_bstride);
-  else
-    hipLaunchKernelGGL((linear_split_kernel<1, true>), dim3((unsigned)(bm * ((n + 63) / 64)), (unsigned)batch),
-                       dim3(256), 0, ctx->stream, a, w, bias, m_dev, k, n, act, y, 0, ldy, a_bstride, w_bstride);
+  dispatch_int<2, 1>(n > 64 ? 2 : 1, [&](auto nj) {
+    constexpr int NJ = decltype(nj)::value;
+    hipLaunchKernelGGL((linear_split_kernel<NJ, true>), linear_split_grid<NJ>(m_cap, n, (unsigned)batch), dim3(256), 0,
+                       ctx->stream, a, w, bias, m_dev, k, n, act, y, 0, ldy, a_bstride, w_bstride);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -4966,19 +4878,16 @@ int32_t gigl_linear_grouped(gigl_ctx* ctx, const gigl_linear_group* groups_dev, 
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (m_cap_max == 0 || n_groups == 0) return GIGL_OK;
   gigl_prof_scope ps(ctx, GIGL_K_LINEAR);
-  const int64_t bm = (m_cap_max + 127) / 128;
   const float* none = nullptr;
   const int32_t* none_i = nullptr;
   float* none_y = nullptr;
   const uint32_t* none_u = nullptr;
-  if (n > 64)
-    hipLaunchKernelGGL((linear_split_kernel<2, true>), dim3((unsigned)(bm * ((n + 127) / 128)), (unsigned)n_groups),
-                       dim3(256), 0, ctx->stream, none, none, none, none_i, k, n, act, none_y, 0, n, (int64_t)0, (int64_t)0, none,
-                       none_u, 0, 0, none, groups_dev);
-  else
-    hipLaunchKernelGGL((linear_split_kernel<1, true>), dim3((unsigned)(bm * ((n + 63) / 64)), (unsigned)n_groups),
-                       dim3(256), 0, ctx->stream, none, none, none, none_i, k, n, act, none_y, 0, n, (int64_t)0, (int64_t)0, none,
-                       none_u, 0, 0, none, groups_dev);
+  dispatch_int<2, 1>(n > 64 ? 2 : 1, [&](auto nj) {
+    constexpr int NJ = decltype(nj)::value;
+    hipLaunchKernelGGL((linear_split_kernel<NJ, true>), linear_split_grid<NJ>(m_cap_max, n, (unsigned)n_groups), dim3(256), 0,
+                       ctx->stream, none, none, none, none_i, k, n, act, none_y, 0, n, (int64_t)0, (int64_t)0, none, none_u, 0,
+                       0, none, groups_dev);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -5033,25 +4942,18 @@ int32_t gigl_gat_input_layer(gigl_ctx* ctx, const void* src, int32_t src_dtype, 
     if (sblocks > 256 * 8) sblocks = 256 * 8;
     if (wblocks > 256 * 16) wblocks = 256 * 16;
     if (gblocks > 256 * 8) gblocks = 256 * 8;
-#define GIGL_GAT_IN(TT, HH)                                                                                             \
-  do {                                                                                                                  \
-    hipLaunchKernelGGL((gat_score_kernel<TT, HH>), dim3((unsigned)sblocks, (unsigned)chunks), dim3(256), 0, st,        \
-                       (const TT*)src, d, ids, n_src_dev, cap_nodes, u, sp);                                            \
-    hipLaunchKernelGGL((gat_edge_weight_kernel<HH>), dim3((unsigned)wblocks), dim3(256), 0, st, ids, sp, chunks,       \
-                       cap_nodes, rowptr, rowend, col, n_rows_dev, negative_slope, gid_e, alpha_e, alpha_self);         \
-    hipLaunchKernelGGL((gat_input_gather_kernel<TT, HH>), dim3((unsigned)gblocks), dim3(256), 0, st, (const TT*)src,   \
-                       d, ids, gid_e, alpha_e, alpha_self, chunks, rowptr, rowend, n_rows_dev, nkc, head_stride, z);    \
-  } while (0)
-#define GIGL_GAT_IN_H(TT)                                                                                               \
-  do {                                                                                                                  \
-    if (H == 1) GIGL_GAT_IN(TT, 1);                                                                                     \
-    else if (H == 2) GIGL_GAT_IN(TT, 2);                                                                                \
-    else GIGL_GAT_IN(TT, 4);                                                                                            \
-  } while (0)
-    if (src_dtype == GIGL_DTYPE_F32) GIGL_GAT_IN_H(float);
-    else GIGL_GAT_IN_H(__half);
-#undef GIGL_GAT_IN_H
-#undef GIGL_GAT_IN
+    dispatch_type<float, __half>(src_dtype, [&](auto t) {
+      dispatch_int<1, 2, 4>(H, [&](auto hh) {
+        using T = typename decltype(t)::type;
+        constexpr int HH = decltype(hh)::value;
+        hipLaunchKernelGGL((gat_score_kernel<T, HH>), dim3((unsigned)sblocks, (unsigned)chunks), dim3(256), 0, st,
+                           (const T*)src, d, ids, n_src_dev, cap_nodes, u, sp);
+        hipLaunchKernelGGL((gat_edge_weight_kernel<HH>), dim3((unsigned)wblocks), dim3(256), 0, st, ids, sp, chunks,
+                           cap_nodes, rowptr, rowend, col, n_rows_dev, negative_slope, gid_e, alpha_e, alpha_self);
+        hipLaunchKernelGGL((gat_input_gather_kernel<T, HH>), dim3((unsigned)gblocks), dim3(256), 0, st, (const T*)src,
+                           d, ids, gid_e, alpha_e, alpha_self, chunks, rowptr, rowend, n_rows_dev, nkc, head_stride, z);
+      });
+    });
     GIGL_HIP_CHECK(ctx, hipGetLastError());
   }
   // the heads' projections in one launch (grid.y = head): z_h [rows][d] (tiled) x W_h^T -> columns [h*C, +C) of out
@@ -5083,6 +4985,56 @@ static int32_t gat_edge_terms_ok(gigl_ctx* ctx, const gigl_gat_edge_terms* edge,
   return GIGL_OK;
 }
 
+// the kernels' view of the caller's edge terms (checked by gat_edge_terms_ok); NULL: no edge terms
+static GatEdgeIn gat_edge_in(const gigl_gat_edge_terms* edge) {
+  GatEdgeIn ed;
+  if (edge) {
+    ed.eid = edge->eid;
+    ed.table = edge->table;
+    ed.v = edge->att_edge_folded;
+    ed.De = edge->edge_dim;
+    ed.ze = edge->w_edge_msg ? edge->ze : nullptr;
+  }
+  return ed;
+}
+static GatEdgeBwd gat_edge_bwd(const gigl_gat_edge_terms* edge, const float* dze, float* dv) {
+  GatEdgeBwd ed;
+  if (edge) {
+    ed.eid = edge->eid;
+    ed.table = edge->table;
+    ed.v = edge->att_edge_folded;
+    ed.De = edge->edge_dim;
+    ed.dze = edge->w_edge_msg ? dze : nullptr;
+    ed.dv = dv;
+  }
+  return ed;
+}
+
+// gat_input_online_kernel over a shape gat_input_shape_ok accepts: one wave per row, four rows per workgroup.  nkc != 0: z
+// in the projection's tiled layout (nkc chunks per row tile), else plain rows; head_stride floats between the heads' z
+static void launch_gat_input_online(hipStream_t st, const void* src, int32_t src_dtype, int d, const uint32_t* gather_ids,
+                                    const int32_t* n_local_dev, const float* u, int heads, float slope, const int32_t* rowptr,
+                                    const int32_t* rowend, const int32_t* col, const int32_t* n_rows_dev, int64_t rows_cap,
+                                    int nkc, int64_t head_stride, float* z, const gigl_gat_edge_terms* edge) {
+  const GatEdgeIn ed = gat_edge_in(edge);
+  int64_t blocks = (rows_cap + 3) / 4;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  dispatch_type<float, __half>(src_dtype, [&](auto t) {
+    dispatch_int<1, 2, 4>(heads, [&](auto hh) {
+      dispatch_int<1, 2, 3, 4>((d + 255) / 256, [&](auto pp) {
+        dispatch_bool(edge != nullptr, [&](auto e) {
+          using T = typename decltype(t)::type;
+          constexpr int HH = decltype(hh)::value, PP = decltype(pp)::value;
+          constexpr bool EDGE = decltype(e)::value;
+          hipLaunchKernelGGL((gat_input_online_kernel<T, PP, HH, EDGE>), dim3((unsigned)blocks), dim3(256), 0, st,
+                             (const T*)src, d, gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, slope, nkc,
+                             head_stride, z, ed);
+        });
+      });
+    });
+  });
+}
+
 int32_t gigl_gat_input_aggregate_edge(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d, const uint32_t* gather_ids,
                                       const float* u, int32_t heads, float negative_slope, const int32_t* rowptr,
                                       const int32_t* rowend, const int32_t* col, const int32_t* n_rows_dev, int64_t rows_cap,
@@ -5092,56 +5044,15 @@ int32_t gigl_gat_input_aggregate_edge(gigl_ctx* ctx, const void* src, int32_t sr
   GIGL_REQUIRE(ctx, d > 0 && rows_cap >= 0, "bad sizes");
   int32_t rc = gat_input_shape_ok(ctx, d, heads, src_dtype, "gigl_gat_input_aggregate");
   if (rc != GIGL_OK) return rc;
-  GatEdgeIn ed;
   if (edge) {
     rc = gat_edge_terms_ok(ctx, edge, "gigl_gat_input_aggregate_edge");
     if (rc != GIGL_OK) return rc;
-    ed.eid = edge->eid;
-    ed.table = edge->table;
-    ed.v = edge->att_edge_folded;
-    ed.De = edge->edge_dim;
-    ed.ze = edge->w_edge_msg ? edge->ze : nullptr;
   }
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (rows_cap == 0) return GIGL_OK;
   gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
-  hipStream_t st = ctx->stream;
-  const int P = (d + 255) / 256, H = heads;
-  const int64_t head_stride = rows_cap * d;
-  const int32_t* n_local_dev = nullptr;
-  const int nkc = 0;
-  const float slope = negative_slope;
-  int64_t blocks = (rows_cap + 3) / 4;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-#define GIGL_GAT_AG(TT, PP, HH)                                                                                        \
-  do {                                                                                                                  \
-    if (edge)                                                                                                           \
-      hipLaunchKernelGGL((gat_input_online_kernel<TT, PP, HH, true>), dim3((unsigned)blocks), dim3(256), 0, st,        \
-                         (const TT*)src, d, gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, slope, nkc,    \
-                         head_stride, z, ed);                                                                           \
-    else                                                                                                                \
-      hipLaunchKernelGGL((gat_input_online_kernel<TT, PP, HH>), dim3((unsigned)blocks), dim3(256), 0, st,              \
-                         (const TT*)src, d, gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, slope, nkc,    \
-                         head_stride, z, ed);                                                                           \
-  } while (0)
-#define GIGL_GAT_AG_P(TT, HH)                                                                                          \
-  do {                                                                                                                  \
-    if (P == 1) GIGL_GAT_AG(TT, 1, HH);                                                                                \
-    else if (P == 2) GIGL_GAT_AG(TT, 2, HH);                                                                           \
-    else if (P == 3) GIGL_GAT_AG(TT, 3, HH);                                                                           \
-    else GIGL_GAT_AG(TT, 4, HH);                                                                                       \
-  } while (0)
-#define GIGL_GAT_AG_H(TT)                                                                                              \
-  do {                                                                                                                  \
-    if (H == 1) GIGL_GAT_AG_P(TT, 1);                                                                                  \
-    else if (H == 2) GIGL_GAT_AG_P(TT, 2);                                                                             \
-    else GIGL_GAT_AG_P(TT, 4);                                                                                         \
-  } while (0)
-  if (src_dtype == GIGL_DTYPE_F32) GIGL_GAT_AG_H(float);
-  else GIGL_GAT_AG_H(__half);
-#undef GIGL_GAT_AG_H
-#undef GIGL_GAT_AG_P
-#undef GIGL_GAT_AG
+  launch_gat_input_online(ctx->stream, src, src_dtype, d, gather_ids, nullptr, u, heads, negative_slope, rowptr, rowend, col,
+                          n_rows_dev, rows_cap, 0, rows_cap * d, z, edge);  // (plain rows: head h's z is rows_cap * d floats on)
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -5174,7 +5085,6 @@ int32_t gigl_gat_input_aggregate_backward_edge(gigl_ctx* ctx, const void* src, i
   GIGL_REQUIRE(ctx, d > 0 && rows_cap >= 0, "bad sizes");
   int32_t rc = gat_input_shape_ok(ctx, d, heads, src_dtype, "gigl_gat_input_aggregate_backward");
   if (rc != GIGL_OK) return rc;
-  GatEdgeBwd ed;
   if (edge) {
     rc = gat_edge_terms_ok(ctx, edge, "gigl_gat_input_aggregate_backward_edge");
     if (rc != GIGL_OK) return rc;
@@ -5182,13 +5092,8 @@ int32_t gigl_gat_input_aggregate_backward_edge(gigl_ctx* ctx, const void* src, i
     if (heads == 4 && d > 768)
       return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "gigl_gat_input_aggregate_backward_edge: four heads over rows wider than 768 "
                        "floats (d=%d) are not built with edge features", d);
-    ed.eid = edge->eid;
-    ed.table = edge->table;
-    ed.v = edge->att_edge_folded;
-    ed.De = edge->edge_dim;
-    ed.dze = edge->w_edge_msg ? dze : nullptr;
-    ed.dv = dv;
   }
+  const GatEdgeBwd ed = gat_edge_bwd(edge, dze, dv);
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (rows_cap == 0) return GIGL_OK;
   gigl_prof_scope ps(ctx, GIGL_K_GATHER_BWD);
@@ -5198,27 +5103,16 @@ int32_t gigl_gat_input_aggregate_backward_edge(gigl_ctx* ctx, const void* src, i
   const float slope = negative_slope;
   int64_t blocks = (rows_cap + 3) / 4;
   if (blocks > 256 * 2) blocks = 256 * 2;  // (two workgroups per CU fill its registers; fewer workgroups = fewer final atomics)
-#define GIGL_GAT_BW(TT, PP, HH)                                                                                        \
-  launch_gat_input_backward<TT, PP, HH>(edge != nullptr, (unsigned)blocks, st, (const TT*)src, d, gather_ids, u, rowptr, \
-                                        rowend, col, n_rows_dev, slope, dz, head_stride, du, ed)
-#define GIGL_GAT_BW_P(TT, HH)                                                                                          \
-  do {                                                                                                                  \
-    if (P == 1) GIGL_GAT_BW(TT, 1, HH);                                                                                \
-    else if (P == 2) GIGL_GAT_BW(TT, 2, HH);                                                                           \
-    else if (P == 3) GIGL_GAT_BW(TT, 3, HH);                                                                           \
-    else GIGL_GAT_BW(TT, 4, HH);                                                                                       \
-  } while (0)
-#define GIGL_GAT_BW_H(TT)                                                                                              \
-  do {                                                                                                                  \
-    if (H == 1) GIGL_GAT_BW_P(TT, 1);                                                                                  \
-    else if (H == 2) GIGL_GAT_BW_P(TT, 2);                                                                             \
-    else GIGL_GAT_BW_P(TT, 4);                                                                                         \
-  } while (0)
-  if (src_dtype == GIGL_DTYPE_F32) GIGL_GAT_BW_H(float);
-  else GIGL_GAT_BW_H(__half);
-#undef GIGL_GAT_BW_H
-#undef GIGL_GAT_BW_P
-#undef GIGL_GAT_BW
+  dispatch_type<float, __half>(src_dtype, [&](auto t) {
+    dispatch_int<1, 2, 4>(H, [&](auto hh) {
+      dispatch_int<1, 2, 3, 4>(P, [&](auto pp) {
+        using T = typename decltype(t)::type;
+        launch_gat_input_backward<T, decltype(pp)::value, decltype(hh)::value>(edge != nullptr, (unsigned)blocks, st, (const T*)src, d,
+                                                                               gather_ids, u, rowptr, rowend, col, n_rows_dev,
+                                                                               slope, dz, head_stride, du, ed);
+      });
+    });
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -5264,10 +5158,8 @@ int32_t gigl_gat_input_layer_fused_hs(gigl_ctx* ctx, const void* src, int32_t sr
   GIGL_REQUIRE(ctx, src && gather_ids && w && att_src && att_dst && rowptr && rowend && col && n_rows_dev && scratch && out,
                "null argument");
   if (edge) {
-    GIGL_REQUIRE(ctx, edge->eid && edge->table && edge->att_edge_folded && (!edge->w_edge_msg || edge->ze), "null edge term");
-    if (edge->edge_dim < 1 || edge->edge_dim > GAT_INPUT_MAX_EDGE_DIM)
-      return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "gigl_gat_input_layer_fused: edge_dim %d outside [1,%d] (a lane per "
-                       "component of the edge messages)", edge->edge_dim, GAT_INPUT_MAX_EDGE_DIM);
+    const int32_t rc = gat_edge_terms_ok(ctx, edge, "gigl_gat_input_layer_fused");
+    if (rc != GIGL_OK) return rc;
   }
   GIGL_REQUIRE(ctx, d > 0 && heads > 0 && channels > 0 && rows_cap >= 0, "bad sizes");
   GIGL_REQUIRE(ctx, src_dtype == GIGL_DTYPE_F32 || src_dtype == GIGL_DTYPE_F16, "bad dtype %d", src_dtype);
@@ -5288,45 +5180,8 @@ int32_t gigl_gat_input_layer_fused_hs(gigl_ctx* ctx, const void* src, int32_t sr
     gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
     hipLaunchKernelGGL(gat_fold_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)(2 * H)), dim3(256), 0, st, w, att_src,
                        att_dst, H, C, d, u);
-    int64_t blocks = (rows_cap + 3) / 4;  // one wave per row, four rows per workgroup
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    GatEdgeIn ed;
-    if (edge) {
-      ed.eid = edge->eid;
-      ed.table = edge->table;
-      ed.v = edge->att_edge_folded;
-      ed.De = edge->edge_dim;
-      ed.ze = edge->w_edge_msg ? edge->ze : nullptr;
-    }
-#define GIGL_GAT_ON(TT, PP, HH)                                                                                         \
-  do {                                                                                                                  \
-    if (edge)                                                                                                           \
-      hipLaunchKernelGGL((gat_input_online_kernel<TT, PP, HH, true>), dim3((unsigned)blocks), dim3(256), 0, st,        \
-                         (const TT*)src, d, gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, negative_slope, \
-                         nkc, head_stride, z, ed);                                                                      \
-    else                                                                                                                \
-      hipLaunchKernelGGL((gat_input_online_kernel<TT, PP, HH>), dim3((unsigned)blocks), dim3(256), 0, st,              \
-                         (const TT*)src, d, gather_ids, n_local_dev, u, rowptr, rowend, col, n_rows_dev, negative_slope, \
-                         nkc, head_stride, z, ed);                                                                      \
-  } while (0)
-#define GIGL_GAT_ON_P(TT, HH)                                                                                           \
-  do {                                                                                                                  \
-    if (P == 1) GIGL_GAT_ON(TT, 1, HH);                                                                                 \
-    else if (P == 2) GIGL_GAT_ON(TT, 2, HH);                                                                            \
-    else if (P == 3) GIGL_GAT_ON(TT, 3, HH);                                                                            \
-    else GIGL_GAT_ON(TT, 4, HH);                                                                                        \
-  } while (0)
-#define GIGL_GAT_ON_H(TT)                                                                                               \
-  do {                                                                                                                  \
-    if (H == 1) GIGL_GAT_ON_P(TT, 1);                                                                                   \
-    else if (H == 2) GIGL_GAT_ON_P(TT, 2);                                                                              \
-    else GIGL_GAT_ON_P(TT, 4);                                                                                          \
-  } while (0)
-    if (src_dtype == GIGL_DTYPE_F32) GIGL_GAT_ON_H(float);
-    else GIGL_GAT_ON_H(__half);
-#undef GIGL_GAT_ON_H
-#undef GIGL_GAT_ON_P
-#undef GIGL_GAT_ON
+    launch_gat_input_online(st, src, src_dtype, d, gather_ids, n_local_dev, u, H, negative_slope, rowptr, rowend, col,
+                            n_rows_dev, rows_cap, nkc, head_stride, z, edge);
     GIGL_HIP_CHECK(ctx, hipGetLastError());
   }
   if (edge && edge->w_edge_msg) {
@@ -5417,13 +5272,11 @@ int32_t gigl_gat_aggregate_backward_indexed(gigl_ctx* ctx, const float* h, const
                      n_nodes_dev, 1, channels, a_src, a_dst);
   int64_t blocks = (rows_cap + 3) / 4;
   if (blocks > 256 * 8) blocks = 256 * 8;
-#define GAT_BWD_IX(VV)                                                                                                       \
-  hipLaunchKernelGGL((gat_backward_indexed_kernel<VV>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, h, a_src, a_dst,   \
-                     rowptr, rowend, col, n_rows_dev, channels, negative_slope, out_pre, dout, eid, table, edge_dim,         \
-                     att_edge_folded, dze, dh, d_alpha_src, d_alpha_dst, dv, z_out)
-  if (channels <= 256) GAT_BWD_IX(1);
-  else GAT_BWD_IX(2);
-#undef GAT_BWD_IX
+  dispatch_int<1, 2>(channels <= 256 ? 1 : 2, [&](auto vv) {
+    hipLaunchKernelGGL((gat_backward_indexed_kernel<decltype(vv)::value>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, h,
+                       a_src, a_dst, rowptr, rowend, col, n_rows_dev, channels, negative_slope, out_pre, dout, eid, table,
+                       edge_dim, att_edge_folded, dze, dh, d_alpha_src, d_alpha_dst, dv, z_out);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }

@@ -10,6 +10,7 @@
 // One wave per destination row; lane l of chunk row v owns the float4 of channels [4q, 4q+4), q = 64 v + l; a head
 // is C/4 adjacent lanes (C/4 a power of two <= 64), so all heads advance together and a source row is read once.
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -287,13 +288,10 @@ int32_t gigl_gatv2_aggregate_edge(gigl_ctx* ctx, const float* xl, const float* x
   int64_t blocks = (rows_cap + 3) / 4;
   if (blocks > 256 * 16) blocks = 256 * 16;
   const int HC = heads * channels;
-#define GIGL_V2_FWD(VV)                                                                                              \
-  hipLaunchKernelGGL((gatv2_forward_kernel<VV>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, xl, xr, att,    \
-                     rowptr, rowend, col, n_rows_dev, HC, group, negative_slope, bias, act, edge_rows, out)
-  if (V == 1) GIGL_V2_FWD(1);
-  else if (V == 2) GIGL_V2_FWD(2);
-  else GIGL_V2_FWD(4);
-#undef GIGL_V2_FWD
+  dispatch_int<1, 2, 4>(V, [&](auto vv) {
+    hipLaunchKernelGGL((gatv2_forward_kernel<decltype(vv)::value>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, xl, xr,
+                       att, rowptr, rowend, col, n_rows_dev, HC, group, negative_slope, bias, act, edge_rows, out);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -326,14 +324,11 @@ int32_t gigl_gatv2_aggregate_edge_backward(gigl_ctx* ctx, const float* xl, const
   int64_t blocks = (rows_cap + 3) / 4;
   if (blocks > 256 * 4) blocks = 256 * 4;  // (every wave ends with one atomic per att component)
   const int HC = heads * channels;
-#define GIGL_V2_BWD(VV)                                                                                              \
-  hipLaunchKernelGGL((gatv2_backward_kernel<VV>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, xl, xr, att,   \
-                     rowptr, rowend, col, n_rows_dev, HC, group, negative_slope, out_pre, dout, dxl, dxr, datt, edge_rows,  \
-                     dedge_rows)
-  if (V == 1) GIGL_V2_BWD(1);
-  else if (V == 2) GIGL_V2_BWD(2);
-  else GIGL_V2_BWD(4);
-#undef GIGL_V2_BWD
+  dispatch_int<1, 2, 4>(V, [&](auto vv) {
+    hipLaunchKernelGGL((gatv2_backward_kernel<decltype(vv)::value>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, xl, xr,
+                       att, rowptr, rowend, col, n_rows_dev, HC, group, negative_slope, out_pre, dout, dxl, dxr, datt,
+                       edge_rows, dedge_rows);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -597,13 +592,10 @@ int32_t gigl_transformer_aggregate_edge(gigl_ctx* ctx, const float* q, const flo
   if (blocks > 256 * 16) blocks = 256 * 16;
   const int HC = heads * channels;
   const float scale = 1.0f / sqrtf((float)channels);
-#define GIGL_TR_FWD(VV)                                                                                                \
-  hipLaunchKernelGGL((transformer_edge_forward_kernel<VV>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, q, k, v, \
-                     edge_rows, rowptr, rowend, col, n_rows_dev, HC, group, scale, out)
-  if (V == 1) GIGL_TR_FWD(1);
-  else if (V == 2) GIGL_TR_FWD(2);
-  else GIGL_TR_FWD(4);
-#undef GIGL_TR_FWD
+  dispatch_int<1, 2, 4>(V, [&](auto vv) {
+    hipLaunchKernelGGL((transformer_edge_forward_kernel<decltype(vv)::value>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
+                       q, k, v, edge_rows, rowptr, rowend, col, n_rows_dev, HC, group, scale, out);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -627,13 +619,11 @@ int32_t gigl_transformer_aggregate_edge_backward(gigl_ctx* ctx, const float* q, 
   if (blocks > 256 * 16) blocks = 256 * 16;
   const int HC = heads * channels;
   const float scale = 1.0f / sqrtf((float)channels);
-#define GIGL_TR_BWD(VV)                                                                                                \
-  hipLaunchKernelGGL((transformer_edge_backward_kernel<VV>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, q, k,  \
-                     v, edge_rows, rowptr, rowend, col, n_rows_dev, HC, group, scale, out, dout, dq, dk, dv, dedge_rows)
-  if (V == 1) GIGL_TR_BWD(1);
-  else if (V == 2) GIGL_TR_BWD(2);
-  else GIGL_TR_BWD(4);
-#undef GIGL_TR_BWD
+  dispatch_int<1, 2, 4>(V, [&](auto vv) {
+    hipLaunchKernelGGL((transformer_edge_backward_kernel<decltype(vv)::value>), dim3((unsigned)blocks), dim3(256), 0,
+                       ctx->stream, q, k, v, edge_rows, rowptr, rowend, col, n_rows_dev, HC, group, scale, out, dout, dq, dk, dv,
+                       dedge_rows);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }

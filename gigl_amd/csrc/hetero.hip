@@ -12,6 +12,7 @@
 // owning float4 chunks of the H*D-wide row so all heads advance together and each source row is read once, coalesced.
 // HBM-bound: per aggregated edge one (SimpleHGN) or two (HGT: k' and v') source rows of 4*H*D bytes.
 #include "common.h"
+#include "dispatch.h"
 
 #include <cstdlib>
 
@@ -424,26 +425,20 @@ int32_t gigl_hgt_aggregate_act(gigl_ctx* ctx, const float* q, const float* k, co
     if (!no_pack && (g == 8 || g == 16 || g == 32) && dim / 4 <= 16) {
       const int rpw = 64 / g;
       const dim3 pgrid((unsigned)((n_dst + 4 * rpw - 1) / (4 * rpw))), pblock(256);
-#define GIGL_LAUNCH_HGT_PACKED(G)                                                                                     \
-  hipLaunchKernelGGL(hgt_aggregate_packed_kernel<G>, pgrid, pblock, 0, ctx->stream, q, k, v, heads, dim, rowptr, col, \
-                     etype, p_rel, n_dst, out, gelu ? 1 : 0)
-      if (g == 8) GIGL_LAUNCH_HGT_PACKED(8);
-      else if (g == 16) GIGL_LAUNCH_HGT_PACKED(16);
-      else GIGL_LAUNCH_HGT_PACKED(32);
-#undef GIGL_LAUNCH_HGT_PACKED
+      dispatch_int<8, 16, 32>(g, [&](auto gg) {
+        hipLaunchKernelGGL(hgt_aggregate_packed_kernel<decltype(gg)::value>, pgrid, pblock, 0, ctx->stream, q, k, v, heads, dim,
+                           rowptr, col, etype, p_rel, n_dst, out, gelu ? 1 : 0);
+      });
       GIGL_HIP_CHECK(ctx, hipGetLastError());
       return GIGL_OK;
     }
   }
   const int passes = (heads * dim + 255) / 256;
   const dim3 grid((unsigned)((n_dst + 3) / 4)), block(256);
-#define GIGL_LAUNCH_HGT(P)                                                                                          \
-  hipLaunchKernelGGL(hgt_aggregate_kernel<P>, grid, block, 0, ctx->stream, q, k, v, heads, dim, rowptr, col, etype, \
-                     p_rel, n_dst, out, gelu ? 1 : 0)
-  if (passes == 1) GIGL_LAUNCH_HGT(1);
-  else if (passes == 2) GIGL_LAUNCH_HGT(2);
-  else GIGL_LAUNCH_HGT(4);
-#undef GIGL_LAUNCH_HGT
+  dispatch_int<1, 2, 4>(passes, [&](auto p) {
+    hipLaunchKernelGGL(hgt_aggregate_kernel<decltype(p)::value>, grid, block, 0, ctx->stream, q, k, v, heads, dim, rowptr, col,
+                       etype, p_rel, n_dst, out, gelu ? 1 : 0);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -458,13 +453,10 @@ int32_t gigl_weighted_aggregate(gigl_ctx* ctx, const float* alpha, const float* 
   if (n_dst == 0) return GIGL_OK;
   const int passes = (heads * dim + 255) / 256;
   const dim3 grid((unsigned)((n_dst + 3) / 4)), block(256);
-#define GIGL_LAUNCH_WA(P)                                                                                         \
-  hipLaunchKernelGGL(weighted_aggregate_kernel<P>, grid, block, 0, ctx->stream, alpha, v, heads, dim, rowptr, col, \
-                     n_dst, out)
-  if (passes == 1) GIGL_LAUNCH_WA(1);
-  else if (passes == 2) GIGL_LAUNCH_WA(2);
-  else GIGL_LAUNCH_WA(4);
-#undef GIGL_LAUNCH_WA
+  dispatch_int<1, 2, 4>(passes, [&](auto p) {
+    hipLaunchKernelGGL(weighted_aggregate_kernel<decltype(p)::value>, grid, block, 0, ctx->stream, alpha, v, heads, dim, rowptr,
+                       col, n_dst, out);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -504,13 +496,10 @@ int32_t gigl_hgt_aggregate_backward(gigl_ctx* ctx, const float* q, const float* 
   if (n_dst == 0) return GIGL_OK;
   const int passes = (heads * dim + 255) / 256;
   const dim3 grid((unsigned)((n_dst + 3) / 4)), block(256);
-#define GIGL_LAUNCH_HGTB(P)                                                                                          \
-  hipLaunchKernelGGL(hgt_aggregate_backward_kernel<P>, grid, block, 0, ctx->stream, q, k, v, heads, dim, rowptr, col, \
-                     etype, p_rel, n_dst, out, dout, dq, dk, dv, dp_rel)
-  if (passes == 1) GIGL_LAUNCH_HGTB(1);
-  else if (passes == 2) GIGL_LAUNCH_HGTB(2);
-  else GIGL_LAUNCH_HGTB(4);
-#undef GIGL_LAUNCH_HGTB
+  dispatch_int<1, 2, 4>(passes, [&](auto p) {
+    hipLaunchKernelGGL(hgt_aggregate_backward_kernel<decltype(p)::value>, grid, block, 0, ctx->stream, q, k, v, heads, dim,
+                       rowptr, col, etype, p_rel, n_dst, out, dout, dq, dk, dv, dp_rel);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -526,13 +515,10 @@ int32_t gigl_weighted_aggregate_backward(gigl_ctx* ctx, const float* alpha, cons
   if (n_dst == 0) return GIGL_OK;
   const int passes = (heads * dim + 255) / 256;
   const dim3 grid((unsigned)((n_dst + 3) / 4)), block(256);
-#define GIGL_LAUNCH_WAB(P)                                                                                            \
-  hipLaunchKernelGGL(weighted_aggregate_backward_kernel<P>, grid, block, 0, ctx->stream, alpha, v, heads, dim, rowptr, \
-                     col, n_dst, dout, dalpha, dv)
-  if (passes == 1) GIGL_LAUNCH_WAB(1);
-  else if (passes == 2) GIGL_LAUNCH_WAB(2);
-  else GIGL_LAUNCH_WAB(4);
-#undef GIGL_LAUNCH_WAB
+  dispatch_int<1, 2, 4>(passes, [&](auto p) {
+    hipLaunchKernelGGL(weighted_aggregate_backward_kernel<decltype(p)::value>, grid, block, 0, ctx->stream, alpha, v, heads, dim,
+                       rowptr, col, n_dst, dout, dalpha, dv);
+  });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }

@@ -27,6 +27,7 @@
 //   9 row_sort_big   one workgroup per queued row, bitonic sort in LDS (<= 16384 entries)
 // Rows keep their pre-dedup capacity: row i is col[rowptr[i] .. rowend[i]).
 #include "common.h"
+#include "dispatch.h"
 
 #include <mutex>
 
@@ -2606,12 +2607,11 @@ int32_t union_build_lg3(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* t
   {
     gigl_prof_scope ps(ctx, GIGL_K_UNION_INSERT);
     hipLaunchKernelGGL(lg3_init_kernel, dim3(256), dim3(256), 0, st, a.rowcnt, T_in, zeros, zero_words, out->meta);
-    if (lg3_nt == 512)
-      hipLaunchKernelGGL(lg3_dedup_kernel<512>, dim3((unsigned)(n_groups * P)), dim3(512), lds_bytes, st, a, tile_counts,
+    dispatch_int<512, 1024>(lg3_nt, [&](auto nt) {
+      constexpr int NT = decltype(nt)::value;
+      hipLaunchKernelGGL(lg3_dedup_kernel<NT>, dim3((unsigned)(n_groups * P)), dim3(NT), lds_bytes, st, a, tile_counts,
                          n_tiles, ticket_count, sort_count, tiny_count);
-    else
-      hipLaunchKernelGGL(lg3_dedup_kernel<1024>, dim3((unsigned)(n_groups * P)), dim3(1024), lds_bytes, st, a, tile_counts,
-                         n_tiles, ticket_count, sort_count, tiny_count);
+    });
   }
   {
     gigl_prof_scope ps(ctx, GIGL_K_UNION_NODES);
@@ -2638,15 +2638,15 @@ int32_t union_build_lg3(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* t
     if (blocks < 64) blocks = 64;
     hipLaunchKernelGGL(lg2_row_sort_kernel, dim3((unsigned)blocks), dim3(256), 0, st, sort_rows, sort_count, out->rowptr,
                        out->rowend, out->col, big_rows, big_count, edge_counters, EC_STRIDE);
-    if (lg_big_cap_wide()) {
+    const bool wide = lg_big_cap_wide();  // (the wide capacity's LDS is past the default limit: opted in)
+    if (wide)
       GIGL_HIP_CHECK(ctx, lds_opt_in(ctx->device, 4, (const void*)lg2_row_sort_big_kernel<BIG_ROW_CAP>, 2 * BIG_ROW_CAP * (int)sizeof(int32_t)));
-      hipLaunchKernelGGL(lg2_row_sort_big_kernel<BIG_ROW_CAP>, dim3(8), dim3(1024), 2 * BIG_ROW_CAP * sizeof(int32_t), st, out->rowptr,
-                       out->rowend, out->col, big_rows, big_count, out->meta + GIGL_META_OVERFLOW, edge_counters,
-                       ticket_big, out->meta, EC_STRIDE, (const int32_t*)tile_edges, n_tiles);
-    } else
-    hipLaunchKernelGGL(lg2_row_sort_big_kernel<LG_BIG_CAP>, dim3(8), dim3(1024), 2 * LG_BIG_CAP * sizeof(int32_t), st, out->rowptr,
-                       out->rowend, out->col, big_rows, big_count, out->meta + GIGL_META_OVERFLOW, edge_counters,
-                       ticket_big, out->meta, EC_STRIDE, (const int32_t*)tile_edges, n_tiles);
+    dispatch_int<BIG_ROW_CAP, LG_BIG_CAP>(wide ? BIG_ROW_CAP : LG_BIG_CAP, [&](auto cap) {
+      constexpr int CAP = decltype(cap)::value;
+      hipLaunchKernelGGL(lg2_row_sort_big_kernel<CAP>, dim3(8), dim3(1024), 2 * CAP * sizeof(int32_t), st, out->rowptr,
+                         out->rowend, out->col, big_rows, big_count, out->meta + GIGL_META_OVERFLOW, edge_counters,
+                         ticket_big, out->meta, EC_STRIDE, (const int32_t*)tile_edges, n_tiles);
+    });
   }
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
