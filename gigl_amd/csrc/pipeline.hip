@@ -1748,6 +1748,13 @@ int32_t train_run_part(gigl_ctx* ctx, hipGraphExec_t* exec, bool* warm, const st
   return GIGL_OK;
 }
 
+// a plan's private ctx (own arena) follows the caller's stream: every launch of the step goes there
+static int32_t train_bind_stream(gigl_ctx* ctx, gigl_ctx* lctx) {
+  if (lctx->stream == ctx->stream && !lctx->own_stream) return GIGL_OK;
+  const int32_t rs = gigl_ctx_set_stream(lctx, ctx->stream);
+  return rs == GIGL_OK ? GIGL_OK : gigl_fail(ctx, rs, "%s", gigl_last_error(lctx));
+}
+
 // the graph part of workspace k for `roots`, on the side stream; ev_graph[k] marks its end
 int32_t train_graph_part(gigl_sage_train_plan* t, int k, const uint32_t* roots, int32_t sampling_seed, int32_t mode) {
   gigl_ctx* sc = t->side[k];
@@ -1926,10 +1933,8 @@ int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* t, const uint32_t* root
                      t->loss_slot, loss_out, pa);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, t->ev_graph[k], 0));
-  if (t->lctx->stream != st || t->lctx->own_stream) {
-    const int32_t rs = gigl_ctx_set_stream(t->lctx, st);
-    if (rs != GIGL_OK) return gigl_fail(ctx, rs, "%s", gigl_last_error(t->lctx));
-  }
+  const int32_t rs = train_bind_stream(ctx, t->lctx);
+  if (rs != GIGL_OK) return rs;
   const int32_t rc = train_run_part(t->lctx, &t->exec_layers[k], &t->warm_layers, [&]() { return train_enqueue_layers(t, k); }, 1);
   if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
   GIGL_HIP_CHECK(ctx, hipEventRecord(t->ev_layers[k], st));
@@ -1958,6 +1963,42 @@ int32_t gigl_sage_train_plan_resume(gigl_sage_train_plan* t) {
 // (1 + P) rooted trees, anchor-major (anchor, its P positive slots; a missing positive repeats the anchor and is masked
 // out by pos_cnt); random negatives = n_rn roots.  Everything is capacity-shaped (Q = b P query rows, C = Q + n_rn
 // candidates, validity masks on the device): no host read, no torch kernel, one captured hipGraph per step.
+namespace {
+// The GAT kind's trainable tensors live in ONE table whose index is the one gigl_nablp_train_plan_moments publishes:
+// 4 l + {w, att_src, att_dst, bias} for the core tensors, 8 + 3 l + {lin_edge.weight, att_edge, lin_edge_message.weight}
+// for the edge tensors of gigl_gat_nablp_train_plan_set_edge_features.  gat_slot is the only place that computes it.
+enum GatPart { GAT_W, GAT_ATT_SRC, GAT_ATT_DST, GAT_BIAS, GAT_W_EDGE, GAT_ATT_EDGE, GAT_W_MSG };
+constexpr int GAT_CORE = 8, GAT_TENSORS = 14;
+constexpr int gat_slot(GatPart part, int l) { return part < GAT_W_EDGE ? 4 * l + part : GAT_CORE + 3 * l + (part - GAT_W_EDGE); }
+static_assert(gat_slot(GAT_W, 0) == 0 && gat_slot(GAT_ATT_SRC, 0) == 1 && gat_slot(GAT_ATT_DST, 0) == 2 && gat_slot(GAT_BIAS, 0) == 3 &&
+              gat_slot(GAT_W, 1) == 4 && gat_slot(GAT_ATT_SRC, 1) == 5 && gat_slot(GAT_ATT_DST, 1) == 6 && gat_slot(GAT_BIAS, 1) == 7 &&
+              gat_slot(GAT_W_EDGE, 0) == 8 && gat_slot(GAT_ATT_EDGE, 0) == 9 && gat_slot(GAT_W_MSG, 0) == 10 &&
+              gat_slot(GAT_W_EDGE, 1) == 11 && gat_slot(GAT_ATT_EDGE, 1) == 12 && gat_slot(GAT_W_MSG, 1) == 13,
+              "the published tensor indices");
+// a forked step's second stream accumulates into slots of its own only where its backward writes a gradient directly: the
+// second layer's attention vectors and bias, the edge weights (att_edge's comes from the fold of d v, after the join)
+constexpr bool gat_slot_forks(int s) {
+  return s < GAT_CORE ? s > gat_slot(GAT_W, 1) : s != gat_slot(GAT_ATT_EDGE, 0) && s != gat_slot(GAT_ATT_EDGE, 1);
+}
+struct PlanTensor {
+  float* p = nullptr;                // the parameter: borrowed, UPDATED IN PLACE
+  float* g[2] = {nullptr, nullptr};  // its gradient on the caller's stream; the forked stream's accumulator, or NULL
+  float *m = nullptr, *v = nullptr;  // Adam's moments
+  int64_t n = 0;                     // elements; 0: absent (no Adam entry, no export)
+  void set(float* prm, int64_t elems) { p = prm; n = prm ? elems : 0; }
+};
+// what ONE stream's backward writes: sc[0] is sized for the larger encode (unforked, both encodes use it one after the
+// other), sc[1] for the random negatives' and exists only when the step forks
+struct GatScratch {
+  gigl_ctx* ctx = nullptr;   // the stream's ctx: the plan's lctx (the caller's stream), actx (the forked one)
+  int64_t rows1 = 0, b = 0;  // the row capacities it is sized for: nodes of level <= 1, roots
+  float *alpha = nullptr, *dxw = nullptr, *ds = nullptr, *dd = nullptr, *dh0 = nullptr, *dh0s = nullptr, *dz = nullptr;
+  float* du = nullptr;  // d u, laid out as u (out of the plan's cleared block: both encodes ADD)
+  // edge features: d v laid out as v (out of the edge block), W_msg^T dy [rows1][H][De], layer 1's sum_e alpha_e e [b][De]
+  float *dv = nullptr, *dze = nullptr, *z1 = nullptr;
+};
+}  // namespace
+
 struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, dims, act_last and hyper-parameters only)
   gigl_ctx* ctx = nullptr;
   gigl_ctx* lctx = nullptr;  // private ctx (own arena) bound to the caller's stream: every launch of the step
@@ -1979,15 +2020,13 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
   struct Gat {
     int32_t heads = 1, c0 = 0, c1 = 0, d_in = 0;
     float slope = 0.2f;
-    float *w[2] = {nullptr, nullptr}, *att_src[2] = {nullptr, nullptr}, *att_dst[2] = {nullptr, nullptr},
-          *bias[2] = {nullptr, nullptr};  // borrowed, UPDATED IN PLACE
-    float* g[8] = {nullptr};    // gradients: w0, att_src0, att_dst0, bias0, w1, att_src1, att_dst1, bias1 (both encodes ADD)
-    float* mom[16] = {nullptr};  // Adam's m, v per parameter tensor
-    int64_t n[8] = {0};
-    float *u = nullptr, *du = nullptr;  // folded attention vectors [2H][d] and their gradient
-    // forward state per encode: z [H][rows1][d], xw [rows1][c1], out_pre [b][c1]; backward scratch shared by both
+    PlanTensor tensor[GAT_TENSORS];  // parameters, gradients (both encodes ADD), Adam's moments
+    PlanTensor& at(GatPart part, int l) { return tensor[gat_slot(part, l)]; }
+    const PlanTensor& at(GatPart part, int l) const { return tensor[gat_slot(part, l)]; }
+    float* u = nullptr;  // folded attention vectors [2H][d]
+    // forward state per encode: z [H][rows1][d], xw [rows1][c1], out_pre [b][c1]
     float *z[2] = {nullptr, nullptr}, *xw[2] = {nullptr, nullptr}, *out_pre[2] = {nullptr, nullptr};
-    float *dxw = nullptr, *ds = nullptr, *dd = nullptr, *alpha = nullptr, *dh0 = nullptr, *dh0s = nullptr, *dz = nullptr;
+    GatScratch sc[2];  // backward scratch and accumulators per STREAM (a forked step folds sc[1]'s into sc[0]'s after the join)
     // (as the SAGE plans) the projections' weight gradients stay per-chunk partial sums — per encode: W1's, and W0's / b0's
     // per head — added up inside the Adam kernel; W1^T and the heads' W0^T are laid out once per step
     float* part_w1[2] = {nullptr, nullptr};
@@ -1998,35 +2037,19 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
     float* wt1 = nullptr;
     float* wt0[4] = {nullptr};
     bool parts_pending = false;  // the gradient buffers do not hold the partial sums yet (gigl_gat_nablp_train_plan_grads adds them)
-    // (fork: the random negatives' encode on a stream of its own) its OWN scratch and accumulators — sized by its rows —
-    // so that nothing is shared with the main batch's encode while both run; folded together after the join
-    struct Alt {
-      float *alpha = nullptr, *dxw = nullptr, *ds = nullptr, *dd = nullptr, *dh0 = nullptr, *dh0s = nullptr, *dz = nullptr,
-            *du = nullptr;
-      float* g[8] = {nullptr};
-    } x;
     // edge features (gigl_gat_nablp_train_plan_set_edge_features): the resident table is read in place through the base
-    // plans' eid (written by the graph part); tensor slot 3 l + {0: lin_edge.weight, 1: att_edge, 2: lin_edge_message.weight}
+    // plans' eid (written by the graph part).  The message weight's slot holds NULL (GATConv), its own buffer, or — shared —
+    // lin_edge.weight's parameter AND gradient slots with n == 0: one tensor, one Adam entry, one update
     struct Edge {
       gigl_feat* table = nullptr;
       int32_t De = 0;
-      float *w_edge[2] = {nullptr, nullptr}, *att_edge[2] = {nullptr, nullptr};  // borrowed, UPDATED IN PLACE
-      float* w_msg[2] = {nullptr, nullptr};  // NULL (GATConv), == w_edge[l] (shared: one tensor, one update) or its own buffer
-      float* v = nullptr;                    // folded att_edge, per step: [H][De] of layer 0, then [De] of layer 1
-      float* ge[6] = {nullptr};              // gradients (a shared message weight's join lin_edge.weight's)
-      float* mom[12] = {nullptr};
-      int64_t n[6] = {0};
-      float* dv = nullptr;                   // d v, laid out as v
-      void* zero_base = nullptr;             // ge | dv (| the forked encode's): cleared at the start of every step
+      float* v = nullptr;                 // folded att_edge, per step: [H][De] of layer 0, then [De] of layer 1
+      void* zero_base = nullptr;          // the edge gradients | dv (| the forked stream's): cleared at the start of every step
       size_t zero_bytes = 0;
-      float* ze[2] = {nullptr, nullptr};     // forward state per encode: sum_e alpha_e e of layer 0 [rows1][H][De]
-      float *dze = nullptr, *z1 = nullptr;   // backward scratch: W_msg^T dy [rows1][H][De], layer 1's sum_e alpha_e e [b][De]
-      struct Alt {
-        float* ge[6] = {nullptr};
-        float *dv = nullptr, *dze = nullptr, *z1 = nullptr;
-      } x;
+      float* ze[2] = {nullptr, nullptr};  // forward state per encode: sum_e alpha_e e of layer 0 [rows1][H][De]
     } e;
   } gat;
+  __attribute__((noinline)) gigl_nablp_train_plan() = default;  // (out of line, as ever: the dynamic symbol table stays what it was)
   bool stepped = false;  // a step has run: the plan's shape is final
   // the optimiser's two other knobs (set after create, before the first step: the step is captured)
   AdamClip clip;           // gigl_nablp_train_plan_set_clip_grad_norm
@@ -2581,6 +2604,31 @@ bool lp_fork_setup(gigl_nablp_train_plan* t) {
   return ok;
 }
 
+// a plan of `kind` with what both kinds' creation is handed: batch shape, head, Adam's hyper-parameters (NULL: no memory)
+static gigl_nablp_train_plan* lp_plan_new(gigl_ctx* ctx, int kind, int32_t L, int32_t b_anchors, int32_t num_positives,
+                                   int32_t n_random_negatives, int32_t act_last, int32_t l2_normalize, float temperature,
+                                   int32_t remove_accidental_hits, float lr, float beta1, float beta2, float eps,
+                                   float weight_decay) {
+  gigl_nablp_train_plan* t = new (std::nothrow) gigl_nablp_train_plan();
+  if (!t) return nullptr;
+  t->ctx = ctx;
+  t->kind = kind;
+  t->L = L;
+  t->b = b_anchors;
+  t->P = num_positives;
+  t->n_rn = n_random_negatives;
+  t->normalize = l2_normalize ? 1 : 0;
+  t->remove_hits = remove_accidental_hits ? 1 : 0;
+  t->temperature = temperature;
+  t->act_last = act_last;
+  t->lr = lr;
+  t->beta1 = beta1;
+  t->beta2 = beta2;
+  t->eps = eps;
+  t->wd = weight_decay;
+  return t;
+}
+
 }  // namespace
 
 int32_t gigl_nablp_train_plan_destroy(gigl_nablp_train_plan* t) {
@@ -2634,22 +2682,9 @@ int32_t gigl_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat
                "bad plan shape");
   GIGL_REQUIRE(ctx, dims[hops] <= 512, "embedding width %d: the head keeps a row in 8 registers per lane (<= 512)", dims[hops]);
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  gigl_nablp_train_plan* t = new (std::nothrow) gigl_nablp_train_plan();
+  gigl_nablp_train_plan* t = lp_plan_new(ctx, 0, hops, b_anchors, num_positives, n_random_negatives, act_last, l2_normalize,
+                                         temperature, remove_accidental_hits, lr, beta1, beta2, eps, weight_decay);
   if (!t) return gigl_fail(ctx, GIGL_E_OOM, "host OOM");
-  t->ctx = ctx;
-  t->L = hops;
-  t->b = b_anchors;
-  t->P = num_positives;
-  t->n_rn = n_random_negatives;
-  t->normalize = l2_normalize ? 1 : 0;
-  t->remove_hits = remove_accidental_hits ? 1 : 0;
-  t->temperature = temperature;
-  t->act_last = act_last;
-  t->lr = lr;
-  t->beta1 = beta1;
-  t->beta2 = beta2;
-  t->eps = eps;
-  t->wd = weight_decay;
   const int32_t rc = lp_create_workspaces(t, graph, feat, fanouts, hops, dims, w, bias, act_last);
   if (rc != GIGL_OK) {
     gigl_nablp_train_plan_destroy(t);
@@ -2708,6 +2743,16 @@ int32_t lp_graph_part(gigl_nablp_train_plan* t, int w, const uint32_t* main_root
   wk.fetched = true;
   return GIGL_OK;
 }
+
+// seed and mode are baked into the captured graph parts: drop every workspace's (the training steps' or the evaluation's)
+static void lp_drop_graph_parts(gigl_nablp_train_plan* t, hipGraphExec_t gigl_nablp_train_plan::Work::*exec) {
+  for (auto& wk : t->work)
+    if (wk.*exec) {
+      hipStreamSynchronize(wk.side->stream);
+      hipGraphExecDestroy(wk.*exec);
+      wk.*exec = nullptr;
+    }
+}
 }  // namespace
 
 int32_t gigl_nablp_train_plan_step2(gigl_nablp_train_plan* t, const uint32_t* main_roots, const int32_t* pos_cnt,
@@ -2723,21 +2768,14 @@ int32_t gigl_nablp_train_plan_step2(gigl_nablp_train_plan* t, const uint32_t* ma
   t->gat.parts_pending = t->kind == 1;  // (this step's gradient buffers will lack the partial sums)
   t->stepped = true;
   hipStream_t st = ctx->stream;
-  if (t->lctx->stream != st || t->lctx->own_stream) {
-    const int32_t rs = gigl_ctx_set_stream(t->lctx, st);
-    if (rs != GIGL_OK) return gigl_fail(ctx, rs, "%s", gigl_last_error(t->lctx));
-  }
-  if (t->cap_seed != sampling_seed || t->cap_mode != mode) {  // seed and mode are baked into the captured graph parts
-    for (auto& wk : t->work) {
-      GIGL_HIP_CHECK(ctx, hipStreamSynchronize(wk.side->stream));
-      if (wk.exec_graph) hipGraphExecDestroy(wk.exec_graph);
-      wk.exec_graph = nullptr;
-      wk.fetched = false;  // (what was prefetched was sampled under the old seed)
-    }
+  int32_t rc = train_bind_stream(ctx, t->lctx);
+  if (rc != GIGL_OK) return rc;
+  if (t->cap_seed != sampling_seed || t->cap_mode != mode) {
+    lp_drop_graph_parts(t, &gigl_nablp_train_plan::Work::exec_graph);
+    for (auto& wk : t->work) wk.fetched = false;  // (what was prefetched was sampled under the old seed)
     t->cap_seed = sampling_seed;
     t->cap_mode = mode;
   }
-  int32_t rc = GIGL_OK;
   const int w = t->cur;
   gigl_nablp_train_plan::Work& wk = t->work[w];
   // this step's trees: prefetched by the previous call for exactly these buffers, or sampled now
@@ -2781,17 +2819,10 @@ int32_t gigl_nablp_train_plan_eval(gigl_nablp_train_plan* t, const uint32_t* mai
   for (int i = 0; i < n_ks; ++i) GIGL_REQUIRE(ctx, ks[i] >= 1, "ks must be greater-or-equal to 1 (got %d)", ks[i]);
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  if (t->lctx->stream != st || t->lctx->own_stream) {
-    const int32_t rs = gigl_ctx_set_stream(t->lctx, st);
-    if (rs != GIGL_OK) return gigl_fail(ctx, rs, "%s", gigl_last_error(t->lctx));
-  }
-  if (t->eval_seed != sampling_seed || t->eval_mode != mode) {  // seed and mode are baked into the captured graph parts
-    for (auto& wk : t->work) {
-      if (!wk.exec_graph_eval) continue;
-      GIGL_HIP_CHECK(ctx, hipStreamSynchronize(wk.side->stream));
-      hipGraphExecDestroy(wk.exec_graph_eval);
-      wk.exec_graph_eval = nullptr;
-    }
+  int32_t rc = train_bind_stream(ctx, t->lctx);
+  if (rc != GIGL_OK) return rc;
+  if (t->eval_seed != sampling_seed || t->eval_mode != mode) {
+    lp_drop_graph_parts(t, &gigl_nablp_train_plan::Work::exec_graph_eval);
     t->eval_seed = sampling_seed;
     t->eval_mode = mode;
   }
@@ -2799,7 +2830,7 @@ int32_t gigl_nablp_train_plan_eval(gigl_nablp_train_plan* t, const uint32_t* mai
   const int w = t->work[t->cur].fetched ? (t->cur + 1) % gigl_nablp_train_plan::WS : t->cur;
   gigl_nablp_train_plan::Work& wk = t->work[w];
   GIGL_REQUIRE(ctx, !wk.fetched, "both workspaces hold an announced batch");
-  int32_t rc = lp_graph_part(t, w, main_roots, rn_roots, sampling_seed, mode, true);
+  rc = lp_graph_part(t, w, main_roots, rn_roots, sampling_seed, mode, true);
   if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(wk.side));
   GIGL_HIP_CHECK(ctx, hipMemcpyAsync(t->pos_cnt, pos_cnt, (size_t)t->b * 4, hipMemcpyDeviceToDevice, st));
   GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, wk.ev_graph, 0));
@@ -2878,6 +2909,44 @@ __global__ __launch_bounds__(256) void lp_add2_kernel(const float* __restrict__ 
                                                       float* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = a[i] + b[i];
 }
+
+// ---- what walks the GAT kind's tensor table, slots [first, last)
+// the slots' gradients of one stream — every tensor on the caller's (alt 0), the forking ones on the second (alt 1) — laid
+// out from float `at` of a cleared block; -> the next free float.  block == NULL only measures.
+static size_t gat_grads_carve(PlanTensor* tb, int first, int last, int alt, float* block, size_t at) {
+  for (int s = first; s < last; ++s)
+    if (!alt || gat_slot_forks(s)) {
+      tb[s].g[alt] = block ? block + at : nullptr;
+      at += (size_t)tb[s].n;
+    }
+  return at;
+}
+// Adam's m, v: zero
+static bool gat_moments_alloc(std::vector<void*>& owned, PlanTensor* tb, int first, int last) {
+  for (int s = first; s < last; ++s)
+    for (float** q : {&tb[s].m, &tb[s].v}) {
+      const size_t bytes = (size_t)(tb[s].n ? tb[s].n : 1) * 4;
+      *q = (float*)train_alloc(owned, bytes);
+      if (!*q || hipMemset(*q, 0, bytes) != hipSuccess) return false;
+    }
+  return true;
+}
+static int32_t gat_moments_adopt(gigl_ctx* ctx, PlanTensor* dst, const PlanTensor* src, int first, int last, const char* mismatch) {
+  for (int s = first; s < last; ++s) {
+    GIGL_REQUIRE(ctx, dst[s].n == src[s].n, "%s", mismatch);
+    const size_t bytes = (size_t)(dst[s].n ? dst[s].n : 1) * 4;
+    GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst[s].m, src[s].m, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst[s].v, src[s].v, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  return GIGL_OK;
+}
+// a tensor's gradient of the last step -> dst (NULL: skipped): both streams' shares, `blocks` workgroups for the second's
+static int32_t gat_grad_export(gigl_ctx* ctx, const PlanTensor& x, float* dst, unsigned blocks) {
+  if (!dst || !x.n) return GIGL_OK;
+  GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst, x.g[0], (size_t)x.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  if (x.g[1]) hipLaunchKernelGGL(lp_acc_kernel, dim3(blocks), dim3(256), 0, ctx->stream, dst, (const float*)x.g[1], x.n);
+  return GIGL_OK;
+}
 }  // namespace
 
 int32_t gigl_sage_train_plan_moments(gigl_sage_train_plan* t, int32_t layer, float* m_w, float* v_w, float* m_b, float* v_b) {
@@ -2897,12 +2966,10 @@ int32_t gigl_nablp_train_plan_moments(gigl_nablp_train_plan* t, int32_t index, f
     GIGL_REQUIRE(ctx, index >= 0 && index < 2 * t->L, "tensor %d", index);
     return sage_moments_copy(ctx, *t, index, m, v);
   }
-  GIGL_REQUIRE(ctx, index >= 0 && index < (t->gat.e.table ? 14 : 8), "tensor %d", index);
-  // (8 + 3 l + j: the edge tensors of gigl_gat_nablp_train_plan_set_edge_features)
-  const size_t n = (size_t)(index < 8 ? t->gat.n[index] : t->gat.e.n[index - 8]);
-  float* const* mom = index < 8 ? t->gat.mom + 2 * index : t->gat.e.mom + 2 * (index - 8);
-  if (m && n) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(m, mom[0], n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  if (v && n) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(v, mom[1], n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  GIGL_REQUIRE(ctx, index >= 0 && index < (t->gat.e.table ? GAT_TENSORS : GAT_CORE), "tensor %d", index);
+  const PlanTensor& x = t->gat.tensor[index];  // (gat_slot: the table's index is the published one)
+  if (m && x.n) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(m, x.m, (size_t)x.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  if (v && x.n) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(v, x.v, (size_t)x.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
   return GIGL_OK;
 }
 
@@ -2925,20 +2992,12 @@ int32_t gigl_nablp_train_plan_adopt(gigl_nablp_train_plan* dst, gigl_nablp_train
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   GIGL_HIP_CHECK(ctx, hipStreamSynchronize(src->ctx->stream));
   if (dst->kind == 1) {
-    for (int i = 0; i < 8; ++i) {
-      GIGL_REQUIRE(ctx, dst->gat.n[i] == src->gat.n[i], "plans of different widths");
-      for (int j = 0; j < 2; ++j)
-        GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->gat.mom[2 * i + j], src->gat.mom[2 * i + j],
-                                           (size_t)(dst->gat.n[i] ? dst->gat.n[i] : 1) * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    }
+    int32_t rc = gat_moments_adopt(ctx, dst->gat.tensor, src->gat.tensor, 0, GAT_CORE, "plans of different widths");
+    if (rc != GIGL_OK) return rc;
     GIGL_REQUIRE(ctx, (dst->gat.e.table != nullptr) == (src->gat.e.table != nullptr), "plans with / without edge features");
-    for (int i = 0; i < 6 && dst->gat.e.table; ++i) {
-      GIGL_REQUIRE(ctx, dst->gat.e.n[i] == src->gat.e.n[i], "plans of different edge widths");
-      for (int j = 0; j < 2; ++j)
-        GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->gat.e.mom[2 * i + j], src->gat.e.mom[2 * i + j],
-                                           (size_t)(dst->gat.e.n[i] ? dst->gat.e.n[i] : 1) * 4, hipMemcpyDeviceToDevice,
-                                           ctx->stream));
-    }
+    if (dst->gat.e.table)
+      rc = gat_moments_adopt(ctx, dst->gat.tensor, src->gat.tensor, GAT_CORE, GAT_TENSORS, "plans of different edge widths");
+    if (rc != GIGL_OK) return rc;
   } else {
     const int32_t rc = sage_moments_adopt(ctx, *dst, *src);
     if (rc != GIGL_OK) return rc;
@@ -3107,7 +3166,7 @@ gigl_gat_edge_terms gat_edge_terms0(const gigl_nablp_train_plan* t, int which) {
   et.table = (const float*)ge.table->rows;
   et.edge_dim = ge.De;
   et.att_edge_folded = ge.v;
-  et.w_edge_msg = ge.w_msg[0];
+  et.w_edge_msg = t->gat.at(GAT_W_MSG, 0).p;
   et.ze = ge.ze[which];
   return et;
 }
@@ -3116,23 +3175,23 @@ gigl_gat_edge_terms gat_edge_terms0(const gigl_nablp_train_plan* t, int which) {
 int32_t gat_lp_begin(gigl_nablp_train_plan* t) {
   const auto& g = t->gat;
   hipLaunchKernelGGL(gat_fold_kernel, dim3((unsigned)(2 * g.heads), (unsigned)((g.d_in + 63) / 64)), dim3(256), 0,
-                     t->lctx->stream, (const float*)g.w[0],
-                     (const float*)g.att_src[0], (const float*)g.att_dst[0], g.heads, g.c0, g.d_in, g.u);
+                     t->lctx->stream, (const float*)g.at(GAT_W, 0).p, (const float*)g.at(GAT_ATT_SRC, 0).p,
+                     (const float*)g.at(GAT_ATT_DST, 0).p, g.heads, g.c0, g.d_in, g.u);
   // W1^T and the heads' W0^T for the input gradients of both encodes
   hipStream_t st = t->lctx->stream;
   const int HC = g.heads * g.c0;
-  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(((int64_t)g.c1 * HC + 255) / 256)), dim3(256), 0, st, (const float*)g.w[1],
-                     g.c1, HC, g.wt1);
+  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(((int64_t)g.c1 * HC + 255) / 256)), dim3(256), 0, st,
+                     (const float*)g.at(GAT_W, 1).p, g.c1, HC, g.wt1);
   for (int h = 0; h < g.heads; ++h)
     hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(((int64_t)g.c0 * g.d_in + 255) / 256)), dim3(256), 0, st,
-                       (const float*)(g.w[0] + (int64_t)h * g.c0 * g.d_in), g.c0, g.d_in, g.wt0[h]);
+                       (const float*)(g.at(GAT_W, 0).p + (int64_t)h * g.c0 * g.d_in), g.c0, g.d_in, g.wt0[h]);
   if (g.e.table) {  // both layers' folded att_edge (the parameters change every step), the edge gradients' clean slate
     const int De = g.e.De;
     gigl_fill_u32(st, g.e.zero_base, 0u, (int64_t)(g.e.zero_bytes / 4));
     hipLaunchKernelGGL(gat_edge_fold_kernel, dim3((unsigned)((g.heads * De + 255) / 256)), dim3(256), 0, st,
-                       (const float*)g.e.w_edge[0], (const float*)g.e.att_edge[0], g.heads, g.c0, De, g.e.v);
-    hipLaunchKernelGGL(gat_edge_fold_kernel, dim3(1), dim3(256), 0, st, (const float*)g.e.w_edge[1],
-                       (const float*)g.e.att_edge[1], 1, g.c1, De, g.e.v + g.heads * De);
+                       (const float*)g.at(GAT_W_EDGE, 0).p, (const float*)g.at(GAT_ATT_EDGE, 0).p, g.heads, g.c0, De, g.e.v);
+    hipLaunchKernelGGL(gat_edge_fold_kernel, dim3(1), dim3(256), 0, st, (const float*)g.at(GAT_W_EDGE, 1).p,
+                       (const float*)g.at(GAT_ATT_EDGE, 1).p, 1, g.c1, De, g.e.v + g.heads * De);
   }
   GIGL_HIP_CHECK(t->lctx, hipGetLastError());
   return GIGL_OK;
@@ -3141,42 +3200,43 @@ int32_t gat_lp_begin(gigl_nablp_train_plan* t) {
 int32_t gat_lp_forward(gigl_nablp_train_plan* t, int which) {
   SageTrainEnc& e = t->enc[which];
   gigl_sage_plan* p = e.base;
-  const bool alt = which == 1 && t->fork;
-  gigl_ctx* ctx = alt ? t->actx : t->lctx;
-  hipStream_t st = ctx->stream;
   auto& g = t->gat;
-  float* alpha = alt ? g.x.alpha : g.alpha;
+  GatScratch& s = g.sc[which == 1 && t->fork];
+  gigl_ctx* ctx = s.ctx;
+  hipStream_t st = ctx->stream;
+  const float *w0 = g.at(GAT_W, 0).p, *b0 = g.at(GAT_BIAS, 0).p, *w1 = g.at(GAT_W, 1).p, *as1 = g.at(GAT_ATT_SRC, 1).p,
+              *ad1 = g.at(GAT_ATT_DST, 1).p, *b1 = g.at(GAT_BIAS, 1).p, *wm0 = g.at(GAT_W_MSG, 0).p, *wm1 = g.at(GAT_W_MSG, 1).p;
   const int H = g.heads, C0 = g.c0, C1 = g.c1, d = g.d_in;
   const int64_t rows1 = gat_rows1(t, which);
   const int32_t* n0 = p->un.meta + GIGL_META_LEVEL0;
   const int32_t* n1 = p->un.meta + GIGL_META_LEVEL0 + 1;
-  const bool edge = g.e.table != nullptr, msg0 = edge && g.e.w_msg[0];
+  const bool edge = g.e.table != nullptr, msg0 = edge && wm0;
   const gigl_gat_edge_terms et = edge ? gat_edge_terms0(t, which) : gigl_gat_edge_terms{};
   int32_t rc = gigl_gat_input_aggregate_edge(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
                                              p->un.rowend, p->un.col, n1, rows1, g.z[which], edge ? &et : nullptr);
   if (rc != GIGL_OK) return rc;
   // h0[:, hC:(h+1)C] = relu(z_h W_h^T (+ W_msg,h ze_h) + b_h): one launch for all heads (the messages' De-wide term, the
   // bias and the relu in one more)
-  rc = gigl_linear_batched(ctx, g.z[which], g.w[0], msg0 ? nullptr : g.bias[0], n1, rows1, d, C0, msg0 ? 0 : 1, H, rows1 * d,
+  rc = gigl_linear_batched(ctx, g.z[which], w0, msg0 ? nullptr : b0, n1, rows1, d, C0, msg0 ? 0 : 1, H, rows1 * d,
                            (int64_t)C0 * d, H * C0, e.h[0]);
-  if (rc == GIGL_OK && msg0) rc = gigl_gat_edge_msg_add(ctx, g.e.ze[which], g.e.w_msg[0], g.bias[0], n1, rows1, H, C0, g.e.De, 1, e.h[0]);
+  if (rc == GIGL_OK && msg0) rc = gigl_gat_edge_msg_add(ctx, g.e.ze[which], wm0, b0, n1, rows1, H, C0, g.e.De, 1, e.h[0]);
   if (rc != GIGL_OK) return rc;
-  rc = gigl_linear(ctx, e.h[0], g.w[1], nullptr, n1, rows1, H * C0, C1, 0, g.xw[which]);
+  rc = gigl_linear(ctx, e.h[0], w1, nullptr, n1, rows1, H * C0, C1, 0, g.xw[which]);
   if (rc != GIGL_OK) return rc;
   if (edge)
-    rc = gigl_gat_aggregate_edge_indexed(ctx, g.xw[which], g.att_src[1], g.att_dst[1], 1, C1, g.slope, 1, p->un.rowptr,
+    rc = gigl_gat_aggregate_edge_indexed(ctx, g.xw[which], as1, ad1, 1, C1, g.slope, 1, p->un.rowptr,
                                          p->un.rowend, p->un.col, n1, rows1, n0, e.rows_cap[1], nullptr, 0,
                                          (const float*)g.e.table->rows, p->eid, g.e.De, p->un.cap_edges, g.e.v + H * g.e.De,
-                                         g.e.w_msg[1], alpha, g.out_pre[which]);
+                                         wm1, s.alpha, g.out_pre[which]);
   else
-    rc = gigl_gat_aggregate(ctx, g.xw[which], g.att_src[1], g.att_dst[1], 1, C1, g.slope, 1, p->un.rowptr, p->un.rowend,
-                            p->un.col, n1, rows1, n0, e.rows_cap[1], nullptr, 0, alpha, g.out_pre[which]);
+    rc = gigl_gat_aggregate(ctx, g.xw[which], as1, ad1, 1, C1, g.slope, 1, p->un.rowptr, p->un.rowend,
+                            p->un.col, n1, rows1, n0, e.rows_cap[1], nullptr, 0, s.alpha, g.out_pre[which]);
   if (rc != GIGL_OK) return rc;
   {
     int64_t blocks = (e.rows_cap[1] * C1 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(gat_add_bias_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)g.out_pre[which],
-                       (const float*)g.bias[1], n0, C1, e.h[1]);
+                       b1, n0, C1, e.h[1]);
   }
   hipLaunchKernelGGL(lp_take_norm_kernel, dim3((unsigned)((e.b + 3) / 4)), dim3(256), 0, st, (const float*)e.h[1],
                      (const int32_t*)p->un.root_local, e.b, C1, t->normalize, (const int32_t*)p->un.meta, e.emb, e.inv);
@@ -3187,155 +3247,140 @@ int32_t gat_lp_forward(gigl_nablp_train_plan* t, int which) {
 int32_t gat_lp_backward(gigl_nablp_train_plan* t, int which) {
   SageTrainEnc& e = t->enc[which];
   gigl_sage_plan* p = e.base;
-  const bool alt = which == 1 && t->fork;
-  gigl_ctx* ctx = alt ? t->actx : t->lctx;
-  hipStream_t st = ctx->stream;
   auto& g = t->gat;
-  float *s_alpha = alt ? g.x.alpha : g.alpha, *s_dxw = alt ? g.x.dxw : g.dxw, *s_ds = alt ? g.x.ds : g.ds,
-        *s_dd = alt ? g.x.dd : g.dd, *s_dh0 = alt ? g.x.dh0 : g.dh0, *s_dh0s = alt ? g.x.dh0s : g.dh0s,
-        *s_dz = alt ? g.x.dz : g.dz, *s_du = alt ? g.x.du : g.du;
-  float* const* gg = alt ? g.x.g : g.g;
+  const int alt = which == 1 && t->fork;
+  GatScratch& s = g.sc[alt];
+  gigl_ctx* ctx = s.ctx;
+  hipStream_t st = ctx->stream;
+  const float *as1 = g.at(GAT_ATT_SRC, 1).p, *ad1 = g.at(GAT_ATT_DST, 1).p, *wm0 = g.at(GAT_W_MSG, 0).p, *wm1 = g.at(GAT_W_MSG, 1).p;
   const int H = g.heads, C0 = g.c0, C1 = g.c1, d = g.d_in, HC = H * C0;
   const int64_t rows1 = gat_rows1(t, which);
   const int32_t* n0 = p->un.meta + GIGL_META_LEVEL0;
   const int32_t* n1 = p->un.meta + GIGL_META_LEVEL0 + 1;
-  // (gg[0..4] — W0, its attention vectors, b0, W1 — come from the partial sums and the fold's backward)
-  float *gas1 = gg[5], *gad1 = gg[6], *gb1 = gg[7];
+  // this stream's gradient slots (W0's, its attention vectors', b0's, W1's come from the partial sums and the fold's backward)
+  float *gas1 = g.at(GAT_ATT_SRC, 1).g[alt], *gad1 = g.at(GAT_ATT_DST, 1).g[alt], *gb1 = g.at(GAT_BIAS, 1).g[alt];
   // ---- second layer (the roots' rows): e.dh[1] = d loss / d (out before the bias)
-  if (g.bias[1])
+  if (g.at(GAT_BIAS, 1).p)
     hipLaunchKernelGGL(gat_bias_grad_kernel, dim3((unsigned)((e.rows_cap[1] + 7) / 8)), dim3(256), 0, st, (const float*)e.dh[1],
                        n0, C1, gb1);
-  gigl_fill_u32(st, s_dxw, 0u, rows1 * C1);
-  gigl_fill_u32(st, s_ds, 0u, s_dd - s_ds + rows1);  // (ds | dd: dd starts where the larger encode's ds ends)
+  gigl_fill_u32(st, s.dxw, 0u, rows1 * C1);
+  gigl_fill_u32(st, s.ds, 0u, s.dd - s.ds + rows1);  // (ds | dd: dd starts where a ds of the scratch's row capacity ends)
   // (edge features: both layers' d v on this stream's buffer, the message weights' gradients on this stream's slots — a
-  // shared weight's on lin_edge.weight's)
+  // shared weight's slot IS lin_edge.weight's)
   const bool edge = g.e.table != nullptr;
   const int De = g.e.De;
-  float* const* ge = alt ? g.e.x.ge : g.e.ge;
-  float *s_dv = alt ? g.e.x.dv : g.e.dv, *s_dze = alt ? g.e.x.dze : g.e.dze, *s_z1 = alt ? g.e.x.z1 : g.e.z1;
-  auto msg_slot = [&](int l) { return ge[g.e.w_msg[l] == g.e.w_edge[l] ? 3 * l : 3 * l + 2]; };
+  float *gm0 = g.at(GAT_W_MSG, 0).g[alt], *gm1 = g.at(GAT_W_MSG, 1).g[alt];
   int32_t rc = GIGL_OK;
   if (edge) {
-    const bool msg1 = g.e.w_msg[1] != nullptr;
+    const bool msg1 = wm1 != nullptr;
     if (msg1)  // dze_i = W_msg^T dout_i
-      rc = gigl_gat_edge_msg_backward(ctx, e.dh[1], 0, g.e.w_msg[1], nullptr, n0, e.rows_cap[1], 1, C1, De, s_dze, nullptr);
+      rc = gigl_gat_edge_msg_backward(ctx, e.dh[1], 0, wm1, nullptr, n0, e.rows_cap[1], 1, C1, De, s.dze, nullptr);
     if (rc == GIGL_OK)
-      rc = gigl_gat_aggregate_backward_indexed(ctx, g.xw[which], g.att_src[1], g.att_dst[1], C1, g.slope, p->un.rowptr,
+      rc = gigl_gat_aggregate_backward_indexed(ctx, g.xw[which], as1, ad1, C1, g.slope, p->un.rowptr,
                                                p->un.rowend, p->un.col, n1, rows1, n0, e.rows_cap[1], g.out_pre[which], e.dh[1],
                                                (const float*)g.e.table->rows, p->eid, De, g.e.v + H * De,
-                                               msg1 ? s_dze : nullptr, s_alpha, s_dxw, s_ds, s_dd, s_dv + H * De,
-                                               msg1 ? s_z1 : nullptr);
+                                               msg1 ? s.dze : nullptr, s.alpha, s.dxw, s.ds, s.dd, s.dv + H * De,
+                                               msg1 ? s.z1 : nullptr);
     if (rc == GIGL_OK && msg1)  // d W_msg += sum_i dout_i (x) z1_i
-      rc = gigl_gat_edge_msg_backward(ctx, e.dh[1], 0, nullptr, s_z1, n0, e.rows_cap[1], 1, C1, De, nullptr, msg_slot(1));
+      rc = gigl_gat_edge_msg_backward(ctx, e.dh[1], 0, nullptr, s.z1, n0, e.rows_cap[1], 1, C1, De, nullptr, gm1);
   } else {
-    rc = gigl_gat_aggregate_backward(ctx, g.xw[which], g.att_src[1], g.att_dst[1], 1, C1, g.slope, p->un.rowptr,
+    rc = gigl_gat_aggregate_backward(ctx, g.xw[which], as1, ad1, 1, C1, g.slope, p->un.rowptr,
                                      p->un.rowend, p->un.col, n1, rows1, n0, e.rows_cap[1], g.out_pre[which], e.dh[1],
-                                     nullptr, 0, p->un.cap_edges, nullptr, s_alpha, s_dxw, s_ds, s_dd, nullptr, nullptr,
+                                     nullptr, 0, p->un.cap_edges, nullptr, s.alpha, s.dxw, s.ds, s.dd, nullptr, nullptr,
                                      nullptr);
   }
   if (rc != GIGL_OK) return rc;
-  rc = gigl_gat_backward_epilogue(ctx, s_dxw, s_ds, s_dd, g.xw[which], g.att_src[1], g.att_dst[1], n1, rows1, 1, C1, gas1, gad1);
+  rc = gigl_gat_backward_epilogue(ctx, s.dxw, s.ds, s.dd, g.xw[which], as1, ad1, n1, rows1, 1, C1, gas1, gad1);
   if (rc != GIGL_OK) return rc;
   // (measured: the main batch's weight gradients on a third stream, as the GraphSAGE plan runs them — 1.75 against 1.71 ms:
   // these 768-wide ones fill the GPU and slow the chain beside them)
-  rc = gigl_linear_weight_grad_parts(ctx, s_dxw, e.h[0], nullptr, n1, rows1, C1, HC, g.part_w1[which], nullptr);
+  rc = gigl_linear_weight_grad_parts(ctx, s.dxw, e.h[0], nullptr, n1, rows1, C1, HC, g.part_w1[which], nullptr);
   if (rc != GIGL_OK) return rc;
-  rc = gigl_linear(ctx, s_dxw, g.wt1, nullptr, n1, rows1, C1, HC, 0, s_dh0);
+  rc = gigl_linear(ctx, s.dxw, g.wt1, nullptr, n1, rows1, C1, HC, 0, s.dh0);
   if (rc != GIGL_OK) return rc;
   // ---- first layer: relu mask, the heads' slices, their projections' backward, the attention-weighted sums' backward
   {
     int64_t blocks = (rows1 * HC + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(gat_split_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)s_dh0, (const float*)e.h[0],
-                       n1, rows1, H, C0, s_dh0s);
+    hipLaunchKernelGGL(gat_split_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)s.dh0, (const float*)e.h[0],
+                       n1, rows1, H, C0, s.dh0s);
   }
   for (int h = 0; h < H; ++h) {
-    const float* dyh = s_dh0s + (int64_t)h * rows1 * C0;
+    const float* dyh = s.dh0s + (int64_t)h * rows1 * C0;
     rc = gigl_linear_weight_grad_parts(ctx, dyh, g.z[which] + (int64_t)h * rows1 * d, nullptr, n1, rows1, C0, d,
-                                       g.part_w0[which][h], g.bias[0] ? g.part_b0[which][h] : nullptr);
+                                       g.part_w0[which][h], g.at(GAT_BIAS, 0).p ? g.part_b0[which][h] : nullptr);
     if (rc != GIGL_OK) return rc;
-    rc = gigl_linear(ctx, dyh, g.wt0[h], nullptr, n1, rows1, C0, d, 0, s_dz + (int64_t)h * rows1 * d);
+    rc = gigl_linear(ctx, dyh, g.wt0[h], nullptr, n1, rows1, C0, d, 0, s.dz + (int64_t)h * rows1 * d);
     if (rc != GIGL_OK) return rc;
   }
   if (edge) {
-    const bool msg0 = g.e.w_msg[0] != nullptr;
+    const bool msg0 = wm0 != nullptr;
     const gigl_gat_edge_terms et = gat_edge_terms0(t, which);
     if (msg0) {  // dze_i,h = W_msg,h^T dy_i,h and d W_msg += sum_i dy_i (x) ze_i, from the heads' masked slices
-      rc = gigl_gat_edge_msg_backward(ctx, s_dh0s, rows1 * C0, g.e.w_msg[0], g.e.ze[which], n1, rows1, H, C0, De, s_dze, msg_slot(0));
+      rc = gigl_gat_edge_msg_backward(ctx, s.dh0s, rows1 * C0, wm0, g.e.ze[which], n1, rows1, H, C0, De, s.dze, gm0);
       if (rc != GIGL_OK) return rc;
     }
     rc = gigl_gat_input_aggregate_backward_edge(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
-                                                p->un.rowend, p->un.col, n1, rows1, s_dz, s_du, &et, msg0 ? s_dze : nullptr, s_dv);
+                                                p->un.rowend, p->un.col, n1, rows1, s.dz, s.du, &et, msg0 ? s.dze : nullptr, s.dv);
   } else {
     rc = gigl_gat_input_aggregate_backward(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
-                                           p->un.rowend, p->un.col, n1, rows1, s_dz, nullptr, s_du);
+                                           p->un.rowend, p->un.col, n1, rows1, s.dz, nullptr, s.du);
   }
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return rc;
 }
 
-// after both encodes: d u -> the first layer's weights and attention vectors, then Adam over the eight tensors
+// after both encodes: d u -> the first layer's weights and attention vectors, then Adam over the table
 int32_t gat_lp_finish(gigl_nablp_train_plan* t) {
   gigl_ctx* ctx = t->lctx;
   hipStream_t st = ctx->stream;
   auto& g = t->gat;
+  const PlanTensor &w0 = g.at(GAT_W, 0), &b0 = g.at(GAT_BIAS, 0), &w1 = g.at(GAT_W, 1);
   if (t->fork)  // the random negatives' share of d u, accumulated on its own stream
-    hipLaunchKernelGGL(lp_acc_kernel, dim3(64), dim3(256), 0, st, g.du, (const float*)g.x.du, (int64_t)2 * g.heads * g.d_in);
-  hipLaunchKernelGGL(gat_fold_backward_kernel, dim3((unsigned)(g.heads * g.c0)), dim3(256), 0, st, (const float*)g.w[0],
-                     (const float*)g.att_src[0], (const float*)g.att_dst[0], (const float*)g.du, g.heads, g.c0, g.d_in, g.g[0],
-                     g.g[1], g.g[2]);
+    hipLaunchKernelGGL(lp_acc_kernel, dim3(64), dim3(256), 0, st, g.sc[0].du, (const float*)g.sc[1].du, (int64_t)2 * g.heads * g.d_in);
+  hipLaunchKernelGGL(gat_fold_backward_kernel, dim3((unsigned)(g.heads * g.c0)), dim3(256), 0, st, (const float*)w0.p,
+                     (const float*)g.at(GAT_ATT_SRC, 0).p, (const float*)g.at(GAT_ATT_DST, 0).p, (const float*)g.sc[0].du, g.heads,
+                     g.c0, g.d_in, w0.g[0], g.at(GAT_ATT_SRC, 0).g[0], g.at(GAT_ATT_DST, 0).g[0]);
   if (g.e.table) {  // d v of both layers -> lin_edge.weight and att_edge (v = W_e^T att_edge per head)
     const int De = g.e.De;
-    if (t->fork) hipLaunchKernelGGL(lp_acc_kernel, dim3(1), dim3(256), 0, st, g.e.dv, (const float*)g.e.x.dv, (int64_t)(g.heads + 1) * De);
+    float* dv = g.sc[0].dv;
+    if (t->fork) hipLaunchKernelGGL(lp_acc_kernel, dim3(1), dim3(256), 0, st, dv, (const float*)g.sc[1].dv, (int64_t)(g.heads + 1) * De);
     hipLaunchKernelGGL(gat_edge_fold_backward_kernel, dim3((unsigned)((g.heads * g.c0 + 3) / 4)), dim3(256), 0, st,
-                       (const float*)g.e.w_edge[0], (const float*)g.e.att_edge[0], (const float*)g.e.dv, g.heads, g.c0, De,
-                       g.e.ge[0], g.e.ge[1]);
+                       (const float*)g.at(GAT_W_EDGE, 0).p, (const float*)g.at(GAT_ATT_EDGE, 0).p, (const float*)dv, g.heads, g.c0,
+                       De, g.at(GAT_W_EDGE, 0).g[0], g.at(GAT_ATT_EDGE, 0).g[0]);
     hipLaunchKernelGGL(gat_edge_fold_backward_kernel, dim3((unsigned)((g.c1 + 3) / 4)), dim3(256), 0, st,
-                       (const float*)g.e.w_edge[1], (const float*)g.e.att_edge[1], (const float*)(g.e.dv + g.heads * De), 1, g.c1,
-                       De, g.e.ge[3], g.e.ge[4]);
+                       (const float*)g.at(GAT_W_EDGE, 1).p, (const float*)g.at(GAT_ATT_EDGE, 1).p, (const float*)(dv + g.heads * De), 1,
+                       g.c1, De, g.at(GAT_W_EDGE, 1).g[0], g.at(GAT_ATT_EDGE, 1).g[0]);
   }
   AdamPack ap{};
   ap.n_src = 2;
-  float* params[8] = {g.w[0], g.att_src[0], g.att_dst[0], g.bias[0], g.w[1], g.att_src[1], g.att_dst[1], g.bias[1]};
   const int32_t* n1a = t->enc[0].base->un.meta + GIGL_META_LEVEL0 + 1;
   const int32_t* n1b = t->enc[1].base->un.meta + GIGL_META_LEVEL0 + 1;
-  auto add = [&](float* prm, const float* grad, float* m, float* v, int64_t n, const float* pa, const float* pb, int32_t rca,
-                 int32_t rcb, const float* grad2 = nullptr) {
+  auto add = [&](const PlanTensor& x, int64_t at, int64_t n, const float* pa, const float* pb, int32_t rca, int32_t rcb) {
     const int k = ap.count++;
-    ap.p[k] = prm;
-    ap.g[0][k] = grad;
-    ap.g[1][k] = grad2;
+    ap.p[k] = x.p + at;
+    ap.g[0][k] = x.g[0] + at;
+    ap.g[1][k] = x.g[1];  // (fork: what the second stream accumulated itself; never a sliced tensor's)
     ap.part[0][k] = pa;
     ap.part[1][k] = pb;
     ap.rows[0][k] = n1a;
     ap.rows[1][k] = n1b;
     ap.rc[0][k] = rca;
     ap.rc[1][k] = rcb;
-    ap.m[k] = m;
-    ap.v[k] = v;
+    ap.m[k] = x.m + at;
+    ap.v[k] = x.v + at;
     ap.n[k] = n;
   };
-  for (int i = 0; i < 8; ++i) {
-    if (!params[i]) continue;
-    if (i == 0 || i == 3) {  // W0 / b0: a slice per head, each with its own partial sums of both encodes
-      const int64_t ns = i == 0 ? (int64_t)g.c0 * g.d_in : g.c0;
-      for (int h = 0; h < g.heads; ++h)
-        add(params[i] + h * ns, g.g[i] + h * ns, g.mom[2 * i] + h * ns, g.mom[2 * i + 1] + h * ns, ns,
-            i == 0 ? g.part_w0[0][h] : g.part_b0[0][h], i == 0 ? g.part_w0[1][h] : g.part_b0[1][h], g.rc_w0[0], g.rc_w0[1]);
-    } else if (i == 4) {
-      add(params[i], g.g[i], g.mom[2 * i], g.mom[2 * i + 1], g.n[i], g.part_w1[0], g.part_w1[1], g.rc_w1[0], g.rc_w1[1]);
-    } else {  // (fork: the second layer's attention vectors and bias were accumulated per encode)
-      add(params[i], g.g[i], g.mom[2 * i], g.mom[2 * i + 1], g.n[i], nullptr, nullptr, 0, 0,
-          t->fork && i >= 5 ? g.x.g[i] : nullptr);
-    }
-  }
-  for (int l = 0; l < 2 && g.e.table; ++l) {  // the edge tensors (a shared message weight IS lin_edge.weight: one entry)
-    float* eprm[3] = {g.e.w_edge[l], g.e.att_edge[l], g.e.w_msg[l]};
-    for (int j = 0; j < 3; ++j) {
-      const int k = 3 * l + j;
-      if (!g.e.n[k]) continue;
-      add(eprm[j], g.e.ge[k], g.e.mom[2 * k], g.e.mom[2 * k + 1], g.e.n[k], nullptr, nullptr, 0, 0,
-          t->fork && j != 1 ? g.e.x.ge[k] : nullptr);
+  // in table order (the gradient norm's fixed-order sum follows it); a shared message weight has n == 0: no entry of its own
+  for (const PlanTensor& x : g.tensor) {
+    if (!x.n) continue;
+    if (&x == &w0 || &x == &b0) {  // a slice per head, each with its own partial sums of both encodes
+      const auto& part = &x == &w0 ? g.part_w0 : g.part_b0;
+      for (int h = 0; h < g.heads; ++h) add(x, h * (x.n / g.heads), x.n / g.heads, part[0][h], part[1][h], g.rc_w0[0], g.rc_w0[1]);
+    } else if (&x == &w1) {
+      add(x, 0, x.n, g.part_w1[0], g.part_w1[1], g.rc_w1[0], g.rc_w1[1]);
+    } else {
+      add(x, 0, x.n, nullptr, nullptr, 0, 0);
     }
   }
   ap.lr = t->lr;
@@ -3349,6 +3394,30 @@ int32_t gat_lp_finish(gigl_nablp_train_plan* t) {
               (const int32_t*)t->enc[1].base->un.meta, (const int32_t*)nullptr, &t->clip);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
+}
+
+// a stream's backward scratch, for encodes of up to rows1 nodes of level <= 1, cap_edges edges and b roots
+static bool gat_scratch_alloc(gigl_nablp_train_plan* t, GatScratch& s, gigl_ctx* stream_ctx, int64_t rows1, int64_t cap_edges, int64_t b) {
+  const auto& g = t->gat;
+  auto alloc = [&](int64_t floats) { return (float*)train_alloc(t->owned, (size_t)floats * 4); };
+  s.ctx = stream_ctx;
+  s.rows1 = rows1;
+  s.b = b;
+  s.dxw = alloc(rows1 * g.c1);
+  s.ds = alloc(2 * rows1);
+  s.dd = s.ds ? s.ds + rows1 : nullptr;
+  s.alpha = alloc(2 * rows1 + cap_edges);
+  s.dh0 = alloc(rows1 * g.heads * g.c0);
+  s.dh0s = alloc(rows1 * g.heads * g.c0);
+  s.dz = alloc(g.heads * rows1 * g.d_in);
+  return s.dxw && s.ds && s.alpha && s.dh0 && s.dh0s && s.dz;
+}
+// ... and what the message weights' backward adds to it
+static bool gat_scratch_alloc_edge(gigl_nablp_train_plan* t, GatScratch& s) {
+  const auto& g = t->gat;
+  s.dze = (float*)train_alloc(t->owned, (size_t)s.rows1 * g.heads * g.e.De * 4);
+  s.z1 = (float*)train_alloc(t->owned, (size_t)s.b * g.e.De * 4);
+  return s.dze && s.z1;
 }
 
 }  // namespace
@@ -3374,37 +3443,23 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
   for (int l = 0; l < 2; ++l) GIGL_REQUIRE(ctx, w[l] && att_src[l] && att_dst[l], "layer %d: null parameter", l);
   if (fanouts[1] > GIGL_FAST_FANOUT) return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "second fan-out beyond %d", GIGL_FAST_FANOUT);
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  gigl_nablp_train_plan* t = new (std::nothrow) gigl_nablp_train_plan();
+  gigl_nablp_train_plan* t = lp_plan_new(ctx, 1, 2, b_anchors, num_positives, n_random_negatives, 0, l2_normalize, temperature,
+                                         remove_accidental_hits, lr, beta1, beta2, eps, weight_decay);
   if (!t) return gigl_fail(ctx, GIGL_E_OOM, "host OOM");
-  t->ctx = ctx;
-  t->kind = 1;
-  t->L = 2;
-  t->b = b_anchors;
-  t->P = num_positives;
-  t->n_rn = n_random_negatives;
-  t->normalize = l2_normalize ? 1 : 0;
-  t->remove_hits = remove_accidental_hits ? 1 : 0;
-  t->temperature = temperature;
-  t->act_last = 0;
-  t->lr = lr;
-  t->beta1 = beta1;
-  t->beta2 = beta2;
-  t->eps = eps;
-  t->wd = weight_decay;
   auto& g = t->gat;
   g.heads = H;
   g.c0 = C0;
   g.c1 = C1;
   g.d_in = d;
   g.slope = negative_slope;
-  for (int l = 0; l < 2; ++l) {
-    g.w[l] = w[l];
-    g.att_src[l] = att_src[l];
-    g.att_dst[l] = att_dst[l];
-    g.bias[l] = bias ? bias[l] : nullptr;
-  }
   const int32_t dims[3] = {d, H * C0, C1};
   for (int l = 0; l <= 2; ++l) t->dims[l] = dims[l];
+  for (int l = 0; l < 2; ++l) {
+    g.at(GAT_W, l).set(w[l], (int64_t)dims[l + 1] * dims[l]);
+    g.at(GAT_ATT_SRC, l).set(att_src[l], dims[l + 1]);
+    g.at(GAT_ATT_DST, l).set(att_dst[l], dims[l + 1]);
+    g.at(GAT_BIAS, l).set(bias ? bias[l] : nullptr, dims[l + 1]);
+  }
   // (the base plans are tree + union workspaces here: their own layer buffers stay unused)
   const int32_t rc = lp_create_workspaces(t, graph, feat, fanouts, hops, dims, w, bias, 0);
   if (rc != GIGL_OK) {
@@ -3416,22 +3471,15 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
     for (gigl_sage_plan* bp : wk.base) bp->leaf_global = false;
   auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
   bool ok = true;
-  const int64_t n_par[8] = {(int64_t)H * C0 * d, H * C0, H * C0, g.bias[0] ? H * C0 : 0, (int64_t)C1 * H * C0, C1, C1, g.bias[1] ? C1 : 0};
-  size_t zero_floats = (size_t)2 * H * d;  // du
-  for (int i = 0; i < 8; ++i) {
-    g.n[i] = n_par[i];
-    zero_floats += (size_t)n_par[i];
-  }
   // (default on, GIGL_LP_FORK=0 off, as the GraphSAGE plan: the forked step's layers part launched eagerly)
   const bool want_fork = lp_fork_wanted(t);
-  if (want_fork) zero_floats += (size_t)2 * H * d + (size_t)(n_par[5] + n_par[6] + n_par[7]);  // the second encode's du, att / bias sums
-  int64_t rows1_max = 0;
+  int64_t rows1_max = 0, b_max = 0;
   for (int k = 0; k < 2; ++k) {
     SageTrainEnc& e = t->enc[k];
     e.rows_cap[0] = gigl_level_rows(ctx->wide, e.b, fanouts, hops, 1);  // nodes of level <= 1
     e.rows_cap[1] = e.b;
     if (e.rows_cap[0] > rows1_max) rows1_max = e.rows_cap[0];
-    zero_floats += (size_t)e.b * C1;  // dh[1]
+    if (e.b > b_max) b_max = e.b;
     e.h[0] = (float*)alloc((size_t)e.rows_cap[0] * H * C0 * 4);
     e.h[1] = (float*)alloc((size_t)e.b * C1 * 4);
     g.z[k] = (float*)alloc((size_t)H * e.rows_cap[0] * d * 4);
@@ -3439,55 +3487,26 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
     g.out_pre[k] = (float*)alloc((size_t)e.b * C1 * 4);
     ok = ok && e.h[0] && e.h[1] && g.z[k] && g.xw[k] && g.out_pre[k];
   }
-  float* z = (float*)alloc(zero_floats * 4);
-  t->zero_base = z;
-  t->zero_bytes = zero_floats * 4;
-  if (z) {
-    for (int i = 0; i < 8; ++i) {
-      g.g[i] = z;
-      z += n_par[i];
-    }
-    g.du = z;
-    z += (size_t)2 * H * d;
-    for (int k = 0; k < 2; ++k) {
-      t->enc[k].dh[1] = z;
-      z += (size_t)t->enc[k].b * C1;
-    }
+  // the block cleared at the start of every step, laid out twice (to measure it, then in the buffer)
+  auto lay_out = [&](float* block) {
+    size_t at = gat_grads_carve(g.tensor, 0, GAT_CORE, 0, block, 0);
+    auto take = [&](float*& q, size_t floats) { q = block ? block + at : nullptr; at += floats; };
+    take(g.sc[0].du, (size_t)2 * H * d);
+    for (SageTrainEnc& e : t->enc) take(e.dh[1], (size_t)e.b * C1);
     if (want_fork) {
-      g.x.du = z;
-      z += (size_t)2 * H * d;
-      for (int i = 5; i < 8; ++i) {
-        g.x.g[i] = z;
-        z += n_par[i];
-      }
+      take(g.sc[1].du, (size_t)2 * H * d);
+      at = gat_grads_carve(g.tensor, 0, GAT_CORE, 1, block, at);
     }
-  }
-  for (int i = 0; i < 8 && ok; ++i)
-    for (int j = 0; j < 2; ++j) {
-      g.mom[2 * i + j] = (float*)alloc((size_t)(n_par[i] ? n_par[i] : 1) * 4);
-      if (!g.mom[2 * i + j] || hipMemset(g.mom[2 * i + j], 0, (size_t)(n_par[i] ? n_par[i] : 1) * 4) != hipSuccess) ok = false;
-    }
-  const int64_t cap_edges = t->work[0].base[0]->un.cap_edges;
+    return at;
+  };
+  t->zero_bytes = lay_out(nullptr) * 4;
+  t->zero_base = alloc(t->zero_bytes);
+  if (t->zero_base) lay_out((float*)t->zero_base);
   g.u = (float*)alloc((size_t)2 * H * d * 4);
-  g.dxw = (float*)alloc((size_t)rows1_max * C1 * 4);
-  g.ds = (float*)alloc((size_t)2 * rows1_max * 4);
-  g.dd = g.ds ? g.ds + rows1_max : nullptr;
-  g.alpha = (float*)alloc((size_t)(2 * rows1_max + cap_edges) * 4);
-  g.dh0 = (float*)alloc((size_t)rows1_max * H * C0 * 4);
-  g.dh0s = (float*)alloc((size_t)rows1_max * H * C0 * 4);
-  g.dz = (float*)alloc((size_t)H * rows1_max * d * 4);
-  ok = ok && t->zero_base && g.u && g.dxw && g.ds && g.alpha && g.dh0 && g.dh0s && g.dz;
-  if (want_fork && ok) {  // the second encode's own scratch (its rows, its edges), a ctx with a stream of its own, the events
-    const int64_t r1 = t->enc[1].rows_cap[0], ce1 = t->work[0].base[1]->un.cap_edges;
-    g.x.dxw = (float*)alloc((size_t)r1 * C1 * 4);
-    g.x.ds = (float*)alloc((size_t)2 * r1 * 4);
-    g.x.dd = g.x.ds ? g.x.ds + r1 : nullptr;
-    g.x.alpha = (float*)alloc((size_t)(2 * r1 + ce1) * 4);
-    g.x.dh0 = (float*)alloc((size_t)r1 * H * C0 * 4);
-    g.x.dh0s = (float*)alloc((size_t)r1 * H * C0 * 4);
-    g.x.dz = (float*)alloc((size_t)H * r1 * d * 4);
-    ok = g.x.dxw && g.x.ds && g.x.alpha && g.x.dh0 && g.x.dh0s && g.x.dz && g.x.du && lp_fork_setup(t);
-  }
+  ok = ok && t->zero_base && g.u && gat_moments_alloc(t->owned, g.tensor, 0, GAT_CORE) &&
+       gat_scratch_alloc(t, g.sc[0], t->lctx, rows1_max, t->work[0].base[0]->un.cap_edges, b_max);
+  if (want_fork && ok)  // the second stream's ctx and events, its own scratch (the random negatives' rows and edges)
+    ok = lp_fork_setup(t) && gat_scratch_alloc(t, g.sc[1], t->actx, t->enc[1].rows_cap[0], t->work[0].base[1]->un.cap_edges, t->enc[1].b);
   if (ok) {
     g.wt1 = (float*)alloc((size_t)C1 * H * C0 * 4);
     ok = g.wt1 != nullptr;
@@ -3525,25 +3544,23 @@ int32_t gigl_gat_nablp_train_plan_grads(gigl_nablp_train_plan* t, int32_t layer,
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (t->gat.parts_pending) {  // the step kept the projections' gradients as partial sums: add them up, once
     auto& g = t->gat;
+    float *gw0 = g.at(GAT_W, 0).g[0], *gb0 = g.at(GAT_BIAS, 0).p ? g.at(GAT_BIAS, 0).g[0] : nullptr;
     for (int k = 0; k < 2; ++k) {
       const int32_t* n1 = t->enc[k].base->un.meta + GIGL_META_LEVEL0 + 1;
-      int32_t rc = gigl_linear_weight_grad_sum(ctx, g.part_w1[k], nullptr, n1, g.c1, g.heads * g.c0, g.rc_w1[k], g.g[4], nullptr);
+      int32_t rc = gigl_linear_weight_grad_sum(ctx, g.part_w1[k], nullptr, n1, g.c1, g.heads * g.c0, g.rc_w1[k], g.at(GAT_W, 1).g[0],
+                                               nullptr);
       for (int h = 0; h < g.heads && rc == GIGL_OK; ++h)
-        rc = gigl_linear_weight_grad_sum(ctx, g.part_w0[k][h], g.bias[0] ? g.part_b0[k][h] : nullptr, n1, g.c0, g.d_in, g.rc_w0[k],
-                                         g.g[0] + (int64_t)h * g.c0 * g.d_in, g.bias[0] ? g.g[3] + h * g.c0 : nullptr);
+        rc = gigl_linear_weight_grad_sum(ctx, g.part_w0[k][h], gb0 ? g.part_b0[k][h] : nullptr, n1, g.c0, g.d_in, g.rc_w0[k],
+                                         gw0 + (int64_t)h * g.c0 * g.d_in, gb0 ? gb0 + h * g.c0 : nullptr);
       if (rc != GIGL_OK) return rc;
     }
     g.parts_pending = false;
   }
-  float* dst[4] = {gw, g_att_src, g_att_dst, gb};
-  for (int i = 0; i < 4; ++i) {
-    const int j = 4 * layer + i;
-    if (!dst[i] || !t->gat.n[j]) continue;
-    GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst[i], t->gat.g[j], (size_t)t->gat.n[j] * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    if (t->fork && j >= 5)  // (the second encode's share, accumulated on its own stream)
-      hipLaunchKernelGGL(lp_acc_kernel, dim3(4), dim3(256), 0, ctx->stream, dst[i], (const float*)t->gat.x.g[j], t->gat.n[j]);
-  }
-  return GIGL_OK;
+  float* const dst[4] = {gw, g_att_src, g_att_dst, gb};
+  const GatPart part[4] = {GAT_W, GAT_ATT_SRC, GAT_ATT_DST, GAT_BIAS};
+  int32_t rc = GIGL_OK;
+  for (int i = 0; i < 4 && rc == GIGL_OK; ++i) rc = gat_grad_export(ctx, t->gat.at(part[i], layer), dst[i], 4);
+  return rc;
 }
 
 int32_t gigl_gat_nablp_train_plan_set_edge_features(gigl_nablp_train_plan* t, gigl_feat* edge_table, float* const* w_edge,
@@ -3571,54 +3588,36 @@ int32_t gigl_gat_nablp_train_plan_set_edge_features(gigl_nablp_train_plan* t, gi
   const int64_t hc[2] = {(int64_t)H * g.c0, g.c1};
   ge.De = De;
   for (int l = 0; l < 2; ++l) {
-    ge.w_edge[l] = w_edge[l];
-    ge.att_edge[l] = att_edge[l];
-    ge.w_msg[l] = w_edge_msg ? w_edge_msg[l] : nullptr;
-    ge.n[3 * l] = hc[l] * De;
-    ge.n[3 * l + 1] = hc[l];
-    ge.n[3 * l + 2] = ge.w_msg[l] && ge.w_msg[l] != ge.w_edge[l] ? hc[l] * De : 0;
+    g.at(GAT_W_EDGE, l).set(w_edge[l], hc[l] * De);
+    g.at(GAT_ATT_EDGE, l).set(att_edge[l], hc[l]);
+    float* w_msg = w_edge_msg ? w_edge_msg[l] : nullptr;
+    g.at(GAT_W_MSG, l).set(w_msg, w_msg != w_edge[l] ? hc[l] * De : 0);  // (shared: n == 0, gradient slots joined below)
   }
-  auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
-  const bool fork = t->fork, any_msg = ge.w_msg[0] || ge.w_msg[1];
+  const bool fork = t->fork, any_msg = g.at(GAT_W_MSG, 0).p || g.at(GAT_W_MSG, 1).p;
   const size_t nv = (size_t)(H + 1) * De;
-  size_t set_floats = nv;  // ge | dv
-  for (int i = 0; i < 6; ++i) set_floats += (size_t)ge.n[i];
-  float* z = (float*)alloc(set_floats * (fork ? 2 : 1) * 4);
-  ge.v = (float*)alloc(nv * 4);
-  bool ok = z && ge.v;
-  ge.zero_base = z;
-  ge.zero_bytes = set_floats * (fork ? 2 : 1) * 4;
-  for (int side = 0; side < (fork ? 2 : 1) && ok; ++side) {
-    float** slots = side ? ge.x.ge : ge.ge;
-    for (int i = 0; i < 6; ++i) {
-      slots[i] = z;
-      z += ge.n[i];
-    }
-    (side ? ge.x.dv : ge.dv) = z;
-    z += nv;
-  }
-  for (int i = 0; i < 6 && ok; ++i)
-    for (int j = 0; j < 2; ++j) {
-      const size_t bytes = (size_t)(ge.n[i] ? ge.n[i] : 1) * 4;
-      ge.mom[2 * i + j] = (float*)alloc(bytes);
-      if (!ge.mom[2 * i + j] || hipMemset(ge.mom[2 * i + j], 0, bytes) != hipSuccess) ok = false;
-    }
+  // the edge block: gradients | dv, and as much again for a forked stream (no att_edge slots there: its tail stays unused)
+  auto lay_out = [&](float* block) {
+    const size_t half = gat_grads_carve(g.tensor, GAT_CORE, GAT_TENSORS, 0, block, 0) + nv;
+    g.sc[0].dv = block ? block + half - nv : nullptr;
+    if (!fork) return half;
+    g.sc[1].dv = block ? block + gat_grads_carve(g.tensor, GAT_CORE, GAT_TENSORS, 1, block, half) : nullptr;
+    return 2 * half;
+  };
+  ge.zero_bytes = lay_out(nullptr) * 4;
+  ge.zero_base = train_alloc(t->owned, ge.zero_bytes);
+  ge.v = (float*)train_alloc(t->owned, nv * 4);
+  bool ok = ge.zero_base && ge.v;
+  if (ok) lay_out((float*)ge.zero_base);
+  for (int l = 0; l < 2; ++l)  // a shared message weight's gradient joins lin_edge.weight's, on both streams
+    if (g.at(GAT_W_MSG, l).p == g.at(GAT_W_EDGE, l).p)
+      for (int k = 0; k < 2; ++k) g.at(GAT_W_MSG, l).g[k] = g.at(GAT_W_EDGE, l).g[k];
+  ok = ok && gat_moments_alloc(t->owned, g.tensor, GAT_CORE, GAT_TENSORS);
   if (any_msg && ok) {
-    int64_t rows1_max = 0, b_max = 0;
     for (int k = 0; k < 2; ++k) {
-      rows1_max = t->enc[k].rows_cap[0] > rows1_max ? t->enc[k].rows_cap[0] : rows1_max;
-      b_max = t->enc[k].b > b_max ? t->enc[k].b : b_max;
-      ge.ze[k] = (float*)alloc((size_t)t->enc[k].rows_cap[0] * H * De * 4);
+      ge.ze[k] = (float*)train_alloc(t->owned, (size_t)t->enc[k].rows_cap[0] * H * De * 4);
       ok = ok && ge.ze[k];
     }
-    ge.dze = (float*)alloc((size_t)rows1_max * H * De * 4);
-    ge.z1 = (float*)alloc((size_t)b_max * De * 4);
-    ok = ok && ge.dze && ge.z1;
-    if (fork) {  // the second encode's own scratch, as its Alt buffers
-      ge.x.dze = (float*)alloc((size_t)t->enc[1].rows_cap[0] * H * De * 4);
-      ge.x.z1 = (float*)alloc((size_t)t->enc[1].b * De * 4);
-      ok = ok && ge.x.dze && ge.x.z1;
-    }
+    for (int k = 0; k < (fork ? 2 : 1); ++k) ok = ok && gat_scratch_alloc_edge(t, g.sc[k]);
   }
   // every workspace's batch graphs get their edge ids from their own graph part (plan_edge_ids_kernel; all rows are numbered)
   for (auto& wk : t->work)
@@ -3646,17 +3645,12 @@ int32_t gigl_gat_nablp_train_plan_edge_grads(gigl_nablp_train_plan* t, int32_t l
   gigl_ctx* ctx = t->ctx;
   GIGL_REQUIRE(ctx, t->kind == 1 && t->gat.e.table && layer >= 0 && layer < 2, "bad plan / layer");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const auto& ge = t->gat.e;
-  float* dst[3] = {g_w_edge, g_att_edge, g_w_edge_msg};
-  for (int j = 0; j < 3; ++j) {
-    const int k = 3 * layer + j;
-    if (!dst[j] || !ge.n[k]) continue;
-    GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst[j], ge.ge[k], (size_t)ge.n[k] * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    if (t->fork && j != 1)  // (the second encode's share of the message weights' gradients, accumulated on its own stream)
-      hipLaunchKernelGGL(lp_acc_kernel, dim3(16), dim3(256), 0, ctx->stream, dst[j], (const float*)ge.x.ge[k], ge.n[k]);
-  }
+  float* const dst[3] = {g_w_edge, g_att_edge, g_w_edge_msg};
+  const GatPart part[3] = {GAT_W_EDGE, GAT_ATT_EDGE, GAT_W_MSG};
+  int32_t rc = GIGL_OK;
+  for (int j = 0; j < 3 && rc == GIGL_OK; ++j) rc = gat_grad_export(ctx, t->gat.at(part[j], layer), dst[j], 16);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
-  return GIGL_OK;
+  return rc;
 }
 
 }  // extern "C"

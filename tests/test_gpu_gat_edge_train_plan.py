@@ -187,10 +187,19 @@ def test_edge_plan_step_against_the_cpu_restatement(conv, share, heads, d, dtype
         eng.close()
 
 
-@pytest.mark.parametrize("conv,share,heads,d,dtype,hid,out,de", [
-    ("gat", True, 4, 100, np.float32, 8, 32, 3),
-    ("edge_attr_gat", True, 2, 768, np.float16, 128, 256, 16),
-    ("edge_attr_gat", False, 1, 320, np.float32, 256, 256, 64)])
+EDGE_STEP_CASES = [("gat", True, 4, 100, np.float32, 8, 32, 3), ("edge_attr_gat", True, 2, 768, np.float16, 128, 256, 16),
+                   ("edge_attr_gat", False, 1, 320, np.float32, 256, 256, 64)]
+
+
+@pytest.mark.parametrize("conv,share,heads,d,dtype,hid,out,de", EDGE_STEP_CASES)
+def test_edge_plan_unforked_step_equals_the_autograd_step(monkeypatch, conv, share, heads, d, dtype, hid, out, de):
+    """the same step, same body and bars, with GIGL_LP_FORK=0 (read at every create): both encodes one after the other on
+    the caller's stream, d v and the message weights' gradients accumulated in one place"""
+    monkeypatch.setenv("GIGL_LP_FORK", "0")
+    test_edge_plan_step_equals_the_autograd_step(conv, share, heads, d, dtype, hid, out, de)
+
+
+@pytest.mark.parametrize("conv,share,heads,d,dtype,hid,out,de", EDGE_STEP_CASES)
 def test_edge_plan_step_equals_the_autograd_step(conv, share, heads, d, dtype, hid, out, de):
     """against the autograd step over the same batches (hbm.ResidentGraph.train_graph with train_as_graph_data ->
     GAT._forward_graph: dense per-batch attributes, every source row projected): all first-step gradients, the three edge

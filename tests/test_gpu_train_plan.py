@@ -344,9 +344,20 @@ def test_transposed_backward_gather_equals_the_scatter_and_a_dense_restatement(d
     eng.close()
 
 
+GAT_LP_STEP_CASES = [(2, 16, 32, True, torch.float32), (1, 32, 16, True, torch.float16), (4, 8, 16, False, torch.float32)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("heads,hid,out,norm,dtype", [(2, 16, 32, True, torch.float32), (1, 32, 16, True, torch.float16),
-                                                       (4, 8, 16, False, torch.float32)])
+@pytest.mark.parametrize("heads,hid,out,norm,dtype", GAT_LP_STEP_CASES)
+def test_library_gat_link_prediction_unforked_step_equals_the_autograd_step(setup, monkeypatch, heads, hid, out, norm, dtype):
+    """the same step, same body and bars, with GIGL_LP_FORK=0 (read at every create): both encodes one after the other on
+    the caller's stream, sharing one scratch and one set of accumulators, the layers part captured and replayed"""
+    monkeypatch.setenv("GIGL_LP_FORK", "0")
+    test_library_gat_link_prediction_step_equals_the_autograd_step(setup, heads, hid, out, norm, dtype)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("heads,hid,out,norm,dtype", GAT_LP_STEP_CASES)
 def test_library_gat_link_prediction_step_equals_the_autograd_step(setup, heads, hid, out, norm, dtype):
     """gigl_gat_nablp_train_plan_* — the link-prediction training step with configs[4]'s encoder (two GATConv layers, the
     first from the input side) as one library call per step — against the autograd step over the same batches handed to
