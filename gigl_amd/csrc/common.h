@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
@@ -194,6 +195,8 @@ int32_t gigl_hs_scale_update(gigl_ctx* ctx, const float* w, int64_t n, float s_a
 // *out_bits = max(*out_bits, largest |element| of rows < *n_rows, columns < d of a tiled reduced half) as float bits
 int32_t gigl_tiled_absmax(gigl_ctx* ctx, const float* a_tiled, const int32_t* n_rows, int64_t rows_cap, int32_t d,
                           uint32_t* out_bits);
+// C linkage for the edge-term entry points (not part of include/gigl_hip.h: the plans call them; the kernel tests do too)
+extern "C" {
 // the first GAT layer's edge terms (the one-call plan over a graph with edge features; semantics of gigl_gat_aggregate_edge):
 // the edge stored at col position p carries row eid[p] of `table` ([n_edges][edge_dim] fp32, read in place); the logits gain
 // <e, att_edge_folded[h]>, the added self loop carries the mean attribute of the row's other in-edges; w_edge_msg != NULL
@@ -206,6 +209,8 @@ struct gigl_gat_edge_terms {
   const float* w_edge_msg;
   float* ze;
 };
+// (mirrored as a ctypes.Structure by the kernel tests)
+static_assert(sizeof(gigl_gat_edge_terms) == 48 && offsetof(gigl_gat_edge_terms, ze) == 40, "gigl_gat_edge_terms layout");
 int32_t gigl_gat_input_layer_fused_hs(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d,
                                       const uint32_t* gather_ids, const int32_t* n_local_dev, const float* w,
                                       const float* att_src, const float* att_dst, int32_t heads, int32_t channels,
@@ -226,7 +231,8 @@ int32_t gigl_gat_aggregate_edge_indexed(gigl_ctx* ctx, const float* h, const flo
 // The training plan's edge-feature pieces (agg.hip; gigl_gat_nablp_train_plan_set_edge_features).  gigl_gat_input_aggregate /
 // _backward with the first layer's edge terms (edge == NULL: exactly those): the forward also writes edge->ze when
 // edge->w_edge_msg is set; the backward takes dze [rows][heads][edge_dim] = W_msg^T dy then and ADDS d v = sum_e dpre_e e_e
-// (the self loop through its mean attribute) to dv [heads][edge_dim] in the same single sweep
+// (the self loop through its mean attribute) to dv [heads][edge_dim] in the same single sweep.  The backward skips a row by
+// its dz alone: dze must be zero wherever dz is (both are products of the same dy; a padding row has neither)
 int32_t gigl_gat_input_aggregate_edge(gigl_ctx* ctx, const void* src, int32_t src_dtype, int32_t d, const uint32_t* gather_ids,
                                       const float* u, int32_t heads, float negative_slope, const int32_t* rowptr,
                                       const int32_t* rowend, const int32_t* col, const int32_t* n_rows_dev, int64_t rows_cap,
@@ -248,6 +254,7 @@ int32_t gigl_gat_aggregate_backward_indexed(gigl_ctx* ctx, const float* h, const
                                             const float* dout, const float* table, const int32_t* eid, int32_t edge_dim,
                                             const float* att_edge_folded, const float* dze, float* alpha_scratch, float* dh,
                                             float* d_alpha_src, float* d_alpha_dst, float* dv, float* z_out);
+}  // extern "C"
 // The fused two-layer projection (agg.hip, linear_fused2x_kernel): layer 0's [mean | self] projection (half split, two-source
 // tiled operand) with the LAST layer's [W_l | W_r] applied to the hidden rows before they leave the workgroup — y2 =
 // [rows][gigl_fused2_row_floats()] of p = [W_l h | W_r h]; gigl_sage_fused_out is the last layer over those rows (one
