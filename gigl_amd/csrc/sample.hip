@@ -524,8 +524,10 @@ struct Sel {
 //                       where its candidates are (threshold T, level, the run of pairs between two index entries):
 //                       a chain of three dependent loads that a wave-per-row kernel would sit through serially, here
 //                       issued for 64 rows at once; 32-byte descriptor per slot.
-//   expand_rows_kernel  one WAVE per parent slot, driven by the descriptor: candidates -> survivors -> f best ->
-//                       neighbour ids; what is left of the dependent chain is descriptor -> pairs -> ids.
+//   expand_rows_kernel  one WAVE per two parent slots and step, driven by their descriptors: candidates -> survivors ->
+//                       f best -> neighbour ids.  A row's dependent chain is item -> descriptor -> candidates -> ids; the
+//                       wave walks its list as a pipeline (items two steps ahead, descriptors one step ahead), so that
+//                       in steady state a step waits twice: for its candidates, then for its ids.
 // ------------------------------------------------------------------------------------------
 enum { ROW_INVALID = 0, ROW_COPY = 1, ROW_FLAT = 2, ROW_LEVEL = 3, ROW_HASH = 4, ROW_SERIAL = 5, ROW_SERIAL_HASH = 6,
        ROW_SKIP = 7 };
@@ -667,109 +669,283 @@ __global__ __launch_bounds__(256) void plan_rows_kernel(ExpandArgs a, RangeTable
   }
 }
 
+// A pointer that was read from memory (RowDesc::ptr, a peer's col array) has no address space the compiler can see,
+// and a load through it is a FLAT load: it counts on lgkmcnt as well as vmcnt, so every wait for a descriptor or an
+// LDS hand-off also waits for it.  All of these point into device memory: say so, and the loads are global loads.
+template <class T>
+__device__ __forceinline__ const T* as_global(const void* p) {
+  return (const T*)(const __attribute__((address_space(1))) T*)(uintptr_t)p;
+}
+
+// The two descriptors of a step, as expand_rows_kernel holds them: ONE vector register, dword w of the first row's
+// descriptor in lane w, of the second row's in lane 8 + w (one load instruction, one wait, and no scalar registers
+// until a field is used).  `o` is 0 or 8.
+__device__ __forceinline__ uint32_t desc_n(uint32_t dv, int o) { return readlane32(dv, o + 2); }
+__device__ __forceinline__ uint32_t desc_base(uint32_t dv, int o) { return readlane32(dv, o + 3); }
+__device__ __forceinline__ uint32_t desc_T(uint32_t dv, int o) { return readlane32(dv, o + 4); }
+__device__ __forceinline__ uint32_t desc_kind_cnt(uint32_t dv, int o) { return readlane32(dv, o + 5); }
+__device__ __forceinline__ int64_t desc_s(uint32_t dv, int o) {
+  return (int64_t)(((uint64_t)readlane32(dv, o + 1) << 32) | readlane32(dv, o));
+}
+__device__ __forceinline__ const void* desc_ptr(uint32_t dv, int o) {
+  return (const void*)(uintptr_t)(((uint64_t)readlane32(dv, o + 7) << 32) | readlane32(dv, o + 6));
+}
+__device__ __forceinline__ RowDesc desc_unpack(uint32_t dv, int o) {
+  RowDesc d;
+  d.s = desc_s(dv, o);
+  d.n = desc_n(dv, o);
+  d.base = desc_base(dv, o);
+  d.T = desc_T(dv, o);
+  d.kind_cnt = desc_kind_cnt(dv, o);
+  d.ptr = desc_ptr(dv, o);
+  return d;
+}
+static_assert(sizeof(RowDesc) == 32 && offsetof(RowDesc, n) == 8 && offsetof(RowDesc, base) == 12 &&
+                  offsetof(RowDesc, T) == 16 && offsetof(RowDesc, kind_cnt) == 20 && offsetof(RowDesc, ptr) == 24,
+              "desc_* read RowDesc by dword");
+
 // candidates of one row fetched ahead of their use: up to two 64-wide chunks of (proxy, j)
 struct Cand {
-  uint32_t k0, j0, k1, j1;
-  bool ahead;  // (wave-uniform) all of the row's candidates are here
+  uint32_t k0, j0, k1, j1;  // j: read from a level's pairs only (a flat row's j is its lane)
+  int mode;                 // (wave-uniform) CAND_*: not CAND_NONE = all of the row's candidates are here
 };
+enum { CAND_NONE = 0, CAND_LEVEL = 1, CAND_FLAT = 2 };
 
+// Shaped for the wait counts, which the compiler derives from the control flow it sees, not from the one that can
+// happen.  Written as `if (level run) {pair loads} else if (flat row) {proxy loads}`, the two cases shared their
+// registers and the compiler's lowering left a path from one case's loads into the other case's block: that block's
+// first register write then waited for loads "pending" on that path — the other ROW's candidates and the prefetches
+// among them — and the two rows' candidates were fetched one after the other.  So both cases are ONE sequence of
+// dword loads from a wave-uniform base plus a lane offset (a pair's proxy and a flat proxy are the same load; a pair's
+// j is a second one), a register is not written again once a load into it is out, and every lane loads: a lane past the
+// run reads the run's last pair, and select_ahead drops it by its lane number.  An empty run has no pair to read: the
+// general path settles it, as it would have after an empty selection here.
 __device__ __forceinline__ Cand fetch_candidates(const RowDesc& d, int lane) {
   Cand c;
-  c.k0 = c.k1 = 0xFFFFFFFFu;
-  c.j0 = c.j1 = d.base;  // position 0: never inside a window
-  c.ahead = false;
   const uint32_t kind = d.kind_cnt & 7u, cnt = d.kind_cnt >> 3;
-  if (kind == ROW_LEVEL && cnt <= 128u) {
-    const uint2* ent = (const uint2*)d.ptr;
-    if ((uint32_t)lane < cnt) {
-      const uint2 x = ent[lane];
-      c.j0 = x.x;
-      c.k0 = x.y;
+  c.mode = kind == ROW_LEVEL && cnt - 1u < 128u ? CAND_LEVEL : kind == ROW_FLAT && d.n <= 128u ? CAND_FLAT : CAND_NONE;
+  c.k0 = c.j0 = c.k1 = c.j1 = 0u;
+  if (c.mode != CAND_NONE) {
+    const bool level = c.mode == CAND_LEVEL;
+    // level: pair e = (j, proxy) at ptr + 8 e;  flat: the proxy of position i = lane + 1 at ptr + 4 (base + i)
+    // (a flat chunk's last lanes may read past the window: inside the table's allocation, dropped later)
+    const char* pj = (const char*)as_global<uint32_t>(d.ptr) + (level ? 0u : 4u * (uint64_t)d.base);
+    const char* pk = pj + 4;
+    const uint32_t o0 = level ? 8u * min((uint32_t)lane, cnt - 1u) : 4u * (uint32_t)lane;
+    const uint32_t o1 = level ? 8u * min((uint32_t)lane + 64u, cnt - 1u) : 4u * (uint32_t)lane + 256u;
+    c.k0 = *(const uint32_t*)(pk + o0);
+    if (level) c.j0 = *(const uint32_t*)(pj + o0);
+    if (level ? cnt > 64u : d.n > 64u) {
+      c.k1 = *(const uint32_t*)(pk + o1);
+      if (level) c.j1 = *(const uint32_t*)(pj + o1);
     }
-    if ((uint32_t)lane + 64u < cnt) {
-      const uint2 x = ent[lane + 64];
-      c.j1 = x.x;
-      c.k1 = x.y;
-    }
-    c.ahead = true;
-  } else if (kind == ROW_FLAT && d.n <= 128u) {
-    const uint32_t* src = (const uint32_t*)d.ptr + d.base;
-    c.j0 = d.base + (uint32_t)lane + 1u;
-    c.k0 = src[lane + 1];  // (the last lanes may read past the window: inside the table's allocation, dropped later)
-    if (d.n > 64u) {
-      c.j1 = c.j0 + 64u;
-      c.k1 = src[lane + 65];
-    }
-    c.ahead = true;
   }
   return c;
 }
 
 // the filter selection over candidates fetched ahead; false: the row goes to the general path
-__device__ __forceinline__ bool select_ahead(Sel<true>& sel, const RowDesc& d, const Cand& c, uint32_t* lk, uint32_t* li) {
-  const uint32_t n = d.n, T = d.T, base = d.base;
-  const bool all = T == 0xFFFFFFFFu;
+__device__ __forceinline__ bool select_ahead(Sel<true>& sel, const RowDesc& d, const Cand& c, uint32_t* lk, uint32_t* li,
+                                             int lane) {
+  const uint32_t n = d.n, T = d.T, base = d.base, cnt = d.kind_cnt >> 3;
+  const bool all = T == 0xFFFFFFFFu, level = c.mode == CAND_LEVEL;
   uint32_t count = 0;
-  const uint32_t i0 = c.j0 - base, i1 = c.j1 - base;
-  sel.offer(c.k0 & sel.dmask, i0, (uint32_t)(i0 - 1u) < n && (all || c.k0 < T), count, lk, li);
-  if ((d.kind_cnt & 7u) == ROW_LEVEL ? (d.kind_cnt >> 3) > 64u : n > 64u)
-    sel.offer(c.k1 & sel.dmask, i1, (uint32_t)(i1 - 1u) < n && (all || c.k1 < T), count, lk, li);
+  // position and presence of the lane's candidates (a level pair's j may lie in the slack around the window: i wraps)
+  const uint32_t i0 = level ? c.j0 - base : (uint32_t)lane + 1u, i1 = level ? c.j1 - base : (uint32_t)lane + 65u;
+  const bool in0 = !level || (uint32_t)lane < cnt, in1 = !level || (uint32_t)lane + 64u < cnt;
+  sel.offer(c.k0 & sel.dmask, i0, in0 && (uint32_t)(i0 - 1u) < n && (all || c.k0 < T), count, lk, li);
+  if (level ? cnt > 64u : n > 64u)
+    sel.offer(c.k1 & sel.dmask, i1, in1 && (uint32_t)(i1 - 1u) < n && (all || c.k1 < T), count, lk, li);
   return sel.finish(count, lk, li);
 }
 
-// Two parent slots per wave: both descriptors, then both rows' candidates, are requested before anything is consumed,
-// and the first row's neighbour ids are in flight while the second row is ranked — the kernel is bound by the latency
-// of its dependent loads (SQ counters: waves wait 3/4 of their cycles at the 8 waves a SIMD holds), so two rows per
-// wave is twice the loads in flight.
+// general path of a step of expand_rows_kernel: every row the fast path left (copies, invalid parents, long runs,
+// windows outside the table, multi-edge graphs, rows the filter could not settle, ties), one row after the other
+__device__ __forceinline__ void expand_general(const ExpandArgs& a, const RangeTable& tb, const RowDesc* __restrict__ desc,
+                                               uint32_t p0, uint32_t p1, bool done0, bool done1, uint32_t* lk,
+                                               uint32_t* li, int lane) {
+  const int f = a.f;
+#pragma nounroll
+  for (int r = 0; r < 2; ++r) {
+    if (r == 0 ? done0 : done1) continue;
+    const uint32_t p = r == 0 ? p0 : p1;
+    const RowDesc d = desc[p];  // (read again, by the scalar unit: the step's copy lives in a vector register, and this
+                                // path is the one that has none to spare)
+    const uint32_t kind = d.kind_cnt & 7u;
+    if (kind == ROW_SKIP) continue;
+    uint32_t* out = a.out_nbr + (int64_t)p * f;
+    if (kind == ROW_INVALID) {
+      if (lane < f) out[lane] = GIGL_INVALID;
+      if (lane == 0) a.out_cnt[p] = 0;
+      continue;
+    }
+    const uint32_t* row = as_global<uint32_t>(row_of_desc(a, d.s));
+    const uint32_t n = d.n, base = d.base, T = d.T;
+    if (kind == ROW_COPY) {  // copy-through: the row is already the canonical ascending set
+      if (a.multi) {
+        const int nw = emit_sorted_distinct(row, (uint32_t)lane < n ? (uint32_t)lane + 1u : 0xFFFFFFFFu, f, lane, out);
+        if (lane == 0) a.out_cnt[p] = nw;
+        continue;
+      }
+      if (lane < f) out[lane] = (uint32_t)lane < n ? row[lane] : GIGL_INVALID;
+      if (lane == 0) a.out_cnt[p] = (int32_t)n;
+      continue;
+    }
+    const bool in_table = kind != ROW_HASH && kind != ROW_SERIAL_HASH;
+    uint32_t sel_idx;
+    {
+      Sel<true> fast;
+      fast.init(f, lane, a.proxy_drop);
+      bool done = false;
+      if (kind == ROW_LEVEL) done = fast.filter_level(as_global<uint2>(d.ptr), d.kind_cnt >> 3, n, T, base, lk, li);
+      else if (kind == ROW_FLAT) done = fast.template filter_positions<SRC_FLAT>(as_global<uint32_t>(d.ptr), n, T, base, lk, li);
+      else if (kind == ROW_HASH) done = fast.template filter_positions<SRC_HASH>(nullptr, n, T, base, lk, li);
+      if (!done) fast.serial(tb, n, base, T, in_table);
+      sel_idx = fast.idx;
+      if (fast.tie) {  // a 32-bit proxy tie touched the result (about once per 10^7 rows): redo exactly
+        Sel<false> exact;
+        exact.init(f, lane);
+        exact.serial(tb, n, base, T, in_table);
+        sel_idx = exact.idx;
+      } else if (fast.ordered) {  // selected lanes hold the positions in ascending order
+        const unsigned long long m = fast.selmask;
+        const bool sel = (m >> lane) & 1ull;
+        const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const uint32_t val = sel ? row[sel_idx - 1] : GIGL_INVALID;
+        if (!a.multi) {
+          if (sel) out[slot] = val;
+          if (lane == 0) a.out_cnt[p] = f;
+          continue;
+        }
+        // ascending positions of an ascending row: a repeated id sits right after its first copy
+        if (sel) lk[slot] = val;
+        wave_lds_sync();
+        const bool keep = sel && (slot == 0 || lk[slot - 1] != val);
+        wave_lds_sync();
+        const unsigned long long km = __ballot(keep);
+        if (lane < f) out[lane] = GIGL_INVALID;
+        if (keep) out[__builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u))] = val;
+        if (lane == 0) a.out_cnt[p] = (int32_t)__popcll(km);
+        continue;
+      }
+    }
+    if (a.multi) {
+      const int nw = emit_sorted_distinct(row, sel_idx, f, lane, out);
+      if (lane == 0) a.out_cnt[p] = nw;
+      continue;
+    }
+    emit_sorted(row, sel_idx, f, lane, out);
+    if (lane == 0) a.out_cnt[p] = f;
+  }
+  wave_lds_sync();  // (the next pair reuses this wave's scratch)
+  // (rare enough to wait here for all of it: the next step starts with nothing in flight, as after a fast one)
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+}
+
+// Two parent slots per wave and step, the wave's steps as a three-stage pipeline.  A step by itself is a chain of
+// four dependent loads — the pair's items, its two descriptors, the rows' candidates, the chosen neighbour ids — but
+// k advances by a fixed stride, so the addresses of the later steps' items do not depend on this step's data: while
+// step k's candidates are in flight, the descriptors of step k + stride and the items of step k + 2 stride are in
+// flight too, requested BEFORE the candidates; vector memory returns in order, so the one wait for the candidates
+// covers all three.  In steady state a step is two round trips: candidates, then ids (the first row's ids are in
+// flight while the second row is ranked).  What keeps the compiler's wait counts exact (see gather_mean_kernel):
+//  - a pair's items are ONE 8-byte load (lists start 8-byte aligned and hold an even number of words) and the two
+//    descriptors ONE load instruction (desc_*), both through a VECTOR address the compiler cannot prove uniform:
+//    scalar loads return out of order and share lgkmcnt with the selection's LDS traffic;
+//  - every prefetch is unconditional and its address valid by construction: the item index is clamped into the list,
+//    and a parent that does not exist (a word at or past n_items is stale) is replaced by n_parents, the ROW_SKIP
+//    descriptor, with a select — nothing reads outside the hop's scratch;
+//  - the next items move to scalar registers right behind the first row's ranking, where they have arrived, and
+//    before the step's stores;
+//  - candidates and ids are global loads (as_global): they do not count on lgkmcnt;
+//  - the loop is entered with nothing in flight.
+// The kernel is bound by the latency of these loads (SQ counters: waves wait 3/4 of their cycles at the 8 waves a SIMD
+// holds), which is why two rows per wave — twice the loads in flight — and the shorter chain both pay.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void expand_rows_kernel(
     ExpandArgs a, RangeTable tb, const RowDesc* __restrict__ desc, WorkLists wl) {
   __shared__ __attribute__((aligned(16))) uint32_t s_lk[4][72], s_li[4][64];  // per-wave survivor scratch
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
   const int lane = threadIdx.x & 63;
-  // the parent slots and everything in their descriptors are the same for all lanes: say so (readfirstlane), and the
-  // per-row control flow below runs on the scalar unit with scalar loads
+  // the parent slots and everything in their descriptors are the same for all lanes: say so (readfirstlane / readlane),
+  // and the per-row control flow below runs on the scalar unit
   const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int f = a.f;
   uint32_t* lk = s_lk[wave_in_block];
   uint32_t* li = s_li[wave_in_block];
   // persistent grid (a multiple of WORK_LISTS waves): wave g walks list g % WORK_LISTS, two rows per step
   // (wl.iters > 0: the grid is `rounds` copies of the persistent one — copy r of a wave walks steps [r iters, (r + 1) iters) of
-  // that wave's sequence and retires, so that other streams' workgroups get wave slots while a hop is expanded)
+  // that wave's sequence and retires, so that other streams' workgroups get wave slots while a hop is expanded; every
+  // copy runs its own prologue)
   const uint32_t wgs_p = wl.iters > 0 ? (uint32_t)wl.wgs : gridDim.x;
   const uint32_t round = blockIdx.x / wgs_p;
   const uint32_t gw = (blockIdx.x % wgs_p) * 4u + (uint32_t)wave_in_block, n_waves = wgs_p * 4u;
   const uint32_t list = gw % WORK_LISTS, stride = n_waves / WORK_LISTS;
-  const int32_t n_items = __builtin_amdgcn_readfirstlane(wl.count[list * WORK_CNT_STRIDE]);
-  const uint32_t* items = wl.items + (int64_t)list * wl.cap;
+  const u32x2* items = reinterpret_cast<const u32x2*>(wl.items + (int64_t)list * wl.cap);  // pair k = words 2k, 2k + 1
+  const uint32_t last_pair = (uint32_t)(wl.cap >> 1) - 1u;  // (cap is a multiple of 256: the pair lies inside the list)
+  const uint32_t skip = (uint32_t)a.n_parents;              // (that slot holds a ROW_SKIP descriptor)
   const uint32_t k_first = gw / WORK_LISTS + stride * round * (uint32_t)wl.iters;
   const uint32_t k_end = wl.iters > 0 ? k_first + stride * (uint32_t)wl.iters : 0xFFFFFFFFu;
-  for (uint32_t k = k_first; (int32_t)(2u * k) < n_items && k < k_end; k += stride) {
-    const uint32_t p0 = __builtin_amdgcn_readfirstlane(items[2u * k]);
-    const uint32_t p1 = (int32_t)(2u * k + 1u) < n_items ? __builtin_amdgcn_readfirstlane(items[2u * k + 1u])
-                                                         : (uint32_t)a.n_parents;  // (that slot holds a ROW_SKIP descriptor)
-    const RowDesc d0 = desc[p0], d1 = desc[p1];
+  auto vec = [](uint32_t x) -> uint32_t {
+    asm("" : "+v"(x));
+    return x;
+  };
+  // the items of step k; a step past the list's capacity reads the list's last pair (nobody uses it)
+  auto load_items = [&](uint32_t k) -> u32x2 { return items[vec(min(k, last_pair))]; };
+  int32_t n_items = 0;
+  // the parents of step k from its items: a word at or past n_items is stale
+  auto parents_of = [&](uint32_t k, u32x2 it, uint32_t& p0, uint32_t& p1) {
+    const uint32_t x = __builtin_amdgcn_readfirstlane(it.x), y = __builtin_amdgcn_readfirstlane(it.y);
+    p0 = (int32_t)(2u * k) < n_items ? x : skip;
+    p1 = (int32_t)(2u * k + 1u) < n_items ? y : skip;
+  };
+  // both descriptors of a step: lanes 0-7 the dwords of desc[p0], lanes 8-15 of desc[p1] (the other lanes repeat them)
+  const uint32_t* desc_w = reinterpret_cast<const uint32_t*>(desc);
+  auto load_desc = [&](uint32_t p0, uint32_t p1) -> uint32_t {
+    return desc_w[(uint64_t)((lane & 8) ? p1 : p0) * 8u + (uint32_t)(lane & 7)];
+  };
+  // prologue: the list's length and the items of the first two steps in one round trip, the first step's descriptors
+  // in a second
+  uint32_t k = k_first;
+  const u32x2 it_a = load_items(k), it_b = load_items(k + stride);
+  n_items = __builtin_amdgcn_readfirstlane(wl.count[list * WORK_CNT_STRIDE]);
+  if (!((int32_t)(2u * k) < n_items)) return;
+  uint32_t p0, p1, p0n, p1n;
+  parents_of(k, it_a, p0, p1);
+  parents_of(k + stride, it_b, p0n, p1n);
+  uint32_t dv = load_desc(p0, p1);
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+  for (;;) {
+    const uint32_t kn = k + stride;
+    const u32x2 it_nn = load_items(kn + stride);  // items two steps ahead,
+    const uint32_t dvn = load_desc(p0n, p1n);     // descriptors one step ahead, then this step's candidates
+    const RowDesc d0 = desc_unpack(dv, 0), d1 = desc_unpack(dv, 8);
     const Cand c0 = fetch_candidates(d0, lane), c1 = fetch_candidates(d1, lane);
     Sel<true> s0, s1;
     s0.init(f, lane, a.proxy_drop);
     s1.init(f, lane, a.proxy_drop);
     // fast path: ordered selections straight to the output
-    const bool done0 = c0.ahead && !a.multi && select_ahead(s0, d0, c0, lk, li) && !s0.tie;
+    const bool done0 = c0.mode != CAND_NONE && !a.multi && select_ahead(s0, d0, c0, lk, li, lane) && !s0.tie;
+    uint32_t p0nn, p1nn;
+    parents_of(kn + stride, it_nn, p0nn, p1nn);
     uint32_t slot0 = 0, val0 = 0;
     bool sel0 = false;
     if (done0) {
       const unsigned long long m = s0.selmask;
       sel0 = (m >> lane) & 1ull;
       slot0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-      if (sel0) val0 = row_of_desc(a, d0.s)[s0.idx - 1];
+      if (sel0) val0 = as_global<uint32_t>(row_of_desc(a, d0.s))[s0.idx - 1];
     }
-    const bool done1 = c1.ahead && !a.multi && select_ahead(s1, d1, c1, lk, li) && !s1.tie;
+    const bool done1 = c1.mode != CAND_NONE && !a.multi && select_ahead(s1, d1, c1, lk, li, lane) && !s1.tie;
     uint32_t slot1 = 0, val1 = 0;
     bool sel1 = false;
     if (done1) {
       const unsigned long long m = s1.selmask;
       sel1 = (m >> lane) & 1ull;
       slot1 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-      if (sel1) val1 = row_of_desc(a, d1.s)[s1.idx - 1];
+      if (sel1) val1 = as_global<uint32_t>(row_of_desc(a, d1.s))[s1.idx - 1];
     }
+    // (the ids are used here whatever the lane masks of the stores below are: a load that some path leaves pending
+    // would be waited for, with the step's stores, before the next step's first register write)
+    asm volatile("" ::"v"(val0), "v"(val1));
     if (done0) {
       if (sel0) a.out_nbr[(int64_t)p0 * f + slot0] = val0;
       if (lane == 0) a.out_cnt[p0] = f;
@@ -778,81 +954,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       if (sel1) a.out_nbr[(int64_t)p1 * f + slot1] = val1;
       if (lane == 0) a.out_cnt[p1] = f;
     }
-    if (done0 && done1) continue;
-    // general path: everything else (copies, invalid parents, long runs, windows outside the table, multi-edge graphs,
-    // rows the filter could not settle, ties), one row after the other
-  #pragma nounroll
-    for (int r = 0; r < 2; ++r) {
-      if (r == 0 ? done0 : done1) continue;
-      const RowDesc d = r == 0 ? d0 : d1;
-      const uint32_t p = r == 0 ? p0 : p1;
-      const uint32_t kind = d.kind_cnt & 7u;
-      if (kind == ROW_SKIP) continue;
-      uint32_t* out = a.out_nbr + (int64_t)p * f;
-      if (kind == ROW_INVALID) {
-        if (lane < f) out[lane] = GIGL_INVALID;
-        if (lane == 0) a.out_cnt[p] = 0;
-        continue;
-      }
-      const uint32_t* row = row_of_desc(a, d.s);
-      const uint32_t n = d.n, base = d.base, T = d.T;
-      if (kind == ROW_COPY) {  // copy-through: the row is already the canonical ascending set
-        if (a.multi) {
-          const int nw = emit_sorted_distinct(row, (uint32_t)lane < n ? (uint32_t)lane + 1u : 0xFFFFFFFFu, f, lane, out);
-          if (lane == 0) a.out_cnt[p] = nw;
-          continue;
-        }
-        if (lane < f) out[lane] = (uint32_t)lane < n ? row[lane] : GIGL_INVALID;
-        if (lane == 0) a.out_cnt[p] = (int32_t)n;
-        continue;
-      }
-      const bool in_table = kind != ROW_HASH && kind != ROW_SERIAL_HASH;
-      uint32_t sel_idx;
-      {
-        Sel<true> fast;
-        fast.init(f, lane, a.proxy_drop);
-        bool done = false;
-        if (kind == ROW_LEVEL) done = fast.filter_level((const uint2*)d.ptr, d.kind_cnt >> 3, n, T, base, lk, li);
-        else if (kind == ROW_FLAT) done = fast.template filter_positions<SRC_FLAT>((const uint32_t*)d.ptr, n, T, base, lk, li);
-        else if (kind == ROW_HASH) done = fast.template filter_positions<SRC_HASH>(nullptr, n, T, base, lk, li);
-        if (!done) fast.serial(tb, n, base, T, in_table);
-        sel_idx = fast.idx;
-        if (fast.tie) {  // a 32-bit proxy tie touched the result (about once per 10^7 rows): redo exactly
-          Sel<false> exact;
-          exact.init(f, lane);
-          exact.serial(tb, n, base, T, in_table);
-          sel_idx = exact.idx;
-        } else if (fast.ordered) {  // selected lanes hold the positions in ascending order
-          const unsigned long long m = fast.selmask;
-          const bool sel = (m >> lane) & 1ull;
-          const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-          const uint32_t val = sel ? row[sel_idx - 1] : GIGL_INVALID;
-          if (!a.multi) {
-            if (sel) out[slot] = val;
-            if (lane == 0) a.out_cnt[p] = f;
-            continue;
-          }
-          // ascending positions of an ascending row: a repeated id sits right after its first copy
-          if (sel) lk[slot] = val;
-          wave_lds_sync();
-          const bool keep = sel && (slot == 0 || lk[slot - 1] != val);
-          wave_lds_sync();
-          const unsigned long long km = __ballot(keep);
-          if (lane < f) out[lane] = GIGL_INVALID;
-          if (keep) out[__builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u))] = val;
-          if (lane == 0) a.out_cnt[p] = (int32_t)__popcll(km);
-          continue;
-        }
-      }
-      if (a.multi) {
-        const int nw = emit_sorted_distinct(row, sel_idx, f, lane, out);
-        if (lane == 0) a.out_cnt[p] = nw;
-        continue;
-      }
-      emit_sorted(row, sel_idx, f, lane, out);
-      if (lane == 0) a.out_cnt[p] = f;
-    }
-    wave_lds_sync();  // (the next pair reuses this wave's scratch)
+    if (!(done0 && done1)) expand_general(a, tb, desc, p0, p1, done0, done1, lk, li, lane);
+    if (!((int32_t)(2u * kn) < n_items && kn < k_end)) break;
+    k = kn;
+    p0 = p0n;
+    p1 = p1n;
+    p0n = p0nn;
+    p1n = p1nn;
+    dv = dvn;
   }
 }
 
