@@ -673,9 +673,13 @@ class ResidentGraph:
     def nablp_root_batches(self, ids: np.ndarray, n_pos: np.ndarray, batch_size: int, num_positives: int):
         """the ROOT side of nablp_batches only — (main roots anchor-major, positives per anchor, anchor ids) per batch, no
         batch graph built: what the library's link-prediction training plan takes (engine.NablpTrainPlan samples and
-        collates inside its step); same anchors, positives and order as nablp_batches"""
+        collates inside its step); same anchors, positives and order as nablp_batches — and, in a world, the same rank
+        striding: a rank's plan route and its autograd route see the same batches, in the same number on every rank"""
         P = int(num_positives)
         spans = [(lo, min(lo + batch_size, ids.size)) for lo in range(0, ids.size, batch_size)]
+        if self.world > 1 and spans:  # (as nablp_batches: batches r, r + world, ..., a short rank wraps around)
+            per_rank = -(-len(spans) // self.world)
+            spans = [spans[(self.rank + k * self.world) % len(spans)] for k in range(per_rank)]
         ar = torch.arange(P, device=self.device).view(1, P)
         for lo, hi in spans:
             chunk = ids[lo:hi]
@@ -686,10 +690,14 @@ class ResidentGraph:
             yield torch.cat([a2, grouped], dim=1).reshape(-1).contiguous(), cnt.to(torch.int32).contiguous(), chunk
 
     def random_negative_root_batches(self, batch_size: int):
-        """the roots of random_negative_batches, batch by batch, forever (no batch graph built)"""
+        """the roots of random_negative_batches, batch by batch, forever (no batch graph built); rank-strided as they are"""
         order = self.inference_root_order()
+        los = list(range(0, order.size, batch_size))
+        if self.world > 1 and los:  # (as random_negative_batches: chunks r, r + world, ... of the pass)
+            per_rank = -(-len(los) // self.world)
+            los = [los[(self.rank + k * self.world) % len(los)] for k in range(per_rank)]
         while order.size:
-            for lo in range(0, order.size, batch_size):
+            for lo in los:
                 chunk = order[lo:lo + batch_size]
                 yield torch.from_numpy(chunk.astype(np.uint32).view(np.int32)).to(self.device)
 

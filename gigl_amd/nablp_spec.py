@@ -866,7 +866,10 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
 
     def _library_plan(self, cfg: GbmlConfigPbWrapper):
         """_library_train_plan's choice and construction; eval() makes its plan for the test pass through this too"""
-        if str(self._kwargs.get("train_plan", "auto")).lower() == "off" or self._hbm_split(cfg) is None:
+        want = str(self._kwargs.get("train_plan", "auto")).lower()
+        if want not in ("auto", "on", "off"):
+            raise ValueError(f"train_plan must be auto, on or off (got {want!r})")
+        if want == "off" or self._hbm_split(cfg) is None:
             return None
         res = self._resident
         inner = self.model.module if hasattr(self.model, "module") else self.model
