@@ -21,6 +21,28 @@ namespace {
 // lanes [g*LPH, (g+1)*LPH) hold the chunks of head g: sum over them (LPH a power of two <= 64)
 __device__ __forceinline__ float head_sum(float v, int lph) { return gigl_group_sum(v, lph); }
 
+// One edge of the HGT forward's online softmax, shared by the wave-per-row and the packed kernel.  The packed kernel promises
+// the wave-per-row kernel's bits, so the operations are pinned here: contraction is off, and what is fused is written as
+// fmaf (left to the compiler, the four unrolled edges of the packed kernel came out fused in three places and unfused in
+// one).  logit is rounded for the maximum; the exponent of w is the fused x * inv_sqrt_d - mn.
+__device__ __forceinline__ float hgt_dot(const float4& a, const float4& b) {
+#pragma clang fp contract(off)
+  return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
+}
+__device__ __forceinline__ void hgt_fold(float d, float pr, float inv_sqrt_d, const float4& vv, float& m, float& s,
+                                         float4& acc) {
+#pragma clang fp contract(off)
+  const float x = d * pr;
+  const float mn = fmaxf(m, x * inv_sqrt_d);
+  const float r = expf(m - mn), w = expf(fmaf(x, inv_sqrt_d, -mn));  // (m = -inf at the first edge: r = 0)
+  s = fmaf(s, r, w);
+  acc.x = fmaf(acc.x, r, w * vv.x);
+  acc.y = fmaf(acc.y, r, w * vv.y);
+  acc.z = fmaf(acc.z, r, w * vv.z);
+  acc.w = fmaf(acc.w, r, w * vv.w);
+  m = mn;
+}
+
 // HGT: online softmax over the in-edges of row i (all edge types), dot-product logits.  HD = heads * dim floats per
 // row, processed in passes of 256 floats (64 lanes x float4) when HD > 256 is not needed: HD <= 256 * PASSES.
 template <int PASSES>
@@ -57,18 +79,9 @@ __global__ __launch_bounds__(256) void hgt_aggregate_kernel(const float* __restr
       const bool in = c < hd;
       const float4 kv = in ? *(const float4*)(k + j * hd + c) : make_float4(0, 0, 0, 0);
       const float4 vv = in ? *(const float4*)(v + j * hd + c) : make_float4(0, 0, 0, 0);
-      float d = qv[p].x * kv.x + qv[p].y * kv.y + qv[p].z * kv.z + qv[p].w * kv.w;
-      d = head_sum(d, lph);
+      const float d = head_sum(hgt_dot(qv[p], kv), lph);
       const int h = in ? c / dim : 0;
-      const float logit = d * (p_rel ? p_rel[t * heads + h] : 1.f) * inv_sqrt_d;
-      const float mn = fmaxf(m[p], logit);
-      const float r = expf(m[p] - mn), w = expf(logit - mn);  // (m = -inf at the first edge: r = 0)
-      s[p] = s[p] * r + w;
-      acc[p].x = acc[p].x * r + w * vv.x;
-      acc[p].y = acc[p].y * r + w * vv.y;
-      acc[p].z = acc[p].z * r + w * vv.z;
-      acc[p].w = acc[p].w * r + w * vv.w;
-      m[p] = mn;
+      hgt_fold(d, p_rel ? p_rel[t * heads + h] : 1.f, inv_sqrt_d, vv, m[p], s[p], acc[p]);
     }
   }
 #pragma unroll
@@ -117,18 +130,9 @@ __global__ __launch_bounds__(256) void hgt_aggregate_packed_kernel(const float* 
   int32_t e = row_ok ? rowptr[i] : 0;
   const int32_t e1 = row_ok ? rowptr[i + 1] : 0;
   auto fold = [&](bool on, const float4& kv, const float4& vv, int t) {
-    float d = qv.x * kv.x + qv.y * kv.y + qv.z * kv.z + qv.w * kv.w;
-    d = head_sum(d, lph);  // (every lane takes part: the sums run on DPP row operations)
+    const float d = head_sum(hgt_dot(qv, kv), lph);  // (every lane takes part: the sums run on DPP row operations)
     if (!on) return;
-    const float logit = d * (p_rel ? p_rel[t * heads + h] : 1.f) * inv_sqrt_d;
-    const float mn = fmaxf(m, logit);
-    const float r = expf(m - mn), w = expf(logit - mn);
-    s = s * r + w;
-    acc.x = acc.x * r + w * vv.x;
-    acc.y = acc.y * r + w * vv.y;
-    acc.z = acc.z * r + w * vv.z;
-    acc.w = acc.w * r + w * vv.w;
-    m = mn;
+    hgt_fold(d, p_rel ? p_rel[t * heads + h] : 1.f, inv_sqrt_d, vv, m, s, acc);
   };
   // a chunk of up to G edges of the row at a time: their source rows and types are fetched by the group's lanes in one
   // coalesced load each (not one dependent load per edge), then four edges' k / v rows are in flight per step

@@ -1050,12 +1050,14 @@ class HipEngine:
         return dw, db
 
     # ---- heterogeneous encoders (csrc/hetero.hip) ------------------------------------------------
-    def hgt_aggregate(self, q, k, v, heads: int, dim: int, rowptr, col, etype, p_rel, n_dst: int, out) -> None:
+    def hgt_aggregate(self, q, k, v, heads: int, dim: int, rowptr, col, etype, p_rel, n_dst: int, out,
+                      gelu: bool = False) -> None:
+        """gelu: the layer's exact-erf GELU in the reduce's epilogue (gigl_hgt_aggregate_act)"""
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         for t in (q, k, v, out):
             assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32
-        check(self._lib.gigl_hgt_aggregate(self._ctx, p(q), p(k), p(v), heads, dim, p(rowptr), p(col), p(etype),
-                                           p(p_rel), n_dst, p(out)), self._ctx)
+        check(self._lib.gigl_hgt_aggregate_act(self._ctx, p(q), p(k), p(v), heads, dim, p(rowptr), p(col), p(etype),
+                                               p(p_rel), n_dst, 1 if gelu else 0, p(out)), self._ctx)
 
     def hgt_aggregate_backward(self, q, k, v, heads: int, dim: int, rowptr, col, etype, p_rel, n_dst: int, out, dout):
         """-> (dq, dk, dv, dp_rel): gigl_hgt_aggregate_backward"""
