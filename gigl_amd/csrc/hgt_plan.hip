@@ -23,6 +23,7 @@
 // Per batch (4,096 roots, DBLP-shaped graph): ~45 kernel launches of the plan + 30 of the layers; bound by the typed
 // aggregate (HBM: two source rows per edge) and launch latency of the small sorts, not by the host.
 #include "common.h"
+#include "step_parts.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -54,8 +55,7 @@ struct gigl_hgt_infer {
   int32_t fetched_b[2] = {0, 0};
   hipEvent_t ev_graph[2] = {nullptr, nullptr};   // GRAPH part of the workspace done (side stream)
   hipEvent_t ev_layers[2] = {nullptr, nullptr};  // LAYERS part done with the workspace (caller's stream)
-  hipGraphExec_t exec_graph[2] = {nullptr, nullptr}, exec_layers[2] = {nullptr, nullptr};
-  bool warm_graph[2] = {false, false}, warm_layers[2] = {false, false};
+  PartGraph part_graph[2], part_layers[2];  // the captured parts per workspace (gigl_run_part)
   bool use_graph = true;
   int32_t cap_b = -1;
   uint64_t cap_arena_gen = 0, cap_side_gen = 0;
@@ -311,49 +311,10 @@ int32_t hgt_layers_part(gigl_hgt_infer* p, int k, int32_t b) {
   return GIGL_OK;
 }
 
-// run a part on `c`'s stream: eagerly the first time (workspace growth, table builds and kernel attributes cannot happen
-// inside a capture), captured the second, replayed from then on
-template <typename F>
-int32_t hgt_run_part(gigl_hgt_infer* p, gigl_ctx* c, hipGraphExec_t* exec, bool* warm, bool graph_ok, F body) {
-  hipStream_t st = c->stream;
-  if (!graph_ok) return body();
-  if (!*exec && !*warm) {
-    const int32_t rc = body();
-    if (rc != GIGL_OK) return rc;
-    *warm = true;
-    return GIGL_OK;
-  }
-  if (!*exec) {
-    hipGraph_t graph = nullptr;
-    int32_t rc = GIGL_OK;
-    hipError_t err = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-    if (err == hipSuccess) {
-      rc = body();
-      const hipError_t e2 = hipStreamEndCapture(st, &graph);
-      if (rc == GIGL_OK && e2 != hipSuccess) err = e2;
-    }
-    if (rc == GIGL_OK && err == hipSuccess) err = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
-    if (graph) hipGraphDestroy(graph);
-    if (rc != GIGL_OK) return rc;
-    if (err != hipSuccess) {
-      *exec = nullptr;
-      return gigl_fail(p->ctx, GIGL_E_HIP, "capturing a part of the typed inference step failed: %s", hipGetErrorString(err));
-    }
-  }
-  GIGL_HIP_CHECK(p->ctx, hipGraphLaunch(*exec, st));
-  return GIGL_OK;
-}
-
 void hgt_drop_graphs(gigl_hgt_infer* p, bool graph_parts, bool layer_parts) {
   for (int k = 0; k < 2; ++k) {
-    if (graph_parts && p->exec_graph[k]) {
-      hipGraphExecDestroy(p->exec_graph[k]);
-      p->exec_graph[k] = nullptr;
-    }
-    if (layer_parts && p->exec_layers[k]) {
-      hipGraphExecDestroy(p->exec_layers[k]);
-      p->exec_layers[k] = nullptr;
-    }
+    if (graph_parts) p->part_graph[k].drop();
+    if (layer_parts) p->part_layers[k].drop();
   }
 }
 
@@ -365,7 +326,7 @@ int32_t hgt_issue_graph(gigl_hgt_infer* p, int k, const uint32_t* roots, int32_t
   GIGL_HIP_CHECK(p->ctx, hipEventRecord(p->ev_layers[k], p->ctx->stream));
   GIGL_HIP_CHECK(p->ctx, hipStreamWaitEvent(sc->stream, p->ev_layers[k], 0));
   hipLaunchKernelGGL(hgt_copy_u32_kernel, grid_of(b), dim3(TB), 0, sc->stream, roots, (int64_t)b, p->roots[k]);
-  const int32_t rc = hgt_run_part(p, sc, &p->exec_graph[k], &p->warm_graph[k], graph_ok, [&] { return hgt_graph_part(p, k, b); });
+  const int32_t rc = gigl_run_part(p->ctx, sc, &p->part_graph[k], graph_ok, "typed inference step", [&] { return hgt_graph_part(p, k, b); });
   if (rc != GIGL_OK) return rc;
   GIGL_HIP_CHECK(p->ctx, hipEventRecord(p->ev_graph[k], sc->stream));
   p->fetched[k] = roots;
@@ -536,11 +497,11 @@ int32_t gigl_hgt_infer_run(gigl_hgt_infer* p, const uint32_t* roots, int32_t b, 
   // graphs are captured for ONE batch size (the job's; a short last batch runs eagerly), off while the ctx's timers are on
   const bool timers = ctx->prof_mask != 0;
   if (p->cap_b < 0) p->cap_b = b;
-  if ((p->exec_graph[0] || p->exec_graph[1]) && p->cap_side_gen != p->side->arena_gen) {
+  if ((p->part_graph[0].exec || p->part_graph[1].exec) && p->cap_side_gen != p->side->arena_gen) {
     GIGL_HIP_CHECK(ctx, hipStreamSynchronize(p->side->stream));
     hgt_drop_graphs(p, true, false);
   }
-  if ((p->exec_layers[0] || p->exec_layers[1]) && p->cap_arena_gen != ctx->arena_gen) {
+  if ((p->part_layers[0].exec || p->part_layers[1].exec) && p->cap_arena_gen != ctx->arena_gen) {
     GIGL_HIP_CHECK(ctx, hipStreamSynchronize(st));
     hgt_drop_graphs(p, false, true);
   }
@@ -558,8 +519,7 @@ int32_t gigl_hgt_infer_run(gigl_hgt_infer* p, const uint32_t* roots, int32_t b, 
   p->cap_side_gen = p->side->arena_gen;
   GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, p->ev_graph[k], 0));
   // (the legacy default stream cannot be captured: the layers then run eagerly, the graph part still replays)
-  rc = hgt_run_part(p, ctx, &p->exec_layers[k], &p->warm_layers[k], graph_ok(b) && st != nullptr,
-                    [&] { return hgt_layers_part(p, k, b); });
+  rc = gigl_run_part(ctx, ctx, &p->part_layers[k], graph_ok(b), "typed inference step", [&] { return hgt_layers_part(p, k, b); });
   if (rc != GIGL_OK) return rc;
   p->cap_arena_gen = ctx->arena_gen;
   GIGL_HIP_CHECK(ctx, hipEventRecord(p->ev_layers[k], st));

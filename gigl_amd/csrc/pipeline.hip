@@ -10,11 +10,11 @@
 //       (.../node_classification_modeling_task_spec.py:176-187),
 //   fed by process_raw_pyg_samples_and_collate_fn (rooted_node_neighborhood_data_loader.py:161-241).
 #include "common.h"
+#include "step_parts.h"
 #include "wave_reduce.h"
 
 #include <algorithm>
 #include <cmath>
-#include <functional>
 #include <new>
 #include <vector>
 
@@ -1645,6 +1645,125 @@ int32_t sage_moments_adopt(gigl_ctx* ctx, const SageTrainShared& dst, const Sage
   return GIGL_OK;
 }
 
+// ---- the workspace ring of a training plan, written once for the node-classification and the link-prediction plans.
+// A step is two parts (see above): the GRAPH part of a batch runs on the side stream of one of the ring's slots, into that
+// slot's tree / union workspaces; the LAYERS part that reads them runs on the caller's stream.  A batch ANNOUNCED ahead is
+// issued into a later slot right away and recognised when its step comes by the ADDRESS of its roots (include/gigl_hip.h:
+// CONTRACT of an announced batch).  Both parts go through gigl_run_part: eager once, captured, replayed.
+extern "C++" {  // (a member template: this file's definitions sit in one extern "C" block)
+struct PlanRing {
+  enum Family { TRAIN = 0, EVAL = 1 };  // whose graph part: a training step's, gigl_nablp_train_plan_eval's
+  struct Slot {
+    gigl_ctx* side = nullptr;                      // private ctx with a stream of its own: the graph part's launches and arena
+    gigl_sage_plan* base[2] = {nullptr, nullptr};  // tree / union workspaces of the plan's root sets (their layer buffers stay unused)
+    hipEvent_t ev_graph = nullptr;                 // end of the graph part last issued for the slot (its side stream)
+    hipEvent_t ev_layers = nullptr;                // end of the layers part that last read it (the caller's stream)
+    PartGraph graph[2], layers;                    // graph part per family (an evaluation's seed / mode need not be the steps')
+    bool fetched = false;                          // the slot holds the graph of an announced batch ...
+    const uint32_t* key[2] = {nullptr, nullptr};   // ... announced as these buffers (the step must name the same ones)
+  } slot[TRAIN_WS];
+  gigl_ctx* ctx = nullptr;  // the caller's: HIP's failures are reported on it
+  int n = 0, n_base = 0;    // slots in use (2 or 3), root sets per slot
+  int cur = 0;              // slot of the next step
+  hipEvent_t ev_now = nullptr;  // "the caller's stream, now": the roots a graph part copies were written before it
+  int32_t seed[2] = {0, 0}, mode[2] = {-1, -1};  // what each family's captured graph parts were captured with
+
+  // per slot a side ctx, a base plan per root set (nb[i] roots) and its events
+  int32_t create(gigl_ctx* caller, int slots, int root_sets, const int32_t* nb, gigl_graph* graph, gigl_feat* feat,
+                 const int32_t* fanouts, int32_t hops, const int32_t* dims, float* const* w, float* const* bias, int32_t act_last) {
+    ctx = caller;
+    n = slots;
+    n_base = root_sets;
+    int32_t rc = GIGL_OK;
+    for (int k = 0; k < n && rc == GIGL_OK; ++k) {
+      Slot& s = slot[k];
+      rc = gigl_ctx_create(ctx->device, &s.side);
+      if (rc != GIGL_OK) break;
+      s.side->wide = ctx->wide;
+      for (int i = 0; i < n_base && rc == GIGL_OK; ++i) {
+        rc = plan_create(s.side, graph, feat, nb[i], fanouts, hops, dims, (const float* const*)w, (const float* const*)bias,
+                         act_last, false, &s.base[i]);
+        if (rc != GIGL_OK) gigl_fail(ctx, rc, "%s", gigl_last_error(s.side));
+      }
+      if (rc == GIGL_OK && (hipEventCreateWithFlags(&s.ev_graph, hipEventDisableTiming) != hipSuccess ||
+                            hipEventCreateWithFlags(&s.ev_layers, hipEventDisableTiming) != hipSuccess))
+        rc = GIGL_E_HIP;
+    }
+    if (rc == GIGL_OK && hipEventCreateWithFlags(&ev_now, hipEventDisableTiming) != hipSuccess) rc = GIGL_E_HIP;
+    return rc;
+  }
+
+  // the graph part of slot k for these roots (count[i] of root set i; 0: the set is absent), on its side stream; ev_graph
+  // marks its end.  A training step's is remembered under the roots' addresses until consume() or reseed()
+  template <typename Body>
+  int32_t issue_graph_part(int k, Family fam, const uint32_t* const* roots, const size_t* count, bool capture_ok, Body&& body) {
+    Slot& s = slot[k];
+    hipStream_t ss = s.side->stream;
+    // the workspace is free once the layers part that last read it is done; the roots were written on the caller's stream
+    GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(ss, s.ev_layers, 0));
+    GIGL_HIP_CHECK(ctx, hipEventRecord(ev_now, ctx->stream));
+    GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(ss, ev_now, 0));
+    for (int i = 0; i < n_base; ++i)
+      if (count[i])
+        GIGL_HIP_CHECK(ctx, hipMemcpyAsync(s.base[i]->roots_buf, roots[i], count[i] * 4, hipMemcpyDeviceToDevice, ss));
+      else
+        gigl_fill_u32(ss, s.base[i]->roots_buf, GIGL_INVALID, 1);
+    const int32_t rc = gigl_run_part(s.side, s.side, &s.graph[fam], capture_ok, "training step", body);
+    if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(s.side));
+    GIGL_HIP_CHECK(ctx, hipEventRecord(s.ev_graph, ss));
+    if (fam == EVAL) return GIGL_OK;  // (an evaluation batch is consumed by the call that samples it: nothing to recognise later)
+    s.fetched = true;
+    s.key[0] = roots[0];
+    s.key[1] = n_base > 1 ? roots[1] : nullptr;
+    return GIGL_OK;
+  }
+  bool holds(int k, const uint32_t* r0, const uint32_t* r1 = nullptr) const {
+    return slot[k].fetched && slot[k].key[0] == r0 && slot[k].key[1] == r1;
+  }
+  void consume(int k) { slot[k].fetched = false; }
+
+  // seed and mode are baked into a family's captured graph parts: a change drops every slot's.  What was announced was
+  // sampled under the training steps' old seed: a change of theirs forgets it (the step samples again)
+  void reseed(Family fam, int32_t sampling_seed, int32_t sampling_mode) {
+    if (seed[fam] == sampling_seed && mode[fam] == sampling_mode) return;
+    for (Slot& s : slot) {
+      if (s.graph[fam].exec) hipStreamSynchronize(s.side->stream);
+      s.graph[fam].drop();
+      if (fam == TRAIN) s.fetched = false;
+    }
+    seed[fam] = sampling_seed;
+    mode[fam] = sampling_mode;
+  }
+
+  // destruction in two steps, around the plan's own buffers (the caller's stream is synchronised already): the side
+  // streams drained, every captured graph gone before the ctx whose stream it was captured on, base plans before their ctx
+  void release() {
+    for (Slot& s : slot)
+      if (s.side) hipStreamSynchronize(s.side->stream);
+    for (Slot& s : slot) {
+      s.graph[TRAIN].drop();
+      s.layers.drop();
+      s.graph[EVAL].drop();
+      if (s.ev_graph) hipEventDestroy(s.ev_graph);
+      if (s.ev_layers) hipEventDestroy(s.ev_layers);
+      for (gigl_sage_plan* b : s.base)
+        if (b) gigl_sage_plan_destroy(b);
+    }
+    if (ev_now) hipEventDestroy(ev_now);
+  }
+  void destroy_ctxs() {
+    for (Slot& s : slot)
+      if (s.side) gigl_ctx_destroy(s.side);
+  }
+};
+}  // extern "C++"
+
+// (A/B knob of the training plans: GIGL_TRAIN_PLAN_EAGER=1 both parts eager, =graph / =layers only that part)
+bool train_part_captures(int part) {
+  static const char* ev = getenv("GIGL_TRAIN_PLAN_EAGER");
+  return !(ev && (ev[0] == '1' || (ev[0] == 'g' && part == 0) || (ev[0] == 'l' && part == 1)));
+}
+
 }  // namespace
 
 struct gigl_sage_train_plan : SageTrainShared {
@@ -1652,17 +1771,10 @@ struct gigl_sage_train_plan : SageTrainShared {
   // two ctxs of the plan's own, for their ARENAS: scratch addresses are baked into the captured launches, and another
   // plan on the caller's ctx (the inference plan of an evaluation pass between epochs) may grow — reallocate — that arena
   gigl_ctx* lctx = nullptr;        // layers part (bound to the caller's stream at every step)
-  gigl_ctx* side[TRAIN_WS] = {nullptr};  // graph part: sample + union — a ctx + stream per workspace
-  gigl_sage_plan* base[TRAIN_WS] = {nullptr};  // tree / union workspaces (each on its own side ctx / stream: two graph
-                                               // parts — of the next batch and of the one after — can be in flight)
-  int32_t cur = 0;                 // workspace of the next step
-  bool fetched[TRAIN_WS] = {false};  // the workspace holds the graph of a prefetched batch
-  const uint32_t* fetched_roots[TRAIN_WS] = {nullptr};  // ... announced as these roots (the step must name the same ones)
-  hipEvent_t ev_graph[TRAIN_WS] = {nullptr};   // graph part of the workspace done (recorded on its side stream)
-  // layers part that read the workspace done (recorded on the caller's stream); [2]: the caller's stream as it stands
-  // when a graph part is issued (the roots it is handed were written there)
-  hipEvent_t ev_layers[TRAIN_WS + 1] = {nullptr};
-  SageTrainEnc enc;                       // the step's one encode (over the workspace base[k] the step reads)
+  // TRAIN_WS workspaces, one root set each (each on its own side ctx / stream: two graph parts — of the next batch and of
+  // the one after — can be in flight)
+  PlanRing ring;
+  SageTrainEnc enc;                       // the step's one encode (over the workspace ring.slot[k].base[0] the step reads)
   int32_t* tlists[TRAIN_WS][GIGL_MAX_HOPS] = {{nullptr}};  // its transposed lists per workspace and layer >= 1, built by the graph part
   float* da = nullptr;                    // [max rows_cap[l >= 1]][2 max dims]: gradient of a layer's operand
   float** loss_slot = nullptr;            // where the caller wants the step's loss (set by train_stage_kernel)
@@ -1673,17 +1785,13 @@ struct gigl_sage_train_plan : SageTrainShared {
   float* loss_rows = nullptr;
   float* loss = nullptr;
   std::vector<void*> owned;
-  // hipGraph replay, per workspace and part
-  hipGraphExec_t exec_graph[TRAIN_WS] = {nullptr}, exec_layers[TRAIN_WS] = {nullptr};
-  bool warm_graph[TRAIN_WS] = {false}, warm_layers = false;  // one eager run of the part has sized arenas / built tables
-  int32_t cap_seed = 0, cap_mode = -1;
 };
 
 namespace {
 
 // everything after the graph part, over workspace k, on lctx's stream (the caller's); train_stage_kernel ran ahead of it
 int32_t train_enqueue_layers(gigl_sage_train_plan* t, int k) {
-  gigl_sage_plan* p = t->base[k];
+  gigl_sage_plan* p = t->ring.slot[k].base[0];
   gigl_ctx* ctx = t->lctx;
   const int L = t->L;
   hipStream_t st = ctx->stream;
@@ -1712,73 +1820,11 @@ int32_t train_enqueue_layers(gigl_sage_train_plan* t, int k) {
   return GIGL_OK;
 }
 
-// run `body` on ctx->stream: eagerly the first time (arena sizing, table builds and kernel attributes cannot happen inside
-// a capture), captured the second, replayed from then on
-int32_t train_run_part(gigl_ctx* ctx, hipGraphExec_t* exec, bool* warm, const std::function<int32_t()>& body, int part) {
-  // (A/B knob: GIGL_TRAIN_PLAN_EAGER=1 both parts eager, =graph / =layers only that part)
-  static const char* ev = getenv("GIGL_TRAIN_PLAN_EAGER");
-  const bool eager = ev && (ev[0] == '1' || (ev[0] == 'g' && part == 0) || (ev[0] == 'l' && part == 1));
-  hipStream_t st = ctx->stream;
-  if (eager || st == nullptr) return body();  // (the legacy default stream cannot be captured)
-  if (!*exec && !*warm) {
-    const int32_t rc = body();
-    if (rc != GIGL_OK) return rc;
-    GIGL_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    *warm = true;
-    return GIGL_OK;
-  }
-  if (!*exec) {
-    hipGraph_t graph = nullptr;
-    int32_t rc = GIGL_OK;
-    hipError_t err = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-    if (err == hipSuccess) {
-      rc = body();
-      const hipError_t e2 = hipStreamEndCapture(st, &graph);
-      if (rc == GIGL_OK && e2 != hipSuccess) err = e2;
-    }
-    if (rc == GIGL_OK && err == hipSuccess) err = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
-    if (graph) hipGraphDestroy(graph);
-    if (rc != GIGL_OK) return rc;
-    if (err != hipSuccess) {
-      *exec = nullptr;
-      return gigl_fail(ctx, GIGL_E_HIP, "capturing a part of the training step failed: %s", hipGetErrorString(err));
-    }
-  }
-  GIGL_HIP_CHECK(ctx, hipGraphLaunch(*exec, st));
-  return GIGL_OK;
-}
-
 // a plan's private ctx (own arena) follows the caller's stream: every launch of the step goes there
 static int32_t train_bind_stream(gigl_ctx* ctx, gigl_ctx* lctx) {
   if (lctx->stream == ctx->stream && !lctx->own_stream) return GIGL_OK;
   const int32_t rs = gigl_ctx_set_stream(lctx, ctx->stream);
   return rs == GIGL_OK ? GIGL_OK : gigl_fail(ctx, rs, "%s", gigl_last_error(lctx));
-}
-
-// the graph part of workspace k for `roots`, on the side stream; ev_graph[k] marks its end
-int32_t train_graph_part(gigl_sage_train_plan* t, int k, const uint32_t* roots, int32_t sampling_seed, int32_t mode) {
-  gigl_ctx* sc = t->side[k];
-  if (t->cap_seed != sampling_seed || t->cap_mode != mode) {  // seed and mode are baked into the captured launches
-    GIGL_HIP_CHECK(sc, hipStreamSynchronize(sc->stream));
-    for (int i = 0; i < TRAIN_WS; ++i)
-      if (t->exec_graph[i]) {
-        if (t->side[i]) hipStreamSynchronize(t->side[i]->stream);
-        hipGraphExecDestroy(t->exec_graph[i]);
-        t->exec_graph[i] = nullptr;
-      }
-    t->cap_seed = sampling_seed;
-    t->cap_mode = mode;
-  }
-  // the workspace is free once the layers part that last read it is done; `roots` was written on the caller's stream
-  if (t->ev_layers[k]) GIGL_HIP_CHECK(sc, hipStreamWaitEvent(sc->stream, t->ev_layers[k], 0));
-  GIGL_HIP_CHECK(sc, hipEventRecord(t->ev_layers[TRAIN_WS], t->ctx->stream));
-  GIGL_HIP_CHECK(sc, hipStreamWaitEvent(sc->stream, t->ev_layers[TRAIN_WS], 0));
-  GIGL_HIP_CHECK(sc, hipMemcpyAsync(t->base[k]->roots_buf, roots, (size_t)t->enc.b * 4, hipMemcpyDeviceToDevice, sc->stream));
-  const int32_t rc = train_run_part(sc, &t->exec_graph[k], &t->warm_graph[k],
-                                    [&]() { return sage_enqueue_graph(*t, t->enc, t->base[k], t->tlists[k], sampling_seed, mode); }, 0);
-  if (rc != GIGL_OK) return rc;
-  GIGL_HIP_CHECK(sc, hipEventRecord(t->ev_graph[k], sc->stream));
-  return GIGL_OK;
 }
 
 }  // namespace
@@ -1789,19 +1835,9 @@ int32_t gigl_sage_train_plan_destroy(gigl_sage_train_plan* t) {
     hipSetDevice(t->ctx->device);
     hipStreamSynchronize(t->ctx->stream);
   }
-  for (int k = 0; k < TRAIN_WS; ++k)
-    if (t->side[k]) hipStreamSynchronize(t->side[k]->stream);
-  for (int k = 0; k < TRAIN_WS; ++k) {
-    if (t->exec_graph[k]) hipGraphExecDestroy(t->exec_graph[k]);
-    if (t->exec_layers[k]) hipGraphExecDestroy(t->exec_layers[k]);
-    if (t->ev_graph[k]) hipEventDestroy(t->ev_graph[k]);
-    if (t->base[k]) gigl_sage_plan_destroy(t->base[k]);
-  }
-  for (int k = 0; k < TRAIN_WS + 1; ++k)
-    if (t->ev_layers[k]) hipEventDestroy(t->ev_layers[k]);
+  t->ring.release();
   for (void* q : t->owned) hipFree(q);
-  for (int k = 0; k < TRAIN_WS; ++k)
-    if (t->side[k]) gigl_ctx_destroy(t->side[k]);
+  t->ring.destroy_ctxs();
   if (t->lctx) {
     gigl_ctx_set_stream(t->lctx, nullptr);  // (the stream is the caller's)
     gigl_ctx_destroy(t->lctx);
@@ -1823,17 +1859,7 @@ int32_t gigl_sage_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat*
   if (!t) return gigl_fail(ctx, GIGL_E_OOM, "host OOM");
   t->ctx = ctx;
   int32_t rc = gigl_ctx_create(ctx->device, &t->lctx);
-  for (int k = 0; k < TRAIN_WS && rc == GIGL_OK; ++k) {
-    rc = gigl_ctx_create(ctx->device, &t->side[k]);
-    if (rc != GIGL_OK) break;
-    t->side[k]->wide = ctx->wide;
-    rc = plan_create(t->side[k], graph, feat, b, fanouts, hops, dims, (const float* const*)w, (const float* const*)bias,
-                     act_last, false, &t->base[k]);
-    if (rc != GIGL_OK) gigl_fail(ctx, rc, "%s", gigl_last_error(t->side[k]));
-    if (rc == GIGL_OK && hipEventCreateWithFlags(&t->ev_graph[k], hipEventDisableTiming) != hipSuccess) rc = GIGL_E_HIP;
-  }
-  for (int k = 0; k < TRAIN_WS + 1 && rc == GIGL_OK; ++k)
-    if (hipEventCreateWithFlags(&t->ev_layers[k], hipEventDisableTiming) != hipSuccess) rc = GIGL_E_HIP;
+  if (rc == GIGL_OK) rc = t->ring.create(ctx, TRAIN_WS, 1, &b, graph, feat, fanouts, hops, dims, w, bias, act_last);
   if (rc != GIGL_OK) {
     gigl_sage_train_plan_destroy(t);
     return rc;
@@ -1855,7 +1881,7 @@ int32_t gigl_sage_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat*
   t->zero_base = z;
   t->zero_bytes = zero_floats * 4;
   if (z) sage_enc_carve(*t, t->enc, false, z);
-  for (int k = 0; k < TRAIN_WS; ++k) ok = sage_tlists_alloc(*t, t->enc, t->owned, t->base[k]->un.cap_edges, t->tlists[k]) && ok;
+  for (int k = 0; k < TRAIN_WS; ++k) ok = sage_tlists_alloc(*t, t->enc, t->owned, t->ring.slot[k].base[0]->un.cap_edges, t->tlists[k]) && ok;
   t->da = (float*)alloc(da_floats * 4);
   t->labels_buf = (int64_t*)alloc((size_t)b * 8);
   t->n_valid_buf = (int32_t*)alloc(16);
@@ -1890,15 +1916,23 @@ int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* t, const uint32_t* root
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "the training plan needs duplicate-free trees (no with-replacement mode)");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const int k = t->cur;
+  PlanRing& ring = t->ring;
+  ring.reseed(PlanRing::TRAIN, sampling_seed, mode);
+  const int k = ring.cur;
+  auto graph_part = [&](int kk, const uint32_t* r) {
+    const size_t count = (size_t)t->enc.b;
+    return ring.issue_graph_part(kk, PlanRing::TRAIN, &r, &count, train_part_captures(0), [&, kk]() {
+      return sage_enqueue_graph(*t, t->enc, ring.slot[kk].base[0], t->tlists[kk], sampling_seed, mode);
+    });
+  };
   // (a prefetched workspace belongs to the roots it was announced with: an epoch cut short, a reshuffle or an evaluation
   // between two steps hands in other roots — the graph part is then issued again instead of training these labels
   // against the old batch's graph; as gigl_hgt_infer_run's guard)
-  if (!t->fetched[k] || t->fetched_roots[k] != roots) {  // the graph part of THIS batch now (the layers wait for it)
-    const int32_t rc = train_graph_part(t, k, roots, sampling_seed, mode);
-    if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->side[k]));
+  if (!ring.holds(k, roots)) {  // the graph part of THIS batch now (the layers wait for it)
+    const int32_t rc = graph_part(k, roots);
+    if (rc != GIGL_OK) return rc;
   }
-  t->fetched[k] = false;
+  ring.consume(k);
   // the NEXT batch's graph part goes to the side stream BEFORE this batch's layers are enqueued: it waits for what the
   // caller's stream holds now (roots_next was written there; the layers that last read the other workspace), not for
   // the layers about to be enqueued
@@ -1907,11 +1941,9 @@ int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* t, const uint32_t* root
   const uint32_t* ahead[2] = {roots_next, roots_next ? roots_next2 : nullptr};
   for (int d = 0; d < 2; ++d) {
     const int kk = (k + 1 + d) % TRAIN_WS;
-    if (!ahead[d] || (t->fetched[kk] && t->fetched_roots[kk] == ahead[d]) || kk == k) continue;
-    const int32_t rc = train_graph_part(t, kk, ahead[d], sampling_seed, mode);
-    if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->side[kk]));
-    t->fetched[kk] = true;
-    t->fetched_roots[kk] = ahead[d];
+    if (!ahead[d] || ring.holds(kk, ahead[d]) || kk == k) continue;
+    const int32_t rc = graph_part(kk, ahead[d]);
+    if (rc != GIGL_OK) return rc;
   }
   // the step's inputs go into the static buffers the (captured) launches read — labels, the number of real roots, where the
   // caller wants the loss (the loss kernel writes it there itself) — in the launch that also clears the dh block and lays out W_l^T
@@ -1932,13 +1964,18 @@ int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* t, const uint32_t* root
   hipLaunchKernelGGL(train_stage_kernel, dim3((unsigned)blocks), dim3(256), 0, st, labels, n_valid, t->labels_buf, t->n_valid_buf,
                      t->loss_slot, loss_out, pa);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
-  GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, t->ev_graph[k], 0));
+  GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, ring.slot[k].ev_graph, 0));
   const int32_t rs = train_bind_stream(ctx, t->lctx);
   if (rs != GIGL_OK) return rs;
-  const int32_t rc = train_run_part(t->lctx, &t->exec_layers[k], &t->warm_layers, [&]() { return train_enqueue_layers(t, k); }, 1);
+  PartGraph& layers = ring.slot[k].layers;
+  const int32_t rc = gigl_run_part(t->lctx, t->lctx, &layers, train_part_captures(1), "training step",
+                                   [&]() { return train_enqueue_layers(t, k); });
   if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
-  GIGL_HIP_CHECK(ctx, hipEventRecord(t->ev_layers[k], st));
-  t->cur = (k + 1) % TRAIN_WS;
+  // (the layers' scratch is the plan's, not a workspace's: one eager run has sized it for every slot's capture)
+  if (layers.warm)
+    for (PlanRing::Slot& s : ring.slot) s.layers.warm = true;
+  GIGL_HIP_CHECK(ctx, hipEventRecord(ring.slot[k].ev_layers, st));
+  ring.cur = (k + 1) % TRAIN_WS;
   return GIGL_OK;
 }
 
@@ -2056,24 +2093,11 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
   float lr_warm = 0.f;     // gigl_nablp_train_plan_set_constant_lr: lr * factor ...
   int32_t warm_iters = 0;  // ... for Adam's first warm_iters steps
   std::vector<void*> owned;
-  // Two workspaces of trees + union graphs (as gigl_sage_train_plan): the graph part of the NEXT step's roots (sample +
-  // union of both root sets: latency-bound launches) runs on a side stream beside this step's layers
+  // Two workspaces of trees + union graphs, two root sets each (0: main batch, 1: random negatives): the graph part of the
+  // NEXT step's roots (sample + union of both root sets: latency-bound launches) runs on a side stream beside this step's layers
   static constexpr int WS = 2;
-  struct Work {
-    gigl_ctx* side = nullptr;                    // private ctx with a stream of its own: the graph part's launches
-    gigl_sage_plan* base[2] = {nullptr, nullptr};  // 0: main batch, 1: random negatives
-    hipGraphExec_t exec_graph = nullptr, exec_layers = nullptr;
-    bool warm_graph = false, warm_layers = false;
-    hipEvent_t ev_graph = nullptr;   // end of the graph part last enqueued for this workspace
-    hipEvent_t ev_layers = nullptr;  // end of the layers part that last read it
-    int32_t* tlists[2][GIGL_MAX_HOPS] = {{nullptr}};  // transposed lists of layers >= 1 per encode (SAGE; built by the graph part)
-    const uint32_t *fetched_main = nullptr, *fetched_rn = nullptr;  // the caller's buffers its graph part ran for
-    bool fetched = false;
-    // gigl_nablp_train_plan_eval's graph part: a captured graph of its own (its seed / mode need not be the training steps')
-    hipGraphExec_t exec_graph_eval = nullptr;
-    bool warm_graph_eval = false;
-  } work[WS];
-  hipEvent_t ev_now = nullptr;  // "the caller's stream, now": the roots a graph part copies were written before it
+  PlanRing ring;
+  int32_t* tlists[WS][2][GIGL_MAX_HOPS] = {{{nullptr}}};  // transposed lists of layers >= 1 per workspace and encode (SAGE; built by the graph part)
   // (round 6; GIGL_LP_FORK=0 turns it off) the random negatives' encode — ~15 launches of a 512-root batch, all latency — runs
   // on a stream of its own beside the main batch's, forward and backward: forked after the step's shared preparation, joined
   // before the scores, forked again after the loss's backward, joined before Adam.  Its only shared scratch is `da`.
@@ -2085,9 +2109,6 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
   // 40-65 us matrix kernel between the chain's latency-bound ones
   gigl_ctx* wctx = nullptr;
   hipEvent_t ev_w = nullptr, ev_wjoin = nullptr;
-  int cur = 0;
-  int32_t cap_seed = 0, cap_mode = -1;
-  int32_t eval_seed = 0, eval_mode = -1;  // ... and what the evaluation's captured graph parts were captured with
   double* rank_part = nullptr;            // [b][2 + GIGL_LP_EVAL_MAX_KS]: the rank metrics' per-anchor values
 };
 
@@ -2400,7 +2421,7 @@ int32_t lp_forward(gigl_nablp_train_plan* t, int which) {
 int32_t lp_backward(gigl_nablp_train_plan* t, int which, int w) {
   const SageTrainEnc& e = t->enc[which];
   const bool alt = which == 1 && t->fork;
-  return sage_enc_backward(alt ? t->actx : t->lctx, *t, e, e.base, t->work[w].tlists[which], alt ? t->da2 : t->da,
+  return sage_enc_backward(alt ? t->actx : t->lctx, *t, e, e.base, t->tlists[w][which], alt ? t->da2 : t->da,
                            which == 0 && t->fork ? t->wctx : nullptr, t->ev_w);
 }
 
@@ -2413,7 +2434,7 @@ int32_t gat_lp_finish(gigl_nablp_train_plan* t);
 // sample + union of both root sets of workspace w, on its side stream (bwd_gather is a SAGE encoder's: no lists for the GAT kind)
 int32_t lp_enqueue_graph(gigl_nablp_train_plan* t, int w, int32_t sampling_seed, int32_t mode) {
   for (int k = 0; k < 2; ++k) {
-    const int32_t rc = sage_enqueue_graph(*t, t->enc[k], t->work[w].base[k], t->work[w].tlists[k], sampling_seed, mode);
+    const int32_t rc = sage_enqueue_graph(*t, t->enc[k], t->ring.slot[w].base[k], t->tlists[w][k], sampling_seed, mode);
     if (rc != GIGL_OK) return rc;
   }
   return GIGL_OK;
@@ -2426,7 +2447,7 @@ int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w) {
   hipStream_t st = ctx->stream;
   const int L = t->L, d = t->dims[L], Q = t->b * t->P, Cn = Q + t->n_rn;
   int32_t rc = GIGL_OK;
-  for (int k = 0; k < 2; ++k) t->enc[k].base = t->work[w].base[k];
+  for (int k = 0; k < 2; ++k) t->enc[k].base = t->ring.slot[w].base[k];
   gigl_fill_u32(st, t->zero_base, 0u, (int64_t)(t->zero_bytes / 4));
   if (t->kind == 1) {
     rc = gat_lp_begin(t);
@@ -2522,30 +2543,16 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
 
 // ---- what the two link-prediction plans' creation shares (t->ctx, b, P, n_rn are set)
 
-// the layers' ctx and, per workspace, a side ctx, the two root sets' tree / union workspaces (base plans: their own layer
-// buffers stay unused) and its events; "the caller's stream, now"
+// the layers' ctx and the ring: per workspace the two root sets' tree / union workspaces
 int32_t lp_create_workspaces(gigl_nablp_train_plan* t, gigl_graph* graph, gigl_feat* feat, const int32_t* fanouts, int32_t hops,
                              const int32_t* dims, float* const* w, float* const* bias, int32_t act_last) {
   gigl_ctx* ctx = t->ctx;
   int32_t rc = gigl_ctx_create(ctx->device, &t->lctx);
   const int32_t nb[2] = {t->b * (1 + t->P), t->n_rn > 0 ? t->n_rn : 1};
-  for (int wi = 0; wi < gigl_nablp_train_plan::WS && rc == GIGL_OK; ++wi) {
-    gigl_nablp_train_plan::Work& wk = t->work[wi];
-    rc = gigl_ctx_create(ctx->device, &wk.side);
-    if (rc == GIGL_OK) wk.side->wide = ctx->wide;
-    for (int k = 0; k < 2 && rc == GIGL_OK; ++k) {
-      t->enc[k].b = nb[k];
-      rc = plan_create(wk.side, graph, feat, nb[k], fanouts, hops, dims, (const float* const*)w, (const float* const*)bias,
-                       act_last, false, &wk.base[k]);
-      if (rc != GIGL_OK) gigl_fail(ctx, rc, "%s", gigl_last_error(wk.side));
-    }
-    if (rc == GIGL_OK && (hipEventCreateWithFlags(&wk.ev_graph, hipEventDisableTiming) != hipSuccess ||
-                          hipEventCreateWithFlags(&wk.ev_layers, hipEventDisableTiming) != hipSuccess))
-      rc = GIGL_E_HIP;
-  }
-  if (rc == GIGL_OK && hipEventCreateWithFlags(&t->ev_now, hipEventDisableTiming) != hipSuccess) rc = GIGL_E_HIP;
+  for (int k = 0; k < 2; ++k) t->enc[k].b = nb[k];
+  if (rc == GIGL_OK) rc = t->ring.create(ctx, gigl_nablp_train_plan::WS, 2, nb, graph, feat, fanouts, hops, dims, w, bias, act_last);
   if (rc == GIGL_OK)
-    for (int k = 0; k < 2; ++k) t->enc[k].base = t->work[0].base[k];
+    for (int k = 0; k < 2; ++k) t->enc[k].base = t->ring.slot[0].base[k];
   return rc;
 }
 
@@ -2637,18 +2644,7 @@ int32_t gigl_nablp_train_plan_destroy(gigl_nablp_train_plan* t) {
     hipSetDevice(t->ctx->device);
     hipStreamSynchronize(t->ctx->stream);
   }
-  for (auto& wk : t->work)
-    if (wk.side) hipStreamSynchronize(wk.side->stream);
-  for (auto& wk : t->work) {
-    if (wk.exec_graph) hipGraphExecDestroy(wk.exec_graph);
-    if (wk.exec_layers) hipGraphExecDestroy(wk.exec_layers);
-    if (wk.exec_graph_eval) hipGraphExecDestroy(wk.exec_graph_eval);
-    if (wk.ev_graph) hipEventDestroy(wk.ev_graph);
-    if (wk.ev_layers) hipEventDestroy(wk.ev_layers);
-    for (int k = 0; k < 2; ++k)
-      if (wk.base[k]) gigl_sage_plan_destroy(wk.base[k]);
-  }
-  if (t->ev_now) hipEventDestroy(t->ev_now);
+  t->ring.release();
   if (t->actx) hipStreamSynchronize(t->actx->stream);
   if (t->wctx) hipStreamSynchronize(t->wctx->stream);
   if (t->ev_w) hipEventDestroy(t->ev_w);
@@ -2658,8 +2654,7 @@ int32_t gigl_nablp_train_plan_destroy(gigl_nablp_train_plan* t) {
     if (t->ev_join[i]) hipEventDestroy(t->ev_join[i]);
   }
   for (void* q : t->owned) hipFree(q);
-  for (auto& wk : t->work)
-    if (wk.side) gigl_ctx_destroy(wk.side);
+  t->ring.destroy_ctxs();
   if (t->actx) gigl_ctx_destroy(t->actx);
   if (t->wctx) gigl_ctx_destroy(t->wctx);
   if (t->lctx) {
@@ -2699,8 +2694,9 @@ int32_t gigl_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat
   t->zero_base = z;
   t->zero_bytes = zero_floats * 4;
   for (int k = 0; k < 2 && z; ++k) z = sage_enc_carve(*t, t->enc[k], true, z);
-  for (auto& wk : t->work)
-    for (int k = 0; k < 2; ++k) ok = sage_tlists_alloc(*t, t->enc[k], t->owned, wk.base[k]->un.cap_edges, wk.tlists[k]) && ok;
+  for (int wi = 0; wi < gigl_nablp_train_plan::WS; ++wi)
+    for (int k = 0; k < 2; ++k)
+      ok = sage_tlists_alloc(*t, t->enc[k], t->owned, t->ring.slot[wi].base[k]->un.cap_edges, t->tlists[wi][k]) && ok;
   t->da = (float*)alloc(da_floats * 4);
   ok = ok && t->zero_base && t->da && lp_head_alloc(t, (size_t)dims[hops]);
   // (GIGL_LP_FORK=0 off: 1.18 -> 1.07 ms per step, bit-identical results.  The forked step's layers part is
@@ -2719,39 +2715,13 @@ int32_t gigl_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat
 }
 
 namespace {
-// the graph part of workspace w for these roots, on its side stream; work[w].ev_graph marks its end
-int32_t lp_graph_part(gigl_nablp_train_plan* t, int w, const uint32_t* main_roots, const uint32_t* rn_roots,
-                      int32_t sampling_seed, int32_t mode, bool eval = false) {
-  gigl_nablp_train_plan::Work& wk = t->work[w];
-  gigl_ctx* sc = wk.side;
-  // the workspace is free once the layers part that last read it is done; the roots were written on the caller's stream
-  GIGL_HIP_CHECK(sc, hipStreamWaitEvent(sc->stream, wk.ev_layers, 0));
-  GIGL_HIP_CHECK(sc, hipEventRecord(t->ev_now, t->ctx->stream));
-  GIGL_HIP_CHECK(sc, hipStreamWaitEvent(sc->stream, t->ev_now, 0));
-  GIGL_HIP_CHECK(sc, hipMemcpyAsync(wk.base[0]->roots_buf, main_roots, (size_t)t->enc[0].b * 4, hipMemcpyDeviceToDevice, sc->stream));
-  if (t->n_rn > 0)
-    GIGL_HIP_CHECK(sc, hipMemcpyAsync(wk.base[1]->roots_buf, rn_roots, (size_t)t->n_rn * 4, hipMemcpyDeviceToDevice, sc->stream));
-  else
-    gigl_fill_u32(sc->stream, wk.base[1]->roots_buf, GIGL_INVALID, 1);
-  const int32_t rc = train_run_part(sc, eval ? &wk.exec_graph_eval : &wk.exec_graph, eval ? &wk.warm_graph_eval : &wk.warm_graph,
-                                    [&]() { return lp_enqueue_graph(t, w, sampling_seed, mode); }, 0);
-  if (rc != GIGL_OK) return rc;
-  GIGL_HIP_CHECK(sc, hipEventRecord(wk.ev_graph, sc->stream));
-  if (eval) return GIGL_OK;  // (an evaluation batch is consumed by the call that samples it: nothing to recognise later)
-  wk.fetched_main = main_roots;
-  wk.fetched_rn = rn_roots;
-  wk.fetched = true;
-  return GIGL_OK;
-}
-
-// seed and mode are baked into the captured graph parts: drop every workspace's (the training steps' or the evaluation's)
-static void lp_drop_graph_parts(gigl_nablp_train_plan* t, hipGraphExec_t gigl_nablp_train_plan::Work::*exec) {
-  for (auto& wk : t->work)
-    if (wk.*exec) {
-      hipStreamSynchronize(wk.side->stream);
-      hipGraphExecDestroy(wk.*exec);
-      wk.*exec = nullptr;
-    }
+// the graph part of workspace w for these roots: sample + union of both root sets (no random negatives: one absent root)
+int32_t lp_issue_graph(gigl_nablp_train_plan* t, int w, PlanRing::Family fam, const uint32_t* main_roots,
+                       const uint32_t* rn_roots, int32_t sampling_seed, int32_t mode) {
+  const uint32_t* roots[2] = {main_roots, rn_roots};
+  const size_t count[2] = {(size_t)t->enc[0].b, (size_t)t->n_rn};
+  return t->ring.issue_graph_part(w, fam, roots, count, train_part_captures(0),
+                                  [&]() { return lp_enqueue_graph(t, w, sampling_seed, mode); });
 }
 }  // namespace
 
@@ -2770,35 +2740,31 @@ int32_t gigl_nablp_train_plan_step2(gigl_nablp_train_plan* t, const uint32_t* ma
   hipStream_t st = ctx->stream;
   int32_t rc = train_bind_stream(ctx, t->lctx);
   if (rc != GIGL_OK) return rc;
-  if (t->cap_seed != sampling_seed || t->cap_mode != mode) {
-    lp_drop_graph_parts(t, &gigl_nablp_train_plan::Work::exec_graph);
-    for (auto& wk : t->work) wk.fetched = false;  // (what was prefetched was sampled under the old seed)
-    t->cap_seed = sampling_seed;
-    t->cap_mode = mode;
-  }
-  const int w = t->cur;
-  gigl_nablp_train_plan::Work& wk = t->work[w];
+  PlanRing& ring = t->ring;
+  ring.reseed(PlanRing::TRAIN, sampling_seed, mode);
+  const int w = ring.cur;
+  PlanRing::Slot& wk = ring.slot[w];
   // this step's trees: prefetched by the previous call for exactly these buffers, or sampled now
-  if (!(wk.fetched && wk.fetched_main == main_roots && wk.fetched_rn == rn_roots)) {
-    rc = lp_graph_part(t, w, main_roots, rn_roots, sampling_seed, mode);
-    if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(wk.side));
+  if (!ring.holds(w, main_roots, rn_roots)) {
+    rc = lp_issue_graph(t, w, PlanRing::TRAIN, main_roots, rn_roots, sampling_seed, mode);
+    if (rc != GIGL_OK) return rc;
   }
-  wk.fetched = false;  // (consumed)
+  ring.consume(w);
   const int wn = (w + 1) % gigl_nablp_train_plan::WS;
   if (next_main_roots) {  // the next step's graph part goes to the other workspace, beside this step's layers
-    rc = lp_graph_part(t, wn, next_main_roots, next_rn_roots, sampling_seed, mode);
-    if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->work[wn].side));
+    rc = lp_issue_graph(t, wn, PlanRing::TRAIN, next_main_roots, next_rn_roots, sampling_seed, mode);
+    if (rc != GIGL_OK) return rc;
   }
   GIGL_HIP_CHECK(ctx, hipMemcpyAsync(t->pos_cnt, pos_cnt, (size_t)t->b * 4, hipMemcpyDeviceToDevice, st));
   GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, wk.ev_graph, 0));
   // (a forked step is launched eagerly: as fast as its replay — 1.07 / 1.71 ms both ways — and no graph with a second branch is
   // ever instantiated; see DESIGN_HISTORY "Round 6" for what those did to a long session)
   if (t->fork) rc = lp_enqueue_layers(t, w);
-  else rc = train_run_part(t->lctx, &wk.exec_layers, &wk.warm_layers, [&]() { return lp_enqueue_layers(t, w); }, 1);
+  else rc = gigl_run_part(t->lctx, t->lctx, &wk.layers, train_part_captures(1), "training step", [&]() { return lp_enqueue_layers(t, w); });
   if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
   GIGL_HIP_CHECK(ctx, hipEventRecord(wk.ev_layers, st));
   if (loss_out) GIGL_HIP_CHECK(ctx, hipMemcpyAsync(loss_out, t->loss, 8, hipMemcpyDeviceToDevice, st));
-  if (next_main_roots) t->cur = wn;
+  if (next_main_roots) ring.cur = wn;
   return GIGL_OK;
 }
 
@@ -2821,17 +2787,14 @@ int32_t gigl_nablp_train_plan_eval(gigl_nablp_train_plan* t, const uint32_t* mai
   hipStream_t st = ctx->stream;
   int32_t rc = train_bind_stream(ctx, t->lctx);
   if (rc != GIGL_OK) return rc;
-  if (t->eval_seed != sampling_seed || t->eval_mode != mode) {
-    lp_drop_graph_parts(t, &gigl_nablp_train_plan::Work::exec_graph_eval);
-    t->eval_seed = sampling_seed;
-    t->eval_mode = mode;
-  }
-  // the workspace that holds no announced batch (a _step2 with next roots left its graph part in work[cur])
-  const int w = t->work[t->cur].fetched ? (t->cur + 1) % gigl_nablp_train_plan::WS : t->cur;
-  gigl_nablp_train_plan::Work& wk = t->work[w];
+  PlanRing& ring = t->ring;
+  ring.reseed(PlanRing::EVAL, sampling_seed, mode);
+  // the workspace that holds no announced batch (a _step2 with next roots left its graph part in slot[cur])
+  const int w = ring.slot[ring.cur].fetched ? (ring.cur + 1) % gigl_nablp_train_plan::WS : ring.cur;
+  PlanRing::Slot& wk = ring.slot[w];
   GIGL_REQUIRE(ctx, !wk.fetched, "both workspaces hold an announced batch");
-  rc = lp_graph_part(t, w, main_roots, rn_roots, sampling_seed, mode, true);
-  if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(wk.side));
+  rc = lp_issue_graph(t, w, PlanRing::EVAL, main_roots, rn_roots, sampling_seed, mode);
+  if (rc != GIGL_OK) return rc;
   GIGL_HIP_CHECK(ctx, hipMemcpyAsync(t->pos_cnt, pos_cnt, (size_t)t->b * 4, hipMemcpyDeviceToDevice, st));
   GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, wk.ev_graph, 0));
   // (eager: no captured layers graph is made or invalidated — and none with a second branch, see gigl_nablp_train_plan_create)
@@ -3467,8 +3430,8 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
     return rc;
   }
   // every node of the batch graph is numbered: gigl_gat_input_aggregate reads its sources through un.nodes
-  for (auto& wk : t->work)
-    for (gigl_sage_plan* bp : wk.base) bp->leaf_global = false;
+  for (int wi = 0; wi < gigl_nablp_train_plan::WS; ++wi)
+    for (gigl_sage_plan* bp : t->ring.slot[wi].base) bp->leaf_global = false;
   auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
   bool ok = true;
   // (default on, GIGL_LP_FORK=0 off, as the GraphSAGE plan: the forked step's layers part launched eagerly)
@@ -3504,9 +3467,9 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
   if (t->zero_base) lay_out((float*)t->zero_base);
   g.u = (float*)alloc((size_t)2 * H * d * 4);
   ok = ok && t->zero_base && g.u && gat_moments_alloc(t->owned, g.tensor, 0, GAT_CORE) &&
-       gat_scratch_alloc(t, g.sc[0], t->lctx, rows1_max, t->work[0].base[0]->un.cap_edges, b_max);
+       gat_scratch_alloc(t, g.sc[0], t->lctx, rows1_max, t->ring.slot[0].base[0]->un.cap_edges, b_max);
   if (want_fork && ok)  // the second stream's ctx and events, its own scratch (the random negatives' rows and edges)
-    ok = lp_fork_setup(t) && gat_scratch_alloc(t, g.sc[1], t->actx, t->enc[1].rows_cap[0], t->work[0].base[1]->un.cap_edges, t->enc[1].b);
+    ok = lp_fork_setup(t) && gat_scratch_alloc(t, g.sc[1], t->actx, t->enc[1].rows_cap[0], t->ring.slot[0].base[1]->un.cap_edges, t->enc[1].b);
   if (ok) {
     g.wt1 = (float*)alloc((size_t)C1 * H * C0 * 4);
     ok = g.wt1 != nullptr;
@@ -3570,7 +3533,7 @@ int32_t gigl_gat_nablp_train_plan_set_edge_features(gigl_nablp_train_plan* t, gi
   GIGL_REQUIRE(ctx, t->kind == 1, "edge features apply to the GAT link-prediction plan (gigl_gat_nablp_train_plan_create)");
   GIGL_REQUIRE(ctx, !t->stepped && !t->gat.e.table, "edge features are set once, after create and before the first step");
   GIGL_REQUIRE(ctx, edge_table && w_edge && att_edge, "null argument");
-  const gigl_graph* graph = t->work[0].base[0]->graph;
+  const gigl_graph* graph = t->ring.slot[0].base[0]->graph;
   const int32_t De = edge_table->d;
   if (edge_table->dtype != GIGL_DTYPE_F32 || De < 1 || De > 64)  // (a lane per component of an edge row)
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "GAT link-prediction plan: the edge table must be fp32, 1..64 wide (dtype %d, %d)",
@@ -3620,8 +3583,8 @@ int32_t gigl_gat_nablp_train_plan_set_edge_features(gigl_nablp_train_plan* t, gi
     for (int k = 0; k < (fork ? 2 : 1); ++k) ok = ok && gat_scratch_alloc_edge(t, g.sc[k]);
   }
   // every workspace's batch graphs get their edge ids from their own graph part (plan_edge_ids_kernel; all rows are numbered)
-  for (auto& wk : t->work)
-    for (gigl_sage_plan* bp : wk.base) {
+  for (int wi = 0; wi < gigl_nablp_train_plan::WS; ++wi)
+    for (gigl_sage_plan* bp : t->ring.slot[wi].base) {
       if (!ok) break;
       const int64_t positions = bp->un.cap_edges + (bp->alias_rows ? bp->last_slots : 0);
       void* q = nullptr;

@@ -1267,7 +1267,10 @@ int32_t gigl_sage_train_plan_step(gigl_sage_train_plan* plan, const uint32_t* ro
  * gigl_nablp_train_plan_step2): the plan samples from the announced DEVICE buffer on its own stream right away and
  * recognises the batch at the next call by the buffer's ADDRESS — the buffer must keep its contents, and must not be
  * handed over again for a different batch, until the step that consumes it has been issued.  A caller that refills one
- * static buffer per step must not announce it (pass NULL: the step then samples when it is called). */
+ * static buffer per step must not announce it (pass NULL: the step then samples when it is called).
+ * SEED RULE: an announced batch was sampled under the (sampling_seed, mode) of the call that announced it.  A step whose
+ * (sampling_seed, mode) differ from the previous step's forgets EVERY announced batch, in both training plans: its own
+ * batch and whatever it announces are sampled under the new pair, as if nothing had been announced. */
 int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* plan, const uint32_t* roots, const int64_t* labels, int32_t n_valid,
                                    const uint32_t* roots_next, const uint32_t* roots_next2, int32_t sampling_seed,
                                    int32_t mode, float* loss_out);
