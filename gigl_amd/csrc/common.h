@@ -48,6 +48,9 @@ struct gigl_ctx {
   // node (roots that are each other's sampled neighbours) — instead of b*(1 + f0 + ...) inner rows: the workspace of the
   // redo of a batch that overflowed a regular plan
   bool wide = false;
+  // gigl_ctx_set_lp_hard_negatives: link-prediction training plans created on this ctx carry this many hard-negative slots
+  // per anchor
+  int32_t lp_hard_negatives = 0;
 };
 
 // rows a plan provisions for the nodes of level <= level_max of a batch of b roots: b*(1 + f0 + ... ) over level_max

@@ -143,6 +143,14 @@ int32_t gigl_ctx_set_wide_workspaces(gigl_ctx* ctx, int32_t on) {
   return GIGL_OK;
 }
 
+int32_t gigl_ctx_set_lp_hard_negatives(gigl_ctx* ctx, int32_t num_hard_negatives) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  GIGL_REQUIRE(ctx, num_hard_negatives >= 0 && num_hard_negatives <= GIGL_MAX_FANOUT,
+               "hard negatives per anchor %d outside [0,%d]", num_hard_negatives, GIGL_MAX_FANOUT);
+  ctx->lp_hard_negatives = num_hard_negatives;
+  return GIGL_OK;
+}
+
 int32_t gigl_ctx_set_stream(gigl_ctx* ctx, void* hip_stream) {
   if (!ctx) return GIGL_E_INVALID_ARG;
   if ((hipStream_t)hip_stream == ctx->stream && !ctx->own_stream) return GIGL_OK;  // already bound: nothing to drain

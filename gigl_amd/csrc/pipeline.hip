@@ -2000,6 +2000,15 @@ int32_t gigl_sage_train_plan_resume(gigl_sage_train_plan* t) {
 // (1 + P) rooted trees, anchor-major (anchor, its P positive slots; a missing positive repeats the anchor and is masked
 // out by pos_cnt); random negatives = n_rn roots.  Everything is capacity-shaped (Q = b P query rows, C = Q + n_rn
 // candidates, validity masks on the device): no host read, no torch kernel, one captured hipGraph per step.
+// A plan created while gigl_ctx_set_lp_hard_negatives(ctx, H) holds H > 0 carries H HARD-NEGATIVE slots per anchor (the
+// user-defined negative label edges of UserDefinedLabelsNodeAnchorBasedLinkPredictionTask): the main batch is b x T trees,
+// T = 1 + P + H (anchor, positive slots, hard-negative slots; an empty slot repeats the anchor), pos_cnt is [2 b] words —
+// positives per anchor, then hard negatives per anchor — and the candidates are cat(positives, hard negatives, random
+// negatives) as in infer_task_inputs: columns [0, Q) the positives, Q + i H + k hard negative k of anchor i, Q + b H
+// onwards the random negatives (C = Q + b H + n_rn).  A hard negative is a candidate of EVERY query row, whether or not
+// its own anchor has a positive; the same-query mask covers the positives' block only, the accidental-hit mask every
+// column.  The evaluation ranks against the random negatives alone (the reference's validate), its loss sees every column.
+// H = 0 is the plan without them: the same launches, the same [b] counts.
 namespace {
 // The GAT kind's trainable tensors live in ONE table whose index is the one gigl_nablp_train_plan_moments publishes:
 // 4 l + {w, att_src, att_dst, bias} for the core tensors, 8 + 3 l + {lin_edge.weight, att_edge, lin_edge_message.weight}
@@ -2040,7 +2049,7 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
   gigl_ctx* ctx = nullptr;
   gigl_ctx* lctx = nullptr;  // private ctx (own arena) bound to the caller's stream: every launch of the step
   SageTrainEnc enc[2];       // 0: main batch, 1: random negatives
-  int32_t b = 0, P = 0, n_rn = 0, normalize = 0, remove_hits = 1;
+  int32_t b = 0, P = 0, H = 0, n_rn = 0, normalize = 0, remove_hits = 1;  // H: ctx->lp_hard_negatives at creation
   float temperature = 0.07f;
   float* da = nullptr;        // gradient of a layer's operand (SAGE)
   void* zero_base = nullptr;  // both encodes' gw | gb | dh: cleared at the start of every step
@@ -2049,7 +2058,9 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
   float *rq = nullptr, *cand = nullptr, *cand_t = nullptr, *scores = nullptr, *dscores = nullptr, *d_rq = nullptr, *d_cand = nullptr;
   int64_t *qid = nullptr, *cid = nullptr;
   int32_t* valid = nullptr;    // [C]: candidate column j takes part (rows i < Q use valid[i])
-  int32_t* pos_cnt = nullptr;  // [b] static copy of the step's input
+  int cand_cols() const { return b * (P + H) + n_rn; }                // C
+  size_t cnt_words() const { return (size_t)b * (H > 0 ? 2 : 1); }   // of pos_cnt
+  int32_t* pos_cnt = nullptr;  // [b] (H > 0: [2 b], the hard negatives' counts behind the positives') static copy of the step's input
   int32_t* consts = nullptr;   // device {Q, C, Adam step, ...}
   float *row_lse = nullptr, *row_loss = nullptr, *loss = nullptr;  // loss[0] = the step's loss, loss[1] = valid query rows
   // ---- GAT encoder (kind == 1, gigl_gat_nablp_train_plan_create): two layers, the first from the INPUT side
@@ -2140,19 +2151,21 @@ __global__ __launch_bounds__(256) void lp_take_norm_kernel(const float* __restri
 }
 
 // the head's operands from the two encodes: row q = (anchor i, positive slot j) of rq = the anchor's embedding, row q of
-// cand = that positive's; rows Q.. of cand = the random negatives'; ids for the loss masks; validity of every candidate
+// cand = that positive's; rows Q + i H + k of cand = hard negative k of anchor i (a candidate whether or not the anchor
+// has a positive: the reference concatenates every root's); rows Q + b H.. = the random negatives'; ids for the loss
+// masks; validity of every candidate
 __global__ __launch_bounds__(256) void lp_pack_kernel(const float* __restrict__ e_main, const float* __restrict__ e_rn,
                                                       const uint32_t* __restrict__ roots_main,
                                                       const uint32_t* __restrict__ roots_rn,
                                                       const int32_t* __restrict__ pos_cnt, const float* __restrict__ inv_main,
-                                                      const float* __restrict__ inv_rn, int b, int P, int n_rn, int d,
-                                                      float* __restrict__ rq, float* __restrict__ cand,
+                                                      const float* __restrict__ inv_rn, int b, int P, int H, int n_rn,
+                                                      int d, float* __restrict__ rq, float* __restrict__ cand,
                                                       int64_t* __restrict__ qid, int64_t* __restrict__ cid,
                                                       int32_t* __restrict__ valid) {
   const int lane = threadIdx.x & 63;
   const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int Q = b * P, T = 1 + P;
-  if (row >= Q + n_rn) return;
+  const int Q = b * P, T = 1 + P + H, R0 = Q + b * H;
+  if (row >= R0 + n_rn) return;
   if (row < Q) {
     const int i = row / P, j = row - i * P;
     const int ra = i * T, rp = ra + 1 + j;
@@ -2169,8 +2182,19 @@ __global__ __launch_bounds__(256) void lp_pack_kernel(const float* __restrict__ 
       cid[row] = (int64_t)pid;
       valid[row] = ok ? 1 : 0;
     }
+  } else if (row < R0) {
+    const int i = (row - Q) / H, k = (row - Q) - i * H;
+    const int ra = i * T, rh = ra + 1 + P + k;
+    const uint32_t id = roots_main[rh];
+    const bool ok = roots_main[ra] != GIGL_INVALID && id != GIGL_INVALID && k < pos_cnt[b + i] && inv_main[rh] != 0.f;
+    const float* ea = e_main + (int64_t)rh * d;
+    for (int c = lane; c < d; c += 64) cand[(int64_t)row * d + c] = ok ? ea[c] : 0.f;
+    if (lane == 0) {
+      cid[row] = (int64_t)id;
+      valid[row] = ok ? 1 : 0;
+    }
   } else {
-    const int r = row - Q;
+    const int r = row - R0;
     const uint32_t id = roots_rn[r];
     const bool ok = id != GIGL_INVALID && inv_rn[r] != 0.f;
     const float* ea = e_rn + (int64_t)r * d;
@@ -2352,16 +2376,17 @@ __global__ __launch_bounds__(256) void lp_loss_backward_kernel(const float* __re
 }
 
 // d emb of the two encodes from d rq / d cand: an anchor's row sums its P query rows, a positive's row is its candidate
-// row, a random negative's its own; then through the normalisation (dx = (g - y <y, g>) / max(|x|, eps)) and added to the
+// row, a hard negative's and a random negative's their own; then through the normalisation (dx = (g - y <y, g>) / max(|x|, eps)) and added to the
 // last layer's output gradient at the root's local row (roots that are the same node share it: atomics).  One wave per root.
 __global__ __launch_bounds__(256) void lp_unpack_scatter_kernel(const float* __restrict__ d_rq, const float* __restrict__ d_cand,
                                                                 const int32_t* __restrict__ valid, const float* __restrict__ emb,
                                                                 const float* __restrict__ inv,
                                                                 const int32_t* __restrict__ root_local, int which, int b, int P,
-                                                                int n_rn, int d, int normalize, float* __restrict__ dh_last) {
+                                                                int H, int n_rn, int d, int normalize,
+                                                                float* __restrict__ dh_last) {
   const int lane = threadIdx.x & 63;
   const int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int T = 1 + P, Q = b * P;
+  const int T = 1 + P + H, Q = b * P, R0 = Q + b * H;
   const int n_roots = which == 0 ? b * T : n_rn;
   if (r >= n_roots) return;
   const float iv = inv[r];
@@ -2378,14 +2403,15 @@ __global__ __launch_bounds__(256) void lp_unpack_scatter_kernel(const float* __r
     float v = 0.f;
     if (c < d) {
       if (which == 1) {
-        v = valid[Q + r] ? d_cand[(int64_t)(Q + r) * d + c] : 0.f;
+        v = valid[R0 + r] ? d_cand[(int64_t)(R0 + r) * d + c] : 0.f;
       } else {
         const int i = r / T, t = r - i * T;
         if (t == 0) {
           for (int j = 0; j < P; ++j)
             if (valid[i * P + j]) v += d_rq[(int64_t)(i * P + j) * d + c];
-        } else if (valid[i * P + t - 1]) {
-          v = d_cand[(int64_t)(i * P + t - 1) * d + c];
+        } else {
+          const int col = t <= P ? i * P + t - 1 : Q + i * H + t - 1 - P;
+          if (valid[col]) v = d_cand[(int64_t)col * d + c];
         }
       }
       dot += v * y[c];
@@ -2445,7 +2471,7 @@ int32_t lp_enqueue_graph(gigl_nablp_train_plan* t, int w, int32_t sampling_seed,
 int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w) {
   gigl_ctx* ctx = t->lctx;
   hipStream_t st = ctx->stream;
-  const int L = t->L, d = t->dims[L], Q = t->b * t->P, Cn = Q + t->n_rn;
+  const int L = t->L, d = t->dims[L], Q = t->b * t->P, Cn = t->cand_cols();
   int32_t rc = GIGL_OK;
   for (int k = 0; k < 2; ++k) t->enc[k].base = t->ring.slot[w].base[k];
   gigl_fill_u32(st, t->zero_base, 0u, (int64_t)(t->zero_bytes / 4));
@@ -2473,8 +2499,8 @@ int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w) {
   const gigl_sage_plan *pm = t->enc[0].base, *pr = t->enc[1].base;
   hipLaunchKernelGGL(lp_pack_kernel, dim3((unsigned)((Cn + 3) / 4)), dim3(256), 0, st, (const float*)t->enc[0].emb,
                      (const float*)t->enc[1].emb, (const uint32_t*)pm->roots_buf, (const uint32_t*)pr->roots_buf,
-                     (const int32_t*)t->pos_cnt, (const float*)t->enc[0].inv, (const float*)t->enc[1].inv, t->b, t->P, t->n_rn,
-                     d, t->rq, t->cand, t->qid, t->cid, t->valid);
+                     (const int32_t*)t->pos_cnt, (const float*)t->enc[0].inv, (const float*)t->enc[1].inv, t->b, t->P, t->H,
+                     t->n_rn, d, t->rq, t->cand, t->qid, t->cid, t->valid);
   // scores[q][c] = <rq[q], cand[c]>  (decoder.py:64-70: torch.mm(q, c.T))
   rc = gigl_linear(ctx, t->rq, t->cand, nullptr, t->consts + 0, Q, d, Cn, 0, t->scores);
   if (rc != GIGL_OK) return rc;
@@ -2489,7 +2515,7 @@ int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w) {
 int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
   gigl_ctx* ctx = t->lctx;
   hipStream_t st = ctx->stream;
-  const int L = t->L, d = t->dims[L], Q = t->b * t->P, Cn = Q + t->n_rn;
+  const int L = t->L, d = t->dims[L], Q = t->b * t->P, Cn = t->cand_cols();
   int32_t rc = lp_enqueue_forward(t, w);
   if (rc != GIGL_OK) return rc;
   const gigl_sage_plan *pm = t->enc[0].base, *pr = t->enc[1].base;
@@ -2512,7 +2538,7 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
     const SageTrainEnc& e = t->enc[k];
     hipLaunchKernelGGL(lp_unpack_scatter_kernel, dim3((unsigned)((e.b + 3) / 4)), dim3(256), 0, st, (const float*)t->d_rq,
                        (const float*)t->d_cand, (const int32_t*)t->valid, (const float*)e.emb, (const float*)e.inv,
-                       (const int32_t*)e.base->un.root_local, k, t->b, t->P, t->n_rn, d, t->normalize, e.dh[L - 1]);
+                       (const int32_t*)e.base->un.root_local, k, t->b, t->P, t->H, t->n_rn, d, t->normalize, e.dh[L - 1]);
   }
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   if (t->fork) {
@@ -2548,7 +2574,7 @@ int32_t lp_create_workspaces(gigl_nablp_train_plan* t, gigl_graph* graph, gigl_f
                              const int32_t* dims, float* const* w, float* const* bias, int32_t act_last) {
   gigl_ctx* ctx = t->ctx;
   int32_t rc = gigl_ctx_create(ctx->device, &t->lctx);
-  const int32_t nb[2] = {t->b * (1 + t->P), t->n_rn > 0 ? t->n_rn : 1};
+  const int32_t nb[2] = {t->b * (1 + t->P + t->H), t->n_rn > 0 ? t->n_rn : 1};
   for (int k = 0; k < 2; ++k) t->enc[k].b = nb[k];
   if (rc == GIGL_OK) rc = t->ring.create(ctx, gigl_nablp_train_plan::WS, 2, nb, graph, feat, fanouts, hops, dims, w, bias, act_last);
   if (rc == GIGL_OK)
@@ -2560,7 +2586,7 @@ int32_t lp_create_workspaces(gigl_nablp_train_plan* t, gigl_graph* graph, gigl_f
 // gradients, the loss words; consts = {Q, C, Adam's step counter}
 bool lp_head_alloc(gigl_nablp_train_plan* t, size_t d) {
   auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
-  const size_t Q = (size_t)t->b * t->P, Cn = Q + (size_t)t->n_rn;
+  const size_t Q = (size_t)t->b * t->P, Cn = (size_t)t->cand_cols();
   bool ok = true;
   for (SageTrainEnc& e : t->enc) {
     e.emb = (float*)alloc((size_t)e.b * d * 4);
@@ -2577,7 +2603,7 @@ bool lp_head_alloc(gigl_nablp_train_plan* t, size_t d) {
   t->qid = (int64_t*)alloc(Q * 8);
   t->cid = (int64_t*)alloc(Cn * 8);
   t->valid = (int32_t*)alloc(Cn * 4);
-  t->pos_cnt = (int32_t*)alloc((size_t)t->b * 4);
+  t->pos_cnt = (int32_t*)alloc(t->cnt_words() * 4);
   t->consts = (int32_t*)alloc(64);
   t->row_lse = (float*)alloc(Q * 4);
   t->row_loss = (float*)alloc(Q * 4);
@@ -2623,6 +2649,7 @@ static gigl_nablp_train_plan* lp_plan_new(gigl_ctx* ctx, int kind, int32_t L, in
   t->L = L;
   t->b = b_anchors;
   t->P = num_positives;
+  t->H = ctx->lp_hard_negatives;
   t->n_rn = n_random_negatives;
   t->normalize = l2_normalize ? 1 : 0;
   t->remove_hits = remove_accidental_hits ? 1 : 0;
@@ -2755,7 +2782,7 @@ int32_t gigl_nablp_train_plan_step2(gigl_nablp_train_plan* t, const uint32_t* ma
     rc = lp_issue_graph(t, wn, PlanRing::TRAIN, next_main_roots, next_rn_roots, sampling_seed, mode);
     if (rc != GIGL_OK) return rc;
   }
-  GIGL_HIP_CHECK(ctx, hipMemcpyAsync(t->pos_cnt, pos_cnt, (size_t)t->b * 4, hipMemcpyDeviceToDevice, st));
+  GIGL_HIP_CHECK(ctx, hipMemcpyAsync(t->pos_cnt, pos_cnt, t->cnt_words() * 4, hipMemcpyDeviceToDevice, st));
   GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, wk.ev_graph, 0));
   // (a forked step is launched eagerly: as fast as its replay — 1.07 / 1.71 ms both ways — and no graph with a second branch is
   // ever instantiated; see DESIGN_HISTORY "Round 6" for what those did to a long session)
@@ -2795,7 +2822,7 @@ int32_t gigl_nablp_train_plan_eval(gigl_nablp_train_plan* t, const uint32_t* mai
   GIGL_REQUIRE(ctx, !wk.fetched, "both workspaces hold an announced batch");
   rc = lp_issue_graph(t, w, PlanRing::EVAL, main_roots, rn_roots, sampling_seed, mode);
   if (rc != GIGL_OK) return rc;
-  GIGL_HIP_CHECK(ctx, hipMemcpyAsync(t->pos_cnt, pos_cnt, (size_t)t->b * 4, hipMemcpyDeviceToDevice, st));
+  GIGL_HIP_CHECK(ctx, hipMemcpyAsync(t->pos_cnt, pos_cnt, t->cnt_words() * 4, hipMemcpyDeviceToDevice, st));
   GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, wk.ev_graph, 0));
   // (eager: no captured layers graph is made or invalidated — and none with a second branch, see gigl_nablp_train_plan_create)
   gigl_sage_plan* const held[2] = {t->enc[0].base, t->enc[1].base};
@@ -2806,8 +2833,9 @@ int32_t gigl_nablp_train_plan_eval(gigl_nablp_train_plan* t, const uint32_t* mai
   const int Q = t->b * t->P;
   hipLaunchKernelGGL(lp_eval_loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->row_loss, (const int32_t*)t->valid, Q,
                      (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta, acc, overflow_acc);
-  rc = gigl_lp_rank_metrics_enqueue(t->lctx, st, t->scores, (int64_t)Q + t->n_rn, t->b, t->P, t->pos_cnt, t->n_rn, Q,
-                                    t->valid + Q, ks, n_ks, pm->un.meta, pr->un.meta, t->rank_part, acc);
+  const int R0 = Q + t->b * t->H;  // (ranked against the random negatives only, as the reference's validate does)
+  rc = gigl_lp_rank_metrics_enqueue(t->lctx, st, t->scores, (int64_t)t->cand_cols(), t->b, t->P, t->pos_cnt, t->n_rn, R0,
+                                    t->valid + R0, ks, n_ks, pm->un.meta, pr->un.meta, t->rank_part, acc);
   if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
   GIGL_HIP_CHECK(ctx, hipEventRecord(wk.ev_layers, st));
   return GIGL_OK;
@@ -2951,7 +2979,7 @@ int32_t gigl_sage_train_plan_adopt(gigl_sage_train_plan* dst, gigl_sage_train_pl
 int32_t gigl_nablp_train_plan_adopt(gigl_nablp_train_plan* dst, gigl_nablp_train_plan* src) {
   if (!dst || !src) return GIGL_E_INVALID_ARG;
   gigl_ctx* ctx = dst->ctx;
-  GIGL_REQUIRE(ctx, dst->L == src->L && dst->kind == src->kind, "plans of different kinds");
+  GIGL_REQUIRE(ctx, dst->L == src->L && dst->kind == src->kind && dst->H == src->H, "plans of different kinds");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   GIGL_HIP_CHECK(ctx, hipStreamSynchronize(src->ctx->stream));
   if (dst->kind == 1) {

@@ -1574,6 +1574,70 @@ __global__ __launch_bounds__(256) void expand_replace_kernel(ExpandArgs a) {
   }
 }
 
+// arena bytes of one out_neighbors_enqueue over b roots
+int64_t out_neighbors_scratch(int64_t b) { return expand_desc_bytes(b) + (b + 1) * 8 + 1024; }
+
+int32_t out_neighbors_check(gigl_ctx* ctx, gigl_graph* g_out, int32_t f, int32_t counter, int32_t mode) {
+  GIGL_REQUIRE(ctx, counter >= 1 && counter <= 64, "permutation call counter %d outside [1,64]", counter);
+  GIGL_REQUIRE(ctx, g_out, "null argument");
+  GIGL_REQUIRE(ctx, mode == GIGL_MODE_SPARK_HASH, "positives are parity-mode only");
+  if (f < 1 || f > GIGL_MAX_FANOUT)
+    return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "num positives %d outside [1,%d]", f, GIGL_MAX_FANOUT);
+  return GIGL_OK;
+}
+
+// the launches of gigl_sample_out_neighbors (b >= 1, arguments checked); scratch out of the arena as it stands: the caller
+// has reset it with out_neighbors_scratch(b) bytes per call
+int32_t out_neighbors_enqueue(gigl_ctx* ctx, gigl_graph* g_out, const uint32_t* roots, int32_t b, int32_t f,
+                              int32_t sampling_seed, int32_t counter, uint32_t* pos, int32_t* cnt) {
+  RowDesc* desc = (RowDesc*)gigl_arena_alloc(ctx, expand_desc_bytes(b));
+  int64_t* heavy_list = (int64_t*)gigl_arena_alloc(ctx, (int64_t)b * 8);
+  int32_t* heavy_count = (int32_t*)gigl_arena_alloc(ctx, 256);
+  if (!desc || !heavy_list || !heavy_count) return gigl_fail(ctx, GIGL_E_OOM, "arena exhausted");
+  ExpandArgs a{};
+  a.rowptr = g_out->rowptr;
+  a.col = g_out->col;
+  a.n_nodes = g_out->n;
+  a.multi = g_out->multi ? 1 : 0;
+  a.roots = roots;
+  a.hop = 0;
+  a.n_parents = b;
+  a.f = f;
+  a.fan[0] = f;
+  a.hash_add = (int32_t)((uint32_t)sampling_seed * (uint32_t)counter);
+  a.out_nbr = pos;
+  a.out_cnt = cnt;
+  const uint64_t bound = window_bound(g_out, 1, counter, sampling_seed);
+  const uint64_t cap = table_cap_j();
+  const int32_t rc = ensure_table(ctx, bound == ~0ULL ? (1ull << 20) : (bound + 1 < cap ? bound + 1 : cap));
+  if (rc != GIGL_OK) return rc;
+  const RangeTable tb = ((TableOwner*)ctx->sampler_table)->t;
+  return run_expand(ctx, a, tb, bound != ~0ULL && bound < tb.dom, heavy_list, heavy_count, desc);
+}
+
+// roots_out [b][1 + P + H] = (anchor, its P positive slots, its H hard-negative slots), an empty slot repeating the anchor;
+// cnt_out [0, b) / [b, 2b) hold the draws' counts already (an absent anchor drew nothing: its row is all 0xFFFFFFFF).
+// Without hard negatives the second half is written here: zeros.
+__global__ __launch_bounds__(256) void nablp_main_roots_kernel(const uint32_t* __restrict__ anchors,
+                                                               const uint32_t* __restrict__ pos,
+                                                               const uint32_t* __restrict__ neg, int b, int P, int H,
+                                                               int has_neg, uint32_t* __restrict__ roots_out,
+                                                               int32_t* __restrict__ cnt_out) {
+  const int T = 1 + P + H;
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)b * T) return;
+  const int i = (int)(idx / T), t = (int)(idx - (int64_t)i * T);
+  const uint32_t a = anchors[i];
+  uint32_t v = a;
+  if (t >= 1 && t <= P) {
+    if (t - 1 < cnt_out[i]) v = pos[(int64_t)i * P + t - 1];
+  } else if (t > P) {
+    if (has_neg && t - 1 - P < cnt_out[b + i]) v = neg[(int64_t)i * H + t - 1 - P];
+  } else if (!has_neg) {
+    cnt_out[b + i] = 0;
+  }
+  roots_out[idx] = v;
+}
 }  // namespace
 
 void gigl_sampler_table_free(gigl_ctx* ctx) {  // (the caller has synchronised the ctx stream)
@@ -1797,38 +1861,44 @@ int32_t gigl_sample_out_neighbors(gigl_ctx* ctx, gigl_graph* g_out, const uint32
                                   int32_t f, int32_t sampling_seed, int32_t counter, int32_t mode, uint32_t* pos,
                                   int32_t* cnt) {
   if (!ctx) return GIGL_E_INVALID_ARG;
-  GIGL_REQUIRE(ctx, counter >= 1 && counter <= 64, "permutation call counter %d outside [1,64]", counter);
-  GIGL_REQUIRE(ctx, g_out && (roots || b == 0) && pos && cnt, "null argument");
-  GIGL_REQUIRE(ctx, mode == GIGL_MODE_SPARK_HASH, "positives are parity-mode only");
-  if (f < 1 || f > GIGL_MAX_FANOUT)
-    return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "num positives %d outside [1,%d]", f, GIGL_MAX_FANOUT);
+  GIGL_REQUIRE(ctx, (roots || b == 0) && pos && cnt, "null argument");
+  int32_t rc = out_neighbors_check(ctx, g_out, f, counter, mode);
+  if (rc != GIGL_OK) return rc;
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (b == 0) return GIGL_OK;
-  int32_t rc = gigl_arena_reset(ctx, expand_desc_bytes(b) + (int64_t)(b + 1) * 8 + 1024);
+  rc = gigl_arena_reset(ctx, out_neighbors_scratch(b));
   if (rc != GIGL_OK) return rc;
-  RowDesc* desc = (RowDesc*)gigl_arena_alloc(ctx, expand_desc_bytes(b));
-  int64_t* heavy_list = (int64_t*)gigl_arena_alloc(ctx, (int64_t)b * 8);
-  int32_t* heavy_count = (int32_t*)gigl_arena_alloc(ctx, 256);
-  if (!desc || !heavy_list || !heavy_count) return gigl_fail(ctx, GIGL_E_OOM, "arena exhausted");
-  ExpandArgs a{};
-  a.rowptr = g_out->rowptr;
-  a.col = g_out->col;
-  a.n_nodes = g_out->n;
-  a.multi = g_out->multi ? 1 : 0;
-  a.roots = roots;
-  a.hop = 0;
-  a.n_parents = b;
-  a.f = f;
-  a.fan[0] = f;
-  a.hash_add = (int32_t)((uint32_t)sampling_seed * (uint32_t)counter);
-  a.out_nbr = pos;
-  a.out_cnt = cnt;
-  const uint64_t bound = window_bound(g_out, 1, counter, sampling_seed);
-  const uint64_t cap = table_cap_j();
-  rc = ensure_table(ctx, bound == ~0ULL ? (1ull << 20) : (bound + 1 < cap ? bound + 1 : cap));
+  return out_neighbors_enqueue(ctx, g_out, roots, b, f, sampling_seed, counter, pos, cnt);
+}
+
+int32_t gigl_nablp_main_roots(gigl_ctx* ctx, const uint32_t* anchors, int32_t b, gigl_graph* g_pos, int32_t P,
+                              gigl_graph* g_neg, int32_t H, int32_t sampling_seed, int32_t mode, uint32_t* roots_out,
+                              int32_t* cnt_out) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  GIGL_REQUIRE(ctx, (anchors || b == 0) && roots_out && cnt_out && b >= 0, "null argument");
+  GIGL_REQUIRE(ctx, H >= 0, "%d hard-negative slots", H);
+  const bool has_neg = H > 0 && g_neg;  // (no list: every hard-negative slot is empty)
+  // counters 3 and 4: the job's third and fourth hashBasedUniformPermutation calls (gigl_sample_positives; the user-defined
+  // task's negatives follow its positives)
+  int32_t rc = out_neighbors_check(ctx, g_pos, P, 3, mode);
+  if (rc == GIGL_OK && has_neg) rc = out_neighbors_check(ctx, g_neg, H, 4, mode);
   if (rc != GIGL_OK) return rc;
-  const RangeTable tb = ((TableOwner*)ctx->sampler_table)->t;
-  return run_expand(ctx, a, tb, bound != ~0ULL && bound < tb.dom, heavy_list, heavy_count, desc);
+  const int64_t n_roots = (int64_t)b * (1 + P + H);
+  GIGL_REQUIRE(ctx, n_roots < (int64_t)1 << 31, "root list too large");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (b == 0) return GIGL_OK;
+  rc = gigl_arena_reset(ctx, 2 * out_neighbors_scratch(b) + (int64_t)b * (P + H) * 4 + 1024);
+  if (rc != GIGL_OK) return rc;
+  uint32_t* pos = (uint32_t*)gigl_arena_alloc(ctx, (int64_t)b * P * 4);
+  uint32_t* neg = has_neg ? (uint32_t*)gigl_arena_alloc(ctx, (int64_t)b * H * 4) : nullptr;
+  if (!pos || (has_neg && !neg)) return gigl_fail(ctx, GIGL_E_OOM, "arena exhausted");
+  rc = out_neighbors_enqueue(ctx, g_pos, anchors, b, P, sampling_seed, 3, pos, cnt_out);
+  if (rc == GIGL_OK && has_neg) rc = out_neighbors_enqueue(ctx, g_neg, anchors, b, H, sampling_seed, 4, neg, cnt_out + b);
+  if (rc != GIGL_OK) return rc;
+  hipLaunchKernelGGL(nablp_main_roots_kernel, dim3((unsigned)((n_roots + 255) / 256)), dim3(256), 0, ctx->stream, anchors,
+                     (const uint32_t*)pos, (const uint32_t*)neg, b, P, H, has_neg ? 1 : 0, roots_out, cnt_out);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
 }
 
 }  // extern "C"

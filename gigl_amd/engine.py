@@ -7,6 +7,7 @@ reference's per-partition `KHopSamplerService.setup()/teardown()`
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 import ctypes as C
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
@@ -460,6 +461,25 @@ class HipEngine:
                                                   sampling_seed, counter, MODE_SPARK_HASH, C.c_void_p(pos.data_ptr()),
                                                   C.c_void_p(cnt.data_ptr())), self._ctx)
         return pos[: b * num_positives], cnt[:b]
+
+    def nablp_main_roots(self, anchors, num_positives: int, num_hard_negatives: int = 0, sampling_seed: int = 42, *,
+                         pos_label_edges: Optional[str] = None, neg_label_edges: Optional[str] = None):
+        """the main batch's roots of a link-prediction plan in one call (gigl_nablp_main_roots): per anchor its id,
+        `num_positives` out-neighbours (of the main out-edge graph, or of the label edge list `pos_label_edges`; counter 3)
+        and `num_hard_negatives` out-neighbours of the list `neg_label_edges` (counter 4; None: every slot empty), an empty
+        slot repeating the anchor.  -> (roots int32 [b * (1 + P + H)] anchor-major, cnt int32 [2 b]: positives per anchor,
+        then hard negatives per anchor); no host read."""
+        gp = self._label_edges[pos_label_edges]["graph"] if pos_label_edges else self._graph_out
+        assert gp is not None, "load the out-edge graph first (out_graph=True)"
+        gn = self._label_edges[neg_label_edges]["graph"] if neg_label_edges else None
+        r = self._roots_tensor(anchors)
+        b, P, H = int(r.numel()), int(num_positives), int(num_hard_negatives)
+        roots = torch.empty(max(b * (1 + P + H), 1), dtype=torch.int32, device=self.device)
+        cnt = torch.empty(max(2 * b, 1), dtype=torch.int32, device=self.device)
+        check(self._lib.gigl_nablp_main_roots(self._ctx, C.c_void_p(r.data_ptr()), b, gp, P, gn, H, int(sampling_seed),
+                                              MODE_SPARK_HASH, C.c_void_p(roots.data_ptr()), C.c_void_p(cnt.data_ptr())),
+              self._ctx)
+        return roots[: b * (1 + P + H)], cnt[: 2 * b]
 
     def load_label_edges(self, name: str, n: int, src, dst, feats=None) -> None:
         """a user-defined label edge list ("pos" / "neg": loadEdgeDataframeIntoSparkSql with EdgeUsageType.POS / NEG —
@@ -1522,6 +1542,25 @@ class SageTrainPlan:
         self._create = None  # (drops the argument arrays it holds)
 
 
+def pad_lp_batch(main_roots: torch.Tensor, pos_cnt: Optional[torch.Tensor], rn_roots: torch.Tensor, b: int, P: int, H: int,
+                 n_rn: int):
+    """a (short) link-prediction batch at the plan's capacity: main_roots int32 [na * T], T = 1 + P + H, -> [b * T] and
+    rn_roots -> [n_rn], absent entries 0xFFFFFFFF; pos_cnt int32 [na] -> [b] (H = 0), or its two halves [2 na] = (positives
+    per anchor, hard negatives per anchor) each padded to b -> [2 b], absent anchors 0.  Works on tensors of any device."""
+    T, halves = 1 + P + H, 2 if H > 0 else 1
+    assert main_roots.dtype == torch.int32 and main_roots.numel() % T == 0
+    na = main_roots.numel() // T
+    assert 0 < na <= b and (pos_cnt is None or pos_cnt.numel() == halves * na) and rn_roots.numel() <= n_rn
+    if na < b:
+        main_roots = torch.cat([main_roots, torch.full(((b - na) * T,), -1, dtype=torch.int32, device=main_roots.device)])
+        if pos_cnt is not None:
+            pos_cnt = torch.cat([pos_cnt.view(halves, na), pos_cnt.new_zeros((halves, b - na))], dim=1).reshape(-1)
+    if rn_roots.numel() < n_rn:
+        rn_roots = torch.cat([rn_roots, torch.full((n_rn - rn_roots.numel(),), -1, dtype=torch.int32,
+                                                   device=main_roots.device)])
+    return (main_roots.contiguous(), None if pos_cnt is None else pos_cnt.to(torch.int32).contiguous(), rn_roots.contiguous())
+
+
 class NablpTrainPlan:
     """one LINK-PREDICTION training step per call in the library (include/gigl_hip.h `gigl_nablp_train_plan_*`): sample +
     union of the main batch (anchors with their positives) and of the random-negative batch -> two GraphSAGE forwards over
@@ -1532,7 +1571,7 @@ class NablpTrainPlan:
     def __init__(self, eng: HipEngine, model, b_anchors: int, num_positives: int, n_random_negatives: int, fanouts,
                  temperature: float = 0.07, remove_accidental_hits: bool = True, lr: float = 5e-3,
                  weight_decay: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8, clip_grad_norm: float = 0.0,
-                 lr_factor: float = 1.0, lr_total_iters: int = 0):
+                 lr_factor: float = 1.0, lr_total_iters: int = 0, num_hard_negatives: int = 0):
         assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
         L = len(fanouts)
         assert model.num_layers == L, "one hop per layer"
@@ -1540,6 +1579,7 @@ class NablpTrainPlan:
                 and model.feature_embedding_layer is None and all(c.lin_r is not None for c in model.conv_layers)):
             raise NotImplementedError("the link-prediction training plan runs plain mean-GraphSAGE layers (conv -> relu)")
         self.eng, self.b, self.P, self.n_rn = eng, int(b_anchors), int(num_positives), int(n_random_negatives)
+        self.H = int(num_hard_negatives)
         self.fanouts = [int(f) for f in fanouts]
         self._lib = eng._lib
         self._optim_knobs = (float(clip_grad_norm), float(lr_factor), int(lr_total_iters))
@@ -1554,10 +1594,11 @@ class NablpTrainPlan:
 
         def create():
             h = C.c_void_p()
-            check(self._lib.gigl_nablp_train_plan_create(
-                eng._ctx, eng._graph, eng._feat, self.b, self.P, self.n_rn, fo, L, dims, w_arr, b_arr, flags[0], flags[1],
-                float(temperature), 1 if remove_accidental_hits else 0, float(lr), float(betas[0]), float(betas[1]), float(eps),
-                float(weight_decay), C.byref(h)), eng._ctx)
+            with self._hard_negative_slots():
+                check(self._lib.gigl_nablp_train_plan_create(
+                    eng._ctx, eng._graph, eng._feat, self.b, self.P, self.n_rn, fo, L, dims, w_arr, b_arr, flags[0], flags[1],
+                    float(temperature), 1 if remove_accidental_hits else 0, float(lr), float(betas[0]), float(betas[1]),
+                    float(eps), float(weight_decay), C.byref(h)), eng._ctx)
             try:
                 self._apply_optim_knobs(h)
             except Exception:
@@ -1569,10 +1610,22 @@ class NablpTrainPlan:
         self._plan = create()
         self.loss = torch.zeros(2, dtype=torch.float32, device=eng.device)  # {loss, query rows} of the last step
 
+    H = 0  # hard-negative slots per anchor (num_hard_negatives)
     load = SageTrainPlan.load
     store = SageTrainPlan.store
     grow = SageTrainPlan.grow
     step_checked = SageTrainPlan.step_checked
+
+    @contextmanager
+    def _hard_negative_slots(self):
+        """the ctx's hard-negative setting around a plan's create call (gigl_ctx_set_lp_hard_negatives): applied immediately
+        before, back to 0 immediately after — inside create(), so that grow()'s wide plan has the same slots and no other plan
+        of the engine inherits them"""
+        check(self._lib.gigl_ctx_set_lp_hard_negatives(self.eng._ctx, self.H), self.eng._ctx)
+        try:
+            yield
+        finally:
+            self._lib.gigl_ctx_set_lp_hard_negatives(self.eng._ctx, 0)
 
     def _apply_optim_knobs(self, handle) -> None:
         """gradient clipping and the ConstantLR warm-up of a (re)created plan handle, before its first step (called inside
@@ -1593,23 +1646,15 @@ class NablpTrainPlan:
         return float(t[0]), float(t[1])
 
     def _padded(self, main_roots: torch.Tensor, pos_cnt: Optional[torch.Tensor], rn_roots: torch.Tensor):
-        T = 1 + self.P
-        assert main_roots.device.type == self.eng.device.type and main_roots.dtype == torch.int32 and main_roots.numel() % T == 0
-        na = main_roots.numel() // T
-        assert 0 < na <= self.b and (pos_cnt is None or pos_cnt.numel() == na) and rn_roots.numel() <= self.n_rn
-        if na < self.b:
-            main_roots = torch.cat([main_roots, torch.full(((self.b - na) * T,), -1, dtype=torch.int32, device=main_roots.device)])
-            if pos_cnt is not None:
-                pos_cnt = torch.cat([pos_cnt, torch.zeros(self.b - na, dtype=torch.int32, device=pos_cnt.device)])
-        if rn_roots.numel() < self.n_rn:
-            rn_roots = torch.cat([rn_roots, torch.full((self.n_rn - rn_roots.numel(),), -1, dtype=torch.int32,
-                                                       device=main_roots.device)])
-        return (main_roots.contiguous(), None if pos_cnt is None else pos_cnt.to(torch.int32).contiguous(), rn_roots.contiguous())
+        assert main_roots.device.type == self.eng.device.type
+        return pad_lp_batch(main_roots, pos_cnt, rn_roots, self.b, self.P, self.H, self.n_rn)
 
     def step(self, main_roots: torch.Tensor, pos_cnt: torch.Tensor, rn_roots: torch.Tensor, sampling_seed: int = 42,
              mode: int = MODE_SPARK_HASH, next_roots=None) -> torch.Tensor:
         """main_roots int32 device [n_anchors * (1 + P)] anchor-major (anchor, its positive slots), pos_cnt int32 device
-        [n_anchors], rn_roots int32 device [<= n_random_negatives]; short batches are padded here (absent anchors /
+        [n_anchors] — with num_hard_negatives = H > 0: [n_anchors * (1 + P + H)] (anchor, positive slots, hard-negative slots)
+        and [2 * n_anchors] (positives per anchor, then hard negatives per anchor), what HipEngine.nablp_main_roots writes —
+        rn_roots int32 device [<= n_random_negatives]; short batches are padded here (absent anchors /
         negatives = 0xFFFFFFFF).  next_roots = (main_roots, rn_roots) of the NEXT step: its sampling and union build then
         run on a side stream beside this step's layers (gigl_nablp_train_plan_step2); the next call recognises them by
         value.  Returns {loss, query rows} (device, owned by the plan)."""
@@ -1727,11 +1772,12 @@ class GatNablpTrainPlan(NablpTrainPlan):
     def __init__(self, eng: HipEngine, model, b_anchors: int, num_positives: int, n_random_negatives: int, fanouts,
                  temperature: float = 0.07, remove_accidental_hits: bool = True, lr: float = 5e-3,
                  weight_decay: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8, clip_grad_norm: float = 0.0,
-                 lr_factor: float = 1.0, lr_total_iters: int = 0):
+                 lr_factor: float = 1.0, lr_total_iters: int = 0, num_hard_negatives: int = 0):
         assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
         if not self._applies_to(eng, model) or len(fanouts) != 2:
             raise NotImplementedError(self._COVERS)
         self.eng, self.b, self.P, self.n_rn = eng, int(b_anchors), int(num_positives), int(n_random_negatives)
+        self.H = int(num_hard_negatives)
         self.fanouts = [int(f) for f in fanouts]
         self._lib = eng._lib
         self._optim_knobs = (float(clip_grad_norm), float(lr_factor), int(lr_total_iters))
@@ -1743,11 +1789,12 @@ class GatNablpTrainPlan(NablpTrainPlan):
 
         def create():
             h = C.c_void_p()
-            check(self._lib.gigl_gat_nablp_train_plan_create(
-                eng._ctx, eng._graph, eng._feat, self.b, self.P, self.n_rn, (C.c_int32 * 2)(*self.fanouts), 2,
-                (C.c_int32 * 2)(*self.heads), (C.c_int32 * 2)(*self.channels), arr(self.w), arr(self.att_src), arr(self.att_dst),
-                arr(self.bias), slope, norm, float(temperature), 1 if remove_accidental_hits else 0, float(lr), float(betas[0]),
-                float(betas[1]), float(eps), float(weight_decay), C.byref(h)), eng._ctx)
+            with self._hard_negative_slots():
+                check(self._lib.gigl_gat_nablp_train_plan_create(
+                    eng._ctx, eng._graph, eng._feat, self.b, self.P, self.n_rn, (C.c_int32 * 2)(*self.fanouts), 2,
+                    (C.c_int32 * 2)(*self.heads), (C.c_int32 * 2)(*self.channels), arr(self.w), arr(self.att_src),
+                    arr(self.att_dst), arr(self.bias), slope, norm, float(temperature), 1 if remove_accidental_hits else 0,
+                    float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), C.byref(h)), eng._ctx)
             try:
                 self._after_create(h)
                 self._apply_optim_knobs(h)

@@ -116,20 +116,38 @@ class HbmNablpBatch:
     ever becoming TFRecords.  The batch graph is the union of the k-hop trees of every anchor AND of every sampled
     positive — the node / edge set the TFRecord route's collate builds from the records' merged neighbourhoods
     (NodeAnchorBasedLinkPredictionTask.scala:146-312) — rooted at [anchor, pos_1 .. pos_P] per anchor; a positive
-    the anchor does not have repeats the anchor (a repeated root adds nothing to the union graph)."""
+    the anchor does not have repeats the anchor (a repeated root adds nothing to the union graph).  A job with user-defined
+    negative label edges has H hard-negative slots per anchor behind the positives' ([anchor, pos_1 .. pos_P, neg_1 .. neg_H]:
+    UserDefinedLabelsNodeAnchorBasedLinkPredictionTask merges their neighbourhoods into the sample too)."""
     graph: "object"                # HipBatch over the n_anchors * trees_per_anchor roots
     n_anchors: int
-    trees_per_anchor: int          # 1 + numPositiveSamples
+    trees_per_anchor: int          # 1 + positive slots + hard-negative slots
     anchor_ids: np.ndarray         # int64 [n_anchors] host
     n_pos: np.ndarray              # int64 [n_anchors] host: sampled positives per anchor (>= 1)
     pos_rows: torch.Tensor         # int64 [sum(n_pos)] device: positions of the real positives in the root list, anchor-major
     root_ids: torch.Tensor         # int64 [n_anchors * trees_per_anchor] device: global ids of the root list
     root_index: Optional[torch.Tensor] = None  # int64 [n_anchors * trees_per_anchor] device: the roots' rows of model(graph)
+    n_neg: Optional[np.ndarray] = None         # int64 [n_anchors] host: sampled hard negatives per anchor (None: none)
+    neg_rows: Optional[torch.Tensor] = None    # int64 [sum(n_neg)] device: their positions in the root list, anchor-major
 
     @property
     def root_nodes(self):
         from .batches import Node
         return [Node(type="node", id=int(v)) for v in self.anchor_ids.tolist()]
+
+
+def nablp_label_rows(n_pos, n_neg, num_positives: int, num_hard_negatives: int) -> Tuple[np.ndarray, np.ndarray]:
+    """positions of the real positives and of the real hard negatives in the anchor-major root list of a link-prediction
+    batch ([anchor, P positive slots, H hard-negative slots] per anchor): anchor i's positive j < n_pos[i] is root
+    i * T + 1 + j, its hard negative k < n_neg[i] is root i * T + 1 + P + k, T = 1 + P + H.  -> (pos_rows, neg_rows), int64,
+    anchor-major"""
+    P, T = int(num_positives), 1 + int(num_positives) + int(num_hard_negatives)
+
+    def rows(k, first: int) -> np.ndarray:
+        k = np.asarray(k, dtype=np.int64)
+        return (np.repeat(np.arange(k.size, dtype=np.int64) * T + first - (np.cumsum(k) - k), k)
+                + np.arange(int(k.sum()), dtype=np.int64))
+    return rows(n_pos, 1), rows(n_neg, 1 + P)
 
 
 class ResidentGraph:
@@ -621,20 +639,68 @@ class ResidentGraph:
                                 root_ids=chunk)
 
     # ---- link-prediction training batches (the homogeneous NABLP trainer's in-HBM route)
+    def nablp_label_lists(self) -> Dict[str, str]:
+        """{"pos" | "neg": the engine's label edge list} of a job whose preprocessed metadata names user-defined label edges
+        (positiveEdgeInfo / negativeEdgeInfo), loaded once with the sampler job's own calls (subgraph_sampler._run_nablp);
+        {} for a job without them"""
+        lists = getattr(self, "_label_lists", None)
+        if lists is None:
+            lists = {}
+            if getattr(self, "cfg", None) is not None:
+                from .subgraph_sampler import load_label_edge_table
+                em = self.cfg.preprocessed_metadata.edges[0]
+                for name, info in (("pos", em.positive_edge_info), ("neg", em.negative_edge_info)):
+                    if info is not None:
+                        self.engine.load_label_edges(name, self.engine.n_nodes, *load_label_edge_table(self.cfg, info))
+                        lists[name] = name
+            self._label_lists = lists
+        return lists
+
+    def nablp_slots(self, num_positives: int) -> Tuple[int, int]:
+        """(positive slots P, hard-negative slots H) per anchor: (numPositiveSamples, 0), or — user-defined label edges —
+        numUserDefinedPositiveSamples where the positives come from a label list and numUserDefinedNegativeSamples hard
+        negatives where the metadata names negative label edges (_run_nablp's rule)"""
+        lists = self.nablp_label_lists()
+        P = int(self.cfg.num_user_defined_positive_samples) if "pos" in lists else int(num_positives)
+        H = int(self.cfg.num_user_defined_negative_samples) if "neg" in lists else 0
+        assert P > 0 and (H > 0 or "neg" not in lists), \
+            "numUserDefinedPositiveSamples / numUserDefinedNegativeSamples must be > 0 where user-defined label edges are given"
+        return P, H
+
+    def _main_roots(self, anchors: torch.Tensor, P: int, H: int):
+        """(roots [b * (1 + P + H)] anchor-major, counts [2 b]) of a batch of anchors (engine.nablp_main_roots)"""
+        lists = self.nablp_label_lists()
+        if not hasattr(self.engine, "nablp_main_roots"):
+            # an engine that only samples (the CPU dispatch tests' stand-in): the composition the library call replaces
+            assert not lists and H == 0
+            pos, cnt = self.engine.sample_positives(anchors, P, sampling_seed=self.seed)
+            a2 = anchors.view(-1, 1)
+            ar = torch.arange(P, device=anchors.device).view(1, P)
+            grouped = torch.where(ar < cnt.view(-1, 1), pos.view(-1, P), a2.expand(-1, P))
+            return (torch.cat([a2, grouped], dim=1).reshape(-1).contiguous(),
+                    torch.cat([cnt, torch.zeros_like(cnt)]).to(torch.int32))
+        return self.engine.nablp_main_roots(anchors, P, H, sampling_seed=self.seed, pos_label_edges=lists.get("pos"),
+                                            neg_label_edges=lists.get("neg"))
+
     def nablp_anchor_order(self, num_positives: int) -> Tuple[np.ndarray, np.ndarray]:
         """(anchors, positives per anchor) of the main samples in the order the TFRecord route reads them: the sampler
         writes one NodeAnchorBasedLinkPredictionSample per node with at least one sampled positive and a neighbourhood of
         its own, in ascending id order, capped by numMaxTrainingSamplesToOutput (subgraph_sampler._run_nablp;
-        NodeAnchorBasedLinkPredictionTask.scala:186-194), into part files that are read in permuted order"""
+        NodeAnchorBasedLinkPredictionTask.scala:186-194), into part files that are read in permuted order.  With
+        user-defined label edges the positives (and hard negatives) are those lists' and a neighbourhood of its own is not
+        asked of an anchor: that task joins against the RootedNodeNeighborhood view, which has the neighbourless nodes too."""
         ids = self.node_ids
+        P, H = self.nablp_slots(num_positives)
         cnt = np.zeros(self.n, dtype=np.int64)
+        self._n_neg_of = np.zeros(self.n, dtype=np.int64)  # sampled hard negatives per node (nablp_batches reads it)
         step = 1 << 20
         for lo in range(0, ids.size, step):  # (one pass over the nodes at setup; the positives themselves are re-drawn per batch)
             chunk = ids[lo:lo + step]
             r32 = torch.from_numpy(chunk.astype(np.uint32).view(np.int32)).to(self.device)
-            _, c = self.engine.sample_positives(r32, num_positives, sampling_seed=self.seed)
-            cnt[chunk] = c.cpu().numpy()
-        emit = ids[(cnt[ids] > 0) & self.has_in_edge[ids]]
+            _, c = self._main_roots(r32, P, H)
+            c = c.cpu().numpy().reshape(2, -1)
+            cnt[chunk], self._n_neg_of[chunk] = c[0], c[1]
+        emit = ids[cnt[ids] > 0] if self.nablp_label_lists() else ids[(cnt[ids] > 0) & self.has_in_edge[ids]]
         limit = self.cfg.num_max_training_samples_to_output
         if limit > 0:
             emit = emit[:limit]
@@ -645,49 +711,41 @@ class ResidentGraph:
                       loop: bool = False) -> Iterator[HbmNablpBatch]:
         """consecutive batches of `batch_size` anchors (`ids`, with `n_pos` positives each) sampled in HBM"""
         from itertools import cycle
-        P, T = int(num_positives), 1 + int(num_positives)
+        P, H = self.nablp_slots(num_positives)
+        T = 1 + P + H
         spans = [(lo, min(lo + batch_size, ids.size)) for lo in range(0, ids.size, batch_size)]
         if self.world > 1 and spans:
             # rank r takes batches r, r + world, ...; every rank the same number (a short rank wraps around: the gradient
             # all-reduce of DistributedDataParallel — and a hash-partitioned graph's exchanges — need equal step counts)
             per_rank = -(-len(spans) // self.world)
             spans = [spans[(self.rank + k * self.world) % len(spans)] for k in range(per_rank)]
-        ar = torch.arange(P, device=self.device).view(1, P)
         for lo, hi in (cycle(spans) if (loop and spans) else spans):
-            chunk, k = ids[lo:hi], n_pos[lo:hi]
+            chunk, k = ids[lo:hi], np.asarray(n_pos[lo:hi], dtype=np.int64)
             anchors = torch.from_numpy(chunk.astype(np.uint32).view(np.int32)).to(self.device)
-            pos, cnt = self.engine.sample_positives(anchors, P, sampling_seed=self.seed)
-            a2 = anchors.view(-1, 1)
-            grouped = torch.where(ar < cnt.view(-1, 1), pos.view(-1, P), a2.expand(-1, P))
-            roots = torch.cat([a2, grouped], dim=1).reshape(-1).contiguous()
+            roots, _ = self._main_roots(anchors, P, H)
             hb, ri = self.train_graph(roots, pad_to=batch_size * T)
-            k64 = np.asarray(k, dtype=np.int64)
-            # rows of the positives in the anchor-major root list: i * T + 1 + j for j < k[i]
-            rows = (np.repeat(np.arange(k64.size, dtype=np.int64) * T + 1 - (np.cumsum(k64) - k64), k64)
-                    + np.arange(int(k64.sum()), dtype=np.int64))
-            yield HbmNablpBatch(graph=hb, n_anchors=int(chunk.size), trees_per_anchor=T, anchor_ids=chunk,
-                                n_pos=np.asarray(k, dtype=np.int64),
-                                pos_rows=torch.from_numpy(rows.astype(np.int64)).to(self.device),
-                                root_ids=roots.to(torch.int64) & 0xFFFFFFFF, root_index=ri)
+            kn = self._n_neg_of[chunk] if H else np.zeros(chunk.size, dtype=np.int64)
+            pos_rows, neg_rows = nablp_label_rows(k, kn, P, H)
+            yield HbmNablpBatch(graph=hb, n_anchors=int(chunk.size), trees_per_anchor=T, anchor_ids=chunk, n_pos=k,
+                                pos_rows=torch.from_numpy(pos_rows).to(self.device),
+                                root_ids=roots.to(torch.int64) & 0xFFFFFFFF, root_index=ri,
+                                n_neg=kn if H else None, neg_rows=torch.from_numpy(neg_rows).to(self.device) if H else None)
 
     def nablp_root_batches(self, ids: np.ndarray, n_pos: np.ndarray, batch_size: int, num_positives: int):
-        """the ROOT side of nablp_batches only — (main roots anchor-major, positives per anchor, anchor ids) per batch, no
-        batch graph built: what the library's link-prediction training plan takes (engine.NablpTrainPlan samples and
+        """the ROOT side of nablp_batches only — (main roots anchor-major, positives per anchor [then, with hard-negative
+        slots, hard negatives per anchor: the plan's two-half count list], anchor ids) per batch, no batch graph built: what the library's link-prediction training plan takes (engine.NablpTrainPlan samples and
         collates inside its step); same anchors, positives and order as nablp_batches — and, in a world, the same rank
         striding: a rank's plan route and its autograd route see the same batches, in the same number on every rank"""
-        P = int(num_positives)
+        P, H = self.nablp_slots(num_positives)
         spans = [(lo, min(lo + batch_size, ids.size)) for lo in range(0, ids.size, batch_size)]
         if self.world > 1 and spans:  # (as nablp_batches: batches r, r + world, ..., a short rank wraps around)
             per_rank = -(-len(spans) // self.world)
             spans = [spans[(self.rank + k * self.world) % len(spans)] for k in range(per_rank)]
-        ar = torch.arange(P, device=self.device).view(1, P)
         for lo, hi in spans:
             chunk = ids[lo:hi]
             anchors = torch.from_numpy(chunk.astype(np.uint32).view(np.int32)).to(self.device)
-            pos, cnt = self.engine.sample_positives(anchors, P, sampling_seed=self.seed)
-            a2 = anchors.view(-1, 1)
-            grouped = torch.where(ar < cnt.view(-1, 1), pos.view(-1, P), a2.expand(-1, P))
-            yield torch.cat([a2, grouped], dim=1).reshape(-1).contiguous(), cnt.to(torch.int32).contiguous(), chunk
+            roots, cnt = self._main_roots(anchors, P, H)
+            yield roots, (cnt if H else cnt[: chunk.size]), chunk
 
     def random_negative_root_batches(self, batch_size: int):
         """the roots of random_negative_batches, batch by batch, forever (no batch graph built); rank-strided as they are"""

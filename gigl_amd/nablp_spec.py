@@ -167,33 +167,37 @@ def _infer_task_inputs_hbm(model: nn.Module, main_batch, random_neg_batch, shoul
     """infer_task_inputs over batches sampled in HBM (hbm.HbmNablpBatch + the random-negative HbmTrainBatch): the same
     embeddings, scores and ids as over the collated TFRecord batches of the same anchors — the batch graphs hold the
     same nodes and edges — with every index already on the device: no per-root host loop, no id dictionaries.  Hard
-    negatives come from user-defined label edges only, which take the TFRecord route."""
+    negatives (user-defined negative label edges) are rows of the main batch's root list like the positives
+    (main_batch.neg_rows); a batch without them has none."""
     inner = model.module if isinstance(model, torch.nn.parallel.DistributedDataParallel) else model
     decoder = inner.decode
     cet = 0
     hb = main_batch.graph
     ri = main_batch.root_index if main_batch.root_index is not None else hb.root_local.long()
-    roots_emb = model(hb)[ri]                                        # [B * (1 + P), d], anchor-major
+    roots_emb = model(hb)[ri]                                        # [B * (1 + P + H), d], anchor-major
     d = int(roots_emb.shape[1])
     query = roots_emb.view(main_batch.n_anchors, main_batch.trees_per_anchor, d)[:, 0]
     pos_emb = roots_emb.index_select(0, main_batch.pos_rows)
     rn_emb = model(random_neg_batch.graph)[random_neg_batch.root_node_indices]
     empty = torch.zeros((0,), dtype=torch.float32, device=device)
-    neg_emb = torch.zeros((0, d), device=device)
+    has_neg = main_batch.neg_rows is not None
+    neg_emb = roots_emb.index_select(0, main_batch.neg_rows) if has_neg else torch.zeros((0, d), device=device)
     want_scores = should_eval or need_batch_scores
     rn_scores = decoder(query, rn_emb) if (want_scores and rn_emb.numel()) else empty
     n_pos = main_batch.n_pos.tolist()
     batch_scores: List[Dict[int, BatchScores]] = []
     if want_scores:
-        batch_scores = _per_root_scores(decoder, query, pos_emb, neg_emb, n_pos, [0] * len(n_pos), rn_scores, cet, empty)
+        n_neg = main_batch.n_neg.tolist() if has_neg else [0] * len(n_pos)
+        batch_scores = _per_root_scores(decoder, query, pos_emb, neg_emb, n_pos, n_neg, rn_scores, cet, empty)
     rep_t = torch.from_numpy(main_batch.n_pos).to(device)
     rep_query = query.repeat_interleave(rep_t, dim=0, output_size=int(main_batch.pos_rows.numel()))
-    cand = torch.cat((pos_emb, rn_emb.reshape(-1, d)))
+    cand = torch.cat((pos_emb, neg_emb, rn_emb.reshape(-1, d))) if has_neg else torch.cat((pos_emb, rn_emb.reshape(-1, d)))
     anchor_ids = main_batch.root_ids.view(main_batch.n_anchors, main_batch.trees_per_anchor)[:, 0]
     combined = BatchCombinedScores(
         repeated_candidate_scores=decoder(rep_query, cand) if rep_query.numel() else empty,
         positive_ids=main_batch.root_ids.index_select(0, main_batch.pos_rows),
-        hard_neg_ids=torch.zeros((0,), dtype=torch.int64, device=device),
+        hard_neg_ids=(main_batch.root_ids.index_select(0, main_batch.neg_rows) if has_neg
+                      else torch.zeros((0,), dtype=torch.int64, device=device)),
         random_neg_ids=torch.from_numpy(np.asarray(random_neg_batch.root_ids, dtype=np.int64)).to(device),
         repeated_query_ids=anchor_ids.repeat_interleave(rep_t, output_size=int(main_batch.pos_rows.numel())),
         num_unique_query_ids=int(main_batch.n_anchors))
@@ -612,7 +616,8 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         """-> {split: (anchors, positives per anchor)} when this job's training batches can be sampled in HBM from the
         resident graph, else None (the TFRecord route below).  In HBM: a homogeneous graph whose tables are readable,
         one process, a GraphSAGE encoder with an autograd forward over HipBatches, positives drawn from the graph's own
-        edges (user-defined label edges: TFRecord route) and NO split-generator output — a transductive link split
+        edges or — with hard negatives — from user-defined label edges (on a sharded graph those take the TFRecord route) and
+        NO split-generator output — a transductive link split
         rewrites every sample's neighbourhood per split (message-passing vs supervision edges), which only the split
         generator's files carry.  The anchors of a split and their order are those of the TFRecord route without split
         files: the sampler's main samples in file order, root id % 10 (0-7 train, 8 val, 9 test), fewer than 100
@@ -627,14 +632,15 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         rank, world = _rank_world()
         if cfg.is_heterogeneous or device is None or device.type != "cuda" or \
                 route_of(cfg, self._kwargs) != "hbm" or not (encoder_trains_over_hip_batches(inner.encoder) or
-                                                             encoder_trains_over_graph_data(inner.encoder)) or \
-                em.positive_edge_info is not None or em.negative_edge_info is not None:
+                                                             encoder_trains_over_graph_data(inner.encoder)):
             return None
         # WORLD_SIZE > 1 (round 5; training_process.py:86-119: DDP around the model, the ranks split the batches): trainerArgs
         # hbm_graph = "replica" (default: the whole graph on every rank) | "sharded" (rank r holds the in-edge rows and
         # feature rows of the nodes with id % world == r — configs[4] on a graph larger than one GPU; a batch's remote
         # neighbours and rows arrive through the staged sharded plan, the supervision edges stay a replica)
         want_shards = str(self._kwargs.get("hbm_graph", "replica")).lower() == "sharded" and world > 1
+        if want_shards and (em.positive_edge_info is not None or em.negative_edge_info is not None):
+            return None  # (user-defined label edge lists are a replica matter: a sharded graph with them takes the TFRecord route)
         if any((cfg.dataset_split_uri(sp) and tfrecord_files(cfg.dataset_split_uri(sp))) for sp in ("train", "val", "test")):
             return None
         try:
@@ -905,11 +911,12 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         n_rn = self.random_negative_sample_batch_size
         if self._eval_in_plan():
             n_rn = max(n_rn, self.random_negative_sample_batch_size_for_evaluation)
+        P, H = res.nablp_slots(cfg.num_positive_samples)  # (user-defined label edges: their own slot counts, hard negatives)
         try:
             return (NablpTrainPlan if sage else GatEdgeNablpTrainPlan if gat_edge else GatNablpTrainPlan)(
-                res.engine, enc, self.main_sample_batch_size, cfg.num_positive_samples,
+                res.engine, enc, self.main_sample_batch_size, P,
                 n_rn, res.fanouts, temperature=float(tasks[0].loss._temperature or 0.0),
-                remove_accidental_hits=bool(tasks[0].loss._remove_accidental_hits), **optim)
+                remove_accidental_hits=bool(tasks[0].loss._remove_accidental_hits), num_hard_negatives=H, **optim)
         except (NotImplementedError, GiglError):
             return None
 

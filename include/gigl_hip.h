@@ -88,6 +88,11 @@ int32_t gigl_ctx_set_stream(gigl_ctx* ctx, void* hip_stream);
  * points create such a plan the first time a batch overflows the regular one and redo the batch through it — the
  * reference's collate has no such bound (rooted_node_neighborhood_data_loader.py:78-158). */
 int32_t gigl_ctx_set_wide_workspaces(gigl_ctx* ctx, int32_t on);
+/* Link-prediction training plans created on this ctx AFTER the call (gigl_nablp_train_plan_create,
+ * gigl_gat_nablp_train_plan_create, with or without edge features) carry num_hard_negatives hard-negative slots per
+ * anchor: see "HARD NEGATIVES" at gigl_nablp_train_plan_create for what the step's arguments then mean.  0 restores the
+ * plan without them.  num_hard_negatives outside [0, GIGL_MAX_FANOUT] is refused. */
+int32_t gigl_ctx_set_lp_hard_negatives(gigl_ctx* ctx, int32_t num_hard_negatives);
 int32_t gigl_ctx_synchronize(gigl_ctx* ctx);
 /* pre-size the ctx scratch arena (bytes); grows on demand otherwise (grow = hipMalloc, so
  * warm up once before capturing a hipGraph) */
@@ -377,6 +382,16 @@ int32_t gigl_sample_positives(gigl_ctx* ctx, gigl_graph* g_out, const uint32_t* 
 int32_t gigl_sample_out_neighbors(gigl_ctx* ctx, gigl_graph* g_out, const uint32_t* roots, int32_t b,
                                   int32_t f, int32_t sampling_seed, int32_t counter, int32_t mode, uint32_t* pos,
                                   int32_t* cnt);
+/* the main batch's root list of a link-prediction training plan in one call: P out-neighbours of every anchor drawn from
+ * g_pos with counter 3 and H from g_neg with counter 4 (gigl_sample_out_neighbors' rule and kernels), written
+ * anchor-major as roots_out DEVICE uint32 [b * (1 + P + H)] = (anchor, its P positive slots, its H hard-negative
+ * slots; an empty slot repeats the anchor) with cnt_out DEVICE int32 [2 b] = positives per anchor, then hard negatives
+ * per anchor.  anchors: DEVICE uint32 [b]; an anchor of 0xFFFFFFFF yields a row of 0xFFFFFFFF with counts 0.  g_neg may
+ * be NULL (every hard-negative slot empty, counts 0); H = 0: a [b * (1 + P)] list, the second half of cnt_out zero.
+ * Enqueued on the ctx's stream; no host read. */
+int32_t gigl_nablp_main_roots(gigl_ctx* ctx, const uint32_t* anchors, int32_t b, gigl_graph* g_pos, int32_t P,
+                              gigl_graph* g_neg /* may be NULL */, int32_t H, int32_t sampling_seed, int32_t mode,
+                              uint32_t* roots_out, int32_t* cnt_out);
 
 /* ---- sampled trees -> serialized training samples in TFRecord framing, encoded on the device.
  *      Replaces the per-root assembly, hydration, proto cast and record writer of the Spark sampler:
@@ -1312,7 +1327,18 @@ int32_t gigl_sage_train_plan_moments(gigl_sage_train_plan* plan, int32_t layer, 
  *   reports a NaN loss.  All work is enqueued on the ctx's stream — or, since round 6, on private streams forked from it and
  *   joined back into it before the step's last launch (the random negatives' encode; the main batch's weight gradients of
  *   the GraphSAGE encoder): nothing a caller synchronises differently.  Environment, read at plan creation (off-switches
- *   of the private streams): GIGL_LP_FORK=0 (none), GIGL_LP_WGRAD_STREAM=0 (weight gradients stay in the chain). */
+ *   of the private streams): GIGL_LP_FORK=0 (none), GIGL_LP_WGRAD_STREAM=0 (weight gradients stay in the chain).
+ * HARD NEGATIVES (a plan created while gigl_ctx_set_lp_hard_negatives(ctx, H) holds H > 0; every kind of link-prediction
+ *   plan; _step, _step2, _eval and _adopt): main_roots is DEVICE uint32 [b_anchors * T], T = 1 + P + H, anchor-major
+ *   (anchor, its P positive slots, its H hard-negative slots; an empty slot repeats the anchor), and pos_cnt is DEVICE
+ *   int32 [2 * b_anchors]: words [0, b) the positives per anchor, words [b, 2b) the hard negatives per anchor
+ *   (gigl_nablp_main_roots writes both).  The candidates are cat(positives, hard negatives, random negatives) as in the
+ *   reference's infer_task_inputs: with Q = b P, columns [0, Q) are the positives, column Q + i H + k is hard negative k
+ *   of anchor i, the random negatives start at Q + b H.  A hard-negative column takes part when its anchor is present,
+ *   k < its count, its id is not 0xFFFFFFFF and its tree fitted — whether or not the anchor has a positive; any other is
+ *   masked (no score, no gradient).  The same-query mask covers the positives' block, the accidental-hit mask every column.
+ *   The evaluation still ranks against the random negatives only (the reference's validate); its loss has every column.
+ *   H = 0 is the plan described above, launch for launch. */
 typedef struct gigl_nablp_train_plan gigl_nablp_train_plan;
 int32_t gigl_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, int32_t b_anchors,
                                      int32_t num_positives, int32_t n_random_negatives, const int32_t* fanouts, int32_t hops,
