@@ -69,6 +69,7 @@ SYMBOLS = [
     "gigl_sage_train_plan_create", "gigl_sage_train_plan_step", "gigl_sage_train_plan_step2", "gigl_sage_train_plan_loss", "gigl_sage_train_plan_destroy",
     "gigl_nablp_train_plan_create", "gigl_nablp_train_plan_step", "gigl_nablp_train_plan_step2", "gigl_gat_nablp_train_plan_create", "gigl_gat_nablp_train_plan_grads", "gigl_gat_nablp_train_plan_set_edge_features", "gigl_gat_nablp_train_plan_edge_grads", "gigl_nablp_train_plan_loss", "gigl_nablp_train_plan_destroy", "gigl_nablp_train_plan_grads", "gigl_nablp_train_plan_set_clip_grad_norm", "gigl_nablp_train_plan_set_constant_lr", "gigl_nablp_train_plan_grad_norm",
     "gigl_lp_rank_metrics", "gigl_nablp_train_plan_eval", "gigl_nablp_train_plan_adam_steps",
+    "gigl_sage_train_plan_set_dropout", "gigl_nablp_train_plan_set_dropout", "gigl_dropout_mask",
 ]
 
 KERNEL_IDS = {
@@ -442,6 +443,9 @@ def load() -> C.CDLL:
         "gigl_nablp_train_plan_set_clip_grad_norm": [vp, C.c_float],
         "gigl_nablp_train_plan_set_constant_lr": [vp, C.c_float, i32],
         "gigl_nablp_train_plan_grad_norm": [vp, vp],
+        "gigl_sage_train_plan_set_dropout": [vp, C.c_float, C.c_uint64],
+        "gigl_nablp_train_plan_set_dropout": [vp, C.c_float, C.c_uint64],
+        "gigl_dropout_mask": [vp, C.c_uint64, C.c_uint32, i32, i32, i64, i32, C.c_float, vp],
         "gigl_lp_rank_metrics": [vp, vp, i64, i32, i32, vp, i32, i32, vp, P(i32), i32, vp],
         "gigl_nablp_train_plan_adam_steps": [vp, vp],
         "gigl_nablp_train_plan_eval": [vp, vp, vp, vp, i32, i32, P(i32), i32, vp, vp],

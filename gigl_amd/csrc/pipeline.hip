@@ -10,6 +10,7 @@
 //       (.../node_classification_modeling_task_spec.py:176-187),
 //   fed by process_raw_pyg_samples_and_collate_fn (rooted_node_neighborhood_data_loader.py:161-241).
 #include "common.h"
+#include "philox.h"
 #include "step_parts.h"
 #include "wave_reduce.h"
 
@@ -639,6 +640,91 @@ __global__ __launch_bounds__(256) void relu_mask_kernel(float* __restrict__ dy, 
   const int64_t n = (int64_t)(*n_rows_dev) * width;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     if (!(y[i] > 0.f)) dy[i] = 0.f;
+}
+
+// ---- dropout between the training plans' layers (include/gigl_hip.h: gigl_sage_train_plan_set_dropout; philox.h)
+
+// rows a kernel may touch: the device count, bounded by the buffer's capacity
+__device__ __forceinline__ int64_t rows_below_cap(const int32_t* __restrict__ n_rows_dev, int64_t rows_cap) {
+  const int64_t n = *n_rows_dev;
+  return n < 0 ? 0 : (n > rows_cap ? rows_cap : n);
+}
+
+// h[r][c] = kept ? h[r][c] * scale : 0, in place on a layer's activated output, rows below *n_rows_dev.  A lane takes the four
+// columns of one Philox block: one 16-byte load and store when the rows are whole float4s (width % 4 == 0), else — rows
+// that do not start on 16 bytes — the block's columns one by one (the last block of a row may hold fewer than four).
+// *step_dev is read BEFORE the step's loss launch moves it on: the plan's count of applied steps.  A row takes 2^lg lanes
+// (lg = dropout_lanes_log2: the blocks of a row rounded up to a power of two, so that row and block come from a shift and
+// a mask — a 64-bit division per block cost more than the block's ten rounds)
+__global__ __launch_bounds__(256) void dropout_rows_kernel(float* __restrict__ h, const int32_t* __restrict__ n_rows_dev,
+                                                           int64_t rows_cap, int width, const int32_t* __restrict__ step_dev,
+                                                           DropoutMask m, int lg) {
+  const int groups = (width + 3) >> 2;
+  const int64_t n = rows_below_cap(n_rows_dev, rows_cap) << lg;
+  const uint32_t step = (uint32_t)*step_dev;
+  const bool whole = (width & 3) == 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i >> lg;
+    const int g = (int)(i & ((1 << lg) - 1));
+    if (g >= groups) continue;
+    uint32_t w[4];
+    gigl_dropout_words(m, (uint32_t)r, (uint32_t)g, step, w);
+    float* q = h + r * width + 4 * g;
+    if (whole) {
+      float4 v = *reinterpret_cast<const float4*>(q);
+      v.x = w[0] >= m.thresh ? v.x * m.scale : 0.f;
+      v.y = w[1] >= m.thresh ? v.y * m.scale : 0.f;
+      v.z = w[2] >= m.thresh ? v.z * m.scale : 0.f;
+      v.w = w[3] >= m.thresh ? v.w * m.scale : 0.f;
+      *reinterpret_cast<float4*>(q) = v;
+    } else {
+      const int cols = width - 4 * g < 4 ? width - 4 * g : 4;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < cols) q[k] = w[k] >= m.thresh ? q[k] * m.scale : 0.f;
+    }
+  }
+}
+
+// dy = y > 0 ? dy * scale : 0 — the rectifier's and the dropout's backward in one pass: a dropped element's output is 0 as a
+// rectified one's, a kept one's gradient carries the forward's scale.  Rows below *n_rows_dev; whole: width % 4 == 0 and
+// both buffers start on 16 bytes (dy may be carved out of a block behind tensors of any size): 16-byte accesses
+__global__ __launch_bounds__(256) void dropout_relu_mask_kernel(float* __restrict__ dy, const float* __restrict__ y,
+                                                                const int32_t* __restrict__ n_rows_dev, int64_t rows_cap,
+                                                                int width, float scale, int whole) {
+  const int64_t n = rows_below_cap(n_rows_dev, rows_cap) * width;
+  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  if (whole) {
+    for (int64_t i = t0; i < (n >> 2); i += stride) {
+      const float4 a = reinterpret_cast<const float4*>(y)[i];
+      float4 g = reinterpret_cast<const float4*>(dy)[i];
+      g.x = a.x > 0.f ? g.x * scale : 0.f;
+      g.y = a.y > 0.f ? g.y * scale : 0.f;
+      g.z = a.z > 0.f ? g.z * scale : 0.f;
+      g.w = a.w > 0.f ? g.w * scale : 0.f;
+      reinterpret_cast<float4*>(dy)[i] = g;
+    }
+  } else {
+    for (int64_t i = t0; i < n; i += stride) dy[i] = y[i] > 0.f ? dy[i] * scale : 0.f;
+  }
+}
+
+// keep[r][c] = 1 where the mask keeps element (r, c) (gigl_dropout_mask): a lane per Philox block, 2^lg lanes per row
+__global__ __launch_bounds__(256) void dropout_keep_kernel(uint8_t* __restrict__ keep, int64_t rows, int width, uint32_t step,
+                                                           DropoutMask m, int lg) {
+  const int groups = (width + 3) >> 2;
+  const int64_t n = rows << lg;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i >> lg;
+    const int g = (int)(i & ((1 << lg) - 1));
+    if (g >= groups) continue;
+    uint32_t w[4];
+    gigl_dropout_words(m, (uint32_t)r, (uint32_t)g, step, w);
+    const int cols = width - 4 * g < 4 ? width - 4 * g : 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < cols) keep[r * width + 4 * g + k] = w[k] >= m.thresh ? 1 : 0;
+  }
 }
 
 __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ w, int rows, int cols, float* __restrict__ wt) {
@@ -1407,6 +1493,9 @@ struct SageTrainShared {
   float* wt_l[GIGL_MAX_HOPS] = {nullptr};
   bool bwd_gather = false;  // layers >= 1 hand their input gradient down by the transposed gather (train_bwd_gather)
   float lr = 0.f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, wd = 0.f;
+  // dropout after every activated layer (gigl_*_train_plan_set_dropout; 0: none, the launches of a plan without it)
+  float drop_p = 0.f;
+  uint64_t drop_seed = 0;
 };
 
 // one encode's state
@@ -1528,8 +1617,24 @@ int32_t sage_enqueue_graph(const SageTrainShared& s, const SageTrainEnc& e, gigl
   return rc;
 }
 
-// forward over workspace p's batch graph, on ctx: every layer's operand a[l] and output h[l] are kept
-int32_t sage_enc_forward(gigl_ctx* ctx, const SageTrainShared& s, const SageTrainEnc& e, const gigl_sage_plan* p) {
+// launch blocks of 256 lanes over n items, a grid-stride loop beyond 4096 of them
+unsigned blocks_256(int64_t n) {
+  const int64_t blocks = (n + 255) / 256;
+  return (unsigned)(blocks > 4096 ? 4096 : (blocks < 1 ? 1 : blocks));
+}
+
+// lanes per row of the dropout kernels, as a power of two: the row's Philox blocks (four columns each) rounded up
+int dropout_lanes_log2(int width) {
+  int lg = 0;
+  while ((1 << lg) < (width + 3) / 4) ++lg;
+  return lg;
+}
+
+// forward over workspace p's batch graph, on ctx: every layer's operand a[l] and output h[l] are kept.  train: a training
+// step's forward — with s.drop_p > 0 every activated output is masked and scaled in place (dropout_rows_kernel: the mask of
+// this `encode` at the step *step_dev counts); an evaluation's forward (train == false) runs without
+int32_t sage_enc_forward(gigl_ctx* ctx, const SageTrainShared& s, const SageTrainEnc& e, const gigl_sage_plan* p, bool train,
+                         int encode, const int32_t* step_dev) {
   const int L = s.L;
   int32_t rc = GIGL_OK;
   const int32_t* n_local = p->leaf_global ? (L >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (L - 2) : p->zero_dev) : nullptr;
@@ -1546,6 +1651,13 @@ int32_t sage_enc_forward(gigl_ctx* ctx, const SageTrainShared& s, const SageTrai
     rc = gigl_linear(ctx, e.a[l], s.w[l], s.bias[l], n_rows, e.rows_cap[l], 2 * d, s.dims[l + 1],
                      (l < L - 1 || s.act_last) ? 1 : 0, e.h[l]);
     if (rc != GIGL_OK) return rc;
+    if (train && s.drop_p > 0.f && (l < L - 1 || s.act_last)) {
+      const int width = s.dims[l + 1];
+      const int lg = dropout_lanes_log2(width);
+      hipLaunchKernelGGL(dropout_rows_kernel, dim3(blocks_256(e.rows_cap[l] << lg)), dim3(256), 0, ctx->stream, e.h[l], n_rows,
+                         e.rows_cap[l], width, step_dev, gigl_dropout_mask_args(s.drop_seed, s.drop_p, encode, l), lg);
+      GIGL_HIP_CHECK(ctx, hipGetLastError());
+    }
   }
   return GIGL_OK;
 }
@@ -1568,10 +1680,23 @@ int32_t sage_enc_backward(gigl_ctx* ctx, const SageTrainShared& s, const SageTra
       if (blocks > 4096) blocks = 4096;
       hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, st, e.dh[l], (const float*)e.h[l], n_rows, n_out);
     };
-    if (wctx) {
+    // with dropout the mask carries the kept elements' scale: it runs first, in both paths, and the weight gradient takes
+    // the masked rows as they are (the masked READ of the unforked path below would lose the scale)
+    const bool drop = act && s.drop_p > 0.f;
+    auto drop_mask = [&]() {
+      const int whole = (n_out & 3) == 0 && (((uintptr_t)e.dh[l] | (uintptr_t)e.h[l]) & 15) == 0;
+      hipLaunchKernelGGL(dropout_relu_mask_kernel, dim3(blocks_256(e.rows_cap[l] * n_out / (whole ? 4 : 1))), dim3(256), 0, st,
+                         e.dh[l], (const float*)e.h[l], n_rows, e.rows_cap[l], n_out, 1.0f / (1.0f - s.drop_p), whole);
+    };
+    if (drop && !wctx) {
+      drop_mask();
+      rc = gigl_linear_weight_grad_parts(ctx, e.dh[l], e.a[l], nullptr, n_rows, e.rows_cap[l], n_out, 2 * d, e.part_w[l],
+                                         s.bias[l] ? e.part_b[l] : nullptr);
+    } else if (wctx) {
       // the mask first (the chain needs the masked rows anyway), then the gradient of the MASKED rows beside the chain: the
       // same products as the masked read of the unmasked rows
-      if (act) relu_mask();
+      if (drop) drop_mask();
+      else if (act) relu_mask();
       GIGL_HIP_CHECK(ctx, hipEventRecord(ev_w, st));
       GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(wctx->stream, ev_w, 0));
       rc = gigl_linear_weight_grad_parts(wctx, e.dh[l], e.a[l], nullptr, n_rows, e.rows_cap[l], n_out, 2 * d, e.part_w[l],
@@ -1582,7 +1707,7 @@ int32_t sage_enc_backward(gigl_ctx* ctx, const SageTrainShared& s, const SageTra
     }
     if (rc != GIGL_OK) return rc;
     if (l == 0) break;  // (the first layer's input is the feature table: no gradient)
-    if (act && !wctx) relu_mask();
+    if (act && !wctx && !drop) relu_mask();
     rc = gigl_linear(ctx, e.dh[l], s.wt_l[l], nullptr, n_rows, e.rows_cap[l], n_out, 2 * d, 0, da);
     if (rc != GIGL_OK) return rc;
     if (s.bwd_gather)
@@ -1784,6 +1909,7 @@ struct gigl_sage_train_plan : SageTrainShared {
   int32_t* n_valid_buf = nullptr;  // [0] real roots of the batch, [1] Adam's step counter, [2] sticky "a batch failed" (halt)
   float* loss_rows = nullptr;
   float* loss = nullptr;
+  bool stepped = false;  // a step has run: what the captured layers part launches is final (gigl_sage_train_plan_set_dropout)
   std::vector<void*> owned;
 };
 
@@ -1796,7 +1922,7 @@ int32_t train_enqueue_layers(gigl_sage_train_plan* t, int k) {
   const int L = t->L;
   hipStream_t st = ctx->stream;
   const SageTrainEnc& e = t->enc;
-  int32_t rc = sage_enc_forward(ctx, *t, e, p);
+  int32_t rc = sage_enc_forward(ctx, *t, e, p, true, 0, t->n_valid_buf + 1);
   if (rc != GIGL_OK) return rc;
   // ---- loss on the roots, its gradient into dh[L - 1]
   {
@@ -1915,6 +2041,7 @@ int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* t, const uint32_t* root
   if (mode == GIGL_MODE_REPLACE)
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "the training plan needs duplicate-free trees (no with-replacement mode)");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  t->stepped = true;
   hipStream_t st = ctx->stream;
   PlanRing& ring = t->ring;
   ring.reseed(PlanRing::TRAIN, sampling_seed, mode);
@@ -1980,6 +2107,38 @@ int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* t, const uint32_t* root
 }
 
 const float* gigl_sage_train_plan_loss(gigl_sage_train_plan* t) { return t ? t->loss : nullptr; }
+
+namespace {
+// the setters' shared half: the plan has not stepped (its layers part is captured with or without the dropout launches),
+// 0 <= p < 1
+int32_t sage_set_dropout(gigl_ctx* ctx, SageTrainShared& s, bool stepped, float p, uint64_t seed) {
+  GIGL_REQUIRE(ctx, !stepped, "dropout is set after create and before the first step (the step is captured)");
+  GIGL_REQUIRE(ctx, p >= 0.f && p < 1.f, "dropout: p must be in [0, 1)");  // (false for a NaN too)
+  s.drop_p = p;
+  s.drop_seed = seed;
+  return GIGL_OK;
+}
+}  // namespace
+
+int32_t gigl_sage_train_plan_set_dropout(gigl_sage_train_plan* t, float p, uint64_t seed) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  return sage_set_dropout(t->ctx, *t, t->stepped, p, seed);
+}
+
+int32_t gigl_dropout_mask(gigl_ctx* ctx, uint64_t seed, uint32_t step, int32_t encode, int32_t layer, int64_t rows, int32_t cols,
+                          float p, uint8_t* keep) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  GIGL_REQUIRE(ctx, (keep || rows == 0) && rows >= 0 && rows <= 0xFFFFFFFFll && cols >= 1, "bad mask shape / null output");
+  GIGL_REQUIRE(ctx, p >= 0.f && p < 1.f, "dropout: p must be in [0, 1)");
+  GIGL_REQUIRE(ctx, encode >= 0 && encode < (1 << 24) && layer >= 0 && layer < 256, "encode / layer outside the counter word");
+  if (rows == 0) return GIGL_OK;
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int lg = dropout_lanes_log2(cols);
+  hipLaunchKernelGGL(dropout_keep_kernel, dim3(blocks_256(rows << lg)), dim3(256), 0, ctx->stream, keep, rows, cols, step,
+                     gigl_dropout_mask_args(seed, p, encode, layer), lg);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
 
 int32_t gigl_sage_train_plan_resume(gigl_sage_train_plan* t) {
   if (!t) return GIGL_E_INVALID_ARG;
@@ -2430,10 +2589,10 @@ __global__ __launch_bounds__(256) void lp_unpack_scatter_kernel(const float* __r
 }
 
 // an encode's forward and the roots' embeddings; the random negatives' on the forked stream
-int32_t lp_forward(gigl_nablp_train_plan* t, int which) {
+int32_t lp_forward(gigl_nablp_train_plan* t, int which, bool train) {
   const SageTrainEnc& e = t->enc[which];
   gigl_ctx* ctx = which == 1 && t->fork ? t->actx : t->lctx;
-  const int32_t rc = sage_enc_forward(ctx, *t, e, e.base);
+  const int32_t rc = sage_enc_forward(ctx, *t, e, e.base, train, which, t->consts + 2);
   if (rc != GIGL_OK) return rc;
   hipLaunchKernelGGL(lp_take_norm_kernel, dim3((unsigned)((e.b + 3) / 4)), dim3(256), 0, ctx->stream, (const float*)e.h[t->L - 1],
                      (const int32_t*)e.base->un.root_local, e.b, t->dims[t->L], t->normalize, (const int32_t*)e.base->un.meta, e.emb,
@@ -2467,8 +2626,8 @@ int32_t lp_enqueue_graph(gigl_nablp_train_plan* t, int w, int32_t sampling_seed,
 }
 
 // the forward half of the layers part over workspace w: both encodes, the head's operands, the scores, the loss rows
-// (shared by the training step and gigl_nablp_train_plan_eval)
-int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w) {
+// (shared by the training step — train: with the plan's dropout — and gigl_nablp_train_plan_eval, which runs without)
+int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w, bool train) {
   gigl_ctx* ctx = t->lctx;
   hipStream_t st = ctx->stream;
   const int L = t->L, d = t->dims[L], Q = t->b * t->P, Cn = t->cand_cols();
@@ -2489,7 +2648,7 @@ int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w) {
     GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(t->actx->stream, t->ev_fork[0], 0));
   }
   for (int k = 0; k < 2; ++k) {
-    rc = t->kind == 1 ? gat_lp_forward(t, k) : lp_forward(t, k);
+    rc = t->kind == 1 ? gat_lp_forward(t, k) : lp_forward(t, k, train);
     if (rc != GIGL_OK) return rc;
   }
   if (t->fork) {
@@ -2516,7 +2675,7 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
   gigl_ctx* ctx = t->lctx;
   hipStream_t st = ctx->stream;
   const int L = t->L, d = t->dims[L], Q = t->b * t->P, Cn = t->cand_cols();
-  int32_t rc = lp_enqueue_forward(t, w);
+  int32_t rc = lp_enqueue_forward(t, w, true);
   if (rc != GIGL_OK) return rc;
   const gigl_sage_plan *pm = t->enc[0].base, *pr = t->enc[1].base;
   hipLaunchKernelGGL(lp_loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->row_loss, (const int32_t*)t->valid, Q,
@@ -2826,7 +2985,7 @@ int32_t gigl_nablp_train_plan_eval(gigl_nablp_train_plan* t, const uint32_t* mai
   GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, wk.ev_graph, 0));
   // (eager: no captured layers graph is made or invalidated — and none with a second branch, see gigl_nablp_train_plan_create)
   gigl_sage_plan* const held[2] = {t->enc[0].base, t->enc[1].base};
-  rc = lp_enqueue_forward(t, w);
+  rc = lp_enqueue_forward(t, w, false);
   const gigl_sage_plan *pm = wk.base[0], *pr = wk.base[1];
   for (int k = 0; k < 2; ++k) t->enc[k].base = held[k];
   if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
@@ -2869,6 +3028,14 @@ int32_t gigl_nablp_train_plan_set_clip_grad_norm(gigl_nablp_train_plan* t, float
   }
   t->clip.max_norm = max_norm;
   return GIGL_OK;
+}
+
+int32_t gigl_nablp_train_plan_set_dropout(gigl_nablp_train_plan* t, float p, uint64_t seed) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  if (t->kind != 0 && p != 0.f)
+    return gigl_fail(t->ctx, GIGL_E_UNSUPPORTED, "dropout: the GAT link-prediction plans have none (feature and attention "
+                                                 "dropout belong together there)");
+  return sage_set_dropout(t->ctx, *t, t->stepped, p, seed);
 }
 
 int32_t gigl_nablp_train_plan_set_constant_lr(gigl_nablp_train_plan* t, float factor, int32_t total_iters) {

@@ -481,6 +481,17 @@ class HipEngine:
               self._ctx)
         return roots[: b * (1 + P + H)], cnt[: 2 * b]
 
+    def dropout_mask(self, seed: int, step: int, encode: int, layer: int, rows: int, cols: int, p: float) -> torch.Tensor:
+        """the keep mask of a training plan's dropout (gigl_dropout_mask; the definition is in include/gigl_hip.h at
+        gigl_sage_train_plan_set_dropout): uint8 [rows, cols], 1 = kept, for the output of conv layer `layer` of encode
+        `encode` (0: the node-classification plan's and the link-prediction main batch's, 1: the random negatives') at the
+        step at which the plan's counter of applied steps reads `step`; kept elements are scaled by
+        float32(1) / (float32(1) - float32(p)).  Written on the engine's stream, no host read."""
+        keep = torch.empty((int(rows), int(cols)), dtype=torch.uint8, device=self.device)
+        check(self._lib.gigl_dropout_mask(self._ctx, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(encode), int(layer),
+                                          int(rows), int(cols), float(p), C.c_void_p(keep.data_ptr())), self._ctx)
+        return keep
+
     def load_label_edges(self, name: str, n: int, src, dst, feats=None) -> None:
         """a user-defined label edge list ("pos" / "neg": loadEdgeDataframeIntoSparkSql with EdgeUsageType.POS / NEG —
         never bidirectionalised) as CSR by source, plus its feature rows put in that graph's `col` order (several
@@ -1378,16 +1389,20 @@ class SageTrainPlan:
     matrix is training lin_l.weight and lin_r.weight)."""
 
     def __init__(self, eng: HipEngine, model, b: int, fanouts, lr: float = 0.01, weight_decay: float = 5e-4,
-                 betas=(0.9, 0.999), eps: float = 1e-8):
+                 betas=(0.9, 0.999), eps: float = 1e-8, dropout: Optional[float] = None, dropout_seed: int = 0):
+        """dropout: p of the dropout after every activated layer (None: model.dropout.p), drawn from the library's own
+        counter-based stream (HipEngine.dropout_mask reproduces a step's mask; torch's stream is another: a plan step and an
+        autograd step of the same job drop different elements of the same distribution); dropout_seed: its 64-bit seed"""
         assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
         L = len(fanouts)
         assert model.num_layers == L, "one hop per layer"
-        if not (model._plain and model.aggr == "mean" and not model.should_l2_normalize_embedding_layer_output
+        if not (model._plain_but_dropout and model.aggr == "mean" and not model.should_l2_normalize_embedding_layer_output
                 and model.feats_interaction is None and model.feature_embedding_layer is None
                 and all(c.lin_r is not None for c in model.conv_layers)):
-            raise NotImplementedError("the training plan runs plain mean-GraphSAGE layers (conv -> relu)")
+            raise NotImplementedError("the training plan runs plain mean-GraphSAGE layers (conv -> relu -> dropout)")
         self.eng, self.b, self.fanouts = eng, int(b), [int(f) for f in fanouts]
         self._lib = eng._lib
+        self._dropout = _plan_dropout(model, dropout, dropout_seed)
         self.w, self.bias = [], []
         self.load(model)
         self.dims = [int(self.w[0].shape[1]) // 2] + [int(w.shape[0]) for w in self.w]
@@ -1402,11 +1417,23 @@ class SageTrainPlan:
             check(self._lib.gigl_sage_train_plan_create(eng._ctx, eng._graph, eng._feat, self.b, fo, L, dims, w_arr, b_arr,
                                                         act_last, float(lr), float(betas[0]), float(betas[1]), float(eps),
                                                         float(weight_decay), C.byref(h)), eng._ctx)
+            try:
+                self._apply_dropout(h, self._lib.gigl_sage_train_plan_set_dropout)
+            except Exception:
+                self._lib.gigl_sage_train_plan_destroy(h)
+                raise
             return h
         self._create, self._adopt, self._destroy = create, self._lib.gigl_sage_train_plan_adopt, self._lib.gigl_sage_train_plan_destroy
         self.wide = False
         self._plan = create()
         self.loss = torch.zeros(1, dtype=torch.float32, device=eng.device)  # the last step's loss (device scalar)
+
+    def _apply_dropout(self, handle, setter) -> None:
+        """the dropout of a (re)created plan handle, before its first step (called inside create(), so that grow()'s wide
+        plan drops the same elements as the one it replaces)"""
+        p, seed = self._dropout
+        if p != 0.0:  # (0 = none; anything else is the library's to judge)
+            check(setter(handle, p, seed), self.eng._ctx)
 
     def load(self, model) -> None:
         """(re)read the model's parameters into the fused buffers the plan trains (in place when they exist)"""
@@ -1542,6 +1569,14 @@ class SageTrainPlan:
         self._create = None  # (drops the argument arrays it holds)
 
 
+def _plan_dropout(model, dropout: Optional[float], seed: int):
+    """(p, seed) of a training plan's dropout: p = `dropout`, or the model's own when that is None; 0 <= p < 1"""
+    p = float(model.dropout.p if dropout is None else dropout)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout must be in [0, 1) (got {p})")
+    return p, int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
 def pad_lp_batch(main_roots: torch.Tensor, pos_cnt: Optional[torch.Tensor], rn_roots: torch.Tensor, b: int, P: int, H: int,
                  n_rn: int):
     """a (short) link-prediction batch at the plan's capacity: main_roots int32 [na * T], T = 1 + P + H, -> [b * T] and
@@ -1571,13 +1606,16 @@ class NablpTrainPlan:
     def __init__(self, eng: HipEngine, model, b_anchors: int, num_positives: int, n_random_negatives: int, fanouts,
                  temperature: float = 0.07, remove_accidental_hits: bool = True, lr: float = 5e-3,
                  weight_decay: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8, clip_grad_norm: float = 0.0,
-                 lr_factor: float = 1.0, lr_total_iters: int = 0, num_hard_negatives: int = 0):
+                 lr_factor: float = 1.0, lr_total_iters: int = 0, num_hard_negatives: int = 0,
+                 dropout: Optional[float] = None, dropout_seed: int = 0):
+        """dropout, dropout_seed: as SageTrainPlan's (both encodes; evaluate() / eval_batch() run without dropout)"""
         assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
         L = len(fanouts)
         assert model.num_layers == L, "one hop per layer"
-        if not (model._plain and model.aggr == "mean" and model.feats_interaction is None
+        if not (model._plain_but_dropout and model.aggr == "mean" and model.feats_interaction is None
                 and model.feature_embedding_layer is None and all(c.lin_r is not None for c in model.conv_layers)):
-            raise NotImplementedError("the link-prediction training plan runs plain mean-GraphSAGE layers (conv -> relu)")
+            raise NotImplementedError("the link-prediction training plan runs plain mean-GraphSAGE layers (conv -> relu -> dropout)")
+        self._dropout = _plan_dropout(model, dropout, dropout_seed)
         self.eng, self.b, self.P, self.n_rn = eng, int(b_anchors), int(num_positives), int(n_random_negatives)
         self.H = int(num_hard_negatives)
         self.fanouts = [int(f) for f in fanouts]
@@ -1601,6 +1639,7 @@ class NablpTrainPlan:
                     float(eps), float(weight_decay), C.byref(h)), eng._ctx)
             try:
                 self._apply_optim_knobs(h)
+                self._apply_dropout(h, self._lib.gigl_nablp_train_plan_set_dropout)
             except Exception:
                 self._lib.gigl_nablp_train_plan_destroy(h)
                 raise
@@ -1614,6 +1653,7 @@ class NablpTrainPlan:
     load = SageTrainPlan.load
     store = SageTrainPlan.store
     grow = SageTrainPlan.grow
+    _apply_dropout = SageTrainPlan._apply_dropout
     step_checked = SageTrainPlan.step_checked
 
     @contextmanager
@@ -1772,10 +1812,17 @@ class GatNablpTrainPlan(NablpTrainPlan):
     def __init__(self, eng: HipEngine, model, b_anchors: int, num_positives: int, n_random_negatives: int, fanouts,
                  temperature: float = 0.07, remove_accidental_hits: bool = True, lr: float = 5e-3,
                  weight_decay: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8, clip_grad_norm: float = 0.0,
-                 lr_factor: float = 1.0, lr_total_iters: int = 0, num_hard_negatives: int = 0):
+                 lr_factor: float = 1.0, lr_total_iters: int = 0, num_hard_negatives: int = 0,
+                 dropout: Optional[float] = None, dropout_seed: int = 0):
         assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
         if not self._applies_to(eng, model) or len(fanouts) != 2:
             raise NotImplementedError(self._COVERS)
+        p = float(dropout or 0.0)  # (models_attn.GAT has no dropout of its own: None means none)
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"dropout must be in [0, 1) (got {p})")
+        if p > 0.0:
+            raise NotImplementedError("the GAT link-prediction plans have no dropout (feature and attention dropout belong "
+                                      "together there): the job keeps the autograd loop")
         self.eng, self.b, self.P, self.n_rn = eng, int(b_anchors), int(num_positives), int(n_random_negatives)
         self.H = int(num_hard_negatives)
         self.fanouts = [int(f) for f in fanouts]

@@ -334,7 +334,9 @@ class ResidentGraph:
         plan = self._plans.get(key)
         if plan is None and key not in self._plans:
             plan = self._build_plan(model, b, groups, self.lane_engine(lane))
-            self._plans[key] = plan
+            # (a model that only its training-mode dropout keeps off the plan is asked again: in eval mode it has one)
+            if plan is not None or getattr(model, "_plain_now", True) == getattr(model, "_plain_but_dropout", True):
+                self._plans[key] = plan
         if plan is not None:
             # weights are snapshotted by the plan: refresh them when a parameter has changed since (in-place updates by
             # the optimiser bump `_version`; re-assigned tensors change the pointer)
@@ -353,7 +355,7 @@ class ResidentGraph:
             if type(model) is GAT:  # (raises NotImplementedError for options outside the sharded plan)
                 return model.make_dist_plan(self.comm, groups * b, self.fanouts, group_roots=b,
                                             max_window_end=self.max_window_end)
-            if type(model) is not GraphSAGE or not model._plain or model.aggr not in ("mean", "sum", "max") or \
+            if type(model) is not GraphSAGE or not model._plain_now or model.aggr not in ("mean", "sum", "max") or \
                     model.feats_interaction is not None or model.feature_embedding_layer is not None:
                 if encoder_trains_over_graph_data(model):
                     return None  # every other encoder of the zoo: staged batches (graph_data) + the encoder's own forward

@@ -143,16 +143,26 @@ class GraphSAGE(nn.Module):
         self._ws = None  # workspace cache
 
     @property
+    def _plain_but_dropout(self) -> bool:
+        """conv -> relu (-> dropout) only: plain apart from dropout — what the training plans run (their own dropout
+        launches) and, dropout being the identity there, everything that only infers"""
+        return (not self.batchnorm and not self.linear_layer and not self.activation_before_norm and self.jk_layer is None)
+
+    @property
     def _plain(self) -> bool:
         """conv -> relu only: what the fused kernels' epilogue and the one-call plan compute"""
-        return (not self.batchnorm and self.dropout.p == 0.0 and not self.linear_layer
-                and not self.activation_before_norm and self.jk_layer is None)
+        return self._plain_but_dropout and self.dropout.p == 0.0
+
+    @property
+    def _plain_now(self) -> bool:
+        """_plain as the forwards see it: outside training mode a dropout module changes nothing"""
+        return self._plain if self.training else self._plain_but_dropout
 
     def _post(self, h: torch.Tensor, l: int, fused_act: bool) -> torch.Tensor:
         """what follows conv l (homogeneous.py:126-141); fused_act: relu already applied by the kernel epilogue"""
         if l == self.num_layers - 1 and not self.activation_after_last_conv and self.jk_layer is None:
             return h
-        if self._plain:
+        if self._plain_now:
             return h if fused_act else torch.relu(h)
         if self.activation_before_norm:
             h = torch.relu(h)
@@ -183,7 +193,7 @@ class GraphSAGE(nn.Module):
             h = self._interact(batch.x, eng)
             xs = []
             for l, conv in enumerate(self.conv_layers):
-                fused = self._plain and (l < self.num_layers - 1 or self.activation_after_last_conv)
+                fused = self._plain_now and (l < self.num_layers - 1 or self.activation_after_last_conv)
                 w_r = conv.lin_r.weight if conv.lin_r is not None else torch.zeros_like(conv.lin_l.weight)
                 h = sage_conv(h, conv.lin_l.weight, conv.lin_l.bias, w_r, eng, batch, fused, self.aggr)
                 h = self._post(h, l, fused)
@@ -219,7 +229,7 @@ class GraphSAGE(nn.Module):
             rows = min(rows, int(u.nodes.numel()))
             n_rows = u.meta[GIGL_META_LEVEL0 + (L - 1 - l): GIGL_META_LEVEL0 + (L - l)]
             view = RowsView(u.rowptr, u.rowend, u.col, n_rows, rows, gather_ids=u.nodes if l == 0 else None)
-            fused = self._plain and (l < L - 1 or self.activation_after_last_conv)
+            fused = self._plain_now and (l < L - 1 or self.activation_after_last_conv)
             w_r = conv.lin_r.weight if conv.lin_r is not None else torch.zeros_like(conv.lin_l.weight)
             h = sage_conv(h, conv.lin_l.weight, conv.lin_l.bias, w_r, eng, view, fused, self.aggr)
             h = self._post(h, l, fused)
@@ -247,10 +257,10 @@ class GraphSAGE(nn.Module):
                                     aggr=self.aggr)
             else:
                 a = eng.gather_mean(h, d, None, u.rowptr, u.rowend, u.col, n_rows, cap, out=abuf, aggr=self.aggr)
-            fused = self._plain and (l < L - 1 or self.activation_after_last_conv)
+            fused = self._plain_now and (l < L - 1 or self.activation_after_last_conv)
             h = eng.linear(a, conv.fused_weight(), conv.lin_l.bias, n_rows, cap, 1 if fused else 0,
                            out=self._buf("h", l, cap, conv.out_channels))
-            if not self._plain:
+            if not self._plain_now:
                 h = self._post(h, l, fused).contiguous()
             xs.append(h)
         if self.jk_layer is not None:
@@ -292,7 +302,7 @@ class GraphSAGE(nn.Module):
         esz = 4 if eng.feat_dtype == DTYPE_F32 else 2
         # (a table of a few thousand rows is projected in microseconds of kernel time but milliseconds of fixed
         # overhead — workspace allocation, synchronisation — which a pass of a handful of batches cannot amortise)
-        return (self._plain and self.aggr in ("mean", "sum") and self.feats_interaction is None
+        return (self._plain_now and self.aggr in ("mean", "sum") and self.feats_interaction is None
                 and self.feature_embedding_layer is None and eng.n_nodes >= (1 << 16)
                 and self.conv_layers[0].out_channels * 4 < self.conv_layers[0].in_channels * esz)
 
@@ -301,8 +311,9 @@ class GraphSAGE(nn.Module):
         `b` roots on `eng`; weights are snapshotted — call plan.set_weights(*model.fused_params()) after updates.
         groups > 1: each call takes groups*b roots and processes them as `groups` independent batches of b."""
         assert len(fanouts) == self.num_layers, "one hop per layer"
-        if not (self._plain and self.feats_interaction is None and self.feature_embedding_layer is None):
-            raise NotImplementedError("the one-call plan computes conv -> relu layers only; use forward(HipBatch)")
+        if not (self._plain_now and self.feats_interaction is None and self.feature_embedding_layer is None):
+            raise NotImplementedError("the one-call plan computes conv -> relu layers only (a dropout module: outside "
+                                      "training mode); use forward(HipBatch)")
         w, bs = self.fused_params()
         return eng.make_sage_plan(w, bs, b, fanouts, act_last=self.activation_after_last_conv, groups=groups,
                                   aggr=self.aggr, l2_normalize=self.should_l2_normalize_embedding_layer_output)

@@ -41,7 +41,7 @@ from .batches import NodeAnchorBasedLinkPredictionBatch, RootedNodeNeighborhoodB
 from .config import GbmlConfigPbWrapper, tfrecord_files
 from .link_prediction import LinkPredictionDecoder, LinkPredictionGNN, RetrievalLoss
 from .models import GraphSAGE
-from .task_specs import _rank_world
+from .task_specs import _dropout_arg, _rank_world
 
 KS_FOR_EVAL = [1, 5, 10, 50, 100, 500]
 
@@ -484,6 +484,13 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         for k in ("conv", "share_edge_att_message_weight"):
             if k in kwargs:
                 self._encoder_kwargs[k] = kwargs[k] if k == "conv" else _strtobool(kwargs[k])
+        # dropout after every activation (BasicHomogeneousGNN's argument; the reference's spec has no such trainer argument:
+        # an addition in the style of gnn_model_class_path), handed to the encoder class when its constructor takes it, and
+        # the seed of the library training plan's own mask stream (engine.NablpTrainPlan)
+        self.dropout = _dropout_arg(kwargs)
+        if self.dropout is not None:
+            self._encoder_kwargs["dropout"] = self.dropout
+        self.dropout_seed = int(kwargs.get("dropout_seed", 0))
         self.should_l2_normalize_embedding_layer_output = bool(
             kwargs.get("should_l2_normalize_embedding_layer_output", True))
         self.validate_every_n_batches = int(kwargs.get("val_every_num_batches", 20))
@@ -916,7 +923,9 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             return (NablpTrainPlan if sage else GatEdgeNablpTrainPlan if gat_edge else GatNablpTrainPlan)(
                 res.engine, enc, self.main_sample_batch_size, P,
                 n_rn, res.fanouts, temperature=float(tasks[0].loss._temperature or 0.0),
-                remove_accidental_hits=bool(tasks[0].loss._remove_accidental_hits), num_hard_negatives=H, **optim)
+                remove_accidental_hits=bool(tasks[0].loss._remove_accidental_hits), num_hard_negatives=H,
+                # (None: the encoder's own p; a GAT kind with p > 0 raises NotImplementedError: the autograd loop below)
+                dropout=self.dropout, dropout_seed=self.dropout_seed, **optim)
         except (NotImplementedError, GiglError):
             return None
 

@@ -36,6 +36,16 @@ def _rank_world():
     return 0, 1
 
 
+def _dropout_arg(kwargs) -> Optional[float]:
+    """trainerArgs `dropout` -> p in [0, 1), or None when the argument is absent"""
+    if kwargs.get("dropout") in (None, "", "None"):
+        return None
+    p = float(kwargs["dropout"])
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout must be in [0, 1) (got {kwargs['dropout']!r})")
+    return p
+
+
 class HipGraphSageNodeClassificationSpec(BaseTrainer, BaseInferencer):
     def __init__(self, is_training: bool = True, **kwargs) -> None:
         self._optim_lr = float(kwargs.get("optim_lr", 0.01))
@@ -55,6 +65,12 @@ class HipGraphSageNodeClassificationSpec(BaseTrainer, BaseInferencer):
             self._encoder_kwargs["edge_dim"] = int(kwargs["edge_dim"])
         if "conv" in kwargs:
             self._encoder_kwargs["conv"] = str(kwargs["conv"])
+        # dropout after every activation (an addition, like gnn_model_class_path: the reference's spec has no such argument),
+        # handed to the encoder class when its constructor takes it; dropout_seed: the library training plan's mask stream
+        self._dropout = _dropout_arg(kwargs)
+        if self._dropout is not None:
+            self._encoder_kwargs["dropout"] = self._dropout
+        self._dropout_seed = int(kwargs.get("dropout_seed", 0))
         self._is_training = is_training
         self._model: Optional[torch.nn.Module] = None
         self._engine = None
@@ -302,7 +318,8 @@ class HipGraphSageNodeClassificationSpec(BaseTrainer, BaseInferencer):
                 return None
             try:
                 plan = SageTrainPlan(res.engine, model, b, res.fanouts, lr=self._optim_lr,
-                                     weight_decay=self._optim_weight_decay)
+                                     weight_decay=self._optim_weight_decay, dropout=self._dropout,
+                                     dropout_seed=self._dropout_seed)
             except NotImplementedError:
                 self._train_plan_unavailable = True
                 return None

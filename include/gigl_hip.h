@@ -1307,6 +1307,47 @@ int32_t gigl_sage_train_plan_adopt(gigl_sage_train_plan* dst, gigl_sage_train_pl
  * parameters of elements with rounding-noise gradients are not) */
 int32_t gigl_sage_train_plan_moments(gigl_sage_train_plan* plan, int32_t layer, float* m_w, float* v_w, float* m_b, float* v_b);
 
+/* ---- DROPOUT between the GraphSAGE layers of the training plans (BasicHomogeneousGNN: conv -> activation -> dropout,
+ * python/gigl/src/common/models/pyg/homogeneous.py:134-140; after the last layer too when act_last).
+ * THE MASK is a function of small integers alone, so that a replayed step needs no stored mask and a redone step sees the
+ * mask of its first attempt.  Generator: Philox4x32-10 with the Random123 constants (multipliers 0xD2511F53 and
+ * 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85).  The mask covers the output of ONE layer of ONE encode at ONE
+ * step; for element (row, col) of that output the block is
+ *     key     = (seed & 0xFFFFFFFF, seed >> 32)
+ *     counter = (row, col >> 2, step, (encode << 8) | layer)
+ * and the element's word is output word col & 3 of the block.
+ *   seed    a 64-bit number (the setters' argument)
+ *   step    the plan's device step counter as it stands BEFORE the step: Adam's count of applied steps, 0 for the first.
+ *           A halted or overflowed step does not advance it: its redo sees the same mask
+ *   encode  0 for the node-classification plan and for the link-prediction plan's main batch, 1 for its random negatives
+ *   layer   the conv layer's index
+ *   row     the row's index in the layer's output buffer: the node's local id in the PLAN's batch graph (the order of its
+ *           union graph's `nodes`, as forwards over a sampled batch use it).  The numbering is the plan's union build's: a
+ *           regular two-hop plan numbers the nodes of level 1 in another order than gigl_union_build does (both first-seen
+ *           per level, over differently ordered streams; a plan with wide workspaces numbers as gigl_union_build); a
+ *           one-call plan of the same batch shape run over the same roots shows it (gigl_sage_plan_buffers)
+ * An element is KEPT iff its word >= T, T = floor(p * 2^32) computed on the host in double from the float p.  Kept
+ * elements are multiplied by 1.0f / (1.0f - p), dropped ones become 0.  0 <= p < 1; p == 0 launches nothing.
+ * Known answers of the block function (the Random123 vectors), counter / key -> output:
+ *     {0,0,0,0} / {0,0}                                              -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *     {ffffffff x 4} / {ffffffff x 2}                                -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *     {243f6a88,85a308d3,13198a2e,03707344} / {a4093822,299f31d0}    -> d16cfe09 94fdcceb 5001e420 24126ea1
+ * The stream is not torch.nn.Dropout's: a plan step and an autograd step of the same job drop different elements of the
+ * same distribution.
+ * set_dropout: called after create and before the first step (GIGL_E_INVALID_ARG afterwards: the step is captured with
+ *   the dropout launches in it); p outside [0, 1) is GIGL_E_INVALID_ARG; p == 0 is accepted and changes nothing — the
+ *   step's launches are then exactly those of a plan that never saw the call.  With p > 0 the forward runs one more launch
+ *   per activated layer and encode (in place on the layer's output, an extra read and write of it), the backward one
+ *   (mask and scale of the output's gradient: a dropped element's output is 0, as a rectified one's) in place of the
+ *   rectifier's mask.  gigl_nablp_train_plan_eval runs WITHOUT dropout.  The GAT kinds of the link-prediction plan return
+ *   GIGL_E_UNSUPPORTED (feature and attention dropout belong together there).  gigl_*_train_plan_adopt does not carry the
+ *   setting over: call the setter on the new plan too.
+ * gigl_dropout_mask: keep[r * cols + c] (DEVICE uint8 [rows][cols]) = 1 where element (r, c) is kept, else 0 — by the
+ *   device function the plans' kernels use, on the ctx's stream: what bindings and tests reproduce a step's mask with. */
+int32_t gigl_sage_train_plan_set_dropout(gigl_sage_train_plan* plan, float p, uint64_t seed);
+int32_t gigl_dropout_mask(gigl_ctx* ctx, uint64_t seed, uint32_t step, int32_t encode, int32_t layer, int64_t rows,
+                          int32_t cols, float p, uint8_t* keep);
+
 /* ---- one LINK-PREDICTION training step per call, all of it in the library (round 5).  Replaces the loop body of
  * NodeAnchorBasedLinkPredictionModelingTaskSpec.train (python/gigl/src/common/modeling_task_specs/
  * node_anchor_based_link_prediction_modeling_task_spec.py:334-451) for the reference's default encoder (GraphSAGE, mean
@@ -1372,6 +1413,9 @@ const float* gigl_nablp_train_plan_loss(gigl_nablp_train_plan* plan);
 int32_t gigl_nablp_train_plan_set_clip_grad_norm(gigl_nablp_train_plan* plan, float max_norm);
 int32_t gigl_nablp_train_plan_set_constant_lr(gigl_nablp_train_plan* plan, float factor, int32_t total_iters);
 int32_t gigl_nablp_train_plan_grad_norm(gigl_nablp_train_plan* plan, float* out2);
+/* dropout after every activated GraphSAGE layer of both encodes (see gigl_sage_train_plan_set_dropout: the mask, the rules
+ * and what the step launches; encode 0 = the main batch, 1 = the random negatives) */
+int32_t gigl_nablp_train_plan_set_dropout(gigl_nablp_train_plan* plan, float p, uint64_t seed);
 /* the LAST step's parameter gradients of layer `layer` (the two encodes' added): gw DEVICE [dims[l+1]][2 dims[l]] (= d loss
  * / d [W_l | W_r]), gb DEVICE [dims[l+1]] (may be NULL) — what the step's Adam update consumed; for gradient parity tests */
 int32_t gigl_nablp_train_plan_grads(gigl_nablp_train_plan* plan, int32_t layer, float* gw, float* gb);
