@@ -21,16 +21,48 @@
 
 namespace {
 
-// a maximal run of consecutive stages: either replayed from a captured graph or launched eagerly
-// (stages that contain launches selected for HIP-event timing stay eager: events recorded inside a
+// what one call of a plan is given
+struct RunArgs {
+  const uint32_t* roots;
+  int32_t seed, mode;
+  float* out;
+};
+
+// one thing a plan does for a batch (the step_* functions below), for layer `layer`; `kernels`: the profile ids
+// (1 << GIGL_K_*) of the launchers it calls.  A plan's list holds only steps that launch something (plan_build_steps)
+struct Step {
+  int32_t (*run)(gigl_sage_plan* p, int layer, const RunArgs& a) = nullptr;
+  int layer = 0;
+  uint32_t kernels = 0;
+};
+
+// steps [0, GRAPH_STEPS) = sample + union (the GRAPH part: integer work, latency-bound, independent of the weights)
+constexpr int GRAPH_STEPS = 2;
+constexpr int MAX_STEPS = 3 + 2 * GIGL_MAX_HOPS;
+
+// a maximal run of consecutive steps: either replayed from a captured graph or launched eagerly
+// (steps that contain launches selected for HIP-event timing stay eager: events recorded inside a
 // captured graph cannot be timed on this runtime)
 struct Segment {
-  int s0 = 0, s1 = 0;  // stages [s0, s1)
+  int s0 = 0, s1 = 0;  // steps [s0, s1)
   hipGraphExec_t exec = nullptr;
 };
 
-// stages [0, GRAPH_STAGES) = sample + union (the GRAPH part: integer work, latency-bound, independent of the weights)
-constexpr int GRAPH_STAGES = 2;
+// launches issued while one of these lives go to `st` instead of the ctx stream
+struct StreamScope {
+  gigl_ctx* ctx;
+  hipStream_t keep;
+  StreamScope(gigl_ctx* c, hipStream_t st) : ctx(c), keep(c->stream) { c->stream = st; }
+  ~StreamScope() { ctx->stream = keep; }
+};
+
+// hipMalloc'd bytes that `owned` frees with its plan (null: out of memory)
+void* plan_alloc(std::vector<void*>& owned, size_t bytes) {
+  void* q = nullptr;
+  if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
+  owned.push_back(q);
+  return q;
+}
 
 }  // namespace
 
@@ -101,11 +133,17 @@ struct gigl_sage_plan {
   float* f2_dev = nullptr;  // {s_h, s_w2, 1 / (s_h s_w2)}: the second product's scales (gigl_fused2_prepare, per run)
   void* w2h = nullptr;      // W1's and W2's fp16 images (gigl_fused2_prepare)
   std::vector<void*> owned;
+  // what a call runs, in order, for the plan as it is configured now (plan_build_steps: at creation and wherever the
+  // configuration changes; a run only walks it)
+  Step steps[MAX_STEPS];
+  int n_steps = 0;
+  bool fused2 = false;  // fused2_on() when the list was built
   // hipGraph replay
   bool use_graph = false;
   uint32_t* roots_buf = nullptr;  // static input of the captured graphs
-  float* out_buf = nullptr;       // (placeholder `out` of the captures; the stage that writes `out` runs eagerly)
-  std::vector<Segment> segs;
+  float* out_buf = nullptr;       // (placeholder `out` of the captures; the step that writes `out` runs eagerly)
+  Segment segs[MAX_STEPS];
+  int n_segs = 0;
   int32_t cap_seed = 0, cap_mode = -1;
   uint32_t cap_prof_mask = 0;
   uint64_t cap_arena_gen = 0;  // the ctx arena the captured launches point into
@@ -263,9 +301,6 @@ __global__ __launch_bounds__(256) void plan_stats_kernel(StatsArgs a, unsigned l
   }
 }
 
-// stages of one batch: 0 sample, 1 union, 2+2l gather l, 3+2l linear l, 2+2L take_rows
-int n_stages(const gigl_sage_plan* p) { return 3 + 2 * p->hops; }
-
 // (A/B knob: GIGL_PLAN_HS_LAYERS=0 keeps layers >= 1 on the three bf16 planes)
 bool hs_layers_on() {
   static const bool on = [] {
@@ -275,154 +310,117 @@ bool hs_layers_on() {
   return on;
 }
 
-// the fused two-layer projection applies to this plan as it is configured now (every input of the decision drops the
-// captured graphs when it changes: weights, reduction, projected input, half split)
+// the fused two-layer projection applies to this plan as it is configured now.  The answer is cached in p->fused2 by
+// plan_build_steps (the steps and gigl_sage_plan_fused_layers read the cache), so every input of the decision — weights
+// and bias pointers, reduction, projected input, half split — must go through plan_invalidate when it changes
 bool fused2_on(const gigl_sage_plan* p) {
   return p->f2_ok && p->kind == 0 && p->hops == 2 && p->tiled && p->two_source && p->hs0 && !p->proj &&
          p->feat->dtype == GIGL_DTYPE_F32 && (p->aggr == GIGL_AGGR_MEAN || p->aggr == GIGL_AGGR_SUM) &&
          (((uintptr_t)p->bias[0]) & 15) == 0;
 }
 
-uint32_t stage_kernel_mask(const gigl_sage_plan* p, int s) {
-  if (s == 0) return (1u << GIGL_K_EXPAND) | (1u << GIGL_K_EXPAND_HEAVY) | (1u << GIGL_K_FIND_HEAVY);
-  if (s == 1)
-    return (1u << GIGL_K_UNION_INSERT) | (1u << GIGL_K_UNION_RELAX) | (1u << GIGL_K_UNION_NODES) |
-           (1u << GIGL_K_UNION_EDGE_SORT) | (1u << GIGL_K_UNION_CSR);
-  if (s == n_stages(p) - 1) return 0;
-  return ((s - 2) & 1) ? (1u << GIGL_K_LINEAR) : (1u << GIGL_K_GATHER_MEAN);
+// (A/B knob: GIGL_F2_ALL_WR set = the fused projection is not told how many of its rows are roots)
+bool f2_all_wr() {
+  static const bool on = getenv("GIGL_F2_ALL_WR") != nullptr;
+  return on;
 }
 
-int32_t enqueue_stage(gigl_sage_plan* p, int s, const uint32_t* roots, int32_t sampling_seed, int32_t mode,
-                      float* out) {
+// A leaf-global union numbers the nodes of level <= L-2 only: the rows of level L-1 — behind this device count; every row
+// of a one-hop plan — keep their sources as GLOBAL ids.  Null: every row holds local ids
+const int32_t* first_global_row(const gigl_sage_plan* p) {
+  if (!p->leaf_global) return nullptr;
+  return p->hops >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (p->hops - 2) : p->zero_dev;
+}
+
+// layer l computes the nodes of level <= L-1-l: at most b*(1 + f0 + f0*f1 + ...) of them — the launch is
+// sized for that bound, not for the whole union (the exact count is read on the device)
+struct LayerRows {
+  const int32_t* n_rows;
+  int64_t rows_cap;
+  int d, act;
+};
+
+LayerRows layer_rows(const gigl_sage_plan* p, int l) {
+  const int L = p->hops;
+  return {p->un.meta + GIGL_META_LEVEL0 + (L - 1 - l), gigl_level_rows(p->wide, p->b, p->fanouts, L, L - 1 - l), p->dims[l],
+          (l < L - 1 || p->act_last) ? 1 : 0};
+}
+
+// ---- the steps of one batch.  Each enqueues on the ctx stream; which of them a plan runs: plan_build_steps
+
+int32_t step_sample(gigl_sage_plan* p, int, const RunArgs& a) {
+  return gigl_sample_khop(p->ctx, p->graph, a.roots, p->b, p->fanouts, p->hops, a.seed, a.mode, &p->tree);
+}
+
+// the batch union graph, the level guard and, with edge features, the edge ids
+int32_t step_union(gigl_sage_plan* p, int, const RunArgs& a) {
   gigl_ctx* ctx = p->ctx;
   const int L = p->hops;
-  if (s == 0)
-    return gigl_sample_khop(ctx, p->graph, roots, p->b, p->fanouts, p->hops, sampling_seed, mode, &p->tree);
-  if (s == 1) {
-    int32_t rc = gigl_union_build_impl(ctx, roots, &p->tree, p->group_roots, &p->un,
-                                       p->leaf_global ? (1 | (p->graph->multi ? 2 : 0)) : 0);
-    if (rc != GIGL_OK) return rc;
-    hipLaunchKernelGGL(guard_levels_kernel, dim3(1), dim3(64), 0, ctx->stream, p->un.meta, p->hops,
-                       (int32_t)(p->act_rows < 0x7FFFFFFF ? p->act_rows : 0x7FFFFFFF));
+  int32_t rc = gigl_union_build_impl(ctx, a.roots, &p->tree, p->group_roots, &p->un,
+                                     p->leaf_global ? (1 | (p->graph->multi ? 2 : 0)) : 0);
+  if (rc != GIGL_OK) return rc;
+  hipLaunchKernelGGL(guard_levels_kernel, dim3(1), dim3(64), 0, ctx->stream, p->un.meta, p->hops,
+                     (int32_t)(p->act_rows < 0x7FFFFFFF ? p->act_rows : 0x7FFFFFFF));
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  if (p->efeat) {  // the edge ids belong to the GRAPH part: integer work over the union, independent of the weights
+    const int64_t rows_cap = gigl_level_rows(p->wide, p->b, p->fanouts, L, L - 1);
+    int64_t blocks = (rows_cap + 3) / 4;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(plan_edge_ids_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, p->graph->rowptr, p->graph->col,
+                       p->graph->n, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col, p->un.meta + GIGL_META_LEVEL0 + (L - 1),
+                       first_global_row(p), rows_cap, p->un.cap_edges + (p->alias_rows ? p->last_slots : 0), p->eid);
     GIGL_HIP_CHECK(ctx, hipGetLastError());
-    if (p->efeat) {  // the edge ids belong to the GRAPH part: integer work over the union, independent of the weights
-      const int64_t rows_cap = gigl_level_rows(p->wide, p->b, p->fanouts, L, L - 1);
-      int64_t blocks = (rows_cap + 3) / 4;
-      if (blocks > 256 * 16) blocks = 256 * 16;
-      const int32_t* n_local = p->leaf_global ? (L >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (L - 2) : p->zero_dev) : nullptr;
-      hipLaunchKernelGGL(plan_edge_ids_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, p->graph->rowptr, p->graph->col,
-                         p->graph->n, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col, p->un.meta + GIGL_META_LEVEL0 + (L - 1),
-                         n_local, rows_cap, p->un.cap_edges + (p->alias_rows ? p->last_slots : 0), p->eid);
-      GIGL_HIP_CHECK(ctx, hipGetLastError());
-    }
-    return GIGL_OK;
   }
-  if (s == n_stages(p) - 1) {
-    const int dout = p->dims[L];
-    if (fused2_on(p)) {  // the last layer over the p rows of the fused projection, one row per root, into `out`
-      const int32_t rc = gigl_sage_fused_out(ctx, p->hbuf[0], p->un.rowptr, p->un.rowend, p->un.col, p->un.root_local, p->b,
-                                             dout, p->bias[L - 1], p->act_last ? 1 : 0, p->aggr, p->un.meta, out);
-      if (rc != GIGL_OK) return rc;
-    } else {
-      gigl_take_rows(ctx->stream, p->hbuf[(L - 1) & 1], p->un.root_local, p->b, dout, p->un.meta, out);
-    }
-    if (p->l2_normalize)
-      hipLaunchKernelGGL(l2_normalize_rows_kernel, dim3((unsigned)((p->b + 3) / 4)), dim3(256), 0, ctx->stream, out, p->b, dout);
-    GIGL_HIP_CHECK(ctx, hipGetLastError());
-    return GIGL_OK;
-  }
-  const int l = (s - 2) >> 1;
-  if (l == 1 && fused2_on(p)) return GIGL_OK;  // (layer 1 runs as the last stage)
-  const int32_t* n_rows = p->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
-  const int d = p->dims[l];
-  // layer l computes the nodes of level <= L-1-l: at most b*(1 + f0 + f0*f1 + ...) of them — the launch is
-  // sized for that bound, not for the whole union (the exact count is read on the device)
-  const int64_t rows_cap = gigl_level_rows(p->wide, p->b, p->fanouts, L, L - 1 - l);
-  int64_t width = p->b;  // slots of hop L-1-l: with rows_cap, the rows of level <= L-l (the sources of layer l)
-  for (int i = 0; i <= L - 1 - l; ++i) width *= p->fanouts[i];
-  if (p->wide) width = 0;  // (rows_cap is the whole tree already)
-  if (p->kind == 1) {
-    const int act = (l < L - 1 || p->act_last) ? 1 : 0;
-    const bool first = ((s - 2) & 1) == 0;
-    if (l == 0) {
-      if (!first) return GIGL_OK;  // (the first layer is one stage: aggregation + both heads' projection)
-      const int32_t* n_local = p->leaf_global ? (L >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (L - 2) : p->zero_dev) : nullptr;
-      if (p->hs0) {
-        const int32_t rc = gigl_hs_scale_update(ctx, p->w[0], (int64_t)p->heads[0] * p->channels[0] * d, p->hs_sa, p->hs_dev);
-        if (rc != GIGL_OK) return rc;
-      }
-      gigl_gat_edge_terms et{};
-      if (p->efeat) {
-        et.eid = p->eid;
-        et.table = (const float*)p->efeat->rows;
-        et.edge_dim = p->efeat->d;
-        et.att_edge_folded = p->att_edge[0];
-        et.w_edge_msg = p->w_msg[0];
-        et.ze = p->ze;
-      }
-      return gigl_gat_input_layer_fused_hs(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, n_local, p->w[0], p->att_src[0],
-                                           p->att_dst[0], p->heads[0], p->channels[0], p->slope, p->un.rowptr, p->un.rowend,
-                                           p->un.col, n_rows, rows_cap, p->bias[0], act, p->gat_scratch, p->hbuf[0],
-                                           p->hs0 ? p->hs_dev : nullptr, p->efeat ? &et : nullptr);
-    }
-    // sources of layer l: the rows layer l-1 computed (level <= L-l)
-    const int32_t* n_src = p->un.meta + GIGL_META_LEVEL0 + (L - l);
-    int64_t src_cap = rows_cap + width;
-    if (first)
-      return gigl_linear(ctx, p->hbuf[(l - 1) & 1], p->w[l], nullptr, n_src, src_cap, d, p->dims[l + 1], 0, p->hw);
-    if (p->efeat)  // (a_edge lies behind the 2 * src_cap * heads node dots of alpha_scratch)
-      return gigl_gat_aggregate_edge_indexed(ctx, p->hw, p->att_src[l], p->att_dst[l], p->heads[l], p->channels[l], p->slope, 1,
-                                             p->un.rowptr, p->un.rowend, p->un.col, n_src, src_cap, n_rows, rows_cap, p->bias[l],
-                                             act, (const float*)p->efeat->rows, p->eid, p->efeat->d,
-                                             p->un.cap_edges + (p->alias_rows ? p->last_slots : 0), p->att_edge[l], p->w_msg[l],
-                                             p->alpha_scratch, p->hbuf[l & 1]);
-    return gigl_gat_aggregate(ctx, p->hw, p->att_src[l], p->att_dst[l], p->heads[l], p->channels[l], p->slope, 1,
-                              p->un.rowptr, p->un.rowend, p->un.col, n_src, src_cap, n_rows, rows_cap, p->bias[l], act,
-                              p->alpha_scratch, p->hbuf[l & 1]);
-  }
-  if (l == 0 && p->proj) {
-    // lin_l(mean_j x_j) = mean_j lin_l(x_j): the rows arrive projected, the layer is the reduction plus the self row
-    if (((s - 2) & 1) != 0) return GIGL_OK;  // (no projection stage)
-    const int act = (l < L - 1 || p->act_last) ? 1 : 0;
-    return gigl_gather_project_mixed(
-        ctx, p->proj, p->proj + p->dims[1], 2 * p->dims[1], p->dims[1], p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col, n_rows, rows_cap,
-        p->aggr, p->leaf_global ? (L >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (L - 2) : p->zero_dev) : nullptr, p->bias[0],
-        act, p->hbuf[0]);
-  }
-  // two-source operand: the projection reads the self half from the fp32 source rows themselves (the feature table
-  // through union.nodes, or the previous layer's output), the gather writes the reduced half only
-  // (an fp16 table's rows serve as the self half too when the layer runs the half split: they are its h1 plane)
-  const bool self_half = l == 0 && p->hs0 && p->feat->dtype == GIGL_DTYPE_F16;
-  const bool two_src = p->tiled && p->two_source && (l > 0 || p->feat->dtype == GIGL_DTYPE_F32 || self_half);
-  const int32_t nkc = p->tiled ? ((two_src ? d : 2 * d) + 31) / 32 : 0;
-  if (((s - 2) & 1) == 0) {
-    if (p->tiled) {
-      if (l == 0)  // (leaf-global: rows of level L-1 — >= the count through level L-2 — hold global source ids)
-        return gigl_gather_reduce_mixed(
-            ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col, n_rows, rows_cap,
-            p->aggr, p->leaf_global ? (L >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (L - 2) : p->zero_dev) : nullptr,
-            p->abuf, nkc, nullptr, nullptr, nullptr, two_src ? 1 : 0);
-      return gigl_gather_reduce_mixed(ctx, p->hbuf[(l - 1) & 1], GIGL_DTYPE_F32, d, nullptr, p->un.rowptr, p->un.rowend,
-                                      p->un.col, n_rows, rows_cap, p->aggr, nullptr, p->abuf, nkc, nullptr, nullptr, nullptr,
-                                      two_src ? 1 : 0);
-    }
-    if (l == 0 && p->leaf_global)  // rows of level L-1 (>= the count through level L-2) hold global source ids
-      return gigl_gather_reduce_mixed(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, p->un.rowptr, p->un.rowend,
-                                      p->un.col, n_rows, rows_cap, p->aggr,
-                                      L >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (L - 2) : p->zero_dev, p->abuf);
+  return GIGL_OK;
+}
+
+// two-source operand: the projection reads the self half from the fp32 source rows themselves (the feature table
+// through union.nodes, or the previous layer's output), the gather writes the reduced half only
+// (an fp16 table's rows serve as the self half too when the layer runs the half split: they are its h1 plane)
+bool sage_self_half(const gigl_sage_plan* p, int l) { return l == 0 && p->hs0 && p->feat->dtype == GIGL_DTYPE_F16; }
+bool sage_two_source(const gigl_sage_plan* p, int l) {
+  return p->tiled && p->two_source && (l > 0 || p->feat->dtype == GIGL_DTYPE_F32 || sage_self_half(p, l));
+}
+
+// SAGE layer l, first half: the reduced neighbour rows (tiled: the mean chunks, or [mean | self]) into abuf
+int32_t step_sage_reduce(gigl_sage_plan* p, int l, const RunArgs&) {
+  gigl_ctx* ctx = p->ctx;
+  const LayerRows r = layer_rows(p, l);
+  const int d = r.d;
+  if (p->tiled) {
+    const bool two_src = sage_two_source(p, l);
+    const int32_t nkc = ((two_src ? d : 2 * d) + 31) / 32;
     if (l == 0)
-      return gigl_gather_reduce(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, p->un.rowptr, p->un.rowend,
-                                p->un.col, n_rows, rows_cap, p->aggr, p->abuf);
-    return gigl_gather_reduce(ctx, p->hbuf[(l - 1) & 1], GIGL_DTYPE_F32, d, nullptr, p->un.rowptr, p->un.rowend,
-                              p->un.col, n_rows, rows_cap, p->aggr, p->abuf);
+      return gigl_gather_reduce_mixed(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col,
+                                      r.n_rows, r.rows_cap, p->aggr, first_global_row(p), p->abuf, nkc, nullptr, nullptr, nullptr,
+                                      two_src ? 1 : 0);
+    return gigl_gather_reduce_mixed(ctx, p->hbuf[(l - 1) & 1], GIGL_DTYPE_F32, d, nullptr, p->un.rowptr, p->un.rowend,
+                                    p->un.col, r.n_rows, r.rows_cap, p->aggr, nullptr, p->abuf, nkc, nullptr, nullptr, nullptr,
+                                    two_src ? 1 : 0);
   }
-  const int act = (l < L - 1 || p->act_last) ? 1 : 0;
+  if (l == 0 && p->leaf_global)
+    return gigl_gather_reduce_mixed(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, p->un.rowptr, p->un.rowend,
+                                    p->un.col, r.n_rows, r.rows_cap, p->aggr, first_global_row(p), p->abuf);
+  if (l == 0)
+    return gigl_gather_reduce(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, p->un.rowptr, p->un.rowend,
+                              p->un.col, r.n_rows, r.rows_cap, p->aggr, p->abuf);
+  return gigl_gather_reduce(ctx, p->hbuf[(l - 1) & 1], GIGL_DTYPE_F32, d, nullptr, p->un.rowptr, p->un.rowend,
+                            p->un.col, r.n_rows, r.rows_cap, p->aggr, p->abuf);
+}
+
+// SAGE layer l, second half: act([reduced | self] W^T + b) into hbuf[l & 1] — by the half split (first layer), the chained
+// half split (layers >= 1), the fused pair of layers, the two-source, tiled or row-major projection
+int32_t step_sage_project(gigl_sage_plan* p, int l, const RunArgs&) {
+  gigl_ctx* ctx = p->ctx;
+  const LayerRows r = layer_rows(p, l);
+  const int d = r.d;
+  const bool two_src = sage_two_source(p, l);
   const float* hs_scale = nullptr;
   if (l == 0 && p->hs0 && p->tiled) {  // the weights' scale follows the weights as they are now (training rewrites them in place)
     uint32_t* a_max = nullptr;  // a sum: the scale follows the operand as the gather wrote it (hs_dev[7]: zero between runs)
     if (p->aggr == GIGL_AGGR_SUM) {
       a_max = reinterpret_cast<uint32_t*>(p->hs_dev + 7);
-      const int32_t rc_m = gigl_tiled_absmax(ctx, p->abuf, n_rows, rows_cap, two_src ? d : 2 * d, a_max);
+      const int32_t rc_m = gigl_tiled_absmax(ctx, p->abuf, r.n_rows, r.rows_cap, two_src ? d : 2 * d, a_max);
       if (rc_m != GIGL_OK) return rc_m;
     }
     const int32_t rc = gigl_hs_scale_update(ctx, p->w[0], (int64_t)p->dims[1] * 2 * d, p->hs_sa, p->hs_dev, a_max,
@@ -436,92 +434,198 @@ int32_t enqueue_stage(gigl_sage_plan* p, int s, const uint32_t* roots, int32_t s
     uint32_t* sum_max = nullptr;  // (a sum of hidden rows: measured, hs_layer[l][7] — zero between runs)
     if (p->aggr == GIGL_AGGR_SUM) {
       sum_max = reinterpret_cast<uint32_t*>(p->hs_layer[l] + 7);
-      const int32_t rc_m = gigl_tiled_absmax(ctx, p->abuf, n_rows, rows_cap, d, sum_max);
+      const int32_t rc_m = gigl_tiled_absmax(ctx, p->abuf, r.n_rows, r.rows_cap, d, sum_max);
       if (rc_m != GIGL_OK) return rc_m;
     }
     int32_t rc = gigl_hs_chain_update(ctx, prev, p->bias[l - 1], p->dims[l], 2 * p->dims[l - 1], sum_max, p->w[l],
                                       (int64_t)p->dims[l + 1] * 2 * d, p->hs_layer[l]);
     if (rc != GIGL_OK) return rc;
-    return gigl_linear_tiled(ctx, p->abuf, p->w[l], p->bias[l], n_rows, rows_cap, 2 * d, p->dims[l + 1], act,
+    return gigl_linear_tiled(ctx, p->abuf, p->w[l], p->bias[l], r.n_rows, r.rows_cap, 2 * d, p->dims[l + 1], r.act,
                              p->hbuf[l & 1], p->hbuf[(l - 1) & 1], nullptr, d, d, p->hs_layer[l]);
   }
-  if (l == 0 && fused2_on(p)) {
+  if (l == 0 && p->fused2) {  // hbuf[0] takes p = [W_l h | W_r h] of the last layer instead of hidden rows (step_roots)
     int32_t rc = gigl_fused2_prepare(ctx, p->hs_dev, p->bias[0], p->w[0], p->w[1], p->dims[2], 2 * d, p->f2_dev, p->w2h);
     if (rc != GIGL_OK) return rc;
-    return gigl_linear_fused2(ctx, p->abuf, p->bias[0], n_rows, rows_cap, 2 * d, p->hbuf[0], (const float*)p->feat->rows,
+    return gigl_linear_fused2(ctx, p->abuf, p->bias[0], r.n_rows, r.rows_cap, 2 * d, p->hbuf[0], (const float*)p->feat->rows,
                               p->un.nodes, d, d, hs_scale, p->f2_dev, p->w2h,
-                              getenv("GIGL_F2_ALL_WR") ? nullptr : p->un.meta + GIGL_META_LEVEL0);
+                              f2_all_wr() ? nullptr : p->un.meta + GIGL_META_LEVEL0);
   }
   if (two_src)
-    return gigl_linear_tiled(ctx, p->abuf, p->w[l], p->bias[l], n_rows, rows_cap, 2 * d, p->dims[l + 1], act,
+    return gigl_linear_tiled(ctx, p->abuf, p->w[l], p->bias[l], r.n_rows, r.rows_cap, 2 * d, p->dims[l + 1], r.act,
                              p->hbuf[l & 1], l == 0 ? (const float*)p->feat->rows : p->hbuf[(l - 1) & 1],
-                             l == 0 ? p->un.nodes : nullptr, d, d, hs_scale, self_half);
+                             l == 0 ? p->un.nodes : nullptr, d, d, hs_scale, sage_self_half(p, l));
   if (p->tiled)
-    return gigl_linear_tiled(ctx, p->abuf, p->w[l], p->bias[l], n_rows, rows_cap, 2 * d, p->dims[l + 1], act,
+    return gigl_linear_tiled(ctx, p->abuf, p->w[l], p->bias[l], r.n_rows, r.rows_cap, 2 * d, p->dims[l + 1], r.act,
                              p->hbuf[l & 1], nullptr, nullptr, 0, 0, hs_scale);
-  return gigl_linear(ctx, p->abuf, p->w[l], p->bias[l], n_rows, rows_cap, 2 * d, p->dims[l + 1], act,
+  return gigl_linear(ctx, p->abuf, p->w[l], p->bias[l], r.n_rows, r.rows_cap, 2 * d, p->dims[l + 1], r.act,
                      p->hbuf[l & 1]);
 }
 
-int32_t enqueue_range(gigl_sage_plan* p, int s0, int s1, const uint32_t* roots, int32_t sampling_seed, int32_t mode,
-                      float* out) {
+// the first SAGE layer over a projected input — lin_l(mean_j x_j) = mean_j lin_l(x_j): the rows arrive projected, the
+// layer is the reduction plus the self row, no projection
+int32_t step_sage_projected_input(gigl_sage_plan* p, int, const RunArgs&) {
+  const LayerRows r = layer_rows(p, 0);
+  return gigl_gather_project_mixed(p->ctx, p->proj, p->proj + p->dims[1], 2 * p->dims[1], p->dims[1], p->un.nodes, p->un.rowptr,
+                                   p->un.rowend, p->un.col, r.n_rows, r.rows_cap, p->aggr, first_global_row(p), p->bias[0], r.act,
+                                   p->hbuf[0]);
+}
+
+// the first GAT layer from the input side: aggregation + every head's projection in one row pass
+int32_t step_gat_input(gigl_sage_plan* p, int, const RunArgs&) {
+  gigl_ctx* ctx = p->ctx;
+  const LayerRows r = layer_rows(p, 0);
+  if (p->hs0) {
+    const int32_t rc = gigl_hs_scale_update(ctx, p->w[0], (int64_t)p->heads[0] * p->channels[0] * r.d, p->hs_sa, p->hs_dev);
+    if (rc != GIGL_OK) return rc;
+  }
+  gigl_gat_edge_terms et{};
+  if (p->efeat) {
+    et.eid = p->eid;
+    et.table = (const float*)p->efeat->rows;
+    et.edge_dim = p->efeat->d;
+    et.att_edge_folded = p->att_edge[0];
+    et.w_edge_msg = p->w_msg[0];
+    et.ze = p->ze;
+  }
+  return gigl_gat_input_layer_fused_hs(ctx, p->feat->rows, p->feat->dtype, r.d, p->un.nodes, first_global_row(p), p->w[0],
+                                       p->att_src[0], p->att_dst[0], p->heads[0], p->channels[0], p->slope, p->un.rowptr,
+                                       p->un.rowend, p->un.col, r.n_rows, r.rows_cap, p->bias[0], r.act, p->gat_scratch, p->hbuf[0],
+                                       p->hs0 ? p->hs_dev : nullptr, p->efeat ? &et : nullptr);
+}
+
+// sources of GAT layer l >= 1: the rows layer l-1 computed (level <= L-l) — rows_cap plus the slots of hop L-1-l
+int64_t gat_src_cap(const gigl_sage_plan* p, int l, int64_t rows_cap) {
+  if (p->wide) return rows_cap;  // (rows_cap is the whole tree already)
+  int64_t width = p->b;
+  for (int i = 0; i <= p->hops - 1 - l; ++i) width *= p->fanouts[i];
+  return rows_cap + width;
+}
+
+// GAT layer l >= 1, first half: hw = h W^T of its source rows
+int32_t step_gat_project(gigl_sage_plan* p, int l, const RunArgs&) {
+  const LayerRows r = layer_rows(p, l);
+  return gigl_linear(p->ctx, p->hbuf[(l - 1) & 1], p->w[l], nullptr, p->un.meta + GIGL_META_LEVEL0 + (p->hops - l),
+                     gat_src_cap(p, l, r.rows_cap), r.d, p->dims[l + 1], 0, p->hw);
+}
+
+// GAT layer l >= 1, second half: attention over hw into hbuf[l & 1], with the edge terms of an edge-featured plan
+int32_t step_gat_attend(gigl_sage_plan* p, int l, const RunArgs&) {
+  gigl_ctx* ctx = p->ctx;
+  const LayerRows r = layer_rows(p, l);
+  const int32_t* n_src = p->un.meta + GIGL_META_LEVEL0 + (p->hops - l);
+  const int64_t src_cap = gat_src_cap(p, l, r.rows_cap);
+  if (p->efeat)  // (a_edge lies behind the 2 * src_cap * heads node dots of alpha_scratch)
+    return gigl_gat_aggregate_edge_indexed(ctx, p->hw, p->att_src[l], p->att_dst[l], p->heads[l], p->channels[l], p->slope, 1,
+                                           p->un.rowptr, p->un.rowend, p->un.col, n_src, src_cap, r.n_rows, r.rows_cap, p->bias[l],
+                                           r.act, (const float*)p->efeat->rows, p->eid, p->efeat->d,
+                                           p->un.cap_edges + (p->alias_rows ? p->last_slots : 0), p->att_edge[l], p->w_msg[l],
+                                           p->alpha_scratch, p->hbuf[l & 1]);
+  return gigl_gat_aggregate(ctx, p->hw, p->att_src[l], p->att_dst[l], p->heads[l], p->channels[l], p->slope, 1,
+                            p->un.rowptr, p->un.rowend, p->un.col, n_src, src_cap, r.n_rows, r.rows_cap, p->bias[l], r.act,
+                            p->alpha_scratch, p->hbuf[l & 1]);
+}
+
+// the roots' rows into the caller's `out`: taken from the last layer's output — a fused plan's last layer IS this step, one
+// reduction over the p rows of the fused projection per root — then normalised when the plan says so
+int32_t step_roots(gigl_sage_plan* p, int l, const RunArgs& a) {
+  gigl_ctx* ctx = p->ctx;
+  const int dout = p->dims[l + 1];
+  if (p->fused2) {
+    const int32_t rc = gigl_sage_fused_out(ctx, p->hbuf[0], p->un.rowptr, p->un.rowend, p->un.col, p->un.root_local, p->b,
+                                           dout, p->bias[l], p->act_last ? 1 : 0, p->aggr, p->un.meta, a.out);
+    if (rc != GIGL_OK) return rc;
+  } else {
+    gigl_take_rows(ctx->stream, p->hbuf[l & 1], p->un.root_local, p->b, dout, p->un.meta, a.out);
+  }
+  if (p->l2_normalize)
+    hipLaunchKernelGGL(l2_normalize_rows_kernel, dim3((unsigned)((p->b + 3) / 4)), dim3(256), 0, ctx->stream, a.out, p->b, dout);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+int32_t run_steps(gigl_sage_plan* p, int s0, int s1, const RunArgs& a) {
   for (int s = s0; s < s1; ++s) {
-    int32_t rc = enqueue_stage(p, s, roots, sampling_seed, mode, out);
+    const int32_t rc = p->steps[s].run(p, p->steps[s].layer, a);
     if (rc != GIGL_OK) return rc;
   }
   return GIGL_OK;
 }
 
+// the ordered steps of one batch for the plan as it is configured now: kind, hops, projected input, fused pair of layers.
+// (Edge features change what step_union and the GAT steps launch, not which steps run.)  Only steps that launch something
+// are listed, each with the profile ids its launchers record under
+void plan_build_steps(gigl_sage_plan* p) {
+  const uint32_t gather = 1u << GIGL_K_GATHER_MEAN, linear = 1u << GIGL_K_LINEAR;
+  const int L = p->hops;
+  p->fused2 = fused2_on(p);
+  int n = 0;
+  auto add = [&](decltype(Step::run) run, int layer, uint32_t kernels) { p->steps[n++] = Step{run, layer, kernels}; };
+  add(step_sample, 0, (1u << GIGL_K_EXPAND) | (1u << GIGL_K_EXPAND_HEAVY) | (1u << GIGL_K_FIND_HEAVY));
+  add(step_union, 0, (1u << GIGL_K_UNION_INSERT) | (1u << GIGL_K_UNION_RELAX) | (1u << GIGL_K_UNION_NODES) |
+                         (1u << GIGL_K_UNION_EDGE_SORT) | (1u << GIGL_K_UNION_CSR));
+  for (int l = 0; l < L; ++l) {
+    if (p->kind == 1) {
+      if (l == 0) {  // (the row pass records as a gather, the heads' projection behind it as a linear)
+        add(step_gat_input, 0, gather | linear);
+      } else {
+        add(step_gat_project, l, linear);
+        add(step_gat_attend, l, gather);
+      }
+    } else if (l == 0 && p->proj) {
+      add(step_sage_projected_input, 0, gather);
+    } else if (l == 1 && p->fused2) {
+      // (layer 0's projection applied this layer's weights already; its reduction is step_roots)
+    } else {
+      add(step_sage_reduce, l, gather);
+      add(step_sage_project, l, linear);
+    }
+  }
+  add(step_roots, L - 1, p->fused2 ? gather : 0);
+  p->n_steps = n;
+}
+
 void drop_graphs(gigl_sage_plan* p) {
-  for (Segment& sg : p->segs)
-    if (sg.exec) hipGraphExecDestroy(sg.exec);
-  p->segs.clear();
+  for (int i = 0; i < p->n_segs; ++i)
+    if (p->segs[i].exec) hipGraphExecDestroy(p->segs[i].exec);
+  p->n_segs = 0;
   p->captured = false;
 }
 
-// split the stages into timed (eager) and untimed (captured) segments and capture the latter
+// the configuration changed: what the captured launches hold is stale, and so may be the list of steps
+void plan_invalidate(gigl_sage_plan* p) {
+  if (p->captured) {
+    hipStreamSynchronize(p->ctx->stream);
+    drop_graphs(p);
+  }
+  plan_build_steps(p);
+}
+
+// split the steps into timed (eager) and untimed (captured) segments, by the steps' own kernel ids, and capture the latter
 int32_t capture_segments(gigl_sage_plan* p, int32_t sampling_seed, int32_t mode) {
   gigl_ctx* ctx = p->ctx;
-  const int n = n_stages(p);
+  const int n = p->n_steps;
   const uint32_t mask = ctx->prof_mask;
-  int s = 0;
-  while (s < n) {
-    Segment sg;
-    sg.s0 = s;
-    // (the last stage — the roots' rows into the caller's `out` — stays out of the graphs: launched eagerly with the
-    // pointer of the call, instead of a captured write to a static buffer and a device copy of it per call)
-    const bool timed = (stage_kernel_mask(p, s) & mask) != 0 || s == n - 1;
-    int e = s + 1;
-    while (e < n - 1 && ((stage_kernel_mask(p, e) & mask) != 0) == timed && s != n - 1 && !(p->split && e == GRAPH_STAGES)) ++e;
-    sg.s1 = e;
-    if (!timed) {
-      hipGraph_t graph = nullptr;
+  // (the last step — the roots' rows into the caller's `out` — stays out of the graphs: launched eagerly with the
+  // pointer of the call, instead of a captured write to a static buffer and a device copy of it per call)
+  auto timed = [&](int s) { return s == n - 1 || (p->steps[s].kernels & mask) != 0; };
+  for (int s = 0; s < n;) {
+    int e = s + 1;  // (the last step is a segment of its own; a split plan's graph part ends one)
+    while (e < n - 1 && timed(e) == timed(s) && !(p->split && e == GRAPH_STEPS)) ++e;
+    Segment& sg = p->segs[p->n_segs] = Segment{s, e, nullptr};
+    if (!timed(s)) {
       // (a graph-part segment of a split plan is captured from — and later launched on — the plan's graph stream)
-      hipStream_t keep = ctx->stream;
-      if (p->split && sg.s1 <= GRAPH_STAGES) ctx->stream = p->gstream;
-      hipError_t err = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
-      int32_t rc = GIGL_OK;
-      if (err == hipSuccess) {
-        rc = enqueue_range(p, sg.s0, sg.s1, p->roots_buf, sampling_seed, mode, p->out_buf);
-        hipError_t e2 = hipStreamEndCapture(ctx->stream, &graph);
-        if (rc == GIGL_OK && e2 != hipSuccess) err = e2;
-      }
-      ctx->stream = keep;
-      if (rc == GIGL_OK && err == hipSuccess) err = hipGraphInstantiate(&sg.exec, graph, nullptr, nullptr, 0);
-      if (graph) hipGraphDestroy(graph);
+      StreamScope on(ctx, p->split && e <= GRAPH_STEPS ? p->gstream : ctx->stream);
+      char what[64];  // (the message keeps its wording; the numbers are positions in the plan's list of steps)
+      snprintf(what, sizeof what, "stages [%d,%d) of the batch pipeline", s, e);
+      const int32_t rc = gigl_capture(ctx, ctx->stream, what, &sg.exec,
+                                      [&] { return run_steps(p, s, e, {p->roots_buf, sampling_seed, mode, p->out_buf}); });
       if (rc != GIGL_OK) return rc;
-      if (err != hipSuccess) {
-        sg.exec = nullptr;
-        return gigl_fail(ctx, GIGL_E_HIP, "capturing stages [%d,%d) of the batch pipeline failed: %s", sg.s0, sg.s1,
-                         hipGetErrorString(err));
-      }
     }
-    p->segs.push_back(sg);
+    ++p->n_segs;
     s = e;
   }
   return GIGL_OK;
 }
-
 
 // ---- training step (gigl_sage_train_plan_*)
 
@@ -980,12 +1084,7 @@ static int32_t plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, in
     delete p;
     return gigl_fail(ctx, GIGL_E_INVALID_ARG, "bad fanouts");
   }
-  auto alloc = [&](size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    p->owned.push_back(q);
-    return q;
-  };
+  auto alloc = [&](size_t bytes) { return plan_alloc(p->owned, bytes); };
   bool ok = true;
   // (the two-hop leaf-global builds keep a hop-0 slot's children in a 64-bit mask: last-hop fanouts beyond 64 — the
   // workgroup-per-row sampler path — take the generic union build)
@@ -1057,6 +1156,7 @@ static int32_t plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, in
       return rc_hs;
     }
   }
+  plan_build_steps(p);
   *out = p;
   return GIGL_OK;
 }
@@ -1094,12 +1194,7 @@ int32_t gigl_gat_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, 
     p->att_src[l] = att_src[l];
     p->att_dst[l] = att_dst[l];
   }
-  auto alloc = [&](size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    p->owned.push_back(q);
-    return q;
-  };
+  auto alloc = [&](size_t bytes) { return plan_alloc(p->owned, bytes); };
   p->gat_scratch = (float*)alloc((size_t)gigl_gat_input_layer_fused_scratch(feat->d, heads[0], p->act_rows) * 4);
   p->alpha_scratch = (float*)alloc((size_t)2 * p->act_rows * max_h * 4);
   p->hw = (float*)alloc((size_t)p->act_rows * max_hc * 4);
@@ -1112,6 +1207,7 @@ int32_t gigl_gat_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, 
     gigl_sage_plan_destroy(p);
     return rc;
   }
+  plan_build_steps(p);  // (the list plan_create left is a SAGE plan's)
   *out = p;
   return GIGL_OK;
 }
@@ -1126,10 +1222,7 @@ int32_t gigl_gat_plan_set_weights(gigl_sage_plan* p, const float* const* w, cons
     p->att_dst[l] = att_dst[l];
     p->bias[l] = bias ? bias[l] : nullptr;
   }
-  if (p->captured) {  // weight pointers are baked into the captured kernels
-    hipStreamSynchronize(p->ctx->stream);
-    drop_graphs(p);
-  }
+  plan_invalidate(p);  // (weight pointers are baked into the captured kernels)
   return plan_refresh_half_split(p);
 }
 
@@ -1147,16 +1240,8 @@ int32_t gigl_gat_plan_set_edge_features(gigl_sage_plan* p, gigl_feat* edge_table
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "GAT plan: edge_dim %d outside [1,64]", De);
   for (int l = 0; l < p->hops; ++l) GIGL_REQUIRE(ctx, att_edge_folded[l], "layer %d: null folded att_edge", l);
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (p->captured) {  // the pointers are baked into the captured kernels
-    hipStreamSynchronize(ctx->stream);
-    drop_graphs(p);
-  }
-  auto alloc = [&](size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    p->owned.push_back(q);
-    return q;
-  };
+  plan_invalidate(p);  // (the pointers are baked into the captured kernels)
+  auto alloc = [&](size_t bytes) { return plan_alloc(p->owned, bytes); };
   const int64_t positions = p->un.cap_edges + (p->alias_rows ? p->last_slots : 0);
   int32_t max_h = 1;
   for (int l = 0; l < p->hops; ++l) max_h = p->heads[l] > max_h ? p->heads[l] : max_h;
@@ -1184,7 +1269,7 @@ int32_t gigl_gat_plan_set_edge_features(gigl_sage_plan* p, gigl_feat* edge_table
 
 int32_t gigl_sage_plan_set_l2_normalize(gigl_sage_plan* p, int32_t on) {
   if (!p) return GIGL_E_INVALID_ARG;
-  p->l2_normalize = on != 0;  // (the stage that writes `out` runs eagerly: no captured graph holds the decision)
+  p->l2_normalize = on != 0;  // (the step that writes `out` runs eagerly: no captured graph holds the decision)
   return GIGL_OK;
 }
 
@@ -1205,16 +1290,13 @@ static int32_t plan_refresh_half_split(gigl_sage_plan* p) {
   if ((gat || sage) && p->feat && p->w[0] && p->hs_dev) {
     // (mean, max and softmax weights stay inside the table's range.  A SUM does not, and no fan-out bounds it: a union row
     // merges the samples of every occurrence of its node — each sampled with its own hash key — up to the node's whole
-    // in-row.  The summed half is measured on the device at every run instead: gigl_tiled_absmax in enqueue_stage.)
+    // in-row.  The summed half is measured on the device at every run instead: gigl_tiled_absmax in step_sage_project.)
     const float fan = 1.f;
     const int32_t rc = gigl_feat_half_split_scale(p->ctx, p->feat, fan, &p->hs_sa);
     if (rc != GIGL_OK) return rc;
     p->hs0 = p->hs_sa > 0.f;
   }
-  if (p->captured && (before != p->hs0 || sa_before != p->hs_sa)) {
-    hipStreamSynchronize(p->ctx->stream);
-    drop_graphs(p);
-  }
+  if (before != p->hs0 || sa_before != p->hs_sa) plan_invalidate(p);
   return GIGL_OK;
 }
 
@@ -1225,26 +1307,21 @@ int32_t gigl_sage_plan_set_weights(gigl_sage_plan* p, const float* const* w, con
     p->w[k] = w[k];
     p->bias[k] = bias ? bias[k] : nullptr;
   }
-  if (p->captured) {  // weight pointers are baked into the captured kernels
-    hipStreamSynchronize(p->ctx->stream);
-    drop_graphs(p);
-  }
+  plan_invalidate(p);  // (weight pointers are baked into the captured kernels)
   return plan_refresh_half_split(p);
 }
 
 int32_t gigl_sage_plan_half_split(gigl_sage_plan* p) { return p && p->hs0 ? 1 : 0; }
 
-int32_t gigl_sage_plan_fused_layers(gigl_sage_plan* p) { return p && fused2_on(p) ? 1 : 0; }
+int32_t gigl_sage_plan_fused_layers(gigl_sage_plan* p) { return p && p->fused2 ? 1 : 0; }
 
 int32_t gigl_sage_plan_set_aggr(gigl_sage_plan* p, int32_t aggr) {
   if (!p) return GIGL_E_INVALID_ARG;
   GIGL_REQUIRE(p->ctx, aggr == GIGL_AGGR_MEAN || aggr == GIGL_AGGR_SUM || aggr == GIGL_AGGR_MAX, "bad aggr %d", aggr);
   GIGL_REQUIRE(p->ctx, p->kind == 0, "the reduction applies to SAGE layers");
-  if (p->aggr != aggr && p->captured) {  // (the reduction is baked into the captured launches)
-    hipStreamSynchronize(p->ctx->stream);
-    drop_graphs(p);
-  }
+  const bool changed = p->aggr != aggr;
   p->aggr = aggr;
+  if (changed) plan_invalidate(p);  // (the reduction is baked into the captured launches)
   return plan_refresh_half_split(p);  // (a sum's operand is bounded by fan-out times the table's largest magnitude)
 }
 
@@ -1257,11 +1334,9 @@ int32_t gigl_sage_plan_set_projected_input(gigl_sage_plan* p, const float* proj)
                  "projected input needs a linear reduction: lin(max_j x_j) != max_j lin(x_j)");
     GIGL_REQUIRE(ctx, (p->dims[1] & 3) == 0 && p->dims[1] <= 2048, "projected input: first-layer width %d", p->dims[1]);
   }
-  if (p->captured && p->proj != proj) {  // the pointer is baked into the captured launches
-    hipStreamSynchronize(ctx->stream);
-    drop_graphs(p);
-  }
+  const bool changed = p->proj != proj;
   p->proj = proj;
+  if (changed) plan_invalidate(p);  // (the pointer is baked into the captured launches)
   return GIGL_OK;
 }
 
@@ -1270,11 +1345,8 @@ int32_t gigl_sage_plan_set_groups(gigl_sage_plan* p, int32_t group_roots) {
   gigl_ctx* ctx = p->ctx;
   GIGL_REQUIRE(ctx, group_roots >= 1 && p->b % group_roots == 0, "group_roots=%d does not divide the plan's b=%d",
                group_roots, p->b);
-  if (p->captured) {  // the group split is baked into the captured kernels
-    hipStreamSynchronize(ctx->stream);
-    drop_graphs(p);
-  }
   p->group_roots = group_roots;
+  plan_invalidate(p);  // (the group split is baked into the captured kernels)
   return GIGL_OK;
 }
 
@@ -1354,9 +1426,8 @@ int32_t gigl_sage_plan_run_part(gigl_sage_plan* p, const uint32_t* roots, int32_
   GIGL_REQUIRE(ctx, roots && out && (part == GIGL_PLAN_PART_GRAPH || part == GIGL_PLAN_PART_LAYERS), "bad argument");
   if (mode == GIGL_MODE_REPLACE)
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "the one-call plan needs duplicate-free trees (no with-replacement mode)");
-  const int n = n_stages(p);
-  return part == GIGL_PLAN_PART_GRAPH ? enqueue_range(p, 0, 2, roots, sampling_seed, mode, out)
-                                      : enqueue_range(p, 2, n, roots, sampling_seed, mode, out);
+  const RunArgs a{roots, sampling_seed, mode, out};
+  return part == GIGL_PLAN_PART_GRAPH ? run_steps(p, 0, GRAPH_STEPS, a) : run_steps(p, GRAPH_STEPS, p->n_steps, a);
 }
 
 int32_t gigl_sage_plan_run(gigl_sage_plan* p, const uint32_t* roots, int32_t sampling_seed, int32_t mode,
@@ -1366,7 +1437,7 @@ int32_t gigl_sage_plan_run(gigl_sage_plan* p, const uint32_t* roots, int32_t sam
   GIGL_REQUIRE(ctx, roots && out, "null argument");
   if (mode == GIGL_MODE_REPLACE)
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "the one-call plan needs duplicate-free trees (no with-replacement mode)");
-  if (!p->use_graph) return enqueue_range(p, 0, n_stages(p), roots, sampling_seed, mode, out);
+  if (!p->use_graph) return run_steps(p, 0, p->n_steps, {roots, sampling_seed, mode, out});
 
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   // (another plan on this ctx may have grown — reallocated — the arena since the capture: the graphs' scratch addresses
@@ -1379,7 +1450,7 @@ int32_t gigl_sage_plan_run(gigl_sage_plan* p, const uint32_t* roots, int32_t sam
     // which may happen inside a capture.  (This batch is produced by that run.)
     const uint32_t keep_mask = ctx->prof_mask;
     ctx->prof_mask = 0;
-    int32_t rc = enqueue_range(p, 0, n_stages(p), roots, sampling_seed, mode, out);
+    int32_t rc = run_steps(p, 0, p->n_steps, {roots, sampling_seed, mode, out});
     ctx->prof_mask = keep_mask;
     if (rc != GIGL_OK) return rc;
     GIGL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1395,39 +1466,29 @@ int32_t gigl_sage_plan_run(gigl_sage_plan* p, const uint32_t* roots, int32_t sam
     p->cap_arena_gen = ctx->arena_gen;
     return GIGL_OK;
   }
+  // A split plan runs its graph part on the plan's graph stream: behind whatever produced `roots` on the ctx stream, and
+  // behind the layers of the previous call (they read the union graph this call's graph part rewrites).  Without a graph
+  // stream the graph part's stream is the ctx stream, and nothing has to wait
+  hipStream_t cs = ctx->stream, gs = p->split ? p->gstream : cs;
   if (p->split) {
-    // graph part on the plan's graph stream: behind whatever produced `roots` on the ctx stream, and behind the layers of
-    // the previous call (they read the union graph this call's graph part rewrites)
-    GIGL_HIP_CHECK(ctx, hipEventRecord(p->ev_in, ctx->stream));
-    GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(p->gstream, p->ev_in, 0));
-    GIGL_HIP_CHECK(ctx, hipMemcpyAsync(p->roots_buf, roots, (size_t)p->b * 4, hipMemcpyDeviceToDevice, p->gstream));
-    hipStream_t keep = ctx->stream;
-    bool joined = false;
-    for (const Segment& sg : p->segs) {
-      const bool gpart = sg.s1 <= GRAPH_STAGES;
-      if (!gpart && !joined) {  // the layers wait for the graph part
-        GIGL_HIP_CHECK(ctx, hipEventRecord(p->ev_graph, p->gstream));
-        GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(keep, p->ev_graph, 0));
-        joined = true;
-      }
-      ctx->stream = gpart ? p->gstream : keep;
-      int32_t rc = GIGL_OK;
-      if (sg.exec) {
-        if (hipGraphLaunch(sg.exec, ctx->stream) != hipSuccess) rc = GIGL_E_HIP;
-      } else {
-        rc = enqueue_range(p, sg.s0, sg.s1, p->roots_buf, sampling_seed, mode, out);
-      }
-      ctx->stream = keep;
-      if (rc != GIGL_OK) return rc == GIGL_E_HIP ? gigl_fail(ctx, rc, "hipGraphLaunch failed") : rc;
-    }
-    return GIGL_OK;
+    GIGL_HIP_CHECK(ctx, hipEventRecord(p->ev_in, cs));
+    GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(gs, p->ev_in, 0));
   }
-  GIGL_HIP_CHECK(ctx, hipMemcpyAsync(p->roots_buf, roots, (size_t)p->b * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  for (const Segment& sg : p->segs) {
+  GIGL_HIP_CHECK(ctx, hipMemcpyAsync(p->roots_buf, roots, (size_t)p->b * 4, hipMemcpyDeviceToDevice, gs));
+  bool joined = !p->split;
+  for (int i = 0; i < p->n_segs; ++i) {
+    const Segment& sg = p->segs[i];
+    const bool gpart = sg.s1 <= GRAPH_STEPS;
+    if (!gpart && !joined) {  // the layers wait for the graph part
+      GIGL_HIP_CHECK(ctx, hipEventRecord(p->ev_graph, gs));
+      GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(cs, p->ev_graph, 0));
+      joined = true;
+    }
+    StreamScope on(ctx, gpart ? gs : cs);
     if (sg.exec) {
       GIGL_HIP_CHECK(ctx, hipGraphLaunch(sg.exec, ctx->stream));
     } else {
-      int32_t rc = enqueue_range(p, sg.s0, sg.s1, p->roots_buf, sampling_seed, mode, out);
+      const int32_t rc = run_steps(p, sg.s0, sg.s1, {p->roots_buf, sampling_seed, mode, out});
       if (rc != GIGL_OK) return rc;
     }
   }
@@ -1519,13 +1580,6 @@ struct SageTrainEnc {
 
 namespace {
 
-void* train_alloc(std::vector<void*>& owned, size_t bytes) {
-  void* q = nullptr;
-  if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-  owned.push_back(q);
-  return q;
-}
-
 // the shapes and parameters (s.L is set), Adam's moments (zero) and the W_l^T buffers
 bool sage_shared_alloc(SageTrainShared& s, std::vector<void*>& owned, const int32_t* dims, float* const* w, float* const* bias) {
   bool ok = true;
@@ -1537,11 +1591,11 @@ bool sage_shared_alloc(SageTrainShared& s, std::vector<void*>& owned, const int3
     const size_t nw = (size_t)dims[l + 1] * 2 * dims[l];
     for (int k = 0; k < 4; ++k) {
       const size_t n = k < 2 ? nw : (size_t)dims[l + 1];
-      s.mom[4 * l + k] = (float*)train_alloc(owned, n * 4);
+      s.mom[4 * l + k] = (float*)plan_alloc(owned, n * 4);
       ok = ok && s.mom[4 * l + k] && hipMemset(s.mom[4 * l + k], 0, n * 4) == hipSuccess;
     }
     if (l >= 1) {
-      s.wt_l[l] = (float*)train_alloc(owned, nw * 4);
+      s.wt_l[l] = (float*)plan_alloc(owned, nw * 4);
       ok = ok && s.wt_l[l];
     }
   }
@@ -1563,17 +1617,17 @@ bool sage_enc_alloc(const SageTrainShared& s, SageTrainEnc& e, std::vector<void*
     e.rows_cap[l] = rows;
     if (grads) *zero_floats += (size_t)n_out * k2 + n_out;
     if (l >= 1) *da_floats = std::max(*da_floats, (size_t)rows * k2);
-    e.a[l] = (float*)train_alloc(owned, (size_t)rows * k2 * 4);
-    e.h[l] = (float*)train_alloc(owned, (size_t)rows * n_out * 4);
+    e.a[l] = (float*)plan_alloc(owned, (size_t)rows * k2 * 4);
+    e.h[l] = (float*)plan_alloc(owned, (size_t)rows * n_out * 4);
     if (sage_dh_cleared(s, l)) {
       *zero_floats += (size_t)rows * n_out;
     } else {
-      e.dh[l] = (float*)train_alloc(owned, (size_t)rows * n_out * 4);
+      e.dh[l] = (float*)plan_alloc(owned, (size_t)rows * n_out * 4);
       ok = ok && e.dh[l];
     }
     const int64_t chunks = gigl_linear_weight_grad_chunks(rows, n_out, k2, &e.part_rc[l]);
-    e.part_w[l] = (float*)train_alloc(owned, (size_t)chunks * n_out * k2 * 4);
-    e.part_b[l] = (float*)train_alloc(owned, (size_t)chunks * n_out * 4);
+    e.part_w[l] = (float*)plan_alloc(owned, (size_t)chunks * n_out * k2 * 4);
+    e.part_b[l] = (float*)plan_alloc(owned, (size_t)chunks * n_out * 4);
     ok = ok && e.a[l] && e.h[l] && e.part_w[l] && e.part_b[l];
   }
   return ok;
@@ -1599,7 +1653,7 @@ float* sage_enc_carve(const SageTrainShared& s, SageTrainEnc& e, bool grads, flo
 // the transposed lists of layers >= 1 for one workspace (cap_edges: its union graph's) of the encode
 bool sage_tlists_alloc(const SageTrainShared& s, const SageTrainEnc& e, std::vector<void*>& owned, int64_t cap_edges, int32_t** tl) {
   for (int l = 1; l < s.L && s.bwd_gather; ++l) {
-    tl[l] = (int32_t*)train_alloc(owned, (size_t)gigl_transposed_rows_words(e.rows_cap[l - 1], cap_edges) * 4);
+    tl[l] = (int32_t*)plan_alloc(owned, (size_t)gigl_transposed_rows_words(e.rows_cap[l - 1], cap_edges) * 4);
     if (!tl[l]) return false;
   }
   return true;
@@ -1608,7 +1662,7 @@ bool sage_tlists_alloc(const SageTrainShared& s, const SageTrainEnc& e, std::vec
 // the graph part of one root set, on workspace p's ctx: sample + union (+ the level guard) ...
 int32_t sage_enqueue_graph(const SageTrainShared& s, const SageTrainEnc& e, gigl_sage_plan* p, int32_t* const* tl,
                            int32_t sampling_seed, int32_t mode) {
-  int32_t rc = enqueue_range(p, 0, 2, p->roots_buf, sampling_seed, mode, nullptr);
+  int32_t rc = run_steps(p, 0, GRAPH_STEPS, {p->roots_buf, sampling_seed, mode, nullptr});
   // ... and who reads which source row in the backward of layers >= 1 (a function of the batch graph alone)
   for (int l = 1; l < s.L && rc == GIGL_OK && s.bwd_gather; ++l)
     rc = gigl_transposed_rows_build(p->ctx, p->un.rowptr, p->un.rowend, p->un.col, p->un.meta + GIGL_META_LEVEL0 + (s.L - 1 - l),
@@ -1637,7 +1691,7 @@ int32_t sage_enc_forward(gigl_ctx* ctx, const SageTrainShared& s, const SageTrai
                          int encode, const int32_t* step_dev) {
   const int L = s.L;
   int32_t rc = GIGL_OK;
-  const int32_t* n_local = p->leaf_global ? (L >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (L - 2) : p->zero_dev) : nullptr;
+  const int32_t* n_local = first_global_row(p);
   for (int l = 0; l < L; ++l) {
     const int32_t* n_rows = p->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
     const int d = s.dims[l];
@@ -1998,7 +2052,7 @@ int32_t gigl_sage_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat*
   t->beta2 = beta2;
   t->eps = eps;
   t->wd = weight_decay;
-  auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
+  auto alloc = [&](size_t bytes) { return plan_alloc(t->owned, bytes); };
   size_t zero_floats = 0, da_floats = 16;
   bool ok = sage_shared_alloc(*t, t->owned, dims, w, bias);
   // (no entry point hands this plan's gradients out: the cleared block is the dh rows alone)
@@ -2744,7 +2798,7 @@ int32_t lp_create_workspaces(gigl_nablp_train_plan* t, gigl_graph* graph, gigl_f
 // the head over embeddings of width d: the encodes' root rows, repeated queries, candidates, ids, validity, scores, their
 // gradients, the loss words; consts = {Q, C, Adam's step counter}
 bool lp_head_alloc(gigl_nablp_train_plan* t, size_t d) {
-  auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
+  auto alloc = [&](size_t bytes) { return plan_alloc(t->owned, bytes); };
   const size_t Q = (size_t)t->b * t->P, Cn = (size_t)t->cand_cols();
   bool ok = true;
   for (SageTrainEnc& e : t->enc) {
@@ -2871,7 +2925,7 @@ int32_t gigl_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat
     gigl_nablp_train_plan_destroy(t);
     return rc;
   }
-  auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
+  auto alloc = [&](size_t bytes) { return plan_alloc(t->owned, bytes); };
   size_t zero_floats = 0, da_floats = 16;
   bool ok = sage_shared_alloc(*t, t->owned, dims, w, bias);
   // (gw | gb are part of the cleared block: gigl_nablp_train_plan_grads adds the partial sums up into them)
@@ -3018,8 +3072,8 @@ int32_t gigl_nablp_train_plan_set_clip_grad_norm(gigl_nablp_train_plan* t, float
   GIGL_REQUIRE(ctx, std::isfinite(max_norm) && max_norm > 0.f, "max_norm must be finite and > 0");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (!t->clip.partials) {
-    t->clip.partials = (double*)train_alloc(t->owned, (size_t)ADAM_MAX * ADAM_GRID_X_MAX * sizeof(double));
-    t->clip.out2 = (float*)train_alloc(t->owned, 16);
+    t->clip.partials = (double*)plan_alloc(t->owned, (size_t)ADAM_MAX * ADAM_GRID_X_MAX * sizeof(double));
+    t->clip.out2 = (float*)plan_alloc(t->owned, 16);
     if (!t->clip.partials || !t->clip.out2) {
       t->clip = AdamClip{};
       return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the gradient norm's partial sums failed");
@@ -3084,7 +3138,7 @@ static bool gat_moments_alloc(std::vector<void*>& owned, PlanTensor* tb, int fir
   for (int s = first; s < last; ++s)
     for (float** q : {&tb[s].m, &tb[s].v}) {
       const size_t bytes = (size_t)(tb[s].n ? tb[s].n : 1) * 4;
-      *q = (float*)train_alloc(owned, bytes);
+      *q = (float*)plan_alloc(owned, bytes);
       if (!*q || hipMemset(*q, 0, bytes) != hipSuccess) return false;
     }
   return true;
@@ -3557,7 +3611,7 @@ int32_t gat_lp_finish(gigl_nablp_train_plan* t) {
 // a stream's backward scratch, for encodes of up to rows1 nodes of level <= 1, cap_edges edges and b roots
 static bool gat_scratch_alloc(gigl_nablp_train_plan* t, GatScratch& s, gigl_ctx* stream_ctx, int64_t rows1, int64_t cap_edges, int64_t b) {
   const auto& g = t->gat;
-  auto alloc = [&](int64_t floats) { return (float*)train_alloc(t->owned, (size_t)floats * 4); };
+  auto alloc = [&](int64_t floats) { return (float*)plan_alloc(t->owned, (size_t)floats * 4); };
   s.ctx = stream_ctx;
   s.rows1 = rows1;
   s.b = b;
@@ -3573,8 +3627,8 @@ static bool gat_scratch_alloc(gigl_nablp_train_plan* t, GatScratch& s, gigl_ctx*
 // ... and what the message weights' backward adds to it
 static bool gat_scratch_alloc_edge(gigl_nablp_train_plan* t, GatScratch& s) {
   const auto& g = t->gat;
-  s.dze = (float*)train_alloc(t->owned, (size_t)s.rows1 * g.heads * g.e.De * 4);
-  s.z1 = (float*)train_alloc(t->owned, (size_t)s.b * g.e.De * 4);
+  s.dze = (float*)plan_alloc(t->owned, (size_t)s.rows1 * g.heads * g.e.De * 4);
+  s.z1 = (float*)plan_alloc(t->owned, (size_t)s.b * g.e.De * 4);
   return s.dze && s.z1;
 }
 
@@ -3627,7 +3681,7 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
   // every node of the batch graph is numbered: gigl_gat_input_aggregate reads its sources through un.nodes
   for (int wi = 0; wi < gigl_nablp_train_plan::WS; ++wi)
     for (gigl_sage_plan* bp : t->ring.slot[wi].base) bp->leaf_global = false;
-  auto alloc = [&](size_t bytes) { return train_alloc(t->owned, bytes); };
+  auto alloc = [&](size_t bytes) { return plan_alloc(t->owned, bytes); };
   bool ok = true;
   // (default on, GIGL_LP_FORK=0 off, as the GraphSAGE plan: the forked step's layers part launched eagerly)
   const bool want_fork = lp_fork_wanted(t);
@@ -3762,8 +3816,8 @@ int32_t gigl_gat_nablp_train_plan_set_edge_features(gigl_nablp_train_plan* t, gi
     return 2 * half;
   };
   ge.zero_bytes = lay_out(nullptr) * 4;
-  ge.zero_base = train_alloc(t->owned, ge.zero_bytes);
-  ge.v = (float*)train_alloc(t->owned, nv * 4);
+  ge.zero_base = plan_alloc(t->owned, ge.zero_bytes);
+  ge.v = (float*)plan_alloc(t->owned, nv * 4);
   bool ok = ge.zero_base && ge.v;
   if (ok) lay_out((float*)ge.zero_base);
   for (int l = 0; l < 2; ++l)  // a shared message weight's gradient joins lin_edge.weight's, on both streams
@@ -3772,7 +3826,7 @@ int32_t gigl_gat_nablp_train_plan_set_edge_features(gigl_nablp_train_plan* t, gi
   ok = ok && gat_moments_alloc(t->owned, g.tensor, GAT_CORE, GAT_TENSORS);
   if (any_msg && ok) {
     for (int k = 0; k < 2; ++k) {
-      ge.ze[k] = (float*)train_alloc(t->owned, (size_t)t->enc[k].rows_cap[0] * H * De * 4);
+      ge.ze[k] = (float*)plan_alloc(t->owned, (size_t)t->enc[k].rows_cap[0] * H * De * 4);
       ok = ok && ge.ze[k];
     }
     for (int k = 0; k < (fork ? 2 : 1); ++k) ok = ok && gat_scratch_alloc_edge(t, g.sc[k]);

@@ -1,11 +1,13 @@
 """TEST INFRASTRUCTURE ONLY: the cases, inputs, float64 reference, per-element bounds and exact probes of
 tests/test_gpu_sage_plan_layers.py, plus a plain-Python mirror of the GraphSAGE plan's dispatch rule (csrc/pipeline.hip
-enqueue_stage / fused2_on / plan_refresh_half_split) and of the half-split scales the library derives on the device
+step_sage_reduce / step_sage_project / fused2_on / plan_refresh_half_split) and of the half-split scales the library derives on the device
 (hs_scale_kernel, hs_chain_kernel, fused2_scale_kernel in csrc/agg.hip).
 
-Run as a program (`python tests/sage_plan_cases.py hs_layers|bf16`) it is the CHILD of the knob tests: GIGL_PLAN_HS_LAYERS
-and GIGL_GEMM_SPLIT are read once per process, so the parent sets one of them in the child's environment; the child runs
-that knob's cases once and prints one line `CASE {json}` per case (label, kernels, err, fp32, ratio, eps, fails).
+Run as a program (`python tests/sage_plan_cases.py hs_layers|bf16|f2_all_wr`) it is the CHILD of the knob tests:
+GIGL_PLAN_HS_LAYERS, GIGL_GEMM_SPLIT and GIGL_F2_ALL_WR are read once per process, so the parent sets one of them in the
+child's environment; the child runs that knob's cases once and prints one line `CASE {json}` per case (label, kernels,
+err, fp32, ratio, eps, fails, digest).  Under GIGL_F2_ALL_WR the fused projection must give the very rows it gives without:
+that child prints each fused case's digest, and the parent compares it with its own run of the case.
 
 Reference.  A plain float64 formula over the very tensors uploaded, row by row over an edge list:
     h_{l+1}[i] = act( reduce_{j -> i} h_l[j] . W_l^T + b + h_l[i] . W_r^T ),   reduce = mean | sum | max (0 for no edge)
@@ -33,6 +35,7 @@ The scales s are recomputed from the inputs the way the kernels do; nothing come
 below 1e-5: a missing plane product costs ~2^-12 S and fails.
 """
 import functools
+import hashlib
 import json
 import math
 import os
@@ -207,7 +210,7 @@ def _probe(label, **kw):
 
 def probe_cases():
     """exact probes: integer tables / weights / biases (sum on the main graph, mean where every degree is a power of
-    two), the column identity, history independence; repeatability and GIGL_F2_ALL_WR ride on every run"""
+    two), the column identity, history independence; repeatability rides on every run"""
     out = [_probe("int fused sum", aggr="sum", roots="inside"), _probe("int fused mean", graph="pow2", roots="inside"),
            _probe("int fused sum groups3 nobias", aggr="sum", groups=3, roots="groups", bias=False, d_in=44, n_out=48),
            _probe("int fused mean l2 out1", graph="pow2", n_out=1, l2=True)]
@@ -238,6 +241,8 @@ def child_cases(mode: str):
                                                                          aggr="sum", table="f16", roots="small", n_out=70),
                 _case("child hs_layers h256 nofuse", no_fuse2=True), _case("child hs_layers fused", d_in=44),
                 _probe("child hs_layers int h64 sum", hidden=[64], aggr="sum")]
+    if mode == "f2_all_wr":  # every case that runs the fused pair of layers: the rows must not depend on the knob
+        return fused_cases() + [c for c in probe_cases() if " fused" in c["label"]]
     assert mode == "bf16", mode  # no half split anywhere: no fused layers, fp16 tables take the [mean | self] operand
     return [_case("child bf16 h256 d36"), _case("child bf16 h256 sum f16", aggr="sum", table="f16"),
             _case("child bf16 h64 L2 f16", hidden=[64], table="f16"), _case("child bf16 h132 L3 max", hidden=[132, 132],
@@ -652,12 +657,12 @@ def _dev_roots(eng, roots):
 
 def run_case(engs, case, knob: str = ""):
     """one case -> {label, kernels, err, fp32, ratio, eps, fails}: the graph check first, then the verdict of the case's
-    kind, repeatability and (fused) GIGL_F2_ALL_WR on every case"""
+    kind and repeatability on every case; digest: sha256 of the first run's rows"""
     inp = case_inputs(case, knob)
     eng = engs.get(case)
     eng.load_features(inp["x"])
     disp = dispatch(case, inp["x"], knob)
-    r = dict(label=case["label"], kernels=sorted(disp["kernels"]), err=0.0, fp32=0.0, ratio=0.0, eps=0.0, fails=[])
+    r = dict(label=case["label"], kernels=sorted(disp["kernels"]), err=0.0, fp32=0.0, ratio=0.0, eps=0.0, fails=[], digest="")
     fails = r["fails"]
     plan = make_plan(eng, case, inp)
     try:
@@ -665,6 +670,7 @@ def run_case(engs, case, knob: str = ""):
             fails.append("dispatch: fused %s half split %s" % (plan.fused_layers(), plan.half_split()))
         roots = _dev_roots(eng, inp["roots"])
         out = plan.run(roots).cpu().numpy()
+        r["digest"] = hashlib.sha256(np.ascontiguousarray(out).tobytes()).hexdigest()
         hb = plan.last_batch_to_host()
         ext = plan_ext(case, hb)
         if hb["meta"][META_OVERFLOW] != 0 or ext is None or not np.array_equal(ext["keys"], inp["ext"]["keys"]):
@@ -675,13 +681,6 @@ def run_case(engs, case, knob: str = ""):
             fails.append("graph: layout %s != %s" % ((ext["n_roots"], ext["n_rows"]), want))
         if not np.array_equal(plan.run(roots).cpu().numpy(), out, equal_nan=True):
             fails.append("repeatability")
-        if disp["fused"]:
-            os.environ["GIGL_F2_ALL_WR"] = "1"
-            try:
-                if not np.array_equal(plan.run(roots).cpu().numpy(), out, equal_nan=True):
-                    fails.append("GIGL_F2_ALL_WR")
-            finally:
-                del os.environ["GIGL_F2_ALL_WR"]
         x64 = inp["x"].float().numpy().astype(np.float64)
         if case["kind"] == "tol":
             params = params_of(case, disp, inp["x"], inp["weights"], inp["biases"], ext)
@@ -727,6 +726,25 @@ def run_case(engs, case, knob: str = ""):
     return r
 
 
+def run_digest(engs, case):
+    """the case's rows only -> {label, fused, digest, fails}: what a process run under a knob that must not change a bit
+    reports for the comparison with run_case's digest of a process without it (the float64 verdict is that process's)"""
+    inp = case_inputs(case)
+    eng = engs.get(case)
+    eng.load_features(inp["x"])
+    plan = make_plan(eng, case, inp)
+    try:
+        roots = _dev_roots(eng, inp["roots"])
+        out = plan.run(roots).cpu().numpy()
+        r = dict(label=case["label"], fused=bool(plan.fused_layers()), fails=[],
+                 digest=hashlib.sha256(np.ascontiguousarray(out).tobytes()).hexdigest())
+        if not np.array_equal(plan.run(roots).cpu().numpy(), out, equal_nan=True):
+            r["fails"].append("repeatability")
+        return r
+    finally:
+        plan.close()
+
+
 def layout_of(case):
     """(distinct roots, rows of the first layer) the layout cases rely on — None where the case does not care.  From the
     oracle; tests/test_gpu_sage_plan_layers.py checks the three layouts against the 128-row tile"""
@@ -741,11 +759,11 @@ def format_case(r) -> str:
 
 
 def main(mode: str) -> int:
-    var = {"hs_layers": "GIGL_PLAN_HS_LAYERS", "bf16": "GIGL_GEMM_SPLIT"}[mode]
+    var = {"hs_layers": "GIGL_PLAN_HS_LAYERS", "bf16": "GIGL_GEMM_SPLIT", "f2_all_wr": "GIGL_F2_ALL_WR"}[mode]
     assert os.environ.get(var), "the knob is not set"
     engs = Engines()
     for case in child_cases(mode):
-        print("CASE " + json.dumps(run_case(engs, case, mode)), flush=True)
+        print("CASE " + json.dumps(run_digest(engs, case) if mode == "f2_all_wr" else run_case(engs, case, mode)), flush=True)
     engs.close()
     return 0
 

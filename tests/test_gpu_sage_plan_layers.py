@@ -7,7 +7,7 @@ gigl_gather_project_mixed (projected input) and l2_normalize_rows_kernel — eve
 formula on the plan's OWN union graph (SagePlan.last_batch_to_host), after that graph's edge multiset (global ids) has
 been found equal to the CPU oracle's (oracle.sample_khop(canonical=True) + oracle.union_build): a mismatch there is a
 GRAPH failure, reported as such, never a numeric one.  Cases, inputs, reference, bounds and probes live in
-tests/sage_plan_cases.py (its docstring derives the bounds; it is also the child process of the two knob tests).
+tests/sage_plan_cases.py (its docstring derives the bounds; it is also the child process of the knob tests).
 
 Graph: 640 nodes built by hand — in-degrees 0, 1, 2, 3, 4, exactly the first fan-out (5), 10 and 14, a hub of 40 in-edges that
 is an in-neighbour of every fourth node (its union row merges the samples of ~40 occurrences: 38 edges at fan-outs
@@ -20,7 +20,8 @@ nodes' feature rows are redrawn), so the relu masks agree with the reference by 
 bit): integer tables in [-8, 8], weights in {-2..2}, integer biases, under a sum and under a mean over power-of-two
 degrees, on the fused path and on every path apart; the column identity (the last layer selects one hidden column per
 output, all 256 columns in six set_weights calls of 48 outputs); history independence (300 distinct roots, then 5, equal
-to a fresh plan); GIGL_F2_ALL_WR set and unset; a second run equal to the first (the last two on EVERY case).
+to a fresh plan); a second run equal to the first, on EVERY case; GIGL_F2_ALL_WR set — the library reads it once per
+process, so in a child process of its own — gives every fused case the rows of this process, where it is unset.
 
 BUG FOUND by `fused sum headroom`, `apart h64 sum headroom` and the cases next to them, and its fix: under a sum the
 half-split scales assumed |operand| <= max fan-out x max|x| (and x fan-out again per layer in hs_chain_kernel), but a union
@@ -54,8 +55,8 @@ two layers and more on three, where each layer's error is carried on over S / |h
 low-plane MFMA — 1e-4 S — fails every fused case of more than four output elements at 1.8 .. 11 x its bound.)  Every exact
 probe held on every case.
 
-The file: 85 GPU tests (63 tolerance cases and 20 exact probes here, 5 + 5 cases in the two children) and 4 CPU tests,
-11.6 s in all on the GPU machine: the two children 2.3 s and 2.2 s, the margin test 1.9 s, every other test under 0.4 s.
+The file: 86 GPU tests (63 tolerance cases and 20 exact probes here, 5 + 5 cases in the two knob children, the 34 fused
+cases in the GIGL_F2_ALL_WR child) and 4 CPU tests.
 """
 import json
 import os
@@ -87,16 +88,25 @@ def _verdict(r):
 
 
 # ---- GPU: this process (no knob) ------------------------------------------------------------------------------------
+_DIGESTS = {}  # label -> sha256 of the case's rows in THIS process (no knob)
+
+
+def _run(engs, case):
+    r = sc.run_case(engs, case)
+    _DIGESTS[case["label"]] = r["digest"]
+    return r
+
+
 @gpu
 @pytest.mark.parametrize("case", sc.default_cases(), ids=_id)
 def test_plan_case_against_float64(engs, case):
-    _verdict(sc.run_case(engs, case))
+    _verdict(_run(engs, case))
 
 
 @gpu
 @pytest.mark.parametrize("case", sc.probe_cases(), ids=_id)
 def test_plan_exact_probe(engs, case):
-    _verdict(sc.run_case(engs, case))
+    _verdict(_run(engs, case))
 
 
 # ---- GPU: one fresh child process per knob --------------------------------------------------------------------------
@@ -115,6 +125,28 @@ def test_knob_cases_in_a_child_process(mode, var, value):
     assert [r["label"] for r in rows] == [c["label"] for c in sc.child_cases(mode)]
     bad = [(sc.format_case(r), r["fails"]) for r in rows if r["fails"]]
     assert not bad, bad
+
+
+@gpu
+def test_f2_all_wr_in_a_child_process_changes_no_bit_of_a_fused_case(engs):
+    """GIGL_F2_ALL_WR=1 (every tile of the fused projection computes the W_r block, not only the tiles that hold roots) is
+    read once per process: a child runs every fused case with it, this process — which must run without — has or takes
+    the same cases' rows, and the two agree bit for bit"""
+    assert "GIGL_F2_ALL_WR" not in os.environ, "the comparison needs this process to run with the knob unset"
+    env = dict(os.environ)
+    for v in ("GIGL_PLAN_HS_LAYERS", "GIGL_GEMM_SPLIT", "GIGL_LINEAR_EXACT", "GIGL_PLAN_NO_FUSE2"):
+        env.pop(v, None)
+    env["GIGL_F2_ALL_WR"] = "1"
+    p = subprocess.run([sys.executable, os.path.abspath(sc.__file__), "f2_all_wr"], env=env, capture_output=True, text=True, timeout=240)
+    rows = [json.loads(line[5:]) for line in p.stdout.splitlines() if line.startswith("CASE ")]
+    assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
+    cases = sc.child_cases("f2_all_wr")
+    assert [r["label"] for r in rows] == [c["label"] for c in cases] and len(cases) >= 30
+    bad = [(r["label"], r["fails"]) for r in rows if r["fails"] or not r["fused"]]
+    assert not bad, bad
+    for r, case in zip(rows, cases):
+        here = _DIGESTS.get(case["label"]) or _run(engs, case)["digest"]
+        assert len(here) == 64 and r["digest"] == here, ("GIGL_F2_ALL_WR changes the rows of", case["label"])
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------
