@@ -17,6 +17,8 @@ GIGL_META_N_NODES, GIGL_META_N_EDGES, GIGL_META_LEVEL0, GIGL_META_OVERFLOW = 0, 
 # words of an evaluation accumulator (gigl_lp_rank_metrics / gigl_nablp_train_plan_eval: doubles)
 LP_EVAL_LOSS_SUM, LP_EVAL_BATCHES, LP_EVAL_MRR_SUM, LP_EVAL_RANK_NODES, LP_EVAL_HITS0 = 0, 1, 2, 3, 4
 LP_EVAL_MAX_KS, LP_EVAL_LEN = 8, 16
+# the link-prediction plans' task (gigl_nablp_train_plan_set_task / gigl_lp_task_loss: GIGL_LP_TASK_*)
+LP_TASKS = {"Retrieval": 0, "Margin": 1, "Softmax": 2}
 LOC_HOST, LOC_DEVICE = 0, 1
 DTYPE_F32, DTYPE_F16 = 0, 1
 MODE_SPARK_HASH, MODE_FAST, MODE_REPLACE = 0, 1, 2
@@ -69,6 +71,7 @@ SYMBOLS = [
     "gigl_sage_train_plan_create", "gigl_sage_train_plan_step", "gigl_sage_train_plan_step2", "gigl_sage_train_plan_loss", "gigl_sage_train_plan_destroy",
     "gigl_nablp_train_plan_create", "gigl_nablp_train_plan_step", "gigl_nablp_train_plan_step2", "gigl_gat_nablp_train_plan_create", "gigl_gat_nablp_train_plan_grads", "gigl_gat_nablp_train_plan_set_edge_features", "gigl_gat_nablp_train_plan_edge_grads", "gigl_nablp_train_plan_loss", "gigl_nablp_train_plan_destroy", "gigl_nablp_train_plan_grads", "gigl_nablp_train_plan_set_clip_grad_norm", "gigl_nablp_train_plan_set_constant_lr", "gigl_nablp_train_plan_grad_norm",
     "gigl_lp_rank_metrics", "gigl_nablp_train_plan_eval", "gigl_nablp_train_plan_adam_steps",
+    "gigl_lp_task_loss", "gigl_lp_task_loss_backward", "gigl_nablp_train_plan_set_task",
     "gigl_sage_train_plan_set_dropout", "gigl_nablp_train_plan_set_dropout", "gigl_dropout_mask",
 ]
 
@@ -448,6 +451,9 @@ def load() -> C.CDLL:
         "gigl_dropout_mask": [vp, C.c_uint64, C.c_uint32, i32, i32, i64, i32, C.c_float, vp],
         "gigl_lp_rank_metrics": [vp, vp, i64, i32, i32, vp, i32, i32, vp, P(i32), i32, vp],
         "gigl_nablp_train_plan_adam_steps": [vp, vp],
+        "gigl_lp_task_loss": [vp, i32, C.c_float, C.c_float, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+        "gigl_lp_task_loss_backward": [vp, i32, C.c_float, C.c_float, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+        "gigl_nablp_train_plan_set_task": [vp, i32, C.c_float, C.c_float],
         "gigl_nablp_train_plan_eval": [vp, vp, vp, vp, i32, i32, P(i32), i32, vp, vp],
         "gigl_gat_input_layer_fused": [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, i64, vp, i32,
                                        vp, vp],

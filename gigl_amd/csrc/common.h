@@ -128,6 +128,29 @@ int32_t gigl_lp_rank_metrics_enqueue(gigl_ctx* ctx, hipStream_t st, const float*
                                      const int32_t* pos_cnt, int32_t n_neg, int32_t neg_col0, const int32_t* neg_valid,
                                      const int32_t* ks, int32_t n_ks, const int32_t* meta_a, const int32_t* meta_b,
                                      double* part, double* acc);
+// the Margin / Softmax task over a score matrix in the link-prediction plan's layout (loss.hip; the contract is gigl_lp_task_loss's
+// in gigl_hip.h): what the three launches share.  pos_cnt may be NULL (valid alone decides)
+struct LpTaskHead {
+  int32_t kind;
+  float param, weight;  // margin | temperature; the task's weight
+  const float* scores;
+  int64_t ld;
+  int32_t b, P, H, n_rn;
+  const int32_t* pos_cnt;
+  const int32_t* valid;
+};
+// GIGL_E_INVALID_ARG for an unknown kind, a Softmax temperature <= 0, a non-finite margin, a weight not finite and > 0
+int32_t gigl_lp_task_check(gigl_ctx* ctx, int32_t kind, float param, float weight);
+// the row partials (one workgroup per query row) -> row_a, row_b [b P]
+void gigl_lp_task_rows_enqueue(hipStream_t st, const LpTaskHead& h, float* row_a, float* row_b);
+// {loss, valid rows, normaliser} -> out3 and *step += 1 (step, meta_a / meta_b may be NULL; a batch whose meta reports an overflow:
+// NaN loss, step unmoved); with eval_acc instead: acc[LOSS_SUM] += loss, acc[BATCHES] += 1, or *overflow_acc += 1
+void gigl_lp_task_sum_enqueue(hipStream_t st, const LpTaskHead& h, const float* row_a, const float* row_b, float* out3,
+                              int32_t* step, const int32_t* meta_a, const int32_t* meta_b, double* eval_acc,
+                              int32_t* overflow_acc);
+// d loss / d scores, every column of every row (rows ldd floats apart)
+void gigl_lp_task_backward_enqueue(hipStream_t st, const LpTaskHead& h, const float* row_a, const float* row_b,
+                                   const float* out3, float* dscores, int64_t ldd);
 // fills g->maxdeg from the resident rowptr (synchronises the ctx stream)
 int32_t gigl_graph_compute_maxdeg(gigl_ctx* ctx, gigl_graph* g);
 // the weight gradient's per-chunk partial sums without the reduction launch (agg.hip): see gigl_linear_weight_grad_parts

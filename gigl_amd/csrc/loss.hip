@@ -13,9 +13,13 @@
 // Row results go to row_lse / row_loss; a second single-workgroup launch adds the rows in a fixed order (the sum is
 // reproducible run to run).  Backward: dscores_ij = g * (softmax_ij - [i == j]) / temperature, 0 for excluded columns.
 // HBM-bound: 4*Q*C bytes read forward, read + written backward.
+// Further down: the Margin and Softmax tasks over the training plan's score matrix (gigl_lp_task_loss), the count-min sketch of
+// the sampling correction, the evaluation's rank metrics.
 #include "common.h"
 
 #include <cfloat>
+#include <cmath>
+#include <cstdint>
 
 namespace {
 
@@ -281,6 +285,286 @@ __global__ __launch_bounds__(1024) void lp_rank_sum_kernel(const double* __restr
   }
 }
 
+
+// ---- the Margin and Softmax tasks over the plan's score matrix (task.py:62-105, MarginLoss / SoftmaxLoss loss.py:21-174;
+// the contract is in include/gigl_hip.h at gigl_lp_task_loss).  Row q = i P + j is anchor i's positive j, its score the
+// diagonal entry; its negatives are the valid columns among its OWN anchor's H hard negatives and the valid random
+// negatives — 1 + H + n_rn entries of a C-wide row are read.  Three launches, as the retrieval loss': rows (one workgroup
+// per query row -> two partial words per row), sum (one workgroup, fp64, fixed order), backward (the whole dscores row).
+template <int KIND>
+struct TaskAcc;
+template <>
+struct TaskAcc<GIGL_LP_TASK_MARGIN> {  // x: hinge sum, y: active pairs (a pair at exactly 0 is active: clamp_min's gradient)
+  float x = 0.f, y = 0.f;
+  __device__ __forceinline__ void take(float s, float pos, float margin) {
+    const float h = (margin - pos) + s;
+    if (h >= 0.f) {
+      x += h;
+      y += 1.f;
+    }
+  }
+  __device__ __forceinline__ void merge(float x2, float y2) {
+    x += x2;
+    y += y2;
+  }
+};
+template <>
+struct TaskAcc<GIGL_LP_TASK_SOFTMAX> {
+  // x: running maximum m, y: sum of exp(v - m) over the terms seen WITHOUT the maximum's own 1 — lse = m + log1p(y): a row whose
+  // positive dominates has y ~ 1e-7 and a loss of that size, which 1 + y would round away
+  float x = -INFINITY, y = 0.f;
+  __device__ __forceinline__ void take(float s, float, float temperature) { merge(s / temperature, 0.f); }
+  __device__ __forceinline__ void merge(float x2, float y2) {
+    if (x2 > x) {
+      y = y2 + (y + 1.f) * expf(x - x2);  // (x == -inf: exp gives 0, nothing was seen)
+      x = x2;
+    } else if (x2 != -INFINITY) {
+      y += (y2 + 1.f) * expf(x2 - x);
+    }
+  }
+};
+
+__device__ __forceinline__ bool task_row_valid(const LpTaskHead& a, int q, int i) {
+  return a.valid[q] != 0 && (!a.pos_cnt || q - i * a.P < a.pos_cnt[i]);
+}
+__device__ __forceinline__ bool task_hard_valid(const LpTaskHead& a, int i, int k) {
+  return a.valid[a.b * a.P + i * a.H + k] != 0 && (!a.pos_cnt || k < a.pos_cnt[a.b + i]);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void lp_task_rows_kernel(LpTaskHead a, float* __restrict__ row_a, float* __restrict__ row_b) {
+  __shared__ float s_x[4], s_y[4];
+  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int i = q / a.P, Q = a.b * a.P, R0 = Q + a.b * a.H;
+  if (!task_row_valid(a, q, i)) {
+    if (tid == 0) {
+      row_a[q] = 0.f;
+      row_b[q] = 0.f;
+    }
+    return;
+  }
+  const float* row = a.scores + (int64_t)q * a.ld;
+  const float pos = row[q];
+  TaskAcc<KIND> acc;
+  if (KIND == GIGL_LP_TASK_SOFTMAX && tid == 0) acc.x = pos / a.param;  // the positive's own term
+  for (int k = tid; k < a.H; k += 256)
+    if (task_hard_valid(a, i, k)) acc.take(row[Q + i * a.H + k], pos, a.param);
+  // the random negatives' span: scalar up to a 16-byte boundary, then four columns per load, then the tail
+  const float* rn = row + R0;
+  const int32_t* vr = a.valid + R0;
+  int head = (int)((4u - (unsigned)(((uintptr_t)rn >> 2) & 3u)) & 3u);
+  if (head > a.n_rn) head = a.n_rn;
+  if (tid < head && vr[tid]) acc.take(rn[tid], pos, a.param);
+  const int nvec = (a.n_rn - head) >> 2;
+  for (int v = tid; v < nvec; v += 256) {
+    const int c = head + 4 * v;
+    const float4 x = *reinterpret_cast<const float4*>(rn + c);
+    if (vr[c]) acc.take(x.x, pos, a.param);
+    if (vr[c + 1]) acc.take(x.y, pos, a.param);
+    if (vr[c + 2]) acc.take(x.z, pos, a.param);
+    if (vr[c + 3]) acc.take(x.w, pos, a.param);
+  }
+  {
+    const int c = head + 4 * nvec + tid;
+    if (c < a.n_rn && vr[c]) acc.take(rn[c], pos, a.param);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const float x2 = __shfl_xor(acc.x, off, 64), y2 = __shfl_xor(acc.y, off, 64);
+    acc.merge(x2, y2);
+  }
+  if (lane == 0) {
+    s_x[w] = acc.x;
+    s_y[w] = acc.y;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    TaskAcc<KIND> t;
+    t.x = s_x[0];
+    t.y = s_y[0];
+    for (int k = 1; k < 4; ++k) t.merge(s_x[k], s_y[k]);
+    if (KIND == GIGL_LP_TASK_MARGIN) {
+      row_a[q] = t.x;
+      row_b[q] = t.y;
+    } else {  // lse as two words, m and log(sum exp(v - m)): their sum would round the small one away
+      row_a[q] = t.x;
+      row_b[q] = log1pf(t.y);
+    }
+  }
+}
+
+// {weighted loss, valid rows, normaliser} in a fixed order, fp64 and integers (one workgroup).  Margin: sum of the hinge sums /
+// N, N = the valid rows' negative counts (64-bit); Softmax: sum of the row losses / valid rows.  Training (eval_acc == NULL):
+// -> out3, a failed batch (either meta word) gives a NaN loss, *step (may be NULL) moves when it did not fail.  Evaluation: as
+// the plan's retrieval sum does it, acc[LOSS_SUM] += the fp32 loss word, acc[BATCHES] += 1, or *overflow_acc += 1.
+template <int KIND>
+__global__ __launch_bounds__(1024) void lp_task_sum_kernel(LpTaskHead a, const float* __restrict__ row_a,
+                                                           const float* __restrict__ row_b, float* __restrict__ out3,
+                                                           int32_t* __restrict__ step, const int32_t* __restrict__ meta_a,
+                                                           const int32_t* __restrict__ meta_b, double* __restrict__ eval_acc,
+                                                           int32_t* __restrict__ overflow_acc) {
+  __shared__ double s_w[16];
+  __shared__ long long s_p[16];
+  __shared__ int s_n[16];
+  __shared__ int s_rn;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int Q = a.b * a.P, R0 = Q + a.b * a.H;
+  int n_rn_valid = 0;
+  if (KIND == GIGL_LP_TASK_MARGIN) {  // the valid random negatives: every valid row has them all
+    int c = 0;
+    for (int r = tid; r < a.n_rn; r += 1024) c += a.valid[R0 + r] ? 1 : 0;
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    if (lane == 0) s_n[w] = c;
+    __syncthreads();
+    if (tid == 0) {
+      int t = 0;
+      for (int k = 0; k < 16; ++k) t += s_n[k];
+      s_rn = t;
+    }
+    __syncthreads();
+    n_rn_valid = s_rn;
+    __syncthreads();
+  }
+  double acc = 0.0;
+  long long pairs = 0;
+  int n = 0;
+  for (int q = tid; q < Q; q += 1024) {
+    const int i = q / a.P;
+    if (!task_row_valid(a, q, i)) continue;
+    ++n;
+    if (KIND == GIGL_LP_TASK_MARGIN) {
+      acc += (double)row_a[q];
+      int nh = 0;
+      for (int k = 0; k < a.H; ++k) nh += task_hard_valid(a, i, k) ? 1 : 0;
+      pairs += nh + n_rn_valid;
+    } else {  // lse - pos / T, the two large words subtracted first: exactly 0 for a row without negatives
+      const float vp = a.scores[(int64_t)q * a.ld + q] / a.param;
+      acc += (double)row_b[q] + ((double)row_a[q] - (double)vp);
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    acc += __shfl_xor(acc, off, 64);
+    pairs += __shfl_xor(pairs, off, 64);
+    n += __shfl_xor(n, off, 64);
+  }
+  if (lane == 0) {
+    s_w[w] = acc;
+    s_p[w] = pairs;
+    s_n[w] = n;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double t = 0.0;
+    long long pp = 0;
+    int nn = 0;
+    for (int k = 0; k < 16; ++k) {
+      t += s_w[k];
+      pp += s_p[k];
+      nn += s_n[k];
+    }
+    const double norm = KIND == GIGL_LP_TASK_MARGIN ? (double)pp : (double)nn;
+    const float loss = (float)((double)a.weight * t / (norm > 0.0 ? norm : 1.0));
+    const bool failed = meta_a && (meta_a[GIGL_META_OVERFLOW] != 0 || meta_b[GIGL_META_OVERFLOW] != 0);
+    if (eval_acc) {
+      if (failed) {
+        *overflow_acc += 1;
+      } else {
+        eval_acc[GIGL_LP_EVAL_LOSS_SUM] += (double)loss;
+        eval_acc[GIGL_LP_EVAL_BATCHES] += 1.0;
+      }
+      return;
+    }
+    out3[0] = failed ? __builtin_nanf("") : loss;
+    out3[1] = (float)nn;
+    out3[2] = (float)norm;
+    if (step && !failed) *step += 1;
+  }
+}
+
+// the whole dscores row (rows ldd floats apart) in one element-wise pass: the diagonal, the row's own hard negatives, the
+// random negatives; exactly 0 on every other column and on an invalid row.  The weight enters through one scale word, so a
+// weight halved halves every bit pattern exactly.
+template <int KIND>
+__global__ __launch_bounds__(256) void lp_task_backward_kernel(LpTaskHead a, const float* __restrict__ row_a,
+                                                               const float* __restrict__ row_b, const float* __restrict__ out3,
+                                                               float* __restrict__ dscores, int64_t ldd) {
+  const int q = blockIdx.x, i = q / a.P, Q = a.b * a.P, R0 = Q + a.b * a.H, Cn = R0 + a.n_rn;
+  float* out = dscores + (int64_t)q * ldd;
+  if (!task_row_valid(a, q, i)) {
+    for (int j = threadIdx.x; j < Cn; j += 256) out[j] = 0.f;
+    return;
+  }
+  const float* row = a.scores + (int64_t)q * a.ld;
+  const float pos = row[q];
+  const float norm = out3[2] > 0.f ? out3[2] : 1.f;
+  const float scale = KIND == GIGL_LP_TASK_MARGIN ? a.weight / norm : a.weight / (a.param * norm);
+  const float ra = row_a[q], rb = row_b[q];
+  const int h0 = Q + i * a.H;
+  for (int j = threadIdx.x; j < Cn; j += 256) {
+    float d = 0.f;
+    if (j == q) {
+      d = KIND == GIGL_LP_TASK_MARGIN ? 0.f - rb * scale : expm1f((pos / a.param - ra) - rb) * scale;
+    } else if (j >= R0 ? a.valid[j] != 0 : (j >= h0 && j < h0 + a.H && task_hard_valid(a, i, j - h0))) {
+      const float s = row[j];
+      if (KIND == GIGL_LP_TASK_MARGIN) d = (a.param - pos) + s >= 0.f ? scale : 0.f;
+      else d = expf((s / a.param - ra) - rb) * scale;
+    }
+    out[j] = d;
+  }
+}
+
+}  // namespace
+
+int32_t gigl_lp_task_check(gigl_ctx* ctx, int32_t kind, float param, float weight) {
+  GIGL_REQUIRE(ctx, kind == GIGL_LP_TASK_RETRIEVAL || kind == GIGL_LP_TASK_MARGIN || kind == GIGL_LP_TASK_SOFTMAX,
+               "task kind %d is none of GIGL_LP_TASK_RETRIEVAL / _MARGIN / _SOFTMAX", kind);
+  GIGL_REQUIRE(ctx, kind != GIGL_LP_TASK_SOFTMAX || (std::isfinite(param) && param > 0.f), "Softmax: the temperature must be finite and > 0");
+  GIGL_REQUIRE(ctx, kind != GIGL_LP_TASK_MARGIN || std::isfinite(param), "Margin: the margin must be finite");
+  GIGL_REQUIRE(ctx, std::isfinite(weight) && weight > 0.f, "the task's weight must be finite and > 0");
+  return GIGL_OK;
+}
+
+void gigl_lp_task_rows_enqueue(hipStream_t st, const LpTaskHead& h, float* row_a, float* row_b) {
+  const dim3 grid((unsigned)(h.b * h.P));
+  if (h.kind == GIGL_LP_TASK_MARGIN)
+    hipLaunchKernelGGL(lp_task_rows_kernel<GIGL_LP_TASK_MARGIN>, grid, dim3(256), 0, st, h, row_a, row_b);
+  else
+    hipLaunchKernelGGL(lp_task_rows_kernel<GIGL_LP_TASK_SOFTMAX>, grid, dim3(256), 0, st, h, row_a, row_b);
+}
+
+void gigl_lp_task_sum_enqueue(hipStream_t st, const LpTaskHead& h, const float* row_a, const float* row_b, float* out3,
+                              int32_t* step, const int32_t* meta_a, const int32_t* meta_b, double* eval_acc,
+                              int32_t* overflow_acc) {
+  if (h.kind == GIGL_LP_TASK_MARGIN)
+    hipLaunchKernelGGL(lp_task_sum_kernel<GIGL_LP_TASK_MARGIN>, dim3(1), dim3(1024), 0, st, h, row_a, row_b, out3, step, meta_a,
+                       meta_b, eval_acc, overflow_acc);
+  else
+    hipLaunchKernelGGL(lp_task_sum_kernel<GIGL_LP_TASK_SOFTMAX>, dim3(1), dim3(1024), 0, st, h, row_a, row_b, out3, step, meta_a,
+                       meta_b, eval_acc, overflow_acc);
+}
+
+void gigl_lp_task_backward_enqueue(hipStream_t st, const LpTaskHead& h, const float* row_a, const float* row_b,
+                                   const float* out3, float* dscores, int64_t ldd) {
+  const dim3 grid((unsigned)(h.b * h.P));
+  if (h.kind == GIGL_LP_TASK_MARGIN)
+    hipLaunchKernelGGL(lp_task_backward_kernel<GIGL_LP_TASK_MARGIN>, grid, dim3(256), 0, st, h, row_a, row_b, out3, dscores, ldd);
+  else
+    hipLaunchKernelGGL(lp_task_backward_kernel<GIGL_LP_TASK_SOFTMAX>, grid, dim3(256), 0, st, h, row_a, row_b, out3, dscores, ldd);
+}
+
+namespace {
+// the stand-alone entries' arguments -> h (Margin and Softmax: the retrieval loss needs the ids, see gigl_retrieval_loss)
+int32_t lp_task_head(gigl_ctx* ctx, LpTaskHead& h, int32_t kind, float param, float weight, const float* scores, int64_t ld,
+                     int32_t b, int32_t P, int32_t H, int32_t n_rn, const int32_t* pos_cnt, const int32_t* valid) {
+  const int32_t rc = gigl_lp_task_check(ctx, kind, param, weight);
+  if (rc != GIGL_OK) return rc;
+  GIGL_REQUIRE(ctx, kind != GIGL_LP_TASK_RETRIEVAL, "the retrieval loss masks by ids: gigl_retrieval_loss");
+  GIGL_REQUIRE(ctx, scores && valid && b >= 1 && P >= 1 && H >= 0 && n_rn >= 0, "bad arguments");
+  const int64_t Cn = (int64_t)b * (P + H) + n_rn;
+  GIGL_REQUIRE(ctx, Cn <= 0x7FFFFFFFll && ld >= Cn, "the score rows (ld=%lld) do not hold the %lld candidates' columns",
+               (long long)ld, (long long)Cn);
+  h = LpTaskHead{kind, param, weight, scores, ld, b, P, H, n_rn, pos_cnt, valid};
+  return GIGL_OK;
+}
 }  // namespace
 
 int32_t gigl_lp_rank_metrics_enqueue(gigl_ctx* ctx, hipStream_t st, const float* scores, int64_t ld, int32_t b, int32_t P,
@@ -367,6 +651,35 @@ int32_t gigl_retrieval_loss_backward(gigl_ctx* ctx, const float* scores, int64_t
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipLaunchKernelGGL(retrieval_backward_kernel, dim3((unsigned)q), dim3(256), 0, ctx->stream, a, row_lse, grad_loss,
                      dscores);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+int32_t gigl_lp_task_loss(gigl_ctx* ctx, int32_t kind, float param, float weight, const float* scores, int64_t ld, int32_t b,
+                          int32_t P, int32_t H, int32_t n_rn, const int32_t* pos_cnt, const int32_t* valid, float* row_a,
+                          float* row_b, float* out3) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  LpTaskHead h{};
+  const int32_t rc = lp_task_head(ctx, h, kind, param, weight, scores, ld, b, P, H, n_rn, pos_cnt, valid);
+  if (rc != GIGL_OK) return rc;
+  GIGL_REQUIRE(ctx, row_a && row_b && out3, "null output");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  gigl_lp_task_rows_enqueue(ctx->stream, h, row_a, row_b);
+  gigl_lp_task_sum_enqueue(ctx->stream, h, row_a, row_b, out3, nullptr, nullptr, nullptr, nullptr, nullptr);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+int32_t gigl_lp_task_loss_backward(gigl_ctx* ctx, int32_t kind, float param, float weight, const float* scores, int64_t ld,
+                                   int32_t b, int32_t P, int32_t H, int32_t n_rn, const int32_t* pos_cnt, const int32_t* valid,
+                                   const float* row_a, const float* row_b, const float* out3, float* dscores) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  LpTaskHead h{};
+  const int32_t rc = lp_task_head(ctx, h, kind, param, weight, scores, ld, b, P, H, n_rn, pos_cnt, valid);
+  if (rc != GIGL_OK) return rc;
+  GIGL_REQUIRE(ctx, row_a && row_b && out3 && dscores, "null argument");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  gigl_lp_task_backward_enqueue(ctx->stream, h, row_a, row_b, out3, dscores, (int64_t)b * (P + H) + n_rn);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }

@@ -2264,6 +2264,9 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
   SageTrainEnc enc[2];       // 0: main batch, 1: random negatives
   int32_t b = 0, P = 0, H = 0, n_rn = 0, normalize = 0, remove_hits = 1;  // H: ctx->lp_hard_negatives at creation
   float temperature = 0.07f;
+  // the job's one task (gigl_nablp_train_plan_set_task): GIGL_LP_TASK_*, Margin's margin | Softmax's temperature, its weight
+  int32_t task_kind = GIGL_LP_TASK_RETRIEVAL;
+  float task_param = 0.f, task_weight = 1.f;
   float* da = nullptr;        // gradient of a layer's operand (SAGE)
   void* zero_base = nullptr;  // both encodes' gw | gb | dh: cleared at the start of every step
   size_t zero_bytes = 0;
@@ -2275,7 +2278,9 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
   size_t cnt_words() const { return (size_t)b * (H > 0 ? 2 : 1); }   // of pos_cnt
   int32_t* pos_cnt = nullptr;  // [b] (H > 0: [2 b], the hard negatives' counts behind the positives') static copy of the step's input
   int32_t* consts = nullptr;   // device {Q, C, Adam step, ...}
-  float *row_lse = nullptr, *row_loss = nullptr, *loss = nullptr;  // loss[0] = the step's loss, loss[1] = valid query rows
+  // loss[0] = the step's loss, loss[1] = valid query rows, loss[2] = a Margin / Softmax task's normaliser; row_lse / row_loss
+  // hold that task's two row partials (gigl_lp_task_loss's row_a / row_b)
+  float *row_lse = nullptr, *row_loss = nullptr, *loss = nullptr;
   // ---- GAT encoder (kind == 1, gigl_gat_nablp_train_plan_create): two layers, the first from the INPUT side
   int kind = 0;
   struct Gat {
@@ -2484,10 +2489,10 @@ __global__ __launch_bounds__(256) void lp_loss_rows_kernel(const float* __restri
   }
 }
 
-// loss[0] = sum of the valid rows' losses / their number (fixed order, in double), loss[1] = that number; Adam's step
+// loss[0] = the task's weight x sum of the valid rows' losses / their number (fixed order, in double), loss[1] = that number; Adam's step
 // counter moves when the step will be applied
 __global__ __launch_bounds__(1024) void lp_loss_sum_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ valid,
-                                                           int Q, float* __restrict__ loss, int32_t* __restrict__ step,
+                                                           int Q, float weight, float* __restrict__ loss, int32_t* __restrict__ step,
                                                            const int32_t* __restrict__ meta_a, const int32_t* __restrict__ meta_b) {
   __shared__ double s_w[16];
   __shared__ int s_n[16];
@@ -2515,7 +2520,7 @@ __global__ __launch_bounds__(1024) void lp_loss_sum_kernel(const float* __restri
       nn += s_n[k];
     }
     const bool failed = meta_a[GIGL_META_OVERFLOW] != 0 || meta_b[GIGL_META_OVERFLOW] != 0;
-    loss[0] = failed ? __builtin_nanf("") : (float)(t / (double)(nn > 0 ? nn : 1));
+    loss[0] = failed ? __builtin_nanf("") : (float)(t / (double)(nn > 0 ? nn : 1)) * weight;  // (x 1.0f: the same bits)
     loss[1] = (float)nn;
     if (!failed) *step += 1;
   }
@@ -2524,7 +2529,7 @@ __global__ __launch_bounds__(1024) void lp_loss_sum_kernel(const float* __restri
 // the evaluation's loss sum: acc[LOSS_SUM] += the valid rows' mean loss (as lp_loss_sum_kernel adds it up), acc[BATCHES] += 1;
 // a batch beyond the workspace adds 1 to *overflow_acc instead.  Adam's step counter is not touched.
 __global__ __launch_bounds__(1024) void lp_eval_loss_sum_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ valid,
-                                                                int Q, const int32_t* __restrict__ meta_a,
+                                                                int Q, float weight, const int32_t* __restrict__ meta_a,
                                                                 const int32_t* __restrict__ meta_b, double* __restrict__ acc,
                                                                 int32_t* __restrict__ overflow_acc) {
   __shared__ double s_w[16];
@@ -2555,18 +2560,18 @@ __global__ __launch_bounds__(1024) void lp_eval_loss_sum_kernel(const float* __r
     if (meta_a[GIGL_META_OVERFLOW] != 0 || meta_b[GIGL_META_OVERFLOW] != 0) {
       *overflow_acc += 1;
     } else {
-      acc[GIGL_LP_EVAL_LOSS_SUM] += (double)(float)(t / (double)(nn > 0 ? nn : 1));  // (the fp32 word a step reports)
+      acc[GIGL_LP_EVAL_LOSS_SUM] += (double)((float)(t / (double)(nn > 0 ? nn : 1)) * weight);  // (the fp32 word a step reports)
       acc[GIGL_LP_EVAL_BATCHES] += 1.0;
     }
   }
 }
 
-// dscores = d loss / d scores: (softmax - onehot) / temperature / rows for the columns that take part, 0 elsewhere
+// dscores = d loss / d scores: weight x (softmax - onehot) / temperature / rows for the columns that take part, 0 elsewhere
 __global__ __launch_bounds__(256) void lp_loss_backward_kernel(const float* __restrict__ scores, int Q, int Cn, float temperature,
                                                                const int64_t* __restrict__ qid, const int64_t* __restrict__ cid,
                                                                const int32_t* __restrict__ valid, int remove_hits,
                                                                const float* __restrict__ row_lse, const float* __restrict__ loss,
-                                                               float* __restrict__ dscores) {
+                                                               float weight, float* __restrict__ dscores) {
   const int i = blockIdx.x;
   float* out = dscores + (int64_t)i * Cn;
   if (!valid[i]) {
@@ -2577,7 +2582,7 @@ __global__ __launch_bounds__(256) void lp_loss_backward_kernel(const float* __re
   const int64_t qid_i = qid[i], cid_i = cid[i];
   const float lse = row_lse[i];
   const float nrows = loss[1] > 0.f ? loss[1] : 1.f;
-  const float scale = (temperature > 0.f ? 1.f / temperature : 1.f) / nrows;
+  const float scale = (temperature > 0.f ? 1.f / temperature : 1.f) / nrows * weight;  // (x 1.0f: the same bits)
   for (int j = threadIdx.x; j < Cn; j += 256) {
     float d = 0.f;
     if (!lp_excluded(qid, cid, valid, remove_hits, Q, i, j, qid_i, cid_i)) {
@@ -2679,6 +2684,12 @@ int32_t lp_enqueue_graph(gigl_nablp_train_plan* t, int w, int32_t sampling_seed,
   return GIGL_OK;
 }
 
+// a Margin / Softmax task over the plan's scores and validity words (loss.hip)
+LpTaskHead lp_task_head(const gigl_nablp_train_plan* t) {
+  return LpTaskHead{t->task_kind, t->task_param, t->task_weight, t->scores, (int64_t)t->cand_cols(), t->b, t->P, t->H, t->n_rn,
+                    t->pos_cnt, t->valid};
+}
+
 // the forward half of the layers part over workspace w: both encodes, the head's operands, the scores, the loss rows
 // (shared by the training step — train: with the plan's dropout — and gigl_nablp_train_plan_eval, which runs without)
 int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w, bool train) {
@@ -2717,9 +2728,12 @@ int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w, bool train) {
   // scores[q][c] = <rq[q], cand[c]>  (decoder.py:64-70: torch.mm(q, c.T))
   rc = gigl_linear(ctx, t->rq, t->cand, nullptr, t->consts + 0, Q, d, Cn, 0, t->scores);
   if (rc != GIGL_OK) return rc;
-  hipLaunchKernelGGL(lp_loss_rows_kernel, dim3((unsigned)Q), dim3(256), 0, st, (const float*)t->scores, Q, Cn, t->temperature,
-                     (const int64_t*)t->qid, (const int64_t*)t->cid, (const int32_t*)t->valid, t->remove_hits, t->row_lse,
-                     t->row_loss);
+  if (t->task_kind != GIGL_LP_TASK_RETRIEVAL)
+    gigl_lp_task_rows_enqueue(st, lp_task_head(t), t->row_lse, t->row_loss);
+  else
+    hipLaunchKernelGGL(lp_loss_rows_kernel, dim3((unsigned)Q), dim3(256), 0, st, (const float*)t->scores, Q, Cn, t->temperature,
+                       (const int64_t*)t->qid, (const int64_t*)t->cid, (const int32_t*)t->valid, t->remove_hits, t->row_lse,
+                       t->row_loss);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -2732,11 +2746,18 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
   int32_t rc = lp_enqueue_forward(t, w, true);
   if (rc != GIGL_OK) return rc;
   const gigl_sage_plan *pm = t->enc[0].base, *pr = t->enc[1].base;
-  hipLaunchKernelGGL(lp_loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->row_loss, (const int32_t*)t->valid, Q,
-                     t->loss, t->consts + 2, (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta);
-  hipLaunchKernelGGL(lp_loss_backward_kernel, dim3((unsigned)Q), dim3(256), 0, st, (const float*)t->scores, Q, Cn,
-                     t->temperature, (const int64_t*)t->qid, (const int64_t*)t->cid, (const int32_t*)t->valid, t->remove_hits,
-                     (const float*)t->row_lse, (const float*)t->loss, t->dscores);
+  if (t->task_kind != GIGL_LP_TASK_RETRIEVAL) {
+    const LpTaskHead h = lp_task_head(t);
+    gigl_lp_task_sum_enqueue(st, h, t->row_lse, t->row_loss, t->loss, t->consts + 2, (const int32_t*)pm->un.meta,
+                             (const int32_t*)pr->un.meta, nullptr, nullptr);
+    gigl_lp_task_backward_enqueue(st, h, t->row_lse, t->row_loss, t->loss, t->dscores, (int64_t)Cn);
+  } else {
+    hipLaunchKernelGGL(lp_loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->row_loss, (const int32_t*)t->valid, Q,
+                       t->task_weight, t->loss, t->consts + 2, (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta);
+    hipLaunchKernelGGL(lp_loss_backward_kernel, dim3((unsigned)Q), dim3(256), 0, st, (const float*)t->scores, Q, Cn,
+                       t->temperature, (const int64_t*)t->qid, (const int64_t*)t->cid, (const int32_t*)t->valid, t->remove_hits,
+                       (const float*)t->row_lse, (const float*)t->loss, t->task_weight, t->dscores);
+  }
   // d rq = dscores . cand ;  d cand = dscores^T . rq
   {
     int64_t blocks = ((int64_t)Cn * d + 255) / 256;
@@ -3044,8 +3065,12 @@ int32_t gigl_nablp_train_plan_eval(gigl_nablp_train_plan* t, const uint32_t* mai
   for (int k = 0; k < 2; ++k) t->enc[k].base = held[k];
   if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
   const int Q = t->b * t->P;
-  hipLaunchKernelGGL(lp_eval_loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->row_loss, (const int32_t*)t->valid, Q,
-                     (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta, acc, overflow_acc);
+  if (t->task_kind != GIGL_LP_TASK_RETRIEVAL)
+    gigl_lp_task_sum_enqueue(st, lp_task_head(t), t->row_lse, t->row_loss, nullptr, nullptr, (const int32_t*)pm->un.meta,
+                             (const int32_t*)pr->un.meta, acc, overflow_acc);
+  else
+    hipLaunchKernelGGL(lp_eval_loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->row_loss, (const int32_t*)t->valid, Q,
+                       t->task_weight, (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta, acc, overflow_acc);
   const int R0 = Q + t->b * t->H;  // (ranked against the random negatives only, as the reference's validate does)
   rc = gigl_lp_rank_metrics_enqueue(t->lctx, st, t->scores, (int64_t)t->cand_cols(), t->b, t->P, t->pos_cnt, t->n_rn, R0,
                                     t->valid + R0, ks, n_ks, pm->un.meta, pr->un.meta, t->rank_part, acc);
@@ -3081,6 +3106,18 @@ int32_t gigl_nablp_train_plan_set_clip_grad_norm(gigl_nablp_train_plan* t, float
     GIGL_HIP_CHECK(ctx, hipMemset(t->clip.out2, 0, 16));
   }
   t->clip.max_norm = max_norm;
+  return GIGL_OK;
+}
+
+int32_t gigl_nablp_train_plan_set_task(gigl_nablp_train_plan* t, int32_t kind, float param, float weight) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  gigl_ctx* ctx = t->ctx;
+  GIGL_REQUIRE(ctx, !t->stepped, "the task is set after create and before the first step (the step is captured)");
+  const int32_t rc = gigl_lp_task_check(ctx, kind, param, weight);
+  if (rc != GIGL_OK) return rc;
+  t->task_kind = kind;
+  t->task_param = kind == GIGL_LP_TASK_RETRIEVAL ? 0.f : param;
+  t->task_weight = weight;
   return GIGL_OK;
 }
 
@@ -3213,6 +3250,14 @@ int32_t gigl_nablp_train_plan_adopt(gigl_nablp_train_plan* dst, gigl_nablp_train
   } else {
     const int32_t rc = sage_moments_adopt(ctx, *dst, *src);
     if (rc != GIGL_OK) return rc;
+  }
+  if (!dst->stepped) {  // (the job's task: a plan that has stepped keeps its own, its step is captured)
+    dst->task_kind = src->task_kind;
+    dst->task_param = src->task_param;
+    dst->task_weight = src->task_weight;
+  } else {
+    GIGL_REQUIRE(ctx, dst->task_kind == src->task_kind && dst->task_param == src->task_param && dst->task_weight == src->task_weight,
+                 "plans of different tasks");
   }
   // (Adam's step counter: the bias correction and the ConstantLR schedule go on where src stood)
   GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->consts + 2, src->consts + 2, 4, hipMemcpyDeviceToDevice, ctx->stream));

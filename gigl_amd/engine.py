@@ -1189,6 +1189,31 @@ class HipEngine:
                                                      p(d)), self._ctx)
         return d
 
+    def lp_task_loss(self, task: str, param: float, weight: float, scores: torch.Tensor, b: int, P: int, H: int, n_rn: int,
+                     pos_cnt: Optional[torch.Tensor], valid: torch.Tensor, backward: bool = True):
+        """the Margin / Softmax task over a score matrix in the training plan's layout (gigl_lp_task_loss and
+        gigl_lp_task_loss_backward; include/gigl_hip.h has the layout and the formulas): scores float32 device [b P, >= C]
+        with unit column stride, C = b (P + H) + n_rn, valid int32 [C], pos_cnt int32 [b] ([2 b] with H > 0) or None ->
+        (out3 = {weighted loss, valid rows, normaliser}, row_a, row_b, dscores [b P, C] | None)"""
+        Q, Cn = int(b) * int(P), int(b) * (int(P) + int(H)) + int(n_rn)
+        assert scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1
+        assert scores.shape[0] == Q and scores.shape[1] >= Cn
+        assert valid.is_cuda and valid.dtype == torch.int32 and valid.is_contiguous() and valid.numel() == Cn
+        assert pos_cnt is None or (pos_cnt.is_cuda and pos_cnt.dtype == torch.int32 and pos_cnt.is_contiguous()
+                                   and pos_cnt.numel() == int(b) * (2 if H > 0 else 1))
+        row_a = torch.empty(Q, dtype=torch.float32, device=self.device)
+        row_b = torch.empty(Q, dtype=torch.float32, device=self.device)
+        out3 = torch.empty(3, dtype=torch.float32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        head = (self._ctx, int(_lib.LP_TASKS[task]), float(param), float(weight), p(scores), int(scores.stride(0)), int(b), int(P),
+                int(H), int(n_rn), p(pos_cnt), p(valid))
+        check(self._lib.gigl_lp_task_loss(*head, p(row_a), p(row_b), p(out3)), self._ctx)
+        d = None
+        if backward:
+            d = torch.empty((Q, Cn), dtype=torch.float32, device=self.device)
+            check(self._lib.gigl_lp_task_loss_backward(*head, p(row_a), p(row_b), p(out3), p(d)), self._ctx)
+        return out3, row_a, row_b, d
+
     def project_features(self, w_fused: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """[X W_l^T | X W_r^T] over the whole resident feature table for a first-layer fused weight [out, 2*in]
         (gigl_sage_project_features): one fp32 table [n_rows, 2*out] on the device — the input of
@@ -1607,8 +1632,11 @@ class NablpTrainPlan:
                  temperature: float = 0.07, remove_accidental_hits: bool = True, lr: float = 5e-3,
                  weight_decay: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8, clip_grad_norm: float = 0.0,
                  lr_factor: float = 1.0, lr_total_iters: int = 0, num_hard_negatives: int = 0,
-                 dropout: Optional[float] = None, dropout_seed: int = 0):
-        """dropout, dropout_seed: as SageTrainPlan's (both encodes; evaluate() / eval_batch() run without dropout)"""
+                 dropout: Optional[float] = None, dropout_seed: int = 0, task: str = "Retrieval", margin: float = 0.5,
+                 softmax_temperature: float = 0.07, task_weight: float = 1.0):
+        """dropout, dropout_seed: as SageTrainPlan's (both encodes; evaluate() / eval_batch() run without dropout)
+        task: the job's one task, "Retrieval" (temperature, remove_accidental_hits), "Margin" (margin) or "Softmax"
+        (softmax_temperature), at weight task_weight (gigl_nablp_train_plan_set_task); evaluate()'s loss is that task's"""
         assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
         L = len(fanouts)
         assert model.num_layers == L, "one hop per layer"
@@ -1621,6 +1649,7 @@ class NablpTrainPlan:
         self.fanouts = [int(f) for f in fanouts]
         self._lib = eng._lib
         self._optim_knobs = (float(clip_grad_norm), float(lr_factor), int(lr_total_iters))
+        self._task = self._task_knobs(task, margin, softmax_temperature, task_weight)
         self.w, self.bias = [], []
         SageTrainPlan.load(self, model)
         self.dims = [int(self.w[0].shape[1]) // 2] + [int(w.shape[0]) for w in self.w]
@@ -1639,6 +1668,7 @@ class NablpTrainPlan:
                     float(eps), float(weight_decay), C.byref(h)), eng._ctx)
             try:
                 self._apply_optim_knobs(h)
+                self._apply_task(h)
                 self._apply_dropout(h, self._lib.gigl_nablp_train_plan_set_dropout)
             except Exception:
                 self._lib.gigl_nablp_train_plan_destroy(h)
@@ -1675,6 +1705,28 @@ class NablpTrainPlan:
             check(self._lib.gigl_nablp_train_plan_set_clip_grad_norm(handle, clip), self.eng._ctx)
         if factor != 1.0 or total_iters < 0:
             check(self._lib.gigl_nablp_train_plan_set_constant_lr(handle, factor, total_iters), self.eng._ctx)
+
+    _task = (0, 0.0, 1.0)  # (kind, param, weight): Retrieval at weight 1, the plan as it is created
+
+    @staticmethod
+    def _task_knobs(task: str, margin: float, softmax_temperature: float, task_weight: float):
+        """(GIGL_LP_TASK_* kind, its parameter, weight) of the constructor's task arguments"""
+        if task not in _lib.LP_TASKS:
+            raise ValueError(f"task must be one of {sorted(_lib.LP_TASKS)} (got {task!r})")
+        param = {"Retrieval": 0.0, "Margin": float(margin), "Softmax": float(softmax_temperature)}[task]
+        return _lib.LP_TASKS[task], param, float(task_weight)
+
+    def _apply_task(self, handle) -> None:
+        """the job's task of a (re)created plan handle, before its first step (called inside create(), so that grow()'s wide
+        plan trains the same loss).  Retrieval at weight 1 is the plan as created: no call, the launches it always issued."""
+        if self._task != (0, 0.0, 1.0):
+            check(self._lib.gigl_nablp_train_plan_set_task(handle, *self._task), self.eng._ctx)
+
+    def set_task(self, task: str, margin: float = 0.5, softmax_temperature: float = 0.07, task_weight: float = 1.0) -> None:
+        """gigl_nablp_train_plan_set_task on the live plan: before the first step only (the library refuses it afterwards)"""
+        knobs = self._task_knobs(task, margin, softmax_temperature, task_weight)
+        check(self._lib.gigl_nablp_train_plan_set_task(self._plan, *knobs), self.eng._ctx)
+        self._task = knobs
 
     def grad_norm(self):
         """(total_norm, coef) of the LAST trained step of a clipping plan (gigl_nablp_train_plan_grad_norm): the 2-norm over
@@ -1813,7 +1865,8 @@ class GatNablpTrainPlan(NablpTrainPlan):
                  temperature: float = 0.07, remove_accidental_hits: bool = True, lr: float = 5e-3,
                  weight_decay: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8, clip_grad_norm: float = 0.0,
                  lr_factor: float = 1.0, lr_total_iters: int = 0, num_hard_negatives: int = 0,
-                 dropout: Optional[float] = None, dropout_seed: int = 0):
+                 dropout: Optional[float] = None, dropout_seed: int = 0, task: str = "Retrieval", margin: float = 0.5,
+                 softmax_temperature: float = 0.07, task_weight: float = 1.0):
         assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
         if not self._applies_to(eng, model) or len(fanouts) != 2:
             raise NotImplementedError(self._COVERS)
@@ -1828,6 +1881,7 @@ class GatNablpTrainPlan(NablpTrainPlan):
         self.fanouts = [int(f) for f in fanouts]
         self._lib = eng._lib
         self._optim_knobs = (float(clip_grad_norm), float(lr_factor), int(lr_total_iters))
+        self._task = self._task_knobs(task, margin, softmax_temperature, task_weight)
         self.load(model)
         c0, c1 = model.conv_layers
         self.heads, self.channels = [int(c0.heads), 1], [int(c0.out_channels), int(c1.out_channels)]
@@ -1845,6 +1899,7 @@ class GatNablpTrainPlan(NablpTrainPlan):
             try:
                 self._after_create(h)
                 self._apply_optim_knobs(h)
+                self._apply_task(h)
             except Exception:
                 self._lib.gigl_nablp_train_plan_destroy(h)
                 raise

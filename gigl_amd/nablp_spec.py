@@ -28,6 +28,7 @@ from __future__ import annotations
 from copy import deepcopy
 from dataclasses import dataclass, field
 from itertools import cycle
+import math
 from typing import Any, Dict, List, Optional
 
 import numpy as np
@@ -862,14 +863,41 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
                     clip_grad_norm=max(float(self.clip_grad_norm), 0.0),  # (the trainer clips only when it is > 0)
                     lr_factor=factor, lr_total_iters=total_iters if factor != 1.0 else 0)
 
+    def _train_plan_task_kwargs(self) -> Optional[Dict[str, Any]]:
+        """-> the task's keyword arguments of the library's training plan (engine.NablpTrainPlan and its GAT kinds) when the
+        plan's head computes this job's loss, else None: ONE task — Retrieval with its own cross-entropy and no
+        candidate-sampling correction, Margin or Softmax (exactly these classes) — at a finite weight > 0.  A job with
+        several tasks keeps the autograd loop."""
+        tasks = list(self.tasks._task_to_fn_map.values())
+        if len(tasks) != 1:
+            return None
+        task = tasks[0]
+        try:
+            weight = float(self.tasks._task_to_weights_map.get(task.task_name))
+        except (TypeError, ValueError):
+            return None
+        if not (math.isfinite(weight) and weight > 0.0):
+            return None
+        if type(task) is Retrieval:
+            if task.should_enable_candidate_sampling_correction or task.loss._loss is not None:
+                return None
+            return dict(task="Retrieval", task_weight=weight, temperature=float(task.loss._temperature or 0.0),
+                        remove_accidental_hits=bool(task.loss._remove_accidental_hits))
+        if type(task) is Margin:
+            return dict(task="Margin", task_weight=weight, margin=float(task.margin)) if math.isfinite(task.margin) else None
+        if type(task) is Softmax:
+            t = float(task.softmax_temperature)
+            return dict(task="Softmax", task_weight=weight, softmax_temperature=t) if math.isfinite(t) and t > 0.0 else None
+        return None
+
     def _library_train_plan(self, cfg: GbmlConfigPbWrapper):
         """-> engine.NablpTrainPlan when this job's training step can run as ONE library call per batch
         (gigl_nablp_train_plan_*: both encodes, the head, the backward and Adam inside the library, a hipGraph per step),
         else None (the autograd loop below).  That is: the in-HBM route with a whole replica in one process, the plain
         mean-GraphSAGE encoder — or configs[4]'s two-layer GAT (engine.GatNablpTrainPlan.applies), or that encoder with
         edge_dim over the engine's resident edge table (engine.GatEdgeNablpTrainPlan: no table raises) —, the inner-product
-        decoder, the Retrieval task alone with its own cross-entropy and no
-        candidate-sampling correction, and an optimiser the plan runs (_train_plan_optim_kwargs: torch.optim.Adam with its
+        decoder, ONE task (_train_plan_task_kwargs: Retrieval with its own cross-entropy and no candidate-sampling
+        correction, Margin or Softmax, at any finite positive weight), and an optimiser the plan runs (_train_plan_optim_kwargs: torch.optim.Adam with its
         default betas / eps — with or without gradient-norm clipping (clip_grad_norm) and the ConstantLR warm-up (factor,
         total_iters), both applied inside the plan's Adam launch sequence —; any other scheduler class keeps the autograd
         loop); trainerArgs train_plan = "off" keeps the autograd loop.  The plan's random-negative capacity is the larger of
@@ -887,7 +915,6 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         res = self._resident
         inner = self.model.module if hasattr(self.model, "module") else self.model
         enc, dec = inner.encoder, inner.decoder
-        tasks = list(self.tasks._task_to_fn_map.values())
         from ._lib import MODE_SPARK_HASH
         from .engine import GatEdgeNablpTrainPlan, GatNablpTrainPlan
         sage = type(enc).__module__ == "gigl_amd.models" and type(enc).__name__ == "GraphSAGE" and not res.train_as_graph_data
@@ -896,9 +923,6 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         gat_edge = (not gat and getattr(enc, "edge_dim", None) is not None and len(res.fanouts) == 2 and
                     GatEdgeNablpTrainPlan.applies(enc, res.feat_dim, res.engine.edge_feat_dim or int(enc.edge_dim)))
         if _rank_world()[1] > 1 or res.sharded or res.mode != MODE_SPARK_HASH or not (sage or gat or gat_edge) or \
-                len(tasks) != 1 or type(tasks[0]) is not Retrieval or \
-                tasks[0].should_enable_candidate_sampling_correction or tasks[0].loss._loss is not None or \
-                self.tasks._task_to_weights_map.get(tasks[0].task_name) != 1.0 or \
                 str(getattr(dec, "decoder_type", "inner_product")).split(".")[-1] != "inner_product" or \
                 int(enc.conv_layers[-1].out_channels) > 512:
             return None
@@ -906,6 +930,10 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         # asks: any other optimiser or scheduler setting keeps the autograd loop
         optim = self._train_plan_optim_kwargs()
         if optim is None:
+            return None
+        # ... and its head computes the job's one task (Retrieval, Margin or Softmax at any finite positive weight)
+        task = self._train_plan_task_kwargs()
+        if task is None:
             return None
         # ... and it trains exactly the tensors its load / store move: the conv layers' weights (+ biases / attention vectors).
         # A model with any other trainable parameter (a decoder MLP, a final linear, batch norm, embeddings) would have it
@@ -922,10 +950,9 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         try:
             return (NablpTrainPlan if sage else GatEdgeNablpTrainPlan if gat_edge else GatNablpTrainPlan)(
                 res.engine, enc, self.main_sample_batch_size, P,
-                n_rn, res.fanouts, temperature=float(tasks[0].loss._temperature or 0.0),
-                remove_accidental_hits=bool(tasks[0].loss._remove_accidental_hits), num_hard_negatives=H,
+                n_rn, res.fanouts, num_hard_negatives=H,
                 # (None: the encoder's own p; a GAT kind with p > 0 raises NotImplementedError: the autograd loop below)
-                dropout=self.dropout, dropout_seed=self.dropout_seed, **optim)
+                dropout=self.dropout, dropout_seed=self.dropout_seed, **optim, **task)
         except (NotImplementedError, GiglError):
             return None
 

@@ -1104,6 +1104,49 @@ int32_t gigl_lp_rank_metrics(gigl_ctx* ctx, const float* scores, int64_t ld, int
                              int32_t n_neg, int32_t neg_col0, const int32_t* neg_valid /* may be NULL */,
                              const int32_t* ks /* HOST */, int32_t n_ks, double* acc /* DEVICE [GIGL_LP_EVAL_LEN], += */);
 
+/* ---- the Margin and Softmax link-prediction tasks over a score matrix in the training plan's layout.  Replaces
+ *      Margin.forward / Softmax.forward (python/gigl/src/common/models/layers/task.py:62-105) with MarginLoss / SoftmaxLoss
+ *      (loss.py:21-174) and their autograd backward: three launches (rows, sum, backward), no padded per-anchor matrices.
+ * LAYOUT (the plan's own): b anchors, P positive slots, H hard-negative slots, n_rn random negatives; Q = b P, R0 = Q + b H,
+ *   C = R0 + n_rn.  scores: DEVICE fp32, Q rows `ld` >= C floats apart.  Row AND column q = i P + j is anchor i's positive j,
+ *   columns Q + i H + k anchor i's hard negatives, columns R0 + r the random negatives.  valid: DEVICE int32 [C] as the plan's
+ *   head writes it (row q takes part when valid[q] != 0, a negative's column c when valid[c] != 0).  pos_cnt: NULL, or DEVICE
+ *   int32 [b] (H == 0) / [2 b] (positives per anchor, then hard negatives per anchor) — then row q additionally needs
+ *   j < pos_cnt[i] and hard negative k of anchor i needs k < pos_cnt[b + i], which a `valid` written by the plan implies.
+ * NEGATIVES of a valid row q of anchor i, pos = s[q][q]: Neg(q) = the valid columns among Q + i H .. Q + i H + H - 1 (its OWN
+ *   anchor's hard negatives only) and the valid columns >= R0.  No same-query and no accidental-hit mask (the reference
+ *   applies none for these tasks).  Other anchors' hard negatives and the positives' block off the diagonal take no part:
+ *   their dscores are exactly 0, as is every entry of an invalid row.
+ * GIGL_LP_TASK_MARGIN, param = margin m (finite), weight w:
+ *   L = w * sum_q sum_{n in Neg(q)} max(0, m - pos + s[q][n]) / max(N, 1), N = sum_q |Neg(q)| counted in 64-bit integers.
+ *   A pair is ACTIVE when m - pos + s >= 0 — torch's margin_ranking_loss differentiates through clamp_min, whose gradient at
+ *   an exact zero is 1.  d s[q][n] = w * active / max(N, 1), d s[q][q] = -w * (#active of the row) / max(N, 1).
+ *   row_a = the row's hinge sum, row_b = its active count; out3 = {L, valid rows, N}.
+ * GIGL_LP_TASK_SOFTMAX, param = temperature T > 0:
+ *   lse_q = log(exp(pos / T) + sum_n exp(s[q][n] / T)), taken online (running maximum), L = w * sum_q (lse_q - pos / T) /
+ *   max(R, 1), R = the valid rows.  d s[q][n] = w * exp(s / T - lse_q) / (T max(R, 1)), d s[q][q] = w * (exp(pos / T - lse_q)
+ *   - 1) / (T max(R, 1)).  A row without negatives has loss exactly 0 and gradient exactly 0.
+ *   row_a = the row's largest logit m, row_b = log(sum exp(logit - m)) through log1p: lse_q = row_a + row_b, kept as two words
+ *   because a dominant positive leaves row_b (and the row's loss) near 1e-7, which the sum would round away; the sum kernel
+ *   forms the row's loss row_b + (row_a - pos / T) in fp64.  out3 = {L, valid rows, R}.
+ * GIGL_LP_TASK_RETRIEVAL names the plan's retrieval loss in gigl_nablp_train_plan_set_task; these two entries return
+ *   GIGL_E_INVALID_ARG for it (it masks by ids: gigl_retrieval_loss).  Also GIGL_E_INVALID_ARG: T <= 0, a non-finite margin,
+ *   a weight that is not finite and > 0.
+ * The sums over rows are fp64 in a fixed order, without atomics: two runs give the same bits.  The weight enters every
+ *   result through one multiplication, so halving it halves loss and gradient bit for bit.  Each valid row reads its 1 + H +
+ *   n_rn relevant entries (Q (1 + H + n_rn) floats forward against the retrieval loss' Q C).  row_a, row_b: DEVICE fp32 [Q];
+ *   out3: DEVICE fp32 [3]; dscores: DEVICE fp32 [Q][C], every entry written.  Enqueued on the ctx stream, no synchronisation. */
+#define GIGL_LP_TASK_RETRIEVAL 0
+#define GIGL_LP_TASK_MARGIN 1
+#define GIGL_LP_TASK_SOFTMAX 2
+int32_t gigl_lp_task_loss(gigl_ctx* ctx, int32_t kind, float param, float weight, const float* scores, int64_t ld, int32_t b,
+                          int32_t P, int32_t H, int32_t n_rn, const int32_t* pos_cnt /* may be NULL */, const int32_t* valid,
+                          float* row_a, float* row_b, float* out3);
+int32_t gigl_lp_task_loss_backward(gigl_ctx* ctx, int32_t kind, float param, float weight, const float* scores, int64_t ld,
+                                   int32_t b, int32_t P, int32_t H, int32_t n_rn, const int32_t* pos_cnt /* may be NULL */,
+                                   const int32_t* valid, const float* row_a, const float* row_b, const float* out3,
+                                   float* dscores);
+
 /* ---- one-call batch pipeline: sample -> union -> GraphSAGE forward -> one output row per root.
  *      Replaces `infer_batch` of the reference's task specs for a RootedNodeNeighborhood batch
  *      (python/gigl/src/common/modeling_task_specs/node_anchor_based_link_prediction_modeling_task_spec.py:626-655,
@@ -1413,6 +1456,18 @@ const float* gigl_nablp_train_plan_loss(gigl_nablp_train_plan* plan);
 int32_t gigl_nablp_train_plan_set_clip_grad_norm(gigl_nablp_train_plan* plan, float max_norm);
 int32_t gigl_nablp_train_plan_set_constant_lr(gigl_nablp_train_plan* plan, float factor, int32_t total_iters);
 int32_t gigl_nablp_train_plan_grad_norm(gigl_nablp_train_plan* plan, float* out2);
+/* The job's ONE task (the trainer spec's task_path: Retrieval, Margin or Softmax; task.py:62-214), for every kind of
+ * link-prediction plan — they share the head.  kind: GIGL_LP_TASK_*; param: Margin's margin, Softmax's temperature, ignored
+ * for Retrieval (whose temperature and accidental-hit removal are _create's arguments); weight: the task's weight, finite and
+ * > 0 (GIGL_E_INVALID_ARG otherwise, as for a temperature <= 0 or a non-finite margin).  Called after create and before the
+ * first step (GIGL_E_INVALID_ARG afterwards: the step is captured); gigl_nablp_train_plan_adopt carries it over to a plan
+ * that has not stepped.  Margin / Softmax: the head's three loss launches become gigl_lp_task_loss's (rows, sum, backward)
+ * over the plan's scores and validity words — the same number of launches — in _step and in _eval, whose
+ * acc[GIGL_LP_EVAL_LOSS_SUM] then adds the task's weighted mean loss; the rank metrics do not depend on the task.
+ * Retrieval with weight w: the loss word and dscores times w.  Without this call, or with Retrieval at weight 1, the step
+ * issues exactly the launches it always did and produces the same bits.  The loss words stay {loss, valid query rows}; a
+ * batch that overflowed its workspace still gives a NaN loss and leaves Adam's counter where it was. */
+int32_t gigl_nablp_train_plan_set_task(gigl_nablp_train_plan* plan, int32_t kind, float param, float weight);
 /* dropout after every activated GraphSAGE layer of both encodes (see gigl_sage_train_plan_set_dropout: the mask, the rules
  * and what the step launches; encode 0 = the main batch, 1 = the random negatives) */
 int32_t gigl_nablp_train_plan_set_dropout(gigl_nablp_train_plan* plan, float p, uint64_t seed);
