@@ -162,6 +162,68 @@ int32_t gigl_linear_weight_grad_parts(gigl_ctx* ctx, const float* dy, const floa
 // union build with the plan-internal leaf-global option (union.hip)
 int32_t gigl_union_build_impl(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* tree, int32_t group_roots,
                               gigl_union* out, int32_t leaf_global);
+// hipMalloc'd bytes that `owned` frees with its plan (null: out of memory)
+static inline void* plan_alloc(std::vector<void*>& owned, size_t bytes) {
+  void* q = nullptr;
+  if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
+  owned.push_back(q);
+  return q;
+}
+// The buffers of one batch's sampled tree and union graph for b roots: tree->cnt / nbr per hop, un->col / meta / nodes /
+// rowptr / rowend / root_local, un->cap_nodes / cap_edges.  alias_rows (two hops, leaf-global union): the last hop's
+// sampled ids lie right behind un->col, so that the rows of level-1 nodes that occur once can BE their tree segments
+// (union.hip, row aliasing).  Returns the positions of un->col a row may address — cap_edges, plus the last hop's slots
+// when aliased — or 0: out of memory
+static inline int64_t gigl_batch_buffers_alloc(std::vector<void*>& owned, int32_t b, const int32_t* fanouts, int hops,
+                                               bool alias_rows, gigl_tree* tree, gigl_union* un) {
+  auto words = [&](int64_t n) { return plan_alloc(owned, (size_t)n * 4); };
+  gigl_union_capacity(b, fanouts, hops, &un->cap_nodes, &un->cap_edges);
+  int64_t parents = b, last_slots = b;
+  for (int k = 0; k < hops; ++k) last_slots *= fanouts[k];
+  const int64_t col_positions = un->cap_edges + (alias_rows ? last_slots : 0);
+  un->col = (int32_t*)words(col_positions);
+  bool ok = un->col != nullptr;
+  for (int k = 0; k < hops && ok; ++k) {
+    tree->cnt[k] = (int32_t*)words(parents);
+    parents *= fanouts[k];
+    tree->nbr[k] = (alias_rows && k == hops - 1) ? (uint32_t*)(un->col + un->cap_edges) : (uint32_t*)words(parents);
+    ok = tree->cnt[k] && tree->nbr[k];
+  }
+  un->meta = (int32_t*)words(GIGL_META_LEN);
+  un->nodes = (uint32_t*)words(un->cap_nodes);
+  un->rowptr = (int32_t*)words(un->cap_nodes + 2);
+  un->rowend = (int32_t*)words(un->cap_nodes + 2);
+  un->root_local = (int32_t*)words(b);
+  return ok && un->meta && un->nodes && un->rowptr && un->rowend && un->root_local ? col_positions : 0;
+}
+
+// A batch-graph workspace: what the GRAPH part of a batch (sample + union) fills and the layers read.  The one-call plan
+// is one of these plus its layer state, the training plans hold rings of them (batch_graph_* in pipeline.hip)
+struct BatchGraph {
+  gigl_ctx* ctx = nullptr;
+  gigl_graph* graph = nullptr;
+  int32_t b = 0, hops = 0;
+  int32_t group_roots = 0;  // roots per independent batch (== b: one batch)
+  int32_t fanouts[GIGL_MAX_HOPS] = {0};
+  // leaf-global union (union.hip): pure leaves get no local id and stay global ids in their parents' rows — nothing is
+  // ever computed for them, their feature rows are only gathered
+  bool leaf_global = false;
+  bool wide = false;  // ctx->wide at creation: rows for the worst batch, every node numbered (generic union)
+  int64_t col_positions = 0;  // of un.col that a row may address: past un.cap_edges where rows may alias tree segments
+  int64_t act_rows = 0;  // rows the layers hold, b*(1 + f0 + f0*f1 + ...) over hops-1 terms: the level guard's bound
+  // [0]: a device int32 0 (hops == 1: no row of the layer-0 gather holds local ids); the 60 zero bytes behind it are the
+  // owner's (the one-call plan keeps its half-split scales there)
+  int32_t* zero_dev = nullptr;
+  gigl_tree tree{};
+  gigl_union un{};
+  uint32_t* roots_buf = nullptr;  // [b] the roots the graph part reads: static input of the captured graphs
+  // edge table (batch_graph_attach_edge_table), read in place through eid [col_positions]: the table row of the edge
+  // stored at every used position of un.col, written by the graph part (plan_edge_ids_kernel)
+  gigl_feat* efeat = nullptr;
+  int32_t* eid = nullptr;
+  std::vector<void*> owned;
+};
+
 // exclusive scan of n int64 sizes on ctx->stream (one workgroup); out[n] = total, *status = total > cap (serialize.hip)
 void gigl_scan_i64(gigl_ctx* ctx, const int64_t* sizes, int64_t n, int64_t cap, int64_t* out, int32_t* status);
 // gather + reduce where the rows i >= *n_local_rows_dev hold GLOBAL source ids (no gather_ids translation): the

@@ -29,7 +29,8 @@
 #include <cstring>
 #include <new>
 #include <vector>
-
+// (plan_alloc inlines its push_back: the weak copy this object has always carried stays in the dynamic symbol table)
+template void std::vector<void*>::push_back(void* const&);
 // ------------------------------------------------------------------------------------------ communicators
 namespace {
 
@@ -1319,15 +1320,9 @@ int32_t gigl_dist_gat_plan_create(gigl_comm* comm, gigl_graph* shard, gigl_feat*
     p->att_src[l] = att_src[l];
     p->att_dst[l] = att_dst[l];
   }
-  auto alloc = [&](size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    p->owned.push_back(q);
-    return q;
-  };
-  p->gat_scratch = (float*)alloc((size_t)gigl_gat_input_layer_fused_scratch(shard_feat->d, heads[0], p->act_rows) * 4);
-  p->alpha_scratch = (float*)alloc((size_t)2 * p->act_rows * max_h * 4);
-  p->hw = (float*)alloc((size_t)p->act_rows * max_hc * 4);
+  p->gat_scratch = (float*)plan_alloc(p->owned, (size_t)gigl_gat_input_layer_fused_scratch(shard_feat->d, heads[0], p->act_rows) * 4);
+  p->alpha_scratch = (float*)plan_alloc(p->owned, (size_t)2 * p->act_rows * max_h * 4);
+  p->hw = (float*)plan_alloc(p->owned, (size_t)p->act_rows * max_hc * 4);
   if (!p->gat_scratch || !p->alpha_scratch || !p->hw) {
     gigl_dist_plan_destroy(p);
     return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the sharded GAT plan's workspace failed");
@@ -1397,18 +1392,12 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
     if (k < hops && dims[k] > max_in) max_in = dims[k];
     if (k > 0 && dims[k] > max_out) max_out = dims[k];
   }
-  auto alloc = [&](size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    p->owned.push_back(q);
-    return q;
-  };
+  auto alloc = [&](size_t bytes) { return plan_alloc(p->owned, bytes); };
   bool ok = true;
   const int64_t W = p->world;
-  int64_t cap_nodes = 0, cap_edges = 0;
-  gigl_union_capacity(b, fanouts, hops, &cap_nodes, &cap_edges);
   int64_t last_slots = b;
   for (int k = 0; k < hops; ++k) last_slots *= fanouts[k];
+  if (last_slots >= ((int64_t)1 << 31)) return fail(GIGL_E_INVALID_ARG, "tree too large");
   p->last_slots = last_slots;
   p->n_global = shard->n * W;
   // (the GAT layers number every union node and read the pulled rows through pos[]: generic union)
@@ -1432,10 +1421,11 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
   if (p->preproj && (!p->dense || (dims[1] & 3) != 0 || dims[1] > 2048))
     return fail(GIGL_E_UNSUPPORTED, "pre-projected rows need the dense pull bookkeeping (two hops, second fan-out <= 64, no "
                                     "owner-side projection) and a first-layer width % 4 == 0, <= 2048");
-  // (dense: the last hop's ids live right behind the union's col array so that rows can alias tree segments)
-  p->un.col = (int32_t*)alloc((size_t)(cap_edges + (p->dense ? last_slots : 0)) * 4);
-  ok = p->un.col != nullptr;
-  // ---- tree + per-hop exchange buffers
+  // ---- tree + union graph (dense: the last hop's ids live right behind the union's col array so that rows can alias
+  // tree segments), as the one-call plan lays them out
+  ok = gigl_batch_buffers_alloc(p->owned, b, fanouts, hops, p->dense, &p->tree, &p->un) != 0;
+  const int64_t cap_nodes = p->un.cap_nodes;
+  // ---- per-hop exchange buffers
   int64_t parents = b, max_served = 0;
   for (int k = 0; k < hops && ok; ++k) {
     p->m[k] = parents;
@@ -1448,9 +1438,7 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
     }
     p->cap[k] = cap;
     if (W * cap > max_served) max_served = W * cap;
-    p->tree.cnt[k] = (int32_t*)alloc((size_t)parents * 4);
     parents *= fanouts[k];
-    p->tree.nbr[k] = (p->dense && k == hops - 1) ? (uint32_t*)(p->un.col + cap_edges) : (uint32_t*)alloc((size_t)parents * 4);
     p->child_ksum[k] = (uint32_t*)alloc((size_t)parents * 4);
     p->rq_nodes_s[k] = (uint32_t*)alloc((size_t)W * cap * 4);
     p->rq_ksum_s[k] = (uint32_t*)alloc((size_t)W * cap * 4);
@@ -1460,9 +1448,8 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
     p->resp_r[k] = (uint32_t*)alloc((size_t)W * cap * fanouts[k] * 4);
     p->hop_pos[k] = (int32_t*)alloc((size_t)p->m[k] * 4);
     p->counts[k] = (int32_t*)alloc((size_t)(W + 1) * 4);
-    ok = p->tree.cnt[k] && p->tree.nbr[k] && p->child_ksum[k] && p->rq_nodes_s[k] && p->rq_ksum_s[k] &&
-         p->rq_nodes_r[k] && p->rq_ksum_r[k] && p->resp_s[k] && p->resp_r[k] && p->hop_pos[k] && p->counts[k];
-    if (parents >= ((int64_t)1 << 31)) return fail(GIGL_E_INVALID_ARG, "tree too large");
+    ok = p->child_ksum[k] && p->rq_nodes_s[k] && p->rq_ksum_s[k] && p->rq_nodes_r[k] && p->rq_ksum_r[k] && p->resp_s[k] &&
+         p->resp_r[k] && p->hop_pos[k] && p->counts[k];
   }
   p->tree.hops = hops;
   p->tree.b = b;
@@ -1484,12 +1471,6 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
     if (!sok) return fail(GIGL_E_OOM, "dist plan: side stream for the in-step overlap");
     p->overlap = true;
   }
-  // ---- union graph
-  p->un.meta = (int32_t*)alloc(GIGL_META_LEN * 4);
-  p->un.nodes = (uint32_t*)alloc((size_t)cap_nodes * 4);
-  p->un.rowptr = (int32_t*)alloc((size_t)(cap_nodes + 2) * 4);
-  p->un.rowend = (int32_t*)alloc((size_t)(cap_nodes + 2) * 4);
-  p->un.root_local = (int32_t*)alloc((size_t)b * 4);
   if (p->dense && !p->peer) {  // (a peer-mapped plan claims nothing; its hot marks are allocated with the hot set)
     p->stamp = (uint32_t*)alloc((size_t)p->n_global * 4);
     p->slot_map = (int32_t*)alloc((size_t)p->n_global * 4);
@@ -1498,8 +1479,6 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
                hipMemsetAsync(p->slot_map, 0, (size_t)p->n_global * 4, ctx->stream) != hipSuccess))
       ok = false;
   }
-  p->un.cap_nodes = cap_nodes;
-  p->un.cap_edges = cap_edges;
   int64_t act_rows = 0, width = b;
   for (int k = 0; k < hops; ++k) {
     act_rows += width;
@@ -1521,8 +1500,7 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
   p->req_counts = (int32_t*)alloc((size_t)(W + 1) * 4);
   p->rows_s = alloc((size_t)W * pc * p->row_bytes);
   p->rows_r = alloc((size_t)W * pc * p->row_bytes);
-  ok = ok && p->own_cnt && p->un.meta && p->un.nodes && p->un.rowptr && p->un.rowend && p->un.col &&
-       p->un.root_local && p->ids_s && p->ids_r && p->pos && p->pull_counts && p->req_counts && p->rows_s && p->rows_r;
+  ok = ok && p->own_cnt && p->ids_s && p->ids_r && p->pos && p->pull_counts && p->req_counts && p->rows_s && p->rows_r;
   p->n_entries_dev = (int32_t*)alloc(16);
   if (p->peer && ok) {
     p->peers_dev = (const void**)alloc((size_t)W * sizeof(void*));
@@ -1538,9 +1516,11 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
     p->peer_col_dev = (const uint32_t**)alloc((size_t)W * sizeof(void*));
     ok = p->peer_rowptr_dev && p->peer_col_dev;
   }
-  if (p->preproj && ok && !p->peer) {  // the second pull's buckets (W_r x of the inner nodes)
-    int64_t pcb = opts && opts->pull_cap_b > 0 ? opts->pull_cap_b
-                                               : (int64_t)std::ceil((double)act_rows / (double)W * (W > 1 ? 1.25 : 1.0)) + 512;
+  // the second pull's buckets: W_r x of the inner nodes (pre-projected rows; the caller's bound when given), or the inner
+  // nodes' own rows (owner-side projection: dense excludes it)
+  if ((p->project || (p->preproj && !p->peer)) && ok) {
+    int64_t pcb = p->preproj && opts->pull_cap_b > 0 ? opts->pull_cap_b
+                                                     : (int64_t)std::ceil((double)act_rows / (double)W * (W > 1 ? 1.25 : 1.0)) + 512;
     if (pcb > act_rows) pcb = act_rows;
     p->pull_cap_b = pcb;
     p->idsb_s = (uint32_t*)alloc((size_t)W * pcb * 4);
@@ -1552,21 +1532,10 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
     ok = p->idsb_s && p->idsb_r && p->posb && p->pullb_counts && p->rowsb_s && p->rowsb_r;
   }
   if (p->project && ok) {
-    int64_t pcb = (int64_t)std::ceil((double)act_rows / (double)W * (W > 1 ? 1.25 : 1.0)) + 512;
-    if (pcb > act_rows) pcb = act_rows;
-    p->pull_cap_b = pcb;
-    p->idsb_s = (uint32_t*)alloc((size_t)W * pcb * 4);
-    p->idsb_r = (uint32_t*)alloc((size_t)W * pcb * 4);
-    p->posb = (int32_t*)alloc((size_t)act_rows * 4);
-    p->pullb_counts = (int32_t*)alloc((size_t)(W + 1) * 4);
-    p->rowsb_s = alloc((size_t)W * pcb * p->row_bytes);
-    p->rowsb_r = alloc((size_t)W * pcb * p->row_bytes);
-    p->stage = (float*)alloc((size_t)W * (pc > pcb ? pc : pcb) * dims[0] * 4);
+    p->stage = (float*)alloc((size_t)W * (pc > p->pull_cap_b ? pc : p->pull_cap_b) * dims[0] * 4);
     p->wl0 = (float*)alloc((size_t)dims[1] * dims[0] * 4);
     p->wr0 = (float*)alloc((size_t)dims[1] * dims[0] * 4);
-    ok = p->idsb_s && p->idsb_r && p->posb && p->pullb_counts && p->rowsb_s && p->rowsb_r && p->stage && p->wl0 &&
-         p->wr0;
-    if (ok && W * pc >= ((int64_t)1 << 31)) ok = false;
+    ok = p->stage && p->wl0 && p->wr0 && W * pc < ((int64_t)1 << 31);
   }
   // ---- activations
   // (a plan over pre-projected rows never forms the first layer's [mean | self] operand: its abuf serves layers >= 1 only —
@@ -1634,10 +1603,8 @@ int32_t gigl_dist_plan_set_hot_rows(gigl_dist_plan* p, const uint32_t* hot_ids, 
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (p->peer) {
     if (!p->slot_map && n_hot > 0) {
-      void* q = nullptr;
-      if (hipMalloc(&q, (size_t)p->n_global * 4) != hipSuccess) return gigl_fail(ctx, GIGL_E_OOM, "hot-row marks: hipMalloc failed");
-      p->owned.push_back(q);
-      p->slot_map = (int32_t*)q;
+      p->slot_map = (int32_t*)plan_alloc(p->owned, (size_t)p->n_global * 4);
+      if (!p->slot_map) return gigl_fail(ctx, GIGL_E_OOM, "hot-row marks: hipMalloc failed");
       p->has_hot = true;  // (cleared below)
     }
     if (p->has_hot) GIGL_HIP_CHECK(ctx, hipMemsetAsync(p->slot_map, 0, (size_t)p->n_global * 4, ctx->stream));

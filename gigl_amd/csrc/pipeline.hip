@@ -56,23 +56,11 @@ struct StreamScope {
   ~StreamScope() { ctx->stream = keep; }
 };
 
-// hipMalloc'd bytes that `owned` frees with its plan (null: out of memory)
-void* plan_alloc(std::vector<void*>& owned, size_t bytes) {
-  void* q = nullptr;
-  if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-  owned.push_back(q);
-  return q;
-}
-
 }  // namespace
 
-struct gigl_sage_plan {
-  gigl_ctx* ctx = nullptr;
-  gigl_graph* graph = nullptr;
+// the one-call plan: a batch-graph workspace (common.h; its `owned` holds the layer buffers too) and the layers' state
+struct gigl_sage_plan : BatchGraph {
   gigl_feat* feat = nullptr;
-  int32_t b = 0, hops = 0;
-  int32_t group_roots = 0;  // roots per independent batch (== b: one batch)
-  int32_t fanouts[GIGL_MAX_HOPS] = {0};
   int32_t dims[GIGL_MAX_HOPS + 1] = {0};  // dims[0] = input dim, dims[l+1] = output dim of layer l
   const float* w[GIGL_MAX_HOPS] = {nullptr};     // fused [dims[l+1]][2*dims[l]] (= [W_l | W_r]), device, borrowed
   const float* bias[GIGL_MAX_HOPS] = {nullptr};  // device, borrowed, may be null
@@ -98,25 +86,12 @@ struct gigl_sage_plan {
   float* gat_scratch = nullptr;    // first layer: folded vectors + the per-head tiled operands
   float* alpha_scratch = nullptr;  // layers >= 1: per-node attention dots [2 * act_rows * max heads]
   float* hw = nullptr;             // layers >= 1: projected source rows [act_rows][max heads*channels]
-  // edge features (gigl_gat_plan_set_edge_features): the resident edge table is read in place through eid — the table row
-  // of the edge stored at every used position of un.col, written by the GRAPH part (plan_edge_ids_kernel)
-  gigl_feat* efeat = nullptr;
+  // edge features (gigl_gat_plan_set_edge_features: the workspace's efeat / eid, and per layer)
   const float* att_edge[GIGL_MAX_HOPS] = {nullptr};  // folded [heads_l][De], device, borrowed
   const float* w_msg[GIGL_MAX_HOPS] = {nullptr};     // [heads_l*channels_l][De] or null, device, borrowed
-  int32_t* eid = nullptr;   // [positions of un.col]
   float* ze = nullptr;      // first layer: sum_e alpha_e e per row and head [act_rows][heads_0][De] (edge messages)
   bool l2_normalize = false;  // the b output rows become x / max(|x|_2, 1e-12) (gigl_sage_plan_set_l2_normalize)
-  // leaf-global union (union.hip): pure leaves get no local id and stay global ids in their parents' rows — the
-  // plan never computes anything for them, it only gathers their feature rows
-  bool leaf_global = false;
-  bool wide = false;  // ctx->wide at creation: rows for the worst batch, every node numbered (generic union)
-  bool alias_rows = false;  // tree.nbr[hops-1] == un.col + un.cap_edges (rows may alias tree segments)
-  int64_t last_slots = 0;
-  int64_t act_rows = 0;         // rows of abuf / hbuf
-  int32_t* zero_dev = nullptr;  // a device int32 0 (hops == 1: no row of the layer-0 gather holds local ids)
-  gigl_tree tree{};
-  gigl_union un{};
-  float* abuf = nullptr;  // [act_rows][2*max_in], act_rows = b*(1 + f0 + f0*f1 + ...) over hops-1 terms
+  float* abuf = nullptr;  // [act_rows][2*max_in]
   // the aggregated matrix in the projection's tiled layout ([row tile of 128][K chunk of 32][128][32]): a tile's chunk
   // is 16 KB contiguous instead of 128 pieces of 128 B at a stride of one row (agg.hip)
   bool tiled = false;
@@ -132,7 +107,6 @@ struct gigl_sage_plan {
   bool f2_ok = false;
   float* f2_dev = nullptr;  // {s_h, s_w2, 1 / (s_h s_w2)}: the second product's scales (gigl_fused2_prepare, per run)
   void* w2h = nullptr;      // W1's and W2's fp16 images (gigl_fused2_prepare)
-  std::vector<void*> owned;
   // what a call runs, in order, for the plan as it is configured now (plan_build_steps: at creation and wherever the
   // configuration changes; a run only walks it)
   Step steps[MAX_STEPS];
@@ -140,7 +114,6 @@ struct gigl_sage_plan {
   bool fused2 = false;  // fused2_on() when the list was built
   // hipGraph replay
   bool use_graph = false;
-  uint32_t* roots_buf = nullptr;  // static input of the captured graphs
   float* out_buf = nullptr;       // (placeholder `out` of the captures; the step that writes `out` runs eagerly)
   Segment segs[MAX_STEPS];
   int n_segs = 0;
@@ -325,11 +298,84 @@ bool f2_all_wr() {
   return on;
 }
 
+// ---- the batch-graph workspace (BatchGraph, common.h), for batches of b roots on ctx.  number_every_node: the generic
+// union (the layers read every source row through un.nodes); else leaf-global where the build allows it — no wide
+// workspaces, hops <= 2, ids below 2^31 (row values are compared as int32) and a last fan-out the two-hop builds keep in
+// a 64-bit mask (beyond it, the workgroup-per-row sampler path, the generic build) — two hops with the aliased layout
+int32_t batch_graph_init(BatchGraph* g, gigl_ctx* ctx, gigl_graph* graph, int32_t b, const int32_t* fanouts, int32_t hops,
+                         bool number_every_node) {
+  g->ctx = ctx;
+  g->graph = graph;
+  g->b = b;
+  g->group_roots = b;
+  g->hops = hops;
+  for (int k = 0; k < hops; ++k) g->fanouts[k] = fanouts[k];
+  g->wide = ctx->wide;
+  g->leaf_global = !number_every_node && !g->wide && hops <= 2 && graph->n < ((int64_t)1 << 31) &&
+                   !(hops == 2 && fanouts[1] > GIGL_FAST_FANOUT);
+  // activations exist only for nodes of level < hops (leaves are read straight from the feature table)
+  g->act_rows = gigl_level_rows(g->wide, b, fanouts, hops, hops - 1);
+  g->col_positions = gigl_batch_buffers_alloc(g->owned, b, fanouts, hops, g->leaf_global && hops == 2, &g->tree, &g->un);
+  g->roots_buf = (uint32_t*)plan_alloc(g->owned, (size_t)b * 4);
+  g->zero_dev = (int32_t*)plan_alloc(g->owned, 64);
+  if (g->col_positions && g->roots_buf && g->zero_dev && hipMemset(g->zero_dev, 0, 64) == hipSuccess) return GIGL_OK;
+  return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the batch workspace failed (cap_nodes=%lld)", (long long)g->un.cap_nodes);
+}
+
+void batch_graph_free(BatchGraph* g) {
+  for (void* q : g->owned) hipFree(q);
+  g->owned.clear();
+}
+
 // A leaf-global union numbers the nodes of level <= L-2 only: the rows of level L-1 — behind this device count; every row
 // of a one-hop plan — keep their sources as GLOBAL ids.  Null: every row holds local ids
-const int32_t* first_global_row(const gigl_sage_plan* p) {
-  if (!p->leaf_global) return nullptr;
-  return p->hops >= 2 ? p->un.meta + GIGL_META_LEVEL0 + (p->hops - 2) : p->zero_dev;
+const int32_t* first_global_row(const BatchGraph* g) {
+  if (!g->leaf_global) return nullptr;
+  return g->hops >= 2 ? g->un.meta + GIGL_META_LEVEL0 + (g->hops - 2) : g->zero_dev;
+}
+
+// the graph part reads `table` (one row per resident edge) in place from now on: eid is sized once, for every later run
+// (nothing is allocated inside a run: the graph part is captured), and filled with -1
+int32_t batch_graph_attach_edge_table(BatchGraph* g, gigl_feat* table) {
+  if (!g->eid) {
+    g->eid = (int32_t*)plan_alloc(g->owned, (size_t)g->col_positions * 4);
+    if (!g->eid) return gigl_fail(g->ctx, GIGL_E_OOM, "hipMalloc of the batch workspace's edge ids failed");
+    GIGL_HIP_CHECK(g->ctx, hipMemset(g->eid, 0xFF, (size_t)g->col_positions * 4));
+  }
+  g->efeat = table;
+  return GIGL_OK;
+}
+
+// the graph part of one batch, on g's ctx stream: the sampled tree of `roots` ...
+int32_t batch_graph_sample(BatchGraph* g, const uint32_t* roots, int32_t seed, int32_t mode) {
+  return gigl_sample_khop(g->ctx, g->graph, roots, g->b, g->fanouts, g->hops, seed, mode, &g->tree);
+}
+// ... and its union graph, the level guard and, with an edge table, the edge ids
+int32_t batch_graph_union(BatchGraph* g, const uint32_t* roots) {
+  gigl_ctx* ctx = g->ctx;
+  const int L = g->hops;
+  int32_t rc = gigl_union_build_impl(ctx, roots, &g->tree, g->group_roots, &g->un,
+                                     g->leaf_global ? (1 | (g->graph->multi ? 2 : 0)) : 0);
+  if (rc != GIGL_OK) return rc;
+  hipLaunchKernelGGL(guard_levels_kernel, dim3(1), dim3(64), 0, ctx->stream, g->un.meta, g->hops,
+                     (int32_t)(g->act_rows < 0x7FFFFFFF ? g->act_rows : 0x7FFFFFFF));
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  if (g->efeat) {  // the edge ids belong to the GRAPH part: integer work over the union, independent of the weights
+    const int64_t rows_cap = gigl_level_rows(g->wide, g->b, g->fanouts, L, L - 1);
+    int64_t blocks = (rows_cap + 3) / 4;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(plan_edge_ids_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, g->graph->rowptr, g->graph->col,
+                       g->graph->n, g->un.nodes, g->un.rowptr, g->un.rowend, g->un.col, g->un.meta + GIGL_META_LEVEL0 + (L - 1),
+                       first_global_row(g), rows_cap, g->col_positions, g->eid);
+    GIGL_HIP_CHECK(ctx, hipGetLastError());
+  }
+  return GIGL_OK;
+}
+
+// both, for g's own roots_buf
+int32_t batch_graph_enqueue(BatchGraph* g, int32_t seed, int32_t mode) {
+  const int32_t rc = batch_graph_sample(g, g->roots_buf, seed, mode);
+  return rc != GIGL_OK ? rc : batch_graph_union(g, g->roots_buf);
 }
 
 // layer l computes the nodes of level <= L-1-l: at most b*(1 + f0 + f0*f1 + ...) of them — the launch is
@@ -348,31 +394,9 @@ LayerRows layer_rows(const gigl_sage_plan* p, int l) {
 
 // ---- the steps of one batch.  Each enqueues on the ctx stream; which of them a plan runs: plan_build_steps
 
-int32_t step_sample(gigl_sage_plan* p, int, const RunArgs& a) {
-  return gigl_sample_khop(p->ctx, p->graph, a.roots, p->b, p->fanouts, p->hops, a.seed, a.mode, &p->tree);
-}
-
-// the batch union graph, the level guard and, with edge features, the edge ids
-int32_t step_union(gigl_sage_plan* p, int, const RunArgs& a) {
-  gigl_ctx* ctx = p->ctx;
-  const int L = p->hops;
-  int32_t rc = gigl_union_build_impl(ctx, a.roots, &p->tree, p->group_roots, &p->un,
-                                     p->leaf_global ? (1 | (p->graph->multi ? 2 : 0)) : 0);
-  if (rc != GIGL_OK) return rc;
-  hipLaunchKernelGGL(guard_levels_kernel, dim3(1), dim3(64), 0, ctx->stream, p->un.meta, p->hops,
-                     (int32_t)(p->act_rows < 0x7FFFFFFF ? p->act_rows : 0x7FFFFFFF));
-  GIGL_HIP_CHECK(ctx, hipGetLastError());
-  if (p->efeat) {  // the edge ids belong to the GRAPH part: integer work over the union, independent of the weights
-    const int64_t rows_cap = gigl_level_rows(p->wide, p->b, p->fanouts, L, L - 1);
-    int64_t blocks = (rows_cap + 3) / 4;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(plan_edge_ids_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, p->graph->rowptr, p->graph->col,
-                       p->graph->n, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col, p->un.meta + GIGL_META_LEVEL0 + (L - 1),
-                       first_global_row(p), rows_cap, p->un.cap_edges + (p->alias_rows ? p->last_slots : 0), p->eid);
-    GIGL_HIP_CHECK(ctx, hipGetLastError());
-  }
-  return GIGL_OK;
-}
+// (the GRAPH part as two steps: their launches are timed under different profile ids)
+int32_t step_sample(gigl_sage_plan* p, int, const RunArgs& a) { return batch_graph_sample(p, a.roots, a.seed, a.mode); }
+int32_t step_union(gigl_sage_plan* p, int, const RunArgs& a) { return batch_graph_union(p, a.roots); }
 
 // two-source operand: the projection reads the self half from the fp32 source rows themselves (the feature table
 // through union.nodes, or the previous layer's output), the gather writes the reduced half only
@@ -517,8 +541,8 @@ int32_t step_gat_attend(gigl_sage_plan* p, int l, const RunArgs&) {
   if (p->efeat)  // (a_edge lies behind the 2 * src_cap * heads node dots of alpha_scratch)
     return gigl_gat_aggregate_edge_indexed(ctx, p->hw, p->att_src[l], p->att_dst[l], p->heads[l], p->channels[l], p->slope, 1,
                                            p->un.rowptr, p->un.rowend, p->un.col, n_src, src_cap, r.n_rows, r.rows_cap, p->bias[l],
-                                           r.act, (const float*)p->efeat->rows, p->eid, p->efeat->d,
-                                           p->un.cap_edges + (p->alias_rows ? p->last_slots : 0), p->att_edge[l], p->w_msg[l],
+                                           r.act, (const float*)p->efeat->rows, p->eid, p->efeat->d, p->col_positions,
+                                           p->att_edge[l], p->w_msg[l],
                                            p->alpha_scratch, p->hbuf[l & 1]);
   return gigl_gat_aggregate(ctx, p->hw, p->att_src[l], p->att_dst[l], p->heads[l], p->channels[l], p->slope, 1,
                             p->un.rowptr, p->un.rowend, p->un.col, n_src, src_cap, r.n_rows, r.rows_cap, p->bias[l], r.act,
@@ -1024,7 +1048,7 @@ int32_t gigl_sage_plan_destroy(gigl_sage_plan* p) {
   drop_graphs(p);
   if (p->ev_in) hipEventDestroy(p->ev_in);
   if (p->ev_graph) hipEventDestroy(p->ev_graph);
-  for (void* q : p->owned) hipFree(q);
+  batch_graph_free(p);
   delete p;
   return GIGL_OK;
 }
@@ -1041,6 +1065,14 @@ int32_t gigl_sage_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat,
   return plan_create(ctx, graph, feat, b, fanouts, hops, dims, w, bias, act_last, true, out);
 }
 
+// what every plan's layers need of their shapes and parameters: widths >= 1 from the table's, no null weight
+static int32_t plan_check_layers(gigl_ctx* ctx, const gigl_feat* feat, int32_t hops, const int32_t* dims, const float* const* w) {
+  GIGL_REQUIRE(ctx, dims[0] == feat->d, "dims[0]=%d != feature dim %d", dims[0], feat->d);
+  for (int k = 0; k < hops; ++k) GIGL_REQUIRE(ctx, w[k], "weight %d is null", k);
+  for (int k = 0; k <= hops; ++k) GIGL_REQUIRE(ctx, dims[k] >= 1, "dims[%d]=%d", k, dims[k]);
+  return GIGL_OK;
+}
+
 // with_abuf false: no [mean | self] operand buffer (the GAT plan aggregates into its own per-head operands)
 static int32_t plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, int32_t b, const int32_t* fanouts,
                            int32_t hops, const int32_t* dims, const float* const* w, const float* const* bias,
@@ -1049,88 +1081,42 @@ static int32_t plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, in
   *out = nullptr;
   GIGL_REQUIRE(ctx, graph && feat && fanouts && dims && w, "null argument");
   GIGL_REQUIRE(ctx, hops >= 1 && hops <= GIGL_MAX_HOPS && b >= 1, "bad plan shape");
-  GIGL_REQUIRE(ctx, dims[0] == feat->d, "dims[0]=%d != feature dim %d", dims[0], feat->d);
+  int32_t rc = plan_check_layers(ctx, feat, hops, dims, w);
+  if (rc != GIGL_OK) return rc;
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   gigl_sage_plan* p = new (std::nothrow) gigl_sage_plan();
   if (!p) return gigl_fail(ctx, GIGL_E_OOM, "host OOM");
-  p->ctx = ctx;
-  p->graph = graph;
+  rc = batch_graph_init(p, ctx, graph, b, fanouts, hops, false);
+  if (rc != GIGL_OK) {
+    gigl_sage_plan_destroy(p);
+    return rc;
+  }
   p->feat = feat;
-  p->b = b;
-  p->group_roots = b;
-  p->hops = hops;
   p->act_last = act_last;
-  int64_t cap_nodes = 0, cap_edges = 0;
   int32_t max_in = 0, max_out = 0;
   for (int k = 0; k < hops; ++k) {
-    p->fanouts[k] = fanouts[k];
     p->w[k] = w[k];
     p->bias[k] = bias ? bias[k] : nullptr;
-    if (!w[k]) {
-      delete p;
-      return gigl_fail(ctx, GIGL_E_INVALID_ARG, "weight %d is null", k);
-    }
   }
   for (int k = 0; k <= hops; ++k) {
     p->dims[k] = dims[k];
-    if (dims[k] < 1) {
-      delete p;
-      return gigl_fail(ctx, GIGL_E_INVALID_ARG, "dims[%d]=%d", k, dims[k]);
-    }
     if (k < hops && dims[k] > max_in) max_in = dims[k];
     if (k > 0 && dims[k] > max_out) max_out = dims[k];
   }
-  if (gigl_union_capacity(b, fanouts, hops, &cap_nodes, &cap_edges) != GIGL_OK) {
-    delete p;
-    return gigl_fail(ctx, GIGL_E_INVALID_ARG, "bad fanouts");
-  }
   auto alloc = [&](size_t bytes) { return plan_alloc(p->owned, bytes); };
   bool ok = true;
-  // (the two-hop leaf-global builds keep a hop-0 slot's children in a 64-bit mask: last-hop fanouts beyond 64 — the
-  // workgroup-per-row sampler path — take the generic union build)
-  p->wide = ctx->wide;
-  p->leaf_global = !p->wide && hops <= 2 && graph->n < ((int64_t)1 << 31) && !(hops == 2 && fanouts[1] > GIGL_FAST_FANOUT);
-  // two hops, leaf-global union: the last hop's sampled ids live right behind the union's col array, so that the
-  // rows of level-1 nodes that occur once can BE their tree segments (union.hip, row aliasing)
-  int64_t last_slots = b;
-  for (int k = 0; k < hops; ++k) last_slots *= fanouts[k];
-  p->alias_rows = p->leaf_global && hops == 2;
-  p->last_slots = last_slots;
-  p->un.col = (int32_t*)alloc((size_t)(cap_edges + (p->alias_rows ? last_slots : 0)) * 4);
-  ok = p->un.col != nullptr;
-  int64_t parents = b;
-  for (int k = 0; k < hops && ok; ++k) {
-    p->tree.cnt[k] = (int32_t*)alloc((size_t)parents * 4);
-    parents *= fanouts[k];
-    p->tree.nbr[k] = (p->alias_rows && k == hops - 1) ? (uint32_t*)(p->un.col + cap_edges)
-                                                      : (uint32_t*)alloc((size_t)parents * 4);
-    ok = p->tree.cnt[k] && p->tree.nbr[k];
-  }
-  p->un.meta = (int32_t*)alloc(GIGL_META_LEN * 4);
-  p->un.nodes = (uint32_t*)alloc((size_t)cap_nodes * 4);
-  p->un.rowptr = (int32_t*)alloc((size_t)(cap_nodes + 2) * 4);
-  p->un.rowend = (int32_t*)alloc((size_t)(cap_nodes + 2) * 4);
-  p->un.root_local = (int32_t*)alloc((size_t)b * 4);
-  p->un.cap_nodes = cap_nodes;
-  p->un.cap_edges = cap_edges;
-  // activations exist only for nodes of level < hops (leaves are read straight from the feature table)
-  const int64_t act_rows = gigl_level_rows(p->wide, b, fanouts, hops, hops - 1);
   p->tiled = getenv("GIGL_PLAN_ROW_MAJOR") == nullptr;  // (A/B knob)
   p->two_source = getenv("GIGL_PLAN_SELF_COPY") == nullptr;  // (A/B knob: set = gather writes [mean | self])
   for (int k = 0; k < hops; ++k)
     if ((dims[k] & 3) != 0 || dims[k] > 2048) p->tiled = false;
   if (with_abuf) {
-    const size_t row_tiles = ((size_t)act_rows + 127) / 128, nkc = ((size_t)2 * max_in + 31) / 32;
-    p->abuf = (float*)alloc(p->tiled ? row_tiles * nkc * 4096 * 4 : (size_t)act_rows * 2 * max_in * 4);
+    const size_t row_tiles = ((size_t)p->act_rows + 127) / 128, nkc = ((size_t)2 * max_in + 31) / 32;
+    p->abuf = (float*)alloc(p->tiled ? row_tiles * nkc * 4096 * 4 : (size_t)p->act_rows * 2 * max_in * 4);
   }
-  p->hbuf[0] = (float*)alloc((size_t)act_rows * max_out * 4);
-  p->hbuf[1] = hops > 1 ? (float*)alloc((size_t)act_rows * max_out * 4) : p->hbuf[0];
-  p->roots_buf = (uint32_t*)alloc((size_t)b * 4);
+  p->hbuf[0] = (float*)alloc((size_t)p->act_rows * max_out * 4);
+  p->hbuf[1] = hops > 1 ? (float*)alloc((size_t)p->act_rows * max_out * 4) : p->hbuf[0];
   p->out_buf = (float*)alloc((size_t)b * dims[hops] * 4);
-  p->zero_dev = (int32_t*)alloc(64);  // [0]: an int32 0; [4..7): hs_dev scales, [8..10): its running maximum + ticket (zero)
-  if (p->zero_dev && hipMemset(p->zero_dev, 0, 64) != hipSuccess) ok = false;
-  p->hs_dev = p->zero_dev ? reinterpret_cast<float*>(p->zero_dev + 4) : nullptr;
-  p->act_rows = act_rows;
+  p->hs_dev = reinterpret_cast<float*>(p->zero_dev + 4);  // [4..7): the scales, [8..10): their running maximum + ticket (zero)
   for (int k = 1; k < hops && with_abuf; ++k) {
     p->hs_layer[k] = (float*)alloc(64);
     ok = ok && p->hs_layer[k] && hipMemset(p->hs_layer[k], 0, 64) == hipSuccess;
@@ -1142,12 +1128,11 @@ static int32_t plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, in
     p->f2_ok = p->f2_dev && p->w2h && hipMemset(p->f2_dev, 0, 64) == hipSuccess;
     ok = ok && p->f2_ok;
   }
-  ok = ok && p->zero_dev && p->un.meta && p->un.nodes && p->un.rowptr && p->un.rowend && p->un.col && p->un.root_local &&
-       (p->abuf || !with_abuf) && p->hbuf[0] && p->hbuf[1] && p->roots_buf && p->out_buf;
+  ok = ok && (p->abuf || !with_abuf) && p->hbuf[0] && p->hbuf[1] && p->out_buf;
   if (!ok) {
     gigl_sage_plan_destroy(p);
     return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the batch workspace failed (cap_nodes=%lld)",
-                     (long long)cap_nodes);
+                     (long long)p->un.cap_nodes);
   }
   {
     const int32_t rc_hs = plan_refresh_half_split(p);
@@ -1242,16 +1227,12 @@ int32_t gigl_gat_plan_set_edge_features(gigl_sage_plan* p, gigl_feat* edge_table
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   plan_invalidate(p);  // (the pointers are baked into the captured kernels)
   auto alloc = [&](size_t bytes) { return plan_alloc(p->owned, bytes); };
-  const int64_t positions = p->un.cap_edges + (p->alias_rows ? p->last_slots : 0);
   int32_t max_h = 1;
   for (int l = 0; l < p->hops; ++l) max_h = p->heads[l] > max_h ? p->heads[l] : max_h;
-  if (!p->eid) {  // sized once, for every later run (nothing is allocated inside a run: the plan is captured)
+  if (!p->eid) {  // the first table: alpha_scratch grows by the edges' logits (sized once, the plan is captured)
     GIGL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (alpha_scratch is replaced: no launch may still use it)
-    int32_t* eid = (int32_t*)alloc((size_t)positions * 4);
-    float* alpha = (float*)alloc((size_t)(2 * p->act_rows + positions) * max_h * 4);
-    if (!eid || !alpha) return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the GAT plan's edge workspace failed");
-    GIGL_HIP_CHECK(ctx, hipMemset(eid, 0xFF, (size_t)positions * 4));
-    p->eid = eid;
+    float* alpha = (float*)alloc((size_t)(2 * p->act_rows + p->col_positions) * max_h * 4);
+    if (!alpha) return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the GAT plan's edge workspace failed");
     p->alpha_scratch = alpha;
   }
   const size_t ze_floats = (size_t)p->act_rows * p->heads[0] * 64;
@@ -1263,8 +1244,7 @@ int32_t gigl_gat_plan_set_edge_features(gigl_sage_plan* p, gigl_feat* edge_table
     p->att_edge[l] = att_edge_folded[l];
     p->w_msg[l] = w_edge_msg ? w_edge_msg[l] : nullptr;
   }
-  p->efeat = edge_table;
-  return GIGL_OK;
+  return batch_graph_attach_edge_table(p, edge_table);
 }
 
 int32_t gigl_sage_plan_set_l2_normalize(gigl_sage_plan* p, int32_t on) {
@@ -1355,7 +1335,7 @@ int32_t gigl_sage_plan_buffers(gigl_sage_plan* p, gigl_tree* tree, gigl_union* u
   if (tree) *tree = p->tree;
   if (un) {
     *un = p->un;
-    if (p->alias_rows) un->cap_edges += p->last_slots;  // rowptr / rowend may point into the aliased tree segments
+    un->cap_edges = p->col_positions;  // rowptr / rowend may point into the aliased tree segments
   }
   return GIGL_OK;
 }
@@ -1545,6 +1525,7 @@ static bool train_bwd_gather(const int32_t* dims, int32_t hops) {
 
 // what the encodes of a plan share: the layers' shapes, the parameters, Adam's state
 struct SageTrainShared {
+  gigl_feat* feat = nullptr;  // the node features every encode's first layer gathers
   int32_t L = 0, act_last = 0;
   int32_t dims[GIGL_MAX_HOPS + 1] = {0};
   float* w[GIGL_MAX_HOPS] = {nullptr};  // fused [dims[l+1]][2 dims[l]]: borrowed, UPDATED IN PLACE
@@ -1561,7 +1542,7 @@ struct SageTrainShared {
 
 // one encode's state
 struct SageTrainEnc {
-  gigl_sage_plan* base = nullptr;  // (link-prediction plans) tree / union workspace of this encode's roots, set per step
+  BatchGraph* base = nullptr;      // (link-prediction plans) batch graph of this encode's roots, set per step
   int32_t b = 0;                   // roots
   int64_t rows_cap[GIGL_MAX_HOPS] = {0};  // rows layer l may compute
   float* a[GIGL_MAX_HOPS] = {nullptr};    // [rows_cap[l]][2 dims[l]]: the layer's [mean | self] operand
@@ -1659,10 +1640,10 @@ bool sage_tlists_alloc(const SageTrainShared& s, const SageTrainEnc& e, std::vec
   return true;
 }
 
-// the graph part of one root set, on workspace p's ctx: sample + union (+ the level guard) ...
-int32_t sage_enqueue_graph(const SageTrainShared& s, const SageTrainEnc& e, gigl_sage_plan* p, int32_t* const* tl,
+// the graph part of one root set, on workspace p's ctx: sample + union (+ the level guard, the edge ids) ...
+int32_t sage_enqueue_graph(const SageTrainShared& s, const SageTrainEnc& e, BatchGraph* p, int32_t* const* tl,
                            int32_t sampling_seed, int32_t mode) {
-  int32_t rc = run_steps(p, 0, GRAPH_STEPS, {p->roots_buf, sampling_seed, mode, nullptr});
+  int32_t rc = batch_graph_enqueue(p, sampling_seed, mode);
   // ... and who reads which source row in the backward of layers >= 1 (a function of the batch graph alone)
   for (int l = 1; l < s.L && rc == GIGL_OK && s.bwd_gather; ++l)
     rc = gigl_transposed_rows_build(p->ctx, p->un.rowptr, p->un.rowend, p->un.col, p->un.meta + GIGL_META_LEVEL0 + (s.L - 1 - l),
@@ -1687,7 +1668,7 @@ int dropout_lanes_log2(int width) {
 // forward over workspace p's batch graph, on ctx: every layer's operand a[l] and output h[l] are kept.  train: a training
 // step's forward — with s.drop_p > 0 every activated output is masked and scaled in place (dropout_rows_kernel: the mask of
 // this `encode` at the step *step_dev counts); an evaluation's forward (train == false) runs without
-int32_t sage_enc_forward(gigl_ctx* ctx, const SageTrainShared& s, const SageTrainEnc& e, const gigl_sage_plan* p, bool train,
+int32_t sage_enc_forward(gigl_ctx* ctx, const SageTrainShared& s, const SageTrainEnc& e, const BatchGraph* p, bool train,
                          int encode, const int32_t* step_dev) {
   const int L = s.L;
   int32_t rc = GIGL_OK;
@@ -1696,7 +1677,7 @@ int32_t sage_enc_forward(gigl_ctx* ctx, const SageTrainShared& s, const SageTrai
     const int32_t* n_rows = p->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
     const int d = s.dims[l];
     if (l == 0)
-      rc = gigl_gather_reduce_mixed(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col,
+      rc = gigl_gather_reduce_mixed(ctx, s.feat->rows, s.feat->dtype, d, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col,
                                     n_rows, e.rows_cap[0], GIGL_AGGR_MEAN, n_local, e.a[0]);
     else
       rc = gigl_gather_reduce(ctx, e.h[l - 1], GIGL_DTYPE_F32, d, nullptr, p->un.rowptr, p->un.rowend, p->un.col, n_rows,
@@ -1720,7 +1701,7 @@ int32_t sage_enc_forward(gigl_ctx* ctx, const SageTrainShared& s, const SageTrai
 // layers' input gradients by one projection over W_l^T (s.wt_l, laid out before) into `da` + the mean's backward over
 // workspace p's batch graph (tl: its transposed lists).  wctx != NULL: the weight gradients run on that ctx's stream
 // beside the chain, each behind ev_w (nothing in the chain waits for them; the caller joins wctx before Adam)
-int32_t sage_enc_backward(gigl_ctx* ctx, const SageTrainShared& s, const SageTrainEnc& e, const gigl_sage_plan* p,
+int32_t sage_enc_backward(gigl_ctx* ctx, const SageTrainShared& s, const SageTrainEnc& e, const BatchGraph* p,
                           int32_t* const* tl, float* da, gigl_ctx* wctx, hipEvent_t ev_w) {
   hipStream_t st = ctx->stream;
   const int L = s.L;
@@ -1775,11 +1756,11 @@ int32_t sage_enc_backward(gigl_ctx* ctx, const SageTrainShared& s, const SageTra
 }
 
 // Adam's pack over the partial sums of one encode (e1 == NULL) or of two, each over its workspace's batch
-AdamPack sage_adam_pack(const SageTrainShared& s, const SageTrainEnc* e0, const gigl_sage_plan* p0, const SageTrainEnc* e1,
-                        const gigl_sage_plan* p1) {
+AdamPack sage_adam_pack(const SageTrainShared& s, const SageTrainEnc* e0, const BatchGraph* p0, const SageTrainEnc* e1,
+                        const BatchGraph* p1) {
   AdamPack ap{};
   const SageTrainEnc* e[2] = {e0, e1};
-  const gigl_sage_plan* p[2] = {p0, p1};
+  const BatchGraph* p[2] = {p0, p1};
   ap.n_src = e1 ? 2 : 1;
   for (int l = 0; l < s.L; ++l)
     for (int is_bias = 0; is_bias < (s.bias[l] ? 2 : 1); ++is_bias) {
@@ -1826,7 +1807,7 @@ int32_t sage_moments_adopt(gigl_ctx* ctx, const SageTrainShared& dst, const Sage
 
 // ---- the workspace ring of a training plan, written once for the node-classification and the link-prediction plans.
 // A step is two parts (see above): the GRAPH part of a batch runs on the side stream of one of the ring's slots, into that
-// slot's tree / union workspaces; the LAYERS part that reads them runs on the caller's stream.  A batch ANNOUNCED ahead is
+// slot's batch graphs; the LAYERS part that reads them runs on the caller's stream.  A batch ANNOUNCED ahead is
 // issued into a later slot right away and recognised when its step comes by the ADDRESS of its roots (include/gigl_hip.h:
 // CONTRACT of an announced batch).  Both parts go through gigl_run_part: eager once, captured, replayed.
 extern "C++" {  // (a member template: this file's definitions sit in one extern "C" block)
@@ -1834,7 +1815,7 @@ struct PlanRing {
   enum Family { TRAIN = 0, EVAL = 1 };  // whose graph part: a training step's, gigl_nablp_train_plan_eval's
   struct Slot {
     gigl_ctx* side = nullptr;                      // private ctx with a stream of its own: the graph part's launches and arena
-    gigl_sage_plan* base[2] = {nullptr, nullptr};  // tree / union workspaces of the plan's root sets (their layer buffers stay unused)
+    BatchGraph base[2];                            // batch graphs of the plan's root sets, on the side ctx
     hipEvent_t ev_graph = nullptr;                 // end of the graph part last issued for the slot (its side stream)
     hipEvent_t ev_layers = nullptr;                // end of the layers part that last read it (the caller's stream)
     PartGraph graph[2], layers;                    // graph part per family (an evaluation's seed / mode need not be the steps')
@@ -1847,9 +1828,9 @@ struct PlanRing {
   hipEvent_t ev_now = nullptr;  // "the caller's stream, now": the roots a graph part copies were written before it
   int32_t seed[2] = {0, 0}, mode[2] = {-1, -1};  // what each family's captured graph parts were captured with
 
-  // per slot a side ctx, a base plan per root set (nb[i] roots) and its events
-  int32_t create(gigl_ctx* caller, int slots, int root_sets, const int32_t* nb, gigl_graph* graph, gigl_feat* feat,
-                 const int32_t* fanouts, int32_t hops, const int32_t* dims, float* const* w, float* const* bias, int32_t act_last) {
+  // per slot a side ctx, a batch graph per root set (nb[i] roots; number_every_node: batch_graph_init) and its events
+  int32_t create(gigl_ctx* caller, int slots, int root_sets, const int32_t* nb, gigl_graph* graph, const int32_t* fanouts,
+                 int32_t hops, bool number_every_node) {
     ctx = caller;
     n = slots;
     n_base = root_sets;
@@ -1860,8 +1841,7 @@ struct PlanRing {
       if (rc != GIGL_OK) break;
       s.side->wide = ctx->wide;
       for (int i = 0; i < n_base && rc == GIGL_OK; ++i) {
-        rc = plan_create(s.side, graph, feat, nb[i], fanouts, hops, dims, (const float* const*)w, (const float* const*)bias,
-                         act_last, false, &s.base[i]);
+        rc = batch_graph_init(&s.base[i], s.side, graph, nb[i], fanouts, hops, number_every_node);
         if (rc != GIGL_OK) gigl_fail(ctx, rc, "%s", gigl_last_error(s.side));
       }
       if (rc == GIGL_OK && (hipEventCreateWithFlags(&s.ev_graph, hipEventDisableTiming) != hipSuccess ||
@@ -1884,9 +1864,9 @@ struct PlanRing {
     GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(ss, ev_now, 0));
     for (int i = 0; i < n_base; ++i)
       if (count[i])
-        GIGL_HIP_CHECK(ctx, hipMemcpyAsync(s.base[i]->roots_buf, roots[i], count[i] * 4, hipMemcpyDeviceToDevice, ss));
+        GIGL_HIP_CHECK(ctx, hipMemcpyAsync(s.base[i].roots_buf, roots[i], count[i] * 4, hipMemcpyDeviceToDevice, ss));
       else
-        gigl_fill_u32(ss, s.base[i]->roots_buf, GIGL_INVALID, 1);
+        gigl_fill_u32(ss, s.base[i].roots_buf, GIGL_INVALID, 1);
     const int32_t rc = gigl_run_part(s.side, s.side, &s.graph[fam], capture_ok, "training step", body);
     if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(s.side));
     GIGL_HIP_CHECK(ctx, hipEventRecord(s.ev_graph, ss));
@@ -1915,7 +1895,7 @@ struct PlanRing {
   }
 
   // destruction in two steps, around the plan's own buffers (the caller's stream is synchronised already): the side
-  // streams drained, every captured graph gone before the ctx whose stream it was captured on, base plans before their ctx
+  // streams drained, every captured graph gone before the ctx whose stream it was captured on, batch graphs before their ctx
   void release() {
     for (Slot& s : slot)
       if (s.side) hipStreamSynchronize(s.side->stream);
@@ -1925,8 +1905,7 @@ struct PlanRing {
       s.graph[EVAL].drop();
       if (s.ev_graph) hipEventDestroy(s.ev_graph);
       if (s.ev_layers) hipEventDestroy(s.ev_layers);
-      for (gigl_sage_plan* b : s.base)
-        if (b) gigl_sage_plan_destroy(b);
+      for (BatchGraph& b : s.base) batch_graph_free(&b);
     }
     if (ev_now) hipEventDestroy(ev_now);
   }
@@ -1953,7 +1932,7 @@ struct gigl_sage_train_plan : SageTrainShared {
   // TRAIN_WS workspaces, one root set each (each on its own side ctx / stream: two graph parts — of the next batch and of
   // the one after — can be in flight)
   PlanRing ring;
-  SageTrainEnc enc;                       // the step's one encode (over the workspace ring.slot[k].base[0] the step reads)
+  SageTrainEnc enc;                       // the step's one encode (over the batch graph ring.slot[k].base[0] the step reads)
   int32_t* tlists[TRAIN_WS][GIGL_MAX_HOPS] = {{nullptr}};  // its transposed lists per workspace and layer >= 1, built by the graph part
   float* da = nullptr;                    // [max rows_cap[l >= 1]][2 max dims]: gradient of a layer's operand
   float** loss_slot = nullptr;            // where the caller wants the step's loss (set by train_stage_kernel)
@@ -1971,7 +1950,7 @@ namespace {
 
 // everything after the graph part, over workspace k, on lctx's stream (the caller's); train_stage_kernel ran ahead of it
 int32_t train_enqueue_layers(gigl_sage_train_plan* t, int k) {
-  gigl_sage_plan* p = t->ring.slot[k].base[0];
+  BatchGraph* p = &t->ring.slot[k].base[0];
   gigl_ctx* ctx = t->lctx;
   const int L = t->L;
   hipStream_t st = ctx->stream;
@@ -2038,8 +2017,10 @@ int32_t gigl_sage_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat*
   gigl_sage_train_plan* t = new (std::nothrow) gigl_sage_train_plan();
   if (!t) return gigl_fail(ctx, GIGL_E_OOM, "host OOM");
   t->ctx = ctx;
+  t->feat = feat;
   int32_t rc = gigl_ctx_create(ctx->device, &t->lctx);
-  if (rc == GIGL_OK) rc = t->ring.create(ctx, TRAIN_WS, 1, &b, graph, feat, fanouts, hops, dims, w, bias, act_last);
+  if (rc == GIGL_OK) rc = plan_check_layers(ctx, feat, hops, dims, w);
+  if (rc == GIGL_OK) rc = t->ring.create(ctx, TRAIN_WS, 1, &b, graph, fanouts, hops, false);
   if (rc != GIGL_OK) {
     gigl_sage_train_plan_destroy(t);
     return rc;
@@ -2061,7 +2042,7 @@ int32_t gigl_sage_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat*
   t->zero_base = z;
   t->zero_bytes = zero_floats * 4;
   if (z) sage_enc_carve(*t, t->enc, false, z);
-  for (int k = 0; k < TRAIN_WS; ++k) ok = sage_tlists_alloc(*t, t->enc, t->owned, t->ring.slot[k].base[0]->un.cap_edges, t->tlists[k]) && ok;
+  for (int k = 0; k < TRAIN_WS; ++k) ok = sage_tlists_alloc(*t, t->enc, t->owned, t->ring.slot[k].base[0].un.cap_edges, t->tlists[k]) && ok;
   t->da = (float*)alloc(da_floats * 4);
   t->labels_buf = (int64_t*)alloc((size_t)b * 8);
   t->n_valid_buf = (int32_t*)alloc(16);
@@ -2103,7 +2084,7 @@ int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* t, const uint32_t* root
   auto graph_part = [&](int kk, const uint32_t* r) {
     const size_t count = (size_t)t->enc.b;
     return ring.issue_graph_part(kk, PlanRing::TRAIN, &r, &count, train_part_captures(0), [&, kk]() {
-      return sage_enqueue_graph(*t, t->enc, ring.slot[kk].base[0], t->tlists[kk], sampling_seed, mode);
+      return sage_enqueue_graph(*t, t->enc, &ring.slot[kk].base[0], t->tlists[kk], sampling_seed, mode);
     });
   };
   // (a prefetched workspace belongs to the roots it was announced with: an epoch cut short, a reshuffle or an evaluation
@@ -2303,8 +2284,8 @@ struct gigl_nablp_train_plan : SageTrainShared {  // (the GAT kind uses its L, d
     float* wt1 = nullptr;
     float* wt0[4] = {nullptr};
     bool parts_pending = false;  // the gradient buffers do not hold the partial sums yet (gigl_gat_nablp_train_plan_grads adds them)
-    // edge features (gigl_gat_nablp_train_plan_set_edge_features): the resident table is read in place through the base
-    // plans' eid (written by the graph part).  The message weight's slot holds NULL (GATConv), its own buffer, or — shared —
+    // edge features (gigl_gat_nablp_train_plan_set_edge_features): the resident table is read in place through the batch
+    // graphs' eid (written by the graph part).  The message weight's slot holds NULL (GATConv), its own buffer, or — shared —
     // lin_edge.weight's parameter AND gradient slots with n == 0: one tensor, one Adam entry, one update
     struct Edge {
       gigl_feat* table = nullptr;
@@ -2678,7 +2659,7 @@ int32_t gat_lp_finish(gigl_nablp_train_plan* t);
 // sample + union of both root sets of workspace w, on its side stream (bwd_gather is a SAGE encoder's: no lists for the GAT kind)
 int32_t lp_enqueue_graph(gigl_nablp_train_plan* t, int w, int32_t sampling_seed, int32_t mode) {
   for (int k = 0; k < 2; ++k) {
-    const int32_t rc = sage_enqueue_graph(*t, t->enc[k], t->ring.slot[w].base[k], t->tlists[w][k], sampling_seed, mode);
+    const int32_t rc = sage_enqueue_graph(*t, t->enc[k], &t->ring.slot[w].base[k], t->tlists[w][k], sampling_seed, mode);
     if (rc != GIGL_OK) return rc;
   }
   return GIGL_OK;
@@ -2697,7 +2678,7 @@ int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w, bool train) {
   hipStream_t st = ctx->stream;
   const int L = t->L, d = t->dims[L], Q = t->b * t->P, Cn = t->cand_cols();
   int32_t rc = GIGL_OK;
-  for (int k = 0; k < 2; ++k) t->enc[k].base = t->ring.slot[w].base[k];
+  for (int k = 0; k < 2; ++k) t->enc[k].base = &t->ring.slot[w].base[k];
   gigl_fill_u32(st, t->zero_base, 0u, (int64_t)(t->zero_bytes / 4));
   if (t->kind == 1) {
     rc = gat_lp_begin(t);
@@ -2720,7 +2701,7 @@ int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w, bool train) {
     GIGL_HIP_CHECK(ctx, hipEventRecord(t->ev_join[0], t->actx->stream));
     GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, t->ev_join[0], 0));
   }
-  const gigl_sage_plan *pm = t->enc[0].base, *pr = t->enc[1].base;
+  const BatchGraph *pm = t->enc[0].base, *pr = t->enc[1].base;
   hipLaunchKernelGGL(lp_pack_kernel, dim3((unsigned)((Cn + 3) / 4)), dim3(256), 0, st, (const float*)t->enc[0].emb,
                      (const float*)t->enc[1].emb, (const uint32_t*)pm->roots_buf, (const uint32_t*)pr->roots_buf,
                      (const int32_t*)t->pos_cnt, (const float*)t->enc[0].inv, (const float*)t->enc[1].inv, t->b, t->P, t->H,
@@ -2745,7 +2726,7 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
   const int L = t->L, d = t->dims[L], Q = t->b * t->P, Cn = t->cand_cols();
   int32_t rc = lp_enqueue_forward(t, w, true);
   if (rc != GIGL_OK) return rc;
-  const gigl_sage_plan *pm = t->enc[0].base, *pr = t->enc[1].base;
+  const BatchGraph *pm = t->enc[0].base, *pr = t->enc[1].base;
   if (t->task_kind != GIGL_LP_TASK_RETRIEVAL) {
     const LpTaskHead h = lp_task_head(t);
     gigl_lp_task_sum_enqueue(st, h, t->row_lse, t->row_loss, t->loss, t->consts + 2, (const int32_t*)pm->un.meta,
@@ -2803,16 +2784,18 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
 
 // ---- what the two link-prediction plans' creation shares (t->ctx, b, P, n_rn are set)
 
-// the layers' ctx and the ring: per workspace the two root sets' tree / union workspaces
+// the layers' ctx and the ring: per workspace the two root sets' batch graphs (number_every_node: batch_graph_init)
 int32_t lp_create_workspaces(gigl_nablp_train_plan* t, gigl_graph* graph, gigl_feat* feat, const int32_t* fanouts, int32_t hops,
-                             const int32_t* dims, float* const* w, float* const* bias, int32_t act_last) {
+                             const int32_t* dims, float* const* w, bool number_every_node) {
   gigl_ctx* ctx = t->ctx;
-  int32_t rc = gigl_ctx_create(ctx->device, &t->lctx);
+  t->feat = feat;
+  int32_t rc = plan_check_layers(ctx, feat, hops, dims, w);
+  if (rc == GIGL_OK) rc = gigl_ctx_create(ctx->device, &t->lctx);
   const int32_t nb[2] = {t->b * (1 + t->P + t->H), t->n_rn > 0 ? t->n_rn : 1};
   for (int k = 0; k < 2; ++k) t->enc[k].b = nb[k];
-  if (rc == GIGL_OK) rc = t->ring.create(ctx, gigl_nablp_train_plan::WS, 2, nb, graph, feat, fanouts, hops, dims, w, bias, act_last);
+  if (rc == GIGL_OK) rc = t->ring.create(ctx, gigl_nablp_train_plan::WS, 2, nb, graph, fanouts, hops, number_every_node);
   if (rc == GIGL_OK)
-    for (int k = 0; k < 2; ++k) t->enc[k].base = t->ring.slot[0].base[k];
+    for (int k = 0; k < 2; ++k) t->enc[k].base = &t->ring.slot[0].base[k];
   return rc;
 }
 
@@ -2941,7 +2924,7 @@ int32_t gigl_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat
   gigl_nablp_train_plan* t = lp_plan_new(ctx, 0, hops, b_anchors, num_positives, n_random_negatives, act_last, l2_normalize,
                                          temperature, remove_accidental_hits, lr, beta1, beta2, eps, weight_decay);
   if (!t) return gigl_fail(ctx, GIGL_E_OOM, "host OOM");
-  const int32_t rc = lp_create_workspaces(t, graph, feat, fanouts, hops, dims, w, bias, act_last);
+  const int32_t rc = lp_create_workspaces(t, graph, feat, fanouts, hops, dims, w, false);
   if (rc != GIGL_OK) {
     gigl_nablp_train_plan_destroy(t);
     return rc;
@@ -2957,7 +2940,7 @@ int32_t gigl_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat
   for (int k = 0; k < 2 && z; ++k) z = sage_enc_carve(*t, t->enc[k], true, z);
   for (int wi = 0; wi < gigl_nablp_train_plan::WS; ++wi)
     for (int k = 0; k < 2; ++k)
-      ok = sage_tlists_alloc(*t, t->enc[k], t->owned, t->ring.slot[wi].base[k]->un.cap_edges, t->tlists[wi][k]) && ok;
+      ok = sage_tlists_alloc(*t, t->enc[k], t->owned, t->ring.slot[wi].base[k].un.cap_edges, t->tlists[wi][k]) && ok;
   t->da = (float*)alloc(da_floats * 4);
   ok = ok && t->zero_base && t->da && lp_head_alloc(t, (size_t)dims[hops]);
   // (GIGL_LP_FORK=0 off: 1.18 -> 1.07 ms per step, bit-identical results.  The forked step's layers part is
@@ -3059,9 +3042,9 @@ int32_t gigl_nablp_train_plan_eval(gigl_nablp_train_plan* t, const uint32_t* mai
   GIGL_HIP_CHECK(ctx, hipMemcpyAsync(t->pos_cnt, pos_cnt, t->cnt_words() * 4, hipMemcpyDeviceToDevice, st));
   GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, wk.ev_graph, 0));
   // (eager: no captured layers graph is made or invalidated — and none with a second branch, see gigl_nablp_train_plan_create)
-  gigl_sage_plan* const held[2] = {t->enc[0].base, t->enc[1].base};
+  BatchGraph* const held[2] = {t->enc[0].base, t->enc[1].base};
   rc = lp_enqueue_forward(t, w, false);
-  const gigl_sage_plan *pm = wk.base[0], *pr = wk.base[1];
+  const BatchGraph *pm = &wk.base[0], *pr = &wk.base[1];
   for (int k = 0; k < 2; ++k) t->enc[k].base = held[k];
   if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
   const int Q = t->b * t->P;
@@ -3415,7 +3398,7 @@ __global__ __launch_bounds__(256) void gat_edge_fold_backward_kernel(const float
 
 int64_t gat_rows1(const gigl_nablp_train_plan* t, int which) { return t->enc[which].rows_cap[0]; }
 
-// the first layer's edge terms over encode `which`'s batch graph (the base plan's eid: its graph part wrote them)
+// the first layer's edge terms over encode `which`'s batch graph (its eid: the graph part wrote them)
 gigl_gat_edge_terms gat_edge_terms0(const gigl_nablp_train_plan* t, int which) {
   const auto& ge = t->gat.e;
   gigl_gat_edge_terms et{};
@@ -3456,7 +3439,7 @@ int32_t gat_lp_begin(gigl_nablp_train_plan* t) {
 
 int32_t gat_lp_forward(gigl_nablp_train_plan* t, int which) {
   SageTrainEnc& e = t->enc[which];
-  gigl_sage_plan* p = e.base;
+  const BatchGraph* p = e.base;
   auto& g = t->gat;
   GatScratch& s = g.sc[which == 1 && t->fork];
   gigl_ctx* ctx = s.ctx;
@@ -3469,7 +3452,7 @@ int32_t gat_lp_forward(gigl_nablp_train_plan* t, int which) {
   const int32_t* n1 = p->un.meta + GIGL_META_LEVEL0 + 1;
   const bool edge = g.e.table != nullptr, msg0 = edge && wm0;
   const gigl_gat_edge_terms et = edge ? gat_edge_terms0(t, which) : gigl_gat_edge_terms{};
-  int32_t rc = gigl_gat_input_aggregate_edge(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
+  int32_t rc = gigl_gat_input_aggregate_edge(ctx, t->feat->rows, t->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
                                              p->un.rowend, p->un.col, n1, rows1, g.z[which], edge ? &et : nullptr);
   if (rc != GIGL_OK) return rc;
   // h0[:, hC:(h+1)C] = relu(z_h W_h^T (+ W_msg,h ze_h) + b_h): one launch for all heads (the messages' De-wide term, the
@@ -3503,7 +3486,7 @@ int32_t gat_lp_forward(gigl_nablp_train_plan* t, int which) {
 
 int32_t gat_lp_backward(gigl_nablp_train_plan* t, int which) {
   SageTrainEnc& e = t->enc[which];
-  gigl_sage_plan* p = e.base;
+  const BatchGraph* p = e.base;
   auto& g = t->gat;
   const int alt = which == 1 && t->fork;
   GatScratch& s = g.sc[alt];
@@ -3577,10 +3560,10 @@ int32_t gat_lp_backward(gigl_nablp_train_plan* t, int which) {
       rc = gigl_gat_edge_msg_backward(ctx, s.dh0s, rows1 * C0, wm0, g.e.ze[which], n1, rows1, H, C0, De, s.dze, gm0);
       if (rc != GIGL_OK) return rc;
     }
-    rc = gigl_gat_input_aggregate_backward_edge(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
+    rc = gigl_gat_input_aggregate_backward_edge(ctx, t->feat->rows, t->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
                                                 p->un.rowend, p->un.col, n1, rows1, s.dz, s.du, &et, msg0 ? s.dze : nullptr, s.dv);
   } else {
-    rc = gigl_gat_input_aggregate_backward(ctx, p->feat->rows, p->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
+    rc = gigl_gat_input_aggregate_backward(ctx, t->feat->rows, t->feat->dtype, d, p->un.nodes, g.u, H, g.slope, p->un.rowptr,
                                            p->un.rowend, p->un.col, n1, rows1, s.dz, nullptr, s.du);
   }
   GIGL_HIP_CHECK(ctx, hipGetLastError());
@@ -3717,15 +3700,12 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
     g.at(GAT_ATT_DST, l).set(att_dst[l], dims[l + 1]);
     g.at(GAT_BIAS, l).set(bias ? bias[l] : nullptr, dims[l + 1]);
   }
-  // (the base plans are tree + union workspaces here: their own layer buffers stay unused)
-  const int32_t rc = lp_create_workspaces(t, graph, feat, fanouts, hops, dims, w, bias, 0);
+  // every node of the batch graphs is numbered: gigl_gat_input_aggregate reads its sources through un.nodes
+  const int32_t rc = lp_create_workspaces(t, graph, feat, fanouts, hops, dims, w, true);
   if (rc != GIGL_OK) {
     gigl_nablp_train_plan_destroy(t);
     return rc;
   }
-  // every node of the batch graph is numbered: gigl_gat_input_aggregate reads its sources through un.nodes
-  for (int wi = 0; wi < gigl_nablp_train_plan::WS; ++wi)
-    for (gigl_sage_plan* bp : t->ring.slot[wi].base) bp->leaf_global = false;
   auto alloc = [&](size_t bytes) { return plan_alloc(t->owned, bytes); };
   bool ok = true;
   // (default on, GIGL_LP_FORK=0 off, as the GraphSAGE plan: the forked step's layers part launched eagerly)
@@ -3761,9 +3741,9 @@ int32_t gigl_gat_nablp_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_
   if (t->zero_base) lay_out((float*)t->zero_base);
   g.u = (float*)alloc((size_t)2 * H * d * 4);
   ok = ok && t->zero_base && g.u && gat_moments_alloc(t->owned, g.tensor, 0, GAT_CORE) &&
-       gat_scratch_alloc(t, g.sc[0], t->lctx, rows1_max, t->ring.slot[0].base[0]->un.cap_edges, b_max);
+       gat_scratch_alloc(t, g.sc[0], t->lctx, rows1_max, t->ring.slot[0].base[0].un.cap_edges, b_max);
   if (want_fork && ok)  // the second stream's ctx and events, its own scratch (the random negatives' rows and edges)
-    ok = lp_fork_setup(t) && gat_scratch_alloc(t, g.sc[1], t->actx, t->enc[1].rows_cap[0], t->ring.slot[0].base[1]->un.cap_edges, t->enc[1].b);
+    ok = lp_fork_setup(t) && gat_scratch_alloc(t, g.sc[1], t->actx, t->enc[1].rows_cap[0], t->ring.slot[0].base[1].un.cap_edges, t->enc[1].b);
   if (ok) {
     g.wt1 = (float*)alloc((size_t)C1 * H * C0 * 4);
     ok = g.wt1 != nullptr;
@@ -3827,7 +3807,7 @@ int32_t gigl_gat_nablp_train_plan_set_edge_features(gigl_nablp_train_plan* t, gi
   GIGL_REQUIRE(ctx, t->kind == 1, "edge features apply to the GAT link-prediction plan (gigl_gat_nablp_train_plan_create)");
   GIGL_REQUIRE(ctx, !t->stepped && !t->gat.e.table, "edge features are set once, after create and before the first step");
   GIGL_REQUIRE(ctx, edge_table && w_edge && att_edge, "null argument");
-  const gigl_graph* graph = t->ring.slot[0].base[0]->graph;
+  const gigl_graph* graph = t->ring.slot[0].base[0].graph;
   const int32_t De = edge_table->d;
   if (edge_table->dtype != GIGL_DTYPE_F32 || De < 1 || De > 64)  // (a lane per component of an edge row)
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "GAT link-prediction plan: the edge table must be fp32, 1..64 wide (dtype %d, %d)",
@@ -3876,22 +3856,13 @@ int32_t gigl_gat_nablp_train_plan_set_edge_features(gigl_nablp_train_plan* t, gi
     }
     for (int k = 0; k < (fork ? 2 : 1); ++k) ok = ok && gat_scratch_alloc_edge(t, g.sc[k]);
   }
+  if (!ok) return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the GAT link-prediction plan's edge workspace failed");
   // every workspace's batch graphs get their edge ids from their own graph part (plan_edge_ids_kernel; all rows are numbered)
   for (int wi = 0; wi < gigl_nablp_train_plan::WS; ++wi)
-    for (gigl_sage_plan* bp : t->ring.slot[wi].base) {
-      if (!ok) break;
-      const int64_t positions = bp->un.cap_edges + (bp->alias_rows ? bp->last_slots : 0);
-      void* q = nullptr;
-      if (hipMalloc(&q, (size_t)(positions > 0 ? positions : 4) * 4) != hipSuccess) {
-        ok = false;
-        break;
-      }
-      bp->owned.push_back(q);
-      if (hipMemset(q, 0xFF, (size_t)(positions > 0 ? positions : 4) * 4) != hipSuccess) ok = false;
-      bp->eid = (int32_t*)q;
-      bp->efeat = edge_table;
+    for (BatchGraph& bg : t->ring.slot[wi].base) {
+      const int32_t rc = batch_graph_attach_edge_table(&bg, edge_table);
+      if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(bg.ctx));
     }
-  if (!ok) return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the GAT link-prediction plan's edge workspace failed");
   ge.table = edge_table;
   return GIGL_OK;
 }
