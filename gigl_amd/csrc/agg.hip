@@ -3772,11 +3772,6 @@ __global__ __launch_bounds__(1024) void gat_gather_heavy_kernel(
   }
 }
 
-__global__ void gat_transpose_kernel(const float* __restrict__ w, int rows, int cols, float* __restrict__ wt) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < rows * cols) wt[(int64_t)(t % cols) * rows + t / cols] = w[t];
-}
-
 // launches the fast pair when the shape allows it (concatenated heads, or a single head); false = use the generic path
 static bool launch_gat_fast(gigl_ctx* ctx, const float* h, const float* att_src, const float* att_dst, int heads, int C,
                             float slope, int concat, const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
@@ -3801,8 +3796,7 @@ static bool launch_gat_fast(gigl_ctx* ctx, const float* h, const float* att_src,
   if (w_msg) {
     wt = (float*)gigl_arena_alloc(ctx, (int64_t)heads * C * De * 4);
     if (!wt) return false;
-    hipLaunchKernelGGL(gat_transpose_kernel, dim3((unsigned)((heads * C * De + 255) / 256)), dim3(256), 0, ctx->stream,
-                       w_msg, heads * C, De, wt);
+    gigl_transpose_f32(ctx->stream, w_msg, heads * C, De, wt);
   }
   if (((uintptr_t)h | (uintptr_t)out | (uintptr_t)att_src | (uintptr_t)att_dst | (uintptr_t)bias) & 15) return false;
   int64_t ablocks = (nodes_cap + 3) / 4, gblocks = (rows_cap + 3) / 4;
@@ -3941,6 +3935,11 @@ __global__ __launch_bounds__(256) void half_rows_to_f32_kernel(const __half* __r
 }
 
 }  // namespace
+
+void gigl_gat_fold(hipStream_t st, const float* w, const float* att_src, const float* att_dst, int H, int C, int d, float* u) {
+  hipLaunchKernelGGL(gat_fold_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)(2 * H)), dim3(256), 0, st, w, att_src, att_dst,
+                     H, C, d, u);
+}
 
 int32_t gigl_gather_project_mixed(gigl_ctx* ctx, const float* src_l, const float* src_r, int32_t ld, int32_t d,
                                   const uint32_t* gather_ids, const int32_t* rowptr, const int32_t* rowend,
@@ -4936,8 +4935,7 @@ int32_t gigl_gat_input_layer(gigl_ctx* ctx, const void* src, int32_t src_dtype, 
   float* alpha_self = alpha_e + cap_edges * H;
   {
     gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
-    hipLaunchKernelGGL(gat_fold_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)(2 * H)), dim3(256), 0, st, w, att_src,
-                       att_dst, H, C, d, u);
+    gigl_gat_fold(st, w, att_src, att_dst, H, C, d, u);
     int64_t sblocks = (cap_nodes + 63) / 64, wblocks = (rows_cap + 3) / 4, gblocks = (rows_cap * chunks + 3) / 4;
     if (sblocks > 256 * 8) sblocks = 256 * 8;
     if (wblocks > 256 * 16) wblocks = 256 * 16;
@@ -5178,8 +5176,7 @@ int32_t gigl_gat_input_layer_fused_hs(gigl_ctx* ctx, const void* src, int32_t sr
   float* u = z + H * head_stride;
   {
     gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
-    hipLaunchKernelGGL(gat_fold_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)(2 * H)), dim3(256), 0, st, w, att_src,
-                       att_dst, H, C, d, u);
+    gigl_gat_fold(st, w, att_src, att_dst, H, C, d, u);
     launch_gat_input_online(st, src, src_dtype, d, gather_ids, n_local_dev, u, H, negative_slope, rowptr, rowend, col,
                             n_rows_dev, rows_cap, nkc, head_stride, z, edge);
     GIGL_HIP_CHECK(ctx, hipGetLastError());

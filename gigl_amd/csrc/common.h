@@ -128,22 +128,24 @@ int32_t gigl_lp_rank_metrics_enqueue(gigl_ctx* ctx, hipStream_t st, const float*
                                      const int32_t* pos_cnt, int32_t n_neg, int32_t neg_col0, const int32_t* neg_valid,
                                      const int32_t* ks, int32_t n_ks, const int32_t* meta_a, const int32_t* meta_b,
                                      double* part, double* acc);
-// the Margin / Softmax task over a score matrix in the link-prediction plan's layout (loss.hip; the contract is gigl_lp_task_loss's
-// in gigl_hip.h): what the three launches share.  pos_cnt may be NULL (valid alone decides)
+// a task (GIGL_LP_TASK_*) over a score matrix in the link-prediction plan's layout (loss.hip; Margin's and Softmax's contract is
+// gigl_lp_task_loss's in gigl_hip.h, Retrieval's gigl_retrieval_loss's with valid as the mask of rows and columns): what the
+// three launches share.  pos_cnt may be NULL (valid alone decides)
 struct LpTaskHead {
   int32_t kind;
-  float param, weight;  // margin | temperature; the task's weight
+  float param, weight;  // Margin's margin | Softmax's and Retrieval's temperature (Retrieval: <= 0 for none); the task's weight
   const float* scores;
   int64_t ld;
   int32_t b, P, H, n_rn;
   const int32_t* pos_cnt;
   const int32_t* valid;
+  const int64_t *qid, *cid;  // Retrieval: the query rows' [b P] and the candidate columns' ids; cid NULL: no hit removal
 };
 // GIGL_E_INVALID_ARG for an unknown kind, a Softmax temperature <= 0, a non-finite margin, a weight not finite and > 0
 int32_t gigl_lp_task_check(gigl_ctx* ctx, int32_t kind, float param, float weight);
-// the row partials (one workgroup per query row) -> row_a, row_b [b P]
+// the row partials (one workgroup per query row) -> row_a, row_b [b P] (Retrieval: row_lse, row_loss)
 void gigl_lp_task_rows_enqueue(hipStream_t st, const LpTaskHead& h, float* row_a, float* row_b);
-// {loss, valid rows, normaliser} -> out3 and *step += 1 (step, meta_a / meta_b may be NULL; a batch whose meta reports an overflow:
+// {loss, valid rows, normaliser (not Retrieval)} -> out3 and *step += 1 (step, meta_a / meta_b may be NULL; a batch whose meta reports an overflow:
 // NaN loss, step unmoved); with eval_acc instead: acc[LOSS_SUM] += loss, acc[BATCHES] += 1, or *overflow_acc += 1
 void gigl_lp_task_sum_enqueue(hipStream_t st, const LpTaskHead& h, const float* row_a, const float* row_b, float* out3,
                               int32_t* step, const int32_t* meta_a, const int32_t* meta_b, double* eval_acc,
@@ -159,6 +161,9 @@ int32_t gigl_linear_weight_grad_sum(gigl_ctx* ctx, const float* part, const floa
                                     int32_t rows_per_chunk, float* dw, float* db);
 int32_t gigl_linear_weight_grad_parts(gigl_ctx* ctx, const float* dy, const float* a, const float* relu_y, const int32_t* m_dev,
                                       int64_t m_cap, int32_t n, int32_t k, float* part, float* partb);
+// the first GAT layer's folded attention vectors (agg.hip): u[h][k] = sum_c att_src[hC + c] W[hC + c][k], u[H + h][k] the same
+// with att_dst — u [2H][d], W [H C][d]
+void gigl_gat_fold(hipStream_t st, const float* w, const float* att_src, const float* att_dst, int H, int C, int d, float* u);
 // union build with the plan-internal leaf-global option (union.hip)
 int32_t gigl_union_build_impl(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* tree, int32_t group_roots,
                               gigl_union* out, int32_t leaf_global);
@@ -386,6 +391,21 @@ static inline void gigl_fill_u32(hipStream_t st, void* p, uint32_t value, int64_
   int64_t blocks = (n_words + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(gigl_fill_u32_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (uint32_t*)p, value, n_words);
+}
+
+// wt [cols][rows] = the transpose of the row-major w [rows][cols]
+static __global__ __launch_bounds__(256) void gigl_transpose_f32_kernel(const float* __restrict__ w, int rows, int cols,
+                                                                        float* __restrict__ wt) {
+  const int64_t n = (int64_t)rows * cols;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / cols), c = (int)(i - (int64_t)r * cols);
+    wt[(int64_t)c * rows + r] = w[i];
+  }
+}
+static inline void gigl_transpose_f32(hipStream_t st, const float* w, int rows, int cols, float* wt) {
+  const int64_t n = (int64_t)rows * cols;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(gigl_transpose_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, rows, cols, wt);
 }
 
 // out[i] = h[root_local[i]] for the b roots of a batch set (rows of d floats) — the last stage of the one-call plans.

@@ -13,9 +13,11 @@
 // Row results go to row_lse / row_loss; a second single-workgroup launch adds the rows in a fixed order (the sum is
 // reproducible run to run).  Backward: dscores_ij = g * (softmax_ij - [i == j]) / temperature, 0 for excluded columns.
 // HBM-bound: 4*Q*C bytes read forward, read + written backward.
+// The training plan's head runs the same kernels over its validity words (LossArgs::valid) through the LpTaskHead interface.
 // Further down: the Margin and Softmax tasks over the training plan's score matrix (gigl_lp_task_loss), the count-min sketch of
 // the sampling correction, the evaluation's rank metrics.
 #include "common.h"
+#include "dispatch.h"
 
 #include <cfloat>
 #include <cmath>
@@ -31,8 +33,9 @@ struct LossArgs {
   const float* cand_prob;
   const int64_t* query_ids;
   const int64_t* cand_ids;
+  const int32_t* valid;  // [c] or NULL (every row and column takes part): the plan's head — column j, and row i < q, take part
   int64_t g_scores;  // grid.y = independent batches: batch g's score block starts g_scores floats on, its ids / prob
-                     // / per-row outputs follow the previous batch's (q or c entries each)
+                     // / per-row outputs follow the previous batch's (q or c entries each; the batched entry has no valid)
 };
 
 __device__ __forceinline__ float logit(const LossArgs& a, float raw, int j) {
@@ -42,9 +45,10 @@ __device__ __forceinline__ float logit(const LossArgs& a, float raw, int j) {
 }
 
 __device__ __forceinline__ bool excluded(const LossArgs& a, int i, int j, int64_t qid_i, int64_t cid_i) {
+  if (a.valid && !a.valid[j]) return true;
   if (j == i) return false;
-  if (a.query_ids && j < a.q && a.query_ids[j] == qid_i) return true;
-  return a.cand_ids && a.cand_ids[j] == cid_i;
+  if (a.query_ids && j < a.q && a.query_ids[j] == qid_i) return true;  // another positive of the same query (loss.py:279-305)
+  return a.cand_ids && a.cand_ids[j] == cid_i;  // the positive itself among the other candidates (:307-331)
 }
 
 // merge two (max, sum of exp relative to max) states
@@ -71,6 +75,10 @@ __global__ __launch_bounds__(256) void retrieval_rows_kernel(LossArgs a0, float*
   }
   const int i = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (a.valid && !a.valid[i]) {
+    if (tid == 0) row_lse[i] = row_loss[i] = 0.f;
+    return;
+  }
   const float* row = a.scores + (int64_t)i * a.ld;
   const int64_t qid_i = a.query_ids ? a.query_ids[i] : 0;
   const int64_t cid_i = a.cand_ids ? a.cand_ids[i] : 0;
@@ -123,20 +131,35 @@ __global__ __launch_bounds__(1024) void sum_rows_kernel(const float* __restrict_
   }
 }
 
+// The scale of the stand-alone entries is g / temperature (g = *grad_loss or 1).  The plan (out3 != NULL: its loss words, out3[1]
+// the valid rows) takes the mean's gradient times the task's weight, 1 / temperature / rows x weight — two roundings that
+// differ, both kept.
 __global__ __launch_bounds__(256) void retrieval_backward_kernel(LossArgs a, const float* __restrict__ row_lse,
                                                                  const float* __restrict__ grad_loss,
-                                                                 float* __restrict__ dscores) {
+                                                                 const float* __restrict__ out3, float weight,
+                                                                 float* __restrict__ dscores, int64_t ldd) {
   const int i = blockIdx.x;
+  float* out = dscores + (int64_t)i * ldd;
+  if (a.valid && !a.valid[i]) {
+    for (int j = threadIdx.x; j < a.c; j += 256) out[j] = 0.f;
+    return;
+  }
   const float* row = a.scores + (int64_t)i * a.ld;
   const int64_t qid_i = a.query_ids ? a.query_ids[i] : 0;
   const int64_t cid_i = a.cand_ids ? a.cand_ids[i] : 0;
   const float lse = row_lse[i];
-  const float g = grad_loss ? *grad_loss : 1.f;
-  const float scale = a.temperature > 0.f ? g / a.temperature : g;
+  float scale;
+  if (out3) {
+    scale = (a.temperature > 0.f ? 1.f / a.temperature : 1.f) / (out3[1] > 0.f ? out3[1] : 1.f) * weight;
+  } else {
+    const float g = grad_loss ? *grad_loss : 1.f;
+    scale = a.temperature > 0.f ? g / a.temperature : g;
+  }
   for (int j = threadIdx.x; j < a.c; j += 256) {
+    const float raw = row[j];  // (before the mask's dependent loads: one round trip less per column)
     float d = 0.f;
-    if (!excluded(a, i, j, qid_i, cid_i)) d = (expf(logit(a, row[j], j) - lse) - (j == i ? 1.f : 0.f)) * scale;
-    dscores[(int64_t)i * a.c + j] = d;
+    if (!excluded(a, i, j, qid_i, cid_i)) d = (expf(logit(a, raw, j) - lse) - (j == i ? 1.f : 0.f)) * scale;
+    out[j] = d;
   }
 }
 
@@ -393,9 +416,9 @@ __global__ __launch_bounds__(256) void lp_task_rows_kernel(LpTaskHead a, float* 
 }
 
 // {weighted loss, valid rows, normaliser} in a fixed order, fp64 and integers (one workgroup).  Margin: sum of the hinge sums /
-// N, N = the valid rows' negative counts (64-bit); Softmax: sum of the row losses / valid rows.  Training (eval_acc == NULL):
-// -> out3, a failed batch (either meta word) gives a NaN loss, *step (may be NULL) moves when it did not fail.  Evaluation: as
-// the plan's retrieval sum does it, acc[LOSS_SUM] += the fp32 loss word, acc[BATCHES] += 1, or *overflow_acc += 1.
+// N, N = the valid rows' negative counts (64-bit); Softmax and Retrieval: sum of the row losses / valid rows (Retrieval writes no
+// normaliser word).  Training (eval_acc == NULL): -> out3, a failed batch (either meta word) gives a NaN loss, *step (may be
+// NULL) moves when it did not fail.  Evaluation: acc[LOSS_SUM] += the fp32 loss word, acc[BATCHES] += 1, or *overflow_acc += 1.
 template <int KIND>
 __global__ __launch_bounds__(1024) void lp_task_sum_kernel(LpTaskHead a, const float* __restrict__ row_a,
                                                            const float* __restrict__ row_b, float* __restrict__ out3,
@@ -428,6 +451,11 @@ __global__ __launch_bounds__(1024) void lp_task_sum_kernel(LpTaskHead a, const f
   long long pairs = 0;
   int n = 0;
   for (int q = tid; q < Q; q += 1024) {
+    if (KIND == GIGL_LP_TASK_RETRIEVAL) {  // row_b = row_loss, 0 on an invalid row
+      acc += (double)row_b[q];
+      n += a.valid[q] ? 1 : 0;
+      continue;
+    }
     const int i = q / a.P;
     if (!task_row_valid(a, q, i)) continue;
     ++n;
@@ -462,7 +490,9 @@ __global__ __launch_bounds__(1024) void lp_task_sum_kernel(LpTaskHead a, const f
       nn += s_n[k];
     }
     const double norm = KIND == GIGL_LP_TASK_MARGIN ? (double)pp : (double)nn;
-    const float loss = (float)((double)a.weight * t / (norm > 0.0 ? norm : 1.0));
+    // (Retrieval keeps its own rounding: the mean as a float, then the weight — x 1.0f gives the same bits)
+    const float loss = KIND == GIGL_LP_TASK_RETRIEVAL ? (float)(t / (double)(nn > 0 ? nn : 1)) * a.weight
+                                                      : (float)((double)a.weight * t / (norm > 0.0 ? norm : 1.0));
     const bool failed = meta_a && (meta_a[GIGL_META_OVERFLOW] != 0 || meta_b[GIGL_META_OVERFLOW] != 0);
     if (eval_acc) {
       if (failed) {
@@ -475,7 +505,7 @@ __global__ __launch_bounds__(1024) void lp_task_sum_kernel(LpTaskHead a, const f
     }
     out3[0] = failed ? __builtin_nanf("") : loss;
     out3[1] = (float)nn;
-    out3[2] = (float)norm;
+    if (KIND != GIGL_LP_TASK_RETRIEVAL) out3[2] = (float)norm;
     if (step && !failed) *step += 1;
   }
 }
@@ -523,32 +553,58 @@ int32_t gigl_lp_task_check(gigl_ctx* ctx, int32_t kind, float param, float weigh
   return GIGL_OK;
 }
 
+namespace {
+// the retrieval loss over a head's layout: q = b P query rows, every candidate column, the temperature in param
+LossArgs retrieval_args(const LpTaskHead& h) {
+  LossArgs a{};
+  a.scores = h.scores;
+  a.ld = h.ld;
+  a.q = h.b * h.P;
+  a.c = h.b * (h.P + h.H) + h.n_rn;
+  a.temperature = h.param;
+  a.query_ids = h.qid;
+  a.cand_ids = h.cid;
+  a.valid = h.valid;
+  return a;
+}
+
+template <typename F>
+void dispatch_task(int32_t kind, F&& f) {
+  dispatch_int<GIGL_LP_TASK_RETRIEVAL, GIGL_LP_TASK_MARGIN, GIGL_LP_TASK_SOFTMAX>(kind, f);
+}
+}  // namespace
+
 void gigl_lp_task_rows_enqueue(hipStream_t st, const LpTaskHead& h, float* row_a, float* row_b) {
   const dim3 grid((unsigned)(h.b * h.P));
-  if (h.kind == GIGL_LP_TASK_MARGIN)
-    hipLaunchKernelGGL(lp_task_rows_kernel<GIGL_LP_TASK_MARGIN>, grid, dim3(256), 0, st, h, row_a, row_b);
-  else
-    hipLaunchKernelGGL(lp_task_rows_kernel<GIGL_LP_TASK_SOFTMAX>, grid, dim3(256), 0, st, h, row_a, row_b);
+  dispatch_task(h.kind, [&](auto k) {
+    constexpr int KIND = decltype(k)::value;
+    if constexpr (KIND == GIGL_LP_TASK_RETRIEVAL)
+      hipLaunchKernelGGL(retrieval_rows_kernel, grid, dim3(256), 0, st, retrieval_args(h), (float*)nullptr, row_a, row_b);
+    else
+      hipLaunchKernelGGL(lp_task_rows_kernel<KIND>, grid, dim3(256), 0, st, h, row_a, row_b);
+  });
 }
 
 void gigl_lp_task_sum_enqueue(hipStream_t st, const LpTaskHead& h, const float* row_a, const float* row_b, float* out3,
                               int32_t* step, const int32_t* meta_a, const int32_t* meta_b, double* eval_acc,
                               int32_t* overflow_acc) {
-  if (h.kind == GIGL_LP_TASK_MARGIN)
-    hipLaunchKernelGGL(lp_task_sum_kernel<GIGL_LP_TASK_MARGIN>, dim3(1), dim3(1024), 0, st, h, row_a, row_b, out3, step, meta_a,
+  dispatch_task(h.kind, [&](auto k) {
+    hipLaunchKernelGGL(lp_task_sum_kernel<decltype(k)::value>, dim3(1), dim3(1024), 0, st, h, row_a, row_b, out3, step, meta_a,
                        meta_b, eval_acc, overflow_acc);
-  else
-    hipLaunchKernelGGL(lp_task_sum_kernel<GIGL_LP_TASK_SOFTMAX>, dim3(1), dim3(1024), 0, st, h, row_a, row_b, out3, step, meta_a,
-                       meta_b, eval_acc, overflow_acc);
+  });
 }
 
 void gigl_lp_task_backward_enqueue(hipStream_t st, const LpTaskHead& h, const float* row_a, const float* row_b,
                                    const float* out3, float* dscores, int64_t ldd) {
   const dim3 grid((unsigned)(h.b * h.P));
-  if (h.kind == GIGL_LP_TASK_MARGIN)
-    hipLaunchKernelGGL(lp_task_backward_kernel<GIGL_LP_TASK_MARGIN>, grid, dim3(256), 0, st, h, row_a, row_b, out3, dscores, ldd);
-  else
-    hipLaunchKernelGGL(lp_task_backward_kernel<GIGL_LP_TASK_SOFTMAX>, grid, dim3(256), 0, st, h, row_a, row_b, out3, dscores, ldd);
+  dispatch_task(h.kind, [&](auto k) {
+    constexpr int KIND = decltype(k)::value;
+    if constexpr (KIND == GIGL_LP_TASK_RETRIEVAL)
+      hipLaunchKernelGGL(retrieval_backward_kernel, grid, dim3(256), 0, st, retrieval_args(h), row_a, (const float*)nullptr,
+                         out3, h.weight, dscores, ldd);
+    else
+      hipLaunchKernelGGL(lp_task_backward_kernel<KIND>, grid, dim3(256), 0, st, h, row_a, row_b, out3, dscores, ldd);
+  });
 }
 
 namespace {
@@ -650,7 +706,7 @@ int32_t gigl_retrieval_loss_backward(gigl_ctx* ctx, const float* scores, int64_t
   GIGL_REQUIRE(ctx, row_lse && dscores, "null argument");
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipLaunchKernelGGL(retrieval_backward_kernel, dim3((unsigned)q), dim3(256), 0, ctx->stream, a, row_lse, grad_loss,
-                     dscores);
+                     (const float*)nullptr, 1.f, dscores, (int64_t)c);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }

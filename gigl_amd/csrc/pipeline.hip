@@ -855,14 +855,6 @@ __global__ __launch_bounds__(256) void dropout_keep_kernel(uint8_t* __restrict__
   }
 }
 
-__global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ w, int rows, int cols, float* __restrict__ wt) {
-  const int64_t n = (int64_t)rows * cols;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int r = (int)(i / cols), c = (int)(i - (int64_t)r * cols);
-    wt[(int64_t)c * rows + r] = w[i];
-  }
-}
-
 // Adam with L2 weight decay (torch.optim.Adam: the decay joins the gradient), every parameter tensor in one launch.
 // A tensor's gradient is the sum of up to two SOURCES (the two encodes of a link-prediction step share the weights).  A
 // source is a plain vector g, or the weight-gradient kernel's per-chunk PARTIAL sums (part != NULL: [chunks][n] floats, the
@@ -2405,175 +2397,6 @@ __global__ __launch_bounds__(256) void lp_pack_kernel(const float* __restrict__ 
   }
 }
 
-__device__ __forceinline__ bool lp_excluded(const int64_t* qid, const int64_t* cid, const int32_t* valid, int remove_hits,
-                                            int Q, int i, int j, int64_t qid_i, int64_t cid_i) {
-  if (!valid[j]) return true;
-  if (j == i) return false;
-  if (j < Q && qid[j] == qid_i) return true;          // another positive of the same query (loss.py:279-305)
-  return remove_hits && cid[j] == cid_i;              // the positive itself among the other candidates (:307-331)
-}
-
-// retrieval loss rows (loss.hip's retrieval_rows_kernel with a validity mask): one workgroup per query row
-__global__ __launch_bounds__(256) void lp_loss_rows_kernel(const float* __restrict__ scores, int Q, int Cn, float temperature,
-                                                           const int64_t* __restrict__ qid, const int64_t* __restrict__ cid,
-                                                           const int32_t* __restrict__ valid, int remove_hits,
-                                                           float* __restrict__ row_lse, float* __restrict__ row_loss) {
-  __shared__ float s_m[4], s_s[4];
-  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (!valid[i]) {
-    if (tid == 0) {
-      row_lse[i] = 0.f;
-      row_loss[i] = 0.f;
-    }
-    return;
-  }
-  const float* row = scores + (int64_t)i * Cn;
-  const int64_t qid_i = qid[i], cid_i = cid[i];
-  const float it = temperature > 0.f ? 1.f / temperature : 1.f;
-  float m = -INFINITY, s = 0.f;
-  for (int j = tid; j < Cn; j += 256) {
-    if (lp_excluded(qid, cid, valid, remove_hits, Q, i, j, qid_i, cid_i)) continue;
-    const float v = temperature > 0.f ? row[j] / temperature : row[j];
-    if (v > m) {
-      s = s * expf(m - v) + 1.f;
-      m = v;
-    } else {
-      s += expf(v - m);
-    }
-  }
-  (void)it;
-  for (int off = 32; off > 0; off >>= 1) {
-    const float m2 = __shfl_xor(m, off, 64), s2 = __shfl_xor(s, off, 64);
-    const float mm = fmaxf(m, m2);
-    if (mm != -INFINITY) {
-      s = s * expf(m - mm) + s2 * expf(m2 - mm);
-      m = mm;
-    }
-  }
-  if (lane == 0) {
-    s_m[w] = m;
-    s_s[w] = s;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float mm = s_m[0], ss = s_s[0];
-    for (int k = 1; k < 4; ++k) {
-      const float m2 = s_m[k], s2 = s_s[k], mx = fmaxf(mm, m2);
-      if (mx != -INFINITY) {
-        ss = ss * expf(mm - mx) + s2 * expf(m2 - mx);
-        mm = mx;
-      }
-    }
-    const float lse = mm + logf(ss);
-    row_lse[i] = lse;
-    row_loss[i] = lse - (temperature > 0.f ? row[i] / temperature : row[i]);
-  }
-}
-
-// loss[0] = the task's weight x sum of the valid rows' losses / their number (fixed order, in double), loss[1] = that number; Adam's step
-// counter moves when the step will be applied
-__global__ __launch_bounds__(1024) void lp_loss_sum_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ valid,
-                                                           int Q, float weight, float* __restrict__ loss, int32_t* __restrict__ step,
-                                                           const int32_t* __restrict__ meta_a, const int32_t* __restrict__ meta_b) {
-  __shared__ double s_w[16];
-  __shared__ int s_n[16];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  double acc = 0.0;
-  int n = 0;
-  for (int i = tid; i < Q; i += 1024) {
-    acc += (double)row_loss[i];
-    n += valid[i] ? 1 : 0;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    acc += __shfl_xor(acc, off, 64);
-    n += __shfl_xor(n, off, 64);
-  }
-  if (lane == 0) {
-    s_w[w] = acc;
-    s_n[w] = n;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-    int nn = 0;
-    for (int k = 0; k < 16; ++k) {
-      t += s_w[k];
-      nn += s_n[k];
-    }
-    const bool failed = meta_a[GIGL_META_OVERFLOW] != 0 || meta_b[GIGL_META_OVERFLOW] != 0;
-    loss[0] = failed ? __builtin_nanf("") : (float)(t / (double)(nn > 0 ? nn : 1)) * weight;  // (x 1.0f: the same bits)
-    loss[1] = (float)nn;
-    if (!failed) *step += 1;
-  }
-}
-
-// the evaluation's loss sum: acc[LOSS_SUM] += the valid rows' mean loss (as lp_loss_sum_kernel adds it up), acc[BATCHES] += 1;
-// a batch beyond the workspace adds 1 to *overflow_acc instead.  Adam's step counter is not touched.
-__global__ __launch_bounds__(1024) void lp_eval_loss_sum_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ valid,
-                                                                int Q, float weight, const int32_t* __restrict__ meta_a,
-                                                                const int32_t* __restrict__ meta_b, double* __restrict__ acc,
-                                                                int32_t* __restrict__ overflow_acc) {
-  __shared__ double s_w[16];
-  __shared__ int s_n[16];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  double sum = 0.0;
-  int n = 0;
-  for (int i = tid; i < Q; i += 1024) {
-    sum += (double)row_loss[i];
-    n += valid[i] ? 1 : 0;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    sum += __shfl_xor(sum, off, 64);
-    n += __shfl_xor(n, off, 64);
-  }
-  if (lane == 0) {
-    s_w[w] = sum;
-    s_n[w] = n;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-    int nn = 0;
-    for (int k = 0; k < 16; ++k) {
-      t += s_w[k];
-      nn += s_n[k];
-    }
-    if (meta_a[GIGL_META_OVERFLOW] != 0 || meta_b[GIGL_META_OVERFLOW] != 0) {
-      *overflow_acc += 1;
-    } else {
-      acc[GIGL_LP_EVAL_LOSS_SUM] += (double)((float)(t / (double)(nn > 0 ? nn : 1)) * weight);  // (the fp32 word a step reports)
-      acc[GIGL_LP_EVAL_BATCHES] += 1.0;
-    }
-  }
-}
-
-// dscores = d loss / d scores: weight x (softmax - onehot) / temperature / rows for the columns that take part, 0 elsewhere
-__global__ __launch_bounds__(256) void lp_loss_backward_kernel(const float* __restrict__ scores, int Q, int Cn, float temperature,
-                                                               const int64_t* __restrict__ qid, const int64_t* __restrict__ cid,
-                                                               const int32_t* __restrict__ valid, int remove_hits,
-                                                               const float* __restrict__ row_lse, const float* __restrict__ loss,
-                                                               float weight, float* __restrict__ dscores) {
-  const int i = blockIdx.x;
-  float* out = dscores + (int64_t)i * Cn;
-  if (!valid[i]) {
-    for (int j = threadIdx.x; j < Cn; j += 256) out[j] = 0.f;
-    return;
-  }
-  const float* row = scores + (int64_t)i * Cn;
-  const int64_t qid_i = qid[i], cid_i = cid[i];
-  const float lse = row_lse[i];
-  const float nrows = loss[1] > 0.f ? loss[1] : 1.f;
-  const float scale = (temperature > 0.f ? 1.f / temperature : 1.f) / nrows * weight;  // (x 1.0f: the same bits)
-  for (int j = threadIdx.x; j < Cn; j += 256) {
-    float d = 0.f;
-    if (!lp_excluded(qid, cid, valid, remove_hits, Q, i, j, qid_i, cid_i)) {
-      const float v = temperature > 0.f ? row[j] / temperature : row[j];
-      d = (expf(v - lse) - (j == i ? 1.f : 0.f)) * scale;
-    }
-    out[j] = d;
-  }
-}
-
 // d emb of the two encodes from d rq / d cand: an anchor's row sums its P query rows, a positive's row is its candidate
 // row, a hard negative's and a random negative's their own; then through the normalisation (dx = (g - y <y, g>) / max(|x|, eps)) and added to the
 // last layer's output gradient at the root's local row (roots that are the same node share it: atomics).  One wave per root.
@@ -2665,10 +2488,11 @@ int32_t lp_enqueue_graph(gigl_nablp_train_plan* t, int w, int32_t sampling_seed,
   return GIGL_OK;
 }
 
-// a Margin / Softmax task over the plan's scores and validity words (loss.hip)
+// the job's task over the plan's scores, ids and validity words (loss.hip)
 LpTaskHead lp_task_head(const gigl_nablp_train_plan* t) {
-  return LpTaskHead{t->task_kind, t->task_param, t->task_weight, t->scores, (int64_t)t->cand_cols(), t->b, t->P, t->H, t->n_rn,
-                    t->pos_cnt, t->valid};
+  const bool retrieval = t->task_kind == GIGL_LP_TASK_RETRIEVAL;
+  return LpTaskHead{t->task_kind, retrieval ? t->temperature : t->task_param, t->task_weight, t->scores, (int64_t)t->cand_cols(),
+                    t->b, t->P, t->H, t->n_rn, t->pos_cnt, t->valid, t->qid, t->remove_hits ? t->cid : nullptr};
 }
 
 // the forward half of the layers part over workspace w: both encodes, the head's operands, the scores, the loss rows
@@ -2684,11 +2508,8 @@ int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w, bool train) {
     rc = gat_lp_begin(t);
     if (rc != GIGL_OK) return rc;
   }
-  for (int l = 1; l < L && t->kind == 0; ++l) {  // W_l^T for the input gradients of both encodes
-    const int64_t nw = (int64_t)t->dims[l + 1] * 2 * t->dims[l];
-    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, (const float*)t->w[l],
-                       t->dims[l + 1], 2 * t->dims[l], t->wt_l[l]);
-  }
+  for (int l = 1; l < L && t->kind == 0; ++l)  // W_l^T for the input gradients of both encodes
+    gigl_transpose_f32(st, t->w[l], t->dims[l + 1], 2 * t->dims[l], t->wt_l[l]);
   if (t->fork) {
     GIGL_HIP_CHECK(ctx, hipEventRecord(t->ev_fork[0], st));
     GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(t->actx->stream, t->ev_fork[0], 0));
@@ -2709,12 +2530,7 @@ int32_t lp_enqueue_forward(gigl_nablp_train_plan* t, int w, bool train) {
   // scores[q][c] = <rq[q], cand[c]>  (decoder.py:64-70: torch.mm(q, c.T))
   rc = gigl_linear(ctx, t->rq, t->cand, nullptr, t->consts + 0, Q, d, Cn, 0, t->scores);
   if (rc != GIGL_OK) return rc;
-  if (t->task_kind != GIGL_LP_TASK_RETRIEVAL)
-    gigl_lp_task_rows_enqueue(st, lp_task_head(t), t->row_lse, t->row_loss);
-  else
-    hipLaunchKernelGGL(lp_loss_rows_kernel, dim3((unsigned)Q), dim3(256), 0, st, (const float*)t->scores, Q, Cn, t->temperature,
-                       (const int64_t*)t->qid, (const int64_t*)t->cid, (const int32_t*)t->valid, t->remove_hits, t->row_lse,
-                       t->row_loss);
+  gigl_lp_task_rows_enqueue(st, lp_task_head(t), t->row_lse, t->row_loss);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
@@ -2727,23 +2543,12 @@ int32_t lp_enqueue_layers(gigl_nablp_train_plan* t, int w) {
   int32_t rc = lp_enqueue_forward(t, w, true);
   if (rc != GIGL_OK) return rc;
   const BatchGraph *pm = t->enc[0].base, *pr = t->enc[1].base;
-  if (t->task_kind != GIGL_LP_TASK_RETRIEVAL) {
-    const LpTaskHead h = lp_task_head(t);
-    gigl_lp_task_sum_enqueue(st, h, t->row_lse, t->row_loss, t->loss, t->consts + 2, (const int32_t*)pm->un.meta,
-                             (const int32_t*)pr->un.meta, nullptr, nullptr);
-    gigl_lp_task_backward_enqueue(st, h, t->row_lse, t->row_loss, t->loss, t->dscores, (int64_t)Cn);
-  } else {
-    hipLaunchKernelGGL(lp_loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->row_loss, (const int32_t*)t->valid, Q,
-                       t->task_weight, t->loss, t->consts + 2, (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta);
-    hipLaunchKernelGGL(lp_loss_backward_kernel, dim3((unsigned)Q), dim3(256), 0, st, (const float*)t->scores, Q, Cn,
-                       t->temperature, (const int64_t*)t->qid, (const int64_t*)t->cid, (const int32_t*)t->valid, t->remove_hits,
-                       (const float*)t->row_lse, (const float*)t->loss, t->task_weight, t->dscores);
-  }
+  const LpTaskHead h = lp_task_head(t);
+  gigl_lp_task_sum_enqueue(st, h, t->row_lse, t->row_loss, t->loss, t->consts + 2, (const int32_t*)pm->un.meta,
+                           (const int32_t*)pr->un.meta, nullptr, nullptr);
+  gigl_lp_task_backward_enqueue(st, h, t->row_lse, t->row_loss, t->loss, t->dscores, (int64_t)Cn);
   // d rq = dscores . cand ;  d cand = dscores^T . rq
-  {
-    int64_t blocks = ((int64_t)Cn * d + 255) / 256;
-    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)t->cand, Cn, d, t->cand_t);
-  }
+  gigl_transpose_f32(st, t->cand, Cn, d, t->cand_t);
   rc = gigl_linear(ctx, t->dscores, t->cand_t, nullptr, t->consts + 0, Q, Cn, d, 0, t->d_rq);
   if (rc != GIGL_OK) return rc;
   gigl_fill_u32(st, t->d_cand, 0u, (int64_t)Cn * d);  // (gigl_linear_weight_grad ADDS its chunks' sums to dw)
@@ -3048,12 +2853,8 @@ int32_t gigl_nablp_train_plan_eval(gigl_nablp_train_plan* t, const uint32_t* mai
   for (int k = 0; k < 2; ++k) t->enc[k].base = held[k];
   if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
   const int Q = t->b * t->P;
-  if (t->task_kind != GIGL_LP_TASK_RETRIEVAL)
-    gigl_lp_task_sum_enqueue(st, lp_task_head(t), t->row_lse, t->row_loss, nullptr, nullptr, (const int32_t*)pm->un.meta,
-                             (const int32_t*)pr->un.meta, acc, overflow_acc);
-  else
-    hipLaunchKernelGGL(lp_eval_loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->row_loss, (const int32_t*)t->valid, Q,
-                       t->task_weight, (const int32_t*)pm->un.meta, (const int32_t*)pr->un.meta, acc, overflow_acc);
+  gigl_lp_task_sum_enqueue(st, lp_task_head(t), t->row_lse, t->row_loss, nullptr, nullptr, (const int32_t*)pm->un.meta,
+                           (const int32_t*)pr->un.meta, acc, overflow_acc);
   const int R0 = Q + t->b * t->H;  // (ranked against the random negatives only, as the reference's validate does)
   rc = gigl_lp_rank_metrics_enqueue(t->lctx, st, t->scores, (int64_t)t->cand_cols(), t->b, t->P, t->pos_cnt, t->n_rn, R0,
                                     t->valid + R0, ks, n_ks, pm->un.meta, pr->un.meta, t->rank_part, acc);
@@ -3285,23 +3086,6 @@ int32_t gigl_nablp_train_plan_grads(gigl_nablp_train_plan* t, int32_t layer, flo
 // encodes ADD into one set of gradients; head, loss, Adam, workspaces and prefetch are gigl_nablp_train_plan's.
 namespace {
 
-// u[h][k] = sum_c att_src[hC + c] W[hC + c][k];  u[H + h][k] = the same with att_dst
-__global__ __launch_bounds__(256) void gat_fold_kernel(const float* __restrict__ w, const float* __restrict__ att_src,
-                                                       const float* __restrict__ att_dst, int H, int C, int d,
-                                                       float* __restrict__ u) {
-  // grid (2H, ceil(d / 64)); a workgroup = 64 columns x 4 slices of the C rows
-  __shared__ float s_part[4][64];
-  const int hh = blockIdx.x;  // 0 .. 2H
-  const int h = hh % H;
-  const float* att = (hh < H ? att_src : att_dst) + h * C;
-  const int k = blockIdx.y * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
-  float acc = 0.f;
-  if (k < d)
-    for (int c = q; c < C; c += 4) acc += att[c] * w[(int64_t)(h * C + c) * d + k];
-  s_part[q][threadIdx.x & 63] = acc;
-  __syncthreads();
-  if (q == 0 && k < d) u[(int64_t)hh * d + k] = s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
-}
 // the fold's backward, one workgroup per weight row r = hC + c:
 //   gw[r][k] += att_src[r] du[h][k] + att_dst[r] du[H + h][k];  g_att_src[r] += <W[r], du[h]>;  g_att_dst[r] += <W[r], du[H + h]>
 __global__ __launch_bounds__(256) void gat_fold_backward_kernel(const float* __restrict__ w, const float* __restrict__ att_src,
@@ -3414,17 +3198,12 @@ gigl_gat_edge_terms gat_edge_terms0(const gigl_nablp_train_plan* t, int which) {
 // once per step: the folded attention vectors of the first layer (both encodes read them)
 int32_t gat_lp_begin(gigl_nablp_train_plan* t) {
   const auto& g = t->gat;
-  hipLaunchKernelGGL(gat_fold_kernel, dim3((unsigned)(2 * g.heads), (unsigned)((g.d_in + 63) / 64)), dim3(256), 0,
-                     t->lctx->stream, (const float*)g.at(GAT_W, 0).p, (const float*)g.at(GAT_ATT_SRC, 0).p,
-                     (const float*)g.at(GAT_ATT_DST, 0).p, g.heads, g.c0, g.d_in, g.u);
-  // W1^T and the heads' W0^T for the input gradients of both encodes
   hipStream_t st = t->lctx->stream;
-  const int HC = g.heads * g.c0;
-  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(((int64_t)g.c1 * HC + 255) / 256)), dim3(256), 0, st,
-                     (const float*)g.at(GAT_W, 1).p, g.c1, HC, g.wt1);
+  gigl_gat_fold(st, g.at(GAT_W, 0).p, g.at(GAT_ATT_SRC, 0).p, g.at(GAT_ATT_DST, 0).p, g.heads, g.c0, g.d_in, g.u);
+  // W1^T and the heads' W0^T for the input gradients of both encodes
+  gigl_transpose_f32(st, g.at(GAT_W, 1).p, g.c1, g.heads * g.c0, g.wt1);
   for (int h = 0; h < g.heads; ++h)
-    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(((int64_t)g.c0 * g.d_in + 255) / 256)), dim3(256), 0, st,
-                       (const float*)(g.at(GAT_W, 0).p + (int64_t)h * g.c0 * g.d_in), g.c0, g.d_in, g.wt0[h]);
+    gigl_transpose_f32(st, g.at(GAT_W, 0).p + (int64_t)h * g.c0 * g.d_in, g.c0, g.d_in, g.wt0[h]);
   if (g.e.table) {  // both layers' folded att_edge (the parameters change every step), the edge gradients' clean slate
     const int De = g.e.De;
     gigl_fill_u32(st, g.e.zero_base, 0u, (int64_t)(g.e.zero_bytes / 4));

@@ -1,6 +1,7 @@
-"""The head of the link-prediction training plans (csrc/pipeline.hip: lp_take_norm_kernel, lp_pack_kernel, lp_excluded,
-lp_loss_rows_kernel, lp_loss_sum_kernel / lp_eval_loss_sum_kernel, lp_loss_backward_kernel, lp_unpack_scatter_kernel and the
-two score-gradient GEMMs between them) against a float64 formula, at the shapes, masks and values the whole-step tests
+"""The head of the link-prediction training plans (csrc/pipeline.hip: lp_take_norm_kernel, lp_pack_kernel,
+lp_unpack_scatter_kernel; csrc/loss.hip through the LpTaskHead interface: excluded, retrieval_rows_kernel,
+lp_task_sum_kernel<RETRIEVAL> for training and evaluation, retrieval_backward_kernel; and the two score-gradient GEMMs
+between them) against a float64 formula, at the shapes, masks and values the whole-step tests
 never reach.  The kernels are static inside the plan; they are reached through HipEngine, models.GraphSAGE and
 NablpTrainPlan.step / grads / store / evaluate / close only.
 
@@ -36,9 +37,9 @@ What each case reaches (b anchors, P positive slots, n_rn random negatives, d; Q
                    negatives) padded by the wrapper
     32/2/1/64      Cn = 65: the second wave holds one column; d = 64: a full chunk
     50/3/106/65    Cn = 256: every thread of the loss block one column; d = 64 + 1: a second chunk of one lane
-    50/3/107/130   Cn = 257: the second 256-stride trip of lp_loss_rows / lp_loss_backward holds one column
+    50/3/107/130   Cn = 257: the second 256-stride trip of retrieval_rows / retrieval_backward holds one column
     96/4/200/512   Cn = 584, Q = 384: three trips, ragged; the widest row (8 registers per lane)
-    300/4/10/16    Q = 1200 > 1024: the second trip of lp_loss_sum_kernel
+    300/4/10/16    Q = 1200 > 1024: the second trip of lp_task_sum_kernel
     513, 516       refused (GIGL_E_INVALID_ARG), nothing left allocated, a valid plan afterwards works
     masks 24/3/20/40, hit removal on and off: a repeated anchor, invalid anchor / counted positive / negative, pos_cnt 0, 1
                    and P + 2, a positive equal to its anchor, shared by two anchors, equal to a random negative (eight
@@ -48,7 +49,7 @@ What each case reaches (b anchors, P positive slots, n_rn random negatives, d; Q
     values 32/2/30/48: unnormalised scores +-60 at temperature 1 (the running-max log-sum-exp); a zero embedding as
                    anchor, positive and negative (the 1e-12 clamp and its backward); temperature 2.5 with an invalid
                    anchor, positive and negative (a zero row's score of 0 weighs as much as any column there)
-    evaluation     lp_eval_loss_sum_kernel on the mask and the Cn = 257 batch; a training step afterwards repeats its bits
+    evaluation     lp_task_sum_kernel's evaluation half on the mask and the Cn = 257 batch; a training step afterwards repeats its bits
 
 Tolerances (nothing is derived from the kernel's output): per compared tensor the larger of the project's own — loss
 rtol 2e-5 (3e-4 unnormalised, as test_gpu_train_plan.py), gradients rtol 1e-4 and atol 1e-4 max|want| — and 4 x the
