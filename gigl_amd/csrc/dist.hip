@@ -409,9 +409,8 @@ __global__ __launch_bounds__(256) void dist_clear_kernel(ClearSegs s) {
 
 // frontier slot i (node v, path sum K) -> bucket owner(v) = v % world, at the next free position p (fixed capacity):
 // nodes_out[r*cap + p] = v, ksum_out[r*cap + p] = K, slot_idx[r*cap + p] = i, pos[i] = r*cap + p (optional).
-// One global atomic per (workgroup, owner): slots take a rank inside the workgroup from LDS counters (same-address
-// atomics serialise; with a small world every slot hits one of `world` counters).  n_valid (optional, device): only
-// the first *n_valid slots exist.
+// (gigl_bucket_position: one global atomic per workgroup and owner.)  n_valid (optional, device): only the first
+// *n_valid slots exist.
 __global__ __launch_bounds__(256) void bucket_kernel(const uint32_t* __restrict__ nodes,
                                                      const uint32_t* __restrict__ ksums, int64_t m,
                                                      const int32_t* __restrict__ n_valid, uint32_t world, int64_t cap,
@@ -432,32 +431,7 @@ __global__ __launch_bounds__(256) void bucket_kernel(const uint32_t* __restrict_
     v = GIGL_INVALID;
   }
   const uint32_t r = v == GIGL_INVALID ? 0xFFFFFFFFu : v % world;
-  const int lane = threadIdx.x & 63;
-  int32_t p = 0;
-  if (world <= 64) {
-    __shared__ int32_t s_cnt[64], s_base[64];
-    if (threadIdx.x < world) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    int32_t rank = 0;
-    if (r != 0xFFFFFFFFu) rank = atomicAdd(&s_cnt[r], 1);
-    __syncthreads();
-    if (threadIdx.x < world && s_cnt[threadIdx.x] > 0)
-      s_base[threadIdx.x] = atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
-    __syncthreads();
-    if (r != 0xFFFFFFFFu) p = s_base[r] + rank;
-  } else {
-    unsigned long long todo = __ballot(r != 0xFFFFFFFFu);
-    while (todo) {
-      const int lead = __ffsll((long long)todo) - 1;
-      const uint32_t r_lead = __shfl(r, lead, 64);
-      const unsigned long long same = __ballot(r == r_lead);
-      int32_t base = 0;
-      if (lane == lead) base = atomicAdd(&counts[r_lead], (int32_t)__popcll(same));
-      base = __shfl(base, lead, 64);
-      if (r == r_lead) p = base + (int32_t)__popcll(same & ((1ull << lane) - 1ull));
-      todo &= ~same;
-    }
-  }
+  const int32_t p = gigl_bucket_position(r, world, counts);
   if (r == 0xFFFFFFFFu) {
     if (pos && i < m && !own) pos[i] = -1;
     return;
@@ -491,7 +465,6 @@ __global__ __launch_bounds__(256) void claim_bucket_kernel(const uint32_t* __res
                                                            int32_t* __restrict__ counts, uint32_t* __restrict__ stamp,
                                                            uint32_t tag, int32_t* __restrict__ slot_map,
                                                            int64_t n_global, int32_t own_rank) {
-  __shared__ int32_t s_cnt[64], s_base[64];
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t lim = n_valid ? (int64_t)*n_valid : m;
   uint32_t v = (i < m && i < lim) ? nodes[i] : GIGL_INVALID;
@@ -507,31 +480,7 @@ __global__ __launch_bounds__(256) void claim_bucket_kernel(const uint32_t* __res
     if (was == tag || was == DIST_HOT_STAMP) v = GIGL_INVALID;
   }
   const uint32_t r = v == GIGL_INVALID ? 0xFFFFFFFFu : v % world;
-  const int lane = threadIdx.x & 63;
-  int32_t p = 0;
-  if (world <= 64) {
-    if (threadIdx.x < world) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    int32_t rank = 0;
-    if (r != 0xFFFFFFFFu) rank = atomicAdd(&s_cnt[r], 1);
-    __syncthreads();
-    if (threadIdx.x < world && s_cnt[threadIdx.x] > 0)
-      s_base[threadIdx.x] = atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
-    __syncthreads();
-    if (r != 0xFFFFFFFFu) p = s_base[r] + rank;
-  } else {
-    unsigned long long todo = __ballot(r != 0xFFFFFFFFu);
-    while (todo) {
-      const int lead = __ffsll((long long)todo) - 1;
-      const uint32_t r_lead = __shfl(r, lead, 64);
-      const unsigned long long same = __ballot(r == r_lead);
-      int32_t base = 0;
-      if (lane == lead) base = atomicAdd(&counts[r_lead], (int32_t)__popcll(same));
-      base = __shfl(base, lead, 64);
-      if (r == r_lead) p = base + (int32_t)__popcll(same & ((1ull << lane) - 1ull));
-      todo &= ~same;
-    }
-  }
+  const int32_t p = gigl_bucket_position(r, world, counts);
   if (r == 0xFFFFFFFFu) return;
   if (p >= cap) {
     atomicOr(&counts[world], 1);
@@ -771,6 +720,11 @@ __global__ __launch_bounds__(256) void dist_stats_kernel(DistStatsArgs a, unsign
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ the sharded plan
+struct DistArgs { const uint32_t* roots; int32_t seed; float* out; };
+// one thing a plan does in phase `phase` of a call (the step_* functions below), for hop or layer `k`
+struct DistStep { int32_t (*run)(gigl_dist_plan* p, int k, const DistArgs& a); int k, phase; };
+constexpr int DIST_MAX_STEPS = 48;  // (6 per hop + 2 per layer at GIGL_MAX_HOPS, + 10 around them)
+
 struct gigl_dist_plan {
   gigl_comm* comm = nullptr;
   gigl_ctx* ctx = nullptr;
@@ -863,6 +817,10 @@ struct gigl_dist_plan {
   float* abuf = nullptr;
   float* hbuf[2] = {nullptr, nullptr};
   int64_t act_rows = 0;
+  // what a call runs, ordered by phase: the plan's route through the steps, decided once (dist_build_steps)
+  DistStep steps[DIST_MAX_STEPS];
+  int n_steps = 0;
+  bool resp_in_place = false;  // a hop's answers to this rank's own requests are written where they are read (resp_r)
   std::vector<void*> owned;
 };
 
@@ -887,8 +845,15 @@ bool own_rows_in_place(const gigl_dist_plan* p) { return p->dense && p->own_in_p
 // creation) and no exchange touches them
 bool pull_self_in_place(const gigl_dist_plan* p) { return own_rows_in_place(p) && comm_self_in_place(p->comm); }
 
+const int32_t* level_count(const gigl_dist_plan* p, int level) { return p->un.meta + GIGL_META_LEVEL0 + level; }
+int64_t level_rows(const gigl_dist_plan* p, int level) { return gigl_level_rows(false, p->b, p->fan, p->hops, level); }
+int32_t own_rank(const gigl_dist_plan* p) { return p->own_in_place ? p->rank : -1; }
+
+// ---- the steps of a call.  Each enqueues on the ctx stream; which of them a plan runs, and in which phase:
+// dist_build_steps — no step asks which route it is on
+
 // one launch at the start of a call: every bucket and counter the call's phases expect cleared (dist_clear_kernel)
-int32_t clear_call(gigl_dist_plan* p) {
+int32_t step_clear(gigl_dist_plan* p, int, const DistArgs&) {
   ClearSegs sg{};
   int n = 0;
   int64_t at = 0;
@@ -943,310 +908,424 @@ int32_t serve_rows(gigl_dist_plan* p, const uint32_t* ids, int64_t n_entries, co
 }
 
 // hop k's answers -> tree slots, counts and the children's path sums (K of a root's path is the root id)
-int32_t scatter_hop(gigl_dist_plan* p, int k, const uint32_t* roots) {
+int32_t step_scatter(gigl_dist_plan* p, int k, const DistArgs& a) {
   const int64_t total = p->m[k] * p->fan[k];
   gigl_prof_scope ps(p->ctx, GIGL_K_DIST_PREP);
   hipLaunchKernelGGL(scatter_slots_kernel, dim3((unsigned)grid256(total)), dim3(256), 0, p->ctx->stream, p->resp_r[k],
-                     p->hop_pos[k], k == 0 ? roots : p->child_ksum[k - 1], p->m[k], p->fan[k], p->tree.nbr[k],
+                     p->hop_pos[k], k == 0 ? a.roots : p->child_ksum[k - 1], p->m[k], p->fan[k], p->tree.nbr[k],
                      p->tree.cnt[k], k + 1 < p->hops ? p->child_ksum[k] : (uint32_t*)nullptr);
   GIGL_HIP_CHECK(p->ctx, hipGetLastError());
   return GIGL_OK;
 }
 
-int32_t phase_impl(gigl_dist_plan* p, int phase, const uint32_t* roots, int32_t seed, float* out) {
+// a LONE rank (world 1 on a transport that needs no self copy) owns every row: its hops are the single-GPU sampler's,
+// straight into the tree — no bucket, no request / answer blocks, no scatter (the same selection rule and table: the
+// owners' expansion IS that sampler, run on explicit frontiers)
+int32_t step_sample_lone(gigl_dist_plan* p, int, const DistArgs& a) {
+  return gigl_sample_khop(p->ctx, p->shard, a.roots, p->b, p->fan, p->hops, a.seed, GIGL_MODE_SPARK_HASH, &p->tree);
+}
+
+// ... and so does a peer-sampled rank, reading the owners' adjacency rows where they live
+int32_t step_sample_peer(gigl_dist_plan* p, int, const DistArgs& a) {
+  if (!p->peer_graphs_ready)
+    return gigl_fail(p->ctx, GIGL_E_INVALID_ARG, "peer-sampled plan: the ranks' graph shards were not set (gigl_dist_plan_set_peer_graphs)");
+  return gigl_sample_khop_peer(p->ctx, p->peer_rowptr_dev, p->peer_col_dev, p->world, p->n_global, p->mwe, a.roots, p->b, p->fan,
+                               p->hops, a.seed, &p->tree);
+}
+
+// requester: hop k's frontier into its owners' buckets (this rank's own requests: where they are read)
+int32_t step_bucket_hop(gigl_dist_plan* p, int k, const DistArgs& a) {
+  const bool in_place = comm_self_in_place(p->comm);
+  gigl_prof_scope ps(p->ctx, GIGL_K_DIST_PREP);
+  hipLaunchKernelGGL(bucket_kernel, dim3((unsigned)grid256(p->m[k])), dim3(256), 0, p->ctx->stream,
+                     k == 0 ? a.roots : p->tree.nbr[k - 1], k == 0 ? (const uint32_t*)nullptr : p->child_ksum[k - 1], p->m[k],
+                     (const int32_t*)nullptr, (uint32_t)p->world, p->cap[k], p->rq_nodes_s[k], p->rq_ksum_s[k], (int32_t*)nullptr,
+                     p->hop_pos[k], p->counts[k], (uint32_t)p->rank, in_place ? p->rq_nodes_r[k] : (uint32_t*)nullptr,
+                     in_place ? p->rq_ksum_r[k] : (uint32_t*)nullptr);
+  GIGL_HIP_CHECK(p->ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+int32_t hop_hash_add(const DistArgs& a, int k) { return (int32_t)((uint32_t)a.seed * (uint32_t)(k + 1)); }
+
+// in-step overlap: the own block sits in the receive buffer already (bucket_kernel wrote it there) — expand it NOW, on
+// the side stream, while the request exchange moves the peers' blocks
+int32_t step_expand_own(gigl_dist_plan* p, int k, const DistArgs& a) {
   gigl_ctx* ctx = p->ctx;
-  hipStream_t st = ctx->stream;
-  const int L = p->hops;
+  const int64_t off = (int64_t)p->rank * p->cap[k];
+  GIGL_HIP_CHECK(ctx, hipEventRecord(p->ev_bucket[k], ctx->stream));
+  GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(p->side->stream, p->ev_bucket[k], 0));
+  const int32_t rc = gigl_expand_frontier(p->side, p->shard, p->rq_nodes_r[k] + off, p->rq_ksum_r[k] + off, p->cap[k], p->fan[k],
+                                          hop_hash_add(a, k), p->world, p->mwe, p->resp_r[k] + off * p->fan[k], p->side_cnt);
+  if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(p->side));
+  GIGL_HIP_CHECK(ctx, hipEventRecord(p->ev_own[k], p->side->stream));
+  return GIGL_OK;
+}
+
+int32_t step_exchange_requests(gigl_dist_plan* p, int k, const DistArgs&) {
+  const bool in_place = comm_self_in_place(p->comm);
+  const int32_t rc = comm_exchange(p->comm, p->rq_nodes_s[k], p->rq_nodes_r[k], p->cap[k] * 4, in_place);
+  return rc != GIGL_OK ? rc : comm_exchange(p->comm, p->rq_ksum_s[k], p->rq_ksum_r[k], p->cap[k] * 4, in_place);
+}
+
+// owner: expand the requests of every rank on this shard (a one-rank world answers itself: straight into the receive
+// buffer, no copy of the whole answer block)
+int32_t step_expand_requests(gigl_dist_plan* p, int k, const DistArgs& a) {
+  return gigl_expand_frontier(p->ctx, p->shard, p->rq_nodes_r[k], p->rq_ksum_r[k], (int64_t)p->world * p->cap[k], p->fan[k],
+                              hop_hash_add(a, k), p->world, p->mwe, p->resp_in_place ? p->resp_r[k] : p->resp_s[k], p->own_cnt);
+}
+
+// ... in-step overlap: the peers' blocks only (before and after the own one); the own block's answers are the side stream's
+int32_t step_expand_peers(gigl_dist_plan* p, int k, const DistArgs& a) {
+  gigl_ctx* ctx = p->ctx;
+  const int64_t first[2] = {0, p->rank + 1}, ranks[2] = {p->rank, p->world - p->rank - 1};
+  for (int q = 0; q < 2; ++q) {
+    const int64_t off = first[q] * p->cap[k];
+    if (ranks[q] == 0) continue;
+    const int32_t rc = gigl_expand_frontier(ctx, p->shard, p->rq_nodes_r[k] + off, p->rq_ksum_r[k] + off, ranks[q] * p->cap[k],
+                                            p->fan[k], hop_hash_add(a, k), p->world, p->mwe, p->resp_s[k] + off * p->fan[k],
+                                            p->own_cnt);
+    if (rc != GIGL_OK) return rc;
+  }
+  GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, p->ev_own[k], 0));
+  return GIGL_OK;
+}
+
+int32_t step_exchange_answers(gigl_dist_plan* p, int k, const DistArgs&) {
+  return comm_exchange(p->comm, p->resp_s[k], p->resp_r[k], p->cap[k] * p->fan[k] * 4, p->resp_in_place);
+}
+
+// the dense union graph (leaves stay global ids), and the call's tag for the claims
+int32_t step_union_dense(gigl_dist_plan* p, int, const DistArgs& a) {
+  const int32_t rc = gigl_union_build_impl(p->ctx, a.roots, &p->tree, p->group_roots, &p->un, 1 | (p->shard->multi ? 2 : 0));
+  if (rc != GIGL_OK) return rc;
+  if (++p->tag == DIST_HOT_STAMP) {  // (the tags are used up: forget every stamp but the hot marks)
+    hipLaunchKernelGGL(hot_unmark_kernel, dim3((unsigned)grid256(p->n_global)), dim3(256), 0, p->ctx->stream, p->stamp,
+                       p->n_global, 0);
+    p->tag = 1;
+  }
+  return GIGL_OK;
+}
+
+// the second pull's requests: the inner nodes (level < hops) into their owners' B buckets, posb[] = where each row will arrive
+void bucket_inner_rows(gigl_dist_plan* p) {
+  hipLaunchKernelGGL(bucket_kernel, dim3((unsigned)grid256(p->act_rows)), dim3(256), 0, p->ctx->stream, p->un.nodes,
+                     (const uint32_t*)nullptr, p->act_rows, level_count(p, p->hops - 1), (uint32_t)p->world, p->pull_cap_b,
+                     p->idsb_s, (uint32_t*)nullptr, (int32_t*)nullptr, p->posb, p->pullb_counts, 0u, (uint32_t*)nullptr,
+                     (uint32_t*)nullptr, own_rank(p));
+}
+
+// dense pull requests: claim every id of the call once (CLAIM — the inner nodes first, then every sampled leaf; a lone
+// rank owns every row and claims nothing), locate the inner nodes' own rows (pos), and over pre-projected rows bucket the
+// inner nodes' W_r x rows (INNER: a second, small pull).  One profile scope over the launches, as they have been timed
+template <bool CLAIM, bool INNER>
+int32_t step_claim_locate(gigl_dist_plan* p, int, const DistArgs&) {
+  hipStream_t st = p->ctx->stream;
+  const int32_t* n_inner = level_count(p, p->hops - 1);
   const uint32_t world = (uint32_t)p->world;
-  int32_t rc = GIGL_OK;
-  // a LONE rank (world 1 on a transport that needs no self copy) owns every row: its hops are the single-GPU sampler's,
-  // straight into the tree — no bucket, no request / answer blocks, no scatter (the same selection rule and table: the
-  // owners' expansion IS that sampler, run on explicit frontiers)
-  const bool peer_hops = p->peer_sample && world > 1;
-  const bool lone_hops = (world == 1 && comm_self_in_place(p->comm) && !p->overlap) || peer_hops;
-  if (lone_hops && phase < 2 * L) {
-    if (phase != 0) return GIGL_OK;
-    rc = clear_call(p);
-    if (rc != GIGL_OK) return rc;
-    if (peer_hops) {
-      if (!p->peer_graphs_ready)
-        return gigl_fail(ctx, GIGL_E_INVALID_ARG, "peer-sampled plan: the ranks' graph shards were not set (gigl_dist_plan_set_peer_graphs)");
-      return gigl_sample_khop_peer(ctx, p->peer_rowptr_dev, p->peer_col_dev, p->world, p->n_global, p->mwe, roots, p->b, p->fan, L,
-                                   seed, &p->tree);
-    }
-    return gigl_sample_khop(ctx, p->shard, roots, p->b, p->fan, L, seed, GIGL_MODE_SPARK_HASH, &p->tree);
+  gigl_prof_scope ps(p->ctx, GIGL_K_DIST_PREP);
+  if (CLAIM) {
+    hipLaunchKernelGGL(claim_bucket_kernel, dim3((unsigned)grid256(p->act_rows)), dim3(256), 0, st, p->un.nodes, p->act_rows,
+                       n_inner, world, p->pull_cap, p->ids_s, p->pull_counts, p->stamp, p->tag, p->slot_map, p->n_global,
+                       own_rank(p));
+    hipLaunchKernelGGL(claim_bucket_kernel, dim3((unsigned)grid256(p->last_slots)), dim3(256), 0, st,
+                       (const uint32_t*)p->tree.nbr[p->hops - 1], p->last_slots, (const int32_t*)nullptr, world, p->pull_cap,
+                       p->ids_s, p->pull_counts, p->stamp, p->tag, p->slot_map, p->n_global, own_rank(p));
   }
-  if (phase < 2 * L && (phase & 1) == 0) {
-    // ---- requester: (scatter the previous hop's answers,) bucket this hop's frontier by owner
-    const int k = phase >> 1;
-    if (k > 0) {
-      rc = scatter_hop(p, k - 1, roots);
-      if (rc != GIGL_OK) return rc;
-    }
-    const uint32_t* nodes = k == 0 ? roots : p->tree.nbr[k - 1];
-    const uint32_t* ksums = k == 0 ? nullptr : p->child_ksum[k - 1];
-    const bool in_place = comm_self_in_place(p->comm);
-    if (k == 0) {
-      rc = clear_call(p);
-      if (rc != GIGL_OK) return rc;
-    }
-    {
-      gigl_prof_scope ps(ctx, GIGL_K_DIST_PREP);
-      hipLaunchKernelGGL(bucket_kernel, dim3((unsigned)grid256(p->m[k])), dim3(256), 0, st, nodes, ksums, p->m[k],
-                         (const int32_t*)nullptr, world, p->cap[k], p->rq_nodes_s[k], p->rq_ksum_s[k], (int32_t*)nullptr,
-                         p->hop_pos[k], p->counts[k], (uint32_t)p->rank, in_place ? p->rq_nodes_r[k] : (uint32_t*)nullptr,
-                         in_place ? p->rq_ksum_r[k] : (uint32_t*)nullptr);
-    }
-    GIGL_HIP_CHECK(ctx, hipGetLastError());
-    if (p->overlap) {
-      // the own block sits in the receive buffer already (bucket_kernel wrote it there): expand it NOW, on the side
-      // stream, while the exchange below moves the peers' blocks
-      const int32_t hash_add = (int32_t)((uint32_t)seed * (uint32_t)(k + 1));
-      const int64_t off = (int64_t)p->rank * p->cap[k];
-      GIGL_HIP_CHECK(ctx, hipEventRecord(p->ev_bucket[k], st));
-      GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(p->side->stream, p->ev_bucket[k], 0));
-      rc = gigl_expand_frontier(p->side, p->shard, p->rq_nodes_r[k] + off, p->rq_ksum_r[k] + off, p->cap[k], p->fan[k],
-                                hash_add, p->world, p->mwe, p->resp_r[k] + off * p->fan[k], p->side_cnt);
-      if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(p->side));
-      GIGL_HIP_CHECK(ctx, hipEventRecord(p->ev_own[k], p->side->stream));
-    }
-    rc = comm_exchange(p->comm, p->rq_nodes_s[k], p->rq_nodes_r[k], p->cap[k] * 4, in_place);
-    if (rc == GIGL_OK) rc = comm_exchange(p->comm, p->rq_ksum_s[k], p->rq_ksum_r[k], p->cap[k] * 4, in_place);
-    return rc;
+  hipLaunchKernelGGL(pos_from_map_kernel, dim3((unsigned)grid256(p->act_rows)), dim3(256), 0, st, p->un.nodes, n_inner,
+                     p->act_rows, p->slot_map, p->n_global, p->pos, world, own_rank(p));
+  if (INNER) bucket_inner_rows(p);
+  GIGL_HIP_CHECK(p->ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+// the generic union graph (every node numbered); its nodes into their owners' buckets, pos[] = where each row will arrive
+int32_t step_union_generic(gigl_dist_plan* p, int, const DistArgs& a) {
+  const int32_t rc = gigl_union_build_groups(p->ctx, a.roots, &p->tree, p->group_roots, &p->un);
+  if (rc != GIGL_OK) return rc;
+  hipLaunchKernelGGL(bucket_kernel, dim3((unsigned)grid256(p->un.cap_nodes)), dim3(256), 0, p->ctx->stream, p->un.nodes,
+                     (const uint32_t*)nullptr, p->un.cap_nodes, p->un.meta + GIGL_META_N_NODES, (uint32_t)p->world, p->pull_cap,
+                     p->ids_s, (uint32_t*)nullptr, (int32_t*)nullptr, p->pos, p->pull_counts, 0u, (uint32_t*)nullptr,
+                     (uint32_t*)nullptr);
+  GIGL_HIP_CHECK(p->ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+int32_t step_bucket_inner(gigl_dist_plan* p, int, const DistArgs&) {
+  bucket_inner_rows(p);
+  GIGL_HIP_CHECK(p->ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+// the requested ids to their owners, and with them the row blocks' sizes
+int32_t step_exchange_ids(gigl_dist_plan* p, int, const DistArgs&) {
+  const bool self_ip = pull_self_in_place(p);
+  const int32_t rc = comm_exchange(p->comm, p->ids_s, p->ids_r, p->pull_cap * 4, self_ip);
+  return rc != GIGL_OK ? rc : comm_exchange(p->comm, p->pull_counts, p->req_counts, 4, self_ip);
+}
+
+int32_t step_exchange_inner_ids(gigl_dist_plan* p, int, const DistArgs&) {
+  return comm_exchange(p->comm, p->idsb_s, p->idsb_r, p->pull_cap_b * 4, pull_self_in_place(p));
+}
+
+// owner: the requested rows, gathered straight into the send buffer (raw rows, or the W_l x half of the pre-projected
+// table's [W_l x | W_r x] rows); only the requested rows travel — the head of each block (comm_exchange_rows)
+int32_t step_serve_rows(gigl_dist_plan* p, int, const DistArgs&) {
+  const bool in_place = comm_self_in_place(p->comm);
+  const char* table = p->preproj ? (const char*)p->preproj : (const char*)p->feat->rows;
+  const int64_t stride = p->preproj ? 2 * p->row_bytes : 0;  // ([W_l x | W_r x]: a served row is half a table row)
+  const int32_t rc = serve_rows(p, p->ids_r, (int64_t)p->world * p->pull_cap, table, stride, (char*)p->rows_s,
+                                (int64_t)p->rank * p->pull_cap, (int64_t)(p->rank + 1) * p->pull_cap,
+                                in_place ? (char*)p->rows_r : (char*)nullptr);
+  if (rc != GIGL_OK) return rc;
+  return comm_exchange_rows(p->comm, p->rows_s, p->rows_r, p->pull_cap * p->row_bytes, p->req_counts, p->pull_counts, p->row_bytes,
+                            in_place);
+}
+
+// ... and the W_r x half rows of the inner nodes (pre-projected rows)
+int32_t step_serve_inner_rows(gigl_dist_plan* p, int, const DistArgs&) {
+  const int32_t rc = serve_rows(p, p->idsb_r, (int64_t)p->world * p->pull_cap_b, (const char*)p->preproj + p->row_bytes, 2 * p->row_bytes,
+                                (char*)p->rowsb_s, (int64_t)0, (int64_t)0, (char*)nullptr);
+  if (rc != GIGL_OK) return rc;
+  return comm_exchange(p->comm, p->rowsb_s, p->rowsb_r, p->pull_cap_b * p->row_bytes, pull_self_in_place(p));
+}
+
+// owner-side projection: the requested rows widened to fp32 and projected into the send buffers — W_l x for every union
+// node, W_r x for the inner nodes (entries without a request keep whatever the operand held: their rows are never read)
+int32_t step_serve_projected(gigl_dist_plan* p, int, const DistArgs&) {
+  gigl_ctx* ctx = p->ctx;
+  const uint32_t world = (uint32_t)p->world;
+  const int64_t na = (int64_t)world * p->pull_cap, nb = (int64_t)world * p->pull_cap_b;
+  hipLaunchKernelGGL(serve_rows_f32_kernel, dim3((unsigned)grid256(na * 64)), dim3(256), 0, ctx->stream, p->ids_r, na, world,
+                     p->feat->rows, p->feat->n, p->feat->d, p->feat->dtype, p->stage);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  int32_t rc = gigl_linear(ctx, p->stage, p->wl0, nullptr, p->n_entries_dev, na, p->dims[0], p->dims[1], 0, (float*)p->rows_s);
+  if (rc != GIGL_OK) return rc;
+  hipLaunchKernelGGL(serve_rows_f32_kernel, dim3((unsigned)grid256(nb * 64)), dim3(256), 0, ctx->stream, p->idsb_r, nb, world,
+                     p->feat->rows, p->feat->n, p->feat->d, p->feat->dtype, p->stage);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  rc = gigl_linear(ctx, p->stage, p->wr0, nullptr, p->n_entries_dev + 1, nb, p->dims[0], p->dims[1], 0, (float*)p->rowsb_s);
+  if (rc != GIGL_OK) return rc;
+  rc = comm_exchange_rows(p->comm, p->rows_s, p->rows_r, p->pull_cap * p->row_bytes, p->req_counts, p->pull_counts, p->row_bytes,
+                          false);
+  return rc != GIGL_OK ? rc : comm_exchange(p->comm, p->rowsb_s, p->rowsb_r, p->pull_cap_b * p->row_bytes);
+}
+
+int32_t step_check_peers(gigl_dist_plan* p, int, const DistArgs&) {
+  if (p->peers_ready) return GIGL_OK;
+  return gigl_fail(p->ctx, GIGL_E_INVALID_ARG, "peer-mapped plan: the ranks' tables were not set (gigl_dist_plan_set_peer_tables)");
+}
+
+int32_t step_fold_overflow(gigl_dist_plan* p, int, const DistArgs&) {
+  hipLaunchKernelGGL(fold_overflow_kernel, dim3(1), dim3(64), 0, p->ctx->stream, p->un.meta, (const int32_t* const*)p->flag_ptrs,
+                     p->n_flags, p->hops, (int32_t)(p->act_rows < 0x7FFFFFFF ? p->act_rows : 0x7FFFFFFF));
+  GIGL_HIP_CHECK(p->ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+// ---- forward over the union graph.  Layer l computes the nodes of level <= hops-1-l from the rows of level <= hops-l
+struct LayerRows {
+  const int32_t* n_rows;
+  int64_t rows_cap;
+  int act;
+};
+LayerRows layer_rows(const gigl_dist_plan* p, int l) {
+  const int L = p->hops;
+  return {level_count(p, L - 1 - l), level_rows(p, L - 1 - l), (l < L - 1 || p->act_last) ? 1 : 0};
+}
+
+// the first GAT layer from the input side: the pulled rows sit in the receive buffer, local node i -> row pos[i]
+int32_t step_gat_input(gigl_dist_plan* p, int, const DistArgs&) {
+  const LayerRows r = layer_rows(p, 0);
+  return gigl_gat_input_layer_fused(p->ctx, p->rows_r, p->feat->dtype, p->dims[0], (const uint32_t*)p->pos, nullptr, p->w[0],
+                                    p->att_src[0], p->att_dst[0], p->heads[0], p->channels[0], p->slope, p->un.rowptr,
+                                    p->un.rowend, p->un.col, r.n_rows, r.rows_cap, p->bias[0], r.act, p->gat_scratch, p->hbuf[0]);
+}
+
+// GAT layer l >= 1, first half: hw = h W^T of its source rows (the rows layer l - 1 computed)
+int32_t step_gat_project(gigl_dist_plan* p, int l, const DistArgs&) {
+  return gigl_linear(p->ctx, p->hbuf[(l - 1) & 1], p->w[l], nullptr, level_count(p, p->hops - l), level_rows(p, p->hops - l),
+                     p->dims[l], p->dims[l + 1], 0, p->hw);
+}
+
+// GAT layer l >= 1, second half: attention over hw into hbuf[l & 1]
+int32_t step_gat_attend(gigl_dist_plan* p, int l, const DistArgs&) {
+  const LayerRows r = layer_rows(p, l);
+  return gigl_gat_aggregate(p->ctx, p->hw, p->att_src[l], p->att_dst[l], p->heads[l], p->channels[l], p->slope, 1, p->un.rowptr,
+                            p->un.rowend, p->un.col, level_count(p, p->hops - l), level_rows(p, p->hops - l), r.n_rows, r.rows_cap,
+                            p->bias[l], r.act, p->alpha_scratch, p->hbuf[l & 1]);
+}
+
+// the first SAGE layer over owner-projected rows: the reduction of the W_l x rows, then + W_r x + bias
+int32_t step_sage_owner_projected(gigl_dist_plan* p, int, const DistArgs&) {
+  const LayerRows r = layer_rows(p, 0);
+  const int dout = p->dims[1];
+  const int32_t rc = gigl_gather_reduce(p->ctx, p->rows_r, GIGL_DTYPE_F32, dout, (const uint32_t*)p->pos, p->un.rowptr, p->un.rowend,
+                                        p->un.col, r.n_rows, r.rows_cap, p->aggr, p->abuf);
+  if (rc != GIGL_OK) return rc;
+  hipLaunchKernelGGL(projected_layer_kernel, dim3((unsigned)grid256(r.rows_cap * dout)), dim3(256), 0, p->ctx->stream, p->abuf,
+                     (const float*)p->rowsb_r, p->posb, p->bias[0], dout, r.act, r.n_rows, r.rows_cap, p->hbuf[0]);
+  GIGL_HIP_CHECK(p->ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+// the first SAGE layer of a peer-mapped plan: every source by its global id (inner rows through un.nodes, leaf rows as
+// they are), read from its owner's table — pre-projected rows: the whole layer in one reduction; raw rows: the reduction
+int32_t step_sage_peer_projected_input(gigl_dist_plan* p, int, const DistArgs&) {
+  const LayerRows r = layer_rows(p, 0);
+  const int dout = p->dims[1];
+  return gigl_gather_project_mixed(p->ctx, nullptr, nullptr, dout, dout, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col, r.n_rows,
+                                   r.rows_cap, p->aggr, level_count(p, p->hops - 2), p->bias[0], r.act, p->hbuf[0],
+                                   p->has_hot ? p->slot_map : nullptr, (const float*)p->hot_rows, nullptr, 2 * dout, nullptr,
+                                   p->world, p->rank, (const float* const*)p->peers_dev);
+}
+int32_t step_sage_reduce_peer(gigl_dist_plan* p, int, const DistArgs&) {
+  const LayerRows r = layer_rows(p, 0);
+  return gigl_gather_reduce_mixed(p->ctx, nullptr, p->feat->dtype, p->dims[0], p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col,
+                                  r.n_rows, r.rows_cap, p->aggr, level_count(p, p->hops - 2), p->abuf, 0,
+                                  p->has_hot ? p->slot_map : nullptr, p->hot_rows, nullptr, 0, p->world, p->rank, p->peers_dev);
+}
+
+// the first SAGE layer over pulled pre-projected rows: one reduction over W_l x rows (receive buffer / own table / hot
+// rows) + W_r x + bias
+int32_t step_sage_projected_input(gigl_dist_plan* p, int, const DistArgs&) {
+  const LayerRows r = layer_rows(p, 0);
+  const int dout = p->dims[1];
+  return gigl_gather_project_mixed(p->ctx, (const float*)p->rows_r, (const float*)p->rowsb_r, dout, dout, (const uint32_t*)p->pos,
+                                   p->un.rowptr, p->un.rowend, p->un.col, r.n_rows, r.rows_cap, p->aggr, level_count(p, p->hops - 2),
+                                   p->bias[0], r.act, p->hbuf[0], p->slot_map, (const float*)p->hot_rows, p->preproj, 2 * dout,
+                                   p->posb, p->own_in_place ? p->world : 0, p->rank);
+}
+
+// the first SAGE layer's reduction over pulled raw rows — dense: rows of level hops-1 hold global ids, located through
+// slot_map (own rows in the feature table, hot rows in theirs); generic: every source through pos[]
+int32_t step_sage_reduce_dense(gigl_dist_plan* p, int, const DistArgs&) {
+  const LayerRows r = layer_rows(p, 0);
+  return gigl_gather_reduce_mixed(p->ctx, p->rows_r, p->feat->dtype, p->dims[0], (const uint32_t*)p->pos, p->un.rowptr, p->un.rowend,
+                                  p->un.col, r.n_rows, r.rows_cap, p->aggr, level_count(p, p->hops - 2), p->abuf, 0, p->slot_map,
+                                  p->hot_rows, p->feat->rows, 0, p->own_in_place ? p->world : 0, p->rank);
+}
+int32_t step_sage_reduce_pulled(gigl_dist_plan* p, int, const DistArgs&) {
+  const LayerRows r = layer_rows(p, 0);
+  return gigl_gather_reduce(p->ctx, p->rows_r, p->feat->dtype, p->dims[0], (const uint32_t*)p->pos, p->un.rowptr, p->un.rowend,
+                            p->un.col, r.n_rows, r.rows_cap, p->aggr, p->abuf);
+}
+
+// SAGE layer l >= 1, first half: the reduced rows of the previous layer's output, row-major [reduced | self] into abuf
+int32_t step_sage_reduce(gigl_dist_plan* p, int l, const DistArgs&) {
+  const LayerRows r = layer_rows(p, l);
+  return gigl_gather_reduce(p->ctx, p->hbuf[(l - 1) & 1], GIGL_DTYPE_F32, p->dims[l], nullptr, p->un.rowptr, p->un.rowend, p->un.col,
+                            r.n_rows, r.rows_cap, p->aggr, p->abuf);
+}
+
+// SAGE layer l, second half: act([reduced | self] W^T + b) into hbuf[l & 1], row-major
+int32_t step_sage_project(gigl_dist_plan* p, int l, const DistArgs&) {
+  const LayerRows r = layer_rows(p, l);
+  return gigl_linear(p->ctx, p->abuf, p->w[l], p->bias[l], r.n_rows, r.rows_cap, 2 * p->dims[l], p->dims[l + 1], r.act, p->hbuf[l & 1]);
+}
+
+// layers >= 1 as in the one-call plan (pipeline.hip): the gather writes the reduced half only, in the projection's tiled
+// operand layout; the projection reads the self half from the previous layer's rows (two-source operand)
+int32_t step_sage_reduce_tiled(gigl_dist_plan* p, int l, const DistArgs&) {
+  const LayerRows r = layer_rows(p, l);
+  const int d = p->dims[l];
+  return gigl_gather_reduce_mixed(p->ctx, p->hbuf[(l - 1) & 1], GIGL_DTYPE_F32, d, nullptr, p->un.rowptr, p->un.rowend, p->un.col,
+                                  r.n_rows, r.rows_cap, p->aggr, nullptr, p->abuf, (d + 31) / 32, nullptr, nullptr, nullptr, 1);
+}
+int32_t step_sage_project_tiled(gigl_dist_plan* p, int l, const DistArgs&) {
+  const LayerRows r = layer_rows(p, l);
+  const int d = p->dims[l];
+  return gigl_linear_tiled(p->ctx, p->abuf, p->w[l], p->bias[l], r.n_rows, r.rows_cap, 2 * d, p->dims[l + 1], r.act, p->hbuf[l & 1],
+                           p->hbuf[(l - 1) & 1], nullptr, d, d, nullptr);
+}
+
+// one row per root into the caller's `out` (a failed step must not hand out the previous step's activations as
+// embeddings: its rows are NaN)
+int32_t step_roots(gigl_dist_plan* p, int, const DistArgs& a) {
+  const int L = p->hops;
+  gigl_take_rows(p->ctx->stream, p->hbuf[(L - 1) & 1], p->un.root_local, p->b, p->dims[L], p->un.meta, a.out);
+  GIGL_HIP_CHECK(p->ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+// The ordered steps of a call, decided ONCE from the plan's route: every input of the decision — transport, world, kind,
+// union flavour, projection flavour, peer routes, overlap, layer layout — is fixed at creation (the setters change
+// arguments, pointers and readiness flags, never a launcher).  Phases 2k / 2k+1: requester / owner side of hop k;
+// 2L: union graph + feature requests; 2L+1: owners serve the rows; 2L+2: forward.  A phase may list nothing
+void dist_build_steps(gigl_dist_plan* p) {
+  const int L = p->hops;
+  const bool solo = p->world == 1 && comm_self_in_place(p->comm);
+  const bool peer_hops = p->peer_sample && p->world > 1;
+  const bool lone_hops = (solo && !p->overlap) || peer_hops;       // the whole tree in phase 0, no collective
+  const bool lone_pull = p->world == 1 && pull_self_in_place(p);   // owns every row: nothing to claim, request or serve
+  p->resp_in_place = p->overlap || solo;
+  int n = 0;
+  auto add = [&](int phase, decltype(DistStep::run) run, int k = 0) { p->steps[n++] = DistStep{run, k, phase}; };
+  add(0, step_clear);
+  if (lone_hops) add(0, peer_hops ? step_sample_peer : step_sample_lone);
+  for (int k = 0; k < L && !lone_hops; ++k) {
+    if (k > 0) add(2 * k, step_scatter, k - 1);
+    add(2 * k, step_bucket_hop, k);
+    if (p->overlap) add(2 * k, step_expand_own, k);
+    add(2 * k, step_exchange_requests, k);
+    add(2 * k + 1, p->overlap ? step_expand_peers : step_expand_requests, k);
+    add(2 * k + 1, step_exchange_answers, k);
   }
-  if (phase < 2 * L) {
-    // ---- owner: expand the requests of every peer on this shard
-    const int k = phase >> 1;
-    const int32_t hash_add = (int32_t)((uint32_t)seed * (uint32_t)(k + 1));
-    // (a one-rank world answers itself: straight into the receive buffer, no copy of the whole answer block)
-    const bool solo = world == 1 && comm_self_in_place(p->comm);
-    if (p->overlap) {  // the peers' blocks (before and after the own one); the own block's answers are the side stream's
-      const int64_t cap = p->cap[k], f = p->fan[k];
-      if (p->rank > 0) {
-        rc = gigl_expand_frontier(ctx, p->shard, p->rq_nodes_r[k], p->rq_ksum_r[k], (int64_t)p->rank * cap, p->fan[k],
-                                  hash_add, p->world, p->mwe, p->resp_s[k], p->own_cnt);
-        if (rc != GIGL_OK) return rc;
-      }
-      if (p->rank + 1 < p->world) {
-        const int64_t off = (int64_t)(p->rank + 1) * cap;
-        rc = gigl_expand_frontier(ctx, p->shard, p->rq_nodes_r[k] + off, p->rq_ksum_r[k] + off,
-                                  (int64_t)(p->world - p->rank - 1) * cap, p->fan[k], hash_add, p->world, p->mwe,
-                                  p->resp_s[k] + off * f, p->own_cnt);
-        if (rc != GIGL_OK) return rc;
-      }
-      GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, p->ev_own[k], 0));
-      return comm_exchange(p->comm, p->resp_s[k], p->resp_r[k], cap * f * 4, true);
-    }
-    rc = gigl_expand_frontier(ctx, p->shard, p->rq_nodes_r[k], p->rq_ksum_r[k], (int64_t)world * p->cap[k], p->fan[k],
-                              hash_add, p->world, p->mwe, solo ? p->resp_r[k] : p->resp_s[k], p->own_cnt);
-    if (rc != GIGL_OK) return rc;
-    return comm_exchange(p->comm, p->resp_s[k], p->resp_r[k], p->cap[k] * p->fan[k] * 4, solo);
+  if (!lone_hops) add(2 * L, step_scatter, L - 1);
+  const bool inner_pull = p->project || (p->preproj && !p->peer);  // a second pull: the inner nodes' own (W_r x) rows
+  if (p->dense) {
+    add(2 * L, step_union_dense);
+    if (!p->peer)  // (a peer-mapped plan reads rows in place, from whichever rank holds them: nothing to request)
+      add(2 * L, lone_pull ? (inner_pull ? step_claim_locate<false, true> : step_claim_locate<false, false>)
+                           : (inner_pull ? step_claim_locate<true, true> : step_claim_locate<true, false>));
+  } else {
+    add(2 * L, step_union_generic);
+    if (inner_pull) add(2 * L, step_bucket_inner);
   }
-  if (phase == 2 * L) {
-    // ---- requester: last scatter, union graph, feature requests
-    if (!lone_hops) {
-      rc = scatter_hop(p, L - 1, roots);
-      if (rc != GIGL_OK) return rc;
-    }
-    if (p->dense) {
-      rc = gigl_union_build_impl(ctx, roots, &p->tree, p->group_roots, &p->un, 1 | (p->shard->multi ? 2 : 0));
-      if (rc != GIGL_OK) return rc;
-      if (++p->tag == DIST_HOT_STAMP) {  // (the tags are used up: forget every stamp but the hot marks)
-        hipLaunchKernelGGL(hot_unmark_kernel, dim3((unsigned)grid256(p->n_global)), dim3(256), 0, st, p->stamp, p->n_global, 0);
-        p->tag = 1;
-      }
-      if (p->peer) return GIGL_OK;  // (rows are read in place, from whichever rank holds them: nothing to request)
-      const int32_t* n_inner = p->un.meta + GIGL_META_LEVEL0 + (L - 1);
-      const int32_t own = p->own_in_place ? p->rank : -1;
-      const bool self_ip = pull_self_in_place(p);
-      const bool lone = world == 1 && self_ip;  // a lone rank owns every row: nothing to claim, request or serve
-      gigl_prof_scope ps(ctx, GIGL_K_DIST_PREP);
-      // the inner nodes first (their own rows: pos), then every sampled leaf
-      if (!lone) {
-        hipLaunchKernelGGL(claim_bucket_kernel, dim3((unsigned)grid256(p->act_rows)), dim3(256), 0, st, p->un.nodes,
-                           p->act_rows, n_inner, world, p->pull_cap, p->ids_s, p->pull_counts, p->stamp, p->tag,
-                           p->slot_map, p->n_global, own);
-        hipLaunchKernelGGL(claim_bucket_kernel, dim3((unsigned)grid256(p->last_slots)), dim3(256), 0, st,
-                           (const uint32_t*)p->tree.nbr[L - 1], p->last_slots, (const int32_t*)nullptr, world, p->pull_cap,
-                           p->ids_s, p->pull_counts, p->stamp, p->tag, p->slot_map, p->n_global, own);
-      }
-      hipLaunchKernelGGL(pos_from_map_kernel, dim3((unsigned)grid256(p->act_rows)), dim3(256), 0, st, p->un.nodes, n_inner,
-                         p->act_rows, p->slot_map, p->n_global, p->pos, world, own);
-      if (p->preproj)  // the inner nodes' own W_r x rows: a second, small pull (a rank's own nodes: read in place)
-        hipLaunchKernelGGL(bucket_kernel, dim3((unsigned)grid256(p->act_rows)), dim3(256), 0, st, p->un.nodes,
-                           (const uint32_t*)nullptr, p->act_rows, n_inner, world, p->pull_cap_b, p->idsb_s,
-                           (uint32_t*)nullptr, (int32_t*)nullptr, p->posb, p->pullb_counts, 0u, (uint32_t*)nullptr,
-                           (uint32_t*)nullptr, own);
-      GIGL_HIP_CHECK(ctx, hipGetLastError());
-      if (lone) return GIGL_OK;
-      rc = comm_exchange(p->comm, p->ids_s, p->ids_r, p->pull_cap * 4, self_ip);
-      if (rc == GIGL_OK) rc = comm_exchange(p->comm, p->pull_counts, p->req_counts, 4, self_ip);  // (the row blocks' sizes)
-      if (rc == GIGL_OK && p->preproj) rc = comm_exchange(p->comm, p->idsb_s, p->idsb_r, p->pull_cap_b * 4, self_ip);
-      return rc;
-    }
-    rc = gigl_union_build_groups(ctx, roots, &p->tree, p->group_roots, &p->un);
-    if (rc != GIGL_OK) return rc;
-    hipLaunchKernelGGL(bucket_kernel, dim3((unsigned)grid256(p->un.cap_nodes)), dim3(256), 0, st, p->un.nodes,
-                       (const uint32_t*)nullptr, p->un.cap_nodes, p->un.meta + GIGL_META_N_NODES, world, p->pull_cap,
-                       p->ids_s, (uint32_t*)nullptr, (int32_t*)nullptr, p->pos, p->pull_counts, 0u, (uint32_t*)nullptr,
-                       (uint32_t*)nullptr);
+  if (!p->peer && !lone_pull) {
+    add(2 * L, step_exchange_ids);
+    if (inner_pull) add(2 * L, step_exchange_inner_ids);
     if (p->project) {
-      hipLaunchKernelGGL(bucket_kernel, dim3((unsigned)grid256(p->act_rows)), dim3(256), 0, st, p->un.nodes,
-                         (const uint32_t*)nullptr, p->act_rows, p->un.meta + GIGL_META_LEVEL0 + (L - 1), world,
-                         p->pull_cap_b, p->idsb_s, (uint32_t*)nullptr, (int32_t*)nullptr, p->posb, p->pullb_counts,
-                         0u, (uint32_t*)nullptr, (uint32_t*)nullptr);
+      add(2 * L + 1, step_serve_projected);
+    } else {
+      add(2 * L + 1, step_serve_rows);
+      if (inner_pull) add(2 * L + 1, step_serve_inner_rows);
     }
-    GIGL_HIP_CHECK(ctx, hipGetLastError());
-    rc = comm_exchange(p->comm, p->ids_s, p->ids_r, p->pull_cap * 4);
-    if (rc == GIGL_OK) rc = comm_exchange(p->comm, p->pull_counts, p->req_counts, 4);  // (the row blocks' sizes)
-    if (rc == GIGL_OK && p->project) rc = comm_exchange(p->comm, p->idsb_s, p->idsb_r, p->pull_cap_b * 4);
-    return rc;
   }
-  if (phase == 2 * L + 1) {
-    // ---- owner: the requested rows, gathered straight into the send buffer (or projected into it)
-    const int64_t na = (int64_t)world * p->pull_cap, nb = (int64_t)world * p->pull_cap_b;
-    if (p->peer) return GIGL_OK;
-    if (!p->project) {
-      const bool in_place = comm_self_in_place(p->comm);
-      if (world == 1 && pull_self_in_place(p)) return GIGL_OK;  // (a lone rank requested nothing)
-      const char* table = p->preproj ? (const char*)p->preproj : (const char*)p->feat->rows;
-      const int64_t stride = p->preproj ? 2 * p->row_bytes : 0;  // ([W_l x | W_r x]: a served row is half a table row)
-      rc = serve_rows(p, p->ids_r, na, table, stride, (char*)p->rows_s, (int64_t)p->rank * p->pull_cap,
-                      (int64_t)(p->rank + 1) * p->pull_cap, in_place ? (char*)p->rows_r : (char*)nullptr);
-      if (rc != GIGL_OK) return rc;
-      // only the requested rows travel: the head of each block (comm_exchange_rows)
-      rc = comm_exchange_rows(p->comm, p->rows_s, p->rows_r, p->pull_cap * p->row_bytes, p->req_counts, p->pull_counts,
-                              p->row_bytes, in_place);
-      if (rc != GIGL_OK || !p->preproj) return rc;
-      rc = serve_rows(p, p->idsb_r, nb, table + p->row_bytes, stride, (char*)p->rowsb_s, (int64_t)0, (int64_t)0, (char*)nullptr);
-      if (rc != GIGL_OK) return rc;
-      return comm_exchange(p->comm, p->rowsb_s, p->rowsb_r, p->pull_cap_b * p->row_bytes, pull_self_in_place(p));
-    }
-    // (entries without a request keep whatever the operand held: their output rows are never read)
-    hipLaunchKernelGGL(serve_rows_f32_kernel, dim3((unsigned)grid256(na * 64)), dim3(256), 0, st, p->ids_r, na, world,
-                       p->feat->rows, p->feat->n, p->feat->d, p->feat->dtype, p->stage);
-    GIGL_HIP_CHECK(ctx, hipGetLastError());
-    rc = gigl_linear(ctx, p->stage, p->wl0, nullptr, p->n_entries_dev, na, p->dims[0], p->dims[1], 0,
-                     (float*)p->rows_s);
-    if (rc != GIGL_OK) return rc;
-    hipLaunchKernelGGL(serve_rows_f32_kernel, dim3((unsigned)grid256(nb * 64)), dim3(256), 0, st, p->idsb_r, nb, world,
-                       p->feat->rows, p->feat->n, p->feat->d, p->feat->dtype, p->stage);
-    GIGL_HIP_CHECK(ctx, hipGetLastError());
-    rc = gigl_linear(ctx, p->stage, p->wr0, nullptr, p->n_entries_dev + 1, nb, p->dims[0], p->dims[1], 0,
-                     (float*)p->rowsb_s);
-    if (rc != GIGL_OK) return rc;
-    rc = comm_exchange_rows(p->comm, p->rows_s, p->rows_r, p->pull_cap * p->row_bytes, p->req_counts, p->pull_counts,
-                            p->row_bytes, false);
-    if (rc == GIGL_OK) rc = comm_exchange(p->comm, p->rowsb_s, p->rowsb_r, p->pull_cap_b * p->row_bytes);
-    return rc;
-  }
-  // ---- requester: forward over the union graph, one row per root
-  if (p->peer && !p->peers_ready)
-    return gigl_fail(ctx, GIGL_E_INVALID_ARG, "peer-mapped plan: the ranks' tables were not set (gigl_dist_plan_set_peer_tables)");
-  hipLaunchKernelGGL(fold_overflow_kernel, dim3(1), dim3(64), 0, st, p->un.meta, (const int32_t* const*)p->flag_ptrs,
-                     p->n_flags, L, (int32_t)(p->act_rows < 0x7FFFFFFF ? p->act_rows : 0x7FFFFFFF));
-  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  if (p->peer) add(2 * L + 2, step_check_peers);
+  add(2 * L + 2, step_fold_overflow);
   for (int l = 0; l < L; ++l) {
-    const int32_t* n_rows = p->un.meta + GIGL_META_LEVEL0 + (L - 1 - l);
-    int64_t rows_cap = 0, width = p->b;
-    for (int i = 0; i <= L - 1 - l; ++i) {
-      rows_cap += width;
-      width *= p->fan[i];
-    }
-    const int act = (l < L - 1 || p->act_last) ? 1 : 0;
     if (p->kind == 1) {
-      if (l == 0) {  // the pulled rows sit in the receive buffer: local node i -> row pos[i]
-        rc = gigl_gat_input_layer_fused(ctx, p->rows_r, p->feat->dtype, p->dims[0], (const uint32_t*)p->pos, nullptr,
-                                        p->w[0], p->att_src[0], p->att_dst[0], p->heads[0], p->channels[0], p->slope,
-                                        p->un.rowptr, p->un.rowend, p->un.col, n_rows, rows_cap, p->bias[0], act,
-                                        p->gat_scratch, p->hbuf[0]);
-        if (rc != GIGL_OK) return rc;
-        continue;
+      if (l == 0) {
+        add(2 * L + 2, step_gat_input);
+      } else {
+        add(2 * L + 2, step_gat_project, l);
+        add(2 * L + 2, step_gat_attend, l);
       }
-      const int32_t* n_src = p->un.meta + GIGL_META_LEVEL0 + (L - l);  // rows layer l - 1 computed
-      const int64_t src_cap = rows_cap + width;
-      rc = gigl_linear(ctx, p->hbuf[(l - 1) & 1], p->w[l], nullptr, n_src, src_cap, p->dims[l], p->dims[l + 1], 0, p->hw);
-      if (rc != GIGL_OK) return rc;
-      rc = gigl_gat_aggregate(ctx, p->hw, p->att_src[l], p->att_dst[l], p->heads[l], p->channels[l], p->slope, 1,
-                              p->un.rowptr, p->un.rowend, p->un.col, n_src, src_cap, n_rows, rows_cap, p->bias[l], act,
-                              p->alpha_scratch, p->hbuf[l & 1]);
-      if (rc != GIGL_OK) return rc;
-      continue;
+    } else if (l == 0 && p->project) {
+      add(2 * L + 2, step_sage_owner_projected);
+    } else if (l == 0 && p->preproj) {
+      add(2 * L + 2, p->peer ? step_sage_peer_projected_input : step_sage_projected_input);
+    } else if (l > 0 && p->tiled_layers) {
+      add(2 * L + 2, step_sage_reduce_tiled, l);
+      add(2 * L + 2, step_sage_project_tiled, l);
+    } else {
+      add(2 * L + 2, l > 0 ? step_sage_reduce : p->peer ? step_sage_reduce_peer : p->dense ? step_sage_reduce_dense
+                                                                                          : step_sage_reduce_pulled, l);
+      add(2 * L + 2, step_sage_project, l);
     }
-    if (l == 0 && p->project) {
-      const int dout = p->dims[1];
-      rc = gigl_gather_reduce(ctx, p->rows_r, GIGL_DTYPE_F32, dout, (const uint32_t*)p->pos, p->un.rowptr, p->un.rowend,
-                              p->un.col, n_rows, rows_cap, p->aggr, p->abuf);
-      if (rc != GIGL_OK) return rc;
-      hipLaunchKernelGGL(projected_layer_kernel, dim3((unsigned)grid256(rows_cap * dout)), dim3(256), 0, st, p->abuf,
-                         (const float*)p->rowsb_r, p->posb, p->bias[0], dout, act, n_rows, rows_cap, p->hbuf[0]);
-      GIGL_HIP_CHECK(ctx, hipGetLastError());
-      continue;
-    }
-    if (l == 0 && p->peer) {
-      // every source by its global id (inner rows through un.nodes, leaf rows as they are), read from its owner's table
-      const int32_t* hot_map = p->has_hot ? p->slot_map : nullptr;
-      const int32_t* n_local = p->un.meta + GIGL_META_LEVEL0 + (L - 2);
-      if (p->preproj) {
-        const int dout = p->dims[1];
-        rc = gigl_gather_project_mixed(ctx, nullptr, nullptr, dout, dout, p->un.nodes, p->un.rowptr, p->un.rowend, p->un.col,
-                                       n_rows, rows_cap, p->aggr, n_local, p->bias[0], act, p->hbuf[0], hot_map,
-                                       (const float*)p->hot_rows, nullptr, 2 * dout, nullptr, p->world, p->rank,
-                                       (const float* const*)p->peers_dev);
-        if (rc != GIGL_OK) return rc;
-        continue;
-      }
-      rc = gigl_gather_reduce_mixed(ctx, nullptr, p->feat->dtype, p->dims[0], p->un.nodes, p->un.rowptr, p->un.rowend,
-                                    p->un.col, n_rows, rows_cap, p->aggr, n_local, p->abuf, 0, hot_map, p->hot_rows, nullptr,
-                                    0, p->world, p->rank, p->peers_dev);
-      if (rc != GIGL_OK) return rc;
-      rc = gigl_linear(ctx, p->abuf, p->w[0], p->bias[0], n_rows, rows_cap, 2 * p->dims[0], p->dims[1], act, p->hbuf[0]);
-      if (rc != GIGL_OK) return rc;
-      continue;
-    }
-    if (l == 0 && p->preproj) {  // one reduction over W_l x rows (receive buffer / own table / hot rows) + W_r x + bias
-      const int dout = p->dims[1];
-      rc = gigl_gather_project_mixed(ctx, (const float*)p->rows_r, (const float*)p->rowsb_r, dout, dout,
-                                     (const uint32_t*)p->pos, p->un.rowptr, p->un.rowend, p->un.col, n_rows, rows_cap,
-                                     p->aggr, p->un.meta + GIGL_META_LEVEL0 + (L - 2), p->bias[0], act, p->hbuf[0],
-                                     p->slot_map, (const float*)p->hot_rows, p->preproj, 2 * dout, p->posb,
-                                     p->own_in_place ? p->world : 0, p->rank);
-      if (rc != GIGL_OK) return rc;
-      continue;
-    }
-    if (l > 0 && p->tiled_layers) {
-      // layers >= 1 as in the one-call plan (pipeline.hip): the gather writes the reduced half only, in the projection's
-      // tiled operand layout; the projection reads the self half from the previous layer's rows (two-source operand)
-      const int d = p->dims[l];
-      rc = gigl_gather_reduce_mixed(ctx, p->hbuf[(l - 1) & 1], GIGL_DTYPE_F32, d, nullptr, p->un.rowptr, p->un.rowend,
-                                    p->un.col, n_rows, rows_cap, p->aggr, nullptr, p->abuf, (d + 31) / 32, nullptr, nullptr,
-                                    nullptr, 1);
-      if (rc != GIGL_OK) return rc;
-      rc = gigl_linear_tiled(ctx, p->abuf, p->w[l], p->bias[l], n_rows, rows_cap, 2 * d, p->dims[l + 1], act,
-                             p->hbuf[l & 1], p->hbuf[(l - 1) & 1], nullptr, d, d, nullptr);
-      if (rc != GIGL_OK) return rc;
-      continue;
-    }
-    if (l == 0 && p->dense)  // rows of level L-1 hold global ids: located through slot_map
-      rc = gigl_gather_reduce_mixed(ctx, p->rows_r, p->feat->dtype, p->dims[0], (const uint32_t*)p->pos, p->un.rowptr,
-                                    p->un.rowend, p->un.col, n_rows, rows_cap, p->aggr,
-                                    p->un.meta + GIGL_META_LEVEL0 + (L - 2), p->abuf, 0, p->slot_map, p->hot_rows,
-                                    p->feat->rows, 0, p->own_in_place ? p->world : 0, p->rank);
-    else if (l == 0)
-      rc = gigl_gather_reduce(ctx, p->rows_r, p->feat->dtype, p->dims[0], (const uint32_t*)p->pos, p->un.rowptr,
-                              p->un.rowend, p->un.col, n_rows, rows_cap, p->aggr, p->abuf);
-    else
-      rc = gigl_gather_reduce(ctx, p->hbuf[(l - 1) & 1], GIGL_DTYPE_F32, p->dims[l], nullptr, p->un.rowptr, p->un.rowend,
-                              p->un.col, n_rows, rows_cap, p->aggr, p->abuf);
-    if (rc != GIGL_OK) return rc;
-    rc = gigl_linear(ctx, p->abuf, p->w[l], p->bias[l], n_rows, rows_cap, 2 * p->dims[l], p->dims[l + 1], act,
-                     p->hbuf[l & 1]);
+  }
+  add(2 * L + 2, step_roots);
+  p->n_steps = n;
+}
+
+int32_t phase_impl(gigl_dist_plan* p, int phase, const uint32_t* roots, int32_t seed, float* out) {
+  const DistArgs a{roots, seed, out};
+  for (int s = 0; s < p->n_steps; ++s) {
+    if (p->steps[s].phase != phase) continue;
+    const int32_t rc = p->steps[s].run(p, p->steps[s].k, a);
     if (rc != GIGL_OK) return rc;
   }
-  const int dout = p->dims[L];
-  // (a failed step must not hand out the previous step's activations as embeddings: its rows are NaN)
-  gigl_take_rows(st, p->hbuf[(L - 1) & 1], p->un.root_local, p->b, dout, p->un.meta, out);
-  GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
 }
 
@@ -1479,12 +1558,7 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
                hipMemsetAsync(p->slot_map, 0, (size_t)p->n_global * 4, ctx->stream) != hipSuccess))
       ok = false;
   }
-  int64_t act_rows = 0, width = b;
-  for (int k = 0; k < hops; ++k) {
-    act_rows += width;
-    width *= fanouts[k];
-  }
-  p->act_rows = act_rows;
+  const int64_t act_rows = p->act_rows = level_rows(p, hops - 1);
   // ---- feature pull.  Rows are the expensive bytes: the bucket capacity per peer is the caller's bound when given
   // (calibrated on warm-up steps, see GIGL_STATS_PULL_BUCKET_MAX), else the worst case / world + 10 %
   int64_t pc = opts && opts->pull_cap > 0 ? opts->pull_cap : (int64_t)std::ceil((double)cap_nodes / (double)W * 1.1) + 512;
@@ -1579,6 +1653,7 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
   hipMemsetAsync(p->ids_r, 0xFF, (size_t)W * pc * 4, ctx->stream);
   if (p->idsb_r) hipMemsetAsync(p->idsb_r, 0xFF, (size_t)W * p->pull_cap_b * 4, ctx->stream);
   hipStreamSynchronize(ctx->stream);
+  dist_build_steps(p);
   *out = p;
   return GIGL_OK;
 }

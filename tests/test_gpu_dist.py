@@ -163,6 +163,79 @@ def test_device_side_exchange_over_rccl_single_rank(graph):
         dist.destroy_process_group()
 
 
+def _bucket_case(world, m):
+    """frontier of m slots: ids from [0, 50 * world), every 7th slot empty, then — where they fit — one aligned run of 64
+    equal ids (a wave with one owner) and one of 64 consecutive ids (a wave with min(64, world) owners)"""
+    rng = np.random.default_rng(1000 * world + m)
+    nodes = rng.integers(0, 50 * world, size=m).astype(np.uint32)
+    nodes[6::7] = 0xFFFFFFFF
+    if m >= 64:
+        nodes[0:64] = 7 * world + world // 2
+    if m >= 128:
+        nodes[64:128] = (5 + np.arange(64, dtype=np.uint32)) % (50 * world)
+    ksums = rng.integers(0, 1 << 32, size=m, dtype=np.uint64).astype(np.uint32)
+    return nodes, ksums
+
+
+def _bucket_reference(nodes, ksums, world):
+    """the bucket rule restated: slot i (node v, key sum K, or v without key sums) belongs to owner v % world; per owner
+    the set of (v, K, i), and the counts"""
+    sets = [set() for _ in range(world)]
+    for i, v in enumerate(nodes.tolist()):
+        if v != 0xFFFFFFFF:
+            sets[v % world].add((v, int(ksums[i]) if ksums is not None else v, i))
+    return sets, np.array([len(s) for s in sets], dtype=np.int64)
+
+
+@pytest.mark.parametrize("m", [1, 255, 257, 1000])
+@pytest.mark.parametrize("world", [1, 63, 64, 65, 200])
+def test_frontier_bucket_rule_on_both_position_paths(world, m):
+    """gigl_frontier_bucket against a numpy restatement of its rule, on the LDS-counter path (world <= 64) and on the
+    per-wave path (world > 64), with and without key sums.  An exact-fit capacity: counts, entry sets, no overflow flag,
+    untouched entries stay 0xFFFFFFFF.  One entry short: the flag is raised, the counters still count every slot (they
+    are bumped before the capacity test) and an overfull owner holds `cap` distinct slots of its own."""
+    from gigl_amd.engine import HipEngine
+    eng = HipEngine(0)
+    dev = eng.device
+    nodes, ksums_h = _bucket_case(world, m)
+    d_nodes = torch.from_numpy(nodes.view(np.int32)).to(dev)
+    d_ksums = torch.from_numpy(ksums_h.view(np.int32)).to(dev)
+
+    def run(cap, with_ksums):
+        req = torch.empty((world, 2, cap), dtype=torch.int32, device=dev)
+        slot_idx = torch.full((world, cap), -1, dtype=torch.int32, device=dev)
+        counts = torch.empty(world + 1, dtype=torch.int32, device=dev)
+        eng.frontier_bucket(d_nodes, d_ksums if with_ksums else None, world, cap, req, slot_idx, counts)
+        return req.cpu().numpy().view(np.uint32), slot_idx.cpu().numpy(), counts.cpu().numpy()
+
+    def filled(req, slot_idx, r, k):
+        return list(zip(req[r, 0, :k].tolist(), req[r, 1, :k].tolist(), slot_idx[r, :k].tolist()))
+
+    for with_ksums in (True, False):
+        sets, ref_counts = _bucket_reference(nodes, ksums_h if with_ksums else None, world)
+        most = int(ref_counts.max())
+        assert most >= 1
+        req, slot_idx, counts = run(most, with_ksums)
+        assert np.array_equal(counts[:world], ref_counts)
+        assert counts[world] == 0
+        for r in range(world):
+            k = int(ref_counts[r])
+            assert set(filled(req, slot_idx, r, k)) == sets[r]
+            assert (req[r, :, k:] == 0xFFFFFFFF).all()
+        if most == 1:
+            continue
+        cap = most - 1
+        req, slot_idx, counts = run(cap, with_ksums)
+        assert counts[world] != 0
+        assert np.array_equal(counts[:world], ref_counts)
+        for r in range(world):
+            k = min(int(ref_counts[r]), cap)
+            got = filled(req, slot_idx, r, k)
+            assert len(set(got)) == k and set(got) <= sets[r]
+            assert (req[r, :, k:] == 0xFFFFFFFF).all()
+    eng.close()
+
+
 @pytest.mark.parametrize("world", [1, 3])
 def test_bucketed_feature_pull_all_ranks_in_one_process(world):
     """HipFeaturePuller for every rank of a world inside one process (all_to_all by hand): x == table[ids]"""
