@@ -155,13 +155,12 @@ int32_t comm_exchange(gigl_comm* c, const void* send, void* recv, int64_t bytes,
 // [world], values above the block's capacity are cut to it.  The receiver's tail keeps what it held (the rows behind a
 // count are never read).  RCCL needs the sizes on the host: one small copy + a stream synchronisation per exchange,
 // paid once per call of a plan (many batches); the host-callback transport has a fixed-size contract and moves full
-// blocks.  GIGL_DIST_FIXED_BLOCKS=1: full blocks everywhere (A/B).
+// blocks.
 int32_t comm_exchange_rows(gigl_comm* c, const void* send, void* recv, int64_t bytes, const int32_t* send_units,
                            const int32_t* recv_units, int64_t unit, bool self_in_place) {
-  static const bool fixed = getenv("GIGL_DIST_FIXED_BLOCKS") != nullptr;
   gigl_ctx* ctx = c->ctx;
   if (bytes == 0) return GIGL_OK;
-  if (fixed || c->fixed_blocks || c->kind == GIGL_COMM_CALLBACK || c->world == 1 || !send_units || !recv_units || unit <= 0)
+  if (c->fixed_blocks || c->kind == GIGL_COMM_CALLBACK || c->world == 1 || !send_units || !recv_units || unit <= 0)
     return comm_exchange(c, send, recv, bytes, self_in_place);  // (a single rank: nothing leaves the device)
   const int64_t cap_units = bytes / unit;
   if (c->kind == GIGL_COMM_LOCAL) {
@@ -790,7 +789,7 @@ struct gigl_dist_plan {
   // their parents' rows), ids are claimed through stamp[] and located through slot_map[] (claim_bucket_kernel)
   bool dense = false;
   // dense mode: a rank's OWN rows are never requested, served or copied — the aggregation reads them from the feature
-  // table (GIGL_DIST_COPY_OWN_ROWS=1: through the receive buffer like everybody else's, for measurements)
+  // table (shards of 2^30 nodes and more: through the receive buffer like everybody else's)
   bool own_in_place = false;
   // replicated hot rows (gigl_dist_plan_set_hot_rows)
   bool has_hot = false;  // stamp[] carries DIST_HOT_STAMP marks (and slot_map[] the rows' entries -1-h)
@@ -1483,8 +1482,8 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
   // (... and the leaf-global union numbers a level-1 row's leaves one per lane: second fan-outs past 64 take the generic one,
   // as in the one-call plan, pipeline.hip)
   p->dense = kind == 0 && hops == 2 && !p->project && p->n_global < ((int64_t)1 << 32) && (shard_feat->d & 3) == 0 &&
-             fanouts[1] <= GIGL_FAST_FANOUT && getenv("GIGL_DIST_GENERIC_UNION") == nullptr && !(opts && opts->staged);
-  p->own_in_place = p->dense && shard->n < ((int64_t)1 << 30) && getenv("GIGL_DIST_COPY_OWN_ROWS") == nullptr;
+             fanouts[1] <= GIGL_FAST_FANOUT && !(opts && opts->staged);
+  p->own_in_place = p->dense && shard->n < ((int64_t)1 << 30);
   p->peer = opts && opts->peer_direct != 0;
   if (p->peer && (!p->dense || p->n_global >= ((int64_t)1 << 31) || W > 64))
     return fail(GIGL_E_UNSUPPORTED, "the peer-mapped route needs the dense plan shape (SAGE layers, two hops, second fan-out "
@@ -1621,7 +1620,7 @@ static int32_t dist_plan_create_impl(gigl_comm* comm, gigl_graph* shard, gigl_fe
   const int64_t a_cols = 2 * (int64_t)(max_in > max_out ? max_in : max_out);
   // (+ whole row tiles of 128 and whole K chunks of 32 for the tiled operand of layers >= 1)
   p->abuf = (float*)alloc((size_t)(act_rows + 128) * (a_cols + 64) * 4);
-  p->tiled_layers = kind == 0 && getenv("GIGL_DIST_ROW_MAJOR") == nullptr;
+  p->tiled_layers = kind == 0;
   for (int k = 1; k < hops; ++k)
     if ((dims[k] & 3) != 0 || dims[k] > 2048) p->tiled_layers = false;
   p->hbuf[0] = (float*)alloc((size_t)act_rows * max_out * 4);

@@ -60,7 +60,7 @@ struct gigl_hgt_infer {
   int32_t cap_b = -1;
   uint64_t cap_arena_gen = 0, cap_side_gen = 0;
   // the layers' per-type / per-slot projections as grouped launches (gigl_linear_grouped): device descriptor table, and per
-  // workspace and layer where its K|V, Q and output groups sit in it (GIGL_HGT_NO_GROUPED=1: one launch per product, A/B)
+  // workspace and layer where its K|V, Q and output groups sit in it (output widths that are no multiple of 4: one launch per product)
   gigl_linear_group* groups_dev = nullptr;
   struct GroupRange {
     int kv_off = 0, kv_n = 0, q_off = 0, q_n = 0, o_off = 0, o_n = 0;
@@ -472,7 +472,7 @@ int32_t gigl_hgt_infer_create(gigl_ctx* ctx, gigl_typed_plan* plan, int32_t b_ma
   HGT_ALLOC(p->b_dev, 8);
   HGT_ALLOC(p->groups_dev, (int64_t)2 * m.n_layers * (2 * m.n_slots + 2 * m.n_types));
 #undef HGT_ALLOC
-  p->grouped = (Fo & 3) == 0 && getenv("GIGL_HGT_NO_GROUPED") == nullptr;
+  p->grouped = (Fo & 3) == 0;
   if (p->grouped) {
     rc = hgt_build_groups(p);
     if (rc != GIGL_OK) {

@@ -1097,7 +1097,7 @@ static int32_t plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, in
   }
   auto alloc = [&](size_t bytes) { return plan_alloc(p->owned, bytes); };
   bool ok = true;
-  p->tiled = getenv("GIGL_PLAN_ROW_MAJOR") == nullptr;  // (A/B knob)
+  p->tiled = true;
   p->two_source = getenv("GIGL_PLAN_SELF_COPY") == nullptr;  // (A/B knob: set = gather writes [mean | self])
   for (int k = 0; k < hops; ++k)
     if ((dims[k] & 3) != 0 || dims[k] > 2048) p->tiled = false;
@@ -2649,9 +2649,9 @@ bool lp_fork_setup(gigl_nablp_train_plan* t) {
   for (int i = 0; i < 2 && ok; ++i)
     ok = hipEventCreateWithFlags(&t->ev_fork[i], hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&t->ev_join[i], hipEventDisableTiming) == hipSuccess;
-  const char* w_env = getenv("GIGL_LP_WGRAD_STREAM");  // (=0: the main batch's weight gradients stay in its chain)
-  // (the GAT plan's 768-wide weight gradients fill the GPU and slow the chain beside them: measured, see gat_lp_backward)
-  if (ok && t->kind == 0 && !(w_env && w_env[0] == '0'))
+  // a third stream for the main batch's weight gradients (the GAT plan's 768-wide ones fill the GPU and slow the chain
+  // beside them: measured, see gat_lp_backward)
+  if (ok && t->kind == 0)
     ok = gigl_ctx_create(t->ctx->device, &t->wctx) == GIGL_OK &&
          hipEventCreateWithFlags(&t->ev_w, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&t->ev_wjoin, hipEventDisableTiming) == hipSuccess;

@@ -556,7 +556,7 @@ struct WorkLists {
   uint32_t* items;  // [WORK_LISTS][cap]
   int32_t* count;   // [WORK_LISTS * WORK_CNT_STRIDE]
   int64_t cap;
-  int32_t iters;  // 0: persistent waves; > 0: steps per copy of a wave (expand_rows_kernel)
+  int32_t iters;  // steps per copy of a wave, > 0 (expand_rows_kernel)
   int32_t wgs;    // workgroups of ONE copy of the grid
 };
 
@@ -871,11 +871,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   const int f = a.f;
   uint32_t* lk = s_lk[wave_in_block];
   uint32_t* li = s_li[wave_in_block];
-  // persistent grid (a multiple of WORK_LISTS waves): wave g walks list g % WORK_LISTS, two rows per step
-  // (wl.iters > 0: the grid is `rounds` copies of the persistent one — copy r of a wave walks steps [r iters, (r + 1) iters) of
-  // that wave's sequence and retires, so that other streams' workgroups get wave slots while a hop is expanded; every
-  // copy runs its own prologue)
-  const uint32_t wgs_p = wl.iters > 0 ? (uint32_t)wl.wgs : gridDim.x;
+  // a grid of wl.wgs workgroups (a multiple of WORK_LISTS waves): wave g walks list g % WORK_LISTS, two rows per step.
+  // The launch is `rounds` copies of that grid — copy r of a wave walks steps [r iters, (r + 1) iters) of that wave's
+  // sequence and retires, so that other streams' workgroups get wave slots while a hop is expanded; every copy runs
+  // its own prologue
+  const uint32_t wgs_p = (uint32_t)wl.wgs;
   const uint32_t round = blockIdx.x / wgs_p;
   const uint32_t gw = (blockIdx.x % wgs_p) * 4u + (uint32_t)wave_in_block, n_waves = wgs_p * 4u;
   const uint32_t list = gw % WORK_LISTS, stride = n_waves / WORK_LISTS;
@@ -883,7 +883,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   const uint32_t last_pair = (uint32_t)(wl.cap >> 1) - 1u;  // (cap is a multiple of 256: the pair lies inside the list)
   const uint32_t skip = (uint32_t)a.n_parents;              // (that slot holds a ROW_SKIP descriptor)
   const uint32_t k_first = gw / WORK_LISTS + stride * round * (uint32_t)wl.iters;
-  const uint32_t k_end = wl.iters > 0 ? k_first + stride * (uint32_t)wl.iters : 0xFFFFFFFFu;
+  const uint32_t k_end = k_first + stride * (uint32_t)wl.iters;
   auto vec = [](uint32_t x) -> uint32_t {
     asm("" : "+v"(x));
     return x;
@@ -1285,12 +1285,7 @@ void table_unref(TableOwner* own) {  // g_table_mu held
 // Largest j domain a table may cover.  12.4 B per j: at least 2^30 j (13.3 GB, as sized for a 2-hop MAG240M job) and
 // up to the whole uint32 axis (53 GB) when a quarter of the device's free memory allows it — a scale-30 RMAT job
 // (windows up to ~3.2e9) then never leaves the table path; windows beyond it are hashed directly (same result).
-// GIGL_TABLE_MAX_J overrides (tests).
 uint64_t table_cap_j() {
-  if (const char* e = getenv("GIGL_TABLE_MAX_J")) {
-    const unsigned long long v = strtoull(e, nullptr, 10);
-    if (v >= 64) return (uint64_t)v;
-  }
   uint64_t cap = 1ull << 30;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
@@ -1418,16 +1413,13 @@ int32_t run_expand(gigl_ctx* ctx, const ExpandArgs& a_in, const RangeTable& tb, 
     GIGL_HIP_CHECK(ctx, hipGetLastError());
     return GIGL_OK;
   }
-  a.proxy_drop = 0;
-  if (const char* e = getenv("GIGL_SAMPLER_PROXY_BITS")) {  // test knob: fewer proxy bits -> forced ties
-    int bits = atoi(e);
-    if (bits >= 1 && bits <= 32) a.proxy_drop = 32 - bits;
-  }
-  static const int32_t flat_max = [] {  // (tuning knob: longest row that reads its hash window flat)
-    const char* e = getenv("GIGL_EXPAND_FLAT_MAX");
-    return e ? atoi(e) : 128;
+  static const int32_t proxy_drop = [] {  // test knob: fewer proxy bits -> forced ties
+    const char* e = getenv("GIGL_SAMPLER_PROXY_BITS");
+    const int bits = e ? atoi(e) : 0;
+    return bits >= 1 && bits <= 32 ? 32 - bits : 0;
   }();
-  a.flat_max = flat_max;
+  a.proxy_drop = proxy_drop;
+  a.flat_max = 128;  // longest row that reads its hash window flat
   if (!covered) gigl_fill_u32(ctx->stream, heavy_count, 0u, 1);
   // the work lists sit behind this hop's descriptors (expand_desc_bytes)
   WorkLists wl{};
@@ -1442,30 +1434,18 @@ int32_t run_expand(gigl_ctx* ctx, const ExpandArgs& a_in, const RangeTable& tb, 
     gigl_prof_scope ps(ctx, GIGL_K_EXPAND);
     hipLaunchKernelGGL(plan_rows_kernel, dim3((unsigned)(a.n_parents / 256 + 1)), dim3(256), 0, ctx->stream, a, tb,
                        desc, covered ? nullptr : heavy_list, heavy_count, wl);
-    // persistent: 8 waves per SIMD on every CU at most, a multiple of WORK_LISTS waves
+    // one copy of the grid: 8 waves per SIMD on every CU at most, a multiple of WORK_LISTS waves
     int64_t wgs = ((a.n_parents + 7) / 8 + 15) / 16 * 16;
-    static const int64_t wgs_max = [] {  // (tuning knob: the persistent grid's size, a multiple of 16)
-      const char* e = getenv("GIGL_EXPAND_WGS");
-      const int64_t v = e ? atoll(e) : 2048;
-      return v < 16 ? (int64_t)16 : v / 16 * 16;
-    }();
-    if (wgs > wgs_max) wgs = wgs_max;
+    if (wgs > 2048) wgs = 2048;
     // (round 6) waves that retire after 16 steps instead of persistent ones: a hop of 1.6 M rows is 13 copies of the 2,048-
     // workgroup grid, and the other streams' workgroups get wave slots as the copies retire — products 19.5 -> 19.3 us per
-    // step on one box, 18.9 -> 18.7 on another, `expand` 4.8 -> 4.7 us alone (profiles/r06am_expand_iters.txt);
-    // GIGL_EXPAND_ITERS=0 keeps the persistent grid (A/B).  Hops of fewer steps than that are one copy: unchanged.
-    static const int32_t iters = [] {
-      const char* e = getenv("GIGL_EXPAND_ITERS");
-      const int v = e ? atoi(e) : 16;
-      return v < 0 ? 0 : v;
-    }();
-    wl.iters = iters;
+    // step on one box, 18.9 -> 18.7 on another, `expand` 4.8 -> 4.7 us alone (profiles/r06am_expand_iters.txt).
+    // Hops of fewer steps than that are one copy.
+    wl.iters = 16;
     wl.wgs = (int32_t)wgs;
-    if (iters > 0) {
-      const int64_t stride = wgs * 4 / WORK_LISTS;                       // steps of a list taken per pass of the grid
-      const int64_t steps = (wl.cap / 2 + stride - 1) / stride;          // a wave's longest possible sequence
-      wgs *= (steps + iters - 1) / iters;
-    }
+    const int64_t stride = wgs * 4 / WORK_LISTS;                // steps of a list taken per pass of the grid
+    const int64_t steps = (wl.cap / 2 + stride - 1) / stride;   // a wave's longest possible sequence
+    wgs *= (steps + wl.iters - 1) / wl.iters;
     hipLaunchKernelGGL(expand_rows_kernel, dim3((unsigned)wgs), dim3(256), 0, ctx->stream, a, tb, (const RowDesc*)desc, wl);
   }
   if (!covered) {

@@ -1741,9 +1741,8 @@ int32_t gigl_records_encode(gigl_ctx* ctx, const uint32_t* tree_roots, const gig
   if (n_records > 0) {
     const unsigned gp = (unsigned)((n_records + wp - 1) / wp);
     e.lds_stride = plan;
-    // (a workgroup per record while the call is latency-bound; GIGL_REC_PLAN_WG = 0 | 1 forces either shape: A/B)
-    static const int wg_knob = getenv("GIGL_REC_PLAN_WG") ? atoi(getenv("GIGL_REC_PLAN_WG")) : -1;
-    const bool plan_wg = !big && plan <= 64 * 1024 && (wg_knob >= 0 ? wg_knob != 0 : n_records <= 6144);
+    // (a workgroup per record while the call is latency-bound)
+    const bool plan_wg = !big && plan <= 64 * 1024 && n_records <= 6144;
     if (plan_wg && plan > 48 * 1024)
       GIGL_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)record_plan_wg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                               (int)plan));

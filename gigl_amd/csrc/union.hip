@@ -50,24 +50,11 @@ static hipError_t lds_opt_in(int device, int site, const void* fn, int bytes, co
   return e;
 }
 
-// The plans' long-row pass keeps the 128-KB shape (16 K distinct values per row in LDS).  GIGL_LG_BIG_CAP=4096 selects a
-// 32-KB shape that finds a CU at once — measured (round 5, same box, 2 runs each): 9.47 / 9.50 G edges/s against 9.79 with
-// the wide shape: the pass that waits for an emptied CU throttles its own stream and the projection next to it runs at
-// 14.8 instead of 21.9 us/step overlapped.  Kept as a knob, not the default.
-static bool lg_big_cap_wide() {
-  static const bool wide = [] {
-    const char* e = getenv("GIGL_LG_BIG_CAP");
-    return !(e && atoi(e) > 0 && atoi(e) <= 4096);
-  }();
-  return wide;
-}
-
 namespace {
 
 constexpr int MAXL = GIGL_MAX_HOPS + 1;
 constexpr int TILE = 1024;          // stream positions per count/assign workgroup
 constexpr int BIG_ROW_CAP = 16384;  // LDS bitonic capacity (64 KiB of int32)
-constexpr int LG_BIG_CAP = 4096;    // ... of the long-row pass under GIGL_LG_BIG_CAP=4096 (32 KB of dynamic LDS; A/B knob)
 
 // one open-addressing slot: everything the passes need about a node sits in ONE 16-byte entry, so a probe
 // costs one random memory access instead of one per attribute array
@@ -108,12 +95,6 @@ struct UnionArgs {
   // are written later)
   uint8_t* root_parent;
   int32_t* overflow;  // meta[GIGL_META_OVERFLOW]
-  // row aliasing (leaf-global, hops == 2, the last hop's nbr array laid out right behind the col buffer): a level-1
-  // node that occurs ONCE in the batch has exactly the in-edges its one parent occurrence sampled — ascending,
-  // duplicate-free global ids sitting in nbr[1][slot*f1 ..) already — so its row is that tree segment itself
-  // (rowptr = alias_base + slot*f1, rowend = rowptr + cnt): no dedup, no fill, no sort for ~90 % of the edges
-  int32_t alias_base;       // index of nbr[1][0] in the col array, or -1
-  const int32_t* cnt_last;  // tree cnt of the last hop
 };
 constexpr int32_t LEAF = -2;  // slot_of value of a leaf occurrence in leaf-global mode
 
@@ -374,8 +355,7 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(int32_t* tile_counts, i
 
 // local id = base[level] + (first occurrences of that level at smaller stream positions)
 __global__ __launch_bounds__(256) void assign_kernel(UnionArgs a, const int32_t* tile_counts, int32_t n_tiles,
-                                                     uint32_t* nodes, int32_t* meta, int32_t* rowptr, int32_t* rowend,
-                                                     int32_t* rowcnt, int32_t* alias_edges) {
+                                                     uint32_t* nodes, int32_t* meta) {
   __shared__ int32_t s_before[MAXL];  // this level's firsts in earlier tiles
   __shared__ int32_t s_total[MAXL];   // totals per level
   __shared__ int32_t s_wave[TILE / 64][MAXL];
@@ -402,7 +382,6 @@ __global__ __launch_bounds__(256) void assign_kernel(UnionArgs a, const int32_t*
     }
   }
   __syncthreads();
-  int32_t alias_c = 0;
 #pragma unroll
   for (int r = 0; r < TILE / 256; ++r) {
     if (lv[r] < 0) continue;
@@ -414,19 +393,6 @@ __global__ __launch_bounds__(256) void assign_kernel(UnionArgs a, const int32_t*
     const int32_t s = a.slot_of[t];
     a.slots[s].lid = id | (lidw[r] & LID_MULTI);
     nodes[id] = slot_key(a.slots[s].kf);
-    // row aliasing: a node whose ONE occurrence is this hop-0 slot owns the tree segment of its children as its
-    // row; rowcnt = -1 tells row_scan to leave the row alone (no winner is ever counted for it)
-    if (a.alias_base >= 0 && !(lidw[r] & LID_MULTI) && t >= a.b && t < a.off[1]) {
-      const int32_t e = (int32_t)(t - a.b), c = a.cnt_last[e];
-      rowptr[id] = a.alias_base + e * a.fan[1];
-      rowend[id] = a.alias_base + e * a.fan[1] + c;
-      rowcnt[id] = -1;
-      alias_c += c;
-    }
-  }
-  if (a.alias_base >= 0) {  // one counter bump per wave, spread over 32 addresses (same-address atomics ~13 ns each)
-    for (int off = 32; off > 0; off >>= 1) alias_c += __shfl_xor(alias_c, off, 64);
-    if (lane == 0 && alias_c) atomicAdd(&alias_edges[blockIdx.x & 31], alias_c);
   }
   if (blockIdx.x == 0 && tid == 0) {
     int32_t cum = 0;
@@ -477,9 +443,7 @@ __global__ void edge_dedup_count_kernel(UnionArgs a, unsigned long long* ekeys, 
     const int32_t dlf = a.slots[a.slot_of[parent_pos(a, k, j)]].lid;
     dl = dlf & ~LID_MULTI;
     sl = s >= 0 ? (a.slots[s].lid & ~LID_MULTI) : (int32_t)pick(a.nbr, k)[j];  // a leaf keeps its global id
-    if (!(dlf & LID_MULTI) && a.alias_base >= 0 && k == a.hops - 1) {
-      // the destination's row is the tree segment itself (patched in by edge_fill): nothing to do for this edge
-    } else if (!(dlf & LID_MULTI)) {
+    if (!(dlf & LID_MULTI)) {
       win = true;  // the destination occurs once in the batch: its f sampled in-edges are distinct already
     } else {
       const unsigned long long key = ((unsigned long long)(uint32_t)dl << 32) | (uint32_t)sl;
@@ -526,7 +490,7 @@ __global__ __launch_bounds__(1024) void row_scan_kernel(const int32_t* rowcnt, i
   const int32_t c_lo = min(n, (int32_t)blockIdx.x * chunk), c_hi = min(n, c_lo + chunk);
   {  // chunk sum -> partials[blockIdx], arrive, wait for everybody, carry = sum of the chunks before mine
     int32_t v = 0;
-    for (int32_t i = c_lo + tid; i < c_hi; i += 1024) v += max(rowcnt[i], 0);  // (-1 = aliased row: no entries)
+    for (int32_t i = c_lo + tid; i < c_hi; i += 1024) v += rowcnt[i];
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     if (lane == 0) s_w[w] = v;
     __syncthreads();
@@ -557,13 +521,8 @@ __global__ __launch_bounds__(1024) void row_scan_kernel(const int32_t* rowcnt, i
   for (int32_t base = c_lo; base < c_hi; base += 1024 * PER) {
     const int32_t i0 = base + tid * PER;
     int32_t c[PER];
-    bool aliased[PER];
 #pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      c[q] = (i0 + q) < c_hi ? rowcnt[i0 + q] : 0;
-      aliased[q] = c[q] < 0;  // the row is a tree segment (assign_kernel set its rowptr / rowend): left alone
-      c[q] = max(c[q], 0);
-    }
+    for (int q = 0; q < PER; ++q) c[q] = (i0 + q) < c_hi ? rowcnt[i0 + q] : 0;
     int32_t v = 0;
 #pragma unroll
     for (int q = 0; q < PER; ++q) v += c[q];
@@ -580,7 +539,7 @@ __global__ __launch_bounds__(1024) void row_scan_kernel(const int32_t* rowcnt, i
     int32_t ex = carry + wave_off + incl - v;
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
-      if (i0 + q < c_hi && !aliased[q]) {
+      if (i0 + q < c_hi) {
         rowptr[i0 + q] = ex;
         rowend[i0 + q] = ex;
       }
@@ -629,20 +588,14 @@ __global__ void edge_fill_kernel(UnionArgs a, const uint8_t* winner, const int2*
 // one wave per row: sort ascending in place (rows <= 64, values are unique); longer rows are queued
 __global__ __launch_bounds__(256) void row_sort_kernel(const int32_t* meta, int hops, const int32_t* rowptr,
                                                        const int32_t* rowend, int32_t* col, int32_t* big_rows,
-                                                       int32_t* big_count, int32_t alias_base, int32_t* meta_rw) {
+                                                       int32_t* big_count) {
   const int lane = threadIdx.x & 63;
   const int32_t n = meta[GIGL_META_LEVEL0 + hops - 1];
   const int32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int32_t waves_total = (gridDim.x * blockDim.x) >> 6;
-  if (alias_base >= 0 && blockIdx.x == 0 && threadIdx.x == 0)
-  {
-    int32_t extra = 0;  // the edges of the aliased rows (counted by edge_fill)
-    for (int q = 0; q < 32; ++q) extra += big_count[32 + q];
-    meta_rw[GIGL_META_N_EDGES] += extra;
-  }
   for (int32_t i = wave; i < n; i += waves_total) {
     const int32_t s = rowptr[i], m = rowend[i] - s;
-    if (m <= 1 || (alias_base >= 0 && s >= alias_base)) continue;  // (an aliased row is a sorted tree segment)
+    if (m <= 1) continue;
     if (m > 64) {
       if (lane == 0) big_rows[atomicAdd(big_count, 1)] = i;
       continue;
@@ -886,7 +839,7 @@ __global__ __launch_bounds__(1024) void row_sort_big_kernel(const int32_t* rowpt
 // b*f0 + b*f0*f1 stream positions in four of its passes and keeps a 64-bit edge hash set sized for every edge; here
 //   * every pass walks the inner stream only (10x fewer positions at [25,10]); the leaves are touched once, by the
 //     threads of the hop-0 slots whose node occurs more than once in the batch (a node that occurs once owns its
-//     tree segment as its row: row aliasing, as above),
+//     tree segment as its row: row aliasing, see Lg2Args::alias_base),
 //   * a node's level is read off its first stream position (a root iff that position is < b): roots and hop-0 slots
 //     are inserted by ONE launch, the rare extras by a second one,
 //   * rows are sized per destination TABLE SLOT while first occurrences are counted (one pass), and get their
@@ -909,8 +862,12 @@ struct Lg2Args {
   int32_t grouped;
   uint32_t group_roots, gdiv0;  // stream slots of ONE batch: roots, hop-0
   int32_t* slot_of;             // [b + S0]
-  int32_t alias_base;
-  int32_t whole_rows;           // a slot with fewer than f1 children holds its node's WHOLE in-neighbourhood (simple graphs)
+  // row aliasing (the last hop's nbr array laid out right behind the col buffer): a level-1 node that occurs ONCE in
+  // the batch has exactly the in-edges its one parent occurrence sampled — ascending, duplicate-free global ids
+  // sitting in nbr[1][slot*f1 ..) already — so its row is that tree segment itself (rowptr = alias_base + slot*f1,
+  // rowend = rowptr + cnt): no dedup, no fill, no sort for ~90 % of the edges
+  int32_t alias_base;           // index of nbr[1][0] in the col array, or -1
+  int32_t whole_rows;          // a slot with fewer than f1 children holds its node's WHOLE in-neighbourhood (simple graphs)
 };
 
 __device__ __forceinline__ uint32_t lg2_base(const Lg2Args& g, const UnionArgs& a, int64_t t) {
@@ -1462,9 +1419,9 @@ __global__ __launch_bounds__(256) void lg2_row_sort_kernel(const int32_t* sort_r
 // queued rows: duplicates removed through an LDS hash set (any number of entries, <= BIG_ROW_CAP distinct), the
 // distinct values written back to the head of the row, then the bucket sort of row_sort_big_kernel.  The last
 // workgroup to finish publishes meta[N_EDGES].
-// CAP: distinct values the LDS set / sort hold (2 * CAP ints of dynamic LDS).  The plans launch CAP = 4096 (32 KB: finds a CU
-// next to other streams' kernels; a row of more distinct values — a hub met under > 400 parents of one batch — takes the
-// global-memory path), round 5: the 128-KB shape waited ~200 us per call for a CU with that much LDS free.
+// CAP: distinct values the LDS set / sort hold (2 * CAP ints of dynamic LDS); a row of more distinct values takes the
+// global-memory path.  Both builders launch CAP = BIG_ROW_CAP (128 KB): a 32-KB shape finds a CU at once, but measured
+// (round 5) 9.47 / 9.50 G edges/s against 9.79 with this one.
 template <int CAP>
 __global__ __launch_bounds__(1024) void lg2_row_sort_big_kernel(const int32_t* rowptr, int32_t* rowend, int32_t* col,
                                                                 const int32_t* big_rows, const int32_t* big_count,
@@ -1766,13 +1723,8 @@ int32_t union_build_lg2(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* t
     hipLaunchKernelGGL(lg2_row_sort_kernel, dim3((unsigned)blocks), dim3(256), 0, st, sort_rows, sort_count,
                        out->rowptr, out->rowend, out->col, big_rows, big_count, edge_counters);
     // (a handful of workgroups; rows of more than MED_ROW entries are rare)
-    if (lg_big_cap_wide()) {
-      GIGL_HIP_CHECK(ctx, lds_opt_in(ctx->device, 0, (const void*)lg2_row_sort_big_kernel<BIG_ROW_CAP>, 2 * BIG_ROW_CAP * (int)sizeof(int32_t)));
-      hipLaunchKernelGGL(lg2_row_sort_big_kernel<BIG_ROW_CAP>, dim3(8), dim3(1024), 2 * BIG_ROW_CAP * sizeof(int32_t), st,
-                       out->rowptr, out->rowend, out->col, big_rows, big_count, out->meta + GIGL_META_OVERFLOW,
-                       edge_counters, ticket_big, out->meta);
-    } else
-    hipLaunchKernelGGL(lg2_row_sort_big_kernel<LG_BIG_CAP>, dim3(8), dim3(1024), 2 * LG_BIG_CAP * sizeof(int32_t), st,
+    GIGL_HIP_CHECK(ctx, lds_opt_in(ctx->device, 0, (const void*)lg2_row_sort_big_kernel<BIG_ROW_CAP>, 2 * BIG_ROW_CAP * (int)sizeof(int32_t)));
+    hipLaunchKernelGGL(lg2_row_sort_big_kernel<BIG_ROW_CAP>, dim3(8), dim3(1024), 2 * BIG_ROW_CAP * sizeof(int32_t), st,
                        out->rowptr, out->rowend, out->col, big_rows, big_count, out->meta + GIGL_META_OVERFLOW,
                        edge_counters, ticket_big, out->meta);
   }
@@ -2502,30 +2454,20 @@ int32_t union_build_lg3(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* t
   const int64_t n_groups = b / group_roots;
   const int64_t gr = group_roots, Tg = gr * (1 + f0), S1g = gr * f0 * f1;
   // (20-bit stream codes; a thread of the dedup pass keeps one bit per 1024 hop-0 slots of the batch in a 64-bit mask)
-  // workgroup shape of the dedup pass (round 5): GIGL_LG3_NT = 512 | 1024 threads, GIGL_LG3_CAP slots per table
-  static const int lg3_nt_env = [] {
-    const char* e = getenv("GIGL_LG3_NT");
-    const int v = e ? atoi(e) : 0;
-    return v == 512 || v == 1024 ? v : 0;
-  }();
+  // workgroup shape of the dedup pass (round 5): 512 | 1024 threads, up to LG3_CAP_DEFAULT slots per table
   // (a thread keeps one bit per NT hop-0 slots of its batch in a 64-bit mask: batches of more than 64 * 512 slots — B = 4096
   // at fan-out 15 — take the 1024-thread shape)
-  int lg3_nt = lg3_nt_env ? lg3_nt_env : (gr * f0 <= 64 * (int64_t)LG3_NT_DEFAULT ? LG3_NT_DEFAULT : 1024);
+  int lg3_nt = gr * f0 <= 64 * (int64_t)LG3_NT_DEFAULT ? LG3_NT_DEFAULT : 1024;
   if (Tg + S1g >= (int64_t)LG3_CODE_MASK || f1 > 64 || b + S0 + S1 >= ((int64_t)1 << 31) || gr * f0 > 64 * (int64_t)lg3_nt) return GIGL_OK;  // -> LG2
   // LDS table: 8-byte slots at load <= 1/2 for the nodes a batch may hold (more do not fit the plan's workspace)
-  static const int64_t cap_max = [] {
-    const char* e = getenv("GIGL_LG3_CAP");  // (A/B knob: slots per workgroup, a power of two)
-    const int64_t v = e ? atoll(e) : 0;
-    return v >= 1024 && v <= 16384 && (v & (v - 1)) == 0 ? v : (int64_t)LG3_CAP_DEFAULT;
-  }();
   int64_t cap = 1024;
-  while (cap < 2 * Tg && cap < cap_max) cap <<= 1;
+  while (cap < 2 * Tg && cap < LG3_CAP_DEFAULT) cap <<= 1;
   const int64_t P = (2 * Tg + cap - 1) / cap;
   if (P > LG3_MAX_PARTS) return GIGL_OK;
   // (the 512-thread shape pays when the launch fills the GPU — a workgroup per CU and more, other streams' kernels beside
   // it; a launch of fewer workgroups than CUs is over sooner with 1024 threads each: the sharded plan's 16-batch calls,
   // lg3_dedup 3.6 -> 5.0 us per rank-step with 512, profiles/r05e_emulated_world8_kernel_time.txt)
-  if (!lg3_nt_env && n_groups * P < 256) lg3_nt = 1024;
+  if (n_groups * P < 256) lg3_nt = 1024;
   // a call of a few batches (a training step: one) leaves most CUs without a workgroup of the dedup pass, whose duration
   // is that of ONE workgroup walking its batch's whole stream (~80 us at [25,10] x 1024): LG2's position-parallel
   // launches finish such a call sooner (training step 0.42 -> 0.39 ms)
@@ -2626,8 +2568,7 @@ int32_t union_build_lg3(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* t
     gigl_prof_scope ps(ctx, GIGL_K_UNION_CSR);
     {
       // (a thread per row: one pass over the queue when up to a quarter of the inner positions own such a row)
-      static const int64_t tiny_div = getenv("GIGL_LG3_TINY_DIV") ? atoll(getenv("GIGL_LG3_TINY_DIV")) : 4;
-      int64_t tb = (T_in / (tiny_div > 0 ? tiny_div : 4) + 255) / 256;
+      int64_t tb = (T_in / 4 + 255) / 256;
       if (tb > 4096) tb = 4096;
       if (tb < 16) tb = 16;
       hipLaunchKernelGGL(lg2_row_sort_tiny_kernel, dim3((unsigned)tb), dim3(256), 0, st, tiny_rows, tiny_count,
@@ -2638,15 +2579,11 @@ int32_t union_build_lg3(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* t
     if (blocks < 64) blocks = 64;
     hipLaunchKernelGGL(lg2_row_sort_kernel, dim3((unsigned)blocks), dim3(256), 0, st, sort_rows, sort_count, out->rowptr,
                        out->rowend, out->col, big_rows, big_count, edge_counters, EC_STRIDE);
-    const bool wide = lg_big_cap_wide();  // (the wide capacity's LDS is past the default limit: opted in)
-    if (wide)
-      GIGL_HIP_CHECK(ctx, lds_opt_in(ctx->device, 4, (const void*)lg2_row_sort_big_kernel<BIG_ROW_CAP>, 2 * BIG_ROW_CAP * (int)sizeof(int32_t)));
-    dispatch_int<BIG_ROW_CAP, LG_BIG_CAP>(wide ? BIG_ROW_CAP : LG_BIG_CAP, [&](auto cap) {
-      constexpr int CAP = decltype(cap)::value;
-      hipLaunchKernelGGL(lg2_row_sort_big_kernel<CAP>, dim3(8), dim3(1024), 2 * CAP * sizeof(int32_t), st, out->rowptr,
-                         out->rowend, out->col, big_rows, big_count, out->meta + GIGL_META_OVERFLOW, edge_counters,
-                         ticket_big, out->meta, EC_STRIDE, (const int32_t*)tile_edges, n_tiles);
-    });
+    // (the capacity's LDS is past the default limit: opted in)
+    GIGL_HIP_CHECK(ctx, lds_opt_in(ctx->device, 4, (const void*)lg2_row_sort_big_kernel<BIG_ROW_CAP>, 2 * BIG_ROW_CAP * (int)sizeof(int32_t)));
+    hipLaunchKernelGGL(lg2_row_sort_big_kernel<BIG_ROW_CAP>, dim3(8), dim3(1024), 2 * BIG_ROW_CAP * sizeof(int32_t), st,
+                       out->rowptr, out->rowend, out->col, big_rows, big_count, out->meta + GIGL_META_OVERFLOW,
+                       edge_counters, ticket_big, out->meta, EC_STRIDE, (const int32_t*)tile_edges, n_tiles);
   }
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
@@ -2684,7 +2621,8 @@ int32_t gigl_union_build_groups(gigl_ctx* ctx, const uint32_t* roots, const gigl
 }  // extern "C"
 
 // leaf_global != 0 (internal, the one-call plan): see UnionArgs::leaf_global.  Only for hops <= 2 and node ids
-// < 2^31 (row values are compared as int32).  Differences of the output: nodes / meta count the nodes of level <
+// < 2^31 (row values are compared as int32); hops == 2 goes to LG3 / LG2 above, the generic build below serves the
+// one-hop plans.  Differences of the output: nodes / meta count the nodes of level <
 // hops only (meta[LEVEL0 + hops] == meta[LEVEL0 + hops - 1] == n_nodes), and the rows of level hops-1 hold global
 // ids; everything else (rows of lower levels, root_local, n_edges, row order) is as documented in gigl_hip.h.
 int32_t gigl_union_build_impl(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* tree, int32_t group_roots,
@@ -2709,7 +2647,7 @@ int32_t gigl_union_build_impl(gigl_ctx* ctx, const uint32_t* roots, const gigl_t
     GIGL_HIP_CHECK(ctx, hipMemsetAsync(out->rowend, 0, sizeof(int32_t), st));
     return GIGL_OK;
   }
-  if (leaf_global && hops == 2 && !getenv("GIGL_UNION_GENERIC")) {
+  if (leaf_global && hops == 2) {
     GIGL_REQUIRE(ctx, group_roots >= 1 && b % group_roots == 0, "group_roots=%d does not divide b=%d", group_roots, b);
     static const bool keep_lg2 = getenv("GIGL_UNION_LG2") != nullptr;  // (A/B knob)
     if (!keep_lg2) {
@@ -2796,11 +2734,6 @@ int32_t gigl_union_build_impl(gigl_ctx* ctx, const uint32_t* roots, const gigl_t
   if (!ekeys || !a.slots || !zeros || !big_rows || !winner || !a.slot_of || !pairs || !tile_counts)
     return gigl_fail(ctx, GIGL_E_OOM, "arena exhausted");
   a.root_parent = winner;  // (free until edge_dedup_count writes the winner flags)
-  a.alias_base = -1;
-  a.cnt_last = tree->cnt[hops - 1];
-  if (a.leaf_global && hops == 2 && tree->nbr[1] == (const uint32_t*)(out->col + out->cap_edges) &&
-      out->cap_edges + (a.off[2] - a.off[1]) < ((int64_t)1 << 31))
-    a.alias_base = (int32_t)out->cap_edges;
   a.overflow = out->meta + GIGL_META_OVERFLOW;
   int32_t* rowcnt = zeros;
   int32_t* big_count = zeros + cap_nodes + 1;  // [0] = number of queued rows
@@ -2826,7 +2759,7 @@ int32_t gigl_union_build_impl(gigl_ctx* ctx, const uint32_t* roots, const gigl_t
     hipLaunchKernelGGL(count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, a, tile_counts);
     hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, st, tile_counts, n_tiles);
     hipLaunchKernelGGL(assign_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, a, tile_counts, n_tiles,
-                       out->nodes, out->meta, out->rowptr, out->rowend, rowcnt, big_count + 32);
+                       out->nodes, out->meta);
   }
   {
     gigl_prof_scope ps(ctx, GIGL_K_UNION_EDGE_SORT);
@@ -2845,7 +2778,7 @@ int32_t gigl_union_build_impl(gigl_ctx* ctx, const uint32_t* roots, const gigl_t
     int64_t blocks = (max_rows + 3) / 4;
     if (blocks > 256 * 64) blocks = 256 * 64;
     hipLaunchKernelGGL(row_sort_kernel, dim3((unsigned)blocks), dim3(256), 0, st, out->meta, hops, out->rowptr,
-                       out->rowend, out->col, big_rows, big_count, a.alias_base, out->meta);
+                       out->rowend, out->col, big_rows, big_count);
     GIGL_HIP_CHECK(ctx, lds_opt_in(ctx->device, 2, (const void*)row_sort_big_kernel, 2 * BIG_ROW_CAP * (int)sizeof(int32_t)));
     hipLaunchKernelGGL(row_sort_big_kernel, dim3(256), dim3(1024), 2 * BIG_ROW_CAP * sizeof(int32_t), st,
                        out->rowptr, out->rowend, out->col, big_rows, big_count, out->meta + GIGL_META_OVERFLOW);

@@ -1410,8 +1410,8 @@ int32_t gigl_dropout_mask(gigl_ctx* ctx, uint64_t seed, uint32_t step, int32_t e
  *   gigl_nablp_train_plan_loss returns the plan's own words.  A batch that does not fit its workspace trains nothing and
  *   reports a NaN loss.  All work is enqueued on the ctx's stream — or, since round 6, on private streams forked from it and
  *   joined back into it before the step's last launch (the random negatives' encode; the main batch's weight gradients of
- *   the GraphSAGE encoder): nothing a caller synchronises differently.  Environment, read at plan creation (off-switches
- *   of the private streams): GIGL_LP_FORK=0 (none), GIGL_LP_WGRAD_STREAM=0 (weight gradients stay in the chain).
+ *   the GraphSAGE encoder): nothing a caller synchronises differently.  Environment, read at plan creation:
+ *   GIGL_LP_FORK=0 (no private streams).
  * HARD NEGATIVES (a plan created while gigl_ctx_set_lp_hard_negatives(ctx, H) holds H > 0; every kind of link-prediction
  *   plan; _step, _step2, _eval and _adopt): main_roots is DEVICE uint32 [b_anchors * T], T = 1 + P + H, anchor-major
  *   (anchor, its P positive slots, its H hard-negative slots; an empty slot repeats the anchor), and pos_cnt is DEVICE
@@ -1635,7 +1635,7 @@ int32_t gigl_comm_set_fixed_blocks(gigl_comm* comm, int32_t on);
 /* bytes this rank has sent to OTHER ranks since the communicator was created: as moved, and as they would have been
  * with every block sent at its full capacity.  The sharded plans' feature-row exchange moves only the requested rows
  * of each block (the counts travel with the id request; RCCL and in-process groups — the host-callback transport has a
- * fixed-size contract and moves full blocks; GIGL_DIST_FIXED_BLOCKS=1 forces full blocks everywhere). */
+ * fixed-size contract and moves full blocks). */
 int32_t gigl_comm_traffic(gigl_comm* comm, int64_t* moved_bytes, int64_t* full_block_bytes);
 int32_t gigl_comm_destroy(gigl_comm* comm);
 

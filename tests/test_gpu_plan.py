@@ -258,6 +258,54 @@ def test_plan_reports_batches_that_do_not_fit_its_workspace():
     eng.close()
 
 
+def test_one_hop_plan_union_against_the_oracle():
+    """a one-hop plan is the one caller of the generic union build in leaf-global mode (two hops go to LG3 / LG2): four
+    roots at fan-out 5 — one with more than 100 in-edges, one repeated (its row is deduplicated through the edge hash set), one
+    with no in-edges — on a directed graph of 300 nodes.  Nodes, level counts, root_local and rows == the oracle's
+    union (the sampled neighbours stay global ids in the roots' rows); the output rows against the staged path at the
+    2e-6 of test_plan_matches_stepwise_and_oracle (same kernels, rows summed in global-id instead of local-id order)."""
+    from gigl_amd.engine import HipEngine
+    from gigl_amd.models import GraphSAGE, HipBatch
+    n, d, hub, lone = 300, 100, 7, 299
+    rng = np.random.default_rng(11)
+    src = np.concatenate([rng.integers(0, n, 1500), np.arange(100, 200)])
+    dst = np.concatenate([rng.integers(0, lone, 1500), np.full(100, hub)])
+    rowptr, col = oracle.build_csc(n, src.astype(np.uint32), dst.astype(np.uint32), is_directed=True)
+    assert rowptr[hub + 1] - rowptr[hub] > 64 and rowptr[lone + 1] == rowptr[lone]
+    x = (rng.standard_normal((n, d)) / 10).astype(np.float32)
+    eng = HipEngine(0)
+    eng.load_csc(rowptr, col)
+    eng.load_features(x)
+    torch.manual_seed(6)
+    model = GraphSAGE(d, 32, 16, num_layers=1).to(eng.device)
+    fan = [5]
+    roots = np.array([hub, 42, lone, 42], np.uint32)
+    plan = model.make_plan(eng, roots.size, fan)
+    out = plan.run(torch.from_numpy(roots.view(np.int32)).to(eng.device)).cpu().numpy()
+    hb = plan.last_batch_to_host()
+    nbr_o, cnt_o = oracle.sample_khop(rowptr, col, roots, fan, canonical=True)
+    assert np.array_equal(hb["nbr"][0], nbr_o[0]) and np.array_equal(hb["cnt"][0], cnt_o[0])
+    assert cnt_o[0].tolist() == [5, cnt_o[0][1], 0, cnt_o[0][1]] and cnt_o[0][1] > 0
+    o = oracle.union_build(roots, fan, nbr_o)
+    n0 = int(o["meta"][2])
+    assert n0 == 3
+    # leaf-global: the roots are the only numbered nodes (n_nodes and both level counts), same unique-edge count
+    assert hb["meta"][0] == n0 and hb["meta"][1] == o["meta"][1] and hb["meta"][2] == n0 and hb["meta"][3] == n0
+    assert hb["meta"][8] == 0  # GIGL_META_OVERFLOW
+    assert np.array_equal(hb["nodes"], o["nodes"][:n0])
+    assert np.array_equal(hb["root_local"], o["root_local"])
+    for i in range(n0):  # rows: ascending GLOBAL source ids, no duplicates
+        mine = hb["col"][hb["rowptr"][i]:hb["rowend"][i]].astype(np.int64) & 0xFFFFFFFF
+        want_row = np.sort(o["nodes"][o["col"][o["rowptr"][i]:o["rowptr"][i + 1]]].astype(np.int64))
+        assert np.array_equal(mine, want_row), i
+    tree = eng.sample_khop(roots, fan)
+    u = eng.union_build(tree)
+    staged = model(HipBatch(eng, tree, u))[u.root_local[:roots.size].long()].cpu().numpy()
+    np.testing.assert_allclose(out, staged, rtol=2e-6, atol=2e-6)
+    plan.close()
+    eng.close()
+
+
 @pytest.mark.parametrize("aggr,fan", [("sum", [25, 10]), ("max", [25, 10]), ("max", [6, 4, 3])])
 def test_plan_with_sum_and_max_reductions(setup, aggr, fan):
     """SAGEConv aggr sum / max through the one-call plan (gigl_sage_plan_set_aggr) == the staged forward"""

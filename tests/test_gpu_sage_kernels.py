@@ -244,7 +244,7 @@ def gmt_lanes(d):
 
 def wgrad_rows_per_chunk(m_cap, n, k):
     """agg.hip's wgrad_rows_per_chunk (not exported): 256 rows, halved down to 32 while m_cap gives fewer than 32 chunks,
-    then doubled while chunks x (64 x 64 tiles of dW) exceeds 4096 workgroups (the default of GIGL_WGRAD_MAX_WGS)"""
+    then doubled while chunks x (64 x 64 tiles of dW) exceeds 4096 workgroups"""
     rc = 256
     while rc > 32 and m_cap // rc < 32:
         rc >>= 1

@@ -77,7 +77,6 @@ def test_lds_staged_union_equals_the_hbm_table_build(tmp_path):
     for tag, env in (("lg3", {"GIGL_LG3_MIN_WGS": "0"}), ("lg2", {"GIGL_UNION_LG2": "1"})):
         path = str(tmp_path / f"{tag}.npz")
         e = dict(os.environ, **env)
-        e.pop("GIGL_UNION_GENERIC", None)
         subprocess.run([sys.executable, "-c", _WORKER, os.path.abspath(ROOT), path], check=True, env=e, timeout=900)
         res[tag] = np.load(path)
     assert sorted(res["lg3"].files) == sorted(res["lg2"].files) and len(res["lg3"].files) > 40
