@@ -73,6 +73,9 @@ SYMBOLS = [
     "gigl_lp_rank_metrics", "gigl_nablp_train_plan_eval", "gigl_nablp_train_plan_adam_steps",
     "gigl_lp_task_loss", "gigl_lp_task_loss_backward", "gigl_nablp_train_plan_set_task",
     "gigl_sage_train_plan_set_dropout", "gigl_nablp_train_plan_set_dropout", "gigl_dropout_mask",
+    "gigl_gcn_dinv", "gigl_gcn_gather", "gigl_gcn_gather_backward_lists",
+    "gigl_gcn_train_plan_create", "gigl_gcn_train_plan_step2", "gigl_gcn_train_plan_loss", "gigl_gcn_train_plan_resume",
+    "gigl_gcn_train_plan_adopt", "gigl_gcn_train_plan_moments", "gigl_gcn_train_plan_set_dropout", "gigl_gcn_train_plan_destroy",
 ]
 
 KERNEL_IDS = {
@@ -449,6 +452,17 @@ def load() -> C.CDLL:
         "gigl_sage_train_plan_set_dropout": [vp, C.c_float, C.c_uint64],
         "gigl_nablp_train_plan_set_dropout": [vp, C.c_float, C.c_uint64],
         "gigl_dropout_mask": [vp, C.c_uint64, C.c_uint32, i32, i32, i64, i32, C.c_float, vp],
+        "gigl_gcn_dinv": [vp, vp, vp, vp, vp, i64, vp],
+        "gigl_gcn_gather": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp],
+        "gigl_gcn_gather_backward_lists": [vp, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp],
+        "gigl_gcn_train_plan_create": [vp, vp, vp, i32, P(i32), P(i32), vp, vp, C.c_float, C.c_float, C.c_float, C.c_float,
+                                       C.c_float, vp],
+        "gigl_gcn_train_plan_step2": [vp, vp, vp, i32, vp, vp, i32, i32, vp],
+        "gigl_gcn_train_plan_resume": [vp],
+        "gigl_gcn_train_plan_adopt": [vp, vp],
+        "gigl_gcn_train_plan_moments": [vp, i32, vp, vp, vp, vp],
+        "gigl_gcn_train_plan_set_dropout": [vp, C.c_float, C.c_uint64],
+        "gigl_gcn_train_plan_destroy": [vp],
         "gigl_lp_rank_metrics": [vp, vp, i64, i32, i32, vp, i32, i32, vp, P(i32), i32, vp],
         "gigl_nablp_train_plan_adam_steps": [vp, vp],
         "gigl_lp_task_loss": [vp, i32, C.c_float, C.c_float, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp],
@@ -474,6 +488,8 @@ def load() -> C.CDLL:
     lib.gigl_json_rows_capacity.restype = i64
     lib.gigl_sage_train_plan_loss.argtypes = [vp]
     lib.gigl_sage_train_plan_loss.restype = vp
+    lib.gigl_gcn_train_plan_loss.argtypes = [vp]
+    lib.gigl_gcn_train_plan_loss.restype = vp
     lib.gigl_nablp_train_plan_loss.argtypes = [vp]
     lib.gigl_nablp_train_plan_loss.restype = vp
     _lib = lib

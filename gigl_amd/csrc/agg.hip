@@ -1732,6 +1732,258 @@ __global__ __launch_bounds__(256) void gcn_gather_kernel(const T* __restrict__ h
   }
 }
 
+// ---- the GCN training plan's aggregation (gigl_gcn_gather / gigl_gcn_gather_backward_lists, include/gigl_hip.h):
+// PyG GCNConv's propagate as TwoLayerGCN uses it (homogeneous.py:488-546), without bias or activation — the projection
+// follows — over a dinv computed once per batch graph (gcn_dinv_kernel).
+//   out[i] = dinv_i * (dinv_i * h[idx(i)] + sum_{e in row i, j = col[e] != i} dinv_j * h[idx(j)])
+// Shaped like gather_mean_kernel (the header comment): one wave per destination row; the row's col entries, their source
+// rows (gather_ids[col]) and weights (dinv[col]) are fetched ONCE, 64 edges at a time, one edge per lane, and broadcast;
+// LPR lanes stream each source row with 16-byte loads, G = 64 / LPR source rows per wave-instruction, four instructions
+// in flight; fp32 accumulate in an order that is a function of the row alone (edge e goes to group e % G, each group adds
+// its edges in stored order, the groups are added in a fixed tree): two runs are bit-identical.  The next row's bounds and
+// first 64 col entries are requested ahead of the current row's source rows.  HBM-bound: per edge 4 B (col) + 4 B (dinv)
+// + d*s B (source row), per row d*s B (its own row) + 4 d B written.
+// (the broadcasts are ds_bpermute, as gather_mean_kernel's: its measured note on v_readlane applies here as well)
+template <typename T, int LPR, int VPL>
+__global__ __launch_bounds__(256) void gcn_gather_rows_kernel(const T* __restrict__ h, int d,
+                                                              const uint32_t* __restrict__ gather_ids,
+                                                              const float* __restrict__ dinv,
+                                                              const int32_t* __restrict__ rowptr,
+                                                              const int32_t* __restrict__ rowend,
+                                                              const int32_t* __restrict__ col,
+                                                              const int32_t* __restrict__ n_rows_dev, int rows_cap,
+                                                              float* __restrict__ out) {
+  constexpr int G = 64 / LPR;
+  const int lane = threadIdx.x & 63;
+  const int sub = lane / LPR, sl = lane % LPR;
+  const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+  const int n_rows = min(*n_rows_dev, rows_cap);
+  const int waves_total = (gridDim.x * blockDim.x) >> 6;
+  const float4_t zero4 = {0.f, 0.f, 0.f, 0.f};
+  auto vec = [](int x) -> int {  // (a vector load of a wave-uniform word: gather_mean_kernel's note on the wait counts)
+    asm("" : "+v"(x));
+    return x;
+  };
+  auto first_col = [&](int e0, int m) -> int { return *(m > 0 ? col + e0 + min(lane, min(64, m) - 1) : rowptr); };
+  // up to 64 edges of row i, one per lane — col entry c of the lanes below mm — as (source row, weight, "is added"): a
+  // stored self loop is not (the row's own term stands for it)
+  auto edge_of = [&](int c, int mm, int i, uint32_t& jl, float& wl) -> uint64_t {
+    const bool on = lane < mm && c != i;
+    jl = gather_ids ? gather_ids[c] : (uint32_t)c;
+    const float w = dinv[c];
+    wl = on ? w : 0.f;
+    return __ballot(on);
+  };
+  auto chunk = [&](uint32_t jl, float wl, uint64_t vm, int mm, float4_t (&acc)[VPL]) {
+    for (int e = 0; e < mm; e += 4 * G) {  // wave-uniform trip count (the broadcasts need every lane)
+      const int ea = e + sub, eb = ea + G, ec = ea + 2 * G, ed = ea + 3 * G;
+      const uint32_t ja = __shfl(jl, ea & 63, 64), jb = __shfl(jl, eb & 63, 64), jc = __shfl(jl, ec & 63, 64),
+                     jd = __shfl(jl, ed & 63, 64);
+      const float wa = __shfl(wl, ea & 63, 64), wb = __shfl(wl, eb & 63, 64), wc = __shfl(wl, ec & 63, 64),
+                  wd = __shfl(wl, ed & 63, 64);
+      const bool va = ea < mm && ((vm >> ea) & 1), vb = eb < mm && ((vm >> eb) & 1), vc = ec < mm && ((vm >> ec) & 1),
+                 vd = ed < mm && ((vm >> ed) & 1);
+      const T* pa = h + (int64_t)ja * d;
+      const T* pb = h + (int64_t)jb * d;
+      const T* pc = h + (int64_t)jc * d;
+      const T* pd = h + (int64_t)jd * d;
+#pragma unroll
+      for (int v = 0; v < VPL; ++v) {
+        const int el = (v * LPR + sl) * 4;
+        if (el < d) {
+          const float4_t a = va ? RowLoader<T>::load4(pa, el) : zero4;
+          const float4_t b = vb ? RowLoader<T>::load4(pb, el) : zero4;
+          const float4_t c = vc ? RowLoader<T>::load4(pc, el) : zero4;
+          const float4_t dd = vd ? RowLoader<T>::load4(pd, el) : zero4;
+          acc[v] += a * (va ? wa : 0.f);
+          acc[v] += b * (vb ? wb : 0.f);
+          acc[v] += c * (vc ? wc : 0.f);
+          acc[v] += dd * (vd ? wd : 0.f);
+        }
+      }
+    }
+  };
+
+  int i = wave;
+  if (i >= n_rows) return;
+  int e0, m, e0n, mn;
+  {
+    const int i1 = min(i + waves_total, n_rows - 1);
+    const int rp = rowptr[vec(i)], re = rowend[vec(i)], rp1 = rowptr[vec(i1)], re1 = rowend[vec(i1)];
+    e0 = __builtin_amdgcn_readfirstlane(rp);
+    m = __builtin_amdgcn_readfirstlane(re) - e0;
+    e0n = __builtin_amdgcn_readfirstlane(rp1);
+    mn = i + waves_total < n_rows ? __builtin_amdgcn_readfirstlane(re1) - e0n : 0;
+  }
+  int c = first_col(e0, m);
+  for (;;) {
+    const int in = i + waves_total;
+    // this row: its own source row and weight, its first 64 edges ...
+    const uint32_t self = gather_ids ? gather_ids[vec(i)] : (uint32_t)i;
+    const float di = dinv[vec(i)];
+    uint32_t jl = 0;
+    float wl = 0.f;
+    uint64_t vm = 0;
+    if (m > 0) vm = edge_of(c, min(64, m), i, jl, wl);
+    // ... the next row's first col entries and the bounds of the row after it, ahead of this row's source rows
+    const int cn = first_col(e0n, mn);
+    const int i2 = min(in + waves_total, n_rows - 1);
+    const int rp2 = rowptr[vec(i2)], re2 = rowend[vec(i2)];
+    const T* ps = h + (int64_t)self * d;
+    float4_t own[VPL], acc[VPL];
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      const int el = (v * LPR + sl) * 4;
+      own[v] = (sub == 0 && el < d) ? RowLoader<T>::load4(ps, el) : zero4;
+      acc[v] = zero4;
+    }
+    if (m > 0) chunk(jl, wl, vm, min(64, m), acc);
+    for (int c0 = 64; c0 < m; c0 += 64) {  // a row past 64 edges: the further entries on demand
+      const int mm = min(64, m - c0);
+      const uint64_t vm2 = edge_of(col[e0 + c0 + min(lane, mm - 1)], mm, i, jl, wl);
+      chunk(jl, wl, vm2, mm, acc);
+    }
+#pragma unroll
+    for (int off = LPR; off < 64; off <<= 1) {  // the G partial sums (lanes sl, sl + LPR, ...)
+#pragma unroll
+      for (int v = 0; v < VPL; ++v) {
+        const float4_t o4 = {__shfl_xor(acc[v].x, off, 64), __shfl_xor(acc[v].y, off, 64), __shfl_xor(acc[v].z, off, 64),
+                             __shfl_xor(acc[v].w, off, 64)};
+        acc[v] += o4;
+      }
+    }
+    const int e0nn = __builtin_amdgcn_readfirstlane(rp2);
+    const int mnn = in + waves_total < n_rows ? __builtin_amdgcn_readfirstlane(re2) - e0nn : 0;
+    if (sub == 0) {
+      float* o = out + (int64_t)i * d;
+#pragma unroll
+      for (int v = 0; v < VPL; ++v) {
+        const int el = (v * LPR + sl) * 4;
+        if (el < d) *reinterpret_cast<float4_t*>(o + el) = (own[v] * di + acc[v]) * di;
+      }
+    }
+    if (in >= n_rows) break;
+    i = in;
+    e0 = e0n;
+    m = mn;
+    c = cn;
+    e0n = e0nn;
+    mn = mnn;
+  }
+}
+
+// the same row for any d (rows that are not whole, 16-byte aligned float4s; rows wider than the widest instantiation
+// above): one wave per destination row, a lane per element, 256 columns per pass held in registers; the row's edges are
+// still fetched once per 64, one per lane, and handed round by v_readlane (the edge is wave-uniform here).  Element
+// (i, c) adds its edges in stored order.
+template <typename T>
+__global__ __launch_bounds__(256) void gcn_gather_scalar_kernel(const T* __restrict__ h, int d,
+                                                                const uint32_t* __restrict__ gather_ids,
+                                                                const float* __restrict__ dinv,
+                                                                const int32_t* __restrict__ rowptr,
+                                                                const int32_t* __restrict__ rowend,
+                                                                const int32_t* __restrict__ col,
+                                                                const int32_t* __restrict__ n_rows_dev, int rows_cap,
+                                                                float* __restrict__ out) {
+  constexpr int K = 4;  // elements per lane and pass
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+  const int n_rows = min(*n_rows_dev, rows_cap);
+  const int waves_total = (gridDim.x * blockDim.x) >> 6;
+  for (int i = wave; i < n_rows; i += waves_total) {
+    const int e0 = rowptr[i], m = rowend[i] - e0;
+    const float di = dinv[i];
+    const T* ps = h + (int64_t)(gather_ids ? gather_ids[i] : (uint32_t)i) * d;
+    // lane l's edge of the 64 from c0 on: source row (-1: none, or a stored self loop) and weight
+    auto edges = [&](int c0, int& jl, float& wl) {
+      jl = -1;
+      wl = 0.f;
+      if (c0 + lane < m) {
+        const int c = col[e0 + c0 + lane];
+        if (c != i) {
+          jl = gather_ids ? (int)gather_ids[c] : c;
+          wl = dinv[c];
+        }
+      }
+    };
+    int j0;
+    float w0;
+    edges(0, j0, w0);
+    for (int cb = 0; cb < d; cb += 64 * K) {
+      float acc[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int el = cb + k * 64 + lane;
+        acc[k] = el < d ? di * (float)ps[el] : 0.f;
+      }
+      for (int c0 = 0; c0 < m; c0 += 64) {
+        int jl = j0;
+        float wl = w0;
+        if (c0 > 0) edges(c0, jl, wl);
+        const int mm = min(64, m - c0);
+        for (int e = 0; e < mm; ++e) {
+          const int j = __builtin_amdgcn_readlane(jl, e);
+          if (j < 0) continue;
+          const float w = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wl), e));
+          const T* p = h + (int64_t)(uint32_t)j * d;
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            const int el = cb + k * 64 + lane;
+            if (el < d) acc[k] += w * (float)p[el];
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int el = cb + k * 64 + lane;
+        if (el < d) out[(int64_t)i * d + el] = di * acc[k];
+      }
+    }
+  }
+}
+
+// the transpose of that row, as a GATHER over the transposed rows gigl_transposed_rows_build writes (gmt_gather_kernel's
+// shape: LPR lanes per source row, 64 / LPR source rows per wave): for every source j < *n_src
+//   dsrc[j] = dinv_j * ([j < n_rows] dinv_j * dout[j] + sum_{readers i of j, i != j} dinv_i * dout[i])
+// written once — no cleared block, no float atomics.  A reader equal to j is the stored self loop the forward skipped.
+// Four readers' rows are in flight per source row.  VEC: whole 16-byte-aligned float4 rows; else element by element
+template <int LPR, bool VEC>
+__global__ __launch_bounds__(256) void gcn_gather_bwd_kernel(const float* __restrict__ dout, int d,
+                                                             const float* __restrict__ dinv,
+                                                             const int32_t* __restrict__ n_rows_dev,
+                                                             const int32_t* __restrict__ n_src_dev, int src_cap,
+                                                             const int32_t* __restrict__ cnt, const int32_t* __restrict__ ptr,
+                                                             const int32_t* __restrict__ list, float* __restrict__ dsrc) {
+  constexpr int G = 64 / LPR, W = VEC ? 4 : 1;
+  using V = std::conditional_t<VEC, float4_t, float>;
+  const int lane = threadIdx.x & 63, sub = lane / LPR, l = lane % LPR;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, waves = (gridDim.x * blockDim.x) >> 6;
+  const int n_src = min(*n_src_dev, src_cap), n_rows = *n_rows_dev;
+  for (int j = wave * G + sub; j < n_src; j += waves * G) {
+    const int c = cnt[j], p0 = ptr[j];
+    const float dj = dinv[j];
+    for (int el = W * l; el < d; el += W * LPR) {
+      V acc = V(0.f);
+      if (j < n_rows) acc = *reinterpret_cast<const V*>(dout + (int64_t)j * d + el) * dj;
+      for (int k = 0; k < c; k += 4) {
+        int ri[4];
+        float rw[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ri[q] = k + q < c ? list[p0 + k + q] : j;  // (j: skipped like a stored self loop)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) rw[q] = ri[q] != j ? dinv[ri[q]] : 0.f;
+        V rv[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          rv[q] = ri[q] != j ? *reinterpret_cast<const V*>(dout + (int64_t)ri[q] * d + el) : V(0.f);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc += rv[q] * rw[q];
+      }
+      *reinterpret_cast<V*>(dsrc + (int64_t)j * d + el) = acc * dj;
+    }
+  }
+}
+
 // alpha[i][hd] = sum_c h[i][hd*C + c] * att[hd*C + c]      (one thread per (node, head))
 __global__ void gat_alpha_kernel(const float* __restrict__ h, const float* __restrict__ att_src,
                                  const float* __restrict__ att_dst, const int32_t* __restrict__ n_dev, int heads,
@@ -4139,6 +4391,89 @@ int32_t gigl_gcn_aggregate(gigl_ctx* ctx, const void* h, int32_t h_dtype, int32_
     using T = typename decltype(t)::type;
     hipLaunchKernelGGL((gcn_gather_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const T*)h, d,
                        gather_ids, dinv_scratch, rowptr, rowend, col, n_rows_dev, bias, act, out);
+  });
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+constexpr int GCN_GATHER_MAX_VECS = 256;  // float4s per row of gcn_gather_rows_kernel's widest instantiation
+
+int32_t gigl_gcn_dinv(gigl_ctx* ctx, const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
+                      const int32_t* n_nodes_dev, int64_t nodes_cap, float* dinv) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  GIGL_REQUIRE(ctx, rowptr && rowend && col && n_nodes_dev && dinv, "null argument");
+  GIGL_REQUIRE(ctx, nodes_cap >= 0 && nodes_cap < ((int64_t)1 << 31), "bad sizes");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (nodes_cap == 0) return GIGL_OK;
+  gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
+  hipLaunchKernelGGL(gcn_dinv_kernel, dim3((unsigned)((nodes_cap + 255) / 256)), dim3(256), 0, ctx->stream, rowptr, rowend, col,
+                     n_nodes_dev, dinv);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+int32_t gigl_gcn_gather(gigl_ctx* ctx, const void* h, int32_t h_dtype, int32_t d, const uint32_t* gather_ids, const float* dinv,
+                        const int32_t* rowptr, const int32_t* rowend, const int32_t* col, const int32_t* n_rows_dev,
+                        int64_t rows_cap, float* out) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  GIGL_REQUIRE(ctx, h && dinv && rowptr && rowend && col && n_rows_dev && out, "null argument");
+  GIGL_REQUIRE(ctx, d > 0 && rows_cap >= 0 && rows_cap < ((int64_t)1 << 31), "bad sizes");
+  GIGL_REQUIRE(ctx, h_dtype == GIGL_DTYPE_F32 || h_dtype == GIGL_DTYPE_F16, "bad dtype %d", h_dtype);
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (rows_cap == 0) return GIGL_OK;
+  gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
+  int64_t blocks = (rows_cap + 3) / 4;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  const dim3 g((unsigned)blocks), b(256);
+  const int vecs = d / 4;
+  dispatch_type<float, __half>(h_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    // whole float4s of 16-byte-aligned rows (fp16 sources: four halves, 8 bytes), up to the widest instantiation: 64 lanes x
+    // 4 float4s, d <= 1024 (8 float4s per lane — the row's sum, its own row and four source rows in flight — compile to
+    // 256 VGPRs, one wave per SIMD; such rows take the element kernel, whose 256-byte wave loads are coalesced as well)
+    const bool whole = (d & 3) == 0 && vecs <= GCN_GATHER_MAX_VECS && ((uintptr_t)h & (4 * sizeof(T) - 1)) == 0 &&
+                       ((uintptr_t)out & 15) == 0;
+    if (!whole) {
+      hipLaunchKernelGGL((gcn_gather_scalar_kernel<T>), g, b, 0, ctx->stream, (const T*)h, d, gather_ids, dinv, rowptr, rowend, col,
+                         n_rows_dev, (int)rows_cap, out);
+      return;
+    }
+    dispatch_int<0, 1, 2, 3, 4, 5>(gather_lanes_index(vecs), [&](auto i) {  // gather_mean_kernel's (lanes, float4s) pairs
+      constexpr int I = decltype(i)::value, LPR = I < 3 ? (8 << I) : 64, VPL = 1 << (I < 4 ? 0 : I - 3);
+      static_assert(LPR * VPL <= GCN_GATHER_MAX_VECS, "the widest instantiation");
+      hipLaunchKernelGGL((gcn_gather_rows_kernel<T, LPR, VPL>), g, b, 0, ctx->stream, (const T*)h, d, gather_ids, dinv, rowptr,
+                         rowend, col, n_rows_dev, (int)rows_cap, out);
+    });
+  });
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+int32_t gigl_gcn_gather_backward_lists(gigl_ctx* ctx, const float* dout, int32_t d, const float* dinv, const int32_t* rowptr,
+                                       const int32_t* rowend, const int32_t* n_rows_dev, const int32_t* n_src_dev,
+                                       int64_t src_cap, const int32_t* lists, float* dsrc) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  (void)rowptr;  // (the rows' bounds are part of the signature the SAGE entry point shares; the weights are dinv's)
+  (void)rowend;
+  GIGL_REQUIRE(ctx, dout && dinv && n_rows_dev && n_src_dev && lists && dsrc, "null argument");
+  GIGL_REQUIRE(ctx, d > 0 && src_cap >= 0 && src_cap < ((int64_t)1 << 31), "bad sizes");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (src_cap == 0) return GIGL_OK;
+  const int32_t* cnt = lists;  // (gigl_transposed_rows_build's layout)
+  const int32_t* ptr = lists + 2 * src_cap + 16;
+  const int32_t* list = ptr + src_cap;
+  gigl_prof_scope ps(ctx, GIGL_K_GATHER_BWD);
+  const bool whole = (d & 3) == 0 && (((uintptr_t)dout | (uintptr_t)dsrc) & 15) == 0;
+  const int units = whole ? d / 4 : d;  // what a lane takes per pass: a float4, or an element
+  const int lpr = units >= 64 ? 64 : (units >= 32 ? 32 : (units >= 16 ? 16 : 8));
+  int64_t gg = (src_cap * lpr / 64 + 3) / 4;
+  if (gg > 256 * 16) gg = 256 * 16;
+  if (gg < 1) gg = 1;
+  dispatch_int<64, 32, 16, 8>(lpr, [&](auto l) {
+    dispatch_bool(whole, [&](auto v) {
+      hipLaunchKernelGGL((gcn_gather_bwd_kernel<decltype(l)::value, decltype(v)::value>), dim3((unsigned)gg), dim3(256), 0,
+                         ctx->stream, dout, d, dinv, n_rows_dev, n_src_dev, (int)src_cap, cnt, ptr, list, dsrc);
+    });
   });
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;

@@ -1914,9 +1914,9 @@ bool train_part_captures(int part) {
   return !(ev && (ev[0] == '1' || (ev[0] == 'g' && part == 0) || (ev[0] == 'l' && part == 1)));
 }
 
-}  // namespace
-
-struct gigl_sage_train_plan : SageTrainShared {
+// ---- what the node-classification training plans (GraphSAGE, GCN) share beyond their layers: the workspace ring, the step's
+// static inputs, the loss on the roots and the step itself, written once
+struct NcTrainState {
   gigl_ctx* ctx = nullptr;         // the caller's (its stream carries the layers part; errors are reported on it)
   // two ctxs of the plan's own, for their ARENAS: scratch addresses are baked into the captured launches, and another
   // plan on the caller's ctx (the inference plan of an evaluation pass between epochs) may grow — reallocate — that arena
@@ -1924,18 +1924,158 @@ struct gigl_sage_train_plan : SageTrainShared {
   // TRAIN_WS workspaces, one root set each (each on its own side ctx / stream: two graph parts — of the next batch and of
   // the one after — can be in flight)
   PlanRing ring;
-  SageTrainEnc enc;                       // the step's one encode (over the batch graph ring.slot[k].base[0] the step reads)
-  int32_t* tlists[TRAIN_WS][GIGL_MAX_HOPS] = {{nullptr}};  // its transposed lists per workspace and layer >= 1, built by the graph part
-  float* da = nullptr;                    // [max rows_cap[l >= 1]][2 max dims]: gradient of a layer's operand
+  int32_t b = 0;                          // roots per batch
   float** loss_slot = nullptr;            // where the caller wants the step's loss (set by train_stage_kernel)
-  void* zero_base = nullptr;              // the dh rows that are added to: cleared at the start of every step
+  void* zero_base = nullptr;              // the gradient rows that are added to: cleared at the start of every step
   size_t zero_bytes = 0;
   int64_t* labels_buf = nullptr;
   int32_t* n_valid_buf = nullptr;  // [0] real roots of the batch, [1] Adam's step counter, [2] sticky "a batch failed" (halt)
   float* loss_rows = nullptr;
   float* loss = nullptr;
-  bool stepped = false;  // a step has run: what the captured layers part launches is final (gigl_sage_train_plan_set_dropout)
+  bool stepped = false;  // a step has run: what the captured layers part launches is final (gigl_*_train_plan_set_dropout)
   std::vector<void*> owned;
+};
+
+// the step's static buffers and the cleared block of zero_floats floats (zeroed words, no loss slot yet)
+bool nc_state_alloc(NcTrainState& t, size_t zero_floats) {
+  auto alloc = [&](size_t bytes) { return plan_alloc(t.owned, bytes); };
+  t.zero_base = alloc(zero_floats * 4);
+  t.zero_bytes = zero_floats * 4;
+  t.labels_buf = (int64_t*)alloc((size_t)t.b * 8);
+  t.n_valid_buf = (int32_t*)alloc(16);
+  t.loss_rows = (float*)alloc((size_t)t.b * 4);
+  t.loss = (float*)alloc(16);
+  // (measured, round 6: the loss sum on a BRANCH of the captured layers — forked after the loss rows, joined before Adam —
+  // took the step from 0.201 to 0.263 ms: a graph with a second branch is replayed through two queues with a barrier
+  // packet per edge.  The layers part stays one stream)
+  t.loss_slot = (float**)alloc(16);
+  return t.zero_base && t.labels_buf && t.n_valid_buf && t.loss_rows && t.loss && t.loss_slot &&
+         hipMemset(t.n_valid_buf, 0, 16) == hipSuccess && hipMemset(t.loss_slot, 0, 16) == hipSuccess;
+}
+
+// everything a plan holds through its NcTrainState (the caller deletes the plan itself)
+void nc_state_release(NcTrainState* t) {
+  if (t->ctx) {
+    hipSetDevice(t->ctx->device);
+    hipStreamSynchronize(t->ctx->stream);
+  }
+  t->ring.release();
+  for (void* q : t->owned) hipFree(q);
+  t->ring.destroy_ctxs();
+  if (t->lctx) {
+    gigl_ctx_set_stream(t->lctx, nullptr);  // (the stream is the caller's)
+    gigl_ctx_destroy(t->lctx);
+  }
+}
+
+// loss on the roots of workspace p's batch over out [*][width], its gradient ADDED into dout (cleared before)
+void nc_loss_launches(const NcTrainState* t, hipStream_t st, const BatchGraph* p, const float* out, int width, float* dout) {
+  // (the loss rows and their sum stay two launches: folding the sum into the last workgroup of the first — a ticket behind
+  // device-scope fences — took 22.7 us instead of 5.0 + 5.1, and the L2 write-backs of its 256 fences slowed the next batch's
+  // graph part on the side stream: measured, round 6)
+  hipLaunchKernelGGL(ce_roots_kernel, dim3((unsigned)((t->b + 3) / 4)), dim3(256), 0, st, out, width,
+                     (const int32_t*)p->un.root_local, (const int64_t*)t->labels_buf, (const int32_t*)t->n_valid_buf, t->b,
+                     (const int32_t*)p->un.meta, dout, t->loss_rows);
+  hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->loss_rows, t->b,
+                     (const int32_t*)t->n_valid_buf, t->loss, t->n_valid_buf + 1, (const int32_t*)p->un.meta,
+                     t->n_valid_buf + 2, (float* const*)t->loss_slot);
+}
+
+// a plan's private ctx (own arena) follows the caller's stream: every launch of the step goes there
+static int32_t train_bind_stream(gigl_ctx* ctx, gigl_ctx* lctx) {
+  if (lctx->stream == ctx->stream && !lctx->own_stream) return GIGL_OK;
+  const int32_t rs = gigl_ctx_set_stream(lctx, ctx->stream);
+  return rs == GIGL_OK ? GIGL_OK : gigl_fail(ctx, rs, "%s", gigl_last_error(lctx));
+}
+
+extern "C++" {
+// One step (gigl_sage_train_plan_step2's contract, include/gigl_hip.h).  graph_body(kk): the graph part of the batch in
+// workspace kk's roots_buf, on that workspace's side ctx; layers_body(k): everything after it over workspace k, on lctx.
+// pa: what train_stage_kernel clears and transposes ahead of the layers
+template <typename GraphBody, typename LayersBody>
+int32_t nc_train_step(NcTrainState* t, const uint32_t* roots, const int64_t* labels, int32_t n_valid, const uint32_t* roots_next,
+                      const uint32_t* roots_next2, int32_t sampling_seed, int32_t mode, float* loss_out, const TrainPrep& pa,
+                      GraphBody&& graph_body, LayersBody&& layers_body) {
+  gigl_ctx* ctx = t->ctx;
+  GIGL_REQUIRE(ctx, roots && labels && n_valid >= 1 && n_valid <= t->b, "bad argument");
+  if (mode == GIGL_MODE_REPLACE)
+    return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "the training plan needs duplicate-free trees (no with-replacement mode)");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  t->stepped = true;
+  hipStream_t st = ctx->stream;
+  PlanRing& ring = t->ring;
+  ring.reseed(PlanRing::TRAIN, sampling_seed, mode);
+  const int k = ring.cur;
+  auto graph_part = [&](int kk, const uint32_t* r) {
+    const size_t count = (size_t)t->b;
+    return ring.issue_graph_part(kk, PlanRing::TRAIN, &r, &count, train_part_captures(0), [&, kk]() { return graph_body(kk); });
+  };
+  // (a prefetched workspace belongs to the roots it was announced with: an epoch cut short, a reshuffle or an evaluation
+  // between two steps hands in other roots — the graph part is then issued again instead of training these labels
+  // against the old batch's graph; as gigl_hgt_infer_run's guard)
+  if (!ring.holds(k, roots)) {  // the graph part of THIS batch now (the layers wait for it)
+    const int32_t rc = graph_part(k, roots);
+    if (rc != GIGL_OK) return rc;
+  }
+  ring.consume(k);
+  // the NEXT batch's graph part goes to the side stream BEFORE this batch's layers are enqueued: it waits for what the
+  // caller's stream holds now (roots_next was written there; the layers that last read the other workspace), not for
+  // the layers about to be enqueued
+  // (two batches ahead: the graph parts are chains of small latency-bound launches, two of them in flight on their own
+  // streams take little more than one)
+  const uint32_t* ahead[2] = {roots_next, roots_next ? roots_next2 : nullptr};
+  for (int d = 0; d < 2; ++d) {
+    const int kk = (k + 1 + d) % TRAIN_WS;
+    if (!ahead[d] || ring.holds(kk, ahead[d]) || kk == k) continue;
+    const int32_t rc = graph_part(kk, ahead[d]);
+    if (rc != GIGL_OK) return rc;
+  }
+  // the step's inputs go into the static buffers the (captured) launches read — labels, the number of real roots, where the
+  // caller wants the loss (the loss kernel writes it there itself) — in the launch that also clears the cleared block and
+  // lays out the transposed weights
+  int64_t blocks = (pa.zero_words + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 64) blocks = 64;
+  // (the layers of the previous step read labels_buf / the cleared block: this launch is behind them on the stream)
+  hipLaunchKernelGGL(train_stage_kernel, dim3((unsigned)blocks), dim3(256), 0, st, labels, n_valid, t->labels_buf, t->n_valid_buf,
+                     t->loss_slot, loss_out, pa);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, ring.slot[k].ev_graph, 0));
+  const int32_t rs = train_bind_stream(ctx, t->lctx);
+  if (rs != GIGL_OK) return rs;
+  PartGraph& layers = ring.slot[k].layers;
+  const int32_t rc = gigl_run_part(t->lctx, t->lctx, &layers, train_part_captures(1), "training step", [&]() { return layers_body(k); });
+  if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
+  // (the layers' scratch is the plan's, not a workspace's: one eager run has sized it for every slot's capture)
+  if (layers.warm)
+    for (PlanRing::Slot& s : ring.slot) s.layers.warm = true;
+  GIGL_HIP_CHECK(ctx, hipEventRecord(ring.slot[k].ev_layers, st));
+  ring.cur = (k + 1) % TRAIN_WS;
+  return GIGL_OK;
+}
+}  // extern "C++"
+
+// clears the device-side halt a failed batch left, on the plan's stream
+int32_t nc_resume(NcTrainState* t) {
+  GIGL_HIP_CHECK(t->ctx, hipSetDevice(t->ctx->device));
+  GIGL_HIP_CHECK(t->ctx, hipMemsetAsync(t->n_valid_buf + 2, 0, 4, t->ctx->stream));
+  return GIGL_OK;
+}
+
+// Adam's step counter of src into dst, behind the moments' copies on dst's stream; both streams are synchronised
+int32_t nc_adopt_counter(NcTrainState* dst, const NcTrainState* src) {
+  gigl_ctx* ctx = dst->ctx;
+  GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->n_valid_buf + 1, src->n_valid_buf + 1, 4, hipMemcpyDeviceToDevice, ctx->stream));
+  GIGL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return GIGL_OK;
+}
+
+}  // namespace
+
+struct gigl_sage_train_plan : SageTrainShared, NcTrainState {
+  SageTrainEnc enc;                       // the step's one encode (over the batch graph ring.slot[k].base[0] the step reads)
+  int32_t* tlists[TRAIN_WS][GIGL_MAX_HOPS] = {{nullptr}};  // its transposed lists per workspace and layer >= 1, built by the graph part
+  float* da = nullptr;                    // [max rows_cap[l >= 1]][2 max dims]: gradient of a layer's operand
 };
 
 namespace {
@@ -1950,18 +2090,7 @@ int32_t train_enqueue_layers(gigl_sage_train_plan* t, int k) {
   int32_t rc = sage_enc_forward(ctx, *t, e, p, true, 0, t->n_valid_buf + 1);
   if (rc != GIGL_OK) return rc;
   // ---- loss on the roots, its gradient into dh[L - 1]
-  {
-    const int width = t->dims[L];
-    // (the loss rows and their sum stay two launches: folding the sum into the last workgroup of the first — a ticket behind
-    // device-scope fences — took 22.7 us instead of 5.0 + 5.1, and the L2 write-backs of its 256 fences slowed the next batch's
-    // graph part on the side stream: measured, round 6)
-    hipLaunchKernelGGL(ce_roots_kernel, dim3((unsigned)((e.b + 3) / 4)), dim3(256), 0, st, (const float*)e.h[L - 1], width,
-                       (const int32_t*)p->un.root_local, (const int64_t*)t->labels_buf, (const int32_t*)t->n_valid_buf, e.b,
-                       (const int32_t*)p->un.meta, e.dh[L - 1], t->loss_rows);
-    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, st, (const float*)t->loss_rows, e.b,
-                       (const int32_t*)t->n_valid_buf, t->loss, t->n_valid_buf + 1, (const int32_t*)p->un.meta,
-                       t->n_valid_buf + 2, (float* const*)t->loss_slot);
-  }
+  nc_loss_launches(t, st, p, e.h[L - 1], t->dims[L], e.dh[L - 1]);
   rc = sage_enc_backward(ctx, *t, e, p, t->tlists[k], t->da, nullptr, nullptr);
   if (rc != GIGL_OK) return rc;
   const AdamPack ap = sage_adam_pack(*t, &e, p, nullptr, nullptr);
@@ -1971,28 +2100,11 @@ int32_t train_enqueue_layers(gigl_sage_train_plan* t, int k) {
   return GIGL_OK;
 }
 
-// a plan's private ctx (own arena) follows the caller's stream: every launch of the step goes there
-static int32_t train_bind_stream(gigl_ctx* ctx, gigl_ctx* lctx) {
-  if (lctx->stream == ctx->stream && !lctx->own_stream) return GIGL_OK;
-  const int32_t rs = gigl_ctx_set_stream(lctx, ctx->stream);
-  return rs == GIGL_OK ? GIGL_OK : gigl_fail(ctx, rs, "%s", gigl_last_error(lctx));
-}
-
 }  // namespace
 
 int32_t gigl_sage_train_plan_destroy(gigl_sage_train_plan* t) {
   if (!t) return GIGL_OK;
-  if (t->ctx) {
-    hipSetDevice(t->ctx->device);
-    hipStreamSynchronize(t->ctx->stream);
-  }
-  t->ring.release();
-  for (void* q : t->owned) hipFree(q);
-  t->ring.destroy_ctxs();
-  if (t->lctx) {
-    gigl_ctx_set_stream(t->lctx, nullptr);  // (the stream is the caller's)
-    gigl_ctx_destroy(t->lctx);
-  }
+  nc_state_release(t);
   delete t;
   return GIGL_OK;
 }
@@ -2018,34 +2130,22 @@ int32_t gigl_sage_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat*
     return rc;
   }
   t->L = hops;
-  t->enc.b = b;
+  t->b = t->enc.b = b;
   t->act_last = act_last;
   t->lr = lr;
   t->beta1 = beta1;
   t->beta2 = beta2;
   t->eps = eps;
   t->wd = weight_decay;
-  auto alloc = [&](size_t bytes) { return plan_alloc(t->owned, bytes); };
   size_t zero_floats = 0, da_floats = 16;
   bool ok = sage_shared_alloc(*t, t->owned, dims, w, bias);
   // (no entry point hands this plan's gradients out: the cleared block is the dh rows alone)
   ok = sage_enc_alloc(*t, t->enc, t->owned, ctx->wide, fanouts, false, &zero_floats, &da_floats) && ok;
-  float* z = (float*)alloc(zero_floats * 4);
-  t->zero_base = z;
-  t->zero_bytes = zero_floats * 4;
-  if (z) sage_enc_carve(*t, t->enc, false, z);
+  ok = nc_state_alloc(*t, zero_floats) && ok;
+  if (t->zero_base) sage_enc_carve(*t, t->enc, false, (float*)t->zero_base);
   for (int k = 0; k < TRAIN_WS; ++k) ok = sage_tlists_alloc(*t, t->enc, t->owned, t->ring.slot[k].base[0].un.cap_edges, t->tlists[k]) && ok;
-  t->da = (float*)alloc(da_floats * 4);
-  t->labels_buf = (int64_t*)alloc((size_t)b * 8);
-  t->n_valid_buf = (int32_t*)alloc(16);
-  t->loss_rows = (float*)alloc((size_t)b * 4);
-  t->loss = (float*)alloc(16);
-  // (measured, round 6: the loss sum on a BRANCH of the captured layers — forked after the loss rows, joined before Adam —
-  // took the step from 0.201 to 0.263 ms: a graph with a second branch is replayed through two queues with a barrier
-  // packet per edge.  The layers part stays one stream)
-  t->loss_slot = (float**)alloc(16);
-  ok = ok && t->zero_base && t->da && t->labels_buf && t->n_valid_buf && t->loss_rows && t->loss && t->loss_slot &&
-       hipMemset(t->n_valid_buf, 0, 16) == hipSuccess && hipMemset(t->loss_slot, 0, 16) == hipSuccess;
+  t->da = (float*)plan_alloc(t->owned, da_floats * 4);
+  ok = ok && t->da;
   if (!ok) {
     gigl_sage_train_plan_destroy(t);
     return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the training workspace failed");
@@ -2063,44 +2163,7 @@ int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* t, const uint32_t* root
                                    const uint32_t* roots_next, const uint32_t* roots_next2, int32_t sampling_seed,
                                    int32_t mode, float* loss_out) {
   if (!t) return GIGL_E_INVALID_ARG;
-  gigl_ctx* ctx = t->ctx;
-  GIGL_REQUIRE(ctx, roots && labels && n_valid >= 1 && n_valid <= t->enc.b, "bad argument");
-  if (mode == GIGL_MODE_REPLACE)
-    return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "the training plan needs duplicate-free trees (no with-replacement mode)");
-  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  t->stepped = true;
-  hipStream_t st = ctx->stream;
-  PlanRing& ring = t->ring;
-  ring.reseed(PlanRing::TRAIN, sampling_seed, mode);
-  const int k = ring.cur;
-  auto graph_part = [&](int kk, const uint32_t* r) {
-    const size_t count = (size_t)t->enc.b;
-    return ring.issue_graph_part(kk, PlanRing::TRAIN, &r, &count, train_part_captures(0), [&, kk]() {
-      return sage_enqueue_graph(*t, t->enc, &ring.slot[kk].base[0], t->tlists[kk], sampling_seed, mode);
-    });
-  };
-  // (a prefetched workspace belongs to the roots it was announced with: an epoch cut short, a reshuffle or an evaluation
-  // between two steps hands in other roots — the graph part is then issued again instead of training these labels
-  // against the old batch's graph; as gigl_hgt_infer_run's guard)
-  if (!ring.holds(k, roots)) {  // the graph part of THIS batch now (the layers wait for it)
-    const int32_t rc = graph_part(k, roots);
-    if (rc != GIGL_OK) return rc;
-  }
-  ring.consume(k);
-  // the NEXT batch's graph part goes to the side stream BEFORE this batch's layers are enqueued: it waits for what the
-  // caller's stream holds now (roots_next was written there; the layers that last read the other workspace), not for
-  // the layers about to be enqueued
-  // (two batches ahead: the graph parts are chains of small latency-bound launches, two of them in flight on their own
-  // streams take little more than one)
-  const uint32_t* ahead[2] = {roots_next, roots_next ? roots_next2 : nullptr};
-  for (int d = 0; d < 2; ++d) {
-    const int kk = (k + 1 + d) % TRAIN_WS;
-    if (!ahead[d] || ring.holds(kk, ahead[d]) || kk == k) continue;
-    const int32_t rc = graph_part(kk, ahead[d]);
-    if (rc != GIGL_OK) return rc;
-  }
-  // the step's inputs go into the static buffers the (captured) launches read — labels, the number of real roots, where the
-  // caller wants the loss (the loss kernel writes it there itself) — in the launch that also clears the dh block and lays out W_l^T
+  // what train_stage_kernel does ahead of the layers: it clears the dh block and lays out W_l^T of layers >= 1
   TrainPrep pa{};
   pa.zero = (uint32_t*)t->zero_base;
   pa.zero_words = (int64_t)(t->zero_bytes / 4);
@@ -2111,26 +2174,10 @@ int32_t gigl_sage_train_plan_step2(gigl_sage_train_plan* t, const uint32_t* root
     pa.cols[pa.n_t] = 2 * t->dims[l];
     ++pa.n_t;
   }
-  int64_t blocks = (pa.zero_words + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 64) blocks = 64;
-  // (the layers of the previous step read labels_buf / the cleared block: this launch is behind them on the stream)
-  hipLaunchKernelGGL(train_stage_kernel, dim3((unsigned)blocks), dim3(256), 0, st, labels, n_valid, t->labels_buf, t->n_valid_buf,
-                     t->loss_slot, loss_out, pa);
-  GIGL_HIP_CHECK(ctx, hipGetLastError());
-  GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(st, ring.slot[k].ev_graph, 0));
-  const int32_t rs = train_bind_stream(ctx, t->lctx);
-  if (rs != GIGL_OK) return rs;
-  PartGraph& layers = ring.slot[k].layers;
-  const int32_t rc = gigl_run_part(t->lctx, t->lctx, &layers, train_part_captures(1), "training step",
-                                   [&]() { return train_enqueue_layers(t, k); });
-  if (rc != GIGL_OK) return gigl_fail(ctx, rc, "%s", gigl_last_error(t->lctx));
-  // (the layers' scratch is the plan's, not a workspace's: one eager run has sized it for every slot's capture)
-  if (layers.warm)
-    for (PlanRing::Slot& s : ring.slot) s.layers.warm = true;
-  GIGL_HIP_CHECK(ctx, hipEventRecord(ring.slot[k].ev_layers, st));
-  ring.cur = (k + 1) % TRAIN_WS;
-  return GIGL_OK;
+  return nc_train_step(
+      t, roots, labels, n_valid, roots_next, roots_next2, sampling_seed, mode, loss_out, pa,
+      [&](int kk) { return sage_enqueue_graph(*t, t->enc, &t->ring.slot[kk].base[0], t->tlists[kk], sampling_seed, mode); },
+      [&](int k) { return train_enqueue_layers(t, k); });
 }
 
 const float* gigl_sage_train_plan_loss(gigl_sage_train_plan* t) { return t ? t->loss : nullptr; }
@@ -2138,7 +2185,9 @@ const float* gigl_sage_train_plan_loss(gigl_sage_train_plan* t) { return t ? t->
 namespace {
 // the setters' shared half: the plan has not stepped (its layers part is captured with or without the dropout launches),
 // 0 <= p < 1
-int32_t sage_set_dropout(gigl_ctx* ctx, SageTrainShared& s, bool stepped, float p, uint64_t seed) {
+// (S: whatever holds a plan's drop_p / drop_seed — SageTrainShared, gigl_gcn_train_plan)
+extern "C++" template <typename S>
+int32_t sage_set_dropout(gigl_ctx* ctx, S& s, bool stepped, float p, uint64_t seed) {
   GIGL_REQUIRE(ctx, !stepped, "dropout is set after create and before the first step (the step is captured)");
   GIGL_REQUIRE(ctx, p >= 0.f && p < 1.f, "dropout: p must be in [0, 1)");  // (false for a NaN too)
   s.drop_p = p;
@@ -2168,10 +2217,250 @@ int32_t gigl_dropout_mask(gigl_ctx* ctx, uint64_t seed, uint32_t step, int32_t e
 }
 
 int32_t gigl_sage_train_plan_resume(gigl_sage_train_plan* t) {
-  if (!t) return GIGL_E_INVALID_ARG;
-  GIGL_HIP_CHECK(t->ctx, hipSetDevice(t->ctx->device));
-  GIGL_HIP_CHECK(t->ctx, hipMemsetAsync(t->n_valid_buf + 2, 0, 4, t->ctx->stream));
+  return t ? nc_resume(t) : GIGL_E_INVALID_ARG;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// gigl_gcn_train_plan: the same step for the reference's STOCK node-classification model, TwoLayerGCN
+// (python/gigl/src/common/models/pyg/homogeneous.py:488-546: conv1 -> relu -> dropout -> conv2, PyG GCNConv): two layers,
+// each AGGREGATED FIRST (A_hat (X W) == (A_hat X) W: only the rows a layer needs are projected),
+//   a1 = A_hat x[nodes] -> h1 = relu(a1 W1^T + b1) [-> dropout] -> a2 = A_hat h1 -> out = a2 W2^T + b2 -> cross-entropy on the roots
+//   -> dW2, db2 -> da2 = g2 W2 -> dh1 = A_hat^T da2 -> rectifier / dropout mask -> dW1, db1 -> Adam
+// over the GENERIC union graph (every node numbered, as gigl_union_build numbers them: a leaf occurrence of a node that is
+// also an inner node needs that node's degree).  What depends on the batch graph alone — A_hat's dinv over every node,
+// the root rows' transposed lists — belongs to the graph part.  Ring, step, loss, Adam and the dropout kernels are the
+// GraphSAGE plan's (NcTrainState).
+struct gigl_gcn_train_plan : NcTrainState {
+  gigl_feat* feat = nullptr;
+  int32_t dims[3] = {0, 0, 0};     // input, hidden, output width
+  float* w[2] = {nullptr, nullptr};     // conv{1,2}.lin.weight [dims[l+1]][dims[l]]: borrowed, UPDATED IN PLACE
+  float* bias[2] = {nullptr, nullptr};  // conv{1,2}.bias (may be NULL)
+  float* mom[8] = {nullptr};            // m_w, v_w, m_b, v_b per layer
+  float* wt2 = nullptr;                 // W2^T [hid][out], laid out once per step (train_stage_kernel)
+  float lr = 0.f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, wd = 0.f;
+  float drop_p = 0.f;  // dropout on h1 (gigl_gcn_train_plan_set_dropout; 0: none)
+  uint64_t drop_seed = 0;
+  int64_t rows_cap[2] = {0, 0};  // rows layer l may compute: the nodes of level <= 1 - l
+  float *a1 = nullptr, *h1 = nullptr, *a2 = nullptr, *out = nullptr;
+  float *g2 = nullptr, *da2 = nullptr, *dh1 = nullptr;  // gradients of out (in the cleared block), a2, h1
+  float* part_w[2] = {nullptr, nullptr};  // the weight gradients' per-chunk partial sums (Adam adds them up)
+  float* part_b[2] = {nullptr, nullptr};
+  int32_t part_rc[2] = {0, 0};
+  float* dinv[TRAIN_WS] = {nullptr};      // per workspace: 1 / sqrt(deg) of every node of its batch graph
+  int32_t* tlists[TRAIN_WS] = {nullptr};  // ... and who reads which level-<=1 node among the root rows
+};
+
+namespace {
+
+const int32_t* gcn_level(const BatchGraph* p, int level) { return p->un.meta + GIGL_META_LEVEL0 + level; }
+
+// the graph part of workspace p's roots_buf: sample + union, then what the layers need of the batch graph alone
+int32_t gcn_enqueue_graph(const gigl_gcn_train_plan* t, BatchGraph* p, float* dinv, int32_t* tl, int32_t sampling_seed, int32_t mode) {
+  int32_t rc = batch_graph_enqueue(p, sampling_seed, mode);
+  if (rc != GIGL_OK) return rc;
+  rc = gigl_gcn_dinv(p->ctx, p->un.rowptr, p->un.rowend, p->un.col, p->un.meta + GIGL_META_N_NODES, p->un.cap_nodes, dinv);
+  if (rc != GIGL_OK) return rc;
+  return gigl_transposed_rows_build(p->ctx, p->un.rowptr, p->un.rowend, p->un.col, gcn_level(p, 0), t->rows_cap[1],
+                                    gcn_level(p, 1), t->rows_cap[0], p->un.cap_edges, tl);
+}
+
+// everything after the graph part, over workspace k, on lctx's stream (the caller's); train_stage_kernel ran ahead of it
+int32_t gcn_enqueue_layers(gigl_gcn_train_plan* t, int k) {
+  const BatchGraph* p = &t->ring.slot[k].base[0];
+  gigl_ctx* ctx = t->lctx;
+  hipStream_t st = ctx->stream;
+  const gigl_union& un = p->un;
+  const int32_t *n0 = gcn_level(p, 0), *n1 = gcn_level(p, 1);
+  const int d_in = t->dims[0], hid = t->dims[1], width = t->dims[2];
+  const int64_t rows1 = t->rows_cap[0], rows0 = t->rows_cap[1];
+  const int32_t* step_dev = t->n_valid_buf + 1;
+  int32_t rc = gigl_gcn_gather(ctx, t->feat->rows, t->feat->dtype, d_in, un.nodes, t->dinv[k], un.rowptr, un.rowend, un.col, n1,
+                               rows1, t->a1);
+  if (rc == GIGL_OK) rc = gigl_linear(ctx, t->a1, t->w[0], t->bias[0], n1, rows1, d_in, hid, 1, t->h1);
+  if (rc != GIGL_OK) return rc;
+  if (t->drop_p > 0.f) {  // (*step_dev is read before the loss launch moves it on)
+    const int lg = dropout_lanes_log2(hid);
+    hipLaunchKernelGGL(dropout_rows_kernel, dim3(blocks_256(rows1 << lg)), dim3(256), 0, st, t->h1, n1, rows1, hid, step_dev,
+                       gigl_dropout_mask_args(t->drop_seed, t->drop_p, 0, 0), lg);
+    GIGL_HIP_CHECK(ctx, hipGetLastError());
+  }
+  rc = gigl_gcn_gather(ctx, t->h1, GIGL_DTYPE_F32, hid, nullptr, t->dinv[k], un.rowptr, un.rowend, un.col, n0, rows0, t->a2);
+  if (rc == GIGL_OK) rc = gigl_linear(ctx, t->a2, t->w[1], t->bias[1], n0, rows0, hid, width, 0, t->out);
+  if (rc != GIGL_OK) return rc;
+  nc_loss_launches(t, st, p, t->out, width, t->g2);
+  // ---- backward: layer 2's weights, its operand's gradient through W2 (g2 . W2 over W2^T as the projection's weight
+  // operand), A_hat^T, the rectifier (with dropout: the mask that carries the kept elements' scale), layer 1's weights
+  rc = gigl_linear_weight_grad_parts(ctx, t->g2, t->a2, nullptr, n0, rows0, width, hid, t->part_w[1], t->bias[1] ? t->part_b[1] : nullptr);
+  if (rc == GIGL_OK) rc = gigl_linear(ctx, t->g2, t->wt2, nullptr, n0, rows0, width, hid, 0, t->da2);
+  if (rc == GIGL_OK)
+    rc = gigl_gcn_gather_backward_lists(ctx, t->da2, hid, t->dinv[k], un.rowptr, un.rowend, n0, n1, rows1, t->tlists[k], t->dh1);
+  if (rc != GIGL_OK) return rc;
+  if (t->drop_p > 0.f) {
+    const int whole = (hid & 3) == 0 && (((uintptr_t)t->dh1 | (uintptr_t)t->h1) & 15) == 0;
+    hipLaunchKernelGGL(dropout_relu_mask_kernel, dim3(blocks_256(rows1 * hid / (whole ? 4 : 1))), dim3(256), 0, st, t->dh1,
+                       (const float*)t->h1, n1, rows1, hid, 1.0f / (1.0f - t->drop_p), whole);
+  } else {
+    hipLaunchKernelGGL(relu_mask_kernel, dim3(blocks_256(rows1 * hid)), dim3(256), 0, st, t->dh1, (const float*)t->h1, n1, hid);
+  }
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  // (the first layer's input is the feature table: no gradient)
+  rc = gigl_linear_weight_grad_parts(ctx, t->dh1, t->a1, nullptr, n1, rows1, hid, d_in, t->part_w[0], t->bias[0] ? t->part_b[0] : nullptr);
+  if (rc != GIGL_OK) return rc;
+  AdamPack ap{};
+  ap.n_src = 1;
+  for (int l = 0; l < 2; ++l)
+    for (int is_bias = 0; is_bias < (t->bias[l] ? 2 : 1); ++is_bias) {
+      const int q = ap.count++;
+      ap.p[q] = is_bias ? t->bias[l] : t->w[l];
+      ap.m[q] = t->mom[4 * l + 2 * is_bias];
+      ap.v[q] = t->mom[4 * l + 2 * is_bias + 1];
+      ap.n[q] = is_bias ? (int64_t)t->dims[l + 1] : (int64_t)t->dims[l + 1] * t->dims[l];
+      ap.part[0][q] = is_bias ? t->part_b[l] : t->part_w[l];
+      ap.rows[0][q] = gcn_level(p, 1 - l);
+      ap.rc[0][q] = t->part_rc[l];
+    }
+  ap.lr = t->lr;
+  ap.beta1 = t->beta1;
+  ap.beta2 = t->beta2;
+  ap.eps = t->eps;
+  ap.wd = t->wd;
+  launch_adam(st, 208, ap, step_dev, (const int32_t*)un.meta, (const int32_t*)nullptr, (const int32_t*)(t->n_valid_buf + 2), nullptr);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
+}
+
+// elements of layer l's weight (is_bias: of its bias)
+size_t gcn_tensor_floats(const gigl_gcn_train_plan* t, int l, int is_bias) {
+  return is_bias ? (size_t)t->dims[l + 1] : (size_t)t->dims[l + 1] * t->dims[l];
+}
+
+}  // namespace
+
+int32_t gigl_gcn_train_plan_destroy(gigl_gcn_train_plan* t) {
+  if (!t) return GIGL_OK;
+  nc_state_release(t);
+  delete t;
+  return GIGL_OK;
+}
+
+int32_t gigl_gcn_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, int32_t b, const int32_t* fanouts,
+                                   const int32_t* dims, float* const* w, float* const* bias, float lr, float beta1, float beta2,
+                                   float eps, float weight_decay, gigl_gcn_train_plan** out) {
+  if (!ctx || !out) return GIGL_E_INVALID_ARG;
+  *out = nullptr;
+  GIGL_REQUIRE(ctx, graph && feat && fanouts && dims && w, "null argument");
+  GIGL_REQUIRE(ctx, b >= 1, "bad plan shape");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  gigl_gcn_train_plan* t = new (std::nothrow) gigl_gcn_train_plan();
+  if (!t) return gigl_fail(ctx, GIGL_E_OOM, "host OOM");
+  t->ctx = ctx;
+  t->feat = feat;
+  t->b = b;
+  int32_t rc = gigl_ctx_create(ctx->device, &t->lctx);
+  if (rc == GIGL_OK) rc = plan_check_layers(ctx, feat, 2, dims, w);
+  if (rc == GIGL_OK) rc = t->ring.create(ctx, TRAIN_WS, 1, &b, graph, fanouts, 2, true);
+  if (rc != GIGL_OK) {
+    gigl_gcn_train_plan_destroy(t);
+    return rc;
+  }
+  t->lr = lr;
+  t->beta1 = beta1;
+  t->beta2 = beta2;
+  t->eps = eps;
+  t->wd = weight_decay;
+  auto floats = [&](size_t n) { return (float*)plan_alloc(t->owned, n * 4); };
+  bool ok = true;
+  for (int l = 0; l <= 2; ++l) t->dims[l] = dims[l];
+  for (int l = 0; l < 2; ++l) {
+    t->w[l] = w[l];
+    t->bias[l] = bias ? bias[l] : nullptr;
+    t->rows_cap[l] = gigl_level_rows(ctx->wide, b, fanouts, 2, 1 - l);
+    for (int q = 0; q < 4; ++q) {
+      const size_t n = gcn_tensor_floats(t, l, q >> 1);
+      t->mom[4 * l + q] = floats(n);
+      ok = ok && t->mom[4 * l + q] && hipMemset(t->mom[4 * l + q], 0, n * 4) == hipSuccess;
+    }
+    const int64_t chunks = gigl_linear_weight_grad_chunks(t->rows_cap[l], dims[l + 1], dims[l], &t->part_rc[l]);
+    t->part_w[l] = floats((size_t)chunks * gcn_tensor_floats(t, l, 0));
+    t->part_b[l] = floats((size_t)chunks * dims[l + 1]);
+    ok = ok && t->part_w[l] && t->part_b[l];
+  }
+  const size_t rows1 = (size_t)t->rows_cap[0], rows0 = (size_t)t->rows_cap[1];
+  t->wt2 = floats(gcn_tensor_floats(t, 1, 0));
+  t->a1 = floats(rows1 * dims[0]);
+  t->h1 = floats(rows1 * dims[1]);
+  t->dh1 = floats(rows1 * dims[1]);
+  t->a2 = floats(rows0 * dims[1]);
+  t->da2 = floats(rows0 * dims[1]);
+  t->out = floats(rows0 * dims[2]);
+  // (the cleared block: the roots' loss gradient is ADDED to — two roots of a batch may be one node)
+  ok = nc_state_alloc(*t, rows0 * dims[2]) && ok;
+  t->g2 = (float*)t->zero_base;
+  for (int k = 0; k < TRAIN_WS; ++k) {
+    const gigl_union& un = t->ring.slot[k].base[0].un;
+    t->dinv[k] = floats((size_t)un.cap_nodes);
+    t->tlists[k] = (int32_t*)plan_alloc(t->owned, (size_t)gigl_transposed_rows_words(t->rows_cap[0], un.cap_edges) * 4);
+    ok = ok && t->dinv[k] && t->tlists[k];
+  }
+  ok = ok && t->wt2 && t->a1 && t->h1 && t->dh1 && t->a2 && t->da2 && t->out;
+  if (!ok) {
+    gigl_gcn_train_plan_destroy(t);
+    return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the training workspace failed");
+  }
+  *out = t;
+  return GIGL_OK;
+}
+
+int32_t gigl_gcn_train_plan_step2(gigl_gcn_train_plan* t, const uint32_t* roots, const int64_t* labels, int32_t n_valid,
+                                  const uint32_t* roots_next, const uint32_t* roots_next2, int32_t sampling_seed, int32_t mode,
+                                  float* loss_out) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  TrainPrep pa{};  // train_stage_kernel clears the roots' loss gradient and lays out W2^T
+  pa.zero = (uint32_t*)t->zero_base;
+  pa.zero_words = (int64_t)(t->zero_bytes / 4);
+  pa.w[0] = t->w[1];
+  pa.wt[0] = t->wt2;
+  pa.rows[0] = t->dims[2];
+  pa.cols[0] = t->dims[1];
+  pa.n_t = 1;
+  return nc_train_step(
+      t, roots, labels, n_valid, roots_next, roots_next2, sampling_seed, mode, loss_out, pa,
+      [&](int kk) { return gcn_enqueue_graph(t, &t->ring.slot[kk].base[0], t->dinv[kk], t->tlists[kk], sampling_seed, mode); },
+      [&](int k) { return gcn_enqueue_layers(t, k); });
+}
+
+const float* gigl_gcn_train_plan_loss(gigl_gcn_train_plan* t) { return t ? t->loss : nullptr; }
+
+int32_t gigl_gcn_train_plan_resume(gigl_gcn_train_plan* t) { return t ? nc_resume(t) : GIGL_E_INVALID_ARG; }
+
+int32_t gigl_gcn_train_plan_set_dropout(gigl_gcn_train_plan* t, float p, uint64_t seed) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  return sage_set_dropout(t->ctx, *t, t->stepped, p, seed);
+}
+
+int32_t gigl_gcn_train_plan_moments(gigl_gcn_train_plan* t, int32_t layer, float* m_w, float* v_w, float* m_b, float* v_b) {
+  if (!t) return GIGL_E_INVALID_ARG;
+  gigl_ctx* ctx = t->ctx;
+  GIGL_REQUIRE(ctx, layer >= 0 && layer < 2, "layer %d", layer);
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  float* dst[4] = {m_w, v_w, m_b, v_b};
+  for (int q = 0; q < 4; ++q)
+    if (dst[q])
+      GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst[q], t->mom[4 * layer + q], gcn_tensor_floats(t, layer, q >> 1) * 4,
+                                         hipMemcpyDeviceToDevice, ctx->stream));
+  return GIGL_OK;
+}
+
+int32_t gigl_gcn_train_plan_adopt(gigl_gcn_train_plan* dst, gigl_gcn_train_plan* src) {
+  if (!dst || !src) return GIGL_E_INVALID_ARG;
+  gigl_ctx* ctx = dst->ctx;
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  GIGL_HIP_CHECK(ctx, hipStreamSynchronize(src->ctx->stream));
+  for (int l = 0; l <= 2; ++l) GIGL_REQUIRE(ctx, dst->dims[l] == src->dims[l], "plans of different widths");
+  for (int q = 0; q < 8; ++q)
+    GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->mom[q], src->mom[q], gcn_tensor_floats(dst, q >> 2, (q >> 1) & 1) * 4,
+                                       hipMemcpyDeviceToDevice, ctx->stream));
+  return nc_adopt_counter(dst, src);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -3012,10 +3301,7 @@ int32_t gigl_sage_train_plan_adopt(gigl_sage_train_plan* dst, gigl_sage_train_pl
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   GIGL_HIP_CHECK(ctx, hipStreamSynchronize(src->ctx->stream));
   const int32_t rc = sage_moments_adopt(ctx, *dst, *src);
-  if (rc != GIGL_OK) return rc;
-  GIGL_HIP_CHECK(ctx, hipMemcpyAsync(dst->n_valid_buf + 1, src->n_valid_buf + 1, 4, hipMemcpyDeviceToDevice, ctx->stream));
-  GIGL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return GIGL_OK;
+  return rc != GIGL_OK ? rc : nc_adopt_counter(dst, src);
 }
 
 int32_t gigl_nablp_train_plan_adopt(gigl_nablp_train_plan* dst, gigl_nablp_train_plan* src) {

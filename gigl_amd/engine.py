@@ -1406,52 +1406,44 @@ class SagePlan:
                 self.eng._plans.remove(self)
 
 
-class SageTrainPlan:
-    """one TRAINING step per call in the library (include/gigl_hip.h `gigl_sage_train_plan_*`): sample -> union graph ->
-    GraphSAGE forward -> cross-entropy on the roots -> backward -> Adam, replayed as one hipGraph per step.  The plan
-    trains FUSED weights [W_l | W_r] (and biases) held here as torch tensors and updated in place by every step;
-    `load(model)` / `store(model)` move them from / to a models.GraphSAGE (Adam is element-wise: training the fused
-    matrix is training lin_l.weight and lin_r.weight)."""
+class _RootTrainPlan:
+    """what the node-classification training plans share (SageTrainPlan, GcnTrainPlan): one family of library entry points
+    `<_PREFIX>_{create, step2, resume, adopt, moments, set_dropout, destroy}` with one contract (include/gigl_hip.h
+    `gigl_sage_train_plan_*`) — the step over padded roots, the redo of a batch that overflowed after growing, the
+    device-side halt and resume.  A subclass holds the parameters (load / store / moments) and opens the plan (_open)."""
+    _PREFIX = ""
 
-    def __init__(self, eng: HipEngine, model, b: int, fanouts, lr: float = 0.01, weight_decay: float = 5e-4,
-                 betas=(0.9, 0.999), eps: float = 1e-8, dropout: Optional[float] = None, dropout_seed: int = 0):
-        """dropout: p of the dropout after every activated layer (None: model.dropout.p), drawn from the library's own
-        counter-based stream (HipEngine.dropout_mask reproduces a step's mask; torch's stream is another: a plan step and an
-        autograd step of the same job drop different elements of the same distribution); dropout_seed: its 64-bit seed"""
-        assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
-        L = len(fanouts)
-        assert model.num_layers == L, "one hop per layer"
-        if not (model._plain_but_dropout and model.aggr == "mean" and not model.should_l2_normalize_embedding_layer_output
-                and model.feats_interaction is None and model.feature_embedding_layer is None
-                and all(c.lin_r is not None for c in model.conv_layers)):
-            raise NotImplementedError("the training plan runs plain mean-GraphSAGE layers (conv -> relu -> dropout)")
+    def _entry(self, name: str):
+        return getattr(self._lib, f"{self._PREFIX}_{name}")
+
+    def _open(self, eng: "HipEngine", b: int, fanouts, create_call) -> None:
+        """create_call(byref(handle)) -> rc: the library's create over this object's parameter tensors; the plan is created
+        (and re-created wide by grow) through it, its dropout applied before the first step"""
         self.eng, self.b, self.fanouts = eng, int(b), [int(f) for f in fanouts]
-        self._lib = eng._lib
-        self._dropout = _plan_dropout(model, dropout, dropout_seed)
-        self.w, self.bias = [], []
-        self.load(model)
-        self.dims = [int(self.w[0].shape[1]) // 2] + [int(w.shape[0]) for w in self.w]
-        w_arr = (C.c_void_p * L)(*[w.data_ptr() for w in self.w])
-        b_arr = (C.c_void_p * L)(*[(x.data_ptr() if x is not None else None) for x in self.bias])
-        fo = (C.c_int32 * L)(*self.fanouts)
-        dims = (C.c_int32 * (L + 1))(*self.dims)
-        act_last = 1 if model.activation_after_last_conv else 0
 
         def create():
             h = C.c_void_p()
-            check(self._lib.gigl_sage_train_plan_create(eng._ctx, eng._graph, eng._feat, self.b, fo, L, dims, w_arr, b_arr,
-                                                        act_last, float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                                        float(weight_decay), C.byref(h)), eng._ctx)
+            check(create_call(C.byref(h)), eng._ctx)
             try:
-                self._apply_dropout(h, self._lib.gigl_sage_train_plan_set_dropout)
+                self._apply_dropout(h, self._entry("set_dropout"))
             except Exception:
-                self._lib.gigl_sage_train_plan_destroy(h)
+                self._entry("destroy")(h)
                 raise
             return h
-        self._create, self._adopt, self._destroy = create, self._lib.gigl_sage_train_plan_adopt, self._lib.gigl_sage_train_plan_destroy
+        self._create, self._adopt, self._destroy = create, self._entry("adopt"), self._entry("destroy")
         self.wide = False
         self._plan = create()
         self.loss = torch.zeros(1, dtype=torch.float32, device=eng.device)  # the last step's loss (device scalar)
+
+    def _layer_moments(self, layer: int, w: torch.Tensor, b: Optional[torch.Tensor]):
+        """Adam's (exp_avg, exp_avg_sq) of `layer`'s weight and bias, shaped like w and b (the bias pair None without one)"""
+        mw, vw = torch.empty_like(w), torch.empty_like(w)
+        mb = vb = None
+        if b is not None:
+            mb, vb = torch.empty_like(b), torch.empty_like(b)
+        p_ = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(self._entry("moments")(self._plan, layer, p_(mw), p_(vw), p_(mb), p_(vb)), self.eng._ctx)
+        return (mw, vw), (mb, vb)
 
     def _apply_dropout(self, handle, setter) -> None:
         """the dropout of a (re)created plan handle, before its first step (called inside create(), so that grow()'s wide
@@ -1459,30 +1451,6 @@ class SageTrainPlan:
         p, seed = self._dropout
         if p != 0.0:  # (0 = none; anything else is the library's to judge)
             check(setter(handle, p, seed), self.eng._ctx)
-
-    def load(self, model) -> None:
-        """(re)read the model's parameters into the fused buffers the plan trains (in place when they exist)"""
-        ws = [c.fused_weight().detach().to(device=self.eng.device, dtype=torch.float32).contiguous() for c in model.conv_layers]
-        bs = [None if c.lin_l.bias is None else c.lin_l.bias.detach().to(device=self.eng.device, dtype=torch.float32)
-              .clone().contiguous() for c in model.conv_layers]
-        if self.w:
-            for dst, src in zip(self.w, ws):
-                dst.copy_(src)
-            for dst, src in zip(self.bias, bs):
-                if dst is not None:
-                    dst.copy_(src)
-        else:
-            self.w, self.bias = ws, bs
-
-    def store(self, model) -> None:
-        """write the trained parameters back into the model (lin_l.weight | lin_r.weight halves of the fused matrix)"""
-        with torch.no_grad():
-            for c, w, b in zip(model.conv_layers, self.w, self.bias):
-                d = c.in_channels
-                c.lin_l.weight.copy_(w[:, :d])
-                c.lin_r.weight.copy_(w[:, d:])
-                if b is not None:
-                    c.lin_l.bias.copy_(b)
 
     def grow(self) -> None:
         """re-create the plan with workspaces for the WORST batch (gigl_ctx_set_wide_workspaces: rows for every node of the
@@ -1520,27 +1488,9 @@ class SageTrainPlan:
             roots = torch.cat([roots, roots[:1].expand(self.b - k)])
         return roots.contiguous()
 
-    def moments(self) -> dict:
-        """Adam's moments as torch.optim.Adam names them, keyed like the model's state dict: {"conv_layers.l.lin_l.weight":
-        (exp_avg, exp_avg_sq), ...lin_r.weight, ...lin_l.bias} (gigl_sage_train_plan_moments; the fused matrix split back)"""
-        out = {}
-        for l, (w, b) in enumerate(zip(self.w, self.bias)):
-            mw, vw = torch.empty_like(w), torch.empty_like(w)
-            mb = vb = None
-            if b is not None:
-                mb, vb = torch.empty_like(b), torch.empty_like(b)
-            p_ = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-            check(self._lib.gigl_sage_train_plan_moments(self._plan, l, p_(mw), p_(vw), p_(mb), p_(vb)), self.eng._ctx)
-            d = int(w.shape[1]) // 2
-            out[f"conv_layers.{l}.lin_l.weight"] = (mw[:, :d], vw[:, :d])
-            out[f"conv_layers.{l}.lin_r.weight"] = (mw[:, d:], vw[:, d:])
-            if b is not None:
-                out[f"conv_layers.{l}.lin_l.bias"] = (mb, vb)
-        return out
-
     def resume(self) -> None:
         """clear the device-side halt a failed batch left (gigl_sage_train_plan_resume): later steps train again"""
-        check(self._lib.gigl_sage_train_plan_resume(self._plan), self.eng._ctx)
+        check(self._entry("resume")(self._plan), self.eng._ctx)
 
     def run_steps(self, n_steps: int, step_args) -> torch.Tensor:
         """steps 0 .. n_steps-1 issued back to back WITHOUT a host read (step_args(i) -> the kwargs of step i), their losses
@@ -1583,15 +1533,154 @@ class SageTrainPlan:
         self._keep = (tuple(getattr(self, "_keep", ()))[-2:]) + ((roots, nxt, nxt2),)
         p_ = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         out = self.loss if loss_out is None else loss_out  # (loss_out: a float32 device slot of the caller's)
-        check(self._lib.gigl_sage_train_plan_step2(self._plan, p_(roots), p_(labels), k, p_(nxt), p_(nxt2),
-                                                   int(sampling_seed), int(mode), p_(out)), self.eng._ctx)
+        check(self._entry("step2")(self._plan, p_(roots), p_(labels), k, p_(nxt), p_(nxt2), int(sampling_seed), int(mode),
+                                   p_(out)), self.eng._ctx)
         return out
 
     def close(self) -> None:
         if getattr(self, "_plan", None):
-            self._lib.gigl_sage_train_plan_destroy(self._plan)
+            self._destroy(self._plan)
             self._plan = None
         self._create = None  # (drops the argument arrays it holds)
+
+
+class SageTrainPlan(_RootTrainPlan):
+    """one TRAINING step per call in the library (include/gigl_hip.h `gigl_sage_train_plan_*`): sample -> union graph ->
+    GraphSAGE forward -> cross-entropy on the roots -> backward -> Adam, replayed as one hipGraph per step.  The plan
+    trains FUSED weights [W_l | W_r] (and biases) held here as torch tensors and updated in place by every step;
+    `load(model)` / `store(model)` move them from / to a models.GraphSAGE (Adam is element-wise: training the fused
+    matrix is training lin_l.weight and lin_r.weight)."""
+    _PREFIX = "gigl_sage_train_plan"
+
+    def __init__(self, eng: HipEngine, model, b: int, fanouts, lr: float = 0.01, weight_decay: float = 5e-4,
+                 betas=(0.9, 0.999), eps: float = 1e-8, dropout: Optional[float] = None, dropout_seed: int = 0):
+        """dropout: p of the dropout after every activated layer (None: model.dropout.p), drawn from the library's own
+        counter-based stream (HipEngine.dropout_mask reproduces a step's mask; torch's stream is another: a plan step and an
+        autograd step of the same job drop different elements of the same distribution); dropout_seed: its 64-bit seed"""
+        assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
+        L = len(fanouts)
+        assert model.num_layers == L, "one hop per layer"
+        if not (model._plain_but_dropout and model.aggr == "mean" and not model.should_l2_normalize_embedding_layer_output
+                and model.feats_interaction is None and model.feature_embedding_layer is None
+                and all(c.lin_r is not None for c in model.conv_layers)):
+            raise NotImplementedError("the training plan runs plain mean-GraphSAGE layers (conv -> relu -> dropout)")
+        self.eng, self._lib = eng, eng._lib
+        self._dropout = _plan_dropout(model, dropout, dropout_seed)
+        self.w, self.bias = [], []
+        self.load(model)
+        self.dims = [int(self.w[0].shape[1]) // 2] + [int(w.shape[0]) for w in self.w]
+        w_arr = (C.c_void_p * L)(*[w.data_ptr() for w in self.w])
+        b_arr = (C.c_void_p * L)(*[(x.data_ptr() if x is not None else None) for x in self.bias])
+        fo = (C.c_int32 * L)(*[int(f) for f in fanouts])
+        dims = (C.c_int32 * (L + 1))(*self.dims)
+        act_last = 1 if model.activation_after_last_conv else 0
+        self._open(eng, b, fanouts, lambda h: self._lib.gigl_sage_train_plan_create(
+            eng._ctx, eng._graph, eng._feat, int(b), fo, L, dims, w_arr, b_arr, act_last, float(lr), float(betas[0]),
+            float(betas[1]), float(eps), float(weight_decay), h))
+
+    def load(self, model) -> None:
+        """(re)read the model's parameters into the fused buffers the plan trains (in place when they exist)"""
+        ws = [c.fused_weight().detach().to(device=self.eng.device, dtype=torch.float32).contiguous() for c in model.conv_layers]
+        bs = [None if c.lin_l.bias is None else c.lin_l.bias.detach().to(device=self.eng.device, dtype=torch.float32)
+              .clone().contiguous() for c in model.conv_layers]
+        if self.w:
+            for dst, src in zip(self.w, ws):
+                dst.copy_(src)
+            for dst, src in zip(self.bias, bs):
+                if dst is not None:
+                    dst.copy_(src)
+        else:
+            self.w, self.bias = ws, bs
+
+    def store(self, model) -> None:
+        """write the trained parameters back into the model (lin_l.weight | lin_r.weight halves of the fused matrix)"""
+        with torch.no_grad():
+            for c, w, b in zip(model.conv_layers, self.w, self.bias):
+                d = c.in_channels
+                c.lin_l.weight.copy_(w[:, :d])
+                c.lin_r.weight.copy_(w[:, d:])
+                if b is not None:
+                    c.lin_l.bias.copy_(b)
+
+    def moments(self) -> dict:
+        """Adam's moments as torch.optim.Adam names them, keyed like the model's state dict: {"conv_layers.l.lin_l.weight":
+        (exp_avg, exp_avg_sq), ...lin_r.weight, ...lin_l.bias} (gigl_sage_train_plan_moments; the fused matrix split back)"""
+        out = {}
+        for l, (w, b) in enumerate(zip(self.w, self.bias)):
+            (mw, vw), (mb, vb) = self._layer_moments(l, w, b)
+            d = int(w.shape[1]) // 2
+            out[f"conv_layers.{l}.lin_l.weight"] = (mw[:, :d], vw[:, :d])
+            out[f"conv_layers.{l}.lin_r.weight"] = (mw[:, d:], vw[:, d:])
+            if b is not None:
+                out[f"conv_layers.{l}.lin_l.bias"] = (mb, vb)
+        return out
+
+
+class GcnTrainPlan(_RootTrainPlan):
+    """the same step for the reference's stock node-classification model, models_attn.TwoLayerGCN (include/gigl_hip.h
+    `gigl_gcn_train_plan_*`: GCNConv -> relu -> dropout -> GCNConv over the generic union graph, cross-entropy on the roots,
+    backward, Adam).  The plan trains conv{1,2}.lin.weight / conv{1,2}.bias as PyG keeps them, held here as torch tensors
+    and updated in place; `load(model)` / `store(model)` move them from / to the model."""
+    _PREFIX = "gigl_gcn_train_plan"
+
+    @staticmethod
+    def applies(model, feat_dim: int) -> bool:
+        """the plan computes exactly TwoLayerGCN over a table of feat_dim columns, without the L2-normalised output"""
+        from .models_attn import TwoLayerGCN
+        return type(model) is TwoLayerGCN and int(model.conv1.in_channels) == int(feat_dim) and not model.should_normalize
+
+    def __init__(self, eng: HipEngine, model, b: int, fanouts, lr: float = 0.01, weight_decay: float = 5e-4,
+                 betas=(0.9, 0.999), eps: float = 1e-8, dropout_seed: int = 0):
+        """dropout is the module's own (models_attn.TwoLayerGCN._forward_graph): p = 0.5 iff model.is_training, drawn from
+        the library's counter-based stream under dropout_seed (HipEngine.dropout_mask reproduces a step's mask)"""
+        assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
+        if not self.applies(model, getattr(eng, "feat_dim", None) or -1):
+            raise NotImplementedError("the GCN training plan runs models_attn.TwoLayerGCN over the loaded feature table, "
+                                      "without an L2-normalised output")
+        if len(fanouts) != 2:
+            raise NotImplementedError("TwoLayerGCN has two layers: one hop each")
+        self.eng, self._lib = eng, eng._lib
+        self._dropout = (0.5 if model.is_training else 0.0, int(dropout_seed) & 0xFFFFFFFFFFFFFFFF)
+        self.w, self.bias = [], []
+        self.load(model)
+        self.dims = [int(self.w[0].shape[1]), int(self.w[0].shape[0]), int(self.w[1].shape[0])]
+        w_arr = (C.c_void_p * 2)(*[w.data_ptr() for w in self.w])
+        b_arr = (C.c_void_p * 2)(*[(x.data_ptr() if x is not None else None) for x in self.bias])
+        fo = (C.c_int32 * 2)(*[int(f) for f in fanouts])
+        dims = (C.c_int32 * 3)(*self.dims)
+        self._open(eng, b, fanouts, lambda h: self._lib.gigl_gcn_train_plan_create(
+            eng._ctx, eng._graph, eng._feat, int(b), fo, dims, w_arr, b_arr, float(lr), float(betas[0]), float(betas[1]),
+            float(eps), float(weight_decay), h))
+
+    def load(self, model) -> None:
+        """(re)read the model's parameters into the buffers the plan trains (in place when they exist)"""
+        take = lambda t: None if t is None else t.detach().to(device=self.eng.device, dtype=torch.float32).clone().contiguous()
+        ws = [take(c.lin.weight) for c in (model.conv1, model.conv2)]
+        bs = [take(c.bias) for c in (model.conv1, model.conv2)]
+        if self.w:
+            for dst, src in zip(self.w + self.bias, ws + bs):
+                if dst is not None:
+                    dst.copy_(src)
+        else:
+            self.w, self.bias = ws, bs
+
+    def store(self, model) -> None:
+        """write the trained parameters back into the model"""
+        with torch.no_grad():
+            for c, w, b in zip((model.conv1, model.conv2), self.w, self.bias):
+                c.lin.weight.copy_(w)
+                if b is not None:
+                    c.bias.copy_(b)
+
+    def moments(self) -> dict:
+        """Adam's moments as torch.optim.Adam names them, keyed like the model's state dict: {"conv1.lin.weight": (exp_avg,
+        exp_avg_sq), "conv1.bias", "conv2.lin.weight", "conv2.bias"} (gigl_gcn_train_plan_moments)"""
+        out = {}
+        for l, (w, b) in enumerate(zip(self.w, self.bias)):
+            out[f"conv{l + 1}.lin.weight"], mb = self._layer_moments(l, w, b)
+            if b is not None:
+                out[f"conv{l + 1}.bias"] = mb
+        return out
 
 
 def _plan_dropout(model, dropout: Optional[float], seed: int):

@@ -183,7 +183,8 @@ class HipGraphSageNodeClassificationSpec(BaseTrainer, BaseInferencer):
         self._resident = ResidentGraph(cfg, self._device, rank=rank, world=world, sharded=want_shards)
         self.hbm_graph = "sharded" if self._resident.sharded else "replica"  # (kept after close(): what the job ran on)
         # (plain GraphSAGE trains over HipBatches — and through the library's training plan; every other encoder, and
-        # every encoder on a sharded graph, over the same in-HBM batch as a GraphData built on the device)
+        # every encoder on a sharded graph, over the same in-HBM batch as a GraphData built on the device — but for the stock
+        # TwoLayerGCN on a replica graph, which _train_graphed hands to the library's GCN plan)
         self._resident.train_as_graph_data = want_shards or not encoder_trains_over_hip_batches(self._inner_model())
         ids, labels = self._resident.labeled_root_order()
         splits = {}
@@ -269,13 +270,21 @@ class HipGraphSageNodeClassificationSpec(BaseTrainer, BaseInferencer):
                 getattr(self, "_graph_capture_failed", False):
             return None
         hbm = self._hbm_split(cfg)
-        if hbm is None or self._resident.train_as_graph_data:
-            return None  # (a GraphData batch reads its sizes on the host: the eager loop)
+        if hbm is None:
+            return None
         ids, labels = hbm["train"]
         if ids.size == 0:
             return None
         b = self._batch_size
         res = self._resident
+        if res.train_as_graph_data:
+            # a GraphData batch reads its sizes on the host: the eager loop — but for the stock TwoLayerGCN on a replica
+            # graph, whose whole step the library runs (engine.GcnTrainPlan).  There is nothing between the two: the
+            # model has no autograd forward over a HipBatch for GraphedTrainStep to capture
+            from .engine import GcnTrainPlan
+            if res.sharded or not GcnTrainPlan.applies(self._inner_model(), getattr(res.engine, "feat_dim", None) or -1):
+                return None
+            return self._train_library_plan(res, ids, labels, b, device)
         loss = self._train_library_plan(res, ids, labels, b, device)
         if loss is not None:
             return loss
@@ -302,24 +311,28 @@ class HipGraphSageNodeClassificationSpec(BaseTrainer, BaseInferencer):
         return loss.detach().clone()
 
     def _train_library_plan(self, res, ids: np.ndarray, labels: np.ndarray, b: int, device: torch.device):
-        """one epoch through the library's training plan (engine.SageTrainPlan: sample -> union -> forward -> cross-entropy
-        -> backward -> Adam in ONE captured library call per step, no torch kernel in between) — plain mean-GraphSAGE
-        encoders under this spec's optimiser settings; None = not applicable (the autograd step is then used).
-        GIGL_AMD_TRAIN_PLAN=0 keeps the autograd step."""
+        """one epoch through the library's training plan (engine.SageTrainPlan / engine.GcnTrainPlan: sample -> union ->
+        forward -> cross-entropy -> backward -> Adam in ONE captured library call per step, no torch kernel in between) —
+        plain mean-GraphSAGE encoders and the stock TwoLayerGCN under this spec's optimiser settings; None = not applicable
+        (the autograd step is then used).  GIGL_AMD_TRAIN_PLAN=0 keeps the autograd step."""
         import os
         if os.environ.get("GIGL_AMD_TRAIN_PLAN", "1") == "0":
             return None
         from ._lib import MODE_REPLACE
-        from .engine import SageTrainPlan
+        from .engine import GcnTrainPlan, SageTrainPlan
         model = self._inner_model()
         plan = getattr(self, "_train_plan", None)
         if plan is None:
             if getattr(self, "_train_plan_unavailable", False) or res.mode == MODE_REPLACE:
                 return None
             try:
-                plan = SageTrainPlan(res.engine, model, b, res.fanouts, lr=self._optim_lr,
-                                     weight_decay=self._optim_weight_decay, dropout=self._dropout,
-                                     dropout_seed=self._dropout_seed)
+                if GcnTrainPlan.applies(model, getattr(res.engine, "feat_dim", None) or -1):
+                    plan = GcnTrainPlan(res.engine, model, b, res.fanouts, lr=self._optim_lr,
+                                        weight_decay=self._optim_weight_decay, dropout_seed=self._dropout_seed)
+                else:
+                    plan = SageTrainPlan(res.engine, model, b, res.fanouts, lr=self._optim_lr,
+                                         weight_decay=self._optim_weight_decay, dropout=self._dropout,
+                                         dropout_seed=self._dropout_seed)
             except NotImplementedError:
                 self._train_plan_unavailable = True
                 return None

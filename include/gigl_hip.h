@@ -804,6 +804,33 @@ int32_t gigl_gcn_aggregate(gigl_ctx* ctx, const void* h, int32_t h_dtype, int32_
                            const int32_t* n_nodes_dev, int64_t nodes_cap, const int32_t* n_rows_dev,
                            int64_t rows_cap, const float* bias, int32_t act, float* dinv_scratch, float* out);
 
+/* The same aggregation in the pieces a TRAINING step needs (PyG 2.5.3 GCNConv as used by TwoLayerGCN,
+ * python/gigl/src/common/models/pyg/homogeneous.py:488-546): the normalisation depends on the batch graph alone, the
+ * gather runs once per layer, and the step needs its transpose.
+ * gigl_gcn_dinv: dinv[i] = 1 / sqrt(1 + #{e in row i : col[e] != i}) for i < *n_nodes_dev (PyG's gcn_norm after
+ *   add_remaining_self_loops: one self loop per node, a stored one replaced).  dinv: DEVICE fp32 [nodes_cap]. */
+int32_t gigl_gcn_dinv(gigl_ctx* ctx, const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
+                      const int32_t* n_nodes_dev, int64_t nodes_cap, float* dinv);
+/* gigl_gcn_gather (GCNConv.propagate of homogeneous.py:488-546 / PyG GCNConv, no bias, no activation: the projection
+ *   follows): out[i][0:d] = dinv_i * (dinv_i * h[idx(i)] + sum_{e in row i, j = col[e] != i} dinv_j * h[idx(j)]) for
+ *   i < *n_rows_dev, idx(j) = gather_ids ? gather_ids[j] : j.  h: [*, d] fp32 / fp16 rows, out: fp32 [rows_cap][d]; rows
+ *   at and beyond *n_rows_dev are not touched.  A stored self loop is skipped, a source stored twice counts twice.  dinv
+ *   covers every id a row names.  Any d >= 1: 16-byte loads for d % 4 == 0, d <= 1024 and aligned rows, else element
+ *   loads.  fp32 sums in an order fixed by the row: two runs give the same bits. */
+int32_t gigl_gcn_gather(gigl_ctx* ctx, const void* h, int32_t h_dtype, int32_t d, const uint32_t* gather_ids,
+                        const float* dinv, const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
+                        const int32_t* n_rows_dev, int64_t rows_cap, float* out);
+/* gigl_gcn_gather_backward_lists: the transpose of gigl_gcn_gather (the backward of GCNConv.propagate,
+ *   homogeneous.py:488-546 / PyG GCNConv) as a gather over the transposed rows gigl_transposed_rows_build wrote into
+ *   `lists` for the same rows: for every j < *n_src_dev
+ *     dsrc[j] = dinv_j * ([j < *n_rows_dev] dinv_j * dout[j] + sum_{readers i of j, i != j} dinv_i * dout[i])
+ *   dout: fp32 [*][d] plain rows, dsrc: fp32 [src_cap][d].  Every row below *n_src_dev is written exactly once (no
+ *   cleared target, no float atomics); rows at and beyond it are not touched.  rowptr / rowend are not read (may be
+ *   NULL).  Any d >= 1. */
+int32_t gigl_gcn_gather_backward_lists(gigl_ctx* ctx, const float* dout, int32_t d, const float* dinv, const int32_t* rowptr,
+                                       const int32_t* rowend, const int32_t* n_rows_dev, const int32_t* n_src_dev,
+                                       int64_t src_cap, const int32_t* lists, float* dsrc);
+
 /* GATConv attention + aggregation (PyG 2.5.3 GATConv as configured by GAT.init_conv_layers, homogeneous.py:300-343):
  *   h: fp32 [nodes][heads*channels] = x W (gigl_linear), att_src/att_dst: [heads*channels];
  *   e_ij = leaky_relu(<h_j, att_src> + <h_i, att_dst>, negative_slope) over the in-edges of i (self loops removed)
@@ -1388,6 +1415,38 @@ int32_t gigl_sage_train_plan_moments(gigl_sage_train_plan* plan, int32_t layer, 
  * gigl_dropout_mask: keep[r * cols + c] (DEVICE uint8 [rows][cols]) = 1 where element (r, c) is kept, else 0 — by the
  *   device function the plans' kernels use, on the ctx's stream: what bindings and tests reproduce a step's mask with. */
 int32_t gigl_sage_train_plan_set_dropout(gigl_sage_train_plan* plan, float p, uint64_t seed);
+
+/* ---- the same training step for the reference's STOCK node-classification model, TwoLayerGCN
+ * (NodeClassificationModelingTaskSpec's default, python/gigl/src/common/models/pyg/homogeneous.py:488-546: PyG GCNConv ->
+ * relu -> dropout -> GCNConv), with the contracts of gigl_sage_train_plan_* above: announced batches recognised by
+ * address, the seed rule, a NaN loss and the device-side halt for a batch that does not fit the workspace or carries a
+ * label outside the output width (resume), GIGL_E_UNSUPPORTED for with-replacement trees, adopt for a plan re-created
+ * with wide workspaces (it does not carry the dropout setting over).
+ * Exactly two hops.  dims = {input, hidden, output}; w[l] = conv{l+1}.lin.weight [dims[l+1]][dims[l]] as PyG keeps it
+ * (nothing is fused), bias[l] = conv{l+1}.bias (array or entries may be NULL): DEVICE fp32, borrowed and UPDATED IN PLACE.
+ * Each layer aggregates first and projects the rows it needs: gigl_gcn_gather over the table through the union's nodes,
+ * gigl_linear (+ relu), dropout, gigl_gcn_gather, gigl_linear, cross-entropy on the roots; backward through
+ * gigl_linear_weight_grad's partial sums, one projection over W2^T and gigl_gcn_gather_backward_lists; one Adam launch.
+ * The batch graph is the GENERIC union (gigl_union_build's numbering: a leaf occurrence of a node that is also an inner
+ * node needs that node's degree); gigl_gcn_dinv over all its nodes and the root rows' transposed lists are built in the
+ * graph part, once per batch.
+ * moments: Adam's exp_avg / exp_avg_sq of layer 0 / 1's weight and bias into the caller's DEVICE buffers (any may be NULL).
+ * set_dropout: the mask of gigl_sage_train_plan_set_dropout with encode 0, layer 0, over h1's rows by local id — with the
+ * generic union those are gigl_union_build's ids; before the first step only.  TwoLayerGCN applies p = 0.5 when its
+ * is_training flag is set. */
+typedef struct gigl_gcn_train_plan gigl_gcn_train_plan;
+int32_t gigl_gcn_train_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, int32_t b, const int32_t* fanouts,
+                                   const int32_t* dims, float* const* w, float* const* bias, float lr, float beta1,
+                                   float beta2, float eps, float weight_decay, gigl_gcn_train_plan** out);
+int32_t gigl_gcn_train_plan_step2(gigl_gcn_train_plan* plan, const uint32_t* roots, const int64_t* labels, int32_t n_valid,
+                                  const uint32_t* roots_next, const uint32_t* roots_next2, int32_t sampling_seed,
+                                  int32_t mode, float* loss_out);
+const float* gigl_gcn_train_plan_loss(gigl_gcn_train_plan* plan);
+int32_t gigl_gcn_train_plan_resume(gigl_gcn_train_plan* plan);
+int32_t gigl_gcn_train_plan_adopt(gigl_gcn_train_plan* dst, gigl_gcn_train_plan* src);
+int32_t gigl_gcn_train_plan_moments(gigl_gcn_train_plan* plan, int32_t layer, float* m_w, float* v_w, float* m_b, float* v_b);
+int32_t gigl_gcn_train_plan_set_dropout(gigl_gcn_train_plan* plan, float p, uint64_t seed);
+int32_t gigl_gcn_train_plan_destroy(gigl_gcn_train_plan* plan);
 int32_t gigl_dropout_mask(gigl_ctx* ctx, uint64_t seed, uint32_t step, int32_t encode, int32_t layer, int64_t rows,
                           int32_t cols, float p, uint8_t* keep);
 
