@@ -76,6 +76,8 @@ SYMBOLS = [
     "gigl_gcn_dinv", "gigl_gcn_gather", "gigl_gcn_gather_backward_lists",
     "gigl_gcn_train_plan_create", "gigl_gcn_train_plan_step2", "gigl_gcn_train_plan_loss", "gigl_gcn_train_plan_resume",
     "gigl_gcn_train_plan_adopt", "gigl_gcn_train_plan_moments", "gigl_gcn_train_plan_set_dropout", "gigl_gcn_train_plan_destroy",
+    "gigl_gcn_plan_create", "gigl_gcn_plan_set_weights", "gigl_gcn_project_features", "gigl_gcn_plan_set_projected_input",
+    "gigl_gcn_plan_set_fused_root", "gigl_gcn_plan_fused_root",
 ]
 
 KERNEL_IDS = {
@@ -457,6 +459,12 @@ def load() -> C.CDLL:
         "gigl_gcn_gather_backward_lists": [vp, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp],
         "gigl_gcn_train_plan_create": [vp, vp, vp, i32, P(i32), P(i32), vp, vp, C.c_float, C.c_float, C.c_float, C.c_float,
                                        C.c_float, vp],
+        "gigl_gcn_plan_create": [vp, vp, vp, i32, P(i32), P(i32), vp, vp, vp],
+        "gigl_gcn_plan_set_weights": [vp, vp, vp],
+        "gigl_gcn_project_features": [vp, vp, vp, i32, vp],
+        "gigl_gcn_plan_set_projected_input": [vp, vp],
+        "gigl_gcn_plan_set_fused_root": [vp, i32],
+        "gigl_gcn_plan_fused_root": [vp],
         "gigl_gcn_train_plan_step2": [vp, vp, vp, i32, vp, vp, i32, i32, vp],
         "gigl_gcn_train_plan_resume": [vp],
         "gigl_gcn_train_plan_adopt": [vp, vp],

@@ -1942,6 +1942,221 @@ __global__ __launch_bounds__(256) void gcn_gather_scalar_kernel(const T* __restr
   }
 }
 
+// ---- the GCN INFERENCE plan's kernels (gigl_gcn_plan_*, include/gigl_hip.h): TwoLayerGCN at eval time
+// (homogeneous.py:488-546) as NodeClassificationModelingTaskSpec.infer_batch runs it
+// (node_classification_modeling_task_spec.py:176-187).
+//
+// Layer 1 over a PROJECTED table P = X W1^T ([feature rows][hid] fp32, gigl_gcn_project_features):
+//   h1[i] = relu(dinv_i * (dinv_i * P[nodes[i]] + sum_{e in row i, j = col[e] != i} dinv_j * P[nodes[j]]) + b1),  i < n_rows
+// Rows are narrow after the projection (hid = 16: 64 bytes, half a cache line), so a wave per row would idle most lanes:
+// LPR = hid / 4 lanes take a row, one float4 each, and 64 / LPR rows share a wave (16 rows for hid = 16); the lanes past
+// the last whole row (hid / 4 no power of two) idle.  No lane talks to another: every row's lanes walk the row's edges in
+// stored order, four edges' ids, weights and source rows in flight, so a row's sum is a function of the row alone (two
+// runs, a batch alone or inside a group: the same bits) and rows of different lengths only diverge.  The next row's
+// bounds, id and weight are requested ahead of the current row's source rows.  Per source occurrence: 4 B (col) + 4 B
+// (nodes) + 4 B (dinv) + 4 hid B — 64 B of payload at hid = 16 against the 5,732 B of a d = 1,433 table row.
+__global__ __launch_bounds__(256) void gcn_layer_rows_kernel(const float* __restrict__ proj, int hid,
+                                                             const uint32_t* __restrict__ nodes, const float* __restrict__ dinv,
+                                                             const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rowend,
+                                                             const int32_t* __restrict__ col, const int32_t* __restrict__ n_rows_dev,
+                                                             int rows_cap, const float* __restrict__ bias, float* __restrict__ out) {
+  const int lpr = hid >> 2, rpw = 64 / lpr;  // lanes per row, rows per wave
+  const int lane = threadIdx.x & 63;
+  const int sub = lane / lpr, el = (lane - sub * lpr) * 4;
+  const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  const int stride = (int)((gridDim.x * blockDim.x) >> 6) * rpw;
+  const int n_rows = min(*n_rows_dev, rows_cap);
+  int i = wave * rpw + sub;
+  if (sub >= rpw || i >= n_rows) return;
+  const float4_t zero4 = {0.f, 0.f, 0.f, 0.f};
+  const float4_t bv = bias ? *reinterpret_cast<const float4_t*>(bias + el) : zero4;
+  auto row_of = [&](uint32_t id) { return reinterpret_cast<const float4_t*>(proj + (int64_t)id * hid + el); };
+  int e0 = rowptr[i], m = rowend[i] - e0;
+  uint32_t self = nodes[i];
+  float di = dinv[i];
+  for (;;) {
+    const int in = i + stride;
+    const bool more = in < n_rows;
+    const int inn = more ? in : i;  // (the last row asks for itself again: no branch around the loads)
+    const int e0n = rowptr[inn], e1n = rowend[inn];
+    const uint32_t selfn = nodes[inn];
+    const float din = dinv[inn];
+    const float4_t own = *row_of(self);
+    float4_t acc = zero4;
+    int e = 0;
+    for (; e + 4 <= m; e += 4) {
+      const int ja = col[e0 + e], jb = col[e0 + e + 1], jc = col[e0 + e + 2], jd = col[e0 + e + 3];
+      const float wa = dinv[ja], wb = dinv[jb], wc = dinv[jc], wd = dinv[jd];
+      const float4_t* pa = row_of(nodes[ja]);
+      const float4_t* pb = row_of(nodes[jb]);
+      const float4_t* pc = row_of(nodes[jc]);
+      const float4_t* pd = row_of(nodes[jd]);
+      const float4_t a = *pa, b = *pb, c = *pc, d = *pd;
+      // (a stored self loop adds nothing: the row's own term stands for it)
+      acc += (ja != i ? a : zero4) * wa;
+      acc += (jb != i ? b : zero4) * wb;
+      acc += (jc != i ? c : zero4) * wc;
+      acc += (jd != i ? d : zero4) * wd;
+    }
+    for (; e < m; ++e) {
+      const int j = col[e0 + e];
+      const float w = dinv[j];
+      const float4_t a = *row_of(nodes[j]);
+      acc += (j != i ? a : zero4) * w;
+    }
+    float4_t v = (own * di + acc) * di + bv;
+    v.x = fmaxf(v.x, 0.f);
+    v.y = fmaxf(v.y, 0.f);
+    v.z = fmaxf(v.z, 0.f);
+    v.w = fmaxf(v.w, 0.f);
+    *reinterpret_cast<float4_t*>(out + (int64_t)i * hid + el) = v;
+    if (!more) break;
+    i = in;
+    e0 = e0n;
+    m = e1n - e0n;
+    self = selfn;
+    di = din;
+  }
+}
+
+// the same rows for any hid (no whole float4 rows, rows wider than 64 float4s, a table off 16-byte alignment): one wave per
+// row, a lane per element, 64 columns per pass; element (i, c) adds its edges in stored order
+__global__ __launch_bounds__(256) void gcn_layer_rows_scalar_kernel(const float* __restrict__ proj, int hid,
+                                                                    const uint32_t* __restrict__ nodes,
+                                                                    const float* __restrict__ dinv,
+                                                                    const int32_t* __restrict__ rowptr,
+                                                                    const int32_t* __restrict__ rowend,
+                                                                    const int32_t* __restrict__ col,
+                                                                    const int32_t* __restrict__ n_rows_dev, int rows_cap,
+                                                                    const float* __restrict__ bias, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  const int waves_total = (int)((gridDim.x * blockDim.x) >> 6);
+  const int n_rows = min(*n_rows_dev, rows_cap);
+  for (int i = wave; i < n_rows; i += waves_total) {
+    const int e0 = rowptr[i], m = rowend[i] - e0;
+    const float di = dinv[i];
+    const float* ps = proj + (int64_t)nodes[i] * hid;
+    for (int c = lane; c < hid; c += 64) {
+      float acc = 0.f;
+      for (int e = 0; e < m; ++e) {
+        const int j = col[e0 + e];
+        if (j == i) continue;
+        acc += dinv[j] * proj[(int64_t)nodes[j] * hid + c];
+      }
+      const float v = (ps[c] * di + acc) * di + (bias ? bias[c] : 0.f);
+      out[(int64_t)i * hid + c] = fmaxf(v, 0.f);
+    }
+  }
+}
+
+// Layer 2 for the ROOT SLOTS, straight into the caller's rows: for slot i < b, r = root_local[i],
+//   a2 = dinv_r * (dinv_r * h1[r] + sum_{e in row r, j = col[e] != r} dinv_j * h1[j]),  out[i] = a2 W2^T + b2
+//   [-> out[i] / max(|out[i]|_2, 1e-12)]
+// One wave per slot, four slots per workgroup; W2 ([n_out][hid], hid * n_out * 4 <= 64 KB) is staged in LDS once per
+// workgroup.  A lane keeps up to four float4s of a2 (hid <= 1024: element (v * 64 + lane) * 4 ...), adds the row's edges in
+// stored order, four source rows in flight; column c of the product is each lane's partial dot over its a2 elements —
+// consecutive lanes read consecutive 16 bytes of W2's row c from LDS, no bank conflict — added across the wave in a fixed
+// butterfly.  Lane c % 64 keeps column c and the wave writes 64 columns at a time; for the L2 switch each lane squares
+// what it wrote, the wave adds that up, and each lane rescales its own columns (its own stores: ordered).  Two slots that
+// hold the same node each compute their row: the same operations on the same data, the same bits.  A failed batch set
+// (meta[GIGL_META_OVERFLOW]) gives NaN rows, a slot without a root (root_local < 0) a zero row, as gigl_take_rows does.
+__global__ __launch_bounds__(256) void gcn_root_layer_kernel(const float* __restrict__ h1, int hid, int n_out,
+                                                             const float* __restrict__ dinv, const int32_t* __restrict__ rowptr,
+                                                             const int32_t* __restrict__ rowend, const int32_t* __restrict__ col,
+                                                             const int32_t* __restrict__ root_local, int b,
+                                                             const float* __restrict__ w2, const float* __restrict__ bias, int l2,
+                                                             const int32_t* __restrict__ meta, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float gcn_w2_lds[];
+  const int nw4 = (hid * n_out) >> 2;
+  for (int t = threadIdx.x; t < nw4; t += 256)
+    reinterpret_cast<float4_t*>(gcn_w2_lds)[t] = reinterpret_cast<const float4_t*>(w2)[t];
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int i = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (i >= b) return;
+  float* o = out + (int64_t)i * n_out;
+  const bool failed = meta[GIGL_META_OVERFLOW] != 0;
+  const int r = failed ? -1 : root_local[i];
+  if (r < 0) {
+    const float fill = failed ? __builtin_nanf("") : 0.f;
+    for (int c = lane; c < n_out; c += 64) o[c] = fill;
+    return;
+  }
+  constexpr int V = 4;
+  const float4_t zero4 = {0.f, 0.f, 0.f, 0.f};
+  const int e0 = rowptr[r], m = rowend[r] - e0;
+  const float di = dinv[r];
+  float4_t a2[V], acc[V];
+  auto load_row = [&](int j, float4_t (&x)[V]) {
+    const float* p = h1 + (int64_t)j * hid;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const int el = (v * 64 + lane) * 4;
+      x[v] = el < hid ? *reinterpret_cast<const float4_t*>(p + el) : zero4;
+    }
+  };
+  load_row(r, a2);
+#pragma unroll
+  for (int v = 0; v < V; ++v) acc[v] = zero4;
+  int e = 0;
+  for (; e + 4 <= m; e += 4) {
+    const int ja = col[e0 + e], jb = col[e0 + e + 1], jc = col[e0 + e + 2], jd = col[e0 + e + 3];
+    const float wa = ja != r ? dinv[ja] : 0.f, wb = jb != r ? dinv[jb] : 0.f, wc = jc != r ? dinv[jc] : 0.f,
+                wd = jd != r ? dinv[jd] : 0.f;
+    float4_t xa[V], xb[V], xc[V], xd[V];
+    load_row(ja, xa);
+    load_row(jb, xb);
+    load_row(jc, xc);
+    load_row(jd, xd);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {  // (a stored self loop is the row itself — finite — times a weight of zero)
+      acc[v] += xa[v] * wa;
+      acc[v] += xb[v] * wb;
+      acc[v] += xc[v] * wc;
+      acc[v] += xd[v] * wd;
+    }
+  }
+  for (; e < m; ++e) {
+    const int j = col[e0 + e];
+    const float w = j != r ? dinv[j] : 0.f;
+    float4_t x[V];
+    load_row(j, x);
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[v] += x[v] * w;
+  }
+#pragma unroll
+  for (int v = 0; v < V; ++v) a2[v] = (a2[v] * di + acc[v]) * di;
+  float ss = 0.f;
+  for (int cb = 0; cb < n_out; cb += 64) {
+    const int cn = min(64, n_out - cb);
+    float mine = 0.f;
+    for (int cc = 0; cc < cn; ++cc) {
+      const float* wr = gcn_w2_lds + (int64_t)(cb + cc) * hid;
+      float4_t s4 = zero4;
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        const int el = (v * 64 + lane) * 4;
+        if (el < hid) s4 += a2[v] * *reinterpret_cast<const float4_t*>(wr + el);
+      }
+      float s = (s4.x + s4.y) + (s4.z + s4.w);
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      if (lane == cc) mine = s;
+    }
+    if (lane < cn) {
+      mine += bias ? bias[cb + lane] : 0.f;
+      o[cb + lane] = mine;
+      ss += mine * mine;
+    }
+  }
+  if (l2) {
+    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+    const float nrm = sqrtf(ss);
+    const float den = nrm < 1e-12f ? 1e-12f : nrm;  // (l2_normalize_rows_kernel's rule: a NaN norm stays)
+    for (int c = lane; c < n_out; c += 64) o[c] = o[c] / den;
+  }
+}
+
 // the transpose of that row, as a GATHER over the transposed rows gigl_transposed_rows_build writes (gmt_gather_kernel's
 // shape: LPR lanes per source row, 64 / LPR source rows per wave): for every source j < *n_src
 //   dsrc[j] = dinv_j * ([j < n_rows] dinv_j * dout[j] + sum_{readers i of j, i != j} dinv_i * dout[i])
@@ -4210,7 +4425,93 @@ int32_t gigl_gather_project_mixed(gigl_ctx* ctx, const float* src_l, const float
                                  own_rank, peers);
 }
 
+int32_t gigl_gcn_layer_rows(gigl_ctx* ctx, const float* proj, int32_t hid, const uint32_t* nodes, const float* dinv,
+                            const int32_t* rowptr, const int32_t* rowend, const int32_t* col, const int32_t* n_rows_dev,
+                            int64_t rows_cap, const float* bias, float* out) {
+  GIGL_REQUIRE(ctx, proj && nodes && dinv && rowptr && rowend && col && n_rows_dev && out, "null argument");
+  GIGL_REQUIRE(ctx, hid > 0 && rows_cap >= 0 && rows_cap < ((int64_t)1 << 30), "bad sizes");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (rows_cap == 0) return GIGL_OK;
+  gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
+  // whole float4s of 16-byte-aligned rows, at most a wave's 64 of them: several rows per wave
+  const bool packed = (hid & 3) == 0 && hid <= 256 && ((((uintptr_t)proj | (uintptr_t)out | (uintptr_t)bias)) & 15) == 0;
+  const int rows_per_wave = packed ? 64 / (hid / 4) : 1;
+  int64_t blocks = (rows_cap + 4 * rows_per_wave - 1) / (4 * rows_per_wave);
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  if (packed)
+    hipLaunchKernelGGL(gcn_layer_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, proj, hid, nodes, dinv, rowptr,
+                       rowend, col, n_rows_dev, (int)rows_cap, bias, out);
+  else
+    hipLaunchKernelGGL(gcn_layer_rows_scalar_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, proj, hid, nodes, dinv,
+                       rowptr, rowend, col, n_rows_dev, (int)rows_cap, bias, out);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+// the shapes gcn_root_layer_kernel is built for: float4 rows of h1 and W2, four float4s per lane, W2 within 64 KB of LDS
+bool gigl_gcn_root_layer_ok(int32_t hid, int32_t n_out, const float* w2) {
+  return (hid & 3) == 0 && hid <= 1024 && n_out >= 1 && (int64_t)hid * n_out * 4 <= 65536 && ((uintptr_t)w2 & 15) == 0;
+}
+
+int32_t gigl_gcn_root_layer(gigl_ctx* ctx, const float* h1, int32_t hid, int32_t n_out, const float* dinv, const int32_t* rowptr,
+                            const int32_t* rowend, const int32_t* col, const int32_t* root_local, int32_t b, const float* w2,
+                            const float* bias, int32_t l2_normalize, const int32_t* meta, float* out) {
+  GIGL_REQUIRE(ctx, h1 && dinv && rowptr && rowend && col && root_local && w2 && meta && out && b >= 1, "null argument");
+  GIGL_REQUIRE(ctx, gigl_gcn_root_layer_ok(hid, n_out, w2) && ((uintptr_t)h1 & 15) == 0, "shape outside the fused root layer");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  gigl_prof_scope ps(ctx, GIGL_K_GATHER_MEAN);
+  hipLaunchKernelGGL(gcn_root_layer_kernel, dim3((unsigned)((b + 3) / 4)), dim3(256), (size_t)hid * n_out * 4, ctx->stream, h1, hid,
+                     n_out, dinv, rowptr, rowend, col, root_local, b, w2, bias, l2_normalize ? 1 : 0, meta, out);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
 extern "C" {
+
+// P = X W1^T over the whole resident feature table (the table of gigl_gcn_plan_set_projected_input): one gigl_linear pass
+// per row chunk, as gigl_sage_project_features runs it; an fp16 table's rows are widened exactly on their way in
+int32_t gigl_gcn_project_features(gigl_ctx* ctx, gigl_feat* feat, const float* w1, int32_t hid, float* out) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  GIGL_REQUIRE(ctx, feat && w1 && out && hid > 0, "null argument");
+  GIGL_REQUIRE(ctx, feat->dtype == GIGL_DTYPE_F32 || feat->dtype == GIGL_DTYPE_F16, "bad feature dtype");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int d = feat->d;
+  const int64_t n = feat->n;
+  if (n == 0) return GIGL_OK;
+  hipStream_t st = ctx->stream;
+  const int64_t chunk = (int64_t)1 << 19, cm = n < chunk ? n : chunk;
+  float* stage = nullptr;
+  int32_t* cnt = nullptr;
+  auto cleanup = [&]() {
+    hipStreamSynchronize(st);
+    hipFree(stage);
+    hipFree(cnt);
+  };
+  const int32_t counts[2] = {(int32_t)cm, (int32_t)(n % cm)};  // row counts: a whole chunk, the tail
+  if (hipMalloc((void**)&cnt, 64) != hipSuccess ||
+      (feat->dtype == GIGL_DTYPE_F16 && hipMalloc((void**)&stage, (size_t)cm * d * 4 + 16) != hipSuccess)) {
+    cleanup();
+    return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the projection workspace failed");
+  }
+  if (hipMemcpyAsync(cnt, counts, 8, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    cleanup();
+    return gigl_fail(ctx, GIGL_E_HIP, "row-count upload failed");
+  }
+  int32_t rc = GIGL_OK;
+  for (int64_t r0 = 0; r0 < n && rc == GIGL_OK; r0 += cm) {
+    const int64_t m = (n - r0) < cm ? (n - r0) : cm;
+    const float* a = (const float*)feat->rows + r0 * d;
+    if (feat->dtype == GIGL_DTYPE_F16) {
+      const int64_t elems = m * d;
+      hipLaunchKernelGGL(half_rows_to_f32_kernel, dim3((unsigned)((elems / 4 + 256) / 256)), dim3(256), 0, st,
+                         (const __half*)feat->rows + r0 * d, elems, stage);
+      a = stage;
+    }
+    rc = gigl_linear(ctx, a, w1, nullptr, cnt + (m == cm ? 0 : 1), m, d, hid, 0, out + r0 * hid);
+  }
+  cleanup();
+  return rc;
+}
 
 // [X W_l^T | X W_r^T] over the whole resident feature table (the table of gigl_sage_plan_set_projected_input): ONE
 // product per row chunk against the stacked weight [W_l ; W_r] — the feature rows are read (and, for an fp16 table,

@@ -372,6 +372,17 @@ int32_t gigl_linear_fused2(gigl_ctx* ctx, const float* a_tiled, const float* bia
 int32_t gigl_sage_fused_out(gigl_ctx* ctx, const float* p, const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
                             const int32_t* root_local, int32_t b, int32_t n_out, const float* bias, int32_t act,
                             int32_t aggr, const int32_t* meta, float* out);
+// the GCN inference plan's two kernels (agg.hip; gigl_gcn_plan_*, include/gigl_hip.h).  gigl_gcn_layer_rows: layer 1 over a
+// projected table P = X W1^T ([feature rows][hid] fp32): h1[i] = relu(dinv_i (dinv_i P[nodes[i]] + sum_{j in row i, j != i}
+// dinv_j P[nodes[j]]) + bias) for i < *n_rows_dev, any hid.  gigl_gcn_root_layer: layer 2 for the b root slots, written into
+// the caller's `out` ([b][n_out]; NaN rows when meta reports a failed batch set), for shapes gigl_gcn_root_layer_ok accepts
+int32_t gigl_gcn_layer_rows(gigl_ctx* ctx, const float* proj, int32_t hid, const uint32_t* nodes, const float* dinv,
+                            const int32_t* rowptr, const int32_t* rowend, const int32_t* col, const int32_t* n_rows_dev,
+                            int64_t rows_cap, const float* bias, float* out);
+bool gigl_gcn_root_layer_ok(int32_t hid, int32_t n_out, const float* w2);
+int32_t gigl_gcn_root_layer(gigl_ctx* ctx, const float* h1, int32_t hid, int32_t n_out, const float* dinv, const int32_t* rowptr,
+                            const int32_t* rowend, const int32_t* col, const int32_t* root_local, int32_t b, const float* w2,
+                            const float* bias, int32_t l2_normalize, const int32_t* meta, float* out);
 bool gigl_half_split_enabled();  // (GIGL_GEMM_SPLIT=bf16 keeps every projection on the bf16 planes)
 int32_t gigl_dev_absmax_f32(gigl_ctx* ctx, const float* p, int64_t n, float* out);  // synchronises the ctx's stream
 int32_t gigl_feat_absmax(gigl_ctx* ctx, gigl_feat* feat, float* out);

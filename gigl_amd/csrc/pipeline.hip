@@ -36,8 +36,8 @@ struct Step {
   uint32_t kernels = 0;
 };
 
-// steps [0, GRAPH_STEPS) = sample + union (the GRAPH part: integer work, latency-bound, independent of the weights)
-constexpr int GRAPH_STEPS = 2;
+// steps [0, plan->graph_steps) = sample + union [+ the GCN kind's dinv] (the GRAPH part: integer work, latency-bound,
+// independent of the weights)
 constexpr int MAX_STEPS = 3 + 2 * GIGL_MAX_HOPS;
 
 // a maximal run of consecutive steps: either replayed from a captured graph or launched eagerly
@@ -78,7 +78,13 @@ struct gigl_sage_plan : BatchGraph {
   float* hs_dev = nullptr;
   // kind 1: GAT layers instead of SAGE layers (gigl_gat_plan_create): w[l] = lin weight [heads*channels][dims[l]],
   // layer 0 from the input side in one row pass (gigl_gat_input_layer_fused), layers >= 1 projection + attention
+  // kind 2: TwoLayerGCN at inference (gigl_gcn_plan_create): w[l] = conv{l+1}.lin.weight [dims[l+1]][dims[l]], over the
+  // GENERIC union; `proj` is then P = X W1^T [feature rows][dims[1]] (gigl_gcn_plan_set_projected_input)
   int32_t kind = 0;
+  float* dinv = nullptr;       // kind 2: 1 / sqrt(deg) of every node of the batch graph [un.cap_nodes] (the graph part's)
+  float* gcn_a = nullptr;      // kind 2: a layer's aggregated rows [act_rows][max(dims[0], dims[1])] (aggregate-first / fallback)
+  bool gcn_fuse_want = false;  // gigl_gcn_plan_set_fused_root (off by default: measured, DESIGN.md §4 "GCN inference plan")
+  bool gcn_fused = false;      // the last layer runs as gcn_root_layer_kernel (decided when the list of steps is built)
   int32_t heads[GIGL_MAX_HOPS] = {0}, channels[GIGL_MAX_HOPS] = {0};
   const float* att_src[GIGL_MAX_HOPS] = {nullptr};
   const float* att_dst[GIGL_MAX_HOPS] = {nullptr};
@@ -111,6 +117,7 @@ struct gigl_sage_plan : BatchGraph {
   // configuration changes; a run only walks it)
   Step steps[MAX_STEPS];
   int n_steps = 0;
+  int graph_steps = 2;  // the leading steps that make up the GRAPH part
   bool fused2 = false;  // fused2_on() when the list was built
   // hipGraph replay
   bool use_graph = false;
@@ -567,6 +574,43 @@ int32_t step_roots(gigl_sage_plan* p, int l, const RunArgs& a) {
   return GIGL_OK;
 }
 
+// ---- the GCN kind (TwoLayerGCN at inference, homogeneous.py:488-546 / node_classification_modeling_task_spec.py:176-187)
+
+// A_hat's normalisation over every node of the union: integer-side work on the batch graph alone — the graph part's
+int32_t step_gcn_dinv(gigl_sage_plan* p, int, const RunArgs&) {
+  return gigl_gcn_dinv(p->ctx, p->un.rowptr, p->un.rowend, p->un.col, p->un.meta + GIGL_META_N_NODES, p->un.cap_nodes, p->dinv);
+}
+
+// layer l, aggregate-first, first half: A_hat over the table through un.nodes (l = 0) or over h1 (l = 1), for the rows the
+// layer computes
+int32_t step_gcn_gather(gigl_sage_plan* p, int l, const RunArgs&) {
+  const LayerRows r = layer_rows(p, l);
+  if (l == 0)
+    return gigl_gcn_gather(p->ctx, p->feat->rows, p->feat->dtype, r.d, p->un.nodes, p->dinv, p->un.rowptr, p->un.rowend, p->un.col,
+                           r.n_rows, r.rows_cap, p->gcn_a);
+  return gigl_gcn_gather(p->ctx, p->hbuf[0], GIGL_DTYPE_F32, r.d, nullptr, p->dinv, p->un.rowptr, p->un.rowend, p->un.col, r.n_rows,
+                         r.rows_cap, p->gcn_a);
+}
+
+// ... second half: the projection with bias (and the rectifier below the last layer) into hbuf[l]
+int32_t step_gcn_project(gigl_sage_plan* p, int l, const RunArgs&) {
+  const LayerRows r = layer_rows(p, l);
+  return gigl_linear(p->ctx, p->gcn_a, p->w[l], p->bias[l], r.n_rows, r.rows_cap, r.d, p->dims[l + 1], r.act, p->hbuf[l]);
+}
+
+// layer 1 over the projected table: one gather over hid-wide rows + bias + rectifier
+int32_t step_gcn_projected_input(gigl_sage_plan* p, int, const RunArgs&) {
+  const LayerRows r = layer_rows(p, 0);
+  return gigl_gcn_layer_rows(p->ctx, p->proj, p->dims[1], p->un.nodes, p->dinv, p->un.rowptr, p->un.rowend, p->un.col, r.n_rows,
+                             r.rows_cap, p->bias[0], p->hbuf[0]);
+}
+
+// layer 2 and the roots' rows in one launch, into the caller's `out`
+int32_t step_gcn_root(gigl_sage_plan* p, int, const RunArgs& a) {
+  return gigl_gcn_root_layer(p->ctx, p->hbuf[0], p->dims[1], p->dims[2], p->dinv, p->un.rowptr, p->un.rowend, p->un.col,
+                             p->un.root_local, p->b, p->w[1], p->bias[1], p->l2_normalize ? 1 : 0, p->un.meta, a.out);
+}
+
 int32_t run_steps(gigl_sage_plan* p, int s0, int s1, const RunArgs& a) {
   for (int s = s0; s < s1; ++s) {
     const int32_t rc = p->steps[s].run(p, p->steps[s].layer, a);
@@ -587,6 +631,27 @@ void plan_build_steps(gigl_sage_plan* p) {
   add(step_sample, 0, (1u << GIGL_K_EXPAND) | (1u << GIGL_K_EXPAND_HEAVY) | (1u << GIGL_K_FIND_HEAVY));
   add(step_union, 0, (1u << GIGL_K_UNION_INSERT) | (1u << GIGL_K_UNION_RELAX) | (1u << GIGL_K_UNION_NODES) |
                          (1u << GIGL_K_UNION_EDGE_SORT) | (1u << GIGL_K_UNION_CSR));
+  p->graph_steps = n;
+  if (p->kind == 2) {
+    add(step_gcn_dinv, 0, gather);
+    p->graph_steps = n;
+    p->gcn_fused = p->gcn_fuse_want && gigl_gcn_root_layer_ok(p->dims[1], p->dims[2], p->w[1]);
+    if (p->proj) {
+      add(step_gcn_projected_input, 0, gather);
+    } else {
+      add(step_gcn_gather, 0, gather);
+      add(step_gcn_project, 0, linear);
+    }
+    if (p->gcn_fused) {
+      add(step_gcn_root, 1, gather);
+    } else {
+      add(step_gcn_gather, 1, gather);
+      add(step_gcn_project, 1, linear);
+      add(step_roots, 1, 0);
+    }
+    p->n_steps = n;
+    return;
+  }
   for (int l = 0; l < L; ++l) {
     if (p->kind == 1) {
       if (l == 0) {  // (the row pass records as a gather, the heads' projection behind it as a linear)
@@ -634,11 +699,11 @@ int32_t capture_segments(gigl_sage_plan* p, int32_t sampling_seed, int32_t mode)
   auto timed = [&](int s) { return s == n - 1 || (p->steps[s].kernels & mask) != 0; };
   for (int s = 0; s < n;) {
     int e = s + 1;  // (the last step is a segment of its own; a split plan's graph part ends one)
-    while (e < n - 1 && timed(e) == timed(s) && !(p->split && e == GRAPH_STEPS)) ++e;
+    while (e < n - 1 && timed(e) == timed(s) && !(p->split && e == p->graph_steps)) ++e;
     Segment& sg = p->segs[p->n_segs] = Segment{s, e, nullptr};
     if (!timed(s)) {
       // (a graph-part segment of a split plan is captured from — and later launched on — the plan's graph stream)
-      StreamScope on(ctx, p->split && e <= GRAPH_STEPS ? p->gstream : ctx->stream);
+      StreamScope on(ctx, p->split && e <= p->graph_steps ? p->gstream : ctx->stream);
       char what[64];  // (the message keeps its wording; the numbers are positions in the plan's list of steps)
       snprintf(what, sizeof what, "stages [%d,%d) of the batch pipeline", s, e);
       const int32_t rc = gigl_capture(ctx, ctx->stream, what, &sg.exec,
@@ -1047,7 +1112,7 @@ int32_t gigl_sage_plan_destroy(gigl_sage_plan* p) {
 
 static int32_t plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, int32_t b, const int32_t* fanouts,
                            int32_t hops, const int32_t* dims, const float* const* w, const float* const* bias,
-                           int32_t act_last, bool with_abuf, gigl_sage_plan** out);
+                           int32_t act_last, bool with_abuf, gigl_sage_plan** out, bool number_every_node = false);
 static int32_t plan_refresh_half_split(gigl_sage_plan* p);
 
 int32_t gigl_sage_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, int32_t b,
@@ -1065,10 +1130,11 @@ static int32_t plan_check_layers(gigl_ctx* ctx, const gigl_feat* feat, int32_t h
   return GIGL_OK;
 }
 
-// with_abuf false: no [mean | self] operand buffer (the GAT plan aggregates into its own per-head operands)
+// with_abuf false: no [mean | self] operand buffer (the GAT plan aggregates into its own per-head operands, the GCN plan
+// into plain rows); number_every_node: the generic union (the GCN plan)
 static int32_t plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, int32_t b, const int32_t* fanouts,
                            int32_t hops, const int32_t* dims, const float* const* w, const float* const* bias,
-                           int32_t act_last, bool with_abuf, gigl_sage_plan** out) {
+                           int32_t act_last, bool with_abuf, gigl_sage_plan** out, bool number_every_node) {
   if (!ctx || !out) return GIGL_E_INVALID_ARG;
   *out = nullptr;
   GIGL_REQUIRE(ctx, graph && feat && fanouts && dims && w, "null argument");
@@ -1078,7 +1144,7 @@ static int32_t plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, in
   GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   gigl_sage_plan* p = new (std::nothrow) gigl_sage_plan();
   if (!p) return gigl_fail(ctx, GIGL_E_OOM, "host OOM");
-  rc = batch_graph_init(p, ctx, graph, b, fanouts, hops, false);
+  rc = batch_graph_init(p, ctx, graph, b, fanouts, hops, number_every_node);
   if (rc != GIGL_OK) {
     gigl_sage_plan_destroy(p);
     return rc;
@@ -1238,6 +1304,56 @@ int32_t gigl_gat_plan_set_edge_features(gigl_sage_plan* p, gigl_feat* edge_table
   }
   return batch_graph_attach_edge_table(p, edge_table);
 }
+
+int32_t gigl_gcn_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, int32_t b, const int32_t* fanouts,
+                             const int32_t* dims, const float* const* w, const float* const* bias, gigl_sage_plan** out) {
+  if (!ctx || !out) return GIGL_E_INVALID_ARG;
+  *out = nullptr;
+  GIGL_REQUIRE(ctx, feat && (feat->dtype == GIGL_DTYPE_F32 || feat->dtype == GIGL_DTYPE_F16), "bad feature table");
+  gigl_sage_plan* p = nullptr;
+  int32_t rc = plan_create(ctx, graph, feat, b, fanouts, 2, dims, w, bias, 0, false, &p, true);
+  if (rc != GIGL_OK) return rc;
+  p->kind = 2;
+  const int32_t widest = dims[0] > dims[1] ? dims[0] : dims[1];
+  p->dinv = (float*)plan_alloc(p->owned, (size_t)p->un.cap_nodes * 4);
+  p->gcn_a = (float*)plan_alloc(p->owned, (size_t)p->act_rows * widest * 4);
+  if (!p->dinv || !p->gcn_a) {
+    gigl_sage_plan_destroy(p);
+    return gigl_fail(ctx, GIGL_E_OOM, "hipMalloc of the GCN plan's workspace failed");
+  }
+  plan_build_steps(p);  // (the list plan_create left is a SAGE plan's)
+  *out = p;
+  return GIGL_OK;
+}
+
+int32_t gigl_gcn_plan_set_weights(gigl_sage_plan* p, const float* const* w, const float* const* bias) {
+  if (!p || !w || p->kind != 2) return GIGL_E_INVALID_ARG;
+  for (int l = 0; l < 2; ++l) {
+    GIGL_REQUIRE(p->ctx, w[l], "layer %d: null weight", l);
+    p->w[l] = w[l];
+    p->bias[l] = bias ? bias[l] : nullptr;
+  }
+  plan_invalidate(p);  // (weight pointers are baked into the captured kernels; W2's alignment decides the fused root layer)
+  return GIGL_OK;
+}
+
+int32_t gigl_gcn_plan_set_projected_input(gigl_sage_plan* p, const float* proj) {
+  if (!p || p->kind != 2) return GIGL_E_INVALID_ARG;
+  const bool changed = p->proj != proj;
+  p->proj = proj;
+  if (changed) plan_invalidate(p);  // (the pointer is baked into the captured launches)
+  return GIGL_OK;
+}
+
+int32_t gigl_gcn_plan_set_fused_root(gigl_sage_plan* p, int32_t on) {
+  if (!p || p->kind != 2) return GIGL_E_INVALID_ARG;
+  const bool changed = p->gcn_fuse_want != (on != 0);
+  p->gcn_fuse_want = on != 0;
+  if (changed) plan_invalidate(p);
+  return GIGL_OK;
+}
+
+int32_t gigl_gcn_plan_fused_root(gigl_sage_plan* p) { return p && p->kind == 2 && p->gcn_fused ? 1 : 0; }
 
 int32_t gigl_sage_plan_set_l2_normalize(gigl_sage_plan* p, int32_t on) {
   if (!p) return GIGL_E_INVALID_ARG;
@@ -1399,7 +1515,7 @@ int32_t gigl_sage_plan_run_part(gigl_sage_plan* p, const uint32_t* roots, int32_
   if (mode == GIGL_MODE_REPLACE)
     return gigl_fail(ctx, GIGL_E_UNSUPPORTED, "the one-call plan needs duplicate-free trees (no with-replacement mode)");
   const RunArgs a{roots, sampling_seed, mode, out};
-  return part == GIGL_PLAN_PART_GRAPH ? run_steps(p, 0, GRAPH_STEPS, a) : run_steps(p, GRAPH_STEPS, p->n_steps, a);
+  return part == GIGL_PLAN_PART_GRAPH ? run_steps(p, 0, p->graph_steps, a) : run_steps(p, p->graph_steps, p->n_steps, a);
 }
 
 int32_t gigl_sage_plan_run(gigl_sage_plan* p, const uint32_t* roots, int32_t sampling_seed, int32_t mode,
@@ -1450,7 +1566,7 @@ int32_t gigl_sage_plan_run(gigl_sage_plan* p, const uint32_t* roots, int32_t sam
   bool joined = !p->split;
   for (int i = 0; i < p->n_segs; ++i) {
     const Segment& sg = p->segs[i];
-    const bool gpart = sg.s1 <= GRAPH_STEPS;
+    const bool gpart = sg.s1 <= p->graph_steps;
     if (!gpart && !joined) {  // the layers wait for the graph part
       GIGL_HIP_CHECK(ctx, hipEventRecord(p->ev_graph, gs));
       GIGL_HIP_CHECK(ctx, hipStreamWaitEvent(cs, p->ev_graph, 0));

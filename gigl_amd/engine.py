@@ -1230,6 +1230,22 @@ class HipEngine:
                                                    C.c_void_p(out.data_ptr())), self._ctx)
         return out
 
+    def gcn_project_features(self, w1: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """P = X W1^T over the whole resident feature table for TwoLayerGCN's conv1.lin.weight [hid, in]
+        (gigl_gcn_project_features): one fp32 table [n_rows, hid] on the device — the input of
+        GcnPlan.set_projected_input"""
+        assert self._feat is not None and w1.dim() == 2 and w1.shape[1] == self.feat_dim
+        w = w1.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        hid = int(w.shape[0])
+        n_rows = C.c_int64()
+        check(self._lib.gigl_features_device_ptr(self._feat, None, C.byref(n_rows), None, None), self._ctx)
+        if out is None:  # (a job re-projects after every weight update: pass the previous table back in)
+            out = torch.empty((n_rows.value, hid), dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n_rows.value, hid)
+        check(self._lib.gigl_gcn_project_features(self._ctx, self._feat, C.c_void_p(w.data_ptr()), hid,
+                                                  C.c_void_p(out.data_ptr())), self._ctx)
+        return out
+
     # ---- one-call batch pipeline -----------------------------------------------------------
     def make_sage_plan(self, weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]], b: int,
                        fanouts: Sequence[int], act_last: bool = False, groups: int = 1, aggr: str = "mean",
@@ -2228,3 +2244,65 @@ class GatPlan(SagePlan):
               self.eng._ctx)
         if att_edge is not None:
             self._set_edge_params(att_edge, edge_msg)
+
+
+class GcnPlan(SagePlan):
+    """sample -> generic union -> TwoLayerGCN's eval-time forward -> one row per root, enqueued by ONE library call
+    (gigl_gcn_plan_create; the handle is a gigl_sage_plan: run / use_graph / stats / last_batch_to_host are SagePlan's)"""
+
+    def __init__(self, eng: HipEngine, weights, biases, b: int, fanouts, groups: int = 1, l2_normalize: bool = False):
+        """weights: [conv1.lin.weight [hid, in], conv2.lin.weight [out, hid]], biases: [conv1.bias, conv2.bias] (None: no
+        bias) — TwoLayerGCN.plan_params()"""
+        assert eng._graph is not None and eng._feat is not None, "load the graph and the features first"
+        assert len(fanouts) == 2 and len(weights) == 2 and len(biases) == 2 and groups >= 1
+        self.group_roots, self.groups = int(b), int(groups)
+        self.eng, self.b, self.fanouts = eng, int(b) * int(groups), [int(f) for f in fanouts]
+        self._lib = eng._lib
+        self.dims = [int(weights[0].shape[1]), int(weights[0].shape[0]), int(weights[1].shape[0])]
+        assert int(weights[1].shape[1]) == self.dims[1]
+        self._keep = None
+        self._proj = None
+        self._plan = C.c_void_p()
+        w_arr, b_arr = self._ptr_arrays(weights, biases)
+        fo = (C.c_int32 * 2)(*self.fanouts)
+        dims = (C.c_int32 * 3)(*self.dims)
+        check(self._lib.gigl_gcn_plan_create(eng._ctx, eng._graph, eng._feat, self.b, fo, dims, w_arr, b_arr,
+                                             C.byref(self._plan)), eng._ctx)
+        if not hasattr(eng, "_plans"):
+            eng._plans = []
+        eng._plans.append(self)
+        try:
+            if self.groups > 1:
+                check(self._lib.gigl_sage_plan_set_groups(self._plan, self.group_roots), eng._ctx)
+            if l2_normalize:
+                self.set_l2_normalize(True)
+        except Exception:
+            self.close()
+            raise
+
+    def set_weights(self, weights, biases) -> None:
+        """the arguments are TwoLayerGCN.plan_params(); a projected input belongs to the first weight it was computed from"""
+        w_arr, b_arr = self._ptr_arrays(weights, biases)
+        check(self._lib.gigl_gcn_plan_set_weights(self._plan, w_arr, b_arr), self.eng._ctx)
+
+    def set_projected_input(self, proj: Optional[torch.Tensor]) -> None:
+        """layer 1 over PROJECTED rows (HipEngine.gcn_project_features of conv1.lin.weight): one gather over hid-wide rows
+        + bias + relu, no per-batch projection (gigl_gcn_plan_set_projected_input); None: back to aggregate-first"""
+        if proj is not None:
+            assert proj.is_cuda and proj.dtype == torch.float32 and proj.is_contiguous() and proj.dim() == 2 and \
+                int(proj.shape[1]) == self.dims[1]
+            n_rows = C.c_int64()
+            check(self._lib.gigl_features_device_ptr(self.eng._feat, None, C.byref(n_rows), None, None), self.eng._ctx)
+            assert int(proj.shape[0]) == n_rows.value, "one projected row per row of the feature table"
+        check(self._lib.gigl_gcn_plan_set_projected_input(self._plan, None if proj is None else C.c_void_p(proj.data_ptr())),
+              self.eng._ctx)
+        self._proj = proj  # borrowed by the plan
+
+    def set_fused_root(self, on: bool = True) -> None:
+        """layer 2 and the roots' rows in one launch where the shape allows (gigl_gcn_plan_set_fused_root); False: gather,
+        projection and a copy of the roots' rows"""
+        check(self._lib.gigl_gcn_plan_set_fused_root(self._plan, 1 if on else 0), self.eng._ctx)
+
+    def fused_root(self) -> bool:
+        """the last layer runs fused (gigl_gcn_plan_fused_root)"""
+        return bool(self._lib.gigl_gcn_plan_fused_root(self._plan))

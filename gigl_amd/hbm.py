@@ -407,6 +407,19 @@ class ResidentGraph:
                     cached = self._proj_tables = ((id(model), stamp), self.engine.project_features(w0, out=old))
                     self.engine.synchronize()  # (once per model state: the other lanes' plans read the table too)
                 plan.set_projected_input(cached[1])
+        elif type(plan).__name__ == "GcnPlan":
+            plan.set_weights(*model.plan_params())
+            # rows wider than the first layer's output: X W1^T once per model state, the first layer gathers hid-wide rows
+            # — one table per resident graph, shared by the lanes' plans of this model
+            if model.projected_input_pays(self.engine):
+                stamp = tuple((p.data_ptr(), p._version) for p in model.conv1.parameters())
+                cached = getattr(self, "_gcn_proj_tables", None)
+                if cached is None or cached[0] != (id(model), stamp):
+                    w1 = model.conv1.lin.weight
+                    old = cached[1] if cached is not None and cached[1].shape[1] == w1.shape[0] else None
+                    cached = self._gcn_proj_tables = ((id(model), stamp), self.engine.gcn_project_features(w1, out=old))
+                    self.engine.synchronize()  # (once per model state: the other lanes' plans read the table too)
+                plan.set_projected_input(cached[1])
         elif hasattr(model, "plan_params"):
             plan.set_weights(*model.plan_params())
 

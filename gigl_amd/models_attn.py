@@ -5,7 +5,8 @@ Mirror of (paths relative to the reference root):
                [-> L2 normalise]; PyG GCNConv params `conv{1,2}.lin.weight`, `conv{1,2}.bias`.
                The reference applies F.dropout(training=self.is_training) with the CONSTRUCTOR flag (default True)
                even in infer_batch; parity is defined for is_training=False, which is
-               what this inference path computes (no dropout).
+               what this inference path computes (no dropout) — forward(HipBatch) and the one-call plan of make_plan
+               (engine.GcnPlan) alike; forward(GraphData) keeps the quirk.
   GAT          :300-343 + BasicHomogeneousGNN.forward :107-153: GATConv(in, hid, heads=H) ... last layer heads=1,
                relu between layers; PyG 2.5.3 GATConv params `lin.weight`, `att_src`, `att_dst`, `bias`.
 Parameter names come from the un-vendored PyG 2.5.3 ("parity unpinned"); the arithmetic is
@@ -133,6 +134,30 @@ class TwoLayerGCN(nn.Module):
         if self.should_normalize:
             out = torch.nn.functional.normalize(out, p=2, dim=1)
         return out
+
+    def plan_params(self):
+        """the arguments of GcnPlan.set_weights: [conv1.lin.weight, conv2.lin.weight], [conv1.bias, conv2.bias] (None per
+        layer without a bias)"""
+        cs = (self.conv1, self.conv2)
+        return [c.lin.weight.detach() for c in cs], [None if c.bias is None else c.bias.detach() for c in cs]
+
+    def projected_input_pays(self, eng) -> bool:
+        """X W1^T once per model state over the resident table, and a first layer that gathers hid-wide rows
+        (GcnPlan.set_projected_input): worth it when the table's rows are wider than the first layer's output"""
+        return int(self.conv1.in_channels) > int(self.conv1.out_channels)
+
+    def make_plan(self, eng, b: int, fanouts, groups: int = 1):
+        """one-call pipeline (sample -> generic union -> this model's eval-time forward -> one row per root) for batches
+        of `b` roots on `eng` (engine.GcnPlan); weights are snapshotted — plan.set_weights(*model.plan_params()) after
+        updates.  No dropout (see the module's note on the reference's is_training quirk); the output is L2-normalised in
+        the plan when the model asks for it."""
+        from .engine import GcnPlan
+        if len(fanouts) != 2:
+            raise NotImplementedError("the one-call GCN plan is two hops, as the model is two layers")
+        if int(eng.feat_dim) != int(self.conv1.in_channels):
+            raise NotImplementedError(f"the feature table is {eng.feat_dim} wide, the model's input {self.conv1.in_channels}")
+        w, bs = self.plan_params()
+        return GcnPlan(eng, w, bs, b, fanouts, groups=groups, l2_normalize=self.should_normalize)
 
 
 class _GatConvFn(torch.autograd.Function):

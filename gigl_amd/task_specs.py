@@ -210,6 +210,14 @@ class HipGraphSageNodeClassificationSpec(BaseTrainer, BaseInferencer):
             self._resident = None
         self._hbm_splits = None
 
+    def _scores_through_encode(self) -> bool:
+        """the validation and test passes of the stock TwoLayerGCN on a replica graph in one process run as root batches
+        through ResidentGraph.encode — the one-call plan (engine.GcnPlan), the eval-time model without dropout, what the
+        in-HBM Inferencer computes — instead of one GraphData batch at a time through the module's autograd forward"""
+        from .models_attn import TwoLayerGCN
+        res = self._resident
+        return res is not None and type(self._inner_model()) is TwoLayerGCN and not res.sharded and res.world == 1
+
     def _split_batches(self, cfg: GbmlConfigPbWrapper, split: str):
         """in-HBM route: batches of the split's roots sampled in HBM (see _hbm_split).  TFRecord route: the split
         generator's output for `split` (datasetMetadata.supervisedNodeClassificationDataset.*DataUri,
@@ -218,6 +226,10 @@ class HipGraphSageNodeClassificationSpec(BaseTrainer, BaseInferencer):
         hbm = self._hbm_split(cfg)
         if hbm is not None:
             ids, labels = hbm[split]
+            if split != "train" and self._scores_through_encode():
+                # (no gradient is taken: the roots alone go to infer_batch, which encodes them through the one-call plan)
+                yield from self._resident.root_batches(ids, self._batch_size, 1, labels=labels)
+                return
             yield from self._resident.train_batches(ids, labels, self._batch_size)
             return
         rank, world = _rank_world()

@@ -1320,6 +1320,41 @@ int32_t gigl_sage_plan_set_graph_stream(gigl_sage_plan* plan, void* hip_stream, 
 int32_t gigl_sage_plan_flush_profile(gigl_sage_plan* plan);
 int32_t gigl_sage_plan_destroy(gigl_sage_plan* plan);
 
+/* The same one-call pipeline for the reference's STOCK node-classification model at inference, TwoLayerGCN
+ * (python/gigl/src/common/models/pyg/homogeneous.py:488-546: PyG GCNConv -> relu -> GCNConv [-> L2 normalise], no
+ * dropout), as NodeClassificationModelingTaskSpec.infer_batch / validation / test run it
+ * (.../node_classification_modeling_task_spec.py:176-187: `model(data)[root_node_indices]`):
+ *   sample -> GENERIC union (every node numbered, as gigl_union_build numbers them: a leaf that is also an inner node needs
+ *   that node's degree) -> gigl_gcn_dinv over all its nodes (graph part) -> layer 1 over the rows of level <= 1 -> layer 2
+ *   over the roots -> one row per root.
+ * Two hops exactly; dims = {in, hidden, out}; w[l] = conv{l+1}.lin.weight [dims[l+1]][dims[l]] as PyG keeps it, bias[l]
+ * (may be NULL): DEVICE fp32, borrowed.  Semantics are gigl_gcn_gather's: one self loop per node, a stored one replaced,
+ * a source stored twice counts twice, deg = 1 + #non-self in-edges in the batch graph.  The handle is a gigl_sage_plan:
+ * run / run_part / set_groups / use_graph / set_graph_stream / buffers / stats / overflow_add / set_l2_normalize /
+ * flush_profile / destroy are the gigl_sage_plan_* calls, with their contracts (with-replacement trees:
+ * GIGL_E_UNSUPPORTED; a batch set that does not fit the workspace: NaN rows and the overflow flag).
+ * Layer 1 runs by one of two routes.  Aggregate-first (the default): gigl_gcn_gather over the table through the union's
+ * nodes, then gigl_linear (+ bias, relu).  Projected input (gigl_gcn_plan_set_projected_input): A_hat (X W) == (A_hat X) W,
+ * so P = X W1^T is computed ONCE per model state over the resident table (gigl_gcn_project_features: gigl_linear per row
+ * chunk, an fp16 table widened exactly; out = DEVICE fp32 [feature rows][hid]) and the layer is one gather over hid-wide
+ * rows (+ bias, relu): 64 / (hid / 4) rows per wave for hid % 4 == 0, hid <= 256, an element path otherwise.  The table is
+ * borrowed and belongs to the weights it was computed from (gigl_gcn_plan_set_weights does NOT touch it); NULL returns to
+ * aggregate-first.
+ * Layer 2 runs fused after gigl_gcn_plan_set_fused_root(plan, 1) where the shape allows (hid % 4 == 0, hid <= 1024,
+ * hid * out * 4 <= 64 KB; off by default: measured faster than its fallback at hidden 16, slower at hidden 256 — README.md):
+ * one wave per root slot aggregates the root's row of h1, multiplies it by W2 (staged
+ * in LDS once per workgroup), adds the bias, normalises when the plan's L2 switch is on, and writes the caller's row — no
+ * aggregated buffer, no output buffer, no copy step; two slots that hold the same node each compute their row.  Otherwise
+ * gigl_gcn_gather over h1 for the root rows, gigl_linear, and the roots' rows are copied out.  gigl_gcn_plan_fused_root: 1
+ * when the last layer runs fused.  fp32 sums in an order fixed by the row in every route: two runs give the same bits. */
+int32_t gigl_gcn_plan_create(gigl_ctx* ctx, gigl_graph* graph, gigl_feat* feat, int32_t b, const int32_t* fanouts,
+                             const int32_t* dims, const float* const* w, const float* const* bias, gigl_sage_plan** out);
+int32_t gigl_gcn_plan_set_weights(gigl_sage_plan* plan, const float* const* w, const float* const* bias);
+int32_t gigl_gcn_project_features(gigl_ctx* ctx, gigl_feat* feat, const float* w1, int32_t hid, float* out);
+int32_t gigl_gcn_plan_set_projected_input(gigl_sage_plan* plan, const float* proj);
+int32_t gigl_gcn_plan_set_fused_root(gigl_sage_plan* plan, int32_t on);
+int32_t gigl_gcn_plan_fused_root(gigl_sage_plan* plan);
+
 /* ---- one TRAINING step per call, all of it in the library: the loop body of NodeClassificationModelingTaskSpec._train
  * (python/gigl/src/common/modeling_task_specs/node_classification_modeling_task_spec.py:134-173 — zero_grad, forward,
  * cross-entropy on `out[root_node_indices]`, backward, Adam step) for batches sampled in HBM:
