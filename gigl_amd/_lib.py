@@ -17,6 +17,9 @@ GIGL_META_N_NODES, GIGL_META_N_EDGES, GIGL_META_LEVEL0, GIGL_META_OVERFLOW = 0, 
 # words of an evaluation accumulator (gigl_lp_rank_metrics / gigl_nablp_train_plan_eval: doubles)
 LP_EVAL_LOSS_SUM, LP_EVAL_BATCHES, LP_EVAL_MRR_SUM, LP_EVAL_RANK_NODES, LP_EVAL_HITS0 = 0, 1, 2, 3, 4
 LP_EVAL_MAX_KS, LP_EVAL_LEN = 8, 16
+# words of a node-classification evaluation accumulator (gigl_nc_eval_metrics: doubles)
+NC_EVAL_CORRECT, NC_EVAL_EVALUATED, NC_EVAL_LOSS_SUM, NC_EVAL_LOSS_ROWS, NC_EVAL_CALLS, NC_EVAL_SKIPPED = 0, 1, 2, 3, 4, 5
+NC_EVAL_LEN = 8
 # the link-prediction plans' task (gigl_nablp_train_plan_set_task / gigl_lp_task_loss: GIGL_LP_TASK_*)
 LP_TASKS = {"Retrieval": 0, "Margin": 1, "Softmax": 2}
 LOC_HOST, LOC_DEVICE = 0, 1
@@ -78,6 +81,7 @@ SYMBOLS = [
     "gigl_gcn_train_plan_adopt", "gigl_gcn_train_plan_moments", "gigl_gcn_train_plan_set_dropout", "gigl_gcn_train_plan_destroy",
     "gigl_gcn_plan_create", "gigl_gcn_plan_set_weights", "gigl_gcn_project_features", "gigl_gcn_plan_set_projected_input",
     "gigl_gcn_plan_set_fused_root", "gigl_gcn_plan_fused_root",
+    "gigl_nc_eval_metrics",
 ]
 
 KERNEL_IDS = {
@@ -472,6 +476,7 @@ def load() -> C.CDLL:
         "gigl_gcn_train_plan_set_dropout": [vp, C.c_float, C.c_uint64],
         "gigl_gcn_train_plan_destroy": [vp],
         "gigl_lp_rank_metrics": [vp, vp, i64, i32, i32, vp, i32, i32, vp, P(i32), i32, vp],
+        "gigl_nc_eval_metrics": [vp, vp, i32, i64, vp, vp, i32, vp, vp, vp],
         "gigl_nablp_train_plan_adam_steps": [vp, vp],
         "gigl_lp_task_loss": [vp, i32, C.c_float, C.c_float, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp],
         "gigl_lp_task_loss_backward": [vp, i32, C.c_float, C.c_float, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],

@@ -490,6 +490,13 @@ __device__ __forceinline__ float gigl_group_sum(float v, int group) {
   return v;
 }
 
+// The cross-entropy of a row of logits, as the training step (ce_root_row, pipeline.hip) and the evaluation pass
+// (nc_eval_rows_kernel, loss.hip) compute it: the row's maximum mx is subtracted before the exponentials, se = sum_c
+// gigl_ce_exp(row[c], mx), and the row's logsumexp is gigl_ce_lse(mx, se).  (The evaluation passes mx - row[label] as the
+// offset: its loss is then free of the cancellation of two large numbers when the logits sit far from zero.)
+__device__ __forceinline__ float gigl_ce_exp(float v, float mx) { return __expf(v - mx); }
+__device__ __forceinline__ float gigl_ce_lse(float offset, float se) { return offset + __logf(se); }
+
 // Position of this thread's slot in the bucket of its owner r (0xFFFFFFFF: no slot, the result is unused): the next free
 // entry of counts[r], which is bumped for every slot, fitting or not.  Called by ALL threads of a 256-thread workgroup.
 // One global atomic per (workgroup, owner) instead of one per slot: same-address atomics serialise (~13 ns each) and with

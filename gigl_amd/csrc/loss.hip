@@ -15,7 +15,7 @@
 // HBM-bound: 4*Q*C bytes read forward, read + written backward.
 // The training plan's head runs the same kernels over its validity words (LossArgs::valid) through the LpTaskHead interface.
 // Further down: the Margin and Softmax tasks over the training plan's score matrix (gigl_lp_task_loss), the count-min sketch of
-// the sampling correction, the evaluation's rank metrics.
+// the sampling correction, the evaluation's rank metrics, the node-classification score pass (gigl_nc_eval_metrics).
 #include "common.h"
 #include "dispatch.h"
 
@@ -306,6 +306,113 @@ __global__ __launch_bounds__(1024) void lp_rank_sum_kernel(const double* __restr
     for (int k = 0; k < 16; ++k) t += s_w[k][tid];
     acc[tid == 0 ? GIGL_LP_EVAL_MRR_SUM : tid == 1 ? GIGL_LP_EVAL_RANK_NODES : GIGL_LP_EVAL_HITS0 + tid - 2] += t;
   }
+}
+
+// ---- accuracy and cross-entropy of rows of class logits against labels (the loop body of the node-classification
+// trainer's score(), node_classification_modeling_task_spec.py:190-227: argmax, ==, .sum() and a host read per batch).
+// A row takes a group of 2^lg adjacent lanes (its four-column chunks rounded up to a power of two, at most a wave): lane s
+// of the group reads chunks s, s + 2^lg, ...  The row is read once for (maximum, its first index) — torch.argmax's choice:
+// a NaN beats every number, among equals the lowest index wins — and once more, from cache, for the exponentials.
+// row_loss[i] = logsumexp(row) - row[label]; row_bits[i] = [prediction == label] | [0 <= label < width] << 1 (a label
+// outside the row is evaluated, never correct, and has no loss).  A skipped call (*skip_flag != 0) writes nothing.
+constexpr uint32_t NC_ROW_CORRECT = 1u, NC_ROW_HAS_LOSS = 2u;
+
+// (v, i) replaces (bv, bi) when torch.argmax would prefer it
+__device__ __forceinline__ void argmax_take(float& bv, int& bi, float v, int i) {
+  const bool vn = v != v, bn = bv != bv;
+  const bool better = vn ? (!bn || i < bi) : (!bn && (v > bv || (v == bv && i < bi)));
+  if (better) {
+    bv = v;
+    bi = i;
+  }
+}
+
+template <bool V4>  // V4: width % 4 == 0 and every row starts on a 16-byte boundary -> one 16-byte load per chunk
+__global__ __launch_bounds__(256) void nc_eval_rows_kernel(const float* __restrict__ rows, int width, int64_t row_stride,
+                                                           const int32_t* __restrict__ row_index,
+                                                           const int64_t* __restrict__ labels, int n, int lg,
+                                                           const int32_t* __restrict__ skip_flag,
+                                                           float* __restrict__ row_loss, uint32_t* __restrict__ row_bits,
+                                                           int64_t* __restrict__ pred_out) {
+  if (skip_flag && *skip_flag != 0) return;
+  const int G = 1 << lg, sub = threadIdx.x & (G - 1);
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> lg;
+  if (i >= n) return;  // (the whole group leaves: the shuffles below stay inside a group)
+  const float* row = rows + (row_index ? (int64_t)row_index[i] : i) * row_stride;
+  const int chunks = (width + 3) >> 2;
+  float bv = -INFINITY;
+  int bi = 0x7FFFFFFF;  // (a lane without a column loses every tie)
+  for (int j = sub; j < chunks; j += G) {
+    const int c = j << 2;
+    if constexpr (V4) {
+      const float4 q = *reinterpret_cast<const float4*>(row + c);
+      argmax_take(bv, bi, q.x, c);
+      argmax_take(bv, bi, q.y, c + 1);
+      argmax_take(bv, bi, q.z, c + 2);
+      argmax_take(bv, bi, q.w, c + 3);
+    } else {
+      for (int k = c; k < min(c + 4, width); ++k) argmax_take(bv, bi, row[k], k);
+    }
+  }
+  for (int off = G >> 1; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(bv, off, 64);
+    const int oi = __shfl_xor(bi, off, 64);
+    argmax_take(bv, bi, ov, oi);
+  }
+  float se = 0.f;
+  for (int j = sub; j < chunks; j += G) {
+    const int c = j << 2;
+    if constexpr (V4) {
+      const float4 q = *reinterpret_cast<const float4*>(row + c);
+      se += (gigl_ce_exp(q.x, bv) + gigl_ce_exp(q.y, bv)) + (gigl_ce_exp(q.z, bv) + gigl_ce_exp(q.w, bv));
+    } else {
+      for (int k = c; k < min(c + 4, width); ++k) se += gigl_ce_exp(row[k], bv);
+    }
+  }
+  for (int off = G >> 1; off > 0; off >>= 1) se += __shfl_xor(se, off, 64);
+  if (sub != 0) return;
+  const int64_t lab = labels[i];
+  const bool has_loss = lab >= 0 && lab < width;
+  row_loss[i] = has_loss ? gigl_ce_lse(bv - row[lab], se) : 0.f;
+  row_bits[i] = ((int64_t)bi == lab ? NC_ROW_CORRECT : 0u) | (has_loss ? NC_ROW_HAS_LOSS : 0u);
+  if (pred_out) pred_out[i] = bi;
+}
+
+// acc[GIGL_NC_EVAL_*] += the n rows' words, added in a fixed order in fp64 (one workgroup); a skipped call adds 1 to
+// acc[GIGL_NC_EVAL_SKIPPED] and nothing else
+__global__ __launch_bounds__(1024) void nc_eval_sum_kernel(const float* __restrict__ row_loss,
+                                                           const uint32_t* __restrict__ row_bits, int n,
+                                                           const int32_t* __restrict__ skip_flag, double* __restrict__ acc) {
+  __shared__ double s_w[16][3];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (skip_flag && *skip_flag != 0) {
+    if (tid == 0) acc[GIGL_NC_EVAL_SKIPPED] += 1.0;
+    return;
+  }
+  double v[3] = {0.0, 0.0, 0.0};  // correct, rows with a loss, their loss
+  for (int i = tid; i < n; i += 1024) {
+    const uint32_t bits = row_bits[i];
+    v[0] += (bits & NC_ROW_CORRECT) ? 1.0 : 0.0;
+    if (bits & NC_ROW_HAS_LOSS) {
+      v[1] += 1.0;
+      v[2] += (double)row_loss[i];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
+    if (lane == 0) s_w[w][c] = v[c];
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  double t[3] = {0.0, 0.0, 0.0};
+  for (int k = 0; k < 16; ++k)
+    for (int c = 0; c < 3; ++c) t[c] += s_w[k][c];
+  acc[GIGL_NC_EVAL_CORRECT] += t[0];
+  acc[GIGL_NC_EVAL_EVALUATED] += (double)n;
+  acc[GIGL_NC_EVAL_LOSS_SUM] += t[2];
+  acc[GIGL_NC_EVAL_LOSS_ROWS] += t[1];
+  acc[GIGL_NC_EVAL_CALLS] += 1.0;
 }
 
 
@@ -657,6 +764,37 @@ int32_t gigl_lp_rank_metrics(gigl_ctx* ctx, const float* scores, int64_t ld, int
   double* part = (double*)gigl_arena_alloc(ctx, bytes);
   return gigl_lp_rank_metrics_enqueue(ctx, ctx->stream, scores, ld, b, P, pos_cnt, n_neg, neg_col0, neg_valid, ks, n_ks, nullptr,
                                       nullptr, part, acc);
+}
+
+int32_t gigl_nc_eval_metrics(gigl_ctx* ctx, const float* rows, int32_t width, int64_t row_stride, const int32_t* row_index,
+                             const int64_t* labels, int32_t n, const int32_t* skip_flag, double* acc, int64_t* pred_out) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  GIGL_REQUIRE(ctx, rows && labels && acc, "null rows, labels or acc");
+  GIGL_REQUIRE(ctx, width >= 1 && n >= 0, "width=%d (at least 1), n=%d (not negative)", width, n);
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  float* row_loss = nullptr;
+  uint32_t* row_bits = nullptr;
+  if (n > 0) {
+    const int64_t bytes = gigl_align_up((int64_t)n * 4, 256);
+    const int32_t rc = gigl_arena_reset(ctx, 2 * bytes + 256);
+    if (rc != GIGL_OK) return rc;
+    row_loss = (float*)gigl_arena_alloc(ctx, bytes);
+    row_bits = (uint32_t*)gigl_arena_alloc(ctx, bytes);
+    int lg = 0;  // lanes per row: the row's four-column chunks rounded up to a power of two, at most a wave
+    while (lg < 6 && (1 << lg) < (width + 3) / 4) ++lg;
+    const unsigned grid = (unsigned)((((int64_t)n << lg) + 255) / 256);
+    const bool v4 = width % 4 == 0 && row_stride % 4 == 0 && ((uintptr_t)rows & 15) == 0;
+    if (v4)
+      hipLaunchKernelGGL(nc_eval_rows_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, rows, width, row_stride, row_index,
+                         labels, n, lg, skip_flag, row_loss, row_bits, pred_out);
+    else
+      hipLaunchKernelGGL(nc_eval_rows_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, rows, width, row_stride, row_index,
+                         labels, n, lg, skip_flag, row_loss, row_bits, pred_out);
+  }
+  hipLaunchKernelGGL(nc_eval_sum_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const float*)row_loss,
+                     (const uint32_t*)row_bits, n, skip_flag, acc);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
 }
 
 

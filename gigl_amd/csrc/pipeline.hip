@@ -739,9 +739,9 @@ __device__ __forceinline__ void ce_root_row(const float* __restrict__ out, int w
   for (int c = lane; c < width; c += 64) mx = fmaxf(mx, row[c]);
   for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
   float se = 0.f;
-  for (int c = lane; c < width; c += 64) se += __expf(row[c] - mx);
+  for (int c = lane; c < width; c += 64) se += gigl_ce_exp(row[c], mx);
   for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
-  const float lse = mx + __logf(se);
+  const float lse = gigl_ce_lse(mx, se);
   const int64_t lab = labels[i];
   if (lab < 0 || lab >= width) {
     // (torch's cross_entropy asserts on such a target; here the batch is reported failed — NaN loss, no update — instead

@@ -1214,6 +1214,31 @@ class HipEngine:
             check(self._lib.gigl_lp_task_loss_backward(*head, p(row_a), p(row_b), p(out3), p(d)), self._ctx)
         return out3, row_a, row_b, d
 
+    def nc_eval_metrics(self, rows: torch.Tensor, labels: torch.Tensor, acc: torch.Tensor,
+                        row_index: Optional[torch.Tensor] = None, skip_flag: Optional[torch.Tensor] = None,
+                        pred_out: Optional[torch.Tensor] = None) -> None:
+        """accuracy and cross-entropy words of rows of class logits ADDED into acc (gigl_nc_eval_metrics; _lib.NC_EVAL_*):
+        rows float32 device [*, width] with unit column stride, labels int64 device [n], acc float64 device [NC_EVAL_LEN];
+        row i of the call is rows[row_index[i]] (int32 device [n]) or rows[i]; skip_flag int32 device [1]: non-zero skips
+        the call; pred_out int64 device [n] takes the predictions.  Enqueued on the bound stream, no host read."""
+        assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and (rows.stride(1) == 1 or rows.shape[1] == 1)
+        assert labels.is_cuda and labels.dtype == torch.int64 and labels.dim() == 1 and labels.is_contiguous()
+        assert acc.is_cuda and acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() >= _lib.NC_EVAL_LEN
+        n = int(labels.numel())
+        if row_index is None:
+            assert rows.shape[0] >= n
+        else:
+            assert row_index.is_cuda and row_index.dtype == torch.int32 and row_index.is_contiguous() and row_index.numel() == n
+        assert skip_flag is None or (skip_flag.is_cuda and skip_flag.dtype == torch.int32 and skip_flag.numel() >= 1)
+        assert pred_out is None or (pred_out.is_cuda and pred_out.dtype == torch.int64 and pred_out.is_contiguous()
+                                    and pred_out.numel() >= n)
+        if n == 0:  # (an empty tensor has no address; the entry wants one even where it reads nothing: a call is counted)
+            labels = torch.zeros(1, dtype=torch.int64, device=self.device)
+            rows = rows if rows.numel() else torch.zeros((1, rows.shape[1]), dtype=torch.float32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(self._lib.gigl_nc_eval_metrics(self._ctx, p(rows), int(rows.shape[1]), int(rows.stride(0)), p(row_index),
+                                             p(labels), n, p(skip_flag), p(acc), p(pred_out)), self._ctx)
+
     def project_features(self, w_fused: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """[X W_l^T | X W_r^T] over the whole resident feature table for a first-layer fused weight [out, 2*in]
         (gigl_sage_project_features): one fp32 table [n_rows, 2*out] on the device — the input of

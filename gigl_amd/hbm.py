@@ -533,6 +533,51 @@ class ResidentGraph:
             raise RuntimeError(f"{n} pipelined plan call(s) overflowed their batch workspace and were not settled "
                                "(ResidentGraph.call_overflowed): their rows are NaN")
 
+    def score_roots(self, model, ids: np.ndarray, labels: np.ndarray, batch_size: int) -> Optional[dict]:
+        """a whole scoring pass of a node-classification model over the roots `ids` with `labels` -> {"correct",
+        "evaluated", "loss" (mean cross-entropy over the roots whose label lies inside the row), "calls", "redone"}: what
+        the trainer's score() computes with an argmax, a comparison, a sum and a host read per batch
+        (node_classification_modeling_task_spec.py:190-227).  Here every batch is one call of the model's one-call plan
+        (encode, pipelined: defer_overflow_check) whose rows go straight into engine.nc_eval_metrics with the call's overflow
+        flag as its skip flag; the labels of the pass are uploaded once and the accumulators read ONCE, after the last call.
+        Calls that overflowed the plan's workspace added nothing; they are redone through the staged launches and added
+        through the same entry (a second read, in that case only).  The divisions are the caller's, in double.
+        None when the model has no one-call plan here (a sharded graph, WORLD_SIZE > 1, encoders outside the plans): the
+        caller keeps its batch-by-batch route."""
+        from ._lib import NC_EVAL_CALLS, NC_EVAL_CORRECT, NC_EVAL_EVALUATED, NC_EVAL_LEN, NC_EVAL_LOSS_ROWS, NC_EVAL_LOSS_SUM
+        b = int(batch_size)
+        if self.sharded or self.world != 1 or self._plan_for(model, b, 1) is None:
+            return None
+        ids, labels = np.asarray(ids, dtype=np.int64), np.asarray(labels, dtype=np.int64)
+        assert ids.shape == labels.shape and ids.ndim == 1
+        if ids.size == 0:
+            return {"correct": 0, "evaluated": 0, "loss": 0.0, "calls": 0, "redone": 0}
+        eng = self.engine
+        labels_dev = torch.from_numpy(labels).pin_memory().to(self.device, non_blocking=True)
+        acc = torch.zeros(NC_EVAL_LEN, dtype=torch.float64, device=self.device)
+        issued = []
+        for c, batch in enumerate(self.root_batches(ids, b, 1)):
+            batch.defer_overflow_check = True
+            rows = self.encode(model, batch)  # (binds the engine to the current stream: the metrics follow the rows on it)
+            slot = getattr(batch, "_overflow_slot", None)
+            eng.nc_eval_metrics(rows, labels_dev[c * b: c * b + rows.shape[0]], acc,
+                                skip_flag=slot["dev"] if slot is not None else None)
+            issued.append((c, batch))
+        host = acc.cpu()  # the pass's one blocking read: every call above has finished, its overflow flag is on the host
+        redo = [(c, batch) for c, batch in issued if self.call_overflowed(batch)]
+        for c, batch in redo:
+            batch.force_staged, batch.defer_overflow_check = True, False
+            rows = self.encode(model, batch)
+            eng.bind_stream(torch.cuda.current_stream(self.device))
+            eng.nc_eval_metrics(rows.contiguous(), labels_dev[c * b: c * b + rows.shape[0]], acc)
+        if redo:
+            self.overflow_redone += len(redo)
+            host = acc.cpu()
+        a = host.tolist()
+        return {"correct": int(a[NC_EVAL_CORRECT]), "evaluated": int(a[NC_EVAL_EVALUATED]),
+                "loss": a[NC_EVAL_LOSS_SUM] / max(a[NC_EVAL_LOSS_ROWS], 1.0), "calls": int(a[NC_EVAL_CALLS]),
+                "redone": len(redo)}
+
     def hip_batch(self, roots: torch.Tensor, train: bool = False):
         """sampled trees + the batch union graph of `roots` (int32 device ids) as a models.HipBatch"""
         from .models import HipBatch

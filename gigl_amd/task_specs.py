@@ -71,6 +71,11 @@ class HipGraphSageNodeClassificationSpec(BaseTrainer, BaseInferencer):
         if self._dropout is not None:
             self._encoder_kwargs["dropout"] = self._dropout
         self._dropout_seed = int(kwargs.get("dropout_seed", 0))
+        # eval_plan: auto (default) | on | off — validation and test passes scored on the device, one host read per pass
+        # (_score_on_device); the link-prediction spec's argument
+        self._eval_plan = str(kwargs.get("eval_plan", "auto")).lower()
+        if self._eval_plan not in ("auto", "on", "off"):
+            raise ValueError(f"eval_plan must be auto, on or off (got {self._eval_plan!r})")
         self._is_training = is_training
         self._model: Optional[torch.nn.Module] = None
         self._engine = None
@@ -402,6 +407,37 @@ class HipGraphSageNodeClassificationSpec(BaseTrainer, BaseInferencer):
             num_correct, num_evaluated = int(t[0].item()), int(t[1].item())
         return num_correct / max(num_evaluated, 1)
 
+    # the encoder classes whose passes `eval_plan: auto` scores on the device: those measured faster than score() over the
+    # parent's route on both shapes of scripts/micro_nc_score.py by more than the runs' spread (profiles/nc_score.txt);
+    # `on` takes every encoder with a one-call plan
+    EVAL_PLAN_AUTO_KINDS = ("TwoLayerGCN", "GraphSAGE")
+
+    @no_grad_eval
+    def _score_on_device(self, cfg: GbmlConfigPbWrapper, split: str) -> Optional[float]:
+        """accuracy of the split's roots through ResidentGraph.score_roots — every batch one call of the model's one-call
+        inference plan, predictions compared and counted on the device (gigl_nc_eval_metrics), ONE host read per pass —
+        or None where that does not apply (eval_plan off, the TFRecord route, WORLD_SIZE > 1, a sharded graph, an encoder
+        without a one-call plan): the caller then runs score() over _split_batches as before"""
+        if self._eval_plan == "off":
+            return None
+        hbm = self._hbm_split(cfg)
+        res = self._resident
+        if hbm is None or res is None or res.sharded or res.world != 1:
+            return None
+        model = self._inner_model()
+        if self._eval_plan == "auto" and type(model).__name__ not in self.EVAL_PLAN_AUTO_KINDS:
+            return None
+        ids, labels = hbm[split]
+        m = res.score_roots(model, ids, labels, self._batch_size)
+        if m is None:
+            return None
+        self.last_score = m  # (the pass's counts, mean loss and redone calls, for whoever wants more than the accuracy)
+        return m["correct"] / max(m["evaluated"], 1)
+
+    def _score_split(self, cfg: GbmlConfigPbWrapper, split: str, device: torch.device) -> float:
+        acc = self._score_on_device(cfg, split)
+        return acc if acc is not None else self.score(self._split_batches(cfg, split), device)
+
     def train(self, gbml_config_pb_wrapper: GbmlConfigPbWrapper, device: torch.device, profiler=None) -> None:
         self._device = device
         self._ensure_engine(device)
@@ -411,7 +447,7 @@ class HipGraphSageNodeClassificationSpec(BaseTrainer, BaseInferencer):
             train_loss = self._train_graphed(gbml_config_pb_wrapper, device)
             if train_loss is None:
                 train_loss = self._train(self._split_batches(gbml_config_pb_wrapper, "train"), device)
-            val_acc = self.score(self._split_batches(gbml_config_pb_wrapper, "val"), device)
+            val_acc = self._score_split(gbml_config_pb_wrapper, "val", device)
             best_val_acc = max(best_val_acc, val_acc)
             self.history.append({"epoch": epoch, "loss": float(train_loss) if train_loss is not None else float("nan"),
                                  "val_acc": val_acc})
@@ -421,5 +457,5 @@ class HipGraphSageNodeClassificationSpec(BaseTrainer, BaseInferencer):
     def eval(self, gbml_config_pb_wrapper: GbmlConfigPbWrapper, device: torch.device) -> EvalMetricsCollection:
         self._device = device
         self._ensure_engine(device)
-        test_acc = self.score(self._split_batches(gbml_config_pb_wrapper, "test"), device)
+        test_acc = self._score_split(gbml_config_pb_wrapper, "test", device)
         return EvalMetricsCollection(metrics=[EvalMetric.from_eval_metric_type(EvalMetricType.acc, test_acc)])

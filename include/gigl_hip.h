@@ -1131,6 +1131,35 @@ int32_t gigl_lp_rank_metrics(gigl_ctx* ctx, const float* scores, int64_t ld, int
                              int32_t n_neg, int32_t neg_col0, const int32_t* neg_valid /* may be NULL */,
                              const int32_t* ks /* HOST */, int32_t n_ks, double* acc /* DEVICE [GIGL_LP_EVAL_LEN], += */);
 
+/* ---- accuracy and cross-entropy of rows of class logits against labels, summed on the device.  Replaces the loop body of
+ *      NodeClassificationModelingTaskSpec.score (python/gigl/src/common/modeling_task_specs/
+ *      node_classification_modeling_task_spec.py:190-227): argmax, ==, .sum() and a host read of the count per batch.
+ * rows: DEVICE fp32, `width` >= 1 columns, rows `row_stride` floats apart; row i of the call is rows[row_index[i]] (DEVICE
+ *   int32 [n]) or rows[i] when row_index == NULL.  labels: DEVICE int64 [n].  n >= 0 (n == 0 counts a call, nothing else).
+ * For each row: the prediction is the index of its maximum as torch.argmax(dim=1) chooses it (the first index among equal
+ *   maxima; a row holding NaN predicts its first NaN; -inf is an ordinary value); acc[GIGL_NC_EVAL_CORRECT] +=
+ *   [prediction == label], acc[GIGL_NC_EVAL_EVALUATED] += 1; with 0 <= label < width also acc[GIGL_NC_EVAL_LOSS_SUM] +=
+ *   logsumexp(row) - row[label] (the maximum subtracted first) and acc[GIGL_NC_EVAL_LOSS_ROWS] += 1.  A label outside the row
+ *   is evaluated and not correct, and is no error.  Every call adds 1 to acc[GIGL_NC_EVAL_CALLS].
+ * skip_flag (DEVICE int32 [1], may be NULL): when *skip_flag != 0 the call adds 1 to acc[GIGL_NC_EVAL_SKIPPED] and nothing to
+ *   the other words, and writes nothing to pred_out — a pass hands in the overflow flag of the plan call that produced
+ *   the rows (gigl_sage_plan_overflow_add: such rows are NaN) and redoes the call later.
+ * acc: DEVICE double [GIGL_NC_EVAL_LEN], ADDED to: the caller zeroes it, issues any number of calls and reads it once.  Row
+ *   results are added in a fixed order in fp64, without atomics: two runs give the same bits.  pred_out: DEVICE int64 [n]
+ *   or NULL.  Reads n * width * 4 bytes of rows once (the exponentials' second read comes from cache).  Enqueued on the ctx
+ *   stream, no synchronisation.  width < 1, n < 0, null rows / labels / acc: GIGL_E_INVALID_ARG, nothing is launched. */
+#define GIGL_NC_EVAL_CORRECT 0
+#define GIGL_NC_EVAL_EVALUATED 1
+#define GIGL_NC_EVAL_LOSS_SUM 2
+#define GIGL_NC_EVAL_LOSS_ROWS 3 /* rows whose label lies inside the row */
+#define GIGL_NC_EVAL_CALLS 4     /* calls that contributed */
+#define GIGL_NC_EVAL_SKIPPED 5   /* calls whose skip_flag was set */
+#define GIGL_NC_EVAL_LEN 8       /* doubles */
+int32_t gigl_nc_eval_metrics(gigl_ctx* ctx, const float* rows, int32_t width, int64_t row_stride,
+                             const int32_t* row_index /* may be NULL */, const int64_t* labels, int32_t n,
+                             const int32_t* skip_flag /* DEVICE, may be NULL */, double* acc /* DEVICE [GIGL_NC_EVAL_LEN], += */,
+                             int64_t* pred_out /* DEVICE [n], may be NULL */);
+
 /* ---- the Margin and Softmax link-prediction tasks over a score matrix in the training plan's layout.  Replaces
  *      Margin.forward / Softmax.forward (python/gigl/src/common/models/layers/task.py:62-105) with MarginLoss / SoftmaxLoss
  *      (loss.py:21-174) and their autograd backward: three launches (rows, sum, backward), no padded per-anchor matrices.
