@@ -36,7 +36,7 @@ SYMBOLS = [
     "gigl_ctx_synchronize", "gigl_ctx_reserve", "gigl_memcpy", "gigl_graph_load_csc", "gigl_graph_build_from_coo",
     "gigl_graph_info", "gigl_graph_device_ptrs", "gigl_graph_destroy", "gigl_features_load",
     "gigl_features_device_ptr", "gigl_features_destroy", "gigl_sample_khop", "gigl_sample_positives",
-    "gigl_union_capacity", "gigl_union_build", "gigl_gather_mean", "gigl_linear",
+    "gigl_union_capacity", "gigl_union_route", "gigl_union_build", "gigl_gather_mean", "gigl_linear",
     "gigl_linear_batched", "gigl_retrieval_loss_batched",
     "gigl_profile_enable", "gigl_profile_read", "gigl_profile_reset",
     "gigl_sage_plan_create", "gigl_sage_plan_set_weights", "gigl_sage_plan_buffers", "gigl_sage_plan_run",
@@ -298,6 +298,7 @@ def load() -> C.CDLL:
         "gigl_sample_positives": [vp, vp, vp, i32, i32, i32, i32, vp, vp],
         "gigl_sample_out_neighbors": [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
         "gigl_union_capacity": [i32, P(i32), i32, P(i64), P(i64)],
+        "gigl_union_route": [i32, P(i32), i32, i32, i32, P(i32)],
         "gigl_union_build": [vp, vp, P(GiglTree), P(GiglUnion)],
         "gigl_union_build_groups": [vp, vp, P(GiglTree), i32, P(GiglUnion)],
         "gigl_sage_plan_set_groups": [vp, i32],

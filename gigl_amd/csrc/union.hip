@@ -28,6 +28,7 @@
 // Rows keep their pre-dedup capacity: row i is col[rowptr[i] .. rowend[i]).
 #include "common.h"
 #include "dispatch.h"
+#include "union_route.h"
 
 #include <mutex>
 
@@ -1077,6 +1078,25 @@ __global__ __launch_bounds__(256) void lg2_count_kernel(UnionArgs a, Lg2Args g, 
 // dependent loads; a thread per row keeps 64 rows in flight per wave.
 constexpr int TINY_ROW = 32;
 
+// a row held in TINY_ROW registers (padded with +inf), ascending: a fully unrolled bitonic network, 240
+// compare-exchanges, no memory access
+__device__ __forceinline__ void tiny_row_sort(int32_t (&v)[TINY_ROW]) {
+#pragma unroll
+  for (int k = 2; k <= TINY_ROW; k <<= 1)
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1)
+#pragma unroll
+      for (int x = 0; x < TINY_ROW; ++x) {
+        const int y = x ^ j;
+        if (y > x) {
+          const bool up = (x & k) == 0;
+          const int32_t lo = min(v[x], v[y]), hi = max(v[x], v[y]);
+          v[x] = up ? lo : hi;
+          v[y] = up ? hi : lo;
+        }
+      }
+}
+
 __global__ __launch_bounds__(256) void lg2_row_sort_tiny_kernel(const int32_t* tiny_rows, const int32_t* tiny_count,
                                                                 const int32_t* rowptr, int32_t* rowend, int32_t* col,
                                                                 int32_t* edge_counters, int ec_stride = 1) {
@@ -1091,20 +1111,7 @@ __global__ __launch_bounds__(256) void lg2_row_sort_tiny_kernel(const int32_t* t
     int32_t v[TINY_ROW];
 #pragma unroll
     for (int j = 0; j < TINY_ROW; ++j) v[j] = j < m ? col[s + j] : 0x7FFFFFFF;  // (independent loads: all in flight together)
-#pragma unroll
-    for (int k = 2; k <= TINY_ROW; k <<= 1)
-#pragma unroll
-      for (int j = k >> 1; j > 0; j >>= 1)
-#pragma unroll
-        for (int x = 0; x < TINY_ROW; ++x) {
-          const int y = x ^ j;
-          if (y > x) {
-            const bool up = (x & k) == 0;
-            const int32_t lo = min(v[x], v[y]), hi = max(v[x], v[y]);
-            v[x] = up ? lo : hi;
-            v[y] = up ? hi : lo;
-          }
-        }
+    tiny_row_sort(v);
     int32_t u = 0, prev = -1;  // (entries are local or global node ids: non-negative)
 #pragma unroll
     for (int j = 0; j < TINY_ROW; ++j) {
@@ -1119,6 +1126,45 @@ __global__ __launch_bounds__(256) void lg2_row_sort_tiny_kernel(const int32_t* t
   }
   for (int off = 32; off > 0; off >>= 1) edges += __shfl_xor(edges, off, 64);
   if ((threadIdx.x & 63) == 0 && edges) atomicAdd(&edge_counters[(blockIdx.x & 31) * ec_stride], edges);
+}
+
+// The row of a root that occurs ONCE in its batch is written by the fill pass in slot order (no cursor, no sort: it is
+// duplicate-free as sampled) — ascending in the sources' GLOBAL ids, while a level-0 row holds LOCAL ids.  One thread
+// per level-0 row of 2..f0 entries (a longer row belongs to a root that occurs more than once: sorted above) puts it in
+// ascending order as the header documents: the register network of the tiny sort up to TINY_ROW entries, an insertion
+// sort in place beyond (fan-outs above 32).  A row that is ascending already — every row the sorts above produced —
+// is read once and left alone.
+__global__ __launch_bounds__(256) void lg_root_rows_ascending_kernel(const int32_t* __restrict__ meta, int32_t f0,
+                                                                     const int32_t* __restrict__ rowptr,
+                                                                     const int32_t* __restrict__ rowend, int32_t* col) {
+  const int32_t n0 = meta[GIGL_META_LEVEL0];
+  for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n0; i += gridDim.x * blockDim.x) {
+    const int32_t s = rowptr[i], m = rowend[i] - s;
+    if (m < 2 || m > f0) continue;
+    if (m > TINY_ROW) {
+      for (int32_t j = 1; j < m; ++j) {
+        const int32_t x = col[s + j];
+        int32_t q = j - 1;
+        while (q >= 0 && col[s + q] > x) {
+          col[s + q + 1] = col[s + q];
+          --q;
+        }
+        col[s + q + 1] = x;
+      }
+      continue;
+    }
+    int32_t v[TINY_ROW];
+#pragma unroll
+    for (int j = 0; j < TINY_ROW; ++j) v[j] = j < m ? col[s + j] : 0x7FFFFFFF;
+    bool ascending = true;
+#pragma unroll
+    for (int j = 1; j < TINY_ROW; ++j) ascending = ascending && v[j - 1] <= v[j];
+    if (ascending) continue;
+    tiny_row_sort(v);
+#pragma unroll
+    for (int j = 0; j < TINY_ROW; ++j)
+      if (j < m) col[s + j] = v[j];
+  }
 }
 
 // local ids, node list, row storage.  A thread numbers the first occurrences it holds (its own position, then its
@@ -1727,6 +1773,12 @@ int32_t union_build_lg2(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* t
     hipLaunchKernelGGL(lg2_row_sort_big_kernel<BIG_ROW_CAP>, dim3(8), dim3(1024), 2 * BIG_ROW_CAP * sizeof(int32_t), st,
                        out->rowptr, out->rowend, out->col, big_rows, big_count, out->meta + GIGL_META_OVERFLOW,
                        edge_counters, ticket_big, out->meta);
+    {
+      int64_t rb = ((int64_t)b + 255) / 256;
+      if (rb > 1024) rb = 1024;
+      hipLaunchKernelGGL(lg_root_rows_ascending_kernel, dim3((unsigned)rb), dim3(256), 0, st, out->meta, (int32_t)f0,
+                         out->rowptr, out->rowend, out->col);
+    }
   }
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
@@ -1759,13 +1811,9 @@ int32_t union_build_lg2(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* t
 //     read at a known position.  Numbering order, row order and every output are LG2's, bit for bit
 //     (GIGL_UNION_LG2=1 in the environment keeps LG2 for A/B runs; shapes whose per-batch stream does not fit 20-bit
 //     codes or 16 partitions fall back to it).
-constexpr int LG3_CODE_BITS = 20;
-constexpr uint32_t LG3_CODE_MASK = (1u << LG3_CODE_BITS) - 1u;
+// (LG3_CODE_BITS, LG3_MAX_PARTS, the workgroup shapes and the table size live with the route arithmetic: union_route.h)
 constexpr uint32_t LG3_EMPTY = 0xFFFFFFFFu;
 constexpr int32_t LG3_XTAG = 1 << 30;  // fpx entry that has become (local id | LG3_XTAG): an extra that is a first occurrence
-constexpr int LG3_MAX_PARTS = 16;
-constexpr int LG3_NT_DEFAULT = 512;      // threads per dedup workgroup (round 5: 512 x 128-KB tables find a CU sooner next to other kernels than 1024 — 7.0 vs 10.7 us/step under three streams; smaller tables lose to their redundant stream scans: profiles/r05d_lg3_shapes.txt)
-constexpr int LG3_CAP_DEFAULT = 16384;   // slots of its LDS table (8 bytes each)
 
 struct Lg3Args {
   const uint32_t* roots;
@@ -1872,8 +1920,6 @@ __device__ __forceinline__ bool lg3_contributes(const Lg3Args& a, uint32_t first
 __device__ __forceinline__ bool lg3_row_is_segment(const Lg3Args& a, uint32_t code, int c) {
   return a.alias_base >= 0 && a.whole_rows && c < a.f1 && code >= (uint32_t)a.gr;
 }
-
-constexpr int LG3_TC = 5;  // per-tile counts: level-0 firsts, level-1 firsts, row entries to store, long / tiny rows to sort
 
 // NT: threads per workgroup (1024, or 512 with smaller tables: more, smaller workgroups that fit next to other kernels)
 template <int NT>
@@ -2445,44 +2491,17 @@ __global__ __launch_bounds__(256) void lg3_fill_kernel(Lg3Args a, int32_t* rowen
   }
 }
 
+// r: union_route()'s answer for this call (r.route == UNION_ROUTE_LG3)
 int32_t union_build_lg3(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* tree, int32_t group_roots,
-                        gigl_union* out, bool multiset_rows, bool* taken) {
-  *taken = false;
+                        gigl_union* out, bool multiset_rows, const UnionRoute& r) {
   const int b = tree->b;
   const int f0 = tree->fanouts[0], f1 = tree->fanouts[1];
   const int64_t S0 = (int64_t)b * f0, S1 = S0 * f1, T_in = b + S0;
   const int64_t n_groups = b / group_roots;
-  const int64_t gr = group_roots, Tg = gr * (1 + f0), S1g = gr * f0 * f1;
-  // (20-bit stream codes; a thread of the dedup pass keeps one bit per 1024 hop-0 slots of the batch in a 64-bit mask)
-  // workgroup shape of the dedup pass (round 5): 512 | 1024 threads, up to LG3_CAP_DEFAULT slots per table
-  // (a thread keeps one bit per NT hop-0 slots of its batch in a 64-bit mask: batches of more than 64 * 512 slots — B = 4096
-  // at fan-out 15 — take the 1024-thread shape)
-  int lg3_nt = gr * f0 <= 64 * (int64_t)LG3_NT_DEFAULT ? LG3_NT_DEFAULT : 1024;
-  if (Tg + S1g >= (int64_t)LG3_CODE_MASK || f1 > 64 || b + S0 + S1 >= ((int64_t)1 << 31) || gr * f0 > 64 * (int64_t)lg3_nt) return GIGL_OK;  // -> LG2
-  // LDS table: 8-byte slots at load <= 1/2 for the nodes a batch may hold (more do not fit the plan's workspace)
-  int64_t cap = 1024;
-  while (cap < 2 * Tg && cap < LG3_CAP_DEFAULT) cap <<= 1;
-  const int64_t P = (2 * Tg + cap - 1) / cap;
-  if (P > LG3_MAX_PARTS) return GIGL_OK;
-  // (the 512-thread shape pays when the launch fills the GPU — a workgroup per CU and more, other streams' kernels beside
-  // it; a launch of fewer workgroups than CUs is over sooner with 1024 threads each: the sharded plan's 16-batch calls,
-  // lg3_dedup 3.6 -> 5.0 us per rank-step with 512, profiles/r05e_emulated_world8_kernel_time.txt)
-  if (n_groups * P < 256) lg3_nt = 1024;
-  // a call of a few batches (a training step: one) leaves most CUs without a workgroup of the dedup pass, whose duration
-  // is that of ONE workgroup walking its batch's whole stream (~80 us at [25,10] x 1024): LG2's position-parallel
-  // launches finish such a call sooner (training step 0.42 -> 0.39 ms)
-  static const int64_t min_wgs = getenv("GIGL_LG3_MIN_WGS") ? atoll(getenv("GIGL_LG3_MIN_WGS")) : 32;
-  if (n_groups * P < min_wgs) return GIGL_OK;
-  int64_t rs = 64;
-  int rs_log2 = 6;
-  while (rs < 2 * gr) {
-    rs <<= 1;
-    ++rs_log2;
-  }
-  const int64_t n_tcnt = LG3_TC * ((gr >> 10) + 2 + ((gr * f0) >> 10) + 2);
-  const size_t lds_bytes = (size_t)cap * 8 + (size_t)(rs + rs / 4 + n_tcnt) * 4;
-  if (lds_bytes > 150 * 1024) return GIGL_OK;
-  *taken = true;
+  const int64_t gr = group_roots, Tg = gr * (1 + f0);
+  const int lg3_nt = r.nt, rs_log2 = r.rs_log2;
+  const int64_t cap = r.cap, P = r.P, rs = r.rs;
+  const size_t lds_bytes = r.lds_bytes;
   hipStream_t st = ctx->stream;
   const int32_t n_tiles = (int32_t)((T_in + TILE - 1) / TILE);
   constexpr int EC_STRIDE = 32;  // every spread edge counter on its own 128-byte line (same-line atomics serialise in L2)
@@ -2584,6 +2603,12 @@ int32_t union_build_lg3(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* t
     hipLaunchKernelGGL(lg2_row_sort_big_kernel<BIG_ROW_CAP>, dim3(8), dim3(1024), 2 * BIG_ROW_CAP * sizeof(int32_t), st,
                        out->rowptr, out->rowend, out->col, big_rows, big_count, out->meta + GIGL_META_OVERFLOW,
                        edge_counters, ticket_big, out->meta, EC_STRIDE, (const int32_t*)tile_edges, n_tiles);
+    {
+      int64_t rb = ((int64_t)b + 255) / 256;
+      if (rb > 1024) rb = 1024;
+      hipLaunchKernelGGL(lg_root_rows_ascending_kernel, dim3((unsigned)rb), dim3(256), 0, st, out->meta, (int32_t)f0,
+                         out->rowptr, out->rowend, out->col);
+    }
   }
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;
@@ -2603,6 +2628,23 @@ int32_t gigl_union_capacity(int32_t b, const int32_t* fanouts, int32_t hops, int
   }
   if (cap_nodes) *cap_nodes = edges + b;
   if (cap_edges) *cap_edges = edges;
+  return GIGL_OK;
+}
+
+int32_t gigl_union_route(int32_t b, const int32_t* fanouts, int32_t hops, int32_t group_roots, int32_t leaf_global,
+                         int32_t out[GIGL_ROUTE_LEN]) {
+  if (!fanouts || !out || hops < 1 || hops > GIGL_MAX_HOPS || b < 1 || group_roots < 1 || b % group_roots) return GIGL_E_INVALID_ARG;
+  for (int k = 0; k < hops; ++k)
+    if (fanouts[k] < 1) return GIGL_E_INVALID_ARG;
+  const UnionRoute r = union_route(b, fanouts, hops, group_roots, leaf_global);
+  out[GIGL_ROUTE_BUILD] = r.route;
+  out[GIGL_ROUTE_THREADS] = r.nt;
+  out[GIGL_ROUTE_PARTS] = (int32_t)r.P;
+  out[GIGL_ROUTE_TABLE_SLOTS] = (int32_t)r.cap;
+  out[GIGL_ROUTE_ROOT_SLOTS] = (int32_t)r.rs;
+  out[GIGL_ROUTE_LDS_BYTES] = (int32_t)r.lds_bytes;
+  out[GIGL_ROUTE_WHY] = r.why;
+  out[7] = 0;
   return GIGL_OK;
 }
 
@@ -2649,12 +2691,8 @@ int32_t gigl_union_build_impl(gigl_ctx* ctx, const uint32_t* roots, const gigl_t
   }
   if (leaf_global && hops == 2) {
     GIGL_REQUIRE(ctx, group_roots >= 1 && b % group_roots == 0, "group_roots=%d does not divide b=%d", group_roots, b);
-    static const bool keep_lg2 = getenv("GIGL_UNION_LG2") != nullptr;  // (A/B knob)
-    if (!keep_lg2) {
-      bool taken = false;
-      const int32_t rc3 = union_build_lg3(ctx, roots, tree, group_roots, out, (leaf_global & 2) != 0, &taken);
-      if (rc3 != GIGL_OK || taken) return rc3;
-    }
+    const UnionRoute r = union_route(b, tree->fanouts, hops, group_roots, leaf_global);
+    if (r.route == UNION_ROUTE_LG3) return union_build_lg3(ctx, roots, tree, group_roots, out, (leaf_global & 2) != 0, r);
     return union_build_lg2(ctx, roots, tree, group_roots, out, (leaf_global & 2) != 0);
   }
 

@@ -746,6 +746,37 @@ typedef struct gigl_union {
 
 int32_t gigl_union_capacity(int32_t b, const int32_t* fanouts, int32_t hops, int64_t* cap_nodes,
                             int64_t* cap_edges);
+/* Which build a union call of this shape takes, and with what launch shape — host only: no context, no device.  b roots
+ * in batches of group_roots (which divides b), leaf_global as the plans pass it (0: the public entry points).  The
+ * library's own dispatch asks the same function (csrc/union_route.h), so the answer is what a call launches; it honours
+ * GIGL_UNION_LG2 and GIGL_LG3_MIN_WGS as the dispatch does (both read once per process).
+ *   out[GIGL_ROUTE_BUILD]        GIGL_ROUTE_GENERIC | GIGL_ROUTE_LG2 (node table in HBM) | GIGL_ROUTE_LG3 (table in LDS)
+ *   out[GIGL_ROUTE_WHY]          LG2 only: the rule that kept the call from LG3 (GIGL_ROUTE_WHY_*)
+ * and LG3's shape, filled as far as the decision got (0 past the rule that sent the call to LG2, and for GENERIC):
+ *   out[GIGL_ROUTE_THREADS]      threads per dedup workgroup (512 | 1024)
+ *   out[GIGL_ROUTE_PARTS]        hash partitions (dedup workgroups) per batch
+ *   out[GIGL_ROUTE_TABLE_SLOTS]  8-byte slots of a workgroup's LDS table
+ *   out[GIGL_ROUTE_ROOT_SLOTS]   slots of its root set
+ *   out[GIGL_ROUTE_LDS_BYTES]    dynamic LDS of a dedup workgroup */
+#define GIGL_ROUTE_BUILD 0
+#define GIGL_ROUTE_THREADS 1
+#define GIGL_ROUTE_PARTS 2
+#define GIGL_ROUTE_TABLE_SLOTS 3
+#define GIGL_ROUTE_ROOT_SLOTS 4
+#define GIGL_ROUTE_LDS_BYTES 5
+#define GIGL_ROUTE_WHY 6
+#define GIGL_ROUTE_LEN 8
+#define GIGL_ROUTE_GENERIC 0
+#define GIGL_ROUTE_LG2 1
+#define GIGL_ROUTE_LG3 2
+#define GIGL_ROUTE_WHY_NONE 0
+#define GIGL_ROUTE_WHY_CODES 1    /* stream codes past 20 bits, hop-0 slots past the root mask, f1 > 64 */
+#define GIGL_ROUTE_WHY_PARTS 2    /* more than 16 partitions per batch */
+#define GIGL_ROUTE_WHY_FEW_WGS 3  /* fewer dedup workgroups than GIGL_LG3_MIN_WGS (default 32) */
+#define GIGL_ROUTE_WHY_LDS 4      /* the workgroup's LDS past 150 KB */
+#define GIGL_ROUTE_WHY_ENV 5      /* GIGL_UNION_LG2 is set */
+int32_t gigl_union_route(int32_t b, const int32_t* fanouts, int32_t hops, int32_t group_roots, int32_t leaf_global,
+                         int32_t out[GIGL_ROUTE_LEN]);
 int32_t gigl_union_build(gigl_ctx* ctx, const uint32_t* roots, const gigl_tree* tree,
                          gigl_union* out);
 /* Several INDEPENDENT batches in one set of launches: the b = n_groups*group_roots trees are treated as

@@ -2,8 +2,8 @@
 replaces ("LG2", kept behind GIGL_UNION_LG2=1): every output of the plan's union graph — node list, level counts, rows
 (after their sort: ascending, duplicate-free), root_local, edge count — and the plan's root rows must be identical bit
 for bit, on batches that exercise roots that are each other's neighbours (extras), repeated roots, several batches per
-call, hubs, multi-edge graphs and invalid roots.  (LG2 itself is checked against the generic build and the oracle in
-test_gpu_plan.py / test_gpu_groups.py; this file pins that nothing moved when the table went to LDS.)
+call, hubs, multi-edge graphs and invalid roots.  (Both builds are checked against the oracle, on every route the
+dispatch takes, in test_gpu_union_leaf_global.py; this file pins that nothing moved when the table went to LDS.)
 
 Reference semantics kept: /root/reference/python/gigl/src/common/graph_builder/abstract_graph_builder.py:16-24,100-150
 (first-seen numbering per level, edges deduplicated per batch)."""
