@@ -82,6 +82,7 @@ SYMBOLS = [
     "gigl_gcn_plan_create", "gigl_gcn_plan_set_weights", "gigl_gcn_project_features", "gigl_gcn_plan_set_projected_input",
     "gigl_gcn_plan_set_fused_root", "gigl_gcn_plan_fused_root",
     "gigl_nc_eval_metrics",
+    "gigl_uniformity_loss", "gigl_uniformity_loss_backward", "gigl_alignment_loss", "gigl_alignment_loss_backward",
 ]
 
 KERNEL_IDS = {
@@ -368,6 +369,10 @@ def load() -> C.CDLL:
         "gigl_dist_plan_destroy": [vp],
         "gigl_retrieval_loss": [vp, vp, i64, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp, vp],
         "gigl_retrieval_loss_backward": [vp, vp, i64, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp],
+        "gigl_uniformity_loss": [vp, vp, i64, i32, i32, C.c_float, vp, vp, vp, vp],
+        "gigl_uniformity_loss_backward": [vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, i64],
+        "gigl_alignment_loss": [vp, vp, i64, vp, i64, i32, i32, C.c_float, vp, vp],
+        "gigl_alignment_loss_backward": [vp, vp, i64, vp, i64, i32, i32, C.c_float, vp, vp, vp, vp],
         "gigl_gather_mean_backward": [vp, vp, i32, vp, vp, vp, vp, i64, vp],
         "gigl_gather_mean_backward_transposed": [vp, vp, i32, vp, vp, vp, vp, i64, vp, i64, i64, i32, vp],
         "gigl_transposed_rows_build": [vp, vp, vp, vp, vp, i64, vp, i64, i64, vp],

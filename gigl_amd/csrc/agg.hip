@@ -46,10 +46,9 @@ __host__ __device__ static inline float hs_pow2_scale(float m) {
   return s;
 }
 
-namespace {
+#include "split_planes.h"  // float4_t, float16_t, bf16x8_t, split3, split_lds_off, split_store
 
-typedef float float4_t __attribute__((ext_vector_type(4)));
-typedef float float16_t __attribute__((ext_vector_type(16)));
+namespace {
 
 template <typename T>
 struct RowLoader;
@@ -801,20 +800,7 @@ __global__ __launch_bounds__(256) void linear_weight_grad_reduce_kernel(const fl
 // two rows of a write group overlapped in banks 0-3, one extra LDS cycle per group — SQ_LDS_BANK_CONFLICT was a third
 // of the LDS cycles, exactly the writes' share — and the tile pair took 61 KB; 49 KB now: three workgroups per CU.)
 // Workgroup tile 128 x 64*NJ, four waves as 2 x 2, each 64 rows x 32*NJ columns.
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split3(float x, uint32_t& b1, uint32_t& b2, uint32_t& b3) {
-  b1 = __float_as_uint(x) & 0xFFFF0000u;
-  const float r1 = x - __uint_as_float(b1);
-  b2 = __float_as_uint(r1) & 0xFFFF0000u;
-  const float r2 = r1 - __uint_as_float(b2);
-  b3 = __float_as_uint(r2) & 0xFFFF0000u;
-}
-
-// offset (in bf16 elements) of element k (0..31) of tile row `row` in a swizzled plane
-__device__ __forceinline__ int split_lds_off(int row, int k) {
-  return row * 32 + ((((k >> 3) ^ (row >> 2)) & 3) << 3) + (k & 7);
-}
+// (split3, split_lds_off and split_store live in split_planes.h: pairwise.hip uses them too)
 
 // Weight gradient on the matrix cores: dW[n][k] = sum_r dy[r][n] * a[r][k] is a product whose INNER dimension is the row
 // index, so both operands enter transposed.  A thread stages eight consecutive ROWS of one column (eight dword loads,
@@ -907,16 +893,6 @@ __global__ __launch_bounds__(256) void linear_weight_grad_mfma_kernel(const floa
     if (tid < 64 && n0 + tid < N)
       partb[(int64_t)blockIdx.x * N + n0 + tid] = (s_cs[0][tid] + s_cs[1][tid]) + (s_cs[2][tid] + s_cs[3][tid]);
   }
-}
-
-// four consecutive k of one row -> four bf16 of each plane, stored as 8 bytes per plane
-__device__ __forceinline__ void split_store(const float4_t v, short* p1, short* p2, short* p3) {
-  uint32_t a1[4], a2[4], a3[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) split3(v[t], a1[t], a2[t], a3[t]);
-  *reinterpret_cast<uint2*>(p1) = make_uint2((a1[0] >> 16) | a1[1], (a1[2] >> 16) | a1[3]);
-  *reinterpret_cast<uint2*>(p2) = make_uint2((a2[0] >> 16) | a2[1], (a2[2] >> 16) | a2[3]);
-  *reinterpret_cast<uint2*>(p3) = make_uint2((a3[0] >> 16) | a3[1], (a3[2] >> 16) | a3[3]);
 }
 
 // (values with at most 16 significant bits — widened halves: the third plane would be zero)

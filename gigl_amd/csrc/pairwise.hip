@@ -1,0 +1,567 @@
+// pairwise.hip — the DirectAU losses over embedding rows (python/gigl/src/common/models/layers/loss.py:591-626): the pairwise
+// uniformity loss and its gradient as two Gram-shaped MFMA kernels that write nothing of size n x n, and the alignment loss.
+//
+// Uniformity.  X fp32 [n][d], t the temperature:
+//     w_ij = exp(-t max(0, |x_i - x_j|^2)),  S = sum_{i<j} w_ij,  U = log(2 S / (n (n - 1)))
+//     dU/dx_i = (-2 t / S) (r_i x_i - sum_{j != i} w_ij x_j),  r_i = sum_{j != i} w_ij
+// The reference is pdist -> pow -> mul -> exp -> mean -> log: n (n - 1) / 2 distances in HBM, forward and again in backward.
+//   prep      Xc = X - column mean (distances are translation invariant; two launches, fixed order), sq_i = |xc_i|^2.  The
+//             centring keeps sq_i + sq_j - 2 g_ij and r_i x_i - sum w x_j free of cancellation when the rows have collapsed
+//             towards one point; sum_i dU/dxc_i = 0, so the gradient with respect to Xc IS the gradient with respect to X.
+//   forward   one workgroup per pair of 64-row tiles I <= J.  gram_tile: the two panels pass through LDS in K chunks of 32,
+//             split on the way in into three bf16 planes (split_planes.h: x = b1 + b2 + b3 exactly), six
+//             v_mfma_f32_32x32x16_bf16 per 16 k carry the product at fp32 accuracy; four waves as 2 x 2, a 32 x 32 block of G
+//             each, two accumulators so that dependent MFMAs alternate.  Epilogue in registers: w masked to i < j < n, lane ->
+//             wave -> workgroup sum, one double per tile pair; pair_fold_kernel adds the partials in a fixed order in fp64.
+//   backward  one workgroup per row tile I and 128-column chunk of d, sweeping EVERY column tile J (no atomics: a row's sums
+//             have one owner and one order).  The first product is taken TRANSPOSED (rows j, columns i): in the 32x32 D
+//             layout a lane then holds one i and sixteen j — which is, up to a fixed permutation of k, the A-operand layout
+//             of the second product acc[i][c] += W[i][j] Xc[j][c].  W never leaves the registers: it is split into its
+//             three planes where it lies, and the permutation (bits 2 and 3 of k swapped, pair_kperm) is applied to the
+//             OTHER operand, which has to be staged anyway: Xc_J enters LDS transposed ([column][32 j], a thread carrying
+//             eight j of one column, as the weight-gradient kernel stages its operands), 64 columns at a time.  A wave owns
+//             one 32-row block of i and one 32-row half of j: per 32 columns an exact accumulator for the one large term
+//             and one for the rest (fixed-point planes, see pair_fix3), 8 accumulators of 32 x 32 for 128 columns; the two
+//             halves of j meet in the epilogue through LDS, in a fixed order, with the plane sums of w that rebuild r_i x_i.
+//
+// Alignment.  mean_i |u_i - p_i|^alpha: one wave per row, a fixed-order fold; backward alpha |.|^(alpha - 2) (u - p) / n,
+// zero where u_i == p_i (torch's subgradient of norm).
+#include "common.h"
+#include "split_planes.h"
+
+#include <cmath>
+#include <cstdint>
+
+namespace {
+
+constexpr int PT = 64;            // rows per tile
+constexpr int PBK = 32;           // k per LDS chunk
+constexpr int PPLANE = PT * PBK;  // bf16 elements of one plane of one panel
+constexpr int PCH = 128;          // columns of d per backward workgroup (two accumulators per 32: 256 spills)
+constexpr int PMAXD = 512;
+
+// ---- prep -------------------------------------------------------------------------------------------------------------
+// part[chunk][c] = sum of column c over rows [256 chunk, +256): lane = column, the four waves take rows 4 apart and meet in
+// a fixed order
+__global__ __launch_bounds__(256) void pair_colsum_kernel(const float* __restrict__ x, int64_t ld, int n, int d,
+                                                          float* __restrict__ part) {
+  __shared__ float s_p[4][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + lane, r0 = blockIdx.y * 256;
+  float acc = 0.f;
+  if (c < d)
+    for (int r = r0 + wv; r < min(n, r0 + 256); r += 4) acc += x[(int64_t)r * ld + c];
+  s_p[wv][lane] = acc;
+  __syncthreads();
+  if (wv == 0 && c < d) part[(int64_t)blockIdx.y * d + c] = (s_p[0][lane] + s_p[1][lane]) + (s_p[2][lane] + s_p[3][lane]);
+}
+
+// xc = x - mean, sq = |xc|^2 for 64 rows per workgroup (a wave takes 16 of them); the mean is folded from the chunk sums in
+// chunk order by every workgroup.  V4: d, ld multiples of 4 and 16-byte aligned bases -> 16-byte loads and stores
+template <bool V4>
+__global__ __launch_bounds__(256) void pair_centre_kernel(const float* __restrict__ x, int64_t ld, int n, int d,
+                                                          const float* __restrict__ part, int chunks,
+                                                          float* __restrict__ xc, float* __restrict__ sq) {
+  __shared__ __attribute__((aligned(16))) float s_mean[PMAXD];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const float inv_n = 1.f / (float)n;
+  for (int c = tid; c < d; c += 256) {
+    float s = 0.f;
+    for (int k = 0; k < chunks; ++k) s += part[(int64_t)k * d + c];
+    s_mean[c] = s * inv_n;
+  }
+  __syncthreads();
+  for (int q = 0; q < 16; ++q) {
+    const int row = blockIdx.x * 64 + wv * 16 + q;
+    if (row >= n) break;  // (the whole wave)
+    const float* src = x + (int64_t)row * ld;
+    float* dst = xc + (int64_t)row * d;
+    float acc = 0.f;
+    if constexpr (V4) {
+      for (int c = lane * 4; c < d; c += 256) {
+        float4 v = *reinterpret_cast<const float4*>(src + c);
+        const float4 m = *reinterpret_cast<const float4*>(&s_mean[c]);
+        v.x -= m.x;
+        v.y -= m.y;
+        v.z -= m.z;
+        v.w -= m.w;
+        *reinterpret_cast<float4*>(dst + c) = v;
+        acc += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+      }
+    } else {
+      for (int c = lane; c < d; c += 64) {
+        const float v = src[c] - s_mean[c];
+        dst[c] = v;
+        acc += v * v;
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane == 0) sq[row] = acc;
+  }
+}
+
+// ---- the Gram tile ------------------------------------------------------------------------------------------------------
+template <bool VEC>  // VEC: d % 4 == 0 and xc 16-byte aligned
+__device__ __forceinline__ float4_t pair_load4(const float* __restrict__ xc, int n, int d, int row, int k) {
+  float4_t v = {0.f, 0.f, 0.f, 0.f};
+  if (row < n) {
+    const float* p = xc + (int64_t)row * d + k;
+    if constexpr (VEC) {
+      if (k < d) v = *reinterpret_cast<const float4_t*>(p);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        if (k + t < d) v[t] = p[t];
+    }
+  }
+  return v;
+}
+
+// D[a][b] = <xc[a0 + a], xc[b0 + b]> over the 64 x 64 tile, by all 256 threads: wave wv holds the 32 x 32 block (wv >> 1, wv & 1)
+// in the D layout (register v of lane (r, g): row 8 (v / 4) + 4 g + v % 4, column r).  Rows >= n and k >= d enter as zeros.
+// s: six planes (three of each panel).  Starts with a barrier: the caller's earlier reads of s are done before it is refilled.
+template <bool VEC>
+__device__ __forceinline__ float16_t gram_tile(const float* __restrict__ xc, int n, int d, int a0, int b0,
+                                               short (*s)[PPLANE]) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 31, g = lane >> 5;
+  const int wa = wv >> 1, wb = wv & 1;
+  const int lr = tid >> 3, lc = (tid & 7) * 4;  // loader: rows lr, lr + 32; k segment lc .. lc + 3
+  float16_t acc0, acc1;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) acc0[v] = acc1[v] = 0.f;
+  float4_t ra[2], rb[2];
+  auto gload = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      ra[i] = pair_load4<VEC>(xc, n, d, a0 + lr + 32 * i, k0 + lc);
+      rb[i] = pair_load4<VEC>(xc, n, d, b0 + lr + 32 * i, k0 + lc);
+    }
+  };
+  gload(0);
+  for (int k0 = 0; k0 < d; k0 += PBK) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int o = split_lds_off(lr + 32 * i, lc);
+      split_store(ra[i], &s[0][o], &s[1][o], &s[2][o]);
+      split_store(rb[i], &s[3][o], &s[4][o], &s[5][o]);
+    }
+    __syncthreads();
+    if (k0 + PBK < d) gload(k0 + PBK);  // lands during this chunk's MFMAs
+    bf16x8_t fa0[3], fb0[3], fa1[3], fb1[3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      fa0[p] = *reinterpret_cast<const bf16x8_t*>(&s[p][split_lds_off(wa * 32 + r, 8 * g)]);
+      fb0[p] = *reinterpret_cast<const bf16x8_t*>(&s[3 + p][split_lds_off(wb * 32 + r, 8 * g)]);
+      fa1[p] = *reinterpret_cast<const bf16x8_t*>(&s[p][split_lds_off(wa * 32 + r, 16 + 8 * g)]);
+      fb1[p] = *reinterpret_cast<const bf16x8_t*>(&s[3 + p][split_lds_off(wb * 32 + r, 16 + 8 * g)]);
+    }
+    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // smallest terms first
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa0[PA[t]], fb0[PB[t]], acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa1[PA[t]], fb1[PB[t]], acc1, 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < 16; ++v) acc0[v] += acc1[v];
+  return acc0;
+}
+
+// ---- forward ------------------------------------------------------------------------------------------------------------
+// part[p] = sum of w_ij over the entries i < j < n of tile pair p = J (J + 1) / 2 + I, I <= J
+template <bool VEC>
+__global__ __launch_bounds__(256) void pair_sum_kernel(const float* __restrict__ xc, const float* __restrict__ sq, int n,
+                                                       int d, float t, double* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) short s[6][PPLANE];
+  __shared__ double s_w[4];
+  const int64_t p = blockIdx.x;
+  int64_t J = (int64_t)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
+  while (J * (J + 1) / 2 > p) --J;
+  while ((J + 1) * (J + 2) / 2 <= p) ++J;
+  const int I = (int)(p - J * (J + 1) / 2);
+  const float16_t acc = gram_tile<VEC>(xc, n, d, I * PT, (int)J * PT, s);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, g = lane >> 5;
+  const int j = (int)J * PT + (wv & 1) * 32 + r;
+  const float sqj = j < n ? sq[j] : 0.f;
+  float sum = 0.f;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int i = I * PT + (wv >> 1) * 32 + 8 * (v >> 2) + 4 * g + (v & 3);
+    if (i < j && j < n) sum += expf(-t * fmaxf(0.f, (sq[i] + sqj) - 2.f * acc[v]));
+  }
+  double ds = (double)sum;
+  for (int off = 32; off > 0; off >>= 1) ds += __shfl_xor(ds, off, 64);
+  if (lane == 0) s_w[wv] = ds;
+  __syncthreads();
+  if (threadIdx.x == 0) part[p] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+}
+
+// S = the partials added in a fixed order (one workgroup, fp64), U = log(2 S / (n (n - 1))): NaN for n < 2 (0 / 0), as the
+// reference's mean over an empty pdist
+__global__ __launch_bounds__(1024) void pair_fold_kernel(const double* __restrict__ part, int64_t np, int n,
+                                                         double* __restrict__ pair_sum, float* __restrict__ loss) {
+  __shared__ double s_w[16];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  double acc = 0.0;
+  for (int64_t i = tid; i < np; i += 1024) acc += part[i];
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if (lane == 0) s_w[w] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double S = 0.0;
+    for (int k = 0; k < 16; ++k) S += s_w[k];
+    *pair_sum = S;
+    *loss = (float)log(2.0 * S / ((double)n * (double)(n - 1)));
+  }
+}
+
+// ---- backward -----------------------------------------------------------------------------------------------------------
+// position kpos of the second product's k order -> row j of the 32-row half: register v = 8 s + t of the first product's D
+// layout holds row 16 s + 8 (t / 4) + 4 g + t % 4, and an operand lane (., g) supplies k = 16 s + 8 g + t
+__device__ __forceinline__ int pair_kperm(int kpos) {
+  return (kpos & 0x13) | ((kpos & 4) << 1) | ((kpos & 8) >> 1);
+}
+
+// The second product's operands are split in FIXED point, not by split3.  r_i x_i - sum_j w_ij x_j cancels: among (near)
+// duplicates w ~ 1 and both terms are ~ their count, while the gradient may be the far rows' e^-8 of that — fp32 accumulators
+// that mix the two round the answer away.  So x / q = t1 + t2 / 2^8 + t3 / 2^16 (+ a remainder < 2^-16) with INTEGERS t1 in
+// [-128, 128], t2, t3 in [0, 255] and q = scale / 128 (scale: a power of two >= every |xc|), and w = u1 + rem with u1 = floor(256
+// w) / 256.  Every plane is exact in bf16.  The products u1 t1 are integers / 256 below 2^15: their sum — the one LARGE term —
+// has its own accumulator and is EXACT (up to 2^24 / 2^15 / ... = 256 rows of weight 1 per wave and half; beyond, fp32
+// rounding of that term alone), the same integers cancel exactly against R1 t1_i, R1 = sum_j u1_ij.  Everything else (u1 t2, u1
+// t3, and rem — as its two leading bf16 planes f2, f3 — against t1, t2) is 2^-8 of that size or carries the small weights, and
+// shares a second accumulator.  Dropped: products below 2^-16 of a term — and the epilogue rebuilds r_i x_i from the SAME
+// products (the plane sums of w times the planes of x_i), so what is dropped is dropped from the difference x_i - x_j, never
+// from one side of it (a weight 1 - 2^-22 between duplicates puts 1 / 256 of the large term into rem: measured, that alone
+// was 1.8e-4 of the gradient when r_i x_i kept all of rem).  Rows far below the scale lose RELATIVE precision
+// (the planes are absolute): the error is 2^-23 scale per unit of weight, the gradient's own size for rows of comparable norm.
+__device__ __forceinline__ void pair_fix3(float x, float inv_q, float& t1, float& t2, float& t3) {
+  const float y = x * inv_q;  // (a power of two: exact)
+  t1 = floorf(y);
+  const float r1 = (y - t1) * 256.f;  // in [0, 256), exact
+  t2 = floorf(r1);
+  t3 = floorf((r1 - t2) * 256.f);
+}
+// the planes as the MFMA reads them, in units of q: t1, t2 / 2^8, t3 / 2^16 (bf16 = the float's upper half: <= 9 bits each)
+__device__ __forceinline__ void pair_fix3_bits(float x, float inv_q, uint32_t& b1, uint32_t& b2, uint32_t& b3) {
+  float t1, t2, t3;
+  pair_fix3(x, inv_q, t1, t2, t3);
+  b1 = __float_as_uint(t1) & 0xFFFF0000u;
+  b2 = __float_as_uint(t2 * (1.f / 256.f)) & 0xFFFF0000u;
+  b3 = __float_as_uint(t3 * (1.f / 65536.f)) & 0xFFFF0000u;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void pair_backward_kernel(const float* __restrict__ xc, const float* __restrict__ sq, int n,
+                                                            int d, float t, const double* __restrict__ pair_sum,
+                                                            const float* __restrict__ gout, float* __restrict__ dx,
+                                                            int64_t ld_dx) {
+  __shared__ __attribute__((aligned(16))) short s[6][PPLANE];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 31, g = lane >> 5;
+  const int wj = wv >> 1, wi = wv & 1;  // this wave: rows j of half wj (the first product's rows), i block wi (its columns)
+  const int I0 = blockIdx.x * PT, c0 = blockIdx.y * PCH;
+  const int i_lane = I0 + wi * 32 + r;
+  const float sqi = i_lane < n ? sq[i_lane] : 0.f;
+  // scale = the power of two above the largest row norm (every workgroup folds the n norms: a few KB from L2)
+  __shared__ float s_mx[4];
+  {
+    float mx = 0.f;
+    for (int k = tid; k < n; k += 256) mx = fmaxf(mx, sq[k]);
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    if (lane == 0) s_mx[wv] = mx;
+    __syncthreads();
+  }
+  int sc_e = 0;
+  frexpf(sqrtf(fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]))) * 1.0001f, &sc_e);  // norm < 2^sc_e
+  const float inv_q = ldexpf(128.f, -sc_e);  // (all rows zero: sc_e = 0)
+  float16_t acc2[PCH / 32][2];  // [.][0]: sum u1 t1, exact; [.][1]: the rest
+#pragma unroll
+  for (int b = 0; b < PCH / 32; ++b)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc2[b][0][v] = acc2[b][1][v] = 0.f;
+  double r_u1 = 0.0, r_f2 = 0.0, r_f3 = 0.0;  // sum_j of each plane of w_ij AS THE PRODUCT TAKES IT: r_i x_i is rebuilt from them
+  const int tiles = (n + PT - 1) / PT;
+  for (int J = 0; J < tiles; ++J) {
+    const int J0 = J * PT;
+    const float16_t gt = gram_tile<VEC>(xc, n, d, J0, I0, s);  // [j][i]
+    // W where it lies, split into the second product's A fragments: fa[s2][plane], k = 16 s2 + 8 g + t <-> register 8 s2 + t
+    bf16x8_t fa[2][3];
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      uint32_t b1[8], b2[8], b3[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int v = 8 * s2 + u;
+        const int j = J0 + wj * 32 + 8 * (v >> 2) + 4 * g + (v & 3);
+        float w = 0.f;
+        if (j < n && i_lane < n && j != i_lane) w = expf(-t * fmaxf(0.f, (sqi + sq[j]) - 2.f * gt[v]));
+        const float u1 = floorf(w * 256.f) * (1.f / 256.f), rem = w - u1;  // (both exact)
+        r_u1 += (double)u1;
+        uint32_t unused;
+        b1[u] = __float_as_uint(u1) & 0xFFFF0000u;  // (<= 9 significant bits: nothing is cut)
+        split3(rem, b2[u], b3[u], unused);
+        r_f2 += (double)__uint_as_float(b2[u]);
+        r_f3 += (double)__uint_as_float(b3[u]);
+      }
+      const uint4 q1 = make_uint4((b1[0] >> 16) | b1[1], (b1[2] >> 16) | b1[3], (b1[4] >> 16) | b1[5], (b1[6] >> 16) | b1[7]);
+      const uint4 q2 = make_uint4((b2[0] >> 16) | b2[1], (b2[2] >> 16) | b2[3], (b2[4] >> 16) | b2[5], (b2[6] >> 16) | b2[7]);
+      const uint4 q3 = make_uint4((b3[0] >> 16) | b3[1], (b3[2] >> 16) | b3[3], (b3[4] >> 16) | b3[5], (b3[6] >> 16) | b3[7]);
+      fa[s2][0] = __builtin_bit_cast(bf16x8_t, q1);
+      fa[s2][1] = __builtin_bit_cast(bf16x8_t, q2);
+      fa[s2][2] = __builtin_bit_cast(bf16x8_t, q3);
+    }
+    // acc2[i][c] += W[i][j] Xc[j][c], 64 columns at a time: planes p + 3 h hold half h of j as [column][32 kpos]
+#pragma unroll
+    for (int sub = 0; sub < PCH / 64; ++sub) {
+      const int cs = c0 + 64 * sub;
+      if (cs < d) {  // (the whole workgroup)
+        __syncthreads();  // the fragments of the Gram tile / of the previous 64 columns have been read
+        const int col = cs + lane, h = wv >> 1;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int kb = (2 * (wv & 1) + q) * 8;  // this thread: kpos kb .. kb + 7 of column `col`, half h
+          uint32_t b1[8], b2[8], b3[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            const int j = J0 + 32 * h + pair_kperm(kb + u);
+            const float x = (j < n && col < d) ? xc[(int64_t)j * d + col] : 0.f;
+            pair_fix3_bits(x, inv_q, b1[u], b2[u], b3[u]);
+          }
+          const int o = split_lds_off(lane, kb);
+          *reinterpret_cast<uint4*>(&s[3 * h + 0][o]) = make_uint4((b1[0] >> 16) | b1[1], (b1[2] >> 16) | b1[3], (b1[4] >> 16) | b1[5], (b1[6] >> 16) | b1[7]);
+          *reinterpret_cast<uint4*>(&s[3 * h + 1][o]) = make_uint4((b2[0] >> 16) | b2[1], (b2[2] >> 16) | b2[3], (b2[4] >> 16) | b2[5], (b2[6] >> 16) | b2[7]);
+          *reinterpret_cast<uint4*>(&s[3 * h + 2][o]) = make_uint4((b3[0] >> 16) | b3[1], (b3[2] >> 16) | b3[3], (b3[4] >> 16) | b3[5], (b3[6] >> 16) | b3[7]);
+        }
+        __syncthreads();
+        // (w plane, x plane): u1 t1 alone into [0]; rem's planes against t1, t2 and u1 against t2, t3 into [1], smallest first
+        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0}, PC[6] = {1, 1, 1, 1, 1, 0};
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          bf16x8_t fb[2][3];
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+              fb[cb][p] = *reinterpret_cast<const bf16x8_t*>(&s[3 * wj + p][split_lds_off(cb * 32 + r, 16 * s2 + 8 * g)]);
+#pragma unroll
+          for (int u = 0; u < 6; ++u)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb)
+              acc2[2 * sub + cb][PC[u]] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s2][PA[u]], fb[cb][PB[u]],
+                                                                                  acc2[2 * sub + cb][PC[u]], 0, 0, 0);
+        }
+      }
+    }
+  }
+  // epilogue: the two halves of j meet — r_i and, 32 columns at a time, the accumulators — then dx = coef (r_i xc_i - acc_i)
+  r_u1 += __shfl_xor(r_u1, 32, 64);
+  r_f2 += __shfl_xor(r_f2, 32, 64);
+  r_f3 += __shfl_xor(r_f3, 32, 64);
+  __syncthreads();
+  double* s_r = reinterpret_cast<double*>(&s[0][0]);                   // [2 halves][u1 | f2 | f3][64 rows]
+  float* strip = reinterpret_cast<float*>(s_r + 384) + wi * 2048;  // [2 accumulators][32 rows][32 columns] per i block
+  if (g == 0) {
+    s_r[wj * 192 + wi * 32 + r] = r_u1;
+    s_r[wj * 192 + 64 + wi * 32 + r] = r_f2;
+    s_r[wj * 192 + 128 + wi * 32 + r] = r_f3;
+  }
+  // (in units of q = 1 / inv_q, put back with the coefficient)
+  const double coef = (double)(gout ? *gout : 1.f) * (-2.0 * (double)t / *pair_sum) / (double)inv_q;
+#pragma unroll
+  for (int b = 0; b < PCH / 32; ++b) {
+    if (c0 + 32 * b < d) {  // (the whole workgroup)
+      if (wj == 1) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          strip[(8 * (v >> 2) + 4 * g + (v & 3)) * 32 + r] = acc2[b][0][v];
+          strip[1024 + (8 * (v >> 2) + 4 * g + (v & 3)) * 32 + r] = acc2[b][1][v];
+        }
+      }
+      __syncthreads();  // (the first one also publishes s_r)
+      if (wj == 0) {
+        const int c = c0 + 32 * b + r;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          const int il = 8 * (v >> 2) + 4 * g + (v & 3), i = I0 + wi * 32 + il;
+          if (i < n && c < d) {
+            // r_i x_i rebuilt from the SAME plane products the accumulators hold (so that equal rows cancel exactly and what
+            // the products drop is dropped from a difference): the large term R1 t1 against its exact accumulator, the rest
+            // against the other one; each half of j on its own, in fp64, before the halves are added
+            float t1, t2, t3;
+            pair_fix3(xc[(int64_t)i * d + c], inv_q, t1, t2, t3);
+            const double x1 = (double)t1, x2 = (double)t2 * (1.0 / 256.0), x3 = (double)t3 * (1.0 / 65536.0);
+            const double* rr = s_r + wi * 32 + il;
+            const double h0 = (rr[0] * x1 - (double)acc2[b][0][v]) +
+                              ((rr[0] * (x2 + x3) + rr[64] * (x1 + x2) + rr[128] * x1) - (double)acc2[b][1][v]);
+            const double h1 = (rr[192] * x1 - (double)strip[il * 32 + r]) +
+                              ((rr[192] * (x2 + x3) + rr[256] * (x1 + x2) + rr[320] * x1) - (double)strip[1024 + il * 32 + r]);
+            dx[(int64_t)i * ld_dx + c] = (float)(coef * (h0 + h1));
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void pair_zero_rows_kernel(float* __restrict__ dx, int64_t ld, int n, int d) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < (int64_t)n * d) dx[(i / d) * ld + i % d] = 0.f;
+}
+
+// ---- alignment ----------------------------------------------------------------------------------------------------------
+// norm[i] = |u_i - p_i|, one wave per row
+__global__ __launch_bounds__(256) void align_rows_kernel(const float* __restrict__ u, int64_t ld_u, const float* __restrict__ p,
+                                                         int64_t ld_p, int n, int d, float* __restrict__ norm) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const float *ur = u + (int64_t)i * ld_u, *pr = p + (int64_t)i * ld_p;
+  float acc = 0.f;
+  for (int c = lane; c < d; c += 64) {
+    const float v = ur[c] - pr[c];
+    acc += v * v;
+  }
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if (lane == 0) norm[i] = sqrtf(acc);
+}
+
+// *loss = mean_i norm[i]^alpha in a fixed order (one workgroup, fp64); NaN for n == 0
+__global__ __launch_bounds__(1024) void align_fold_kernel(const float* __restrict__ norm, int n, float alpha,
+                                                          float* __restrict__ loss) {
+  __shared__ double s_w[16];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  double acc = 0.0;
+  for (int i = tid; i < n; i += 1024) {
+    const double v = (double)norm[i];
+    acc += alpha == 2.f ? v * v : pow(v, (double)alpha);
+  }
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if (lane == 0) s_w[w] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double t = 0.0;
+    for (int k = 0; k < 16; ++k) t += s_w[k];
+    *loss = (float)(t / (double)n);
+  }
+}
+
+// du_i = gout alpha norm_i^(alpha - 2) (u_i - p_i) / n, dp_i = -du_i ([n][d] contiguous); zero rows where norm_i == 0
+__global__ __launch_bounds__(256) void align_backward_kernel(const float* __restrict__ u, int64_t ld_u,
+                                                             const float* __restrict__ p, int64_t ld_p, int n, int d,
+                                                             float alpha, const float* __restrict__ norm,
+                                                             const float* __restrict__ gout, float* __restrict__ du,
+                                                             float* __restrict__ dp) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const float nv = norm[i];
+  float k = 0.f;
+  if (nv > 0.f) k = (gout ? *gout : 1.f) * alpha * (alpha == 2.f ? 1.f : powf(nv, alpha - 2.f)) / (float)n;
+  const float *ur = u + (int64_t)i * ld_u, *pr = p + (int64_t)i * ld_p;
+  for (int c = lane; c < d; c += 64) {
+    const float v = k * (ur[c] - pr[c]);
+    du[(int64_t)i * d + c] = v;
+    dp[(int64_t)i * d + c] = -v;
+  }
+}
+
+constexpr int32_t PAIR_MAX_N = 1 << 18;  // 4096 row tiles: 8.4 M tile pairs, 67 MB of partials
+
+int32_t pair_check(gigl_ctx* ctx, int32_t n, int32_t d) {
+  GIGL_REQUIRE(ctx, d >= 1 && d <= PMAXD, "the pairwise kernels serve 1 <= d <= %d (d=%d)", PMAXD, d);
+  GIGL_REQUIRE(ctx, n >= 0 && n <= PAIR_MAX_N, "n=%d outside [0, %d]", n, PAIR_MAX_N);
+  return GIGL_OK;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int32_t gigl_uniformity_loss(gigl_ctx* ctx, const float* x, int64_t ld, int32_t n, int32_t d, float temperature,
+                             float* xc_out, float* sq_out, double* pair_sum_out, float* loss_out) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  const int32_t rc0 = pair_check(ctx, n, d);
+  if (rc0 != GIGL_OK) return rc0;
+  GIGL_REQUIRE(ctx, pair_sum_out && loss_out && (n == 0 || (x && xc_out && sq_out && ld >= d)), "null argument or ld < d");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int64_t tiles = (n + PT - 1) / PT, pairs = n >= 2 ? tiles * (tiles + 1) / 2 : 0;
+  const int chunks = (n + 255) / 256;
+  const int64_t part_bytes = gigl_align_up(pairs * 8, 256), cs_bytes = gigl_align_up((int64_t)chunks * d * 4, 256);
+  const int32_t rc = gigl_arena_reset(ctx, part_bytes + cs_bytes + 1024);
+  if (rc != GIGL_OK) return rc;
+  double* part = (double*)gigl_arena_alloc(ctx, part_bytes + 256);
+  float* colsum = (float*)gigl_arena_alloc(ctx, cs_bytes + 256);
+  GIGL_REQUIRE(ctx, part && colsum, "scratch arena exhausted");
+  hipStream_t st = ctx->stream;
+  if (n >= 2) {
+    hipLaunchKernelGGL(pair_colsum_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)chunks), dim3(256), 0, st, x, ld, n, d, colsum);
+    const bool v4 = d % 4 == 0 && ld % 4 == 0 && aligned16(x) && aligned16(xc_out);
+    if (v4)
+      hipLaunchKernelGGL(pair_centre_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, st, x, ld, n, d, (const float*)colsum, chunks, xc_out, sq_out);
+    else
+      hipLaunchKernelGGL(pair_centre_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, st, x, ld, n, d, (const float*)colsum, chunks, xc_out, sq_out);
+    if (d % 4 == 0 && aligned16(xc_out))
+      hipLaunchKernelGGL(pair_sum_kernel<true>, dim3((unsigned)pairs), dim3(256), 0, st, (const float*)xc_out, (const float*)sq_out, n, d, temperature, part);
+    else
+      hipLaunchKernelGGL(pair_sum_kernel<false>, dim3((unsigned)pairs), dim3(256), 0, st, (const float*)xc_out, (const float*)sq_out, n, d, temperature, part);
+  }
+  hipLaunchKernelGGL(pair_fold_kernel, dim3(1), dim3(1024), 0, st, (const double*)part, pairs, n, pair_sum_out, loss_out);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+int32_t gigl_uniformity_loss_backward(gigl_ctx* ctx, const float* xc, const float* sq, int32_t n, int32_t d, float temperature,
+                                      const double* pair_sum, const float* gout_dev, float* dx, int64_t ld_dx) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  const int32_t rc0 = pair_check(ctx, n, d);
+  if (rc0 != GIGL_OK) return rc0;
+  GIGL_REQUIRE(ctx, n == 0 || (dx && ld_dx >= d && (n < 2 || (xc && sq && pair_sum))), "null argument or ld_dx < d");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (n == 0) return GIGL_OK;
+  if (n < 2) {
+    hipLaunchKernelGGL(pair_zero_rows_kernel, dim3((unsigned)(((int64_t)n * d + 255) / 256)), dim3(256), 0, st, dx, ld_dx, n, d);
+  } else {
+    const dim3 grid((unsigned)((n + PT - 1) / PT), (unsigned)((d + PCH - 1) / PCH));
+    if (d % 4 == 0 && aligned16(xc))
+      hipLaunchKernelGGL(pair_backward_kernel<true>, grid, dim3(256), 0, st, xc, sq, n, d, temperature, pair_sum, gout_dev, dx, ld_dx);
+    else
+      hipLaunchKernelGGL(pair_backward_kernel<false>, grid, dim3(256), 0, st, xc, sq, n, d, temperature, pair_sum, gout_dev, dx, ld_dx);
+  }
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+int32_t gigl_alignment_loss(gigl_ctx* ctx, const float* u, int64_t ld_u, const float* p, int64_t ld_p, int32_t n, int32_t d,
+                            float alpha, float* norm_out, float* loss_out) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  const int32_t rc0 = pair_check(ctx, n, d);
+  if (rc0 != GIGL_OK) return rc0;
+  GIGL_REQUIRE(ctx, loss_out && (n == 0 || (u && p && norm_out && ld_u >= d && ld_p >= d)), "null argument or a row stride < d");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (n > 0)
+    hipLaunchKernelGGL(align_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, u, ld_u, p, ld_p, n, d, norm_out);
+  hipLaunchKernelGGL(align_fold_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const float*)norm_out, n, alpha, loss_out);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+int32_t gigl_alignment_loss_backward(gigl_ctx* ctx, const float* u, int64_t ld_u, const float* p, int64_t ld_p, int32_t n,
+                                     int32_t d, float alpha, const float* norm, const float* gout_dev, float* du, float* dp) {
+  if (!ctx) return GIGL_E_INVALID_ARG;
+  const int32_t rc0 = pair_check(ctx, n, d);
+  if (rc0 != GIGL_OK) return rc0;
+  GIGL_REQUIRE(ctx, n == 0 || (u && p && norm && du && dp && ld_u >= d && ld_p >= d), "null argument or a row stride < d");
+  GIGL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (n > 0)
+    hipLaunchKernelGGL(align_backward_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, u, ld_u, p, ld_p, n, d, alpha,
+                       norm, gout_dev, du, dp);
+  GIGL_HIP_CHECK(ctx, hipGetLastError());
+  return GIGL_OK;
+}
+
+}  // extern "C"

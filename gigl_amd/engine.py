@@ -1189,6 +1189,57 @@ class HipEngine:
                                                      p(d)), self._ctx)
         return d
 
+    @staticmethod
+    def _embedding_rows(x: torch.Tensor) -> torch.Tensor:
+        """fp32 device rows with unit column stride, as the pairwise entry points read them (a row view keeps its stride)"""
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+        return x if x.stride(1) == 1 and x.stride(0) >= x.shape[1] else x.contiguous()
+
+    def uniformity_loss(self, x: torch.Tensor, temperature: float):
+        """-> (loss [] fp32, xc [n, d] centred rows, sq [n], pair_sum [] fp64): gigl_uniformity_loss"""
+        x = self._embedding_rows(x)
+        n, d = int(x.shape[0]), int(x.shape[1])
+        dev = self.device
+        xc = torch.empty((n, d), dtype=torch.float32, device=dev)
+        sq = torch.empty(n, dtype=torch.float32, device=dev)
+        pair_sum = torch.empty((), dtype=torch.float64, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        check(self._lib.gigl_uniformity_loss(self._ctx, p(x), int(x.stride(0)), n, d, float(temperature), p(xc), p(sq),
+                                             p(pair_sum), p(loss)), self._ctx)
+        return loss, xc, sq, pair_sum
+
+    def uniformity_loss_backward(self, xc, sq, temperature: float, pair_sum, grad_loss) -> torch.Tensor:
+        n, d = int(xc.shape[0]), int(xc.shape[1])
+        dx = torch.empty((n, d), dtype=torch.float32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(self._lib.gigl_uniformity_loss_backward(self._ctx, p(xc), p(sq), n, d, float(temperature), p(pair_sum),
+                                                      p(grad_loss), p(dx), d), self._ctx)
+        return dx
+
+    def alignment_loss(self, u: torch.Tensor, v: torch.Tensor, alpha: float):
+        """-> (loss [] fp32, norm [n]): gigl_alignment_loss"""
+        u, v = self._embedding_rows(u), self._embedding_rows(v)
+        assert u.shape == v.shape
+        n, d = int(u.shape[0]), int(u.shape[1])
+        norm = torch.empty(n, dtype=torch.float32, device=self.device)
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        check(self._lib.gigl_alignment_loss(self._ctx, p(u), int(u.stride(0)), p(v), int(v.stride(0)), n, d, float(alpha),
+                                            p(norm), p(loss)), self._ctx)
+        return loss, norm
+
+    def alignment_loss_backward(self, u, v, alpha: float, norm, grad_loss):
+        """-> (du, dv) [n, d]: gigl_alignment_loss_backward"""
+        u, v = self._embedding_rows(u), self._embedding_rows(v)
+        n, d = int(u.shape[0]), int(u.shape[1])
+        du = torch.empty((n, d), dtype=torch.float32, device=self.device)
+        dv = torch.empty((n, d), dtype=torch.float32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(self._lib.gigl_alignment_loss_backward(self._ctx, p(u), int(u.stride(0)), p(v), int(v.stride(0)), n, d,
+                                                     float(alpha), p(norm), p(grad_loss), p(du), p(dv)), self._ctx)
+        return du, dv
+
     def lp_task_loss(self, task: str, param: float, weight: float, scores: torch.Tensor, b: int, P: int, H: int, n_rn: int,
                      pos_cnt: Optional[torch.Tensor], valid: torch.Tensor, backward: bool = True):
         """the Margin / Softmax task over a score matrix in the training plan's layout (gigl_lp_task_loss and

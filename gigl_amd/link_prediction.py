@@ -8,6 +8,7 @@ Mirror of (paths relative to the reference root):
   LinkPredictionGNN                    python/gigl/src/common/models/pyg/link_prediction.py:33-60
   RetrievalLoss                        python/gigl/src/common/models/layers/loss.py:177-360
       calculate_batch_retrieval_loss :209-277, _mask_by_query_ids :279-305, _mask_by_candidate_ids :307-331
+  AligmentLoss, UniformityLoss         python/gigl/src/common/models/layers/loss.py:591-626  (csrc/pairwise.hip)
 The loss is one fused device pass over the score matrix (csrc/loss.hip: temperature, sampling-probability correction,
 both masks, log-softmax and the summed cross-entropy, plus its backward), pinned by the reference's known-answer tests
 (tests/test_link_prediction.py restates loss_test.py:61-166 and decoder_test.py:44-62).
@@ -233,3 +234,78 @@ class RetrievalLoss(nn.Module):
             return _FusedRetrievalLoss.apply(scores, eng, self._temperature, prob, qid, cid)
         masked = _MaskedLogits.apply(scores, eng, self._temperature, prob, qid, cid)
         return self._loss(masked, target=torch.eye(q, c, device=dev))
+
+
+class _FusedUniformity(torch.autograd.Function):
+    """rows -> log of the mean pairwise Gaussian potential (csrc/pairwise.hip: centring, the Gram tiles on the matrix cores,
+    exp and the reduction in one pass); backward = a second sweep that recomputes the weights, no n x n tensor either way"""
+
+    @staticmethod
+    def forward(ctx, x, eng, temperature):
+        loss, xc, sq, pair_sum = eng.uniformity_loss(x, temperature)
+        ctx.eng, ctx.temperature = eng, temperature
+        ctx.save_for_backward(xc, sq, pair_sum)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, sq, pair_sum = ctx.saved_tensors
+        dx = ctx.eng.uniformity_loss_backward(xc, sq, ctx.temperature, pair_sum, g.to(torch.float32).contiguous())
+        return dx, None, None
+
+
+class _FusedAlignment(torch.autograd.Function):
+    """mean_i |u_i - p_i|^alpha over the rows (csrc/pairwise.hip)"""
+
+    @staticmethod
+    def forward(ctx, u, p, eng, alpha):
+        loss, norm = eng.alignment_loss(u, p, alpha)
+        ctx.eng, ctx.alpha = eng, alpha
+        ctx.save_for_backward(u, p, norm)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        u, p, norm = ctx.saved_tensors
+        du, dp = ctx.eng.alignment_loss_backward(u, p, ctx.alpha, norm, g.to(torch.float32).contiguous())
+        return du, dp, None, None
+
+
+def _device_rows(t: torch.Tensor, who: str) -> torch.Tensor:
+    if not t.is_cuda:
+        raise RuntimeError(f"{who} runs on the HIP device only (got a CPU tensor); no CPU fallback")
+    if t.dim() != 2:
+        raise ValueError(f"{who}: expected [n, d] embeddings, got shape {tuple(t.shape)}")
+    return t.to(torch.float32)
+
+
+class AligmentLoss(nn.Module):
+    """The reference's AligmentLoss (python/gigl/src/common/models/layers/loss.py:591-606; its spelling): the mean of
+    |user_i - item_i|^alpha over the positive pairs, one fused device pass (gigl_alignment_loss).  Device tensors only."""
+
+    def __init__(self, alpha: Optional[float] = 2.0):
+        super().__init__()
+        self.alpha = alpha
+
+    def forward(self, user_embeddings: torch.Tensor, item_embeddings: torch.Tensor) -> torch.Tensor:
+        from .engine import default_engine
+        u, p = _device_rows(user_embeddings, "AligmentLoss"), _device_rows(item_embeddings, "AligmentLoss")
+        if u.shape != p.shape:
+            raise ValueError(f"AligmentLoss: {tuple(u.shape)} user rows against {tuple(p.shape)} item rows")
+        return _FusedAlignment.apply(u, p, default_engine(u.device), float(self.alpha))
+
+
+class UniformityLoss(nn.Module):
+    """The reference's UniformityLoss (loss.py:609-626): (U(user) + U(item)) / 2 with U(x) = log mean_{i<j}
+    exp(-temperature |x_i - x_j|^2), each side one fused MFMA pass (gigl_uniformity_loss) instead of pdist -> pow -> mul ->
+    exp -> mean -> log.  Device tensors only."""
+
+    def __init__(self, temperature: float = 2.0):
+        super().__init__()
+        self.temperature = temperature
+
+    def forward(self, user_embeddings: torch.Tensor, item_embeddings: torch.Tensor) -> torch.Tensor:
+        from .engine import default_engine
+        u, p = _device_rows(user_embeddings, "UniformityLoss"), _device_rows(item_embeddings, "UniformityLoss")
+        eng, t = default_engine(u.device), float(self.temperature)
+        return (_FusedUniformity.apply(u, eng, t) + _FusedUniformity.apply(p, eng, t)) / 2

@@ -16,7 +16,9 @@ retrieval loss over the [queries x candidates] score matrix (gigl_retrieval_loss
 sampling correction when enabled).
 Scope: homogeneous graphs (one condensed node type / edge type) and heterogeneous ones (typed batches through the
 native typed collate, HGT / SimpleHGN encoders, first supervision edge type: spec :245-271, infer.py on HeteroData); the
-Retrieval, Margin and Softmax tasks — the self-supervised ones (GRACE, BGRL, ...) are not built.
+Retrieval, Margin, Softmax and DirectAU tasks (DirectAU through the autograd loop: its losses read the embeddings, not the
+score matrix the training plans' head works on) — the augmentation-based self-supervised ones (GRACE, BGRL, ...) are not
+built.
 Data: main samples are the NodeAnchorBasedLinkPredictionSample TFRecords and random negatives the
 RootedNodeNeighborhood TFRecords the sampler wrote, re-filed into train/val/test by the split generator
 (gigl_amd/split_generator.py; datasetMetadata.nodeAnchorBasedLinkPredictionDataset URIs).  Without split outputs
@@ -40,7 +42,7 @@ from .base import (BaseInferencer, BaseTrainer, EvalMetric, EvalMetricsCollectio
                    hit_rate_at_k, import_obj, mean_reciprocal_rank, no_grad_eval)
 from .batches import NodeAnchorBasedLinkPredictionBatch, RootedNodeNeighborhoodBatch, iterate_tfrecord_batches
 from .config import GbmlConfigPbWrapper, tfrecord_files
-from .link_prediction import LinkPredictionDecoder, LinkPredictionGNN, RetrievalLoss
+from .link_prediction import AligmentLoss, LinkPredictionDecoder, LinkPredictionGNN, RetrievalLoss, UniformityLoss
 from .models import GraphSAGE
 from .task_specs import _dropout_arg, _rank_world
 
@@ -407,6 +409,31 @@ class Softmax(nn.Module):
         return loss, int(M.sum().item())
 
 
+class DirectAU(nn.Module):
+    """task.py:656-696: alignment of every (anchor, positive) pair + gamma x uniformity of the anchors' and the positives'
+    embeddings, per condensed edge type; no negatives, no scores.  Both losses are fused device passes (AligmentLoss /
+    UniformityLoss, csrc/pairwise.hip).  forward -> (loss, 1)."""
+    task_name = "DirectAU"
+    result_types = ("batch_embeddings",)
+
+    def __init__(self, gamma: float = 1.0, alpha: float = 2.0, temperature: float = 2.0):
+        super().__init__()
+        self.alignment_loss = AligmentLoss(alpha=alpha)
+        self.uniformity_loss = UniformityLoss(temperature=temperature)
+        self.gamma = float(gamma)
+
+    def forward(self, task_input: NodeAnchorBasedLinkPredictionTaskInputs, gbml_config_pb_wrapper=None,
+                should_eval: bool = False, device: torch.device = torch.device("cpu")):
+        assert task_input.batch_embeddings is not None
+        emb = task_input.batch_embeddings
+        running_loss = torch.tensor(0.0, device=device)
+        for cet in emb.pos_embeddings:
+            anchors, pos = emb.repeated_query_embeddings[cet], emb.pos_embeddings[cet]
+            running_loss = running_loss + self.alignment_loss(user_embeddings=anchors, item_embeddings=pos)
+            running_loss = running_loss + self.gamma * self.uniformity_loss(user_embeddings=anchors, item_embeddings=pos)
+        return running_loss, 1
+
+
 class NodeAnchorBasedLinkPredictionTasks:
     """task.py:699-758: weighted sum of per-sample task losses"""
 
@@ -517,6 +544,10 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
                    "softmax_temperature": float(kwargs.get("softmax_temp", 0.07)),
                    "remove_accidental_hits": _strtobool(kwargs.get("should_remove_accidental_hits", "True")),
                    "margin": float(kwargs.get("margin", 0.5))}
+        if isinstance(task_cls, type) and issubclass(task_cls, DirectAU):
+            # (DirectAU's `temperature` is the uniformity kernel's width, 2.0 in the paper — never the softmax temperature)
+            offered = {"temperature": float(kwargs.get("directau_temperature", 2.0)),
+                       "gamma": float(kwargs.get("gamma", 1.0)), "alpha": float(kwargs.get("alpha", 2.0))}
         takes = inspect.signature(task_cls.__init__).parameters
         # (the reference passes temperature / remove_accidental_hits to whatever class task_path names — its Margin and
         # Softmax tasks cannot be built that way; here every task gets the arguments its constructor declares)

@@ -1137,6 +1137,31 @@ int32_t gigl_retrieval_loss_backward(gigl_ctx* ctx, const float* scores, int64_t
                                      const int64_t* cand_ids, const float* row_lse, const float* grad_loss,
                                      float* dscores);
 
+/* ---- the DirectAU losses over embedding rows (AligmentLoss / UniformityLoss, python/gigl/src/common/models/layers/
+ *      loss.py:591-626).  All pointers DEVICE; the work is issued on the ctx's stream, tile partials come from the ctx's
+ *      arena, nothing synchronises the host.  1 <= d <= 512 (GIGL_E_INVALID_ARG with a message beyond); results are
+ *      bit-reproducible run to run.
+ * Uniformity loss of the rows x [n][d] (fp32, `ld` floats apart, unit column stride), loss.py:624 (one of the two sides of
+ * :621-626): w_ij = exp(-temperature max(0, |x_i - x_j|^2)), *pair_sum_out = S = sum_{i<j} w_ij (double), *loss_out =
+ * log(2 S / (n (n - 1))) — NaN for n < 2, as the reference's mean over an empty pdist.  Replaces pdist -> pow -> mul -> exp
+ * -> mean -> log: the Gram tiles run on the matrix cores and nothing of size n x n is written.  xc_out [n][d] (contiguous)
+ * receives the rows minus their column mean, sq_out [n] their squared norms: what the backward reads. */
+int32_t gigl_uniformity_loss(gigl_ctx* ctx, const float* x, int64_t ld, int32_t n, int32_t d, float temperature,
+                             float* xc_out, float* sq_out, double* pair_sum_out, float* loss_out);
+/* The gradient of gigl_uniformity_loss (loss.py:591-626: autograd through :624 in the reference): dx[i] = *gout_dev
+ * (-2 temperature / S) (r_i xc_i - sum_{j != i} w_ij xc_j), r_i = sum_{j != i} w_ij, written to rows ld_dx floats apart
+ * (gout_dev NULL: 1).  xc, sq, pair_sum: the forward's outputs.  n < 2: zeros. */
+int32_t gigl_uniformity_loss_backward(gigl_ctx* ctx, const float* xc, const float* sq, int32_t n, int32_t d, float temperature,
+                                      const double* pair_sum, const float* gout_dev, float* dx, int64_t ld_dx);
+/* Alignment loss (loss.py:591-626, AligmentLoss.forward :603-606): norm_out[i] = |u_i - p_i| and *loss_out = mean_i
+ * norm_out[i]^alpha, added in a fixed order (rows ld_u / ld_p floats apart). */
+int32_t gigl_alignment_loss(gigl_ctx* ctx, const float* u, int64_t ld_u, const float* p, int64_t ld_p, int32_t n, int32_t d,
+                            float alpha, float* norm_out, float* loss_out);
+/* The gradient of gigl_alignment_loss (loss.py:591-626): du[i] = *gout_dev alpha norm[i]^(alpha - 2) (u_i - p_i) / n and
+ * dp[i] = -du[i] (both [n][d] contiguous); a row with u_i == p_i gets zeros, torch's subgradient of norm. */
+int32_t gigl_alignment_loss_backward(gigl_ctx* ctx, const float* u, int64_t ld_u, const float* p, int64_t ld_p, int32_t n,
+                                     int32_t d, float alpha, const float* norm, const float* gout_dev, float* du, float* dp);
+
 /* ---- rank metrics of a score matrix: MRR and hits@k of every anchor's positives among the random negatives, one wave per
  *      anchor, summed on the device.  Replaces hit_rate_at_k / mean_reciprocal_rank (python/gigl/src/common/utils/
  *      eval_metrics.py:6-73) as the trainer's validate() calls them once per anchor (node_anchor_based_link_prediction_
