@@ -83,6 +83,7 @@ SYMBOLS = [
     "gigl_gcn_plan_set_fused_root", "gigl_gcn_plan_fused_root",
     "gigl_nc_eval_metrics",
     "gigl_uniformity_loss", "gigl_uniformity_loss_backward", "gigl_alignment_loss", "gigl_alignment_loss_backward",
+    "gigl_grace_loss", "gigl_grace_loss_backward",
 ]
 
 KERNEL_IDS = {
@@ -373,6 +374,8 @@ def load() -> C.CDLL:
         "gigl_uniformity_loss_backward": [vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, i64],
         "gigl_alignment_loss": [vp, vp, i64, vp, i64, i32, i32, C.c_float, vp, vp],
         "gigl_alignment_loss_backward": [vp, vp, i64, vp, i64, i32, i32, C.c_float, vp, vp, vp, vp],
+        "gigl_grace_loss": [vp, vp, i64, vp, i64, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp],
+        "gigl_grace_loss_backward": [vp, vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, i64, vp, i64],
         "gigl_gather_mean_backward": [vp, vp, i32, vp, vp, vp, vp, i64, vp],
         "gigl_gather_mean_backward_transposed": [vp, vp, i32, vp, vp, vp, vp, i64, vp, i64, i64, i32, vp],
         "gigl_transposed_rows_build": [vp, vp, vp, vp, vp, i64, vp, i64, i64, vp],

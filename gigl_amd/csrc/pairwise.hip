@@ -8,8 +8,8 @@
 //   prep      Xc = X - column mean (distances are translation invariant; two launches, fixed order), sq_i = |xc_i|^2.  The
 //             centring keeps sq_i + sq_j - 2 g_ij and r_i x_i - sum w x_j free of cancellation when the rows have collapsed
 //             towards one point; sum_i dU/dxc_i = 0, so the gradient with respect to Xc IS the gradient with respect to X.
-//   forward   one workgroup per pair of 64-row tiles I <= J.  gram_tile: the two panels pass through LDS in K chunks of 32,
-//             split on the way in into three bf16 planes (split_planes.h: x = b1 + b2 + b3 exactly), six
+//   forward   one workgroup per pair of 64-row tiles I <= J.  gram_tile (gram_tile.h): the two panels pass through LDS in K chunks
+//             of 32, split on the way in into three bf16 planes (split_planes.h: x = b1 + b2 + b3 exactly), six
 //             v_mfma_f32_32x32x16_bf16 per 16 k carry the product at fp32 accuracy; four waves as 2 x 2, a 32 x 32 block of G
 //             each, two accumulators so that dependent MFMAs alternate.  Epilogue in registers: w masked to i < j < n, lane ->
 //             wave -> workgroup sum, one double per tile pair; pair_fold_kernel adds the partials in a fixed order in fp64.
@@ -27,16 +27,13 @@
 // Alignment.  mean_i |u_i - p_i|^alpha: one wave per row, a fixed-order fold; backward alpha |.|^(alpha - 2) (u - p) / n,
 // zero where u_i == p_i (torch's subgradient of norm).
 #include "common.h"
-#include "split_planes.h"
+#include "gram_tile.h"
 
 #include <cmath>
 #include <cstdint>
 
 namespace {
 
-constexpr int PT = 64;            // rows per tile
-constexpr int PBK = 32;           // k per LDS chunk
-constexpr int PPLANE = PT * PBK;  // bf16 elements of one plane of one panel
 constexpr int PCH = 128;          // columns of d per backward workgroup (two accumulators per 32: 256 spills)
 constexpr int PMAXD = 512;
 
@@ -100,74 +97,6 @@ __global__ __launch_bounds__(256) void pair_centre_kernel(const float* __restric
   }
 }
 
-// ---- the Gram tile ------------------------------------------------------------------------------------------------------
-template <bool VEC>  // VEC: d % 4 == 0 and xc 16-byte aligned
-__device__ __forceinline__ float4_t pair_load4(const float* __restrict__ xc, int n, int d, int row, int k) {
-  float4_t v = {0.f, 0.f, 0.f, 0.f};
-  if (row < n) {
-    const float* p = xc + (int64_t)row * d + k;
-    if constexpr (VEC) {
-      if (k < d) v = *reinterpret_cast<const float4_t*>(p);
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        if (k + t < d) v[t] = p[t];
-    }
-  }
-  return v;
-}
-
-// D[a][b] = <xc[a0 + a], xc[b0 + b]> over the 64 x 64 tile, by all 256 threads: wave wv holds the 32 x 32 block (wv >> 1, wv & 1)
-// in the D layout (register v of lane (r, g): row 8 (v / 4) + 4 g + v % 4, column r).  Rows >= n and k >= d enter as zeros.
-// s: six planes (three of each panel).  Starts with a barrier: the caller's earlier reads of s are done before it is refilled.
-template <bool VEC>
-__device__ __forceinline__ float16_t gram_tile(const float* __restrict__ xc, int n, int d, int a0, int b0,
-                                               short (*s)[PPLANE]) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 31, g = lane >> 5;
-  const int wa = wv >> 1, wb = wv & 1;
-  const int lr = tid >> 3, lc = (tid & 7) * 4;  // loader: rows lr, lr + 32; k segment lc .. lc + 3
-  float16_t acc0, acc1;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) acc0[v] = acc1[v] = 0.f;
-  float4_t ra[2], rb[2];
-  auto gload = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      ra[i] = pair_load4<VEC>(xc, n, d, a0 + lr + 32 * i, k0 + lc);
-      rb[i] = pair_load4<VEC>(xc, n, d, b0 + lr + 32 * i, k0 + lc);
-    }
-  };
-  gload(0);
-  for (int k0 = 0; k0 < d; k0 += PBK) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int o = split_lds_off(lr + 32 * i, lc);
-      split_store(ra[i], &s[0][o], &s[1][o], &s[2][o]);
-      split_store(rb[i], &s[3][o], &s[4][o], &s[5][o]);
-    }
-    __syncthreads();
-    if (k0 + PBK < d) gload(k0 + PBK);  // lands during this chunk's MFMAs
-    bf16x8_t fa0[3], fb0[3], fa1[3], fb1[3];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      fa0[p] = *reinterpret_cast<const bf16x8_t*>(&s[p][split_lds_off(wa * 32 + r, 8 * g)]);
-      fb0[p] = *reinterpret_cast<const bf16x8_t*>(&s[3 + p][split_lds_off(wb * 32 + r, 8 * g)]);
-      fa1[p] = *reinterpret_cast<const bf16x8_t*>(&s[p][split_lds_off(wa * 32 + r, 16 + 8 * g)]);
-      fb1[p] = *reinterpret_cast<const bf16x8_t*>(&s[3 + p][split_lds_off(wb * 32 + r, 16 + 8 * g)]);
-    }
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // smallest terms first
-#pragma unroll
-    for (int t = 0; t < 6; ++t) {
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa0[PA[t]], fb0[PB[t]], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa1[PA[t]], fb1[PB[t]], acc1, 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < 16; ++v) acc0[v] += acc1[v];
-  return acc0;
-}
-
 // ---- forward ------------------------------------------------------------------------------------------------------------
 // part[p] = sum of w_ij over the entries i < j < n of tile pair p = J (J + 1) / 2 + I, I <= J
 template <bool VEC>
@@ -180,7 +109,7 @@ __global__ __launch_bounds__(256) void pair_sum_kernel(const float* __restrict__
   while (J * (J + 1) / 2 > p) --J;
   while ((J + 1) * (J + 2) / 2 <= p) ++J;
   const int I = (int)(p - J * (J + 1) / 2);
-  const float16_t acc = gram_tile<VEC>(xc, n, d, I * PT, (int)J * PT, s);
+  const float16_t acc = gram_tile<VEC>(xc, xc, n, d, I * PT, (int)J * PT, s);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, g = lane >> 5;
   const int j = (int)J * PT + (wv & 1) * 32 + r;
   const float sqj = j < n ? sq[j] : 0.f;
@@ -217,12 +146,6 @@ __global__ __launch_bounds__(1024) void pair_fold_kernel(const double* __restric
 }
 
 // ---- backward -----------------------------------------------------------------------------------------------------------
-// position kpos of the second product's k order -> row j of the 32-row half: register v = 8 s + t of the first product's D
-// layout holds row 16 s + 8 (t / 4) + 4 g + t % 4, and an operand lane (., g) supplies k = 16 s + 8 g + t
-__device__ __forceinline__ int pair_kperm(int kpos) {
-  return (kpos & 0x13) | ((kpos & 4) << 1) | ((kpos & 8) >> 1);
-}
-
 // The second product's operands are split in FIXED point, not by split3.  r_i x_i - sum_j w_ij x_j cancels: among (near)
 // duplicates w ~ 1 and both terms are ~ their count, while the gradient may be the far rows' e^-8 of that — fp32 accumulators
 // that mix the two round the answer away.  So x / q = t1 + t2 / 2^8 + t3 / 2^16 (+ a remainder < 2^-16) with INTEGERS t1 in
@@ -284,7 +207,7 @@ __global__ __launch_bounds__(256) void pair_backward_kernel(const float* __restr
   const int tiles = (n + PT - 1) / PT;
   for (int J = 0; J < tiles; ++J) {
     const int J0 = J * PT;
-    const float16_t gt = gram_tile<VEC>(xc, n, d, J0, I0, s);  // [j][i]
+    const float16_t gt = gram_tile<VEC>(xc, xc, n, d, J0, I0, s);  // [j][i]
     // W where it lies, split into the second product's A fragments: fa[s2][plane], k = 16 s2 + 8 g + t <-> register 8 s2 + t
     bf16x8_t fa[2][3];
 #pragma unroll

@@ -1217,6 +1217,30 @@ class HipEngine:
                                                       p(grad_loss), p(dx), d), self._ctx)
         return dx
 
+    def grace_loss(self, h1: torch.Tensor, h2: torch.Tensor, temperature: float):
+        """-> (loss [] fp32, a, b [n, d] normalised rows, norm [2, n], lse [2, n]): gigl_grace_loss"""
+        h1, h2 = self._embedding_rows(h1), self._embedding_rows(h2)
+        assert h1.shape == h2.shape
+        n, d = int(h1.shape[0]), int(h1.shape[1])
+        dev = self.device
+        a, b = (torch.empty((n, d), dtype=torch.float32, device=dev) for _ in range(2))
+        norm, lse = (torch.empty((2, n), dtype=torch.float32, device=dev) for _ in range(2))
+        dg = torch.empty(n, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        check(self._lib.gigl_grace_loss(self._ctx, p(h1), int(h1.stride(0)), p(h2), int(h2.stride(0)), n, d, float(temperature),
+                                        p(a), p(b), p(norm), p(dg), p(lse), p(loss)), self._ctx)
+        return loss, a, b, norm, lse
+
+    def grace_loss_backward(self, a, b, norm, lse, temperature: float, grad_loss):
+        """-> (dh1, dh2) [n, d]: gigl_grace_loss_backward"""
+        n, d = int(a.shape[0]), int(a.shape[1])
+        dh1, dh2 = (torch.empty((n, d), dtype=torch.float32, device=self.device) for _ in range(2))
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(self._lib.gigl_grace_loss_backward(self._ctx, p(a), p(b), p(norm), p(lse), n, d, float(temperature), p(grad_loss),
+                                                 p(dh1), d, p(dh2), d), self._ctx)
+        return dh1, dh2
+
     def alignment_loss(self, u: torch.Tensor, v: torch.Tensor, alpha: float):
         """-> (loss [] fp32, norm [n]): gigl_alignment_loss"""
         u, v = self._embedding_rows(u), self._embedding_rows(v)

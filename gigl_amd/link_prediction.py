@@ -9,6 +9,7 @@ Mirror of (paths relative to the reference root):
   RetrievalLoss                        python/gigl/src/common/models/layers/loss.py:177-360
       calculate_batch_retrieval_loss :209-277, _mask_by_query_ids :279-305, _mask_by_candidate_ids :307-331
   AligmentLoss, UniformityLoss         python/gigl/src/common/models/layers/loss.py:591-626  (csrc/pairwise.hip)
+  GRACELoss                            python/gigl/src/common/models/layers/loss.py:362-416  (csrc/contrast.hip)
 The loss is one fused device pass over the score matrix (csrc/loss.hip: temperature, sampling-probability correction,
 both masks, log-softmax and the summed cross-entropy, plus its backward), pinned by the reference's known-answer tests
 (tests/test_link_prediction.py restates loss_test.py:61-166 and decoder_test.py:44-62).
@@ -309,3 +310,42 @@ class UniformityLoss(nn.Module):
         u, p = _device_rows(user_embeddings, "UniformityLoss"), _device_rows(item_embeddings, "UniformityLoss")
         eng, t = default_engine(u.device), float(self.temperature)
         return (_FusedUniformity.apply(u, eng, t) + _FusedUniformity.apply(p, eng, t)) / 2
+
+
+class _FusedGrace(torch.autograd.Function):
+    """two views' rows -> the GRACE contrastive loss (csrc/contrast.hip: normalisation, the three cosine Gram matrices on the
+    matrix cores, a running-maximum log-sum-exp per row); backward = a second sweep that recomputes the softmax weights and
+    multiplies them into the rows, no n x n tensor either way"""
+
+    @staticmethod
+    def forward(ctx, h1, h2, eng, temperature):
+        loss, a, b, norm, lse = eng.grace_loss(h1, h2, temperature)
+        ctx.eng, ctx.temperature = eng, temperature
+        ctx.save_for_backward(a, b, norm, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, norm, lse = ctx.saved_tensors
+        dh1, dh2 = ctx.eng.grace_loss_backward(a, b, norm, lse, ctx.temperature, g.to(torch.float32).contiguous())
+        return dh1, dh2, None, None
+
+
+class GRACELoss(nn.Module):
+    """The reference's GRACELoss (loss.py:362-416): the mean over rows of -log(e^{sim12_ii / T} / (sum_{j != i} e^{sim11_ij / T}
+    + sum_j e^{sim12_ij / T})), averaged with its mirror image, sim = cosine similarity — evaluated in log space by one fused
+    MFMA pass (gigl_grace_loss) instead of four n x n exp matrices, so it is finite at the reference task's default T = 0.001
+    where the literal form is inf - inf.  forward -> (loss, 1).  Device tensors only."""
+
+    def __init__(self, temperature: Optional[float] = None):
+        super().__init__()
+        if temperature is None:  # (the reference would fail dividing by it)
+            raise ValueError("GRACELoss needs a temperature")
+        self.temperature = float(temperature)
+
+    def forward(self, h1: torch.Tensor, h2: torch.Tensor, device: Optional[torch.device] = None):
+        from .engine import default_engine
+        h1, h2 = _device_rows(h1, "GRACELoss"), _device_rows(h2, "GRACELoss")
+        if h1.shape != h2.shape:
+            raise ValueError(f"GRACELoss: {tuple(h1.shape)} rows of view 1 against {tuple(h2.shape)} of view 2")
+        return _FusedGrace.apply(h1, h2, default_engine(h1.device), self.temperature), 1

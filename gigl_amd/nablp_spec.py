@@ -16,9 +16,10 @@ retrieval loss over the [queries x candidates] score matrix (gigl_retrieval_loss
 sampling correction when enabled).
 Scope: homogeneous graphs (one condensed node type / edge type) and heterogeneous ones (typed batches through the
 native typed collate, HGT / SimpleHGN encoders, first supervision edge type: spec :245-271, infer.py on HeteroData); the
-Retrieval, Margin, Softmax and DirectAU tasks (DirectAU through the autograd loop: its losses read the embeddings, not the
-score matrix the training plans' head works on) — the augmentation-based self-supervised ones (GRACE, BGRL, ...) are not
-built.
+Retrieval, Margin, Softmax, DirectAU and GRACE tasks (DirectAU and GRACE through the autograd loop: their losses read
+embeddings, not the score matrix the training plans' head works on; GRACE, the first task over the input batch — two
+augmented views, task.py:212-279 — on homogeneous TFRecord batches in one process) — the other augmentation-based
+self-supervised ones (WhiteningDecorrelation, GBT, BGRL, TBGRL, FeatureReconstruction) are not built.
 Data: main samples are the NodeAnchorBasedLinkPredictionSample TFRecords and random negatives the
 RootedNodeNeighborhood TFRecords the sampler wrote, re-filed into train/val/test by the split generator
 (gigl_amd/split_generator.py; datasetMetadata.nodeAnchorBasedLinkPredictionDataset URIs).  Without split outputs
@@ -42,7 +43,8 @@ from .base import (BaseInferencer, BaseTrainer, EvalMetric, EvalMetricsCollectio
                    hit_rate_at_k, import_obj, mean_reciprocal_rank, no_grad_eval)
 from .batches import NodeAnchorBasedLinkPredictionBatch, RootedNodeNeighborhoodBatch, iterate_tfrecord_batches
 from .config import GbmlConfigPbWrapper, tfrecord_files
-from .link_prediction import AligmentLoss, LinkPredictionDecoder, LinkPredictionGNN, RetrievalLoss, UniformityLoss
+from .link_prediction import (AligmentLoss, GRACELoss, LinkPredictionDecoder, LinkPredictionGNN, RetrievalLoss,
+                              UniformityLoss)
 from .models import GraphSAGE
 from .task_specs import _dropout_arg, _rank_world
 
@@ -434,6 +436,61 @@ class DirectAU(nn.Module):
         return running_loss, 1
 
 
+class GRACE(nn.Module):
+    """task.py:212-279: two corrupted views of the main batch's graph (augmentations.get_augmented_graph), both encoded by
+    the job's encoder, the roots' rows through a task head Linear(out, hid) -> ReLU -> Linear(hid, out) (on gigl_linear), and
+    the two-view contrastive loss (GRACELoss, csrc/contrast.hip).  forward -> (loss, 1).
+    The encoder is the model's own: it is bound after construction (bind_encoder; init_model does it) and held WITHOUT being
+    registered as a submodule, so that its parameters appear once in a state dict; the head is built then.
+    View 1 drops features with feat_drop_1: the reference passes edge_drop_2 there (task.py:252), an evident slip.
+    Homogeneous GraphData batches only (the TFRecord route); `seed` starts the augmentations' own generator."""
+    task_name = "GRACE"
+    result_types = ("input_batch",)
+
+    def __init__(self, encoder: Optional[nn.Module] = None, temperature: float = 0.001, feat_drop_1: float = 0.3,
+                 edge_drop_1: float = 0.3, feat_drop_2: float = 0.3, edge_drop_2: float = 0.3, seed: int = 0):
+        super().__init__()
+        self.loss = GRACELoss(temperature=temperature)
+        self.feat_drop_1, self.edge_drop_1 = float(feat_drop_1), float(edge_drop_1)
+        self.feat_drop_2, self.edge_drop_2 = float(feat_drop_2), float(edge_drop_2)
+        self._generator = torch.Generator().manual_seed(int(seed))
+        self._encoder_ref = ()  # (a tuple: not a registered submodule)
+        self.head: Optional[nn.Sequential] = None
+        if encoder is not None:
+            self.bind_encoder(encoder)
+
+    def bind_encoder(self, encoder: nn.Module) -> None:
+        self._encoder_ref = (encoder,)
+        if self.head is None:
+            hid_dim, out_dim = int(encoder.hid_dim), int(encoder.out_dim)
+            self.head = nn.Sequential(nn.Linear(out_dim, hid_dim), nn.ReLU(), nn.Linear(hid_dim, out_dim))
+
+    def _apply_head(self, x: torch.Tensor) -> torch.Tensor:
+        from .engine import default_engine
+        from .models_hetero import _linear
+        eng = default_engine(x.device)
+        hidden = torch.relu(_linear(eng, x, self.head[0].weight, self.head[0].bias))
+        return _linear(eng, hidden, self.head[2].weight, self.head[2].bias)
+
+    def forward(self, task_input: NodeAnchorBasedLinkPredictionTaskInputs, gbml_config_pb_wrapper=None,
+                should_eval: bool = False, device: torch.device = torch.device("cpu")):
+        from .augmentations import get_augmented_graph
+        from .nn import GraphData
+        if not self._encoder_ref:
+            raise RuntimeError("GRACE: no encoder is bound (bind_encoder; the task spec's init_model does it)")
+        main_batch = task_input.main_batch
+        if not isinstance(main_batch.graph, GraphData):
+            raise NotImplementedError(f"GRACE augments homogeneous GraphData batches (the TFRecord route), not "
+                                      f"{type(main_batch.graph).__name__}")
+        graph = main_batch.graph.to(device)
+        roots = main_batch.root_node_indices.to(device)
+        views = []
+        for edge_drop, feat_drop in ((self.edge_drop_1, self.feat_drop_1), (self.edge_drop_2, self.feat_drop_2)):
+            view = get_augmented_graph(graph, edge_drop_ratio=edge_drop, feat_drop_ratio=feat_drop, generator=self._generator)
+            views.append(self._apply_head(self._encoder_ref[0](view)[roots]))
+        return self.loss(h1=views[0], h2=views[1], device=device)
+
+
 class NodeAnchorBasedLinkPredictionTasks:
     """task.py:699-758: weighted sum of per-sample task losses"""
 
@@ -548,6 +605,11 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             # (DirectAU's `temperature` is the uniformity kernel's width, 2.0 in the paper — never the softmax temperature)
             offered = {"temperature": float(kwargs.get("directau_temperature", 2.0)),
                        "gamma": float(kwargs.get("gamma", 1.0)), "alpha": float(kwargs.get("alpha", 2.0))}
+        if isinstance(task_cls, type) and issubclass(task_cls, GRACE):
+            # (likewise its own temperature, the reference task's default; the encoder is bound in init_model)
+            offered = {"temperature": float(kwargs.get("grace_temperature", 0.001)),
+                       "seed": int(kwargs.get("augment_seed", 0)),
+                       **{k: float(kwargs.get(k, 0.3)) for k in ("feat_drop_1", "edge_drop_1", "feat_drop_2", "edge_drop_2")}}
         takes = inspect.signature(task_cls.__init__).parameters
         # (the reference passes temperature / remove_accidental_hits to whatever class task_path names — its Margin and
         # Softmax tasks cannot be built that way; here every task gets the arguments its constructor declares)
@@ -602,8 +664,24 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             in_dim=max(in_dim, 1), hid_dim=self.hidden_dim, out_dim=self.out_channels, num_layers=self.num_layers,
             should_l2_normalize_embedding_layer_output=self.should_l2_normalize_embedding_layer_output, **extra)
         model = LinkPredictionGNN(encoder=encoder, decoder=LinkPredictionDecoder())
+        # tasks that encode the input batch themselves (result type input_batch: GRACE) get the model's encoder, and their
+        # heads become part of the model, `task_heads.<task name>`: one parameter list for the optimiser, one state dict
+        heads = {}
+        for task in self.tasks._task_to_fn_map.values():
+            if hasattr(task, "bind_encoder"):
+                task.bind_encoder(encoder)
+                heads[task.task_name] = task.head
+        if heads:
+            model.task_heads = nn.ModuleDict(heads)
         if state_dict is not None:
-            model.load_state_dict(state_dict)
+            # (a checkpoint written without the task heads still loads: they keep their initial values; one that carries
+            # heads this job does not have loads without them)
+            mine = model.state_dict().keys()
+            known = {k: v for k, v in state_dict.items() if k in mine or not k.startswith("task_heads.")}
+            missing, unexpected = model.load_state_dict(known, strict=False)
+            other = [k for k in missing if not k.startswith("task_heads.")] + list(unexpected)
+            if other:
+                raise RuntimeError(f"init_model: the state dict does not match the model ({other})")
         self.model = model
         return model
 
@@ -611,6 +689,8 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         """the heterogeneous branch of init_model (node_anchor_based_link_prediction_modeling_task_spec.py:245-271): the
         encoder class (gnn_model_class_path; default HGT) takes the per-type feature dims, hid / out dims, num_layers,
         num_heads"""
+        if "input_batch" in self.tasks.result_types:
+            raise NotImplementedError("tasks over the input batch (GRACE) are built for homogeneous graphs only")
         pm = cfg.preprocessed_metadata
         node_dims = {name: max(pm.nodes[c].feature_dim, 1) for c, name in cfg.condensed_node_type_map.items()}
         edge_dims = {tuple(t): pm.edges[c].feature_dim for c, t in cfg.condensed_edge_type_map.items()}
@@ -664,6 +744,12 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         if self._hbm_anchors is not None:
             return self._hbm_anchors or None
         self._hbm_anchors = {}
+        if "input_batch" in self.tasks.result_types:
+            # (GRACE augments the batch's GraphData; the batch graph of the in-HBM route is not one)
+            import os
+            if (self._kwargs.get("data_route") or os.environ.get("GIGL_AMD_ROUTE") or "auto").lower() == "hbm":
+                raise ValueError("data_route hbm cannot serve a task over the input batch (GRACE): it takes the TFRecord route")
+            return None
         from .hbm import ResidentGraph, encoder_trains_over_graph_data, encoder_trains_over_hip_batches, route_of
         device = getattr(self, "_device", None)
         inner = self.model.module if hasattr(self.model, "module") else self.model
@@ -1076,6 +1162,9 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         self._ensure_engine(device)
         cfg = gbml_config_pb_wrapper
         _, world = _rank_world()
+        if world > 1 and "input_batch" in self.tasks.result_types:
+            raise NotImplementedError("tasks over the input batch (GRACE) train in one process: the data-parallel wrapper's "
+                                      "forward does not run their heads")
         plan = self._library_train_plan(cfg)
         if plan is not None:
             try:

@@ -1162,6 +1162,29 @@ int32_t gigl_alignment_loss(gigl_ctx* ctx, const float* u, int64_t ld_u, const f
 int32_t gigl_alignment_loss_backward(gigl_ctx* ctx, const float* u, int64_t ld_u, const float* p, int64_t ld_p, int32_t n,
                                      int32_t d, float alpha, const float* norm, const float* gout_dev, float* du, float* dp);
 
+/* ---- the GRACE two-view contrastive loss over embedding rows (GRACELoss, python/gigl/src/common/models/layers/
+ *      loss.py:362-416).  All pointers DEVICE; the work is issued on the ctx's stream, nothing synchronises the host, nothing
+ *      of size n x n is written.  1 <= d <= 512, n <= 2^18, temperature > 0 (GIGL_E_INVALID_ARG with a message beyond);
+ *      results are bit-reproducible run to run.
+ * h1, h2 [n][d] fp32, rows ld1 / ld2 floats apart, not normalised.  With a_i = h1_i / max(|h1_i|, 1e-8), b_i likewise from h2,
+ * z11 = a a^T / T, z12 = a b^T / T, z22 = b b^T / T (loss.py:392-400, :406):
+ *   L1_i = log(sum_{j != i} e^{z11_ij} + sum_j e^{z12_ij}),  L2_i = log(sum_{j != i} e^{z22_ij} + sum_j e^{z12_ji}),
+ *   *loss_out = (1 / n) sum_i ((L1_i + L2_i) / 2 - z12_ii)
+ * — loss.py:407-416 in log space: the same value wherever exp(1 / T) is finite, and a finite value where the literal form
+ * gives NaN (the reference task's default T = 0.001).  n == 0: NaN; n == 1: 0.
+ * What the backward reads: a_out, b_out [n][d] contiguous (the normalised rows), norm_out [2][n] (|h1_i|, then |h2_i|),
+ * lse_out [2][n] (L1, then L2); dg_out [n] receives z12_ii. */
+int32_t gigl_grace_loss(gigl_ctx* ctx, const float* h1, int64_t ld1, const float* h2, int64_t ld2, int32_t n, int32_t d,
+                        float temperature, float* a_out, float* b_out, float* norm_out, float* dg_out, float* lse_out,
+                        float* loss_out);
+/* The gradient of gigl_grace_loss (loss.py:362-416: autograd through :392-416 in the reference), scaled by *gout_dev (NULL:
+ * 1), written to dh1 / dh2 [n][d], rows ld1 / ld2 floats apart.  a, b, norm, lse: the forward's outputs.  A row with |h_i| <=
+ * 1e-8 gets the gradient of h_i / 1e-8, as autograd through torch.max(norm, eps) (:397-398).  n == 1: zeros.  Scratch (2 n d
+ * floats) comes from the ctx's arena. */
+int32_t gigl_grace_loss_backward(gigl_ctx* ctx, const float* a, const float* b, const float* norm, const float* lse, int32_t n,
+                                 int32_t d, float temperature, const float* gout_dev, float* dh1, int64_t ld1, float* dh2,
+                                 int64_t ld2);
+
 /* ---- rank metrics of a score matrix: MRR and hits@k of every anchor's positives among the random negatives, one wave per
  *      anchor, summed on the device.  Replaces hit_rate_at_k / mean_reciprocal_rank (python/gigl/src/common/utils/
  *      eval_metrics.py:6-73) as the trainer's validate() calls them once per anchor (node_anchor_based_link_prediction_
