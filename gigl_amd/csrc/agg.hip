@@ -800,7 +800,7 @@ __global__ __launch_bounds__(256) void linear_weight_grad_reduce_kernel(const fl
 // two rows of a write group overlapped in banks 0-3, one extra LDS cycle per group — SQ_LDS_BANK_CONFLICT was a third
 // of the LDS cycles, exactly the writes' share — and the tile pair took 61 KB; 49 KB now: three workgroups per CU.)
 // Workgroup tile 128 x 64*NJ, four waves as 2 x 2, each 64 rows x 32*NJ columns.
-// (split3, split_lds_off and split_store live in split_planes.h: pairwise.hip uses them too)
+// (split3, split8, split_lds_off and split_store live in split_planes.h: pairwise.hip and contrast.hip use them too)
 
 // Weight gradient on the matrix cores: dW[n][k] = sum_r dy[r][n] * a[r][k] is a product whose INNER dimension is the row
 // index, so both operands enter transposed.  A thread stages eight consecutive ROWS of one column (eight dword loads,
@@ -845,14 +845,10 @@ __global__ __launch_bounds__(256) void linear_weight_grad_mfma_kernel(const floa
       va[t] = x;
     }
   };
-  auto stage = [&](const float* v, short (*pl)[64 * 32]) {
-    uint32_t b1[8], b2[8], b3[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) split3(v[t], b1[t], b2[t], b3[t]);
+  auto stage = [&](const float (&v)[8], short (*pl)[64 * 32]) {
     const int o = split_lds_off(c, rb * 8);
-    *reinterpret_cast<uint4*>(&pl[0][o]) = make_uint4((b1[0] >> 16) | b1[1], (b1[2] >> 16) | b1[3], (b1[4] >> 16) | b1[5], (b1[6] >> 16) | b1[7]);
-    *reinterpret_cast<uint4*>(&pl[1][o]) = make_uint4((b2[0] >> 16) | b2[1], (b2[2] >> 16) | b2[3], (b2[4] >> 16) | b2[5], (b2[6] >> 16) | b2[7]);
-    *reinterpret_cast<uint4*>(&pl[2][o]) = make_uint4((b3[0] >> 16) | b3[1], (b3[2] >> 16) | b3[3], (b3[4] >> 16) | b3[5], (b3[6] >> 16) | b3[7]);
+    split8(v, *reinterpret_cast<bf16x8_t*>(&pl[0][o]), *reinterpret_cast<bf16x8_t*>(&pl[1][o]),
+           *reinterpret_cast<bf16x8_t*>(&pl[2][o]));
   };
   const int wn = wv >> 1, wk = wv & 1, r = lane & 31, g = lane >> 5;
   float16_t acc0, acc1;

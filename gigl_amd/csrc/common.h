@@ -404,6 +404,17 @@ static inline void gigl_fill_u32(hipStream_t st, void* p, uint32_t value, int64_
   hipLaunchKernelGGL(gigl_fill_u32_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (uint32_t*)p, value, n_words);
 }
 
+// x[i][c] = 0 for the n rows of d floats, ld floats apart (a gradient that is zero whatever the input)
+static __global__ __launch_bounds__(256) void gigl_zero_rows_kernel(float* __restrict__ x, int64_t ld, int n, int d) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < (int64_t)n * d) x[(i / d) * ld + i % d] = 0.f;
+}
+static inline void gigl_zero_rows(hipStream_t st, float* x, int64_t ld, int n, int d) {
+  hipLaunchKernelGGL(gigl_zero_rows_kernel, dim3((unsigned)(((int64_t)n * d + 255) / 256)), dim3(256), 0, st, x, ld, n, d);
+}
+
+static inline bool gigl_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // wt [cols][rows] = the transpose of the row-major w [rows][cols]
 static __global__ __launch_bounds__(256) void gigl_transpose_f32_kernel(const float* __restrict__ w, int rows, int cols,
                                                                         float* __restrict__ wt) {

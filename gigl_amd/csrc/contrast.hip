@@ -19,15 +19,17 @@
 //   backward  with w_ij = e^(z_ij - L_v[i]) + e^(z_ij - L_u[j]) (u = v in the own-view tiles, the other view otherwise):
 //                 ga_i = (g / (2 n T)) [sum_{j != i} w11_ij a_j + sum_j w12_ij b_j - 2 b_i],   gb_i its mirror image.
 //             One workgroup per (view, row tile I, 128-column chunk of d), sweeping every J, two Gram tiles and two second
-//             products (own view, other view) per J.  The structure is pair_backward_kernel's (pairwise.hip): the first
-//             product transposed, so that the weights lie in the second product's A-operand layout and never pass through
-//             LDS; the other operand staged transposed ([column][32 j]) under pair_kperm.  Both operands are split with the
-//             plain split3 (a row's weights sum to about 2: nothing here cancels as DirectAU's r_i x_i does); the two halves
-//             of j meet in the epilogue through LDS, in a fixed order.
+//             products (own view, other view) per J: the weights are computed from the TRANSPOSED Gram tile, where they
+//             lie, and multiplied into the rows by gram_tile.h's second product (which explains the layout), as in
+//             pair_backward_kernel (pairwise.hip).  Both operands are split with the plain split3 (a row's weights sum to
+//             about 2: nothing here cancels as DirectAU's r_i x_i does); the two halves of j meet in the epilogue through
+//             LDS, in a fixed order.
 //   norm bwd  one wave per row: gh_i = (ga_i - <ga_i, a_i> a_i) / |h_i|, or ga_i / 1e-8 where |h_i| <= 1e-8 (autograd
 //             through the reference's torch.max(norm, eps)).
 #include "common.h"
+#include "dispatch.h"
 #include "gram_tile.h"
+#include "wave_reduce.h"
 
 #include <cmath>
 #include <cstdint>
@@ -101,7 +103,7 @@ __global__ __launch_bounds__(256) void grace_lse_kernel(const float* __restrict_
       float z[16], tm = -INFINITY;
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int j = J0 + wj * 32 + 8 * (v >> 2) + 4 * g + (v & 3);
+        const int j = J0 + wj * 32 + gram_row(v, g);
         z[v] = (j < n && (w == 1 || j != i_lane)) ? gt[v] * inv_t : -INFINITY;
         tm = fmaxf(tm, z[v]);
       }
@@ -135,35 +137,20 @@ __global__ __launch_bounds__(256) void grace_lse_kernel(const float* __restrict_
 // *loss = (1 / n) sum_i ((L1_i + L2_i) / 2 - dg_i) in a fixed order (one workgroup, fp64); NaN for n == 0, the mean of nothing
 __global__ __launch_bounds__(1024) void grace_fold_kernel(const float* __restrict__ L, const float* __restrict__ dg, int n,
                                                           float* __restrict__ loss) {
-  __shared__ double s_w[16];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   double acc = 0.0;
-  for (int i = tid; i < n; i += 1024) acc += 0.5 * ((double)L[i] + (double)L[n + i]) - (double)dg[i];
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  if (lane == 0) s_w[w] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-    for (int k = 0; k < 16; ++k) t += s_w[k];
-    // (n == 1: the one row is its own only term, L = dg in exact arithmetic)
-    *loss = n == 1 ? 0.f : (float)(t / (double)n);
-  }
+  for (int i = threadIdx.x; i < n; i += 1024) acc += 0.5 * ((double)L[i] + (double)L[n + i]) - (double)dg[i];
+  const double t = gigl_block1024_sum_f64(acc);
+  // (n == 1: the one row is its own only term, L = dg in exact arithmetic)
+  if (threadIdx.x == 0) *loss = n == 1 ? 0.f : (float)(t / (double)n);
 }
 
 // ---- backward -----------------------------------------------------------------------------------------------------------
-// eight floats -> the three bf16 planes of a fragment
-__device__ __forceinline__ void grace_split8(const float (&x)[8], bf16x8_t& f1, bf16x8_t& f2, bf16x8_t& f3) {
-  uint32_t b1[8], b2[8], b3[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) split3(x[u], b1[u], b2[u], b3[u]);
-  f1 = __builtin_bit_cast(bf16x8_t, make_uint4((b1[0] >> 16) | b1[1], (b1[2] >> 16) | b1[3], (b1[4] >> 16) | b1[5], (b1[6] >> 16) | b1[7]));
-  f2 = __builtin_bit_cast(bf16x8_t, make_uint4((b2[0] >> 16) | b2[1], (b2[2] >> 16) | b2[3], (b2[4] >> 16) | b2[5], (b2[6] >> 16) | b2[7]));
-  f3 = __builtin_bit_cast(bf16x8_t, make_uint4((b3[0] >> 16) | b3[1], (b3[2] >> 16) | b3[3], (b3[4] >> 16) | b3[5], (b3[6] >> 16) | b3[7]));
-}
+constexpr gram2_sched GRACE_SCHED = {{2, 0, 1, 1, 0, 0}, {0, 2, 1, 0, 1, 0}, {0, 0, 0, 0, 0, 0}};  // smallest terms first
 
 // ga[view][i][c] (contiguous [2][n][d]) for view blockIdx.z, row tile blockIdx.x, columns [128 blockIdx.y, +128); coef = 1 / (2 n T)
+// (two waves per SIMD: the registers allow two workgroups per CU; left to itself the compiler spends them on one)
 template <bool VEC>
-__global__ __launch_bounds__(256) void grace_backward_kernel(const float* __restrict__ a, const float* __restrict__ b,
+__global__ __launch_bounds__(256, 2) void grace_backward_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                              const float* __restrict__ L, int n, int d, float inv_t, float coef,
                                                              const float* __restrict__ gout, float* __restrict__ ga) {
   __shared__ __attribute__((aligned(16))) short s[6][PPLANE];
@@ -174,11 +161,11 @@ __global__ __launch_bounds__(256) void grace_backward_kernel(const float* __rest
   const float *L_own = L + (int64_t)view * n, *L_oth = L + (int64_t)(1 - view) * n;
   const int i_lane = I0 + wi * 32 + r;
   const float Li = i_lane < n ? L_own[i_lane] : 0.f;
-  float16_t acc2[GCH / 32];
+  float16_t acc2[GCH / 32][1];
 #pragma unroll
   for (int q = 0; q < GCH / 32; ++q)
 #pragma unroll
-    for (int v = 0; v < 16; ++v) acc2[q][v] = 0.f;
+    for (int v = 0; v < 16; ++v) acc2[q][0][v] = 0.f;
   const int tiles = (n + PT - 1) / PT;
   for (int J = 0; J < tiles; ++J) {
     const int J0 = J * PT;
@@ -195,82 +182,26 @@ __global__ __launch_bounds__(256) void grace_backward_kernel(const float* __rest
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const int v = 8 * s2 + u;
-          const int j = J0 + wj * 32 + 8 * (v >> 2) + 4 * g + (v & 3);
+          const int j = J0 + wj * 32 + gram_row(v, g);
           wt[u] = 0.f;
           if (j < n && i_lane < n && (w == 1 || j != i_lane)) {
             const float z = gt[v] * inv_t;
             wt[u] = expf(z - Li) + expf(z - Lj[j]);
           }
         }
-        grace_split8(wt, fa[s2][0], fa[s2][1], fa[s2][2]);
+        split8(wt, fa[s2][0], fa[s2][1], fa[s2][2]);
       }
-      // acc2[i][c] += W[i][j] X[j][c], 64 columns at a time: planes p + 3 h hold half h of j as [column][32 kpos]
-#pragma unroll
-      for (int sub = 0; sub < GCH / 64; ++sub) {
-        const int cs = c0 + 64 * sub;
-        if (cs < d) {  // (the whole workgroup)
-          __syncthreads();  // the fragments of the Gram tile / of the previous 64 columns have been read
-          const int col = cs + lane, h = wv >> 1;
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const int kb = (2 * (wv & 1) + q) * 8;  // this thread: kpos kb .. kb + 7 of column `col`, half h
-            float xv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-              const int j = J0 + 32 * h + pair_kperm(kb + u);
-              xv[u] = (j < n && col < d) ? x[(int64_t)j * d + col] : 0.f;
-            }
-            bf16x8_t f1, f2, f3;
-            grace_split8(xv, f1, f2, f3);
-            const int o = split_lds_off(lane, kb);
-            *reinterpret_cast<bf16x8_t*>(&s[3 * h + 0][o]) = f1;
-            *reinterpret_cast<bf16x8_t*>(&s[3 * h + 1][o]) = f2;
-            *reinterpret_cast<bf16x8_t*>(&s[3 * h + 2][o]) = f3;
-          }
-          __syncthreads();
-          constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // smallest terms first
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            bf16x8_t fb[2][3];
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-              for (int p = 0; p < 3; ++p)
-                fb[cb][p] = *reinterpret_cast<const bf16x8_t*>(&s[3 * wj + p][split_lds_off(cb * 32 + r, 16 * s2 + 8 * g)]);
-#pragma unroll
-            for (int u = 0; u < 6; ++u)
-#pragma unroll
-              for (int cb = 0; cb < 2; ++cb)
-                acc2[2 * sub + cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s2][PA[u]], fb[cb][PB[u]], acc2[2 * sub + cb], 0, 0, 0);
-          }
-        }
-      }
+      gram2_tile<GCH, 1, GRACE_SCHED>(fa, x, n, d, J0, c0, s, acc2,
+                                      [](float v, uint32_t& b1, uint32_t& b2, uint32_t& b3) { split3(v, b1, b2, b3); });
     }
   }
   // epilogue: the two halves of j meet, 32 columns at a time (half 0 + half 1), then ga = k (acc - 2 other_i)
   float* strip = reinterpret_cast<float*>(&s[0][0]) + wi * 1024;  // [32 rows][32 columns] per i block
   const float k = (gout ? *gout : 1.f) * coef;
   float* out = ga + (int64_t)view * n * d;
-#pragma unroll
-  for (int q = 0; q < GCH / 32; ++q) {
-    if (c0 + 32 * q < d) {  // (the whole workgroup)
-      __syncthreads();
-      if (wj == 1) {
-#pragma unroll
-        for (int v = 0; v < 16; ++v) strip[(8 * (v >> 2) + 4 * g + (v & 3)) * 32 + r] = acc2[q][v];
-      }
-      __syncthreads();
-      if (wj == 0) {
-        const int c = c0 + 32 * q + r;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-          const int il = 8 * (v >> 2) + 4 * g + (v & 3), i = I0 + wi * 32 + il;
-          if (i < n && c < d)
-            out[(int64_t)i * d + c] = k * ((acc2[q][v] + strip[il * 32 + r]) - 2.f * oth[(int64_t)i * d + c]);
-        }
-      }
-    }
-  }
+  gram2_meet<GCH, 1>(acc2, strip, I0 + wi * 32, c0, n, d, [&](int i, int c, const float (&lo)[1], const float (&hi)[1]) {
+    out[(int64_t)i * d + c] = k * ((lo[0] + hi[0]) - 2.f * oth[(int64_t)i * d + c]);
+  });
 }
 
 // one wave per (row, view): the gradient of the normalisation; h_v's gradient to rows ld floats apart
@@ -296,19 +227,12 @@ __global__ __launch_bounds__(256) void grace_norm_backward_kernel(const float* _
   }
 }
 
-__global__ __launch_bounds__(256) void grace_zero_rows_kernel(float* __restrict__ dx, int64_t ld, int n, int d) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < (int64_t)n * d) dx[(i / d) * ld + i % d] = 0.f;
-}
-
 int32_t grace_check(gigl_ctx* ctx, int32_t n, int32_t d, float temperature) {
   GIGL_REQUIRE(ctx, d >= 1 && d <= GMAXD, "the GRACE kernels serve 1 <= d <= %d (d=%d)", GMAXD, d);
   GIGL_REQUIRE(ctx, n >= 0 && n <= GRACE_MAX_N, "n=%d outside [0, %d]", n, GRACE_MAX_N);
   GIGL_REQUIRE(ctx, temperature > 0.f, "temperature=%g is not positive", (double)temperature);
   return GIGL_OK;
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -329,10 +253,10 @@ int32_t gigl_grace_loss(gigl_ctx* ctx, const float* h1, int64_t ld1, const float
     const unsigned tiles = (unsigned)((n + PT - 1) / PT);
     hipLaunchKernelGGL(grace_prep_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, h1, ld1, h2, ld2, n, d, inv_t, a_out, b_out,
                        norm_out, dg_out);
-    if (d % 4 == 0 && aligned16(a_out) && aligned16(b_out))
-      hipLaunchKernelGGL(grace_lse_kernel<true>, dim3(tiles, 2), dim3(256), 0, st, (const float*)a_out, (const float*)b_out, n, d, inv_t, lse_out);
-    else
-      hipLaunchKernelGGL(grace_lse_kernel<false>, dim3(tiles, 2), dim3(256), 0, st, (const float*)a_out, (const float*)b_out, n, d, inv_t, lse_out);
+    dispatch_bool(d % 4 == 0 && gigl_aligned16(a_out) && gigl_aligned16(b_out), [&](auto vec) {
+      hipLaunchKernelGGL(grace_lse_kernel<decltype(vec)::value>, dim3(tiles, 2), dim3(256), 0, st, (const float*)a_out,
+                         (const float*)b_out, n, d, inv_t, lse_out);
+    });
   }
   hipLaunchKernelGGL(grace_fold_kernel, dim3(1), dim3(1024), 0, st, (const float*)lse_out, (const float*)dg_out, n, loss_out);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
@@ -351,8 +275,8 @@ int32_t gigl_grace_loss_backward(gigl_ctx* ctx, const float* a, const float* b, 
   hipStream_t st = ctx->stream;
   if (n == 0) return GIGL_OK;
   if (n < 2) {  // the one row is its own only term: the loss is 0 whatever the row
-    hipLaunchKernelGGL(grace_zero_rows_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, dh1, ld1, n, d);
-    hipLaunchKernelGGL(grace_zero_rows_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, dh2, ld2, n, d);
+    gigl_zero_rows(st, dh1, ld1, n, d);
+    gigl_zero_rows(st, dh2, ld2, n, d);
   } else {
     const int64_t ga_bytes = gigl_align_up(2 * (int64_t)n * d * 4, 256);
     const int32_t rc = gigl_arena_reset(ctx, ga_bytes + 1024);
@@ -362,10 +286,10 @@ int32_t gigl_grace_loss_backward(gigl_ctx* ctx, const float* a, const float* b, 
     const float inv_t = 1.f / temperature;
     const float coef = (float)(1.0 / (2.0 * (double)n * (double)temperature));
     const dim3 grid((unsigned)((n + PT - 1) / PT), (unsigned)((d + GCH - 1) / GCH), 2);
-    if (d % 4 == 0 && aligned16(a) && aligned16(b))
-      hipLaunchKernelGGL(grace_backward_kernel<true>, grid, dim3(256), 0, st, a, b, lse, n, d, inv_t, coef, gout_dev, ga);
-    else
-      hipLaunchKernelGGL(grace_backward_kernel<false>, grid, dim3(256), 0, st, a, b, lse, n, d, inv_t, coef, gout_dev, ga);
+    dispatch_bool(d % 4 == 0 && gigl_aligned16(a) && gigl_aligned16(b), [&](auto vec) {
+      hipLaunchKernelGGL(grace_backward_kernel<decltype(vec)::value>, grid, dim3(256), 0, st, a, b, lse, n, d, inv_t, coef, gout_dev,
+                         ga);
+    });
     hipLaunchKernelGGL(grace_norm_backward_kernel, dim3((unsigned)((n + 3) / 4), 2), dim3(256), 0, st, (const float*)ga, a, b, norm, n, d,
                        dh1, ld1, dh2, ld2);
   }

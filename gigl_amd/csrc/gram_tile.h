@@ -1,6 +1,7 @@
 // gram_tile.h — one 64 x 64 tile of a Gram-shaped product A B^T at fp32 accuracy on the bf16 matrix cores, shared by the
 // pairwise kernels (pairwise.hip: both panels from one matrix) and the contrastive kernels (contrast.hip: the panels of two
-// matrices).  Device code only.
+// matrices) — and, for their backward kernels, the second product of a function of that tile with one of the panels' matrices
+// (gram2_*, below).  Device code only.
 #pragma once
 
 #include "split_planes.h"
@@ -79,9 +80,132 @@ __device__ __forceinline__ float16_t gram_tile(const float* __restrict__ xa, con
   return acc0;
 }
 
-// position kpos of a second product's k order -> row j of the 32-row half, when the first product was taken transposed and its
-// accumulator is the second one's A operand: register v = 8 s + t of the D layout holds row 16 s + 8 (t / 4) + 4 g + t % 4, and
-// an operand lane (., g) supplies k = 16 s + 8 g + t
+// row (of the 32 x 32 block) that register v of a lane of group g = lane / 32 holds in the D layout; the column is lane % 32
+__device__ __forceinline__ constexpr int gram_row(int v, int g) { return 8 * (v >> 2) + 4 * g + (v & 3); }
+
+// ---- the second product ---------------------------------------------------------------------------------------------------
+// acc[i][c] += W[i][j] X[j][c] for weights W that are a function of the Gram tile (the backward kernels of pairwise.hip and
+// contrast.hip), without W ever leaving the registers.  The first product is taken TRANSPOSED, gram_tile(x, own, .., J0, I0):
+// rows j, columns i.  In the D layout a lane then holds one i and sixteen j — which is, up to a fixed permutation of k, the
+// A-operand layout of the second product: register v = 8 s2 + t holds row 16 s2 + 8 (t / 4) + 4 g + t % 4 of the 32-row half
+// of j, and an operand lane (., g) supplies k = 16 s2 + 8 g + t.  So the kernel computes its weights where the Gram tile lies
+// and splits them into planes there (fa[s2][plane], eight registers each), and the permutation (bits 2 and 3 of k swapped,
+// pair_kperm) is applied to the OTHER operand, which has to be staged anyway: X_J enters LDS transposed ([column][32 kpos], a
+// thread carrying eight j of one column, as the weight-gradient kernel of agg.hip stages its operands), 64 columns at a time.
+// A wave owns one 32-row block of i (wi = wave & 1) and one 32-row half of j (wj = wave >> 1): NACC accumulators of 32 x 32
+// per 32 columns, CH / 32 of those for the workgroup's CH columns from c0; the two halves of j meet in the epilogue through
+// LDS (gram2_meet), in a fixed order.
+
+// position kpos of the second product's k order -> row j of the 32-row half
 __device__ __forceinline__ int pair_kperm(int kpos) {
   return (kpos & 0x13) | ((kpos & 4) << 1) | ((kpos & 8) >> 1);
+}
+
+// the MFMAs of one 16 k of the second product: plane of the weights, plane of the staged operand, accumulator (< NACC)
+struct gram2_sched {
+  int pa[6], pb[6], pc[6];
+};
+
+// columns [cs, cs + 64) of rows J0 .. J0 + 63 of x ([n][d] contiguous) -> s, transposed: planes 3 h + p hold half h of j as
+// [column][32 kpos] under pair_kperm.  split(x, b1, b2, b3): one element -> its three planes (as split3).  Rows >= n and
+// columns >= d enter as zeros.  Starts with a barrier (the fragments of the Gram tile / of the previous 64 columns have been
+// read) and ends with one.  By all 256 threads.
+template <typename Split>
+__device__ __forceinline__ void gram2_stage(const float* __restrict__ x, int n, int d, int J0, int cs, short (*s)[PPLANE],
+                                            Split split) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  __syncthreads();
+  const int col = cs + lane, h = wv >> 1;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int kb = (2 * (wv & 1) + q) * 8;  // this thread: kpos kb .. kb + 7 of column `col`, half h
+    float xv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int j = J0 + 32 * h + pair_kperm(kb + u);
+      xv[u] = (j < n && col < d) ? x[(int64_t)j * d + col] : 0.f;
+    }
+    uint32_t b1[8], b2[8], b3[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) split(xv[u], b1[u], b2[u], b3[u]);
+    const int o = split_lds_off(lane, kb);
+    *reinterpret_cast<uint4*>(&s[3 * h + 0][o]) = pack8(b1);
+    *reinterpret_cast<uint4*>(&s[3 * h + 1][o]) = pack8(b2);
+    *reinterpret_cast<uint4*>(&s[3 * h + 2][o]) = pack8(b3);
+  }
+  __syncthreads();
+}
+
+// the staged 64 columns times this wave's weights: acc[cb][SCH.pc[u]] += fa[s2][SCH.pa[u]] x (plane SCH.pb[u] of columns
+// 32 cb + ., kpos 16 s2 + .), the six MFMAs of a 16 k in the schedule's order, the two column blocks alternating
+template <int NACC, const gram2_sched& SCH>
+__device__ __forceinline__ void gram2_mfma(const bf16x8_t (&fa)[2][3], short (*s)[PPLANE], float16_t (*acc)[NACC]) {
+  const int lane = threadIdx.x & 63, r = lane & 31, g = lane >> 5, wj = threadIdx.x >> 7;
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2) {
+    bf16x8_t fb[2][3];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        fb[cb][p] = *reinterpret_cast<const bf16x8_t*>(&s[3 * wj + p][split_lds_off(cb * 32 + r, 16 * s2 + 8 * g)]);
+#pragma unroll
+    for (int u = 0; u < 6; ++u)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+        acc[cb][SCH.pc[u]] =
+            __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s2][SCH.pa[u]], fb[cb][SCH.pb[u]], acc[cb][SCH.pc[u]], 0, 0, 0);
+  }
+}
+
+// acc[.][.] += W (fa: this wave's weights of tile J, split) times rows J0 .. J0 + 63 of x, columns [c0, c0 + CH) below d
+template <int CH, int NACC, const gram2_sched& SCH, typename Split>
+__device__ __forceinline__ void gram2_tile(const bf16x8_t (&fa)[2][3], const float* __restrict__ x, int n, int d, int J0,
+                                           int c0, short (*s)[PPLANE], float16_t (&acc)[CH / 32][NACC], Split split) {
+#pragma unroll
+  for (int sub = 0; sub < CH / 64; ++sub) {
+    if (c0 + 64 * sub < d) {  // (the whole workgroup)
+      gram2_stage(x, n, d, J0, c0 + 64 * sub, s, split);
+      gram2_mfma<NACC, SCH>(fa, s, acc + 2 * sub);
+    }
+  }
+}
+
+// The two halves of j meet, 32 columns at a time: the waves of half 1 put their accumulators into `strip` (LDS: this wave's
+// i block's [NACC][32 rows][32 columns] floats, the same for both halves, another for the other i block), the waves of half 0
+// then call f(i, c, own, other) — row i0 + local row < n, column < d, this wave's NACC accumulator values of that element and
+// half 1's — for every element they hold.  Starts with a barrier: the strips may lie in s.  By all 256 threads.
+template <int CH, int NACC, typename F>
+__device__ __forceinline__ void gram2_meet(const float16_t (&acc)[CH / 32][NACC], float* strip, int i0, int c0, int n, int d,
+                                           F f) {
+  const int lane = threadIdx.x & 63, r = lane & 31, g = lane >> 5, wj = threadIdx.x >> 7;
+#pragma unroll
+  for (int b = 0; b < CH / 32; ++b) {
+    if (c0 + 32 * b < d) {  // (the whole workgroup)
+      __syncthreads();
+      if (wj == 1) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+#pragma unroll
+          for (int a = 0; a < NACC; ++a) strip[a * 1024 + gram_row(v, g) * 32 + r] = acc[b][a][v];
+      }
+      __syncthreads();
+      if (wj == 0) {
+        const int c = c0 + 32 * b + r;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          const int il = gram_row(v, g);
+          if (i0 + il < n && c < d) {
+            float own[NACC], other[NACC];
+#pragma unroll
+            for (int a = 0; a < NACC; ++a) {
+              own[a] = acc[b][a][v];
+              other[a] = strip[a * 1024 + il * 32 + r];
+            }
+            f(i0 + il, c, own, other);
+          }
+        }
+      }
+    }
+  }
 }

@@ -18,6 +18,7 @@
 // the sampling correction, the evaluation's rank metrics, the node-classification score pass (gigl_nc_eval_metrics).
 #include "common.h"
 #include "dispatch.h"
+#include "wave_reduce.h"
 
 #include <cfloat>
 #include <cmath>
@@ -115,20 +116,11 @@ __global__ __launch_bounds__(256) void retrieval_rows_kernel(LossArgs a0, float*
 
 // fixed-order sum of n floats into *out (one workgroup; accumulates in double)
 __global__ __launch_bounds__(1024) void sum_rows_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
-  __shared__ double s_w[16];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   v += (int64_t)blockIdx.x * n;  // (one workgroup per batch)
-  out += blockIdx.x;
   double acc = 0.0;
-  for (int i = tid; i < n; i += 1024) acc += (double)v[i];
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  if (lane == 0) s_w[w] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-    for (int k = 0; k < 16; ++k) t += s_w[k];
-    *out = (float)t;
-  }
+  for (int i = threadIdx.x; i < n; i += 1024) acc += (double)v[i];
+  const double t = gigl_block1024_sum_f64(acc);
+  if (threadIdx.x == 0) out[blockIdx.x] = (float)t;
 }
 
 // The scale of the stand-alone entries is g / temperature (g = *grad_loss or 1).  The plan (out3 != NULL: its loss words, out3[1]

@@ -14,20 +14,18 @@
 //             each, two accumulators so that dependent MFMAs alternate.  Epilogue in registers: w masked to i < j < n, lane ->
 //             wave -> workgroup sum, one double per tile pair; pair_fold_kernel adds the partials in a fixed order in fp64.
 //   backward  one workgroup per row tile I and 128-column chunk of d, sweeping EVERY column tile J (no atomics: a row's sums
-//             have one owner and one order).  The first product is taken TRANSPOSED (rows j, columns i): in the 32x32 D
-//             layout a lane then holds one i and sixteen j — which is, up to a fixed permutation of k, the A-operand layout
-//             of the second product acc[i][c] += W[i][j] Xc[j][c].  W never leaves the registers: it is split into its
-//             three planes where it lies, and the permutation (bits 2 and 3 of k swapped, pair_kperm) is applied to the
-//             OTHER operand, which has to be staged anyway: Xc_J enters LDS transposed ([column][32 j], a thread carrying
-//             eight j of one column, as the weight-gradient kernel stages its operands), 64 columns at a time.  A wave owns
-//             one 32-row block of i and one 32-row half of j: per 32 columns an exact accumulator for the one large term
-//             and one for the rest (fixed-point planes, see pair_fix3), 8 accumulators of 32 x 32 for 128 columns; the two
-//             halves of j meet in the epilogue through LDS, in a fixed order, with the plane sums of w that rebuild r_i x_i.
+//             have one owner and one order).  The weights of a tile are computed from its TRANSPOSED Gram tile, where they
+//             lie, and multiplied into Xc_J by gram_tile.h's second product (which explains the layout): acc[i][c] += W[i][j]
+//             Xc[j][c] without W leaving the registers.  Per 32 columns an exact accumulator for the one large term and one
+//             for the rest (fixed-point planes, see pair_fix3), 8 accumulators of 32 x 32 for 128 columns; the two halves
+//             of j meet in the epilogue through LDS, in a fixed order, with the plane sums of w that rebuild r_i x_i.
 //
 // Alignment.  mean_i |u_i - p_i|^alpha: one wave per row, a fixed-order fold; backward alpha |.|^(alpha - 2) (u - p) / n,
 // zero where u_i == p_i (torch's subgradient of norm).
 #include "common.h"
+#include "dispatch.h"
 #include "gram_tile.h"
+#include "wave_reduce.h"
 
 #include <cmath>
 #include <cstdint>
@@ -116,7 +114,7 @@ __global__ __launch_bounds__(256) void pair_sum_kernel(const float* __restrict__
   float sum = 0.f;
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int i = I * PT + (wv >> 1) * 32 + 8 * (v >> 2) + 4 * g + (v & 3);
+    const int i = I * PT + (wv >> 1) * 32 + gram_row(v, g);
     if (i < j && j < n) sum += expf(-t * fmaxf(0.f, (sq[i] + sqj) - 2.f * acc[v]));
   }
   double ds = (double)sum;
@@ -130,16 +128,10 @@ __global__ __launch_bounds__(256) void pair_sum_kernel(const float* __restrict__
 // reference's mean over an empty pdist
 __global__ __launch_bounds__(1024) void pair_fold_kernel(const double* __restrict__ part, int64_t np, int n,
                                                          double* __restrict__ pair_sum, float* __restrict__ loss) {
-  __shared__ double s_w[16];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   double acc = 0.0;
-  for (int64_t i = tid; i < np; i += 1024) acc += part[i];
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  if (lane == 0) s_w[w] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double S = 0.0;
-    for (int k = 0; k < 16; ++k) S += s_w[k];
+  for (int64_t i = threadIdx.x; i < np; i += 1024) acc += part[i];
+  const double S = gigl_block1024_sum_f64(acc);
+  if (threadIdx.x == 0) {
     *pair_sum = S;
     *loss = (float)log(2.0 * S / ((double)n * (double)(n - 1)));
   }
@@ -174,6 +166,8 @@ __device__ __forceinline__ void pair_fix3_bits(float x, float inv_q, uint32_t& b
   b2 = __float_as_uint(t2 * (1.f / 256.f)) & 0xFFFF0000u;
   b3 = __float_as_uint(t3 * (1.f / 65536.f)) & 0xFFFF0000u;
 }
+// (w plane, x plane): u1 t1 alone into [0]; rem's planes against t1, t2 and u1 against t2, t3 into [1], smallest first
+constexpr gram2_sched PAIR_SCHED = {{2, 1, 0, 1, 0, 0}, {0, 1, 2, 0, 1, 0}, {1, 1, 1, 1, 1, 0}};
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void pair_backward_kernel(const float* __restrict__ xc, const float* __restrict__ sq, int n,
@@ -216,7 +210,7 @@ __global__ __launch_bounds__(256) void pair_backward_kernel(const float* __restr
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int v = 8 * s2 + u;
-        const int j = J0 + wj * 32 + 8 * (v >> 2) + 4 * g + (v & 3);
+        const int j = J0 + wj * 32 + gram_row(v, g);
         float w = 0.f;
         if (j < n && i_lane < n && j != i_lane) w = expf(-t * fmaxf(0.f, (sqi + sq[j]) - 2.f * gt[v]));
         const float u1 = floorf(w * 256.f) * (1.f / 256.f), rem = w - u1;  // (both exact)
@@ -227,110 +221,41 @@ __global__ __launch_bounds__(256) void pair_backward_kernel(const float* __restr
         r_f2 += (double)__uint_as_float(b2[u]);
         r_f3 += (double)__uint_as_float(b3[u]);
       }
-      const uint4 q1 = make_uint4((b1[0] >> 16) | b1[1], (b1[2] >> 16) | b1[3], (b1[4] >> 16) | b1[5], (b1[6] >> 16) | b1[7]);
-      const uint4 q2 = make_uint4((b2[0] >> 16) | b2[1], (b2[2] >> 16) | b2[3], (b2[4] >> 16) | b2[5], (b2[6] >> 16) | b2[7]);
-      const uint4 q3 = make_uint4((b3[0] >> 16) | b3[1], (b3[2] >> 16) | b3[3], (b3[4] >> 16) | b3[5], (b3[6] >> 16) | b3[7]);
-      fa[s2][0] = __builtin_bit_cast(bf16x8_t, q1);
-      fa[s2][1] = __builtin_bit_cast(bf16x8_t, q2);
-      fa[s2][2] = __builtin_bit_cast(bf16x8_t, q3);
+      fa[s2][0] = __builtin_bit_cast(bf16x8_t, pack8(b1));
+      fa[s2][1] = __builtin_bit_cast(bf16x8_t, pack8(b2));
+      fa[s2][2] = __builtin_bit_cast(bf16x8_t, pack8(b3));
     }
-    // acc2[i][c] += W[i][j] Xc[j][c], 64 columns at a time: planes p + 3 h hold half h of j as [column][32 kpos]
-#pragma unroll
-    for (int sub = 0; sub < PCH / 64; ++sub) {
-      const int cs = c0 + 64 * sub;
-      if (cs < d) {  // (the whole workgroup)
-        __syncthreads();  // the fragments of the Gram tile / of the previous 64 columns have been read
-        const int col = cs + lane, h = wv >> 1;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int kb = (2 * (wv & 1) + q) * 8;  // this thread: kpos kb .. kb + 7 of column `col`, half h
-          uint32_t b1[8], b2[8], b3[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            const int j = J0 + 32 * h + pair_kperm(kb + u);
-            const float x = (j < n && col < d) ? xc[(int64_t)j * d + col] : 0.f;
-            pair_fix3_bits(x, inv_q, b1[u], b2[u], b3[u]);
-          }
-          const int o = split_lds_off(lane, kb);
-          *reinterpret_cast<uint4*>(&s[3 * h + 0][o]) = make_uint4((b1[0] >> 16) | b1[1], (b1[2] >> 16) | b1[3], (b1[4] >> 16) | b1[5], (b1[6] >> 16) | b1[7]);
-          *reinterpret_cast<uint4*>(&s[3 * h + 1][o]) = make_uint4((b2[0] >> 16) | b2[1], (b2[2] >> 16) | b2[3], (b2[4] >> 16) | b2[5], (b2[6] >> 16) | b2[7]);
-          *reinterpret_cast<uint4*>(&s[3 * h + 2][o]) = make_uint4((b3[0] >> 16) | b3[1], (b3[2] >> 16) | b3[3], (b3[4] >> 16) | b3[5], (b3[6] >> 16) | b3[7]);
-        }
-        __syncthreads();
-        // (w plane, x plane): u1 t1 alone into [0]; rem's planes against t1, t2 and u1 against t2, t3 into [1], smallest first
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0}, PC[6] = {1, 1, 1, 1, 1, 0};
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          bf16x8_t fb[2][3];
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-              fb[cb][p] = *reinterpret_cast<const bf16x8_t*>(&s[3 * wj + p][split_lds_off(cb * 32 + r, 16 * s2 + 8 * g)]);
-#pragma unroll
-          for (int u = 0; u < 6; ++u)
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
-              acc2[2 * sub + cb][PC[u]] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s2][PA[u]], fb[cb][PB[u]],
-                                                                                  acc2[2 * sub + cb][PC[u]], 0, 0, 0);
-        }
-      }
-    }
+    gram2_tile<PCH, 2, PAIR_SCHED>(fa, xc, n, d, J0, c0, s, acc2, [inv_q](float x, uint32_t& b1, uint32_t& b2, uint32_t& b3) {
+      pair_fix3_bits(x, inv_q, b1, b2, b3);
+    });
   }
   // epilogue: the two halves of j meet — r_i and, 32 columns at a time, the accumulators — then dx = coef (r_i xc_i - acc_i)
   r_u1 += __shfl_xor(r_u1, 32, 64);
   r_f2 += __shfl_xor(r_f2, 32, 64);
   r_f3 += __shfl_xor(r_f3, 32, 64);
   __syncthreads();
-  double* s_r = reinterpret_cast<double*>(&s[0][0]);                   // [2 halves][u1 | f2 | f3][64 rows]
+  double* s_r = reinterpret_cast<double*>(&s[0][0]);               // [2 halves][u1 | f2 | f3][64 rows]
   float* strip = reinterpret_cast<float*>(s_r + 384) + wi * 2048;  // [2 accumulators][32 rows][32 columns] per i block
-  if (g == 0) {
+  if (g == 0) {  // (published by gram2_meet's first barrier)
     s_r[wj * 192 + wi * 32 + r] = r_u1;
     s_r[wj * 192 + 64 + wi * 32 + r] = r_f2;
     s_r[wj * 192 + 128 + wi * 32 + r] = r_f3;
   }
   // (in units of q = 1 / inv_q, put back with the coefficient)
   const double coef = (double)(gout ? *gout : 1.f) * (-2.0 * (double)t / *pair_sum) / (double)inv_q;
-#pragma unroll
-  for (int b = 0; b < PCH / 32; ++b) {
-    if (c0 + 32 * b < d) {  // (the whole workgroup)
-      if (wj == 1) {
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-          strip[(8 * (v >> 2) + 4 * g + (v & 3)) * 32 + r] = acc2[b][0][v];
-          strip[1024 + (8 * (v >> 2) + 4 * g + (v & 3)) * 32 + r] = acc2[b][1][v];
-        }
-      }
-      __syncthreads();  // (the first one also publishes s_r)
-      if (wj == 0) {
-        const int c = c0 + 32 * b + r;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-          const int il = 8 * (v >> 2) + 4 * g + (v & 3), i = I0 + wi * 32 + il;
-          if (i < n && c < d) {
-            // r_i x_i rebuilt from the SAME plane products the accumulators hold (so that equal rows cancel exactly and what
-            // the products drop is dropped from a difference): the large term R1 t1 against its exact accumulator, the rest
-            // against the other one; each half of j on its own, in fp64, before the halves are added
-            float t1, t2, t3;
-            pair_fix3(xc[(int64_t)i * d + c], inv_q, t1, t2, t3);
-            const double x1 = (double)t1, x2 = (double)t2 * (1.0 / 256.0), x3 = (double)t3 * (1.0 / 65536.0);
-            const double* rr = s_r + wi * 32 + il;
-            const double h0 = (rr[0] * x1 - (double)acc2[b][0][v]) +
-                              ((rr[0] * (x2 + x3) + rr[64] * (x1 + x2) + rr[128] * x1) - (double)acc2[b][1][v]);
-            const double h1 = (rr[192] * x1 - (double)strip[il * 32 + r]) +
-                              ((rr[192] * (x2 + x3) + rr[256] * (x1 + x2) + rr[320] * x1) - (double)strip[1024 + il * 32 + r]);
-            dx[(int64_t)i * ld_dx + c] = (float)(coef * (h0 + h1));
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void pair_zero_rows_kernel(float* __restrict__ dx, int64_t ld, int n, int d) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < (int64_t)n * d) dx[(i / d) * ld + i % d] = 0.f;
+  gram2_meet<PCH, 2>(acc2, strip, I0 + wi * 32, c0, n, d, [&](int i, int c, const float (&own)[2], const float (&other)[2]) {
+    // r_i x_i rebuilt from the SAME plane products the accumulators hold (so that equal rows cancel exactly and what the
+    // products drop is dropped from a difference): the large term R1 t1 against its exact accumulator, the rest against the
+    // other one; each half of j on its own, in fp64, before the halves are added
+    float t1, t2, t3;
+    pair_fix3(xc[(int64_t)i * d + c], inv_q, t1, t2, t3);
+    const double x1 = (double)t1, x2 = (double)t2 * (1.0 / 256.0), x3 = (double)t3 * (1.0 / 65536.0);
+    const double* rr = s_r + (i - I0);
+    const double h0 = (rr[0] * x1 - (double)own[0]) + ((rr[0] * (x2 + x3) + rr[64] * (x1 + x2) + rr[128] * x1) - (double)own[1]);
+    const double h1 =
+        (rr[192] * x1 - (double)other[0]) + ((rr[192] * (x2 + x3) + rr[256] * (x1 + x2) + rr[320] * x1) - (double)other[1]);
+    dx[(int64_t)i * ld_dx + c] = (float)(coef * (h0 + h1));
+  });
 }
 
 // ---- alignment ----------------------------------------------------------------------------------------------------------
@@ -353,21 +278,13 @@ __global__ __launch_bounds__(256) void align_rows_kernel(const float* __restrict
 // *loss = mean_i norm[i]^alpha in a fixed order (one workgroup, fp64); NaN for n == 0
 __global__ __launch_bounds__(1024) void align_fold_kernel(const float* __restrict__ norm, int n, float alpha,
                                                           float* __restrict__ loss) {
-  __shared__ double s_w[16];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   double acc = 0.0;
-  for (int i = tid; i < n; i += 1024) {
+  for (int i = threadIdx.x; i < n; i += 1024) {
     const double v = (double)norm[i];
     acc += alpha == 2.f ? v * v : pow(v, (double)alpha);
   }
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  if (lane == 0) s_w[w] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-    for (int k = 0; k < 16; ++k) t += s_w[k];
-    *loss = (float)(t / (double)n);
-  }
+  const double t = gigl_block1024_sum_f64(acc);
+  if (threadIdx.x == 0) *loss = (float)(t / (double)n);
 }
 
 // du_i = gout alpha norm_i^(alpha - 2) (u_i - p_i) / n, dp_i = -du_i ([n][d] contiguous); zero rows where norm_i == 0
@@ -398,8 +315,6 @@ int32_t pair_check(gigl_ctx* ctx, int32_t n, int32_t d) {
   return GIGL_OK;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -422,15 +337,14 @@ int32_t gigl_uniformity_loss(gigl_ctx* ctx, const float* x, int64_t ld, int32_t 
   hipStream_t st = ctx->stream;
   if (n >= 2) {
     hipLaunchKernelGGL(pair_colsum_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)chunks), dim3(256), 0, st, x, ld, n, d, colsum);
-    const bool v4 = d % 4 == 0 && ld % 4 == 0 && aligned16(x) && aligned16(xc_out);
-    if (v4)
-      hipLaunchKernelGGL(pair_centre_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, st, x, ld, n, d, (const float*)colsum, chunks, xc_out, sq_out);
-    else
-      hipLaunchKernelGGL(pair_centre_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, st, x, ld, n, d, (const float*)colsum, chunks, xc_out, sq_out);
-    if (d % 4 == 0 && aligned16(xc_out))
-      hipLaunchKernelGGL(pair_sum_kernel<true>, dim3((unsigned)pairs), dim3(256), 0, st, (const float*)xc_out, (const float*)sq_out, n, d, temperature, part);
-    else
-      hipLaunchKernelGGL(pair_sum_kernel<false>, dim3((unsigned)pairs), dim3(256), 0, st, (const float*)xc_out, (const float*)sq_out, n, d, temperature, part);
+    dispatch_bool(d % 4 == 0 && ld % 4 == 0 && gigl_aligned16(x) && gigl_aligned16(xc_out), [&](auto v4) {
+      hipLaunchKernelGGL(pair_centre_kernel<decltype(v4)::value>, dim3((unsigned)tiles), dim3(256), 0, st, x, ld, n, d,
+                         (const float*)colsum, chunks, xc_out, sq_out);
+    });
+    dispatch_bool(d % 4 == 0 && gigl_aligned16(xc_out), [&](auto vec) {
+      hipLaunchKernelGGL(pair_sum_kernel<decltype(vec)::value>, dim3((unsigned)pairs), dim3(256), 0, st, (const float*)xc_out,
+                         (const float*)sq_out, n, d, temperature, part);
+    });
   }
   hipLaunchKernelGGL(pair_fold_kernel, dim3(1), dim3(1024), 0, st, (const double*)part, pairs, n, pair_sum_out, loss_out);
   GIGL_HIP_CHECK(ctx, hipGetLastError());
@@ -447,13 +361,13 @@ int32_t gigl_uniformity_loss_backward(gigl_ctx* ctx, const float* xc, const floa
   hipStream_t st = ctx->stream;
   if (n == 0) return GIGL_OK;
   if (n < 2) {
-    hipLaunchKernelGGL(pair_zero_rows_kernel, dim3((unsigned)(((int64_t)n * d + 255) / 256)), dim3(256), 0, st, dx, ld_dx, n, d);
+    gigl_zero_rows(st, dx, ld_dx, n, d);
   } else {
     const dim3 grid((unsigned)((n + PT - 1) / PT), (unsigned)((d + PCH - 1) / PCH));
-    if (d % 4 == 0 && aligned16(xc))
-      hipLaunchKernelGGL(pair_backward_kernel<true>, grid, dim3(256), 0, st, xc, sq, n, d, temperature, pair_sum, gout_dev, dx, ld_dx);
-    else
-      hipLaunchKernelGGL(pair_backward_kernel<false>, grid, dim3(256), 0, st, xc, sq, n, d, temperature, pair_sum, gout_dev, dx, ld_dx);
+    dispatch_bool(d % 4 == 0 && gigl_aligned16(xc), [&](auto vec) {
+      hipLaunchKernelGGL(pair_backward_kernel<decltype(vec)::value>, grid, dim3(256), 0, st, xc, sq, n, d, temperature, pair_sum,
+                         gout_dev, dx, ld_dx);
+    });
   }
   GIGL_HIP_CHECK(ctx, hipGetLastError());
   return GIGL_OK;

@@ -1,6 +1,7 @@
-// split_planes.h — the exact-sum split of an fp32 operand into three bf16 planes and the swizzled LDS tile the MFMA fragments
-// are read from, shared by the projection kernels (agg.hip, which describes the scheme at linear_split_kernel) and the
-// pairwise kernels (pairwise.hip).  Device code only.
+// split_planes.h — the exact-sum split of an fp32 operand into three bf16 planes, the packing of a plane's bf16 values and the
+// swizzled LDS tile the MFMA fragments are read from, shared by the projection and weight-gradient kernels (agg.hip, which
+// describes the scheme at linear_split_kernel) and, through gram_tile.h, the pairwise kernels (pairwise.hip) and the
+// contrastive kernels (contrast.hip).  Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -31,4 +32,19 @@ __device__ __forceinline__ void split_store(const float4_t v, short* p1, short* 
   *reinterpret_cast<uint2*>(p1) = make_uint2((a1[0] >> 16) | a1[1], (a1[2] >> 16) | a1[3]);
   *reinterpret_cast<uint2*>(p2) = make_uint2((a2[0] >> 16) | a2[1], (a2[2] >> 16) | a2[3]);
   *reinterpret_cast<uint2*>(p3) = make_uint2((a3[0] >> 16) | a3[1], (a3[2] >> 16) | a3[3]);
+}
+
+// eight plane values (each a float's bits with the low 16 cleared, split3's b) -> their bf16 halves, in order, as 16 bytes
+__device__ __forceinline__ uint4 pack8(const uint32_t (&b)[8]) {
+  return make_uint4((b[0] >> 16) | b[1], (b[2] >> 16) | b[3], (b[4] >> 16) | b[5], (b[6] >> 16) | b[7]);
+}
+
+// eight floats -> the three bf16 planes of a fragment (or of 16 bytes of a plane in LDS)
+__device__ __forceinline__ void split8(const float (&x)[8], bf16x8_t& f1, bf16x8_t& f2, bf16x8_t& f3) {
+  uint32_t b1[8], b2[8], b3[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) split3(x[u], b1[u], b2[u], b3[u]);
+  f1 = __builtin_bit_cast(bf16x8_t, pack8(b1));
+  f2 = __builtin_bit_cast(bf16x8_t, pack8(b2));
+  f3 = __builtin_bit_cast(bf16x8_t, pack8(b3));
 }

@@ -20,6 +20,19 @@ __device__ __forceinline__ double gigl_wave_sum_f64(double v) {
   return v;
 }
 
+// One fp64 value per thread of a 1024-thread workgroup -> their total, in thread 0 ONLY (0 elsewhere): the sixteen waves'
+// gigl_wave_sum_f64 through LDS, added by thread 0 in wave order.  Called by all threads, once per kernel.
+__device__ __forceinline__ double gigl_block1024_sum_f64(double v) {
+  __shared__ double s_w[16];
+  v = gigl_wave_sum_f64(v);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x == 0)
+    for (int k = 0; k < 16; ++k) t += s_w[k];
+  return t;
+}
+
 __device__ __forceinline__ float gigl_wave_reduce16(const float (&p)[16]) {
   typedef unsigned int gigl_u2 __attribute__((ext_vector_type(2)));
   auto f2u = [](float x) { return __builtin_bit_cast(unsigned, x); };

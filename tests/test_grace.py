@@ -70,7 +70,8 @@ def check(h1, h2, t):
 
 
 SHAPES = [(n, d) for n in (1, 2, 3, 63, 64, 65, 129, 257) for d in (16, 30)] + \
-         [(n, d) for n in (65, 129) for d in (1, 4, 36, 260)]
+         [(n, d) for n in (65, 129) for d in (1, 4, 36, 260)] + \
+         [(65, 100), (65, 97), (65, 512)]  # a partly filled 64-column group and 32-column block of the backward; the widest rows
 
 
 @gpu
