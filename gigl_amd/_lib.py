@@ -84,6 +84,8 @@ SYMBOLS = [
     "gigl_nc_eval_metrics",
     "gigl_uniformity_loss", "gigl_uniformity_loss_backward", "gigl_alignment_loss", "gigl_alignment_loss_backward",
     "gigl_grace_loss", "gigl_grace_loss_backward",
+    "gigl_gbt_loss", "gigl_gbt_loss_backward", "gigl_whitening_loss", "gigl_whitening_loss_backward",
+    "gigl_correlate_chunk_rows",
 ]
 
 KERNEL_IDS = {
@@ -376,6 +378,11 @@ def load() -> C.CDLL:
         "gigl_alignment_loss_backward": [vp, vp, i64, vp, i64, i32, i32, C.c_float, vp, vp, vp, vp],
         "gigl_grace_loss": [vp, vp, i64, vp, i64, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp],
         "gigl_grace_loss_backward": [vp, vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, i64, vp, i64],
+        "gigl_gbt_loss": [vp, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp],
+        "gigl_gbt_loss_backward": [vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, i64],
+        "gigl_whitening_loss": [vp, vp, i64, vp, i64, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp, vp],
+        "gigl_whitening_loss_backward": [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, i64],
+        "gigl_correlate_chunk_rows": [i32, i32, i32],
         "gigl_gather_mean_backward": [vp, vp, i32, vp, vp, vp, vp, i64, vp],
         "gigl_gather_mean_backward_transposed": [vp, vp, i32, vp, vp, vp, vp, i64, vp, i64, i64, i32, vp],
         "gigl_transposed_rows_build": [vp, vp, vp, vp, vp, i64, vp, i64, i64, vp],

@@ -73,6 +73,10 @@ class UnionGraph:
 _DEFAULT_ENGINES = {}
 
 
+# rows of the shortest chunk but the last of the split-K correlation sweep (CORR_MIN_CHUNK, csrc/correlate.hip)
+CORRELATE_MIN_CHUNK_ROWS = 64
+
+
 def default_engine(device) -> "HipEngine":
     """one shared ctx per device for the stateless ops (loss, decoder) that the reference calls as free functions;
     bound to torch's current stream of that device at every use"""
@@ -1240,6 +1244,61 @@ class HipEngine:
         check(self._lib.gigl_grace_loss_backward(self._ctx, p(a), p(b), p(norm), p(lse), n, d, float(temperature), p(grad_loss),
                                                  p(dh1), d, p(dh2), d), self._ctx)
         return dh1, dh2
+
+    def correlate_chunk_rows(self, n: int, d: int, products: int) -> int:
+        """rows per chunk of the split-K correlation sweep (products: 1 GBT, 2 whitening): gigl_correlate_chunk_rows"""
+        return int(self._lib.gigl_correlate_chunk_rows(int(n), int(d), int(products)))
+
+    def _correlation_loss(self, h1: torch.Tensor, h2: torch.Tensor, lambd: Optional[float]):
+        """-> (loss [] fp32, saved, stat): gigl_gbt_loss (lambd None) or gigl_whitening_loss; saved = (z [2, npad, d], m [2, dpad,
+        d], colv [2, 2, d], coef [8]) and, for whitening, dz [n, d] — what the backward reads; stat [2, 2, d] fp64: per view
+        the columns' s, then rinv"""
+        h1, h2 = self._embedding_rows(h1), self._embedding_rows(h2)
+        assert h1.shape == h2.shape
+        n, d = int(h1.shape[0]), int(h1.shape[1])
+        dev = self.device
+        new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+        z, m = new(2, (n + 63) // 64 * 64, d), new(2, (d + 63) // 64 * 64, d)
+        stat, colv, coef, loss = new(2, 2, d, dtype=torch.float64), new(2, 2, d), new(8), new()
+        p = lambda t: C.c_void_p(t.data_ptr())
+        head = (self._ctx, p(h1), int(h1.stride(0)), p(h2), int(h2.stride(0)), n, d)
+        if lambd is None:
+            check(self._lib.gigl_gbt_loss(*head, p(z), p(m), p(stat), p(colv), p(coef), p(loss)), self._ctx)
+            saved = (z, m, colv, coef)
+        else:
+            dz = new(n, d)
+            check(self._lib.gigl_whitening_loss(*head, float(lambd), p(z), p(dz), p(m), p(stat), p(colv), p(coef), p(loss)),
+                  self._ctx)
+            saved = (z, m, colv, coef, dz)
+        return loss, saved, stat
+
+    def _correlation_loss_backward(self, saved, n: int, grad_loss):
+        z, m, colv, coef = saved[:4]
+        d = int(z.shape[2])
+        dh1, dh2 = (torch.empty((n, d), dtype=torch.float32, device=self.device) for _ in range(2))
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        tail = (p(colv), p(coef), n, d, p(grad_loss), p(dh1), d, p(dh2), d)
+        if len(saved) == 4:
+            check(self._lib.gigl_gbt_loss_backward(self._ctx, p(z), p(m), *tail), self._ctx)
+        else:
+            check(self._lib.gigl_whitening_loss_backward(self._ctx, p(z), p(saved[4]), p(m), *tail), self._ctx)
+        return dh1, dh2
+
+    def gbt_loss(self, z_a: torch.Tensor, z_b: torch.Tensor):
+        """-> (loss, saved, stat): gigl_gbt_loss"""
+        return self._correlation_loss(z_a, z_b, None)
+
+    def gbt_loss_backward(self, saved, n: int, grad_loss):
+        """-> (dz_a, dz_b) [n, d]: gigl_gbt_loss_backward"""
+        return self._correlation_loss_backward(saved, n, grad_loss)
+
+    def whitening_loss(self, h1: torch.Tensor, h2: torch.Tensor, lambd: float):
+        """-> (loss, saved, stat): gigl_whitening_loss"""
+        return self._correlation_loss(h1, h2, float(lambd))
+
+    def whitening_loss_backward(self, saved, n: int, grad_loss):
+        """-> (dh1, dh2) [n, d]: gigl_whitening_loss_backward"""
+        return self._correlation_loss_backward(saved, n, grad_loss)
 
     def alignment_loss(self, u: torch.Tensor, v: torch.Tensor, alpha: float):
         """-> (loss [] fp32, norm [n]): gigl_alignment_loss"""

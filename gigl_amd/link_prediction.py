@@ -10,6 +10,7 @@ Mirror of (paths relative to the reference root):
       calculate_batch_retrieval_loss :209-277, _mask_by_query_ids :279-305, _mask_by_candidate_ids :307-331
   AligmentLoss, UniformityLoss         python/gigl/src/common/models/layers/loss.py:591-626  (csrc/pairwise.hip)
   GRACELoss                            python/gigl/src/common/models/layers/loss.py:362-416  (csrc/contrast.hip)
+  WhiteningDecorrelationLoss, GBTLoss  python/gigl/src/common/models/layers/loss.py:444-534  (csrc/correlate.hip)
 The loss is one fused device pass over the score matrix (csrc/loss.hip: temperature, sampling-probability correction,
 both masks, log-softmax and the summed cross-entropy, plus its backward), pinned by the reference's known-answer tests
 (tests/test_link_prediction.py restates loss_test.py:61-166 and decoder_test.py:44-62).
@@ -349,3 +350,59 @@ class GRACELoss(nn.Module):
         if h1.shape != h2.shape:
             raise ValueError(f"GRACELoss: {tuple(h1.shape)} rows of view 1 against {tuple(h2.shape)} of view 2")
         return _FusedGrace.apply(h1, h2, default_engine(h1.device), self.temperature), 1
+
+
+class _FusedCorrelation(torch.autograd.Function):
+    """two views' rows -> GBTLoss (lambd None) or WhiteningDecorrelationLoss (csrc/correlate.hip: column statistics in fp64, the
+    d x d correlation as a split-K MFMA product, loss and dL/dC from the folded tiles); backward = one Gram-shaped product per
+    view with the standardisation's gradient in its epilogue"""
+
+    @staticmethod
+    def forward(ctx, h1, h2, eng, lambd):
+        loss, saved, _ = eng.gbt_loss(h1, h2) if lambd is None else eng.whitening_loss(h1, h2, lambd)
+        ctx.eng, ctx.n, ctx.gbt = eng, int(h1.shape[0]), lambd is None
+        ctx.save_for_backward(*saved)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        back = ctx.eng.gbt_loss_backward if ctx.gbt else ctx.eng.whitening_loss_backward
+        dh1, dh2 = back(ctx.saved_tensors, ctx.n, g.to(torch.float32).contiguous())
+        return dh1, dh2, None, None
+
+
+def _two_views(h1: torch.Tensor, h2: torch.Tensor, who: str):
+    h1, h2 = _device_rows(h1, who), _device_rows(h2, who)
+    if h1.shape != h2.shape:
+        raise ValueError(f"{who}: {tuple(h1.shape)} rows of view 1 against {tuple(h2.shape)} of view 2")
+    return h1, h2
+
+
+class GBTLoss(nn.Module):
+    """The reference's GBTLoss (loss.py:491-534), graph Barlow Twins: with both views' columns standardised (mean, unbiased
+    std + 1e-15) and C = z_a^T z_b / n, sum_a (1 - C_aa)^2 + (1 / d) sum_{a != b} C_ab^2 — one fused pass (gigl_gbt_loss).
+    forward -> (loss, 1).  A constant column gets z = 0 as in the reference and a zero gradient where the reference's autograd
+    gives NaN.  Device tensors only; n >= 2, d <= 512."""
+
+    def forward(self, z_a: torch.Tensor, z_b: torch.Tensor, device: Optional[torch.device] = None):
+        from .engine import default_engine
+        z_a, z_b = _two_views(z_a, z_b, "GBTLoss")
+        return _FusedCorrelation.apply(z_a, z_b, default_engine(z_a.device), None), 1
+
+
+class WhiteningDecorrelationLoss(nn.Module):
+    """The reference's WhiteningDecorrelationLoss (loss.py:444-488), CCA-SSG: with z_k the standardised views and c_k = z_k^T z_k
+    / N, |z1 - z2|_F / N + lambd (|I - c1|_F + |I - c2|_F) — one fused pass (gigl_whitening_loss), fp32 (the reference's loss is
+    fp64 because its identity matrix is).  forward -> (loss, 1); N must be the row count.  A constant column, where the
+    reference's loss is NaN, enters as z = 0 and receives a zero gradient.  Device tensors only; n >= 2, d <= 512."""
+
+    def __init__(self, lambd: float = 1e-3):
+        super().__init__()
+        self.lambd = float(lambd)
+
+    def forward(self, h1: torch.Tensor, h2: torch.Tensor, N: int, device: Optional[torch.device] = None):
+        from .engine import default_engine
+        h1, h2 = _two_views(h1, h2, "WhiteningDecorrelationLoss")
+        if int(N) != h1.shape[0]:
+            raise ValueError(f"WhiteningDecorrelationLoss: N={N} is not the number of rows ({h1.shape[0]})")
+        return _FusedCorrelation.apply(h1, h2, default_engine(h1.device), self.lambd), 1

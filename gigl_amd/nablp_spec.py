@@ -16,10 +16,11 @@ retrieval loss over the [queries x candidates] score matrix (gigl_retrieval_loss
 sampling correction when enabled).
 Scope: homogeneous graphs (one condensed node type / edge type) and heterogeneous ones (typed batches through the
 native typed collate, HGT / SimpleHGN encoders, first supervision edge type: spec :245-271, infer.py on HeteroData); the
-Retrieval, Margin, Softmax, DirectAU and GRACE tasks (DirectAU and GRACE through the autograd loop: their losses read
-embeddings, not the score matrix the training plans' head works on; GRACE, the first task over the input batch — two
-augmented views, task.py:212-279 — on homogeneous TFRecord batches in one process) — the other augmentation-based
-self-supervised ones (WhiteningDecorrelation, GBT, BGRL, TBGRL, FeatureReconstruction) are not built.
+Retrieval, Margin, Softmax, DirectAU, GRACE, WhiteningDecorrelation and GBT tasks (DirectAU and the last three through the
+autograd loop: their losses read embeddings, not the score matrix the training plans' head works on; GRACE,
+WhiteningDecorrelation and GBT are the tasks over the input batch — two augmented views, task.py:212-279, :351-480 — on
+homogeneous TFRecord batches in one process) — the other augmentation-based self-supervised ones (BGRL, TBGRL,
+FeatureReconstruction: row-wise cosine losses) are not built.
 Data: main samples are the NodeAnchorBasedLinkPredictionSample TFRecords and random negatives the
 RootedNodeNeighborhood TFRecords the sampler wrote, re-filed into train/val/test by the split generator
 (gigl_amd/split_generator.py; datasetMetadata.nodeAnchorBasedLinkPredictionDataset URIs).  Without split outputs
@@ -43,8 +44,8 @@ from .base import (BaseInferencer, BaseTrainer, EvalMetric, EvalMetricsCollectio
                    hit_rate_at_k, import_obj, mean_reciprocal_rank, no_grad_eval)
 from .batches import NodeAnchorBasedLinkPredictionBatch, RootedNodeNeighborhoodBatch, iterate_tfrecord_batches
 from .config import GbmlConfigPbWrapper, tfrecord_files
-from .link_prediction import (AligmentLoss, GRACELoss, LinkPredictionDecoder, LinkPredictionGNN, RetrievalLoss,
-                              UniformityLoss)
+from .link_prediction import (AligmentLoss, GBTLoss, GRACELoss, LinkPredictionDecoder, LinkPredictionGNN, RetrievalLoss,
+                              UniformityLoss, WhiteningDecorrelationLoss)
 from .models import GraphSAGE
 from .task_specs import _dropout_arg, _rank_world
 
@@ -436,21 +437,20 @@ class DirectAU(nn.Module):
         return running_loss, 1
 
 
-class GRACE(nn.Module):
-    """task.py:212-279: two corrupted views of the main batch's graph (augmentations.get_augmented_graph), both encoded by
-    the job's encoder, the roots' rows through a task head Linear(out, hid) -> ReLU -> Linear(hid, out) (on gigl_linear), and
-    the two-view contrastive loss (GRACELoss, csrc/contrast.hip).  forward -> (loss, 1).
+class _TwoViewTask(nn.Module):
+    """What the tasks over the input batch share (task.py:212-279, :351-480): two corrupted views of the main batch's graph
+    (augmentations.get_augmented_graph), both encoded by the job's encoder, the roots' rows — through a task head Linear(out,
+    hid) -> ReLU -> Linear(hid, out) (on gigl_linear) where the task has one (with_head).
     The encoder is the model's own: it is bound after construction (bind_encoder; init_model does it) and held WITHOUT being
     registered as a submodule, so that its parameters appear once in a state dict; the head is built then.
     View 1 drops features with feat_drop_1: the reference passes edge_drop_2 there (task.py:252), an evident slip.
     Homogeneous GraphData batches only (the TFRecord route); `seed` starts the augmentations' own generator."""
-    task_name = "GRACE"
     result_types = ("input_batch",)
+    with_head = True
 
-    def __init__(self, encoder: Optional[nn.Module] = None, temperature: float = 0.001, feat_drop_1: float = 0.3,
-                 edge_drop_1: float = 0.3, feat_drop_2: float = 0.3, edge_drop_2: float = 0.3, seed: int = 0):
+    def __init__(self, encoder: Optional[nn.Module], feat_drop_1: float, edge_drop_1: float, feat_drop_2: float,
+                 edge_drop_2: float, seed: int):
         super().__init__()
-        self.loss = GRACELoss(temperature=temperature)
         self.feat_drop_1, self.edge_drop_1 = float(feat_drop_1), float(edge_drop_1)
         self.feat_drop_2, self.edge_drop_2 = float(feat_drop_2), float(edge_drop_2)
         self._generator = torch.Generator().manual_seed(int(seed))
@@ -461,26 +461,28 @@ class GRACE(nn.Module):
 
     def bind_encoder(self, encoder: nn.Module) -> None:
         self._encoder_ref = (encoder,)
-        if self.head is None:
+        if self.head is None and self.with_head:
             hid_dim, out_dim = int(encoder.hid_dim), int(encoder.out_dim)
             self.head = nn.Sequential(nn.Linear(out_dim, hid_dim), nn.ReLU(), nn.Linear(hid_dim, out_dim))
 
     def _apply_head(self, x: torch.Tensor) -> torch.Tensor:
         from .engine import default_engine
         from .models_hetero import _linear
+        if self.head is None:
+            return x
         eng = default_engine(x.device)
         hidden = torch.relu(_linear(eng, x, self.head[0].weight, self.head[0].bias))
         return _linear(eng, hidden, self.head[2].weight, self.head[2].bias)
 
-    def forward(self, task_input: NodeAnchorBasedLinkPredictionTaskInputs, gbml_config_pb_wrapper=None,
-                should_eval: bool = False, device: torch.device = torch.device("cpu")):
+    def _views(self, task_input: NodeAnchorBasedLinkPredictionTaskInputs, device: torch.device):
+        """-> the roots' rows of both views, through the head"""
         from .augmentations import get_augmented_graph
         from .nn import GraphData
         if not self._encoder_ref:
-            raise RuntimeError("GRACE: no encoder is bound (bind_encoder; the task spec's init_model does it)")
+            raise RuntimeError(f"{self.task_name}: no encoder is bound (bind_encoder; the task spec's init_model does it)")
         main_batch = task_input.main_batch
         if not isinstance(main_batch.graph, GraphData):
-            raise NotImplementedError(f"GRACE augments homogeneous GraphData batches (the TFRecord route), not "
+            raise NotImplementedError(f"{self.task_name} augments homogeneous GraphData batches (the TFRecord route), not "
                                       f"{type(main_batch.graph).__name__}")
         graph = main_batch.graph.to(device)
         roots = main_batch.root_node_indices.to(device)
@@ -488,7 +490,56 @@ class GRACE(nn.Module):
         for edge_drop, feat_drop in ((self.edge_drop_1, self.feat_drop_1), (self.edge_drop_2, self.feat_drop_2)):
             view = get_augmented_graph(graph, edge_drop_ratio=edge_drop, feat_drop_ratio=feat_drop, generator=self._generator)
             views.append(self._apply_head(self._encoder_ref[0](view)[roots]))
-        return self.loss(h1=views[0], h2=views[1], device=device)
+        return views
+
+
+class GRACE(_TwoViewTask):
+    """task.py:212-279: the two views' head outputs (_TwoViewTask) under the two-view contrastive loss (GRACELoss,
+    csrc/contrast.hip).  forward -> (loss, 1)."""
+    task_name = "GRACE"
+
+    def __init__(self, encoder: Optional[nn.Module] = None, temperature: float = 0.001, feat_drop_1: float = 0.3,
+                 edge_drop_1: float = 0.3, feat_drop_2: float = 0.3, edge_drop_2: float = 0.3, seed: int = 0):
+        super().__init__(encoder, feat_drop_1, edge_drop_1, feat_drop_2, edge_drop_2, seed)
+        self.loss = GRACELoss(temperature=temperature)
+
+    def forward(self, task_input: NodeAnchorBasedLinkPredictionTaskInputs, gbml_config_pb_wrapper=None,
+                should_eval: bool = False, device: torch.device = torch.device("cpu")):
+        h1, h2 = self._views(task_input, device)
+        return self.loss(h1=h1, h2=h2, device=device)
+
+
+class WhiteningDecorrelation(_TwoViewTask):
+    """task.py:351-418 (CCA-SSG): the two views' head outputs under WhiteningDecorrelationLoss (csrc/correlate.hip), N the
+    number of roots.  forward -> (loss, 1)."""
+    task_name = "WhiteningDecorrelation"
+
+    def __init__(self, encoder: Optional[nn.Module] = None, lambd: float = 1e-3, feat_drop_1: float = 0.2,
+                 edge_drop_1: float = 0.2, feat_drop_2: float = 0.2, edge_drop_2: float = 0.2, seed: int = 0):
+        super().__init__(encoder, feat_drop_1, edge_drop_1, feat_drop_2, edge_drop_2, seed)
+        self.loss = WhiteningDecorrelationLoss(lambd=lambd)
+
+    def forward(self, task_input: NodeAnchorBasedLinkPredictionTaskInputs, gbml_config_pb_wrapper=None,
+                should_eval: bool = False, device: torch.device = torch.device("cpu")):
+        h1, h2 = self._views(task_input, device)
+        return self.loss(h1=h1, h2=h2, N=h1.shape[0], device=device)
+
+
+class GBT(_TwoViewTask):
+    """task.py:421-480 (graph Barlow Twins): the two views' encoder rows, no head, under GBTLoss (csrc/correlate.hip).
+    forward -> (loss, 1)."""
+    task_name = "GBT"
+    with_head = False
+
+    def __init__(self, encoder: Optional[nn.Module] = None, feat_drop_1: float = 0.2, edge_drop_1: float = 0.2,
+                 feat_drop_2: float = 0.2, edge_drop_2: float = 0.2, seed: int = 0):
+        super().__init__(encoder, feat_drop_1, edge_drop_1, feat_drop_2, edge_drop_2, seed)
+        self.loss = GBTLoss()
+
+    def forward(self, task_input: NodeAnchorBasedLinkPredictionTaskInputs, gbml_config_pb_wrapper=None,
+                should_eval: bool = False, device: torch.device = torch.device("cpu")):
+        z_a, z_b = self._views(task_input, device)
+        return self.loss(z_a=z_a, z_b=z_b, device=device)
 
 
 class NodeAnchorBasedLinkPredictionTasks:
@@ -610,6 +661,10 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             offered = {"temperature": float(kwargs.get("grace_temperature", 0.001)),
                        "seed": int(kwargs.get("augment_seed", 0)),
                        **{k: float(kwargs.get(k, 0.3)) for k in ("feat_drop_1", "edge_drop_1", "feat_drop_2", "edge_drop_2")}}
+        if isinstance(task_cls, type) and issubclass(task_cls, (GBT, WhiteningDecorrelation)):
+            # (the reference tasks' defaults: lambd 1e-3, drop ratios 0.2)
+            offered = {"lambd": float(kwargs.get("wd_lambd", 1e-3)), "seed": int(kwargs.get("augment_seed", 0)),
+                       **{k: float(kwargs.get(k, 0.2)) for k in ("feat_drop_1", "edge_drop_1", "feat_drop_2", "edge_drop_2")}}
         takes = inspect.signature(task_cls.__init__).parameters
         # (the reference passes temperature / remove_accidental_hits to whatever class task_path names — its Margin and
         # Softmax tasks cannot be built that way; here every task gets the arguments its constructor declares)
@@ -664,13 +719,15 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             in_dim=max(in_dim, 1), hid_dim=self.hidden_dim, out_dim=self.out_channels, num_layers=self.num_layers,
             should_l2_normalize_embedding_layer_output=self.should_l2_normalize_embedding_layer_output, **extra)
         model = LinkPredictionGNN(encoder=encoder, decoder=LinkPredictionDecoder())
-        # tasks that encode the input batch themselves (result type input_batch: GRACE) get the model's encoder, and their
-        # heads become part of the model, `task_heads.<task name>`: one parameter list for the optimiser, one state dict
+        # tasks that encode the input batch themselves (result type input_batch: GRACE, WhiteningDecorrelation, GBT) get the
+        # model's encoder, and the heads of those that have one become part of the model, `task_heads.<task name>`: one
+        # parameter list for the optimiser, one state dict
         heads = {}
         for task in self.tasks._task_to_fn_map.values():
             if hasattr(task, "bind_encoder"):
                 task.bind_encoder(encoder)
-                heads[task.task_name] = task.head
+                if task.head is not None:
+                    heads[task.task_name] = task.head
         if heads:
             model.task_heads = nn.ModuleDict(heads)
         if state_dict is not None:
@@ -690,7 +747,8 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         encoder class (gnn_model_class_path; default HGT) takes the per-type feature dims, hid / out dims, num_layers,
         num_heads"""
         if "input_batch" in self.tasks.result_types:
-            raise NotImplementedError("tasks over the input batch (GRACE) are built for homogeneous graphs only")
+            raise NotImplementedError("tasks over the input batch (GRACE, WhiteningDecorrelation, GBT) are built for homogeneous "
+                                      "graphs only")
         pm = cfg.preprocessed_metadata
         node_dims = {name: max(pm.nodes[c].feature_dim, 1) for c, name in cfg.condensed_node_type_map.items()}
         edge_dims = {tuple(t): pm.edges[c].feature_dim for c, t in cfg.condensed_edge_type_map.items()}
@@ -745,10 +803,11 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             return self._hbm_anchors or None
         self._hbm_anchors = {}
         if "input_batch" in self.tasks.result_types:
-            # (GRACE augments the batch's GraphData; the batch graph of the in-HBM route is not one)
+            # (these tasks augment the batch's GraphData; the batch graph of the in-HBM route is not one)
             import os
             if (self._kwargs.get("data_route") or os.environ.get("GIGL_AMD_ROUTE") or "auto").lower() == "hbm":
-                raise ValueError("data_route hbm cannot serve a task over the input batch (GRACE): it takes the TFRecord route")
+                raise ValueError("data_route hbm cannot serve a task over the input batch (GRACE, WhiteningDecorrelation, GBT): it "
+                                 "takes the TFRecord route")
             return None
         from .hbm import ResidentGraph, encoder_trains_over_graph_data, encoder_trains_over_hip_batches, route_of
         device = getattr(self, "_device", None)
@@ -1163,8 +1222,8 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         cfg = gbml_config_pb_wrapper
         _, world = _rank_world()
         if world > 1 and "input_batch" in self.tasks.result_types:
-            raise NotImplementedError("tasks over the input batch (GRACE) train in one process: the data-parallel wrapper's "
-                                      "forward does not run their heads")
+            raise NotImplementedError("tasks over the input batch (GRACE, WhiteningDecorrelation, GBT) train in one process: the "
+                                      "data-parallel wrapper's forward does not run their heads")
         plan = self._library_train_plan(cfg)
         if plan is not None:
             try:

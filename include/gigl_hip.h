@@ -1185,6 +1185,42 @@ int32_t gigl_grace_loss_backward(gigl_ctx* ctx, const float* a, const float* b, 
                                  int32_t d, float temperature, const float* gout_dev, float* dh1, int64_t ld1, float* dh2,
                                  int64_t ld2);
 
+/* ---- the two losses over the d x d correlation of two column-standardised views (csrc/correlate.hip): GBTLoss (python/gigl/
+ *      src/common/models/layers/loss.py:491-534) and WhiteningDecorrelationLoss (loss.py:444-488).  All pointers DEVICE; the
+ *      work is issued on the ctx's stream, nothing synchronises the host, nothing of size n x n is written, no atomics;
+ *      results are bit-reproducible run to run.  2 <= n <= 2^18, 1 <= d <= 512 (GIGL_E_INVALID_ARG with a message beyond).
+ * h1, h2 [n][d] fp32, rows ld1 / ld2 floats apart.  Per view and column: mean, unbiased standard deviation s (fp64, fixed
+ * order, mean first, then centred squares), z = (x - mean) rinv, rinv = 1 / (s + 1e-15) (GBT) or 1 / s (whitening); a column
+ * with s == 0 gets z = 0 and a zero gradient in both modes (GBT: the reference's forward value, where its autograd gradient
+ * is NaN; whitening: the reference's forward is NaN).  With npad, dpad = n, d rounded up to 64, the outputs the backward reads:
+ *   z_out [2][npad][d] (view 1, then view 2; padding rows zero), m_out [2][dpad][d] (dL/dC and its transpose for GBT, I - c_1
+ *   and I - c_2 for whitening; padding rows zero), colv_out [2][2][d] (per view: rinv, then r_a (s + eps) / (s (n - 1)) with
+ *   r_a = sum_i dL/dz_ia z_ia), coef_out [8] (alpha_1, alpha_2, beta of dL/dz = alpha_v src M_v^T + beta (z_v - z_other),
+ *   then |z1 - z2|_F / N, |I - c1|_F, |I - c2|_F), and for whitening dz_out [n][d] = z1 - z2 taken before rounding.
+ *   stat_out [2][2][d] doubles: per view s, then rinv.  Partial tiles and sums come from the ctx's arena (at most
+ *   512 x 16 KB of tiles for GBT, less than twice that for whitening).
+ * gigl_gbt_loss (loss.py:491-534): C = z1^T z2 / n, *loss_out = sum_a (1 - C_aa)^2 + (1 / d) sum_{a != b} C_ab^2. */
+int32_t gigl_gbt_loss(gigl_ctx* ctx, const float* h1, int64_t ld1, const float* h2, int64_t ld2, int32_t n, int32_t d,
+                      float* z_out, float* m_out, double* stat_out, float* colv_out, float* coef_out, float* loss_out);
+/* The gradient of gigl_gbt_loss (loss.py:491-534: autograd through :524-533 in the reference) scaled by *gout_dev (NULL: 1), to
+ * dh1 / dh2 [n][d], rows ld1 / ld2 floats apart.  z, m, colv, coef: the forward's outputs.  n == 2: zeros (a standardised
+ * column of two rows is +-1 / sqrt 2 whatever the rows: the loss is locally constant). */
+int32_t gigl_gbt_loss_backward(gigl_ctx* ctx, const float* z, const float* m, const float* colv, const float* coef, int32_t n,
+                               int32_t d, const float* gout_dev, float* dh1, int64_t ld1, float* dh2, int64_t ld2);
+/* gigl_whitening_loss (loss.py:444-488): c_k = z_k^T z_k / N, *loss_out = |z1 - z2|_F / N + lambd (|I - c1|_F + |I - c2|_F), N
+ * = n; fp32 (the reference's is fp64 because its identity matrix is). */
+int32_t gigl_whitening_loss(gigl_ctx* ctx, const float* h1, int64_t ld1, const float* h2, int64_t ld2, int32_t n, int32_t d,
+                            float lambd, float* z_out, float* dz_out, float* m_out, double* stat_out, float* colv_out,
+                            float* coef_out, float* loss_out);
+/* The gradient of gigl_whitening_loss (loss.py:444-488: autograd through :474-488 in the reference), as
+ * gigl_gbt_loss_backward; a zero norm (identical standardised views, c_k = I) contributes zeros, not NaN. */
+int32_t gigl_whitening_loss_backward(gigl_ctx* ctx, const float* z, const float* dz, const float* m, const float* colv,
+                                     const float* coef, int32_t n, int32_t d, const float* gout_dev, float* dh1, int64_t ld1,
+                                     float* dh2, int64_t ld2);
+/* Rows per chunk of the split-K sweep behind both losses (products: 1 for GBT, 2 for whitening), a pure function of its
+ * arguments: ceil(n / rows) chunks, all but the last at least 64 rows; 0 for arguments out of range. */
+int32_t gigl_correlate_chunk_rows(int32_t n, int32_t d, int32_t products);
+
 /* ---- rank metrics of a score matrix: MRR and hits@k of every anchor's positives among the random negatives, one wave per
  *      anchor, summed on the device.  Replaces hit_rate_at_k / mean_reciprocal_rank (python/gigl/src/common/utils/
  *      eval_metrics.py:6-73) as the trainer's validate() calls them once per anchor (node_anchor_based_link_prediction_
