@@ -2,7 +2,8 @@
 
 Mirror of python/gigl/src/common/models/pyg/graph/augmentations.py:6-57 (drop_feature, get_augmented_graph): every edge is
 kept with probability 1 - edge_drop_ratio (PyG dropout_edge), self loops are removed and one self loop per node is added,
-and whole feature columns are zeroed with probability feat_drop_ratio.  Plain torch ops on whatever device the graph is
+and whole feature columns are zeroed with probability feat_drop_ratio; graph_perm (TBGRL's negative view) first shuffles the
+rows of x and redraws every edge's ends.  Plain torch ops on whatever device the graph is
 on: O(E + n D) per view, not the hot path.  `generator` makes the draws reproducible (the reference uses the global one).
 """
 from __future__ import annotations
@@ -37,14 +38,18 @@ def get_augmented_graph(graph: GraphData, edge_drop_ratio: float = 0.3, feat_dro
         raise ValueError(f"Invalid probability provided for Edge Drop, got {edge_drop_ratio}")
     if feat_drop_ratio < 0 or feat_drop_ratio > 1:
         raise ValueError(f"Invalid probability provided for Feat Drop, got {feat_drop_ratio}")
-    if graph_perm:
-        raise NotImplementedError("graph_perm is not built: GRACE does not use it")
     if graph.edge_attr is not None:
         # (the reference masks edge_attr by the dropped edges and then rewrites the self loops of edge_index alone: the two
         # end up with different lengths)
         raise NotImplementedError("get_augmented_graph over a graph with edge_attr is not built")
     x, ei = graph.features(), graph.edge_index
     n, dev = int(x.shape[0]), x.device
+    if graph_perm:
+        # augmentations.py:44-47: the rows of x shuffled, every edge end redrawn below num_nodes - 1 (drawn on the generator's
+        # device, as _uniform)
+        gen_dev = generator.device if generator is not None else dev
+        x = x[torch.randperm(n, device=gen_dev, generator=generator).to(dev)]
+        ei = torch.randint(0, max(n - 1, 1), tuple(ei.shape), dtype=ei.dtype, device=gen_dev, generator=generator).to(dev)
     keep = ei[0] != ei[1]
     if edge_drop_ratio > 0:
         keep = keep & (_uniform(int(ei.shape[1]), dev, generator) >= edge_drop_ratio)

@@ -10,11 +10,11 @@ constexpr int PT = 64;            // rows per tile
 constexpr int PBK = 32;           // k per LDS chunk
 constexpr int PPLANE = PT * PBK;  // bf16 elements of one plane of one panel
 
-template <bool VEC>  // VEC: d % 4 == 0 and x 16-byte aligned
-__device__ __forceinline__ float4_t pair_load4(const float* __restrict__ x, int n, int d, int row, int k) {
+template <bool VEC>  // VEC: d % 4 == 0, ld % 4 == 0 and x 16-byte aligned; rows ld floats apart
+__device__ __forceinline__ float4_t pair_load4(const float* __restrict__ x, int n, int64_t ld, int d, int row, int k) {
   float4_t v = {0.f, 0.f, 0.f, 0.f};
   if (row < n) {
-    const float* p = x + (int64_t)row * d + k;
+    const float* p = x + (int64_t)row * ld + k;
     if constexpr (VEC) {
       if (k < d) v = *reinterpret_cast<const float4_t*>(p);
     } else {
@@ -32,9 +32,11 @@ __device__ __forceinline__ float4_t pair_load4(const float* __restrict__ x, int 
 // b3 exactly), six v_mfma_f32_32x32x16_bf16 per 16 k, two accumulators so that dependent MFMAs alternate.  Rows >= n and
 // k >= d enter as zeros.  s: six planes (three of each panel).  Starts with a barrier: the caller's earlier reads of s are
 // done before it is refilled.
+// The general form: panel a has na rows lda floats apart, panel b nb rows ldb apart (an activation tile against a weight
+// matrix: bootstrap.hip); either may lie in LDS, outside s.
 template <bool VEC>
-__device__ __forceinline__ float16_t gram_tile(const float* __restrict__ xa, const float* __restrict__ xb, int n, int d, int a0,
-                                               int b0, short (*s)[PPLANE]) {
+__device__ __forceinline__ float16_t gram_tile(const float* __restrict__ xa, int na, int64_t lda, const float* __restrict__ xb,
+                                               int nb, int64_t ldb, int d, int a0, int b0, short (*s)[PPLANE]) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 31, g = lane >> 5;
   const int wa = wv >> 1, wb = wv & 1;
   const int lr = tid >> 3, lc = (tid & 7) * 4;  // loader: rows lr, lr + 32; k segment lc .. lc + 3
@@ -45,8 +47,8 @@ __device__ __forceinline__ float16_t gram_tile(const float* __restrict__ xa, con
   auto gload = [&](int k0) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      ra[i] = pair_load4<VEC>(xa, n, d, a0 + lr + 32 * i, k0 + lc);
-      rb[i] = pair_load4<VEC>(xb, n, d, b0 + lr + 32 * i, k0 + lc);
+      ra[i] = pair_load4<VEC>(xa, na, lda, d, a0 + lr + 32 * i, k0 + lc);
+      rb[i] = pair_load4<VEC>(xb, nb, ldb, d, b0 + lr + 32 * i, k0 + lc);
     }
   };
   gload(0);
@@ -78,6 +80,13 @@ __device__ __forceinline__ float16_t gram_tile(const float* __restrict__ xa, con
 #pragma unroll
   for (int v = 0; v < 16; ++v) acc0[v] += acc1[v];
   return acc0;
+}
+
+// both panels [n][d] contiguous
+template <bool VEC>
+__device__ __forceinline__ float16_t gram_tile(const float* __restrict__ xa, const float* __restrict__ xb, int n, int d, int a0,
+                                               int b0, short (*s)[PPLANE]) {
+  return gram_tile<VEC>(xa, n, d, xb, n, d, d, a0, b0, s);
 }
 
 // row (of the 32 x 32 block) that register v of a lane of group g = lane / 32 holds in the D layout; the column is lane % 32

@@ -1300,6 +1300,65 @@ class HipEngine:
         """-> (dh1, dh2) [n, d]: gigl_whitening_loss_backward"""
         return self._correlation_loss_backward(saved, n, grad_loss)
 
+    def bootstrap_loss(self, e1, e2, y1, y2, neg_y=None, head=None, neg_lambda: float = 0.0):
+        """-> (loss [] fp32, saved): gigl_bootstrap_loss.  e1, e2 [n, out]: the online rows of the two views; y1, y2, neg_y (None:
+        BGRL) the targets; head = (W1 [hid, out], b1, W2 [out, hid], b2) or None (e1, e2 are q already).  saved = (q [2, n, out],
+        stat [2, 5, n], hidden [2, n, hid] | None, the rows as the kernel read them)"""
+        rows = [self._embedding_rows(t) if t is not None else None for t in (e1, e2, y1, y2, neg_y)]
+        n, out = int(rows[0].shape[0]), int(rows[0].shape[1])
+        assert all(t is None or t.shape == (n, out) for t in rows)
+        if head is not None:
+            head = tuple(t.detach().to(torch.float32).contiguous() for t in head)
+            hid = int(head[0].shape[0])
+            assert head[0].shape == (hid, out) and head[1].shape == (hid,) and head[2].shape == (out, hid) and head[3].shape == (out,)
+        else:
+            hid = 0
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        hidden, q, stat, loss = new(2, n, hid) if head is not None else None, new(2, n, out), new(2, 5, n), new()
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        ld = lambda t: int(t.stride(0)) if t is not None else 0
+        views = [x for t in rows for x in (p(t), ld(t))]
+        check(self._lib.gigl_bootstrap_loss(self._ctx, *views, *(p(t) for t in (head or (None,) * 4)), n, out, hid, float(neg_lambda),
+                                            p(hidden), p(q), p(stat), p(loss)), self._ctx)
+        return loss, (q, stat, hidden, rows, head)
+
+    def bootstrap_loss_backward(self, saved, neg_lambda: float, grad_loss):
+        """-> (de1, de2 [n, out], (dW1, db1, dW2, db2) | None): gigl_bootstrap_loss_backward, then — with a head — gigl_linear_
+        weight_grad twice over the two views' 2n stacked rows (dQ against the hidden rows; dH against the encoder rows, which
+        are copied into one [2n, out] matrix for it)"""
+        q, stat, hidden, rows, head = saved
+        e1, e2, y1, y2, neg_y = rows
+        n, out = int(q.shape[1]), int(q.shape[2])
+        hid = int(hidden.shape[2]) if head is not None else 0
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        de1, de2 = new(n, out), new(n, out)
+        dq, dh = (new(2 * n, out), new(2 * n, hid)) if head is not None else (None, None)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        ld = lambda t: int(t.stride(0)) if t is not None else 0
+        w1, w2 = (head[0], head[2]) if head is not None else (None, None)
+        check(self._lib.gigl_bootstrap_loss_backward(self._ctx, p(q), p(stat), p(hidden), p(y1), ld(y1), p(y2), ld(y2), p(neg_y),
+                                                     ld(neg_y), p(w1), p(w2), n, out, hid, float(neg_lambda), p(grad_loss), p(dq),
+                                                     p(dh), p(de1), out, p(de2), out), self._ctx)
+        if head is None or n == 0:
+            return de1, de2, None if head is None else tuple(torch.zeros_like(t) for t in head)
+        m_dev = torch.full((1,), 2 * n, dtype=torch.int32, device=self.device)
+        dw2, db2 = self.linear_weight_grad(dq, hidden.view(2 * n, hid), m_dev, want_bias=True)
+        dw1, db1 = self.linear_weight_grad(dh, torch.cat((e1, e2)), m_dev, want_bias=True)
+        return de1, de2, (dw1, db1, dw2, db2)
+
+    def ema_update(self, dst: Sequence[torch.Tensor], src: Sequence[torch.Tensor], mm: float) -> None:
+        """dst_k = mm dst_k + (1 - mm) src_k for every pair, in place, one launch: gigl_ema_update"""
+        assert len(dst) == len(src)
+        for d, s in zip(dst, src):
+            assert d.is_cuda and s.is_cuda and d.dtype == s.dtype == torch.float32 and d.shape == s.shape
+            assert d.is_contiguous() and s.is_contiguous()
+        if not dst:
+            return
+        table = torch.tensor([[d.data_ptr(), s.data_ptr(), d.numel()] for d, s in zip(dst, src)], dtype=torch.int64)
+        table = table.to(self.device)
+        check(self._lib.gigl_ema_update(self._ctx, C.c_void_p(table.data_ptr()), len(dst), max(d.numel() for d in dst), float(mm)),
+              self._ctx)
+
     def alignment_loss(self, u: torch.Tensor, v: torch.Tensor, alpha: float):
         """-> (loss [] fp32, norm [n]): gigl_alignment_loss"""
         u, v = self._embedding_rows(u), self._embedding_rows(v)

@@ -11,6 +11,7 @@ Mirror of (paths relative to the reference root):
   AligmentLoss, UniformityLoss         python/gigl/src/common/models/layers/loss.py:591-626  (csrc/pairwise.hip)
   GRACELoss                            python/gigl/src/common/models/layers/loss.py:362-416  (csrc/contrast.hip)
   WhiteningDecorrelationLoss, GBTLoss  python/gigl/src/common/models/layers/loss.py:444-534  (csrc/correlate.hip)
+  BGRLLoss, TBGRLLoss                  python/gigl/src/common/models/layers/loss.py:537-588  (csrc/bootstrap.hip)
 The loss is one fused device pass over the score matrix (csrc/loss.hip: temperature, sampling-probability correction,
 both masks, log-softmax and the summed cross-entropy, plus its backward), pinned by the reference's known-answer tests
 (tests/test_link_prediction.py restates loss_test.py:61-166 and decoder_test.py:44-62).
@@ -406,3 +407,70 @@ class WhiteningDecorrelationLoss(nn.Module):
         if int(N) != h1.shape[0]:
             raise ValueError(f"WhiteningDecorrelationLoss: N={N} is not the number of rows ({h1.shape[0]})")
         return _FusedCorrelation.apply(h1, h2, default_engine(h1.device), self.lambd), 1
+
+
+class _FusedBootstrapHead(torch.autograd.Function):
+    """the two views' online rows, the targets and the predictor head's parameters -> the BGRL (neg_y None) or TBGRL loss
+    (csrc/bootstrap.hip: Linear -> ReLU -> Linear on the matrix cores with the hidden tile kept in LDS, the cosine terms folded
+    from the second product's accumulators); backward = one launch for the row side (dQ, dH, dE) and two weight-gradient
+    calls.  w1 None: enc1, enc2 are already projected (the loss modules)."""
+
+    @staticmethod
+    def forward(ctx, enc1, enc2, y1, y2, neg_y, w1, b1, w2, b2, eng, neg_lambda):
+        head = None if w1 is None else (w1, b1, w2, b2)
+        loss, (q, stat, hidden, rows, head) = eng.bootstrap_loss(enc1, enc2, y1, y2, neg_y, head, neg_lambda)
+        ctx.eng, ctx.neg_lambda, ctx.tbgrl, ctx.head = eng, neg_lambda, neg_y is not None, head is not None
+        ctx.save_for_backward(q, stat, *rows[:4], *(rows[4:] if ctx.tbgrl else ()), *((hidden, *head) if ctx.head else ()))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        q, stat, *rest = ctx.saved_tensors
+        rows = rest[:4] + ([rest[4]] if ctx.tbgrl else [None])
+        tail = rest[5 if ctx.tbgrl else 4:]
+        hidden, head = (tail[0], tuple(tail[1:])) if ctx.head else (None, None)
+        de1, de2, dhead = ctx.eng.bootstrap_loss_backward((q, stat, hidden, rows, head), ctx.neg_lambda,
+                                                          g.to(torch.float32).contiguous())
+        return (de1, de2, None, None, None, *(dhead or (None,) * 4), None, None)
+
+
+def _bootstrap_rows(who: str, *rows):
+    rows = [_device_rows(t.detach() if k >= 2 else t, who) for k, t in enumerate(rows)]
+    if any(t.shape != rows[0].shape for t in rows):
+        raise ValueError(f"{who}: rows of different shapes {[tuple(t.shape) for t in rows]}")
+    return rows
+
+
+class BGRLLoss(nn.Module):
+    """The reference's BGRLLoss (loss.py:537-556): 2 - mean cos(q1, y2) - mean cos(q2, y1) over already-projected rows, the
+    targets constants — the row sums and their gradient by the bootstrap kernels without the head's products (gigl_bootstrap_
+    loss, w1 NULL).  forward -> (loss, 1).  Device tensors only; the tasks go through _FusedBootstrapHead, head included."""
+
+    def forward(self, q1: torch.Tensor, q2: torch.Tensor, y1: torch.Tensor, y2: torch.Tensor):
+        from .engine import default_engine
+        q1, q2, y1, y2 = _bootstrap_rows("BGRLLoss", q1, q2, y1, y2)
+        return _FusedBootstrapHead.apply(q1, q2, y1, y2, None, None, None, None, None, default_engine(q1.device), 0.0), 1
+
+
+class TBGRLLoss(nn.Module):
+    """The reference's TBGRLLoss (loss.py:559-588): neg_lambda (mean cos(q1, neg_y) + mean cos(q2, neg_y)) - (1 - neg_lambda)
+    (mean cos(q1, y2) + mean cos(q2, y1)), as BGRLLoss.  forward -> (loss, 1)."""
+
+    def __init__(self, neg_lambda: float = 0.12):
+        super().__init__()
+        self.neg_lambda = float(neg_lambda)
+
+    def forward(self, q1: torch.Tensor, q2: torch.Tensor, y1: torch.Tensor, y2: torch.Tensor, neg_y: torch.Tensor):
+        from .engine import default_engine
+        q1, q2, y1, y2, neg_y = _bootstrap_rows("TBGRLLoss", q1, q2, y1, y2, neg_y)
+        return _FusedBootstrapHead.apply(q1, q2, y1, y2, neg_y, None, None, None, None, default_engine(q1.device),
+                                         self.neg_lambda), 1
+
+
+def bootstrap_head_loss(enc1, enc2, y1, y2, neg_y, head: nn.Sequential, neg_lambda: float):
+    """the tasks' entry: head = Sequential(Linear(out, hid), ReLU, Linear(hid, out)) -> the loss tensor"""
+    from .engine import default_engine
+    who = "TBGRL" if neg_y is not None else "BGRL"
+    rows = _bootstrap_rows(who, enc1, enc2, y1, y2, *(() if neg_y is None else (neg_y,)))
+    return _FusedBootstrapHead.apply(*rows[:4], rows[4] if neg_y is not None else None, head[0].weight, head[0].bias,
+                                     head[2].weight, head[2].bias, default_engine(rows[0].device), float(neg_lambda))

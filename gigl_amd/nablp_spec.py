@@ -16,11 +16,12 @@ retrieval loss over the [queries x candidates] score matrix (gigl_retrieval_loss
 sampling correction when enabled).
 Scope: homogeneous graphs (one condensed node type / edge type) and heterogeneous ones (typed batches through the
 native typed collate, HGT / SimpleHGN encoders, first supervision edge type: spec :245-271, infer.py on HeteroData); the
-Retrieval, Margin, Softmax, DirectAU, GRACE, WhiteningDecorrelation and GBT tasks (DirectAU and the last three through the
-autograd loop: their losses read embeddings, not the score matrix the training plans' head works on; GRACE,
-WhiteningDecorrelation and GBT are the tasks over the input batch — two augmented views, task.py:212-279, :351-480 — on
-homogeneous TFRecord batches in one process) — the other augmentation-based self-supervised ones (BGRL, TBGRL,
-FeatureReconstruction: row-wise cosine losses) are not built.
+Retrieval, Margin, Softmax, DirectAU, GRACE, WhiteningDecorrelation, GBT, BGRL and TBGRL tasks (DirectAU and the last five
+through the autograd loop: their losses read embeddings, not the score matrix the training plans' head works on; GRACE,
+WhiteningDecorrelation, GBT, BGRL and TBGRL are the tasks over the input batch — two augmented views, task.py:212-279,
+:351-654, the bootstrap pair with a frozen offline copy of the encoder that follows the online one by a moving average after
+every optimiser step — on homogeneous TFRecord batches in one process) — the last augmentation-based self-supervised one,
+FeatureReconstruction (a GraphConv decoder over the whole batch graph), is not built.
 Data: main samples are the NodeAnchorBasedLinkPredictionSample TFRecords and random negatives the
 RootedNodeNeighborhood TFRecords the sampler wrote, re-filed into train/val/test by the split generator
 (gigl_amd/split_generator.py; datasetMetadata.nodeAnchorBasedLinkPredictionDataset URIs).  Without split outputs
@@ -476,6 +477,11 @@ class _TwoViewTask(nn.Module):
 
     def _views(self, task_input: NodeAnchorBasedLinkPredictionTaskInputs, device: torch.device):
         """-> the roots' rows of both views, through the head"""
+        graphs, roots = self._augmented(task_input, device)
+        return [self._apply_head(self._encoder_ref[0](view)[roots]) for view in graphs]
+
+    def _augmented(self, task_input: NodeAnchorBasedLinkPredictionTaskInputs, device: torch.device, neg_drops=None):
+        """-> ([view 1, view 2(, the permuted negative view: neg_drops = (edge, feature) drop ratios)], the roots' rows)"""
         from .augmentations import get_augmented_graph
         from .nn import GraphData
         if not self._encoder_ref:
@@ -486,11 +492,9 @@ class _TwoViewTask(nn.Module):
                                       f"{type(main_batch.graph).__name__}")
         graph = main_batch.graph.to(device)
         roots = main_batch.root_node_indices.to(device)
-        views = []
-        for edge_drop, feat_drop in ((self.edge_drop_1, self.feat_drop_1), (self.edge_drop_2, self.feat_drop_2)):
-            view = get_augmented_graph(graph, edge_drop_ratio=edge_drop, feat_drop_ratio=feat_drop, generator=self._generator)
-            views.append(self._apply_head(self._encoder_ref[0](view)[roots]))
-        return views
+        drops = [(self.edge_drop_1, self.feat_drop_1), (self.edge_drop_2, self.feat_drop_2)] + ([neg_drops] if neg_drops else [])
+        return [get_augmented_graph(graph, edge_drop_ratio=edge_drop, feat_drop_ratio=feat_drop, graph_perm=k == 2,
+                                    generator=self._generator) for k, (edge_drop, feat_drop) in enumerate(drops)], roots
 
 
 class GRACE(_TwoViewTask):
@@ -540,6 +544,64 @@ class GBT(_TwoViewTask):
                 should_eval: bool = False, device: torch.device = torch.device("cpu")):
         z_a, z_b = self._views(task_input, device)
         return self.loss(z_a=z_a, z_b=z_b, device=device)
+
+
+class BGRL(_TwoViewTask):
+    """task.py:483-560 (bootstrapped graph latents): the online encoder's root rows of both views go through the predictor head
+    and are pulled towards the OTHER view's rows under a frozen copy of the encoder (offline_encoder: a registered submodule,
+    so its keys sit under the task's prefix; no gradient reaches it) — head, cosine loss and their gradient in the bootstrap
+    kernels (csrc/bootstrap.hip).  update_offline_encoder(mm) moves the copy towards the online encoder.  forward -> (loss, 1)."""
+    task_name = "BGRL"
+    neg_lambda = 0.0
+    _neg_drops = None
+
+    def __init__(self, encoder: Optional[nn.Module] = None, feat_drop_1: float = 0.8, edge_drop_1: float = 0.8,
+                 feat_drop_2: float = 0.1, edge_drop_2: float = 0.8, seed: int = 0):
+        super().__init__(None, feat_drop_1, edge_drop_1, feat_drop_2, edge_drop_2, seed)
+        self.offline_encoder: Optional[nn.Module] = None
+        if encoder is not None:
+            self.bind_encoder(encoder)
+
+    def bind_encoder(self, encoder: nn.Module) -> None:
+        super().bind_encoder(encoder)
+        if self.offline_encoder is None:
+            engine = getattr(encoder, "engine", None)  # (shared, not copied)
+            self.offline_encoder = deepcopy(encoder, {id(engine): engine}).requires_grad_(False)
+
+    def forward(self, task_input: NodeAnchorBasedLinkPredictionTaskInputs, gbml_config_pb_wrapper=None,
+                should_eval: bool = False, device: torch.device = torch.device("cpu")):
+        from .link_prediction import bootstrap_head_loss
+        graphs, roots = self._augmented(task_input, device, self._neg_drops)
+        online = self._encoder_ref[0]
+        if hasattr(online, "engine"):
+            self.offline_encoder.engine = online.engine
+        enc1, enc2 = (online(view)[roots] for view in graphs[:2])
+        with torch.no_grad():
+            targets = [self.offline_encoder(view)[roots] for view in graphs]
+        neg_y = targets[2] if self._neg_drops else None
+        return bootstrap_head_loss(enc1, enc2, targets[0], targets[1], neg_y, self.head, self.neg_lambda), 1
+
+    def update_offline_encoder(self, mm: float) -> None:
+        """task.py:552-556: offline = mm offline + (1 - mm) online, every parameter in one launch (gigl_ema_update)"""
+        from .engine import default_engine
+        dst = [p.data for p in self.offline_encoder.parameters()]
+        if dst:
+            default_engine(dst[0].device).ema_update(dst, [p.data for p in self._encoder_ref[0].parameters()], mm)
+
+
+class TBGRL(BGRL):
+    """task.py:563-654: BGRL with a third, negative view — the graph with its feature rows permuted and its edges redrawn
+    (get_augmented_graph(graph_perm=True)), through the offline encoder only — whose rows the predictions are pushed away from
+    with weight neg_lambda.  forward -> (loss, 1)."""
+    task_name = "TBGRL"
+
+    def __init__(self, encoder: Optional[nn.Module] = None, neg_lambda: float = 0.12, feat_drop_1: float = 0.8,
+                 edge_drop_1: float = 0.8, feat_drop_2: float = 0.1, edge_drop_2: float = 0.8, feat_drop_neg: float = 0.95,
+                 edge_drop_neg: float = 0.95, seed: int = 0):
+        super().__init__(encoder, feat_drop_1, edge_drop_1, feat_drop_2, edge_drop_2, seed)
+        self.neg_lambda = float(neg_lambda)
+        self.feat_drop_neg, self.edge_drop_neg = float(feat_drop_neg), float(edge_drop_neg)
+        self._neg_drops = (self.edge_drop_neg, self.feat_drop_neg)
 
 
 class NodeAnchorBasedLinkPredictionTasks:
@@ -665,6 +727,15 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             # (the reference tasks' defaults: lambd 1e-3, drop ratios 0.2)
             offered = {"lambd": float(kwargs.get("wd_lambd", 1e-3)), "seed": int(kwargs.get("augment_seed", 0)),
                        **{k: float(kwargs.get(k, 0.2)) for k in ("feat_drop_1", "edge_drop_1", "feat_drop_2", "edge_drop_2")}}
+        if isinstance(task_cls, type) and issubclass(task_cls, BGRL):
+            # (the reference tasks' defaults, task.py:488-495, :568-578)
+            drops = {"feat_drop_1": 0.8, "edge_drop_1": 0.8, "feat_drop_2": 0.1, "edge_drop_2": 0.8, "feat_drop_neg": 0.95,
+                     "edge_drop_neg": 0.95}
+            offered = {"neg_lambda": float(kwargs.get("neg_lambda", 0.12)), "seed": int(kwargs.get("augment_seed", 0)),
+                       **{k: float(kwargs.get(k, v)) for k, v in drops.items()}}
+        # the offline encoder's momentum (tasks with update_offline_encoder; the reference defines the method and never calls
+        # it: 1.0 reproduces that)
+        self.offline_momentum = float(kwargs.get("offline_momentum", 0.99))
         takes = inspect.signature(task_cls.__init__).parameters
         # (the reference passes temperature / remove_accidental_hits to whatever class task_path names — its Margin and
         # Softmax tasks cannot be built that way; here every task gets the arguments its constructor declares)
@@ -719,15 +790,16 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             in_dim=max(in_dim, 1), hid_dim=self.hidden_dim, out_dim=self.out_channels, num_layers=self.num_layers,
             should_l2_normalize_embedding_layer_output=self.should_l2_normalize_embedding_layer_output, **extra)
         model = LinkPredictionGNN(encoder=encoder, decoder=LinkPredictionDecoder())
-        # tasks that encode the input batch themselves (result type input_batch: GRACE, WhiteningDecorrelation, GBT) get the
-        # model's encoder, and the heads of those that have one become part of the model, `task_heads.<task name>`: one
-        # parameter list for the optimiser, one state dict
+        # tasks that encode the input batch themselves (result type input_batch: GRACE, WhiteningDecorrelation, GBT, BGRL, TBGRL)
+        # get the model's encoder, and the heads of those that have one become part of the model, `task_heads.<task name>`: one
+        # parameter list for the optimiser, one state dict.  A bootstrap task goes in whole — its keys are `task_heads.<task
+        # name>.head.*` and `.offline_encoder.*` (frozen: the optimiser skips it) — the online encoder it holds unregistered
         heads = {}
         for task in self.tasks._task_to_fn_map.values():
             if hasattr(task, "bind_encoder"):
                 task.bind_encoder(encoder)
                 if task.head is not None:
-                    heads[task.task_name] = task.head
+                    heads[task.task_name] = task if hasattr(task, "offline_encoder") else task.head
         if heads:
             model.task_heads = nn.ModuleDict(heads)
         if state_dict is not None:
@@ -747,7 +819,7 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         encoder class (gnn_model_class_path; default HGT) takes the per-type feature dims, hid / out dims, num_layers,
         num_heads"""
         if "input_batch" in self.tasks.result_types:
-            raise NotImplementedError("tasks over the input batch (GRACE, WhiteningDecorrelation, GBT) are built for homogeneous "
+            raise NotImplementedError("tasks over the input batch (GRACE, WhiteningDecorrelation, GBT, BGRL, TBGRL) are built for homogeneous "
                                       "graphs only")
         pm = cfg.preprocessed_metadata
         node_dims = {name: max(pm.nodes[c].feature_dim, 1) for c, name in cfg.condensed_node_type_map.items()}
@@ -806,7 +878,7 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             # (these tasks augment the batch's GraphData; the batch graph of the in-HBM route is not one)
             import os
             if (self._kwargs.get("data_route") or os.environ.get("GIGL_AMD_ROUTE") or "auto").lower() == "hbm":
-                raise ValueError("data_route hbm cannot serve a task over the input batch (GRACE, WhiteningDecorrelation, GBT): it "
+                raise ValueError("data_route hbm cannot serve a task over the input batch (GRACE, WhiteningDecorrelation, GBT, BGRL, TBGRL): it "
                                  "takes the TFRecord route")
             return None
         from .hbm import ResidentGraph, encoder_trains_over_graph_data, encoder_trains_over_hip_batches, route_of
@@ -1222,7 +1294,7 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         cfg = gbml_config_pb_wrapper
         _, world = _rank_world()
         if world > 1 and "input_batch" in self.tasks.result_types:
-            raise NotImplementedError("tasks over the input batch (GRACE, WhiteningDecorrelation, GBT) train in one process: the "
+            raise NotImplementedError("tasks over the input batch (GRACE, WhiteningDecorrelation, GBT, BGRL, TBGRL) train in one process: the "
                                       "data-parallel wrapper's forward does not run their heads")
         plan = self._library_train_plan(cfg)
         if plan is not None:
@@ -1245,6 +1317,9 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             if self.clip_grad_norm > 0:
                 nn.utils.clip_grad_norm_(self.model.parameters(), self.clip_grad_norm)
             self._optimizer.step()
+            for task in self.tasks._task_to_fn_map.values():
+                if hasattr(task, "update_offline_encoder"):
+                    task.update_offline_encoder(self.offline_momentum)
             self._lr_scheduler.step()
             self.history.append({"batch": batch_index, "loss": float(loss)})
             if batch_index % every == 0:

@@ -1221,6 +1221,41 @@ int32_t gigl_whitening_loss_backward(gigl_ctx* ctx, const float* z, const float*
  * arguments: ceil(n / rows) chunks, all but the last at least 64 rows; 0 for arguments out of range. */
 int32_t gigl_correlate_chunk_rows(int32_t n, int32_t d, int32_t products);
 
+/* ---- the bootstrap tasks' predictor head and row-wise cosine loss (csrc/bootstrap.hip): BGRL and TBGRL (python/gigl/src/
+ *      common/models/layers/task.py:483-654, loss.py:537-588).  All pointers DEVICE; the work is issued on the ctx's stream,
+ *      nothing synchronises the host, no atomics; results are bit-reproducible run to run.  1 <= out, hid <= 512, n <= 2^18
+ *      (GIGL_E_INVALID_ARG with a message beyond).
+ * e1, e2 [n][out]: the online encoder's rows of the two views; y1, y2 and (TBGRL; NULL: BGRL) yneg [n][out]: the offline
+ * encoder's rows, constants; every matrix with its own row stride in floats.  w1 [hid][out], b1 [hid], w2 [out][hid], b2
+ * [out]: the head (torch Linear layout).  Per view v: H_v = relu(E_v w1^T + b1), Q_v = H_v w2^T + b2 — one launch over (64-row
+ * tile, view), H_v staying in LDS between the two products — and with cos(a, b) = a.b / (max(|a|, 1e-8) max(|b|, 1e-8)):
+ *   BGRL   *loss_out = 2 - mean_i cos(q1_i, y2_i) - mean_i cos(q2_i, y1_i)
+ *   TBGRL  *loss_out = neg_lambda (mean cos(q1, yneg) + mean cos(q2, yneg)) - (1 - neg_lambda) (mean cos(q1, y2) + mean cos(q2, y1))
+ * n == 0: NaN.  What the backward reads: hid_out [2][n][hid] (H_1, then H_2), q_out [2][n][out], stat_out [2][5][n]: per
+ * view the rows' |q|^2, q.y, |y|^2, q.yneg, |yneg|^2 (y the OTHER view's target; the last two zero for BGRL).  The tiles'
+ * partial sums (32 bytes a tile) come from the ctx's arena and are added in tile order.
+ * w1 == NULL: no head, q_v = e_v (b1, w2, b2, hid, hid_out unused). */
+int32_t gigl_bootstrap_loss(gigl_ctx* ctx, const float* e1, int64_t ld_e1, const float* e2, int64_t ld_e2, const float* y1,
+                            int64_t ld_y1, const float* y2, int64_t ld_y2, const float* yneg, int64_t ld_yneg, const float* w1,
+                            const float* b1, const float* w2, const float* b2, int32_t n, int32_t out, int32_t hid,
+                            float neg_lambda, float* hid_out, float* q_out, float* stat_out, float* loss_out);
+/* The row side of the gradient of gigl_bootstrap_loss, scaled by *gout_dev (NULL: 1), one launch over the same tiles: dQ_v
+ * from q, the targets and the row stats (a row with |q| <= 1e-8: the norm's value clamped and its derivative kept, as autograd
+ * through F.cosine_similarity gives; |q| = 0: no norm term) -> dq_out [2][n][out]; dH_v = (dQ_v w2) . [H_v > 0] -> dh_out [2][n][hid]; dE_v = dH_v w1 -> de1 /
+ * de2 [n][out], rows ld_d1 / ld_d2 floats apart.  q, stat, hid_in: the forward's outputs.  The weights' gradients are
+ * gigl_linear_weight_grad over the stacked rows: (dq_out, hid_in) for w2 and b2, (dh_out, the stacked e) for w1 and b1.
+ * w1^T and w2^T (at most 1 MB each) are written to the ctx's arena.  w1 == NULL: no head, de_v = dQ_v. */
+int32_t gigl_bootstrap_loss_backward(gigl_ctx* ctx, const float* q, const float* stat, const float* hid_in, const float* y1,
+                                     int64_t ld_y1, const float* y2, int64_t ld_y2, const float* yneg, int64_t ld_yneg,
+                                     const float* w1, const float* w2, int32_t n, int32_t out, int32_t hid, float neg_lambda,
+                                     const float* gout_dev, float* dq_out, float* dh_out, float* de1, int64_t ld_d1, float* de2,
+                                     int64_t ld_d2);
+/* dst = mm dst + (1 - mm) src for n_tensors fp32 tensors in one launch (the offline encoder's moving average, task.py:552-556:
+ * a mul_ / add_ pair per parameter in the reference).  table_dev: DEVICE, n_tensors entries {float* dst; const float* src;
+ * int64_t count;} (24 bytes); max_count: the largest count (it sizes the grid).  0 <= mm <= 1, n_tensors <= 65535.  mm == 1
+ * launches nothing: dst keeps its bits. */
+int32_t gigl_ema_update(gigl_ctx* ctx, const void* table_dev, int32_t n_tensors, int64_t max_count, double mm);
+
 /* ---- rank metrics of a score matrix: MRR and hits@k of every anchor's positives among the random negatives, one wave per
  *      anchor, summed on the device.  Replaces hit_rate_at_k / mean_reciprocal_rank (python/gigl/src/common/utils/
  *      eval_metrics.py:6-73) as the trainer's validate() calls them once per anchor (node_anchor_based_link_prediction_
