@@ -87,6 +87,7 @@ SYMBOLS = [
     "gigl_gbt_loss", "gigl_gbt_loss_backward", "gigl_whitening_loss", "gigl_whitening_loss_backward",
     "gigl_correlate_chunk_rows",
     "gigl_bootstrap_loss", "gigl_bootstrap_loss_backward", "gigl_ema_update",
+    "gigl_feature_reconstruction_loss", "gigl_feature_reconstruction_loss_backward",
 ]
 
 KERNEL_IDS = {
@@ -389,6 +390,10 @@ def load() -> C.CDLL:
         "gigl_bootstrap_loss_backward": [vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, vp,
                                          i64, vp, i64],
         "gigl_ema_update": [vp, vp, i32, i64, C.c_double],
+        "gigl_feature_reconstruction_loss": [vp, vp, i64, vp, vp, i32, vp, vp, i64, vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp,
+                                             vp, vp, vp, vp],
+        "gigl_feature_reconstruction_loss_backward": [vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, i64, i32, i32, i32,
+                                                      C.c_float, vp, vp, i64, vp, vp, vp, i64],
         "gigl_gather_mean_backward": [vp, vp, i32, vp, vp, vp, vp, i64, vp],
         "gigl_gather_mean_backward_transposed": [vp, vp, i32, vp, vp, vp, vp, i64, vp, i64, i64, i32, vp],
         "gigl_transposed_rows_build": [vp, vp, vp, vp, vp, i64, vp, i64, i64, vp],

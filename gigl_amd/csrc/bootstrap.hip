@@ -55,22 +55,6 @@ struct boot_args {
 
 __host__ __device__ inline int boot_ld(int k) { return (k + 3) / 4 * 4 + 4; }  // floats between the rows of an LDS tile
 
-// the row sums of lanes (., g) over their 32 columns, then over the two column halves (waves wb = 0, 1) through s_row, [half]
-// [sum][row]; afterwards thread t < 64 reads row t's totals as s_row[0][j][t] + s_row[1][j][t]
-__device__ __forceinline__ void boot_rows_meet(float (&rs)[BSTAT][16], float (*s_row)[BSTAT][PT]) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, g = lane >> 5;
-#pragma unroll
-  for (int j = 0; j < BSTAT; ++j)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      float t = rs[j][v];
-#pragma unroll
-      for (int off = 16; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-      if (r == 0) s_row[wv & 1][j][(wv >> 1) * 32 + gram_row(v, g)] = t;
-    }
-  __syncthreads();
-}
-
 __device__ __forceinline__ float boot_cos(float dot, float qq, float yy) {
   return dot / (fmaxf(sqrtf(qq), BEPS) * fmaxf(sqrtf(yy), BEPS));
 }
@@ -138,7 +122,7 @@ __global__ __launch_bounds__(256) void boot_forward_kernel(const boot_args a, fl
       }
     }
   }
-  boot_rows_meet(rs, s_row);
+  gram_rows_meet<BSTAT>(rs, s_row);
   if (wv == 0) {  // a row per lane
     const int i = I0 + lane;
     float t[BSTAT];

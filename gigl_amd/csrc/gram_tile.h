@@ -92,6 +92,24 @@ __device__ __forceinline__ float16_t gram_tile(const float* __restrict__ xa, con
 // row (of the 32 x 32 block) that register v of a lane of group g = lane / 32 holds in the D layout; the column is lane % 32
 __device__ __forceinline__ constexpr int gram_row(int v, int g) { return 8 * (v >> 2) + 4 * g + (v & 3); }
 
+// The row sums a kernel folds from its accumulators (NS sums, sixteen rows per lane in the D layout) meet: over the 32 lanes
+// (., g) of a row by butterfly, then over the two column halves (waves wb = 0, 1) through s_row, [half][sum][row]; afterwards
+// thread t < 64 reads row t's totals as s_row[0][j][t] + s_row[1][j][t].  Ends with a barrier.  By all 256 threads.
+template <int NS>
+__device__ __forceinline__ void gram_rows_meet(float (&rs)[NS][16], float (*s_row)[NS][PT]) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, g = lane >> 5;
+#pragma unroll
+  for (int j = 0; j < NS; ++j)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      float t = rs[j][v];
+#pragma unroll
+      for (int off = 16; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+      if (r == 0) s_row[wv & 1][j][(wv >> 1) * 32 + gram_row(v, g)] = t;
+    }
+  __syncthreads();
+}
+
 // ---- the second product ---------------------------------------------------------------------------------------------------
 // acc[i][c] += W[i][j] X[j][c] for weights W that are a function of the Gram tile (the backward kernels of pairwise.hip and
 // contrast.hip), without W ever leaving the registers.  The first product is taken TRANSPOSED, gram_tile(x, own, .., J0, I0):

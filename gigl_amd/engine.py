@@ -1359,6 +1359,67 @@ class HipEngine:
         check(self._lib.gigl_ema_update(self._ctx, C.c_void_p(table.data_ptr()), len(dst), max(d.numel() for d in dst), float(mm)),
               self._ctx)
 
+    def feature_reconstruction_loss(self, e, x, alpha: float, graph=None, roots=None, decoder=None):
+        """-> (loss [] fp32, saved): gigl_feature_reconstruction_loss.  With a decoder = (W_ed [out, out], W_rel [in, out], b_rel
+        [in]): e [N, out] the encoder's rows of all nodes, x [N, in] the unmasked features, graph the batch graph (rowptr, col
+        by destination), roots [B] node ids.  decoder None: e [B, in] the predictions, x [B, in] the targets, row for row.
+        saved: what feature_reconstruction_loss_backward reads."""
+        e, x = self._embedding_rows(e), self._embedding_rows(x)
+        new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        stat_loss = lambda b: (new(3, b), new())
+        if decoder is None:
+            b, d_in = int(e.shape[0]), int(e.shape[1])
+            assert x.shape == e.shape
+            stat, loss = stat_loss(b)
+            check(self._lib.gigl_feature_reconstruction_loss(self._ctx, p(e), int(e.stride(0)), None, None, 0, None, p(x), int(x.stride(0)),
+                                                             None, None, None, b, 0, d_in, float(alpha), None, None, None, None, None,
+                                                             p(stat), p(loss)), self._ctx)
+            return loss, dict(p=e, x=x, stat=stat, alpha=float(alpha))
+        w_ed, w_rel, b_rel = (t.detach().to(torch.float32).contiguous() for t in decoder)
+        n, out, d_in = int(e.shape[0]), int(e.shape[1]), int(x.shape[1])
+        assert x.shape[0] == n and w_ed.shape == (out, out) and w_rel.shape == (d_in, out) and b_rel.shape == (d_in,)
+        assert graph.rowptr.numel() == n + 1 and graph.rowptr.dtype == graph.col.dtype == torch.int32
+        roots = roots.to(device=self.device, dtype=torch.int32).contiguous()
+        b = int(roots.numel())
+        is_root, root_rows = new((n + 3) // 4 * 4, dtype=torch.uint8), new(2, b, dtype=torch.int32)
+        s, t, pred = new(b, out), new(b, out), new(b, d_in)
+        stat, loss = stat_loss(b)
+        check(self._lib.gigl_feature_reconstruction_loss(self._ctx, p(e), int(e.stride(0)), p(graph.rowptr), p(graph.col), n, p(roots),
+                                                         p(x), int(x.stride(0)), p(w_ed), p(w_rel), p(b_rel), b, out, d_in, float(alpha),
+                                                         p(is_root), p(root_rows), p(s), p(t), p(pred), p(stat), p(loss)), self._ctx)
+        return loss, dict(p=pred, x=x, stat=stat, alpha=float(alpha), roots=roots, col=graph.col, n=n, is_root=is_root,
+                          root_rows=root_rows, s=s, t=t, w_ed=w_ed, w_rel=w_rel)
+
+    def feature_reconstruction_loss_backward(self, saved, grad_loss):
+        """-> (dE [N, out], (dW_ed, dW_rel, db_rel)) — or, without a decoder, (d predictions [B, in], None): gigl_feature_
+        reconstruction_loss_backward, then gigl_linear_weight_grad over (g, t) for lin_rel and over (dT, s) for enc_dec.  The
+        transposed lists are sized by the listed roots' in-degrees, summed on the device and read once."""
+        pred, x, stat, alpha = saved["p"], saved["x"], saved["stat"], saved["alpha"]
+        b, d_in = int(pred.shape[0]), int(pred.shape[1])
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        g = new(b, d_in)
+        if "w_ed" not in saved:
+            check(self._lib.gigl_feature_reconstruction_loss_backward(
+                self._ctx, ptr(pred), int(pred.stride(0)), ptr(stat), None, ptr(x), int(x.stride(0)), None, None, None, None, None, 0, 0,
+                b, 0, d_in, alpha, ptr(grad_loss), ptr(g), d_in, None, None, None, 0), self._ctx)
+            return g, None
+        w_ed, w_rel, root_rows, n = saved["w_ed"], saved["w_rel"], saved["root_rows"], saved["n"]
+        out = int(w_ed.shape[0])
+        dt, ds, de = new(b, out), new(b, out), new(n, out)
+        edges = int((root_rows[1] - root_rows[0]).sum()) if b else 0
+        check(self._lib.gigl_feature_reconstruction_loss_backward(
+            self._ctx, ptr(pred), d_in, ptr(stat), ptr(saved["roots"]), ptr(x), int(x.stride(0)), ptr(w_ed), ptr(w_rel),
+            ptr(saved["is_root"]), ptr(root_rows), ptr(saved["col"]), n, edges, b, out, d_in, alpha, ptr(grad_loss), ptr(g), d_in,
+            ptr(dt), ptr(ds), ptr(de), out), self._ctx)
+        if b == 0:
+            return de, (torch.zeros_like(w_ed), torch.zeros_like(w_rel), new(d_in).zero_())
+        m_dev = dev_i32(self.device, b)
+        dw_rel, db_rel = self.linear_weight_grad(g, saved["t"], m_dev, want_bias=True)
+        dw_ed, _ = self.linear_weight_grad(dt, saved["s"], m_dev)
+        return de, (dw_ed, dw_rel, db_rel)
+
     def alignment_loss(self, u: torch.Tensor, v: torch.Tensor, alpha: float):
         """-> (loss [] fp32, norm [n]): gigl_alignment_loss"""
         u, v = self._embedding_rows(u), self._embedding_rows(v)

@@ -12,6 +12,7 @@ Mirror of (paths relative to the reference root):
   GRACELoss                            python/gigl/src/common/models/layers/loss.py:362-416  (csrc/contrast.hip)
   WhiteningDecorrelationLoss, GBTLoss  python/gigl/src/common/models/layers/loss.py:444-534  (csrc/correlate.hip)
   BGRLLoss, TBGRLLoss                  python/gigl/src/common/models/layers/loss.py:537-588  (csrc/bootstrap.hip)
+  FeatureReconstructionLoss            python/gigl/src/common/models/layers/loss.py:419-441  (csrc/reconstruct.hip)
 The loss is one fused device pass over the score matrix (csrc/loss.hip: temperature, sampling-probability correction,
 both masks, log-softmax and the summed cross-entropy, plus its backward), pinned by the reference's known-answer tests
 (tests/test_link_prediction.py restates loss_test.py:61-166 and decoder_test.py:44-62).
@@ -474,3 +475,53 @@ def bootstrap_head_loss(enc1, enc2, y1, y2, neg_y, head: nn.Sequential, neg_lamb
     rows = _bootstrap_rows(who, enc1, enc2, y1, y2, *(() if neg_y is None else (neg_y,)))
     return _FusedBootstrapHead.apply(*rows[:4], rows[4] if neg_y is not None else None, head[0].weight, head[0].bias,
                                      head[2].weight, head[2].bias, default_engine(rows[0].device), float(neg_lambda))
+
+
+class _FusedFeatureReconstruction(torch.autograd.Function):
+    """the encoder's rows of all nodes, the unmasked features, the roots and the decoder's parameters -> the scaled-cosine-error
+    loss of the reconstructed root rows (csrc/reconstruct.hip: the root rows' neighbour sums, both Linears on the matrix cores
+    with the intermediate kept in LDS, the row sums folded from the second product's accumulators); backward = one launch for
+    the row side, a gather that writes every row of dE once, and two weight-gradient calls.  Gradients to enc, w_ed, w_rel,
+    b_rel; none to x.  w_ed None: enc holds the predictions and x the targets, row for row (the loss module)."""
+
+    @staticmethod
+    def forward(ctx, enc, x, w_ed, w_rel, b_rel, eng, alpha, graph, roots):
+        decoder = None if w_ed is None else (w_ed, w_rel, b_rel)
+        loss, saved = eng.feature_reconstruction_loss(enc, x, alpha, graph, roots, decoder)
+        ctx.eng = eng
+        ctx.keys = [k for k, v in saved.items() if torch.is_tensor(v)]
+        ctx.rest = {k: v for k, v in saved.items() if not torch.is_tensor(v)}
+        ctx.save_for_backward(*(saved[k] for k in ctx.keys))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = dict(zip(ctx.keys, ctx.saved_tensors), **ctx.rest)
+        d_rows, d_dec = ctx.eng.feature_reconstruction_loss_backward(saved, g.to(torch.float32).contiguous())
+        return (d_rows, None, *(d_dec or (None,) * 3), None, None, None, None)
+
+
+class FeatureReconstructionLoss(nn.Module):
+    """The reference's FeatureReconstructionLoss (loss.py:419-441; GraphMAE's scaled cosine error): mean_i (1 - <x_i / |x_i|,
+    y_i / |y_i|>)^alpha over already-decoded rows, the targets constants — the row sums, the fold and their gradient by the
+    reconstruction kernels without the gather and the products (gigl_feature_reconstruction_loss, w_ed NULL).  forward -> (loss,
+    1).  Device tensors only; the task goes through feature_reconstruction_loss, decoder included."""
+
+    def __init__(self, alpha: float = 3.0):
+        super().__init__()
+        self.alpha = float(alpha)
+
+    def forward(self, x_target: torch.Tensor, x_pred: torch.Tensor):
+        from .engine import default_engine
+        x_target, x_pred = _device_rows(x_target.detach(), "FeatureReconstructionLoss"), _device_rows(x_pred, "FeatureReconstructionLoss")
+        if x_target.shape != x_pred.shape:
+            raise ValueError(f"FeatureReconstructionLoss: rows of different shapes {tuple(x_target.shape)}, {tuple(x_pred.shape)}")
+        return _FusedFeatureReconstruction.apply(x_pred, x_target, None, None, None, default_engine(x_pred.device), self.alpha, None,
+                                                 None), 1
+
+
+def feature_reconstruction_loss(enc, x, graph, roots, w_ed, w_rel, b_rel, alpha: float):
+    """the task's entry: enc [N, out] the encoder's rows over `graph`, x [N, in] the unmasked features, roots [B] -> the loss"""
+    from .engine import default_engine
+    enc, x = _device_rows(enc, "FeatureReconstruction"), _device_rows(x.detach(), "FeatureReconstruction")
+    return _FusedFeatureReconstruction.apply(enc, x, w_ed, w_rel, b_rel, default_engine(enc.device), float(alpha), graph, roots)

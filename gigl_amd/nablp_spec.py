@@ -16,12 +16,13 @@ retrieval loss over the [queries x candidates] score matrix (gigl_retrieval_loss
 sampling correction when enabled).
 Scope: homogeneous graphs (one condensed node type / edge type) and heterogeneous ones (typed batches through the
 native typed collate, HGT / SimpleHGN encoders, first supervision edge type: spec :245-271, infer.py on HeteroData); the
-Retrieval, Margin, Softmax, DirectAU, GRACE, WhiteningDecorrelation, GBT, BGRL and TBGRL tasks (DirectAU and the last five
-through the autograd loop: their losses read embeddings, not the score matrix the training plans' head works on; GRACE,
-WhiteningDecorrelation, GBT, BGRL and TBGRL are the tasks over the input batch — two augmented views, task.py:212-279,
+Retrieval, Margin, Softmax, DirectAU, GRACE, WhiteningDecorrelation, GBT, BGRL, TBGRL and FeatureReconstruction tasks (DirectAU
+and the last six through the autograd loop: their losses read embeddings, not the score matrix the training plans' head works
+on; GRACE, WhiteningDecorrelation, GBT, BGRL and TBGRL are the tasks over the input batch — two augmented views, task.py:212-279,
 :351-654, the bootstrap pair with a frozen offline copy of the encoder that follows the online one by a moving average after
-every optimiser step — on homogeneous TFRecord batches in one process) — the last augmentation-based self-supervised one,
-FeatureReconstruction (a GraphConv decoder over the whole batch graph), is not built.
+every optimiser step — and FeatureReconstruction, task.py:282-348, masks the roots' features and reconstructs them from their
+neighbours' rows, its GraphConv decoder collapsed to the root rows (csrc/reconstruct.hip); all on homogeneous TFRecord batches
+in one process): every task the reference ships.
 Data: main samples are the NodeAnchorBasedLinkPredictionSample TFRecords and random negatives the
 RootedNodeNeighborhood TFRecords the sampler wrote, re-filed into train/val/test by the split generator
 (gigl_amd/split_generator.py; datasetMetadata.nodeAnchorBasedLinkPredictionDataset URIs).  Without split outputs
@@ -448,6 +449,7 @@ class _TwoViewTask(nn.Module):
     Homogeneous GraphData batches only (the TFRecord route); `seed` starts the augmentations' own generator."""
     result_types = ("input_batch",)
     with_head = True
+    whole_in_model = False  # (True: init_model registers the task itself under task_heads.<name>, not only its head)
 
     def __init__(self, encoder: Optional[nn.Module], feat_drop_1: float, edge_drop_1: float, feat_drop_2: float,
                  edge_drop_2: float, seed: int):
@@ -552,6 +554,7 @@ class BGRL(_TwoViewTask):
     so its keys sit under the task's prefix; no gradient reaches it) — head, cosine loss and their gradient in the bootstrap
     kernels (csrc/bootstrap.hip).  update_offline_encoder(mm) moves the copy towards the online encoder.  forward -> (loss, 1)."""
     task_name = "BGRL"
+    whole_in_model = True
     neg_lambda = 0.0
     _neg_drops = None
 
@@ -602,6 +605,60 @@ class TBGRL(BGRL):
         self.neg_lambda = float(neg_lambda)
         self.feat_drop_neg, self.edge_drop_neg = float(feat_drop_neg), float(edge_drop_neg)
         self._neg_drops = (self.edge_drop_neg, self.feat_drop_neg)
+
+
+class FeatureReconstruction(_TwoViewTask):
+    """task.py:282-348 (GraphMAE's auxiliary loss): the roots' feature rows are replaced by a learned mask token, the masked
+    graph (edges dropped with edge_drop) is encoded over ALL nodes, and the roots' features are reconstructed from their
+    non-root in-neighbours' rows — reconstruction_enc_dec, then a GraphConv decoder — under the scaled cosine error with
+    exponent alpha.  Only root rows of the decoder are kept, and on them GraphConv's root term vanishes: decoder, loss and their
+    gradient are the reconstruction kernels' B rows of work (csrc/reconstruct.hip).  The parameters carry the reference's names
+    (a checkpoint maps key for key); reconstruction_decoder.lin_root is kept for the state dict, is never read and gets no
+    gradient.  The mask token's gradient arrives through the encoder's input gradient.  forward -> (loss, 1)."""
+    task_name = "FeatureReconstruction"
+    with_head = False
+    whole_in_model = True
+
+    def __init__(self, encoder: Optional[nn.Module] = None, alpha: float = 3.0, edge_drop: float = 0.3, seed: int = 0):
+        super().__init__(None, 0.0, edge_drop, 0.0, edge_drop, seed)
+        self.alpha, self.edge_drop = float(alpha), float(edge_drop)
+        self.reconstruction_mask: Optional[nn.Parameter] = None
+        if encoder is not None:
+            self.bind_encoder(encoder)
+
+    def bind_encoder(self, encoder: nn.Module) -> None:
+        super().bind_encoder(encoder)
+        if self.reconstruction_mask is None:
+            in_dim, out_dim = int(encoder.in_dim), int(encoder.out_dim)
+            self.reconstruction_mask = nn.Parameter(torch.zeros(1, in_dim))
+            self.reconstruction_enc_dec = nn.Linear(out_dim, out_dim, bias=False)
+            self.reconstruction_decoder = nn.Module()  # (PyG GraphConv(out_dim, in_dim)'s parameters)
+            self.reconstruction_decoder.lin_rel = nn.Linear(out_dim, in_dim)
+            self.reconstruction_decoder.lin_root = nn.Linear(out_dim, in_dim, bias=False)
+
+    def forward(self, task_input: NodeAnchorBasedLinkPredictionTaskInputs, gbml_config_pb_wrapper=None,
+                should_eval: bool = False, device: torch.device = torch.device("cpu")):
+        from dataclasses import replace
+        from .augmentations import get_augmented_graph
+        from .link_prediction import feature_reconstruction_loss
+        from .nn import GraphData
+        if getattr(gbml_config_pb_wrapper, "is_heterogeneous", False):
+            raise NotImplementedError("FeatureReconstruction is built for homogeneous graphs only")
+        if not self._encoder_ref:
+            raise RuntimeError("FeatureReconstruction: no encoder is bound (bind_encoder; the task spec's init_model does it)")
+        main_batch = task_input.main_batch
+        if not isinstance(main_batch.graph, GraphData):
+            raise NotImplementedError("FeatureReconstruction augments homogeneous GraphData batches (the TFRecord route), not "
+                                      f"{type(main_batch.graph).__name__}")
+        graph = get_augmented_graph(main_batch.graph.to(device), edge_drop_ratio=self.edge_drop, feat_drop_ratio=0.0,
+                                    generator=self._generator)
+        roots = main_batch.root_node_indices.to(device)
+        mask = self.reconstruction_mask.expand(int(roots.numel()), -1)
+        masked = replace(graph, x=graph.x.index_copy(0, roots, mask))  # (differentiable: the mask's gradient)
+        enc = self._encoder_ref[0](masked)
+        lin_rel = self.reconstruction_decoder.lin_rel
+        return feature_reconstruction_loss(enc, graph.x, graph, roots, self.reconstruction_enc_dec.weight, lin_rel.weight,
+                                           lin_rel.bias, self.alpha), 1
 
 
 class NodeAnchorBasedLinkPredictionTasks:
@@ -733,6 +790,10 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
                      "edge_drop_neg": 0.95}
             offered = {"neg_lambda": float(kwargs.get("neg_lambda", 0.12)), "seed": int(kwargs.get("augment_seed", 0)),
                        **{k: float(kwargs.get(k, v)) for k, v in drops.items()}}
+        if isinstance(task_cls, type) and issubclass(task_cls, FeatureReconstruction):
+            # (task.py:287-292; fr_alpha: DirectAU's `alpha` is another exponent)
+            offered = {"alpha": float(kwargs.get("fr_alpha", 3.0)), "edge_drop": float(kwargs.get("edge_drop", 0.3)),
+                       "seed": int(kwargs.get("augment_seed", 0))}
         # the offline encoder's momentum (tasks with update_offline_encoder; the reference defines the method and never calls
         # it: 1.0 reproduces that)
         self.offline_momentum = float(kwargs.get("offline_momentum", 0.99))
@@ -790,16 +851,20 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             in_dim=max(in_dim, 1), hid_dim=self.hidden_dim, out_dim=self.out_channels, num_layers=self.num_layers,
             should_l2_normalize_embedding_layer_output=self.should_l2_normalize_embedding_layer_output, **extra)
         model = LinkPredictionGNN(encoder=encoder, decoder=LinkPredictionDecoder())
-        # tasks that encode the input batch themselves (result type input_batch: GRACE, WhiteningDecorrelation, GBT, BGRL, TBGRL)
+        # tasks that encode the input batch themselves (result type input_batch: GRACE, WhiteningDecorrelation, GBT, BGRL, TBGRL,
+        # FeatureReconstruction)
         # get the model's encoder, and the heads of those that have one become part of the model, `task_heads.<task name>`: one
         # parameter list for the optimiser, one state dict.  A bootstrap task goes in whole — its keys are `task_heads.<task
-        # name>.head.*` and `.offline_encoder.*` (frozen: the optimiser skips it) — the online encoder it holds unregistered
+        # name>.head.*` and `.offline_encoder.*` (frozen: the optimiser skips it) — the online encoder it holds unregistered;
+        # FeatureReconstruction likewise, with its mask token and decoder under the reference's names
         heads = {}
         for task in self.tasks._task_to_fn_map.values():
             if hasattr(task, "bind_encoder"):
                 task.bind_encoder(encoder)
-                if task.head is not None:
-                    heads[task.task_name] = task if hasattr(task, "offline_encoder") else task.head
+                if task.whole_in_model:
+                    heads[task.task_name] = task
+                elif task.head is not None:
+                    heads[task.task_name] = task.head
         if heads:
             model.task_heads = nn.ModuleDict(heads)
         if state_dict is not None:
@@ -819,8 +884,8 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         encoder class (gnn_model_class_path; default HGT) takes the per-type feature dims, hid / out dims, num_layers,
         num_heads"""
         if "input_batch" in self.tasks.result_types:
-            raise NotImplementedError("tasks over the input batch (GRACE, WhiteningDecorrelation, GBT, BGRL, TBGRL) are built for homogeneous "
-                                      "graphs only")
+            raise NotImplementedError("tasks over the input batch (GRACE, WhiteningDecorrelation, GBT, BGRL, TBGRL, "
+                                      "FeatureReconstruction) are built for homogeneous graphs only")
         pm = cfg.preprocessed_metadata
         node_dims = {name: max(pm.nodes[c].feature_dim, 1) for c, name in cfg.condensed_node_type_map.items()}
         edge_dims = {tuple(t): pm.edges[c].feature_dim for c, t in cfg.condensed_edge_type_map.items()}
@@ -878,8 +943,8 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
             # (these tasks augment the batch's GraphData; the batch graph of the in-HBM route is not one)
             import os
             if (self._kwargs.get("data_route") or os.environ.get("GIGL_AMD_ROUTE") or "auto").lower() == "hbm":
-                raise ValueError("data_route hbm cannot serve a task over the input batch (GRACE, WhiteningDecorrelation, GBT, BGRL, TBGRL): it "
-                                 "takes the TFRecord route")
+                raise ValueError("data_route hbm cannot serve a task over the input batch (GRACE, WhiteningDecorrelation, GBT, BGRL, "
+                                 "TBGRL, FeatureReconstruction): it takes the TFRecord route")
             return None
         from .hbm import ResidentGraph, encoder_trains_over_graph_data, encoder_trains_over_hip_batches, route_of
         device = getattr(self, "_device", None)
@@ -1294,8 +1359,9 @@ class HipNodeAnchorLinkPredictionSpec(BaseTrainer, BaseInferencer):
         cfg = gbml_config_pb_wrapper
         _, world = _rank_world()
         if world > 1 and "input_batch" in self.tasks.result_types:
-            raise NotImplementedError("tasks over the input batch (GRACE, WhiteningDecorrelation, GBT, BGRL, TBGRL) train in one process: the "
-                                      "data-parallel wrapper's forward does not run their heads")
+            raise NotImplementedError("tasks over the input batch (GRACE, WhiteningDecorrelation, GBT, BGRL, TBGRL, "
+                                      "FeatureReconstruction) train in one process: the data-parallel wrapper's forward does not run "
+                                      "their heads")
         plan = self._library_train_plan(cfg)
         if plan is not None:
             try:

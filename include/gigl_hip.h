@@ -1256,6 +1256,45 @@ int32_t gigl_bootstrap_loss_backward(gigl_ctx* ctx, const float* q, const float*
  * launches nothing: dst keeps its bits. */
 int32_t gigl_ema_update(gigl_ctx* ctx, const void* table_dev, int32_t n_tensors, int64_t max_count, double mm);
 
+/* ---- the FeatureReconstruction task's decoder and scaled-cosine-error loss (csrc/reconstruct.hip; python/gigl/src/common/
+ *      models/layers/task.py:282-348, loss.py:419-441), collapsed to the b root rows.  All pointers DEVICE; the work is issued on
+ *      the ctx's stream, nothing synchronises the host, no float atomics; results are bit-reproducible run to run.  1 <= out <=
+ *      512, 1 <= in <= 8192, b <= 2^18 (GIGL_E_INVALID_ARG with a message beyond).
+ * e [n_nodes][out]: the encoder's rows of ALL nodes; rowptr [n_nodes + 1], col: the batch graph's CSR by destination; roots
+ * [b]: node ids, in any order, duplicates allowed (an id outside [0, n_nodes) is a root without edges and with a zero target);
+ * x [n_nodes][in]: the unmasked features, read in place at the roots' rows; e and x with their own row stride in floats.  w_ed
+ * [out][out] (reconstruction_enc_dec), w_rel [in][out], b_rel [in] (GraphConv.lin_rel), torch Linear layout.  Per root position i:
+ *   s_i = sum of e[col[k]] over the in-edges k of roots[i] whose source is not itself a root (CSR order within a lane group)
+ *   t_i = s_i w_ed^T,  p_i = t_i w_rel^T + b_rel,  c_i = <x_i, p_i> / (max(|x_i|, 1e-12) max(|p_i|, 1e-12))
+ *   *loss_out = (1 / b) sum_i max(1 - c_i, 0)^alpha          (b == 0: NaN, nothing else is launched)
+ * — one launch over 64-row tiles, t_i staying in LDS between the two products, after a launch that writes is_root_out [n_nodes
+ * rounded up to a multiple of 4] bytes (1: the node is a root) and root_rows_out [2][b] (where the roots' CSR rows start, then
+ * end).  What the backward reads besides those: s_out, t_out [b][out], p_out [b][in], stat_out [3][b]: the rows' |p|^2, p.x,
+ * |x|^2.  The tiles' partial sums (8 bytes a tile) come from the ctx's arena and are added in tile order.
+ * w_ed == NULL: no decoder, p_i = e_i — e [b][in] the predictions, x [b][in] the targets row for row (roots NULL), only stat_out
+ * and loss_out written. */
+int32_t gigl_feature_reconstruction_loss(gigl_ctx* ctx, const float* e, int64_t ld_e, const int32_t* rowptr, const int32_t* col,
+                                         int32_t n_nodes, const int32_t* roots, const float* x, int64_t ld_x, const float* w_ed,
+                                         const float* w_rel, const float* b_rel, int32_t b, int32_t out, int32_t in, float alpha,
+                                         uint8_t* is_root_out, int32_t* root_rows_out, float* s_out, float* t_out, float* p_out,
+                                         float* stat_out, float* loss_out);
+/* The row side of the gradient of gigl_feature_reconstruction_loss, scaled by *gout_dev (NULL: 1).  One launch over the same
+ * tiles: g_i = dL/dp_i from p (the forward's p_out, rows ld_p apart), the targets and stat (a row with |p| <= 1e-12: the
+ * norm's value clamped and no norm term, as autograd through F.normalize gives; in == 1: zeros) -> g_out [b][in], contiguous;
+ * dT = G w_rel -> dt_out [b][out]; dS = dT w_ed -> ds_out [b][out].  Then de [n_nodes][out], rows ld_de apart, every row
+ * WRITTEN once: de[j] = the sum of dS_i over the root positions i whose CSR row lists j, in ascending i — zeros for roots and
+ * for nodes no root lists.  is_root, root_rows: the forward's outputs; edges_cap >= the sum of the listed roots' in-degrees
+ * (root_rows[1] - root_rows[0], summed).  The weights' gradients are gigl_linear_weight_grad calls: (g_out, t_out) for w_rel
+ * and b_rel, (dt_out, s_out) for w_ed; GraphConv.lin_root's is zero.  From the ctx's arena: w_rel^T and w_ed^T (at most 17 MB)
+ * and the transposed lists (gigl_transposed_rows_words(max(n_nodes, b), edges_cap) + edges_cap words).
+ * w_ed == NULL: no decoder; only g_out is written, rows ld_g apart: the gradient of the predictions. */
+int32_t gigl_feature_reconstruction_loss_backward(gigl_ctx* ctx, const float* p, int64_t ld_p, const float* stat, const int32_t* roots,
+                                                  const float* x, int64_t ld_x, const float* w_ed, const float* w_rel,
+                                                  const uint8_t* is_root, const int32_t* root_rows, const int32_t* col,
+                                                  int32_t n_nodes, int64_t edges_cap, int32_t b, int32_t out, int32_t in, float alpha,
+                                                  const float* gout_dev, float* g_out, int64_t ld_g, float* dt_out, float* ds_out,
+                                                  float* de, int64_t ld_de);
+
 /* ---- rank metrics of a score matrix: MRR and hits@k of every anchor's positives among the random negatives, one wave per
  *      anchor, summed on the device.  Replaces hit_rate_at_k / mean_reciprocal_rank (python/gigl/src/common/utils/
  *      eval_metrics.py:6-73) as the trainer's validate() calls them once per anchor (node_anchor_based_link_prediction_
