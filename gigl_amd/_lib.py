@@ -88,6 +88,7 @@ SYMBOLS = [
     "gigl_correlate_chunk_rows",
     "gigl_bootstrap_loss", "gigl_bootstrap_loss_backward", "gigl_ema_update",
     "gigl_feature_reconstruction_loss", "gigl_feature_reconstruction_loss_backward",
+    "gigl_hadamard_mlp_scores", "gigl_hadamard_mlp_scores_backward",
 ]
 
 KERNEL_IDS = {
@@ -394,6 +395,9 @@ def load() -> C.CDLL:
                                              vp, vp, vp, vp],
         "gigl_feature_reconstruction_loss_backward": [vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, i64, i32, i32, i32,
                                                       C.c_float, vp, vp, i64, vp, vp, vp, i64],
+        "gigl_hadamard_mlp_scores": [vp, vp, i64, vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64],
+        "gigl_hadamard_mlp_scores_backward": [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, vp,
+                                              i64, vp, vp, vp, vp],
         "gigl_gather_mean_backward": [vp, vp, i32, vp, vp, vp, vp, i64, vp],
         "gigl_gather_mean_backward_transposed": [vp, vp, i32, vp, vp, vp, vp, i64, vp, i64, i64, i32, vp],
         "gigl_transposed_rows_build": [vp, vp, vp, vp, vp, i64, vp, i64, i64, vp],

@@ -1420,6 +1420,48 @@ class HipEngine:
         dw_ed, _ = self.linear_weight_grad(dt, saved["s"], m_dev)
         return de, (dw_ed, dw_rel, db_rel)
 
+    @staticmethod
+    def _hadamard_head(q, c, w0, b0, w1, b1):
+        """the decoder's parameters as the kernels read them: w0 [h, d] and w1 [h] contiguous fp32, the biases [h] / [1] or None"""
+        d = int(q.shape[1])
+        flat = lambda t: None if t is None else t.detach().to(torch.float32).contiguous().view(-1)
+        w0 = w0.detach().to(torch.float32).contiguous()
+        h = int(w0.shape[0])
+        w1, b0, b1 = flat(w1), flat(b0), flat(b1)
+        assert c.shape[1] == d and w0.shape == (h, d) and w1.numel() == h
+        assert (b0 is None or b0.numel() == h) and (b1 is None or b1.numel() == 1)
+        return w0, b0, w1, b1, d, h
+
+    def hadamard_mlp_scores(self, q, c, w0, b0, w1, b1, plain_last: bool = False):
+        """-> scores [Q, C]: gigl_hadamard_mlp_scores.  q [Q, d], c [C, d] (row views keep their stride); w0 [h, d], b0 [h] | None
+        (lins.0); w1 [1, h] or [h], b1 [1] | None (lins.1)"""
+        q, c = self._embedding_rows(q), self._embedding_rows(c)
+        w0, b0, w1, b1, d, h = self._hadamard_head(q, c, w0, b0, w1, b1)
+        nq, nc = int(q.shape[0]), int(c.shape[0])
+        scores = torch.empty((nq, nc), dtype=torch.float32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if nq and nc:
+            check(self._lib.gigl_hadamard_mlp_scores(self._ctx, p(q), int(q.stride(0)), p(c), int(c.stride(0)), p(w0), p(b0), p(w1),
+                                                     p(b1), nq, nc, d, h, int(bool(plain_last)), p(scores), nc), self._ctx)
+        return scores
+
+    def hadamard_mlp_scores_backward(self, q, c, w0, b0, w1, b1, plain_last: bool, d_scores):
+        """-> (dq [Q, d], dc [C, d], dw0 [h, d], db0 [h] | None, dw1 [h], db1 [1] | None): gigl_hadamard_mlp_scores_backward, from
+        the forward's inputs and d_scores [Q, C]"""
+        q, c, ds = self._embedding_rows(q), self._embedding_rows(c), self._embedding_rows(d_scores)
+        w0, b0, w1, b1, d, h = self._hadamard_head(q, c, w0, b0, w1, b1)
+        nq, nc = int(q.shape[0]), int(c.shape[0])
+        assert ds.shape == (nq, nc)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        dq, dc, dw0, dw1 = new(nq, d), new(nc, d), new(h, d), new(h)
+        db0, db1 = new(h) if b0 is not None else None, new(1) if b1 is not None else None
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(self._lib.gigl_hadamard_mlp_scores_backward(self._ctx, p(q), int(q.stride(0)), p(c), int(c.stride(0)), p(w0), p(b0),
+                                                          p(w1), p(b1), p(ds), int(ds.stride(0)), nq, nc, d, h,
+                                                          int(bool(plain_last)), p(dq), d, p(dc), d, p(dw0), p(db0), p(dw1), p(db1)),
+              self._ctx)
+        return dq, dc, dw0, db0, dw1, db1
+
     def alignment_loss(self, u: torch.Tensor, v: torch.Tensor, alpha: float):
         """-> (loss [] fp32, norm [n]): gigl_alignment_loss"""
         u, v = self._embedding_rows(u), self._embedding_rows(v)

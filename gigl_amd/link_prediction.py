@@ -4,7 +4,9 @@ Mirror of (paths relative to the reference root):
   DecoderType, LinkPredictionDecoder   python/gigl/src/common/models/layers/decoder.py:10-70
       inner_product: scores = torch.mm(q, c.T)   (:64-66)  -> gigl_linear(q, c) (same NT GEMM, exact fp32 MFMA)
       hadamard_MLP: scores = MLP(q.unsqueeze(1) * c).sum(-1)  (:67-69, PyG MLP, un-vendored: "parity unpinned")
-          -> the first layer of all pairs as one projection by query-scaled weights, the rest on gigl_linear
+          -> one hidden layer ([D, h, 1], relu, D and h <= 512): csrc/hadamard.hip, scores and gradients fused, no per-pair
+             tensor; other depths: the first layer of all pairs as one projection by query-scaled weights, the rest on
+             gigl_linear
   LinkPredictionGNN                    python/gigl/src/common/models/pyg/link_prediction.py:33-60
   RetrievalLoss                        python/gigl/src/common/models/layers/loss.py:177-360
       calculate_batch_retrieval_loss :209-277, _mask_by_query_ids :279-305, _mask_by_candidate_ids :307-331
@@ -107,10 +109,14 @@ class _DecoderMLP(nn.Module):
         if len(biases) != n:
             raise ValueError(f"Number of bias values provided ({len(biases)}) does not match the number of layers ({n})")
         self.lins = nn.ModuleList([nn.Linear(channel_list[i], channel_list[i + 1], bias=biases[i]) for i in range(n)])
-        self.act, self.plain_last = act, plain_last
+        self.act, self.act_first, self.plain_last = act, bool(act_first), plain_last
 
     def pair_scores(self, q: torch.Tensor, c: torch.Tensor, eng) -> torch.Tensor:
         from .models_hetero import _linear
+        if (len(self.lins) == 2 and self.act is torch.relu and not self.act_first and q.dim() == c.dim() == 2
+                and max(self.lins[0].weight.shape) <= HADAMARD_MAX_WIDTH):  # [D, h, 1]: the fused kernels
+            return hadamard_mlp_scores(q, c, self.lins[0].weight, self.lins[0].bias, self.lins[1].weight, self.lins[1].bias,
+                                       self.plain_last, eng)
         nq, nc = int(q.shape[0]), int(c.shape[0])
         n = len(self.lins)
         w0 = self.lins[0].weight                                     # [h1, D]
@@ -125,6 +131,38 @@ class _DecoderMLP(nn.Module):
             if self.act is not None and not (self.plain_last and i == n - 1):
                 x = self.act(x)
         return x.view(nc, nq, -1).sum(dim=-1).t().contiguous()
+
+
+HADAMARD_MAX_WIDTH = 512  # csrc/hadamard.hip serves 1 <= D, h <= 512
+
+
+class _FusedHadamardMLP(torch.autograd.Function):
+    """the hadamard_MLP decoder with one hidden layer, all Q x C pairs (csrc/hadamard.hip: the first layer on the matrix cores
+    with q * c formed on the way into LDS; bias, ReLU and lins.1 folded from the accumulators); backward = two launches that
+    rebuild the hidden tile — nothing but the inputs is saved — and fixed-order folds of their partial sums."""
+
+    @staticmethod
+    def forward(ctx, q, c, w0, b0, w1, b1, plain_last, eng):
+        ctx.eng, ctx.plain_last = eng, bool(plain_last)
+        ctx.save_for_backward(q, c, w0, b0, w1, b1)
+        return eng.hadamard_mlp_scores(q, c, w0, b0, w1, b1, plain_last)
+
+    @staticmethod
+    def backward(ctx, ds):
+        q, c, w0, b0, w1, b1 = ctx.saved_tensors
+        dq, dc, dw0, db0, dw1, db1 = ctx.eng.hadamard_mlp_scores_backward(q, c, w0, b0, w1, b1, ctx.plain_last,
+                                                                          ds.to(torch.float32))
+        return dq, dc, dw0, db0, dw1.view(w1.shape), None if db1 is None else db1.view(b1.shape), None, None
+
+
+def hadamard_mlp_scores(q, c, w0, b0, w1, b1, plain_last: bool, engine):
+    """scores [Q, C] = relu(relu((q[:, None] * c) @ w0.T + b0) @ w1.T + b1).sum(-1) — without the outer relu when plain_last —
+    of the hadamard_MLP decoder with decoder_channel_list [D, h, 1]: w0 [h, D], b0 [h] | None, w1 [1, h], b1 [1] | None; D, h
+    <= 512.  Differentiable in all six tensors; device fp32 tensors."""
+    if w0.dim() != 2 or max(w0.shape) > HADAMARD_MAX_WIDTH or w1.numel() != w0.shape[0]:
+        raise ValueError(f"hadamard_mlp_scores serves [D, h, 1] with D, h <= {HADAMARD_MAX_WIDTH}: w0 {tuple(w0.shape)}, w1 "
+                         f"{tuple(w1.shape)}")
+    return _FusedHadamardMLP.apply(q, c, w0, b0, w1, b1, bool(plain_last), engine)
 
 
 class LinkPredictionGNN(nn.Module):

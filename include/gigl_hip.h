@@ -1295,6 +1295,31 @@ int32_t gigl_feature_reconstruction_loss_backward(gigl_ctx* ctx, const float* p,
                                                   const float* gout_dev, float* g_out, int64_t ld_g, float* dt_out, float* ds_out,
                                                   float* de, int64_t ld_de);
 
+/* ---- the hadamard_MLP link decoder with one hidden layer (csrc/hadamard.hip; python/gigl/src/common/models/layers/
+ *      decoder.py:64-70 with decoder_channel_list [d, h, 1]).  All pointers DEVICE; the work is issued on the ctx's stream,
+ *      nothing synchronises the host, no float atomics; results are bit-reproducible run to run.  1 <= d, h <= 512
+ *      (GIGL_E_INVALID_ARG with a message beyond).
+ * q [n_q][d], c [n_c][d]: the query and candidate rows, each with its own row stride in floats; w0 [h][d] contiguous, b0 [h]
+ * or NULL (lins.0); w1 [h], b1 [1] or NULL (lins.1), torch Linear layout.  For every pair:
+ *   pre_j = sum_k w0[j][k] q[q][k] c[c][k] + b0[j],  s = sum_j w1[j] relu(pre_j) + b1,
+ *   scores[q][c] = s (plain_last != 0) or relu(s)                      (scores [n_q][n_c], rows ld_s floats apart)
+ * — one launch, a workgroup per (64 candidates, block of queries); the products q (.) c exist only on the way into LDS and
+ * nothing of per-pair size but scores is written.  n_q == 0 or n_c == 0: nothing is launched. */
+int32_t gigl_hadamard_mlp_scores(gigl_ctx* ctx, const float* q, int64_t ld_q, const float* c, int64_t ld_c, const float* w0,
+                                 const float* b0, const float* w1, const float* b1, int32_t n_q, int32_t n_c, int32_t d, int32_t h,
+                                 int32_t plain_last, float* scores, int64_t ld_s);
+/* The gradient of sum(d_scores * scores) of gigl_hadamard_mlp_scores (decoder.py:64-70) from the same inputs — pre is rebuilt
+ * per tile, nothing of the forward is read; relu's derivative at 0 is 0 -> dq [n_q][d], dc [n_c][d] (rows ld_dq / ld_dc
+ * apart), dw0 [h][d], dw1 [h], and where not NULL db0 [h], db1 [1]; every element WRITTEN.  Two launches over the pair tiles
+ * (the rows' gradients; the weights' with both biases') and six folds.  From the ctx's arena, with T = ceil(n_c / 64), tq the
+ * queries per workgroup (64, halved down to 4 while fewer than 512 workgroups result) and B = ceil(n_q / tq): 4 (T n_q d + B
+ * n_c d + T B (h d + 2 h + 1)) bytes of partial sums, added in index order.  No pairs: zeros. */
+int32_t gigl_hadamard_mlp_scores_backward(gigl_ctx* ctx, const float* q, int64_t ld_q, const float* c, int64_t ld_c,
+                                          const float* w0, const float* b0, const float* w1, const float* b1,
+                                          const float* d_scores, int64_t ld_ds, int32_t n_q, int32_t n_c, int32_t d, int32_t h,
+                                          int32_t plain_last, float* dq, int64_t ld_dq, float* dc, int64_t ld_dc, float* dw0,
+                                          float* db0, float* dw1, float* db1);
+
 /* ---- rank metrics of a score matrix: MRR and hits@k of every anchor's positives among the random negatives, one wave per
  *      anchor, summed on the device.  Replaces hit_rate_at_k / mean_reciprocal_rank (python/gigl/src/common/utils/
  *      eval_metrics.py:6-73) as the trainer's validate() calls them once per anchor (node_anchor_based_link_prediction_
